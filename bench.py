@@ -13,7 +13,9 @@ the engine and gathers the depth maps back to rank 0 -- scatter and gather are I
 region, double-buffered so that the transfers of step k+1 / k-1 overlap the
 compute of step k; the one-time weight broadcast from rank 0 is outside it and reported separately.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = one timed step). With
+`--dump-outputs DIR` it also writes what the last timed step returned as DIR/<name>.npy (dump_outputs). With `--full` the
+JSON line also carries (--no-kernel-timing, --no-cpu-baseline and --no-extras still switch their parts off)
   * "roofline": MFMA roofline of the dominant kernel family, from HIP events recorded on the launch
     stream around every launch of that family during the timed steps (md_model_enable_timing +
     md_model_set_timing_filter: ONLY that family is timed inside the timed region -- two event records
@@ -23,7 +25,10 @@ The JSON line also carries
   * "cpu_baseline": the CPU oracle (a port of the reference's NdArray path; the Rust reference
     cannot be built here) timed on this host's cores on ONE whole frame (BASELINE config 1: zeros
     [1,3,1536,1536], bench/inference.rs:21-48), or on a bounded sample when a frame would not fit
-    the time budget.
+    the time budget;
+  * "box" (box_probe), and for the default Depth Pro bf16 run "host_io", "configs", "accurate_mode",
+    "fp32_mode_fps" and "accuracy" (extra_measurements);
+  * for --model da3_*: "kernels" from HIP events around every launch of the eager timed steps.
 
 `--dry-run` replaces the engine by a CPU stand-in and RCCL by gloo: it exercises the launcher, the
 scatter / gather pipeline and the JSON contract without a GPU (tests/test_bench_launcher.py).
@@ -135,8 +140,8 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=1,
                     help="independent in-flight batches per GPU, each on its own HIP stream with its own workspace; the weights are shared (md_model_fork)")
     ap.add_argument("--graph", action="store_true",
-                    help="replay the launch schedule from a hipGraph and drop the per-kernel HIP events from the timed region "
-                         "(no `kernels` / `roofline` in the line: latency mode for the single-image configurations)")
+                    help="replay the launch schedule from a hipGraph (latency mode for the single-image configurations); with --full it "
+                         "also drops the per-kernel HIP events from the timed region and the per-kernel pass (no `kernels` / `roofline` in the line)")
     ap.add_argument("--attention-form", choices=["asm", "hip"], default="asm",
                     help="bf16 Depth Pro attention (577 tokens): the assembly-owned gfx950 kernel (the product) or the HIP kernel every other shape runs -- an A/B switch (md_debug_attention_asm), recorded in config.attention_form when it is not the default")
     ap.add_argument("--ln-fold", choices=["auto", "off", "neutral", "finish-launch"], default="auto",
@@ -147,7 +152,8 @@ def parse_args(argv=None):
     ap.add_argument("--persistent-fc1", choices=["on", "off", "fc1", "fc1qkv", "noqkv", "noconv"], default="on",
                     help="the GEMMs that run as persistent tile loops (md_debug_gemm_persistent; on = fc1 + QKV + proj / fc2 + the lean 3x3 convolutions): an A/B switch, same bits")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="no per-launch HIP events in the timed region (the `kernels` / `roofline` objects are then empty): measures what the events themselves cost")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: no per-launch HIP events in the timed region and no per-kernel pass (the `kernels` / `roofline` objects are then empty, "
+                         "as in a run without --full): measures what the events themselves cost")
     ap.add_argument("--cpu-baseline-budget", type=float, default=150.0, help="seconds the whole-frame CPU baseline may take (predicted from a 2-tile probe); beyond it the sampled estimate is reported")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: no depth gather to rank 0")
     ap.add_argument("--no-scatter", action="store_true", help="N > 1: every rank synthesises its own batch instead of receiving it from rank 0")
@@ -165,7 +171,19 @@ def parse_args(argv=None):
                     help="default N = 1 Depth Pro bf16 run only: skip the objects measured after the timed region (`configs`: the other BASELINE "
                          "configurations; `accurate_mode` / `fp32_mode_fps`; `accuracy` at 1536^2 against the CPU-baseline frame; `host_io`)")
     ap.add_argument("--host-io", action="store_true", help="report `host_io` (host NCHW in, host depth out through md_depth_pro_infer, as INTEGRATION.md section 2's shim calls it) for any precision / preset")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel pass and the `roofline` family timed inside the timed region, "
+                         "the `box` copy probe, `cpu_baseline`, and for the default Depth Pro bf16 run `host_io`, `configs`, `accurate_mode`, "
+                         "`fp32_mode_fps` and `accuracy` (--no-kernel-timing / --no-cpu-baseline / --no-extras still switch theirs off); for the "
+                         "Depth-Anything-v3 models the per-launch HIP events of `kernels` in eager runs. Without it a run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the arrays the timed path returned in its last step as DIR/<name>.npy (float32; "
+                         "an array beyond its share of 48 MiB is written as a fixed seeded sample of its elements, see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 _JSON_OUT = None
@@ -187,6 +205,30 @@ def emit(obj) -> None:
     out = _JSON_OUT if _JSON_OUT is not None else sys.stdout
     out.write(json.dumps(obj) + "\n")
     out.flush()
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all arrays of one --dump-outputs together
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """--dump-outputs: `arrays` (name -> tensor or None, None skipped) as DIR/<name>.npy in float32, so that two builds can be
+    compared output for output on the same seeded inputs. When all of them fit DUMP_BUDGET_BYTES they are written whole;
+    otherwise every array above 1 MiB gets an equal share of what the smaller ones leave and is written as its elements at
+    sorted flat positions drawn without replacement by numpy's default_rng([DUMP_SAMPLE_SEED, element count]): the same
+    positions on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    big = [] if sum(v.size * 4 for v in arrays.values()) <= DUMP_BUDGET_BYTES else [k for k, v in arrays.items() if v.size * 4 > 1 << 20]
+    left = DUMP_BUDGET_BYTES - sum(v.size * 4 for k, v in arrays.items() if k not in big)
+    for name, a in arrays.items():
+        if name in big:
+            k = min(a.size, left // (4 * len(big)))
+            pos = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, a.size]).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[pos]
+            print(f"note: --dump-outputs {name}: {k} of {arrays[name].size} elements of shape {list(arrays[name].shape)} (seeded sample)", file=sys.stderr)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main(argv=None) -> int:
@@ -376,10 +418,10 @@ def main(argv=None) -> int:
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    # Per-launch HIP events on EVERY kernel cost 0.7 % of a step (226 launches x 2 records; measured with --no-kernel-timing),
+    # --full: per-launch HIP events on EVERY kernel cost 0.7 % of a step (226 launches x 2 records; measured with --no-kernel-timing),
     # so the timed region times only the family that is reported against its roofline (found by one untimed, fully timed step)
     # and the per-family table comes from a separate fully timed pass after the timed region.
-    per_kernel = not args.graph and not args.no_kernel_timing
+    per_kernel = args.full and not args.graph and not args.no_kernel_timing
     dom_family = None
     if per_kernel:
         model.enable_timing(True)
@@ -412,6 +454,10 @@ def main(argv=None) -> int:
     redo_units = int(_l_asm.load().md_debug_attention_redo_units(dev.handle, 0))
     model.enable_timing(False)
     model.set_timing_filter(None)
+    last = (pending["k"] - 1) % nbuf
+    if args.dump_outputs and rank == 0:  # before any pass of --full overwrites the buffers
+        dump_outputs(args.dump_outputs, {"depth": torch.cat(gathered[last], 0) if do_gather else depths[last],
+                                         "focallength_px": focal, "fovx_deg": fovx, "fovy_rad": fovy})
     table_steps = 0
     timing = {}
     if per_kernel:
@@ -509,7 +555,7 @@ def main(argv=None) -> int:
             # FLOPs the schedule EXECUTES per frame (layers composed at commit count once); null when no per-family pass ran (--graph)
             "frame_tflops_executed": round(total_flops / B / 1e12, 3) if kernels else None,
             "frame_mfma_frac": round((total_flops / B) * (fps / world) / 1e12 / peak, 4) if kernels else None,
-            "gpu_kernel_ms_per_step": round(gpu_ms, 3),
+            "gpu_kernel_ms_per_step": round(gpu_ms, 3) if timing else None,
             "weight_broadcast_s": round(t_bcast, 4),
             "roofline": roofline,
             "roofline_attention": roofline_attention,
@@ -517,17 +563,17 @@ def main(argv=None) -> int:
                              "the ~226 launches cost 0.7 % of a step, so inside the timed region only the roofline family is timed") if table_steps else None,
             "kernels": kernels,
         }
-        if world == 1:
+        if world == 1 and args.full:
             out["box"] = box_probe(tdev)
         if args.accuracy:
             out["accuracy"] = accuracy_report(dev, cfg.precision)
         ref_frame = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], ref_frame = cpu_baseline(cfg, args.cpu_baseline_budget)
-        headline = world == 1 and args.preset == "full" and args.precision == "bf16" and args.streams == 1 and not args.graph
-        if args.host_io or (headline and not args.no_extras):
+        extras = args.full and not args.no_extras and world == 1 and args.preset == "full" and args.precision == "bf16" and args.streams == 1 and not args.graph
+        if args.host_io or extras:
             out["host_io"] = measure_host_io(model, B, S, fps)
-        if headline and not args.no_extras:
+        if extras:
             for e in extra:
                 e[0].destroy()
             extra = []
@@ -922,6 +968,8 @@ def bench_tile_parallel(args, dev, tdev, world: int, rank: int) -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, vars(last["out"]))
         ok = bool(torch.isfinite(last["out"].depth).all().item())
         emit(({
             "metric": "frames/sec Depth Pro @1536^2 bf16" if args.preset == "full" and args.precision == "bf16" else f"frames/sec Depth Pro preset={args.preset} {args.precision}",
@@ -1045,6 +1093,8 @@ def bench_dry(args, world: int, rank: int) -> int:
     if native is not None:
         ok = ok and not native["races"]
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"depth": torch.cat(gathered, 0) if (world > 1 or hb is not None) else depth})
         emit(({"metric": "frames/sec dry run (CPU stand-in, gloo)", "value": round(args.steps * B * world / elapsed, 3), "unit": "frames/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -1077,7 +1127,8 @@ def bench_da3(args, dev, tdev, world, rank) -> int:
     x = torch.randn(B, 3, S, S, generator=g).to(tdev)
     depth = torch.empty((B, S, S), dtype=torch.float32, device=tdev)
     # the dual-head variant is timed with EVERY output of DepthAnything3Inference (confidence, aux rays, camera)
-    step = (lambda: model.infer(x)) if small else (lambda: model.infer_into(x, depth))
+    last = {}
+    step = (lambda: last.update(out=model.infer(x))) if small else (lambda: model.infer_into(x, depth))
     if args.graph:
         if small:  # fixed output buffers so that the graph key repeats
             from burn_depth_amd import _lib as L
@@ -1087,7 +1138,9 @@ def bench_da3(args, dev, tdev, world, rank) -> int:
             bufs = [depth] + [torch.empty(sh, dtype=torch.float32, device=tdev) for sh in
                               ((B, S, S), (B, cfg.aux_output_dim - 1, ah, ah), (B, ah, ah), (B, 1, 9), (B, 1, 3, 4), (B, 1, 3, 3))]
             o = L.MdDa3Outputs(*(t.data_ptr() for t in bufs))
+            from burn_depth_amd.depth_anything3 import DepthAnything3Inference
             from burn_depth_amd.depth_pro import _stream_ptr
+            last["out"] = DepthAnything3Inference(*bufs)
             step = lambda: L.check(L.load().md_da3_infer_ex(model._h, C.c_void_p(x.data_ptr()), B, S, S, L.MD_MEM_DEVICE, C.byref(o),
                                                             L.MD_MEM_DEVICE, _stream_ptr(dev.ordinal)))
         model.enable_graph(True)
@@ -1097,7 +1150,7 @@ def bench_da3(args, dev, tdev, world, rank) -> int:
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    model.enable_timing(not args.graph)
+    model.enable_timing(args.full and not args.graph)  # --full: per-launch HIP events for `kernels` (none under graph replay)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -1107,6 +1160,8 @@ def bench_da3(args, dev, tdev, world, rank) -> int:
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timing = model.read_timing()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, vars(last["out"]) if small else {"depth": depth})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

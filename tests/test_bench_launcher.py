@@ -43,6 +43,72 @@ def test_single_rank_dry_run_and_contract_keys():
     assert line["n_gpus"] == 1 and line["vs_baseline"] is None
 
 
+@pytest.mark.timeout(300)
+def test_dump_outputs_writes_the_gathered_last_step(tmp_path):
+    """`--dump-outputs DIR` writes what the timed path returned in its last step: in the two-rank dry run, the depth maps rank 0
+    gathered, which are the stand-in's map of the seeded global batch."""
+    import numpy as np
+    import torch
+    p, lines = _run(["--gpus", "2", "--dry-run", "--preset", "tiny", "--steps", "2", "--warmup", "1", "--batch", "2",
+                     "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads(lines[0])["finite_output"] is True
+    full = torch.rand(4, 3, 32, 32, generator=torch.Generator().manual_seed(7))
+    depth = np.load(tmp_path / "depth.npy")
+    assert depth.dtype == np.float32 and np.array_equal(depth, (full.sum(1) + 1.0).numpy())
+
+
+def test_dump_outputs_samples_large_arrays_the_same_way_every_time(tmp_path):
+    """An output beyond the dump budget (Depth Pro's [8,1536,1536] depth) is written as a fixed seeded sample, small ones whole;
+    the files stay under 64 MB together and repeat bit for bit."""
+    import numpy as np
+    import torch
+    import bench
+    depth = torch.arange(8 * 1536 * 1536, dtype=torch.float32).view(8, 1536, 1536)
+    focal = torch.tensor([1.5, 2.5])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"depth": depth, "focallength_px": focal, "unused": None})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["depth.npy", "focallength_px.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64e6
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert np.array_equal(np.load(tmp_path / "a" / "focallength_px.npy"), focal.numpy())
+    s = np.load(tmp_path / "a" / "depth.npy")  # values = flat positions (exact in float32 below 2^24): sorted, distinct, in range
+    assert s.dtype == np.float32 and s.size > depth.numel() // 2 and np.all(np.diff(s[s < 2 ** 24]) > 0) and s[-1] <= depth.numel()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_dump_outputs_of_the_depth_pro_path_equal_its_infer(tmp_path):
+    """`bench.py --preset tiny --dump-outputs DIR` on the GPU writes the four DepthProInference arrays of the timed path, equal
+    to DepthPro.infer on the same weights (seed 0, rounded to f16) and images (bench.py's synth: seed 1234, ImageNet-normalised)."""
+    import numpy as np
+    import torch
+    from burn_depth_amd import weights as Wt
+    from burn_depth_amd.config import DepthProConfig, Precision
+    from burn_depth_amd.depth_pro import DepthPro, Device
+    p, lines = _run(["--preset", "tiny", "--batch", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads(lines[0])["finite_output"] is True
+    cfg = DepthProConfig.tiny_test()
+    cfg.precision, cfg.max_batch = Precision.BF16, 2
+    S = cfg.img_size()
+    mean = torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)
+    std = torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1)
+    x = (torch.rand(2, 3, S, S, generator=torch.Generator().manual_seed(1234)) - mean) / std
+    model = DepthPro.new(Device(0), cfg, seed=0, init_scheme=Wt.INIT_PARITY)
+    try:
+        model.round_weights_to_f16()
+        out = model.infer(x.cuda())
+        torch.cuda.synchronize()
+        for name in ("depth", "focallength_px", "fovx_deg", "fovy_rad"):
+            got = np.load(tmp_path / f"{name}.npy")
+            assert np.array_equal(got, getattr(out, name).cpu().numpy()), name
+    finally:
+        model.destroy()
+
+
 def test_the_parent_of_a_multi_rank_run_never_imports_torch():
     """`python bench.py --gpus N` must hand over to its child before anything can initialise HIP: the spawn decision sits
     above every torch / engine import, and the module itself imports neither at load time."""

@@ -16,7 +16,7 @@ bash tools/pmc_collect.sh md_attn577 "$O/pmc_asm.json" -- python3 "$ROOT/tools/a
 bash tools/pmc_collect.sh attention_kernel "$O/pmc_hip.json" -- python3 "$ROOT/tools/attn_bench.py" 296 577 16 0 0.7 hip > "$O/pmc_hip.log" 2>&1 || exit 4
 cd "$ROOT"
 for form in asm hip asm; do
-  timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --attention-form $form > "$O/bench_$form.json" 2> "$O/bench_$form.err" || exit 5
+  timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --attention-form $form > "$O/bench_$form.json" 2> "$O/bench_$form.err" || exit 5
   python3 - "$O/bench_$form.json" "$form" <<'PY' >> "$O/inmodel.txt"
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

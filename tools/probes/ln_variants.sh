@@ -8,7 +8,7 @@ for v in "" "-DMD_LN_NO_PREFETCH"; do
   echo "== EXTRA='$v'"
   timeout -k 10 300 python3 tools/gpu_diag.py --only ops 2>&1 | grep -E "layernorm" | head -8
   for p in bf16 f16x2; do
-    timeout -k 10 300 python3 bench.py --precision $p --no-extras --no-cpu-baseline --steps 6 2>/dev/null | python3 -c "
+    timeout -k 10 300 python3 bench.py --full --precision $p --no-extras --no-cpu-baseline --steps 6 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']; print('   $p:', d['value'], 'frames/s, layernorm', k['layernorm'], 'step', d['ms_per_step'])"
   done
 done

@@ -7,6 +7,6 @@ for v in "-DMD_RABL=0" "-DMD_RABL=1" "-DMD_RABL=2" "-DMD_RABL=4" "-DMD_RABL=8" "
   touch burn_depth_amd/csrc/kernels/gemm_impl.h
   make -C burn_depth_amd/csrc EXTRA="$v" -j16 > /dev/null 2>&1 || { echo "variant '$v': build failed"; continue; }
   echo "== EXTRA='$v'"
-  timeout -k 10 300 python3 bench.py --no-extras --no-cpu-baseline --steps 6 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --no-extras --no-cpu-baseline --steps 6 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']; print('   bf16:', d['value'], 'frames/s, proj', k['proj_gemm']['ms_per_step'], 'fc2', k['fc2_gemm']['ms_per_step'], 'fc1', k['fc1_gemm']['ms_per_step'], 'qkv', k['qkv_gemm']['ms_per_step'], 'step', d['ms_per_step'])"
 done

@@ -21,9 +21,9 @@ timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/prof_w
 python3 "$ROOT/tools/pmc_traffic.py" "$OUT/prof_fetch" "$OUT/prof_write" "$OUT/launch_order.json" "$OUT/traffic.json" \
   "$BATCH" bf16 full > "$OUT/traffic.txt" || exit 5
 cp "$OUT/traffic.json" "$ROOT/profiles/${ROUND:-r05}_traffic.json"
-timeout -k 10 500 python3 "$ROOT/bench.py" --steps 10 --warmup 3 --side-kernels > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+timeout -k 10 500 python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --side-kernels > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_stats" -- \
-  python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-extras > "$OUT/bench_prof.json" 2> "$OUT/prof_stats.err" || exit 2
+  python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras > "$OUT/bench_prof.json" 2> "$OUT/prof_stats.err" || exit 2
 # keep the merge-back small: drop the raw per-dispatch counter CSVs, keep stats + summaries
 find "$OUT/prof_fetch" "$OUT/prof_write" -name '*counter_collection.csv' -delete
 find "$OUT/prof_stats" -name '*kernel_trace.csv' -delete

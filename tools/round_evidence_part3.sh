@@ -9,7 +9,7 @@ cd "$ROOT"
 timeout -k 10 900 python -m pytest tests -x -q -m gpu --durations=15 > "$OUT/r04_pytest_gpu.log" 2>&1; rc=$?
 tail -3 "$OUT/r04_pytest_gpu.log"
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 600 python bench.py > "$OUT/r04_bench.json" 2> "$OUT/bench.err" || exit 3
+timeout -k 10 600 python bench.py --full > "$OUT/r04_bench.json" 2> "$OUT/bench.err" || exit 3
 python - "$OUT/r04_bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
