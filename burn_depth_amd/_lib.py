@@ -90,10 +90,12 @@ SYMBOLS = {
     "md_model_destroy": (_I, [_P]),
     "md_model_fork": (_I, [_P, C.POINTER(_P)]),
     "md_depth_pro_infer": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "md_depth_pro_infer_with_focal": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "md_depth_pro_decoder_from_features": (_I, [_P, C.POINTER(MdNchwView), _I, _I, _I, _P, _P, C.POINTER(C.c_void_p), _I, _P]),
     "md_depth_pro_head_debug": (_I, [_P, C.POINTER(MdNchwView), _I, _I, C.POINTER(MdHeadDebug), _I, _P]),
     "md_depth_pro_infer_windows": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "md_infer_from_rgb": (_I, [_P, _P, C.c_size_t, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "md_infer_from_rgb_with_focal": (_I, [_P, _P, C.c_size_t, _I, _I, _I, C.c_float, _P, _P, _P, _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),
@@ -131,6 +133,7 @@ SYMBOLS = {
     "md_op_deconv2x2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_conv2d_direct": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_fov_to_focal": (_I, [C.c_float, _I, _I, _F, _F]),
+    "md_op_focal_to_fov": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_bench_gemm": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F]),
     "md_gemm_pick_tile": (_I, [_I, _I, _I, _I]),
     "md_bench_attention": (_I, [_P, _I, _I, _I, _I, _F]),

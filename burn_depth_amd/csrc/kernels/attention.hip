@@ -530,10 +530,12 @@ __global__ __launch_bounds__(64 * QW * KS, is_split<T>::value ? (KS == 1 ? 3 : 2
 //   attention_redo_kernel        a grid of at most four workgroups per CU walks the (flagged unit, query block) items, grid-strided: with no
 //                                flag raised -- every launch on the seeded weights -- each workgroup is one load; with every flag raised it
 //                                is the HIP kernel's own launch shape.
-// `redo` holds nunits flags followed by the list (2 + nunits ints): attention_redo_ints().
-__global__ __launch_bounds__(1024) void attention_redo_scan_kernel(int* __restrict__ redo, int nunits, unsigned long long* __restrict__ stats) {
+// `redo` holds cap >= nunits flags followed by the list (2 + cap ints): attention_redo_ints(cap). The list sits behind the buffer's whole
+// capacity, not behind this launch's units: a launch over fewer sequences (a smaller batch, a call without the FOV encoder) would otherwise
+// leave its list on flag slots that a later, larger launch reads as raised.
+__global__ __launch_bounds__(1024) void attention_redo_scan_kernel(int* __restrict__ redo, int nunits, int cap, unsigned long long* __restrict__ stats) {
   __shared__ int count;
-  int* list = redo + nunits;
+  int* list = redo + cap;
   if (threadIdx.x == 0) count = 0;
   __syncthreads();
   for (int u = threadIdx.x; u < nunits; u += 1024) {
@@ -667,10 +669,12 @@ static bool attention_asm_eligible(int n_tokens, int D, int heads, int kpad, int
 }
 
 static int launch_attention_asm(const void* qk, const void* vT, void* out, int nseq, int S, int n_tokens, int heads, int D, int kpad,
-                                int* redo, hipStream_t s) {
+                                int* redo, int redo_units, hipStream_t s) {
   int ordinal = 0;
   MD_HIP(hipGetDevice(&ordinal));
   const int nunits = nseq * heads;
+  const int redo_cap = redo_units > 0 ? redo_units : nunits;  // where the compacted list sits: behind the buffer's capacity
+  if (redo_cap < nunits) MD_FAIL(MD_ERR_INVALID_ARG, "attention: redo buffer of %d units for a launch of %d", redo_cap, nunits);
   int hlog = 0;
   while ((1 << hlog) < heads) ++hlog;
   const int grid = nunits < g_asm[ordinal].cus ? nunits : g_asm[ordinal].cus;
@@ -687,16 +691,16 @@ static int launch_attention_asm(const void* qk, const void* vT, void* out, int n
   g_attn_asm_launches.fetch_add(1, std::memory_order_relaxed);
   // the units it flagged (a row sum outside [2^-64, 2^100)) run again in the running-maximum body: compacted, then four workgroups per CU
   const int qblocks = (n_tokens + 127) / 128;
-  hipLaunchKernelGGL(attention_redo_scan_kernel, dim3(1), dim3(1024), 0, s, redo, nunits, g_asm[ordinal].stats);
+  hipLaunchKernelGGL(attention_redo_scan_kernel, dim3(1), dim3(1024), 0, s, redo, nunits, redo_cap, g_asm[ordinal].stats);
   const long items = (long)nunits * qblocks, cap = 4L * g_asm[ordinal].cus;
   hipLaunchKernelGGL(attention_redo_kernel, dim3((unsigned)(items < cap ? items : cap)), dim3(256), 0, s, (const bf16_t*)qk, (const bf16_t*)vT,
-                     (bf16_t*)out, S, n_tokens, heads, D, kpad, qblocks, (const int*)(redo + nunits));
+                     (bf16_t*)out, S, n_tokens, heads, D, kpad, qblocks, (const int*)(redo + redo_cap));
   MD_HIP(hipGetLastError());
   return MD_OK;
 }
 
 int launch_attention(const void* qk, const void* vT, void* out, int nseq, int S, int n_tokens, int heads, int D,
-                     int kpad, int prec, hipStream_t s, float out_fp8_inv, long v_plane, int* redo) {
+                     int kpad, int prec, hipStream_t s, float out_fp8_inv, long v_plane, int* redo, int redo_units) {
   if (prec != MD_PREC_BF16 && prec != MD_PREC_F16 && prec != MD_PREC_F16X2) MD_FAIL(MD_ERR_UNSUPPORTED, "fused attention takes bf16, f16 or split-half operands (precision %d)", prec);
   if (D != heads * 64) MD_FAIL(MD_ERR_UNSUPPORTED, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
   if (kpad % 64 != 0 || kpad < (n_tokens + 63) / 64 * 64)
@@ -706,7 +710,7 @@ int launch_attention(const void* qk, const void* vT, void* out, int nseq, int S,
   const long blocks = (long)qblocks * heads * nseq;
   if (nseq <= 0 || blocks > 0x7fffffffL) MD_FAIL(MD_ERR_UNSUPPORTED, "attention: %d sequences", nseq);
   if (attention_asm_eligible(n_tokens, D, heads, kpad, prec, out_fp8_inv, redo))
-    return launch_attention_asm(qk, vT, out, nseq, S, n_tokens, heads, D, kpad, redo, s);
+    return launch_attention_asm(qk, vT, out, nseq, S, n_tokens, heads, D, kpad, redo, redo_units, s);
   const dim3 grid((unsigned)blocks), block(256);
   // small launches over long sequences: 64 queries x two key groups per workgroup (the kernel's header)
   const bool small = n_tokens >= kKeySplitMin && blocks <= kKeySplitBlocks && out_fp8_inv <= 0.f && key_split_enabled() && g_attn_small_ok != 0;

@@ -152,6 +152,9 @@ int launch_pose_to_camera(const float* pose, int B, int H, int W, float* extrins
 // fov degrees -> focal length / fovy / ratio (mod.rs:330-346, 370-414). All [B] f32.
 int launch_fov_post(const float* fov_deg, int B, int H, int W, float* focal_px, float* fovy_rad, float* ratio,
                     hipStream_t s);
+// the caller's focal length f_px[B] (device memory, read at run time) -> focal_px = f_px, fovx / fovy / ratio (the known-focal tail).
+int launch_focal_post(const float* f_px, int B, int H, int W, float* focal_px, float* fovx_deg, float* fovy_rad, float* ratio,
+                      hipStream_t s);
 // inv = canonical * ratio[b]; post 1: depth = 1/clamp(inv); post 0: keep inv (then resize).
 int launch_depth_post(const float* canonical, const float* ratio, int B, long hw, float* out, int post, hipStream_t s);
 
@@ -175,11 +178,14 @@ inline float attn_qscale(int prec) { return prec == MD_PREC_F32 ? 1.0f : kAttnQS
 // out_fp8_inv > 0 (bf16 only): the output rows are OCP e4m3 bytes (value * out_fp8_inv, saturating).
 // prec = MD_PREC_F16X2: split-half operands -- qk rows [q_hi | q_lo | k_hi | k_lo] (4D wide), the lo plane of V^T `v_plane`
 // elements behind its hi plane, out rows [hi: D | lo: D]; scores on three MFMA terms, P.V on two or three (attention.hip).
-// redo: attention_redo_ints(nseq * heads) zero-initialised ints owned by the caller's context (one buffer per stream that may run attention
-// at a time: the flags, then the compacted list of raised ones), or null. With it, bf16 launches of exactly 577 tokens take the assembly-owned kernel (attn577_gfx950.s) once attention_asm_prepare()
-// has loaded its code object on the device; the flags it raises are consumed and cleared inside the same call.
+// redo: attention_redo_ints(redo_units) zero-initialised ints owned by the caller's context (one buffer per stream that may run attention
+// at a time: redo_units flags, then the compacted list of raised ones at redo + redo_units), or null. redo_units is the buffer's capacity in
+// (sequence, head) units (0: exactly nseq * heads); it must not change between the launches that share the buffer, so that no launch's
+// list lands on the flags of a later, larger launch. With it, bf16 launches of exactly 577 tokens take the assembly-owned kernel (attn577_gfx950.s)
+// once attention_asm_prepare() has loaded its code object on the device; the flags it raises are consumed and cleared inside the same call.
 int launch_attention(const void* qk, const void* vT, void* out, int nseq, int S, int n_tokens, int heads, int D,
-                     int kpad, int prec, hipStream_t s, float out_fp8_inv = 0.f, long v_plane = 0, int* redo = nullptr);
+                     int kpad, int prec, hipStream_t s, float out_fp8_inv = 0.f, long v_plane = 0, int* redo = nullptr,
+                     int redo_units = 0);
 // Loads the embedded code object on the CURRENT device (idempotent; not capturable -- call it when a context is created).
 int attention_asm_prepare();
 // Process-wide: may launch_attention take the assembly kernel? Default 1; returns the previous value (A/B runs, the bench).

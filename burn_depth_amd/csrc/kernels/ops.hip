@@ -1250,6 +1250,25 @@ int launch_pose_to_camera(const float* pose, int B, int H, int W, float* extrins
 // ------------------------------------------------------------------------------------------------
 // a12/a13 scalar tail (depth_pro/mod.rs:330-346, 370-414)
 // ------------------------------------------------------------------------------------------------
+// `fovy_from_fovx_rad` (mod.rs:370-414): 2 atan((H/W) tan(fovx/2)) through the reference's range-reduced rational approximation
+__host__ __device__ inline float fovy_from_fovx_rad_math(float fovx_rad, int H, int W) {
+#pragma clang fp contract(off)
+  const float k = (float)0.273;
+  const float pi4 = (float)0.78539816339744830962, pi2 = (float)1.57079632679489661923;
+  const float aspect = (float)((double)H / (double)W);
+  const float t = tanf(fovx_rad * 0.5f) * aspect;
+  const float sgn = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
+  const float ax = fabsf(t);
+  const float use_inv = ax > 1.0f ? 1.f : 0.f;
+  const float inv = 1.0f / ax;
+  const float xr = ax * (1.0f - use_inv) + (use_inv != 0.f ? inv * use_inv : 0.f);
+  const float inner = (1.0f - xr) * k + pi4;
+  const float atan_reduced = xr * inner;
+  const float delta = pi2 - atan_reduced * 2.0f;
+  const float atan_ax = atan_reduced + delta * use_inv;
+  return atan_ax * sgn * 2.0f;
+}
+
 __host__ __device__ inline void fov_scalar_math(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad,
                                                 float* ratio) {
 #pragma clang fp contract(off)
@@ -1258,22 +1277,18 @@ __host__ __device__ inline void fov_scalar_math(float fovx_deg, int H, int W, fl
   const float focal = ((float)W * 0.5f) / denom;
   if (focal_px) *focal_px = focal;
   if (ratio) *ratio = (float)W / focal;
-  if (fovy_rad) {
-    const float k = (float)0.273;
-    const float pi4 = (float)0.78539816339744830962, pi2 = (float)1.57079632679489661923;
-    const float aspect = (float)((double)H / (double)W);
-    const float t = tanf(fovx_rad * 0.5f) * aspect;
-    const float sgn = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
-    const float ax = fabsf(t);
-    const float use_inv = ax > 1.0f ? 1.f : 0.f;
-    const float inv = 1.0f / ax;
-    const float xr = ax * (1.0f - use_inv) + (use_inv != 0.f ? inv * use_inv : 0.f);
-    const float inner = (1.0f - xr) * k + pi4;
-    const float atan_reduced = xr * inner;
-    const float delta = pi2 - atan_reduced * 2.0f;
-    const float atan_ax = atan_reduced + delta * use_inv;
-    *fovy_rad = atan_ax * sgn * 2.0f;
-  }
+  if (fovy_rad) *fovy_rad = fovy_from_fovx_rad_math(fovx_rad, H, W);
+}
+
+// The tail of a call with the caller's focal length f (pixels of the W-wide input): fovx = 2 atan(W / 2f) in degrees, fovy from
+// that fovx like the predicting path, ratio = W / f with the same division as fov_scalar_math -- so an f equal to the predicted
+// focal length gives the predicting path's ratio, and its depth, bit for bit.
+__host__ __device__ inline void focal_scalar_math(float f_px, int H, int W, float* fovx_deg, float* fovy_rad, float* ratio) {
+#pragma clang fp contract(off)
+  const float fovx_d = 2.0f * atanf(((float)W * 0.5f) / f_px) * (float)(180.0 / 3.14159265358979323846);
+  if (fovx_deg) *fovx_deg = fovx_d;
+  if (ratio) *ratio = (float)W / f_px;
+  if (fovy_rad) *fovy_rad = fovy_from_fovx_rad_math(fovx_d * (float)(3.14159265358979323846 / 180.0), H, W);
 }
 
 __global__ void fov_post_kernel(const float* __restrict__ fov_deg, int B, int H, int W, float* focal_px,
@@ -1290,8 +1305,30 @@ int launch_fov_post(const float* fov_deg, int B, int H, int W, float* focal_px, 
   return MD_OK;
 }
 
+// reads f_px on the device at run time: a captured graph replays with whatever the caller's buffer then holds
+__global__ void focal_post_kernel(const float* __restrict__ f_px, int B, int H, int W, float* __restrict__ focal_px,
+                                  float* __restrict__ fovx_deg, float* __restrict__ fovy_rad, float* __restrict__ ratio) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float f = f_px[b];
+  focal_px[b] = f;
+  focal_scalar_math(f, H, W, fovx_deg + b, fovy_rad + b, ratio + b);
+}
+
+int launch_focal_post(const float* f_px, int B, int H, int W, float* focal_px, float* fovx_deg, float* fovy_rad, float* ratio,
+                      hipStream_t s) {
+  if (!f_px || !focal_px || !fovx_deg || !fovy_rad || !ratio) MD_FAIL(MD_ERR_INVALID_ARG, "focal_post: null buffer");
+  hipLaunchKernelGGL(focal_post_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, f_px, B, H, W, focal_px, fovx_deg, fovy_rad, ratio);
+  MD_HIP(hipGetLastError());
+  return MD_OK;
+}
+
 void fov_scalar_host(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad) {
   fov_scalar_math(fovx_deg, H, W, focal_px, fovy_rad, nullptr);
+}
+
+void focal_scalar_host(float f_px, int H, int W, float* fovx_deg, float* fovy_rad) {
+  focal_scalar_math(f_px, H, W, fovx_deg, fovy_rad, nullptr);
 }
 
 __global__ void depth_post_kernel(const float* __restrict__ canonical, const float* __restrict__ ratio, int B, long hw,

@@ -229,6 +229,14 @@ int md_depth_pro_infer(md_model_t m, const float* nchw, int B, int H, int W, int
                      nullptr, 0);
 }
 
+int md_depth_pro_infer_with_focal(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const float* f_px, float* depth,
+                                  float* focallength_px, float* fovx_deg, float* fovy_rad, int out_kind, void* stream) {
+  if (!nchw) MD_FAIL(MD_ERR_INVALID_ARG, "input pointer is null");
+  if (m && m->kind != 0) MD_FAIL(MD_ERR_INVALID_ARG, "not a Depth Pro model");
+  return model_infer(m, nchw, B, H, W, in_kind, depth, focallength_px, fovx_deg, fovy_rad, out_kind, (hipStream_t)stream,
+                     nullptr, 0, f_px, in_kind);
+}
+
 int md_depth_pro_decoder_from_features(md_model_t m, const md_nchw_view* features, int levels, int B, int in_kind,
                                        float* out_features, float* out_lowres, float* const* out_fusions, int out_kind,
                                        void* stream) {
@@ -264,6 +272,17 @@ int md_infer_from_rgb(md_model_t m, const uint8_t* rgb, size_t rgb_len, int w, i
   if (m && m->kind != 0) MD_FAIL(MD_ERR_INVALID_ARG, "not a Depth Pro model");
   return model_infer(m, nullptr, 1, h, w, in_kind, depth, focallength_px, nullptr, fovy_rad, out_kind, (hipStream_t)stream,
                      rgb, rgb_len);
+}
+
+int md_infer_from_rgb_with_focal(md_model_t m, const uint8_t* rgb, size_t rgb_len, int w, int h, int in_kind, float f_px,
+                                 float* depth, float* focallength_px, float* fovy_rad, int out_kind, void* stream) {
+  if (!rgb) MD_FAIL(MD_ERR_INVALID_ARG, "rgb pointer is null");
+  if (w <= 0 || h <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid image size %dx%d", w, h);
+  const size_t expected = (size_t)w * (size_t)h * 3;
+  if (rgb_len != expected) MD_FAIL(MD_ERR_SHAPE, "expected %zu RGB bytes for %dx%d, got %zu", expected, w, h, rgb_len);
+  if (m && m->kind != 0) MD_FAIL(MD_ERR_INVALID_ARG, "not a Depth Pro model");
+  return model_infer(m, nullptr, 1, h, w, in_kind, depth, focallength_px, nullptr, fovy_rad, out_kind, (hipStream_t)stream,
+                     rgb, rgb_len, &f_px, MD_MEM_HOST);
 }
 
 int md_model_enable_graph(md_model_t m, int enable) {
@@ -696,6 +715,13 @@ int md_op_conv2d_direct(md_device_t dev, const float* x_dev, const float* w_dev,
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad) {
   if (H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid image size");
   fov_scalar_host(fovx_deg, H, W, focal_px, fovy_rad);
+  return MD_OK;
+}
+
+int md_op_focal_to_fov(float f_px, int H, int W, float* fovx_deg, float* fovy_rad) {
+  if (H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid image size");
+  if (!std::isfinite(f_px) || !(f_px > 0.f)) MD_FAIL(MD_ERR_INVALID_ARG, "f_px = %g: a focal length must be finite and > 0", (double)f_px);
+  focal_scalar_host(f_px, H, W, fovx_deg, fovy_rad);
   return MD_OK;
 }
 

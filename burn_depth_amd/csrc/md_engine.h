@@ -177,8 +177,10 @@ int model_round_weights_f16(md_model_t m);
 int model_destroy(md_model_t m);
 int model_fork(md_model_t src, md_model_t* out);
 inline md_model_s* model_root(md_model_s* m) { return m->parent ? m->parent : m; }
+// f_px non-null: the caller's focal lengths [B] (memory kind f_kind) replace the FOV network's (md_depth_pro_infer_with_focal)
 int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, float* focal,
-                float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len);
+                float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len,
+                const float* f_px = nullptr, int f_kind = 0);
 // DepthPro::decoder_from_features / head_debug (depth_pro/mod.rs:262-307): the decoder / the depth head alone on caller tensors
 int model_decoder_from_features(md_model_t m, const md_nchw_view* features, int levels, int B, int in_kind, float* out_features,
                                 float* out_lowres, float* const* out_fusions, int out_kind, hipStream_t stream);
@@ -211,6 +213,8 @@ int pack_weight(const float* src, const PackEntry& e, int prec, hipStream_t s);
 // number of values of w[0..n) that are not exactly representable as an IEEE half (synchronises the stream)
 int count_inexact_f16(const float* w, long n, hipStream_t s, unsigned* out);
 void fov_scalar_host(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad);
+// the known-focal tail on host scalars: f_px -> fovx_deg, fovy_rad (what focal_post computes on the device)
+void focal_scalar_host(float f_px, int H, int W, float* fovx_deg, float* fovy_rad);
 
 // ---- Depth-Anything-v3 (md_da3.hip) ----
 struct Da3Cfg {

@@ -299,6 +299,7 @@ struct md_model_s::Buffers {
   void* vT = nullptr;         // [nseq][heads][64][kpad] T
   void* ao = nullptr;         // [nseq*SS, D] T
   int* attn_redo = nullptr;   // [attention_redo_ints(nseq*heads)] flags + compacted list of the assembly attention kernel (raised = that unit re-runs in the safe body)
+  int attn_redo_units = 0;    // its capacity in (sequence, head) units: every launch puts its list behind all of them
   void* hbuf = nullptr;       // [nseq*SS, 4D] T
   float* scores = nullptr;    // fp32 attention only
   void* hook[2] = {nullptr, nullptr};  // [n0*SS, D] T
@@ -323,6 +324,10 @@ struct md_model_s::Buffers {
   size_t rgb_cap = 0, xraw_cap = 0;
   void *pin_in = nullptr, *pin_out = nullptr;
   size_t pin_in_cap = 0, pin_out_cap = 0;
+  // the caller's focal lengths of a known-focal call from host memory: device copy [B] and its own pinned bounce buffer
+  float* fpx = nullptr;
+  void* pin_fpx = nullptr;
+  size_t fpx_cap = 0, pin_fpx_cap = 0;
   // fov
   float *fovproj = nullptr, *fv0 = nullptr, *fv1 = nullptr, *fv2 = nullptr, *fv3 = nullptr, *fvr = nullptr;
   float *fov_deg = nullptr, *focal = nullptr, *fovy = nullptr, *ratio = nullptr;
@@ -380,6 +385,7 @@ static int plan_workspace(md_model_s* m, bool dry, size_t* total_out) {
   m->vt_plane = m->xm == 2 ? (size_t)nseq * c.pv.heads * 64 * m->kpad : 0;
   MD_TAKE(ao, void*, rows * D * esz);
   MD_TAKE(attn_redo, int*, (size_t)attention_redo_ints(nseq * c.pv.heads) * 4);  // the assembly attention kernel's per-(sequence, head) flags (zero = the arena's memset)
+  if (!dry) b->attn_redo_units = nseq * c.pv.heads;
   MD_TAKE(hbuf, void*, rows * 4 * D * esz);
   if (m->prec == MD_PREC_F32) MD_TAKE(scores, float*, (size_t)nseq * c.pv.heads * SS * m->kpad * 4);
   MD_TAKE(hook[0], void*, ((size_t)n0 * SS + 64) * D * esz);
@@ -682,6 +688,8 @@ int model_destroy(md_model_t m) {
     if (m->buf->depth_stage) (void)hipFree(m->buf->depth_stage);
     if (m->buf->pin_in) (void)hipHostFree(m->buf->pin_in);
     if (m->buf->pin_out) (void)hipHostFree(m->buf->pin_out);
+    if (m->buf->fpx) (void)hipFree(m->buf->fpx);
+    if (m->buf->pin_fpx) (void)hipHostFree(m->buf->pin_fpx);
     delete m->buf;
   }
   delete m;
@@ -1095,7 +1103,7 @@ static int run_vit(Run& r, int nseq_p, int nseq, int s_lo, int s_hi) {
     if (m->prec != MD_PREC_F32) {
       r.begin("attention");
       MD_TRY(launch_attention(trow(b->qk, 2 * D), vT_w, trow(b->ao, D), WS, SS, NT, heads, D, m->kpad, m->prec, r.st, 0.f, (long)m->vt_plane,
-                              b->attn_redo));
+                              b->attn_redo, b->attn_redo_units));
       r.end();
     } else {
       // fp32: scores = q k^T (batched GEMM) -> row softmax -> P V^T^T (batched GEMM)
@@ -1648,7 +1656,7 @@ static int run_fov(Run& r, const md_model_s::IndexSet& ix) {
 
 static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, float* focal,
                              float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len,
-                             const ShardPlan* sp = nullptr);
+                             const float* f_px, int f_kind, const ShardPlan* sp = nullptr);
 
 // Grow-only staging: (re)allocates only when `need` exceeds the capacity. hipFree is a device-wide synchronisation and
 // hipMalloc takes the allocator lock, so a caller that feeds host pointers or a fixed non-native size (the reference's
@@ -1676,27 +1684,34 @@ static int ensure_pinned(md_model_s* m, void** p, size_t* cap, size_t need) {
 }
 // pageable caller memory -> pinned bounce buffer -> device, asynchronously on `st` (the bounce buffer is reused by the next
 // call, which first waits for this stream's work: one in-flight infer per model, see the threading rule in mi_depth.h)
-static int stage_host_to_device(md_model_s* m, void* dst_dev, const void* src_host, size_t bytes, hipStream_t st) {
+// (the input's bounce buffer by default; the caller's focal lengths travel through one of their own)
+static int stage_host_to_device(md_model_s* m, void* dst_dev, const void* src_host, size_t bytes, hipStream_t st,
+                                void** pin = nullptr, size_t* pin_cap = nullptr) {
   md_model_s::Buffers* b = m->buf;
-  if (b->pin_in_cap < bytes) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
-  MD_TRY(ensure_pinned(m, &b->pin_in, &b->pin_in_cap, bytes));
+  if (!pin) { pin = &b->pin_in; pin_cap = &b->pin_in_cap; }
+  if (*pin_cap < bytes) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
+  MD_TRY(ensure_pinned(m, pin, pin_cap, bytes));
   MD_HIP(hipStreamSynchronize(st));  // the previous call's copy out of the bounce buffer has finished
-  memcpy(b->pin_in, src_host, bytes);
-  MD_HIP(hipMemcpyAsync(dst_dev, b->pin_in, bytes, hipMemcpyHostToDevice, st));
+  memcpy(*pin, src_host, bytes);
+  MD_HIP(hipMemcpyAsync(dst_dev, *pin, bytes, hipMemcpyHostToDevice, st));
   return MD_OK;
 }
 
 int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, float* focal,
-                float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len) {
+                float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len, const float* f_px,
+                int f_kind) {
   if (!m) MD_FAIL(MD_ERR_INVALID_ARG, "model is null");
-  auto body = [&]() { return model_infer_eager(m, nchw, B, H, W, in_kind, depth, focal, fovx, fovy, out_kind, stream, rgb, rgb_len); };
+  auto body = [&]() {
+    return model_infer_eager(m, nchw, B, H, W, in_kind, depth, focal, fovx, fovy, out_kind, stream, rgb, rgb_len, f_px, f_kind);
+  };
   if (!m->graph_enabled) return body();
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
   const bool eligible = nchw && !rgb && in_kind == MD_MEM_DEVICE && out_kind == MD_MEM_DEVICE && model_root(m)->committed && B > 0 &&
-                        B <= m->cfg.max_batch && H == m->S && W == m->S;
+                        B <= m->cfg.max_batch && H == m->S && W == m->S && (!f_px || f_kind == MD_MEM_DEVICE);
   // the commit generation of the weights is part of the key: a graph bakes by-value launch parameters (the head's output
-  // bias, the split-half term count), and a fork's graphs cannot be reached from the root's commit
+  // bias, the split-half term count), and a fork's graphs cannot be reached from the root's commit. The focal-length pointer is
+  // too: a graph with the FOV network never replays a known-focal call, nor the reverse (its values are read at run time).
   const unsigned gen = model_root(m)->commit_gen;
   if (m->graphs_gen != gen) {  // a fork's graphs of an older commit can never be replayed again (the root clears its own in model_commit)
     for (auto& kv : m->graphs)
@@ -1705,7 +1720,7 @@ int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kin
     m->graphs_gen = gen;
   }
   const std::vector<uintptr_t> key = {(uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw, (uintptr_t)depth,
-                                      (uintptr_t)focal, (uintptr_t)fovx, (uintptr_t)fovy, (uintptr_t)gen};
+                                      (uintptr_t)focal, (uintptr_t)fovx, (uintptr_t)fovy, (uintptr_t)gen, (uintptr_t)f_px};
   return run_with_graph(m, st, key, eligible, body);
 }
 
@@ -1730,22 +1745,36 @@ int model_infer_sharded(md_model_t m, const float* nchw, int B, int H, int W, in
   if (sp.parts < 1 || sp.part < -1 || sp.part >= sp.parts || sp.root < 0 || sp.root >= sp.parts)
     MD_FAIL(MD_ERR_INVALID_ARG, "tile-parallel plan: part %d of %d, root %d", sp.part, sp.parts, sp.root);
   if (sp.part >= 0 && sp.parts > 1 && !sp.exchange) MD_FAIL(MD_ERR_INVALID_ARG, "tile-parallel plan: no exchange function");
-  return model_infer_eager(m, nchw, B, H, W, in_kind, depth, focal, fovx, fovy, out_kind, stream, nullptr, 0, &sp);
+  return model_infer_eager(m, nchw, B, H, W, in_kind, depth, focal, fovx, fovy, out_kind, stream, nullptr, 0, nullptr, 0, &sp);
 }
 
+// f_px (memory kind f_kind) non-null: the caller's focal lengths [B] in pixels of the W-wide input. The ViT stage then leaves
+// out the FOV encoder's row group, the FOV network does not run, and focal_post turns f_px into the tail's ratio / fovx / fovy.
 static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, float* focal,
                              float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len,
-                             const ShardPlan* sp) {
+                             const float* f_px, int f_kind, const ShardPlan* sp) {
   if (!m) MD_FAIL(MD_ERR_INVALID_ARG, "model is null");
   if (!model_root(m)->committed) MD_FAIL(MD_ERR_INVALID_ARG, "weights were modified; call md_model_commit_weights first");
   if (!nchw && !rgb) MD_FAIL(MD_ERR_INVALID_ARG, "input pointer is null");
   if (B <= 0 || H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid input shape [%d,3,%d,%d]", B, H, W);
   if (B > m->cfg.max_batch) MD_FAIL(MD_ERR_SHAPE, "batch %d exceeds max_batch %d", B, m->cfg.max_batch);
-  if (!m->cfg.use_fov_head) MD_FAIL(MD_ERR_NO_FOV, "FOV head required for focal length");  // mod.rs:329
+  const bool known_focal = f_px != nullptr;
+  if (known_focal && sp) MD_FAIL(MD_ERR_INVALID_ARG, "the tile-parallel mode takes no focal length");
+  if (!known_focal && !m->cfg.use_fov_head) MD_FAIL(MD_ERR_NO_FOV, "FOV head required for focal length");  // mod.rs:329
+  if (known_focal && f_kind == MD_MEM_HOST)
+    for (int i = 0; i < B; ++i)
+      if (!std::isfinite(f_px[i]) || !(f_px[i] > 0.f)) MD_FAIL(MD_ERR_INVALID_ARG, "f_px[%d] = %g: a focal length must be finite and > 0", i, (double)f_px[i]);
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
   md_model_s::Buffers* b = m->buf;
   Run r{m, st, B};
+  const float* fpx_dev = f_px;
+  if (known_focal && f_kind == MD_MEM_HOST) {  // grow-only device copy through its own pinned bounce buffer (before the input's)
+    if (b->fpx_cap < (size_t)B * 4) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
+    MD_TRY(ensure_device(m, (void**)&b->fpx, &b->fpx_cap, (size_t)B * 4));
+    MD_TRY(stage_host_to_device(m, b->fpx, f_px, (size_t)B * 4, st, &b->pin_fpx, &b->pin_fpx_cap));
+    fpx_dev = b->fpx;
+  }
   const int S = m->S;
   const size_t in_elems = (size_t)B * 3 * H * W;
   const bool resize_needed = H != S || W != S;  // mod.rs:317
@@ -1806,7 +1835,8 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
   hipEvent_t* ev_w = ev_set.e;
   const bool time_windows = sp && sp->part < 0 && (sp->window_ms || sp->tail_ms) && sp->parts <= 64;
   if (!sp) {
-    MD_TRY(run_vit(r, nseq_p, nseq, 0, nseq));
+    // known focal length: the FOV encoder's row group (the last B sequences) is left out
+    MD_TRY(run_vit(r, nseq_p, nseq, 0, known_focal ? nseq_p + B : nseq));
   } else {
     auto lo_of = [&](int p) { return (int)((long)nseq * p / sp->parts); };
     if (sp->part < 0) {  // every window in turn on this device: the same launches a rank of each part would issue
@@ -1844,11 +1874,25 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
   };
   MD_TRY(run_encoder_tail(r, ix));
   MD_TRY(run_decoder_head(r));
-  MD_TRY(run_fov(r, ix));
   // ---- tail (mod.rs:330-363) ----
-  r.begin("fov_post");
-  MD_TRY(launch_fov_post(b->fov_deg, B, H, W, b->focal, b->fovy, b->ratio, st));
-  r.end();
+  if (!known_focal) {
+    MD_TRY(run_fov(r, ix));
+    r.begin("fov_post");
+    MD_TRY(launch_fov_post(b->fov_deg, B, H, W, b->focal, b->fovy, b->ratio, st));
+    r.end();
+  } else {
+    // no FOV prediction in this call: an earlier call's fov_deg tap must not read as this one's (the first eager call of a replay
+    // key erases it; a capture never frees)
+    auto tp = m->taps.find("fov_deg");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (tp != m->taps.end() && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+      if (tp->second.dev) MD_HIP(hipFree(tp->second.dev));
+      m->taps.erase(tp);
+    }
+    r.begin("focal_post");
+    MD_TRY(launch_focal_post(fpx_dev, B, H, W, b->focal, b->fov_deg, b->fovy, b->ratio, st));
+    r.end();
+  }
   const size_t out_elems = (size_t)B * H * W;
   float* depth_dev = nullptr;
   if (depth) {

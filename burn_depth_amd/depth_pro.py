@@ -7,6 +7,8 @@ reference repository):
 * ``DepthPro.load(device, path)``             -- depth_pro/mod.rs:193-198
 * ``DepthPro.load_with_config``               -- depth_pro/mod.rs:200-208
 * ``DepthPro.infer(x) -> DepthProInference``  -- depth_pro/mod.rs:312-364
+* ``DepthPro.infer(x, f_px)``                 -- the same with the caller's focal length (ml-depth-pro's ``infer(x, f_px)``):
+                                                 no FOV network, md_depth_pro_infer_with_focal
 * ``img_size`` / ``interpolation_method``     -- depth_pro/mod.rs:296,308
 * ``decoder_from_features`` / ``head_debug``  -- depth_pro/mod.rs:262-267, 289-307
 * debug taps                                  -- encoder.rs:106-123, mod.rs:135-142,285-287
@@ -83,6 +85,27 @@ def _c_cfg(cfg: DepthProConfig) -> Tuple[_lib.MdDepthProCfg, list]:
 
 def _stream_ptr(device_ordinal: int) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device_ordinal).cuda_stream)
+
+
+def _focal_arg(f_px, B: int, on_device: bool, device_ordinal: int):
+    """The caller's focal lengths as the fp32 [B] buffer md_depth_pro_infer_with_focal reads, in the memory kind of the image:
+    a float is broadcast to B, a sequence or a [B] tensor gives one value per image. A CUDA fp32 contiguous [B] tensor on this GPU
+    is passed as it is (a replayed graph reads whatever it then holds). Returns (pointer, keep-alive)."""
+    if isinstance(f_px, torch.Tensor):
+        t = f_px.detach().reshape(-1)
+        if t.numel() == 1 and B != 1:
+            t = t.expand(B)
+    elif isinstance(f_px, (int, float, np.floating, np.integer)):
+        t = torch.full((B,), float(f_px), dtype=torch.float32)
+    else:
+        t = torch.tensor([float(v) for v in f_px], dtype=torch.float32)
+    if t.numel() != B:
+        raise _lib.MdError(_lib.MD_ERR_SHAPE, f"f_px holds {t.numel()} focal lengths for a batch of {B}")
+    if on_device:
+        t = t.to(device=torch.device("cuda", device_ordinal), dtype=torch.float32).contiguous()
+    else:
+        t = t.to(device="cpu", dtype=torch.float32).contiguous()
+    return C.c_void_p(t.data_ptr()), t
 
 
 class DepthPro:
@@ -208,8 +231,10 @@ class DepthPro:
         return int(p.value), int(n.value)
 
     # ---- inference ------------------------------------------------------------------------
-    def infer(self, x: torch.Tensor) -> DepthProInference:
-        """x: [B,3,H,W] fp32, ImageNet-normalised (any H, W), on the GPU or the host."""
+    def infer(self, x: torch.Tensor, f_px=None) -> DepthProInference:
+        """x: [B,3,H,W] fp32, ImageNet-normalised (any H, W), on the GPU or the host.
+        f_px: the caller's focal length in pixels of the W-wide input -- a float (every image), a sequence or a [B] tensor --
+        or None to predict it with the FOV network. With f_px the FOV network does not run and focallength_px is f_px."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         x = x.contiguous().to(torch.float32)
@@ -220,20 +245,26 @@ class DepthPro:
         fovx = torch.empty((B,), dtype=torch.float32, device=dev)
         fovy = torch.empty((B,), dtype=torch.float32, device=dev)
         in_kind = _lib.MD_MEM_DEVICE if x.is_cuda else _lib.MD_MEM_HOST
-        _lib.check(self._lib.md_depth_pro_infer(self._h, C.c_void_p(x.data_ptr()), B, H, W, in_kind,
-                                                C.c_void_p(depth.data_ptr()), C.c_void_p(focal.data_ptr()),
-                                                C.c_void_p(fovx.data_ptr()), C.c_void_p(fovy.data_ptr()),
-                                                _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        self._infer_call(x, B, H, W, in_kind, f_px, depth, focal, fovx, fovy)
         return DepthProInference(depth, focal, fovx, fovy)
 
     def infer_into(self, x: torch.Tensor, depth: torch.Tensor, focal: torch.Tensor, fovx: torch.Tensor,
-                   fovy: torch.Tensor) -> None:
-        """Allocation-free variant used by the benchmark loop (all tensors on this GPU)."""
+                   fovy: torch.Tensor, f_px=None) -> None:
+        """Allocation-free variant used by the benchmark loop (all tensors on this GPU; f_px as in `infer`, a CUDA [B] fp32
+        tensor keeps it allocation-free)."""
         B, _, H, W = x.shape
-        _lib.check(self._lib.md_depth_pro_infer(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                C.c_void_p(depth.data_ptr()), C.c_void_p(focal.data_ptr()),
-                                                C.c_void_p(fovx.data_ptr()), C.c_void_p(fovy.data_ptr()),
-                                                _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        self._infer_call(x, B, H, W, _lib.MD_MEM_DEVICE, f_px, depth, focal, fovx, fovy)
+
+    def _infer_call(self, x, B, H, W, in_kind, f_px, depth, focal, fovx, fovy) -> None:
+        outs = (C.c_void_p(depth.data_ptr()), C.c_void_p(focal.data_ptr()), C.c_void_p(fovx.data_ptr()), C.c_void_p(fovy.data_ptr()))
+        if f_px is None:
+            _lib.check(self._lib.md_depth_pro_infer(self._h, C.c_void_p(x.data_ptr()), B, H, W, in_kind, *outs,
+                                                    _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+            return
+        fp, keep = _focal_arg(f_px, B, in_kind == _lib.MD_MEM_DEVICE, self.device.ordinal)
+        _lib.check(self._lib.md_depth_pro_infer_with_focal(self._h, C.c_void_p(x.data_ptr()), B, H, W, in_kind, fp, *outs,
+                                                           _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        del keep
 
     def infer_windows(self, x: torch.Tensor, parts: int, timings: bool = False):
         """`infer` with the ViT stage run as `parts` consecutive windows of its 37 B sequences on this GPU -- the launches the
@@ -333,17 +364,27 @@ class DepthPro:
                                                              C.c_void_p(fovy.data_ptr()), _lib.MD_MEM_DEVICE, _stream_ptr(me.device.ordinal)))
         return DepthProInference(depth, focal, fovx, fovy)
 
-    def infer_from_rgb(self, rgb: bytes, width: int, height: int) -> DepthProInference:
-        """`infer_from_rgb` (src/inference.rs:128-137); raises MdError(MD_ERR_SHAPE) on a bad length."""
+    def infer_from_rgb(self, rgb: bytes, width: int, height: int, f_px=None) -> DepthProInference:
+        """`infer_from_rgb` (src/inference.rs:128-137); raises MdError(MD_ERR_SHAPE) on a bad length. f_px: the caller's focal
+        length in pixels of the image (a float), or None to predict it."""
         dev = torch.device("cuda", self.device.ordinal)
         depth = torch.empty((1, height, width), dtype=torch.float32, device=dev) if width > 0 and height > 0 else None
         focal = torch.empty((1,), dtype=torch.float32, device=dev)
         fovy = torch.empty((1,), dtype=torch.float32, device=dev)
         buf = (C.c_uint8 * len(rgb)).from_buffer_copy(rgb) if len(rgb) else (C.c_uint8 * 1)()
-        _lib.check(self._lib.md_infer_from_rgb(self._h, C.cast(buf, C.c_void_p), len(rgb), int(width), int(height),
-                                               _lib.MD_MEM_HOST, C.c_void_p(depth.data_ptr() if depth is not None else 0),
-                                               C.c_void_p(focal.data_ptr()), C.c_void_p(fovy.data_ptr()),
-                                               _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        outs = (C.c_void_p(depth.data_ptr() if depth is not None else 0), C.c_void_p(focal.data_ptr()), C.c_void_p(fovy.data_ptr()),
+                _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal))
+        if f_px is None:
+            _lib.check(self._lib.md_infer_from_rgb(self._h, C.cast(buf, C.c_void_p), len(rgb), int(width), int(height),
+                                                   _lib.MD_MEM_HOST, *outs))
+        else:
+            if isinstance(f_px, torch.Tensor) or not isinstance(f_px, (int, float, np.floating, np.integer)):
+                vals = [float(v) for v in (f_px.reshape(-1).tolist() if isinstance(f_px, torch.Tensor) else f_px)]
+                if len(vals) != 1:
+                    raise _lib.MdError(_lib.MD_ERR_SHAPE, f"f_px holds {len(vals)} focal lengths for one image")
+                f_px = vals[0]
+            _lib.check(self._lib.md_infer_from_rgb_with_focal(self._h, C.cast(buf, C.c_void_p), len(rgb), int(width), int(height),
+                                                              _lib.MD_MEM_HOST, C.c_float(float(f_px)), *outs))
         return DepthProInference(depth, focal, torch.empty(0), fovy)
 
     # ---- debug taps / timing --------------------------------------------------------------

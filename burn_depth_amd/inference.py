@@ -3,6 +3,8 @@
 * ``DepthPrediction``      -- src/inference.rs:10-20
 * ``rgb_to_input_tensor``  -- src/inference.rs:79-121 (device kernel; Err on a wrong byte length)
 * ``infer_from_rgb``       -- src/inference.rs:128-137
+* ``f_px``                 -- the caller's focal length (pixels of the input's width): the FOV network does not run and the
+                              prediction carries that focal length
 """
 from __future__ import annotations
 
@@ -39,12 +41,12 @@ def rgb_to_input_tensor(rgb: bytes, width: int, height: int, device: Device) -> 
     return out
 
 
-def infer_depth(model: DepthPro, x: torch.Tensor) -> DepthPrediction:
-    """`DepthModel::infer_depth` for DepthPro (src/inference.rs:36-40)."""
-    r = model.infer(x)
+def infer_depth(model: DepthPro, x: torch.Tensor, f_px=None) -> DepthPrediction:
+    """`DepthModel::infer_depth` for DepthPro (src/inference.rs:36-40); f_px as in `DepthPro.infer`."""
+    r = model.infer(x, f_px)
     return DepthPrediction(r.depth, r.focallength_px, r.fovy_rad)
 
 
-def infer_from_rgb(model: DepthPro, rgb: bytes, width: int, height: int) -> DepthPrediction:
-    r = model.infer_from_rgb(rgb, width, height)
+def infer_from_rgb(model: DepthPro, rgb: bytes, width: int, height: int, f_px=None) -> DepthPrediction:
+    r = model.infer_from_rgb(rgb, width, height, f_px)
     return DepthPrediction(r.depth, r.focallength_px, r.fovy_rad)

@@ -250,5 +250,10 @@ class AnyDepthModel:
             return PreparedModelImage(rgb.shape[1], rgb.shape[0], rgb.copy(), None)
         return prepare_depth_anything3_image(rgb, self.model.img_size())
 
-    def infer_from_rgb(self, prepared: PreparedModelImage):
-        return self.model.infer_from_rgb(prepared.rgb.tobytes(), prepared.width, prepared.height)
+    def infer_from_rgb(self, prepared: PreparedModelImage, f_px: Optional[float] = None):
+        """f_px: the caller's focal length in pixels of the prepared image (Depth Pro only: the FOV network does not run)."""
+        if f_px is None:
+            return self.model.infer_from_rgb(prepared.rgb.tobytes(), prepared.width, prepared.height)
+        if self.kind != DepthModelKind.DEPTH_PRO:
+            raise ValueError(f"a known focal length applies to Depth Pro only, not to `{self.kind.value}`")
+        return self.model.infer_from_rgb(prepared.rgb.tobytes(), prepared.width, prepared.height, f_px)

@@ -149,6 +149,19 @@ int md_model_fork(md_model_t m, md_model_t* out);
 int md_depth_pro_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth,
                        float* focallength_px, float* fovx_deg, float* fovy_rad, int out_kind, void* stream);
 
+/* `md_depth_pro_infer` with the caller's focal length (Apple ml-depth-pro's `infer(x, f_px)`; burn_depth's README passes
+ * `None`): f_px[B] fp32, one focal length per image in pixels of the input as passed (width W before any resize), in memory of
+ * kind `in_kind` like the image. f_px == NULL is exactly md_depth_pro_infer (same launches, same bits, MD_ERR_NO_FOV without a
+ * FOV head). With f_px the FOV encoder and head do not run -- a model built with use_fov_head = 0 infers depth this way -- and
+ *   focallength_px = f_px (bit for bit), fovx_deg = 2 atan(W / (2 f_px)) in degrees, fovy_rad from that fovx through the
+ *   reference's fovy_from_fovx_rad (mod.rs:370-414), depth = mod.rs:330-363 with ratio = W / f_px
+ * (an f_px equal to the predicted focal length gives md_depth_pro_infer's depth bit for bit). Host values that are not finite
+ * or not > 0 -> MD_ERR_INVALID_ARG before anything is launched; device values are not inspected (the call stays
+ * asynchronous) and are read at run time, also by a replayed graph. One batch is either all known or all predicted. */
+int md_depth_pro_infer_with_focal(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const float* f_px,
+                                  float* depth, float* focallength_px, float* fovx_deg, float* fovy_rad, int out_kind,
+                                  void* stream);
+
 /* One NCHW fp32 tensor handed across the boundary with its shape: `data` is [B, channels, height, width] (B is the call's). */
 typedef struct md_nchw_view {
   const float* data;
@@ -208,6 +221,12 @@ int md_depth_pro_infer_windows(md_model_t m, const float* nchw, int B, int H, in
  * row-major, `rgb_len` must equal w*h*3 (else MD_ERR_SHAPE, as the reference's Err). B = 1. */
 int md_infer_from_rgb(md_model_t m, const uint8_t* rgb, size_t rgb_len, int w, int h, int in_kind,
                       float* depth, float* focallength_px, float* fovy_rad, int out_kind, void* stream);
+
+/* md_infer_from_rgb with the caller's focal length f_px (a host scalar, pixels of the w-wide image): the outputs of
+ * md_depth_pro_infer_with_focal. A value that is not finite or not > 0 -> MD_ERR_INVALID_ARG. */
+int md_infer_from_rgb_with_focal(md_model_t m, const uint8_t* rgb, size_t rgb_len, int w, int h, int in_kind,
+                                 float f_px, float* depth, float* focallength_px, float* fovy_rad, int out_kind,
+                                 void* stream);
 
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
@@ -389,6 +408,10 @@ int md_op_conv2d_direct(md_device_t dev, const float* x_dev, const float* w_dev,
                         void* stream);
 /* `fovy_from_fovx_rad` (mod.rs:370-414) + focal length (mod.rs:330-336) on host scalars. */
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad);
+/* The reverse, on host scalars: a focal length f_px (pixels of the W-wide image) -> fovx_deg = 2 atan(W / (2 f_px)) in
+ * degrees and fovy_rad through `fovy_from_fovx_rad` (what md_depth_pro_infer_with_focal returns). f_px not finite or
+ * not > 0 -> MD_ERR_INVALID_ARG. */
+int md_op_focal_to_fov(float f_px, int H, int W, float* fovx_deg, float* fovy_rad);
 
 /* Kernel micro-benchmark: times `iters` launches of the GEMM kernel (random bf16/f32 operands resident
  * in HBM, plain store epilogue, out element = operand type) with HIP events on the launch stream and

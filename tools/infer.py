@@ -2,6 +2,9 @@
 
   python tools/infer.py --model depth-pro        --checkpoint depth_pro.safetensors --image photo.npy [--output depth.png]
   python tools/infer.py --model depth-anything-3 --checkpoint da3_small.safetensors  --image photo.npy
+  python tools/infer.py --model depth-pro        --checkpoint depth_pro.safetensors --image photo.npy --focal-px 1200
+
+`--focal-px F` (Depth Pro only): the camera's known focal length in pixels of the image; the FOV network does not run.
 
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
@@ -22,7 +25,14 @@ def main(argv=None) -> int:
     ap.add_argument("--image", required=True)
     ap.add_argument("--output", default="")
     ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16")
+    ap.add_argument("--focal-px", type=float, default=None, help="known focal length in pixels of the image (Depth Pro only)")
     a = ap.parse_args(argv)
+    if a.focal_px is not None and a.model != "depth-pro":
+        print(f"--focal-px applies to Depth Pro only, not to `{a.model}`", file=sys.stderr)
+        return 2
+    if a.focal_px is not None and not (np.isfinite(a.focal_px) and a.focal_px > 0):
+        print(f"--focal-px must be a finite focal length > 0, got {a.focal_px}", file=sys.stderr)
+        return 2
     from burn_depth_amd import pipeline as P
     from burn_depth_amd.config import Precision
     from burn_depth_amd.depth_pro import Device
@@ -41,7 +51,7 @@ def main(argv=None) -> int:
         return 1
     oh, ow = rgb.shape[:2]
     prep = model.prepare_input_image(rgb)
-    out = model.infer_from_rgb(prep)
+    out = model.infer_from_rgb(prep, a.focal_px)
     restore = (ow, oh) if (prep.width != ow or prep.height != oh or prep.crop is not None) else None
     path = a.output or os.path.join(os.path.dirname(os.path.abspath(a.image)), "depth.png")
     P.save_depth_map(out.depth.cpu().numpy(), path, prep.crop, restore)
