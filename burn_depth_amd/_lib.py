@@ -16,6 +16,7 @@ MD_ERR_INVALID_ARG, MD_ERR_SHAPE, MD_ERR_IO, MD_ERR_FORMAT, MD_ERR_HIP = -1, -2,
 MD_ERR_UNSUPPORTED, MD_ERR_NO_FOV, MD_ERR_OOM, MD_ERR_LEVELS = -6, -7, -8, -9
 MD_MEM_HOST, MD_MEM_DEVICE = 0, 1
 MD_COMM_ID_BYTES = 128
+MD_FRAME_U8_GRAY, MD_FRAME_RGBA_F32 = 0, 1
 TILE_256x256, TILE_128x128, TILE_256x32, TILE_128x64, TILE_64x64, TILE_AUTO = 0, 1, 2, 3, 4, 99
 
 
@@ -32,6 +33,17 @@ class MdDa3Outputs(C.Structure):
     """md_da3_outputs (include/mi_depth.h)."""
     _fields_ = [("depth", C.c_void_p), ("depth_confidence", C.c_void_p), ("aux", C.c_void_p), ("aux_confidence", C.c_void_p),
                 ("pose_encoding", C.c_void_p), ("extrinsics", C.c_void_p), ("intrinsics", C.c_void_p)]
+
+
+class MdFrameOpts(C.Structure):
+    """md_frame_opts (include/mi_depth.h)."""
+    _fields_ = [("target", C.c_int), ("restore", C.c_int), ("normalize", C.c_int), ("format", C.c_int)]
+
+
+class MdFrameOutputs(C.Structure):
+    """md_frame_outputs (include/mi_depth.h)."""
+    _fields_ = [("display", C.c_void_p), ("depth", C.c_void_p), ("depth_range", C.c_void_p), ("prepared", C.c_void_p),
+                ("focallength_px", C.c_void_p), ("fovy_rad", C.c_void_p)]
 
 
 class MdDa3Cfg(C.Structure):
@@ -96,6 +108,8 @@ SYMBOLS = {
     "md_depth_pro_infer_windows": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "md_infer_from_rgb": (_I, [_P, _P, C.c_size_t, _I, _I, _I, _P, _P, _P, _I, _P]),
     "md_infer_from_rgb_with_focal": (_I, [_P, _P, C.c_size_t, _I, _I, _I, C.c_float, _P, _P, _P, _I, _P]),
+    "md_frame_geometry": (_I, [_P, _I, _I, C.POINTER(MdFrameOpts), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "md_process_frame": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(MdFrameOpts), C.POINTER(MdFrameOutputs), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),
@@ -119,6 +133,9 @@ SYMBOLS = {
     "md_model_read_timing": (_I, [_P, C.POINTER(C.c_char_p), _F, C.POINTER(_I), _I, C.POINTER(_I)]),
     "md_model_read_launch_order": (_I, [_P, C.POINTER(C.c_char_p), _I, C.POINTER(_I)]),
     "md_op_rgb_to_input": (_I, [_P, _P, C.c_size_t, _I, _I, _P, _P]),
+    "md_catmull_rom_taps": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), _F]),
+    "md_op_resize_catmull_rom": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "md_op_depth_display": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "md_op_resize_bilinear": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "md_op_pyramid_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I), _P]),
     "md_op_resize_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P]),

@@ -8,6 +8,32 @@ namespace md {
 // a1  rgb_to_input_tensor (src/inference.rs:79-121): u8 HWC -> f32 NCHW, one image.
 int launch_rgb_to_input(const uint8_t* rgb, int w, int h, float* out, hipStream_t s);
 
+// ---- frame path (kernels/frame.hip; md_process_frame) ----
+// One axis of the separable Catmull-Rom resampler on the device: win[o] = (left, count), weights w[o * maxc + k].
+struct CrAxis {
+  const int2* win;
+  const float* w;
+  int maxc;
+};
+// host: window and normalised weights of output o of an in_len -> out_len pass (pipeline._sample_axis; weights may be null)
+void catmull_rom_window(int in_len, int out_len, int o, int* left, int* count, float* weights);
+int catmull_rom_max_taps(int in_len, int out_len);
+// host: the byte columns [xb0, xb0 + 4 nq) of an input row that output columns [cx, cx + tw) read
+void catmull_rom_span(const int* left, const int* count, int cx, int tw, int* xb0, int* nq);
+// u8 [B,h,w,3] -> vertical pass over output rows [cy, cy + th) into tmp [B,th,4 nq] f32 -> horizontal pass over output
+// columns [cx, cx + tw) -> out_u8 [B,th,tw,3] and / or out_nchw [B,3,th,tw] (rgb_to_input normalisation); either may be null
+int launch_resize_catmull_rom(const uint8_t* rgb, int B, int h, int w, const CrAxis& ax_v, int cy, int th, const CrAxis& ax_h, int cx,
+                              int tw, int xb0, int nq, float* tmp, uint8_t* out_u8, float* out_nchw, hipStream_t s);
+// depth [B,h,w] -> crop (cx, cy, cw, ch) -> resize = 1: bilinear restore to ow x oh with sx = cw / ow, sy = ch / oh
+// (pipeline.resize_depth_field); resize = 0: ow = cw, oh = ch
+struct DisplayGeom {
+  int B, h, w, cx, cy, cw, ch, ow, oh, resize;
+  float sx, sy;
+};
+int display_parts(const DisplayGeom& g);  // partial min / max pairs per frame (parts needs B * display_parts(g) float2)
+int launch_depth_display(const float* depth, const DisplayGeom& g, int normalize, int format, void* out, float* range, float2* parts,
+                         hipStream_t s);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

@@ -436,6 +436,94 @@ int md_op_rgb_to_input(md_device_t dev, const uint8_t* rgb_dev, size_t rgb_len, 
   return launch_rgb_to_input(rgb_dev, w, h, out_dev, pick_stream(dev, stream));
 }
 
+int md_frame_geometry(md_model_t m, int w, int h, const md_frame_opts* o, int* th, int* tw, int* oh, int* ow) {
+  return frame_geometry(m, w, h, o, th, tw, oh, ow);
+}
+
+int md_process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_kind, const md_frame_opts* o,
+                     const md_frame_outputs* out, int out_kind, void* stream) {
+  return process_frame(m, rgb, B, w, h, in_kind, o, out, out_kind, (hipStream_t)stream);
+}
+
+int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {
+  if (!left || !count) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (in_len <= 0 || out_len <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid pass %d -> %d", in_len, out_len);
+  if (index < 0 || index >= out_len) MD_FAIL(MD_ERR_INVALID_ARG, "index %d outside [0, %d)", index, out_len);
+  catmull_rom_window(in_len, out_len, index, left, count, weights);
+  return MD_OK;
+}
+
+int md_op_resize_catmull_rom(md_device_t dev, const uint8_t* rgb_dev, int B, int h, int w, int sw, int sh, int cx, int cy, int tw, int th,
+                             uint8_t* out_u8, float* out_nchw, void* stream) {
+  if (!rgb_dev || (!out_u8 && !out_nchw)) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (B <= 0 || h <= 0 || w <= 0 || sw <= 0 || sh <= 0 || tw <= 0 || th <= 0 || cx < 0 || cy < 0 || cx + tw > sw || cy + th > sh)
+    MD_FAIL(MD_ERR_SHAPE, "invalid resize %dx%d -> %dx%d, crop %dx%d at (%d, %d)", w, h, sw, sh, tw, th, cx, cy);
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  // tables of the two passes (identity when the size stays), uploaded for this call only
+  const bool crop_only = sw == w && sh == h;
+  std::vector<int> left[2], count[2];
+  std::vector<int2> win[2];
+  std::vector<float> wt[2];
+  int maxc[2] = {1, 1};
+  const int in_len[2] = {h, w}, out_len[2] = {sh, sw};
+  DevBuf tab[2], wbuf[2], tmp;
+  for (int a = 0; a < 2; ++a) {
+    const int n = out_len[a];
+    maxc[a] = crop_only ? 1 : catmull_rom_max_taps(in_len[a], n);
+    left[a].assign(n, 0);
+    count[a].assign(n, 1);
+    wt[a].assign((size_t)n * maxc[a], 0.f);
+    win[a].resize(n);
+    for (int o = 0; o < n; ++o) {
+      if (crop_only) {
+        left[a][o] = o;
+        wt[a][(size_t)o * maxc[a]] = 1.f;
+      } else {
+        catmull_rom_window(in_len[a], n, o, &left[a][o], &count[a][o], &wt[a][(size_t)o * maxc[a]]);
+      }
+      win[a][o] = make_int2(left[a][o], count[a][o]);
+    }
+    MD_TRY(tab[a].alloc((size_t)n * sizeof(int2)));
+    MD_TRY(wbuf[a].alloc(wt[a].size() * 4));
+    MD_HIP(hipMemcpy(tab[a].p, win[a].data(), (size_t)n * sizeof(int2), hipMemcpyHostToDevice));
+    MD_HIP(hipMemcpy(wbuf[a].p, wt[a].data(), wt[a].size() * 4, hipMemcpyHostToDevice));
+  }
+  int xb0 = 0, nq = 0;
+  catmull_rom_span(left[1].data(), count[1].data(), cx, tw, &xb0, &nq);
+  MD_TRY(tmp.alloc((size_t)B * th * nq * 16));
+  MD_TRY(launch_resize_catmull_rom(rgb_dev, B, h, w, CrAxis{(const int2*)tab[0].p, (const float*)wbuf[0].p, maxc[0]}, cy, th,
+                                   CrAxis{(const int2*)tab[1].p, (const float*)wbuf[1].p, maxc[1]}, cx, tw, xb0, nq, (float*)tmp.p, out_u8,
+                                   out_nchw, st));
+  MD_HIP(hipStreamSynchronize(st));  // the tables and the intermediate are freed on return
+  return MD_OK;
+}
+
+int md_op_depth_display(md_device_t dev, const float* depth_dev, int B, int h, int w, int crop_x, int crop_y, int crop_w, int crop_h, int ow,
+                        int oh, int normalize, int format, void* out, float* range, void* stream) {
+  if (!depth_dev || (!out && !range)) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (format != MD_FRAME_U8_GRAY && format != MD_FRAME_RGBA_F32) MD_FAIL(MD_ERR_INVALID_ARG, "unknown display format %d", format);
+  if (format == MD_FRAME_U8_GRAY && !normalize) MD_FAIL(MD_ERR_INVALID_ARG, "the u8 grey display needs normalize = 1");
+  if (crop_w == 0) {
+    crop_x = crop_y = 0;
+    crop_w = w;
+    crop_h = h;
+  }
+  if (B <= 0 || h <= 0 || w <= 0 || ow <= 0 || oh <= 0 || crop_x < 0 || crop_y < 0 || crop_w <= 0 || crop_h <= 0 || crop_x + crop_w > w ||
+      crop_y + crop_h > h)
+    MD_FAIL(MD_ERR_SHAPE, "invalid display of [%d,%d,%d]: crop %dx%d at (%d, %d) -> %dx%d", B, h, w, crop_w, crop_h, crop_x, crop_y, ow, oh);
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const DisplayGeom g = display_geom(B, h, w, crop_x, crop_y, crop_w, crop_h, ow, oh);
+  DevBuf parts;
+  MD_TRY(parts.alloc((size_t)B * display_parts(g) * sizeof(float2)));
+  MD_TRY(launch_depth_display(depth_dev, g, normalize, format, out, range, (float2*)parts.p, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
 int md_op_resize_bilinear(md_device_t dev, const float* in_dev, int B, int C, int H, int W, float* out_dev, int OH, int OW,
                           int method, void* stream) {
   if (!dev || !in_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");

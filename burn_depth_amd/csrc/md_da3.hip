@@ -622,6 +622,12 @@ int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
   return MD_OK;
 }
 
+void da3_frame_info(md_model_t m, int* patch, int* cur_h, int* cur_w) {
+  *patch = m->da3->cfg.vit.ps;
+  *cur_h = m->da3->tok_index ? m->da3->ih : 0;
+  *cur_w = m->da3->tok_index ? m->da3->iw : 0;
+}
+
 long da3_shape_builds(md_model_t m) { return (m && m->da3) ? m->da3->table_builds : 0; }
 
 void da3_destroy_state(md_model_t m) {
@@ -1316,6 +1322,12 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
   }
   if (out_kind == MD_MEM_HOST) MD_HIP(hipStreamSynchronize(st));
   return MD_OK;
+}
+
+int da3_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, hipStream_t stream) {
+  Da3Outputs o;
+  o.depth = depth;
+  return da3_infer_eager(m, nchw, B, H, W, MD_MEM_DEVICE, o, MD_MEM_DEVICE, stream);
 }
 
 int da3_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, int out_kind,

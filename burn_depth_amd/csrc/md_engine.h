@@ -161,6 +161,9 @@ struct md_model_s {
   int kind = 0;
   struct Da3State;
   Da3State* da3 = nullptr;
+  // ---- md_process_frame: tap tables, staging and scratch of the frame path (md_frame.hip); per model, so per fork ----
+  struct FrameState;
+  FrameState* frame = nullptr;
   // geometry shared by create/infer
   int S = 0, win = 0, g = 0, P = 0, NT = 0, SS = 0, kpad = 0;
   int steps0 = 0, stride0 = 0, steps1 = 0, stride1 = 0, pad_hi = 0, pad_mid = 0;
@@ -209,6 +212,17 @@ int model_infer_sharded(md_model_t m, const float* nchw, int B, int H, int W, in
                         float* fovx, float* fovy, int out_kind, hipStream_t stream, const ShardPlan& sp);
 // the model's grow-only input staging buffer, holding `elems` floats: filled from `nchw` (host or device) when it is given
 int model_stage_input(md_model_t m, const float* nchw, size_t elems, int in_kind, hipStream_t stream, float** dev);
+// md_process_frame's pieces: model_infer / da3_infer_ex without the graph layer (the frame call captures its own graph around
+// them), the grow-only pinned staging of a host u8 frame (`bytes` of `rgb` -> the model's device copy *dev), and the frame
+// path's state (md_frame.hip)
+int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, float* focal, float* fovy, hipStream_t stream);
+int model_stage_rgb(md_model_t m, const uint8_t* rgb, size_t bytes, hipStream_t stream, const uint8_t** dev);
+void frame_destroy_state(md_model_t m);
+int frame_geometry(md_model_t m, int w, int h, const md_frame_opts* o, int* th, int* tw, int* oh, int* ow);
+int process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_kind, const md_frame_opts* o, const md_frame_outputs* out,
+                  int out_kind, hipStream_t stream);
+// crop (cx, cy, cw, ch) of a [B,h,w] map, restored to ow x oh (no restore at the crop's own size)
+DisplayGeom display_geom(int B, int h, int w, int cx, int cy, int cw, int ch, int ow, int oh);
 int pack_weight(const float* src, const PackEntry& e, int prec, hipStream_t s);
 // number of values of w[0..n) that are not exactly representable as an IEEE half (synchronises the stream)
 int count_inexact_f16(const float* w, long n, hipStream_t s, unsigned* out);
@@ -259,7 +273,10 @@ struct Da3Outputs {
 int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const Da3Outputs& out, int out_kind,
                  hipStream_t stream);
 void da3_destroy_state(md_model_t m);
-long da3_shape_builds(md_model_t m);  // input sizes whose tables were built so far (0 for Depth Pro models)
+long da3_shape_builds(md_model_t m);
+int da3_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, hipStream_t stream);  // device in / out
+// patch size and the current input size (rows, columns; 0 before the first plan) of a Depth-Anything-v3 model
+void da3_frame_info(md_model_t m, int* patch, int* cur_h, int* cur_w);  // input sizes whose tables were built so far (0 for Depth Pro models)
 int da3_on_commit(md_model_t m);  // re-derives the (interpolated) position table from the weights
 int model_load_params_from_container(md_model_t m, const char* path);
 

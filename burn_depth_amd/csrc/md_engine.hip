@@ -682,6 +682,7 @@ int model_destroy(md_model_t m) {
     (void)hipEventDestroy(t.b);
   }
   if (m->da3) da3_destroy_state(m);
+  if (m->frame) frame_destroy_state(m);
   if (m->buf) {
     if (m->buf->xraw) (void)hipFree(m->buf->xraw);
     if (m->buf->rgb) (void)hipFree(m->buf->rgb);
@@ -1722,6 +1723,20 @@ int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kin
   const std::vector<uintptr_t> key = {(uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw, (uintptr_t)depth,
                                       (uintptr_t)focal, (uintptr_t)fovx, (uintptr_t)fovy, (uintptr_t)gen, (uintptr_t)f_px};
   return run_with_graph(m, st, key, eligible, body);
+}
+
+int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, float* focal, float* fovy, hipStream_t stream) {
+  return model_infer_eager(m, nchw, B, H, W, MD_MEM_DEVICE, depth, focal, nullptr, fovy, MD_MEM_DEVICE, stream, nullptr, 0, nullptr, 0);
+}
+
+int model_stage_rgb(md_model_t m, const uint8_t* rgb, size_t bytes, hipStream_t st, const uint8_t** dev) {
+  if (!m->buf) m->buf = new md_model_s::Buffers();  // a Depth-Anything-v3 model stages through the same grow-only buffers
+  md_model_s::Buffers* b = m->buf;
+  if (b->rgb_cap < bytes) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
+  MD_TRY(ensure_device(m, (void**)&b->rgb, &b->rgb_cap, bytes));
+  MD_TRY(stage_host_to_device(m, b->rgb, rgb, bytes, st));
+  *dev = (const uint8_t*)b->rgb;
+  return MD_OK;
 }
 
 int model_stage_input(md_model_t m, const float* nchw, size_t elems, int in_kind, hipStream_t stream, float** dev) {

@@ -38,7 +38,8 @@ def _c_cfg(cfg: DepthAnything3Config):
 
 
 class DepthAnything3(DepthPro):
-    """Shares the record / timing / query plumbing of the md_model_t handle with DepthPro."""
+    """Shares the record / timing / query / frame-path plumbing of the md_model_t handle with DepthPro."""
+    MODEL_KIND = "depth-anything-3"
 
     @staticmethod
     def new(device: Device, config: Optional[DepthAnything3Config] = None, seed: int = 0, init_scheme: int = 0) -> "DepthAnything3":

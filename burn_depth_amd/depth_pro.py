@@ -65,6 +65,19 @@ class DepthProInference:
 
 
 @dataclass
+class FrameResult:
+    """What `md_process_frame` returns (include/mi_depth.h): the display map (u8 [B,oh,ow] or RGBA f32 [B,oh,ow,4]), the
+    model-resolution depth [B,th,tw], the normalisation range [B,2], the prepared frame [B,th,tw,3] and, for Depth Pro,
+    focal length and vertical field of view [B]. Device tensors."""
+    display: Optional[torch.Tensor]
+    depth: torch.Tensor
+    depth_range: torch.Tensor
+    prepared: Optional[torch.Tensor] = None
+    focallength_px: Optional[torch.Tensor] = None
+    fovy_rad: Optional[torch.Tensor] = None
+
+
+@dataclass
 class HeadDebug:
     """depth_pro/mod.rs:135-142."""
     conv0: torch.Tensor      # [B, F/2, s, s]
@@ -386,6 +399,61 @@ class DepthPro:
             _lib.check(self._lib.md_infer_from_rgb_with_focal(self._h, C.cast(buf, C.c_void_p), len(rgb), int(width), int(height),
                                                               _lib.MD_MEM_HOST, C.c_float(float(f_px)), *outs))
         return DepthProInference(depth, focal, torch.empty(0), fovy)
+
+    # ---- frame path --------------------------------------------------------------------------
+    MODEL_KIND = "depth-pro"
+    _FRAME_FORMATS = {"u8": _lib.MD_FRAME_U8_GRAY, "rgba": _lib.MD_FRAME_RGBA_F32}
+
+    def _frame_opts(self, target: int, restore: bool, normalize: bool, fmt: str) -> "_lib.MdFrameOpts":
+        if fmt not in self._FRAME_FORMATS:
+            raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown display format `{fmt}` (u8 | rgba)")
+        return _lib.MdFrameOpts(int(target), int(bool(restore)), int(bool(normalize)), self._FRAME_FORMATS[fmt])
+
+    def frame_geometry(self, width: int, height: int, target: int = 0, restore: bool = True, normalize: bool = True,
+                       fmt: str = "u8") -> Tuple[int, int, int, int]:
+        """(th, tw, oh, ow) of `process_frame` on width x height frames: model input / depth size, display size."""
+        o = self._frame_opts(target, restore, normalize, fmt)
+        v = [C.c_int() for _ in range(4)]
+        _lib.check(self._lib.md_frame_geometry(self._h, int(width), int(height), C.byref(o), *(C.byref(x) for x in v)))
+        return tuple(x.value for x in v)
+
+    def process_frame(self, rgb, target: int = 0, restore: bool = True, normalize: bool = True, fmt: str = "u8",
+                      prepared: bool = True, out: Optional[FrameResult] = None) -> FrameResult:
+        """`md_process_frame`: uint8 RGB frames [H,W,3] / [B,H,W,3] (numpy: host memory; torch: its device) -> prepared input,
+        inference and display in one device call. target / restore / normalize / fmt: `md_frame_opts`. `out`: a FrameResult
+        of an earlier call to write into again (fixed output pointers: what a captured graph replays)."""
+        if isinstance(rgb, np.ndarray):
+            if rgb.dtype != np.uint8:
+                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"expected uint8 frames, got {rgb.dtype}")
+            rgb = np.ascontiguousarray(rgb)
+            keep, ptr, in_kind = rgb, rgb.ctypes.data, _lib.MD_MEM_HOST
+        elif isinstance(rgb, torch.Tensor):
+            if rgb.dtype != torch.uint8:
+                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"expected uint8 frames, got {rgb.dtype}")
+            rgb = rgb.contiguous()
+            keep, ptr, in_kind = rgb, rgb.data_ptr(), (_lib.MD_MEM_DEVICE if rgb.is_cuda else _lib.MD_MEM_HOST)
+        else:
+            raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "rgb must be a numpy array or a torch tensor")
+        if keep.ndim == 3:
+            keep = keep[None] if isinstance(keep, np.ndarray) else keep.unsqueeze(0)
+        if keep.ndim != 4 or keep.shape[3] != 3:
+            raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,H,W,3] frames, got {tuple(keep.shape)}")
+        B, H, W = (int(x) for x in keep.shape[:3])
+        th, tw, oh, ow = self.frame_geometry(W, H, target, restore, normalize, fmt)
+        if out is None:
+            dev = torch.device("cuda", self.device.ordinal)
+            f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+            pro = self.MODEL_KIND == "depth-pro"
+            out = FrameResult(display=f(B, oh, ow, dt=torch.uint8) if fmt == "u8" else f(B, oh, ow, 4), depth=f(B, th, tw),
+                              depth_range=f(B, 2), prepared=f(B, th, tw, 3, dt=torch.uint8) if prepared else None,
+                              focallength_px=f(B) if pro else None, fovy_rad=f(B) if pro else None)
+        ptr_of = lambda t: t.data_ptr() if t is not None else None
+        o = self._frame_opts(target, restore, normalize, fmt)
+        outs = _lib.MdFrameOutputs(ptr_of(out.display), ptr_of(out.depth), ptr_of(out.depth_range), ptr_of(out.prepared),
+                                   ptr_of(out.focallength_px), ptr_of(out.fovy_rad))
+        _lib.check(self._lib.md_process_frame(self._h, C.c_void_p(ptr), B, W, H, in_kind, C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE,
+                                              _stream_ptr(self.device.ordinal)))
+        return out
 
     # ---- debug taps / timing --------------------------------------------------------------
     def enable_taps(self, enable: bool = True) -> None:

@@ -8,6 +8,8 @@
   test of the reference touches it).
 * `crop_depth_field`, `resize_depth_field`, `sample_depth_bilinear`, the min-max normalisation of `save_depth_map`
                                               -- example/inference.rs:103-273 (restated exactly, fp32)
+* `prepare_input_frame`, `depth_to_display`   -- the viewer's frame path (crates/bevy_burn_depth/src/lib.rs:16-132): the host
+  references of the device frame call `md_process_frame` (`DepthPro.process_frame`)
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
   stands in (8-bit grayscale, filter 0), `read_gray_png` reads it back for the tests.
 JPEG decoding stays out of scope: images come in as uint8 arrays."""
@@ -162,6 +164,59 @@ def depth_to_u8(depth: np.ndarray, crop: Optional[ImageCropRegion] = None,
     return np.clip(np.floor(norm * f32(255) + f32(0.5)), 0, 255).astype(np.uint8)  # f32::round on non-negative values
 
 
+def prepare_input_frame(rgb: np.ndarray, patch_size: int, preferred_resolution: Optional[int]) -> PreparedModelImage:
+    """`prepare_input_frame` (crates/bevy_burn_depth/src/lib.rs:76-132): with a preferred resolution, the shortest-side
+    Catmull-Rom resize + centre crop of `prepare_depth_anything3_image` (target raised to the patch size); without one, a
+    centre crop to patch-aligned sizes (`align_down`: multiples of 4 * patch from 4 * patch on, of patch below that, the size
+    itself below one patch)."""
+    patch_size = max(int(patch_size), 1)
+    if preferred_resolution is not None:
+        return prepare_depth_anything3_image(rgb, max(int(preferred_resolution), patch_size, 1))
+    h, w = rgb.shape[:2]
+    alignment = patch_size * 4
+
+    def align_down(v: int) -> int:
+        if v < patch_size:
+            return v
+        return v - v % (alignment if v >= alignment else patch_size)
+
+    cw, ch = max(align_down(w), 1), max(align_down(h), 1)
+    if cw == w and ch == h:
+        return PreparedModelImage(w, h, rgb.copy(), None)
+    ox, oy = (w - cw) // 2, (h - ch) // 2
+    return PreparedModelImage(cw, ch, np.ascontiguousarray(rgb[oy:oy + ch, ox:ox + cw]), None)
+
+
+def depth_to_display(depth: np.ndarray, crop: Optional[ImageCropRegion] = None, target_dims: Optional[Tuple[int, int]] = None,
+                     normalize: bool = True, fmt: str = "u8") -> np.ndarray:
+    """The display step of the frame path, per frame of [H,W] or [B,H,W]: `depth_to_u8`'s pixels for fmt "u8" (needs
+    normalize); for fmt "rgba" the viewer's texture (lib.rs:40-73) -- grey = the same min-max normalised value (or the raw
+    depth without normalize) three times, alpha 1 -- as f32 [..., 4]."""
+    if fmt not in ("u8", "rgba"):
+        raise ValueError(f"unknown display format `{fmt}`")
+    if fmt == "u8" and not normalize:
+        raise ValueError("the u8 display needs normalize")
+    frames = depth[None] if depth.ndim == 2 else depth
+    out = []
+    for d in frames:
+        if fmt == "u8":
+            out.append(depth_to_u8(d, crop, target_dims))
+            continue
+        v = d.astype(f32)
+        if crop is not None:
+            v = crop_depth_field(v, crop)
+        if target_dims is not None and (target_dims[0] != v.shape[1] or target_dims[1] != v.shape[0]):
+            v = resize_depth_field(v, target_dims[0], target_dims[1])
+        if normalize:
+            fin = np.isfinite(v)
+            lo, hi = (f32(v[fin].min()), f32(v[fin].max())) if fin.any() else (f32(0), f32(1))
+            rng = max(f32(hi - lo), np.finfo(f32).eps)
+            v = np.where(fin, np.clip((v - lo) / rng, 0, 1), 0).astype(f32)
+        out.append(np.stack([v, v, v, np.ones_like(v)], axis=-1).astype(f32))
+    res = np.stack(out)
+    return res[0] if depth.ndim == 2 else res
+
+
 def write_gray_png(path: str, pixels: np.ndarray) -> None:
     if pixels.dtype != np.uint8 or pixels.ndim != 2:
         raise ValueError("expected uint8 [H,W]")
@@ -241,6 +296,12 @@ class AnyDepthModel:
             except _lib.MdError as e:
                 last = e
         raise RuntimeError(f"Failed to load Depth Anything 3 checkpoint `{checkpoint}`: {last}")
+
+    def process_frame(self, rgb, normalize_relative_depth: bool = True, fmt: str = "rgba"):
+        """`process_frame` (crates/bevy_burn_depth/src/lib.rs:16-74) on the device: prepare at the model's resolution, infer,
+        min-max normalise (normalize_relative_depth) and build the display at the model's resolution -- RGBA f32 for the
+        viewer's texture, or "u8" grey. rgb: uint8 [H,W,3] / [B,H,W,3] (numpy or torch). Returns a `FrameResult`."""
+        return self.model.process_frame(rgb, target=0, restore=False, normalize=normalize_relative_depth, fmt=fmt)
 
     def preferred_input_resolution(self) -> Optional[int]:
         return None if self.kind == DepthModelKind.DEPTH_PRO else self.model.img_size()

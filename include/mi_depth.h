@@ -228,6 +228,42 @@ int md_infer_from_rgb_with_focal(md_model_t m, const uint8_t* rgb, size_t rgb_le
                                  float f_px, float* depth, float* focallength_px, float* fovy_rad, int out_kind,
                                  void* stream);
 
+/* ---- frame path: u8 RGB camera frames in, a displayable depth map out (the viewer's `process_frame`,
+ * crates/bevy_burn_depth/src/lib.rs:16-132, and the CLI's prepare / save_depth_map, example/inference.rs:79-273) ---------
+ * Everything runs on the device in one call: preparation (Catmull-Rom resize + centre crop, or a patch-aligned crop, and
+ * the input normalisation), the model, and the display step (crop back to the frame's aspect, bilinear restore to the
+ * frame's size, per-frame min-max over the finite values, grey u8 or RGBA f32). */
+#define MD_FRAME_U8_GRAY 0  /* u8 [B,oh,ow]: floor(n * 255 + 0.5), the CLI's PNG pixels; needs normalize = 1 */
+#define MD_FRAME_RGBA_F32 1 /* f32 [B,oh,ow,4]: (n, n, n, 1), the viewer's texture */
+typedef struct md_frame_opts {
+  int target;    /* Depth-Anything-v3: > 0 shortest-side Catmull-Rom resize to target (raised to the patch size) + centre
+                    crop (prepare_depth_anything3_image); 0 = the model's img_size; -1 = patch-aligned centre crop, no resize
+                    (prepare_input_frame without a preferred resolution). Depth Pro: must be 0 (the model resizes). */
+  int restore;   /* 1: the display map is brought back to the frame's w x h (example/inference.rs:82-93) */
+  int normalize; /* 1: per-frame min-max over the finite values (depth_to_u8); 0: raw depth (RGBA only) */
+  int format;    /* MD_FRAME_U8_GRAY | MD_FRAME_RGBA_F32 */
+} md_frame_opts;
+
+typedef struct md_frame_outputs {
+  void* display;          /* u8 [B,oh,ow] or f32 [B,oh,ow,4]; NULL = skip */
+  float* depth;           /* model-resolution depth [B,th,tw]; NULL = skip */
+  float* depth_range;     /* [B,2] lo, hi of the normalisation (0, 1 for a frame without a finite value); NULL = skip */
+  uint8_t* prepared;      /* [B,th,tw,3] the resized / cropped frame the model saw; NULL = skip */
+  float* focallength_px;  /* Depth Pro only, [B]; NULL = skip */
+  float* fovy_rad;        /* Depth Pro only, [B]; NULL = skip */
+} md_frame_outputs;
+
+/* Sizes of a frame call: th x tw = the model input (and `depth`), oh x ow = the display map. */
+int md_frame_geometry(md_model_t m, int w, int h, const md_frame_opts* o, int* th, int* tw, int* oh, int* ow);
+/* B >= 1 frames of one size w x h, packed u8 RGB [B,h,w,3] in memory kind in_kind; every output in out_kind. With
+ * md_model_enable_graph(m, 1), a device frame with device outputs replays one captured graph per (stream, B, w, h, opts,
+ * output pointers). No host synchronisation inside the call except for host frames (pinned staging) and host outputs.
+ * Errors: rgb / o / out NULL -> MD_ERR_INVALID_ARG; w, h <= 0 or B outside 1..max_batch -> MD_ERR_SHAPE; a target the
+ * Depth-Anything-v3 model rejects -> MD_ERR_SHAPE; Depth Pro with target != 0, an unknown format or U8 without normalize
+ * -> MD_ERR_INVALID_ARG. */
+int md_process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_kind, const md_frame_opts* o,
+                     const md_frame_outputs* out, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).
@@ -373,6 +409,20 @@ int md_op_pyramid_patchify(md_device_t dev, const float* x_dev, int B, int S, in
  * / f32), C a multiple of 8. method MD_INTERP_BURN = align_corners=True (what that head uses), MD_INTERP_CUSTOM = False. */
 int md_op_resize_nhwc(md_device_t dev, const void* in_dev, int B, int H, int W, int C, void* out_dev, int OH, int OW,
                       int method, int precision, void* stream);
+/* The frame path's Catmull-Rom taps (pipeline._catmull_rom / _sample_axis, host only): the window [left, left + count) of
+ * output `index` of an in_len -> out_len pass and its normalised weights (capacity: count, at most 4 * in_len / out_len + 6;
+ * weights may be NULL to query the window). */
+int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights);
+/* The frame path's preparation alone: u8 [B,h,w,3] (device) -> shortest-side Catmull-Rom resize to sw x sh, centre crop at
+ * (cx, cy) of size tw x th -> out_u8 [B,th,tw,3] and / or the normalised fp32 NCHW input out_nchw [B,3,th,tw] (either may be
+ * NULL). sw = w and sh = h: a pure crop. */
+int md_op_resize_catmull_rom(md_device_t dev, const uint8_t* rgb_dev, int B, int h, int w, int sw, int sh, int cx, int cy,
+                             int tw, int th, uint8_t* out_u8, float* out_nchw, void* stream);
+/* The frame path's display step alone: depth [B,h,w] (device) -> crop (crop_w = 0: the whole map) -> bilinear restore to
+ * ow x oh (pipeline.resize_depth_field; the crop's size: no restore) -> MD_FRAME_U8_GRAY / MD_FRAME_RGBA_F32 `out`,
+ * range [B,2] (either may be NULL). */
+int md_op_depth_display(md_device_t dev, const float* depth_dev, int B, int h, int w, int crop_x, int crop_y, int crop_w,
+                        int crop_h, int ow, int oh, int normalize, int format, void* out, float* range, void* stream);
 /* `resize_bilinear_scale` (interpolate.rs:136-145): writes the output dims to oh/ow. */
 int md_op_resize_output_size(int H, int W, float scale_h, float scale_w, int* oh, int* ow);
 /* `DepthProEncoder::split` (encoder.rs:190-232): fp32 NCHW [B,C,S,S] -> [steps^2*B,C,win,win]. */

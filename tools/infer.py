@@ -5,6 +5,9 @@
   python tools/infer.py --model depth-pro        --checkpoint depth_pro.safetensors --image photo.npy --focal-px 1200
 
 `--focal-px F` (Depth Pro only): the camera's known focal length in pixels of the image; the FOV network does not run.
+`--on-device`: the whole flow (prepare, inference, restore, min-max normalisation, 8-bit pixels) runs in one device call,
+`md_process_frame`; the PNG is the same as the default path's up to the resize's rounding (bit-identical when the image
+needs no resize).
 
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
@@ -26,6 +29,7 @@ def main(argv=None) -> int:
     ap.add_argument("--output", default="")
     ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--focal-px", type=float, default=None, help="known focal length in pixels of the image (Depth Pro only)")
+    ap.add_argument("--on-device", action="store_true", help="prepare, infer and build the PNG's pixels in one device call (md_process_frame)")
     a = ap.parse_args(argv)
     if a.focal_px is not None and a.model != "depth-pro":
         print(f"--focal-px applies to Depth Pro only, not to `{a.model}`", file=sys.stderr)
@@ -49,11 +53,22 @@ def main(argv=None) -> int:
     except RuntimeError as e:
         print(str(e), file=sys.stderr)
         return 1
+    if a.on_device and a.focal_px is not None:
+        print("--on-device takes no --focal-px (the frame call predicts the focal length)", file=sys.stderr)
+        return 2
     oh, ow = rgb.shape[:2]
+    path = a.output or os.path.join(os.path.dirname(os.path.abspath(a.image)), "depth.png")
+    if a.on_device:
+        fr = model.model.process_frame(rgb, target=0, restore=True, normalize=True, fmt="u8", prepared=False)
+        P.write_gray_png(path, fr.display[0].cpu().numpy())
+        f, fy = fr.focallength_px, fr.fovy_rad
+        print(f"Focal length (px): {f.cpu().tolist() if f is not None else 'not provided by this model'}")
+        print(f"Vertical FOV (rad): {fy.cpu().tolist() if fy is not None else 'not provided by this model'}")
+        print(f"Model `{kind.value}` wrote normalized depth map to {path}")
+        return 0
     prep = model.prepare_input_image(rgb)
     out = model.infer_from_rgb(prep, a.focal_px)
     restore = (ow, oh) if (prep.width != ow or prep.height != oh or prep.crop is not None) else None
-    path = a.output or os.path.join(os.path.dirname(os.path.abspath(a.image)), "depth.png")
     P.save_depth_map(out.depth.cpu().numpy(), path, prep.crop, restore)
     f = getattr(out, "focallength_px", None)
     print(f"Focal length (px): {f.cpu().tolist() if f is not None else 'not provided by this model'}")
