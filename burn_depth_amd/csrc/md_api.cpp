@@ -329,9 +329,7 @@ int md_model_set_option(md_model_t m, const char* key, int64_t value) {
       m->batch_invariant = value != 0;
       MD_HIP(hipSetDevice(m->dev->ordinal));
       MD_HIP(hipDeviceSynchronize());
-      for (auto& kv : m->graphs)  // captured graphs hold the kernel forms of the old setting
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-      m->graphs.clear();
+      m->graphs.clear();  // captured graphs hold the kernel forms of the old setting
     }
     return MD_OK;
   }
@@ -342,9 +340,7 @@ int md_model_set_option(md_model_t m, const char* key, int64_t value) {
       m->ln_fold_opt = (int)value;
       MD_HIP(hipSetDevice(m->dev->ordinal));
       MD_HIP(hipDeviceSynchronize());
-      for (auto& kv : m->graphs)  // captured graphs hold the launches of the old setting
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-      m->graphs.clear();
+      m->graphs.clear();  // captured graphs hold the launches of the old setting
     }
     return MD_OK;
   }

@@ -253,7 +253,7 @@ int md_comm_depth_pro_infer_tiles(md_comm_t c, md_model_t m, const float* nchw, 
   if (!m->cfg.use_fov_head) MD_FAIL(MD_ERR_NO_FOV, "FOV head required for focal length");
   if (in_kind != MD_MEM_HOST && in_kind != MD_MEM_DEVICE) MD_FAIL(MD_ERR_INVALID_ARG, "unknown memory kind %d", in_kind);
   MD_HIP(hipSetDevice(c->dev->ordinal));
-  hipStream_t st = stream ? (hipStream_t)stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, (hipStream_t)stream);
   // 1. the root's image reaches every rank's staging buffer (28 MB per 1536^2 frame)
   const size_t elems = (size_t)B * 3 * H * W;
   float* x_dev = nullptr;

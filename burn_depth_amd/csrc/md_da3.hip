@@ -32,8 +32,7 @@ struct md_model_s::Da3State {
   void* hookn[4] = {0, 0, 0, 0};
   void *sp[4] = {0, 0, 0, 0}, *sr[4] = {0, 0, 0, 0}, *rn[4] = {0, 0, 0, 0}, *rnr[4] = {0, 0, 0, 0};
   void *t = nullptr, *x = nullptr, *xr = nullptr, *y = nullptr, *up = nullptr, *o = nullptr, *c1 = nullptr, *c1r = nullptr;
-  float* depth_stage = nullptr;
-  size_t depth_stage_elems = 0;
+  GrowBuf<float> depth_stage;  // device home of a host output (grow-only, md::grow)
   // ---- per-shape tables: the reference's `PosEmbedCache` (dpt.rs:784-833: UV tables built once per (C, h, w, W, H) key and
   //      kept) and burn_dino's position-embedding interpolation, keyed by the input size. `infer` takes any H x W that are
   //      multiples of the patch size (mod.rs:509-520); the first call at a new size builds its tables (host work + uploads),
@@ -67,11 +66,9 @@ struct md_model_s::Da3State {
   float* pos_aux = nullptr;
   float *conf_stage = nullptr, *aux_stage = nullptr;  // device staging when the caller wants host outputs
   // camera encoder (`infer_with_camera`): grow-only scratch = staged inputs [B*V*21] | encoded tokens [B*D] | kernel scratch
-  float* cam_enc_ws = nullptr;
-  size_t cam_enc_cap = 0;
-  // `infer_from_tokens`: caller-supplied hook tokens staged as fp32 rows [max_batch * SS + 64, din] (grow-only, zero-filled once)
-  float* tok_stage = nullptr;
-  size_t tok_stage_cap = 0;
+  GrowBuf<float> cam_enc_ws;
+  // `infer_from_tokens`: caller-supplied hook tokens staged as fp32 rows [max_batch * SS + 64, din] (grow-only, zero-filled on growth)
+  GrowBuf<float> tok_stage;
   void *up2 = nullptr, *o2 = nullptr;
   std::vector<float> main_bias, aux_bias;             // output_conv2.conv2.bias, output_conv2_aux.<last>.project.bias
   // ---- MD_PREC_FP8: the four ViT linear layers on e4m3 operands (weights per output channel, static activation scales) ----
@@ -309,19 +306,13 @@ static void da3_free_tables(md_model_s::Da3State::ShapeTables& t) {
   t = md_model_s::Da3State::ShapeTables();
 }
 
-static void da3_drop_graphs(md_model_s* m) {  // captured graphs hold workspace / table pointers of the shape they were captured at
-  for (auto& kv : m->graphs)
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-  m->graphs.clear();
-}
-
 static void da3_drop_shapes(md_model_s* m) {
   md_model_s::Da3State* d = m->da3;
   (void)hipDeviceSynchronize();
   for (auto& kv : d->shapes) da3_free_tables(kv.second);
   d->shapes.clear();
   d->tok_index = nullptr;
-  da3_drop_graphs(m);
+  m->graphs.clear();  // captured graphs hold workspace / table pointers of the shape they were captured at
 }
 
 // UV position tables, interpolated position embedding and RoPE tables of one input size (PosEmbedCache::add /
@@ -416,7 +407,7 @@ static int da3_set_shape(md_model_s* m, int H, int W, bool force) {
     }
     m->ws.cap = need;
     m->alloc_count += 1;
-    da3_drop_graphs(m);
+    m->graphs.clear();
   }
   // padding rows / channels / keys must be finite zeros for every kernel: the buffers move with the plan, so the arena is
   // cleared whenever the plan changes (a few hundred MB at HBM speed, once per change of size)
@@ -431,7 +422,7 @@ static int da3_set_shape(md_model_s* m, int H, int W, bool force) {
         if (j->second.last_use < lru->second.last_use) lru = j;
       da3_free_tables(lru->second);
       d->shapes.erase(lru);
-      da3_drop_graphs(m);
+      m->graphs.clear();
     }
     md_model_s::Da3State::ShapeTables t;
     const int st = da3_build_tables(m, t);
@@ -635,9 +626,6 @@ void da3_destroy_state(md_model_t m) {
   if (!m || !m->da3) return;
   for (auto& kv : m->da3->shapes) da3_free_tables(kv.second);
   m->da3->shapes.clear();
-  if (m->da3->depth_stage) (void)hipFree(m->da3->depth_stage);
-  if (m->da3->cam_enc_ws) (void)hipFree(m->da3->cam_enc_ws);
-  if (m->da3->tok_stage) (void)hipFree(m->da3->tok_stage);
   delete m->da3;
   m->da3 = nullptr;
 }
@@ -690,7 +678,7 @@ int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   auto body = [&]() { return da3_infer_eager(m, nchw, B, H, W, in_kind, outp, out_kind, stream); };
   if (!m->graph_enabled) return body();
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : m->dev->stream;
+  hipStream_t st = model_stream(m, stream);
   const bool eligible = nchw && !outp.tokens[0] && outp.depth && !outp.raw_logits && in_kind == MD_MEM_DEVICE && out_kind == MD_MEM_DEVICE && m->committed && B > 0 &&
                         B <= m->da3->cfg.max_batch && H == m->da3->ih && W == m->da3->iw;
   const std::vector<uintptr_t> key = {(uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw, (uintptr_t)outp.depth,
@@ -721,7 +709,7 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
   if (B > c.max_batch) MD_FAIL(MD_ERR_SHAPE, "batch %d exceeds max_batch %d", B, c.max_batch);
   MD_HIP(hipSetDevice(m->dev->ordinal));
   MD_TRY(da3_set_shape(m, H, W, false));  // any multiple of the patch size (mod.rs:509-520); a no-op at the current size
-  hipStream_t st = stream ? stream : m->dev->stream;
+  hipStream_t st = model_stream(m, stream);
   Run r{m, st, B};
   const int D = v.D, heads = v.heads, SS = d->SS, NT = d->NT, P = d->P, ph = d->ph, pw = d->pw, F = c.features;
   const int IH = d->ih, IW = d->iw;
@@ -748,15 +736,9 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
       if (!outp.tokens[hk]) MD_FAIL(MD_ERR_LEVELS, "Backbone returned fewer hooks (%d) than requested (4)", hk);
     const int start = T == P ? 0 : 1;
     const size_t need = ((size_t)c.max_batch * SS + 64) * din;
-    if (need > d->tok_stage_cap) {
-      MD_HIP(hipStreamSynchronize(st));
-      if (d->tok_stage) MD_HIP(hipFree(d->tok_stage));
-      d->tok_stage = nullptr; d->tok_stage_cap = 0;
-      MD_HIP(hipMalloc((void**)&d->tok_stage, need * 4));
-      MD_HIP(hipMemset(d->tok_stage, 0, need * 4));
-      d->tok_stage_cap = need;
-      m->alloc_count += 1;
-    }
+    bool grown = false;
+    MD_TRY(grow(m, st, d->tok_stage, need * 4, &grown));
+    if (grown) MD_HIP(hipMemset(d->tok_stage.p, 0, need * 4));
     SeqGroups tg;
     memset(&tg, 0, sizeof(tg));
     tg.ngroups = 1;
@@ -766,12 +748,12 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
     const hipMemcpyKind kind = in_kind == MD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     for (int hk = 0; hk < 4; ++hk) {
       for (int b = 0; b < B; ++b)  // patch rows of image b -> rows b*SS + 1 .. of the staging tensor (the layout the head gathers from)
-        MD_HIP(hipMemcpyAsync(d->tok_stage + ((size_t)b * SS + 1) * din, outp.tokens[hk] + ((size_t)b * T + start) * din, (size_t)P * din * 4,
+        MD_HIP(hipMemcpyAsync(d->tok_stage.p + ((size_t)b * SS + 1) * din, outp.tokens[hk] + ((size_t)b * T + start) * din, (size_t)P * din * 4,
                               kind, st));
       r.begin("layernorm");
-      MD_TRY(launch_layernorm(d->tok_stage, d->hookn[hk], (long)B * SS, din, 1e-5f, SS, tg, m->prec, 0, st));
+      MD_TRY(launch_layernorm(d->tok_stage.p, d->hookn[hk], (long)B * SS, din, 1e-5f, SS, tg, m->prec, 0, st));
       r.end();
-      if (m->taps_enabled) MD_TRY(r.tap_token_rows(("backbone_tokens_" + std::to_string(hk)).c_str(), d->tok_stage, SS, 1, P, din, din, 0));
+      if (m->taps_enabled) MD_TRY(r.tap_token_rows(("backbone_tokens_" + std::to_string(hk)).c_str(), d->tok_stage.p, SS, 1, P, din, din, 0));
     }
   } else {
   // ---- camera encoder (`infer_with_camera`, mod.rs:522-527: a model without one ignores the camera inputs) ----
@@ -781,22 +763,14 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
     if (V < 1 || V > MD_CAM_MAX_VIEWS) MD_FAIL(MD_ERR_SHAPE, "camera inputs with %d views (1..%d supported)", V, MD_CAM_MAX_VIEWS);
     const size_t n_in = (size_t)B * V * 21, n_tok = align_up((size_t)B * D, 64);
     const size_t need = align_up(n_in, 64) + n_tok + camera_encoder_scratch_floats(B, V, D);
-    if (need > d->cam_enc_cap) {
-      MD_HIP(hipStreamSynchronize(st));
-      da3_drop_graphs(m);  // graphs captured with camera inputs hold the old buffer's addresses (cam_tok, the staged inputs)
-      if (d->cam_enc_ws) MD_HIP(hipFree(d->cam_enc_ws));
-      d->cam_enc_ws = nullptr; d->cam_enc_cap = 0;
-      MD_HIP(hipMalloc((void**)&d->cam_enc_ws, need * 4));
-      d->cam_enc_cap = need;
-      m->alloc_count += 1;
-    }
+    MD_TRY(grow(m, st, d->cam_enc_ws, need * 4));
     const float *e_dev = outp.cam_extrinsics, *k_dev = outp.cam_intrinsics;
     if (in_kind == MD_MEM_HOST) {
-      MD_HIP(hipMemcpyAsync(d->cam_enc_ws, outp.cam_extrinsics, (size_t)B * V * 12 * 4, hipMemcpyHostToDevice, st));
-      MD_HIP(hipMemcpyAsync(d->cam_enc_ws + (size_t)B * V * 12, outp.cam_intrinsics, (size_t)B * V * 9 * 4, hipMemcpyHostToDevice, st));
-      e_dev = d->cam_enc_ws; k_dev = d->cam_enc_ws + (size_t)B * V * 12;
+      MD_HIP(hipMemcpyAsync(d->cam_enc_ws.p, outp.cam_extrinsics, (size_t)B * V * 12 * 4, hipMemcpyHostToDevice, st));
+      MD_HIP(hipMemcpyAsync(d->cam_enc_ws.p + (size_t)B * V * 12, outp.cam_intrinsics, (size_t)B * V * 9 * 4, hipMemcpyHostToDevice, st));
+      e_dev = d->cam_enc_ws.p; k_dev = d->cam_enc_ws.p + (size_t)B * V * 12;
     }
-    cam_tok = d->cam_enc_ws + align_up(n_in, 64);
+    cam_tok = d->cam_enc_ws.p + align_up(n_in, 64);
     CamEncW w;
     memset(&w, 0, sizeof(w));
     const std::string ce = "camera_encoder.";
@@ -1176,14 +1150,8 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
   const size_t stage_elems = out_elems * (outp.raw_logits ? c.output_dim : 1);
   float* depth_dev = outp.raw_logits ? outp.raw_logits : outp.depth;
   if (out_kind == MD_MEM_HOST) {
-    if (d->depth_stage_elems < stage_elems) {
-      if (d->depth_stage) (void)hipFree(d->depth_stage);
-      d->depth_stage = nullptr; d->depth_stage_elems = 0;
-      MD_HIP(hipMalloc((void**)&d->depth_stage, stage_elems * 4));
-      m->alloc_count += 1;
-      d->depth_stage_elems = stage_elems;
-    }
-    depth_dev = d->depth_stage;
+    MD_TRY(grow(m, st, d->depth_stage, stage_elems * 4));
+    depth_dev = d->depth_stage.p;
   }
   // ---- aux branch (build_aux_logits, dpt.rs:356-441): aux fusion pyramid on the same layerN_rn maps -> last level's 5-conv
   //      neck -> + 2 x 0.1 x UV -> reduce 3x3 -> ReLU -> project 1x1 (7 ch: 6 ray values + confidence) ----

@@ -82,6 +82,86 @@ struct TimingEntry {
   hipEvent_t a, b;
 };
 
+// The captured hipGraphs of one model, keyed by stream, shapes and every in / out pointer of a call. No captured graph may outlive
+// a device address it baked in: whatever frees or moves such an address (a staging growth, a workspace re-plan) clears the cache.
+struct GraphCache {
+  GraphCache() = default;
+  GraphCache(const GraphCache&) = delete;
+  GraphCache& operator=(const GraphCache&) = delete;
+  ~GraphCache() { clear(); }
+  void clear() {
+    for (auto& kv : entries)
+      if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+    entries.clear();
+  }
+  // `root_gen`: the root's commit_gen. Entries captured under an older generation can never be replayed again (the root clears
+  // its own cache in model_commit; a fork's cannot be reached from there)
+  void track_generation(unsigned root_gen) {
+    if (gen == root_gen) return;
+    clear();
+    gen = root_gen;
+  }
+  // Runs `body` (the launch schedule of one call) eagerly the first time `key` is seen -- that call allocates index tables and
+  // sets function attributes --, captures it into a hipGraph the second time and replays the instantiated graph from then on.
+  template <typename F>
+  int run(hipStream_t st, const std::vector<uintptr_t>& key, F&& body) {
+    {
+      Entry& e = entries[key];  // not held across body(): a body that grows a buffer clears the cache (this entry included)
+      if (e.exec) {
+        MD_HIP(hipGraphLaunch(e.exec, st));
+        return MD_OK;
+      }
+      if (e.seen++ == 0) return body();
+    }
+    MD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    const int s = body();
+    hipGraph_t g = nullptr;
+    const hipError_t ce = hipStreamEndCapture(st, &g);
+    if (s != MD_OK || ce != hipSuccess || !g) {
+      if (g) (void)hipGraphDestroy(g);
+      entries.erase(key);
+      if (s != MD_OK) return s;
+      MD_FAIL(MD_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ce));
+    }
+    hipGraphExec_t ex = nullptr;
+    const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (ie != hipSuccess || !ex) {
+      entries.erase(key);
+      MD_FAIL(MD_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+    }
+    entries[key].exec = ex;
+    MD_HIP(hipGraphLaunch(ex, st));
+    return MD_OK;
+  }
+
+ private:
+  struct Entry {
+    int seen = 0;
+    hipGraphExec_t exec = nullptr;
+  };
+  std::map<std::vector<uintptr_t>, Entry> entries;
+  unsigned gen = 0;  // the root's commit_gen the entries were captured under
+};
+
+// A model-owned grow-only buffer of device memory (or of pinned host memory: the bounce buffers between pageable caller memory and
+// the DMA engine). grow() below is its one way to (re)allocate; the owner's destructor frees it.
+template <typename T, bool Pinned = false>
+struct GrowBuf {
+  T* p = nullptr;
+  size_t cap = 0;  // bytes
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf&) = delete;
+  GrowBuf& operator=(const GrowBuf&) = delete;
+  ~GrowBuf() { release(); }
+  void release() {
+    if (p) (void)(Pinned ? hipHostFree((void*)p) : hipFree((void*)p));
+    p = nullptr;
+    cap = 0;
+  }
+};
+using PinnedBuf = GrowBuf<void, true>;
+
 }  // namespace md
 
 struct md_model_s {
@@ -144,12 +224,7 @@ struct md_model_s {
   bool ln_fold_can = false;    // 16-bit Depth Pro, D % 256 == 0: the workspace and the fold vectors exist
   float* lnfold_base = nullptr;  // root: the c / d vectors of every block (VitBlockW points into it)
   bool ln_fold_on() const { return ln_fold_can && (ln_fold_opt == 2 || ln_fold_opt == 4 || (ln_fold_opt == 1 && NT >= 256)); }  // (3: a bench diagnostic, run_vit)
-  struct GraphEntry {
-    int seen = 0;
-    hipGraphExec_t exec = nullptr;
-  };
-  std::map<std::vector<uintptr_t>, GraphEntry> graphs;  // key: stream, shapes and every in/out pointer
-  unsigned graphs_gen = 0;  // the root's commit_gen the entries of `graphs` were captured under (a fork drops them when it moves)
+  md::GraphCache graphs;
 
   // ---- md_model_fork: a fork shares the parameter / packed-weight arenas of its root model (never frees them) and
   //      owns its workspace, index tables, taps, timing, graphs and default stream ----
@@ -180,6 +255,29 @@ int model_round_weights_f16(md_model_t m);
 int model_destroy(md_model_t m);
 int model_fork(md_model_t src, md_model_t* out);
 inline md_model_s* model_root(md_model_s* m) { return m->parent ? m->parent : m; }
+// the stream of a call: the caller's, else the model's default (a fork's own stream, else the device's)
+inline hipStream_t model_stream(const md_model_s* m, hipStream_t stream) { return stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream); }
+// Grow-only staging: makes `b` hold at least `bytes`, and allocates only when it does not. hipFree is a device-wide synchronisation
+// and hipMalloc takes the allocator lock, so a steady stream of same-sized calls must not pay either. A growth first waits for `st`
+// (nothing may still read the buffer being replaced) and clears the model's captured graphs (they bake the old address); it never
+// happens inside a capture, since the eager first call of a replay key has grown every buffer the key needs. It counts in
+// md_model_query("allocs"). *grown (if given) tells whether it reallocated.
+template <typename T, bool Pinned>
+int grow(md_model_s* m, hipStream_t st, GrowBuf<T, Pinned>& b, size_t bytes, bool* grown = nullptr) {
+  if (grown) *grown = false;
+  if (b.cap >= bytes) return MD_OK;
+  MD_HIP(hipStreamSynchronize(st));
+  m->graphs.clear();
+  b.release();
+  void* p = nullptr;
+  const hipError_t e = Pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+  if (e != hipSuccess) MD_FAIL(MD_ERR_OOM, "%s(%zu) of a staging buffer failed: %s", Pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+  b.p = (T*)p;
+  b.cap = bytes;
+  m->alloc_count += 1;
+  if (grown) *grown = true;
+  return MD_OK;
+}
 // f_px non-null: the caller's focal lengths [B] (memory kind f_kind) replace the FOV network's (md_depth_pro_infer_with_focal)
 int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, float* focal,
                 float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len,

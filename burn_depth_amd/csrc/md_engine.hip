@@ -288,8 +288,6 @@ using namespace md;
 // ------------------------------------------------------------------------------------------------
 struct md_model_s::Buffers {
   float* xin = nullptr;       // [B,3,S,S] fp32 (resized / staged input)
-  float* xraw = nullptr;      // staged raw input when it arrives on the host or needs resizing
-  uint8_t* rgb = nullptr;     // staged RGB bytes
   void* patches = nullptr;    // [nseq_p*P, Kpe] T
   float* xres = nullptr;      // [nseq*SS, D] fp32 residual stream
   void* xn = nullptr;         // [nseq*SS, D] T
@@ -318,20 +316,17 @@ struct md_model_s::Buffers {
   void *h0 = nullptr, *h1 = nullptr;
   float* canonical = nullptr;  // [B, S*S]
   float* inv = nullptr;        // [B, S*S] (resize path)
-  float* depth_stage = nullptr;  // device staging for host outputs [B, Hmax*Wmax]
-  // grow-only capacities (bytes) of the staging buffers that serve host pointers and non-native input sizes, and the pinned
-  // bounce buffers between pageable caller memory and the DMA engine: a steady stream of same-sized calls allocates nothing
-  size_t rgb_cap = 0, xraw_cap = 0;
-  void *pin_in = nullptr, *pin_out = nullptr;
-  size_t pin_in_cap = 0, pin_out_cap = 0;
-  // the caller's focal lengths of a known-focal call from host memory: device copy [B] and its own pinned bounce buffer
-  float* fpx = nullptr;
-  void* pin_fpx = nullptr;
-  size_t fpx_cap = 0, pin_fpx_cap = 0;
   // fov
   float *fovproj = nullptr, *fv0 = nullptr, *fv1 = nullptr, *fv2 = nullptr, *fv3 = nullptr, *fvr = nullptr;
   float *fov_deg = nullptr, *focal = nullptr, *fovy = nullptr, *ratio = nullptr;
-  size_t depth_stage_elems = 0;
+  // grow-only staging that serves host pointers and non-native input sizes (md::grow)
+  md::GrowBuf<float> xraw;         // raw input when it arrives on the host or needs resizing
+  md::GrowBuf<uint8_t> rgb;        // RGB bytes
+  md::GrowBuf<float> depth_stage;  // device home of a host depth output [B, H*W]
+  md::PinnedBuf pin_in, pin_out;   // bounce buffers between pageable caller memory and the DMA engine
+  // the caller's focal lengths of a known-focal call from host memory: device copy [B] and its own pinned bounce buffer
+  md::GrowBuf<float> fpx;
+  md::PinnedBuf pin_fpx;
 };
 
 namespace md {
@@ -674,8 +669,7 @@ int model_destroy(md_model_t m) {
   if (m->ws.base) (void)hipFree(m->ws.base);
   if (m->zero_page) (void)hipFree(m->zero_page);
   for (auto& kv : m->index_tables) (void)hipFree(kv.second);
-  for (auto& kv : m->graphs)
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+  m->graphs.clear();
   for (auto& kv : m->taps) (void)hipFree(kv.second.dev);
   for (auto& t : m->timing) {
     (void)hipEventDestroy(t.a);
@@ -683,16 +677,7 @@ int model_destroy(md_model_t m) {
   }
   if (m->da3) da3_destroy_state(m);
   if (m->frame) frame_destroy_state(m);
-  if (m->buf) {
-    if (m->buf->xraw) (void)hipFree(m->buf->xraw);
-    if (m->buf->rgb) (void)hipFree(m->buf->rgb);
-    if (m->buf->depth_stage) (void)hipFree(m->buf->depth_stage);
-    if (m->buf->pin_in) (void)hipHostFree(m->buf->pin_in);
-    if (m->buf->pin_out) (void)hipHostFree(m->buf->pin_out);
-    if (m->buf->fpx) (void)hipFree(m->buf->fpx);
-    if (m->buf->pin_fpx) (void)hipHostFree(m->buf->pin_fpx);
-    delete m->buf;
-  }
+  delete m->buf;
   delete m;
   return MD_OK;
 }
@@ -897,8 +882,6 @@ int model_commit(md_model_t m) {
   if (composed) MD_HIP(hipFree(composed));
   if (m->kind == 1) MD_TRY(da3_on_commit(m));
   // captured graphs bake by-value launch parameters (the head's output bias, the split-half term count): none survives a commit
-  for (auto& kv : m->graphs)
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
   m->graphs.clear();
   m->commit_gen += 1;
   m->committed = true;
@@ -1473,7 +1456,7 @@ int model_decoder_from_features(md_model_t m, const md_nchw_view* features, int 
     max_elems = std::max(max_elems, (size_t)B * v.channels * v.height * v.width);
   }
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, stream);
   md_model_s::Buffers* b = m->buf;
   DeviceScratch stage;
   if (in_kind == MD_MEM_HOST) MD_TRY(stage.alloc(max_elems * 4));
@@ -1505,7 +1488,7 @@ int model_head_debug(md_model_t m, const md_nchw_view* feature, int B, int in_ki
     MD_FAIL(MD_ERR_SHAPE, "feature is [B,%d,%d,%d]; this model's head takes [B,%d,%d,%d]", feature->channels, feature->height, feature->width, F, s0, s0);
   if (!PK(m, "head.conv1.weight")) MD_FAIL(MD_ERR_UNSUPPORTED, "head_debug: the un-fused conv1 operand is not packed");
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, stream);
   md_model_s::Buffers* b = m->buf;
   const size_t px1 = (size_t)B * 4 * s0 * s0;
   const size_t map_bytes = align_up(px1 * C1p * m->esz * m->xm + 256, 256);
@@ -1659,42 +1642,16 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
                              float* fovx, float* fovy, int out_kind, hipStream_t stream, const uint8_t* rgb, size_t rgb_len,
                              const float* f_px, int f_kind, const ShardPlan* sp = nullptr);
 
-// Grow-only staging: (re)allocates only when `need` exceeds the capacity. hipFree is a device-wide synchronisation and
-// hipMalloc takes the allocator lock, so a caller that feeds host pointers or a fixed non-native size (the reference's
-// `infer_from_rgb` path, src/inference.rs:128-137; the auto-resize of mod.rs:312-325) must not pay either per call.
-// md_model_query("allocs") counts what the infer calls of a model have allocated.
-static int ensure_device(md_model_s* m, void** p, size_t* cap, size_t need) {
-  if (*cap >= need && *p) return MD_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  MD_HIP(hipMalloc(p, need));
-  *cap = need;
-  m->alloc_count += 1;
-  return MD_OK;
-}
-static int ensure_pinned(md_model_s* m, void** p, size_t* cap, size_t need) {
-  if (*cap >= need && *p) return MD_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  MD_HIP(hipHostMalloc(p, need, hipHostMallocDefault));
-  *cap = need;
-  m->alloc_count += 1;
-  return MD_OK;
-}
 // pageable caller memory -> pinned bounce buffer -> device, asynchronously on `st` (the bounce buffer is reused by the next
 // call, which first waits for this stream's work: one in-flight infer per model, see the threading rule in mi_depth.h)
 // (the input's bounce buffer by default; the caller's focal lengths travel through one of their own)
 static int stage_host_to_device(md_model_s* m, void* dst_dev, const void* src_host, size_t bytes, hipStream_t st,
-                                void** pin = nullptr, size_t* pin_cap = nullptr) {
-  md_model_s::Buffers* b = m->buf;
-  if (!pin) { pin = &b->pin_in; pin_cap = &b->pin_in_cap; }
-  if (*pin_cap < bytes) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
-  MD_TRY(ensure_pinned(m, pin, pin_cap, bytes));
+                                PinnedBuf* pin = nullptr) {
+  if (!pin) pin = &m->buf->pin_in;
+  MD_TRY(grow(m, st, *pin, bytes));
   MD_HIP(hipStreamSynchronize(st));  // the previous call's copy out of the bounce buffer has finished
-  memcpy(*pin, src_host, bytes);
-  MD_HIP(hipMemcpyAsync(dst_dev, *pin, bytes, hipMemcpyHostToDevice, st));
+  memcpy(pin->p, src_host, bytes);
+  MD_HIP(hipMemcpyAsync(dst_dev, pin->p, bytes, hipMemcpyHostToDevice, st));
   return MD_OK;
 }
 
@@ -1707,19 +1664,13 @@ int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kin
   };
   if (!m->graph_enabled) return body();
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, stream);
   const bool eligible = nchw && !rgb && in_kind == MD_MEM_DEVICE && out_kind == MD_MEM_DEVICE && model_root(m)->committed && B > 0 &&
                         B <= m->cfg.max_batch && H == m->S && W == m->S && (!f_px || f_kind == MD_MEM_DEVICE);
   // the commit generation of the weights is part of the key: a graph bakes by-value launch parameters (the head's output
   // bias, the split-half term count), and a fork's graphs cannot be reached from the root's commit. The focal-length pointer is
   // too: a graph with the FOV network never replays a known-focal call, nor the reverse (its values are read at run time).
   const unsigned gen = model_root(m)->commit_gen;
-  if (m->graphs_gen != gen) {  // a fork's graphs of an older commit can never be replayed again (the root clears its own in model_commit)
-    for (auto& kv : m->graphs)
-      if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    m->graphs.clear();
-    m->graphs_gen = gen;
-  }
   const std::vector<uintptr_t> key = {(uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw, (uintptr_t)depth,
                                       (uintptr_t)focal, (uintptr_t)fovx, (uintptr_t)fovy, (uintptr_t)gen, (uintptr_t)f_px};
   return run_with_graph(m, st, key, eligible, body);
@@ -1732,25 +1683,23 @@ int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, flo
 int model_stage_rgb(md_model_t m, const uint8_t* rgb, size_t bytes, hipStream_t st, const uint8_t** dev) {
   if (!m->buf) m->buf = new md_model_s::Buffers();  // a Depth-Anything-v3 model stages through the same grow-only buffers
   md_model_s::Buffers* b = m->buf;
-  if (b->rgb_cap < bytes) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
-  MD_TRY(ensure_device(m, (void**)&b->rgb, &b->rgb_cap, bytes));
-  MD_TRY(stage_host_to_device(m, b->rgb, rgb, bytes, st));
-  *dev = (const uint8_t*)b->rgb;
+  MD_TRY(grow(m, st, b->rgb, bytes));
+  MD_TRY(stage_host_to_device(m, b->rgb.p, rgb, bytes, st));
+  *dev = b->rgb.p;
   return MD_OK;
 }
 
 int model_stage_input(md_model_t m, const float* nchw, size_t elems, int in_kind, hipStream_t stream, float** dev) {
   if (!m || !dev || elems == 0) MD_FAIL(MD_ERR_INVALID_ARG, "model_stage_input: null argument");
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, stream);
   md_model_s::Buffers* b = m->buf;
-  if (b->xraw_cap < elems * 4) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
-  MD_TRY(ensure_device(m, (void**)&b->xraw, &b->xraw_cap, elems * 4));
+  MD_TRY(grow(m, st, b->xraw, elems * 4));
   if (nchw) {
-    if (in_kind == MD_MEM_HOST) MD_TRY(stage_host_to_device(m, b->xraw, nchw, elems * 4, st));
-    else MD_HIP(hipMemcpyAsync(b->xraw, nchw, elems * 4, hipMemcpyDeviceToDevice, st));
+    if (in_kind == MD_MEM_HOST) MD_TRY(stage_host_to_device(m, b->xraw.p, nchw, elems * 4, st));
+    else MD_HIP(hipMemcpyAsync(b->xraw.p, nchw, elems * 4, hipMemcpyDeviceToDevice, st));
   }
-  *dev = b->xraw;
+  *dev = b->xraw.p;
   return MD_OK;
 }
 
@@ -1780,15 +1729,14 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
     for (int i = 0; i < B; ++i)
       if (!std::isfinite(f_px[i]) || !(f_px[i] > 0.f)) MD_FAIL(MD_ERR_INVALID_ARG, "f_px[%d] = %g: a focal length must be finite and > 0", i, (double)f_px[i]);
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, stream);
   md_model_s::Buffers* b = m->buf;
   Run r{m, st, B};
   const float* fpx_dev = f_px;
   if (known_focal && f_kind == MD_MEM_HOST) {  // grow-only device copy through its own pinned bounce buffer (before the input's)
-    if (b->fpx_cap < (size_t)B * 4) MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
-    MD_TRY(ensure_device(m, (void**)&b->fpx, &b->fpx_cap, (size_t)B * 4));
-    MD_TRY(stage_host_to_device(m, b->fpx, f_px, (size_t)B * 4, st, &b->pin_fpx, &b->pin_fpx_cap));
-    fpx_dev = b->fpx;
+    MD_TRY(grow(m, st, b->fpx, (size_t)B * 4));
+    MD_TRY(stage_host_to_device(m, b->fpx.p, f_px, (size_t)B * 4, st, &b->pin_fpx));
+    fpx_dev = b->fpx.p;
   }
   const int S = m->S;
   const size_t in_elems = (size_t)B * 3 * H * W;
@@ -1799,14 +1747,14 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
     if (rgb_len != (size_t)W * H * 3) MD_FAIL(MD_ERR_SHAPE, "expected %zu RGB bytes for %dx%d, got %zu", (size_t)W * H * 3, W, H, rgb_len);
     const uint8_t* rgb_dev = rgb;
     if (in_kind == MD_MEM_HOST) {
-      MD_TRY(ensure_device(m, (void**)&b->rgb, &b->rgb_cap, rgb_len));
-      MD_TRY(stage_host_to_device(m, b->rgb, rgb, rgb_len, st));
-      rgb_dev = b->rgb;
+      MD_TRY(grow(m, st, b->rgb, rgb_len));
+      MD_TRY(stage_host_to_device(m, b->rgb.p, rgb, rgb_len, st));
+      rgb_dev = b->rgb.p;
     }
     float* dst = b->xin;
     if (resize_needed) {
-      MD_TRY(ensure_device(m, (void**)&b->xraw, &b->xraw_cap, in_elems * 4));
-      dst = b->xraw;
+      MD_TRY(grow(m, st, b->xraw, in_elems * 4));
+      dst = b->xraw.p;
     }
     r.begin("rgb_to_input");
     MD_TRY(launch_rgb_to_input(rgb_dev, W, H, dst, st));
@@ -1815,8 +1763,8 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
   } else if (in_kind == MD_MEM_HOST) {
     float* dst = b->xin;
     if (resize_needed) {
-      MD_TRY(ensure_device(m, (void**)&b->xraw, &b->xraw_cap, in_elems * 4));
-      dst = b->xraw;
+      MD_TRY(grow(m, st, b->xraw, in_elems * 4));
+      dst = b->xraw.p;
     }
     MD_TRY(stage_host_to_device(m, dst, nchw, in_elems * 4, st));
     x_dev = dst;
@@ -1914,10 +1862,8 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
     if (out_kind == MD_MEM_DEVICE) {
       depth_dev = depth;
     } else {
-      size_t cap = b->depth_stage_elems * 4;
-      MD_TRY(ensure_device(m, (void**)&b->depth_stage, &cap, out_elems * 4));
-      b->depth_stage_elems = cap / 4;
-      depth_dev = b->depth_stage;
+      MD_TRY(grow(m, st, b->depth_stage, out_elems * 4));
+      depth_dev = b->depth_stage.p;
     }
     r.begin("depth_post");
     if (!resize_needed) {
@@ -1935,8 +1881,8 @@ static int model_infer_eager(md_model_t m, const float* nchw, int B, int H, int 
     // host outputs: one pinned bounce buffer [depth | focal | fovx | fovy], asynchronous device -> pinned copies, ONE stream
     // synchronisation, then plain memcpy into the caller's (pageable) memory
     const size_t dbytes = depth ? out_elems * 4 : 0, need = dbytes + 3 * (size_t)B * 4;
-    MD_TRY(ensure_pinned(m, &b->pin_out, &b->pin_out_cap, need));
-    char* ph = (char*)b->pin_out;
+    MD_TRY(grow(m, st, b->pin_out, need));
+    char* ph = (char*)b->pin_out.p;
     if (depth) MD_HIP(hipMemcpyAsync(ph, depth_dev, dbytes, hipMemcpyDeviceToHost, st));
     const float* srcs[3] = {b->focal, b->fov_deg, b->fovy};
     float* dsts[3] = {focal, fovx, fovy};

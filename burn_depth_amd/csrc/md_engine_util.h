@@ -158,40 +158,14 @@ inline void add_pack_deconv_pair(md_model_s* m, const std::string& name, const s
   m->packs.push_back(e);
 }
 
-// Runs `body` (the launch schedule of one infer) eagerly the first time a (stream, shapes, pointers) key is
-// seen -- that call allocates index tables and sets function attributes --, captures it into a hipGraph the second
-// time and replays the instantiated graph from then on. Timing / tap modes and host-side buffers always run eagerly.
+// The graph layer of an infer entry: `body` through the model's GraphCache when graphs are on and the call is `eligible`. Timing /
+// tap modes and calls with host-side buffers always run eagerly.
 template <typename F>
 inline int run_with_graph(md_model_s* m, hipStream_t st, const std::vector<uintptr_t>& key, bool eligible, F&& body) {
-  if (!m->graph_enabled || !eligible || m->timing_enabled || m->taps_enabled) return body();
-  {
-    md_model_s::GraphEntry& e = m->graphs[key];  // not held across body(): a body that regrows a buffer drops every graph (and this entry)
-    if (e.exec) {
-      MD_HIP(hipGraphLaunch(e.exec, st));
-      return MD_OK;
-    }
-    if (e.seen++ == 0) return body();
-  }
-  MD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-  const int s = body();
-  hipGraph_t g = nullptr;
-  const hipError_t ce = hipStreamEndCapture(st, &g);
-  if (s != MD_OK || ce != hipSuccess || !g) {
-    if (g) (void)hipGraphDestroy(g);
-    m->graphs.erase(key);
-    if (s != MD_OK) return s;
-    MD_FAIL(MD_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ce));
-  }
-  hipGraphExec_t ex = nullptr;
-  const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ie != hipSuccess || !ex) {
-    m->graphs.erase(key);
-    MD_FAIL(MD_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-  }
-  m->graphs[key].exec = ex;
-  MD_HIP(hipGraphLaunch(ex, st));
-  return MD_OK;
+  if (!m->graph_enabled) return body();
+  m->graphs.track_generation(model_root(m)->commit_gen);
+  if (!eligible || m->timing_enabled || m->taps_enabled) return body();
+  return m->graphs.run(st, key, body);
 }
 
 struct Run {
@@ -215,47 +189,46 @@ struct Run {
     (void)hipEventRecord(m->timing[pending].b, st);
     pending = -1;
   }
-  // NHWC T tensor -> NCHW fp32 tap
-  int tap_nhwc(const char* name, const void* p, int C, int H, int W, long ld, int coff = 0) {
-    if (!m->taps_enabled) return MD_OK;
+  // the tap `name` holding n floats: reallocated at exactly n when the count changes (debug memory, not counted in alloc_count)
+  int sized_tap(const char* name, size_t n, Tap** out) {
     Tap& t = m->taps[name];
-    const size_t n = (size_t)B * C * H * W;
     if (t.count != n) {
       if (t.dev) (void)hipFree(t.dev);
+      t.dev = nullptr;
+      t.count = 0;
       MD_HIP(hipMalloc((void**)&t.dev, n * 4));
       t.count = n;
     }
-    t.dims[0] = B; t.dims[1] = C; t.dims[2] = H; t.dims[3] = W;
-    return launch_nhwc_to_nchw(p, B, C, H, W, ld, coff, t.dev, m->prec, st);
+    *out = &t;
+    return MD_OK;
+  }
+  // NHWC T tensor -> NCHW fp32 tap
+  int tap_nhwc(const char* name, const void* p, int C, int H, int W, long ld, int coff = 0) {
+    if (!m->taps_enabled) return MD_OK;
+    Tap* t = nullptr;
+    MD_TRY(sized_tap(name, (size_t)B * C * H * W, &t));
+    t->dims[0] = B; t->dims[1] = C; t->dims[2] = H; t->dims[3] = W;
+    return launch_nhwc_to_nchw(p, B, C, H, W, ld, coff, t->dev, m->prec, st);
   }
   // token rows of an fp32 [B*S, width] tensor -> tap [B, nrows, dst_width] columns [coff, coff + width): rows row0 .. row0+nrows of
   // every sequence (the patch tokens of a hook, depth_anything3/mod.rs:344-347). Call once per column block.
   int tap_token_rows(const char* name, const float* src, int S, int row0, int nrows, int width, int dst_width, int coff) {
     if (!m->taps_enabled) return MD_OK;
-    Tap& t = m->taps[name];
-    const size_t n = (size_t)B * nrows * dst_width;
-    if (t.count != n) {
-      if (t.dev) (void)hipFree(t.dev);
-      MD_HIP(hipMalloc((void**)&t.dev, n * 4));
-      t.count = n;
-    }
-    t.dims[0] = B; t.dims[1] = nrows; t.dims[2] = dst_width; t.dims[3] = 0;
+    Tap* t = nullptr;
+    MD_TRY(sized_tap(name, (size_t)B * nrows * dst_width, &t));
+    t->dims[0] = B; t->dims[1] = nrows; t->dims[2] = dst_width; t->dims[3] = 0;
     for (int b = 0; b < B; ++b)
-      MD_HIP(hipMemcpy2DAsync(t.dev + ((size_t)b * nrows) * dst_width + coff, (size_t)dst_width * 4, src + ((size_t)b * S + row0) * width,
+      MD_HIP(hipMemcpy2DAsync(t->dev + ((size_t)b * nrows) * dst_width + coff, (size_t)dst_width * 4, src + ((size_t)b * S + row0) * width,
                               (size_t)width * 4, (size_t)width * 4, (size_t)nrows, hipMemcpyDeviceToDevice, st));
     return MD_OK;
   }
   int tap_f32(const char* name, const float* p, int64_t d0, int64_t d1, int64_t d2, int64_t d3) {
     if (!m->taps_enabled) return MD_OK;
-    Tap& t = m->taps[name];
     const size_t n = (size_t)d0 * std::max<int64_t>(d1, 1) * std::max<int64_t>(d2, 1) * std::max<int64_t>(d3, 1);
-    if (t.count != n) {
-      if (t.dev) (void)hipFree(t.dev);
-      MD_HIP(hipMalloc((void**)&t.dev, n * 4));
-      t.count = n;
-    }
-    t.dims[0] = d0; t.dims[1] = d1; t.dims[2] = d2; t.dims[3] = d3;
-    MD_HIP(hipMemcpyAsync(t.dev, p, n * 4, hipMemcpyDeviceToDevice, st));
+    Tap* t = nullptr;
+    MD_TRY(sized_tap(name, n, &t));
+    t->dims[0] = d0; t->dims[1] = d1; t->dims[2] = d2; t->dims[3] = d3;
+    MD_HIP(hipMemcpyAsync(t->dev, p, n * 4, hipMemcpyDeviceToDevice, st));
     return MD_OK;
   }
 };

@@ -23,25 +23,15 @@ struct AxisTable {
 
 }  // namespace md
 
-// Tap tables are never freed before the model: a captured graph bakes their addresses. The scratch buffers grow only; a
-// growth drops every captured graph of the model (they bake the old addresses) -- only an eager call grows them.
+// Tap tables are never freed before the model: a captured graph bakes their addresses. The scratch buffers grow only (md::grow).
 struct md_model_s::FrameState {
   std::map<std::pair<int, int>, md::AxisTable> tables;  // (in_len, out_len); out_len 0 = the identity (crop-only) table of in_len
-  float* nchw = nullptr;
-  size_t nchw_cap = 0;
-  float* tmp = nullptr;
-  size_t tmp_cap = 0;
-  float* depth = nullptr;
-  size_t depth_cap = 0;
-  float2* parts = nullptr;
-  size_t parts_cap = 0;
+  md::GrowBuf<float> nchw, tmp, depth;
+  md::GrowBuf<float2> parts;
   // device homes of outputs the caller wants in host memory
-  void* display = nullptr;
-  size_t display_cap = 0;
-  uint8_t* prepared = nullptr;
-  size_t prepared_cap = 0;
-  float* small = nullptr;  // range [B,2] | focal [B] | fovy [B]
-  size_t small_cap = 0;
+  md::GrowBuf<void> display;
+  md::GrowBuf<uint8_t> prepared;
+  md::GrowBuf<float> small;  // range [B,2] | focal [B] | fovy [B]
 };
 
 namespace md {
@@ -53,31 +43,8 @@ void frame_destroy_state(md_model_t m) {
     if (kv.second.win) (void)hipFree(kv.second.win);
     if (kv.second.w) (void)hipFree(kv.second.w);
   }
-  void* bufs[] = {f->nchw, f->tmp, f->depth, f->parts, f->display, f->prepared, f->small};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
   delete f;
   m->frame = nullptr;
-}
-
-static void drop_graphs(md_model_s* m) {
-  for (auto& kv : m->graphs)
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-  m->graphs.clear();
-}
-
-// grow-only device scratch of the frame path
-static int frame_ensure(md_model_s* m, hipStream_t st, void** p, size_t* cap, size_t bytes) {
-  if (*p && *cap >= bytes) return MD_OK;
-  MD_HIP(hipStreamSynchronize(st));  // nothing may still read the buffer being replaced
-  drop_graphs(m);
-  if (*p) MD_HIP(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, bytes) != hipSuccess) MD_FAIL(MD_ERR_OOM, "hipMalloc(%zu) for the frame path failed", bytes);
-  *cap = bytes;
-  m->alloc_count += 1;
-  return MD_OK;
 }
 
 // host tables of one axis: Catmull-Rom (out_len > 0) or the identity of a crop (out_len == 0)
@@ -221,40 +188,40 @@ static int frame_eager(md_model_s* m, const uint8_t* rgb, int B, int w, int h, i
   const size_t in_bytes = (size_t)B * h * w * 3, tpx = (size_t)B * p.th * p.tw, opx = (size_t)B * p.oh * p.ow;
   const size_t disp_bytes = opx * (o.format == MD_FRAME_U8_GRAY ? 1 : 16);
   // ---- device homes (grow-only, before anything is enqueued) ----
-  MD_TRY(frame_ensure(m, st, (void**)&f->nchw, &f->nchw_cap, tpx * 3 * 4));
+  MD_TRY(grow(m, st, f->nchw, tpx * 3 * 4));
   float* depth = out.depth;
   if (!depth || host_out) {
-    MD_TRY(frame_ensure(m, st, (void**)&f->depth, &f->depth_cap, tpx * 4));
-    depth = f->depth;
+    MD_TRY(grow(m, st, f->depth, tpx * 4));
+    depth = f->depth.p;
   }
   void* display = out.display;
   uint8_t* prepared = out.prepared;
   float *range = out.depth_range, *focal = out.focallength_px, *fovy = out.fovy_rad;
   if (host_out) {
     if (display) {
-      MD_TRY(frame_ensure(m, st, &f->display, &f->display_cap, disp_bytes));
-      display = f->display;
+      MD_TRY(grow(m, st, f->display, disp_bytes));
+      display = f->display.p;
     }
     if (prepared) {
-      MD_TRY(frame_ensure(m, st, (void**)&f->prepared, &f->prepared_cap, tpx * 3));
-      prepared = f->prepared;
+      MD_TRY(grow(m, st, f->prepared, tpx * 3));
+      prepared = f->prepared.p;
     }
     if (range || focal || fovy) {
-      MD_TRY(frame_ensure(m, st, (void**)&f->small, &f->small_cap, (size_t)B * 4 * 4));
-      range = range ? f->small : nullptr;
-      focal = focal ? f->small + 2 * B : nullptr;
-      fovy = fovy ? f->small + 3 * B : nullptr;
+      MD_TRY(grow(m, st, f->small, (size_t)B * 4 * 4));
+      range = range ? f->small.p : nullptr;
+      focal = focal ? f->small.p + 2 * B : nullptr;
+      fovy = fovy ? f->small.p + 3 * B : nullptr;
     }
   }
   const DisplayGeom g = display_geom(B, p.th, p.tw, 0, 0, p.tw, p.th, p.ow, p.oh);
-  if (o.normalize || range) MD_TRY(frame_ensure(m, st, (void**)&f->parts, &f->parts_cap, (size_t)B * display_parts(g) * sizeof(float2)));
+  if (o.normalize || range) MD_TRY(grow(m, st, f->parts, (size_t)B * display_parts(g) * sizeof(float2)));
   const AxisTable *av = nullptr, *ah = nullptr;
   int xb0 = 0, nq = 0;
   if (m->kind == 1) {
     MD_TRY(frame_axis(m, h, p.resize ? p.sh : 0, &av));
     MD_TRY(frame_axis(m, w, p.resize ? p.sw : 0, &ah));
     catmull_rom_span(ah->left.data(), ah->count.data(), p.cx, p.tw, &xb0, &nq);
-    MD_TRY(frame_ensure(m, st, (void**)&f->tmp, &f->tmp_cap, (size_t)B * p.th * nq * 16));
+    MD_TRY(grow(m, st, f->tmp, (size_t)B * p.th * nq * 16));
   }
   // ---- the frame on the device ----
   const uint8_t* src = rgb;
@@ -264,20 +231,20 @@ static int frame_eager(md_model_s* m, const uint8_t* rgb, int B, int w, int h, i
   if (m->kind == 1) {
     r.begin("frame_prepare");
     MD_TRY(launch_resize_catmull_rom(src, B, h, w, CrAxis{av->win, av->w, av->maxc}, p.cy, p.th, CrAxis{ah->win, ah->w, ah->maxc}, p.cx,
-                                     p.tw, xb0, nq, f->tmp, prepared, f->nchw, st));
+                                     p.tw, xb0, nq, f->tmp.p, prepared, f->nchw.p, st));
     r.end();
-    MD_TRY(da3_infer_direct(m, f->nchw, B, p.th, p.tw, depth, st));
+    MD_TRY(da3_infer_direct(m, f->nchw.p, B, p.th, p.tw, depth, st));
   } else {
     r.begin("frame_prepare");
     for (int b = 0; b < B; ++b)  // rgb_to_input_tensor per frame (what md_infer_from_rgb runs)
-      MD_TRY(launch_rgb_to_input(src + (size_t)b * h * w * 3, w, h, f->nchw + (size_t)b * 3 * h * w, st));
+      MD_TRY(launch_rgb_to_input(src + (size_t)b * h * w * 3, w, h, f->nchw.p + (size_t)b * 3 * h * w, st));
     if (prepared) MD_HIP(hipMemcpyAsync(prepared, src, in_bytes, hipMemcpyDeviceToDevice, st));
     r.end();
-    MD_TRY(model_infer_direct(m, f->nchw, B, h, w, depth, focal, fovy, st));
+    MD_TRY(model_infer_direct(m, f->nchw.p, B, h, w, depth, focal, fovy, st));
   }
   // ---- display ----
   r.begin("frame_display");
-  MD_TRY(launch_depth_display(depth, g, o.normalize, o.format, display, range, f->parts, st));
+  MD_TRY(launch_depth_display(depth, g, o.normalize, o.format, display, range, f->parts.p, st));
   r.end();
   if (!host_out) return MD_OK;
   auto d2h = [&](void* dst, const void* srcp, size_t bytes) -> int {
@@ -311,16 +278,12 @@ int process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_
   FramePlan p;
   MD_TRY(frame_plan(m, w, h, *o, &p));
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  hipStream_t st = stream ? stream : (m->own_stream ? m->own_stream : m->dev->stream);
+  hipStream_t st = model_stream(m, stream);
   auto body = [&]() { return frame_eager(m, rgb, B, w, h, in_kind, *o, p, *out, out_kind, st); };
   if (!m->graph_enabled) return body();
   // the key: stream, frame size, every option, every pointer and the commit generation (a graph bakes the weights' by-value
   // launch parameters); a Depth-Anything-v3 graph only replays at the model's current input size (its workspace plan)
   const unsigned gen = model_root(m)->commit_gen;
-  if (m->graphs_gen != gen) {  // graphs of an older commit can never be replayed again
-    drop_graphs(m);
-    m->graphs_gen = gen;
-  }
   bool eligible = in_kind == MD_MEM_DEVICE && out_kind == MD_MEM_DEVICE;
   if (m->kind == 1) {
     int ps = 0, ch = 0, cw = 0;

@@ -989,6 +989,60 @@ def test_host_pointer_path_allocates_nothing_after_the_first_call(dev):
     m.destroy()
 
 
+@pytest.mark.gpu
+def test_staging_growth_between_replayed_calls_keeps_them_exact(dev):
+    """Every grow-only staging buffer waits for the stream and clears the model's captured graphs when it grows. A host-pointer
+    call at a non-native size between replayed device calls grows xraw, the depth staging and the pinned bounce buffers; the
+    device calls around it (eager, capture, replay) stay bit-identical to an eager twin, and only the growing call allocates."""
+    import ctypes as C
+    import numpy as np
+    from burn_depth_amd import _lib, weights as Wt
+    from burn_depth_amd.config import DepthProConfig
+    from burn_depth_amd.depth_pro import DepthPro
+    m = DepthPro.new(dev, DepthProConfig.tiny_test(), seed=0, init_scheme=Wt.INIT_PARITY)
+    twin = DepthPro.new(dev, DepthProConfig.tiny_test(), seed=0, init_scheme=Wt.INIT_PARITY)
+    lib = _lib.load()
+    torch.manual_seed(7)
+    x = torch.randn(1, 3, 512, 512, device="cuda")
+    want = twin.infer(x)
+    bufs = [torch.empty(1, 512, 512, device="cuda")] + [torch.empty(1, device="cuda") for _ in range(3)]
+
+    def device_call(it):
+        for b in bufs:
+            b.fill_(-1.0)
+        m.infer_into(x, *bufs)
+        torch.cuda.synchronize()
+        assert torch.equal(bufs[0], want.depth) and torch.equal(bufs[1], want.focallength_px), it
+        assert torch.equal(bufs[2], want.fovx_deg) and torch.equal(bufs[3], want.fovy_rad), it
+
+    H, W = 400, 600
+    xh = np.random.default_rng(7).standard_normal((1, 3, H, W)).astype(np.float32)
+
+    def host_call(model):
+        depth = np.full((1, H, W), -1.0, np.float32)
+        focal, fovx, fovy = (np.zeros(1, np.float32) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _lib.check(lib.md_depth_pro_infer(model._h, p(xh), 1, H, W, _lib.MD_MEM_HOST, p(depth), p(focal), p(fovx), p(fovy),
+                                          _lib.MD_MEM_HOST, None))
+        return depth, focal, fovx, fovy
+
+    m.enable_graph(True)
+    device_call(0)  # eager (builds the index table of B = 1)
+    a0 = m.query("allocs")
+    for it in (1, 2):  # capture, replay
+        device_call(it)
+    assert m.query("allocs") == a0
+    got = host_call(m)
+    a1 = m.query("allocs")
+    assert a1 > a0, "the host-pointer call at a new size must grow the staging"
+    assert all(np.array_equal(g, w) for g, w in zip(got, host_call(twin)))
+    for it in (3, 4, 5):  # the growth cleared the graphs: eager, capture, replay again
+        device_call(it)
+    assert m.query("allocs") == a1
+    twin.destroy()
+    m.destroy()
+
+
 def test_graph_replay_sees_recommitted_weights_on_root_and_fork(dev):
     """A captured graph bakes by-value launch parameters (the head's output bias); the commit generation is part of the replay
     key, so set_tensor + commit is seen by the root's AND a fork's next replayed call."""
