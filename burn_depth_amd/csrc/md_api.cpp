@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "md_engine.h"
+#include "md_engine_util.h"
 
 using namespace md;
 
@@ -684,22 +685,7 @@ int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int hea
     MD_HIP(hipStreamSynchronize(st));  // `redo` is released at the end of this scope
   } else {
     MD_TRY(sc.alloc((size_t)T * heads * SS * kpad * 4));
-    GemmParams p;
-    p.N = SS; p.K = 64; p.ngroups = 1; p.g_rows[0] = N;
-    p.batch = T * heads; p.batch_inner = heads;
-    p.A = qk.p; p.lda = 2 * D; p.a_bs[0] = (long)SS * 2 * D; p.a_bs[1] = 64;
-    p.W[0] = (const float*)qk.p + D; p.ldw = 2 * D; p.w_bs[0] = (long)SS * 2 * D; p.w_bs[1] = 64;
-    p.epi = EPI_STORE; p.out_f32 = 1; p.out = sc.p; p.ldo = kpad;
-    p.o_bs[0] = (long)heads * SS * kpad; p.o_bs[1] = (long)SS * kpad;
-    MD_TRY(launch_gemm(p, A_DENSE, precision, TILE_128x128, st));
-    MD_TRY(launch_softmax_rows((float*)sc.p, (long)T * heads * SS, N, kpad, 0.125f, st));
-    GemmParams q;
-    q.N = 64; q.K = kpad; q.ngroups = 1; q.g_rows[0] = N;
-    q.batch = T * heads; q.batch_inner = heads;
-    q.A = sc.p; q.lda = kpad; q.a_bs[0] = (long)heads * SS * kpad; q.a_bs[1] = (long)SS * kpad;
-    q.W[0] = vT.p; q.ldw = kpad; q.w_bs[0] = (long)heads * 64 * kpad; q.w_bs[1] = 64L * kpad;
-    q.epi = EPI_STORE; q.out = ao.p; q.ldo = D; q.o_bs[0] = (long)SS * D; q.o_bs[1] = 64;
-    MD_TRY(launch_gemm(q, A_DENSE, precision, TILE_128x128, st));
+    MD_TRY(attention_f32(nullptr, st, qk.p, vT.p, ao.p, (float*)sc.p, T, SS, N, heads, kpad));
   }
   MD_TRY(launch_unpad_rows(ao.p, T, N, SS, D, out_dev, precision, st));
   MD_HIP(hipStreamSynchronize(st));

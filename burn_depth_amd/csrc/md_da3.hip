@@ -58,6 +58,8 @@ struct md_model_s::Da3State {
   int native_grid = 0;
   // ---- `small` (dual head) ----
   std::string hp = "head_mono";       // head parameter prefix
+  const float *head_norm_g = nullptr, *head_norm_b = nullptr;  // the dual head's token norm
+  const float* camera_token = nullptr;  // the learned reference-view camera token (dual head)
   int din = 0;                        // head input width: D (mono) or 2D (concatenated hooks)
   float* xlocal = nullptr;            // [rows, D] fp32: residual stream after the last LOCAL block
   float* rope_cos = nullptr;          // current shape's tables (aliases)
@@ -73,12 +75,7 @@ struct md_model_s::Da3State {
   std::vector<float> main_bias, aux_bias;             // output_conv2.conv2.bias, output_conv2_aux.<last>.project.bias
   // ---- MD_PREC_FP8: the four ViT linear layers on e4m3 operands (weights per output channel, static activation scales) ----
   bool fp8 = false;
-  char* w8_base = nullptr;                            // one allocation: per block qkv | proj | fc1 | fc2 (e4m3) + their scales
-  struct Fp8Block {
-    void* w[4] = {0, 0, 0, 0};
-    float* s[4] = {0, 0, 0, 0};
-  };
-  std::vector<Fp8Block> w8;
+  char* w8_base = nullptr;                            // one allocation: per block qkv | proj | fc1 | fc2 (e4m3) + their scales (VitBlockW::w8 / s8)
   static constexpr float kActScale = 8.0f / 448.0f;   // LayerNorm output, attention output
   static constexpr float kHidScale = 16.0f / 448.0f;  // GELU output
 };
@@ -175,13 +172,11 @@ int da3_on_commit(md_model_t m) {
   md_model_s::Da3State* d = m->da3;
   const int D = d->cfg.vit.D, M = d->native_grid;
   if (d->fp8) {  // e4m3 copies of the ViT linear weights, one scale per output channel
-    const char* names[4] = {".attn.qkv.weight", ".attn.proj.weight", ".mlp.fc1.weight", ".mlp.fc2.weight"};
     const int nn[4] = {3 * D, D, 4 * D, D}, kk[4] = {D, D, D, 4 * D};
-    for (int i = 0; i < d->cfg.vit.depth; ++i)
+    for (const VitBlockW& k : d->vit.blk)
       for (int j = 0; j < 4; ++j) {
-        const float* src = P32(m, "backbone.pretrained.blocks." + std::to_string(i) + names[j]);
-        if (!src) MD_FAIL(MD_ERR_FORMAT, "missing ViT weight for the fp8 pack");
-        MD_TRY(launch_pack_fp8_rows(src, nn[j], kk[j], kk[j], d->w8[i].w[j], d->w8[i].s[j], m->dev->stream));
+        if (!k.w32[j]) MD_FAIL(MD_ERR_FORMAT, "missing ViT weight for the fp8 pack");
+        MD_TRY(launch_pack_fp8_rows(k.w32[j], nn[j], kk[j], kk[j], k.w8[j], k.s8[j], m->dev->stream));
       }
     MD_HIP(hipStreamSynchronize(m->dev->stream));
   }
@@ -507,14 +502,7 @@ int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
   const int D = v.D, F = cfg.features;
   const int* oc = cfg.out_channels;
   const std::string bp = "backbone.pretrained";
-  add_pack(m, bp + ".patch_embed.proj.weight", PACK_NK, D, 3 * v.ps * v.ps, 1);
-  for (int i = 0; i < v.depth; ++i) {
-    const std::string b = bp + ".blocks." + std::to_string(i);
-    add_pack(m, b + ".attn.qkv.weight", PACK_NK, 3 * D, D, 1);
-    add_pack(m, b + ".attn.proj.weight", PACK_NK, D, D, 1);
-    add_pack(m, b + ".mlp.fc1.weight", PACK_NK, 4 * D, D, 1);
-    add_pack(m, b + ".mlp.fc2.weight", PACK_NK, D, 4 * D, 1);
-  }
+  vit_add_packs(m, bp, v);
   const std::string hp = d->hp;
   for (int s = 0; s < 4; ++s) add_pack(m, hp + ".projects." + std::to_string(s) + ".weight", PACK_NK, oc[s], d->din, 1);
   add_pack(m, hp + ".resize_layers.0.conv_t.weight", PACK_DECONV, oc[0], oc[0], 4);
@@ -557,6 +545,13 @@ int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
   (void)hipMemset(m->wpk_base, 0, m->wpk_bytes);
   for (auto& e : m->packs) e.dst = m->wpk_base + (size_t)e.dst;
 
+  VitW& w = d->vit;
+  vit_bind(m, bp, v.depth, w);
+  for (int i = 0; i < v.depth; ++i)  // the extended backbone alternates local and global blocks from ext_block_start on
+    w.blk[i].global = cfg.dual_head && i >= cfg.ext_block_start && i % 2 == 1;
+  d->head_norm_g = P32(m, hp + ".norm.gamma");
+  d->head_norm_b = P32(m, hp + ".norm.beta");
+  d->camera_token = P32(m, bp + ".camera_token");
   if (fp8) {
     const size_t per_block = (size_t)12 * D * D + (size_t)(3 * D + D + 4 * D + D) * 4 + 8 * 256;
     if (hipMalloc((void**)&d->w8_base, per_block * v.depth) != hipSuccess) {
@@ -566,35 +561,13 @@ int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
     (void)hipMemset(d->w8_base, 0, per_block * v.depth);
     char* q = d->w8_base;
     const int nn[4] = {3 * D, D, 4 * D, D}, kk[4] = {D, D, D, 4 * D};
-    for (int i = 0; i < v.depth; ++i) {
-      md_model_s::Da3State::Fp8Block b8;
+    for (VitBlockW& k : w.blk)
       for (int j = 0; j < 4; ++j) {
-        b8.w[j] = q;
+        k.w8[j] = q;
         q += align_up((size_t)nn[j] * kk[j], 256);
-        b8.s[j] = (float*)q;
+        k.s8[j] = (float*)q;
         q += align_up((size_t)nn[j] * 4, 256);
       }
-      d->w8.push_back(b8);
-    }
-  }
-  VitW& w = d->vit;
-  w.pe_w = PK(m, bp + ".patch_embed.proj.weight");
-  w.pe_b = P32(m, bp + ".patch_embed.proj.bias");
-  w.cls = P32(m, bp + ".cls_token");
-  w.pos = P32(m, bp + ".pos_embed");
-  w.norm_g = P32(m, bp + ".norm.gamma");
-  w.norm_b = P32(m, bp + ".norm.beta");
-  for (int i = 0; i < v.depth; ++i) {
-    const std::string b = bp + ".blocks." + std::to_string(i);
-    VitBlockW k;
-    k.n1g = P32(m, b + ".norm1.gamma"); k.n1b = P32(m, b + ".norm1.beta");
-    k.n2g = P32(m, b + ".norm2.gamma"); k.n2b = P32(m, b + ".norm2.beta");
-    k.qkv_w = PK(m, b + ".attn.qkv.weight"); k.qkv_b = P32(m, b + ".attn.qkv.bias");
-    k.proj_w = PK(m, b + ".attn.proj.weight"); k.proj_b = P32(m, b + ".attn.proj.bias");
-    k.ls1 = P32(m, b + ".ls1.gamma"); k.ls2 = P32(m, b + ".ls2.gamma");
-    k.fc1_w = PK(m, b + ".mlp.fc1.weight"); k.fc1_b = P32(m, b + ".mlp.fc1.bias");
-    k.fc2_w = PK(m, b + ".mlp.fc2.weight"); k.fc2_b = P32(m, b + ".mlp.fc2.bias");
-    w.blk.push_back(k);
   }
 
   if (hipMalloc(&m->zero_page, 4096) != hipSuccess) return fail(MD_ERR_OOM);
@@ -716,7 +689,7 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
   const int din = d->din;
   const int* oc = c.out_channels;
   const int Fp = cpad(m, F), F2 = F / 2, F2p = cpad(m, F2);
-  const std::string hp = d->hp, bp = "backbone.pretrained";
+  const std::string hp = d->hp;
   const float* x_dev = nchw;
   if (in_kind == MD_MEM_HOST && !from_tokens) {
     MD_HIP(hipMemcpyAsync(d->xin, nchw, (size_t)B * 3 * H * W * 4, hipMemcpyHostToDevice, st));
@@ -743,8 +716,8 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
     memset(&tg, 0, sizeof(tg));
     tg.ngroups = 1;
     tg.nseq[0] = B;
-    tg.a[0] = c.dual_head ? Bi(hp + ".norm.gamma") : nullptr;
-    tg.b[0] = c.dual_head ? Bi(hp + ".norm.beta") : nullptr;
+    tg.a[0] = c.dual_head ? d->head_norm_g : nullptr;
+    tg.b[0] = c.dual_head ? d->head_norm_b : nullptr;
     const hipMemcpyKind kind = in_kind == MD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     for (int hk = 0; hk < 4; ++hk) {
       for (int b = 0; b < B; ++b)  // patch rows of image b -> rows b*SS + 1 .. of the staging tensor (the layout the head gathers from)
@@ -815,136 +788,34 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
     r.end();
   }
   const long rows = (long)B * SS;
-  auto dense = [&](GemmParams& p) { p.ngroups = 1; p.g_rows[0] = (int)rows; };
   int hook_slot = 0;
-  // The residual stream lives in `xcur`. A GLOBAL block of the extended backbone needs the state behind the last LOCAL block
+  // The residual stream lives in `vp.x`. A GLOBAL block of the extended backbone needs the state behind the last LOCAL block
   // for its hook (cat(x_local, LayerNorm(x))): its output projection therefore writes x + ls * (...) into the other buffer
   // (GemmParams::resid_src) and the two swap -- the copy of the whole stream that used to precede every global block is gone.
-  float *xcur = d->xres, *xalt = d->xlocal;
-  const int ext0 = c.dual_head ? c.ext_block_start : v.depth + 1;
+  VitPlan vp;
+  vp.vit[0] = &d->vit; vp.gcnt[0] = B; vp.WS = B;
+  vp.D = D; vp.heads = heads; vp.SS = SS; vp.NT = NT; vp.kpad = d->kpad; vp.ln_eps = c.ln_eps;
+  vp.x = d->xres; vp.xalt = d->xlocal; vp.xn = d->xn; vp.qk = d->qk; vp.vT = d->vT; vp.ao = d->ao; vp.hbuf = d->hbuf; vp.scores = d->scores;
+  vp.lin_prec = d->fp8 ? MD_PREC_FP8 : m->prec;
+  if (d->fp8) { vp.a_scale = md_model_s::Da3State::kActScale; vp.h_scale = md_model_s::Da3State::kHidScale; }
+  vp.qk_norm_eps = c.qk_norm_eps; vp.rope_cos = d->rope_cos; vp.rope_sin = d->rope_sin; vp.rope_pw = pw;
+  // entering block ext_block_start the camera token takes the cls slot -- the encoder's (mod.rs:522-531) or the learned
+  // reference-view one
+  vp.tok0_block = c.dual_head ? c.ext_block_start : -1;
+  vp.tok0 = cam_tok ? cam_tok : d->camera_token;
+  vp.tok0_stride = cam_tok ? D : 0;
   for (int i = 0; i < v.depth; ++i) {
-    const VitBlockW& k = d->vit.blk[i];
-    const bool ext = i >= ext0, is_global = ext && (i % 2 == 1);
-    // entering block ext0 the camera token takes the cls slot -- the encoder's (mod.rs:522-531) or the learned reference-view one:
-    // this block's first LayerNorm replaces row 0 of every sequence on its way in (and writes it back to the residual stream)
-    const float* tok0 = i == ext0 ? (cam_tok ? cam_tok : Bi(bp + ".camera_token")) : nullptr;
-    const int tok0_stride = (i == ext0 && cam_tok) ? D : 0;
-    // MD_PREC_FP8: the operands of the four linear layers are e4m3 (LayerNorm / attention / GELU outputs are
-    // written as e4m3 on static scales; weights were quantised per output channel at commit)
-    const bool f8 = d->fp8;
-    const int lin_prec = f8 ? MD_PREC_FP8 : m->prec;
-    const float a_inv = 1.0f / md_model_s::Da3State::kActScale, h_inv = 1.0f / md_model_s::Da3State::kHidScale;
-    sg.a[0] = k.n1g; sg.b[0] = k.n1b;
-    r.begin("layernorm");
-    MD_TRY(launch_layernorm(xcur, d->xn, rows, D, c.ln_eps, SS, sg, lin_prec, 0, st, a_inv, tok0, tok0_stride, tok0 ? xcur : nullptr));
-    r.end();
-    {
-      GemmParams p;
-      p.N = 3 * D; dense(p); p.W[0] = k.qkv_w; p.bias[0] = k.qkv_b; p.A = d->xn;
-      if (f8) { p.K = D; p.lda = D; } else split_dense_a(m, p, D, D, 0);
-      p.v_plane = (long)m->vt_plane;
-      p.epi = EPI_QKV; p.out = d->qk; p.vT = d->vT; p.seq_stride = SS; p.embed = D; p.heads = heads; p.kpad = d->kpad; p.qscale = attn_qscale(m->prec);
-      if (f8) { p.W[0] = d->w8[i].w[0]; p.wscale[0] = d->w8[i].s[0]; p.ascale = md_model_s::Da3State::kActScale; }
-      if (ext && !f8) {  // per-head q/k LayerNorm + 2-D RoPE in this GEMM's epilogue (global blocks: every patch at position (1, 1))
-        const std::string a = bp + ".blocks." + std::to_string(i) + ".attn.";
-        p.qkn_g[0] = Bi(a + "q_norm.gamma"); p.qkn_b[0] = Bi(a + "q_norm.beta");
-        p.qkn_g[1] = Bi(a + "k_norm.gamma"); p.qkn_b[1] = Bi(a + "k_norm.beta");
-        p.qkn_eps = c.qk_norm_eps; p.rope_cos = d->rope_cos; p.rope_sin = d->rope_sin;
-        p.rope_pw = pw; p.rope_global = is_global ? 1 : 0; p.rope_ntok = NT;
-      }
-      r.begin("qkv_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, lin_prec, TILE_AUTO, st));
-      r.end();
-    }
-    if (ext && f8) {  // e4m3 operands: the separate kernel (the fused epilogue is not built for the block-scaled GEMM)
-      const std::string a = bp + ".blocks." + std::to_string(i) + ".attn.";
-      r.begin("qk_norm_rope");
-      MD_TRY(launch_qk_norm_rope(d->qk, rows, SS, NT, D, heads, pw, Bi(a + "q_norm.gamma"), Bi(a + "q_norm.beta"),
-                                 Bi(a + "k_norm.gamma"), Bi(a + "k_norm.beta"), c.qk_norm_eps, d->rope_cos, d->rope_sin,
-                                 is_global ? 1 : 0, attn_qscale(m->prec), m->prec, st));
-      r.end();
-    }
-    if (m->prec != MD_PREC_F32) {
-      r.begin("attention");
-      MD_TRY(launch_attention(d->qk, d->vT, d->ao, B, SS, NT, heads, D, d->kpad, m->prec, st, f8 ? a_inv : 0.f, (long)m->vt_plane));
-      r.end();
-    } else {
-      GemmParams p;
-      p.N = SS; p.K = 64; p.ngroups = 1; p.g_rows[0] = NT; p.batch = B * heads; p.batch_inner = heads;
-      p.A = d->qk; p.lda = 2 * D; p.a_bs[0] = (long)SS * 2 * D; p.a_bs[1] = 64;
-      p.W[0] = (const float*)d->qk + D; p.ldw = 2 * D; p.w_bs[0] = (long)SS * 2 * D; p.w_bs[1] = 64;
-      p.epi = EPI_STORE; p.out_f32 = 1; p.out = d->scores; p.ldo = d->kpad;
-      p.o_bs[0] = (long)heads * SS * d->kpad; p.o_bs[1] = (long)SS * d->kpad;
-      r.begin("attn_scores_f32");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_128x128, st));
-      r.end();
-      r.begin("attn_softmax_f32");
-      MD_TRY(launch_softmax_rows(d->scores, (long)B * heads * SS, NT, d->kpad, 0.125f, st));
-      r.end();
-      GemmParams q;
-      q.N = 64; q.K = d->kpad; q.ngroups = 1; q.g_rows[0] = NT; q.batch = B * heads; q.batch_inner = heads;
-      q.A = d->scores; q.lda = d->kpad; q.a_bs[0] = (long)heads * SS * d->kpad; q.a_bs[1] = (long)SS * d->kpad;
-      q.W[0] = d->vT; q.ldw = d->kpad; q.w_bs[0] = (long)heads * 64 * d->kpad; q.w_bs[1] = 64L * d->kpad;
-      q.epi = EPI_STORE; q.out = d->ao; q.ldo = D; q.o_bs[0] = (long)SS * D; q.o_bs[1] = 64;
-      r.begin("attn_pv_f32");
-      MD_TRY(launch_gemm(q, A_DENSE, m->prec, TILE_128x128, st));
-      r.end();
-    }
-    {
-      GemmParams p;
-      p.N = D; dense(p); p.W[0] = k.proj_w; p.bias[0] = k.proj_b; p.scale[0] = k.ls1;
-      p.A = d->ao;
-      if (f8) { p.K = D; p.lda = D; } else split_dense_a(m, p, D, D, 0);
-      p.epi = EPI_RESID_LS; p.out = xcur; p.ldo = D;
-      if (is_global) {  // x_i = x_{i-1} + ...: read the last local state, write the other buffer, keep x_{i-1} for the hook
-        p.resid_src = xcur; p.out = xalt;
-        std::swap(xcur, xalt);
-      }
-      if (f8) { p.W[0] = d->w8[i].w[1]; p.wscale[0] = d->w8[i].s[1]; p.ascale = md_model_s::Da3State::kActScale; }
-      r.begin("proj_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, lin_prec, TILE_AUTO, st));
-      r.end();
-    }
-    sg.a[0] = k.n2g; sg.b[0] = k.n2b;
-    r.begin("layernorm");
-    MD_TRY(launch_layernorm(xcur, d->xn, rows, D, c.ln_eps, SS, sg, lin_prec, 0, st, a_inv));
-    r.end();
-    {
-      GemmParams p;
-      p.N = 4 * D; dense(p); p.W[0] = k.fc1_w; p.bias[0] = k.fc1_b; p.A = d->xn;
-      if (f8) { p.K = D; p.lda = D; } else split_dense_a(m, p, D, D, 0);
-      p.epi = EPI_STORE; p.act = ACT_GELU; p.out = d->hbuf;
-      split_out(m, p, 4 * D, true);
-      if (f8) {
-        p.W[0] = d->w8[i].w[2]; p.wscale[0] = d->w8[i].s[2]; p.ascale = md_model_s::Da3State::kActScale;
-        p.out_fp8 = 1; p.out_inv_scale = h_inv;
-      }
-      r.begin("fc1_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, lin_prec, f8 ? TILE_256x256 : TILE_AUTO, st));
-      r.end();
-    }
-    {
-      GemmParams p;
-      p.N = D; dense(p); p.W[0] = k.fc2_w; p.bias[0] = k.fc2_b; p.scale[0] = k.ls2;
-      p.A = d->hbuf;
-      if (f8) { p.K = 4 * D; p.lda = 4 * D; } else split_dense_a(m, p, 4 * D, 4 * D, 0);
-      p.epi = EPI_RESID_LS; p.out = xcur; p.ldo = D;
-      if (f8) { p.W[0] = d->w8[i].w[3]; p.wscale[0] = d->w8[i].s[3]; p.ascale = md_model_s::Da3State::kHidScale; }
-      r.begin("fc2_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, lin_prec, TILE_AUTO, st));
-      r.end();
-    }
+    MD_TRY(run_vit_block(r, vp, i));
+    const float* xcur = vp.x;
     if (c.dual_head) {
       // hooks = LayerNorm_head(cat(x after the last local block, LayerNorm_final(x))); the camera feature is
       // token 0 of the raw concat at the last hook
-      bool hooked = false;
-      for (int hk = 0; hk < 4; ++hk) hooked |= c.hook_ids[hk] == i;
-      const float* xl = is_global ? xalt : xcur;  // a local block is its own "last local" state; behind a global block the other buffer holds it
+      const float* xl = d->vit.blk[i].global ? vp.xalt : xcur;  // a local block is its own "last local" state; behind a global block the other buffer holds it
       for (int hk = 0; hk < 4; ++hk)
         if (c.hook_ids[hk] == i) {
           r.begin("hook_cat_ln");
-          MD_TRY(launch_hook_cat_ln(xl, xcur, rows, SS, NT, D, d->vit.norm_g, d->vit.norm_b, c.ln_eps, Bi(hp + ".norm.gamma"),
-                                    Bi(hp + ".norm.beta"), 1e-5f, d->hookn[hk], hk == 3 ? d->cam_raw : nullptr, m->prec, st));
+          MD_TRY(launch_hook_cat_ln(xl, xcur, rows, SS, NT, D, d->vit.norm_g, d->vit.norm_b, c.ln_eps, d->head_norm_g,
+                                    d->head_norm_b, 1e-5f, d->hookn[hk], hk == 3 ? d->cam_raw : nullptr, m->prec, st));
           r.end();
           if (m->taps_enabled) {  // DepthTrace::backbone_tokens (mod.rs:241-246,344-347): cat(x_local, LayerNorm_final(x)) patch rows
             const std::string tn = "backbone_tokens_" + std::to_string(hk);
@@ -955,7 +826,6 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
           }
           ++hook_slot;
         }
-      (void)hooked;
     } else {
       // hooks (mod.rs:202-215): final LayerNorm of the block output, then the head's non-affine token
       // norm (apply_token_norm, dpt.rs:761-766: biased variance, eps 1e-5). A block may feed several hooks.

@@ -514,17 +514,7 @@ int model_create(md_device_t dev, const ModelCfg& cfg, md_model_t* out) {
   const int D = cfg.pv.D, F = cfg.F;
   const int* dims = cfg.pv.feat_dims;
   const char* vnames[3] = {"encoder.patch_encoder", "encoder.image_encoder", "fov.encoder"};
-  for (int gi = 0; gi < m->ngroups; ++gi) {
-    const std::string v = vnames[gi];
-    add_pack(m, v + ".patch_embed.proj.weight", PACK_NK, D, 3 * cfg.pv.ps * cfg.pv.ps, 1);
-    for (int i = 0; i < cfg.pv.depth; ++i) {
-      const std::string b = v + ".blocks." + std::to_string(i);
-      add_pack(m, b + ".attn.qkv.weight", PACK_NK, 3 * D, D, 1);
-      add_pack(m, b + ".attn.proj.weight", PACK_NK, D, D, 1);
-      add_pack(m, b + ".mlp.fc1.weight", PACK_NK, 4 * D, D, 1);
-      add_pack(m, b + ".mlp.fc2.weight", PACK_NK, D, 4 * D, 1);
-    }
-  }
+  for (int gi = 0; gi < m->ngroups; ++gi) vit_add_packs(m, vnames[gi], cfg.pv);
   auto pub = [&](const std::string& n, int din, int dout, int layers, int dint) {
     const int inter = dint > 0 ? dint : dout;
     add_pack(m, n + ".projection.weight", PACK_NK, inter, din, 1);
@@ -592,28 +582,7 @@ int model_create(md_device_t dev, const ModelCfg& cfg, md_model_t* out) {
   for (auto& e : m->packs) e.dst = m->wpk_base + (size_t)e.dst;
 
   // ---- ViT weight tables ----
-  for (int gi = 0; gi < m->ngroups; ++gi) {
-    const std::string v = vnames[gi];
-    VitW& w = m->vit[gi];
-    w.pe_w = PK(m, v + ".patch_embed.proj.weight");
-    w.pe_b = P32(m, v + ".patch_embed.proj.bias");
-    w.cls = P32(m, v + ".cls_token");
-    w.pos = P32(m, v + ".pos_embed");
-    w.norm_g = P32(m, v + ".norm.gamma");
-    w.norm_b = P32(m, v + ".norm.beta");
-    for (int i = 0; i < cfg.pv.depth; ++i) {
-      const std::string b = v + ".blocks." + std::to_string(i);
-      VitBlockW k;
-      k.n1g = P32(m, b + ".norm1.gamma"); k.n1b = P32(m, b + ".norm1.beta");
-      k.n2g = P32(m, b + ".norm2.gamma"); k.n2b = P32(m, b + ".norm2.beta");
-      k.qkv_w = PK(m, b + ".attn.qkv.weight"); k.qkv_b = P32(m, b + ".attn.qkv.bias");
-      k.proj_w = PK(m, b + ".attn.proj.weight"); k.proj_b = P32(m, b + ".attn.proj.bias");
-      k.ls1 = P32(m, b + ".ls1.gamma"); k.ls2 = P32(m, b + ".ls2.gamma");
-      k.fc1_w = PK(m, b + ".mlp.fc1.weight"); k.fc1_b = P32(m, b + ".mlp.fc1.bias");
-      k.fc2_w = PK(m, b + ".mlp.fc2.weight"); k.fc2_b = P32(m, b + ".mlp.fc2.bias");
-      w.blk.push_back(k);
-    }
-  }
+  for (int gi = 0; gi < m->ngroups; ++gi) vit_bind(m, vnames[gi], cfg.pv.depth, m->vit[gi]);
   if (m->ln_fold_can) {  // c / d of every block's two folded LayerNorms: [group][block][qkv_c 3D | qkv_d 3D | fc1_c 4D | fc1_d 4D]
     const size_t per_blk = (size_t)14 * D;
     if (hipMalloc((void**)&m->lnfold_base, ((size_t)m->ngroups * cfg.pv.depth * per_blk + 4 * D) * 4) != hipSuccess ||
@@ -867,13 +836,10 @@ int model_commit(md_model_t m) {
   }
   if (m->kind == 0 && m->ln_fold_can && m->lnfold_base) {
     const int D = m->cfg.pv.D;
-    const char* vnames[3] = {"encoder.patch_encoder", "encoder.image_encoder", "fov.encoder"};
     for (int gi = 0; gi < m->ngroups; ++gi)
-      for (int i = 0; i < m->cfg.pv.depth; ++i) {
-        const std::string b = std::string(vnames[gi]) + ".blocks." + std::to_string(i);
-        const VitBlockW& k = m->vit[gi].blk[i];
-        MD_TRY(launch_ln_fold_vectors(P32(m, b + ".attn.qkv.weight"), k.n1g, k.n1b, k.qkv_b, 3 * D, D, m->prec, (float*)k.qkv_c, (float*)k.qkv_d, s));
-        MD_TRY(launch_ln_fold_vectors(P32(m, b + ".mlp.fc1.weight"), k.n2g, k.n2b, k.fc1_b, 4 * D, D, m->prec, (float*)k.fc1_c, (float*)k.fc1_d, s));
+      for (const VitBlockW& k : m->vit[gi].blk) {
+        MD_TRY(launch_ln_fold_vectors(k.w32[0], k.n1g, k.n1b, k.qkv_b, 3 * D, D, m->prec, (float*)k.qkv_c, (float*)k.qkv_d, s));
+        MD_TRY(launch_ln_fold_vectors(k.w32[2], k.n2g, k.n2b, k.fc1_b, 4 * D, D, m->prec, (float*)k.fc1_c, (float*)k.fc1_d, s));
       }
   }
   auto it = m->pindex.find(m->kind == 1 ? "head_mono.scratch.output_conv2.conv2.bias" : "head.conv_out.bias");
@@ -960,6 +926,242 @@ static int get_index_set(md_model_s* m, int B, md_model_s::IndexSet* out) {
 // ------------------------------------------------------------------------------------------------
 // forward schedule
 // ------------------------------------------------------------------------------------------------
+int attention_f32(Run* r, hipStream_t st, const void* qk, const void* vT, void* out, float* scores, int nseq, int S, int n_tokens,
+                  int heads, int kpad) {
+  const int D = heads * 64;
+  GemmParams p;
+  p.N = S; p.K = 64; p.ngroups = 1; p.g_rows[0] = n_tokens;
+  p.batch = nseq * heads; p.batch_inner = heads;
+  p.A = qk; p.lda = 2 * D; p.a_bs[0] = (long)S * 2 * D; p.a_bs[1] = 64;
+  p.W[0] = (const float*)qk + D; p.ldw = 2 * D; p.w_bs[0] = (long)S * 2 * D; p.w_bs[1] = 64;
+  p.epi = EPI_STORE; p.out_f32 = 1; p.out = scores; p.ldo = kpad;
+  p.o_bs[0] = (long)heads * S * kpad; p.o_bs[1] = (long)S * kpad;
+  if (r) r->begin("attn_scores_f32");
+  MD_TRY(launch_gemm(p, A_DENSE, MD_PREC_F32, TILE_128x128, st));
+  if (r) r->end();
+  if (r) r->begin("attn_softmax_f32");
+  MD_TRY(launch_softmax_rows(scores, (long)nseq * heads * S, n_tokens, kpad, 0.125f, st));
+  if (r) r->end();
+  GemmParams q;
+  q.N = 64; q.K = kpad; q.ngroups = 1; q.g_rows[0] = n_tokens;
+  q.batch = nseq * heads; q.batch_inner = heads;
+  q.A = scores; q.lda = kpad; q.a_bs[0] = (long)heads * S * kpad; q.a_bs[1] = (long)S * kpad;
+  q.W[0] = vT; q.ldw = kpad; q.w_bs[0] = (long)heads * 64 * kpad; q.w_bs[1] = 64L * kpad;
+  q.epi = EPI_STORE; q.out = out; q.ldo = D; q.o_bs[0] = (long)S * D; q.o_bs[1] = 64;
+  if (r) r->begin("attn_pv_f32");
+  MD_TRY(launch_gemm(q, A_DENSE, MD_PREC_F32, TILE_128x128, st));
+  if (r) r->end();
+  return MD_OK;
+}
+
+void vit_add_packs(md_model_s* m, const std::string& prefix, const ViTDims& v) {
+  const int D = v.D;
+  add_pack(m, prefix + ".patch_embed.proj.weight", PACK_NK, D, 3 * v.ps * v.ps, 1);
+  for (int i = 0; i < v.depth; ++i) {
+    const std::string b = prefix + ".blocks." + std::to_string(i);
+    add_pack(m, b + ".attn.qkv.weight", PACK_NK, 3 * D, D, 1);
+    add_pack(m, b + ".attn.proj.weight", PACK_NK, D, D, 1);
+    add_pack(m, b + ".mlp.fc1.weight", PACK_NK, 4 * D, D, 1);
+    add_pack(m, b + ".mlp.fc2.weight", PACK_NK, D, 4 * D, 1);
+  }
+}
+
+void vit_bind(md_model_s* m, const std::string& prefix, int depth, VitW& w) {
+  w.pe_w = PK(m, prefix + ".patch_embed.proj.weight");
+  w.pe_b = P32(m, prefix + ".patch_embed.proj.bias");
+  w.cls = P32(m, prefix + ".cls_token");
+  w.pos = P32(m, prefix + ".pos_embed");
+  w.norm_g = P32(m, prefix + ".norm.gamma");
+  w.norm_b = P32(m, prefix + ".norm.beta");
+  for (int i = 0; i < depth; ++i) {
+    const std::string b = prefix + ".blocks." + std::to_string(i);
+    VitBlockW k;
+    k.n1g = P32(m, b + ".norm1.gamma"); k.n1b = P32(m, b + ".norm1.beta");
+    k.n2g = P32(m, b + ".norm2.gamma"); k.n2b = P32(m, b + ".norm2.beta");
+    k.qkv_w = PK(m, b + ".attn.qkv.weight"); k.qkv_b = P32(m, b + ".attn.qkv.bias");
+    k.proj_w = PK(m, b + ".attn.proj.weight"); k.proj_b = P32(m, b + ".attn.proj.bias");
+    k.ls1 = P32(m, b + ".ls1.gamma"); k.ls2 = P32(m, b + ".ls2.gamma");
+    k.fc1_w = PK(m, b + ".mlp.fc1.weight"); k.fc1_b = P32(m, b + ".mlp.fc1.bias");
+    k.fc2_w = PK(m, b + ".mlp.fc2.weight"); k.fc2_b = P32(m, b + ".mlp.fc2.bias");
+    k.w32[0] = P32(m, b + ".attn.qkv.weight"); k.w32[1] = P32(m, b + ".attn.proj.weight");
+    k.w32[2] = P32(m, b + ".mlp.fc1.weight"); k.w32[3] = P32(m, b + ".mlp.fc2.weight");
+    k.qkn_g[0] = P32(m, b + ".attn.q_norm.gamma"); k.qkn_b[0] = P32(m, b + ".attn.q_norm.beta");
+    k.qkn_g[1] = P32(m, b + ".attn.k_norm.gamma"); k.qkn_b[1] = P32(m, b + ".attn.k_norm.beta");
+    w.blk.push_back(k);
+  }
+}
+
+// Per-block features (q / k norm, global) are read from group 0's block: GemmParams carries one q / k norm per launch, and only
+// single-group plans have them.
+int run_vit_block(Run& r, VitPlan& v, int i) {
+  md_model_s* m = r.m;
+  const int G = v.G, D = v.D, heads = v.heads, SS = v.SS, NT = v.NT;
+  const size_t esz = (size_t)m->esz * m->xm;  // bytes per logical element of a T tensor
+  auto trow = [&](void* base, int width) { return (void*)((char*)base + (size_t)v.s_lo * SS * width * esz); };
+  const long rows = (long)v.WS * SS;
+  const VitBlockW& k0 = v.vit[0]->blk[i];
+  const int depth = (int)v.vit[0]->blk.size();
+  // MD_PREC_FP8: the operands of the four linear layers are e4m3 (LayerNorm / attention / GELU outputs are written as e4m3 on
+  // static scales; weights were quantised per output channel at commit)
+  const bool f8 = v.lin_prec == MD_PREC_FP8;
+  // (launch_layernorm reads its scale only when it writes e4m3 -- the fp8o form in kernels/ops.hip; 1 is its default)
+  const float a_inv = f8 ? 1.0f / v.a_scale : 1.f;
+  auto dense_a = [&](GemmParams& p, int K) {
+    if (f8) { p.K = K; p.lda = K; } else split_dense_a(m, p, K, K, 0);
+  };
+  auto group_rows = [&](GemmParams& p) {
+    p.ngroups = G;
+    for (int g = 0; g < G; ++g) {
+      p.g_row0[g] = v.glo[g] * SS;
+      p.g_arow0[g] = v.glo[g] * SS;
+      p.g_rows[g] = v.gcnt[g] * SS;
+    }
+  };
+  SeqGroups sg;  // sequence numbers relative to the window
+  memset(&sg, 0, sizeof(sg));
+  sg.ngroups = G;
+  for (int g = 0; g < G; ++g) { sg.seq0[g] = v.glo[g] - v.s_lo; sg.nseq[g] = v.gcnt[g]; }
+  auto layernorm = [&](bool norm2, const float* tok0) -> int {
+    for (int g = 0; g < G; ++g) {
+      const VitBlockW& k = v.vit[g]->blk[i];
+      sg.a[g] = norm2 ? k.n2g : k.n1g; sg.b[g] = norm2 ? k.n2b : k.n1b;
+    }
+    float* x = v.x + (size_t)v.s_lo * SS * D;  // the window's rows of the current residual stream
+    r.begin("layernorm");
+    const int st_ = launch_layernorm(x, trow(v.xn, D), rows, D, v.ln_eps, SS, sg, v.lin_prec, 0, r.st, a_inv, tok0,
+                                     tok0 ? v.tok0_stride : 0, tok0 ? x : nullptr);
+    r.end();
+    return st_;
+  };
+  // LayerNorm fold: the producer (proj / fc2) writes the next norm's input and the rows' statistics, the consumer (qkv / fc1)
+  // finishes its accumulators with them
+  const bool fold = v.fold, neutral = v.neutral;
+  const bool fold1 = fold && i > 0;  // this block's norm1 was folded by the previous block's fc2
+  auto fold_producer = [&](GemmParams& p, int blk, bool norm2) {
+    p.ln_out = v.xn; p.ln_ldo = (long)D * m->xm; p.ln_plane = m->xm == 2 ? D : 0;
+    p.ln_stats_out = v.ln_stats; p.ln_parts = D / 256;
+    for (int g = 0; g < G; ++g) p.ln_gamma[g] = norm2 ? v.vit[g]->blk[blk].n2g : v.vit[g]->blk[blk].n1g;
+  };
+  auto fold_consumer = [&](GemmParams& p) {
+    p.ln_stats = v.finish_launch ? v.ln_ab : v.ln_stats; p.ln_raw = v.finish_launch ? 0 : 1;
+    p.ln_parts = D / 256; p.ln_inv_n = 1.0f / (float)D; p.ln_eps = v.ln_eps;
+  };
+  auto fold_finish = [&]() -> int {  // the window's rows: (mean, M2) x 4 -> (rstd, -mu rstd)
+    if (!v.finish_launch) return MD_OK;
+    r.begin("ln_finish");
+    const int st_ = launch_ln_finish(v.ln_stats + (size_t)v.s_lo * SS * (D / 256) * 2, v.ln_ab + (size_t)v.s_lo * SS * 2, rows,
+                                     1.0f / (float)D, v.ln_eps, r.st);
+    r.end();
+    return st_;
+  };
+
+  // entering block tok0_block, row 0 of every sequence is replaced on its way in (and written back to the residual stream)
+  if (!fold1) MD_TRY(layernorm(false, i == v.tok0_block ? v.tok0 : nullptr));
+  {
+    GemmParams p;
+    p.N = 3 * D; group_rows(p);
+    for (int g = 0; g < G; ++g) {
+      const VitBlockW& k = v.vit[g]->blk[i];
+      p.W[g] = f8 ? k.w8[0] : k.qkv_w;
+      p.wscale[g] = k.s8[0];
+      p.bias[g] = fold1 ? k.qkv_d : k.qkv_b;
+      if (fold1) p.ln_c[g] = k.qkv_c;
+      if (neutral) p.ln_c[g] = v.zero_c;
+    }
+    if (fold1 || neutral) fold_consumer(p);
+    p.A = v.xn;
+    dense_a(p, D);
+    p.v_plane = (long)m->vt_plane;
+    p.epi = EPI_QKV; p.out = v.qk; p.vT = v.vT; p.seq_stride = SS; p.embed = D; p.heads = heads; p.kpad = v.kpad; p.qscale = attn_qscale(m->prec);
+    if (f8) p.ascale = v.a_scale;
+    if (k0.qkn_g[0] && !f8) {  // per-head q/k LayerNorm + 2-D RoPE in this GEMM's epilogue (global blocks: every patch at position (1, 1))
+      p.qkn_g[0] = k0.qkn_g[0]; p.qkn_b[0] = k0.qkn_b[0]; p.qkn_g[1] = k0.qkn_g[1]; p.qkn_b[1] = k0.qkn_b[1];
+      p.qkn_eps = v.qk_norm_eps; p.rope_cos = v.rope_cos; p.rope_sin = v.rope_sin;
+      p.rope_pw = v.rope_pw; p.rope_global = k0.global ? 1 : 0; p.rope_ntok = NT;
+    }
+    r.begin("qkv_gemm");
+    MD_TRY(launch_gemm(p, A_DENSE, v.lin_prec, (fold1 || neutral) ? TILE_256x256 : TILE_AUTO, r.st));
+    r.end();
+  }
+  if (k0.qkn_g[0] && f8) {  // e4m3 operands: the separate kernel (the fused epilogue is not built for the block-scaled GEMM)
+    r.begin("qk_norm_rope");
+    MD_TRY(launch_qk_norm_rope(trow(v.qk, 2 * D), rows, SS, NT, D, heads, v.rope_pw, k0.qkn_g[0], k0.qkn_b[0], k0.qkn_g[1], k0.qkn_b[1],
+                               v.qk_norm_eps, v.rope_cos, v.rope_sin, k0.global ? 1 : 0, attn_qscale(m->prec), m->prec, r.st));
+    r.end();
+  }
+  void* vT_w = (char*)v.vT + (size_t)v.s_lo * heads * 64 * v.kpad * m->esz;  // the window's first sequence of the V^T plane
+  if (m->prec != MD_PREC_F32) {
+    r.begin("attention");
+    MD_TRY(launch_attention(trow(v.qk, 2 * D), vT_w, trow(v.ao, D), v.WS, SS, NT, heads, D, v.kpad, m->prec, r.st, f8 ? a_inv : 0.f,
+                            (long)m->vt_plane, v.redo, v.redo_units));
+    r.end();
+  } else {
+    MD_TRY(attention_f32(&r, r.st, trow(v.qk, 2 * D), vT_w, trow(v.ao, D), v.scores, v.WS, SS, NT, heads, v.kpad));
+  }
+  {
+    GemmParams p;
+    p.N = D; group_rows(p);
+    for (int g = 0; g < G; ++g) {
+      const VitBlockW& k = v.vit[g]->blk[i];
+      p.W[g] = f8 ? k.w8[1] : k.proj_w; p.wscale[g] = k.s8[1]; p.bias[g] = k.proj_b; p.scale[g] = k.ls1;
+    }
+    p.A = v.ao;
+    dense_a(p, D);
+    p.epi = EPI_RESID_LS; p.out = v.x; p.ldo = D;
+    if (k0.global) {  // x_i = x_{i-1} + ...: read the last local state, write the other buffer, keep x_{i-1} for the hook
+      p.resid_src = v.x; p.out = v.xalt;
+      std::swap(v.x, v.xalt);
+    }
+    if (f8) p.ascale = v.a_scale;
+    if (fold) fold_producer(p, i, true);
+    r.begin("proj_gemm");
+    MD_TRY(launch_gemm(p, A_DENSE, v.lin_prec, fold ? TILE_256x256 : TILE_AUTO, r.st));
+    r.end();
+    if (fold) MD_TRY(fold_finish());
+  }
+  if (!fold) MD_TRY(layernorm(true, nullptr));
+  {
+    GemmParams p;
+    p.N = 4 * D; group_rows(p);
+    for (int g = 0; g < G; ++g) {
+      const VitBlockW& k = v.vit[g]->blk[i];
+      p.W[g] = f8 ? k.w8[2] : k.fc1_w;
+      p.wscale[g] = k.s8[2];
+      p.bias[g] = fold ? k.fc1_d : k.fc1_b;
+      if (fold) p.ln_c[g] = k.fc1_c;
+      if (neutral) p.ln_c[g] = v.zero_c;
+    }
+    if (fold || neutral) fold_consumer(p);
+    p.A = v.xn;
+    dense_a(p, D);
+    p.epi = EPI_STORE; p.act = ACT_GELU; p.out = v.hbuf;
+    split_out(m, p, 4 * D, true);
+    if (f8) { p.ascale = v.a_scale; p.out_fp8 = 1; p.out_inv_scale = 1.0f / v.h_scale; }
+    r.begin("fc1_gemm");
+    MD_TRY(launch_gemm(p, A_DENSE, v.lin_prec, (fold || neutral || f8) ? TILE_256x256 : TILE_AUTO, r.st));
+    r.end();
+  }
+  {
+    const bool fold_next = fold && i + 1 < depth;
+    GemmParams p;
+    p.N = D; group_rows(p);
+    for (int g = 0; g < G; ++g) {
+      const VitBlockW& k = v.vit[g]->blk[i];
+      p.W[g] = f8 ? k.w8[3] : k.fc2_w; p.wscale[g] = k.s8[3]; p.bias[g] = k.fc2_b; p.scale[g] = k.ls2;
+    }
+    p.A = v.hbuf;
+    dense_a(p, 4 * D);
+    p.epi = EPI_RESID_LS; p.out = v.x; p.ldo = D;
+    if (f8) p.ascale = v.h_scale;
+    if (fold_next) fold_producer(p, i + 1, false);
+    r.begin("fc2_gemm");
+    MD_TRY(launch_gemm(p, A_DENSE, v.lin_prec, fold ? TILE_256x256 : TILE_AUTO, r.st));
+    r.end();
+    if (fold_next) MD_TRY(fold_finish());
+  }
+  return MD_OK;
+}
+
 // The ViT stage over the sequences [s_lo, s_hi) of the 37 B (patch tiles, image, fov): the whole range in the ordinary
 // call; one rank's share in the tile-parallel mode (SURVEY 8(e) second mode -- the tiles of encoder.rs:329-348 never
 // interact before `merge`, so any split of the sequence range is exact). Every launch addresses absolute rows of the
@@ -1018,157 +1220,30 @@ static int run_vit(Run& r, int nseq_p, int nseq, int s_lo, int s_hi) {
     r.end();
   }
   const long rows = (long)WS * SS;
-  auto group_rows = [&](GemmParams& p) {
-    p.ngroups = G;
-    for (int g = 0; g < G; ++g) {
-      p.g_row0[g] = glo[g] * SS;
-      p.g_arow0[g] = glo[g] * SS;
-      p.g_rows[g] = gcnt[g] * SS;
-    }
-  };
-  const size_t vt_seq = (size_t)heads * 64 * m->kpad * m->esz;  // bytes of one sequence in a V^T plane
+  VitPlan v;
+  v.G = G;
+  for (int g = 0; g < G; ++g) { v.vit[g] = &m->vit[gi[g]]; v.glo[g] = glo[g]; v.gcnt[g] = gcnt[g]; }
+  v.s_lo = s_lo; v.WS = WS;
+  v.D = D; v.heads = heads; v.SS = SS; v.NT = NT; v.kpad = m->kpad; v.ln_eps = c.ln_eps;
+  v.x = b->xres; v.xn = b->xn; v.qk = b->qk; v.vT = b->vT; v.ao = b->ao; v.hbuf = b->hbuf; v.scores = b->scores;
+  v.redo = b->attn_redo; v.redo_units = b->attn_redo_units;
+  v.lin_prec = m->prec;
   // LayerNorm fold (gemm.h GemmParams::ln_*): norm2 of every block and norm1 of blocks 1.. never run as launches -- the GEMM that
   // produces the residual stream (proj / fc2) also writes round_T(gamma . x) and the rows' statistics, the GEMM behind the norm
   // (fc1 / qkv) finishes its accumulators with them. Block 0's norm1 (behind the patch embedding) and the final norm stay launches.
   // The four GEMMs of a block then always run the 256 x 256 kernel: the fold is a model-level choice, so that any window of a call
   // (tile-parallel mode) computes the same bits as the whole call.
-  const bool fold = m->ln_fold_on();
-  const int fold_tile = fold ? TILE_256x256 : TILE_AUTO;
+  v.fold = m->ln_fold_on();
   // ln_fold = 3 (diagnostic, benches only): the UNFOLDED schedule through the fold-form consumer kernels (EK 6 / 7) on neutral statistics
   // (rstd = 1, mu = 0, c = 0, d = bias): isolates what those epilogues cost from what the colder A operand of the folded schedule costs
-  const bool neutral = !fold && m->ln_fold_can && m->ln_fold_opt == 3;
-  const float* zero_c = m->lnfold_base ? m->lnfold_base + (size_t)m->ngroups * c.pv.depth * 14 * D : nullptr;
-  if (neutral) MD_TRY(launch_fill_pairs(b->ln_ab + (size_t)s_lo * SS * 2, rows, 1.0f, 0.0f, r.st));
-  auto fold_producer = [&](GemmParams& p, int blk, bool norm2) {
-    p.ln_out = b->xn; p.ln_ldo = (long)D * m->xm; p.ln_plane = m->xm == 2 ? D : 0;
-    p.ln_stats_out = b->ln_stats; p.ln_parts = D / 256;
-    for (int g = 0; g < G; ++g) p.ln_gamma[g] = norm2 ? m->vit[gi[g]].blk[blk].n2g : m->vit[gi[g]].blk[blk].n1g;
-  };
+  v.neutral = !v.fold && m->ln_fold_can && m->ln_fold_opt == 3;
   // (ln_fold = 4: the pairs come from the ln_finish launch -- the A/B form; default: the consumer combines the partials itself)
-  const bool finish_launch = neutral || m->ln_fold_opt == 4;
-  auto fold_consumer = [&](GemmParams& p) {
-    p.ln_stats = finish_launch ? b->ln_ab : b->ln_stats; p.ln_raw = finish_launch ? 0 : 1;
-    p.ln_parts = D / 256; p.ln_inv_n = 1.0f / (float)D; p.ln_eps = c.ln_eps;
-  };
-  auto fold_finish = [&]() -> int {  // the window's rows: (mean, M2) x 4 -> (rstd, -mu rstd)
-    if (!finish_launch) return MD_OK;
-    r.begin("ln_finish");
-    const int st_ = launch_ln_finish(b->ln_stats + (size_t)s_lo * SS * (D / 256) * 2, b->ln_ab + (size_t)s_lo * SS * 2, rows, 1.0f / (float)D, c.ln_eps, r.st);
-    r.end();
-    return st_;
-  };
+  v.finish_launch = v.neutral || m->ln_fold_opt == 4;
+  v.ln_stats = b->ln_stats; v.ln_ab = b->ln_ab;
+  v.zero_c = m->lnfold_base ? m->lnfold_base + (size_t)m->ngroups * c.pv.depth * 14 * D : nullptr;
+  if (v.neutral) MD_TRY(launch_fill_pairs(b->ln_ab + (size_t)s_lo * SS * 2, rows, 1.0f, 0.0f, r.st));
   for (int i = 0; i < c.pv.depth; ++i) {
-    const bool fold1 = fold && i > 0;  // this block's norm1 was folded by the previous block's fc2
-    if (!fold1) {
-      for (int g = 0; g < G; ++g) { sg.a[g] = m->vit[gi[g]].blk[i].n1g; sg.b[g] = m->vit[gi[g]].blk[i].n1b; }
-      r.begin("layernorm");
-      MD_TRY(launch_layernorm(xres_w, trow(b->xn, D), rows, D, c.ln_eps, SS, sg, m->prec, 0, r.st));
-      r.end();
-    }
-    {
-      GemmParams p;
-      p.N = 3 * D; group_rows(p);
-      for (int g = 0; g < G; ++g) {
-        p.W[g] = m->vit[gi[g]].blk[i].qkv_w;
-        p.bias[g] = fold1 ? m->vit[gi[g]].blk[i].qkv_d : m->vit[gi[g]].blk[i].qkv_b;
-        if (fold1) p.ln_c[g] = m->vit[gi[g]].blk[i].qkv_c;
-      }
-      if (fold1) fold_consumer(p);
-      if (neutral) { fold_consumer(p); for (int g = 0; g < G; ++g) p.ln_c[g] = zero_c; }
-      p.A = b->xn;
-      split_dense_a(m, p, D, D, 0);
-      p.v_plane = (long)m->vt_plane;
-      p.epi = EPI_QKV; p.out = b->qk; p.vT = b->vT; p.seq_stride = SS; p.embed = D; p.heads = heads; p.kpad = m->kpad; p.qscale = attn_qscale(m->prec);
-      r.begin("qkv_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, (fold1 || neutral) ? TILE_256x256 : TILE_AUTO, r.st));
-      r.end();
-    }
-    void* vT_w = (char*)b->vT + (size_t)s_lo * vt_seq;
-    if (m->prec != MD_PREC_F32) {
-      r.begin("attention");
-      MD_TRY(launch_attention(trow(b->qk, 2 * D), vT_w, trow(b->ao, D), WS, SS, NT, heads, D, m->kpad, m->prec, r.st, 0.f, (long)m->vt_plane,
-                              b->attn_redo, b->attn_redo_units));
-      r.end();
-    } else {
-      // fp32: scores = q k^T (batched GEMM) -> row softmax -> P V^T^T (batched GEMM)
-      const float* qk_w = (const float*)trow(b->qk, 2 * D);
-      GemmParams p;
-      p.N = SS; p.K = 64; p.ngroups = 1; p.g_rows[0] = NT;
-      p.batch = WS * heads; p.batch_inner = heads;
-      p.A = qk_w; p.lda = 2 * D; p.a_bs[0] = (long)SS * 2 * D; p.a_bs[1] = 64;
-      p.W[0] = qk_w + D; p.ldw = 2 * D; p.w_bs[0] = (long)SS * 2 * D; p.w_bs[1] = 64;
-      p.epi = EPI_STORE; p.out_f32 = 1; p.out = b->scores; p.ldo = m->kpad;
-      p.o_bs[0] = (long)heads * SS * m->kpad; p.o_bs[1] = (long)SS * m->kpad;
-      r.begin("attn_scores_f32");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_128x128, r.st));
-      r.end();
-      r.begin("attn_softmax_f32");
-      MD_TRY(launch_softmax_rows(b->scores, (long)WS * heads * SS, NT, m->kpad, 0.125f, r.st));
-      r.end();
-      GemmParams q;
-      q.N = 64; q.K = m->kpad; q.ngroups = 1; q.g_rows[0] = NT;
-      q.batch = WS * heads; q.batch_inner = heads;
-      q.A = b->scores; q.lda = m->kpad; q.a_bs[0] = (long)heads * SS * m->kpad; q.a_bs[1] = (long)SS * m->kpad;
-      q.W[0] = vT_w; q.ldw = m->kpad; q.w_bs[0] = (long)heads * 64 * m->kpad; q.w_bs[1] = 64L * m->kpad;
-      q.epi = EPI_STORE; q.out = trow(b->ao, D); q.ldo = D; q.o_bs[0] = (long)SS * D; q.o_bs[1] = 64;
-      r.begin("attn_pv_f32");
-      MD_TRY(launch_gemm(q, A_DENSE, m->prec, TILE_128x128, r.st));
-      r.end();
-    }
-    {
-      GemmParams p;
-      p.N = D; group_rows(p);
-      for (int g = 0; g < G; ++g) {
-        p.W[g] = m->vit[gi[g]].blk[i].proj_w; p.bias[g] = m->vit[gi[g]].blk[i].proj_b; p.scale[g] = m->vit[gi[g]].blk[i].ls1;
-      }
-      p.A = b->ao;
-      split_dense_a(m, p, D, D, 0);
-      p.epi = EPI_RESID_LS; p.out = b->xres; p.ldo = D;
-      if (fold) fold_producer(p, i, true);
-      r.begin("proj_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, fold_tile, r.st));
-      r.end();
-      if (fold) MD_TRY(fold_finish());
-    }
-    if (!fold) {
-      for (int g = 0; g < G; ++g) { sg.a[g] = m->vit[gi[g]].blk[i].n2g; sg.b[g] = m->vit[gi[g]].blk[i].n2b; }
-      r.begin("layernorm");
-      MD_TRY(launch_layernorm(xres_w, trow(b->xn, D), rows, D, c.ln_eps, SS, sg, m->prec, 0, r.st));
-      r.end();
-    }
-    {
-      GemmParams p;
-      p.N = 4 * D; group_rows(p);
-      for (int g = 0; g < G; ++g) {
-        p.W[g] = m->vit[gi[g]].blk[i].fc1_w;
-        p.bias[g] = fold ? m->vit[gi[g]].blk[i].fc1_d : m->vit[gi[g]].blk[i].fc1_b;
-        if (fold) p.ln_c[g] = m->vit[gi[g]].blk[i].fc1_c;
-      }
-      if (fold) fold_consumer(p);
-      if (neutral) { fold_consumer(p); for (int g = 0; g < G; ++g) p.ln_c[g] = zero_c; }
-      p.A = b->xn;
-      split_dense_a(m, p, D, D, 0);
-      p.epi = EPI_STORE; p.act = ACT_GELU; p.out = b->hbuf;
-      split_out(m, p, 4 * D, true);
-      r.begin("fc1_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, (fold || neutral) ? TILE_256x256 : TILE_AUTO, r.st));
-      r.end();
-    }
-    {
-      GemmParams p;
-      p.N = D; group_rows(p);
-      for (int g = 0; g < G; ++g) {
-        p.W[g] = m->vit[gi[g]].blk[i].fc2_w; p.bias[g] = m->vit[gi[g]].blk[i].fc2_b; p.scale[g] = m->vit[gi[g]].blk[i].ls2;
-      }
-      p.A = b->hbuf;
-      split_dense_a(m, p, 4 * D, 4 * D, 0);
-      p.epi = EPI_RESID_LS; p.out = b->xres; p.ldo = D;
-      if (fold && i + 1 < c.pv.depth) fold_producer(p, i + 1, false);
-      r.begin("fc2_gemm");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, fold_tile, r.st));
-      r.end();
-      if (fold && i + 1 < c.pv.depth) MD_TRY(fold_finish());
-    }
+    MD_TRY(run_vit_block(r, v, i));
     // hooks: un-normalised tokens incl. cls after blocks hook_ids[0], hook_ids[1] (vit.rs:30,63): the first n0 sequences
     // (the 5 x 5 high-resolution tiles, encoder.rs:379-390)
     for (int hk = 0; hk < 2; ++hk)

@@ -311,5 +311,48 @@ inline int conv3(Run& r, const char* name, const void* in, int H, int W, int Cin
   return s;
 }
 
+// fp32 attention as three launches: scores = q k^T (batched GEMM) -> row softmax -> P V^T^T (batched GEMM). qk [nseq*S, 2D] (q | k),
+// vT [nseq][heads][64][kpad], scores [nseq*heads*S, kpad] fp32 scratch, out [nseq*S, D]. `r` (optional) times the three launches.
+int attention_f32(Run* r, hipStream_t st, const void* qk, const void* vT, void* out, float* scores, int nseq, int S, int n_tokens,
+                  int heads, int kpad);
+
+// ---- the DINOv2 ViT block (Depth Pro's three encoders, Depth-Anything-v3's backbone) ----
+// the packs of the ViT under `prefix`: patch embedding, then qkv | proj | fc1 | fc2 of every block
+void vit_add_packs(md_model_s* m, const std::string& prefix, const ViTDims& v);
+// the weight tables of the ViT under `prefix` (after the packed arena is placed)
+void vit_bind(md_model_s* m, const std::string& prefix, int depth, VitW& w);
+
+// One call's ViT stage as run_vit_block sees it, filled once per call. Row group g is vit[g] on sequences [glo[g], glo[g] + gcnt[g])
+// (Depth Pro: its encoders clipped to the window; Depth-Anything-v3: one group over the batch). Buffers are the workspace bases:
+// GEMMs address absolute rows, LayerNorms and attention the window's sequences [s_lo, s_lo + WS).
+struct VitPlan {
+  int G = 1;
+  const VitW* vit[3] = {nullptr, nullptr, nullptr};
+  int glo[3] = {0, 0, 0}, gcnt[3] = {0, 0, 0};
+  int s_lo = 0, WS = 0;
+  int D = 0, heads = 0, SS = 0, NT = 0, kpad = 0;
+  float ln_eps = 0.f;
+  float* x = nullptr;     // fp32 residual stream; a global block writes `xalt` and the two swap
+  float* xalt = nullptr;
+  void *xn = nullptr, *qk = nullptr, *vT = nullptr, *ao = nullptr, *hbuf = nullptr;
+  float* scores = nullptr;                  // MD_PREC_F32 attention
+  int* redo = nullptr;                      // launch_attention's assembly-kernel flags (null: never the assembly kernel)
+  int redo_units = 0;
+  // LayerNorm fold (md_model_s::ln_fold_opt): folded / neutral (3) statistics, finished by an ln_finish launch (3, 4)
+  bool fold = false, neutral = false, finish_launch = false;
+  float *ln_stats = nullptr, *ln_ab = nullptr;
+  const float* zero_c = nullptr;
+  int lin_prec = MD_PREC_BF16;              // operands of the four linear layers (MD_PREC_FP8: e4m3, VitBlockW::w8)
+  float a_scale = 0.f, h_scale = 0.f;       // MD_PREC_FP8: static scales of the LayerNorm / attention and of the GELU outputs
+  float qk_norm_eps = 0.f;                  // blocks with VitBlockW::qkn_*: RoPE tables of this input size
+  const float *rope_cos = nullptr, *rope_sin = nullptr;
+  int rope_pw = 0;
+  int tok0_block = -1;                      // entering this block, row 0 of every sequence becomes tok0 (+ b * tok0_stride)
+  const float* tok0 = nullptr;
+  int tok0_stride = 0;
+};
+// Block i: LayerNorm 1 -> qkv GEMM -> attention -> proj GEMM (+ residual) -> LayerNorm 2 -> fc1 GEMM (GELU) -> fc2 GEMM (+ residual)
+int run_vit_block(Run& r, VitPlan& v, int i);
+
 
 }  // namespace md
