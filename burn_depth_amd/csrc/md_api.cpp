@@ -1063,7 +1063,7 @@ int md_da3_create(md_device_t dev, const md_da3_cfg* cfg, uint64_t seed, int ini
   MD_TRY(parse_da3_cfg(cfg, &dc));
   md_model_t m = nullptr;
   MD_TRY(da3_create(dev, dc, &m));
-  int s = da3_init_seeded(m, seed, init_scheme);
+  int s = model_init_seeded(m, seed, init_scheme);
   if (s != MD_OK) {
     model_destroy(m);
     return s;
@@ -1082,7 +1082,7 @@ int md_da3_load(md_device_t dev, const md_da3_cfg* cfg, const char* path, md_mod
   }
   md_model_t m = nullptr;
   MD_TRY(da3_create(dev, dc, &m));
-  int s = da3_load_container(m, path);
+  int s = model_load_container(m, path);
   if (s != MD_OK) {
     model_destroy(m);
     return s;

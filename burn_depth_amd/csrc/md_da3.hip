@@ -58,8 +58,19 @@ struct md_model_s::Da3State {
   int native_grid = 0;
   // ---- `small` (dual head) ----
   std::string hp = "head_mono";       // head parameter prefix
+  // ---- weight tables behind the backbone, bound at create (da3_bind) ----
+  const float* pos_native = nullptr;  // the pos_embed parameter (its native grid)
   const float *head_norm_g = nullptr, *head_norm_b = nullptr;  // the dual head's token norm
   const float* camera_token = nullptr;  // the learned reference-view camera token (dual head)
+  ConvW proj[4], resize[4], layer_rn[4];  // projects, resize_layers 0 | 1 | 3 (2 is the identity), layerN_rn (no bias)
+  // refinenet1..4 of the main | aux ("_aux") pyramid, group innermost: residual1 (none at level 3) | residual2, out_conv
+  ResUnitW res[4][2][2];
+  ConvW out_conv[4][2];
+  ConvW oc1, oc2_1, oc2_2;              // output_conv1, output_conv2.conv1, output_conv2.conv2 (fp32 weight and bias)
+  std::vector<ConvW> aux_neck;          // the last aux level: output_conv1_aux layers, output_conv2_aux reduce | project (fp32)
+  ConvW aux_reduce, aux_project;
+  CamEncW cam_enc{};                    // camera encoder (checked where it runs), camera decoder
+  CamDecW cam_dec{};
   int din = 0;                        // head input width: D (mono) or 2D (concatenated hooks)
   float* xlocal = nullptr;            // [rows, D] fp32: residual stream after the last LOCAL block
   float* rope_cos = nullptr;          // current shape's tables (aliases)
@@ -170,7 +181,7 @@ static int da3_set_shape(md_model_s* m, int H, int W, bool force);
 
 int da3_on_commit(md_model_t m) {
   md_model_s::Da3State* d = m->da3;
-  const int D = d->cfg.vit.D, M = d->native_grid;
+  const int D = d->cfg.vit.D;
   if (d->fp8) {  // e4m3 copies of the ViT linear weights, one scale per output channel
     const int nn[4] = {3 * D, D, 4 * D, D}, kk[4] = {D, D, D, 4 * D};
     for (const VitBlockW& k : d->vit.blk)
@@ -180,17 +191,13 @@ int da3_on_commit(md_model_t m) {
       }
     MD_HIP(hipStreamSynchronize(m->dev->stream));
   }
-  {
-    const Da3Cfg& c = d->cfg;
-    d->main_bias.assign(c.output_dim, 0.f);
-    MD_HIP(hipMemcpy(d->main_bias.data(), P32(m, d->hp + ".scratch.output_conv2.conv2.bias"), c.output_dim * 4, hipMemcpyDeviceToHost));
-    if (c.dual_head) {
-      d->aux_bias.assign(c.aux_output_dim, 0.f);
-      MD_HIP(hipMemcpy(d->aux_bias.data(), P32(m, d->hp + ".scratch.output_conv2_aux." + std::to_string(c.aux_levels - 1) + ".project.bias"),
-                       c.aux_output_dim * 4, hipMemcpyDeviceToHost));
-    }
+  const Da3Cfg& c = d->cfg;
+  d->main_bias.assign(c.output_dim, 0.f);
+  MD_HIP(hipMemcpy(d->main_bias.data(), d->oc2_2.b, c.output_dim * 4, hipMemcpyDeviceToHost));
+  if (c.dual_head) {
+    d->aux_bias.assign(c.aux_output_dim, 0.f);
+    MD_HIP(hipMemcpy(d->aux_bias.data(), d->aux_project.b, c.aux_output_dim * 4, hipMemcpyDeviceToHost));
   }
-  (void)D; (void)M;
   // the interpolated position embeddings were made from the previous weights: drop every cached shape and rebuild the
   // current one from the committed parameters
   da3_drop_shapes(m);
@@ -360,9 +367,8 @@ static int da3_build_tables(md_model_s* m, md_model_s::Da3State::ShapeTables& t)
     MD_HIP(hipMemcpy(t.rope_sin, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
   }
   if (d->ph != M || d->pw != M) {  // position embedding interpolated from the parameter's native grid
-    const float* pos_param = P32(m, "backbone.pretrained.pos_embed");
     std::vector<float> pos((size_t)(1 + M * M) * D);
-    MD_HIP(hipMemcpy(pos.data(), pos_param, pos.size() * 4, hipMemcpyDeviceToHost));
+    MD_HIP(hipMemcpy(pos.data(), d->pos_native, pos.size() * 4, hipMemcpyDeviceToHost));
     std::vector<float> ip = interpolate_pos_embed(pos, M, D, d->ph, d->pw);
     MD_HIP(hipMalloc((void**)&t.pos_used, ip.size() * 4));
     MD_HIP(hipMemcpy(t.pos_used, ip.data(), ip.size() * 4, hipMemcpyHostToDevice));
@@ -437,9 +443,104 @@ static int da3_set_shape(md_model_s* m, int H, int W, bool force) {
   d->rope_sin = t.rope_sin;
   d->pos_used = t.pos_used;
   d->tok_index = &t.tok_index;
-  d->vit.pos = t.pos_used ? t.pos_used : P32(m, "backbone.pretrained.pos_embed");
+  d->vit.pos = t.pos_used ? t.pos_used : d->pos_native;
   MD_HIP(hipDeviceSynchronize());
   return MD_OK;
+}
+
+// the packs of the DPT head (behind the backbone's, vit_add_packs) ...
+static void da3_add_packs(md_model_s* m) {
+  const Da3Cfg& cfg = m->da3->cfg;
+  const int F = cfg.features;
+  const int* oc = cfg.out_channels;
+  const std::string& hp = m->da3->hp;
+  for (int s = 0; s < 4; ++s) add_pack(m, hp + ".projects." + std::to_string(s) + ".weight", PACK_NK, oc[s], m->da3->din, 1);
+  add_pack(m, hp + ".resize_layers.0.conv_t.weight", PACK_DECONV, oc[0], oc[0], 4);
+  add_pack(m, hp + ".resize_layers.1.conv_t.weight", PACK_DECONV, oc[1], oc[1], 2);
+  add_pack(m, hp + ".resize_layers.3.conv.weight", PACK_CONV3, oc[3], oc[3], 3);
+  for (int s = 0; s < 4; ++s) add_pack(m, hp + ".scratch.layer" + std::to_string(s + 1) + "_rn.weight", PACK_CONV3, F, oc[s], 3);
+  for (const char* suffix : {"", "_aux"}) {
+    if (suffix[0] && !cfg.dual_head) continue;
+    for (int i = 1; i <= 4; ++i) {
+      const std::string r = hp + ".scratch.refinenet" + std::to_string(i) + suffix;
+      for (const char* u : {"residual1", "residual2"}) {
+        add_pack(m, r + "." + u + ".conv1.weight", PACK_CONV3, F, F, 3);
+        add_pack(m, r + "." + u + ".conv2.weight", PACK_CONV3, F, F, 3);
+      }
+      add_pack(m, r + ".out_conv.weight", PACK_NK, F, F, 1);
+    }
+  }
+  add_pack(m, hp + ".scratch.output_conv1.weight", PACK_CONV3, F / 2, F, 3);
+  add_pack(m, hp + ".scratch.output_conv2.conv1.weight", PACK_CONV3, 32, F / 2, 3);
+  if (cfg.dual_head) {  // only the last aux level reaches the outputs (build_aux_logits, dpt.rs:405-440)
+    const std::string lv = std::to_string(cfg.aux_levels - 1);
+    int cin = F;
+    for (int j = 0; j < cfg.aux_out1_conv_num; ++j) {
+      const int cout = j % 2 == 0 ? F / 2 : F;
+      add_pack(m, hp + ".scratch.output_conv1_aux." + lv + ".layers." + std::to_string(j) + ".weight", PACK_CONV3, cout, cin, 3);
+      cin = cout;
+    }
+    add_pack(m, hp + ".scratch.output_conv2_aux." + lv + ".reduce.weight", PACK_CONV3, 32, F / 2, 3);
+  }
+}
+
+// ... and the tables of everything behind the backbone (after the packed arena is placed)
+static int da3_bind(md_model_s* m) {
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const std::string &hp = d->hp, sc = hp + ".scratch.", bp = "backbone.pretrained";
+  Binder bd{m, {}};
+  d->pos_native = bd.p32(bp + ".pos_embed");
+  d->head_norm_g = bd.p32(hp + ".norm.gamma", c.dual_head);
+  d->head_norm_b = bd.p32(hp + ".norm.beta", c.dual_head);
+  d->camera_token = bd.p32(bp + ".camera_token", c.dual_head);
+  for (int s = 0; s < 4; ++s) {
+    d->proj[s] = bd.conv(hp + ".projects." + std::to_string(s));
+    d->layer_rn[s] = bd.conv(sc + "layer" + std::to_string(s + 1) + "_rn", false);
+  }
+  d->resize[0] = bd.conv(hp + ".resize_layers.0.conv_t");
+  d->resize[1] = bd.conv(hp + ".resize_layers.1.conv_t");
+  d->resize[3] = bd.conv(hp + ".resize_layers.3.conv");
+  for (int g = 0; g < (c.dual_head ? 2 : 1); ++g)
+    for (int lvl = 0; lvl < 4; ++lvl) {
+      const std::string r = sc + "refinenet" + std::to_string(lvl + 1) + (g ? "_aux" : "");
+      if (lvl != 3) d->res[lvl][0][g] = {bd.conv(r + ".residual1.conv1"), bd.conv(r + ".residual1.conv2")};
+      d->res[lvl][1][g] = {bd.conv(r + ".residual2.conv1"), bd.conv(r + ".residual2.conv2")};
+      d->out_conv[lvl][g] = bd.conv(r + ".out_conv");
+    }
+  d->oc1 = bd.conv(sc + "output_conv1");
+  d->oc2_1 = bd.conv(sc + "output_conv2.conv1");
+  d->oc2_2 = {bd.p32(sc + "output_conv2.conv2.weight"), bd.p32(sc + "output_conv2.conv2.bias")};
+  if (c.dual_head) {
+    const std::string lv = std::to_string(c.aux_levels - 1), oh = sc + "output_conv2_aux." + lv;
+    for (int j = 0; j < c.aux_out1_conv_num; ++j) d->aux_neck.push_back(bd.conv(sc + "output_conv1_aux." + lv + ".layers." + std::to_string(j)));
+    d->aux_reduce = bd.conv(oh + ".reduce");
+    d->aux_project = {bd.p32(oh + ".project.weight"), bd.p32(oh + ".project.bias")};
+    auto cw = [&](const char* n) { return bd.p32(std::string("camera_decoder.") + n); };
+    CamDecW& w = d->cam_dec;
+    w.w1 = cw("backbone_1.weight"); w.b1 = cw("backbone_1.bias"); w.w2 = cw("backbone_2.weight"); w.b2 = cw("backbone_2.bias");
+    w.wt = cw("fc_t.weight"); w.bt = cw("fc_t.bias"); w.wq = cw("fc_qvec.weight"); w.bq = cw("fc_qvec.bias");
+    w.wf = cw("fc_fov.weight"); w.bf = cw("fc_fov.bias");
+  }
+  if (c.camera_encoder) {  // optional here: da3_camera_encoder reports what is missing when it runs
+    auto ce = [&](const std::string& n) { return bd.p32("camera_encoder." + n, false); };
+    CamEncW& w = d->cam_enc;
+    w.fc1_w = ce("pose_branch.fc1.weight"); w.fc1_b = ce("pose_branch.fc1.bias");
+    w.fc2_w = ce("pose_branch.fc2.weight"); w.fc2_b = ce("pose_branch.fc2.bias");
+    w.tn_g = ce("token_norm.gamma"); w.tn_b = ce("token_norm.beta");
+    w.on_g = ce("trunk_norm.gamma"); w.on_b = ce("trunk_norm.beta");
+    w.depth = c.cam_trunk_depth;
+    for (int i = 0; i < std::min(w.depth, (int)CamEncW::kMaxDepth); ++i) {
+      const std::string bk = "trunk." + std::to_string(i) + ".";
+      CamEncW::Blk& k = w.blk[i];
+      k.n1g = ce(bk + "norm1.gamma"); k.n1b = ce(bk + "norm1.beta"); k.n2g = ce(bk + "norm2.gamma"); k.n2b = ce(bk + "norm2.beta");
+      k.qkv_w = ce(bk + "attn.qkv.weight"); k.qkv_b = ce(bk + "attn.qkv.bias");
+      k.proj_w = ce(bk + "attn.proj.weight"); k.proj_b = ce(bk + "attn.proj.bias"); k.ls1 = ce(bk + "ls1.gamma");
+      k.fc1_w = ce(bk + "mlp.fc1.weight"); k.fc1_b = ce(bk + "mlp.fc1.bias");
+      k.fc2_w = ce(bk + "mlp.fc2.weight"); k.fc2_b = ce(bk + "mlp.fc2.bias"); k.ls2 = ce(bk + "ls2.gamma");
+    }
+  }
+  return bd.status();
 }
 
 int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
@@ -483,75 +584,18 @@ int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
     model_destroy(m);
     return code;
   };
-  m->params = da3_param_specs(cfg, MD_INIT_REFERENCE);
-  size_t off = 0;
-  std::vector<size_t> offs;
-  for (size_t i = 0; i < m->params.size(); ++i) {
-    m->pindex[m->params[i].name] = (int)i;
-    offs.push_back(off);
-    off += align_up(m->params[i].count() * 4, 256);
-  }
-  m->w32_bytes = off;
-  if (hipMalloc((void**)&m->w32_base, m->w32_bytes) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the fp32 weights failed", m->w32_bytes);
-    return fail(MD_ERR_OOM);
-  }
-  (void)hipMemset(m->w32_base, 0, m->w32_bytes);
-  for (size_t i = 0; i < m->params.size(); ++i) m->w32.push_back((float*)(m->w32_base + offs[i]));
-
-  const int D = v.D, F = cfg.features;
-  const int* oc = cfg.out_channels;
+  int st = alloc_param_arena(m, da3_param_specs(cfg, MD_INIT_REFERENCE));
+  if (st != MD_OK) return fail(st);
+  const int D = v.D;
   const std::string bp = "backbone.pretrained";
   vit_add_packs(m, bp, v);
-  const std::string hp = d->hp;
-  for (int s = 0; s < 4; ++s) add_pack(m, hp + ".projects." + std::to_string(s) + ".weight", PACK_NK, oc[s], d->din, 1);
-  add_pack(m, hp + ".resize_layers.0.conv_t.weight", PACK_DECONV, oc[0], oc[0], 4);
-  add_pack(m, hp + ".resize_layers.1.conv_t.weight", PACK_DECONV, oc[1], oc[1], 2);
-  add_pack(m, hp + ".resize_layers.3.conv.weight", PACK_CONV3, oc[3], oc[3], 3);
-  for (int s = 0; s < 4; ++s) add_pack(m, hp + ".scratch.layer" + std::to_string(s + 1) + "_rn.weight", PACK_CONV3, F, oc[s], 3);
-  for (const char* suffix : {"", "_aux"}) {
-    if (suffix[0] && !cfg.dual_head) continue;
-    for (int i = 1; i <= 4; ++i) {
-      const std::string r = hp + ".scratch.refinenet" + std::to_string(i) + suffix;
-      for (const char* u : {"residual1", "residual2"}) {
-        add_pack(m, r + "." + u + ".conv1.weight", PACK_CONV3, F, F, 3);
-        add_pack(m, r + "." + u + ".conv2.weight", PACK_CONV3, F, F, 3);
-      }
-      add_pack(m, r + ".out_conv.weight", PACK_NK, F, F, 1);
-    }
-  }
-  add_pack(m, hp + ".scratch.output_conv1.weight", PACK_CONV3, F / 2, F, 3);
-  add_pack(m, hp + ".scratch.output_conv2.conv1.weight", PACK_CONV3, 32, F / 2, 3);
-  if (cfg.dual_head) {  // only the last aux level reaches the outputs (build_aux_logits, dpt.rs:405-440)
-    const std::string lv = std::to_string(cfg.aux_levels - 1);
-    int cin = F;
-    for (int j = 0; j < cfg.aux_out1_conv_num; ++j) {
-      const int cout = j % 2 == 0 ? F / 2 : F;
-      add_pack(m, hp + ".scratch.output_conv1_aux." + lv + ".layers." + std::to_string(j) + ".weight", PACK_CONV3, cout, cin, 3);
-      cin = cout;
-    }
-    add_pack(m, hp + ".scratch.output_conv2_aux." + lv + ".reduce.weight", PACK_CONV3, 32, F / 2, 3);
-  }
-  size_t poff = 0;
-  for (auto& e : m->packs) {
-    e.dst = (void*)poff;
-    poff += align_up(e.bytes + 256, 256);
-  }
-  m->wpk_bytes = poff;
-  if (hipMalloc((void**)&m->wpk_base, m->wpk_bytes) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the packed weights failed", m->wpk_bytes);
-    return fail(MD_ERR_OOM);
-  }
-  (void)hipMemset(m->wpk_base, 0, m->wpk_bytes);
-  for (auto& e : m->packs) e.dst = m->wpk_base + (size_t)e.dst;
-
+  da3_add_packs(m);
+  if ((st = place_packs(m)) != MD_OK) return fail(st);
   VitW& w = d->vit;
   vit_bind(m, bp, v.depth, w);
   for (int i = 0; i < v.depth; ++i)  // the extended backbone alternates local and global blocks from ext_block_start on
     w.blk[i].global = cfg.dual_head && i >= cfg.ext_block_start && i % 2 == 1;
-  d->head_norm_g = P32(m, hp + ".norm.gamma");
-  d->head_norm_b = P32(m, hp + ".norm.beta");
-  d->camera_token = P32(m, bp + ".camera_token");
+  if ((st = da3_bind(m)) != MD_OK) return fail(st);
   if (fp8) {
     const size_t per_block = (size_t)12 * D * D + (size_t)(3 * D + D + 4 * D + D) * 4 + 8 * 256;
     if (hipMalloc((void**)&d->w8_base, per_block * v.depth) != hipSuccess) {
@@ -574,12 +618,9 @@ int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out) {
   (void)hipMemset(m->zero_page, 0, 4096);
   // workspace for the configured size + its tables (PosEmbedCache, dpt.rs:784-833: built once per shape); other sizes get
   // theirs on their first infer call (da3_set_shape)
-  {
-    d->ih = 0;
-    d->iw = 0;
-    const int st = da3_set_shape(m, img_h, img_w, true);
-    if (st != MD_OK) return fail(st);
-  }
+  d->ih = 0;
+  d->iw = 0;
+  if ((st = da3_set_shape(m, img_h, img_w, true)) != MD_OK) return fail(st);
   m->alloc_count = 0;  // count what the infer calls allocate, not the construction
   (void)hipDeviceSynchronize();
   *out = m;
@@ -592,6 +633,7 @@ void da3_frame_info(md_model_t m, int* patch, int* cur_h, int* cur_w) {
   *cur_w = m->da3->tok_index ? m->da3->iw : 0;
 }
 
+const Da3Cfg& da3_cfg(md_model_t m) { return m->da3->cfg; }
 long da3_shape_builds(md_model_t m) { return (m && m->da3) ? m->da3->table_builds : 0; }
 
 void da3_destroy_state(md_model_t m) {
@@ -601,26 +643,6 @@ void da3_destroy_state(md_model_t m) {
   m->da3->shapes.clear();
   delete m->da3;
   m->da3 = nullptr;
-}
-
-int da3_init_seeded(md_model_t m, uint64_t seed, int scheme) {
-  if (scheme != MD_INIT_REFERENCE && scheme != MD_INIT_PARITY) MD_FAIL(MD_ERR_INVALID_ARG, "unknown init scheme %d", scheme);
-  MD_HIP(hipSetDevice(m->dev->ordinal));
-  std::vector<ParamSpec> specs = da3_param_specs(m->da3->cfg, scheme);
-  if (specs.size() != m->params.size()) MD_FAIL(MD_ERR_FORMAT, "internal: inventory mismatch");
-  std::vector<float> tmp;
-  for (size_t i = 0; i < specs.size(); ++i) {
-    const size_t n = specs[i].count();
-    tmp.resize(n);
-    uniform_stream(specs[i].name, seed, n, specs[i].lo, specs[i].hi, tmp.data());
-    MD_HIP(hipMemcpy(m->w32[i], tmp.data(), n * 4, hipMemcpyHostToDevice));
-  }
-  return model_commit(m);
-}
-
-int da3_load_container(md_model_t m, const char* path) {
-  MD_TRY(model_load_params_from_container(m, path));
-  return model_commit(m);
 }
 
 static int da3_tok_index(md_model_s* m, int B, int** out) {
@@ -661,6 +683,419 @@ int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   return run_with_graph(m, st, key, eligible, body);
 }
 
+// ---- the stages of one call (da3_infer_eager) ----
+// what the stages share of one call
+struct Da3Call {
+  const Da3Outputs& outp;
+  int in_kind, out_kind, H, W;
+  bool want_aux, want_cam;
+  int G;                           // pyramid weight groups: 2 = main | aux in the same launches (want_aux)
+  int sh[4], sw[4];                // prepare_stage sizes (rows, columns)
+  const float* cam_tok = nullptr;  // the camera encoder's tokens [B, D] (null: the learned reference-view token)
+  float* depth_dev = nullptr;      // device home of `depth` (infer_raw: of `raw_logits`)
+  const void* c1_map = nullptr;    // output_conv1's result
+  const void* aux_cur = nullptr;   // want_aux: the aux neck's first map
+};
+
+static int host_out(hipStream_t st, int out_kind, float* dst, const float* src, size_t n) {
+  if (out_kind == MD_MEM_HOST && dst) MD_HIP(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, st));
+  return MD_OK;
+}
+
+// fused tail: out_c[img][pixel] = act_c(w_c . relu(conv3x3(in) + b1) + b_c) for `nch` channels in ONE launch over a
+// [B, hh, ww, 64-padded] map (ConvStack / `reduce` + `project`, dpt.rs:481-513,1287-1290)
+struct TailCh { const float* w; float b; int act; float* out; long bstride; };
+static int tail(Run& r, const char* name, const void* in, int hh, int ww, const ConvW& w1, const TailCh* chs, int nch) {
+  if (nch <= 0) return MD_OK;
+  md_model_s* m = r.m;
+  GemmParams p;
+  p.N = 32; p.ngroups = 1; p.g_rows[0] = r.B * hh * ww; p.W[0] = w1.w;
+  p.A = in; p.cH = hh; p.cW = ww; p.zero_page = m->zero_page;
+  split_conv_a(m, p, cpad(m, m->da3->cfg.features / 2), 0);
+  p.epi = EPI_HEAD; p.bias[0] = w1.b; p.head_nch = nch; p.head_plane = hh * ww;
+  for (int i = 0; i < nch; ++i) {
+    p.head_wc[i] = chs[i].w; p.head_bs[i] = chs[i].b; p.head_acts[i] = chs[i].act; p.head_out[i] = chs[i].out; p.head_bstride[i] = chs[i].bstride;
+  }
+  r.begin(name);
+  int s = launch_gemm(p, A_CONV3, m->prec, TILE_256x32, r.st);
+  r.end();
+  return s;
+}
+
+// `infer_from_tokens` (mod.rs:405-469): no backbone, no camera prediction; the head's token LayerNorm (mono: non-affine,
+// dpt.rs:761-766; dual: the affine `norm`, dpt.rs:308) on the caller's hook tokens, patch rows only
+static int da3_stage_tokens(Run& r, const Da3Call& k) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const Da3Outputs& outp = k.outp;
+  const int B = r.B, SS = d->SS, P = d->P, din = d->din;
+  if (outp.pose_encoding || outp.extrinsics || outp.intrinsics)
+    MD_FAIL(MD_ERR_UNSUPPORTED, "infer_from_tokens has no camera prediction (finalize_inference(head_output, None), mod.rs:468)");
+  const int T = outp.tokens_per_image;
+  if (T != P && T != P + 1)  // mod.rs:419-424: tokens == expected -> patch_start 0, else patch_token_start = 1
+    MD_FAIL(MD_ERR_SHAPE, "%d tokens per image for a %dx%d input: expected %d patch rows (or %d with a leading cls row)", T, k.H, k.W, P, P + 1);
+  for (int hk = 0; hk < 4; ++hk)
+    if (!outp.tokens[hk]) MD_FAIL(MD_ERR_LEVELS, "Backbone returned fewer hooks (%d) than requested (4)", hk);
+  const int start = T == P ? 0 : 1;
+  const size_t need = ((size_t)c.max_batch * SS + 64) * din;
+  bool grown = false;
+  MD_TRY(grow(m, r.st, d->tok_stage, need * 4, &grown));
+  if (grown) MD_HIP(hipMemset(d->tok_stage.p, 0, need * 4));
+  SeqGroups tg;
+  memset(&tg, 0, sizeof(tg));
+  tg.ngroups = 1;
+  tg.nseq[0] = B;
+  tg.a[0] = c.dual_head ? d->head_norm_g : nullptr;
+  tg.b[0] = c.dual_head ? d->head_norm_b : nullptr;
+  const hipMemcpyKind kind = k.in_kind == MD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  for (int hk = 0; hk < 4; ++hk) {
+    for (int b = 0; b < B; ++b)  // patch rows of image b -> rows b*SS + 1 .. of the staging tensor (the layout the head gathers from)
+      MD_HIP(hipMemcpyAsync(d->tok_stage.p + ((size_t)b * SS + 1) * din, outp.tokens[hk] + ((size_t)b * T + start) * din, (size_t)P * din * 4,
+                            kind, r.st));
+    r.begin("layernorm");
+    MD_TRY(launch_layernorm(d->tok_stage.p, d->hookn[hk], (long)B * SS, din, 1e-5f, SS, tg, m->prec, 0, r.st));
+    r.end();
+    if (m->taps_enabled) MD_TRY(r.tap_token_rows(("backbone_tokens_" + std::to_string(hk)).c_str(), d->tok_stage.p, SS, 1, P, din, din, 0));
+  }
+  return MD_OK;
+}
+
+// camera encoder (`infer_with_camera`, mod.rs:522-527): the known cameras -> one token per image (k.cam_tok)
+static int da3_camera_encoder(Run& r, Da3Call& k) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const Da3Outputs& outp = k.outp;
+  const int B = r.B, V = outp.cam_views, D = c.vit.D;
+  if (V < 1 || V > MD_CAM_MAX_VIEWS) MD_FAIL(MD_ERR_SHAPE, "camera inputs with %d views (1..%d supported)", V, MD_CAM_MAX_VIEWS);
+  const size_t n_in = (size_t)B * V * 21, n_tok = align_up((size_t)B * D, 64);
+  const size_t need = align_up(n_in, 64) + n_tok + camera_encoder_scratch_floats(B, V, D);
+  MD_TRY(grow(m, r.st, d->cam_enc_ws, need * 4));
+  const float *e_dev = outp.cam_extrinsics, *k_dev = outp.cam_intrinsics;
+  if (k.in_kind == MD_MEM_HOST) {
+    MD_HIP(hipMemcpyAsync(d->cam_enc_ws.p, outp.cam_extrinsics, (size_t)B * V * 12 * 4, hipMemcpyHostToDevice, r.st));
+    MD_HIP(hipMemcpyAsync(d->cam_enc_ws.p + (size_t)B * V * 12, outp.cam_intrinsics, (size_t)B * V * 9 * 4, hipMemcpyHostToDevice, r.st));
+    e_dev = d->cam_enc_ws.p; k_dev = d->cam_enc_ws.p + (size_t)B * V * 12;
+  }
+  float* cam_tok = d->cam_enc_ws.p + align_up(n_in, 64);
+  const CamEncW& w = d->cam_enc;
+  if (w.depth > CamEncW::kMaxDepth) MD_FAIL(MD_ERR_UNSUPPORTED, "camera encoder trunk of %d blocks", w.depth);
+  for (int i = 0; i < w.depth; ++i)
+    if (!w.blk[i].qkv_w || !w.blk[i].ls2) MD_FAIL(MD_ERR_FORMAT, "camera encoder block %d is not in the inventory", i);
+  if (!w.fc1_w || !w.on_b) MD_FAIL(MD_ERR_FORMAT, "camera encoder is not in the inventory");
+  r.begin("camera_encoder");
+  MD_TRY(launch_camera_encoder(e_dev, k_dev, B, V, D, c.cam_heads, k.H, k.W, c.cam_ln_eps, c.ln_eps, w, cam_tok + n_tok, cam_tok, r.st));
+  r.end();
+  MD_TRY(r.tap_f32("camera_token", cam_tok, B, D, 0, 0));  // CameraEncoder::forward's result (camera.rs:89-110)
+  k.cam_tok = cam_tok;
+  return MD_OK;
+}
+
+// the backbone: patchify, patch embedding, the blocks and their hooks (d->hookn)
+static int da3_backbone(Run& r, const Da3Call& k, const float* x_dev) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const ViTDims& v = c.vit;
+  const int B = r.B, D = v.D, SS = d->SS, NT = d->NT, P = d->P;
+  r.begin("patchify");  // + the cls rows (cls + pos[0]) and the zero padding rows of the residual stream, in the same launch
+  MD_TRY(launch_patchify(x_dev, B, k.H, k.W, v.ps, d->Kp, d->patches, m->prec, r.st, d->xres, SS, NT, D, d->vit.cls, d->vit.pos));
+  r.end();
+  SeqGroups sg;
+  memset(&sg, 0, sizeof(sg));
+  sg.ngroups = 1;
+  sg.nseq[0] = B;
+  {
+    GemmParams p;
+    p.N = D; p.ngroups = 1; p.g_rows[0] = B * P; p.W[0] = d->vit.pe_w; p.bias[0] = d->vit.pe_b; p.pos[0] = d->vit.pos;
+    p.A = d->patches;
+    split_dense_a(m, p, d->Kp, d->Kp, 0);
+    p.epi = EPI_PATCH_EMBED; p.out = d->xres; p.ldo = D; p.seq_stride = SS; p.seq_patches = P; p.embed = D;
+    r.begin("patch_embed");
+    MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_AUTO, r.st));
+    r.end();
+  }
+  const long rows = (long)B * SS;
+  int hook_slot = 0;
+  // The residual stream lives in `vp.x`. A GLOBAL block of the extended backbone needs the state behind the last LOCAL block
+  // for its hook (cat(x_local, LayerNorm(x))): its output projection therefore writes x + ls * (...) into the other buffer
+  // (GemmParams::resid_src) and the two swap -- the copy of the whole stream that used to precede every global block is gone.
+  VitPlan vp;
+  vp.vit[0] = &d->vit; vp.gcnt[0] = B; vp.WS = B;
+  vp.D = D; vp.heads = v.heads; vp.SS = SS; vp.NT = NT; vp.kpad = d->kpad; vp.ln_eps = c.ln_eps;
+  vp.x = d->xres; vp.xalt = d->xlocal; vp.xn = d->xn; vp.qk = d->qk; vp.vT = d->vT; vp.ao = d->ao; vp.hbuf = d->hbuf; vp.scores = d->scores;
+  vp.lin_prec = d->fp8 ? MD_PREC_FP8 : m->prec;
+  if (d->fp8) { vp.a_scale = md_model_s::Da3State::kActScale; vp.h_scale = md_model_s::Da3State::kHidScale; }
+  vp.qk_norm_eps = c.qk_norm_eps; vp.rope_cos = d->rope_cos; vp.rope_sin = d->rope_sin; vp.rope_pw = d->pw;
+  // entering block ext_block_start the camera token takes the cls slot -- the encoder's (mod.rs:522-531) or the learned
+  // reference-view one
+  vp.tok0_block = c.dual_head ? c.ext_block_start : -1;
+  vp.tok0 = k.cam_tok ? k.cam_tok : d->camera_token;
+  vp.tok0_stride = k.cam_tok ? D : 0;
+  for (int i = 0; i < v.depth; ++i) {
+    MD_TRY(run_vit_block(r, vp, i));
+    const float* xcur = vp.x;
+    const float* xl = d->vit.blk[i].global ? vp.xalt : xcur;  // a local block is its own "last local" state; behind a global block the other buffer holds it
+    for (int hk = 0; hk < 4; ++hk) {  // a block may feed several hooks
+      if (c.hook_ids[hk] != i) continue;
+      const std::string tn = "backbone_tokens_" + std::to_string(hk);  // DepthTrace::backbone_tokens (mod.rs:241-246,344-347)
+      if (c.dual_head) {
+        // hooks = LayerNorm_head(cat(x after the last local block, LayerNorm_final(x))); the camera feature is
+        // token 0 of the raw concat at the last hook
+        r.begin("hook_cat_ln");
+        MD_TRY(launch_hook_cat_ln(xl, xcur, rows, SS, NT, D, d->vit.norm_g, d->vit.norm_b, c.ln_eps, d->head_norm_g,
+                                  d->head_norm_b, 1e-5f, d->hookn[hk], hk == 3 ? d->cam_raw : nullptr, m->prec, r.st));
+        r.end();
+        if (m->taps_enabled) {  // cat(x_local, LayerNorm_final(x)) patch rows
+          sg.a[0] = d->vit.norm_g; sg.b[0] = d->vit.norm_b;
+          MD_TRY(launch_layernorm(xcur, d->lnf, rows, D, c.ln_eps, SS, sg, m->prec, 1, r.st));
+          MD_TRY(r.tap_token_rows(tn.c_str(), xl, SS, 1, P, D, 2 * D, 0));
+          MD_TRY(r.tap_token_rows(tn.c_str(), d->lnf, SS, 1, P, D, 2 * D, D));
+        }
+      } else {
+        // hooks (mod.rs:202-215): final LayerNorm of the block output, then the head's non-affine token
+        // norm (apply_token_norm, dpt.rs:761-766: biased variance, eps 1e-5)
+        sg.a[0] = d->vit.norm_g; sg.b[0] = d->vit.norm_b;
+        r.begin("layernorm");
+        MD_TRY(launch_layernorm(xcur, d->lnf, rows, D, c.ln_eps, SS, sg, m->prec, 1, r.st));
+        r.end();
+        if (m->taps_enabled) MD_TRY(r.tap_token_rows(tn.c_str(), d->lnf, SS, 1, P, D, D, 0));
+        sg.a[0] = nullptr; sg.b[0] = nullptr;
+        r.begin("layernorm");
+        MD_TRY(launch_layernorm(d->lnf, d->hookn[hk], rows, D, 1e-5f, SS, sg, m->prec, 0, r.st));
+        r.end();
+      }
+      ++hook_slot;
+    }
+  }
+  if (hook_slot < 4) MD_FAIL(MD_ERR_LEVELS, "Backbone returned fewer hooks (%d) than requested (4)", hook_slot);  // mod.rs:532-537
+  return MD_OK;
+}
+
+// DPT head: prepare_stage (dpt.rs:282-317 / 649-689) -> the layerN_rn maps (d->rn, d->rnr)
+static int da3_prepare_stages(Run& r, const Da3Call& k) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const int B = r.B, P = d->P, ph = d->ph, pw = d->pw, F = c.features, Fp = cpad(m, F);
+  const int* oc = c.out_channels;
+  int* tok_idx = nullptr;
+  MD_TRY(da3_tok_index(m, B, &tok_idx));
+  for (int s = 0; s < 4; ++s) {
+    const int ocp = cpad(m, oc[s]);
+    {  // 1x1 projection over gathered patch tokens + 0.1 * UV position table
+      GemmParams p;
+      p.N = oc[s]; p.ngroups = 1; p.g_rows[0] = B * P; p.W[0] = d->proj[s].w; p.bias[0] = d->proj[s].b;
+      p.A = d->hookn[s]; p.a_index = tok_idx;
+      split_dense_a(m, p, d->din, d->din, 0);
+      p.epi = EPI_STORE; p.out = d->sp[s];
+      split_out(m, p, ocp, true);
+      p.res1 = d->pos_stage[s]; p.ldr = p.ldo; p.r_plane = p.o_plane; p.res_mod = P;
+      r.begin("head_proj");
+      MD_TRY(launch_gemm(p, A_INDEXED, m->prec, TILE_AUTO, r.st));
+      r.end();
+    }
+    const void* feat = d->sp[s];
+    if (s == 0 || s == 1) {  // ConvTranspose k4s4 / k2s2 (+bias)
+      MD_TRY(deconv2(r, "head_deconv", d->sp[s], ocp, nullptr, ph, pw, d->resize[s].w, ocp, oc[s], d->resize[s].b, d->sr[s], ocp, 0, nullptr,
+                     s == 0 ? 4 : 2));
+      feat = d->sr[s];
+    } else if (s == 3) {  // Conv2d 3x3 stride 2 pad 1 (+bias)
+      GemmParams p;
+      p.N = oc[3]; p.ngroups = 1; p.g_rows[0] = B * d->h3h * d->h3w;
+      p.W[0] = d->resize[3].w; p.bias[0] = d->resize[3].b;
+      p.A = d->sp[3]; p.cH = ph; p.cW = pw; p.cOH = d->h3h; p.cOW = d->h3w; p.cstride = 2; p.zero_page = m->zero_page;
+      split_conv_a(m, p, ocp, 0);
+      p.epi = EPI_STORE; p.out = d->sr[3];
+      split_out(m, p, ocp, true);
+      r.begin("head_conv_s2");
+      MD_TRY(launch_gemm(p, A_CONV3, m->prec, TILE_AUTO, r.st));
+      r.end();
+      feat = d->sr[3];
+    }
+    // layerN_rn: 3x3, no bias -> features (+ relu copy for the residual units)
+    MD_TRY(conv3(r, "head_conv3x3", feat, k.sh[s], k.sw[s], ocp, &d->layer_rn[s], F, d->rn[s], Fp, ACT_NONE, nullptr, nullptr, d->rnr[s]));
+    if (m->taps_enabled) {  // prepare_stage output and its layerN_rn map (dpt.rs:649-703)
+      MD_TRY(r.tap_nhwc(("stage_" + std::to_string(s)).c_str(), feat, oc[s], k.sh[s], k.sw[s], ocp));
+      MD_TRY(r.tap_nhwc(("layer" + std::to_string(s + 1) + "_rn").c_str(), d->rn[s], F, k.sh[s], k.sw[s], Fp));
+    }
+  }
+  return MD_OK;
+}
+
+// the four FeatureFusionBlocks (dpt.rs:1206-1222) from the coarsest stage up, then output_conv1 (dpt.rs:337-344). Dual head: the main
+// fusion pyramid (depth, confidence) and the aux fusion pyramid (rays, confidence) have the same shapes and share their inputs (the
+// layerN_rn maps): with the aux outputs wanted they run in the SAME launches as two weight groups -- group 0 = main on images [0, B),
+// group 1 = aux on images [B, 2B) of every pyramid map. A 64-feature 3x3 convolution costs ~11 us at 37^2 and ~14 us at 296^2
+// (launch floor + nine dependent k-tiles, not throughput), so the second group is nearly free where a second chain of launches was
+// not (round 4: 44 -> 22 pyramid launches; the side-stream form overlapped only a third of the aux pyramid,
+// profiles/r04_cfg2_branches.txt).
+static int da3_pyramid(Run& r, Da3Call& k) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const int B = r.B, G = k.G, ph = d->ph, pw = d->pw, F = d->cfg.features, Fp = cpad(m, F), F2p = cpad(m, F / 2);
+  const size_t px_bytes = (size_t)Fp * m->esz * m->xm;  // one pixel of an F-channel map
+  const int target[4] = {8 * ph, 4 * ph, 2 * ph, ph}, targw[4] = {8 * pw, 4 * pw, 2 * pw, pw};  // output size of refinenet1..4
+  const void* top = nullptr;
+  for (int lvl = 3; lvl >= 0; --lvl) {
+    const void *yx = d->rn[3], *yxr = d->rnr[3];
+    if (lvl != 3) {
+      MD_TRY(residual_unit(r, "head_conv3x3", d->res[lvl][0], G, k.sh[lvl], k.sw[lvl], Fp, F, d->rn[lvl], d->rnr[lvl], true, top, d->t, d->x, d->xr));
+      yx = d->x; yxr = d->xr;
+    }
+    MD_TRY(residual_unit(r, "head_conv3x3", d->res[lvl][1], G, k.sh[lvl], k.sw[lvl], Fp, F, yx, yxr, lvl == 3, nullptr, d->t, d->y, nullptr));
+    r.begin("head_resize");
+    MD_TRY(launch_resize_nhwc(d->y, G * B, k.sh[lvl], k.sw[lvl], F, Fp, d->up, target[lvl], targw[lvl], Fp, MD_INTERP_BURN, nullptr, m->prec, r.st));
+    r.end();
+    {  // out_conv 1x1 (+bias), one weight set per group
+      GemmParams p;
+      const int M2 = B * target[lvl] * targw[lvl];
+      p.N = F; p.ngroups = G;
+      for (int g = 0; g < G; ++g) {
+        p.g_rows[g] = M2; p.g_row0[g] = g * M2; p.g_arow0[g] = g * M2;
+        p.W[g] = d->out_conv[lvl][g].w; p.bias[g] = d->out_conv[lvl][g].b;
+      }
+      p.A = d->up;
+      split_dense_a(m, p, Fp, Fp, 0);
+      p.epi = EPI_STORE; p.out = d->o;
+      split_out(m, p, Fp, true);
+      r.begin("head_out_conv");
+      MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_AUTO, r.st));
+      r.end();
+    }
+    top = d->o;
+    if (m->taps_enabled)  // FeatureFusionBlock outputs (dpt.rs:705-720), main and aux pyramids
+      for (int g = 0; g < G; ++g)
+        MD_TRY(r.tap_nhwc(("refinenet" + std::to_string(lvl + 1) + (g ? "_aux" : "")).c_str(),
+                          (const char*)d->o + (size_t)g * B * target[lvl] * targw[lvl] * px_bytes, F, target[lvl], targw[lvl], Fp));
+  }
+  // output_conv1 and the first convolution of the aux neck (dpt.rs:1085-1113) are both 3x3 F -> F/2 on the 8ph x 8pw results of their
+  // pyramids: one launch, two weight groups, into the (now free) `up` map -- main | aux
+  const ConvW c1w[2] = {d->oc1, k.want_aux ? d->aux_neck[0] : ConvW{}};
+  void* c1 = k.want_aux ? d->up : d->c1;
+  MD_TRY(conv3(r, "head_conv3x3", d->o, 8 * ph, 8 * pw, Fp, c1w, F / 2, c1, F2p, ACT_NONE, nullptr, nullptr, nullptr, 0, G));
+  k.c1_map = c1;
+  if (k.want_aux) k.aux_cur = (const char*)c1 + (size_t)B * 64 * ph * pw * F2p * m->esz * m->xm;
+  return MD_OK;
+}
+
+// aux branch (build_aux_logits, dpt.rs:356-441): the last level's 5-conv neck (its first convolution ran in da3_pyramid) -> + 2 x 0.1 x
+// UV -> reduce 3x3 -> ReLU -> project 1x1 (7 ch: 6 ray values + confidence)
+static int da3_aux_tail(Run& r, const Da3Call& k) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const Da3Outputs& outp = k.outp;
+  const int B = r.B, F = c.features, F2 = F / 2, F2p = cpad(m, F2), ah = 8 * d->ph, aw = 8 * d->pw;
+  const void* cur = k.aux_cur;
+  void* pp[2] = {d->up2, d->o2};
+  int cin = F2;
+  for (int j = 1; j < c.aux_out1_conv_num; ++j) {
+    const int cout = j % 2 == 0 ? F / 2 : F;
+    MD_TRY(conv3(r, "aux_conv3x3", cur, ah, aw, cpad(m, cin), &d->aux_neck[j], cout, pp[j & 1], cpad(m, cout), ACT_NONE, nullptr, nullptr, nullptr));
+    cur = pp[j & 1];
+    cin = cout;
+  }
+  void* hin = cur == d->up2 ? d->o2 : d->up2;
+  r.begin("head_resize");
+  MD_TRY(launch_resize_nhwc(cur, B, ah, aw, F2, F2p, hin, ah, aw, F2p, MD_INTERP_BURN, d->pos_aux, m->prec, r.st));
+  r.end();
+  if (m->taps_enabled) {  // DepthTrace::aux_stage_necks (last level) / aux_head_input (mod.rs:241-246)
+    MD_TRY(r.tap_nhwc("aux_neck", cur, F2, ah, aw, F2p));
+    MD_TRY(r.tap_nhwc("aux_head_input", hin, F2, ah, aw, F2p));
+  }
+  const size_t plane = (size_t)ah * aw;
+  const int K7 = c.aux_output_dim;
+  TailCh chs[8];
+  int nch = 0;
+  for (int ch = 0; ch < K7; ++ch) {  // aux lands as [B, 6, h, w], the confidence as [B, h, w]; host outputs through [B, 7, h, w] staging
+    const bool conf = ch == K7 - 1;
+    float* user = conf ? outp.aux_confidence : outp.aux;
+    if (!user) continue;
+    TailCh t;
+    t.w = (const float*)d->aux_project.w + 32 * ch; t.b = d->aux_bias[ch]; t.act = conf ? 3 : 2;
+    if (k.out_kind == MD_MEM_HOST) { t.out = d->aux_stage + (size_t)ch * plane; t.bstride = (long)K7 * plane; }
+    else if (conf) { t.out = user; t.bstride = (long)plane; }
+    else { t.out = user + (size_t)ch * plane; t.bstride = (long)(K7 - 1) * plane; }
+    chs[nch++] = t;
+  }
+  MD_TRY(tail(r, "aux_tail_fused", hin, ah, aw, d->aux_reduce, chs, nch));
+  if (k.out_kind == MD_MEM_HOST)
+    for (int ch = 0; ch < K7; ++ch) {
+      const bool conf = ch == K7 - 1;
+      float* user = conf ? outp.aux_confidence : outp.aux;
+      if (!user) continue;
+      for (int b = 0; b < B; ++b)
+        MD_TRY(host_out(r.st, k.out_kind, conf ? user + (size_t)b * plane : user + ((size_t)b * (K7 - 1) + ch) * plane,
+                        d->aux_stage + ((size_t)b * K7 + ch) * plane, plane));
+    }
+  return MD_OK;
+}
+
+// camera decoder (camera.rs:143-199) on the raw camera feature of the last hook, fp32: pose = (t3 | quat4 | relu(fov2)) rows [B, 9];
+// device outputs are written straight into the caller's buffers
+static int da3_camera_decoder(Run& r, const Da3Call& k) {
+  md_model_s::Da3State* d = r.m->da3;
+  const Da3Outputs& outp = k.outp;
+  const int B = r.B;
+  const bool dev_out = k.out_kind == MD_MEM_DEVICE;
+  float* pose = (dev_out && outp.pose_encoding) ? outp.pose_encoding : d->pose;
+  float* extr = (dev_out && outp.extrinsics) ? outp.extrinsics : d->extr;
+  float* intr = (dev_out && outp.intrinsics) ? outp.intrinsics : d->intr;
+  r.begin("camera_decoder");
+  MD_TRY(launch_camera_decoder(d->cam_raw, B, d->din, d->cam_dec, k.H, k.W, d->cam_h1, d->cam_h2, pose, outp.extrinsics ? extr : nullptr,
+                               outp.intrinsics ? intr : nullptr, r.st));
+  r.end();
+  if (!dev_out) {
+    if (outp.pose_encoding) MD_HIP(hipMemcpyAsync(outp.pose_encoding, pose, (size_t)B * 9 * 4, hipMemcpyDeviceToHost, r.st));
+    if (outp.extrinsics) MD_HIP(hipMemcpyAsync(outp.extrinsics, extr, (size_t)B * 12 * 4, hipMemcpyDeviceToHost, r.st));
+    if (outp.intrinsics) MD_HIP(hipMemcpyAsync(outp.intrinsics, intr, (size_t)B * 9 * 4, hipMemcpyDeviceToHost, r.st));
+  }
+  return MD_OK;
+}
+
+// main branch: output_conv1 -> resize to the image size (+ UV table) -> output_conv2 + activation
+static int da3_main_tail(Run& r, const Da3Call& k) {
+  md_model_s* m = r.m;
+  md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  const Da3Outputs& outp = k.outp;
+  const int B = r.B, ph = d->ph, pw = d->pw, IH = d->ih, IW = d->iw, F2 = c.features / 2, F2p = cpad(m, F2);
+  r.begin("head_resize");
+  MD_TRY(launch_resize_nhwc(k.c1_map, B, 8 * ph, 8 * pw, F2, F2p, d->c1r, IH, IW, F2p, MD_INTERP_BURN, d->pos_final, m->prec, r.st));
+  r.end();
+  if (m->taps_enabled) {
+    MD_TRY(r.tap_nhwc("output_conv1", k.c1_map, F2, 8 * ph, 8 * pw, F2p));
+    MD_TRY(r.tap_nhwc("head_input", d->c1r, F2, IH, IW, F2p));  // resized + UV table: the input of output_conv2
+  }
+  const float* w2 = (const float*)d->oc2_2.w;
+  const size_t out_elems = (size_t)B * IH * IW;
+  TailCh chs[8];
+  int nch = 0;
+  if (outp.raw_logits) {
+    // infer_raw (mod.rs:364-380): the dual head hands out `depth_logits` = output_conv2's result as it is (dpt.rs:337-354, 271);
+    // the mono head's `forward_raw` has its activation applied (dpt.rs:700)
+    if (c.output_dim > 8) MD_FAIL(MD_ERR_UNSUPPORTED, "infer_raw with %d channels", c.output_dim);
+    for (int ch = 0; ch < c.output_dim; ++ch)
+      chs[nch++] = TailCh{w2 + 32 * ch, d->main_bias[ch], c.dual_head ? 2 : 1, k.depth_dev + (size_t)ch * IH * IW, (long)c.output_dim * IH * IW};
+    MD_TRY(tail(r, "head_tail_fused", d->c1r, IH, IW, d->oc2_1, chs, nch));
+    MD_TRY(host_out(r.st, k.out_kind, outp.raw_logits, k.depth_dev, out_elems * c.output_dim));
+  } else {
+    float* cd = nullptr;
+    chs[nch++] = TailCh{w2, d->main_bias[0], 1, k.depth_dev, (long)IH * IW};  // depth = exp(ch 0)
+    if (c.dual_head && outp.depth_confidence) {  // confidence = exp(last channel) + 1 (select_conf_channel, ExpP1)
+      cd = k.out_kind == MD_MEM_HOST ? d->conf_stage : outp.depth_confidence;
+      chs[nch++] = TailCh{w2 + 32 * (c.output_dim - 1), d->main_bias[c.output_dim - 1], 3, cd, (long)IH * IW};
+    }
+    MD_TRY(tail(r, "head_tail_fused", d->c1r, IH, IW, d->oc2_1, chs, nch));
+    MD_TRY(host_out(r.st, k.out_kind, outp.depth, k.depth_dev, out_elems));
+    if (cd) MD_TRY(host_out(r.st, k.out_kind, outp.depth_confidence, cd, out_elems));
+  }
+  if (k.out_kind == MD_MEM_HOST) MD_HIP(hipStreamSynchronize(r.st));
+  return MD_OK;
+}
+
 static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const Da3Outputs& outp, int out_kind,
                            hipStream_t stream) {
   if (!m || m->kind != 1 || !m->da3) MD_FAIL(MD_ERR_INVALID_ARG, "not a Depth-Anything-v3 model");
@@ -684,482 +1119,36 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
   MD_TRY(da3_set_shape(m, H, W, false));  // any multiple of the patch size (mod.rs:509-520); a no-op at the current size
   hipStream_t st = model_stream(m, stream);
   Run r{m, st, B};
-  const int D = v.D, heads = v.heads, SS = d->SS, NT = d->NT, P = d->P, ph = d->ph, pw = d->pw, F = c.features;
-  const int IH = d->ih, IW = d->iw;
-  const int din = d->din;
-  const int* oc = c.out_channels;
-  const int Fp = cpad(m, F), F2 = F / 2, F2p = cpad(m, F2);
-  const std::string hp = d->hp;
+  const bool want_aux = c.dual_head && (outp.aux || outp.aux_confidence);
+  const bool want_cam = c.dual_head && !from_tokens && (outp.pose_encoding || outp.extrinsics || outp.intrinsics);
+  Da3Call k{outp, in_kind, out_kind, H, W, want_aux, want_cam, want_aux ? 2 : 1,
+            {4 * d->ph, 2 * d->ph, d->ph, d->h3h}, {4 * d->pw, 2 * d->pw, d->pw, d->h3w}};
   const float* x_dev = nchw;
   if (in_kind == MD_MEM_HOST && !from_tokens) {
     MD_HIP(hipMemcpyAsync(d->xin, nchw, (size_t)B * 3 * H * W * 4, hipMemcpyHostToDevice, st));
     x_dev = d->xin;
   }
-  auto Wk = [&](const std::string& n) { return PK(m, n); };
-  auto Bi = [&](const std::string& n) { return P32(m, n); };
   if (from_tokens) {
-    // ---- `infer_from_tokens` (mod.rs:405-469): no backbone, no camera prediction; the head's token LayerNorm (mono: non-affine,
-    //      dpt.rs:761-766; dual: the affine `norm`, dpt.rs:308) on the caller's hook tokens, patch rows only ----
-    if (outp.pose_encoding || outp.extrinsics || outp.intrinsics)
-      MD_FAIL(MD_ERR_UNSUPPORTED, "infer_from_tokens has no camera prediction (finalize_inference(head_output, None), mod.rs:468)");
-    const int T = outp.tokens_per_image;
-    if (T != P && T != P + 1)  // mod.rs:419-424: tokens == expected -> patch_start 0, else patch_token_start = 1
-      MD_FAIL(MD_ERR_SHAPE, "%d tokens per image for a %dx%d input: expected %d patch rows (or %d with a leading cls row)", T, H, W, P, P + 1);
-    for (int hk = 0; hk < 4; ++hk)
-      if (!outp.tokens[hk]) MD_FAIL(MD_ERR_LEVELS, "Backbone returned fewer hooks (%d) than requested (4)", hk);
-    const int start = T == P ? 0 : 1;
-    const size_t need = ((size_t)c.max_batch * SS + 64) * din;
-    bool grown = false;
-    MD_TRY(grow(m, st, d->tok_stage, need * 4, &grown));
-    if (grown) MD_HIP(hipMemset(d->tok_stage.p, 0, need * 4));
-    SeqGroups tg;
-    memset(&tg, 0, sizeof(tg));
-    tg.ngroups = 1;
-    tg.nseq[0] = B;
-    tg.a[0] = c.dual_head ? d->head_norm_g : nullptr;
-    tg.b[0] = c.dual_head ? d->head_norm_b : nullptr;
-    const hipMemcpyKind kind = in_kind == MD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    for (int hk = 0; hk < 4; ++hk) {
-      for (int b = 0; b < B; ++b)  // patch rows of image b -> rows b*SS + 1 .. of the staging tensor (the layout the head gathers from)
-        MD_HIP(hipMemcpyAsync(d->tok_stage.p + ((size_t)b * SS + 1) * din, outp.tokens[hk] + ((size_t)b * T + start) * din, (size_t)P * din * 4,
-                              kind, st));
-      r.begin("layernorm");
-      MD_TRY(launch_layernorm(d->tok_stage.p, d->hookn[hk], (long)B * SS, din, 1e-5f, SS, tg, m->prec, 0, st));
-      r.end();
-      if (m->taps_enabled) MD_TRY(r.tap_token_rows(("backbone_tokens_" + std::to_string(hk)).c_str(), d->tok_stage.p, SS, 1, P, din, din, 0));
-    }
+    MD_TRY(da3_stage_tokens(r, k));
   } else {
-  // ---- camera encoder (`infer_with_camera`, mod.rs:522-527: a model without one ignores the camera inputs) ----
-  float* cam_tok = nullptr;
-  if (c.camera_encoder && c.dual_head && outp.cam_extrinsics && outp.cam_intrinsics) {
-    const int V = outp.cam_views;
-    if (V < 1 || V > MD_CAM_MAX_VIEWS) MD_FAIL(MD_ERR_SHAPE, "camera inputs with %d views (1..%d supported)", V, MD_CAM_MAX_VIEWS);
-    const size_t n_in = (size_t)B * V * 21, n_tok = align_up((size_t)B * D, 64);
-    const size_t need = align_up(n_in, 64) + n_tok + camera_encoder_scratch_floats(B, V, D);
-    MD_TRY(grow(m, st, d->cam_enc_ws, need * 4));
-    const float *e_dev = outp.cam_extrinsics, *k_dev = outp.cam_intrinsics;
-    if (in_kind == MD_MEM_HOST) {
-      MD_HIP(hipMemcpyAsync(d->cam_enc_ws.p, outp.cam_extrinsics, (size_t)B * V * 12 * 4, hipMemcpyHostToDevice, st));
-      MD_HIP(hipMemcpyAsync(d->cam_enc_ws.p + (size_t)B * V * 12, outp.cam_intrinsics, (size_t)B * V * 9 * 4, hipMemcpyHostToDevice, st));
-      e_dev = d->cam_enc_ws.p; k_dev = d->cam_enc_ws.p + (size_t)B * V * 12;
-    }
-    cam_tok = d->cam_enc_ws.p + align_up(n_in, 64);
-    CamEncW w;
-    memset(&w, 0, sizeof(w));
-    const std::string ce = "camera_encoder.";
-    w.fc1_w = Bi(ce + "pose_branch.fc1.weight"); w.fc1_b = Bi(ce + "pose_branch.fc1.bias");
-    w.fc2_w = Bi(ce + "pose_branch.fc2.weight"); w.fc2_b = Bi(ce + "pose_branch.fc2.bias");
-    w.tn_g = Bi(ce + "token_norm.gamma"); w.tn_b = Bi(ce + "token_norm.beta");
-    w.on_g = Bi(ce + "trunk_norm.gamma"); w.on_b = Bi(ce + "trunk_norm.beta");
-    w.depth = c.cam_trunk_depth;
-    if (w.depth > CamEncW::kMaxDepth) MD_FAIL(MD_ERR_UNSUPPORTED, "camera encoder trunk of %d blocks", w.depth);
-    for (int i = 0; i < w.depth; ++i) {
-      const std::string bk = ce + "trunk." + std::to_string(i) + ".";
-      CamEncW::Blk& k = w.blk[i];
-      k.n1g = Bi(bk + "norm1.gamma"); k.n1b = Bi(bk + "norm1.beta"); k.n2g = Bi(bk + "norm2.gamma"); k.n2b = Bi(bk + "norm2.beta");
-      k.qkv_w = Bi(bk + "attn.qkv.weight"); k.qkv_b = Bi(bk + "attn.qkv.bias");
-      k.proj_w = Bi(bk + "attn.proj.weight"); k.proj_b = Bi(bk + "attn.proj.bias"); k.ls1 = Bi(bk + "ls1.gamma");
-      k.fc1_w = Bi(bk + "mlp.fc1.weight"); k.fc1_b = Bi(bk + "mlp.fc1.bias");
-      k.fc2_w = Bi(bk + "mlp.fc2.weight"); k.fc2_b = Bi(bk + "mlp.fc2.bias"); k.ls2 = Bi(bk + "ls2.gamma");
-      if (!k.qkv_w || !k.ls2) MD_FAIL(MD_ERR_FORMAT, "camera encoder block %d is not in the inventory", i);
-    }
-    if (!w.fc1_w || !w.on_b) MD_FAIL(MD_ERR_FORMAT, "camera encoder is not in the inventory");
-    r.begin("camera_encoder");
-    MD_TRY(launch_camera_encoder(e_dev, k_dev, B, V, D, c.cam_heads, H, W, c.cam_ln_eps, c.ln_eps, w, cam_tok + n_tok, cam_tok, st));
-    r.end();
-    MD_TRY(r.tap_f32("camera_token", cam_tok, B, D, 0, 0));  // CameraEncoder::forward's result (camera.rs:89-110)
+    // a model without a camera encoder ignores the camera inputs (mod.rs:522-527)
+    if (c.camera_encoder && c.dual_head && outp.cam_extrinsics && outp.cam_intrinsics) MD_TRY(da3_camera_encoder(r, k));
+    MD_TRY(da3_backbone(r, k, x_dev));
   }
-  // ---- backbone ----
-  r.begin("patchify");  // + the cls rows (cls + pos[0]) and the zero padding rows of the residual stream, in the same launch
-  MD_TRY(launch_patchify(x_dev, B, H, W, v.ps, d->Kp, d->patches, m->prec, st, d->xres, SS, NT, D, d->vit.cls, d->vit.pos));
-  r.end();
-  SeqGroups sg;
-  memset(&sg, 0, sizeof(sg));
-  sg.ngroups = 1;
-  sg.nseq[0] = B;
-  {
-    GemmParams p;
-    p.N = D; p.ngroups = 1; p.g_rows[0] = B * P; p.W[0] = d->vit.pe_w; p.bias[0] = d->vit.pe_b; p.pos[0] = d->vit.pos;
-    p.A = d->patches;
-    split_dense_a(m, p, d->Kp, d->Kp, 0);
-    p.epi = EPI_PATCH_EMBED; p.out = d->xres; p.ldo = D; p.seq_stride = SS; p.seq_patches = P; p.embed = D;
-    r.begin("patch_embed");
-    MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_AUTO, st));
-    r.end();
+  MD_TRY(da3_prepare_stages(r, k));
+  k.depth_dev = outp.raw_logits ? outp.raw_logits : outp.depth;
+  if (out_kind == MD_MEM_HOST) {
+    MD_TRY(grow(m, st, d->depth_stage, (size_t)B * H * W * (outp.raw_logits ? c.output_dim : 1) * 4));
+    k.depth_dev = d->depth_stage.p;
   }
-  const long rows = (long)B * SS;
-  int hook_slot = 0;
-  // The residual stream lives in `vp.x`. A GLOBAL block of the extended backbone needs the state behind the last LOCAL block
-  // for its hook (cat(x_local, LayerNorm(x))): its output projection therefore writes x + ls * (...) into the other buffer
-  // (GemmParams::resid_src) and the two swap -- the copy of the whole stream that used to precede every global block is gone.
-  VitPlan vp;
-  vp.vit[0] = &d->vit; vp.gcnt[0] = B; vp.WS = B;
-  vp.D = D; vp.heads = heads; vp.SS = SS; vp.NT = NT; vp.kpad = d->kpad; vp.ln_eps = c.ln_eps;
-  vp.x = d->xres; vp.xalt = d->xlocal; vp.xn = d->xn; vp.qk = d->qk; vp.vT = d->vT; vp.ao = d->ao; vp.hbuf = d->hbuf; vp.scores = d->scores;
-  vp.lin_prec = d->fp8 ? MD_PREC_FP8 : m->prec;
-  if (d->fp8) { vp.a_scale = md_model_s::Da3State::kActScale; vp.h_scale = md_model_s::Da3State::kHidScale; }
-  vp.qk_norm_eps = c.qk_norm_eps; vp.rope_cos = d->rope_cos; vp.rope_sin = d->rope_sin; vp.rope_pw = pw;
-  // entering block ext_block_start the camera token takes the cls slot -- the encoder's (mod.rs:522-531) or the learned
-  // reference-view one
-  vp.tok0_block = c.dual_head ? c.ext_block_start : -1;
-  vp.tok0 = cam_tok ? cam_tok : d->camera_token;
-  vp.tok0_stride = cam_tok ? D : 0;
-  for (int i = 0; i < v.depth; ++i) {
-    MD_TRY(run_vit_block(r, vp, i));
-    const float* xcur = vp.x;
-    if (c.dual_head) {
-      // hooks = LayerNorm_head(cat(x after the last local block, LayerNorm_final(x))); the camera feature is
-      // token 0 of the raw concat at the last hook
-      const float* xl = d->vit.blk[i].global ? vp.xalt : xcur;  // a local block is its own "last local" state; behind a global block the other buffer holds it
-      for (int hk = 0; hk < 4; ++hk)
-        if (c.hook_ids[hk] == i) {
-          r.begin("hook_cat_ln");
-          MD_TRY(launch_hook_cat_ln(xl, xcur, rows, SS, NT, D, d->vit.norm_g, d->vit.norm_b, c.ln_eps, d->head_norm_g,
-                                    d->head_norm_b, 1e-5f, d->hookn[hk], hk == 3 ? d->cam_raw : nullptr, m->prec, st));
-          r.end();
-          if (m->taps_enabled) {  // DepthTrace::backbone_tokens (mod.rs:241-246,344-347): cat(x_local, LayerNorm_final(x)) patch rows
-            const std::string tn = "backbone_tokens_" + std::to_string(hk);
-            sg.a[0] = d->vit.norm_g; sg.b[0] = d->vit.norm_b;
-            MD_TRY(launch_layernorm(xcur, d->lnf, rows, D, c.ln_eps, SS, sg, m->prec, 1, st));
-            MD_TRY(r.tap_token_rows(tn.c_str(), xl, SS, 1, P, D, 2 * D, 0));
-            MD_TRY(r.tap_token_rows(tn.c_str(), d->lnf, SS, 1, P, D, 2 * D, D));
-          }
-          ++hook_slot;
-        }
-    } else {
-      // hooks (mod.rs:202-215): final LayerNorm of the block output, then the head's non-affine token
-      // norm (apply_token_norm, dpt.rs:761-766: biased variance, eps 1e-5). A block may feed several hooks.
-      for (int hk = 0; hk < 4; ++hk)
-        if (c.hook_ids[hk] == i) {
-          sg.a[0] = d->vit.norm_g; sg.b[0] = d->vit.norm_b;
-          r.begin("layernorm");
-          MD_TRY(launch_layernorm(xcur, d->lnf, rows, D, c.ln_eps, SS, sg, m->prec, 1, st));
-          r.end();
-          if (m->taps_enabled) {  // DepthTrace::backbone_tokens (mod.rs:241-246,344-347)
-            const std::string tn = "backbone_tokens_" + std::to_string(hk);
-            MD_TRY(r.tap_token_rows(tn.c_str(), d->lnf, SS, 1, P, D, D, 0));
-          }
-          sg.a[0] = nullptr; sg.b[0] = nullptr;
-          r.begin("layernorm");
-          MD_TRY(launch_layernorm(d->lnf, d->hookn[hk], rows, D, 1e-5f, SS, sg, m->prec, 0, st));
-          r.end();
-          ++hook_slot;
-        }
-    }
-  }
-  if (hook_slot < 4) MD_FAIL(MD_ERR_LEVELS, "Backbone returned fewer hooks (%d) than requested (4)", hook_slot);  // mod.rs:532-537
-  }  // !from_tokens
-
-  // ---- DPT head: prepare_stage (dpt.rs:282-317 / 649-689) ----
-  int* tok_idx = nullptr;
-  MD_TRY(da3_tok_index(m, B, &tok_idx));
-  const int sh[4] = {4 * ph, 2 * ph, ph, d->h3h}, sw[4] = {4 * pw, 2 * pw, pw, d->h3w};  // stage sizes (rows, columns)
-  for (int s = 0; s < 4; ++s) {
-    const int ocp = cpad(m, oc[s]);
-    const std::string ps = hp + ".projects." + std::to_string(s);
-    {  // 1x1 projection over gathered patch tokens + 0.1 * UV position table
-      GemmParams p;
-      p.N = oc[s]; p.ngroups = 1; p.g_rows[0] = B * P; p.W[0] = Wk(ps + ".weight"); p.bias[0] = Bi(ps + ".bias");
-      p.A = d->hookn[s]; p.a_index = tok_idx;
-      split_dense_a(m, p, din, din, 0);
-      p.epi = EPI_STORE; p.out = d->sp[s];
-      split_out(m, p, ocp, true);
-      p.res1 = d->pos_stage[s]; p.ldr = p.ldo; p.r_plane = p.o_plane; p.res_mod = P;
-      r.begin("head_proj");
-      MD_TRY(launch_gemm(p, A_INDEXED, m->prec, TILE_AUTO, st));
-      r.end();
-    }
-    const void* feat = d->sp[s];
-    if (s == 0 || s == 1) {  // ConvTranspose k4s4 / k2s2 (+bias)
-      const int f = s == 0 ? 4 : 2;
-      const std::string rl = hp + ".resize_layers." + std::to_string(s) + ".conv_t";
-      GemmParams p;
-      p.N = f * f * oc[s]; p.ngroups = 1; p.g_rows[0] = B * P; p.W[0] = Wk(rl + ".weight"); p.bias[0] = Bi(rl + ".bias");
-      p.A = d->sp[s];
-      split_dense_a(m, p, ocp, ocp, 0);
-      p.epi = EPI_PIXSHUF; p.out = d->sr[s];
-      split_out(m, p, ocp, true);
-      p.psH = ph; p.psW = pw; p.psC = oc[s]; p.ps_f = f;
-      r.begin("head_deconv");
-      MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_AUTO, st));
-      r.end();
-      feat = d->sr[s];
-    } else if (s == 3) {  // Conv2d 3x3 stride 2 pad 1 (+bias)
-      GemmParams p;
-      p.N = oc[3]; p.ngroups = 1; p.g_rows[0] = B * d->h3h * d->h3w;
-      p.W[0] = Wk(hp + ".resize_layers.3.conv.weight"); p.bias[0] = Bi(hp + ".resize_layers.3.conv.bias");
-      p.A = d->sp[3]; p.cH = ph; p.cW = pw; p.cOH = d->h3h; p.cOW = d->h3w; p.cstride = 2; p.zero_page = m->zero_page;
-      split_conv_a(m, p, ocp, 0);
-      p.epi = EPI_STORE; p.out = d->sr[3];
-      split_out(m, p, ocp, true);
-      r.begin("head_conv_s2");
-      MD_TRY(launch_gemm(p, A_CONV3, m->prec, TILE_AUTO, st));
-      r.end();
-      feat = d->sr[3];
-    }
-    // layerN_rn: 3x3, no bias -> features (+ relu copy for the residual units)
-    MD_TRY(conv3(r, "head_conv3x3", feat, sh[s], sw[s], ocp, Wk(hp + ".scratch.layer" + std::to_string(s + 1) + "_rn.weight"), nullptr,
-                 F, d->rn[s], Fp, ACT_NONE, nullptr, nullptr, d->rnr[s]));
-    if (m->taps_enabled) {  // prepare_stage output and its layerN_rn map (dpt.rs:649-703)
-      MD_TRY(r.tap_nhwc(("stage_" + std::to_string(s)).c_str(), feat, oc[s], sh[s], sw[s], ocp));
-      MD_TRY(r.tap_nhwc(("layer" + std::to_string(s + 1) + "_rn").c_str(), d->rn[s], F, sh[s], sw[s], Fp));
-    }
-  }
-  // ---- the head's tails. Dual head: the main fusion pyramid (depth, confidence) and the aux fusion pyramid (rays, confidence) have
-  //      the same shapes and share their inputs (the layerN_rn maps): with the aux outputs wanted they run in the SAME launches as
-  //      two weight groups -- group 0 = main on images [0, B), group 1 = aux on images [B, 2B) of every pyramid map. A 64-feature
-  //      3x3 convolution costs ~11 us at 37^2 and ~14 us at 296^2 (launch floor + nine dependent k-tiles, not throughput), so the
-  //      second group is nearly free where a second chain of launches was not (round 4: 44 -> 22 pyramid launches; the side-stream
-  //      form overlapped only a third of the aux pyramid, profiles/r04_cfg2_branches.txt). ----
-  struct Bufs { void *t, *x, *xr, *y, *up, *o; };
-  Bufs bf{d->t, d->x, d->xr, d->y, d->up, d->o};
-  const bool want_aux = c.dual_head && (outp.aux || outp.aux_confidence);
-  const bool want_cam = c.dual_head && !from_tokens && (outp.pose_encoding || outp.extrinsics || outp.intrinsics);
   // Everything runs on the caller's stream. Rounds 3-4 ran the aux branch and the camera decoder on side streams (parallel branches of
   // the captured graph): every fork / join cost more than the overlap gave back (config 2, all outputs: 1.97 ms with two side streams,
   // 1.80 on one stream, 1.70 with the aux branch alone on a side stream; with the pyramids grouped 1.74 with a side stream for the aux
   // tail against 1.63 without -- profiles/r04_cfg2_branches.txt).
-  Run& ra = r;  // aux neck + tail
-  Run& rc = r;  // camera decoder
-  const int G = want_aux ? 2 : 1;
-  const char* const sfx[2] = {"", "_aux"};
-  const size_t px_bytes = (size_t)Fp * m->esz * m->xm;  // one pixel of an F-channel map
-  // 3x3 convolution F -> F over [G*B, hh, ww] with one weight set per group; `in_shared`: both groups read images [0, B) of `in`;
-  // res1_shared: the same for the first residual input
-  auto conv3g = [&](Run& rr, const void* in, bool in_shared, int hh, int ww, const std::string& rfb, const std::string& unit, void* out, int act,
-                    const void* res1, bool res1_shared, const void* res2, void* out2) -> int {
-    GemmParams p;
-    const int M = B * hh * ww;
-    p.N = F; p.ngroups = G;
-    for (int g = 0; g < G; ++g) {
-      p.g_rows[g] = M; p.g_row0[g] = g * M; p.g_arow0[g] = in_shared ? 0 : g * M;
-      p.W[g] = Wk(rfb + sfx[g] + unit + ".weight"); p.bias[g] = Bi(rfb + sfx[g] + unit + ".bias");
-    }
-    p.A = in; p.cH = hh; p.cW = ww; p.zero_page = m->zero_page;
-    split_conv_a(m, p, Fp, 0);
-    p.epi = EPI_STORE; p.act = act; p.out = out; p.out2 = out2;
-    split_out(m, p, Fp, true);
-    p.res1 = res1; p.res2 = res2; p.ldr = p.ldo; p.r_plane = (res1 || res2) ? p.o_plane : 0;
-    if (res1 && res1_shared && G > 1) p.res_mod = M;
-    rr.begin("head_conv3x3");
-    int s2 = launch_gemm(p, A_CONV3, m->prec, TILE_AUTO, rr.st);
-    rr.end();
-    return s2;
-  };
-  // ResidualConvUnit (dpt.rs:1248-1252): out = x + conv2(relu(conv1(relu(x)))) [+ extra]
-  auto rcu = [&](Run& rr, const std::string& rfb, const std::string& unit, int hh, int ww, const void* x, const void* xr, bool x_shared,
-                 const void* extra, void* out, void* out_relu) -> int {
-    MD_TRY(conv3g(rr, xr, x_shared, hh, ww, rfb, unit + ".conv1", bf.t, ACT_RELU, nullptr, false, nullptr, nullptr));
-    return conv3g(rr, bf.t, false, hh, ww, rfb, unit + ".conv2", out, ACT_NONE, x, x_shared, extra, out_relu);
-  };
-  // the four FeatureFusionBlocks (dpt.rs:1206-1222) from the coarsest stage up; result in bf.o at 8ph x 8pw (G*B images)
-  const int target[4] = {8 * ph, 4 * ph, 2 * ph, ph}, targw[4] = {8 * pw, 4 * pw, 2 * pw, pw};  // output size of refinenet1..4
-  auto pyramid = [&](Run& rr) -> int {
-    const void* top = nullptr;
-    for (int lvl = 3; lvl >= 0; --lvl) {
-      const std::string rfb = hp + ".scratch.refinenet" + std::to_string(lvl + 1);
-      const void *yx, *yxr;
-      bool y_shared;
-      if (lvl == 3) {
-        yx = d->rn[3]; yxr = d->rnr[3]; y_shared = true;
-      } else {
-        MD_TRY(rcu(rr, rfb, ".residual1", sh[lvl], sw[lvl], d->rn[lvl], d->rnr[lvl], true, top, bf.x, bf.xr));
-        yx = bf.x; yxr = bf.xr; y_shared = false;
-      }
-      MD_TRY(rcu(rr, rfb, ".residual2", sh[lvl], sw[lvl], yx, yxr, y_shared, nullptr, bf.y, nullptr));
-      rr.begin("head_resize");
-      MD_TRY(launch_resize_nhwc(bf.y, G * B, sh[lvl], sw[lvl], F, Fp, bf.up, target[lvl], targw[lvl], Fp, MD_INTERP_BURN, nullptr, m->prec, rr.st));
-      rr.end();
-      {  // out_conv 1x1 (+bias), one weight set per group
-        GemmParams p;
-        const int M2 = B * target[lvl] * targw[lvl];
-        p.N = F; p.ngroups = G;
-        for (int g = 0; g < G; ++g) {
-          p.g_rows[g] = M2; p.g_row0[g] = g * M2; p.g_arow0[g] = g * M2;
-          p.W[g] = Wk(rfb + sfx[g] + ".out_conv.weight"); p.bias[g] = Bi(rfb + sfx[g] + ".out_conv.bias");
-        }
-        p.A = bf.up;
-        split_dense_a(m, p, Fp, Fp, 0);
-        p.epi = EPI_STORE; p.out = bf.o;
-        split_out(m, p, Fp, true);
-        rr.begin("head_out_conv");
-        MD_TRY(launch_gemm(p, A_DENSE, m->prec, TILE_AUTO, rr.st));
-        rr.end();
-      }
-      top = bf.o;
-      if (m->taps_enabled)  // FeatureFusionBlock outputs (dpt.rs:705-720), main and aux pyramids
-        for (int g = 0; g < G; ++g)
-          MD_TRY(rr.tap_nhwc(("refinenet" + std::to_string(lvl + 1) + sfx[g]).c_str(),
-                             (const char*)bf.o + (size_t)g * B * target[lvl] * targw[lvl] * px_bytes, F, target[lvl], targw[lvl], Fp));
-    }
-    return MD_OK;
-  };
-  // fused tail: out_c[img][pixel] = act_c(w_c . relu(conv3x3(in) + b1) + b_c) for `nch` channels in ONE launch over a
-  // [B, hh, ww, 64-padded] map (ConvStack / `reduce` + `project`, dpt.rs:481-513,1287-1290)
-  struct TailCh { const float* w; float b; int act; float* out; long bstride; };
-  auto tail = [&](Run& rr, const char* name, const void* in, int hh, int ww, const void* w1, const float* b1, const TailCh* chs, int nch) -> int {
-    if (nch <= 0) return MD_OK;
-    GemmParams p;
-    p.N = 32; p.ngroups = 1; p.g_rows[0] = B * hh * ww; p.W[0] = w1;
-    p.A = in; p.cH = hh; p.cW = ww; p.zero_page = m->zero_page;
-    split_conv_a(m, p, F2p, 0);
-    p.epi = EPI_HEAD; p.bias[0] = b1; p.head_nch = nch; p.head_plane = hh * ww;
-    for (int i = 0; i < nch; ++i) {
-      p.head_wc[i] = chs[i].w; p.head_bs[i] = chs[i].b; p.head_acts[i] = chs[i].act; p.head_out[i] = chs[i].out; p.head_bstride[i] = chs[i].bstride;
-    }
-    rr.begin(name);
-    int s2 = launch_gemm(p, A_CONV3, m->prec, TILE_256x32, rr.st);
-    rr.end();
-    return s2;
-  };
-  auto host_out = [&](hipStream_t hs, float* dst, const float* src, size_t n) -> int {
-    if (out_kind == MD_MEM_HOST && dst) MD_HIP(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, hs));
-    return MD_OK;
-  };
-  const size_t out_elems = (size_t)B * IH * IW;
-  const size_t stage_elems = out_elems * (outp.raw_logits ? c.output_dim : 1);
-  float* depth_dev = outp.raw_logits ? outp.raw_logits : outp.depth;
-  if (out_kind == MD_MEM_HOST) {
-    MD_TRY(grow(m, st, d->depth_stage, stage_elems * 4));
-    depth_dev = d->depth_stage.p;
-  }
-  // ---- aux branch (build_aux_logits, dpt.rs:356-441): aux fusion pyramid on the same layerN_rn maps -> last level's 5-conv
-  //      neck -> + 2 x 0.1 x UV -> reduce 3x3 -> ReLU -> project 1x1 (7 ch: 6 ray values + confidence) ----
-  MD_TRY(pyramid(r));  // both pyramids (two weight groups) when the aux outputs are wanted
-  // output_conv1 (main, dpt.rs:337-344) and the first convolution of the aux neck (dpt.rs:1085-1113) are both 3x3 F -> F/2 on the
-  // 8ph x 8pw results of their pyramids: one launch, two weight groups, into the (now free) `up` map -- main | aux
-  const void* c1_map = d->c1;
-  const void* aux_cur = nullptr;
-  const std::string lv = std::to_string(c.aux_levels - 1);
-  if (want_aux) {
-    GemmParams p;
-    const int M = B * 8 * ph * 8 * pw;
-    const std::string n0 = hp + ".scratch.output_conv1_aux." + lv + ".layers.0";
-    p.N = F2; p.ngroups = 2;
-    for (int g = 0; g < 2; ++g) { p.g_rows[g] = M; p.g_row0[g] = g * M; p.g_arow0[g] = g * M; }
-    p.W[0] = Wk(hp + ".scratch.output_conv1.weight"); p.bias[0] = Bi(hp + ".scratch.output_conv1.bias");
-    p.W[1] = Wk(n0 + ".weight"); p.bias[1] = Bi(n0 + ".bias");
-    p.A = bf.o; p.cH = 8 * ph; p.cW = 8 * pw; p.zero_page = m->zero_page;
-    split_conv_a(m, p, Fp, 0);
-    p.epi = EPI_STORE; p.out = bf.up;
-    split_out(m, p, F2p, true);
-    r.begin("head_conv3x3");
-    MD_TRY(launch_gemm(p, A_CONV3, m->prec, TILE_AUTO, st));
-    r.end();
-    c1_map = bf.up;
-    aux_cur = (const char*)bf.up + (size_t)M * F2p * m->esz * m->xm;
-  } else {
-    MD_TRY(conv3(r, "head_conv3x3", d->o, 8 * ph, 8 * pw, Fp, Wk(hp + ".scratch.output_conv1.weight"), Bi(hp + ".scratch.output_conv1.bias"), F2,
-                 d->c1, F2p, ACT_NONE, nullptr, nullptr, nullptr));
-  }
-  if (want_aux) {
-    const int ah = 8 * ph, aw = 8 * pw;
-    const void* cur = aux_cur;  // the neck's first convolution ran beside output_conv1
-    void* pp[2] = {d->up2, d->o2};
-    int cin = F2;
-    for (int j = 1; j < c.aux_out1_conv_num; ++j) {
-      const int cout = j % 2 == 0 ? F / 2 : F;
-      const std::string n = hp + ".scratch.output_conv1_aux." + lv + ".layers." + std::to_string(j);
-      MD_TRY(conv3(ra, "aux_conv3x3", cur, ah, aw, cpad(m, cin), Wk(n + ".weight"), Bi(n + ".bias"), cout, pp[j & 1], cpad(m, cout), ACT_NONE,
-                   nullptr, nullptr, nullptr));
-      cur = pp[j & 1];
-      cin = cout;
-    }
-    void* hin = cur == d->up2 ? d->o2 : d->up2;
-    ra.begin("head_resize");
-    MD_TRY(launch_resize_nhwc(cur, B, ah, aw, F2, F2p, hin, ah, aw, F2p, MD_INTERP_BURN, d->pos_aux, m->prec, ra.st));
-    ra.end();
-    if (m->taps_enabled) {  // DepthTrace::aux_stage_necks (last level) / aux_head_input (mod.rs:241-246)
-      MD_TRY(ra.tap_nhwc("aux_neck", cur, F2, ah, aw, F2p));
-      MD_TRY(ra.tap_nhwc("aux_head_input", hin, F2, ah, aw, F2p));
-    }
-    const std::string oh = hp + ".scratch.output_conv2_aux." + lv;
-    const size_t plane = (size_t)ah * aw;
-    const int K7 = c.aux_output_dim;
-    const float* pw_ = Bi(oh + ".project.weight");
-    TailCh chs[8];
-    int nch = 0;
-    for (int ch = 0; ch < K7; ++ch) {  // aux lands as [B, 6, h, w], the confidence as [B, h, w]; host outputs through [B, 7, h, w] staging
-      const bool conf = ch == K7 - 1;
-      float* user = conf ? outp.aux_confidence : outp.aux;
-      if (!user) continue;
-      TailCh t;
-      t.w = pw_ + 32 * ch; t.b = d->aux_bias[ch]; t.act = conf ? 3 : 2;
-      if (out_kind == MD_MEM_HOST) { t.out = d->aux_stage + (size_t)ch * plane; t.bstride = (long)K7 * plane; }
-      else if (conf) { t.out = user; t.bstride = (long)plane; }
-      else { t.out = user + (size_t)ch * plane; t.bstride = (long)(K7 - 1) * plane; }
-      chs[nch++] = t;
-    }
-    MD_TRY(tail(ra, "aux_tail_fused", hin, ah, aw, Wk(oh + ".reduce.weight"), Bi(oh + ".reduce.bias"), chs, nch));
-    if (out_kind == MD_MEM_HOST)
-      for (int ch = 0; ch < K7; ++ch) {
-        const bool conf = ch == K7 - 1;
-        float* user = conf ? outp.aux_confidence : outp.aux;
-        if (!user) continue;
-        for (int b = 0; b < B; ++b)
-          MD_TRY(host_out(ra.st, conf ? user + (size_t)b * plane : user + ((size_t)b * (K7 - 1) + ch) * plane,
-                          d->aux_stage + ((size_t)b * K7 + ch) * plane, plane));
-      }
-  }
-  // ---- camera decoder (camera.rs:143-199) on the raw camera feature of the last hook, fp32 ----
-  if (want_cam) {
-    // pose = (t3 | quat4 | relu(fov2)) rows [B, 9]; device outputs are written straight into the caller's buffers
-    const bool dev_out = out_kind == MD_MEM_DEVICE;
-    float* pose = (dev_out && outp.pose_encoding) ? outp.pose_encoding : d->pose;
-    float* extr = (dev_out && outp.extrinsics) ? outp.extrinsics : d->extr;
-    float* intr = (dev_out && outp.intrinsics) ? outp.intrinsics : d->intr;
-    CamDecW w;
-    auto CW = [&](const char* n) { return Bi(std::string("camera_decoder.") + n); };
-    w.w1 = CW("backbone_1.weight"); w.b1 = CW("backbone_1.bias"); w.w2 = CW("backbone_2.weight"); w.b2 = CW("backbone_2.bias");
-    w.wt = CW("fc_t.weight"); w.bt = CW("fc_t.bias"); w.wq = CW("fc_qvec.weight"); w.bq = CW("fc_qvec.bias");
-    w.wf = CW("fc_fov.weight"); w.bf = CW("fc_fov.bias");
-    rc.begin("camera_decoder");
-    MD_TRY(launch_camera_decoder(d->cam_raw, B, din, w, H, W, d->cam_h1, d->cam_h2, pose, outp.extrinsics ? extr : nullptr,
-                                 outp.intrinsics ? intr : nullptr, rc.st));
-    rc.end();
-    if (!dev_out) {
-      if (outp.pose_encoding) MD_HIP(hipMemcpyAsync(outp.pose_encoding, pose, (size_t)B * 9 * 4, hipMemcpyDeviceToHost, rc.st));
-      if (outp.extrinsics) MD_HIP(hipMemcpyAsync(outp.extrinsics, extr, (size_t)B * 12 * 4, hipMemcpyDeviceToHost, rc.st));
-      if (outp.intrinsics) MD_HIP(hipMemcpyAsync(outp.intrinsics, intr, (size_t)B * 9 * 4, hipMemcpyDeviceToHost, rc.st));
-    }
-  }
-  // ---- main branch: output_conv1 -> resize to the image size (+ UV table) -> output_conv2 + activation ----
-  r.begin("head_resize");
-  MD_TRY(launch_resize_nhwc(c1_map, B, 8 * ph, 8 * pw, F2, F2p, d->c1r, IH, IW, F2p, MD_INTERP_BURN, d->pos_final, m->prec, st));
-  r.end();
-  if (m->taps_enabled) {
-    MD_TRY(r.tap_nhwc("output_conv1", c1_map, F2, 8 * ph, 8 * pw, F2p));
-    MD_TRY(r.tap_nhwc("head_input", d->c1r, F2, IH, IW, F2p));  // resized + UV table: the input of output_conv2
-  }
-  {
-    const void* w1 = Wk(hp + ".scratch.output_conv2.conv1.weight");
-    const float* b1 = Bi(hp + ".scratch.output_conv2.conv1.bias");
-    const float* w2 = Bi(hp + ".scratch.output_conv2.conv2.weight");
-    TailCh chs[8];
-    int nch = 0;
-    float* cd = nullptr;
-    if (outp.raw_logits) {
-      // infer_raw (mod.rs:364-380): the dual head hands out `depth_logits` = output_conv2's result as it is (dpt.rs:337-354, 271);
-      // the mono head's `forward_raw` has its activation applied (dpt.rs:700)
-      if (c.output_dim > 8) MD_FAIL(MD_ERR_UNSUPPORTED, "infer_raw with %d channels", c.output_dim);
-      for (int ch = 0; ch < c.output_dim; ++ch)
-        chs[nch++] = TailCh{w2 + 32 * ch, d->main_bias[ch], c.dual_head ? 2 : 1, depth_dev + (size_t)ch * IH * IW, (long)c.output_dim * IH * IW};
-      MD_TRY(tail(r, "head_tail_fused", d->c1r, IH, IW, w1, b1, chs, nch));
-      MD_TRY(host_out(st, outp.raw_logits, depth_dev, stage_elems));
-      if (out_kind == MD_MEM_HOST) MD_HIP(hipStreamSynchronize(st));
-      return MD_OK;
-    }
-    chs[nch++] = TailCh{w2, d->main_bias[0], 1, depth_dev, (long)IH * IW};  // depth = exp(ch 0)
-    if (c.dual_head && outp.depth_confidence) {  // confidence = exp(last channel) + 1 (select_conf_channel, ExpP1)
-      cd = out_kind == MD_MEM_HOST ? d->conf_stage : outp.depth_confidence;
-      chs[nch++] = TailCh{w2 + 32 * (c.output_dim - 1), d->main_bias[c.output_dim - 1], 3, cd, (long)IH * IW};
-    }
-    MD_TRY(tail(r, "head_tail_fused", d->c1r, IH, IW, w1, b1, chs, nch));
-    MD_TRY(host_out(st, outp.depth, depth_dev, out_elems));
-    if (cd) MD_TRY(host_out(st, outp.depth_confidence, cd, out_elems));
-  }
-  if (out_kind == MD_MEM_HOST) MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  MD_TRY(da3_pyramid(r, k));  // both pyramids (two weight groups) when the aux outputs are wanted
+  if (want_aux) MD_TRY(da3_aux_tail(r, k));
+  if (want_cam) MD_TRY(da3_camera_decoder(r, k));
+  return da3_main_tail(r, k);
 }
 
 int da3_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, hipStream_t stream) {

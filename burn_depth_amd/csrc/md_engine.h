@@ -80,6 +80,25 @@ struct VitW {
   const float *pe_b, *cls, *pos, *norm_g, *norm_b;
   std::vector<VitBlockW> blk;
 };
+// Every weight behind the ViT is bound at create too (dp_bind in md_engine.hip, da3_bind in md_da3.hip): a packed convolution /
+// linear weight and its fp32 bias (null: none), and the residual unit of both heads (ResidualBlock, ResidualConvUnit)
+struct ConvW { const void* w = nullptr; const float* b = nullptr; };
+struct ResUnitW { ConvW c1, c2; };
+struct DepthProW {
+  // encoder tail: projection and first deconvolution of upsample_latent0 | upsample_latent1 (its composed 0x1 pair) | upsample0 |
+  // upsample1 | upsample2, latent0's composed 1x2 pair, upsample_lowres, fuse_lowres
+  const void *enc_proj[5] = {}, *enc_up[5] = {}, *latent0_1x2 = nullptr;
+  ConvW lowres, fuse;
+  // decoder: convs[1..4], fusions[l].resnet1 | resnet2, fusions[l]'s out_conv (l > 0: the composed deconv_out_conv)
+  const void* convs[5] = {};
+  ResUnitW res[5][2];
+  ConvW out[5];
+  // head (outconv_conv0.b, deconv_conv1.b: the nine bias classes; outconv_conv0 and conv1 are optional forms)
+  ConvW conv0, outconv_conv0, deconv, deconv_conv1, conv1, conv_out;
+  // FOV: the stride-2 downsample (direct form; down_gemm: its implicit-GEMM operand, optional), encoder_proj, head_blocks
+  ConvW down, fov_proj, head[4];
+  const void* down_gemm = nullptr;
+};
 
 struct Tap {
   float* dev = nullptr;
@@ -199,6 +218,7 @@ struct md_model_s {
   unsigned commit_gen = 0;  // bumped by every model_commit (part of the graph-replay key)
   int ngroups = 2;
   md::VitW vit[3];
+  md::DepthProW dp;
   float head_b_host = 0.f;
 
   // ---- workspace ----
@@ -358,8 +378,7 @@ struct Da3Cfg {
 };
 std::vector<ParamSpec> da3_param_specs(const Da3Cfg& cfg, int scheme);
 int da3_create(md_device_t dev, const Da3Cfg& cfg, md_model_t* out);
-int da3_init_seeded(md_model_t m, uint64_t seed, int scheme);
-int da3_load_container(md_model_t m, const char* path);
+const Da3Cfg& da3_cfg(md_model_t m);
 int da3_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, int out_kind,
               hipStream_t stream);
 // DepthAnything3Inference (mod.rs:231-239); null = not wanted. aux is [B, aux_output_dim-1, 8ph, 8pw].

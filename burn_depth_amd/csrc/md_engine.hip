@@ -447,6 +447,148 @@ static int plan_workspace(md_model_s* m, bool dry, size_t* total_out) {
 // ------------------------------------------------------------------------------------------------
 // model construction
 // ------------------------------------------------------------------------------------------------
+// the fp32 master arena (model_create, da3_create)
+int alloc_param_arena(md_model_s* m, std::vector<ParamSpec> specs) {
+  m->params = std::move(specs);
+  for (size_t i = 0; i < m->params.size(); ++i) {
+    m->pindex[m->params[i].name] = (int)i;
+    m->w32.push_back((float*)m->w32_bytes);  // offset for now
+    m->w32_bytes += align_up(m->params[i].count() * 4, 256);
+  }
+  if (hipMalloc((void**)&m->w32_base, m->w32_bytes) != hipSuccess)
+    MD_FAIL(MD_ERR_OOM, "hipMalloc of %zu bytes for the fp32 weights failed", m->w32_bytes);
+  (void)hipMemset(m->w32_base, 0, m->w32_bytes);
+  for (float*& p : m->w32) p = (float*)(m->w32_base + (size_t)p);
+  return MD_OK;
+}
+
+int place_packs(md_model_s* m) {
+  for (auto& e : m->packs) {
+    e.dst = (void*)m->wpk_bytes;  // offset for now
+    m->wpk_bytes += align_up(e.bytes + 256, 256);
+  }
+  if (hipMalloc((void**)&m->wpk_base, m->wpk_bytes) != hipSuccess)
+    MD_FAIL(MD_ERR_OOM, "hipMalloc of %zu bytes for the packed weights failed", m->wpk_bytes);
+  (void)hipMemset(m->wpk_base, 0, m->wpk_bytes);
+  for (auto& e : m->packs) e.dst = m->wpk_base + (size_t)e.dst;
+  return MD_OK;
+}
+
+// the workspace of a Depth Pro model or fork: the zeroed arena of its plan (padding rows / channels / keys must be finite zeros), the
+// attention code object and the zero page
+static int alloc_workspace(md_model_s* m) {
+  m->buf = new md_model_s::Buffers();
+  size_t need = 0;
+  plan_workspace(m, true, &need);
+  if (hipMalloc((void**)&m->ws.base, need) != hipSuccess)
+    MD_FAIL(MD_ERR_OOM, "hipMalloc of %zu bytes for %s workspace failed (max_batch=%d)", need, m->parent ? "the fork's" : "the", m->cfg.max_batch);
+  m->ws.cap = need;
+  if (hipMemset(m->ws.base, 0, need) != hipSuccess) MD_FAIL(MD_ERR_HIP, "hipMemset of the workspace failed");
+  MD_TRY(plan_workspace(m, false, nullptr));
+  if (m->prec == MD_PREC_BF16) MD_TRY(attention_asm_prepare());  // the code object loads here, never inside a capture
+  if (hipMalloc(&m->zero_page, 4096) != hipSuccess) return MD_ERR_OOM;
+  (void)hipMemset(m->zero_page, 0, 4096);
+  (void)hipDeviceSynchronize();
+  return MD_OK;
+}
+
+// the packs of everything behind the ViTs ...
+static void dp_add_packs(md_model_s* m) {
+  const ModelCfg& cfg = m->cfg;
+  const int D = cfg.pv.D, F = cfg.F;
+  const int* dims = cfg.pv.feat_dims;
+  auto pub = [&](const std::string& n, int din, int dout, int layers, int dint) {
+    const int inter = dint > 0 ? dint : dout;
+    add_pack(m, n + ".projection.weight", PACK_NK, inter, din, 1);
+    for (int l = 0; l < layers; ++l)
+      add_pack(m, n + ".upsample." + std::to_string(l) + ".weight", PACK_DECONV, l == 0 ? inter : dout, dout, 2);
+  };
+  pub("encoder.upsample_latent0", D, F, 3, dims[0]);
+  pub("encoder.upsample_latent1", D, dims[0], 2, 0);
+  // the last two k2s2 deconvolutions of each latent chain run as one k4s4 (their 2x intermediate is never written)
+  add_pack_product(m, "encoder.upsample_latent0.upsample.1x2", "encoder.upsample_latent0.upsample.1.weight",
+                   "encoder.upsample_latent0.upsample.2.weight", 4, F, F, F);
+  add_pack_product(m, "encoder.upsample_latent1.upsample.0x1", "encoder.upsample_latent1.upsample.0.weight",
+                   "encoder.upsample_latent1.upsample.1.weight", 4, dims[0], dims[0], dims[0]);
+  pub("encoder.upsample0", D, dims[1], 1, 0);
+  pub("encoder.upsample1", D, dims[2], 1, 0);
+  pub("encoder.upsample2", D, dims[3], 1, 0);
+  add_pack(m, "encoder.upsample_lowres.weight", PACK_DECONV, cfg.iv.D, dims[3], 2);
+  add_pack(m, "encoder.fuse_lowres.weight", PACK_NK, dims[3], 2 * dims[3], 1);
+  const int ddims[5] = {F, dims[0], dims[1], dims[2], dims[3]};
+  for (int l = 1; l < 5; ++l) add_pack(m, "decoder.convs." + std::to_string(l) + ".conv.weight", PACK_CONV3, F, ddims[l], 3);
+  for (int l = 0; l < 5; ++l) {
+    const std::string f = "decoder.fusions." + std::to_string(l);
+    for (const char* r : {"resnet1", "resnet2"}) {
+      add_pack(m, f + "." + r + ".conv1.weight", PACK_CONV3, F, F, 3);
+      add_pack(m, f + "." + r + ".conv2.weight", PACK_CONV3, F, F, 3);
+    }
+    if (l != 0)
+      add_pack_product(m, f + ".deconv_out_conv", f + ".deconv.weight", f + ".out_conv.weight", 2, F, F, F);
+    else
+      add_pack(m, f + ".out_conv.weight", PACK_NK, F, F, 1);
+  }
+  add_pack(m, "head.conv0.weight", PACK_CONV3, F / 2, F, 3);
+  add_pack_fused(m, PACK_C1C3_W, "head.outconv_conv0", "decoder.fusions.0.out_conv", "head.conv0", F, F, F / 2);
+  add_pack(m, "head.deconv.weight", PACK_DECONV, F / 2, F / 2, 2);
+  add_pack_fused(m, PACK_HEAD_W, "head.deconv_conv1", "head.deconv", "head.conv1", F / 2, F / 2, 32);
+  add_pack(m, "head.conv1.weight", PACK_CONV3, 32, F / 2, 3);  // head_debug's un-fused conv1 (mod.rs:292); 74 KB
+  if (cfg.use_fov_head) {
+    if (cfg.has_fov_vit) {
+      add_pack(m, "fov.encoder_proj.weight", PACK_NK, F / 2, cfg.fv.D, 1);
+      add_pack(m, "fov.downsample_blocks.0.conv.weight", PACK_DIRECT, F / 2, F, 3, true);
+      // the same weight as an implicit-GEMM operand: the stride-2 downsample of the lowres feature (fov.rs:79-87,185) is 2.7 GFLOP at B = 8 and
+      // took 374 us as a direct convolution (one wave per output pixel) -- the MFMA family's stride-2 3x3 form does it in a tenth of that
+      add_pack(m, "fov.downsample_blocks.0.conv.gemm", PACK_CONV3, F / 2, F, 3, false, "fov.downsample_blocks.0.conv.weight");
+      add_pack(m, "fov.head_blocks.0.conv.weight", PACK_DIRECT, F / 4, F / 2, 3, true);
+      add_pack(m, "fov.head_blocks.1.conv.weight", PACK_DIRECT, F / 8, F / 4, 3, true);
+      add_pack(m, "fov.head_blocks.2.conv.weight", PACK_DIRECT, 1, F / 8, 6, true);
+    } else {
+      add_pack(m, "fov.head_blocks.0.conv.weight", PACK_DIRECT, F / 2, F, 3, true);
+      add_pack(m, "fov.head_blocks.1.conv.weight", PACK_DIRECT, F / 4, F / 2, 3, true);
+      add_pack(m, "fov.head_blocks.2.conv.weight", PACK_DIRECT, F / 8, F / 4, 3, true);
+      add_pack(m, "fov.head_blocks.3.conv.weight", PACK_DIRECT, 1, F / 8, 6, true);
+    }
+  }
+}
+
+// ... and their tables (after the packed arena is placed)
+static int dp_bind(md_model_s* m) {
+  const ModelCfg& c = m->cfg;
+  DepthProW& w = m->dp;
+  Binder bd{m, {}};
+  const std::string pub[5] = {"encoder.upsample_latent0", "encoder.upsample_latent1", "encoder.upsample0", "encoder.upsample1", "encoder.upsample2"};
+  for (int i = 0; i < 5; ++i) {
+    w.enc_proj[i] = bd.pk(pub[i] + ".projection.weight");
+    w.enc_up[i] = bd.pk(pub[i] + (i == 1 ? ".upsample.0x1" : ".upsample.0.weight"));
+  }
+  w.latent0_1x2 = bd.pk("encoder.upsample_latent0.upsample.1x2");
+  w.lowres = bd.conv("encoder.upsample_lowres");
+  w.fuse = bd.conv("encoder.fuse_lowres");
+  for (int l = 0; l < 5; ++l) {
+    const std::string f = "decoder.fusions." + std::to_string(l);
+    if (l != 0) w.convs[l] = bd.pk("decoder.convs." + std::to_string(l) + ".conv.weight");
+    w.res[l][0] = {bd.conv(f + ".resnet1.conv1"), bd.conv(f + ".resnet1.conv2")};
+    w.res[l][1] = {bd.conv(f + ".resnet2.conv1"), bd.conv(f + ".resnet2.conv2")};
+    w.out[l] = {bd.pk(l != 0 ? f + ".deconv_out_conv" : f + ".out_conv.weight"), bd.p32(f + ".out_conv.bias")};
+  }
+  w.conv0 = bd.conv("head.conv0");
+  w.outconv_conv0 = bd.composed("head.outconv_conv0", false);
+  w.deconv = bd.conv("head.deconv");
+  w.deconv_conv1 = bd.composed("head.deconv_conv1");
+  w.conv1 = {bd.pk("head.conv1.weight", false), bd.p32("head.conv1.bias")};
+  w.conv_out = {bd.p32("head.conv_out.weight"), bd.p32("head.conv_out.bias")};
+  if (c.use_fov_head) {
+    if (c.has_fov_vit) {
+      w.down = bd.conv("fov.downsample_blocks.0.conv");
+      w.down_gemm = bd.pk("fov.downsample_blocks.0.conv.gemm", false);
+      w.fov_proj = bd.conv("fov.encoder_proj");
+    }
+    for (int i = 0; i < (c.has_fov_vit ? 3 : 4); ++i) w.head[i] = bd.conv("fov.head_blocks." + std::to_string(i) + ".conv");
+  }
+  return bd.status();
+}
+
 int model_create(md_device_t dev, const ModelCfg& cfg, md_model_t* out) {
   if (!dev || !out) MD_FAIL(MD_ERR_INVALID_ARG, "device/model pointer is null");
   if (!cfg.iv.same_arch(cfg.pv) || (cfg.use_fov_head && cfg.has_fov_vit && !cfg.fv.same_arch(cfg.pv)))
@@ -493,96 +635,16 @@ int model_create(md_device_t dev, const ModelCfg& cfg, md_model_t* out) {
     return fail(MD_ERR_UNSUPPORTED);
   }
 
-  // ---- parameters: fp32 master arena ----
-  m->params = depth_pro_param_specs(cfg, MD_INIT_REFERENCE);
-  size_t off = 0;
-  std::vector<size_t> offs;
-  for (size_t i = 0; i < m->params.size(); ++i) {
-    m->pindex[m->params[i].name] = (int)i;
-    offs.push_back(off);
-    off += align_up(m->params[i].count() * 4, 256);
-  }
-  m->w32_bytes = off;
-  if (hipMalloc((void**)&m->w32_base, m->w32_bytes) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the fp32 weights failed", m->w32_bytes);
-    return fail(MD_ERR_OOM);
-  }
-  (void)hipMemset(m->w32_base, 0, m->w32_bytes);
-  for (size_t i = 0; i < m->params.size(); ++i) m->w32.push_back((float*)(m->w32_base + offs[i]));
-
-  // ---- pack plan ----
-  const int D = cfg.pv.D, F = cfg.F;
-  const int* dims = cfg.pv.feat_dims;
+  // ---- parameters, packs, weight tables ----
+  int st = alloc_param_arena(m, depth_pro_param_specs(cfg, MD_INIT_REFERENCE));
+  if (st != MD_OK) return fail(st);
+  const int D = cfg.pv.D;
   const char* vnames[3] = {"encoder.patch_encoder", "encoder.image_encoder", "fov.encoder"};
   for (int gi = 0; gi < m->ngroups; ++gi) vit_add_packs(m, vnames[gi], cfg.pv);
-  auto pub = [&](const std::string& n, int din, int dout, int layers, int dint) {
-    const int inter = dint > 0 ? dint : dout;
-    add_pack(m, n + ".projection.weight", PACK_NK, inter, din, 1);
-    for (int l = 0; l < layers; ++l)
-      add_pack(m, n + ".upsample." + std::to_string(l) + ".weight", PACK_DECONV, l == 0 ? inter : dout, dout, 2);
-  };
-  pub("encoder.upsample_latent0", D, F, 3, dims[0]);
-  pub("encoder.upsample_latent1", D, dims[0], 2, 0);
-  // the last two k2s2 deconvolutions of each latent chain run as one k4s4 (their 2x intermediate is never written)
-  add_pack_deconv_pair(m, "encoder.upsample_latent0.upsample.1x2", "encoder.upsample_latent0.upsample.1.weight",
-                       "encoder.upsample_latent0.upsample.2.weight", F, F, F);
-  add_pack_deconv_pair(m, "encoder.upsample_latent1.upsample.0x1", "encoder.upsample_latent1.upsample.0.weight",
-                       "encoder.upsample_latent1.upsample.1.weight", dims[0], dims[0], dims[0]);
-  pub("encoder.upsample0", D, dims[1], 1, 0);
-  pub("encoder.upsample1", D, dims[2], 1, 0);
-  pub("encoder.upsample2", D, dims[3], 1, 0);
-  add_pack(m, "encoder.upsample_lowres.weight", PACK_DECONV, cfg.iv.D, dims[3], 2);
-  add_pack(m, "encoder.fuse_lowres.weight", PACK_NK, dims[3], 2 * dims[3], 1);
-  const int ddims[5] = {F, dims[0], dims[1], dims[2], dims[3]};
-  for (int l = 1; l < 5; ++l) add_pack(m, "decoder.convs." + std::to_string(l) + ".conv.weight", PACK_CONV3, F, ddims[l], 3);
-  for (int l = 0; l < 5; ++l) {
-    const std::string f = "decoder.fusions." + std::to_string(l);
-    for (const char* r : {"resnet1", "resnet2"}) {
-      add_pack(m, f + "." + r + ".conv1.weight", PACK_CONV3, F, F, 3);
-      add_pack(m, f + "." + r + ".conv2.weight", PACK_CONV3, F, F, 3);
-    }
-    if (l != 0)
-      add_pack_composed(m, f + ".deconv_out_conv", f + ".deconv.weight", f + ".out_conv.weight", F, F);
-    else
-      add_pack(m, f + ".out_conv.weight", PACK_NK, F, F, 1);
-  }
-  add_pack(m, "head.conv0.weight", PACK_CONV3, F / 2, F, 3);
-  add_pack_c1c3(m, "head.outconv_conv0", "decoder.fusions.0.out_conv", "head.conv0", F, F, F / 2);
-  add_pack(m, "head.deconv.weight", PACK_DECONV, F / 2, F / 2, 2);
-  add_pack_head_fused(m, "head.deconv_conv1", "head.deconv", "head.conv1", F / 2, F / 2, 32);
-  add_pack(m, "head.conv1.weight", PACK_CONV3, 32, F / 2, 3);  // head_debug's un-fused conv1 (mod.rs:292); 74 KB
-  if (cfg.use_fov_head) {
-    if (cfg.has_fov_vit) {
-      add_pack(m, "fov.encoder_proj.weight", PACK_NK, F / 2, cfg.fv.D, 1);
-      add_pack(m, "fov.downsample_blocks.0.conv.weight", PACK_DIRECT, F / 2, F, 3, true);
-      // the same weight as an implicit-GEMM operand: the stride-2 downsample of the lowres feature (fov.rs:79-87,185) is 2.7 GFLOP at B = 8 and
-      // took 374 us as a direct convolution (one wave per output pixel) -- the MFMA family's stride-2 3x3 form does it in a tenth of that
-      add_pack_as(m, "fov.downsample_blocks.0.conv.gemm", "fov.downsample_blocks.0.conv.weight", PACK_CONV3, F / 2, F, 3);
-      add_pack(m, "fov.head_blocks.0.conv.weight", PACK_DIRECT, F / 4, F / 2, 3, true);
-      add_pack(m, "fov.head_blocks.1.conv.weight", PACK_DIRECT, F / 8, F / 4, 3, true);
-      add_pack(m, "fov.head_blocks.2.conv.weight", PACK_DIRECT, 1, F / 8, 6, true);
-    } else {
-      add_pack(m, "fov.head_blocks.0.conv.weight", PACK_DIRECT, F / 2, F, 3, true);
-      add_pack(m, "fov.head_blocks.1.conv.weight", PACK_DIRECT, F / 4, F / 2, 3, true);
-      add_pack(m, "fov.head_blocks.2.conv.weight", PACK_DIRECT, F / 8, F / 4, 3, true);
-      add_pack(m, "fov.head_blocks.3.conv.weight", PACK_DIRECT, 1, F / 8, 6, true);
-    }
-  }
-  size_t poff = 0;
-  for (auto& e : m->packs) {
-    e.dst = (void*)poff;  // offset for now
-    poff += align_up(e.bytes + 256, 256);
-  }
-  m->wpk_bytes = poff;
-  if (hipMalloc((void**)&m->wpk_base, m->wpk_bytes) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the packed weights failed", m->wpk_bytes);
-    return fail(MD_ERR_OOM);
-  }
-  (void)hipMemset(m->wpk_base, 0, m->wpk_bytes);
-  for (auto& e : m->packs) e.dst = m->wpk_base + (size_t)e.dst;
-
-  // ---- ViT weight tables ----
+  dp_add_packs(m);
+  if ((st = place_packs(m)) != MD_OK) return fail(st);
   for (int gi = 0; gi < m->ngroups; ++gi) vit_bind(m, vnames[gi], cfg.pv.depth, m->vit[gi]);
+  if ((st = dp_bind(m)) != MD_OK) return fail(st);
   if (m->ln_fold_can) {  // c / d of every block's two folded LayerNorms: [group][block][qkv_c 3D | qkv_d 3D | fc1_c 4D | fc1_d 4D]
     const size_t per_blk = (size_t)14 * D;
     if (hipMalloc((void**)&m->lnfold_base, ((size_t)m->ngroups * cfg.pv.depth * per_blk + 4 * D) * 4) != hipSuccess ||
@@ -598,25 +660,7 @@ int model_create(md_device_t dev, const ModelCfg& cfg, md_model_t* out) {
       }
   }
 
-  // ---- workspace ----
-  m->buf = new md_model_s::Buffers();
-  size_t need = 0;
-  plan_workspace(m, true, &need);
-  if (hipMalloc((void**)&m->ws.base, need) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the workspace failed (max_batch=%d)", need, cfg.max_batch);
-    return fail(MD_ERR_OOM);
-  }
-  m->ws.cap = need;
-  if (hipMemset(m->ws.base, 0, need) != hipSuccess) {  // padding rows/channels/keys must be finite zeros
-    set_error("hipMemset of the workspace failed");
-    return fail(MD_ERR_HIP);
-  }
-  int st = plan_workspace(m, false, nullptr);
-  if (st != MD_OK) return fail(st);
-  if (m->prec == MD_PREC_BF16 && (st = attention_asm_prepare()) != MD_OK) return fail(st);  // the code object loads here, never inside a capture
-  if (hipMalloc(&m->zero_page, 4096) != hipSuccess) return fail(MD_ERR_OOM);
-  (void)hipMemset(m->zero_page, 0, 4096);
-  (void)hipDeviceSynchronize();
+  if ((st = alloc_workspace(m)) != MD_OK) return fail(st);
   *out = m;
   return MD_OK;
 }
@@ -674,6 +718,7 @@ int model_fork(md_model_t src, md_model_t* out) {
   m->ngroups = root->ngroups;
   m->ln_fold_can = root->ln_fold_can; m->ln_fold_opt = root->ln_fold_opt; m->lnfold_base = root->lnfold_base;
   for (int g = 0; g < 3; ++g) m->vit[g] = root->vit[g];
+  m->dp = root->dp;
   m->head_b_host = root->head_b_host;
   m->S = root->S; m->win = root->win; m->g = root->g; m->P = root->P; m->NT = root->NT; m->SS = root->SS; m->kpad = root->kpad;
   m->steps0 = root->steps0; m->stride0 = root->stride0; m->steps1 = root->steps1; m->stride1 = root->stride1;
@@ -690,21 +735,8 @@ int model_fork(md_model_t src, md_model_t* out) {
     set_error("hipStreamCreate failed");
     return fail(MD_ERR_HIP);
   }
-  m->buf = new md_model_s::Buffers();
-  size_t need = 0;
-  plan_workspace(m, true, &need);
-  if (hipMalloc((void**)&m->ws.base, need) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the fork's workspace failed (max_batch=%d)", need, m->cfg.max_batch);
-    return fail(MD_ERR_OOM);
-  }
-  m->ws.cap = need;
-  if (hipMemset(m->ws.base, 0, need) != hipSuccess) return fail(MD_ERR_HIP);  // padding rows / channels / keys: finite zeros
-  int st = plan_workspace(m, false, nullptr);
+  const int st = alloc_workspace(m);
   if (st != MD_OK) return fail(st);
-  if (m->prec == MD_PREC_BF16 && (st = attention_asm_prepare()) != MD_OK) return fail(st);  // the code object loads here, never inside a capture
-  if (hipMalloc(&m->zero_page, 4096) != hipSuccess) return fail(MD_ERR_OOM);
-  (void)hipMemset(m->zero_page, 0, 4096);
-  (void)hipDeviceSynchronize();
   *out = m;
   return MD_OK;
 }
@@ -712,7 +744,7 @@ int model_fork(md_model_t src, md_model_t* out) {
 int model_init_seeded(md_model_t m, uint64_t seed, int scheme) {
   if (scheme != MD_INIT_REFERENCE && scheme != MD_INIT_PARITY) MD_FAIL(MD_ERR_INVALID_ARG, "unknown init scheme %d", scheme);
   MD_HIP(hipSetDevice(m->dev->ordinal));
-  std::vector<ParamSpec> specs = depth_pro_param_specs(m->cfg, scheme);
+  std::vector<ParamSpec> specs = m->kind == 1 ? da3_param_specs(da3_cfg(m), scheme) : depth_pro_param_specs(m->cfg, scheme);
   if (specs.size() != m->params.size()) MD_FAIL(MD_ERR_FORMAT, "internal: inventory mismatch");
   std::vector<float> tmp;
   for (size_t i = 0; i < specs.size(); ++i) {
@@ -1272,40 +1304,38 @@ static int run_encoder_tail(Run& r, const md_model_s::IndexSet& ix) {
   const int* dims = c.pv.feat_dims;
   const int hi = m->mh_hi, mid = m->mh_mid;
   const long Mhi = (long)B * hi * hi, Mmid = (long)B * mid * mid, Mlo = (long)B * g * g;
-  auto W = [&](const char* n) { return PK(m, n); };
+  const DepthProW& w = m->dp;
   // latent0: 1x1 (D -> dims0) then 3 deconvs -> F @ 8x (encoder.rs:146-151,423)
-  MD_TRY(gemm_rows(r, "enc_proj", b->hook[0], D, ix.hi, Mhi, W("encoder.upsample_latent0.projection.weight"), dims[0], D,
+  MD_TRY(gemm_rows(r, "enc_proj", b->hook[0], D, ix.hi, Mhi, w.enc_proj[0], dims[0], D,
                    nullptr, b->l0p, cpad(m, dims[0])));
-  MD_TRY(deconv2(r, "enc_deconv", b->l0p, cpad(m, dims[0]), nullptr, hi, hi, W("encoder.upsample_latent0.upsample.0.weight"),
+  MD_TRY(deconv2(r, "enc_deconv", b->l0p, cpad(m, dims[0]), nullptr, hi, hi, w.enc_up[0],
                  cpad(m, dims[0]), F, nullptr, b->l0a, cpad(m, F), 0));
   // upsample.1 and upsample.2 (k2s2, no bias, nothing between them) as ONE k4s4 deconvolution on their weight product
-  MD_TRY(deconv2(r, "enc_deconv", b->l0a, cpad(m, F), nullptr, 2 * hi, 2 * hi, W("encoder.upsample_latent0.upsample.1x2"),
+  MD_TRY(deconv2(r, "enc_deconv", b->l0a, cpad(m, F), nullptr, 2 * hi, 2 * hi, w.latent0_1x2,
                  cpad(m, F), F, nullptr, b->enc0, cpad(m, F), 0, b->enc0r, 4, 3));
   // latent1: 1x1 (D -> dims0), 2 deconvs @ 4x (encoder.rs:152,424): the two deconvolutions as one k4s4
-  MD_TRY(gemm_rows(r, "enc_proj", b->hook[1], D, ix.hi, Mhi, W("encoder.upsample_latent1.projection.weight"), dims[0], D,
+  MD_TRY(gemm_rows(r, "enc_proj", b->hook[1], D, ix.hi, Mhi, w.enc_proj[1], dims[0], D,
                    nullptr, b->l1p, cpad(m, dims[0])));
-  MD_TRY(deconv2(r, "enc_deconv", b->l1p, cpad(m, dims[0]), nullptr, hi, hi, W("encoder.upsample_latent1.upsample.0x1"),
+  MD_TRY(deconv2(r, "enc_deconv", b->l1p, cpad(m, dims[0]), nullptr, hi, hi, w.enc_up[1],
                  cpad(m, dims[0]), dims[0], nullptr, b->enc1, cpad(m, dims[0]), 0, nullptr, 4, 3));
   // x0 (encoder.rs:153,425)
-  MD_TRY(gemm_rows(r, "enc_proj", b->tok, D, ix.hi, Mhi, W("encoder.upsample0.projection.weight"), dims[1], D, nullptr,
+  MD_TRY(gemm_rows(r, "enc_proj", b->tok, D, ix.hi, Mhi, w.enc_proj[2], dims[1], D, nullptr,
                    b->x0p, cpad(m, dims[1])));
-  MD_TRY(deconv2(r, "enc_deconv", b->x0p, cpad(m, dims[1]), nullptr, hi, hi, W("encoder.upsample0.upsample.0.weight"),
+  MD_TRY(deconv2(r, "enc_deconv", b->x0p, cpad(m, dims[1]), nullptr, hi, hi, w.enc_up[2],
                  cpad(m, dims[1]), dims[1], nullptr, b->enc2, cpad(m, dims[1]), 0));
   // x1 (encoder.rs:154,426)
-  MD_TRY(gemm_rows(r, "enc_proj", b->tok, D, ix.mid, Mmid, W("encoder.upsample1.projection.weight"), dims[2], D, nullptr,
+  MD_TRY(gemm_rows(r, "enc_proj", b->tok, D, ix.mid, Mmid, w.enc_proj[3], dims[2], D, nullptr,
                    b->x1p, cpad(m, dims[2])));
-  MD_TRY(deconv2(r, "enc_deconv", b->x1p, cpad(m, dims[2]), nullptr, mid, mid, W("encoder.upsample1.upsample.0.weight"),
+  MD_TRY(deconv2(r, "enc_deconv", b->x1p, cpad(m, dims[2]), nullptr, mid, mid, w.enc_up[3],
                  cpad(m, dims[2]), dims[2], nullptr, b->enc3, cpad(m, dims[2]), 0));
   // x2 + global image features -> cat -> fuse (encoder.rs:409-421)
   const int catld = 2 * cpad(m, dims[3]);
-  MD_TRY(gemm_rows(r, "enc_proj", b->tok, D, ix.x2, Mlo, W("encoder.upsample2.projection.weight"), dims[3], D, nullptr,
+  MD_TRY(gemm_rows(r, "enc_proj", b->tok, D, ix.x2, Mlo, w.enc_proj[4], dims[3], D, nullptr,
                    b->x2p, cpad(m, dims[3])));
-  MD_TRY(deconv2(r, "enc_deconv", b->x2p, cpad(m, dims[3]), nullptr, g, g, W("encoder.upsample2.upsample.0.weight"),
+  MD_TRY(deconv2(r, "enc_deconv", b->x2p, cpad(m, dims[3]), nullptr, g, g, w.enc_up[4],
                  cpad(m, dims[3]), dims[3], nullptr, b->cat, catld, 0));
-  MD_TRY(deconv2(r, "enc_deconv", b->tok, D, ix.img, g, g, W("encoder.upsample_lowres.weight"), D, dims[3],
-                 P32(m, "encoder.upsample_lowres.bias"), b->cat, catld, cpad(m, dims[3])));
-  MD_TRY(gemm_rows(r, "enc_fuse", b->cat, catld, nullptr, Mlo * 4, W("encoder.fuse_lowres.weight"), dims[3], catld,
-                   P32(m, "encoder.fuse_lowres.bias"), b->enc4, cpad(m, dims[3])));
+  MD_TRY(deconv2(r, "enc_deconv", b->tok, D, ix.img, g, g, w.lowres.w, D, dims[3], w.lowres.b, b->cat, catld, cpad(m, dims[3])));
+  MD_TRY(gemm_rows(r, "enc_fuse", b->cat, catld, nullptr, Mlo * 4, w.fuse.w, dims[3], catld, w.fuse.b, b->enc4, cpad(m, dims[3])));
   if (m->taps_enabled) {
     MD_TRY(r.tap_nhwc("encoder_feature_0", b->enc0, F, 8 * hi, 8 * hi, cpad(m, F)));
     MD_TRY(r.tap_nhwc("encoder_feature_1", b->enc1, dims[0], 4 * hi, 4 * hi, cpad(m, dims[0])));
@@ -1326,27 +1356,17 @@ static int run_decoder_head(Run& r, bool decoder_only = false) {
   level_sizes(m, hw);
   const int ddims[5] = {F, dims[0], dims[1], dims[2], dims[3]};
   const void* enc[5] = {b->enc0, b->enc1, b->enc2, b->enc3, b->enc4};
-  auto W = [&](const std::string& n) { return PK(m, n); };
-  auto Bi = [&](const std::string& n) { return P32(m, n); };
-  // ResidualBlock (decoder.rs:74-87): out = x + conv2(relu(conv1(relu(x)))) [+ extra]
-  auto resblock = [&](const std::string& name, int l, const void* x, const void* xr, const void* extra, void* t,
-                      void* out, void* out_relu) -> int {
-    MD_TRY(conv3(r, "dec_conv3x3", xr, hw[l], hw[l], Fp, W(name + ".conv1.weight"), Bi(name + ".conv1.bias"), F, t, Fp,
-                 ACT_RELU, nullptr, nullptr, nullptr));
-    return conv3(r, "dec_conv3x3", t, hw[l], hw[l], Fp, W(name + ".conv2.weight"), Bi(name + ".conv2.bias"), F, out, Fp,
-                 ACT_NONE, x, extra, out_relu);
-  };
-  const bool fused_c0 = PK(m, "head.outconv_conv0.weight") != nullptr && hw[0] >= 2;
+  const DepthProW& w = m->dp;
+  const bool fused_c0 = w.outconv_conv0.w != nullptr && hw[0] >= 2;
   const void* feats = nullptr;
   for (int l = 4; l >= 0; --l) {
-    const std::string f = "decoder.fusions." + std::to_string(l);
     const void *pj, *pjr;
     if (l == 0) {  // convs[0] is the identity (decoder.rs:155-165)
       pj = b->enc0;
       pjr = b->enc0r;
     } else {
-      MD_TRY(conv3(r, "dec_conv3x3", enc[l], hw[l], hw[l], cpad(m, ddims[l]), W("decoder.convs." + std::to_string(l) + ".conv.weight"),
-                   nullptr, F, b->proj[l], Fp, ACT_NONE, nullptr, nullptr, b->projr[l]));
+      const ConvW cv{w.convs[l], nullptr};
+      MD_TRY(conv3(r, "dec_conv3x3", enc[l], hw[l], hw[l], cpad(m, ddims[l]), &cv, F, b->proj[l], Fp, ACT_NONE, nullptr, nullptr, b->projr[l]));
       pj = b->proj[l];
       pjr = b->projr[l];
     }
@@ -1356,21 +1376,20 @@ static int run_decoder_head(Run& r, bool decoder_only = false) {
       x = pj;
       xr = pjr;
     } else {
-      MD_TRY(resblock(f + ".resnet1", l, pj, pjr, feats, b->dt[l], b->dx[l], b->dxr[l]));
+      MD_TRY(residual_unit(r, "dec_conv3x3", &w.res[l][0], 1, hw[l], hw[l], Fp, F, pj, pjr, false, feats, b->dt[l], b->dx[l], b->dxr[l]));
       x = b->dx[l];
       xr = b->dxr[l];
     }
-    MD_TRY(resblock(f + ".resnet2", l, x, xr, nullptr, b->dt[l], b->dy[l], nullptr));
+    MD_TRY(residual_unit(r, "dec_conv3x3", &w.res[l][1], 1, hw[l], hw[l], Fp, F, x, xr, false, nullptr, b->dt[l], b->dy[l], nullptr));
     int ohw = hw[l];
     if (l != 0) {
       // deconv (no bias) then 1x1 out_conv (decoder.rs:124-141): one GEMM on the weight product packed at commit
-      MD_TRY(deconv2(r, "dec_deconv_out", b->dy[l], Fp, nullptr, hw[l], hw[l], W(f + ".deconv_out_conv"), Fp, F,
-                     Bi(f + ".out_conv.bias"), b->df[l], Fp, 0, nullptr, 2, 3));
+      MD_TRY(deconv2(r, "dec_deconv_out", b->dy[l], Fp, nullptr, hw[l], hw[l], w.out[l].w, Fp, F, w.out[l].b, b->df[l], Fp, 0, nullptr, 2, 3));
       ohw = 2 * hw[l];
     } else if (!fused_c0 || m->taps_enabled) {  // level 0: the product path composes this 1x1 into head.conv0 (below);
                                                 // its output exists only for the taps
-      MD_TRY(gemm_rows(r, "dec_out_conv", b->dy[l], Fp, nullptr, (long)r.B * ohw * ohw, W(f + ".out_conv.weight"), F, Fp,
-                       Bi(f + ".out_conv.bias"), b->df[l], Fp));
+      MD_TRY(gemm_rows(r, "dec_out_conv", b->dy[l], Fp, nullptr, (long)r.B * ohw * ohw, w.out[l].w, F, Fp, w.out[l].b, b->df[l],
+                       Fp));
     }
     feats = b->df[l];
     if (m->taps_enabled) {
@@ -1385,32 +1404,30 @@ static int run_decoder_head(Run& r, bool decoder_only = false) {
   if (fused_c0) {
     // out_conv 1x1 (+bias) -> conv0 3x3 (decoder.rs:137 -> mod.rs:105) as ONE 3x3 convolution on the last residual block's
     // output: the convolution adds the interior bias class, the border pixels get their class afterwards
-    const float* bias9 = (const float*)PK(m, "head.outconv_conv0.bias");
-    MD_TRY(conv3(r, "head_conv0", b->dy[0], hw[0], hw[0], Fp, W("head.outconv_conv0.weight"), bias9 + 4 * F2, F2, b->h0, F2p,
-                 ACT_NONE, nullptr, nullptr, nullptr, 3));
+    const float* bias9 = w.outconv_conv0.b;
+    const ConvW c0{w.outconv_conv0.w, bias9 + 4 * F2};
+    MD_TRY(conv3(r, "head_conv0", b->dy[0], hw[0], hw[0], Fp, &c0, F2, b->h0, F2p, ACT_NONE, nullptr, nullptr, nullptr, 3));
     r.begin("head_conv0");
     MD_TRY(launch_border_bias_fix(b->h0, r.B, hw[0], hw[0], F2, F2p, bias9, m->prec, r.st));
     r.end();
   } else {
-    MD_TRY(conv3(r, "head_conv0", feats, hw[0], hw[0], Fp, W("head.conv0.weight"), Bi("head.conv0.bias"), F2, b->h0, F2p,
-                 ACT_NONE, nullptr, nullptr, nullptr));
+    MD_TRY(conv3(r, "head_conv0", feats, hw[0], hw[0], Fp, &w.conv0, F2, b->h0, F2p, ACT_NONE, nullptr, nullptr, nullptr));
   }
   if (m->taps_enabled) {
     // the deconv's output exists only as a debug tap: the product path below never materialises the 2x-resolution map
-    MD_TRY(deconv2(r, "head_deconv_tap", b->h0, F2p, nullptr, hw[0], hw[0], W("head.deconv.weight"), F2p, F2,
-                   Bi("head.deconv.bias"), b->h1, F2p, 0));
+    MD_TRY(deconv2(r, "head_deconv_tap", b->h0, F2p, nullptr, hw[0], hw[0], w.deconv.w, F2p, F2, w.deconv.b, b->h1, F2p, 0));
     MD_TRY(r.tap_nhwc("head_conv0", b->h0, F2, hw[0], hw[0], F2p));
     MD_TRY(r.tap_nhwc("head_deconv", b->h1, F2, 2 * hw[0], 2 * hw[0], F2p));
   }
   {
     // deconv k2s2 -> conv1 3x3 -> relu -> conv_out 1x1 -> relu (mod.rs:106-111) as ONE 3x3 convolution on conv0's output:
-    // deconv and conv1 have nothing between them, so their product is packed at commit (add_pack_head_fused) as a 3x3
+    // deconv and conv1 have nothing between them, so their product is packed at commit (add_pack_fused) as a 3x3
     // weight with 4 x 32 output columns, one 32-column group per output parity; the epilogue finishes the 1x1 tail.
     GemmParams p;
-    p.N = 4 * 32; p.ngroups = 1; p.g_rows[0] = r.B * hw[0] * hw[0]; p.W[0] = W("head.deconv_conv1.weight");
+    p.N = 4 * 32; p.ngroups = 1; p.g_rows[0] = r.B * hw[0] * hw[0]; p.W[0] = w.deconv_conv1.w;
     p.A = b->h0; p.cH = hw[0]; p.cW = hw[0]; p.zero_page = m->zero_page;
     split_conv_a(m, p, F2p, 3);
-    p.epi = EPI_HEAD_UP2; p.bias[0] = (const float*)PK(m, "head.deconv_conv1.bias"); p.head_w = Bi("head.conv_out.weight");
+    p.epi = EPI_HEAD_UP2; p.bias[0] = w.deconv_conv1.b; p.head_w = (const float*)w.conv_out.w;
     p.head_b = model_root(m)->head_b_host;
     p.out = b->canonical;
     r.begin("head_tail_fused");
@@ -1561,7 +1578,8 @@ int model_head_debug(md_model_t m, const md_nchw_view* feature, int B, int in_ki
   const int F = m->cfg.F, Fp = cpad(m, F), F2 = F / 2, F2p = cpad(m, F2), C1 = 32, C1p = cpad(m, C1), s0 = hw[0];
   if (feature->channels != F || feature->height != s0 || feature->width != s0)
     MD_FAIL(MD_ERR_SHAPE, "feature is [B,%d,%d,%d]; this model's head takes [B,%d,%d,%d]", feature->channels, feature->height, feature->width, F, s0, s0);
-  if (!PK(m, "head.conv1.weight")) MD_FAIL(MD_ERR_UNSUPPORTED, "head_debug: the un-fused conv1 operand is not packed");
+  const DepthProW& w = m->dp;
+  if (!w.conv1.w) MD_FAIL(MD_ERR_UNSUPPORTED, "head_debug: the un-fused conv1 operand is not packed");
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = model_stream(m, stream);
   md_model_s::Buffers* b = m->buf;
@@ -1575,18 +1593,14 @@ int model_head_debug(md_model_t m, const md_nchw_view* feature, int B, int in_ki
   void* c1r = (char*)maps.p + map_bytes;
   float* pre = (float*)tails.p;
   float* can = pre + px1;
-  auto W = [&](const char* n) { return PK(m, n); };
-  auto Bi = [&](const char* n) { return P32(m, n); };
   MD_TRY(stage_nchw_feature(m, st, *feature, B, in_kind, (float*)stage.p, b->df[0], nullptr, Fp));
   Run r{m, st, B};
   DebugTapScope tap_scope(m);
   TapsOn taps(m);
-  MD_TRY(conv3(r, "head_conv0", b->df[0], s0, s0, Fp, W("head.conv0.weight"), Bi("head.conv0.bias"), F2, b->h0, F2p, ACT_NONE, nullptr,
-               nullptr, nullptr));
-  MD_TRY(deconv2(r, "head_deconv_tap", b->h0, F2p, nullptr, s0, s0, W("head.deconv.weight"), F2p, F2, Bi("head.deconv.bias"), b->h1, F2p, 0));
-  MD_TRY(conv3(r, "head_conv1_debug", b->h1, 2 * s0, 2 * s0, F2p, W("head.conv1.weight"), Bi("head.conv1.bias"), C1, c1, C1p, ACT_NONE,
-               nullptr, nullptr, c1r));
-  MD_TRY(launch_head_tail_debug(c1r, C1p, (long)px1, C1, Bi("head.conv_out.weight"), Bi("head.conv_out.bias"), pre, can, m->prec, st));
+  MD_TRY(conv3(r, "head_conv0", b->df[0], s0, s0, Fp, &w.conv0, F2, b->h0, F2p, ACT_NONE, nullptr, nullptr, nullptr));
+  MD_TRY(deconv2(r, "head_deconv_tap", b->h0, F2p, nullptr, s0, s0, w.deconv.w, F2p, F2, w.deconv.b, b->h1, F2p, 0));
+  MD_TRY(conv3(r, "head_conv1_debug", b->h1, 2 * s0, 2 * s0, F2p, &w.conv1, C1, c1, C1p, ACT_NONE, nullptr, nullptr, c1r));
+  MD_TRY(launch_head_tail_debug(c1r, C1p, (long)px1, C1, (const float*)w.conv_out.w, w.conv_out.b, pre, can, m->prec, st));
   MD_TRY(r.tap_nhwc("head_conv0", b->h0, F2, s0, s0, F2p));
   MD_TRY(r.tap_nhwc("head_deconv", b->h1, F2, 2 * s0, 2 * s0, F2p));
   MD_TRY(r.tap_nhwc("head_conv1", c1, C1, 2 * s0, 2 * s0, C1p));
@@ -1632,8 +1646,7 @@ static int run_fov(Run& r, const md_model_s::IndexSet& ix) {
   level_sizes(m, hw);
   const void* lowres = b->proj[4];  // convs[4](enc[4]) (decoder.rs:207-208)
   const int Fp = cpad(m, F);
-  auto Wd = [&](const std::string& n) { return (const float*)PK(m, n); };
-  auto Bi = [&](const std::string& n) { return P32(m, n); };
+  const DepthProW& w = m->dp;
   if (Fp != F) MD_FAIL(MD_ERR_UNSUPPORTED, "fov: decoder_features must be a multiple of the MFMA k-tile");
   float* stage[4] = {b->fv0, b->fv1, b->fv2, b->fv3};
   float* sa = b->fvr;
@@ -1642,26 +1655,24 @@ static int run_fov(Run& r, const md_model_s::IndexSet& ix) {
     r.begin("fov_head");
     // fov.rs:178-227: downsample(lowres) + Linear(tokens) -> head convs
     int h = (hw[4] + 2 - 3) / 2 + 1;
-    if (PK(m, "fov.downsample_blocks.0.conv.gemm") && (F / 2) % 4 == 0) {
+    if (w.down_gemm && (F / 2) % 4 == 0) {
       GemmParams p;
       p.N = F / 2; p.ngroups = 1; p.g_rows[0] = B * h * h;
-      p.W[0] = PK(m, "fov.downsample_blocks.0.conv.gemm"); p.bias[0] = Bi("fov.downsample_blocks.0.conv.bias");
+      p.W[0] = w.down_gemm; p.bias[0] = w.down.b;
       p.A = lowres; p.cH = hw[4]; p.cW = hw[4]; p.cOH = h; p.cOW = h; p.cstride = 2; p.zero_page = m->zero_page;
       split_conv_a(m, p, Fp, 0);
       p.epi = EPI_STORE; p.act = ACT_RELU; p.out_f32 = 1; p.out = stage[0]; p.ldo = F / 2;
       MD_TRY(launch_gemm(p, A_CONV3, m->prec, TILE_AUTO, r.st));
     } else {
-      MD_TRY(launch_conv_direct(lowres, m->prec, nullptr, B, hw[4], hw[4], F, Wd("fov.downsample_blocks.0.conv.weight"),
-                                Bi("fov.downsample_blocks.0.conv.bias"), F / 2, 3, 2, 1, 1, stage[0], r.st));
+      MD_TRY(launch_conv_direct(lowres, m->prec, nullptr, B, hw[4], hw[4], F, (const float*)w.down.w, w.down.b, F / 2, 3, 2, 1, 1, stage[0], r.st));
     }
     if (h != g) MD_FAIL(MD_ERR_UNSUPPORTED, "fov: downsampled lowres %d does not match the token grid %d", h, g);
     r.end();
-    MD_TRY(gemm_rows(r, "fov_proj", b->tok, c.pv.D, ix.fov, (long)B * m->P, PK(m, "fov.encoder_proj.weight"), F / 2, c.pv.D,
-                     Bi("fov.encoder_proj.bias"), b->fovproj, F / 2, 1));
+    MD_TRY(gemm_rows(r, "fov_proj", b->tok, c.pv.D, ix.fov, (long)B * m->P, w.fov_proj.w, F / 2, c.pv.D, w.fov_proj.b,
+                     b->fovproj, F / 2, 1));
     float* cur = stage[0];
     int ch = F / 2;
     const float* add = b->fovproj;
-    const char* names[3] = {"fov.head_blocks.0.conv", "fov.head_blocks.1.conv", "fov.head_blocks.2.conv"};
     const int couts[3] = {F / 4, F / 8, 1}, ks[3] = {3, 3, 6}, strides[3] = {2, 2, 1}, pads[3] = {1, 1, 0},
               relus[3] = {1, 1, 0};
     for (int i = 0; i < 3; ++i) {
@@ -1671,8 +1682,7 @@ static int run_fov(Run& r, const md_model_s::IndexSet& ix) {
       }
       float* out = i == 2 ? b->fov_deg : stage[i + 1];
       r.begin("fov_head");
-      MD_TRY(launch_conv_direct(cur, MD_PREC_F32, add, B, h, h, ch, Wd(std::string(names[i]) + ".weight"),
-                                Bi(std::string(names[i]) + ".bias"), couts[i], ks[i], strides[i], pads[i], relus[i], out,
+      MD_TRY(launch_conv_direct(cur, MD_PREC_F32, add, B, h, h, ch, (const float*)w.head[i].w, w.head[i].b, couts[i], ks[i], strides[i], pads[i], relus[i], out,
                                 r.st));
       r.end();
       add = nullptr;
@@ -1683,8 +1693,6 @@ static int run_fov(Run& r, const md_model_s::IndexSet& ix) {
     if (h != 1) MD_FAIL(MD_ERR_UNSUPPORTED, "fov head ends at %dx%d, expected 1x1", h, h);
   } else {
     // fov.rs:118-155: four head blocks straight on the lowres feature
-    const char* names[4] = {"fov.head_blocks.0.conv", "fov.head_blocks.1.conv", "fov.head_blocks.2.conv",
-                            "fov.head_blocks.3.conv"};
     const int couts[4] = {F / 2, F / 4, F / 8, 1}, ks[4] = {3, 3, 3, 6}, strides[4] = {2, 2, 2, 1}, pads[4] = {1, 1, 1, 0},
               relus[4] = {1, 1, 1, 0};
     const void* cur = lowres;
@@ -1698,8 +1706,7 @@ static int run_fov(Run& r, const md_model_s::IndexSet& ix) {
       }
       float* out = i == 3 ? b->fov_deg : stage[i];
       r.begin("fov_head");
-      MD_TRY(launch_conv_direct(cur, cur_prec, nullptr, B, h, h, ch, Wd(std::string(names[i]) + ".weight"),
-                                Bi(std::string(names[i]) + ".bias"), couts[i], ks[i], strides[i], pads[i], relus[i], out,
+      MD_TRY(launch_conv_direct(cur, cur_prec, nullptr, B, h, h, ch, (const float*)w.head[i].w, w.head[i].b, couts[i], ks[i], strides[i], pads[i], relus[i], out,
                                 r.st));
       r.end();
       h = (h + 2 * pads[i] - ks[i]) / strides[i] + 1;

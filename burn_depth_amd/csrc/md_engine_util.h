@@ -39,123 +39,91 @@ inline const void* PK(md_model_s* m, const std::string& name) {
   return it == m->pack_index.end() ? nullptr : m->packs[it->second].dst;
 }
 
-inline void add_pack(md_model_s* m, const std::string& name, int kind, int d0, int d1, int k, bool f32 = false) {
-  auto it = m->pindex.find(name);
+// ---- create scaffold shared by both models (md_engine.hip) ----
+// the zeroed fp32 master arena of `specs`: params, pindex, w32
+int alloc_param_arena(md_model_s* m, std::vector<ParamSpec> specs);
+// places every pack added so far in one zeroed arena (PackEntry::dst)
+int place_packs(md_model_s* m);
+
+// Fills the weight tables at create, once the packed arena is placed. A required name that is not there fails the create with
+// MD_ERR_FORMAT (status()); an optional one leaves its field null.
+struct Binder {
+  md_model_s* m;
+  std::string missing;  // the first required name that was not found
+  const void* pk(const std::string& n, bool required = true) { return need(PK(m, n), n, required); }
+  const float* p32(const std::string& n, bool required = true) { return need(P32(m, n), n, required); }
+  // `name`.weight packed (bias: + the fp32 `name`.bias)
+  ConvW conv(const std::string& name, bool bias = true) { return {pk(name + ".weight"), bias ? p32(name + ".bias") : nullptr}; }
+  // the composed packs: `name`.weight + their nine bias classes `name`.bias
+  ConvW composed(const std::string& name, bool required = true) {
+    return {pk(name + ".weight", required), (const float*)pk(name + ".bias", required)};
+  }
+  int status() const {
+    if (!missing.empty()) MD_FAIL(MD_ERR_FORMAT, "parameter `%s` is not in the model's inventory", missing.c_str());
+    return MD_OK;
+  }
+
+ private:
+  template <typename T>
+  T need(T p, const std::string& n, bool required) {
+    if (!p && required && missing.empty()) missing = n;
+    return p;
+  }
+};
+
+// the common tail of the add_pack* helpers: the entry's size, its name and its place in the plan
+inline void push_pack(md_model_s* m, const std::string& name, PackEntry e) {
+  e.bytes = pack_bytes(m, e);
+  m->pack_index[name] = (int)m->packs.size();
+  m->packs.push_back(e);
+}
+
+// `param` (default: `name` itself) packed under `name`: a second packed form of a parameter has a name of its own (e.g. a
+// convolution weight both as a direct-convolution and as an implicit-GEMM operand)
+inline void add_pack(md_model_s* m, const std::string& name, int kind, int d0, int d1, int k, bool f32 = false, const std::string& param = "") {
+  auto it = m->pindex.find(param.empty() ? name : param);
   if (it == m->pindex.end()) return;
   PackEntry e;
-  e.param = it->second;
-  e.kind = kind;
-  e.d0 = d0;
-  e.d1 = d1;
-  e.k = k;
+  e.param = it->second; e.kind = kind; e.d0 = d0; e.d1 = d1; e.k = k;
   e.f32 = f32 ? 1 : 0;
-  const int contraction = kind == PACK_NK ? d1 : kind == PACK_CONV3 ? d1 : kind == PACK_DECONV ? d0 : d1;
-  e.kp = f32 ? contraction : round_up(contraction, m->ke);
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name] = (int)m->packs.size();
-  m->packs.push_back(e);
-}
-
-// a second packed form of a parameter under a name of its own (e.g. a convolution weight both as a direct-convolution and as an
-// implicit-GEMM operand)
-inline void add_pack_as(md_model_s* m, const std::string& pack_name, const std::string& param, int kind, int d0, int d1, int k) {
-  auto it = m->pindex.find(param);
-  if (it == m->pindex.end()) return;
-  PackEntry e;
-  e.param = it->second;
-  e.kind = kind;
-  e.d0 = d0;
-  e.d1 = d1;
-  e.k = k;
-  e.f32 = 0;
   const int contraction = kind == PACK_DECONV ? d0 : d1;
-  e.kp = round_up(contraction, m->ke);
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[pack_name] = (int)m->packs.size();
-  m->packs.push_back(e);
+  e.kp = f32 ? contraction : round_up(contraction, m->ke);
+  push_pack(m, name, e);
 }
 
-// deconv k2s2 (no bias) followed by a 1x1 conv: packed as ONE deconv whose weight is their product
-// W'[ci][co][q] = sum_m Wd[ci][m][q] * Wo[co][m]  (decoder.rs:124-141 applies out_conv right after deconv)
-inline void add_pack_composed(md_model_s* m, const std::string& name, const std::string& deconv, const std::string& conv1x1,
-                              int cin, int cout) {
-  auto a = m->pindex.find(deconv), b = m->pindex.find(conv1x1);
-  if (a == m->pindex.end() || b == m->pindex.end()) return;
-  PackEntry e;
-  e.param = a->second;
-  e.param2 = b->second;
-  e.kind = PACK_DECONV;
-  e.d0 = cin;
-  e.d1 = cout;
-  e.k = 2;
-  e.kp = round_up(cin, m->ke);
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name] = (int)m->packs.size();
-  m->packs.push_back(e);
-}
-
-// depth head: deconv k2s2 (+bias) -> conv 3x3 (+bias) composed into one 3x3 conv with 4 * cout columns on the deconv's
-// input grid (`name`.weight, PACK_CONV3 layout) and nine position-class bias vectors (`name`.bias, f32 [9][cout])
-inline void add_pack_head_fused(md_model_s* m, const std::string& name, const std::string& deconv, const std::string& conv,
-                                int cin, int cmid, int cout) {
-  auto wd = m->pindex.find(deconv + ".weight"), bd = m->pindex.find(deconv + ".bias");
-  auto wc = m->pindex.find(conv + ".weight"), bc = m->pindex.find(conv + ".bias");
-  if (wd == m->pindex.end() || bd == m->pindex.end() || wc == m->pindex.end() || bc == m->pindex.end()) return;
-  PackEntry e;
-  e.param = wd->second; e.param2 = wc->second; e.param3 = bd->second; e.param4 = bc->second;
-  e.kind = PACK_HEAD_W;
-  e.d0 = cout; e.d1 = cin; e.k = cmid;
-  e.kp = round_up(cin, m->ke);
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name + ".weight"] = (int)m->packs.size();
-  m->packs.push_back(e);
-  e.kind = PACK_HEAD_B;
-  e.f32 = 1;
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name + ".bias"] = (int)m->packs.size();
-  m->packs.push_back(e);
-}
-
-// conv 1x1 (+bias) -> conv 3x3 pad 1 (+bias) composed into one 3x3 convolution (`name`.weight, PACK_CONV3 layout) and nine
-// position-class bias vectors (`name`.bias, f32 [9][cout]); c1 = the 1x1 conv [cmid, cin], c3 = the 3x3 conv [cout, cmid]
-inline void add_pack_c1c3(md_model_s* m, const std::string& name, const std::string& c1, const std::string& c3, int cin, int cmid,
-                          int cout) {
-  auto w1 = m->pindex.find(c1 + ".weight"), b1 = m->pindex.find(c1 + ".bias");
-  auto w3 = m->pindex.find(c3 + ".weight"), b3 = m->pindex.find(c3 + ".bias");
-  if (w1 == m->pindex.end() || b1 == m->pindex.end() || w3 == m->pindex.end() || b3 == m->pindex.end()) return;
-  PackEntry e;
-  e.param = w1->second; e.param2 = w3->second; e.param3 = b1->second; e.param4 = b3->second;
-  e.kind = PACK_C1C3_W;
-  e.d0 = cout; e.d1 = cin; e.k = cmid;
-  e.kp = round_up(cin, m->ke);
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name + ".weight"] = (int)m->packs.size();
-  m->packs.push_back(e);
-  e.kind = PACK_C1C3_B;
-  e.f32 = 1;
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name + ".bias"] = (int)m->packs.size();
-  m->packs.push_back(e);
-}
-
-// two bias-free k2s2 deconvolutions in a row (encoder.rs:146-152, nothing between them) = ONE k4s4 deconvolution on the
-// weight product W''[ci][co][2 dy1 + dy2][2 dx1 + dx2] = sum_m Wa[ci][m][dy1][dx1] * Wb[m][co][dy2][dx2]
-inline void add_pack_deconv_pair(md_model_s* m, const std::string& name, const std::string& a, const std::string& b, int cin,
-                                 int cmid, int cout) {
+// a bias-free deconv k2s2 and the layer behind it, packed as ONE deconvolution on their weight product. k == 2: a 1x1 conv [cout, cout]
+// behind it, W'[ci][co][q] = sum_m Wd[ci][m][q] * Wo[co][m] (decoder.rs:124-141 applies out_conv right after deconv); k == 4: a second
+// bias-free k2s2 deconvolution (encoder.rs:146-152, nothing between them) = ONE k4s4 deconvolution on the weight product
+// W''[ci][co][2 dy1 + dy2][2 dx1 + dx2] = sum_m Wa[ci][m][dy1][dx1] * Wb[m][co][dy2][dx2]
+inline void add_pack_product(md_model_s* m, const std::string& name, const std::string& a, const std::string& b, int k, int cin,
+                             int cmid, int cout) {
   auto wa = m->pindex.find(a), wb = m->pindex.find(b);
   if (wa == m->pindex.end() || wb == m->pindex.end()) return;
   PackEntry e;
-  e.param = wa->second;
-  e.param2 = wb->second;
-  e.param3 = cmid;  // PACK_DECONV with k == 4 and param2: the middle channel count rides here
-  e.kind = PACK_DECONV;
-  e.d0 = cin;
-  e.d1 = cout;
-  e.k = 4;
+  e.param = wa->second; e.param2 = wb->second;
+  if (k == 4) e.param3 = cmid;  // PACK_DECONV with k == 4 and param2: the middle channel count rides here
+  e.kind = PACK_DECONV; e.d0 = cin; e.d1 = cout; e.k = k;
   e.kp = round_up(cin, m->ke);
-  e.bytes = pack_bytes(m, e);
-  m->pack_index[name] = (int)m->packs.size();
-  m->packs.push_back(e);
+  push_pack(m, name, e);
+}
+
+// `first` (+bias) -> `second` (+bias), nothing between them, composed at commit into one 3x3 convolution (`name`.weight, PACK_CONV3
+// layout) and nine position-class bias vectors (`name`.bias, f32 [9][cout]). PACK_HEAD_W: the depth head's deconv k2s2 [cin, cmid] ->
+// conv 3x3 [cout, cmid] on the deconv's input grid with 4 * cout columns; PACK_C1C3_W: a conv 1x1 [cmid, cin] -> conv 3x3 pad 1
+inline void add_pack_fused(md_model_s* m, int kind, const std::string& name, const std::string& first, const std::string& second, int cin,
+                           int cmid, int cout) {
+  auto w1 = m->pindex.find(first + ".weight"), b1 = m->pindex.find(first + ".bias");
+  auto w2 = m->pindex.find(second + ".weight"), b2 = m->pindex.find(second + ".bias");
+  if (w1 == m->pindex.end() || b1 == m->pindex.end() || w2 == m->pindex.end() || b2 == m->pindex.end()) return;
+  PackEntry e;
+  e.param = w1->second; e.param2 = w2->second; e.param3 = b1->second; e.param4 = b2->second;
+  e.kind = kind;
+  e.d0 = cout; e.d1 = cin; e.k = cmid;
+  e.kp = round_up(cin, m->ke);
+  push_pack(m, name + ".weight", e);
+  e.kind = kind + 1;  // PACK_HEAD_B / PACK_C1C3_B
+  e.f32 = 1;
+  push_pack(m, name + ".bias", e);
 }
 
 // The graph layer of an infer entry: `body` through the model's GraphCache when graphs are on and the call is `eligible`. Timing /
@@ -295,20 +263,37 @@ inline int deconv2(Run& r, const char* name, const void* A, long lda, const int*
   return s;
 }
 
-// Conv2d 3x3 s1 p1 over NHWC as implicit GEMM (decoder.rs:55-72,167-175; mod.rs:78-87)
-inline int conv3(Run& r, const char* name, const void* in, int H, int W, int Cin_p, const void* Wp, const float* bias,
-          int Cout, void* out, long ldo, int act, const void* res1, const void* res2, void* out2, int terms = 0) {
+// Conv2d 3x3 s1 p1 over NHWC as implicit GEMM (decoder.rs:55-72,167-175; mod.rs:78-87). G > 1: weight set w[g] over images
+// [g*B, (g+1)*B) of `in` / `out` (`in_shared`: every group reads images [0, B) of `in`; `res1_shared`: the same for res1)
+inline int conv3(Run& r, const char* name, const void* in, int H, int W, int Cin_p, const ConvW* w, int Cout, void* out, long ldo,
+                 int act, const void* res1, const void* res2, void* out2, int terms = 0, int G = 1, bool in_shared = false,
+                 bool res1_shared = false) {
   GemmParams p;
-  p.N = Cout; p.ngroups = 1; p.g_rows[0] = r.B * H * W; p.W[0] = Wp;
+  const int M = r.B * H * W;
+  p.N = Cout; p.ngroups = G;
+  for (int g = 0; g < G; ++g) {
+    p.g_rows[g] = M; p.g_row0[g] = g * M; p.g_arow0[g] = in_shared ? 0 : g * M;
+    p.W[g] = w[g].w; p.bias[g] = w[g].b;
+  }
   p.A = in; p.cH = H; p.cW = W; p.zero_page = r.m->zero_page;
   split_conv_a(r.m, p, Cin_p, terms);
-  p.epi = EPI_STORE; p.act = act; p.bias[0] = bias; p.out = out; p.out2 = out2;
+  p.epi = EPI_STORE; p.act = act; p.out = out; p.out2 = out2;
   split_out(r.m, p, ldo, true);
   p.res1 = res1; p.res2 = res2; p.ldr = p.ldo; p.r_plane = (res1 || res2) ? p.o_plane : 0;
+  if (res1 && res1_shared && G > 1) p.res_mod = M;
   r.begin(name);
   int s = launch_gemm(p, A_CONV3, r.m->prec, TILE_AUTO, r.st);
   r.end();
   return s;
+}
+
+// ResidualBlock / ResidualConvUnit (decoder.rs:74-87, dpt.rs:1248-1252): out = x + conv2(relu(conv1(relu(x)))) [+ extra] on C
+// channels (Cp padded), `xr` = relu(x), `t` scratch; u[g] per weight group as in conv3 (`x_shared`: x and xr are shared)
+inline int residual_unit(Run& r, const char* name, const ResUnitW* u, int G, int H, int W, int Cp, int C, const void* x,
+                         const void* xr, bool x_shared, const void* extra, void* t, void* out, void* out_relu) {
+  const ConvW c1[2] = {u[0].c1, u[G - 1].c1}, c2[2] = {u[0].c2, u[G - 1].c2};
+  MD_TRY(conv3(r, name, xr, H, W, Cp, c1, C, t, Cp, ACT_RELU, nullptr, nullptr, nullptr, 0, G, x_shared));
+  return conv3(r, name, t, H, W, Cp, c2, C, out, Cp, ACT_NONE, x, extra, out_relu, 0, G, false, x_shared);
 }
 
 // fp32 attention as three launches: scores = q k^T (batched GEMM) -> row softmax -> P V^T^T (batched GEMM). qk [nseq*S, 2D] (q | k),
