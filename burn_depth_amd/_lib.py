@@ -46,6 +46,23 @@ class MdFrameOutputs(C.Structure):
                 ("focallength_px", C.c_void_p), ("fovy_rad", C.c_void_p)]
 
 
+class MdPointsOpts(C.Structure):
+    """md_points_opts (include/mi_depth.h)."""
+    _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_min", C.c_float),
+                ("edge_rtol", C.c_float), ("stride", C.c_int), ("world", C.c_int)]
+
+
+class MdPointsCameras(C.Structure):
+    """md_points_cameras (include/mi_depth.h)."""
+    _fields_ = [("intrinsics", C.c_void_p), ("extrinsics", C.c_void_p), ("focal_px", C.c_void_p)]
+
+
+class MdPointsOutputs(C.Structure):
+    """md_points_outputs (include/mi_depth.h)."""
+    _fields_ = [("point_map", C.c_void_p), ("mask", C.c_void_p), ("xyz", C.c_void_p), ("rgb", C.c_void_p), ("conf", C.c_void_p),
+                ("count", C.c_void_p), ("capacity", C.c_int64), ("depth", C.c_void_p)]
+
+
 class MdDa3Cfg(C.Structure):
     _fields_ = [("variant", C.c_char_p), ("image_size", C.c_int), ("precision", C.c_int), ("max_batch", C.c_int),
                 ("ln_eps", C.c_float), ("image_width", C.c_int)]
@@ -110,6 +127,10 @@ SYMBOLS = {
     "md_infer_from_rgb_with_focal": (_I, [_P, _P, C.c_size_t, _I, _I, _I, C.c_float, _P, _P, _P, _I, _P]),
     "md_frame_geometry": (_I, [_P, _I, _I, C.POINTER(MdFrameOpts), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "md_process_frame": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(MdFrameOpts), C.POINTER(MdFrameOutputs), _I, _P]),
+    "md_points_opts_default": (None, [C.POINTER(MdPointsOpts)]),
+    "md_op_unproject": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), _P]),
+    "md_infer_points": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
+                             C.POINTER(MdPointsOutputs), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

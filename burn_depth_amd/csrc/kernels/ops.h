@@ -34,6 +34,31 @@ int display_parts(const DisplayGeom& g);  // partial min / max pairs per frame (
 int launch_depth_display(const float* depth, const DisplayGeom& g, int normalize, int format, void* out, float* range, float2* parts,
                          hipStream_t s);
 
+// ---- point path (kernels/points.hip; md_op_unproject, md_infer_points) ----
+// depth [B,H,W] (+ confidence, + u8 rgb [B,H,W,3]) and pinhole cameras -> dense point map / mask and the ordered, compacted
+// cloud. Every pointer is a device pointer; the cameras are read in the kernels. K [B,3,3] or focal [B] (K = f, f, W/2, H/2);
+// E [B,3,4] world-to-camera when world = 1.
+struct PointsParams {
+  const float* depth = nullptr;
+  const float* conf = nullptr;
+  const uint8_t* rgb = nullptr;
+  const float *K = nullptr, *E = nullptr, *focal = nullptr;
+  int B = 0, H = 0, W = 0;
+  float off = 0.f, dmin = 0.f, dmax = 0.f, conf_min = 0.f, edge_rtol = 0.f;  // dmin / dmax already resolved (no 0 = default here)
+  int stride = 1, world = 0;
+  float* point_map = nullptr;
+  uint8_t* mask = nullptr;
+  float* xyz = nullptr;
+  uint8_t* rgb_out = nullptr;
+  float* conf_out = nullptr;
+  int32_t* count = nullptr;  // [B + 1]; non-null = the list passes run
+  long capacity = 0;
+};
+// bytes of the list's scratch (bit mask, block counts, block offsets) for B views of H x W; 256-byte aligned parts
+size_t points_scratch_bytes(int B, int H, int W);
+// classify (+ scan + scatter when p.count is set); scratch may be null when p.count is
+int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

@@ -1,0 +1,235 @@
+// Point path kernels for gfx950 (md_op_unproject, md_infer_points): depth + pinhole cameras -> a dense world / camera space
+// point map with its validity mask, and the same points as an ordered, compacted cloud. HBM-bound: three launches
+// (classify, scan, scatter). Contraction is off in the whole file (Makefile): every step below is one rounded f32 operation,
+// in the order pipeline.unproject_depth restates in numpy, so the two agree bit for bit.
+//
+// The list keeps the (view, row, column) order without atomics: classify leaves one 64-bit ballot word per wave and step
+// (bit l = lane l's pixel enters the list) and one count per workgroup; scan turns the counts into exclusive offsets and
+// the per-view totals; scatter ranks a pixel by the popcount of the lower bits of its word, the words before it in the
+// workgroup and the workgroup's offset.
+#include <cfloat>
+#include <cmath>
+
+#include "ops.h"
+
+namespace md {
+
+namespace {
+
+constexpr int kThreads = 256;                // 4 waves of 64
+constexpr int kSteps = 16;                   // pixels per thread
+constexpr int kTile = kThreads * kSteps;     // 4096 pixels per workgroup: pixel = tile * 4096 + step * 256 + thread
+constexpr int kWords = kTile / 64;           // 64 ballot words per workgroup: word = step * 4 + wave
+
+struct Camera {
+  float fx, fy, cx, cy;
+  float r[9], t[3];
+};
+
+__device__ __forceinline__ Camera load_camera(const PointsParams& p, int b) {
+  Camera c;
+  if (p.K) {
+    const float* k = p.K + (long)b * 9;
+    c.fx = k[0]; c.fy = k[4]; c.cx = k[2]; c.cy = k[5];
+  } else {
+    c.fx = c.fy = p.focal[b];
+    c.cx = (float)p.W / 2.0f;
+    c.cy = (float)p.H / 2.0f;
+  }
+  if (p.world) {
+    const float* e = p.E + (long)b * 12;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) c.r[3 * i + j] = e[4 * i + j];
+      c.t[i] = e[4 * i + 3];
+    }
+  }
+  return c;
+}
+
+// the arithmetic contract: back-projection, then p_w = R^T (p_c - t)
+__device__ __forceinline__ void unproject(const Camera& c, int world, float off, int v, int u, float d, float* out) {
+  const float rx = (((float)u + off) - c.cx) / c.fx;
+  const float ry = (((float)v + off) - c.cy) / c.fy;
+  float x = rx * d, y = ry * d, z = d;
+  if (world) {
+    const float qx = x - c.t[0], qy = y - c.t[1], qz = z - c.t[2];
+    x = (c.r[0] * qx + c.r[3] * qy) + c.r[6] * qz;
+    y = (c.r[1] * qx + c.r[4] * qy) + c.r[7] * qz;
+    z = (c.r[2] * qx + c.r[5] * qy) + c.r[8] * qz;
+  }
+  out[0] = x; out[1] = y; out[2] = z;
+}
+
+// a neighbour that is not finite or <= 0 is ignored
+__device__ __forceinline__ bool edge_ok(float d, float dn, float rtol) {
+  if (!isfinite(dn) || !(dn > 0.f)) return true;
+  return fabsf(d - dn) <= rtol * fminf(d, dn);
+}
+
+__device__ __forceinline__ bool pixel_valid(const PointsParams& p, const float* __restrict__ dv, const float* __restrict__ cv, int v, int u,
+                                            float d) {
+  if (!isfinite(d) || !(d >= p.dmin) || !(d <= p.dmax)) return false;
+  const long i = (long)v * p.W + u;
+  if (cv && !(cv[i] >= p.conf_min)) return false;
+  if (p.edge_rtol > 0.f) {
+    if (v > 0 && !edge_ok(d, dv[i - p.W], p.edge_rtol)) return false;
+    if (v + 1 < p.H && !edge_ok(d, dv[i + p.W], p.edge_rtol)) return false;
+    if (u > 0 && !edge_ok(d, dv[i - 1], p.edge_rtol)) return false;
+    if (u + 1 < p.W && !edge_ok(d, dv[i + 1], p.edge_rtol)) return false;
+  }
+  return true;
+}
+
+// grid (tiles, B). bits [B][tiles * 64] and counts [B * tiles] are written only when the list is wanted.
+__global__ void __launch_bounds__(kThreads) points_classify_kernel(PointsParams p, unsigned long long* __restrict__ bits,
+                                                                   int* __restrict__ counts) {
+  __shared__ int wave_n[kThreads / 64];
+  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const long hw = (long)p.H * p.W;
+  const float* dv = p.depth + (long)b * hw;
+  const float* cv = p.conf ? p.conf + (long)b * hw : nullptr;
+  const bool dense = p.point_map || p.mask;
+  const bool list = p.count != nullptr;
+  Camera cam;
+  if (p.point_map) cam = load_camera(p, b);
+  int n = 0;
+  for (int s = 0; s < kSteps; ++s) {
+    const long i = (long)tile * kTile + s * kThreads + tid;
+    bool ok = false, in_list = false;
+    if (i < hw) {
+      const int v = (int)(i / p.W), u = (int)(i % p.W);
+      const float d = dv[i];
+      ok = pixel_valid(p, dv, cv, v, u, d);
+      in_list = ok && u % p.stride == 0 && v % p.stride == 0;
+      if (dense) {
+        const long o = (long)b * hw + i;
+        if (p.mask) p.mask[o] = ok ? 1 : 0;
+        if (p.point_map) {
+          float q[3] = {0.f, 0.f, 0.f};
+          if (ok) unproject(cam, p.world, p.off, v, u, d, q);
+          float* dst = p.point_map + o * 3;
+          dst[0] = q[0]; dst[1] = q[1]; dst[2] = q[2];
+        }
+      }
+    }
+    if (list) {
+      const unsigned long long word = __ballot(in_list);
+      if (lane == 0) bits[((long)b * gridDim.x + tile) * kWords + s * (kThreads / 64) + wave] = word;
+      n += __popcll(word);  // the same in every lane of the wave
+    }
+  }
+  if (!list) return;
+  if (lane == 0) wave_n[wave] = n;
+  __syncthreads();
+  if (tid == 0) counts[(long)b * gridDim.x + tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+}
+
+// one workgroup: offsets[i] = sum of counts[0 .. i), offsets[n] = the total; count[b] = points of view b, count[B] = total
+__global__ void __launch_bounds__(kThreads) points_scan_kernel(const int* __restrict__ counts, int n, int tiles, int B,
+                                                               int* __restrict__ offsets, int32_t* __restrict__ count) {
+  __shared__ int part[kThreads];
+  const int tid = threadIdx.x;
+  const int per = (n + kThreads - 1) / kThreads;
+  const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+  int sum = 0;
+  for (int i = lo; i < hi; ++i) sum += counts[i];
+  part[tid] = sum;
+  __syncthreads();
+  for (int d = 1; d < kThreads; d <<= 1) {  // inclusive scan of the 256 chunk sums
+    const int v = tid >= d ? part[tid - d] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int run = part[tid] - sum;
+  for (int i = lo; i < hi; ++i) {
+    offsets[i] = run;
+    run += counts[i];
+  }
+  if (tid == kThreads - 1) offsets[n] = part[tid];
+  __syncthreads();  // the offsets this workgroup wrote are visible to all of it
+  for (int b = tid; b < B; b += kThreads) count[b] = offsets[(b + 1) * tiles] - offsets[b * tiles];
+  if (tid == 0) count[B] = offsets[n];
+}
+
+__global__ void __launch_bounds__(kThreads) points_scatter_kernel(PointsParams p, const unsigned long long* __restrict__ bits,
+                                                                  const int* __restrict__ offsets) {
+  __shared__ int word_off[kWords];
+  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const long blk = (long)b * gridDim.x + tile;
+  const unsigned long long* words = bits + blk * kWords;
+  if (tid < kWords) {  // wave 0: exclusive scan of the 64 word popcounts (word order = pixel order)
+    const int c = __popcll(words[tid]);
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    word_off[tid] = incl - c;
+  }
+  __syncthreads();
+  const long base = offsets[blk];
+  if (base >= p.capacity) return;  // everything of this workgroup lies beyond the capacity
+  const long hw = (long)p.H * p.W;
+  const float* dv = p.depth + (long)b * hw;
+  const Camera cam = load_camera(p, b);
+  for (int s = 0; s < kSteps; ++s) {
+    const int w = s * (kThreads / 64) + wave;
+    const unsigned long long word = words[w];
+    if (!((word >> lane) & 1ull)) continue;
+    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
+    const long idx = base + word_off[w] + below;
+    if (idx >= p.capacity) continue;
+    const long i = (long)tile * kTile + s * kThreads + tid;  // < hw: the bit is only ever set for a pixel of the image
+    const int v = (int)(i / p.W), u = (int)(i % p.W);
+    if (p.xyz) {
+      float q[3];
+      unproject(cam, p.world, p.off, v, u, dv[i], q);
+      float* dst = p.xyz + idx * 3;
+      dst[0] = q[0]; dst[1] = q[1]; dst[2] = q[2];
+    }
+    const long o = (long)b * hw + i;
+    if (p.rgb_out) {
+      const uint8_t* src = p.rgb + o * 3;
+      uint8_t* dst = p.rgb_out + idx * 3;
+      dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+    }
+    if (p.conf_out) p.conf_out[idx] = p.conf[o];
+  }
+}
+
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+inline int tiles_of(int H, int W) { return (int)(((long)H * W + kTile - 1) / kTile); }
+
+}  // namespace
+
+size_t points_scratch_bytes(int B, int H, int W) {
+  const size_t nb = (size_t)B * tiles_of(H, W);
+  return up256(nb * kWords * 8) + up256(nb * 4) + up256((nb + 1) * 4);
+}
+
+int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s) {
+  const bool dense = p.point_map || p.mask, list = p.count != nullptr;
+  if (!dense && !list) return MD_OK;
+  if (list && !scratch) MD_FAIL(MD_ERR_INVALID_ARG, "unproject: the list needs its scratch buffer");
+  const int tiles = tiles_of(p.H, p.W);
+  const size_t nb = (size_t)p.B * tiles;
+  unsigned long long* bits = (unsigned long long*)scratch;
+  int* counts = list ? (int*)((char*)scratch + up256(nb * kWords * 8)) : nullptr;
+  int* offsets = list ? (int*)((char*)counts + up256(nb * 4)) : nullptr;
+  const dim3 grid(tiles, p.B);
+  hipLaunchKernelGGL(points_classify_kernel, grid, dim3(kThreads), 0, s, p, bits, counts);
+  MD_HIP(hipGetLastError());
+  if (!list) return MD_OK;
+  hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kThreads), 0, s, counts, (int)nb, tiles, p.B, offsets, p.count);
+  MD_HIP(hipGetLastError());
+  if (!p.xyz && !p.rgb_out && !p.conf_out) return MD_OK;  // counts only
+  hipLaunchKernelGGL(points_scatter_kernel, grid, dim3(kThreads), 0, s, p, bits, offsets);
+  MD_HIP(hipGetLastError());
+  return MD_OK;
+}
+
+}  // namespace md

@@ -1157,6 +1157,10 @@ int da3_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float
   return da3_infer_eager(m, nchw, B, H, W, MD_MEM_DEVICE, o, MD_MEM_DEVICE, stream);
 }
 
+int da3_infer_ex_direct(md_model_t m, const float* nchw, int B, int H, int W, const Da3Outputs& out, hipStream_t stream) {
+  return da3_infer_eager(m, nchw, B, H, W, MD_MEM_DEVICE, out, MD_MEM_DEVICE, stream);
+}
+
 int da3_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, float* depth, int out_kind,
               hipStream_t stream) {
   Da3Outputs o;

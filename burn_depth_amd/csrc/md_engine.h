@@ -269,6 +269,9 @@ struct md_model_s {
   // ---- md_process_frame: tap tables, staging and scratch of the frame path (md_frame.hip); per model, so per fork ----
   struct FrameState;
   FrameState* frame = nullptr;
+  // ---- md_infer_points: device homes and scratch of the point path (md_points.hip); per model, so per fork ----
+  struct PointsState;
+  PointsState* points = nullptr;
   // geometry shared by create/infer
   int S = 0, win = 0, g = 0, P = 0, NT = 0, SS = 0, kpad = 0;
   int steps0 = 0, stride0 = 0, steps1 = 0, stride1 = 0, pad_hi = 0, pad_mid = 0;
@@ -343,7 +346,9 @@ int model_stage_input(md_model_t m, const float* nchw, size_t elems, int in_kind
 // md_process_frame's pieces: model_infer / da3_infer_ex without the graph layer (the frame call captures its own graph around
 // them), the grow-only pinned staging of a host u8 frame (`bytes` of `rgb` -> the model's device copy *dev), and the frame
 // path's state (md_frame.hip)
-int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, float* focal, float* fovy, hipStream_t stream);
+// (f_px_dev: the caller's focal lengths [B] on the device = md_depth_pro_infer_with_focal's body)
+int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, float* focal, float* fovy, hipStream_t stream,
+                       const float* f_px_dev = nullptr);
 int model_stage_rgb(md_model_t m, const uint8_t* rgb, size_t bytes, hipStream_t stream, const uint8_t** dev);
 void frame_destroy_state(md_model_t m);
 int frame_geometry(md_model_t m, int w, int h, const md_frame_opts* o, int* th, int* tw, int* oh, int* ow);
@@ -351,6 +356,12 @@ int process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_
                   int out_kind, hipStream_t stream);
 // crop (cx, cy, cw, ch) of a [B,h,w] map, restored to ow x oh (no restore at the crop's own size)
 DisplayGeom display_geom(int B, int h, int w, int cx, int cy, int cw, int ch, int ow, int oh);
+// the point path (md_points.hip): the stand-alone operator on caller tensors, the model -> points call and its state
+int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
+                 const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, hipStream_t stream);
+int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                 const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream);
+void points_destroy_state(md_model_t m);
 int pack_weight(const float* src, const PackEntry& e, int prec, hipStream_t s);
 // number of values of w[0..n) that are not exactly representable as an IEEE half (synchronises the stream)
 int count_inexact_f16(const float* w, long n, hipStream_t s, unsigned* out);
@@ -402,6 +413,8 @@ int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
 void da3_destroy_state(md_model_t m);
 long da3_shape_builds(md_model_t m);
 int da3_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, hipStream_t stream);  // device in / out
+// da3_infer_ex without the graph layer, device in / out (md_infer_points captures its own graph around it)
+int da3_infer_ex_direct(md_model_t m, const float* nchw, int B, int H, int W, const Da3Outputs& out, hipStream_t stream);
 // patch size and the current input size (rows, columns; 0 before the first plan) of a Depth-Anything-v3 model
 void da3_frame_info(md_model_t m, int* patch, int* cur_h, int* cur_w);  // input sizes whose tables were built so far (0 for Depth Pro models)
 int da3_on_commit(md_model_t m);  // re-derives the (interpolated) position table from the weights

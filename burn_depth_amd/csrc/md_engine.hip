@@ -690,6 +690,7 @@ int model_destroy(md_model_t m) {
   }
   if (m->da3) da3_destroy_state(m);
   if (m->frame) frame_destroy_state(m);
+  if (m->points) points_destroy_state(m);
   delete m->buf;
   delete m;
   return MD_OK;
@@ -1758,8 +1759,10 @@ int model_infer(md_model_t m, const float* nchw, int B, int H, int W, int in_kin
   return run_with_graph(m, st, key, eligible, body);
 }
 
-int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, float* focal, float* fovy, hipStream_t stream) {
-  return model_infer_eager(m, nchw, B, H, W, MD_MEM_DEVICE, depth, focal, nullptr, fovy, MD_MEM_DEVICE, stream, nullptr, 0, nullptr, 0);
+int model_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, float* focal, float* fovy, hipStream_t stream,
+                       const float* f_px_dev) {
+  return model_infer_eager(m, nchw, B, H, W, MD_MEM_DEVICE, depth, focal, nullptr, fovy, MD_MEM_DEVICE, stream, nullptr, 0, f_px_dev,
+                           MD_MEM_DEVICE);
 }
 
 int model_stage_rgb(md_model_t m, const uint8_t* rgb, size_t bytes, hipStream_t st, const uint8_t** dev) {

@@ -143,6 +143,12 @@ class DepthAnything3(DepthPro):
         _lib.check(self._lib.md_da3_infer(self._h, C.c_void_p(x.data_ptr()), B, H, W, in_kind, C.c_void_p(depth.data_ptr()),
                                           _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
 
+    def infer_points(self, x: torch.Tensor, intrinsics=None, extrinsics=None, focal_px=None, **kw):
+        """`md_infer_points`: depth, confidence and the camera decoder's intrinsics / extrinsics (dual head) as a point cloud in one
+        device call; the caller's cameras replace the model's when given. The mono head has no camera decoder: it needs
+        `intrinsics` or `focal_px` (MdError(MD_ERR_UNSUPPORTED) without). Other keywords as `DepthPro.infer_points`."""
+        return super().infer_points(x, f_px=focal_px, intrinsics=intrinsics, extrinsics=extrinsics, **kw)
+
     def infer_from_rgb(self, rgb: bytes, width: int, height: int):
         from .inference import rgb_to_input_tensor
         return self.infer(rgb_to_input_tensor(rgb, width, height, self.device))

@@ -78,6 +78,73 @@ class FrameResult:
 
 
 @dataclass
+class PointCloud:
+    """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
+    mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
+    which the first min(count[B], capacity) rows are points; count int32 [B+1] (per view, then the total); the depth [B,H,W]."""
+    point_map: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+    xyz: Optional[torch.Tensor] = None
+    rgb: Optional[torch.Tensor] = None
+    conf: Optional[torch.Tensor] = None
+    count: Optional[torch.Tensor] = None
+    depth: Optional[torch.Tensor] = None
+
+    def points(self):
+        """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
+        n = min(int(self.count[-1].item()), int(self.xyz.shape[0]))
+        cut = lambda t: t[:n] if t is not None else None  # noqa: E731
+        return cut(self.xyz), cut(self.rgb), cut(self.conf)
+
+
+def _points_opts(pixel_offset=0.0, depth_min=0.0, depth_max=0.0, conf_min=0.0, edge_rtol=0.0, stride=1, world=False) -> "_lib.MdPointsOpts":
+    return _lib.MdPointsOpts(float(pixel_offset), float(depth_min), float(depth_max), float(conf_min), float(edge_rtol), int(stride),
+                             int(bool(world)))
+
+
+def _points_outputs(dev, B: int, H: int, W: int, dense: bool, compact: bool, capacity: Optional[int], stride: int, want_rgb: bool,
+                    want_conf: bool, want_depth: bool, out: Optional[PointCloud]):
+    """A PointCloud of fresh device tensors (or `out`, to write into again) and its md_points_outputs."""
+    if out is None:
+        stride = max(int(stride), 1)  # a bad stride is the library's to refuse
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        out = PointCloud()
+        if dense:
+            out.point_map, out.mask = f(B, H, W, 3), f(B, H, W, dt=torch.uint8)
+        if compact:
+            cap = int(capacity) if capacity is not None else B * ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+            out.xyz, out.count = f(cap, 3), f(B + 1, dt=torch.int32)
+            out.rgb = f(cap, 3, dt=torch.uint8) if want_rgb else None
+            out.conf = f(cap) if want_conf else None
+        if want_depth:
+            out.depth = f(B, H, W)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    c = _lib.MdPointsOutputs(ptr(out.point_map), ptr(out.mask), ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count),
+                             int(out.xyz.shape[0]) if out.xyz is not None else 0, ptr(out.depth))
+    return out, c
+
+
+def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
+    """md_points_cameras of device fp32 tensors ([B,3,3] / [B,1,3,3], [B,3,4] / [B,1,3,4], [B] or a float). Returns (struct, keep-alive)."""
+    keep = []
+
+    def put(t, n):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(np.asarray(t, dtype=np.float32))
+        if t.numel() == 1 and n == B:
+            t = t.reshape(1).expand(B)
+        t = t.to(device=dev, dtype=torch.float32).contiguous()
+        if t.numel() != n:
+            raise _lib.MdError(_lib.MD_ERR_SHAPE, f"camera tensor of {t.numel()} values, expected {n}")
+        keep.append(t)
+        return t.data_ptr()
+
+    return _lib.MdPointsCameras(put(intrinsics, B * 9), put(extrinsics, B * 12), put(focal_px, B)), keep
+
+
+@dataclass
 class HeadDebug:
     """depth_pro/mod.rs:135-142."""
     conv0: torch.Tensor      # [B, F/2, s, s]
@@ -454,6 +521,31 @@ class DepthPro:
         _lib.check(self._lib.md_process_frame(self._h, C.c_void_p(ptr), B, W, H, in_kind, C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE,
                                               _stream_ptr(self.device.ordinal)))
         return out
+
+    # ---- point path --------------------------------------------------------------------------
+    def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
+                     dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
+                     **opts) -> PointCloud:
+        """`md_infer_points`: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the caller's
+        (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True). rgb: u8
+        [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
+        world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays)."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
+        dev = torch.device("cuda", self.device.ordinal)
+        x = x.to(device=dev, dtype=torch.float32).contiguous()
+        B, _, H, W = (int(v) for v in x.shape)
+        if rgb is not None:
+            rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
+        o = _points_opts(**opts)
+        has_conf = bool(getattr(self.config, "dual_head", False))
+        res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, rgb is not None, has_conf, True, out)
+        cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, f_px)
+        _lib.check(self._lib.md_infer_points(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                             C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), C.byref(o),
+                                             C.byref(outs), _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        del keep
+        return res
 
     # ---- debug taps / timing --------------------------------------------------------------
     def enable_taps(self, enable: bool = True) -> None:

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import Device, _stream_ptr
+from .depth_pro import Device, PointCloud, _points_cameras, _points_opts, _points_outputs, _stream_ptr
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -170,6 +170,26 @@ def conv2d_direct(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[
     _lib.check(_lib.load().md_op_conv2d_direct(dev.handle, _p(x), _p(w), _p(bias), B, Cin, H, W, Cout, k, stride, pad,
                                                int(relu), _p(out), _stream_ptr(dev.ordinal)))
     return out
+
+
+def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None, focal_px=None, conf: Optional[torch.Tensor] = None,
+              rgb: Optional[torch.Tensor] = None, dense: bool = True, compact: bool = True, capacity: Optional[int] = None,
+              out: Optional[PointCloud] = None, **opts) -> PointCloud:
+    """md_op_unproject: depth [B,H,W] (+ conf [B,H,W], + u8 rgb [B,H,W,3]) and pinhole cameras (intrinsics [B,3,3] or focal_px [B];
+    extrinsics [B,3,4] world-to-camera for world=True) -> `PointCloud`. opts: the fields of `md_points_opts`. Bit-identical to
+    `pipeline.unproject_depth`."""
+    depth = _f32c(depth)
+    B, H, W = (int(v) for v in depth.shape)
+    conf = _f32c(conf) if conf is not None else None
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
+    o = _points_opts(**opts)
+    res, outs = _points_outputs(depth.device, B, H, W, dense, compact, capacity, max(o.stride, 1), rgb is not None, conf is not None, False, out)
+    cam, keep = _points_cameras(depth.device, B, intrinsics, extrinsics, focal_px)
+    _lib.check(_lib.load().md_op_unproject(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
+                                           _stream_ptr(dev.ordinal)))
+    del keep
+    return res
 
 
 def fov_to_focal(fovx_deg: float, H: int, W: int) -> Tuple[float, float]:

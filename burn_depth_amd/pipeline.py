@@ -10,6 +10,8 @@
                                               -- example/inference.rs:103-273 (restated exactly, fp32)
 * `prepare_input_frame`, `depth_to_display`   -- the viewer's frame path (crates/bevy_burn_depth/src/lib.rs:16-132): the host
   references of the device frame call `md_process_frame` (`DepthPro.process_frame`)
+* `unproject_depth`, `write_ply` / `read_ply`  -- the point path (no counterpart in the reference): the host reference the
+  device kernels of `md_op_unproject` / `md_infer_points` are bit-identical to, and a binary little-endian PLY writer / reader
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
   stands in (8-bit grayscale, filter 0), `read_gray_png` reads it back for the tests.
 JPEG decoding stays out of scope: images come in as uint8 arrays."""
@@ -254,6 +256,127 @@ def read_gray_png(path: str) -> np.ndarray:
     return rows[:, 1:].copy()
 
 
+# ------------------------------------------------------------------------------------------------------------
+# point path: the host reference of md_op_unproject / md_infer_points (include/mi_depth.h states the op order)
+# ------------------------------------------------------------------------------------------------------------
+@dataclass
+class HostPoints:
+    point_map: np.ndarray            # [B,H,W,3], (0,0,0) at invalid pixels
+    mask: np.ndarray                 # uint8 [B,H,W]
+    xyz: np.ndarray                  # [N,3], order (b, v, u) ascending
+    rgb: Optional[np.ndarray]        # uint8 [N,3]
+    conf: Optional[np.ndarray]       # [N]
+    count: np.ndarray                # int32 [B+1]: per view, then the total
+
+
+def unproject_depth(depth, intrinsics=None, extrinsics=None, focal_px=None, conf=None, rgb=None, *, pixel_offset=0.0,
+                    depth_min=0.0, depth_max=0.0, conf_min=0.0, edge_rtol=0.0, stride=1, world=False,
+                    dtype=np.float32) -> HostPoints:
+    """depth [B,H,W] and pinhole cameras -> point map, validity mask and the ordered list of valid points. Every step is one
+    rounded operation of `dtype`, in the order of the device kernels (kernels/points.hip): with dtype f32 the results are
+    theirs bit for bit; dtype=np.float64 is the same formulas for the geometric tests. intrinsics [B,3,3] or focal_px [B]
+    (K = f, f, W/2, H/2); extrinsics [B,3,4] world-to-camera (camera.rs:248-254), applied inverted when `world`."""
+    T = np.dtype(dtype).type
+    d = np.asarray(depth, dtype=dtype)
+    if d.ndim != 3:
+        raise ValueError(f"expected depth [B,H,W], got {d.shape}")
+    B, H, W = d.shape
+    if stride < 1:
+        raise ValueError("stride must be at least 1")
+    if intrinsics is not None:
+        K = np.asarray(intrinsics, dtype=dtype).reshape(B, 3, 3)
+        fx, fy, cx, cy = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    elif focal_px is not None:
+        f = np.asarray(focal_px, dtype=dtype).reshape(B)
+        fx, fy = f, f
+        cx, cy = np.full(B, T(W) / T(2), dtype), np.full(B, T(H) / T(2), dtype)
+    else:
+        raise ValueError("neither intrinsics nor a focal length")
+    if world and extrinsics is None:
+        raise ValueError("world needs extrinsics")
+    f32i = np.finfo(np.float32)
+    dmin = T(depth_min) if depth_min > 0 else T(f32i.tiny)
+    dmax = T(depth_max) if depth_max > 0 else T(f32i.max)
+    with np.errstate(all="ignore"):
+        valid = np.isfinite(d) & (d >= dmin) & (d <= dmax)
+        cf = None
+        if conf is not None:
+            cf = np.asarray(conf, dtype=dtype).reshape(B, H, W)
+            valid &= cf >= T(conf_min)
+        if edge_rtol > 0:
+            rt = T(edge_rtol)
+
+            def ok(dc, dn):  # a neighbour that is not finite or <= 0 is ignored
+                return ~(np.isfinite(dn) & (dn > 0)) | (np.abs(dc - dn) <= rt * np.minimum(dc, dn))
+
+            valid[:, 1:, :] &= ok(d[:, 1:, :], d[:, :-1, :])
+            valid[:, :-1, :] &= ok(d[:, :-1, :], d[:, 1:, :])
+            valid[:, :, 1:] &= ok(d[:, :, 1:], d[:, :, :-1])
+            valid[:, :, :-1] &= ok(d[:, :, :-1], d[:, :, 1:])
+        off = T(pixel_offset)
+        u = np.arange(W, dtype=dtype)[None, None, :]
+        v = np.arange(H, dtype=dtype)[None, :, None]
+        b3 = lambda a: a.astype(dtype)[:, None, None]  # noqa: E731
+        rx = ((u + off) - b3(cx)) / b3(fx)
+        ry = ((v + off) - b3(cy)) / b3(fy)
+        x, y, z = rx * d, ry * d, d
+        if world:
+            E = np.asarray(extrinsics, dtype=dtype).reshape(B, 3, 4)
+            R = lambda i, j: E[:, i, j][:, None, None]  # noqa: E731
+            qx, qy, qz = x - R(0, 3), y - R(1, 3), z - R(2, 3)
+            x = (R(0, 0) * qx + R(1, 0) * qy) + R(2, 0) * qz
+            y = (R(0, 1) * qx + R(1, 1) * qy) + R(2, 1) * qz
+            z = (R(0, 2) * qx + R(1, 2) * qy) + R(2, 2) * qz
+        pm = np.stack([np.broadcast_to(c, d.shape) for c in (x, y, z)], axis=-1).astype(dtype)
+    pm = np.where(valid[..., None], pm, T(0)).astype(dtype)
+    sel = valid.copy()
+    if stride > 1:
+        keep = np.zeros((H, W), bool)
+        keep[::stride, ::stride] = True
+        sel &= keep[None]
+    count = np.concatenate([sel.reshape(B, -1).sum(1), [sel.sum()]]).astype(np.int32)
+    return HostPoints(pm, valid.astype(np.uint8), pm[sel], None if rgb is None else np.asarray(rgb, np.uint8).reshape(B, H, W, 3)[sel],
+                      None if cf is None else cf[sel], count)
+
+
+def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None) -> None:
+    """Binary little-endian PLY: `x y z` float, optional `red green blue` uchar."""
+    xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if rgb is not None:
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        if len(rgb) != len(xyz):
+            raise ValueError(f"{len(rgb)} colours for {len(xyz)} points")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    rec = np.empty(len(xyz), dtype=np.dtype(fields))
+    for i, n in enumerate("xyz"):
+        rec[n] = xyz[:, i]
+    if rgb is not None:
+        for i, n in enumerate(("red", "green", "blue")):
+            rec[n] = rgb[:, i]
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(xyz)}"]
+    head += [f"property {'float' if t == '<f4' else 'uchar'} {n}" for n, t in fields] + ["end_header"]
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii") + rec.tobytes())
+
+
+def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """Reader for the files `write_ply` produces -> (xyz f32 [N,3], rgb uint8 [N,3] or None)."""
+    b = open(path, "rb").read()
+    end = b.index(b"end_header\n") + len(b"end_header\n")
+    lines = b[:end].decode("ascii").split("\n")
+    assert lines[0] == "ply" and lines[1] == "format binary_little_endian 1.0"
+    n = int(next(l for l in lines if l.startswith("element vertex")).split()[2])
+    fields = [(l.split()[2], "<f4" if l.split()[1] == "float" else "u1") for l in lines if l.startswith("property")]
+    rec = np.frombuffer(b, dtype=np.dtype(fields), count=n, offset=end)
+    xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float32)
+    rgb = np.stack([rec["red"], rec["green"], rec["blue"]], axis=-1) if "red" in rec.dtype.names else None
+    return xyz, rgb
+
+
 def save_depth_map(depth: np.ndarray, path: str, crop: Optional[ImageCropRegion] = None,
                    target_dims: Optional[Tuple[int, int]] = None) -> np.ndarray:
     px = depth_to_u8(depth, crop, target_dims)
@@ -302,6 +425,11 @@ class AnyDepthModel:
         min-max normalise (normalize_relative_depth) and build the display at the model's resolution -- RGBA f32 for the
         viewer's texture, or "u8" grey. rgb: uint8 [H,W,3] / [B,H,W,3] (numpy or torch). Returns a `FrameResult`."""
         return self.model.process_frame(rgb, target=0, restore=False, normalize=normalize_relative_depth, fmt=fmt)
+
+    def infer_points(self, x, **kw):
+        """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
+        Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`."""
+        return self.model.infer_points(x, **kw)
 
     def preferred_input_resolution(self) -> Optional[int]:
         return None if self.kind == DepthModelKind.DEPTH_PRO else self.model.img_size()

@@ -264,6 +264,65 @@ int md_frame_geometry(md_model_t m, int w, int h, const md_frame_opts* o, int* t
 int md_process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_kind, const md_frame_opts* o,
                      const md_frame_outputs* out, int out_kind, void* stream);
 
+/* ---- point path: depth and pinhole cameras to a point cloud on the device ----------------------------------------
+ * Pixel (row v, column u) of view b with depth d, in f32, one rounded operation per step and no fused multiply-add
+ * (pipeline.unproject_depth restates it in numpy bit for bit):
+ *   rx = ((u + off) - cx) / fx,  ry = ((v + off) - cy) / fy,  p_c = (rx d, ry d, d)     fx = K[0][0], fy = K[1][1],
+ *                                                                                       cx = K[0][2], cy = K[1][2]; skew ignored
+ *   world = 1, E = [R | t] world-to-camera (camera.rs:248-254): q = p_c - t, p_w = R^T q, each coordinate
+ *   (R0j qx + R1j qy) + R2j qz.
+ * A pixel is valid when d is finite and depth_min <= d <= depth_max; a confidence map, when there is one, holds
+ * conf >= conf_min; and, with edge_rtol > 0, |d - dn| <= edge_rtol * min(d, dn) for each of the 4 neighbours inside the
+ * image whose depth dn is finite and > 0. */
+typedef struct md_points_opts {
+  float pixel_offset;         /* 0.0 = integer grid (goes with cx = W/2, cy = H/2) | 0.5 = pixel centres; any finite value */
+  float depth_min, depth_max; /* 0 = the default of that bound: the smallest positive normal f32 / FLT_MAX (d <= 0 is never valid) */
+  float conf_min;             /* used only when there is a confidence map */
+  float edge_rtol;            /* 0 = off */
+  int stride;                 /* >= 1: only pixels with u % stride == 0 and v % stride == 0 enter the compacted list */
+  int world;                  /* 1: apply the inverse of `extrinsics` */
+} md_points_opts;
+typedef struct md_points_cameras {
+  const float* intrinsics; /* [B,3,3] */
+  const float* extrinsics; /* [B,3,4] world-to-camera; required when world = 1 (md_infer_points: unless the model predicts them) */
+  const float* focal_px;   /* [B]; alternative to intrinsics: K = (f, f, W/2, H/2) */
+} md_points_cameras;
+typedef struct md_points_outputs {
+  float* point_map;  /* dense f32 [B,H,W,3], (0,0,0) at invalid pixels; NULL = skip */
+  uint8_t* mask;     /* dense u8 [B,H,W], 1 = valid; NULL = skip */
+  float* xyz;        /* compacted f32 [capacity,3], order (b, v, u) ascending; needs count */
+  uint8_t* rgb;      /* u8 [capacity,3] gathered from the rgb input; needs count */
+  float* conf;       /* f32 [capacity] gathered from the confidence map; needs count */
+  int32_t* count;    /* [B+1]: count[b] = points of view b, count[B] = their total (also when it exceeds capacity: then
+                        only the first `capacity` points are written) */
+  int64_t capacity;  /* points the compacted outputs hold */
+  float* depth;      /* md_infer_points only: the depth that was unprojected, [B,H,W]; NULL = skip */
+} md_points_outputs;
+
+/* pixel_offset 0, depth bounds 0 (defaults), conf_min 0, edge_rtol 0, stride 1, world 0 */
+void md_points_opts_default(md_points_opts* o);
+/* The stand-alone operator on caller tensors: every pointer (cameras included) is a device pointer. conf_dev / rgb_dev may
+ * be NULL. Errors, before any launch: o / out / cam NULL, stride < 1, capacity < 0, xyz / rgb / conf without count, an rgb
+ * output without rgb_dev, a conf output without conf_dev, pixel_offset / edge_rtol / conf_min / a depth bound not finite or
+ * negative (or depth_max < depth_min), world = 1 without extrinsics, neither intrinsics nor focal_px -> MD_ERR_INVALID_ARG;
+ * B, H, W <= 0 or B*H*W >= 2^31 -> MD_ERR_SHAPE. */
+int md_op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
+                    const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, void* stream);
+/* Model -> points in one call: the model's infer body, then the operator's kernels on its results, on the caller's stream.
+ * nchw, rgb ([B,H,W,3] u8 or NULL) and the pointers of cam are of in_kind, every output of out_kind. cam NULL (or a NULL
+ * field) = the model's own:
+ *   Depth Pro: depth + the predicted focal length; cam->focal_px = the known-focal call (the FOV network does not run);
+ *     no confidence; world = 1 needs cam->extrinsics.
+ *   Depth-Anything-v3 dual head (`small`): depth, depth_confidence and the camera decoder's intrinsics / extrinsics.
+ *   Depth-Anything-v3 mono head (`metric_large`): cam->intrinsics or cam->focal_px is required (MD_ERR_UNSUPPORTED
+ *     without), no confidence (conf_min is ignored).
+ * With md_model_enable_graph(m, 1), device inputs and outputs replay one captured graph per (stream, shape, options,
+ * pointers). No host synchronisation inside the call except for host inputs / outputs. Errors as md_op_unproject's, plus
+ * nchw NULL / an unknown memory kind -> MD_ERR_INVALID_ARG and B > max_batch -> MD_ERR_SHAPE. */
+int md_infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                    const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, int out_kind,
+                    void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

@@ -9,6 +9,11 @@
 `md_process_frame`; the PNG is the same as the default path's up to the resize's rounding (bit-identical when the image
 needs no resize).
 
+`--ply OUT.ply`: also writes the depth as a coloured point cloud (binary little-endian PLY), back-projected on the device in the
+same call as the inference (`md_infer_points`): Depth Pro with its predicted (or `--focal-px`) focal length in camera space,
+Depth-Anything-v3 `small` with its predicted intrinsics / extrinsics in world space. `--conf-min`, `--edge-rtol`, `--stride`
+filter the cloud (`md_points_opts`).
+
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
 restored to the original size, min-max normalised and written as an 8-bit PNG (example/inference.rs:103-199)."""
@@ -30,6 +35,10 @@ def main(argv=None) -> int:
     ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--focal-px", type=float, default=None, help="known focal length in pixels of the image (Depth Pro only)")
     ap.add_argument("--on-device", action="store_true", help="prepare, infer and build the PNG's pixels in one device call (md_process_frame)")
+    ap.add_argument("--ply", default="", help="write the point cloud of the prepared image to this .ply (md_infer_points)")
+    ap.add_argument("--conf-min", type=float, default=0.0, help="--ply: keep pixels whose confidence is at least this (Depth-Anything-v3 small)")
+    ap.add_argument("--edge-rtol", type=float, default=0.0, help="--ply: drop pixels whose depth differs from a neighbour's by more than this ratio (0 = off)")
+    ap.add_argument("--stride", type=int, default=1, help="--ply: keep every stride-th row and column")
     a = ap.parse_args(argv)
     if a.focal_px is not None and a.model != "depth-pro":
         print(f"--focal-px applies to Depth Pro only, not to `{a.model}`", file=sys.stderr)
@@ -56,6 +65,24 @@ def main(argv=None) -> int:
     if a.on_device and a.focal_px is not None:
         print("--on-device takes no --focal-px (the frame call predicts the focal length)", file=sys.stderr)
         return 2
+    if a.ply:
+        import torch
+        from burn_depth_amd import _lib
+        from burn_depth_amd.inference import rgb_to_input_tensor
+        prep = model.prepare_input_image(rgb)
+        x = rgb_to_input_tensor(prep.rgb.tobytes(), prep.width, prep.height, model.model.device)
+        try:
+            pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
+                                    dense=False, conf_min=a.conf_min, edge_rtol=a.edge_rtol, stride=a.stride,
+                                    world=bool(getattr(model.model.config, "dual_head", False)))
+        except _lib.MdError as e:
+            print(str(e), file=sys.stderr)
+            return 1
+        xyz, col, _ = pc.points()
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy())
+        print(f"Model `{kind.value}` wrote {xyz.shape[0]} points to {a.ply}")
+        if not a.output:
+            return 0
     oh, ow = rgb.shape[:2]
     path = a.output or os.path.join(os.path.dirname(os.path.abspath(a.image)), "depth.png")
     if a.on_device:
