@@ -170,6 +170,12 @@ SYMBOLS = {
     "md_op_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_deconv2x2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_conv2d_direct": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "md_op_qkv_norm_rope": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _P, _P, _P]),
+    "md_op_qk_norm_rope": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _I, _P, _P]),
+    "md_op_hook_cat_ln": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P, C.c_float, _I, _P, _P, _P]),
+    "md_op_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "md_op_set_token0": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
+    "md_op_border_bias_fix": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "md_op_fov_to_focal": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_op_focal_to_fov": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_bench_gemm": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F]),

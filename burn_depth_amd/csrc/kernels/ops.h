@@ -162,6 +162,8 @@ int launch_pack_fp8_rows(const float* w, int N, int K, int Kp, void* out, float*
 // ---- Depth-Anything-v3 `small` backbone extras (burn_dino, restated -- see oracle/da3_ref.py) ----
 // Per-head affine LayerNorm(64) of q and k followed by the 2-D rotary embedding, in place on qk [rows, 2D] T.
 // rope_cos/rope_sin: [max_pos + 1][16] tables (angle = pos * base^(-f/16)). global_pos: every patch at (1,1).
+// The q rows arrive scaled by q_scale (the QKV epilogue's) and leave scaled by it; their LayerNorm runs with eps * q_scale^2, which
+// is LN(q; eps) of the unscaled projection. Rows t >= n_tokens are left alone.
 int launch_qk_norm_rope(void* qk, long rows, int S, int n_tokens, int D, int heads, int pw, const float* q_gamma,
                         const float* q_beta, const float* k_gamma, const float* k_beta, float eps, const float* rope_cos,
                         const float* rope_sin, int global_pos, float q_scale, int prec, hipStream_t s);

@@ -1112,7 +1112,10 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(T* __restrict__ qk, l
     const float v = ld1p<T>(p, D);
     const float mean = wave_sum(v) * (1.0f / 64.0f);
     const float c = v - mean;
-    const float rstd = 1.0f / sqrtf(wave_sum(c * c) * (1.0f / 64.0f) + eps);
+    // q rows arrive scaled by q_scale (the QKV epilogue's): their variance is q_scale^2 times the projection's, so eps scales with it --
+    // LN(s y; s^2 eps) = LN(y; eps). With the plain eps the q rows were normalised with eps / q_scale^2 (1.5e-4 / var relative).
+    const float eps_w = which ? eps : eps * q_scale * q_scale;
+    const float rstd = 1.0f / sqrtf(wave_sum(c * c) * (1.0f / 64.0f) + eps_w);
     const float y = c * rstd * (which ? kg[lane] : qg[lane]) + (which ? kb[lane] : qb[lane]);
     int py = 0, px = 0;
     if (t > 0) {

@@ -802,6 +802,174 @@ int md_op_conv2d_direct(md_device_t dev, const float* x_dev, const float* w_dev,
   return MD_OK;
 }
 
+// ---- the Depth-Anything-v3 token kernels alone ----
+namespace {
+bool token_op_prec(int precision) {
+  return precision == MD_PREC_BF16 || precision == MD_PREC_F32 || precision == MD_PREC_F16 || precision == MD_PREC_F16X2;
+}
+struct RopeDev {  // the model's tables of one grid, uploaded for one call
+  DevBuf cos, sin;
+  int build(int n_tokens, int pw, float base) {
+    std::vector<float> rc, rs;
+    da3_rope_tables((n_tokens - 1) / pw, pw, base, &rc, &rs);
+    MD_TRY(cos.alloc(rc.size() * 4));
+    MD_TRY(sin.alloc(rs.size() * 4));
+    MD_HIP(hipMemcpy(cos.p, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    MD_HIP(hipMemcpy(sin.p, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+    return MD_OK;
+  }
+};
+int check_token_grid(const char* op, int T, int S, int n_tokens, int D, int pw) {
+  if (T <= 0 || n_tokens <= 0 || S < n_tokens || D <= 0 || D % 64 != 0) MD_FAIL(MD_ERR_SHAPE, "%s: T=%d S=%d n_tokens=%d D=%d", op, T, S, n_tokens, D);
+  if (pw <= 0 || (n_tokens - 1) % pw != 0) MD_FAIL(MD_ERR_SHAPE, "%s: %d patches do not fill rows of %d", op, n_tokens - 1, pw);
+  return MD_OK;
+}
+}  // namespace
+
+int md_op_qkv_norm_rope(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* q_gamma,
+                        const float* q_beta, const float* k_gamma, const float* k_beta, int T, int S, int n_tokens, int K, int D, int pw,
+                        int global_pos, float rope_frequency, float eps, int precision, int tile, int form, float* qk_out, float* vt_out,
+                        void* stream) {
+  if (!dev || !x_dev || !w_dev || !bias_dev || !q_gamma || !q_beta || !k_gamma || !k_beta || !qk_out || !vt_out)
+    MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (form != 0 && form != 1) MD_FAIL(MD_ERR_INVALID_ARG, "form = %d (0: GEMM + kernel, 1: fused epilogue)", form);
+  MD_TRY(check_token_grid("qkv_norm_rope", T, S, n_tokens, D, pw));
+  if (K <= 0 || K % ke_of(precision) != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "K=%d must be a multiple of %d", K, ke_of(precision));
+  // no k-split: the fused epilogue never runs it (pick_ksplit), so the plain GEMM of form 0 keeps the same summation order and the
+  // V tiles of the two forms can be compared bit for bit
+  const KsplitScope ksplit(0);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const bool split = precision == MD_PREC_F16X2;
+  const int heads = D / 64, kpad = (S + 63) / 64 * 64, N = 3 * D;
+  const long rows = (long)T * S;
+  const size_t es = esz_of(precision) * (split ? 2 : 1), vt_elems = (size_t)T * heads * 64 * kpad;
+  if (vt_elems >= ((size_t)1 << 31) || rows * 2 * D >= (1L << 31)) MD_FAIL(MD_ERR_UNSUPPORTED, "qkv_norm_rope: tensors of this size are not a test");
+  DevBuf xa, wa, qk, vT;
+  RopeDev rope;
+  MD_TRY(xa.alloc((size_t)rows * K * es));
+  MD_TRY(wa.alloc((size_t)N * K * esz_of(precision) * (split ? 3 : 1)));
+  MD_TRY(qk.alloc(((size_t)rows + 64) * 2 * D * es));
+  MD_TRY(vT.alloc(vt_elems * es));
+  MD_TRY(rope.build(n_tokens, pw, rope_frequency));
+  int terms = 1;
+  if (split) {  // x rows [hi | lo], w rows [W | W] or [Wh | Wh | Wl] (md_op_linear_tile)
+    MD_TRY(split_terms_of(w_dev, (long)N * K, st, &terms));
+    MD_TRY(launch_f32_to_rows(x_dev, rows * K, xa.p, precision, st, K));
+    PackEntry e;
+    e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; e.kp = K; e.terms = terms; e.dst = wa.p;
+    MD_TRY(pack_weight(w_dev, e, precision, st));
+  } else {
+    MD_TRY(launch_f32_to_rows(x_dev, rows * K, xa.p, precision, st));
+    MD_TRY(launch_f32_to_rows(w_dev, (long)N * K, wa.p, precision, st));
+  }
+  GemmParams p;
+  p.N = N; p.K = K * terms; p.ngroups = 1; p.g_rows[0] = (int)rows; p.W[0] = wa.p; p.A = xa.p; p.lda = split ? 2 * K : K;
+  p.a_wrap = terms == 3 ? 2 * K / ke_of(precision) : 0;
+  p.bias[0] = bias_dev;
+  p.v_plane = split ? (long)vt_elems : 0;
+  p.epi = EPI_QKV; p.out = qk.p; p.vT = vT.p; p.seq_stride = S; p.embed = D; p.heads = heads; p.kpad = kpad; p.qscale = attn_qscale(precision);
+  if (form == 1) {
+    p.qkn_g[0] = q_gamma; p.qkn_b[0] = q_beta; p.qkn_g[1] = k_gamma; p.qkn_b[1] = k_beta;
+    p.qkn_eps = eps; p.rope_cos = (const float*)rope.cos.p; p.rope_sin = (const float*)rope.sin.p;
+    p.rope_pw = pw; p.rope_global = global_pos ? 1 : 0; p.rope_ntok = n_tokens;
+  } else if (tile != TILE_AUTO && tile != TILE_64x64 && tile != TILE_128x64) {
+    MD_FAIL(MD_ERR_UNSUPPORTED, "qkv_norm_rope: tile %d (the 64-column tiles or auto)", tile);
+  }
+  MD_TRY(launch_gemm(p, A_DENSE, precision, tile, st));
+  if (form == 0)
+    MD_TRY(launch_qk_norm_rope(qk.p, rows, S, n_tokens, D, heads, pw, q_gamma, q_beta, k_gamma, k_beta, eps, (const float*)rope.cos.p,
+                               (const float*)rope.sin.p, global_pos ? 1 : 0, attn_qscale(precision), precision, st));
+  // q | k rows: split-half [q_hi | q_lo | k_hi | k_lo] reads as 2 * rows rows of [hi: D | lo: D]
+  MD_TRY(launch_rows_to_f32(qk.p, rows * 2 * D, qk_out, precision, st, D));
+  MD_TRY(launch_rows_to_f32(vT.p, (long)vt_elems, vt_out, precision, st, (int)vt_elems));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_qk_norm_rope(md_device_t dev, const float* qk_in, const float* q_gamma, const float* q_beta, const float* k_gamma,
+                       const float* k_beta, int T, int S, int n_tokens, int D, int pw, int global_pos, float rope_frequency, float eps,
+                       int precision, float* qk_out, void* stream) {
+  if (!dev || !qk_in || !q_gamma || !q_beta || !k_gamma || !k_beta || !qk_out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  MD_TRY(check_token_grid("qk_norm_rope", T, S, n_tokens, D, pw));
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const long rows = (long)T * S;
+  DevBuf qk;
+  RopeDev rope;
+  MD_TRY(qk.alloc((size_t)rows * 2 * D * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
+  MD_TRY(rope.build(n_tokens, pw, rope_frequency));
+  MD_TRY(launch_f32_to_rows(qk_in, rows * 2 * D, qk.p, precision, st, D));
+  MD_TRY(launch_qk_norm_rope(qk.p, rows, S, n_tokens, D, D / 64, pw, q_gamma, q_beta, k_gamma, k_beta, eps, (const float*)rope.cos.p,
+                             (const float*)rope.sin.p, global_pos ? 1 : 0, attn_qscale(precision), precision, st));
+  MD_TRY(launch_rows_to_f32(qk.p, rows * 2 * D, qk_out, precision, st, D));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_hook_cat_ln(md_device_t dev, const float* x_local, const float* x, int T, int S, int n_tokens, int D, const float* norm_g,
+                      const float* norm_b, float eps_final, const float* head_g, const float* head_b, float eps_head, int precision,
+                      float* out, float* cam_out, void* stream) {
+  if (!dev || !x_local || !x || !norm_g || !norm_b || !head_g || !head_b || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (T <= 0 || n_tokens <= 0 || S < n_tokens || D <= 0) MD_FAIL(MD_ERR_SHAPE, "hook_cat_ln: T=%d S=%d n_tokens=%d D=%d", T, S, n_tokens, D);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const long rows = (long)T * S;
+  DevBuf ob;
+  MD_TRY(ob.alloc((size_t)rows * 2 * D * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
+  MD_TRY(launch_f32_to_rows(out, rows * 2 * D, ob.p, precision, st, 2 * D));
+  MD_TRY(launch_hook_cat_ln(x_local, x, rows, S, n_tokens, D, norm_g, norm_b, eps_final, head_g, head_b, eps_head, ob.p, cam_out, precision, st));
+  MD_TRY(launch_rows_to_f32(ob.p, rows * 2 * D, out, precision, st, 2 * D));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_patchify(md_device_t dev, const float* x_dev, int B, int H, int W, int ps, int Kp, int precision, float* out, float* cls_x,
+                   int S, int n_tokens, int D, const float* cls, const float* pos0, void* stream) {
+  if (!dev || !x_dev || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (B <= 0 || H <= 0 || W <= 0 || ps <= 0 || H % ps || W % ps || Kp < 3 * ps * ps) MD_FAIL(MD_ERR_SHAPE, "patchify: %dx%d / patch %d / K %d", H, W, ps, Kp);
+  if (cls_x && n_tokens != 1 + (H / ps) * (W / ps)) MD_FAIL(MD_ERR_SHAPE, "patchify: n_tokens = %d for a %dx%d grid", n_tokens, H / ps, W / ps);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const long count = (long)B * (H / ps) * (W / ps) * Kp;
+  DevBuf ob;
+  MD_TRY(ob.alloc((size_t)count * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
+  MD_TRY(launch_patchify(x_dev, B, H, W, ps, Kp, ob.p, precision, st, cls_x, S, n_tokens, D, cls, pos0));
+  MD_TRY(launch_rows_to_f32(ob.p, count, out, precision, st, Kp));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_set_token0(md_device_t dev, float* x, int nseq, int S, int D, const float* src, int src_stride, void* stream) {
+  if (!dev || !x || !src) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (nseq <= 0 || S <= 0 || D <= 0 || src_stride < 0) MD_FAIL(MD_ERR_SHAPE, "set_token0: nseq=%d S=%d D=%d stride=%d", nseq, S, D, src_stride);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_set_token0(x, nseq, S, D, src, st, src_stride));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int C, int ld, const float* bias9, int precision, void* stream) {
+  if (!dev || !map || !bias9) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (B <= 0 || H < 2 || W < 2 || C <= 0 || ld < C) MD_FAIL(MD_ERR_SHAPE, "border_bias_fix: [%d,%d,%d] C=%d ld=%d", B, H, W, C, ld);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const long count = (long)B * H * W * ld;
+  DevBuf mb;
+  MD_TRY(mb.alloc((size_t)count * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
+  MD_TRY(launch_f32_to_rows(map, count, mb.p, precision, st, ld));
+  MD_TRY(launch_border_bias_fix(mb.p, B, H, W, C, ld, bias9, precision, st));
+  MD_TRY(launch_rows_to_f32(mb.p, count, map, precision, st, ld));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad) {
   if (H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid image size");
   fov_scalar_host(fovx_deg, H, W, focal_px, fovy_rad);

@@ -133,6 +133,21 @@ static std::vector<float> build_pos_table_nhwc(int C, int h, int w, int image_w,
   return t;
 }
 
+// 2-D RoPE tables: angle(pos, f) = pos * base^(-2f/32), f < 16 (fp32 like the oracle); positions 0 .. max(ph, pw) + 1
+void da3_rope_tables(int ph, int pw, float base, std::vector<float>* cos_out, std::vector<float>* sin_out) {
+  const int npos = std::max(ph, pw) + 2;
+  std::vector<float>&rc = *cos_out, &rs = *sin_out;
+  rc.assign((size_t)npos * 16, 0.f);
+  rs.assign((size_t)npos * 16, 0.f);
+  for (int pz = 0; pz < npos; ++pz)
+    for (int f = 0; f < 16; ++f) {
+      const float inv = 1.0f / powf(base, (float)(2 * f) / 32.0f);
+      const float ang = (float)pz * inv;
+      rc[(size_t)pz * 16 + f] = cosf(ang);
+      rs[(size_t)pz * 16 + f] = sinf(ang);
+    }
+}
+
 // DINOv2 `interpolate_pos_encoding`: bicubic (A = -0.75, align_corners = False), scale factor
 // (grid + 0.1) / native_grid per axis, source index = (dst + 0.5) / scale - 0.5, border-clamped taps.
 // burn_dino's version is not visible (parity unpinned); this restates the public DINOv2 code path
@@ -351,16 +366,8 @@ static int da3_build_tables(md_model_s* m, md_model_s::Da3State::ShapeTables& t)
     for (auto& x : ta) x = x + x;
     MD_HIP(hipMalloc((void**)&t.pos_aux, ta.size() * 4));
     MD_HIP(hipMemcpy(t.pos_aux, ta.data(), ta.size() * 4, hipMemcpyHostToDevice));
-    // 2-D RoPE tables: angle(pos, f) = pos * base^(-2f/32), f < 16 (fp32 like the oracle)
-    const int npos = std::max(d->ph, d->pw) + 2;
-    std::vector<float> rc((size_t)npos * 16), rs((size_t)npos * 16);
-    for (int pz = 0; pz < npos; ++pz)
-      for (int f = 0; f < 16; ++f) {
-        const float inv = 1.0f / powf(c.rope_frequency, (float)(2 * f) / 32.0f);
-        const float ang = (float)pz * inv;
-        rc[(size_t)pz * 16 + f] = cosf(ang);
-        rs[(size_t)pz * 16 + f] = sinf(ang);
-      }
+    std::vector<float> rc, rs;
+    da3_rope_tables(d->ph, d->pw, c.rope_frequency, &rc, &rs);
     MD_HIP(hipMalloc((void**)&t.rope_cos, rc.size() * 4));
     MD_HIP(hipMalloc((void**)&t.rope_sin, rs.size() * 4));
     MD_HIP(hipMemcpy(t.rope_cos, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));

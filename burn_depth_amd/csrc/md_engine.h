@@ -412,6 +412,9 @@ int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
                  hipStream_t stream);
 void da3_destroy_state(md_model_t m);
 long da3_shape_builds(md_model_t m);
+// The 2-D RoPE tables of a ph x pw patch grid: [max(ph, pw) + 2][16] cos and sin of angle(pos, f) = pos * base^(-2f/32), the angle
+// formed in fp32 like the oracle. One function for the model (md_da3.hip) and the stand-alone operators (md_api.cpp).
+void da3_rope_tables(int ph, int pw, float base, std::vector<float>* cos_out, std::vector<float>* sin_out);
 int da3_infer_direct(md_model_t m, const float* nchw, int B, int H, int W, float* depth, hipStream_t stream);  // device in / out
 // da3_infer_ex without the graph layer, device in / out (md_infer_points captures its own graph around it)
 int da3_infer_ex_direct(md_model_t m, const float* nchw, int B, int H, int W, const Da3Outputs& out, hipStream_t stream);

@@ -172,6 +172,89 @@ def conv2d_direct(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[
     return out
 
 
+def qkv_norm_rope(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, q_gamma: torch.Tensor, q_beta: torch.Tensor,
+                  k_gamma: torch.Tensor, k_beta: torch.Tensor, n_tokens: int, S: int, pw: int, global_pos: bool = False,
+                  rope_frequency: float = 100.0, eps: float = 1e-5, precision: int = 0, tile: int = _lib.TILE_AUTO,
+                  form: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """md_op_qkv_norm_rope: x [T*S, K], w [3D, K] -> (q' [T*S, D], k' [T*S, D], V [T, S, D]); form 0 = QKV GEMM + the stand-alone
+    q/k-norm + RoPE kernel, form 1 = the GEMM's fused epilogue. V is read back from the V^T layout the epilogue writes."""
+    x, w = _f32c(x), _f32c(w)
+    rows, K = x.shape
+    D = w.shape[0] // 3
+    T, heads, kpad = rows // S, D // 64, (S + 63) // 64 * 64
+    assert rows == T * S and w.shape == (3 * D, K)
+    qk = torch.empty((rows, 2 * D), dtype=torch.float32, device=x.device)
+    vt = torch.empty((T, heads, 64, kpad), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().md_op_qkv_norm_rope(dev.handle, _p(x), _p(w), _p(_f32c(bias)), _p(_f32c(q_gamma)), _p(_f32c(q_beta)),
+                                               _p(_f32c(k_gamma)), _p(_f32c(k_beta)), T, S, n_tokens, K, D, pw, int(global_pos),
+                                               C.c_float(rope_frequency), C.c_float(eps), precision, tile, form, _p(qk), _p(vt),
+                                               _stream_ptr(dev.ordinal)))
+    v = vt[..., :S].permute(0, 3, 1, 2).reshape(T, S, D).contiguous()
+    return qk[:, :D].contiguous(), qk[:, D:].contiguous(), v
+
+
+def qk_norm_rope(dev: Device, qk: torch.Tensor, q_gamma: torch.Tensor, q_beta: torch.Tensor, k_gamma: torch.Tensor,
+                 k_beta: torch.Tensor, n_tokens: int, S: int, pw: int, global_pos: bool = False, rope_frequency: float = 100.0,
+                 eps: float = 1e-5, precision: int = 0) -> torch.Tensor:
+    """md_op_qk_norm_rope: the stand-alone kernel on rows qk [T*S, 2D] = q | k (q pre-scaled by the mode's softmax scale)."""
+    qk = _f32c(qk)
+    rows, D2 = qk.shape
+    out = torch.empty_like(qk)
+    _lib.check(_lib.load().md_op_qk_norm_rope(dev.handle, _p(qk), _p(_f32c(q_gamma)), _p(_f32c(q_beta)), _p(_f32c(k_gamma)),
+                                              _p(_f32c(k_beta)), rows // S, S, n_tokens, D2 // 2, pw, int(global_pos),
+                                              C.c_float(rope_frequency), C.c_float(eps), precision, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def hook_cat_ln(dev: Device, x_local: torch.Tensor, x: torch.Tensor, n_tokens: int, S: int, norm_g: torch.Tensor, norm_b: torch.Tensor,
+                eps_final: float, head_g: torch.Tensor, head_b: torch.Tensor, eps_head: float, precision: int, out: torch.Tensor,
+                with_cam: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """md_op_hook_cat_ln: x_local, x [T*S, D] -> (hook [T*S, 2D], camera feature [T, 2D] or None). `out` holds the rows the kernel
+    must leave alone (t >= n_tokens); a copy of it is updated and returned."""
+    x_local, x, out = _f32c(x_local), _f32c(x), _f32c(out).clone()
+    rows, D = x.shape
+    T = rows // S
+    cam = torch.zeros((T, 2 * D), dtype=torch.float32, device=x.device) if with_cam else None
+    _lib.check(_lib.load().md_op_hook_cat_ln(dev.handle, _p(x_local), _p(x), T, S, n_tokens, D, _p(_f32c(norm_g)), _p(_f32c(norm_b)),
+                                             C.c_float(eps_final), _p(_f32c(head_g)), _p(_f32c(head_b)), C.c_float(eps_head), precision,
+                                             _p(out), _p(cam), _stream_ptr(dev.ordinal)))
+    return out, cam
+
+
+def patchify(dev: Device, x: torch.Tensor, ps: int, Kp: int, precision: int, cls_x: Optional[torch.Tensor] = None, S: int = 0,
+             cls: Optional[torch.Tensor] = None, pos0: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """md_op_patchify: x [B,3,H,W] -> (patch rows [B * ph * pw, Kp], the updated copy of cls_x [B*S, D] or None)."""
+    x = _f32c(x)
+    B, _, H, W = x.shape
+    n_tokens = 1 + (H // ps) * (W // ps)
+    out = torch.empty((B * (n_tokens - 1), Kp), dtype=torch.float32, device=x.device)
+    D = 0
+    if cls_x is not None:
+        cls_x = _f32c(cls_x).clone()
+        D = cls_x.shape[1]
+        cls, pos0 = _f32c(cls), _f32c(pos0)
+    _lib.check(_lib.load().md_op_patchify(dev.handle, _p(x), B, H, W, ps, Kp, precision, _p(out), _p(cls_x), S, n_tokens, D, _p(cls),
+                                          _p(pos0), _stream_ptr(dev.ordinal)))
+    return out, cls_x
+
+
+def set_token0(dev: Device, x: torch.Tensor, S: int, src: torch.Tensor, src_stride: int) -> torch.Tensor:
+    """md_op_set_token0 on a copy of x [nseq*S, D]: row 0 of every sequence <- src[b * src_stride, :D]."""
+    x, src = _f32c(x).clone(), _f32c(src)
+    rows, D = x.shape
+    _lib.check(_lib.load().md_op_set_token0(dev.handle, _p(x), rows // S, S, D, _p(src), src_stride, _stream_ptr(dev.ordinal)))
+    return x
+
+
+def border_bias_fix(dev: Device, fmap: torch.Tensor, C_: int, bias9: torch.Tensor, precision: int) -> torch.Tensor:
+    """md_op_border_bias_fix on a copy of the NHWC map [B,H,W,ld] (channels 0 .. C_-1 are corrected)."""
+    fmap = _f32c(fmap).clone()
+    B, H, W, ld = fmap.shape
+    _lib.check(_lib.load().md_op_border_bias_fix(dev.handle, _p(fmap), B, H, W, C_, ld, _p(_f32c(bias9)), precision,
+                                                 _stream_ptr(dev.ordinal)))
+    return fmap
+
+
 def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None, focal_px=None, conf: Optional[torch.Tensor] = None,
               rgb: Optional[torch.Tensor] = None, dense: bool = True, compact: bool = True, capacity: Optional[int] = None,
               out: Optional[PointCloud] = None, **opts) -> PointCloud:

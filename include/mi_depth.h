@@ -515,6 +515,37 @@ int md_op_deconv2x2(md_device_t dev, const float* x_dev, const float* w_dev, con
 int md_op_conv2d_direct(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B,
                         int Cin, int H, int W, int Cout, int k, int stride, int pad, int relu, float* out_dev,
                         void* stream);
+/* ---- the Depth-Anything-v3 token kernels alone (test-only). fp32 device tensors in and out; rows pass through `precision`'s
+ * storage type (MD_PREC_BF16 / F32 / F16 / F16X2) exactly as the engine holds them. RoPE tables: the model's own function, for
+ * the grid ph x pw with ph = (n_tokens - 1) / pw. ---- */
+/* The QKV projection with the per-head q/k LayerNorm(64) + 2-D RoPE: x [T*S, K], w [3D, K], bias [3D], gammas / betas [64];
+ * token t = row % S sits at (0, 0) for t == 0 or t >= n_tokens, else at patch (1 + (t-1) / pw, 1 + (t-1) % pw), or at (1, 1)
+ * when global_pos. form 0: the plain QKV GEMM followed by the stand-alone q/k-norm + RoPE kernel (rows t >= n_tokens keep
+ * the GEMM's plain q | k); form 1: the GEMM's fused epilogue. tile: 3 = 128x64, 4 = 64x64, 99 = auto; a tile the fused
+ * epilogue cannot take is MD_ERR_UNSUPPORTED. qk_out [T*S, 2D] = q' | k' (q' carries the softmax scale of the mode),
+ * vt_out [T, D/64, 64, kpad] = V^T as the epilogue lays it out, kpad = S rounded up to 64. */
+int md_op_qkv_norm_rope(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* q_gamma,
+                        const float* q_beta, const float* k_gamma, const float* k_beta, int T, int S, int n_tokens, int K, int D,
+                        int pw, int global_pos, float rope_frequency, float eps, int precision, int tile, int form,
+                        float* qk_out, float* vt_out, void* stream);
+/* The stand-alone q/k-norm + RoPE kernel on caller rows qk_in [T*S, 2D] = q | k -> qk_out (rows t >= n_tokens untouched). */
+int md_op_qk_norm_rope(md_device_t dev, const float* qk_in, const float* q_gamma, const float* q_beta, const float* k_gamma,
+                       const float* k_beta, int T, int S, int n_tokens, int D, int pw, int global_pos, float rope_frequency,
+                       float eps, int precision, float* qk_out, void* stream);
+/* hook = LayerNorm_head(cat(x_local, LayerNorm_final(x))): x_local, x [T*S, D] -> out [T*S, 2D], updated in place (rows
+ * t >= n_tokens keep the caller's values); cam_out [T, 2D] = the raw token-0 concat, may be NULL. */
+int md_op_hook_cat_ln(md_device_t dev, const float* x_local, const float* x, int T, int S, int n_tokens, int D,
+                      const float* norm_g, const float* norm_b, float eps_final, const float* head_g, const float* head_b,
+                      float eps_head, int precision, float* out, float* cam_out, void* stream);
+/* Generic patch extraction: x [B,3,H,W] -> out [B * (H/ps) * (W/ps), Kp] (Kp >= 3 ps^2, tail zero). cls_x != NULL: the same
+ * launch writes cls + pos0 to row 0 and zeroes rows n_tokens .. S-1 of every sequence of cls_x [B*S, D] (in place). */
+int md_op_patchify(md_device_t dev, const float* x_dev, int B, int H, int W, int ps, int Kp, int precision, float* out,
+                   float* cls_x, int S, int n_tokens, int D, const float* cls, const float* pos0, void* stream);
+/* x[b*S, :] = src[b * src_stride, 0:D] for every sequence of x [nseq*S, D] (in place). */
+int md_op_set_token0(md_device_t dev, float* x, int nseq, int S, int D, const float* src, int src_stride, void* stream);
+/* Adds bias9[class] - bias9[4] to the border pixels of the NHWC map [B,H,W,ld] (columns 0 .. C-1; in place), bias9 [9, C]. */
+int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int C, int ld, const float* bias9, int precision,
+                          void* stream);
 /* `fovy_from_fovx_rad` (mod.rs:370-414) + focal length (mod.rs:330-336) on host scalars. */
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad);
 /* The reverse, on host scalars: a focal length f_px (pixels of the W-wide image) -> fovx_deg = 2 atan(W / (2 f_px)) in
