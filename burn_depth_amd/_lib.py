@@ -63,6 +63,17 @@ class MdPointsOutputs(C.Structure):
                 ("count", C.c_void_p), ("capacity", C.c_int64), ("depth", C.c_void_p)]
 
 
+class MdViewFilterOpts(C.Structure):
+    """md_view_filter_opts (include/mi_depth.h)."""
+    _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_percentile", C.c_int),
+                ("view_rtol", C.c_float), ("min_views", C.c_int)]
+
+
+class MdViewFilterOutputs(C.Structure):
+    """md_view_filter_outputs (include/mi_depth.h)."""
+    _fields_ = [("depth", C.c_void_p), ("support", C.c_void_p), ("conf_threshold", C.c_void_p), ("kept", C.c_void_p)]
+
+
 class MdDa3Cfg(C.Structure):
     _fields_ = [("variant", C.c_char_p), ("image_size", C.c_int), ("precision", C.c_int), ("max_batch", C.c_int),
                 ("ln_eps", C.c_float), ("image_width", C.c_int)]
@@ -131,6 +142,11 @@ SYMBOLS = {
     "md_op_unproject": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), _P]),
     "md_infer_points": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
                              C.POINTER(MdPointsOutputs), _I, _P]),
+    "md_view_filter_opts_default": (None, [C.POINTER(MdViewFilterOpts)]),
+    "md_op_filter_views": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                C.POINTER(MdViewFilterOutputs), _P]),
+    "md_infer_points_filtered": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                      C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

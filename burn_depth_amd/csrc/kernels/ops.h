@@ -59,6 +59,29 @@ size_t points_scratch_bytes(int B, int H, int W);
 // classify (+ scan + scatter when p.count is set); scratch may be null when p.count is
 int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s);
 
+// ---- view filter (kernels/view_filter.hip; md_op_filter_views, md_infer_points_filtered) ----
+// depth [B,H,W] (+ confidence) and the cameras of the point path -> the depth with rejected pixels set to 0: an exact
+// confidence percentile over all candidates of the call (radix select, four histogram + select launch pairs), then the
+// cross-view support count. Every pointer is a device pointer. E is read only when rtol > 0.
+struct ViewFilterParams {
+  const float* depth = nullptr;
+  const float* conf = nullptr;
+  const float *K = nullptr, *E = nullptr, *focal = nullptr;
+  int B = 0, H = 0, W = 0;
+  float off = 0.f, dmin = 0.f, dmax = 0.f;  // dmin / dmax already resolved
+  int q = 0;                                // percentile, 0 = off (tau = 0)
+  float rtol = 0.f;                         // 0 = no cross-view test (support = 0, every survivor is kept)
+  int min_views = 0;
+  float* depth_out = nullptr;
+  uint8_t* support = nullptr;
+  float* tau = nullptr;     // [1]
+  int32_t* kept = nullptr;  // [B + 1]
+};
+constexpr int kViewFilterMaxViews = 64;  // support is u8 and the B cameras sit in LDS
+// bytes of the filter's scratch (histogram table, select state)
+size_t view_filter_scratch_bytes();
+int launch_view_filter(const ViewFilterParams& p, void* scratch, hipStream_t s);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

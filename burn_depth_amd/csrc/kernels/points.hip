@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "ops.h"
+#include "points_math.h"
 
 namespace md {
 
@@ -20,47 +21,6 @@ constexpr int kThreads = 256;                // 4 waves of 64
 constexpr int kSteps = 16;                   // pixels per thread
 constexpr int kTile = kThreads * kSteps;     // 4096 pixels per workgroup: pixel = tile * 4096 + step * 256 + thread
 constexpr int kWords = kTile / 64;           // 64 ballot words per workgroup: word = step * 4 + wave
-
-struct Camera {
-  float fx, fy, cx, cy;
-  float r[9], t[3];
-};
-
-__device__ __forceinline__ Camera load_camera(const PointsParams& p, int b) {
-  Camera c;
-  if (p.K) {
-    const float* k = p.K + (long)b * 9;
-    c.fx = k[0]; c.fy = k[4]; c.cx = k[2]; c.cy = k[5];
-  } else {
-    c.fx = c.fy = p.focal[b];
-    c.cx = (float)p.W / 2.0f;
-    c.cy = (float)p.H / 2.0f;
-  }
-  if (p.world) {
-    const float* e = p.E + (long)b * 12;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) c.r[3 * i + j] = e[4 * i + j];
-      c.t[i] = e[4 * i + 3];
-    }
-  }
-  return c;
-}
-
-// the arithmetic contract: back-projection, then p_w = R^T (p_c - t)
-__device__ __forceinline__ void unproject(const Camera& c, int world, float off, int v, int u, float d, float* out) {
-  const float rx = (((float)u + off) - c.cx) / c.fx;
-  const float ry = (((float)v + off) - c.cy) / c.fy;
-  float x = rx * d, y = ry * d, z = d;
-  if (world) {
-    const float qx = x - c.t[0], qy = y - c.t[1], qz = z - c.t[2];
-    x = (c.r[0] * qx + c.r[3] * qy) + c.r[6] * qz;
-    y = (c.r[1] * qx + c.r[4] * qy) + c.r[7] * qz;
-    z = (c.r[2] * qx + c.r[5] * qy) + c.r[8] * qz;
-  }
-  out[0] = x; out[1] = y; out[2] = z;
-}
 
 // a neighbour that is not finite or <= 0 is ignored
 __device__ __forceinline__ bool edge_ok(float d, float dn, float rtol) {
@@ -93,7 +53,7 @@ __global__ void __launch_bounds__(kThreads) points_classify_kernel(PointsParams 
   const bool dense = p.point_map || p.mask;
   const bool list = p.count != nullptr;
   Camera cam;
-  if (p.point_map) cam = load_camera(p, b);
+  if (p.point_map) cam = load_camera(p.K, p.focal, p.world ? p.E : nullptr, p.H, p.W, b);
   int n = 0;
   for (int s = 0; s < kSteps; ++s) {
     const long i = (long)tile * kTile + s * kThreads + tid;
@@ -175,7 +135,7 @@ __global__ void __launch_bounds__(kThreads) points_scatter_kernel(PointsParams p
   if (base >= p.capacity) return;  // everything of this workgroup lies beyond the capacity
   const long hw = (long)p.H * p.W;
   const float* dv = p.depth + (long)b * hw;
-  const Camera cam = load_camera(p, b);
+  const Camera cam = load_camera(p.K, p.focal, p.world ? p.E : nullptr, p.H, p.W, b);
   for (int s = 0; s < kSteps; ++s) {
     const int w = s * (kThreads / 64) + wave;
     const unsigned long long word = words[w];

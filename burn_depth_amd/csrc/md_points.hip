@@ -1,6 +1,8 @@
 // The point path: md_op_unproject (depth + cameras -> point map / mask / ordered cloud on caller tensors) and md_infer_points
 // (the model's infer body, then the same kernels on its results, in one call). model (model_infer / da3_infer_ex bodies) ->
 // classify / scan / scatter (kernels/points.hip); one captured graph per replay key when the model replays graphs.
+// md_op_filter_views / md_infer_points_filtered put the view filter (kernels/view_filter.hip: confidence percentile, cross-view
+// support) in front of those launches: it hands them a depth in which rejected pixels are 0.
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -14,6 +16,8 @@
 struct md_model_s::PointsState {
   md::GrowBuf<void> scratch;      // bit mask | block counts | block offsets
   md::GrowBuf<float> depth, conf; // the model's depth (no device `depth` output) and confidence
+  md::GrowBuf<float> raw;         // md_infer_points_filtered: the model's depth; `depth` / the caller's buffer take the filtered one
+  md::GrowBuf<void> filter;       // the view filter's histogram table and select state
   md::GrowBuf<float> cams;        // K [B,9] | E [B,12] | focal [B]: the model's cameras, or the device copy of host ones
   md::GrowBuf<float> x;           // host input image
   md::GrowBuf<uint8_t> rgb;       // host rgb
@@ -54,16 +58,55 @@ int check_points(const md_points_opts* o, const md_points_outputs* out, const So
   return MD_OK;
 }
 
+// 0 = the default of that bound
+float depth_min_of(float v) { return v > 0.f ? v : FLT_MIN; }
+float depth_max_of(float v) { return v > 0.f ? v : FLT_MAX; }
+
 PointsParams make_params(int B, int H, int W, const md_points_opts& o) {
   PointsParams p;
   p.B = B; p.H = H; p.W = W;
   p.off = o.pixel_offset;
-  p.dmin = o.depth_min > 0.f ? o.depth_min : FLT_MIN;
-  p.dmax = o.depth_max > 0.f ? o.depth_max : FLT_MAX;
+  p.dmin = depth_min_of(o.depth_min);
+  p.dmax = depth_max_of(o.depth_max);
   p.conf_min = o.conf_min;
   p.edge_rtol = o.edge_rtol;
   p.stride = o.stride;
   p.world = o.world ? 1 : 0;
+  return p;
+}
+
+// has_conf / has_intr / has_E: what the filter will find on the device (the caller's or the model's)
+int check_filter(const md_view_filter_opts* o, bool has_conf, bool has_intr, bool has_E, int B, int H, int W) {
+  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "view filter options are null");
+  if (o->conf_percentile < 0 || o->conf_percentile > 99) MD_FAIL(MD_ERR_INVALID_ARG, "conf_percentile %d outside 0..99", o->conf_percentile);
+  if (o->conf_percentile > 0 && !has_conf) MD_FAIL(MD_ERR_INVALID_ARG, "conf_percentile > 0 needs a confidence map");
+  if (!std::isfinite(o->view_rtol) || o->view_rtol < 0.f) MD_FAIL(MD_ERR_INVALID_ARG, "view_rtol = %g: must be finite and >= 0", (double)o->view_rtol);
+  if (!std::isfinite(o->pixel_offset)) MD_FAIL(MD_ERR_INVALID_ARG, "pixel_offset is not finite");
+  if (!std::isfinite(o->depth_min) || o->depth_min < 0.f || !std::isfinite(o->depth_max) || o->depth_max < 0.f)
+    MD_FAIL(MD_ERR_INVALID_ARG, "depth bounds %g, %g: must be finite and >= 0", (double)o->depth_min, (double)o->depth_max);
+  if (o->depth_min > 0.f && o->depth_max > 0.f && o->depth_max < o->depth_min)
+    MD_FAIL(MD_ERR_INVALID_ARG, "depth_max %g < depth_min %g", (double)o->depth_max, (double)o->depth_min);
+  const bool views = o->view_rtol > 0.f;
+  if (!views && o->min_views != 0) MD_FAIL(MD_ERR_INVALID_ARG, "min_views %d without view_rtol", o->min_views);
+  if (views && o->min_views < 1) MD_FAIL(MD_ERR_INVALID_ARG, "view_rtol > 0 needs min_views >= 1, got %d", o->min_views);
+  if (views && !has_E) MD_FAIL(MD_ERR_INVALID_ARG, "view_rtol > 0 needs extrinsics");
+  if (views && !has_intr) MD_FAIL(MD_ERR_INVALID_ARG, "view_rtol > 0 needs intrinsics or a focal length");
+  if (B <= 0 || H <= 0 || W <= 0 || (long)B * H * W >= (1l << 31) || B >= 65536) MD_FAIL(MD_ERR_SHAPE, "invalid depth shape [%d,%d,%d]", B, H, W);
+  if (views && (B < 2 || B > kViewFilterMaxViews)) MD_FAIL(MD_ERR_SHAPE, "view_rtol > 0 takes 2..%d views, got %d", kViewFilterMaxViews, B);
+  if (views && (H >= (1 << 24) || W >= (1 << 24))) MD_FAIL(MD_ERR_SHAPE, "view_rtol > 0: image sides below 2^24, got %d x %d", H, W);
+  if (views && o->min_views > B - 1) MD_FAIL(MD_ERR_INVALID_ARG, "min_views %d: only %d other views", o->min_views, B - 1);
+  return MD_OK;
+}
+
+ViewFilterParams make_filter_params(int B, int H, int W, const md_view_filter_opts& o) {
+  ViewFilterParams p;
+  p.B = B; p.H = H; p.W = W;
+  p.off = o.pixel_offset;
+  p.dmin = depth_min_of(o.depth_min);
+  p.dmax = depth_max_of(o.depth_max);
+  p.q = o.conf_percentile;
+  p.rtol = o.view_rtol;
+  p.min_views = o.min_views;
   return p;
 }
 
@@ -102,11 +145,38 @@ int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev,
   return rc;
 }
 
+int op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_dev, int B, int H, int W, const md_points_cameras* cam,
+                    const md_view_filter_opts* o, const md_view_filter_outputs* out, hipStream_t stream) {
+  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "view filter options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "view filter outputs are null");
+  if (!out->depth && !out->support && !out->conf_threshold && !out->kept) MD_FAIL(MD_ERR_INVALID_ARG, "every view filter output is null");
+  if (out->depth && out->depth == depth_dev) MD_FAIL(MD_ERR_INVALID_ARG, "the filtered depth may not be the input");
+  const md_points_cameras none = {nullptr, nullptr, nullptr};
+  const md_points_cameras& c = cam ? *cam : none;
+  MD_TRY(check_filter(o, conf_dev != nullptr, c.intrinsics || c.focal_px, c.extrinsics != nullptr, B, H, W));
+  if (!depth_dev) MD_FAIL(MD_ERR_INVALID_ARG, "depth pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  ViewFilterParams p = make_filter_params(B, H, W, *o);
+  p.depth = depth_dev; p.conf = conf_dev;
+  p.K = c.intrinsics; p.focal = c.intrinsics ? nullptr : c.focal_px; p.E = c.extrinsics;
+  p.depth_out = out->depth; p.support = out->support; p.tau = out->conf_threshold; p.kept = out->kept;
+  void* scratch = nullptr;
+  MD_HIP(hipMalloc(&scratch, view_filter_scratch_bytes()));
+  const int rc = launch_view_filter(p, scratch, st);
+  const hipError_t se = hipStreamSynchronize(st);  // the scratch is freed on return
+  (void)hipFree(scratch);
+  if (rc == MD_OK) MD_HIP(se);
+  return rc;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the model call
 // ------------------------------------------------------------------------------------------------
 static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras& cam,
-                        const md_points_opts& o, const md_points_outputs& out, int out_kind, bool dual, hipStream_t st) {
+                        const md_points_opts& o, const md_points_outputs& out, int out_kind, bool dual, hipStream_t st,
+                        const md_view_filter_opts* fo) {
   if (!m->points) m->points = new md_model_s::PointsState();
   md_model_s::PointsState* f = m->points;
   const bool host_in = in_kind == MD_MEM_HOST, host_out = out_kind == MD_MEM_HOST;
@@ -117,6 +187,13 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   if (!depth || host_out) {
     MD_TRY(grow(m, st, f->depth, npx * 4));
     depth = f->depth.p;
+  }
+  float* raw = depth;  // what the model writes; with the filter, `depth` takes the filtered map
+  const bool views = fo && fo->view_rtol > 0.f;
+  if (fo) {
+    MD_TRY(grow(m, st, f->raw, npx * 4));
+    raw = f->raw.p;
+    MD_TRY(grow(m, st, f->filter, view_filter_scratch_bytes()));
   }
   float* conf = nullptr;
   if (dual) {
@@ -175,24 +252,34 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
     if (f_dev) { MD_TRY(h2d(f_home, f_dev, (size_t)B * 4)); f_dev = f_home; }
   }
   // ---- the model: its cameras land in the homes of those the caller did not give ----
-  const bool need_k = !k_dev && !f_dev, need_e = o.world && !e_dev;
+  const bool need_k = !k_dev && !f_dev, need_e = (o.world || views) && !e_dev;
   if (m->kind == 1) {
     Da3Outputs d;
-    d.depth = depth;
+    d.depth = raw;
     d.depth_confidence = conf;
     if (dual && need_k) { d.intrinsics = k_home; k_dev = k_home; }
     if (dual && need_e) { d.extrinsics = e_home; e_dev = e_home; }
     MD_TRY(da3_infer_ex_direct(m, x_dev, B, H, W, d, st));
   } else if (cam.focal_px) {
-    MD_TRY(model_infer_direct(m, x_dev, B, H, W, depth, nullptr, nullptr, st, f_dev));
+    MD_TRY(model_infer_direct(m, x_dev, B, H, W, raw, nullptr, nullptr, st, f_dev));
   } else {
-    MD_TRY(model_infer_direct(m, x_dev, B, H, W, depth, need_k ? f_home : nullptr, nullptr, st));
+    MD_TRY(model_infer_direct(m, x_dev, B, H, W, raw, need_k ? f_home : nullptr, nullptr, st));
     if (need_k) f_dev = f_home;
+  }
+  Run r{m, st, B};
+  // ---- view filter: raw -> depth, rejected pixels 0 ----
+  if (fo) {
+    ViewFilterParams v = make_filter_params(B, H, W, *fo);
+    v.depth = raw; v.conf = conf;
+    v.K = k_dev; v.focal = k_dev ? nullptr : f_dev; v.E = views ? e_dev : nullptr;
+    v.depth_out = depth;
+    r.begin("points_view_filter");
+    MD_TRY(launch_view_filter(v, f->filter.p, st));
+    r.end();
   }
   // ---- points ----
   p.depth = depth; p.conf = conf; p.rgb = rgb_dev;
   p.K = k_dev; p.focal = k_dev ? nullptr : f_dev; p.E = o.world ? e_dev : nullptr;
-  Run r{m, st, B};
   r.begin("points_unproject");
   MD_TRY(launch_unproject(p, f->scratch.p, st));
   r.end();
@@ -217,7 +304,8 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
 }
 
 int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
-                 const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream) {
+                 const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream, const md_view_filter_opts* fo,
+                 bool filtered) {
   if (!m) MD_FAIL(MD_ERR_INVALID_ARG, "model is null");
   if (!nchw) MD_FAIL(MD_ERR_INVALID_ARG, "input pointer is null");
   if ((in_kind != MD_MEM_HOST && in_kind != MD_MEM_DEVICE) || (out_kind != MD_MEM_HOST && out_kind != MD_MEM_DEVICE))
@@ -228,6 +316,7 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   const bool own_cams = m->kind == 0 || dual;  // Depth Pro predicts a focal length, the dual head's camera decoder K and E
   if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "point options are null");
   if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  if (filtered && !fo) MD_FAIL(MD_ERR_INVALID_ARG, "view filter options are null");
   if (!own_cams && !c.intrinsics && !c.focal_px)
     MD_FAIL(MD_ERR_UNSUPPORTED, "this Depth-Anything-v3 variant has no camera decoder: intrinsics or a focal length are required");
   Sources s;
@@ -237,6 +326,12 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   s.focal = c.focal_px != nullptr || m->kind == 0;
   s.E = c.extrinsics != nullptr || dual;
   MD_TRY(check_points(o, out, s, B, H, W));
+  if (fo) {
+    MD_TRY(check_filter(fo, s.conf, s.K || s.focal, s.E, B, H, W));
+    if (fbits(fo->pixel_offset) != fbits(o->pixel_offset) || depth_min_of(fo->depth_min) != depth_min_of(o->depth_min) ||
+        depth_max_of(fo->depth_max) != depth_max_of(o->depth_max))
+      MD_FAIL(MD_ERR_INVALID_ARG, "pixel_offset and the depth bounds of the view filter and the point options differ");
+  }
   if (B > m->cfg.max_batch) MD_FAIL(MD_ERR_SHAPE, "batch %d exceeds max_batch %d", B, m->cfg.max_batch);
   if (m->kind == 0 && c.focal_px && in_kind == MD_MEM_HOST)
     for (int i = 0; i < B; ++i)
@@ -245,7 +340,7 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   if (!model_root(m)->committed) MD_FAIL(MD_ERR_INVALID_ARG, "weights were modified; call md_model_commit_weights first");
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = model_stream(m, stream);
-  auto body = [&]() { return points_eager(m, nchw, B, H, W, in_kind, rgb, c, *o, *out, out_kind, dual, st); };
+  auto body = [&]() { return points_eager(m, nchw, B, H, W, in_kind, rgb, c, *o, *out, out_kind, dual, st, fo); };
   if (!m->graph_enabled) return body();
   // the key: stream, shape, every option, every in / out pointer and the commit generation (md_frame.hip); a graph only
   // replays at the model's current input size (its workspace plan)
@@ -258,13 +353,14 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   } else {
     eligible = eligible && H == m->S && W == m->S;
   }
-  const std::vector<uintptr_t> key = {(uintptr_t)0x504f494eu, (uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw,
+  std::vector<uintptr_t> key = {(uintptr_t)0x504f494eu, (uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw,
                                       (uintptr_t)rgb, (uintptr_t)c.intrinsics, (uintptr_t)c.extrinsics, (uintptr_t)c.focal_px,
                                       fbits(o->pixel_offset), fbits(o->depth_min), fbits(o->depth_max), fbits(o->conf_min),
                                       fbits(o->edge_rtol), (uintptr_t)o->stride, (uintptr_t)(o->world ? 1 : 0),
                                       (uintptr_t)out->point_map, (uintptr_t)out->mask, (uintptr_t)out->xyz, (uintptr_t)out->rgb,
                                       (uintptr_t)out->conf, (uintptr_t)out->count, (uintptr_t)out->capacity, (uintptr_t)out->depth,
                                       (uintptr_t)gen};
+  if (fo) key.insert(key.end(), {(uintptr_t)0x56464c54u, (uintptr_t)fo->conf_percentile, fbits(fo->view_rtol), (uintptr_t)fo->min_views});
   return run_with_graph(m, st, key, eligible, body);
 }
 

@@ -102,6 +102,10 @@ def _points_opts(pixel_offset=0.0, depth_min=0.0, depth_max=0.0, conf_min=0.0, e
                              int(bool(world)))
 
 
+def _view_filter_opts(pixel_offset=0.0, depth_min=0.0, depth_max=0.0, conf_percentile=0, view_rtol=0.0, min_views=0) -> "_lib.MdViewFilterOpts":
+    return _lib.MdViewFilterOpts(float(pixel_offset), float(depth_min), float(depth_max), int(conf_percentile), float(view_rtol), int(min_views))
+
+
 def _points_outputs(dev, B: int, H: int, W: int, dense: bool, compact: bool, capacity: Optional[int], stride: int, want_rgb: bool,
                     want_conf: bool, want_depth: bool, out: Optional[PointCloud]):
     """A PointCloud of fresh device tensors (or `out`, to write into again) and its md_points_outputs."""
@@ -525,11 +529,14 @@ class DepthPro:
     # ---- point path --------------------------------------------------------------------------
     def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
-                     **opts) -> PointCloud:
+                     conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, **opts) -> PointCloud:
         """`md_infer_points`: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the caller's
         (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True). rgb: u8
         [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
-        world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays)."""
+        world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
+        conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the call is
+        `md_infer_points_filtered`, which drops the lowest conf_percentile % of the confidences of the call and the pixels fewer
+        than min_views other views confirm within view_rtol before the unprojection; `depth` is then the filtered depth."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -541,9 +548,15 @@ class DepthPro:
         has_conf = bool(getattr(self.config, "dual_head", False))
         res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, rgb is not None, has_conf, True, out)
         cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, f_px)
-        _lib.check(self._lib.md_infer_points(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                             C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), C.byref(o),
-                                             C.byref(outs), _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        rgb_p = C.c_void_p(rgb.data_ptr()) if rgb is not None else None
+        if conf_percentile or view_rtol or min_views:
+            fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
+            _lib.check(self._lib.md_infer_points_filtered(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
+                                                          C.byref(fo), C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE,
+                                                          _stream_ptr(self.device.ordinal)))
+        else:
+            _lib.check(self._lib.md_infer_points(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
+                                                 C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

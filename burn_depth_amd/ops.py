@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import Device, PointCloud, _points_cameras, _points_opts, _points_outputs, _stream_ptr
+from .depth_pro import Device, PointCloud, _points_cameras, _points_opts, _points_outputs, _stream_ptr, _view_filter_opts
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -273,6 +273,27 @@ def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None
                                            _stream_ptr(dev.ordinal)))
     del keep
     return res
+
+
+def filter_views(dev: Device, depth: torch.Tensor, conf: Optional[torch.Tensor] = None, intrinsics=None, extrinsics=None, focal_px=None,
+                 out: Optional[dict] = None, **opts):
+    """md_op_filter_views: depth [B,H,W] (+ conf [B,H,W]) and the cameras of `unproject` -> (depth_out [B,H,W], support u8 [B,H,W],
+    tau [1], kept int32 [B+1]). opts: the fields of `md_view_filter_opts`. `out`: a dict with any of the keys depth, support, tau,
+    kept -> the tensors to write into (None = that output is skipped); default: four fresh tensors. Bit-identical to
+    `pipeline.filter_views`."""
+    depth = _f32c(depth)
+    B, H, W = (int(v) for v in depth.shape)
+    conf = _f32c(conf) if conf is not None else None
+    if out is None:
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=depth.device)  # noqa: E731
+        out = dict(depth=f(B, H, W), support=f(B, H, W, dt=torch.uint8), tau=f(1), kept=f(B + 1, dt=torch.int32))
+    o = _view_filter_opts(**opts)
+    outs = _lib.MdViewFilterOutputs(*((out[k].data_ptr() if out.get(k) is not None else None) for k in ("depth", "support", "tau", "kept")))
+    cam, keep = _points_cameras(depth.device, B, intrinsics, extrinsics, focal_px)
+    _lib.check(_lib.load().md_op_filter_views(dev.handle, _p(depth), _p(conf), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
+                                              _stream_ptr(dev.ordinal)))
+    del keep
+    return out.get("depth"), out.get("support"), out.get("tau"), out.get("kept")
 
 
 def fov_to_focal(fovx_deg: float, H: int, W: int) -> Tuple[float, float]:

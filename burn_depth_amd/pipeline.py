@@ -12,6 +12,8 @@
   references of the device frame call `md_process_frame` (`DepthPro.process_frame`)
 * `unproject_depth`, `write_ply` / `read_ply`  -- the point path (no counterpart in the reference): the host reference the
   device kernels of `md_op_unproject` / `md_infer_points` are bit-identical to, and a binary little-endian PLY writer / reader
+* `filter_views`                              -- the host reference of `md_op_filter_views` / `md_infer_points_filtered`: the exact
+  confidence percentile and the cross-view support test in front of the point path
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
   stands in (8-bit grayscale, filter 0), `read_gray_png` reads it back for the tests.
 JPEG decoding stays out of scope: images come in as uint8 arrays."""
@@ -339,6 +341,90 @@ def unproject_depth(depth, intrinsics=None, extrinsics=None, focal_px=None, conf
                       None if cf is None else cf[sel], count)
 
 
+def filter_views(depth, conf=None, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, depth_min=0.0,
+                 depth_max=0.0, conf_percentile=0, view_rtol=0.0, min_views=0, dtype=np.float32):
+    """The host reference of md_op_filter_views (include/mi_depth.h states the contract): depth [B,H,W], optional conf [B,H,W]
+    and the cameras of `unproject_depth` -> (depth_out [B,H,W]: d where kept, else 0; support uint8 [B,H,W]; tau, a `dtype`
+    scalar; kept int32 [B+1]: per view, then the total). Every step is one rounded operation of `dtype`, in the order of the
+    device kernels (kernels/view_filter.hip): with f32 the results are theirs bit for bit; dtype=np.float64 is the same
+    formulas for the geometric tests."""
+    T = np.dtype(dtype).type
+    d = np.asarray(depth, dtype=dtype)
+    if d.ndim != 3:
+        raise ValueError(f"expected depth [B,H,W], got {d.shape}")
+    B, H, W = d.shape
+    q = int(conf_percentile)
+    if not 0 <= q <= 99:
+        raise ValueError("conf_percentile outside 0..99")
+    if q > 0 and conf is None:
+        raise ValueError("conf_percentile needs a confidence map")
+    if not np.isfinite(view_rtol) or view_rtol < 0:
+        raise ValueError("view_rtol must be finite and >= 0")
+    views = view_rtol > 0
+    if (not views and min_views != 0) or (views and not 1 <= min_views <= B - 1):
+        raise ValueError("min_views: 0 without view_rtol, 1..B-1 with it")
+    if views and not 2 <= B <= 64:
+        raise ValueError("view_rtol takes 2..64 views")
+    f32i = np.finfo(np.float32)
+    dmin = T(depth_min) if depth_min > 0 else T(f32i.tiny)
+    dmax = T(depth_max) if depth_max > 0 else T(f32i.max)
+    with np.errstate(all="ignore"):
+        cand = np.isfinite(d) & (d >= dmin) & (d <= dmax)
+        cf = None
+        if conf is not None:
+            cf = np.asarray(conf, dtype=dtype).reshape(B, H, W)
+            cand &= np.isfinite(cf) & (cf >= T(0))
+        # ---- percentile: tau = the k-th smallest candidate confidence, k = (N - 1) q // 100 ----
+        tau = T(0)
+        if q > 0:
+            c = cf[cand]
+            c = np.where(c == 0, T(0), c)  # -0 counts as +0
+            if c.size:
+                tau = np.sort(c)[((c.size - 1) * q) // 100]
+        surv = cand & (cf >= tau) if cf is not None else cand
+        # ---- cross-view support ----
+        support = np.zeros((B, H, W), np.uint8)
+        if views:
+            if extrinsics is None:
+                raise ValueError("view_rtol needs extrinsics")
+            if intrinsics is not None:
+                K = np.asarray(intrinsics, dtype=dtype).reshape(B, 3, 3)
+                fx, fy, cx, cy = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+            elif focal_px is not None:
+                fx = fy = np.asarray(focal_px, dtype=dtype).reshape(B)
+                cx, cy = np.full(B, T(W) / T(2), dtype), np.full(B, T(H) / T(2), dtype)
+            else:
+                raise ValueError("neither intrinsics nor a focal length")
+            E = np.asarray(extrinsics, dtype=dtype).reshape(B, 3, 4)
+            off, rt, half = T(pixel_offset), T(view_rtol), T(0.5)
+            u = np.arange(W, dtype=dtype)[None, :]
+            v = np.arange(H, dtype=dtype)[:, None]
+            for i in range(B):
+                # X_w exactly as unproject_depth(world=True) computes it
+                rx = ((u + off) - cx[i]) / fx[i]
+                ry = ((v + off) - cy[i]) / fy[i]
+                qx, qy, qz = rx * d[i] - E[i, 0, 3], ry * d[i] - E[i, 1, 3], d[i] - E[i, 2, 3]
+                X = [(E[i, 0, a] * qx + E[i, 1, a] * qy) + E[i, 2, a] * qz for a in range(3)]
+                sup = np.zeros((H, W), np.int32)
+                for j in range(B):
+                    if j == i:
+                        continue
+                    px, py, pz = [((E[j, a, 0] * X[0] + E[j, a, 1] * X[1]) + E[j, a, 2] * X[2]) + E[j, a, 3] for a in range(3)]
+                    uf = ((fx[j] * (px / pz)) + cx[j]) - off
+                    vf = ((fy[j] * (py / pz)) + cy[j]) - off
+                    uu, vv = np.floor(uf + half), np.floor(vf + half)
+                    seen = (pz > 0) & (uu >= 0) & (uu < T(W)) & (vv >= 0) & (vv < T(H))
+                    ui, vi = np.where(seen, uu, 0).astype(np.int64), np.where(seen, vv, 0).astype(np.int64)
+                    dj = d[j][vi, ui]
+                    ok = seen & surv[j][vi, ui] & (np.abs(pz - dj) <= rt * np.minimum(pz, dj))
+                    sup += ok
+                support[i] = np.where(surv[i], sup, 0).astype(np.uint8)
+        kept_mask = surv & (support >= min_views)
+    depth_out = np.where(kept_mask, d, T(0)).astype(dtype)
+    kept = np.concatenate([kept_mask.reshape(B, -1).sum(1), [kept_mask.sum()]]).astype(np.int32)
+    return depth_out, support, T(tau), kept
+
+
 def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None) -> None:
     """Binary little-endian PLY: `x y z` float, optional `red green blue` uchar."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
@@ -428,7 +514,8 @@ class AnyDepthModel:
 
     def infer_points(self, x, **kw):
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
-        Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`."""
+        Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
+        filter, `md_infer_points_filtered`) included."""
         return self.model.infer_points(x, **kw)
 
     def preferred_input_resolution(self) -> Optional[int]:

@@ -323,6 +323,58 @@ int md_infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in
                     const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, int out_kind,
                     void* stream);
 
+/* ---- view filter: a confidence percentile and a cross-view consistency test in front of the point path ---------------
+ * depth [B,H,W], an optional confidence map [B,H,W] and the cameras of the point path -> the same depth with rejected
+ * pixels set to 0, which md_op_unproject never keeps (d <= 0). f32, one rounded operation per step, no fused multiply-add
+ * (pipeline.filter_views restates it in numpy bit for bit):
+ *   candidate: d finite and depth_min <= d <= depth_max (0 = the defaults of md_points_opts); with a confidence map also
+ *     conf finite and >= 0.
+ *   percentile q = conf_percentile in 0..99, 0 = off (tau = 0): N = the candidates over all B views of the call,
+ *     k = ((int64)(N - 1) * q) / 100, tau = the k-th smallest candidate confidence counting from 0 (N = 0: tau = 0; -0
+ *     counts as +0). The selection is exact. A survivor is a candidate with conf >= tau; without a confidence map every
+ *     candidate survives and q must be 0.
+ *   cross-view support, view_rtol > 0: for a survivor (i, v, u) with depth d, X_w = the point md_op_unproject writes for it
+ *     with world = 1. For every other view j, ascending: p = R_j X_w + t_j, each coordinate ((Rk0 x + Rk1 y) + Rk2 z) + tk;
+ *     the view sees the point when p.z > 0 and, with uf = ((fx_j (p.x / p.z)) + cx_j) - off, uu = floorf(uf + 0.5f) (vf, vv
+ *     likewise), 0 <= uu < W and 0 <= vv < H compared in float; it supports the pixel when pixel (vv, uu) of view j is a
+ *     survivor with depth d_j and |p.z - d_j| <= view_rtol * min(p.z, d_j). support = the number of supporting views; the
+ *     pixel is kept when support >= min_views. view_rtol = 0: no test, support = 0, every survivor is kept. */
+typedef struct md_view_filter_opts {
+  float pixel_offset;         /* as md_points_opts */
+  float depth_min, depth_max; /* as md_points_opts: 0 = the default of that bound */
+  int conf_percentile;        /* q in 0..99: the lowest q % of the candidate confidences are dropped; 0 = off */
+  float view_rtol;            /* > 0: the cross-view test (needs extrinsics, 2 <= B <= 64); 0 = off */
+  int min_views;              /* 1 .. B-1 with view_rtol > 0; 0 with view_rtol = 0 */
+} md_view_filter_opts;
+typedef struct md_view_filter_outputs {
+  float* depth;          /* f32 [B,H,W]: d where kept, else 0; must not be the input. NULL = skip */
+  uint8_t* support;      /* u8 [B,H,W]: supporting views of a survivor, 0 elsewhere. NULL = skip */
+  float* conf_threshold; /* f32 [1]: tau. NULL = skip */
+  int32_t* kept;         /* int32 [B+1]: kept pixels per view, then their total. NULL = skip */
+} md_view_filter_outputs;
+
+/* everything 0: a pass-through of the candidates */
+void md_view_filter_opts_default(md_view_filter_opts* o);
+/* The stand-alone operator on caller tensors: every pointer (cameras included) is a device pointer; conf_dev may be NULL.
+ * cam is needed only with view_rtol > 0 (intrinsics or focal_px, and extrinsics). Everything is enqueued on `stream`; the
+ * call returns after the stream has drained, because its scratch is freed on return. Errors, before any launch: o / out
+ * NULL, every output NULL, out->depth == depth_dev, conf_percentile outside 0..99 or > 0 without conf_dev, view_rtol not
+ * finite or negative, min_views != 0 with view_rtol = 0, min_views < 1 or > B - 1 with view_rtol > 0, view_rtol > 0 without
+ * extrinsics or without intrinsics / focal_px, pixel_offset or a depth bound not finite (a bound negative, or
+ * depth_max < depth_min) -> MD_ERR_INVALID_ARG; B, H, W <= 0, B*H*W >= 2^31, B >= 65536, or with view_rtol > 0: B < 2,
+ * B > 64, H or W >= 2^24 -> MD_ERR_SHAPE (the shape is checked before min_views against B). */
+int md_op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_dev, int B, int H, int W,
+                       const md_points_cameras* cam, const md_view_filter_opts* o, const md_view_filter_outputs* out, void* stream);
+/* md_infer_points with the filter between the model and the unprojection: the filter reads the model's depth and
+ * confidence (dual head) and the cameras the unprojection uses (the model's own or the caller's); the filtered depth is
+ * what is unprojected and what out->depth receives. `o` applies afterwards, unchanged (conf_min on top of tau).
+ * fo->pixel_offset / depth_min / depth_max must equal o's. Graph replay, memory kinds and errors as md_infer_points',
+ * plus md_op_filter_views' (conf_percentile > 0 on a model without a confidence map, view_rtol > 0 where neither the
+ * model nor the caller has extrinsics -> MD_ERR_INVALID_ARG). After the first call of a shape nothing is allocated. */
+int md_infer_points_filtered(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                             const md_points_cameras* cam, const md_view_filter_opts* fo, const md_points_opts* o,
+                             const md_points_outputs* out, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

@@ -12,7 +12,8 @@ needs no resize).
 `--ply OUT.ply`: also writes the depth as a coloured point cloud (binary little-endian PLY), back-projected on the device in the
 same call as the inference (`md_infer_points`): Depth Pro with its predicted (or `--focal-px`) focal length in camera space,
 Depth-Anything-v3 `small` with its predicted intrinsics / extrinsics in world space. `--conf-min`, `--edge-rtol`, `--stride`
-filter the cloud (`md_points_opts`).
+filter the cloud (`md_points_opts`); `--conf-percentile Q` first drops the lowest Q % of the confidences on the device
+(`md_infer_points_filtered`; Depth-Anything-v3 `small`, whose confidence has no scale a caller could know in advance).
 
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
@@ -37,6 +38,7 @@ def main(argv=None) -> int:
     ap.add_argument("--on-device", action="store_true", help="prepare, infer and build the PNG's pixels in one device call (md_process_frame)")
     ap.add_argument("--ply", default="", help="write the point cloud of the prepared image to this .ply (md_infer_points)")
     ap.add_argument("--conf-min", type=float, default=0.0, help="--ply: keep pixels whose confidence is at least this (Depth-Anything-v3 small)")
+    ap.add_argument("--conf-percentile", type=int, default=0, help="--ply: drop the lowest this-many percent (0..99) of the confidences (Depth-Anything-v3 small)")
     ap.add_argument("--edge-rtol", type=float, default=0.0, help="--ply: drop pixels whose depth differs from a neighbour's by more than this ratio (0 = off)")
     ap.add_argument("--stride", type=int, default=1, help="--ply: keep every stride-th row and column")
     a = ap.parse_args(argv)
@@ -73,7 +75,7 @@ def main(argv=None) -> int:
         x = rgb_to_input_tensor(prep.rgb.tobytes(), prep.width, prep.height, model.model.device)
         try:
             pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
-                                    dense=False, conf_min=a.conf_min, edge_rtol=a.edge_rtol, stride=a.stride,
+                                    dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
                                     world=bool(getattr(model.model.config, "dual_head", False)))
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
