@@ -192,6 +192,17 @@ SYMBOLS = {
     "md_op_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "md_op_set_token0": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "md_op_border_bias_fix": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "md_op_layernorm_ex": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_P), C.POINTER(_P), C.c_float, _I, _I,
+                                C.c_float, _P, _I, _P, _P]),
+    "md_op_store_rows": (_I, [_P, _P, C.c_int64, _I, _I, _P, _P]),
+    "md_op_load_rows": (_I, [_P, _P, C.c_int64, _I, _I, _P, _P]),
+    "md_op_f32_to_fp8": (_I, [_P, _P, C.c_int64, C.c_float, _P, _P]),
+    "md_op_pack_fp8_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "md_op_nchw_to_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "md_op_nhwc_to_nchw": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "md_op_ln_fold_vectors": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "md_op_ln_finish": (_I, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
+    "md_op_conv2d_direct_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_fov_to_focal": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_op_focal_to_fov": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_bench_gemm": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F]),

@@ -990,6 +990,145 @@ int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int 
   return MD_OK;
 }
 
+// ---- the kernels that write MFMA operands, alone: the caller's buffers hold the stored bytes (no widened copy) ----
+namespace {
+size_t storage_bytes(int precision) { return esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1); }
+}  // namespace
+
+int md_op_layernorm_ex(md_device_t dev, float* x, int rows, int D, int S, int ngroups, const int* seq0, const int* nseq,
+                       const float* const* gamma, const float* const* beta, float eps, int precision, int out_f32, float fp8_inv_scale,
+                       const float* tok0, int tok0_stride, void* out, void* stream) {
+  if (!dev || !x || !out || !seq0 || !nseq || !gamma || !beta) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision) && precision != MD_PREC_FP8) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (rows <= 0 || D <= 0 || S <= 0 || tok0_stride < 0) MD_FAIL(MD_ERR_SHAPE, "layernorm_ex: rows=%d D=%d S=%d stride=%d", rows, D, S, tok0_stride);
+  if (ngroups < 1 || ngroups > 4) MD_FAIL(MD_ERR_INVALID_ARG, "layernorm_ex: %d groups (1..4)", ngroups);
+  SeqGroups g;
+  memset(&g, 0, sizeof(g));
+  g.ngroups = ngroups;
+  int next = 0;
+  for (int i = 0; i < ngroups; ++i) {  // consecutive sequence ranges from 0, as the engine builds them
+    if (seq0[i] != next || nseq[i] <= 0) MD_FAIL(MD_ERR_INVALID_ARG, "layernorm_ex: group %d = [%d, +%d) does not follow sequence %d", i, seq0[i], nseq[i], next);
+    if (gamma[i] && !beta[i]) MD_FAIL(MD_ERR_INVALID_ARG, "layernorm_ex: group %d has gamma but no beta", i);
+    g.seq0[i] = seq0[i]; g.nseq[i] = nseq[i]; g.a[i] = gamma[i]; g.b[i] = beta[i];
+    next += nseq[i];
+  }
+  if ((long)next * S < rows) MD_FAIL(MD_ERR_SHAPE, "layernorm_ex: %d sequences of %d rows do not cover %d rows", next, S, rows);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_layernorm(x, out, rows, D, eps, S, g, precision, out_f32, st, fp8_inv_scale, tok0, tok0_stride, tok0 ? x : nullptr));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_store_rows(md_device_t dev, const float* in, int64_t count, int width, int precision, void* out, void* stream) {
+  if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (count <= 0 || width < 0) MD_FAIL(MD_ERR_SHAPE, "store_rows: count=%lld width=%d", (long long)count, width);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_f32_to_rows(in, (long)count, out, precision, st, width));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_load_rows(md_device_t dev, const void* in, int64_t count, int width, int precision, float* out, void* stream) {
+  if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (count <= 0 || width < 0) MD_FAIL(MD_ERR_SHAPE, "load_rows: count=%lld width=%d", (long long)count, width);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_rows_to_f32(in, (long)count, out, precision, st, width));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_f32_to_fp8(md_device_t dev, const float* in, int64_t count, float inv_scale, void* out, void* stream) {
+  if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (count <= 0) MD_FAIL(MD_ERR_SHAPE, "f32_to_fp8: count=%lld", (long long)count);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_f32_to_fp8(in, (long)count, inv_scale, out, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_pack_fp8_rows(md_device_t dev, const float* w, int N, int K, int Kp, void* out, float* scale, void* stream) {
+  if (!dev || !w || !out || !scale) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (N <= 0 || K <= 0) MD_FAIL(MD_ERR_SHAPE, "pack_fp8_rows: N=%d K=%d", N, K);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_pack_fp8_rows(w, N, K, Kp, out, scale, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_nchw_to_nhwc(md_device_t dev, const float* in, int B, int C, int H, int W, int precision, int relu, int ld, void* out,
+                       void* stream) {
+  if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ld < 0) MD_FAIL(MD_ERR_SHAPE, "nchw_to_nhwc: [%d,%d,%d,%d] ld=%d", B, C, H, W, ld);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_nchw_to_nhwc(in, B, C, H, W, out, precision, relu ? 1 : 0, st, ld));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_nhwc_to_nchw(md_device_t dev, const void* in, int B, int C, int H, int W, int ld, int coff, int precision, float* out,
+                       void* stream) {
+  if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "nhwc_to_nchw: [%d,%d,%d,%d]", B, C, H, W);
+  if (coff < 0 || ld < coff + C) MD_FAIL(MD_ERR_INVALID_ARG, "nhwc_to_nchw: channels [%d, %d) outside a pixel of %d", coff, coff + C, ld);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_nhwc_to_nchw(in, B, C, H, W, ld, coff, out, precision, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_ln_fold_vectors(md_device_t dev, const float* w, const float* gamma, const float* beta, const float* bias, int N, int K,
+                          int precision, float* c, float* d, void* stream) {
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_ln_fold_vectors(w, gamma, beta, bias, N, K, precision, c, d, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_ln_finish(md_device_t dev, const float* parts, int64_t rows, float inv_n, float eps, float* ab, void* stream) {
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_ln_finish(parts, ab, (long)rows, inv_n, eps, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* add_dev, int B,
+                           int Cin, int H, int W, int Cout, int k, int stride, int pad, int relu, int in_precision, int out_ld,
+                           float* out_dev, void* stream) {
+  if (!dev || !x_dev || !w_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (!token_op_prec(in_precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", in_precision);
+  if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0) MD_FAIL(MD_ERR_SHAPE, "invalid shape");
+  if (H + 2 * pad < k || W + 2 * pad < k) MD_FAIL(MD_ERR_SHAPE, "input %dx%d smaller than kernel %d", H, W, k);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  DevBuf xa, wa;
+  MD_TRY(xa.alloc((size_t)B * H * W * Cin * storage_bytes(in_precision)));
+  MD_TRY(wa.alloc((size_t)Cout * k * k * Cin * 4));
+  MD_TRY(launch_nchw_to_nhwc(x_dev, B, Cin, H, W, xa.p, in_precision, 0, st));
+  PackEntry e;
+  e.kind = PACK_DIRECT; e.d0 = Cout; e.d1 = Cin; e.k = k; e.kp = Cin; e.f32 = 1; e.dst = wa.p;
+  MD_TRY(pack_weight(w_dev, e, MD_PREC_F32, st));
+  MD_TRY(launch_conv_direct(xa.p, in_precision, add_dev, B, H, W, Cin, (const float*)wa.p, bias_dev, Cout, k, stride, pad, relu, out_dev, st,
+                            out_ld));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad) {
   if (H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid image size");
   fov_scalar_host(fovx_deg, H, W, focal_px, fovy_rad);

@@ -255,6 +255,127 @@ def border_bias_fix(dev: Device, fmap: torch.Tensor, C_: int, bias9: torch.Tenso
     return fmap
 
 
+# ---- the kernels that write MFMA operands, alone: outputs are the STORED bytes (bf16 / f16 / fp32 tensors, split-half rows as f16
+# [.., 2 * width] = hi | lo, e4m3 as uint8) ----
+_RAW_DTYPE = {0: torch.bfloat16, 1: torch.float32, 2: torch.uint8, 3: torch.float16, 4: torch.float16}
+
+
+def _raw_empty(shape, width: int, precision: int, device) -> torch.Tensor:
+    """Storage rows of logical shape [..., width]."""
+    return torch.empty((*shape, width * (2 if precision == 4 else 1)), dtype=_RAW_DTYPE.get(precision, torch.uint8), device=device)
+
+
+def layernorm_ex(dev: Device, x: torch.Tensor, S: int, groups, eps: float, precision: int, out_f32: bool = False,
+                 fp8_inv_scale: float = 1.0, tok0: Optional[torch.Tensor] = None, tok0_stride: int = 0):
+    """md_op_layernorm_ex: x [rows, D]; groups = [(seq0, nseq, gamma or None, beta or None), ...] -> (raw output rows, the rewritten
+    copy of x when tok0 is given, else None)."""
+    x = _f32c(x).clone()
+    rows, D = x.shape
+    n = len(groups)
+    keep = [(None if g is None else _f32c(g), None if b is None else _f32c(b)) for _, _, g, b in groups]
+    seq0, nseq = (C.c_int * n)(*[int(g[0]) for g in groups]), (C.c_int * n)(*[int(g[1]) for g in groups])
+    ga = (C.c_void_p * n)(*[t[0].data_ptr() if t[0] is not None else None for t in keep])
+    be = (C.c_void_p * n)(*[t[1].data_ptr() if t[1] is not None else None for t in keep])
+    if tok0 is not None:
+        tok0 = _f32c(tok0)
+        assert tok0.numel() >= ((rows + S - 1) // S - 1) * tok0_stride + D, "tok0 is shorter than the sequences read from it"
+    out = torch.empty((rows, D), dtype=torch.float32, device=x.device) if out_f32 else _raw_empty((rows,), D, precision, x.device)
+    _lib.check(_lib.load().md_op_layernorm_ex(dev.handle, _p(x), rows, D, S, n, seq0, nseq, ga, be, C.c_float(eps), precision, int(out_f32),
+                                              C.c_float(fp8_inv_scale), _p(tok0), tok0_stride, _p(out), _stream_ptr(dev.ordinal)))
+    del keep
+    return out, (x if tok0 is not None else None)
+
+
+def store_rows(dev: Device, x: torch.Tensor, width: int, precision: int) -> torch.Tensor:
+    """md_op_store_rows: fp32 [count] -> raw rows [count / width, width] of the storage type."""
+    x = _f32c(x).reshape(-1)
+    out = _raw_empty((x.numel() // max(width, 1),), width, precision, x.device) if width else _raw_empty((), x.numel(), precision, x.device)
+    _lib.check(_lib.load().md_op_store_rows(dev.handle, _p(x), x.numel(), width, precision, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def load_rows(dev: Device, raw: torch.Tensor, count: int, width: int, precision: int) -> torch.Tensor:
+    """md_op_load_rows: raw storage -> fp32 [count]."""
+    assert raw.is_cuda and raw.is_contiguous() and raw.dtype == _RAW_DTYPE[precision] and raw.numel() == count * (2 if precision == 4 else 1)
+    out = torch.empty(count, dtype=torch.float32, device=raw.device)
+    _lib.check(_lib.load().md_op_load_rows(dev.handle, _p(raw), count, width, precision, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def f32_to_fp8(dev: Device, x: torch.Tensor, inv_scale: float) -> torch.Tensor:
+    """md_op_f32_to_fp8: e4m3 bytes (uint8) of clamp(x * inv_scale, +-448)."""
+    x = _f32c(x)
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().md_op_f32_to_fp8(dev.handle, _p(x), x.numel(), C.c_float(inv_scale), _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def pack_fp8_rows(dev: Device, w: torch.Tensor, Kp: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """md_op_pack_fp8_rows: w [N, K] -> (e4m3 bytes [N, Kp] uint8, scale [N])."""
+    w = _f32c(w)
+    N, K = w.shape
+    out = torch.full((N, max(Kp, 0)), 0x55, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    _lib.check(_lib.load().md_op_pack_fp8_rows(dev.handle, _p(w), N, K, Kp, _p(out), _p(scale), _stream_ptr(dev.ordinal)))
+    return out, scale
+
+
+def nchw_to_nhwc(dev: Device, x: torch.Tensor, precision: int, relu: bool, ld: int, out: torch.Tensor) -> torch.Tensor:
+    """md_op_nchw_to_nhwc into a copy of the pre-filled raw buffer `out` [B, H, W, ld (x 2 for split-half)]."""
+    x, out = _f32c(x), out.contiguous().clone()
+    B, Cn, H, W = x.shape
+    assert out.is_cuda and out.dtype == _RAW_DTYPE[precision] and out.numel() == B * H * W * (ld or Cn) * (2 if precision == 4 else 1)
+    _lib.check(_lib.load().md_op_nchw_to_nhwc(dev.handle, _p(x), B, Cn, H, W, precision, int(relu), ld, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def nhwc_to_nchw(dev: Device, raw: torch.Tensor, Cn: int, ld: int, coff: int, precision: int) -> torch.Tensor:
+    """md_op_nhwc_to_nchw: raw [B, H, W, ld (x 2 for split-half)], channels coff .. coff + Cn -> fp32 [B, Cn, H, W]."""
+    assert raw.is_cuda and raw.is_contiguous() and raw.dtype == _RAW_DTYPE[precision] and raw.shape[3] == ld * (2 if precision == 4 else 1)
+    B, H, W, _ = raw.shape
+    out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=raw.device)
+    _lib.check(_lib.load().md_op_nhwc_to_nchw(dev.handle, _p(raw), B, Cn, H, W, ld, coff, precision, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def ln_fold_vectors(dev: Device, w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Optional[torch.Tensor],
+                    precision: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """md_op_ln_fold_vectors: w [N, K] -> (c [N], d [N])."""
+    w, gamma, beta = _f32c(w), _f32c(gamma), _f32c(beta)
+    bias = _f32c(bias) if bias is not None else None
+    N, K = w.shape
+    c, d = torch.empty(N, dtype=torch.float32, device=w.device), torch.empty(N, dtype=torch.float32, device=w.device)
+    _lib.check(_lib.load().md_op_ln_fold_vectors(dev.handle, _p(w), _p(gamma), _p(beta), _p(bias), N, K, precision, _p(c), _p(d),
+                                                 _stream_ptr(dev.ordinal)))
+    return c, d
+
+
+def ln_finish(dev: Device, parts: torch.Tensor, inv_n: float, eps: float) -> torch.Tensor:
+    """md_op_ln_finish: parts [rows, 4, 2] -> ab [rows, 2]."""
+    parts = _f32c(parts)
+    rows = parts.shape[0]
+    assert parts.shape == (rows, 4, 2)
+    ab = torch.empty((rows, 2), dtype=torch.float32, device=parts.device)
+    _lib.check(_lib.load().md_op_ln_finish(dev.handle, _p(parts), rows, C.c_float(inv_n), C.c_float(eps), _p(ab), _stream_ptr(dev.ordinal)))
+    return ab
+
+
+def conv2d_direct_ex(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor], stride: int,
+                     pad: int, relu: bool, in_precision: int, out_ld: int, out: torch.Tensor) -> torch.Tensor:
+    """md_op_conv2d_direct_ex: x [B, Cin, H, W], w [Cout, Cin, k, k], add fp32 NHWC or None -> a copy of the pre-filled fp32
+    `out` [B, OH, OW, out_ld or Cout] with the first Cout columns of every pixel written."""
+    x, w, out = _f32c(x), _f32c(w), _f32c(out).clone()
+    B, Cin, H, W = x.shape
+    Cout, _, k, _ = w.shape
+    OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    assert out.shape == (B, OH, OW, out_ld or Cout) and (add is None or add.shape == (B, H, W, Cin))
+    add = _f32c(add) if add is not None else None
+    bias = _f32c(bias) if bias is not None else None
+    _lib.check(_lib.load().md_op_conv2d_direct_ex(dev.handle, _p(x), _p(w), _p(bias), _p(add), B, Cin, H, W, Cout, k, stride, pad, int(relu),
+                                                  in_precision, out_ld, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
 def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None, focal_px=None, conf: Optional[torch.Tensor] = None,
               rgb: Optional[torch.Tensor] = None, dense: bool = True, compact: bool = True, capacity: Optional[int] = None,
               out: Optional[PointCloud] = None, **opts) -> PointCloud:

@@ -598,6 +598,41 @@ int md_op_set_token0(md_device_t dev, float* x, int nseq, int S, int D, const fl
 /* Adds bias9[class] - bias9[4] to the border pixels of the NHWC map [B,H,W,ld] (columns 0 .. C-1; in place), bias9 [9, C]. */
 int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int C, int ld, const float* bias9, int precision,
                           void* stream);
+/* ---- the kernels that write MFMA operands, alone (test-only). Every output buffer is the caller's device memory and receives the
+ * STORED bytes of `precision`'s storage type -- bf16, f16, fp32, split-half rows [hi: width | lo: width] of f16, e4m3 bytes --, no
+ * widened copy, so a test can compare roundings bit for bit. Each call synchronises its stream before it returns. ---- */
+/* The engine's LayerNorm launch: x [rows, D] fp32, sequences of S rows, `ngroups` (1..4) consecutive sequence ranges
+ * [seq0[i], seq0[i] + nseq[i]) with their own gamma[i] / beta[i] (host arrays of device pointers; gamma[i] NULL = non-affine).
+ * out: rows of `precision` (MD_PREC_FP8: e4m3 bytes of value * fp8_inv_scale, saturating), or fp32 when out_f32. tok0 != NULL: row 0 of
+ * every sequence is first replaced by tok0[seq * tok0_stride .. + D] and written back into x. D % 4 != 0 or D > 1024 -> MD_ERR_UNSUPPORTED. */
+int md_op_layernorm_ex(md_device_t dev, float* x, int rows, int D, int S, int ngroups, const int* seq0, const int* nseq,
+                       const float* const* gamma, const float* const* beta, float eps, int precision, int out_f32, float fp8_inv_scale,
+                       const float* tok0, int tok0_stride, void* out, void* stream);
+/* fp32 [count] -> storage rows (width = logical row width; MD_PREC_F16X2 needs it and count % width == 0), and back. */
+int md_op_store_rows(md_device_t dev, const float* in, int64_t count, int width, int precision, void* out, void* stream);
+int md_op_load_rows(md_device_t dev, const void* in, int64_t count, int width, int precision, float* out, void* stream);
+/* out[i] = e4m3(clamp(in[i] * inv_scale, +-448)); count % 4 == 0. */
+int md_op_f32_to_fp8(md_device_t dev, const float* in, int64_t count, float inv_scale, void* out, void* stream);
+/* w [N, K] fp32 -> e4m3 [N, Kp] (columns K .. Kp zero; Kp % 4 == 0) and scale [N] = amax_n / 448 (1 for an all-zero row). */
+int md_op_pack_fp8_rows(md_device_t dev, const float* w, int N, int K, int Kp, void* out, float* scale, void* stream);
+/* fp32 NCHW -> storage NHWC with `ld` logical elements per pixel (0 = C; split-half pixels are [hi: ld | lo: ld]); columns C .. ld of
+ * `out` are not written. relu: max(v, 0) first. */
+int md_op_nchw_to_nhwc(md_device_t dev, const float* in, int B, int C, int H, int W, int precision, int relu, int ld, void* out,
+                       void* stream);
+/* storage NHWC with `ld` elements per pixel, channels coff .. coff + C -> fp32 NCHW [B, C, H, W]. */
+int md_op_nhwc_to_nchw(md_device_t dev, const void* in, int B, int C, int H, int W, int ld, int coff, int precision, float* out,
+                       void* stream);
+/* The vectors of a LayerNorm folded into the linear layer behind it: c[n] = sum_k gamma[k] Wr[n][k], d[n] = bias[n] + sum_k beta[k] Wr[n][k],
+ * Wr = w [N, K] as `precision`'s operand holds it; bias may be NULL. */
+int md_op_ln_fold_vectors(md_device_t dev, const float* w, const float* gamma, const float* beta, const float* bias, int N, int K,
+                          int precision, float* c, float* d, void* stream);
+/* parts [rows][4][2] = (mean, centred sum of squares) of four 256-column tiles -> ab [rows][2] = (rstd, -mu * rstd). */
+int md_op_ln_finish(md_device_t dev, const float* parts, int64_t rows, float inv_n, float eps, float* ab, void* stream);
+/* md_op_conv2d_direct as the FOV head runs it: the input held in `in_precision`'s storage type, add = optional fp32 NHWC tensor added
+ * to the input, out = fp32 NHWC [B, OH, OW, out_ld] (out_ld 0 = Cout; columns Cout .. out_ld are not written). */
+int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* add_dev, int B,
+                           int Cin, int H, int W, int Cout, int k, int stride, int pad, int relu, int in_precision, int out_ld,
+                           float* out_dev, void* stream);
 /* `fovy_from_fovx_rad` (mod.rs:370-414) + focal length (mod.rs:330-336) on host scalars. */
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad);
 /* The reverse, on host scalars: a focal length f_px (pixels of the W-wide image) -> fovx_deg = 2 atan(W / (2 f_px)) in

@@ -49,16 +49,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import close_check
+from close_check import A_LN, A_MFMA, BF16, F16, F16X2, F32, PNAME, PRECS, ROUND, near_boundary, rejects, ulp_T  # noqa: F401
 from oracle import da3_ref
-from oracle.depth_pro_ref import f16x2_round
 
-BF16, F32, F16, F16X2 = 0, 1, 3, 4
-PRECS = [BF16, F16, F32, F16X2]
-PNAME = {BF16: "bf16", F32: "f32", F16: "f16", F16X2: "f16x2"}
-ROUND = {BF16: lambda t: t.bfloat16().float(), F32: lambda t: t, F16: lambda t: t.half().float(), F16X2: f16x2_round}
-SIG_BITS = {BF16: 8, F16: 11, F16X2: 22}
-ULP_FLOOR = {BF16: 2.0 ** -133, F16: 2.0 ** -24, F16X2: 2.0 ** -24}
-A_MFMA, A_LN = 2e-5, 2e-6
+assert_close_in = functools.partial(close_check.assert_close_in, tag="da3_token_ops")
 ATTN_QSCALE = 0.125 * 1.4426950408889634
 ROPE_BASE, QK_EPS = 100.0, 1e-5
 TILE_128x64, TILE_64x64, TILE_256x256 = 3, 4, 0
@@ -66,55 +61,6 @@ TILE_128x64, TILE_64x64, TILE_256x256 = 3, 4, 0
 
 def qscale_of(prec):
     return 1.0 if prec == F32 else ATTN_QSCALE
-
-
-# ---------------------------------------------------------------------------------------------
-# the checker
-# ---------------------------------------------------------------------------------------------
-def ulp_T(a, prec):
-    """Spacing of the storage type at magnitude a (fp64 tensor, >= 0); zeros for f32 (the term is absent)."""
-    if prec == F32:
-        return torch.zeros_like(a)
-    _, ex = torch.frexp(a.clamp_min(1e-300))  # a = m * 2^ex, m in [0.5, 1)
-    return torch.ldexp(torch.ones_like(a), ex - SIG_BITS[prec]).clamp_min(ULP_FLOOR[prec])
-
-
-def near_boundary(v, prec, dist):
-    """True where v lies within `dist` of a rounding boundary (the midpoint of two neighbouring values) of T."""
-    if prec == F32:
-        return torch.zeros_like(v, dtype=torch.bool)
-    u = ulp_T(v.abs(), prec)
-    t = v.abs() / u
-    return ((t - t.floor()) - 0.5).abs() * u <= dist
-
-
-def close_report(got, ref64, prec, a32, extra=None):
-    ref, got = ref64.double(), got.double()
-    A = a32 * ref.abs().max()
-    u = ulp_T(ref.abs(), prec)
-    err = (got - ref).abs()
-    plain = 0.5 * u + A
-    bound = plain + 0.5 * u * near_boundary(ref, prec, A)
-    if extra is not None:
-        bound = bound + extra
-    ratio = err / bound
-    return {"max_err": err.max().item(), "bound_at_max": bound.flatten()[err.argmax()].item(), "worst_ratio": ratio.max().item(),
-            "n_bad": int((err > bound).sum()), "slack_share": (err > plain).double().mean().item(), "n": err.numel()}
-
-
-def assert_close_in(got, ref64, prec, a32, extra=None, what=""):
-    assert torch.isfinite(got).all(), f"{what}: non-finite values"
-    r = close_report(got, ref64, prec, a32, extra)
-    print(f"[da3_token_ops] {what} {PNAME[prec]}: max err {r['max_err']:.3e} (bound there {r['bound_at_max']:.3e}), "
-          f"worst err/bound {r['worst_ratio']:.3f}, slack users {r['slack_share']:.2e}")
-    assert r["n_bad"] == 0, f"{what} {PNAME[prec]}: {r['n_bad']} of {r['n']} elements outside the bound, worst err/bound {r['worst_ratio']:.3f}"
-    assert r["slack_share"] < 0.01, f"{what} {PNAME[prec]}: {r['slack_share']:.3%} of the elements need the tie slack"
-    return r
-
-
-def rejects(got, ref64, prec, a32):
-    r = close_report(got, ref64, prec, a32)
-    return r["n_bad"] > 0 or r["slack_share"] >= 0.01
 
 
 # ---------------------------------------------------------------------------------------------
