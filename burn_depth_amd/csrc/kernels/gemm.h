@@ -91,7 +91,7 @@ struct GemmParams {
   const void* res1 = nullptr;   // optional residual inputs, element type T
   const void* res2 = nullptr;
   long ldr = 0;
-  // ---- LayerNorm folded into the GEMMs on either side of it (round 6; the 256 x 256 kernel's EK 5 / 6 / 7, dense A, 16-bit operands) ----
+  // ---- LayerNorm folded into the GEMMs on either side of it (round 6; the 256 x 256 kernel's kinds EK_RMW_LN / EK_QKV_LN / EK_GELU_LN, dense A, 16-bit operands) ----
   // LN(x) W^T + b  =  rstd_m * (round(gamma . x) W^T  -  mu_m * c)  +  d,   c[n] = sum_k gamma[k] W[n][k],  d[n] = b[n] + sum_k beta[k] W[n][k]:
   // the PRODUCER of x (EPI_RESID_LS: proj / fc2) also writes round_T(gamma_next . x_new) as the next GEMM's A operand and, per row and
   // 256-column tile, (sum x, sum x^2) of x_new in fp32; the CONSUMER (qkv / fc1) finishes its accumulators with the row's mu / rstd. The
@@ -106,14 +106,14 @@ struct GemmParams {
   int ln_parts = 0;
   float ln_inv_n = 0.f, ln_eps = 0.f;
   const float* ln_c[kMaxGroups] = {nullptr, nullptr, nullptr, nullptr};      // consumer: c [N] (bias[] then carries d)
-  // 256 x 256 kernel, lean 2-byte store kinds (EK 2 / 4 / 6 / 7, no residual inputs / second output): stores straight from the accumulator
+  // 256 x 256 kernel, lean 2-byte store kinds (EK_STORE / EK_GELU / EK_QKV_LN / EK_GELU_LN, no residual inputs / second output): stores straight from the accumulator
   // layout, no LDS staging. The W tile's LDS image is filled in a PERMUTED row order (the LDS-DMA source rows; LDS addressing, bank
   // pattern and register use unchanged) such that a lane's accumulators of the n-blocks 2h, 2h + 1 are 8 CONSECUTIVE output columns: one
   // 16-byte store per (m-block, h), 16 rows x 64 bytes per wave-instruction, the two h of a row completing its 128-byte line back to
   // back. Same values, same bits as the staged form. Set by launch_gemm for eligible launches (gemm_direct_store()).
   int direct_store = 0;
   int persist = 0;   // set by launch_gemm (gemm_persistent()): which forms may run as persistent tile loops (1 fc1, 2 QKV, 8 3 x 3 convolutions -- lean: gemm256p_kernel, with residual inputs / second output: gemm256r_kernel; 4 read-modify-write: gemm256r_kernel)
-  int ptiles = 0;    // persistent form: tiles of the launch (set by launch_256)
+  int ptiles = 0;    // persistent form: tiles of the launch (set by launch_256 from gemm256_form)
   int stagger = 0;   // read-modify-write tile loop: the odd workgroups of every XCD start this many 10-ns ticks late (gemm_stagger(); set by launch_256 per k-tile count)
   int ksplit_ok = 0;            // set by launch_gemm from gemm_allow_ksplit(): the 64 x 64 kernel may split K over wave groups (KSPLIT)
   int res_mod = 0;              // > 0: res1's row = m % res_mod (a per-image table shared by the batch, or an input two weight groups share); res2 is never wrapped
@@ -193,6 +193,47 @@ struct KsplitScope {
  private:
   int prev_;
 };
+
+// ---- the 256 x 256 kernel: epilogue kinds and the choice of its form ------------------------------------------------------
+// Epilogue kinds = the EK template argument of gemm256_kernel. The VALUES are part of the kernels' symbol names (profiles and
+// bench.py match `gemm256_kernel<bf16_t, 0, 9, false>`): they stay plain ints and keep their numbers.
+constexpr int EK_GENERIC = 0;      // epilogue4 per vector: everything the kinds below do not take
+constexpr int EK_RMW = 1;          // read-modify-write residual x += scale * (acc + bias)  (EPI_RESID_LS: proj, fc2)
+constexpr int EK_STORE = 2;        // 2-byte store, optional residual inputs / second output (EPI_STORE; q | k | V^T of EPI_QKV)
+constexpr int EK_PIXSHUF = 3;      // pixel shuffle (EPI_PIXSHUF)
+constexpr int EK_GELU = 4;         // EK_STORE with the GELU fused at compile time (fc1)
+constexpr int EK_RMW_LN = 5;       // EK_RMW + the LayerNorm fold's producer part (operand of the next GEMM, row statistics)
+constexpr int EK_QKV_LN = 6;       // EK_STORE of EPI_QKV + the fold's consumer part
+constexpr int EK_GELU_LN = 7;      // EK_GELU + the fold's consumer part
+constexpr int EK_STORE_DS = 8;     // the direct-store forms (GemmParams::direct_store) of EK_STORE ..
+constexpr int EK_GELU_DS = 9;      // .. EK_GELU ..
+constexpr int EK_QKV_LN_DS = 10;   // .. EK_QKV_LN ..
+constexpr int EK_GELU_LN_DS = 11;  // .. EK_GELU_LN
+
+enum Family256 : int {
+  F256_ONE_TILE = 0,  // gemm256_kernel<T, AMODE, ek, diag>: one workgroup per tile
+  F256_LOOP_P = 1,    // gemm256p_kernel<T, fold, qkv, conv>: tile loop of fc1 / the QKV projection / the lean 3 x 3 convolution
+  F256_LOOP_R = 2     // gemm256r_kernel<T, fold, conv>: tile loop of the read-modify-write GEMMs / the 3 x 3 convolution with residuals
+};
+
+// What a 256 x 256 launch runs: the kernel instantiation (family, kind, boolean template arguments), its grid and the
+// launcher-set parameters of the tile loops. err != MD_OK: the launch is refused (the message goes to gemm256_form's why_not).
+struct Form256 {
+  int family = F256_ONE_TILE;
+  int ek = EK_GENERIC;  // one-tile: the kernel's EK; tile loops: the kind of the one-tile kernel they replace
+  bool fold = false;    // gemm256p's FOLD / gemm256r's EMIT: the LayerNorm fold's consumer / producer part
+  bool qkv = false;     // gemm256p's QKV (the staged q | k | V^T store; the lean convolution runs on it as well)
+  bool conv = false;    // gemm256p's CONV / gemm256r's CONVR: implicit 3 x 3 GEMM
+  bool diag = false;    // gemm256_kernel's DIAG (md_bench_gemm: stamps / ablation flags)
+  long blocks = 0;      // 256 x 256 tiles of the launch (0: nothing to launch)
+  int grid = 0;         // workgroups (grid.x): blocks, or the tile loops' cus rounded down to a multiple of 8 (at least 8)
+  int ptiles = 0;       // tile loops: GemmParams::ptiles
+  int stagger = 0;      // tile loops: GemmParams::stagger
+  int err = MD_OK;
+};
+// THE place a 256 x 256 launch's kernel is chosen (launch_256 only maps the result to an instantiation). Pure host code: no HIP
+// call, `cus` = the device's CU count. `p` as launch_gemm hands it to the launcher (direct_store, persist, ps_fast set).
+Form256 gemm256_form(const GemmParams& p, int amode, int prec, int cus, std::string* why_not = nullptr);
 
 enum GemmTile : int { TILE_256x256 = 0, TILE_128x128 = 1, TILE_256x32 = 2, TILE_128x64 = 3, TILE_64x64 = 4, TILE_AUTO = 99 };
 

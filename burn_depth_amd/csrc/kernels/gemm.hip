@@ -80,6 +80,137 @@ static std::atomic<long long> g_ksplit_launches{0};
 void gemm_count_ksplit_launch() { g_ksplit_launches.fetch_add(1, std::memory_order_relaxed); }
 long long gemm_ksplit_launches() { return g_ksplit_launches.load(std::memory_order_relaxed); }
 
+// ---- the form of a 256 x 256 launch -----------------------------------------------------------------------------------------
+static Form256 refuse(Form256 f, std::string* why_not, int code, const char* fmt, ...) __attribute__((format(printf, 4, 5)));
+static Form256 refuse(Form256 f, std::string* why_not, int code, const char* fmt, ...) {
+  if (why_not) {
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    *why_not = buf;
+  }
+  f.err = code;
+  return f;
+}
+
+// What every persistent tile loop needs: enough tiles to give each CU several, and a k-tile count (of 64 elements: the loops are
+// built for the 2-byte operand types) that leaves ring slot 4 idle in the last k-tile -- the epilogue's operands land there (16, 32, 64;
+// not 3, 8, 48, 128).
+static bool loop_ok(long blocks, int KT, long min_tiles) { return blocks >= min_tiles && KT >= 3 && (2 * KT - 2) % 5 != 4 && (2 * KT - 1) % 5 != 4; }
+
+Form256 gemm256_form(const GemmParams& p, int amode, int prec, int cus, std::string* why_not) {
+  constexpr int BM = 256, BN = 256;
+  const bool fp8 = prec == MD_PREC_FP8, split = prec == MD_PREC_F16X2, bf16 = prec == MD_PREC_BF16;
+  const bool out2b = prec != MD_PREC_F32;  // 2-byte outputs / residuals (fp8 operands: bf16)
+  Form256 f;
+  if (fp8 && amode != A_DENSE) return refuse(f, why_not, MD_ERR_UNSUPPORTED, "fp8 operands are built for dense GEMMs only");
+  long tiles_m = 0;
+  for (int g = 0; g < p.ngroups; ++g) tiles_m += cdiv(p.g_rows[g], BM);
+  const long blocks = tiles_m * cdiv(p.N, BN);
+  if (blocks <= 0) return f;
+  if (blocks > 0x7fffffffL) return refuse(f, why_not, MD_ERR_UNSUPPORTED, "gemm: too many tiles (%ld)", blocks);
+  f.blocks = blocks;
+  f.grid = (int)blocks;
+
+  // ---- the epilogue kind from the runtime parameters ----
+  const bool ln_prod = p.ln_out != nullptr, ln_cons = p.ln_stats != nullptr;
+  if (ln_prod || ln_cons) {  // the LayerNorm fold exists for the dense 16-bit forms of the 256 x 256 kernel only: refuse anything else loudly
+    if (amode != A_DENSE || !out2b || fp8 || p.N % BN != 0 || p.batch > 1)
+      return refuse(f, why_not, MD_ERR_UNSUPPORTED, "gemm: the LayerNorm fold needs dense 16-bit operands and N %% 256 == 0 (N=%d)", p.N);
+    if (ln_prod && (p.epi != EPI_RESID_LS || !p.ln_stats_out || p.ln_parts != p.N / BN || !p.ln_gamma[0] || p.ln_ldo % 4 != 0))
+      return refuse(f, why_not, MD_ERR_INVALID_ARG, "gemm: LayerNorm-fold producer parameters");
+    if (ln_cons && (!p.ln_c[0] || !p.bias[0] || p.wscale[0] || p.res1 || p.res2 || p.out2 || p.out_f32 || p.out_fp8 ||
+                    !((p.epi == EPI_QKV && p.embed % BN == 0) || (p.epi == EPI_STORE && p.act == ACT_GELU && p.res_mod == 0))))
+      return refuse(f, why_not, MD_ERR_INVALID_ARG, "gemm: LayerNorm-fold consumer parameters");
+  }
+  int ek = EK_GENERIC;
+  if (p.epi == EPI_RESID_LS) ek = ln_prod ? EK_RMW_LN : EK_RMW;
+  else if (p.epi == EPI_PIXSHUF) ek = EK_PIXSHUF;
+  else if (out2b) {
+    const long ldo_e = p.epi == EPI_QKV ? 2L * p.embed : p.ldo;
+    const bool vec8 = p.N % 8 == 0 && ldo_e % 8 == 0 && (!(p.res1 || p.res2) || p.ldr % 8 == 0);
+    // split-half outputs take the store kinds only when both planes can be stored in 16-byte vectors (no fp32 / fp8 output) and,
+    // for q | k tiles, when a tile cannot straddle the q | k sections of the [q_hi | q_lo | k_hi | k_lo] rows
+    const bool split_ok = !split || (!p.out_f32 && !p.out_fp8 && p.o_plane % 8 == 0 && (!(p.res1 || p.res2) || p.r_plane % 8 == 0) &&
+                                     (p.epi != EPI_QKV || p.embed % BN == 0));
+    if (!split_ok) ek = EK_GENERIC;
+    else if (vec8 && p.epi == EPI_STORE && p.res_mod == 0 && p.act == ACT_GELU) ek = ln_cons ? EK_GELU_LN : EK_GELU;
+    else if (vec8 && ((p.epi == EPI_STORE && p.res_mod == 0 && p.act != ACT_GELU) || (p.epi == EPI_QKV && (2 * p.embed) % BN == 0)))
+      ek = (ln_cons && p.epi == EPI_QKV) ? EK_QKV_LN : EK_STORE;
+    if (ln_cons && ek != EK_QKV_LN && ek != EK_GELU_LN)
+      return refuse(f, why_not, MD_ERR_UNSUPPORTED, "gemm: the LayerNorm-fold consumer needs the 16-byte store epilogue (N, ldo %% 8 == 0)");
+  }
+  f.ek = ek;
+  const bool diag = p.stamps != nullptr || p.debug_flags != 0;
+  // a lean store launch: one 2-byte output, whole tiles in n, no batch
+  const bool lean = !p.res1 && !p.res2 && !p.out2 && !p.out_f32 && !p.out_fp8 && p.N % BN == 0 && p.batch <= 1;
+
+  // ---- the persistent tile loops (GemmParams::persist): 2-byte operand types, a bias vector to request, no weight scales ----
+  if (out2b && !fp8 && !diag && !p.wscale[0] && p.bias[0]) {
+    const int KT = p.K / 64;
+    auto loop = [&](int family, bool fold, bool qkv, bool conv, int stagger_slot) {
+      f.family = family, f.fold = fold, f.qkv = qkv, f.conv = conv;
+      f.grid = cus >= 8 ? (cus & ~7) : 8;  // (a multiple of 8: XCD x = blocks x, x + 8, ..; more workgroups than CUs only costs residency)
+      f.ptiles = (int)blocks;
+      // (the start offset is idle time at either end of the launch: 8 rounds of tiles and more)
+      f.stagger = stagger_slot >= 0 && blocks >= 2048 ? gemm_stagger_ticks(stagger_slot) : 0;
+      return f;
+    };
+    if (amode == A_CONV3 && !split) {
+      // the implicit 3 x 3 GEMM with bias and optional ReLU, one weight group, one 256-column tile in n (persist bit 8)
+      const bool conv_ok = (p.persist & 8) && ek == EK_STORE && p.epi == EPI_STORE && p.ngroups <= 1 && p.a_wrap == 0 && loop_ok(blocks, KT, 1024) &&
+                           p.N == BN && (p.act == ACT_NONE || p.act == ACT_RELU);
+      // lean (the first convolution of the decoder's residual units): the tile loop of the q | k form
+      if (conv_ok && lean) return loop(F256_LOOP_P, false, true, true, -1);
+      // residual inputs and / or a relu'd second output (the second convolution of a residual unit: x + conv2(..) [+ skip], and its
+      // relu'd copy for the next unit): the read-modify-write loop's skeleton, 32-row staging passes
+      if (conv_ok && !lean && (p.res1 || p.res2 || p.out2) && !p.out_f32 && !p.out_fp8 && p.batch <= 1) return loop(F256_LOOP_R, false, false, true, -1);
+    }
+    if (amode == A_DENSE) {
+      // fc1 (persist bit 1): the direct-store GELU kinds; the fold's consumer part reads the producer's raw partials
+      if ((p.persist & 1) && p.direct_store && lean && (ek == EK_GELU || (ek == EK_GELU_LN && p.ln_raw)) && loop_ok(blocks, KT, 1024))
+        return loop(F256_LOOP_P, ek == EK_GELU_LN, false, false, 2);
+      // the read-modify-write GEMMs (persist bit 4: proj, fc2; with the fold's producer part), in place, with a LayerScale vector
+      if ((p.persist & 4) && (ek == EK_RMW || ek == EK_RMW_LN) && p.scale[0] && !p.resid_src && p.N % BN == 0 && p.batch <= 1 && loop_ok(blocks, KT, 1024))
+        return loop(F256_LOOP_R, ek == EK_RMW_LN, false, false, KT <= 16 ? 0 : 1);
+      // the fused QKV projection (persist bit 2; one-plane types, no fused q/k-norm): from 768 tiles -- one image's 1008 tiles run the loop
+      if (!split && (p.persist & 2) && lean && p.epi == EPI_QKV && (ek == EK_STORE || (ek == EK_QKV_LN && p.ln_raw)) && !p.qkn_g[0] && loop_ok(blocks, KT, 768) &&
+          p.embed % BN == 0 && (p.seq_stride & 3) == 0 && p.N == 3 * p.embed)
+        return loop(F256_LOOP_P, ek == EK_QKV_LN, true, false, 3);
+    }
+  }
+
+  // ---- the one-tile kernel ----
+  // The direct-store form of a lean store launch (GemmParams::direct_store). Measured in the model (bench.py --direct-store off | on, one
+  // box, twice each; profiles/r06_direct_store_ab.txt): the GELU kinds gain (fc1 36.18 -> 35.46 ms per step: their stores leave spread out
+  // between the polynomial's arithmetic), the plain kinds LOSE (qkv 23.61 -> 24.52: sixteen half-line stores per wave in one burst cost
+  // more than the LDS transpose they replace) -- so only EK_GELU / EK_GELU_LN take the direct form; EK_STORE_DS / EK_QKV_LN_DS stay
+  // instantiable for A/B builds (MD_DIRECT_STORE_ALL).
+  if (out2b && !diag && p.direct_store && lean) {
+#ifdef MD_DIRECT_STORE_ALL
+    if (amode != A_CONV3 && ek == EK_STORE) f.ek = EK_STORE_DS;
+    if (amode == A_DENSE && !fp8 && ek == EK_QKV_LN) f.ek = EK_QKV_LN_DS;
+#endif
+    if (amode == A_DENSE && ek == EK_GELU) f.ek = EK_GELU_DS;
+    if (amode == A_DENSE && !fp8 && ek == EK_GELU_LN) f.ek = EK_GELU_LN_DS;
+    if (f.ek != ek) return f;
+  }
+  // the fold kinds (dense 16-bit launches only: anything else was refused above) have no diagnostic build
+  if (ek == EK_RMW_LN || ek == EK_QKV_LN || ek == EK_GELU_LN) return f;
+  if (diag) {  // md_bench_gemm only: the stamped / ablation build exists for dense bf16 operands
+    if (!bf16 || amode != A_DENSE)
+      return refuse(f, why_not, MD_ERR_UNSUPPORTED, "gemm: the diagnostic build (stamps / ablation flags) exists for dense bf16 operands only");
+    f.diag = true;
+    return f;
+  }
+  // split-half operands take the pixel shuffle in its fast form only (16-byte stores of both planes). The GELU store kind is built for
+  // dense A only (the MLP's fc1): a GELU behind a gathered / convolution A operand takes the generic epilogue's runtime activation
+  if ((ek == EK_PIXSHUF && split && !p.ps_fast) || (ek == EK_GELU && amode != A_DENSE)) f.ek = EK_GENERIC;
+  return f;
+}
+
 int launch_gemm(GemmParams p, int amode, int prec, int tile, hipStream_t stream) {
   const int ke = prec == MD_PREC_F32 ? 32 : (prec == MD_PREC_FP8 ? 128 : 64);
   p.ksplit_ok = g_ksplit_ok;

@@ -792,12 +792,16 @@ __global__ __launch_bounds__(WGM* WGN * 64 * KSPLIT) void gemm_kernel(const Gemm
 // 128/256-byte row segments.
 //
 // EK selects the epilogue specialisation at compile time (a runtime switch around the unrolled row loops cost 40 VGPRs
-// and scratch spills): 0 generic (epilogue4 per vector), 1 read-modify-write residual (EPI_RESID_LS), 2 2-byte store
-// with optional residual inputs (EPI_STORE / q,k of EPI_QKV), 3 pixel shuffle (EPI_PIXSHUF), 4 = 2 with the GELU fused
-// at compile time (the fc1 GEMM: its own kernel symbol, so profilers report it separately).
-// LayerNorm folded into its neighbours (GemmParams::ln_*, round 6): 5 = 1 that also emits round_T(gamma_next . x_new) and the row
-// statistics of x_new (per 256-column tile: mean and centred sum of squares, combined without cancellation), 6 = 2 / 7 = 4 that finish
-// the accumulators with rstd_m * (acc - mu_m * c[n]) + d[n] before the store (q | k | V^T tiles of EPI_QKV; fc1's GELU).
+// and scratch spills); the kinds are named in gemm.h (EK_*, the numbers are part of the kernel symbols): EK_GENERIC 0 (epilogue4 per
+// vector), EK_RMW 1 read-modify-write residual (EPI_RESID_LS), EK_STORE 2 2-byte store with optional residual inputs (EPI_STORE / q,k of
+// EPI_QKV), EK_PIXSHUF 3 pixel shuffle (EPI_PIXSHUF), EK_GELU 4 = EK_STORE with the GELU fused at compile time (the fc1 GEMM: its own
+// kernel symbol, so profilers report it separately).
+// LayerNorm folded into its neighbours (GemmParams::ln_*, round 6): EK_RMW_LN 5 = EK_RMW that also emits round_T(gamma_next . x_new) and
+// the row statistics of x_new (per 256-column tile: mean and centred sum of squares, combined without cancellation), EK_QKV_LN 6 =
+// EK_STORE / EK_GELU_LN 7 = EK_GELU that finish the accumulators with rstd_m * (acc - mu_m * c[n]) + d[n] before the store (q | k | V^T
+// tiles of EPI_QKV; fc1's GELU). EK_STORE_DS .. EK_GELU_LN_DS 8 - 11: the direct-store forms of 2 / 4 / 6 / 7.
+// Which kind, and whether this kernel or one of the tile loops (gemm256p_kernel, gemm256r_kernel) runs a launch, is decided in ONE place:
+// gemm256_form (gemm.hip), pure host code; launch_256 only maps its answer to an instantiation.
 // DIAG = true is the diagnostic build used by md_bench_gemm only (in-kernel stamps and timing-only ablation flags); the
 // engine never launches it and the production instantiations contain none of that code.
 // sum over the 16 lanes of a DPP row (lanes 16 r .. 16 r + 15), the total in every lane: rotations by 8, 4, 2, 1 add the same pairs
@@ -813,11 +817,11 @@ constexpr int kLnXchg = 8 * 64 * 272;  // LDS offset of the LayerNorm-fold excha
 
 template <typename T, int AMODE, int EK, bool DIAG>
 __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
-  // EK 8 / 9 / 10 / 11 = the lean 2-byte store kinds 2 / 4 / 6 / 7 in their DIRECT-store form (GemmParams::direct_store): its own
+  // EK_STORE_DS / EK_GELU_DS / EK_QKV_LN_DS / EK_GELU_LN_DS = the lean 2-byte store kinds EK_STORE / EK_GELU / EK_QKV_LN / EK_GELU_LN in their DIRECT-store form (GemmParams::direct_store): its own
   // instantiation, so that the staged form's code and live ranges are not part of it (as a runtime branch of one kernel the pair sat
   // at 256 VGPRs and hipcc spilled LDS-DMA source addresses into the main loop's first k-tile)
-  constexpr bool DS = EK >= 8;
-  constexpr int EKB = EK == 8 ? 2 : (EK == 9 ? 4 : (EK == 10 ? 6 : (EK == 11 ? 7 : EK)));
+  constexpr bool DS = EK >= EK_STORE_DS;
+  constexpr int EKB = EK == EK_STORE_DS ? EK_STORE : (EK == EK_GELU_DS ? EK_GELU : (EK == EK_QKV_LN_DS ? EK_QKV_LN : (EK == EK_GELU_LN_DS ? EK_GELU_LN : EK)));
   constexpr int BM = 256, BN = 256, NW = 8, WGN = 4;
   constexpr int WTM = 128, WTN = 64;
   constexpr int HALF_BYTES = 256 * 128;  // one half-tile slot
@@ -982,7 +986,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
   const int q16 = lane >> 4;
   const int lane_off16 = (lane & 15) * 128 + (((((lane & 15) >> 1) & 7) ^ q16) << 4);
 
-  constexpr bool ln_cons = EKB == 6 || EKB == 7, ln_emit = EKB == 5, gelu_k = EKB == 4 || EKB == 7;
+  constexpr bool ln_cons = EKB == EK_QKV_LN || EKB == EK_GELU_LN, ln_emit = EKB == EK_RMW_LN, gelu_k = EKB == EK_GELU || EKB == EK_GELU_LN;
   // half-tile order: A0 W0 A1 W1 A2 | W2 A3 | W3 A4 | ...   (slot = order index mod 5)
   if (DIAG && stamp) stamp[1] = __builtin_amdgcn_s_memrealtime();
   int issued = 2, slot_i = 2;
@@ -1036,7 +1040,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     }
   };
 
-  // LayerNorm-fold consumer (EK 6 / 7): the tile's 256 (rstd, -mu rstd) pairs (2 KB of p.ln_stats) arrive by LDS-DMA -- no VGPR rides
+  // LayerNorm-fold consumer (EK_QKV_LN / EK_GELU_LN): the tile's 256 (rstd, -mu rstd) pairs (2 KB of p.ln_stats) arrive by LDS-DMA -- no VGPR rides
   // through the main loop, no compiler-placed wait: waves 0 and 1 request them in the load segment of the LAST k-tile into the exchange
   // area at kLnXchg (inside ring slot 4, behind every wave's staging region), when that slot is idle then (its last reader was k-tile
   // KT - 2 or earlier: true for KT = 16 and 32); otherwise behind the loop's last barrier. Three earlier forms -- the partials combined
@@ -1176,7 +1180,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     }
   };
   float* const lnx = (float*)(smem + kLnXchg);
-  // LayerNorm-fold consumer (EK 6 / 7): p.ln_stats = [rows][2] fp32 (rstd, -mu rstd) per row, finished from the producer's partials by
+  // LayerNorm-fold consumer (EK_QKV_LN / EK_GELU_LN): p.ln_stats = [rows][2] fp32 (rstd, -mu rstd) per row, finished from the producer's partials by
   // ln_finish_kernel between the two GEMMs. (Two earlier forms: the partials combined here behind the main loop -- dependent loads, a
   // division and a square root in front of the epilogue: +2.4 us per 32-us fc1 tile; combined in the prologue and carried through the
   // main loop in two VGPRs -- the kernel sits at the 256-register edge, hipcc spilled an address register and its reload in k-tile 0
@@ -1286,9 +1290,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
   const int col = (lane & 15) * 4;
   const int n = n0 + wn * WTN + col;
   const bool nvalid = n < p.N;
-  constexpr bool rmw = EKB == 1 || EKB == 5;
-  constexpr bool fast_store = (EKB == 2 || EKB == 4 || EKB == 6 || EKB == 7) && sizeof(TO) == 2;  // EK 4 / 7: GELU fused at compile time (fc1)
-  constexpr bool pixshuf = EKB == 3;
+  constexpr bool rmw = EKB == EK_RMW || EKB == EK_RMW_LN;
+  constexpr bool fast_store = (EKB == EK_STORE || EKB == EK_GELU || EKB == EK_QKV_LN || EKB == EK_GELU_LN) && sizeof(TO) == 2;  // EK_GELU / EK_GELU_LN: GELU fused at compile time (fc1)
+  constexpr bool pixshuf = EKB == EK_PIXSHUF;
   const float* biasp = MD_SEL_G(p.bias, g);
   const int r16 = lane & 15;
   const int c8 = (lane & 7) * 8, rsub = lane >> 3;
@@ -1670,7 +1674,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     stamp_end();
     return;
   }
-  // ---- fp32-staged forms: read-modify-write residual (EK 1), generic pixel shuffle (EK 3), generic (EK 0) ----
+  // ---- fp32-staged forms: read-modify-write residual (EK_RMW), generic pixel shuffle (EK_PIXSHUF), generic (EK_GENERIC) ----
   f32x4_t bias4 = {0.f, 0.f, 0.f, 0.f}, scale4 = {0.f, 0.f, 0.f, 0.f};
   int ps_co = 0, ps_dy = 0, ps_dx = 0;  // pixel shuffle: the lane's 4 columns fix (tap, channel) once
   if constexpr (pixshuf) {
@@ -1756,7 +1760,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
           for (int j = 0; j < 8; ++j) prefetch(1, j);
         }
       }
-    } else if constexpr (pixshuf && !is_split<TO>::value) {  // split-half launches reach EK 3 only in its fast form (launch_256)
+    } else if constexpr (pixshuf && !is_split<TO>::value) {  // split-half launches reach EK_PIXSHUF only in its fast form (gemm256_form)
       const int f = p.ps_f;
 #pragma unroll
       for (int it = 0; it < 16; ++it) {
@@ -1810,7 +1814,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// PERSISTENT form of the fc1 GEMM (round 6): dense A, bias (+ LayerNorm fold) + GELU, 2-byte direct stores -- EK 9 / 11 of gemm256_kernel as a
+// PERSISTENT form of the fc1 GEMM (round 6): dense A, bias (+ LayerNorm fold) + GELU, 2-byte direct stores -- EK_GELU_DS / EK_GELU_LN_DS of gemm256_kernel as a
 // tile LOOP: one workgroup per CU walks its XCD's share of the raster, and the first k-tile of the NEXT tile is requested before the
 // epilogue of the current one, so the 2.5 - 3 us of a tile's prologue (setup, issue, first k-tile landing) pass under the 4 - 5 us of
 // the GELU epilogue. What makes that possible here and did not in rounds 1 - 2 (whose tile loop around the staged epilogues spilled
@@ -2179,7 +2183,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmParams p) {
         }
       }
     }
-    // ---- epilogue: direct stores from the accumulator layout (the permuted W image: gemm256_kernel's EK 9 / 11) ----
+    // ---- epilogue: direct stores from the accumulator layout (the permuted W image: gemm256_kernel's EK_GELU_DS / EK_GELU_LN_DS) ----
     if constexpr (!QKV) {
       const bool interior = e_m_base + BM <= e_m_end;
       // (lane indices made opaque per tile: hipcc otherwise hoists the epilogue's LDS and store offsets out of the TILE loop, spills them and
@@ -2477,7 +2481,7 @@ __global__ __launch_bounds__(512) void gemm256r_kernel(const GemmParams p) {
       issue_W(0, 1);
     }
     // ---- epilogue: x(f32) += scale * (acc + bias), in four passes of 32 rows per wave through fp32 staging in ring slots 2 - 4 (8.5 KB per wave:
-    //      slots 0 - 1 belong to the next tile's first k-tile); EMIT: + round_T(gamma_next . x_new) and the rows' (mean, M2) (gemm256_kernel's EK 5) ----
+    //      slots 0 - 1 belong to the next tile's first k-tile); EMIT: + round_T(gamma_next . x_new) and the rows' (mean, M2) (gemm256_kernel's EK_RMW_LN) ----
     const bool interior = e_m_base + BM <= e_m_end;
     if constexpr (CONVR) {
       // ---- the 2-byte store epilogue with residual inputs and / or a relu'd second output (gemm256_kernel's one-plane form of it: out = act(acc + bias
@@ -2657,277 +2661,111 @@ static inline void prep_tile_map(GemmParams& p, int tiles_m, int tiles_n) {
   p.fd_map_rn = make_fastdiv(p.map_rn);
 }
 
-template <typename T, int AMODE>
-static int launch_256(GemmParams& p, hipStream_t stream) {
-  constexpr int BM = 256, BN = 256;
+// the group -> m-tile prefix of a launch (GemmParams::g_tile0); returns the m-tiles of all groups
+static inline int prep_groups(GemmParams& p, int BM) {
   int tiles_m = 0;
   for (int g = 0; g < p.ngroups; ++g) {
     p.g_tile0[g] = tiles_m;
     tiles_m += cdiv(p.g_rows[g], BM);
   }
-  p.g_tile0[p.ngroups] = tiles_m;
-  for (int g = p.ngroups + 1; g <= kMaxGroups; ++g) p.g_tile0[g] = tiles_m;
-  const long blocks = (long)tiles_m * cdiv(p.N, BN);
-  if (blocks <= 0) return MD_OK;
-  if (blocks > 0x7fffffffL) MD_FAIL(MD_ERR_UNSUPPORTED, "gemm: too many tiles (%ld)", blocks);
-  prep_tile_map(p, tiles_m, cdiv(p.N, BN));
+  for (int g = p.ngroups; g <= kMaxGroups; ++g) p.g_tile0[g] = tiles_m;
+  return tiles_m;
+}
+
+// Launch of a kernel that needs more dynamic LDS than the default limit. hipFuncAttributeMaxDynamicSharedMemorySize is per DEVICE:
+// one bit per device ordinal (a process may drive several GPUs), one word per kernel (KERN is a template argument).
+typedef void (*GemmKernel)(const GemmParams);
+template <GemmKernel KERN>
+static int launch_lds(dim3 grid, dim3 block, int smem, hipStream_t stream, const GemmParams& p) {
+  static std::atomic<unsigned long> attr_set{0};
+  int ordinal = 0;
+  MD_HIP(hipGetDevice(&ordinal));
+  const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
+  if (!bit || !(attr_set.load(std::memory_order_acquire) & bit)) {  // concurrent first launches at worst both set the attribute
+    MD_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    attr_set.fetch_or(bit, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(KERN, grid, block, smem, stream, p);
+  MD_HIP(hipGetLastError());
+  return MD_OK;
+}
+
+template <typename T>
+constexpr int kPrecOf = std::is_same<T, bf16_t>::value ? MD_PREC_BF16
+                        : std::is_same<T, f16_t>::value ? MD_PREC_F16
+                        : std::is_same<T, f16s_t>::value ? MD_PREC_F16X2
+                        : std::is_same<T, fp8_t>::value ? MD_PREC_FP8 : MD_PREC_F32;
+
+// The 256 x 256 launch: gemm256_form (gemm.hip) chooses the kernel, the switch below maps its answer to the instantiation. The
+// `if constexpr` guards are the set of kernels that is built per <T, AMODE>; a form outside it is an error, never another kernel.
+template <typename T, int AMODE>
+static int launch_256(GemmParams& p, hipStream_t stream) {
+  constexpr int BM = 256, BN = 256;
   constexpr int smem = 5 * 256 * 128;  // 160 KB: the whole LDS of a CU
-  const dim3 grid((unsigned)blocks, (unsigned)(p.batch > 1 ? p.batch : 1));
-  auto go = [&](auto kern, std::atomic<unsigned long>* attr_set) -> int {
-    // hipFuncAttributeMaxDynamicSharedMemorySize is per DEVICE: one bit per device ordinal (a process may drive several GPUs)
-    int ordinal = 0;
-    MD_HIP(hipGetDevice(&ordinal));
-    const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-    if (!bit || !(attr_set->load(std::memory_order_acquire) & bit)) {  // concurrent first launches at worst both set the attribute
-      MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-      attr_set->fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, stream, p);
-    MD_HIP(hipGetLastError());
-    return MD_OK;
-  };
-  // epilogue specialisation (EK) from the runtime parameters
-  int ek = 0;
-  const bool ln_prod = p.ln_out != nullptr, ln_cons = p.ln_stats != nullptr;
-  if (ln_prod || ln_cons) {  // the LayerNorm fold exists for the dense 16-bit forms of the 256 x 256 kernel only: refuse anything else loudly
-    if (AMODE != A_DENSE || sizeof(typename OutT<T>::type) != 2 || std::is_same<T, fp8_t>::value || p.N % BN != 0 || p.batch > 1)
-      MD_FAIL(MD_ERR_UNSUPPORTED, "gemm: the LayerNorm fold needs dense 16-bit operands and N %% 256 == 0 (N=%d)", p.N);
-    if (ln_prod && (p.epi != EPI_RESID_LS || !p.ln_stats_out || p.ln_parts != p.N / BN || !p.ln_gamma[0] || p.ln_ldo % 4 != 0))
-      MD_FAIL(MD_ERR_INVALID_ARG, "gemm: LayerNorm-fold producer parameters");
-    if (ln_cons && (!p.ln_c[0] || !p.bias[0] || p.wscale[0] || p.res1 || p.res2 || p.out2 || p.out_f32 || p.out_fp8 ||
-                    !((p.epi == EPI_QKV && p.embed % BN == 0) || (p.epi == EPI_STORE && p.act == ACT_GELU && p.res_mod == 0))))
-      MD_FAIL(MD_ERR_INVALID_ARG, "gemm: LayerNorm-fold consumer parameters");
-  }
-  if (p.epi == EPI_RESID_LS) ek = ln_prod ? 5 : 1;
-  else if (p.epi == EPI_PIXSHUF) ek = 3;
-  else if (sizeof(typename OutT<T>::type) == 2) {
-    const long ldo_e = p.epi == EPI_QKV ? 2L * p.embed : p.ldo;
-    const bool vec8 = p.N % 8 == 0 && ldo_e % 8 == 0 && (!(p.res1 || p.res2) || p.ldr % 8 == 0);
-    // split-half outputs take the store kinds only for their lean sub-path (no residual inputs, no second / fp32 output) and,
-    // for q | k tiles, when a tile cannot straddle the q | k sections of the [q_hi | q_lo | k_hi | k_lo] rows
-    // (round 6: residual inputs and the relu'd second output included)
-    const bool split_ok = !is_split<T>::value || (!p.out_f32 && !p.out_fp8 && p.o_plane % 8 == 0 && (!(p.res1 || p.res2) || p.r_plane % 8 == 0) &&
-                                                  (p.epi != EPI_QKV || p.embed % BN == 0));
-    if (!split_ok) ek = 0;
-    else if (vec8 && p.epi == EPI_STORE && p.res_mod == 0 && p.act == ACT_GELU) ek = ln_cons ? 7 : 4;
-    else if (vec8 && ((p.epi == EPI_STORE && p.res_mod == 0 && p.act != ACT_GELU) || (p.epi == EPI_QKV && (2 * p.embed) % BN == 0))) ek = (ln_cons && p.epi == EPI_QKV) ? 6 : 2;
-    if (ln_cons && ek != 6 && ek != 7) MD_FAIL(MD_ERR_UNSUPPORTED, "gemm: the LayerNorm-fold consumer needs the 16-byte store epilogue (N, ldo %% 8 == 0)");
-  }
-  const bool diag = p.stamps != nullptr || p.debug_flags != 0;
-  static std::atomic<unsigned long> set[12], dset[5];  // zero-initialised statics
-  // the direct-store form of a lean store launch (GemmParams::direct_store)
-  const bool lean = !p.res1 && !p.res2 && !p.out2 && !p.out_f32 && !p.out_fp8 && p.N % BN == 0 && p.batch <= 1;
-  if constexpr (sizeof(typename OutT<T>::type) == 2) {
-    // Measured in the model (bench.py --direct-store off | on, one box, twice each; profiles/r06_direct_store_ab.txt): the GELU kinds gain
-    // (fc1 36.18 -> 35.46 ms per step: their stores leave spread out between the polynomial's arithmetic), the plain kinds LOSE (qkv 23.61 ->
-    // 24.52: sixteen half-line stores per wave in one burst cost more than the LDS transpose they replace) -- so only EK 4 / 7 take the
-    // direct form; EK 8 / 10 stay instantiable for A/B builds (MD_DIRECT_STORE_ALL).
-    if constexpr (AMODE == A_CONV3 && !is_split<T>::value && !std::is_same<T, fp8_t>::value) {
-      // the implicit 3 x 3 GEMM with a lean store epilogue (bias, optional ReLU, one 2-byte output: the first convolution of the decoder's residual
-      // units) as the tile loop of the q | k form (persist bit 8)
-      const int KTc = p.K / 64;
-      if (!diag && (p.persist & 8) && lean && ek == 2 && p.epi == EPI_STORE && !p.wscale[0] && p.bias[0] && p.ngroups <= 1 && p.a_wrap == 0 && blocks >= 1024 &&
-          KTc >= 3 && (2 * KTc - 2) % 5 != 4 && (2 * KTc - 1) % 5 != 4 && p.N == BN && (p.act == ACT_NONE || p.act == ACT_RELU)) {
-        int ordinal = 0, cus = 0;
-        MD_HIP(hipGetDevice(&ordinal));
-        MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
-        const int G = cus >= 8 ? (cus & ~7) : 8;
-        p.ptiles = (int)blocks;
-        p.stagger = 0;
-        static std::atomic<unsigned long> cset;
-        const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-        auto kern = gemm256p_kernel<T, false, true, true>;
-        if (!bit || !(cset.load(std::memory_order_acquire) & bit)) {
-          MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-          cset.fetch_or(bit, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(512), smem, stream, p);
-        MD_HIP(hipGetLastError());
-        return MD_OK;
-      }
-      // the same with residual inputs and / or a relu'd second output (the second convolution of a residual unit: x + conv2(..) [+ skip], and
-      // its relu'd copy for the next unit): the read-modify-write loop's skeleton, 32-row staging passes
-      if (!diag && (p.persist & 8) && !lean && ek == 2 && p.epi == EPI_STORE && (p.res1 || p.res2 || p.out2) && !p.out_f32 && !p.out_fp8 && !p.wscale[0] &&
-          p.bias[0] && p.ngroups <= 1 && p.a_wrap == 0 && p.batch <= 1 && blocks >= 1024 && KTc >= 3 && (2 * KTc - 2) % 5 != 4 && (2 * KTc - 1) % 5 != 4 &&
-          p.N == BN && (p.act == ACT_NONE || p.act == ACT_RELU)) {
-        int ordinal = 0, cus = 0;
-        MD_HIP(hipGetDevice(&ordinal));
-        MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
-        const int G = cus >= 8 ? (cus & ~7) : 8;
-        p.ptiles = (int)blocks;
-        p.stagger = 0;
-        static std::atomic<unsigned long> c2set;
-        const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-        auto kern = gemm256r_kernel<T, false, true>;
-        if (!bit || !(c2set.load(std::memory_order_acquire) & bit)) {
-          MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-          c2set.fetch_or(bit, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(512), smem, stream, p);
-        MD_HIP(hipGetLastError());
-        return MD_OK;
-      }
-    }
-    if constexpr (AMODE == A_DENSE && !std::is_same<T, fp8_t>::value) {
-      // the persistent tile loop of the fc1 form (gemm256p_kernel): GemmParams::persist, enough tiles to give every CU several, a k-tile
-      // count that leaves ring slot 4 idle in the last k-tile (16, 32: K' = 1024, 2048)
-      const int KTp = p.K / 64;
-      if (!diag && (p.persist & 1) && p.direct_store && lean && (ek == 4 || ek == 7) && !p.wscale[0] && p.bias[0] && blocks >= 1024 && KTp >= 3 &&
-          (2 * KTp - 2) % 5 != 4 && (2 * KTp - 1) % 5 != 4 && (ek == 4 || p.ln_raw)) {
-        int ordinal = 0, cus = 0;
-        MD_HIP(hipGetDevice(&ordinal));
-        MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
-        const int G = cus >= 8 ? (cus & ~7) : 8;  // (a multiple of 8: XCD x = blocks x, x + 8, ..; more workgroups than CUs only costs residency)
-        p.ptiles = (int)blocks;
-        p.stagger = blocks >= 2048 ? gemm_stagger_ticks(2) : 0;
-        auto gop = [&](auto kern, std::atomic<unsigned long>* attr_set) -> int {
-          const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-          if (!bit || !(attr_set->load(std::memory_order_acquire) & bit)) {
-            MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            attr_set->fetch_or(bit, std::memory_order_release);
-          }
-          hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(512), smem, stream, p);
-          MD_HIP(hipGetLastError());
-          return MD_OK;
-        };
-        static std::atomic<unsigned long> pset[2];
-        if (ek == 7) return gop(gemm256p_kernel<T, true>, &pset[1]);
-        return gop(gemm256p_kernel<T, false>, &pset[0]);
-      }
-      // the read-modify-write GEMMs (proj, fc2; with the LayerNorm fold's producer part: EK 5) as the tile loop gemm256r_kernel
-      if (!diag && (p.persist & 4) && (ek == 1 || ek == 5) && !p.wscale[0] && p.bias[0] && p.scale[0] && !p.resid_src && p.N % BN == 0 && p.batch <= 1 &&
-          blocks >= 1024 && KTp >= 3 && (2 * KTp - 2) % 5 != 4 && (2 * KTp - 1) % 5 != 4) {
-        int ordinal = 0, cus = 0;
-        MD_HIP(hipGetDevice(&ordinal));
-        MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
-        const int G = cus >= 8 ? (cus & ~7) : 8;  // (a multiple of 8: XCD x = blocks x, x + 8, ..; more workgroups than CUs only costs residency)
-        p.ptiles = (int)blocks;
-        p.stagger = blocks >= 2048 ? gemm_stagger_ticks(KTp <= 16 ? 0 : 1) : 0;  // (the offset is idle time at either end of the launch: 8 rounds of tiles and more)
-        auto gop = [&](auto kern, std::atomic<unsigned long>* attr_set) -> int {
-          const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-          if (!bit || !(attr_set->load(std::memory_order_acquire) & bit)) {
-            MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            attr_set->fetch_or(bit, std::memory_order_release);
-          }
-          hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(512), smem, stream, p);
-          MD_HIP(hipGetLastError());
-          return MD_OK;
-        };
-        static std::atomic<unsigned long> rset[2];
-        if (ek == 5) return gop(gemm256r_kernel<T, true>, &rset[1]);
-        return gop(gemm256r_kernel<T, false>, &rset[0]);
-      }
-      // the fused QKV projection as the same tile loop (one-plane types)
-      if constexpr (!is_split<T>::value) {
-        if (!diag && (p.persist & 2) && lean && p.epi == EPI_QKV && (ek == 2 || ek == 6) && !p.wscale[0] && p.bias[0] && !p.qkn_g[0] && blocks >= 768 &&
-            KTp >= 3 && (2 * KTp - 2) % 5 != 4 && (2 * KTp - 1) % 5 != 4 && (ek == 2 || p.ln_raw) && p.embed % BN == 0 && (p.seq_stride & 3) == 0 &&
-            p.N == 3 * p.embed) {
-          int ordinal = 0, cus = 0;
-          MD_HIP(hipGetDevice(&ordinal));
-          MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
-          const int G = cus >= 8 ? (cus & ~7) : 8;  // (a multiple of 8: XCD x = blocks x, x + 8, ..; more workgroups than CUs only costs residency)
-          p.ptiles = (int)blocks;
-          p.stagger = blocks >= 2048 ? gemm_stagger_ticks(3) : 0;
-          auto gop = [&](auto kern, std::atomic<unsigned long>* attr_set) -> int {
-            const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-            if (!bit || !(attr_set->load(std::memory_order_acquire) & bit)) {
-              MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-              attr_set->fetch_or(bit, std::memory_order_release);
-            }
-            hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(512), smem, stream, p);
-            MD_HIP(hipGetLastError());
-            return MD_OK;
-          };
-          static std::atomic<unsigned long> qset[2];
-          if (ek == 6) return gop(gemm256p_kernel<T, true, true>, &qset[1]);
-          return gop(gemm256p_kernel<T, false, true>, &qset[0]);
-        }
-      }
-    }
-    if (!diag && p.direct_store && lean) {
+  constexpr bool OUT2B = sizeof(typename OutT<T>::type) == 2, FP8 = std::is_same<T, fp8_t>::value, SPLIT = is_split<T>::value;
+  constexpr bool DENSE16 = AMODE == A_DENSE && OUT2B && !FP8;            // the LayerNorm-fold kinds, the fc1 / read-modify-write loops
+  constexpr bool CONV16 = AMODE == A_CONV3 && OUT2B && !FP8 && !SPLIT;   // the convolution loops
+  constexpr bool DIAG_OK = std::is_same<T, bf16_t>::value && AMODE == A_DENSE;
+  const int tiles_m = prep_groups(p, BM);
+  int ordinal = 0, cus = 0;
+  MD_HIP(hipGetDevice(&ordinal));
+  MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
+  std::string why_not;
+  const Form256 f = gemm256_form(p, AMODE, kPrecOf<T>, cus, &why_not);
+  if (f.err != MD_OK) MD_FAIL(f.err, "%s", why_not.c_str());
+  if (f.blocks <= 0) return MD_OK;
+  prep_tile_map(p, tiles_m, cdiv(p.N, BN));
+  if (f.family != F256_ONE_TILE) p.ptiles = f.ptiles, p.stagger = f.stagger;
+  const dim3 grid((unsigned)f.grid, (unsigned)(p.batch > 1 ? p.batch : 1));  // (the tile loops never run batched)
+#define MD_GO(...) return launch_lds<__VA_ARGS__>(grid, dim3(512), smem, stream, p)
+  constexpr int LOOP = 32, FOLD = 1, QKV = 2, CONV = 4, DIAG = 16;
+  switch (f.family == F256_ONE_TILE ? f.ek | (f.diag ? DIAG : 0) : f.family * LOOP | (f.fold ? FOLD : 0) | (f.qkv ? QKV : 0) | (f.conv ? CONV : 0)) {
+    case EK_GENERIC: MD_GO(gemm256_kernel<T, AMODE, EK_GENERIC, false>);
+    case EK_RMW: MD_GO(gemm256_kernel<T, AMODE, EK_RMW, false>);
+    case EK_PIXSHUF: MD_GO(gemm256_kernel<T, AMODE, EK_PIXSHUF, false>);
+    case EK_STORE: if constexpr (OUT2B) MD_GO(gemm256_kernel<T, AMODE, EK_STORE, false>); break;
+    case EK_GELU: if constexpr (OUT2B && AMODE == A_DENSE) MD_GO(gemm256_kernel<T, AMODE, EK_GELU, false>); break;
+    case EK_GELU_DS: if constexpr (OUT2B && AMODE == A_DENSE) MD_GO(gemm256_kernel<T, AMODE, EK_GELU_DS, false>); break;
+    case EK_RMW_LN: if constexpr (DENSE16) MD_GO(gemm256_kernel<T, AMODE, EK_RMW_LN, false>); break;
+    case EK_QKV_LN: if constexpr (DENSE16) MD_GO(gemm256_kernel<T, AMODE, EK_QKV_LN, false>); break;
+    case EK_GELU_LN: if constexpr (DENSE16) MD_GO(gemm256_kernel<T, AMODE, EK_GELU_LN, false>); break;
+    case EK_GELU_LN_DS: if constexpr (DENSE16) MD_GO(gemm256_kernel<T, AMODE, EK_GELU_LN_DS, false>); break;
 #ifdef MD_DIRECT_STORE_ALL
-      if constexpr (AMODE != A_CONV3) {
-        if (ek == 2) return go(gemm256_kernel<T, AMODE, 8, false>, &set[8]);
-      }
+    case EK_STORE_DS: if constexpr (OUT2B && AMODE != A_CONV3) MD_GO(gemm256_kernel<T, AMODE, EK_STORE_DS, false>); break;
+    case EK_QKV_LN_DS: if constexpr (DENSE16) MD_GO(gemm256_kernel<T, AMODE, EK_QKV_LN_DS, false>); break;
 #endif
-      if constexpr (AMODE == A_DENSE) {
-        if (ek == 4) return go(gemm256_kernel<T, AMODE, 9, false>, &set[9]);
-        if constexpr (!std::is_same<T, fp8_t>::value) {
-#ifdef MD_DIRECT_STORE_ALL
-          if (ek == 6) return go(gemm256_kernel<T, AMODE, 10, false>, &set[10]);
-#endif
-          if (ek == 7) return go(gemm256_kernel<T, AMODE, 11, false>, &set[11]);
-        }
-      }
-    }
-  }
-  if constexpr (AMODE == A_DENSE && sizeof(typename OutT<T>::type) == 2 && !std::is_same<T, fp8_t>::value) {
-    if (ek == 5) return go(gemm256_kernel<T, AMODE, 5, false>, &set[5]);
-    if (ek == 6) return go(gemm256_kernel<T, AMODE, 6, false>, &set[6]);
-    if (ek == 7) return go(gemm256_kernel<T, AMODE, 7, false>, &set[7]);
-  }
-  if (diag) {  // md_bench_gemm only: the stamped / ablation build exists for dense bf16 operands
-    if constexpr (std::is_same<T, bf16_t>::value && AMODE == A_DENSE) {
-      switch (ek) {
-        case 1: return go(gemm256_kernel<T, AMODE, 1, true>, &dset[1]);
-        case 2: return go(gemm256_kernel<T, AMODE, 2, true>, &dset[2]);
-        case 3: return go(gemm256_kernel<T, AMODE, 3, true>, &dset[3]);
-        case 4: return go(gemm256_kernel<T, AMODE, 4, true>, &dset[4]);
-        default: return go(gemm256_kernel<T, AMODE, 0, true>, &dset[0]);
-      }
-    } else {
-      MD_FAIL(MD_ERR_UNSUPPORTED, "gemm: the diagnostic build (stamps / ablation flags) exists for dense bf16 operands only");
-    }
-  }
-  (void)dset;
-  switch (ek) {
-    case 1: return go(gemm256_kernel<T, AMODE, 1, false>, &set[1]);
-    case 3:  // split-half operands: the fast form only (16-byte stores of both planes); anything else takes the generic kind
-      if (!is_split<T>::value || p.ps_fast) return go(gemm256_kernel<T, AMODE, 3, false>, &set[3]);
-      break;
-    case 2:
-      if constexpr (sizeof(typename OutT<T>::type) == 2) return go(gemm256_kernel<T, AMODE, 2, false>, &set[2]);
-      break;
-    case 4:  // the GELU store kind is built for dense A only (the MLP's fc1); a GELU behind a gathered / convolution A operand
-             // takes the store kind's runtime activation path of the generic epilogue
-      if constexpr (sizeof(typename OutT<T>::type) == 2 && AMODE == A_DENSE) return go(gemm256_kernel<T, AMODE, 4, false>, &set[4]);
-      break;
+    case DIAG | EK_GENERIC: if constexpr (DIAG_OK) MD_GO(gemm256_kernel<T, AMODE, EK_GENERIC, true>); break;
+    case DIAG | EK_RMW: if constexpr (DIAG_OK) MD_GO(gemm256_kernel<T, AMODE, EK_RMW, true>); break;
+    case DIAG | EK_STORE: if constexpr (DIAG_OK) MD_GO(gemm256_kernel<T, AMODE, EK_STORE, true>); break;
+    case DIAG | EK_PIXSHUF: if constexpr (DIAG_OK) MD_GO(gemm256_kernel<T, AMODE, EK_PIXSHUF, true>); break;
+    case DIAG | EK_GELU: if constexpr (DIAG_OK) MD_GO(gemm256_kernel<T, AMODE, EK_GELU, true>); break;
+    case F256_LOOP_P * LOOP: if constexpr (DENSE16) MD_GO(gemm256p_kernel<T, false>); break;
+    case F256_LOOP_P * LOOP | FOLD: if constexpr (DENSE16) MD_GO(gemm256p_kernel<T, true>); break;
+    case F256_LOOP_P * LOOP | QKV: if constexpr (DENSE16 && !SPLIT) MD_GO(gemm256p_kernel<T, false, true>); break;
+    case F256_LOOP_P * LOOP | QKV | FOLD: if constexpr (DENSE16 && !SPLIT) MD_GO(gemm256p_kernel<T, true, true>); break;
+    case F256_LOOP_P * LOOP | QKV | CONV: if constexpr (CONV16) MD_GO(gemm256p_kernel<T, false, true, true>); break;
+    case F256_LOOP_R * LOOP: if constexpr (DENSE16) MD_GO(gemm256r_kernel<T, false>); break;
+    case F256_LOOP_R * LOOP | FOLD: if constexpr (DENSE16) MD_GO(gemm256r_kernel<T, true>); break;
+    case F256_LOOP_R * LOOP | CONV: if constexpr (CONV16) MD_GO(gemm256r_kernel<T, false, true>); break;
     default: break;
   }
-  return go(gemm256_kernel<T, AMODE, 0, false>, &set[0]);
+#undef MD_GO
+  MD_FAIL(MD_ERR_UNSUPPORTED, "gemm: no 256 x 256 kernel is built for family %d, kind %d (fold %d, qkv %d, conv %d, diag %d)", f.family, f.ek, (int)f.fold,
+          (int)f.qkv, (int)f.conv, (int)f.diag);
 }
 
 // ------------------------------------------------------------------------------------------------
 template <typename T, int BM, int BN, int WGM, int WGN, int AMODE, int KSPLIT = 1>
 static int launch_cfg(GemmParams& p, hipStream_t stream) {
-  int tiles_m = 0;
-  for (int g = 0; g < p.ngroups; ++g) {
-    p.g_tile0[g] = tiles_m;
-    tiles_m += cdiv(p.g_rows[g], BM);
-  }
-  p.g_tile0[p.ngroups] = tiles_m;
-  for (int g = p.ngroups + 1; g <= kMaxGroups; ++g) p.g_tile0[g] = tiles_m;
-  const int tiles_n = cdiv(p.N, BN);
+  const int tiles_m = prep_groups(p, BM), tiles_n = cdiv(p.N, BN);
   const long blocks = (long)tiles_m * tiles_n;
   if (blocks <= 0) return MD_OK;
   if (blocks > 0x7fffffffL) MD_FAIL(MD_ERR_UNSUPPORTED, "gemm: too many tiles (%ld)", blocks);
   prep_tile_map(p, tiles_m, tiles_n);
   constexpr int smem = 2 * (BM + BN) * 128 * KSPLIT;
-  auto kern = gemm_kernel<T, BM, BN, WGM, WGN, AMODE, KSPLIT>;
-  static std::atomic<unsigned long> attr_set{0};  // one bit per device ordinal (the attribute is per device)
-  {
-    int ordinal = 0;
-    MD_HIP(hipGetDevice(&ordinal));
-    const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
-    if (!bit || !(attr_set.load(std::memory_order_acquire) & bit)) {
-      MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-      attr_set.fetch_or(bit, std::memory_order_release);
-    }
-  }
   if (KSPLIT > 1) gemm_count_ksplit_launch();
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)(p.batch > 1 ? p.batch : 1)), dim3(WGM * WGN * 64 * KSPLIT), smem, stream, p);
-  MD_HIP(hipGetLastError());
-  return MD_OK;
+  return launch_lds<gemm_kernel<T, BM, BN, WGM, WGN, AMODE, KSPLIT>>(dim3((unsigned)blocks, (unsigned)(p.batch > 1 ? p.batch : 1)), dim3(WGM * WGN * 64 * KSPLIT), smem,
+                                                                   stream, p);
 }
 
 // k-groups for a 64 x 64 launch (gemm_kernel's KSPLIT): only launches of at most kSplitBlocks workgroups (one or two four-wave

@@ -1267,7 +1267,7 @@ static int run_vit(Run& r, int nseq_p, int nseq, int s_lo, int s_hi) {
   // The four GEMMs of a block then always run the 256 x 256 kernel: the fold is a model-level choice, so that any window of a call
   // (tile-parallel mode) computes the same bits as the whole call.
   v.fold = m->ln_fold_on();
-  // ln_fold = 3 (diagnostic, benches only): the UNFOLDED schedule through the fold-form consumer kernels (EK 6 / 7) on neutral statistics
+  // ln_fold = 3 (diagnostic, benches only): the UNFOLDED schedule through the fold-form consumer kernels (EK_QKV_LN / EK_GELU_LN) on neutral statistics
   // (rstd = 1, mu = 0, c = 0, d = bias): isolates what those epilogues cost from what the colder A operand of the folded schedule costs
   v.neutral = !v.fold && m->ln_fold_can && m->ln_fold_opt == 3;
   // (ln_fold = 4: the pairs come from the ln_finish launch -- the A/B form; default: the consumer combines the partials itself)

@@ -149,6 +149,32 @@ def test_persistent_fc1_kernel_is_bit_identical_to_the_one_tile_kernel(dev, prec
     assert bool(torch.isfinite(got).all()) and float(got.abs().max()) > 0.1
 
 
+@pytest.mark.parametrize("precision", [0, 3])
+def test_convolution_tile_loop_is_bit_identical_to_the_one_tile_kernel(dev, precision):
+    """The implicit 3 x 3 GEMM with a lean store epilogue runs `gemm256p_kernel<T, false, true, true>` from 1024 tiles (persist bit 8): the
+    operator entry on [1, 64, 512, 512] -> 256 channels with bias and a storage-type output is 1024 tiles of 9 k-tiles, one 256-column
+    tile in n -- tests/golden/gemm256_form_table.txt: `conv3 store` (bias, no activation) and `conv3 conv_lean` from 1024 tiles with persist
+    bit 8 take loop_p (qkv, conv), with persist 0 the one-tile store kind; 9 k-tiles leave ring slot 4 idle in the last one (16 % 5,
+    17 % 5 != 4). The same bits with the loop (twice: the tile walk is
+    deterministic) and with the one-tile kernel, bf16 and f16 (the loop is built for the one-plane 16-bit types)."""
+    from burn_depth_amd import _lib, ops
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(9)
+    x = torch.randn(1, 64, 512, 512, generator=g).cuda()
+    w = (torch.randn(256, 64, 3, 3, generator=g) * 0.05).cuda()
+    b = (torch.randn(256, generator=g) * 0.1).cuda()
+    prev = lib.md_debug_gemm_persistent(0)
+    try:
+        ref = ops.conv3x3(dev, x, w, b, precision=precision, storage_out=True)
+        lib.md_debug_gemm_persistent(15)
+        got = ops.conv3x3(dev, x, w, b, precision=precision, storage_out=True)
+        got2 = ops.conv3x3(dev, x, w, b, precision=precision, storage_out=True)
+    finally:
+        lib.md_debug_gemm_persistent(prev)
+    assert torch.equal(ref, got) and torch.equal(got, got2)
+    assert bool(torch.isfinite(got).all()) and float(got.abs().max()) > 0.1
+
+
 @pytest.mark.parametrize("precision", [0, 4])
 def test_persistent_fc1_kernel_inside_the_model(dev, precision):
     """DepthPro::infer on [2,3,1536,1536] (default configuration: fc1 = 2688 tiles per launch, the LayerNorm fold on) with the persistent
