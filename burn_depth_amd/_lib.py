@@ -17,6 +17,7 @@ MD_ERR_UNSUPPORTED, MD_ERR_NO_FOV, MD_ERR_OOM, MD_ERR_LEVELS = -6, -7, -8, -9
 MD_MEM_HOST, MD_MEM_DEVICE = 0, 1
 MD_COMM_ID_BYTES = 128
 MD_FRAME_U8_GRAY, MD_FRAME_RGBA_F32 = 0, 1
+VIT_GEMM_RESID, VIT_GEMM_QKV, VIT_GEMM_FC1, VIT_GEMM_PATCH_EMBED = 0, 1, 2, 3
 TILE_256x256, TILE_128x128, TILE_256x32, TILE_128x64, TILE_64x64, TILE_AUTO = 0, 1, 2, 3, 4, 99
 
 
@@ -77,6 +78,21 @@ class MdViewFilterOutputs(C.Structure):
 class MdDa3Cfg(C.Structure):
     _fields_ = [("variant", C.c_char_p), ("image_size", C.c_int), ("precision", C.c_int), ("max_batch", C.c_int),
                 ("ln_eps", C.c_float), ("image_width", C.c_int)]
+
+
+class MdVitGemmGroup(C.Structure):
+    """md_vit_gemm_group (include/mi_depth.h)."""
+    _fields_ = [("row0", C.c_int), ("rows", C.c_int), ("arow0", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_void_p),
+                ("gamma_next", C.c_void_p), ("c", C.c_void_p), ("pos", C.c_void_p)]
+
+
+class MdVitGemm(C.Structure):
+    """md_vit_gemm (include/mi_depth.h)."""
+    _fields_ = [("kind", C.c_int), ("precision", C.c_int), ("tile", C.c_int), ("N", C.c_int), ("K", C.c_int), ("a_rows", C.c_int),
+                ("a", C.c_void_p), ("ngroups", C.c_int), ("g", MdVitGemmGroup * 4), ("out_rows", C.c_int), ("x", C.c_void_p),
+                ("x_out", C.c_void_p), ("ln_out", C.c_void_p), ("ln_stats_out", C.c_void_p), ("ln_stats", C.c_void_p), ("ln_raw", C.c_int),
+                ("ln_eps", C.c_float), ("ln_inv_n", C.c_float), ("S", C.c_int), ("D", C.c_int), ("P", C.c_int), ("qk", C.c_void_p),
+                ("vT", C.c_void_p), ("out", C.c_void_p)]
 
 
 class MdNchwView(C.Structure):
@@ -158,6 +174,7 @@ SYMBOLS = {
     "md_debug_gemm_direct_store": (_I, [_I]),
     "md_debug_gemm_persistent": (_I, [_I]),
     "md_debug_gemm_stagger": (_I, [_I, _I]),
+    "md_debug_gemm_stagger_ticks": (_I, [_I]),
     "md_da3_infer_raw": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "md_da3_infer_from_tokens": (_I, [_P, C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _P, _I, _P]),
     "md_da3_param_inventory": (_I, [C.POINTER(MdDa3Cfg), _I, _I, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _F, _F]),
@@ -202,6 +219,8 @@ SYMBOLS = {
     "md_op_nhwc_to_nchw": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_ln_fold_vectors": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "md_op_ln_finish": (_I, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
+    "md_op_vit_gemm": (_I, [_P, C.POINTER(MdVitGemm), _P]),
+    "md_debug_gemm_last_form": (_I, [C.POINTER(_I * 8)]),
     "md_op_conv2d_direct_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_fov_to_focal": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_op_focal_to_fov": (_I, [C.c_float, _I, _I, _F, _F]),

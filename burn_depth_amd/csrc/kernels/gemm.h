@@ -94,13 +94,13 @@ struct GemmParams {
   // ---- LayerNorm folded into the GEMMs on either side of it (round 6; the 256 x 256 kernel's kinds EK_RMW_LN / EK_QKV_LN / EK_GELU_LN, dense A, 16-bit operands) ----
   // LN(x) W^T + b  =  rstd_m * (round(gamma . x) W^T  -  mu_m * c)  +  d,   c[n] = sum_k gamma[k] W[n][k],  d[n] = b[n] + sum_k beta[k] W[n][k]:
   // the PRODUCER of x (EPI_RESID_LS: proj / fc2) also writes round_T(gamma_next . x_new) as the next GEMM's A operand and, per row and
-  // 256-column tile, (sum x, sum x^2) of x_new in fp32; the CONSUMER (qkv / fc1) finishes its accumulators with the row's mu / rstd. The
+  // 256-column tile, (mean, centred sum of squares) of x_new in fp32; the CONSUMER (qkv / fc1) finishes its accumulators with the row's mu / rstd. The
   // stand-alone LayerNorm launch between them (read 4 B + write 2 B per element at HBM rate, 49 per ViT pass) is gone. The weights stay
   // untouched (f16 checkpoint weights remain exact split-half operands); c, d are built at commit from the operand-rounded weights.
   void* ln_out = nullptr;          // producer: [rows][ln_ldo] T (split-half: lo plane ln_plane elements behind the hi plane)
   long ln_ldo = 0, ln_plane = 0;
   const float* ln_gamma[kMaxGroups] = {nullptr, nullptr, nullptr, nullptr};  // producer: gamma of the NEXT LayerNorm [N]
-  float* ln_stats_out = nullptr;   // producer: [rows][N / 256][2] fp32 partial (sum, sum of squares)
+  float* ln_stats_out = nullptr;   // producer: [rows][N / 256][2] fp32 partial (mean, centred sum of squares) of the row's 256 columns of x_new
   const float* ln_stats = nullptr; // consumer: ln_raw = 1: the producer's array (4 partials per row, combined in the epilogue); 0: [rows][2] (rstd, -mu rstd) from ln_finish
   int ln_raw = 0;
   int ln_parts = 0;
@@ -234,6 +234,11 @@ struct Form256 {
 // THE place a 256 x 256 launch's kernel is chosen (launch_256 only maps the result to an instantiation). Pure host code: no HIP
 // call, `cus` = the device's CU count. `p` as launch_gemm hands it to the launcher (direct_store, persist, ps_fast set).
 Form256 gemm256_form(const GemmParams& p, int amode, int prec, int cus, std::string* why_not = nullptr);
+// The form the calling host thread's last 256 x 256 launch ran (launch_256 records what it maps to an instantiation; host state only,
+// one thread-local store per launch). gemm_forget_form() sets family = -1: "no 256 x 256 launch since" (md_debug_gemm_last_form).
+void gemm_record_form(const Form256& f);
+void gemm_forget_form();
+Form256 gemm_last_form();
 
 enum GemmTile : int { TILE_256x256 = 0, TILE_128x128 = 1, TILE_256x32 = 2, TILE_128x64 = 3, TILE_64x64 = 4, TILE_AUTO = 99 };
 

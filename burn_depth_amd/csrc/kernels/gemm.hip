@@ -211,6 +211,16 @@ Form256 gemm256_form(const GemmParams& p, int amode, int prec, int cus, std::str
   return f;
 }
 
+static constexpr Form256 no_form() {
+  Form256 f;
+  f.family = -1;
+  return f;
+}
+static thread_local Form256 g_last_form = no_form();  // constant-initialised: recording a launch is one plain thread-local store
+void gemm_record_form(const Form256& f) { g_last_form = f; }
+void gemm_forget_form() { g_last_form = no_form(); }
+Form256 gemm_last_form() { return g_last_form; }
+
 int launch_gemm(GemmParams p, int amode, int prec, int tile, hipStream_t stream) {
   const int ke = prec == MD_PREC_F32 ? 32 : (prec == MD_PREC_FP8 ? 128 : 64);
   p.ksplit_ok = g_ksplit_ok;

@@ -2714,6 +2714,7 @@ static int launch_256(GemmParams& p, hipStream_t stream) {
   const Form256 f = gemm256_form(p, AMODE, kPrecOf<T>, cus, &why_not);
   if (f.err != MD_OK) MD_FAIL(f.err, "%s", why_not.c_str());
   if (f.blocks <= 0) return MD_OK;
+  gemm_record_form(f);
   prep_tile_map(p, tiles_m, cdiv(p.N, BN));
   if (f.family != F256_ONE_TILE) p.ptiles = f.ptiles, p.stagger = f.stagger;
   const dim3 grid((unsigned)f.grid, (unsigned)(p.batch > 1 ? p.batch : 1));  // (the tile loops never run batched)

@@ -1107,6 +1107,161 @@ int md_op_ln_finish(md_device_t dev, const float* parts, int64_t rows, float inv
   return MD_OK;
 }
 
+// ---- the GEMM forms of the ViT token stream alone ----
+namespace {
+// a storage-typed output of md_op_vit_gemm: narrowed from the caller's fp32 values before the launch, widened back behind it, so the
+// bytes the launch leaves alone return as they came
+struct StorageOut {
+  DevBuf buf;
+  float* user = nullptr;
+  long count = 0;
+  int width = 0;
+  int open(float* u, long n, int w, int prec, hipStream_t st) {
+    user = u; count = n; width = w;
+    MD_TRY(buf.alloc((size_t)n * storage_bytes(prec)));
+    return launch_f32_to_rows(u, n, buf.p, prec, st, w);
+  }
+  int close(int prec, hipStream_t st) { return launch_rows_to_f32(buf.p, count, user, prec, st, width); }
+};
+}  // namespace
+
+int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* d, void* stream) {
+  if (!dev || !d || !d->a) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  const int prec = d->precision, kind = d->kind, N = d->N, K = d->K, G = d->ngroups;
+  if (!token_op_prec(prec) && !(prec == MD_PREC_FP8 && kind == MD_VIT_GEMM_RESID)) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: kind %d has no precision %d", kind, prec);
+  if (kind < MD_VIT_GEMM_RESID || kind > MD_VIT_GEMM_PATCH_EMBED) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: kind %d", kind);
+  if (G < 1 || G > kMaxGroups) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: %d groups (1..%d)", G, kMaxGroups);
+  if (N <= 0 || N % 4 != 0 || K <= 0 || K % ke_of(prec) != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: N=%d (x4), K=%d (x%d)", N, K, ke_of(prec));
+  if (d->a_rows <= 0 || d->out_rows <= 0) MD_FAIL(MD_ERR_SHAPE, "vit_gemm: a_rows=%d out_rows=%d", d->a_rows, d->out_rows);
+  const bool patch = kind == MD_VIT_GEMM_PATCH_EMBED, resid = kind == MD_VIT_GEMM_RESID, qkv = kind == MD_VIT_GEMM_QKV;
+  const bool producer = resid && d->g[0].gamma_next, consumer = (qkv || kind == MD_VIT_GEMM_FC1) && d->g[0].c;
+  // the row space the groups' output rows live in: patch rows for the patch embedding (x row = seq * S + 1 + p), else rows of the outputs
+  long row_space = d->out_rows;
+  if (patch) {
+    if (d->P <= 0 || d->S < 1 + d->P || d->out_rows % d->S != 0 || !d->x) MD_FAIL(MD_ERR_SHAPE, "vit_gemm: patch embed P=%d S=%d rows=%d", d->P, d->S, d->out_rows);
+    row_space = (long)(d->out_rows / d->S) * d->P;
+  }
+  // fold consumer and V^T store: four-row groups all inside or all outside a weight group, as the token buffers (rows padded to x4) give them
+  const int row_mult = (consumer || qkv) ? 4 : 1;
+  for (int g = 0; g < G; ++g) {
+    const md_vit_gemm_group& q = d->g[g];
+    if (!q.w || !q.bias) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: group %d has no weight / bias", g);
+    if (q.rows <= 0 || q.row0 < 0 || (long)q.row0 + q.rows > row_space || q.arow0 < 0 || (long)q.arow0 + q.rows > d->a_rows)
+      MD_FAIL(MD_ERR_SHAPE, "vit_gemm: group %d = rows [%d, +%d) from A row %d outside %ld output / %d A rows", g, q.row0, q.rows, q.arow0, row_space, d->a_rows);
+    if (q.rows % row_mult != 0 || q.row0 % row_mult != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: group %d: rows [%d, +%d) must be multiples of %d here", g, q.row0, q.rows, row_mult);
+    if (resid && !q.scale) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: group %d has no LayerScale", g);
+    if (patch && !q.pos) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: group %d has no position table", g);
+    if ((resid && !q.gamma_next != !producer) || (!resid && !patch && !q.c != !consumer)) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: the LayerNorm fold is for every group or for none");
+  }
+  if (producer || consumer) {  // (gemm256_form refuses the rest; the smaller tiles would silently ignore the fold's fields)
+    if (d->tile != TILE_256x256 || N % 256 != 0 || prec == MD_PREC_F32 || prec == MD_PREC_FP8) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: the LayerNorm fold runs on the 256 x 256 kernel, 16-bit operands, N %% 256 == 0");
+    if (producer && (!d->ln_out || !d->ln_stats_out)) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: fold producer outputs missing");
+    if (consumer && (!d->ln_stats || (d->ln_raw && K != 1024))) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: fold consumer statistics missing (raw partials: four per row, K = 1024)");
+  }
+  const int D = d->D, S = d->S, heads = D / 64, kpad = (S + 63) / 64 * 64;
+  size_t vt_elems = 0;
+  if (resid && !d->x) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: x missing");
+  if (kind == MD_VIT_GEMM_FC1 && !d->out) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: out missing");
+  if (qkv) {
+    if (!d->qk || !d->vT) MD_FAIL(MD_ERR_INVALID_ARG, "vit_gemm: qk / vT missing");
+    if (D <= 0 || D % 64 != 0 || N != 3 * D || S <= 0 || S % 4 != 0 || d->out_rows % S != 0) MD_FAIL(MD_ERR_SHAPE, "vit_gemm: qkv N=%d D=%d S=%d rows=%d", N, D, S, d->out_rows);
+    vt_elems = (size_t)(d->out_rows / S) * heads * 64 * kpad;
+    if (vt_elems >= ((size_t)1 << 31) || (long)d->out_rows * 2 * D >= (1L << 31)) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: tensors of this size are not a test");
+  }
+  const KsplitScope ksplit(1);  // as md_op_linear_tile: the k-split form of the 64 x 64 kernel is what the DA3 engine runs
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const bool split = prec == MD_PREC_F16X2, f8 = prec == MD_PREC_FP8;
+  const int xm = split ? 2 : 1;
+
+  // ---- operands, staged as md_op_linear_tile stages them ----
+  DevBuf xa, wa[kMaxGroups], ws[kMaxGroups];
+  GemmParams p;
+  int terms = 1;
+  MD_TRY(xa.alloc((size_t)d->a_rows * K * esz_of(prec) * xm));
+  if (split) {
+    for (int g = 0; g < G; ++g) {  // one K for the launch: three terms as soon as one group's weights are not exact halves
+      int t = 2;
+      MD_TRY(split_terms_of(d->g[g].w, (long)N * K, st, &t));
+      terms = std::max(terms, t);
+    }
+    MD_TRY(launch_f32_to_rows(d->a, (long)d->a_rows * K, xa.p, prec, st, K));
+  } else if (f8) {
+    if (((long)d->a_rows * K) % 4 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: e4m3 A operand: a_rows * K must be a multiple of 4");
+    p.ascale = 8.0f / 448.0f;
+    MD_TRY(launch_f32_to_fp8(d->a, (long)d->a_rows * K, 1.0f / p.ascale, xa.p, st));
+  } else {
+    MD_TRY(launch_f32_to_rows(d->a, (long)d->a_rows * K, xa.p, prec, st));
+  }
+  for (int g = 0; g < G; ++g) {
+    const md_vit_gemm_group& q = d->g[g];
+    MD_TRY(wa[g].alloc((size_t)N * K * esz_of(prec) * (split ? terms : 1)));
+    if (split) {
+      PackEntry e;
+      e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; e.kp = K; e.terms = terms; e.dst = wa[g].p;
+      MD_TRY(pack_weight(q.w, e, prec, st));
+    } else if (f8) {
+      MD_TRY(ws[g].alloc((size_t)N * 4));
+      MD_TRY(launch_pack_fp8_rows(q.w, N, K, K, wa[g].p, (float*)ws[g].p, st));
+      p.wscale[g] = (const float*)ws[g].p;
+    } else {
+      MD_TRY(launch_f32_to_rows(q.w, (long)N * K, wa[g].p, prec, st));
+    }
+    p.g_row0[g] = q.row0; p.g_rows[g] = q.rows; p.g_arow0[g] = q.arow0;
+    p.W[g] = wa[g].p; p.bias[g] = q.bias; p.scale[g] = q.scale; p.pos[g] = q.pos;
+    if (producer) p.ln_gamma[g] = q.gamma_next;
+    if (consumer) p.ln_c[g] = q.c;
+  }
+  p.N = N; p.K = K * terms; p.ngroups = G; p.A = xa.p; p.lda = (long)K * xm;
+  p.a_wrap = terms == 3 ? 2 * K / ke_of(prec) : 0;
+  if (consumer) {
+    p.ln_stats = d->ln_stats; p.ln_raw = d->ln_raw ? 1 : 0; p.ln_parts = K / 256; p.ln_inv_n = d->ln_inv_n; p.ln_eps = d->ln_eps;
+  }
+
+  // ---- the epilogue and its outputs ----
+  StorageOut o1, o2;
+  const long rows = d->out_rows;
+  if (resid) {
+    p.epi = EPI_RESID_LS; p.ldo = N;
+    p.out = d->x_out ? d->x_out : d->x;
+    p.resid_src = d->x_out ? d->x : nullptr;
+    if (producer) {
+      MD_TRY(o1.open(d->ln_out, rows * N, N, prec, st));
+      p.ln_out = o1.buf.p; p.ln_ldo = (long)N * xm; p.ln_plane = split ? N : 0;
+      p.ln_stats_out = d->ln_stats_out; p.ln_parts = N / 256;
+    }
+  } else if (qkv) {
+    MD_TRY(o1.open(d->qk, rows * 2 * D, D, prec, st));  // (no slack rows: every row is the caller's and returns to it) split-half rows [q_hi | q_lo | k_hi | k_lo] = 2 * rows rows of [hi: D | lo: D]
+    MD_TRY(o2.open(d->vT, (long)vt_elems, (int)vt_elems, prec, st));     // split-half: the lo plane behind the whole hi plane
+    p.epi = EPI_QKV; p.out = o1.buf.p; p.vT = o2.buf.p; p.v_plane = split ? (long)vt_elems : 0;
+    p.seq_stride = S; p.embed = D; p.heads = heads; p.kpad = kpad; p.qscale = attn_qscale(prec);
+  } else if (kind == MD_VIT_GEMM_FC1) {
+    p.epi = EPI_STORE; p.act = ACT_GELU; p.ldo = N;
+    if (prec == MD_PREC_F32) {
+      p.out_f32 = 1; p.out = d->out;
+    } else {
+      MD_TRY(o1.open(d->out, rows * N, N, prec, st));
+      p.out = o1.buf.p; p.ldo = (long)N * xm; p.o_plane = split ? N : 0;
+    }
+  } else {
+    p.epi = EPI_PATCH_EMBED; p.out = d->x; p.ldo = N; p.seq_stride = S; p.seq_patches = d->P; p.embed = N;
+  }
+  gemm_forget_form();
+  MD_TRY(launch_gemm(p, A_DENSE, prec, d->tile, st));
+  if (o1.user) MD_TRY(o1.close(prec, st));
+  if (o2.user) MD_TRY(o2.close(prec, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_debug_gemm_last_form(int out[8]) {
+  if (!out) return MD_ERR_INVALID_ARG;
+  const Form256 f = gemm_last_form();
+  out[0] = f.family; out[1] = f.ek; out[2] = f.fold; out[3] = f.qkv; out[4] = f.conv; out[5] = f.diag;
+  out[6] = (int)std::min<long>(f.blocks, 0x7fffffffL); out[7] = f.grid;
+  return MD_OK;
+}
+
 int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* add_dev, int B,
                            int Cin, int H, int W, int Cout, int k, int stride, int pad, int relu, int in_precision, int out_ld,
                            float* out_dev, void* stream) {
@@ -1169,6 +1324,8 @@ int md_debug_gemm_stagger(int which, int ticks) {
   md::gemm_stagger(which, ticks);
   return MD_OK;
 }
+
+int md_debug_gemm_stagger_ticks(int which) { return which < 0 || which > 3 ? MD_ERR_INVALID_ARG : md::gemm_stagger_ticks(which); }
 
 int md_gemm_ksplit_launches(void) { return (int)(md::gemm_ksplit_launches() & 0x7fffffff); }
 

@@ -360,6 +360,48 @@ def ln_finish(dev: Device, parts: torch.Tensor, inv_n: float, eps: float) -> tor
     return ab
 
 
+def vit_gemm(dev: Device, kind: int, a: torch.Tensor, groups, precision: int, tile: int = _lib.TILE_AUTO, *, x: Optional[torch.Tensor] = None,
+             x_out: Optional[torch.Tensor] = None, ln_out: Optional[torch.Tensor] = None, ln_stats_out: Optional[torch.Tensor] = None,
+             ln_stats: Optional[torch.Tensor] = None, ln_raw: bool = False, ln_eps: float = 0.0, ln_inv_n: float = 0.0, S: int = 0, D: int = 0,
+             P: int = 0, qk: Optional[torch.Tensor] = None, vT: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> None:
+    """md_op_vit_gemm: one GEMM form of the ViT token stream (kind = _lib.VIT_GEMM_*) on the CALLER's buffers -- contiguous fp32 device
+    tensors, updated in place; nothing is pre-filled. a [a_rows, K]; groups = dicts with row0, rows, arow0, w [N, K], bias [N] and, by
+    kind, scale, gamma_next, c, pos."""
+    tensors = [a, x, x_out, ln_out, ln_stats_out, ln_stats, qk, vT, out] + [g.get(k) for g in groups for k in ("w", "bias", "scale", "gamma_next", "c", "pos")]
+    for t in tensors:
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32), "vit_gemm takes contiguous fp32 device tensors"
+    d = _lib.MdVitGemm()
+    d.kind, d.precision, d.tile = kind, precision, tile
+    d.N, d.K = groups[0]["w"].shape
+    d.a_rows, d.a, d.ngroups = a.shape[0], a.data_ptr(), len(groups)
+    assert a.shape[1] == d.K and 1 <= len(groups) <= 4
+    for i, g in enumerate(groups):
+        assert g["w"].shape == (d.N, d.K) and g["bias"].shape == (d.N,)
+        d.g[i].row0, d.g[i].rows, d.g[i].arow0 = g["row0"], g["rows"], g.get("arow0", g["row0"])
+        for k in ("w", "bias", "scale", "gamma_next", "c", "pos"):
+            setattr(d.g[i], k, g[k].data_ptr() if g.get(k) is not None else None)
+    first = next(t for t in (x, qk, out) if t is not None)
+    d.out_rows = first.shape[0]
+    for name, t, cols in (("x", x, d.N), ("x_out", x_out, d.N), ("ln_out", ln_out, d.N), ("out", out, d.N), ("qk", qk, 2 * D)):
+        assert t is None or t.shape == (d.out_rows, cols), name
+        setattr(d, name, t.data_ptr() if t is not None else None)
+    assert ln_stats_out is None or ln_stats_out.shape == (d.out_rows, d.N // 256, 2)
+    assert ln_stats is None or ln_stats.shape == ((d.out_rows, 4, 2) if ln_raw else (d.out_rows, 2))
+    assert vT is None or vT.shape == (d.out_rows // S, D // 64, 64, (S + 63) // 64 * 64)
+    d.ln_stats_out = ln_stats_out.data_ptr() if ln_stats_out is not None else None
+    d.ln_stats = ln_stats.data_ptr() if ln_stats is not None else None
+    d.vT = vT.data_ptr() if vT is not None else None
+    d.ln_raw, d.ln_eps, d.ln_inv_n, d.S, d.D, d.P = int(ln_raw), ln_eps, ln_inv_n, S, D, P
+    _lib.check(_lib.load().md_op_vit_gemm(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
+
+
+def gemm_last_form() -> dict:
+    """md_debug_gemm_last_form: what this thread's last 256 x 256 GEMM launch ran (family -1: md_op_vit_gemm took another tile)."""
+    v = (C.c_int * 8)()
+    _lib.check(_lib.load().md_debug_gemm_last_form(C.byref(v)))
+    return dict(zip(("family", "ek", "fold", "qkv", "conv", "diag", "blocks", "grid"), list(v)))
+
+
 def conv2d_direct_ex(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor], stride: int,
                      pad: int, relu: bool, in_precision: int, out_ld: int, out: torch.Tensor) -> torch.Tensor:
     """md_op_conv2d_direct_ex: x [B, Cin, H, W], w [Cout, Cin, k, k], add fp32 NHWC or None -> a copy of the pre-filled fp32

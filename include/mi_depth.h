@@ -628,6 +628,48 @@ int md_op_ln_fold_vectors(md_device_t dev, const float* w, const float* gamma, c
                           int precision, float* c, float* d, void* stream);
 /* parts [rows][4][2] = (mean, centred sum of squares) of four 256-column tiles -> ab [rows][2] = (rstd, -mu * rstd). */
 int md_op_ln_finish(md_device_t dev, const float* parts, int64_t rows, float inv_n, float eps, float* ab, void* stream);
+/* ---- the GEMM forms of the ViT token stream alone (test-only): the residual + LayerScale update of proj / fc2 (with the LayerNorm
+ * fold's producer part), the QKV projection and fc1's GELU store (with the fold's consumer part), the patch embedding. Every tensor is
+ * an fp32 device tensor; operands are staged into `precision`'s storage type as md_op_linear_tile stages them (split-half: two or three
+ * terms by the weights; e4m3: activations on the scale 8/448, weights per row), storage-typed results are widened back. The entry
+ * pre-fills NOTHING: every output buffer is the caller's, a storage-typed one is first narrowed from the caller's values (which must
+ * be exact in the type) and widened back behind the launch, so bytes the launch leaves alone come back as they went in. ---- */
+typedef enum md_vit_gemm_kind { MD_VIT_GEMM_RESID = 0, MD_VIT_GEMM_QKV = 1, MD_VIT_GEMM_FC1 = 2, MD_VIT_GEMM_PATCH_EMBED = 3 } md_vit_gemm_kind;
+typedef struct md_vit_gemm_group {
+  int row0, rows, arow0;   /* first output row, rows, first A row (groups may alias A rows) */
+  const float* w;          /* [N, K] */
+  const float* bias;       /* [N]; fold consumer: d */
+  const float* scale;      /* RESID: LayerScale [N] */
+  const float* gamma_next; /* RESID, optional (all groups or none): the fold's producer part */
+  const float* c;          /* QKV / FC1, optional (all groups or none): the fold's consumer part */
+  const float* pos;        /* PATCH_EMBED: [1 + P, N] */
+} md_vit_gemm_group;
+typedef struct md_vit_gemm {
+  int kind, precision, tile;
+  int N, K;                /* QKV: N = 3 D */
+  int a_rows;              /* rows of a */
+  const float* a;          /* [a_rows, K] */
+  int ngroups;             /* 1 .. 4 */
+  md_vit_gemm_group g[4];
+  int out_rows;            /* rows of every output below */
+  float* x;                /* RESID: [out_rows, N] in/out (read only when x_out is set); PATCH_EMBED: [nseq * S, N] in/out */
+  float* x_out;            /* RESID, optional: the out-of-place form's output */
+  float* ln_out;           /* RESID producer: [out_rows, N] = gamma_next . x_new in the storage type */
+  float* ln_stats_out;     /* RESID producer: [out_rows, N / 256, 2] (mean, centred sum of squares) per 256-column tile */
+  const float* ln_stats;   /* consumer: ln_raw 1: [out_rows, 4, 2] partials; 0: [out_rows, 2] (rstd, -mu rstd) */
+  int ln_raw;
+  float ln_eps, ln_inv_n;
+  int S, D;                /* QKV: rows per sequence (out_rows = T * S), embedding; PATCH_EMBED: S = rows per sequence of x */
+  int P;                   /* PATCH_EMBED: patches per sequence */
+  float* qk;               /* QKV: [out_rows, 2 D] = q * attn_qscale | k */
+  float* vT;               /* QKV: [T, D / 64, 64, kpad], kpad = S rounded up to 64 */
+  float* out;              /* FC1: [out_rows, N] = gelu(..) in the storage type */
+} md_vit_gemm;
+int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* desc, void* stream);
+/* Host-only: what the calling thread's last launch of the 256 x 256 GEMM family ran -- out[8] = family (0 one tile per workgroup,
+ * 1 the fc1 / QKV / lean-convolution tile loop, 2 the read-modify-write tile loop; -1: md_op_vit_gemm launched another tile), epilogue kind
+ * (the one-tile kernel's EK; for a loop the kind it replaces), fold, qkv, conv, diag, tiles, workgroups. */
+int md_debug_gemm_last_form(int out[8]);
 /* md_op_conv2d_direct as the FOV head runs it: the input held in `in_precision`'s storage type, add = optional fp32 NHWC tensor added
  * to the input, out = fp32 NHWC [B, OH, OW, out_ld] (out_ld 0 = Cout; columns Cout .. out_ld are not written). */
 int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* add_dev, int B,
@@ -675,6 +717,8 @@ int md_debug_gemm_persistent(int mask);
  * which: 0 the read-modify-write loop at <= 16 k-tiles per tile (proj; default 2000), 1 the same at more (fc2; 0), 2 the fc1 loop (0),
  * 3 the QKV loop (0). Same bits. MD_ERR_INVALID_ARG for another `which` or negative ticks. */
 int md_debug_gemm_stagger(int which, int ticks);
+/* The value in force for `which` (so that a test restores what it found); MD_ERR_INVALID_ARG (< 0) for another `which`. */
+int md_debug_gemm_stagger_ticks(int which);
 /* Same for the fused bf16 attention kernel: T sequences of n_tokens, `heads` heads of 64. */
 int md_bench_attention(md_device_t dev, int T, int n_tokens, int heads, int iters, float* avg_ms);
 /* The same with the operand type (MD_PREC_BF16 | MD_PREC_F16) and the range of the random q / k values, uniform in
