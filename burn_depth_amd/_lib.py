@@ -168,6 +168,7 @@ SYMBOLS = {
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),
     "md_da3_infer": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "md_da3_infer_ex": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "md_da3_infer_views": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "md_model_enable_graph": (_I, [_P, _I]),
     "md_da3_infer_with_camera": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "md_gemm_ksplit_launches": (_I, []),
@@ -200,6 +201,7 @@ SYMBOLS = {
     "md_op_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_linear_tile": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_attention": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "md_op_attention_views": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_deconv2x2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_conv2d_direct": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),

@@ -96,11 +96,22 @@ __device__ __forceinline__ void glds16a(const void* g, void* l) {
 // profiles/r05_attention_prio.txt.)
 // The body of one workgroup: `id` = its logical (unit, query block) index. Two kernels run it: attention_kernel (one workgroup per
 // index, XCD-aware block order) and attention_redo_kernel (the safe body over the units the assembly kernel flagged).
-template <typename T, bool FP8OUT, bool FAST, int PTERMS = 1, int KS = 1, int QW = 4>
+//
+// Cross-view keys (MV; attention_views_kernel): the sequences come in groups of `views` consecutive ones (the views
+// of one scene) and a query of any of them attends over the n_tokens keys of EVERY sequence of its group, in sequence order -- one softmax
+// over views * n_tokens keys. The walk is the same walk over views * NT tiles (tile u = view * NT + t sits in ring stage u & 1): K and V^T
+// are addressed from the group's first sequence through ONE descriptor each, a view adds a scalar offset (view * S rows of q | k, view *
+// heads * 64 * kpad elements of V^T), and every view's last tile masks its own rows past n_tokens (behind them lie the padding rows up to S
+// and then the NEXT view's rows: they are read, so the mask is what keeps them out). Row sums, the O accumulator, the fast body's range
+// check (first tile of the first view; a score in a later view that leaves the range shows in the row sums like one in a later tile) and
+// the safe body's running maximum carry across the view boundary unchanged. One key group only (KS = 1): a launch over V views has V
+// times the workgroups of the single-view launch, which is what the key split was there to provide.
+template <typename T, bool FP8OUT, bool FAST, int PTERMS = 1, int KS = 1, int QW = 4, bool MV = false>
 __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T* __restrict__ vT, T* __restrict__ out,
                                                int S, int n_tokens, int heads, int D, int kpad, int qblocks,
-                                               float out_fp8_inv, long v_plane, const int id) {
+                                               float out_fp8_inv, long v_plane, const int id, const int views = 1) {
   constexpr bool SP = is_split<T>::value;
+  static_assert(!MV || (KS == 1 && QW == 4 && !FP8OUT), "cross-view keys run in the plain form");
   constexpr int STAGE = SP ? 32768 : 16384;  // K tile 64x128B + V^T tile 64x128B (split-half: hi tiles, then the lo tiles 16 KB behind)
   // Split-half, one key group (the Depth Pro form): the four tiles of a stage are 32 KB, two stages 64 KB = two workgroups per CU, two
   // waves per SIMD, although the 148 registers allow three. CK (compact K): ONE K buffer (hi | lo, 16 KB) + TWO V^T stages (hi | lo,
@@ -129,7 +140,14 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
   auto kbuf = [&](int t) __attribute__((always_inline)) { return CK ? ring : ring + (t & 1) * STAGE; };
   auto vbuf = [&](int t) __attribute__((always_inline)) { return CK ? ring + 16384 + (t & 1) * 16384 : ring + (t & 1) * STAGE + VOFF; };
   const int unit = id / qblocks, qb = id - unit * qblocks;
-  const int seq = unit / heads, head = unit - seq * heads;
+  int seq = unit / heads, head = unit - seq * heads;
+  int seq0 = seq;  // the sequence K and V^T are addressed from
+  if constexpr (MV) {  // units in (group, head, view) order: the workgroups that walk the same keys are neighbours (one XCD's L2)
+    const int per = views * heads, g = unit / per, w = unit - g * per;
+    head = w / views;
+    seq0 = g * views;
+    seq = seq0 + (w - head * views);
+  }
   const int q0 = qb * (32 * QW) + wave * 32;
   const bool active = q0 < n_tokens;  // wave-uniform
   const int h = lane >> 5, c = lane & 31;
@@ -161,9 +179,13 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
   // them or reads them, they are masked below -- the callers keep >= 64 rows of slack behind the last sequence for the latter.
   // (split-half: k_hi starts 2D into the row and k_lo D behind it: one descriptor, its range extended by that D)
   const int klo_bytes = SP ? D * (int)sizeof(T) : 0;
-  const auto ksrd = __builtin_amdgcn_make_buffer_rsrc((void*)(qk + seq_row0 * two_d + (SP ? 2 * D : D) + head * 64), 0, (int)((unsigned)(n_tokens - 1) * krow_bytes + 128u) + klo_bytes, 0x00020000);
-  const auto vsrd = __builtin_amdgcn_make_buffer_rsrc((void*)(vT + ((long)seq * heads + head) * 64 * kpad), 0, 64 * kpad * (int)sizeof(T), 0x00020000);
-  const auto vsrd_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(vT + (SP ? v_plane : 0) + ((long)seq * heads + head) * 64 * kpad), 0, 64 * kpad * (int)sizeof(T), 0x00020000);
+  // MV: both descriptors start at the group's first sequence and reach to the last view's rows (the launcher keeps that below 2 GB)
+  const long key_row0 = MV ? (long)seq0 * S : seq_row0;
+  const int vview_bytes = MV ? heads * 64 * kpad * (int)sizeof(T) : 0;  // V^T: from one sequence to the next
+  const int kviews_rows = MV ? (views - 1) * S : 0, vviews_bytes = MV ? (views - 1) * vview_bytes : 0;
+  const auto ksrd = __builtin_amdgcn_make_buffer_rsrc((void*)(qk + key_row0 * two_d + (SP ? 2 * D : D) + head * 64), 0, (int)((unsigned)(n_tokens - 1 + kviews_rows) * krow_bytes + 128u) + klo_bytes, 0x00020000);
+  const auto vsrd = __builtin_amdgcn_make_buffer_rsrc((void*)(vT + ((long)seq0 * heads + head) * 64 * kpad), 0, 64 * kpad * (int)sizeof(T) + vviews_bytes, 0x00020000);
+  const auto vsrd_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(vT + (SP ? v_plane : 0) + ((long)seq0 * heads + head) * 64 * kpad), 0, 64 * kpad * (int)sizeof(T) + vviews_bytes, 0x00020000);
   int kvoff[2], vvoff[2];  // NJ <= 2 (a fixed bound: an array of template-dependent size captured by the lambdas below loses the kernel's host stub)
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -173,32 +195,35 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
     vvoff[j] = r0 * kpad * (int)sizeof(T) + lc0 * 16;
   }
   const int NT = (n_tokens + 63) / 64;
-  auto issue_k = [&](int t) __attribute__((always_inline)) {
+  // Tile t of view `vw` into the ring stage of walk position u (one view: u = t, vw = 0).
+  auto issue_k = [&](int u, int t, int vw) __attribute__((always_inline)) {
+    const int row0 = MV ? vw * S : 0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      __attribute__((address_space(3))) char* kb = (__attribute__((address_space(3))) char*)(kbuf(t) + (wave + QW * j) * 1024);
+      __attribute__((address_space(3))) char* kb = (__attribute__((address_space(3))) char*)(kbuf(u) + (wave + QW * j) * 1024);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ksrd, kb + i * 4096, 16, kvoff[j], (t * 64 + i * 32) * (int)krow_bytes, 0, 0);
-        if constexpr (SP) __builtin_amdgcn_raw_ptr_buffer_load_lds(ksrd, kb + KLO + i * 4096, 16, kvoff[j], (t * 64 + i * 32) * (int)krow_bytes + klo_bytes, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ksrd, kb + i * 4096, 16, kvoff[j], (row0 + t * 64 + i * 32) * (int)krow_bytes, 0, 0);
+        if constexpr (SP) __builtin_amdgcn_raw_ptr_buffer_load_lds(ksrd, kb + KLO + i * 4096, 16, kvoff[j], (row0 + t * 64 + i * 32) * (int)krow_bytes + klo_bytes, 0, 0);
       }
     }
   };
-  auto issue_v = [&](int t) __attribute__((always_inline)) {
+  auto issue_v = [&](int u, int t, int vw) __attribute__((always_inline)) {
+    const int v0 = MV ? vw * vview_bytes : 0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      __attribute__((address_space(3))) char* vb = (__attribute__((address_space(3))) char*)(vbuf(t) + (wave + QW * j) * 1024);
+      __attribute__((address_space(3))) char* vb = (__attribute__((address_space(3))) char*)(vbuf(u) + (wave + QW * j) * 1024);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(vsrd, vb + i * 4096, 16, vvoff[j], t * 128 + i * 32 * kpad * (int)sizeof(T), 0, 0);
-        if constexpr (SP) __builtin_amdgcn_raw_ptr_buffer_load_lds(vsrd_lo, vb + VLO + i * 4096, 16, vvoff[j], t * 128 + i * 32 * kpad * (int)sizeof(T), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(vsrd, vb + i * 4096, 16, vvoff[j], v0 + t * 128 + i * 32 * kpad * (int)sizeof(T), 0, 0);
+        if constexpr (SP) __builtin_amdgcn_raw_ptr_buffer_load_lds(vsrd_lo, vb + VLO + i * 4096, 16, vvoff[j], v0 + t * 128 + i * 32 * kpad * (int)sizeof(T), 0, 0);
       }
     }
   };
   // the whole tile's requests (CK: only the V^T half; K follows at the previous tile's mid barrier)
-  auto issue = [&](int t) __attribute__((always_inline)) {
-    if constexpr (!CK) issue_k(t);
-    issue_v(t);
+  auto issue = [&](int u, int t, int vw) __attribute__((always_inline)) {
+    if constexpr (!CK) issue_k(u, t, vw);
+    issue_v(u, t, vw);
   };
 
   // LDS read offsets. K rows are read through the bit-2/bit-3 swap; V^T rows (= d) directly.
@@ -225,27 +250,38 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
   float m_run, l_run;
   bool bad = false;  // wave-uniform: a fast-body range check failed
 
+  int cv = 0;  // MV: the view whose tiles are being walked
+  // what follows tile t of view cv in the walk, handed to `f(u + 1, tile, view)`: the view's next tile, or the next view's first
+  auto with_next = [&](int u, int t, auto f) __attribute__((always_inline)) {
+    if constexpr (MV) {
+      const bool wrap = t + 1 >= NT;
+      const int nv = wrap ? cv + 1 : cv;
+      if (nv < views) f(u + 1, wrap ? 0 : t + 1, nv);
+    } else {
+      if (t + 1 < NT) f(t + 1, t + 1, 0);
+    }
+  };
   // every wave of the workgroup runs these statements exactly once per tile
-  auto top = [&](int t) __attribute__((always_inline)) {
+  auto top = [&](int u, int t) __attribute__((always_inline)) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (t + 1 < NT) issue(t + 1);
+    with_next(u, t, issue);
   };
   // CK: behind a tile's score MFMAs -- every wave has read its K fragments (the MFMAs that consumed them are issued) -- the single K
   // buffer takes the next tile's K. An inactive wave (no valid query) meets the same barrier from `idle_mid`.
-  auto mid = [&](int t) __attribute__((always_inline)) {
+  auto mid = [&](int u, int t) __attribute__((always_inline)) {
     if constexpr (CK) {
       // a raw barrier behind the wave's own LDS reads: __syncthreads() would also drain vmcnt, i.e. wait for the V^T tile requested
       // a few hundred cycles ago at the top of this tile
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (t + 1 < NT) issue_k(t + 1);
+      with_next(u, t, issue_k);
     }
   };
   // S^T[sub] = K[sub] . Q^T (log2 units: q is pre-scaled); register r of lane half h holds local key (r&7) + 8h + 16(r>>3)
-  auto scores_sub = [&](int t, int sub, f32x16_t& st) __attribute__((always_inline)) {
-    const char* sb = kbuf(t);
+  auto scores_sub = [&](int u, int sub, f32x16_t& st) __attribute__((always_inline)) {
+    const char* sb = kbuf(u);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const i32x4_t kf = *(const i32x4_t*)(sb + (koff[sub] ^ (s << 5)));
@@ -297,8 +333,8 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
     }
   };
   // O^T[dt] += V^T[dt][keys of sub] . P^T[sub]: k-step s2 holds local keys 16 s2 .. 16 s2 + 15 of the 32-key block
-  auto pv_sub = [&](int t, int sub, const i32x4_t (&pf)[2], const i32x4_t (&pfl)[2], int nsteps) __attribute__((always_inline)) {
-    const char* sb = vbuf(t);
+  auto pv_sub = [&](int u, int sub, const i32x4_t (&pf)[2], const i32x4_t (&pfl)[2], int nsteps) __attribute__((always_inline)) {
+    const char* sb = vbuf(u);
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       if (s2 < nsteps) {
@@ -318,16 +354,17 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
   // One 64-key tile. SAFE: running maximum; PARTIAL: the sequence ends inside the tile -- blocks and k-steps without a
   // valid key are skipped (Depth Pro: 577 = 9 x 64 + 1 keys, the last tile costs 4 + 2 MFMAs instead of 16); CHECK: the
   // fast body's one-time range check on the true row maxima (first tile: key 0 is always valid: finite, +inf or NaN).
-  auto tile = [&](int t, auto safe_c, auto partial_c, auto check_c) __attribute__((always_inline)) {
+  // (u: the ring stage's walk position, t: the tile inside its sequence -- what the mask counts from)
+  auto tile = [&](int u, int t, auto safe_c, auto partial_c, auto check_c) __attribute__((always_inline)) {
     constexpr bool SAFE = decltype(safe_c)::value, PARTIAL = decltype(partial_c)::value, CHECK = decltype(check_c)::value;
     const int rem = PARTIAL ? n_tokens - t * 64 : 64;  // valid keys of this tile (wave-uniform)
     const bool two = !PARTIAL || rem > 32;             // the second 32-key block holds valid keys
     f32x16_t st0, st1;
     i32x4_t pf0[2], pf1[2], pfl0[2], pfl1[2];
     float ps[4] = {0.f, 0.f, 0.f, 0.f};
-    scores_sub(t, 0, st0);
-    if (two) scores_sub(t, 1, st1);
-    mid(t);
+    scores_sub(u, 0, st0);
+    if (two) scores_sub(u, 1, st1);
+    mid(u, t);
     if constexpr (PARTIAL) {
       mask_sub(t, 0, st0);
       if (two) mask_sub(t, 1, st1);
@@ -355,10 +392,10 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
     }
     typedef std::integral_constant<bool, !SAFE && !kOffsetFast> no_offset_t;
     exp_pack_sub(st0, m_run, pf0, pfl0, ps, no_offset_t());
-    pv_sub(t, 0, pf0, pfl0, PARTIAL && rem <= 16 ? 1 : 2);
+    pv_sub(u, 0, pf0, pfl0, PARTIAL && rem <= 16 ? 1 : 2);
     if (two) {
       exp_pack_sub(st1, m_run, pf1, pfl1, ps, no_offset_t());
-      pv_sub(t, 1, pf1, pfl1, PARTIAL && rem <= 48 ? 1 : 2);
+      pv_sub(u, 1, pf1, pfl1, PARTIAL && rem <= 48 ? 1 : 2);
     }
     l_run += (ps[0] + ps[1]) + (ps[2] + ps[3]);
   };
@@ -374,25 +411,51 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
       for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     m_run = SAFE ? -INFINITY : 0.f;  // safe: alpha = 2^-inf = 0 multiplies zeros at the first tile
     l_run = 0.f;
-    if constexpr (KS == 1) {
-      if constexpr (CK) issue_k(0);
-      issue(0);
-      top(0);
+    if constexpr (MV) {
+      // views * NT tiles, the first one peeled for the range check; the stage alternates with the walk position u, not with t
+      cv = 0;
+      if constexpr (CK) issue_k(0, 0, 0);
+      issue(0, 0, 0);
+      top(0, 0);
       if (active) {
-        if (NFULL == 0) tile(0, safe_c, std::true_type(), check_t());
-        else tile(0, safe_c, std::false_type(), check_t());
+        if (NFULL == 0) tile(0, 0, safe_c, std::true_type(), check_t());
+        else tile(0, 0, safe_c, std::false_type(), check_t());
       } else {
-        mid(0);
+        mid(0, 0);
+      }
+      int u = 1;
+      for (; cv < views; ++cv) {
+        for (int t = cv == 0 ? 1 : 0; t < NFULL; ++t, ++u) {
+          top(u, t);
+          if (active) tile(u, t, safe_c, std::false_type(), std::false_type());
+          else mid(u, t);
+        }
+        if (last_partial && (cv > 0 || NT > 1)) {
+          top(u, NT - 1);
+          if (active) tile(u, NT - 1, safe_c, std::true_type(), std::false_type());
+          else mid(u, NT - 1);
+          ++u;
+        }
+      }
+    } else if constexpr (KS == 1) {
+      if constexpr (CK) issue_k(0, 0, 0);
+      issue(0, 0, 0);
+      top(0, 0);
+      if (active) {
+        if (NFULL == 0) tile(0, 0, safe_c, std::true_type(), check_t());
+        else tile(0, 0, safe_c, std::false_type(), check_t());
+      } else {
+        mid(0, 0);
       }
       for (int t = 1; t < NFULL; ++t) {
-        top(t);
-        if (active) tile(t, safe_c, std::false_type(), std::false_type());
-        else mid(t);
+        top(t, t);
+        if (active) tile(t, t, safe_c, std::false_type(), std::false_type());
+        else mid(t, t);
       }
       if (last_partial && NT > 1) {
-        top(NT - 1);
-        if (active) tile(NT - 1, safe_c, std::true_type(), std::false_type());
-        else mid(NT - 1);
+        top(NT - 1, NT - 1);
+        if (active) tile(NT - 1, NT - 1, safe_c, std::true_type(), std::false_type());
+        else mid(NT - 1, NT - 1);
       }
     } else {
       // this group's tiles [tb, te): a quarter of the keys in the fast pass; the safe pass runs on group 0 alone. Every wave of
@@ -405,22 +468,22 @@ __device__ __forceinline__ void attention_body(const T* __restrict__ qk, const T
       auto top_g = [&](int t) __attribute__((always_inline)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (t + 1 < te) issue(t + 1);
+        if (t + 1 < te) issue(t + 1, t + 1, 0);
       };
       if (n > 0) {
-        issue(tb);
+        issue(tb, tb, 0);
         top_g(tb);
         if (active) {
-          if (nfull == 0) tile(tb, safe_c, std::true_type(), check_t());
-          else tile(tb, safe_c, std::false_type(), check_t());
+          if (nfull == 0) tile(tb, tb, safe_c, std::true_type(), check_t());
+          else tile(tb, tb, safe_c, std::false_type(), check_t());
         }
         for (int t = tb + 1; t < tb + nfull; ++t) {
           top_g(t);
-          if (active) tile(t, safe_c, std::false_type(), std::false_type());
+          if (active) tile(t, t, safe_c, std::false_type(), std::false_type());
         }
         if (nfull < n && n > 1) {
           top_g(te - 1);
-          if (active) tile(te - 1, safe_c, std::true_type(), std::false_type());
+          if (active) tile(te - 1, te - 1, safe_c, std::true_type(), std::false_type());
         }
       }
       for (int i = n; i < per; ++i) {
@@ -520,6 +583,16 @@ __global__ __launch_bounds__(64 * QW * KS, is_split<T>::value ? (KS == 1 ? 3 : 2
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
   const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   attention_body<T, FP8OUT, FAST, PTERMS, KS, QW>(qk, vT, out, S, n_tokens, heads, D, kpad, qblocks, out_fp8_inv, v_plane, id);
+}
+
+// Cross-view keys: the same grid and block order; units are (group of `views` sequences, head, view).
+template <typename T, int PTERMS = 1>
+__global__ __launch_bounds__(256, is_split<T>::value ? 3 : 4) void attention_views_kernel(const T* __restrict__ qk, const T* __restrict__ vT, T* __restrict__ out,
+                                                           int S, int n_tokens, int heads, int D, int kpad, int qblocks, long v_plane, int views) {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  attention_body<T, false, true, PTERMS, 1, 4, true>(qk, vT, out, S, n_tokens, heads, D, kpad, qblocks, 0.f, v_plane, id, views);
 }
 
 // The units (sequence, head) whose row sums left the fast body's range in the assembly kernel (attn577_gfx950.s raises redo[unit]) run
@@ -767,6 +840,53 @@ int launch_attention(const void* qk, const void* vT, void* out, int nseq, int S,
   } else {
     hipLaunchKernelGGL((attention_kernel<bf16_t, false, true>), grid, block, 0, s, (const bf16_t*)qk, (const bf16_t*)vT, (bf16_t*)out, S,
                        n_tokens, heads, D, kpad, qblocks, out_fp8_inv, 0L);
+  }
+  MD_HIP(hipGetLastError());
+  return MD_OK;
+}
+
+// Cross-view keys: `nseq` sequences in groups of `views` consecutive ones; every query attends over the keys of its whole group
+// (attention_body, MV). views = 1 is launch_attention itself.
+int launch_attention_views(const void* qk, const void* vT, void* out, int nseq, int views, int S, int n_tokens, int heads, int D,
+                           int kpad, int prec, hipStream_t s, long v_plane, int* redo, int redo_units) {
+  if (views == 1) return launch_attention(qk, vT, out, nseq, S, n_tokens, heads, D, kpad, prec, s, 0.f, v_plane, redo, redo_units);
+  if (prec != MD_PREC_BF16 && prec != MD_PREC_F16 && prec != MD_PREC_F16X2) MD_FAIL(MD_ERR_UNSUPPORTED, "cross-view attention takes bf16, f16 or split-half operands (precision %d)", prec);
+  if (views < 1 || nseq <= 0 || nseq % views != 0) MD_FAIL(MD_ERR_SHAPE, "cross-view attention: %d sequences in groups of %d", nseq, views);
+  if (D != heads * 64) MD_FAIL(MD_ERR_UNSUPPORTED, "attention: head_dim must be 64 (D=%d heads=%d)", D, heads);
+  if (n_tokens <= 0 || S < n_tokens) MD_FAIL(MD_ERR_SHAPE, "attention: %d tokens in sequences of %d rows", n_tokens, S);
+  if (kpad % 64 != 0 || kpad < (n_tokens + 63) / 64 * 64)
+    MD_FAIL(MD_ERR_INVALID_ARG, "attention: kpad=%d must be a multiple of 64 covering %d keys", kpad, n_tokens);
+  const int planes = prec == MD_PREC_F16X2 ? 2 : 1;
+  // one descriptor spans the q | k rows of a whole group, another its V^T tiles
+  if ((long)views * S * 2 * D * 2 * planes >= (1L << 31) || (long)views * heads * 64 * kpad * 2 >= (1L << 31))
+    MD_FAIL(MD_ERR_UNSUPPORTED, "cross-view attention: %d views of %d rows exceed the 2-GB descriptor range", views, S);
+  const int qblocks = (n_tokens + 127) / 128;
+  const long blocks = (long)qblocks * heads * nseq;
+  if (blocks > 0x7fffffffL) MD_FAIL(MD_ERR_UNSUPPORTED, "attention: %d sequences", nseq);
+  const dim3 grid((unsigned)blocks), block(256);
+  if (prec == MD_PREC_F16X2) {
+    if (v_plane <= 0) MD_FAIL(MD_ERR_INVALID_ARG, "attention: split-half operands need the V^T plane offset");
+    constexpr int smem = 49152 + 16;  // the compact-K form
+    auto go = [&](auto kern) -> int {
+      static std::atomic<unsigned long> attr_set{0};  // the attribute is per device: once per (kernel, device ordinal)
+      int ordinal = 0;
+      MD_HIP(hipGetDevice(&ordinal));
+      const unsigned long bit = (ordinal >= 0 && ordinal < 64) ? 1ul << ordinal : 0ul;
+      if (!bit || !(attr_set.load(std::memory_order_acquire) & bit)) {
+        MD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        attr_set.fetch_or(bit, std::memory_order_release);
+      }
+      hipLaunchKernelGGL(kern, grid, block, smem, s, (const f16s_t*)qk, (const f16s_t*)vT, (f16s_t*)out, S, n_tokens, heads, D, kpad, qblocks, v_plane, views);
+      return MD_OK;
+    };
+    if (attn_pterms() == 1) MD_TRY(go(attention_views_kernel<f16s_t, 1>));
+    else MD_TRY(go(attention_views_kernel<f16s_t, 2>));
+  } else if (prec == MD_PREC_F16) {
+    hipLaunchKernelGGL((attention_views_kernel<f16_t>), grid, block, 0, s, (const f16_t*)qk, (const f16_t*)vT, (f16_t*)out, S, n_tokens, heads, D,
+                       kpad, qblocks, 0L, views);
+  } else {
+    hipLaunchKernelGGL((attention_views_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)qk, (const bf16_t*)vT, (bf16_t*)out, S, n_tokens, heads, D,
+                       kpad, qblocks, 0L, views);
   }
   MD_HIP(hipGetLastError());
   return MD_OK;

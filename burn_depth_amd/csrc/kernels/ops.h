@@ -264,6 +264,11 @@ int launch_attention(const void* qk, const void* vT, void* out, int nseq, int S,
                      int redo_units = 0);
 // Loads the embedded code object on the CURRENT device (idempotent; not capturable -- call it when a context is created).
 int attention_asm_prepare();
+// Cross-view keys: the nseq sequences come in groups of `views` consecutive ones and every query attends over
+// the n_tokens keys of each sequence of its group, in sequence order (one softmax over views * n_tokens keys). Same layout contract as
+// launch_attention; bf16 / f16 / split-half operands, plain output rows. views = 1 is launch_attention (same launch, same bits).
+int launch_attention_views(const void* qk, const void* vT, void* out, int nseq, int views, int S, int n_tokens, int heads, int D,
+                           int kpad, int prec, hipStream_t s, long v_plane = 0, int* redo = nullptr, int redo_units = 0);
 // Process-wide: may launch_attention take the assembly kernel? Default 1; returns the previous value (A/B runs, the bench).
 int attention_allow_asm(int on);
 // launches of the assembly kernel since the library was loaded (what a bench line says about the form it measured)

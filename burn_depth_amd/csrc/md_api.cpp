@@ -705,9 +705,17 @@ int md_op_linear_tile(md_device_t dev, const float* x_dev, const float* w_dev, c
   return MD_OK;
 }
 
-int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int heads, int precision, float* out_dev, void* stream) {
+// md_op_attention (V = 1) and md_op_attention_views: one staging, one launcher
+static int op_attention(md_device_t dev, const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev, void* stream) {
   if (!dev || !qkv_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (T <= 0 || N <= 0 || heads <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid shape");
+  if (V < 1 || T % V != 0) MD_FAIL(MD_ERR_SHAPE, "%d sequences in groups of %d views", T, V);
+  // MD_OP_POISON_PAD: whatever the staging does not write (rows N .. S of every sequence, the slack rows, columns N .. kpad of V^T)
+  // holds a large finite value (0x7000: 8192 as a half, 1.6e29 as bf16) instead of zero
+  const bool poison = (precision & MD_OP_POISON_PAD) != 0;
+  precision &= ~MD_OP_POISON_PAD;
+  if (poison && precision == MD_PREC_F32) MD_FAIL(MD_ERR_UNSUPPORTED, "MD_OP_POISON_PAD fills 16-bit staging tensors");
+  if (V > 1 && precision == MD_PREC_F32) MD_FAIL(MD_ERR_UNSUPPORTED, "cross-view attention runs in the bf16, f16 and f16x2 modes");
   MD_HIP(hipSetDevice(dev->ordinal));
   hipStream_t st = pick_stream(dev, stream);
   const int D = heads * 64, SS = (N + 3) / 4 * 4, kpad = (N + 63) / 64 * 64;
@@ -716,12 +724,16 @@ int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int hea
   MD_TRY(qk.alloc(((size_t)T * SS + 64) * 2 * D * es));
   MD_TRY(vT.alloc((size_t)T * heads * 64 * kpad * es));
   MD_TRY(ao.alloc(((size_t)T * SS + 64) * D * es));
+  if (poison) {
+    MD_HIP(hipMemsetD16Async((hipDeviceptr_t)qk.p, 0x7000, ((size_t)T * SS + 64) * 2 * D * es / 2, st));
+    MD_HIP(hipMemsetD16Async((hipDeviceptr_t)vT.p, 0x7000, (size_t)T * heads * 64 * kpad * es / 2, st));
+  }
   MD_TRY(launch_qkv_split(qkv_dev, T, N, heads, SS, kpad, qk.p, vT.p, attn_qscale(precision), precision, st));
   if (precision != MD_PREC_F32) {
     DevBuf redo;  // zeroed flags: 577-token bf16 launches take the assembly kernel, like the model's
     MD_TRY(redo.alloc((size_t)attention_redo_ints(T * heads) * 4));
     if (precision == MD_PREC_BF16) MD_TRY(attention_asm_prepare());
-    MD_TRY(launch_attention(qk.p, vT.p, ao.p, T, SS, N, heads, D, kpad, precision, st, 0.f, (long)T * heads * 64 * kpad, (int*)redo.p));
+    MD_TRY(launch_attention_views(qk.p, vT.p, ao.p, T, V, SS, N, heads, D, kpad, precision, st, (long)T * heads * 64 * kpad, (int*)redo.p));
     MD_HIP(hipStreamSynchronize(st));  // `redo` is released at the end of this scope
   } else {
     MD_TRY(sc.alloc((size_t)T * heads * SS * kpad * 4));
@@ -730,6 +742,14 @@ int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int hea
   MD_TRY(launch_unpad_rows(ao.p, T, N, SS, D, out_dev, precision, st));
   MD_HIP(hipStreamSynchronize(st));
   return MD_OK;
+}
+
+int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int heads, int precision, float* out_dev, void* stream) {
+  return op_attention(dev, qkv_dev, T, 1, N, heads, precision, out_dev, stream);
+}
+
+int md_op_attention_views(md_device_t dev, const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev, void* stream) {
+  return op_attention(dev, qkv_dev, T, V, N, heads, precision, out_dev, stream);
 }
 
 int md_op_conv3x3(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B, int Cin, int H, int W,
@@ -1606,6 +1626,18 @@ int md_da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in
   o.depth = out->depth; o.depth_confidence = out->depth_confidence; o.aux = out->aux; o.aux_confidence = out->aux_confidence;
   o.pose_encoding = out->pose_encoding; o.extrinsics = out->extrinsics; o.intrinsics = out->intrinsics;
   return da3_infer_ex(m, nchw, B, H, W, in_kind, o, out_kind, (hipStream_t)stream);
+}
+
+int md_da3_infer_views(md_model_t m, const float* nchw, int B, int V, int H, int W, int in_kind, const md_da3_outputs* out, int out_kind,
+                       void* stream) {
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "outputs struct is null");
+  if (B <= 0 || V <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid input shape [%d,%d,3,%d,%d]", B, V, H, W);
+  if ((long)B * V > 0x7fffffffL) MD_FAIL(MD_ERR_SHAPE, "%d scenes of %d views", B, V);
+  Da3Outputs o;
+  o.depth = out->depth; o.depth_confidence = out->depth_confidence; o.aux = out->aux; o.aux_confidence = out->aux_confidence;
+  o.pose_encoding = out->pose_encoding; o.extrinsics = out->extrinsics; o.intrinsics = out->intrinsics;
+  o.views = V;
+  return da3_infer_ex(m, nchw, B * V, H, W, in_kind, o, out_kind, (hipStream_t)stream);
 }
 
 int md_da3_infer_with_camera(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const float* extrinsics,

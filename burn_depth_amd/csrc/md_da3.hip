@@ -76,6 +76,7 @@ struct md_model_s::Da3State {
   float* rope_cos = nullptr;          // current shape's tables (aliases)
   float* rope_sin = nullptr;
   float *cam_raw = nullptr, *cam_h1 = nullptr, *cam_h2 = nullptr, *pose = nullptr, *extr = nullptr, *intr = nullptr;
+  float* view_tok = nullptr;          // [max_batch, D]: the camera token of every sequence of a multi-view call (slot 0 | slot 1 ...)
   float* pos_aux = nullptr;
   float *conf_stage = nullptr, *aux_stage = nullptr;  // device staging when the caller wants host outputs
   // camera encoder (`infer_with_camera`): grow-only scratch = staged inputs [B*V*21] | encoded tokens [B*D] | kernel scratch
@@ -259,6 +260,7 @@ static int da3_plan(md_model_s* m, bool dry, size_t* total_out) {
   if (c.dual_head) {
     DA3_TAKE(xlocal, float*, rows * D * 4);
     DA3_TAKE(cam_raw, float*, (size_t)B * d->din * 4);
+    DA3_TAKE(view_tok, float*, (size_t)B * D * 4);
     DA3_TAKE(cam_h1, float*, (size_t)B * d->din * 4);
     DA3_TAKE(cam_h2, float*, (size_t)B * d->din * 4);
     DA3_TAKE(pose, float*, (size_t)B * 9 * 4);
@@ -674,9 +676,25 @@ static int da3_tok_index(md_model_s* m, int B, int** out) {
 static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const Da3Outputs& outp, int out_kind,
                            hipStream_t stream);
 
+// what a multi-view call (Da3Outputs::views > 1) asks of the model; checked before anything is launched or captured
+static int da3_check_views(md_model_t m, int B, const Da3Outputs& outp) {
+  const md_model_s::Da3State* d = m->da3;
+  const Da3Cfg& c = d->cfg;
+  if (outp.views == 1) return MD_OK;
+  if (outp.views < 1 || B % outp.views != 0) MD_FAIL(MD_ERR_SHAPE, "%d images in scenes of %d views", B, outp.views);
+  if (B > c.max_batch) MD_FAIL(MD_ERR_SHAPE, "%d scenes of %d views exceed max_batch %d", B / outp.views, outp.views, c.max_batch);
+  if (!c.dual_head) MD_FAIL(MD_ERR_UNSUPPORTED, "multi-view inference needs the extended backbone's global blocks (the mono head has none)");
+  if (outp.tokens[0]) MD_FAIL(MD_ERR_UNSUPPORTED, "multi-view inference runs the backbone; infer_from_tokens has none");
+  if (outp.cam_extrinsics || outp.cam_intrinsics)
+    MD_FAIL(MD_ERR_UNSUPPORTED, "multi-view inference with caller cameras: the camera encoder yields one token per image, not per view");
+  if (m->prec == MD_PREC_F32 || d->fp8) MD_FAIL(MD_ERR_UNSUPPORTED, "multi-view inference runs in the bf16, f16 and f16x2 modes");
+  return MD_OK;
+}
+
 int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const Da3Outputs& outp, int out_kind,
                  hipStream_t stream) {
   if (!m || m->kind != 1 || !m->da3) MD_FAIL(MD_ERR_INVALID_ARG, "not a Depth-Anything-v3 model");
+  MD_TRY(da3_check_views(m, B, outp));
   auto body = [&]() { return da3_infer_eager(m, nchw, B, H, W, in_kind, outp, out_kind, stream); };
   if (!m->graph_enabled) return body();
   MD_HIP(hipSetDevice(m->dev->ordinal));
@@ -686,7 +704,8 @@ int da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   const std::vector<uintptr_t> key = {(uintptr_t)st, (uintptr_t)B, (uintptr_t)H, (uintptr_t)W, (uintptr_t)nchw, (uintptr_t)outp.depth,
                                       (uintptr_t)outp.depth_confidence, (uintptr_t)outp.aux, (uintptr_t)outp.aux_confidence,
                                       (uintptr_t)outp.pose_encoding, (uintptr_t)outp.extrinsics, (uintptr_t)outp.intrinsics,
-                                      (uintptr_t)outp.cam_extrinsics, (uintptr_t)outp.cam_intrinsics, (uintptr_t)outp.cam_views};
+                                      (uintptr_t)outp.cam_extrinsics, (uintptr_t)outp.cam_intrinsics, (uintptr_t)outp.cam_views,
+                                      (uintptr_t)outp.views};
   return run_with_graph(m, st, key, eligible, body);
 }
 
@@ -840,6 +859,17 @@ static int da3_backbone(Run& r, const Da3Call& k, const float* x_dev) {
   vp.tok0_block = c.dual_head ? c.ext_block_start : -1;
   vp.tok0 = k.cam_tok ? k.cam_tok : d->camera_token;
   vp.tok0_stride = k.cam_tok ? D : 0;
+  if (k.outp.views > 1) {
+    // B / views scenes of `views` views: the global blocks attend across a scene, and the learned camera token [1, 2, D] gives slot 0
+    // to view 0 of every scene and slot 1 to the other views -- laid out per sequence in view_tok
+    vp.views = k.outp.views;
+    r.begin("view_tokens");
+    MD_TRY(launch_set_token0(d->view_tok, B, 1, D, d->camera_token + D, r.st, 0));
+    MD_TRY(launch_set_token0(d->view_tok, B / vp.views, vp.views, D, d->camera_token, r.st, 0));
+    r.end();
+    vp.tok0 = d->view_tok;
+    vp.tok0_stride = D;
+  }
   for (int i = 0; i < v.depth; ++i) {
     MD_TRY(run_vit_block(r, vp, i));
     const float* xcur = vp.x;
@@ -1122,6 +1152,7 @@ static int da3_infer_eager(md_model_t m, const float* nchw, int B, int H, int W,
   if (H % v.ps != 0 || W % v.ps != 0)  // depth_anything3/mod.rs:509-520 (assert -> checked precondition)
     MD_FAIL(MD_ERR_SHAPE, "Input %dx%d must be divisible by patch size %d", H, W, v.ps);
   if (B > c.max_batch) MD_FAIL(MD_ERR_SHAPE, "batch %d exceeds max_batch %d", B, c.max_batch);
+  MD_TRY(da3_check_views(m, B, outp));
   MD_HIP(hipSetDevice(m->dev->ordinal));
   MD_TRY(da3_set_shape(m, H, W, false));  // any multiple of the patch size (mod.rs:509-520); a no-op at the current size
   hipStream_t st = model_stream(m, stream);

@@ -404,6 +404,9 @@ struct Da3Outputs {
   // memory kind of the input image. Both set + a model with a camera encoder => the encoded token conditions the backbone.
   const float *cam_extrinsics = nullptr, *cam_intrinsics = nullptr;
   int cam_views = 0;
+  // multi-view inference (md_da3_infer_views): the B images are B / views scenes of `views` views each, scene-major; the global blocks
+  // attend across the views of a scene and views 1.. take the source-view camera token. 1 = every image a scene of its own.
+  int views = 1;
   // `infer_from_tokens` (mod.rs:389-469): the head alone on caller-supplied hook tokens. tokens[i] = [B, tokens_per_image, din] fp32
   // in the memory kind `in_kind`; tokens_per_image = P (patch rows only) or P + 1 (a leading cls row is skipped, `patch_token_start`)
   const float* tokens[4] = {nullptr, nullptr, nullptr, nullptr};

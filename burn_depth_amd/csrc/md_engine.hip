@@ -1123,7 +1123,12 @@ int run_vit_block(Run& r, VitPlan& v, int i) {
     r.end();
   }
   void* vT_w = (char*)v.vT + (size_t)v.s_lo * heads * 64 * v.kpad * m->esz;  // the window's first sequence of the V^T plane
-  if (m->prec != MD_PREC_F32) {
+  if (v.views > 1 && k0.global) {  // cross-view keys: the sequences of a scene share one key set
+    if (m->prec == MD_PREC_F32 || f8) MD_FAIL(MD_ERR_UNSUPPORTED, "cross-view attention runs in the bf16, f16 and f16x2 modes");
+    r.begin("attention_views");
+    MD_TRY(launch_attention_views(trow(v.qk, 2 * D), vT_w, trow(v.ao, D), v.WS, v.views, SS, NT, heads, D, v.kpad, m->prec, r.st, (long)m->vt_plane));
+    r.end();
+  } else if (m->prec != MD_PREC_F32) {
     r.begin("attention");
     MD_TRY(launch_attention(trow(v.qk, 2 * D), vT_w, trow(v.ao, D), v.WS, SS, NT, heads, D, v.kpad, m->prec, r.st, f8 ? a_inv : 0.f,
                             (long)m->vt_plane, v.redo, v.redo_units));

@@ -315,6 +315,7 @@ struct VitPlan {
   const VitW* vit[3] = {nullptr, nullptr, nullptr};
   int glo[3] = {0, 0, 0}, gcnt[3] = {0, 0, 0};
   int s_lo = 0, WS = 0;
+  int views = 1;                            // > 1: global blocks attend across the `views` consecutive sequences of a scene (WS % views == 0)
   int D = 0, heads = 0, SS = 0, NT = 0, kpad = 0;
   float ln_eps = 0.f;
   float* x = nullptr;     // fp32 residual stream; a global block writes `xalt` and the two swap

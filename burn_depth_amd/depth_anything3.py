@@ -137,6 +137,36 @@ class DepthAnything3(DepthPro):
                                              _stream_ptr(self.device.ordinal)))
         return out
 
+    def infer_views(self, x: torch.Tensor, extrinsics=None, intrinsics=None) -> DepthAnything3Inference:
+        """`md_da3_infer_views`: x [B, V, 3, H, W] = B scenes of V views (view 0 is the reference view). The global blocks attend across
+        the views of a scene; every field of the result is [B*V, ...] in (scene, view) order. V = 1 is `infer` on the B images. Caller
+        cameras with V > 1 are MdError(MD_ERR_UNSUPPORTED): the camera encoder yields one token per image, not per view."""
+        if x.dim() != 5 or x.shape[2] != 3:
+            raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,V,3,H,W], got {tuple(x.shape)}")
+        B, V, _, H, W = x.shape
+        if extrinsics is not None or intrinsics is not None:
+            if V > 1:
+                raise _lib.MdError(_lib.MD_ERR_UNSUPPORTED, "multi-view inference with caller cameras: the camera encoder yields one token per image, not per view")
+            return self.infer_with_camera(x.reshape(B, 3, H, W), extrinsics, intrinsics)
+        x = x.contiguous().to(torch.float32)
+        dev = torch.device("cuda", self.device.ordinal)
+        n = B * V
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = DepthAnything3Inference(depth=f(n, H, W))
+        if self.config.dual_head:
+            ps = self.config.patch_size
+            ah, aw = 8 * (H // ps), 8 * (W // ps)
+            out = DepthAnything3Inference(depth=out.depth, depth_confidence=f(n, H, W), aux=f(n, self.config.aux_output_dim - 1, ah, aw),
+                                          aux_confidence=f(n, ah, aw), pose_encoding=f(n, 1, 9), extrinsics=f(n, 1, 3, 4),
+                                          intrinsics=f(n, 1, 3, 3))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        o = _lib.MdDa3Outputs(ptr(out.depth), ptr(out.depth_confidence), ptr(out.aux), ptr(out.aux_confidence), ptr(out.pose_encoding),
+                              ptr(out.extrinsics), ptr(out.intrinsics))
+        in_kind = _lib.MD_MEM_DEVICE if x.is_cuda else _lib.MD_MEM_HOST
+        _lib.check(self._lib.md_da3_infer_views(self._h, C.c_void_p(x.data_ptr()), int(B), int(V), int(H), int(W), in_kind, C.byref(o),
+                                                _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        return out
+
     def infer_into(self, x: torch.Tensor, depth: torch.Tensor, *unused) -> None:
         B, _, H, W = x.shape
         in_kind = _lib.MD_MEM_DEVICE if x.is_cuda else _lib.MD_MEM_HOST

@@ -128,11 +128,25 @@ def linear(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
     return out
 
 
+POISON_PAD = 0x200  # MD_OP_POISON_PAD: the attention staging's padding holds a large finite value instead of zero
+
+
 def attention(dev: Device, qkv: torch.Tensor, heads: int, precision: int = 0) -> torch.Tensor:
     qkv = _f32c(qkv)
     T, N, _ = qkv.shape
     out = torch.empty((T, N, heads * 64), dtype=torch.float32, device=qkv.device)
     _lib.check(_lib.load().md_op_attention(dev.handle, _p(qkv), T, N, heads, precision, _p(out), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def attention_views(dev: Device, qkv: torch.Tensor, views: int, heads: int, precision: int = 0, poison_pad: bool = False) -> torch.Tensor:
+    """`md_op_attention_views`: qkv [T, N, 3*heads*64], the T sequences in groups of `views`; every query attends over the
+    views * N keys of its group (one softmax). views = 1 is `attention`."""
+    precision |= POISON_PAD if poison_pad else 0
+    qkv = _f32c(qkv)
+    T, N, _ = qkv.shape
+    out = torch.empty((T, N, heads * 64), dtype=torch.float32, device=qkv.device)
+    _lib.check(_lib.load().md_op_attention_views(dev.handle, _p(qkv), T, int(views), N, heads, precision, _p(out), _stream_ptr(dev.ordinal)))
     return out
 
 

@@ -478,7 +478,7 @@ class AnyDepthModel:
         self.kind, self.model = kind, model
 
     @staticmethod
-    def load(kind: DepthModelKind, device, checkpoint: str, precision=None) -> "AnyDepthModel":
+    def load(kind: DepthModelKind, device, checkpoint: str, precision=None, max_batch=None) -> "AnyDepthModel":
         """`AnyDepthModel::load`: Depth Pro loads directly; Depth-Anything-v3 tries metric_large then small, small
         first when the file name contains "small" (mod.rs:62-100). Errors carry the reference's message prefix."""
         from . import _lib
@@ -500,6 +500,8 @@ class AnyDepthModel:
         for cfg in configs:
             if precision is not None:
                 cfg.precision = precision
+            if max_batch is not None:  # images per call (`infer_views`: scenes x views)
+                cfg.max_batch = int(max_batch)
             try:
                 return AnyDepthModel(kind, DepthAnything3.load_file(device, cfg, checkpoint))
             except _lib.MdError as e:
@@ -517,6 +519,13 @@ class AnyDepthModel:
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`) included."""
         return self.model.infer_points(x, **kw)
+
+    def infer_views(self, x):
+        """`md_da3_infer_views`: x [B, V, 3, H, W], B scenes of V views -> `DepthAnything3Inference` with every field [B*V, ...].
+        Depth-Anything-v3 `small` only: Depth Pro has no cross-view attention."""
+        if self.kind == DepthModelKind.DEPTH_PRO:
+            raise ValueError("multi-view inference applies to Depth-Anything-v3, not to Depth Pro")
+        return self.model.infer_views(x)
 
     def preferred_input_resolution(self) -> Optional[int]:
         return None if self.kind == DepthModelKind.DEPTH_PRO else self.model.img_size()

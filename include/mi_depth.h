@@ -58,6 +58,10 @@ typedef enum md_precision { MD_PREC_BF16 = 0, MD_PREC_F32 = 1, MD_PREC_FP8 = 2, 
  * result through the engine's storage type (bf16 in the BF16 / FP8 modes) before it is widened to the fp32 output --
  * the store epilogues the engine itself uses -- instead of the fp32 store. Ignored for MD_PREC_F32. */
 #define MD_OP_STORAGE_OUT 0x100
+/* OR into `precision` of md_op_attention / md_op_attention_views (16-bit modes): the staging tensors' padding -- the rows between N and
+ * the sequence stride, the slack rows behind the last sequence, the V^T columns between N and the padded key count -- holds a large
+ * finite value instead of zero before the kernel runs. The result must not change by a bit: the kernel masks what it over-reads. */
+#define MD_OP_POISON_PAD 0x200
 typedef enum md_interp { MD_INTERP_CUSTOM = 0, MD_INTERP_BURN = 1 } md_interp;
 /* synthetic initialisation (no trained weights exist in the reference tree) */
 typedef enum md_init_scheme { MD_INIT_REFERENCE = 0, MD_INIT_PARITY = 1 } md_init_scheme;
@@ -427,6 +431,19 @@ typedef struct md_da3_outputs {
 } md_da3_outputs;
 int md_da3_infer_ex(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const md_da3_outputs* out,
                     int out_kind, void* stream);
+/* Multi-view inference of the dual-head `small` variant (restated from the public Depth-Anything-3 definition,
+ * the reference tree only ever passes one view: parity unpinned). nchw is [B*V, 3, H, W]: B scenes of V views each, scene-major; view 0
+ * of a scene is its reference view (no reordering). Patch embedding, the blocks before `ext_block_start` and the local blocks run per
+ * view exactly as in md_da3_infer_ex on B*V images. Entering block `ext_block_start`, token 0 of view 0 becomes camera_token[:, 0] and
+ * token 0 of views 1 .. V-1 camera_token[:, 1]. In a global block (odd index >= ext_block_start) every query attends over the V * NT
+ * tokens of all views of its scene in view order, one softmax over all of them; q/k-norm, RoPE positions, LayerNorm, the linear layers
+ * and the hooks stay per token. The head and the camera decoder run per view: every output is [B*V, ...] in (scene, view) order with
+ * the per-image shapes of md_da3_outputs. Arithmetic: the mode's operand rounding, fp32 softmax and accumulation, as md_da3_infer_ex.
+ * V = 1 is md_da3_infer_ex on the same batch (same launches, same bits). B*V > max_batch -> MD_ERR_SHAPE. With V > 1: the mono-head
+ * variant (`metric_large`, no global blocks), the fp32 parity mode (its attention materialises one view's scores) and a call that also
+ * carries caller cameras (the camera encoder yields one token per image, not per view) -> MD_ERR_UNSUPPORTED. */
+int md_da3_infer_views(md_model_t m, const float* nchw, int B, int V, int H, int W, int in_kind, const md_da3_outputs* out,
+                       int out_kind, void* stream);
 /* `DepthAnything3::infer_with_camera` (depth_anything3/mod.rs:301-309 -> 522-531): known cameras condition the backbone.
  * extrinsics [B, views, 3, 4] (world-to-camera) and intrinsics [B, views, 3, 3], fp32, in the same memory kind as `nchw`;
  * 1 <= views <= 16. The camera encoder (camera.rs:50-110: pose encoding of each view -> PoseBranch -> token_norm -> a trunk
@@ -557,6 +574,14 @@ int md_op_linear_tile(md_device_t dev, const float* x_dev, const float* w_dev, c
  * softmax(q k^T / 8) v -> [T, N, heads*64]. (burn_dino attention, quiet_softmax=false) */
 int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int heads, int precision, float* out_dev,
                     void* stream);
+/* Cross-view attention (Depth-Anything-v3 global blocks over V views of a scene): the T sequences of
+ * qkv [T, N, 3*heads*64] come in groups of V consecutive ones (T % V == 0, else MD_ERR_SHAPE); a query of sequence g*V + i attends
+ * over the V*N keys of sequences g*V .. g*V + V-1 taken in that order -- ONE softmax over all of them:
+ *   out[g*V+i, n, h*64+d] = sum_{j<V, k<N} softmax_{(j,k)}(q[g*V+i, n, h] . k[g*V+j, k, h] / 8) * v[g*V+j, k, h, d].
+ * Same staging, operand rounding and fp32 softmax / accumulation as md_op_attention; bf16, f16 and f16x2 (the fp32 mode returns
+ * MD_ERR_UNSUPPORTED for V > 1). V = 1 is md_op_attention: the same launch, the same bits. */
+int md_op_attention_views(md_device_t dev, const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev,
+                          void* stream);
 /* Conv2d 3x3 stride 1 pad 1 (burn nn::Conv2d): fp32 NCHW in/out, w [Cout,Cin,3,3]. */
 int md_op_conv3x3(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B, int Cin,
                   int H, int W, int Cout, int pre_relu, int precision, float* out_dev, void* stream);

@@ -15,6 +15,11 @@ Depth-Anything-v3 `small` with its predicted intrinsics / extrinsics in world sp
 filter the cloud (`md_points_opts`); `--conf-percentile Q` first drops the lowest Q % of the confidences on the device
 (`md_infer_points_filtered`; Depth-Anything-v3 `small`, whose confidence has no scale a caller could know in advance).
 
+`--views A.npy B.npy ...` (Depth-Anything-v3 `small`): the images are the views of ONE scene, the first one its reference view; they run
+through `infer_views` (cross-view attention, `md_da3_infer_views`), so depths and cameras are mutually consistent. One depth PNG per
+view is written beside `--output` (`depth_v0.png`, ...). With `--ply` the device outputs go to `ops.filter_views` (`--view-rtol`,
+`--min-views`, `--conf-percentile`) and `ops.unproject` with the model's own extrinsics and intrinsics: one world-space cloud.
+
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
 restored to the original size, min-max normalised and written as an 8-bit PNG (example/inference.rs:103-199)."""
@@ -27,11 +32,68 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def run_views(a) -> int:
+    """--views: one scene through `infer_views`; depth PNGs per view, and with --ply one filtered world-space cloud."""
+    import torch
+    from burn_depth_amd import _lib, ops
+    from burn_depth_amd import pipeline as P
+    from burn_depth_amd.config import Precision
+    from burn_depth_amd.depth_pro import Device
+    from burn_depth_amd.inference import rgb_to_input_tensor
+    if a.model != "depth-anything-3":
+        print("--views applies to Depth-Anything-v3 `small`", file=sys.stderr)
+        return 2
+    imgs = [np.load(v) for v in a.views]
+    for v, im in zip(a.views, imgs):
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            print(f"{v}: expected uint8 [H,W,3], got {im.dtype} {im.shape}", file=sys.stderr)
+            return 2
+    dev = Device(0)
+    try:
+        model = P.AnyDepthModel.load(P.DepthModelKind(a.model), dev, a.checkpoint, Precision.BF16 if a.precision == "bf16" else Precision.F32, max_batch=len(imgs))
+    except RuntimeError as e:
+        print(str(e), file=sys.stderr)
+        return 1
+    preps = [model.prepare_input_image(im) for im in imgs]
+    if len({(p.width, p.height) for p in preps}) != 1:
+        print("--views: the prepared views must share one size", file=sys.stderr)
+        return 2
+    x = torch.stack([rgb_to_input_tensor(p.rgb.tobytes(), p.width, p.height, dev)[0] for p in preps])[None]  # [1, V, 3, H, W]
+    try:
+        out = model.infer_views(x)
+    except _lib.MdError as e:
+        print(str(e), file=sys.stderr)
+        return 1
+    base = a.output or os.path.join(os.path.dirname(os.path.abspath(a.views[0])), "depth.png")
+    stem, ext = os.path.splitext(base)
+    for i, (im, p) in enumerate(zip(imgs, preps)):
+        oh, ow = im.shape[:2]
+        restore = (ow, oh) if (p.width != ow or p.height != oh or p.crop is not None) else None
+        P.save_depth_map(out.depth[i:i + 1].cpu().numpy(), f"{stem}_v{i}{ext}", p.crop, restore)
+    print(f"Model `{a.model}` wrote {len(imgs)} normalized depth maps to {stem}_v*{ext}")
+    if a.ply:
+        K, E = out.intrinsics[:, 0], out.extrinsics[:, 0]
+        depth = out.depth
+        if a.view_rtol > 0 or a.conf_percentile > 0:
+            depth, _, _, _ = ops.filter_views(dev, out.depth, out.depth_confidence, intrinsics=K, extrinsics=E, conf_percentile=a.conf_percentile,
+                                              view_rtol=a.view_rtol, min_views=a.min_views)
+        rgb = torch.from_numpy(np.stack([p.rgb for p in preps])).to(depth.device)
+        pc = ops.unproject(dev, depth, intrinsics=K, extrinsics=E, conf=out.depth_confidence, rgb=rgb, dense=False, conf_min=a.conf_min,
+                           edge_rtol=a.edge_rtol, stride=a.stride, world=True)
+        xyz, col, _ = pc.points()
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy())
+        print(f"Model `{a.model}` wrote {xyz.shape[0]} points of {len(imgs)} views to {a.ply}")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=["depth-pro", "depth-anything-3"], default="depth-pro")
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--image", required=True)
+    ap.add_argument("--image", default="")
+    ap.add_argument("--views", nargs="+", default=[], help="the views of one scene, reference view first (Depth-Anything-v3 small; instead of --image)")
+    ap.add_argument("--view-rtol", type=float, default=0.0, help="--views --ply: drop a pixel that other views contradict by more than this ratio (0 = off)")
+    ap.add_argument("--min-views", type=int, default=0, help="--views --ply: keep pixels that at least this many other views support")
     ap.add_argument("--output", default="")
     ap.add_argument("--precision", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--focal-px", type=float, default=None, help="known focal length in pixels of the image (Depth Pro only)")
@@ -54,6 +116,11 @@ def main(argv=None) -> int:
     if not os.path.exists(a.checkpoint):   # example/inference.rs:52-62
         print(f"Checkpoint `{a.checkpoint}` not found. Run tools/import_weights.py first.", file=sys.stderr)
         return 1
+    if bool(a.image) == bool(a.views):
+        print("give either --image or --views", file=sys.stderr)
+        return 2
+    if a.views:
+        return run_views(a)
     rgb = np.load(a.image)
     if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
         print(f"--image must be uint8 [H,W,3], got {rgb.dtype} {rgb.shape}", file=sys.stderr)
