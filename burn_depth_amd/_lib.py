@@ -64,6 +64,11 @@ class MdPointsOutputs(C.Structure):
                 ("count", C.c_void_p), ("capacity", C.c_int64), ("depth", C.c_void_p)]
 
 
+class MdPointsNormals(C.Structure):
+    """md_points_normals (include/mi_depth.h)."""
+    _fields_ = [("normal_map", C.c_void_p), ("normals", C.c_void_p), ("min_cos", C.c_float)]
+
+
 class MdViewFilterOpts(C.Structure):
     """md_view_filter_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_percentile", C.c_int),
@@ -163,6 +168,10 @@ SYMBOLS = {
                                 C.POINTER(MdViewFilterOutputs), _P]),
     "md_infer_points_filtered": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
                                       C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), _I, _P]),
+    "md_op_unproject_normals": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
+                                     C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), _P]),
+    "md_infer_points_normals": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                     C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

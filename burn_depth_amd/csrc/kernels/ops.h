@@ -54,10 +54,17 @@ struct PointsParams {
   int32_t* count = nullptr;  // [B + 1]; non-null = the list passes run
   long capacity = 0;
 };
+// the normals forms of classify / scatter (md_op_unproject_normals): all zero = the forms without normals
+struct NormalsParams {
+  float* normal_map = nullptr;  // [B,H,W,3]
+  float* normals = nullptr;     // [capacity,3], rows parallel to xyz; needs p.count
+  float min_cos = 0.f;          // > 0: the grazing-angle test enters the validity
+};
 // bytes of the list's scratch (bit mask, block counts, block offsets) for B views of H x W; 256-byte aligned parts
 size_t points_scratch_bytes(int B, int H, int W);
-// classify (+ scan + scatter when p.count is set); scratch may be null when p.count is
-int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s);
+// classify (+ scan + scatter when p.count is set); scratch may be null when p.count is. nrm null or all zero: the launches
+// and kernels of the point path without normals
+int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s, const NormalsParams* nrm = nullptr);
 
 // ---- view filter (kernels/view_filter.hip; md_op_filter_views, md_infer_points_filtered) ----
 // depth [B,H,W] (+ confidence) and the cameras of the point path -> the depth with rejected pixels set to 0: an exact

@@ -482,6 +482,18 @@ int md_infer_points_filtered(md_model_t m, const float* nchw, int B, int H, int 
   return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, true);
 }
 
+int md_op_unproject_normals(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
+                            const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                            void* stream) {
+  return op_unproject(dev, depth_dev, conf_dev, rgb_dev, B, H, W, cam, o, out, (hipStream_t)stream, nrm);
+}
+
+int md_infer_points_normals(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                            const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                            int out_kind, void* stream) {
+  return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, false, nrm);
+}
+
 int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {
   if (!left || !count) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (in_len <= 0 || out_len <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid pass %d -> %d", in_len, out_len);

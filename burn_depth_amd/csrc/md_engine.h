@@ -358,11 +358,13 @@ int process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_
 DisplayGeom display_geom(int B, int h, int w, int cx, int cy, int cw, int ch, int ow, int oh);
 // the point path (md_points.hip): the stand-alone operator on caller tensors, the model -> points call and its state
 int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
-                 const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, hipStream_t stream);
-// filtered = the md_infer_points_filtered entry: `fo` is required and the view filter runs between the model and the unprojection
+                 const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, hipStream_t stream,
+                 const md_points_normals* nrm = nullptr);
+// filtered = the md_infer_points_filtered entry: `fo` is required and the view filter runs between the model and the unprojection.
+// nrm (md_op_unproject_normals / md_infer_points_normals): null or all zero = the call without normals
 int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                  const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream,
-                 const md_view_filter_opts* fo = nullptr, bool filtered = false);
+                 const md_view_filter_opts* fo = nullptr, bool filtered = false, const md_points_normals* nrm = nullptr);
 int op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_dev, int B, int H, int W, const md_points_cameras* cam,
                     const md_view_filter_opts* o, const md_view_filter_outputs* out, hipStream_t stream);
 void points_destroy_state(md_model_t m);

@@ -1,5 +1,6 @@
 // The point path: md_op_unproject (depth + cameras -> point map / mask / ordered cloud on caller tensors) and md_infer_points
-// (the model's infer body, then the same kernels on its results, in one call). model (model_infer / da3_infer_ex bodies) ->
+// (the model's infer body, then the same kernels on its results, in one call); md_op_unproject_normals / md_infer_points_normals
+// are the same two calls with the normals forms of the kernels. model (model_infer / da3_infer_ex bodies) ->
 // classify / scan / scatter (kernels/points.hip); one captured graph per replay key when the model replays graphs.
 // md_op_filter_views / md_infer_points_filtered put the view filter (kernels/view_filter.hip: confidence percentile, cross-view
 // support) in front of those launches: it hands them a depth in which rejected pixels are 0.
@@ -37,9 +38,14 @@ struct Sources {  // what the kernels will read, known before the model runs
   bool rgb = false, conf = false, K = false, focal = false, E = false;
 };
 
-int check_points(const md_points_opts* o, const md_points_outputs* out, const Sources& s, int B, int H, int W) {
+int check_points(const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm, const Sources& s, int B, int H, int W) {
   if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "point options are null");
   if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  if (nrm) {
+    if (!std::isfinite(nrm->min_cos) || nrm->min_cos < 0.f || nrm->min_cos > 1.f)
+      MD_FAIL(MD_ERR_INVALID_ARG, "min_cos = %g: must lie in [0, 1]", (double)nrm->min_cos);
+    if (nrm->normals && !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "the compacted normals need `count`");
+  }
   if (o->stride < 1) MD_FAIL(MD_ERR_INVALID_ARG, "stride %d: at least 1", o->stride);
   if (out->capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "capacity %lld is negative", (long long)out->capacity);
   if ((out->xyz || out->rgb || out->conf) && !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "the compacted outputs need `count`");
@@ -73,6 +79,12 @@ PointsParams make_params(int B, int H, int W, const md_points_opts& o) {
   p.stride = o.stride;
   p.world = o.world ? 1 : 0;
   return p;
+}
+
+NormalsParams make_normals(const md_points_normals* nrm) {
+  NormalsParams q;
+  if (nrm) { q.normal_map = nrm->normal_map; q.normals = nrm->normals; q.min_cos = nrm->min_cos; }
+  return q;
 }
 
 // has_conf / has_intr / has_E: what the filter will find on the device (the caller's or the model's)
@@ -119,12 +131,13 @@ uintptr_t fbits(float v) {
 }  // namespace
 
 int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
-                 const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, hipStream_t stream) {
+                 const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, hipStream_t stream,
+                 const md_points_normals* nrm) {
   if (!cam) MD_FAIL(MD_ERR_INVALID_ARG, "cameras are null");
   Sources s;
   s.rgb = rgb_dev != nullptr; s.conf = conf_dev != nullptr;
   s.K = cam->intrinsics != nullptr; s.focal = cam->focal_px != nullptr; s.E = cam->extrinsics != nullptr;
-  MD_TRY(check_points(o, out, s, B, H, W));
+  MD_TRY(check_points(o, out, nrm, s, B, H, W));
   if (!depth_dev) MD_FAIL(MD_ERR_INVALID_ARG, "depth pointer is null");
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
   MD_HIP(hipSetDevice(dev->ordinal));
@@ -136,7 +149,8 @@ int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev,
   p.xyz = out->xyz; p.rgb_out = out->rgb; p.conf_out = out->conf; p.count = out->count; p.capacity = out->capacity;
   void* scratch = nullptr;
   if (p.count) MD_HIP(hipMalloc(&scratch, points_scratch_bytes(B, H, W)));
-  const int rc = launch_unproject(p, scratch, st);
+  const NormalsParams q = make_normals(nrm);
+  const int rc = launch_unproject(p, scratch, st, &q);
   if (scratch) {  // the scratch is freed on return
     const hipError_t se = hipStreamSynchronize(st);
     (void)hipFree(scratch);
@@ -176,7 +190,7 @@ int op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_d
 // ------------------------------------------------------------------------------------------------
 static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras& cam,
                         const md_points_opts& o, const md_points_outputs& out, int out_kind, bool dual, hipStream_t st,
-                        const md_view_filter_opts* fo) {
+                        const md_view_filter_opts* fo, const md_points_normals* nrm) {
   if (!m->points) m->points = new md_model_s::PointsState();
   md_model_s::PointsState* f = m->points;
   const bool host_in = in_kind == MD_MEM_HOST, host_out = out_kind == MD_MEM_HOST;
@@ -205,7 +219,8 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   if (out.count) MD_TRY(grow(m, st, f->scratch, points_scratch_bytes(B, H, W)));
   PointsParams p = make_params(B, H, W, o);
   p.capacity = out.capacity;
-  size_t off_map = 0, off_mask = 0, off_xyz = 0, off_rgb = 0, off_conf = 0, off_count = 0, total = 0;
+  NormalsParams q = make_normals(nrm);
+  size_t off_map = 0, off_mask = 0, off_xyz = 0, off_rgb = 0, off_conf = 0, off_count = 0, off_nmap = 0, off_nrm = 0, total = 0;
   if (host_out) {
     auto take = [&](bool want, size_t bytes) {
       const size_t at = total;
@@ -218,6 +233,8 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
     off_rgb = take(out.rgb, cap * 3);
     off_conf = take(out.conf, cap * 4);
     off_count = take(out.count, (size_t)(B + 1) * 4);
+    off_nmap = take(q.normal_map, npx * 12);
+    off_nrm = take(q.normals, cap * 12);
     if (total) MD_TRY(grow(m, st, f->out, total));
     char* base = (char*)f->out.p;
     p.point_map = out.point_map ? (float*)(base + off_map) : nullptr;
@@ -226,6 +243,8 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
     p.rgb_out = out.rgb ? (uint8_t*)(base + off_rgb) : nullptr;
     p.conf_out = out.conf ? (float*)(base + off_conf) : nullptr;
     p.count = out.count ? (int32_t*)(base + off_count) : nullptr;
+    if (q.normal_map) q.normal_map = (float*)(base + off_nmap);
+    if (q.normals) q.normals = (float*)(base + off_nrm);
   } else {
     p.point_map = out.point_map; p.mask = out.mask;
     p.xyz = out.xyz; p.rgb_out = out.rgb; p.conf_out = out.conf; p.count = out.count;
@@ -281,7 +300,7 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   p.depth = depth; p.conf = conf; p.rgb = rgb_dev;
   p.K = k_dev; p.focal = k_dev ? nullptr : f_dev; p.E = o.world ? e_dev : nullptr;
   r.begin("points_unproject");
-  MD_TRY(launch_unproject(p, f->scratch.p, st));
+  MD_TRY(launch_unproject(p, f->scratch.p, st, &q));
   r.end();
   if (!host_out) return MD_OK;
   auto d2h = [&](void* dst, const void* srcp, size_t bytes) -> int {
@@ -291,6 +310,7 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   MD_TRY(d2h(out.depth, depth, npx * 4));
   MD_TRY(d2h(out.point_map, p.point_map, npx * 12));
   MD_TRY(d2h(out.mask, p.mask, npx));
+  if (nrm) MD_TRY(d2h(nrm->normal_map, q.normal_map, npx * 12));
   MD_TRY(d2h(out.count, p.count, (size_t)(B + 1) * 4));
   MD_HIP(hipStreamSynchronize(st));  // host outputs are complete when the call returns
   if (out.count) {  // only the points that exist travel: the caller's memory beyond them stays as it was
@@ -298,6 +318,7 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
     MD_TRY(d2h(out.xyz, p.xyz, n * 12));
     MD_TRY(d2h(out.rgb, p.rgb_out, n * 3));
     MD_TRY(d2h(out.conf, p.conf_out, n * 4));
+    if (nrm) MD_TRY(d2h(nrm->normals, q.normals, n * 12));
     MD_HIP(hipStreamSynchronize(st));
   }
   return MD_OK;
@@ -305,7 +326,7 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
 
 int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                  const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream, const md_view_filter_opts* fo,
-                 bool filtered) {
+                 bool filtered, const md_points_normals* nrm) {
   if (!m) MD_FAIL(MD_ERR_INVALID_ARG, "model is null");
   if (!nchw) MD_FAIL(MD_ERR_INVALID_ARG, "input pointer is null");
   if ((in_kind != MD_MEM_HOST && in_kind != MD_MEM_DEVICE) || (out_kind != MD_MEM_HOST && out_kind != MD_MEM_DEVICE))
@@ -325,7 +346,7 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   s.K = c.intrinsics != nullptr || dual;
   s.focal = c.focal_px != nullptr || m->kind == 0;
   s.E = c.extrinsics != nullptr || dual;
-  MD_TRY(check_points(o, out, s, B, H, W));
+  MD_TRY(check_points(o, out, nrm, s, B, H, W));
   if (fo) {
     MD_TRY(check_filter(fo, s.conf, s.K || s.focal, s.E, B, H, W));
     if (fbits(fo->pixel_offset) != fbits(o->pixel_offset) || depth_min_of(fo->depth_min) != depth_min_of(o->depth_min) ||
@@ -340,7 +361,7 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   if (!model_root(m)->committed) MD_FAIL(MD_ERR_INVALID_ARG, "weights were modified; call md_model_commit_weights first");
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = model_stream(m, stream);
-  auto body = [&]() { return points_eager(m, nchw, B, H, W, in_kind, rgb, c, *o, *out, out_kind, dual, st, fo); };
+  auto body = [&]() { return points_eager(m, nchw, B, H, W, in_kind, rgb, c, *o, *out, out_kind, dual, st, fo, nrm); };
   if (!m->graph_enabled) return body();
   // the key: stream, shape, every option, every in / out pointer and the commit generation (md_frame.hip); a graph only
   // replays at the model's current input size (its workspace plan)
@@ -361,6 +382,8 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
                                       (uintptr_t)out->conf, (uintptr_t)out->count, (uintptr_t)out->capacity, (uintptr_t)out->depth,
                                       (uintptr_t)gen};
   if (fo) key.insert(key.end(), {(uintptr_t)0x56464c54u, (uintptr_t)fo->conf_percentile, fbits(fo->view_rtol), (uintptr_t)fo->min_views});
+  if (nrm && (nrm->normal_map || nrm->normals || nrm->min_cos > 0.f))  // all zero: the key, and the graph, of the call without normals
+    key.insert(key.end(), {(uintptr_t)0x4e524d4cu, (uintptr_t)nrm->normal_map, (uintptr_t)nrm->normals, fbits(nrm->min_cos)});
   return run_with_graph(m, st, key, eligible, body);
 }
 

@@ -81,7 +81,9 @@ class FrameResult:
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
-    which the first min(count[B], capacity) rows are points; count int32 [B+1] (per view, then the total); the depth [B,H,W]."""
+    which the first min(count[B], capacity) rows are points; count int32 [B+1] (per view, then the total); the depth [B,H,W].
+    With normals (`md_op_unproject_normals` / `md_infer_points_normals`): normal_map [B,H,W,3] and normals [capacity,3], rows
+    parallel to xyz."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -89,6 +91,8 @@ class PointCloud:
     conf: Optional[torch.Tensor] = None
     count: Optional[torch.Tensor] = None
     depth: Optional[torch.Tensor] = None
+    normal_map: Optional[torch.Tensor] = None
+    normals: Optional[torch.Tensor] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -126,6 +130,21 @@ def _points_outputs(dev, B: int, H: int, W: int, dense: bool, compact: bool, cap
     c = _lib.MdPointsOutputs(ptr(out.point_map), ptr(out.mask), ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count),
                              int(out.xyz.shape[0]) if out.xyz is not None else 0, ptr(out.depth))
     return out, c
+
+
+def _points_normals(dev, B: int, H: int, W: int, normals: bool, min_cos: float, out: PointCloud, fresh: bool):
+    """md_points_normals for `out`: with `fresh` (the PointCloud was made for this call) the normal tensors are created beside the
+    dense map and the list it has; otherwise the ones it carries are written again, and asking for normals with an `out` that
+    carries none is refused."""
+    if normals and not fresh and out.normal_map is None and out.normals is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "normals=True with an `out` that carries neither `normal_map` nor `normals`")
+    if fresh and normals:
+        if out.point_map is not None:
+            out.normal_map = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        if out.xyz is not None:
+            out.normals = torch.empty((int(out.xyz.shape[0]), 3), dtype=torch.float32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    return _lib.MdPointsNormals(ptr(out.normal_map), ptr(out.normals), float(min_cos))
 
 
 def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
@@ -529,14 +548,18 @@ class DepthPro:
     # ---- point path --------------------------------------------------------------------------
     def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
-                     conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, **opts) -> PointCloud:
+                     conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
+                     normal_min_cos: float = 0.0, **opts) -> PointCloud:
         """`md_infer_points`: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the caller's
         (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True). rgb: u8
         [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the call is
         `md_infer_points_filtered`, which drops the lowest conf_percentile % of the confidences of the call and the pixels fewer
-        than min_views other views confirm within view_rtol before the unprojection; `depth` is then the filtered depth."""
+        than min_views other views confirm within view_rtol before the unprojection; `depth` is then the filtered depth.
+        normals / normal_min_cos (`md_points_normals`): the call is `md_infer_points_normals`, which also returns the surface normals
+        (`normal_map`, `normals`) and, with normal_min_cos > 0, drops the pixels seen at a grazing angle; it composes with the view
+        filter."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -549,7 +572,14 @@ class DepthPro:
         res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, rgb is not None, has_conf, True, out)
         cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, f_px)
         rgb_p = C.c_void_p(rgb.data_ptr()) if rgb is not None else None
-        if conf_percentile or view_rtol or min_views:
+        filtered = bool(conf_percentile or view_rtol or min_views)
+        if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
+            nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
+            fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views) if filtered else None
+            _lib.check(self._lib.md_infer_points_normals(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
+                                                         C.byref(fo) if filtered else None, C.byref(o), C.byref(outs), C.byref(nrm),
+                                                         _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        elif filtered:
             fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
             _lib.check(self._lib.md_infer_points_filtered(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
                                                           C.byref(fo), C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE,

@@ -269,15 +269,21 @@ class HostPoints:
     rgb: Optional[np.ndarray]        # uint8 [N,3]
     conf: Optional[np.ndarray]       # [N]
     count: np.ndarray                # int32 [B+1]: per view, then the total
+    normal_map: Optional[np.ndarray] = None  # [B,H,W,3] (normals=True): the unit normal, (0,0,0) where invalid or not defined
+    normals: Optional[np.ndarray] = None     # [N,3], rows parallel to xyz
 
 
 def unproject_depth(depth, intrinsics=None, extrinsics=None, focal_px=None, conf=None, rgb=None, *, pixel_offset=0.0,
                     depth_min=0.0, depth_max=0.0, conf_min=0.0, edge_rtol=0.0, stride=1, world=False,
-                    dtype=np.float32) -> HostPoints:
+                    normals=False, normal_min_cos=0.0, dtype=np.float32) -> HostPoints:
     """depth [B,H,W] and pinhole cameras -> point map, validity mask and the ordered list of valid points. Every step is one
     rounded operation of `dtype`, in the order of the device kernels (kernels/points.hip): with dtype f32 the results are
     theirs bit for bit; dtype=np.float64 is the same formulas for the geometric tests. intrinsics [B,3,3] or focal_px [B]
-    (K = f, f, W/2, H/2); extrinsics [B,3,4] world-to-camera (camera.rs:248-254), applied inverted when `world`."""
+    (K = f, f, W/2, H/2); extrinsics [B,3,4] world-to-camera (camera.rs:248-254), applied inverted when `world`.
+
+    normals / normal_min_cos (md_op_unproject_normals; include/mi_depth.h states the contract): the surface normal of every pixel
+    from its four neighbours, and with normal_min_cos > 0 the grazing-angle test in the validity. The defaults compute what the
+    call computed before they existed."""
     T = np.dtype(dtype).type
     d = np.asarray(depth, dtype=dtype)
     if d.ndim != 3:
@@ -296,6 +302,9 @@ def unproject_depth(depth, intrinsics=None, extrinsics=None, focal_px=None, conf
         raise ValueError("neither intrinsics nor a focal length")
     if world and extrinsics is None:
         raise ValueError("world needs extrinsics")
+    if not np.isfinite(normal_min_cos) or not 0 <= normal_min_cos <= 1:
+        raise ValueError("normal_min_cos must lie in [0, 1]")
+    want_normals = bool(normals) or normal_min_cos > 0
     f32i = np.finfo(np.float32)
     dmin = T(depth_min) if depth_min > 0 else T(f32i.tiny)
     dmax = T(depth_max) if depth_max > 0 else T(f32i.max)
@@ -322,14 +331,23 @@ def unproject_depth(depth, intrinsics=None, extrinsics=None, focal_px=None, conf
         rx = ((u + off) - b3(cx)) / b3(fx)
         ry = ((v + off) - b3(cy)) / b3(fy)
         x, y, z = rx * d, ry * d, d
+        nm = None
+        if want_normals:
+            nrm, defined, cosv = _pixel_normals(d, cf, (x, y, np.broadcast_to(z, d.shape)), dmin, dmax, T(conf_min), T(edge_rtol), T(f32i.tiny))
+            if normal_min_cos > 0:
+                valid &= defined & (cosv >= T(normal_min_cos))
         if world:
             E = np.asarray(extrinsics, dtype=dtype).reshape(B, 3, 4)
             R = lambda i, j: E[:, i, j][:, None, None]  # noqa: E731
+            if want_normals:  # n_w = R^T n in the operation order of the point below, not renormalised
+                nrm = [(R(0, j) * nrm[0] + R(1, j) * nrm[1]) + R(2, j) * nrm[2] for j in range(3)]
             qx, qy, qz = x - R(0, 3), y - R(1, 3), z - R(2, 3)
             x = (R(0, 0) * qx + R(1, 0) * qy) + R(2, 0) * qz
             y = (R(0, 1) * qx + R(1, 1) * qy) + R(2, 1) * qz
             z = (R(0, 2) * qx + R(1, 2) * qy) + R(2, 2) * qz
         pm = np.stack([np.broadcast_to(c, d.shape) for c in (x, y, z)], axis=-1).astype(dtype)
+        if want_normals:
+            nm = np.where((valid & defined)[..., None], np.stack(nrm, axis=-1), T(0)).astype(dtype)
     pm = np.where(valid[..., None], pm, T(0)).astype(dtype)
     sel = valid.copy()
     if stride > 1:
@@ -338,7 +356,47 @@ def unproject_depth(depth, intrinsics=None, extrinsics=None, focal_px=None, conf
         sel &= keep[None]
     count = np.concatenate([sel.reshape(B, -1).sum(1), [sel.sum()]]).astype(np.int32)
     return HostPoints(pm, valid.astype(np.uint8), pm[sel], None if rgb is None else np.asarray(rgb, np.uint8).reshape(B, H, W, 3)[sel],
-                      None if cf is None else cf[sel], count)
+                      None if cf is None else cf[sel], count, nm if normals else None, nm[sel] if normals else None)
+
+
+def _pixel_normals(d, cf, P, dmin, dmax, conf_min, rt, tiny):
+    """The normal of md_op_unproject_normals (include/mi_depth.h) for every pixel of d [B,H,W] at once: P = the camera-space
+    points (x, y, z), cf = the confidence map or None. -> ((nx, ny, nz) in camera space, defined, cosv). One rounded operation of
+    d's dtype per step, in the order of pixel_normal (kernels/points.hip). With x right, y down, z forward every cross of the
+    pair order below points at the camera: for positive depths the sign of P_c . (e_a x e_b) is the sign of det(r_c, r_a, r_b)
+    of the three pixel rays, whatever the depths, so cosv > 0 in exact arithmetic and nothing is flipped."""
+    B, H, W = d.shape
+
+    def at(a, dv, du, fill):  # a at (v + dv, u + du), `fill` outside the image
+        pad = np.pad(a, ((0, 0), (1, 1), (1, 1)), constant_values=fill)
+        return pad[:, 1 + dv:1 + dv + H, 1 + du:1 + du + W]
+
+    inside = np.ones((B, H, W), bool)
+    e, use = {}, {}
+    for name, (dv, du) in (("E", (0, 1)), ("S", (1, 0)), ("W", (0, -1)), ("N", (-1, 0))):
+        dn = at(d, dv, du, 0)
+        ok = at(inside, dv, du, False) & np.isfinite(dn) & (dn >= dmin) & (dn <= dmax)
+        if cf is not None:
+            ok &= at(cf, dv, du, 0) >= conf_min
+        if rt > 0:
+            ok &= np.abs(d - dn) <= rt * np.minimum(d, dn)
+        use[name] = ok
+        e[name] = [at(c, dv, du, 0) - c for c in P]
+    m = [np.zeros_like(d) for _ in range(3)]
+    have = np.zeros((B, H, W), bool)
+    for a, b in (("S", "E"), ("E", "N"), ("N", "W"), ("W", "S")):
+        (ax, ay, az), (bx, by, bz) = e[a], e[b]
+        c = ((ay * bz) - (az * by), (az * bx) - (ax * bz), (ax * by) - (ay * bx))
+        both = use[a] & use[b]
+        m = [np.where(both, np.where(have, mi + ci, ci), mi) for mi, ci in zip(m, c)]  # summed from the first usable pair on
+        have |= both
+    len2 = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]
+    defined = have & np.isfinite(len2) & (len2 >= tiny)
+    s = np.sqrt(len2)
+    n = [np.where(defined, mi / s, d.dtype.type(0)) for mi in m]
+    px, py, pz = P
+    cosv = -((n[0] * px + n[1] * py) + n[2] * pz) / np.sqrt((px * px + py * py) + pz * pz)
+    return n, defined, cosv
 
 
 def filter_views(depth, conf=None, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, depth_min=0.0,
@@ -425,10 +483,15 @@ def filter_views(depth, conf=None, intrinsics=None, extrinsics=None, focal_px=No
     return depth_out, support, T(tau), kept
 
 
-def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None) -> None:
-    """Binary little-endian PLY: `x y z` float, optional `red green blue` uchar."""
+def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None) -> None:
+    """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype="<f4").reshape(-1, 3)
+        if len(normals) != len(xyz):
+            raise ValueError(f"{len(normals)} normals for {len(xyz)} points")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if rgb is not None:
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
         if len(rgb) != len(xyz):
@@ -437,6 +500,8 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None) -> N
     rec = np.empty(len(xyz), dtype=np.dtype(fields))
     for i, n in enumerate("xyz"):
         rec[n] = xyz[:, i]
+        if normals is not None:
+            rec["n" + n] = normals[:, i]
     if rgb is not None:
         for i, n in enumerate(("red", "green", "blue")):
             rec[n] = rgb[:, i]
@@ -451,6 +516,12 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None) -> N
 
 def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     """Reader for the files `write_ply` produces -> (xyz f32 [N,3], rgb uint8 [N,3] or None)."""
+    xyz, rgb, _ = read_ply_normals(path)
+    return xyz, rgb
+
+
+def read_ply_normals(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+    """`read_ply` with the normals -> (xyz f32 [N,3], rgb uint8 [N,3] or None, normals f32 [N,3] or None)."""
     b = open(path, "rb").read()
     end = b.index(b"end_header\n") + len(b"end_header\n")
     lines = b[:end].decode("ascii").split("\n")
@@ -460,7 +531,8 @@ def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     rec = np.frombuffer(b, dtype=np.dtype(fields), count=n, offset=end)
     xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float32)
     rgb = np.stack([rec["red"], rec["green"], rec["blue"]], axis=-1) if "red" in rec.dtype.names else None
-    return xyz, rgb
+    nrm = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=-1).astype(np.float32) if "nx" in rec.dtype.names else None
+    return xyz, rgb, nrm
 
 
 def save_depth_map(depth: np.ndarray, path: str, crop: Optional[ImageCropRegion] = None,
@@ -517,7 +589,7 @@ class AnyDepthModel:
     def infer_points(self, x, **kw):
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
-        filter, `md_infer_points_filtered`) included."""
+        filter, `md_infer_points_filtered`) and normals= / normal_min_cos= (`md_infer_points_normals`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

@@ -379,6 +379,44 @@ int md_infer_points_filtered(md_model_t m, const float* nchw, int B, int H, int 
                              const md_points_cameras* cam, const md_view_filter_opts* fo, const md_points_opts* o,
                              const md_points_outputs* out, int out_kind, void* stream);
 
+/* ---- point path: surface normals and a grazing-angle filter ------------------------------------------------------------
+ * The normal of pixel c = (v, u) of view b with depth d_c, from its one ring of four neighbours. f32, one rounded operation
+ * per step and no fused multiply-add (pipeline.unproject_depth(normals=True) restates it in numpy bit for bit):
+ *   P(v, u) = the camera-space point p_c of the point path above (world = 0).
+ *   A neighbour n out of E = (v, u+1), S = (v+1, u), W = (v, u-1), N = (v-1, u) is usable when it lies inside the image, its
+ *     depth d_n is finite and depth_min <= d_n <= depth_max (the bounds resolved as md_points_opts resolves them), a
+ *     confidence map, when there is one, holds conf_n >= conf_min, and, with edge_rtol > 0,
+ *     |d_c - d_n| <= edge_rtol * min(d_c, d_n). Only this ring is read: the neighbour's own edge test does not enter.
+ *   e_n = P_n - P_c per component. For the pairs (a, b) = (S,E), (E,N), (N,W), (W,S), in this order, whose two neighbours
+ *     are usable: a x b = ((ay bz) - (az by), (az bx) - (ax bz), (ax by) - (ay bx)); m = their sum from left to right,
+ *     starting from the first usable pair. With x right, y down, z forward every such cross points at the camera.
+ *   len2 = (mx mx + my my) + mz mz. The normal is defined when a pair was usable and len2 is finite and >= FLT_MIN:
+ *     n = (mx / s, my / s, mz / s), s = sqrtf(len2); otherwise n = (0, 0, 0).
+ *   world = 1: n_w = R^T n, each coordinate (R0j nx + R1j ny) + R2j nz, not renormalised.
+ *   cosv = -((nx px + ny py) + nz pz) / sqrtf((px px + py py) + pz pz), n and p = P_c in camera space. With min_cos > 0 a
+ *     pixel is valid only when every condition of the point path holds, its normal is defined and cosv >= min_cos; this
+ *     validity feeds the mask, the point map, the list and count as the other conditions do.
+ *   stride thins the list only: the neighbours are always the adjacent pixels. f32 denormals are outside the contract. */
+typedef struct md_points_normals {
+  float* normal_map; /* dense f32 [B,H,W,3]: the normal at valid pixels with a defined normal, (0,0,0) elsewhere; NULL = skip */
+  float* normals;    /* compacted f32 [capacity,3], rows parallel to xyz; needs count */
+  float min_cos;     /* 0 = off, else in (0, 1] */
+} md_points_normals;
+
+/* md_op_unproject with normals. nrm NULL or all zero: md_op_unproject on the same arguments, the same launches and bits.
+ * Errors as md_op_unproject's, plus, before any launch: min_cos not finite, negative or above 1, normals without count
+ * -> MD_ERR_INVALID_ARG. */
+int md_op_unproject_normals(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H,
+                            int W, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
+                            const md_points_normals* nrm, void* stream);
+/* md_infer_points (fo NULL) / md_infer_points_filtered (fo given) with normals; nrm's pointers are of out_kind. nrm NULL or
+ * all zero: those calls on the same arguments. The graph key contains nrm's three fields. Errors as theirs, plus
+ * md_op_unproject_normals'. After the first call of a shape nothing is allocated. */
+int md_infer_points_normals(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                            const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                            const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm, int out_kind,
+                            void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

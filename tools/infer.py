@@ -11,7 +11,8 @@ needs no resize).
 
 `--ply OUT.ply`: also writes the depth as a coloured point cloud (binary little-endian PLY), back-projected on the device in the
 same call as the inference (`md_infer_points`): Depth Pro with its predicted (or `--focal-px`) focal length in camera space,
-Depth-Anything-v3 `small` with its predicted intrinsics / extrinsics in world space. `--conf-min`, `--edge-rtol`, `--stride`
+Depth-Anything-v3 `small` with its predicted intrinsics / extrinsics in world space. `--normals` adds the surface
+normals (`nx ny nz`, `md_infer_points_normals`) and `--normal-min-cos` drops surfaces seen at a grazing angle. `--conf-min`, `--edge-rtol`, `--stride`
 filter the cloud (`md_points_opts`); `--conf-percentile Q` first drops the lowest Q % of the confidences on the device
 (`md_infer_points_filtered`; Depth-Anything-v3 `small`, whose confidence has no scale a caller could know in advance).
 
@@ -79,9 +80,9 @@ def run_views(a) -> int:
                                               view_rtol=a.view_rtol, min_views=a.min_views)
         rgb = torch.from_numpy(np.stack([p.rgb for p in preps])).to(depth.device)
         pc = ops.unproject(dev, depth, intrinsics=K, extrinsics=E, conf=out.depth_confidence, rgb=rgb, dense=False, conf_min=a.conf_min,
-                           edge_rtol=a.edge_rtol, stride=a.stride, world=True)
+                           edge_rtol=a.edge_rtol, stride=a.stride, world=True, normals=a.normals, normal_min_cos=a.normal_min_cos)
         xyz, col, _ = pc.points()
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy())
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None)
         print(f"Model `{a.model}` wrote {xyz.shape[0]} points of {len(imgs)} views to {a.ply}")
     return 0
 
@@ -103,6 +104,9 @@ def main(argv=None) -> int:
     ap.add_argument("--conf-percentile", type=int, default=0, help="--ply: drop the lowest this-many percent (0..99) of the confidences (Depth-Anything-v3 small)")
     ap.add_argument("--edge-rtol", type=float, default=0.0, help="--ply: drop pixels whose depth differs from a neighbour's by more than this ratio (0 = off)")
     ap.add_argument("--stride", type=int, default=1, help="--ply: keep every stride-th row and column")
+    ap.add_argument("--normals", action="store_true", help="--ply: also write the surface normals (nx ny nz; md_infer_points_normals)")
+    ap.add_argument("--normal-min-cos", type=float, default=0.0,
+                    help="--ply: drop pixels whose surface is seen at a cosine below this (grazing angles; 0 = off, at most 1)")
     a = ap.parse_args(argv)
     if a.focal_px is not None and a.model != "depth-pro":
         print(f"--focal-px applies to Depth Pro only, not to `{a.model}`", file=sys.stderr)
@@ -143,12 +147,13 @@ def main(argv=None) -> int:
         try:
             pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
                                     dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
-                                    world=bool(getattr(model.model.config, "dual_head", False)))
+                                    world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
+                                    normal_min_cos=a.normal_min_cos)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
         xyz, col, _ = pc.points()
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy())
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None)
         print(f"Model `{kind.value}` wrote {xyz.shape[0]} points to {a.ply}")
         if not a.output:
             return 0
