@@ -69,6 +69,11 @@ class MdPointsNormals(C.Structure):
     _fields_ = [("normal_map", C.c_void_p), ("normals", C.c_void_p), ("min_cos", C.c_float)]
 
 
+class MdPointsVoxel(C.Structure):
+    """md_points_voxel (include/mi_depth.h)."""
+    _fields_ = [("voxel", C.c_float), ("index", C.c_void_p), ("weight", C.c_void_p), ("dropped", C.c_void_p)]
+
+
 class MdViewFilterOpts(C.Structure):
     """md_view_filter_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_percentile", C.c_int),
@@ -172,6 +177,10 @@ SYMBOLS = {
                                      C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), _P]),
     "md_infer_points_normals": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
                                      C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), _I, _P]),
+    "md_op_voxel_thin": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsVoxel), C.POINTER(MdPointsOutputs), _P, _P]),
+    "md_infer_points_voxel": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                   C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                   C.POINTER(MdPointsVoxel), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

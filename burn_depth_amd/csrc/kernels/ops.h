@@ -89,6 +89,37 @@ constexpr int kViewFilterMaxViews = 64;  // support is u8 and the B cameras sit 
 size_t view_filter_scratch_bytes();
 int launch_view_filter(const ViewFilterParams& p, void* scratch, hipStream_t s);
 
+// ---- voxel thinning (kernels/voxel.hip; md_op_voxel_thin, md_infer_points_voxel) ----
+// A point list xyz [n,3] (+ conf [n], u8 rgb [n,3], normals [n,3]) -> one row per occupied voxel, the rows in ascending input
+// index: reset, insert (hash table of 64-bit cell keys; atomicMax of a rank word, integer count), select (ballot words), scan,
+// scatter. Every pointer is a device pointer. Selection only: no float is summed, nothing depends on the order of arrival.
+struct VoxelParams {
+  const float* xyz = nullptr;
+  const float* conf = nullptr;       // null: every weight is 0 and the smallest index of a voxel wins
+  const uint8_t* rgb = nullptr;      // carried to rgb_out
+  const float* normals = nullptr;    // carried to normals_out
+  const int32_t* in_count = nullptr; // [B + 1] per-view rows of the input, then their total = the live rows (read on the device); null: n rows, one view
+  int n = 0;                         // rows the launches cover: the live count is min(in_count[B], n)
+  int B = 1;
+  float voxel = 0.f;
+  float* xyz_out = nullptr;
+  float* conf_out = nullptr;
+  uint8_t* rgb_out = nullptr;
+  float* normals_out = nullptr;
+  int32_t* index = nullptr;    // [capacity] source row
+  int32_t* weight = nullptr;   // [capacity] in-range points of the survivor's voxel
+  int32_t* count = nullptr;    // [B + 1] survivors per view, then their total
+  int32_t* dropped = nullptr;  // [1] rows that are not finite or out of range
+  long capacity = 0;
+};
+// table slots for n rows: the power of two >= max(2 n, 1024)
+size_t voxel_table_slots(int n);
+// bytes of the scratch (table 20 B per slot | slot of every row | ballot words | block counts | block offsets | flags)
+size_t voxel_scratch_bytes(int n);
+// five launches on s. flags (device, inside the scratch): voxel_flags(scratch, n)[0] != 0 after the launches = the probe loop ran out
+int launch_voxel_thin(const VoxelParams& p, void* scratch, hipStream_t s);
+const int32_t* voxel_flags(const void* scratch, int n);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

@@ -312,6 +312,7 @@ int md_model_query(md_model_t m, const char* key, int64_t* out) {
   else if (k == "forks") *out = m->forks.load();
   else if (k == "weight_terms") *out = model_root(m)->wterms;
   else if (k == "allocs") *out = m->alloc_count;
+  else if (k == "voxel_overflow") return points_voxel_overflow(m, out);
   else if (k == "da3_shape_builds") *out = da3_shape_builds(m);
   else if (k == "batch_invariant") *out = m->batch_invariant ? 1 : 0;
   else if (k == "ln_fold") *out = m->ln_fold_opt;
@@ -492,6 +493,17 @@ int md_infer_points_normals(md_model_t m, const float* nchw, int B, int H, int W
                             const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                             int out_kind, void* stream) {
   return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, false, nrm);
+}
+
+int md_op_voxel_thin(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                     int64_t N, const md_points_voxel* vox, const md_points_outputs* out, float* normals_out, void* stream) {
+  return op_voxel_thin(dev, xyz_dev, conf_dev, rgb_dev, normals_dev, N, vox, out, normals_out, (hipStream_t)stream);
+}
+
+int md_infer_points_voxel(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                          const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                          const md_points_voxel* vox, int out_kind, void* stream) {
+  return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, false, nrm, vox);
 }
 
 int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {

@@ -364,7 +364,13 @@ int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev,
 // nrm (md_op_unproject_normals / md_infer_points_normals): null or all zero = the call without normals
 int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                  const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream,
-                 const md_view_filter_opts* fo = nullptr, bool filtered = false, const md_points_normals* nrm = nullptr);
+                 const md_view_filter_opts* fo = nullptr, bool filtered = false, const md_points_normals* nrm = nullptr,
+                 const md_points_voxel* vox = nullptr);
+// voxel thinning (md_op_voxel_thin; md_infer_points_voxel = infer_points with `vox`): vox null or voxel == 0 = the call without it
+int op_voxel_thin(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev, int64_t N,
+                  const md_points_voxel* vox, const md_points_outputs* out, float* normals_out, hipStream_t stream);
+// the probe-loop flag of the model's last md_infer_points_voxel (waits for its stream); 0 when it never ran
+int points_voxel_overflow(md_model_t m, int64_t* out);
 int op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_dev, int B, int H, int W, const md_points_cameras* cam,
                     const md_view_filter_opts* o, const md_view_filter_outputs* out, hipStream_t stream);
 void points_destroy_state(md_model_t m);

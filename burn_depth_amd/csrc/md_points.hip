@@ -4,6 +4,8 @@
 // classify / scan / scatter (kernels/points.hip); one captured graph per replay key when the model replays graphs.
 // md_op_filter_views / md_infer_points_filtered put the view filter (kernels/view_filter.hip: confidence percentile, cross-view
 // support) in front of those launches: it hands them a depth in which rejected pixels are 0.
+// md_op_voxel_thin / md_infer_points_voxel put the voxel thinning (kernels/voxel.hip) behind them: the scatter then fills a list
+// of the model's own, and the thinned list goes to the caller.
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -23,6 +25,9 @@ struct md_model_s::PointsState {
   md::GrowBuf<float> x;           // host input image
   md::GrowBuf<uint8_t> rgb;       // host rgb
   md::GrowBuf<void> out;          // device homes of host outputs
+  md::GrowBuf<void> vlist;        // md_infer_points_voxel: the unthinned list (xyz | conf | rgb | normals | count)
+  md::GrowBuf<void> vtable;       // its hash table and compaction scratch (voxel_scratch_bytes)
+  int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
 };
 
 namespace md {
@@ -122,6 +127,22 @@ ViewFilterParams make_filter_params(int B, int H, int W, const md_view_filter_op
   return p;
 }
 
+// rows the unthinned list of a model call can have
+long list_rows(int B, int H, int W, int stride) { return (long)B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride); }
+
+bool voxel_on(const md_points_voxel* vox) { return vox && vox->voxel != 0.f; }
+
+// model call: voxel == 0 is the call without thinning and takes no thinning output
+int check_voxel(const md_points_voxel* vox, const md_points_outputs* out, bool op) {
+  if (!vox) return MD_OK;
+  if (!std::isfinite(vox->voxel) || vox->voxel < 0.f || (op && vox->voxel == 0.f))
+    MD_FAIL(MD_ERR_INVALID_ARG, "voxel = %g: must be finite and %s 0", (double)vox->voxel, op ? ">" : ">=");
+  if ((vox->index || vox->weight) && !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "index / weight need `count`");
+  if (vox->voxel == 0.f && (vox->index || vox->weight || vox->dropped))
+    MD_FAIL(MD_ERR_INVALID_ARG, "index / weight / dropped without a voxel size");
+  return MD_OK;
+}
+
 uintptr_t fbits(float v) {
   uint32_t u;
   memcpy(&u, &v, 4);
@@ -185,12 +206,61 @@ int op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_d
   return rc;
 }
 
+int op_voxel_thin(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev, int64_t N,
+                  const md_points_voxel* vox, const md_points_outputs* out, float* normals_out, hipStream_t stream) {
+  if (!vox) MD_FAIL(MD_ERR_INVALID_ARG, "voxel options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  MD_TRY(check_voxel(vox, out, true));
+  if (N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)N);
+  if (out->capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "capacity %lld is negative", (long long)out->capacity);
+  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "voxel thinning has no dense output");
+  if ((out->xyz || out->rgb || out->conf || normals_out) && !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "the compacted outputs need `count`");
+  if (out->rgb && !rgb_dev) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
+  if (out->conf && !conf_dev) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
+  if (normals_out && !normals_dev) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+  if (N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, got %lld", (long long)N);
+  if (N > 0 && !xyz_dev) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  VoxelParams p;
+  p.xyz = xyz_dev; p.conf = conf_dev; p.rgb = rgb_dev; p.normals = normals_dev;
+  p.n = (int)N; p.B = 1; p.voxel = vox->voxel;
+  p.xyz_out = out->xyz; p.conf_out = out->conf; p.rgb_out = out->rgb; p.normals_out = normals_out;
+  p.index = vox->index; p.weight = vox->weight; p.count = out->count; p.dropped = vox->dropped; p.capacity = out->capacity;
+  void* scratch = nullptr;
+  MD_HIP(hipMalloc(&scratch, voxel_scratch_bytes(p.n)));
+  int rc = launch_voxel_thin(p, scratch, st);
+  int32_t flag = 0;
+  hipError_t se = hipSuccess;
+  if (rc == MD_OK) se = hipMemcpyAsync(&flag, voxel_flags(scratch, p.n), 4, hipMemcpyDeviceToHost, st);
+  const hipError_t sy = hipStreamSynchronize(st);  // the scratch is freed on return
+  (void)hipFree(scratch);
+  if (rc != MD_OK) return rc;
+  MD_HIP(se);
+  MD_HIP(sy);
+  if (flag) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
+  return MD_OK;
+}
+
+int points_voxel_overflow(md_model_t m, int64_t* out) {
+  *out = 0;
+  md_model_s::PointsState* f = m->points;
+  if (!f || !f->vox_rows || !f->vtable.p) return MD_OK;
+  MD_HIP(hipSetDevice(m->dev->ordinal));
+  MD_HIP(hipDeviceSynchronize());  // the call may have run on any stream
+  int32_t flag = 0;
+  MD_HIP(hipMemcpy(&flag, voxel_flags(f->vtable.p, f->vox_rows), 4, hipMemcpyDeviceToHost));
+  *out = flag;
+  return MD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the model call
 // ------------------------------------------------------------------------------------------------
 static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras& cam,
                         const md_points_opts& o, const md_points_outputs& out, int out_kind, bool dual, hipStream_t st,
-                        const md_view_filter_opts* fo, const md_points_normals* nrm) {
+                        const md_view_filter_opts* fo, const md_points_normals* nrm, const md_points_voxel* vox) {
   if (!m->points) m->points = new md_model_s::PointsState();
   md_model_s::PointsState* f = m->points;
   const bool host_in = in_kind == MD_MEM_HOST, host_out = out_kind == MD_MEM_HOST;
@@ -220,7 +290,10 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   PointsParams p = make_params(B, H, W, o);
   p.capacity = out.capacity;
   NormalsParams q = make_normals(nrm);
+  const bool thin = voxel_on(vox) && out.count;  // without the list there is nothing to thin
+  int32_t *v_index = thin ? vox->index : nullptr, *v_weight = thin ? vox->weight : nullptr, *v_dropped = thin ? vox->dropped : nullptr;
   size_t off_map = 0, off_mask = 0, off_xyz = 0, off_rgb = 0, off_conf = 0, off_count = 0, off_nmap = 0, off_nrm = 0, total = 0;
+  size_t off_index = 0, off_weight = 0, off_dropped = 0;
   if (host_out) {
     auto take = [&](bool want, size_t bytes) {
       const size_t at = total;
@@ -235,6 +308,9 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
     off_count = take(out.count, (size_t)(B + 1) * 4);
     off_nmap = take(q.normal_map, npx * 12);
     off_nrm = take(q.normals, cap * 12);
+    off_index = take(v_index, cap * 4);
+    off_weight = take(v_weight, cap * 4);
+    off_dropped = take(v_dropped, 4);
     if (total) MD_TRY(grow(m, st, f->out, total));
     char* base = (char*)f->out.p;
     p.point_map = out.point_map ? (float*)(base + off_map) : nullptr;
@@ -245,9 +321,29 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
     p.count = out.count ? (int32_t*)(base + off_count) : nullptr;
     if (q.normal_map) q.normal_map = (float*)(base + off_nmap);
     if (q.normals) q.normals = (float*)(base + off_nrm);
+    if (v_index) v_index = (int32_t*)(base + off_index);
+    if (v_weight) v_weight = (int32_t*)(base + off_weight);
+    if (v_dropped) v_dropped = (int32_t*)(base + off_dropped);
   } else {
     p.point_map = out.point_map; p.mask = out.mask;
     p.xyz = out.xyz; p.rgb_out = out.rgb; p.conf_out = out.conf; p.count = out.count;
+  }
+  // ---- voxel thinning: the scatter fills the model's own list, the thinning writes where the list would have gone ----
+  const PointsParams dst = p;  // the list outputs of the call, on the device
+  const NormalsParams dstq = q;
+  const long rows = thin ? list_rows(B, H, W, o.stride) : 0;
+  if (thin) {
+    const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = dual ? align_up((size_t)rows * 4, 256) : 0;
+    const size_t b_rgb = dst.rgb_out ? align_up((size_t)rows * 3, 256) : 0, b_nrm = dstq.normals ? b_xyz : 0;
+    MD_TRY(grow(m, st, f->vlist, b_xyz + b_conf + b_rgb + b_nrm + align_up((size_t)(B + 1) * 4, 256)));
+    MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
+    char* base = (char*)f->vlist.p;
+    p.xyz = (float*)base;
+    p.conf_out = dual ? (float*)(base + b_xyz) : nullptr;  // the rank reads the confidence whether or not the caller takes it
+    p.rgb_out = dst.rgb_out ? (uint8_t*)(base + b_xyz + b_conf) : nullptr;
+    q.normals = dstq.normals ? (float*)(base + b_xyz + b_conf + b_rgb) : nullptr;
+    p.count = (int32_t*)(base + b_xyz + b_conf + b_rgb + b_nrm);
+    p.capacity = rows;
   }
   // ---- inputs on the device ----
   const float* x_dev = nchw;
@@ -302,6 +398,17 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   r.begin("points_unproject");
   MD_TRY(launch_unproject(p, f->scratch.p, st, &q));
   r.end();
+  if (thin) {
+    VoxelParams v;
+    v.xyz = p.xyz; v.conf = p.conf_out; v.rgb = p.rgb_out; v.normals = q.normals; v.in_count = p.count;
+    v.n = (int)rows; v.B = B; v.voxel = vox->voxel;
+    v.xyz_out = dst.xyz; v.conf_out = dst.conf_out; v.rgb_out = dst.rgb_out; v.normals_out = dstq.normals;
+    v.index = v_index; v.weight = v_weight; v.count = dst.count; v.dropped = v_dropped; v.capacity = dst.capacity;
+    r.begin("points_voxel");
+    MD_TRY(launch_voxel_thin(v, f->vtable.p, st));
+    r.end();
+    f->vox_rows = (int)rows;
+  }
   if (!host_out) return MD_OK;
   auto d2h = [&](void* dst, const void* srcp, size_t bytes) -> int {
     if (dst && bytes) MD_HIP(hipMemcpyAsync(dst, srcp, bytes, hipMemcpyDeviceToHost, st));
@@ -311,14 +418,24 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
   MD_TRY(d2h(out.point_map, p.point_map, npx * 12));
   MD_TRY(d2h(out.mask, p.mask, npx));
   if (nrm) MD_TRY(d2h(nrm->normal_map, q.normal_map, npx * 12));
-  MD_TRY(d2h(out.count, p.count, (size_t)(B + 1) * 4));
+  MD_TRY(d2h(out.count, dst.count, (size_t)(B + 1) * 4));
+  int32_t overflow = 0;
+  if (thin) {
+    MD_TRY(d2h(vox->dropped, v_dropped, 4));
+    MD_TRY(d2h(&overflow, voxel_flags(f->vtable.p, (int)rows), 4));
+  }
   MD_HIP(hipStreamSynchronize(st));  // host outputs are complete when the call returns
+  if (overflow) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
   if (out.count) {  // only the points that exist travel: the caller's memory beyond them stays as it was
     const size_t n = std::min((size_t)out.count[B], cap);
-    MD_TRY(d2h(out.xyz, p.xyz, n * 12));
-    MD_TRY(d2h(out.rgb, p.rgb_out, n * 3));
-    MD_TRY(d2h(out.conf, p.conf_out, n * 4));
-    if (nrm) MD_TRY(d2h(nrm->normals, q.normals, n * 12));
+    MD_TRY(d2h(out.xyz, dst.xyz, n * 12));
+    MD_TRY(d2h(out.rgb, dst.rgb_out, n * 3));
+    MD_TRY(d2h(out.conf, dst.conf_out, n * 4));
+    if (nrm) MD_TRY(d2h(nrm->normals, dstq.normals, n * 12));
+    if (thin) {
+      MD_TRY(d2h(vox->index, v_index, n * 4));
+      MD_TRY(d2h(vox->weight, v_weight, n * 4));
+    }
     MD_HIP(hipStreamSynchronize(st));
   }
   return MD_OK;
@@ -326,7 +443,7 @@ static int points_eager(md_model_s* m, const float* nchw, int B, int H, int W, i
 
 int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                  const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream, const md_view_filter_opts* fo,
-                 bool filtered, const md_points_normals* nrm) {
+                 bool filtered, const md_points_normals* nrm, const md_points_voxel* vox) {
   if (!m) MD_FAIL(MD_ERR_INVALID_ARG, "model is null");
   if (!nchw) MD_FAIL(MD_ERR_INVALID_ARG, "input pointer is null");
   if ((in_kind != MD_MEM_HOST && in_kind != MD_MEM_DEVICE) || (out_kind != MD_MEM_HOST && out_kind != MD_MEM_DEVICE))
@@ -347,6 +464,9 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   s.focal = c.focal_px != nullptr || m->kind == 0;
   s.E = c.extrinsics != nullptr || dual;
   MD_TRY(check_points(o, out, nrm, s, B, H, W));
+  MD_TRY(check_voxel(vox, out, false));
+  if (voxel_on(vox) && list_rows(B, H, W, o->stride) >= (1l << 30))
+    MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
   if (fo) {
     MD_TRY(check_filter(fo, s.conf, s.K || s.focal, s.E, B, H, W));
     if (fbits(fo->pixel_offset) != fbits(o->pixel_offset) || depth_min_of(fo->depth_min) != depth_min_of(o->depth_min) ||
@@ -361,7 +481,7 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   if (!model_root(m)->committed) MD_FAIL(MD_ERR_INVALID_ARG, "weights were modified; call md_model_commit_weights first");
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = model_stream(m, stream);
-  auto body = [&]() { return points_eager(m, nchw, B, H, W, in_kind, rgb, c, *o, *out, out_kind, dual, st, fo, nrm); };
+  auto body = [&]() { return points_eager(m, nchw, B, H, W, in_kind, rgb, c, *o, *out, out_kind, dual, st, fo, nrm, vox); };
   if (!m->graph_enabled) return body();
   // the key: stream, shape, every option, every in / out pointer and the commit generation (md_frame.hip); a graph only
   // replays at the model's current input size (its workspace plan)
@@ -384,6 +504,8 @@ int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_ki
   if (fo) key.insert(key.end(), {(uintptr_t)0x56464c54u, (uintptr_t)fo->conf_percentile, fbits(fo->view_rtol), (uintptr_t)fo->min_views});
   if (nrm && (nrm->normal_map || nrm->normals || nrm->min_cos > 0.f))  // all zero: the key, and the graph, of the call without normals
     key.insert(key.end(), {(uintptr_t)0x4e524d4cu, (uintptr_t)nrm->normal_map, (uintptr_t)nrm->normals, fbits(nrm->min_cos)});
+  if (voxel_on(vox))  // voxel == 0: the key, and the graph, of the call without thinning
+    key.insert(key.end(), {(uintptr_t)0x564f584cu, fbits(vox->voxel), (uintptr_t)vox->index, (uintptr_t)vox->weight, (uintptr_t)vox->dropped});
   return run_with_graph(m, st, key, eligible, body);
 }
 

@@ -83,7 +83,9 @@ class PointCloud:
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
     which the first min(count[B], capacity) rows are points; count int32 [B+1] (per view, then the total); the depth [B,H,W].
     With normals (`md_op_unproject_normals` / `md_infer_points_normals`): normal_map [B,H,W,3] and normals [capacity,3], rows
-    parallel to xyz."""
+    parallel to xyz. With voxel thinning (`md_op_voxel_thin` / `md_infer_points_voxel`): the list holds one row per occupied
+    voxel, index int32 [capacity] is the source row of every output row in the unthinned list, weight int32 [capacity] the
+    points of its voxel, dropped int32 [1] the rows outside the grid."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -93,6 +95,9 @@ class PointCloud:
     depth: Optional[torch.Tensor] = None
     normal_map: Optional[torch.Tensor] = None
     normals: Optional[torch.Tensor] = None
+    index: Optional[torch.Tensor] = None
+    weight: Optional[torch.Tensor] = None
+    dropped: Optional[torch.Tensor] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -145,6 +150,18 @@ def _points_normals(dev, B: int, H: int, W: int, normals: bool, min_cos: float, 
             out.normals = torch.empty((int(out.xyz.shape[0]), 3), dtype=torch.float32, device=dev)
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     return _lib.MdPointsNormals(ptr(out.normal_map), ptr(out.normals), float(min_cos))
+
+
+def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
+    """md_points_voxel for `out`: with `fresh` index, weight and dropped are created beside the list it has; otherwise the ones it
+    carries are written again."""
+    if fresh and voxel and out.xyz is not None:
+        cap = int(out.xyz.shape[0])
+        out.index = torch.empty(cap, dtype=torch.int32, device=dev)
+        out.weight = torch.empty(cap, dtype=torch.int32, device=dev)
+        out.dropped = torch.empty(1, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    return _lib.MdPointsVoxel(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped))
 
 
 def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
@@ -549,7 +566,7 @@ class DepthPro:
     def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
-                     normal_min_cos: float = 0.0, **opts) -> PointCloud:
+                     normal_min_cos: float = 0.0, voxel: float = 0.0, **opts) -> PointCloud:
         """`md_infer_points`: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the caller's
         (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True). rgb: u8
         [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
@@ -559,7 +576,10 @@ class DepthPro:
         than min_views other views confirm within view_rtol before the unprojection; `depth` is then the filtered depth.
         normals / normal_min_cos (`md_points_normals`): the call is `md_infer_points_normals`, which also returns the surface normals
         (`normal_map`, `normals`) and, with normal_min_cos > 0, drops the pixels seen at a grazing angle; it composes with the view
-        filter."""
+        filter.
+        voxel > 0 (`md_points_voxel`): the call is `md_infer_points_voxel`, which thins the list to one point per occupied voxel of
+        that side (the most confident one, ties to the first) and returns `index`, `weight` and `dropped` beside it; the B views
+        share one grid. It composes with the view filter and the normals."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -573,7 +593,16 @@ class DepthPro:
         cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, f_px)
         rgb_p = C.c_void_p(rgb.data_ptr()) if rgb is not None else None
         filtered = bool(conf_percentile or view_rtol or min_views)
-        if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
+        if voxel or res.index is not None or res.weight is not None or res.dropped is not None:
+            want_nrm = bool(normals or normal_min_cos or res.normal_map is not None or res.normals is not None)
+            nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None) if want_nrm else None
+            vox = _points_voxel(dev, voxel, res, out is None)
+            fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views) if filtered else None
+            _lib.check(self._lib.md_infer_points_voxel(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
+                                                       C.byref(fo) if filtered else None, C.byref(o), C.byref(outs),
+                                                       C.byref(nrm) if want_nrm else None, C.byref(vox), _lib.MD_MEM_DEVICE,
+                                                       _stream_ptr(self.device.ordinal)))
+        elif normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
             nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
             fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views) if filtered else None
             _lib.check(self._lib.md_infer_points_normals(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),

@@ -479,6 +479,34 @@ def filter_views(dev: Device, depth: torch.Tensor, conf: Optional[torch.Tensor] 
     return out.get("depth"), out.get("support"), out.get("tau"), out.get("kept")
 
 
+def voxel_thin(dev: Device, xyz: torch.Tensor, voxel: float, conf: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None,
+               normals: Optional[torch.Tensor] = None, capacity: Optional[int] = None, out: Optional[PointCloud] = None) -> PointCloud:
+    """md_op_voxel_thin: a point list xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) -> `PointCloud` with one input row per
+    occupied voxel of side `voxel`, in input order: xyz / conf / rgb / normals [capacity, ..], index and weight int32 [capacity],
+    count int32 [2] (the survivors, twice: one view), dropped int32 [1]. capacity defaults to N. `out`: a PointCloud of an
+    earlier call to write into again. Bit-identical to `pipeline.voxel_thin`."""
+    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    xyz = _f32c(xyz)
+    N = int(xyz.shape[0])
+    conf = _f32c(conf).reshape(N) if conf is not None else None
+    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if out is None:
+        cap = N if capacity is None else int(capacity)
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=xyz.device)  # noqa: E731
+        out = PointCloud(xyz=f(cap, 3), conf=f(cap) if conf is not None else None, rgb=f(cap, 3, dt=torch.uint8) if rgb is not None else None,
+                         normals=f(cap, 3) if normals is not None else None, count=f(2, dt=torch.int32), index=f(cap, dt=torch.int32),
+                         weight=f(cap, dt=torch.int32), dropped=f(1, dt=torch.int32))
+    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index, out.weight) if t is not None]
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
+    vox = _lib.MdPointsVoxel(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped))
+    _lib.check(_lib.load().md_op_voxel_thin(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(vox), C.byref(outs),
+                                            _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
 def fov_to_focal(fovx_deg: float, H: int, W: int) -> Tuple[float, float]:
     f, y = C.c_float(), C.c_float()
     _lib.check(_lib.load().md_op_fov_to_focal(C.c_float(fovx_deg), H, W, C.byref(f), C.byref(y)))

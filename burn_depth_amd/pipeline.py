@@ -483,6 +483,68 @@ def filter_views(depth, conf=None, intrinsics=None, extrinsics=None, focal_px=No
     return depth_out, support, T(tau), kept
 
 
+@dataclass
+class HostVoxels:
+    xyz: np.ndarray                  # f32 [M,3]: one input row per occupied voxel, in ascending input index
+    conf: Optional[np.ndarray]       # f32 [M]
+    rgb: Optional[np.ndarray]        # uint8 [M,3]
+    normals: Optional[np.ndarray]    # f32 [M,3]
+    index: np.ndarray                # int32 [M]: the source row
+    weight: np.ndarray               # int32 [M]: in-range points of the row's voxel
+    count: np.ndarray                # int32 [B+1]: survivors per view, then their total
+    dropped: int                     # rows that are not finite or outside the grid
+
+
+def voxel_thin(xyz, voxel, conf=None, rgb=None, normals=None, counts=None) -> HostVoxels:
+    """The host reference of md_op_voxel_thin / md_infer_points_voxel (include/mi_depth.h states the contract): of the points of
+    every voxel of side `voxel` the one with the largest confidence survives, among equals the first; the survivors keep the input
+    order and every row is copied unchanged. f32, one rounded operation per step: the device kernels (kernels/voxel.hip) give the
+    same bits. counts: the rows of every view of the input, [B] (default: one view) -> `count` per view."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    N = len(p)
+    vs = np.float32(voxel)
+    if not np.isfinite(vs) or not vs > 0:
+        raise ValueError("voxel must be finite and > 0")
+    if N >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows")
+    cf = None if conf is None else np.ascontiguousarray(conf, dtype=np.float32).reshape(N)
+    half = np.float32(1 << 20)
+    with np.errstate(all="ignore"):
+        c = np.floor(p / vs)
+        ok = np.isfinite(p).all(1) & (c >= -half).all(1) & (c < half).all(1)
+    idx = np.nonzero(ok)[0].astype(np.uint64)
+    cell = (c[ok].astype(np.int64) + (1 << 20)).astype(np.uint64)
+    key = (cell[:, 0] << np.uint64(42)) | (cell[:, 1] << np.uint64(21)) | cell[:, 2]
+    w = np.zeros(len(idx), np.uint64)
+    if cf is not None:
+        ci = cf[ok]
+        with np.errstate(all="ignore"):
+            use = np.isfinite(ci) & (ci >= 0)
+        wb = ci.view(np.uint32).astype(np.uint64)
+        wb[wb == 0x80000000] = 0  # -0 counts as +0
+        w = np.where(use, wb, np.uint64(0))
+    rank = (w << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx)  # the device's atomicMax word
+    order = np.lexsort((rank, key))
+    ks = key[order]
+    last = np.ones(len(ks), bool)
+    last[:-1] = ks[1:] != ks[:-1]  # the largest rank of every key
+    first = np.ones(len(ks), bool)
+    first[1:] = last[:-1]
+    size = np.diff(np.append(np.nonzero(first)[0], len(ks)))
+    win = (np.uint64(0xFFFFFFFF) - (rank[order][last] & np.uint64(0xFFFFFFFF))).astype(np.int64)
+    asc = np.argsort(win, kind="stable")
+    index, weight = win[asc].astype(np.int32), size[asc].astype(np.int32)
+    if counts is None:
+        bounds = np.array([0, N], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64).reshape(-1))]), N)
+    per_view = np.diff(np.searchsorted(index, bounds, side="left"))
+    count = np.concatenate([per_view, [len(index)]]).astype(np.int32)
+    take = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)[index]  # noqa: E731
+    return HostVoxels(p[index], None if cf is None else cf[index], take(rgb, np.uint8, (N, 3)), take(normals, np.float32, (N, 3)), index,
+                      weight, count, int(N - ok.sum()))
+
+
 def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None) -> None:
     """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
@@ -589,7 +651,8 @@ class AnyDepthModel:
     def infer_points(self, x, **kw):
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
-        filter, `md_infer_points_filtered`) and normals= / normal_min_cos= (`md_infer_points_normals`) included."""
+        filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`) and voxel= (`md_infer_points_voxel`)
+        included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

@@ -417,6 +417,59 @@ int md_infer_points_normals(md_model_t m, const float* nchw, int B, int H, int W
                             const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm, int out_kind,
                             void* stream);
 
+/* ---- point path: voxel thinning of a point list ------------------------------------------------------------------------
+ * A list xyz f32 [N,3] with optional parallel rows conf f32 [N], rgb u8 [N,3] and normals f32 [N,3] -> one input row per
+ * occupied voxel of side `voxel` > 0. Selection, not averaging: the output is a subset of the input rows, and nothing in
+ * it depends on the order in which threads arrive. f32, one rounded operation per step, no fused multiply-add
+ * (pipeline.voxel_thin restates it in numpy bit for bit):
+ *   cell: c_a = floorf(p_a / voxel) for a = x, y, z. Point i is in range when its three coordinates are finite and
+ *     -2^20 <= c_a < 2^20 on every axis (compared in float). key = ((c_x + 2^20) << 42) | ((c_y + 2^20) << 21) |
+ *     (c_z + 2^20), an unsigned 64-bit integer; the all-ones word never occurs and marks an empty table slot. Points out of
+ *     range are dropped and counted (`dropped`).
+ *   rank: w = conf_i when there is a confidence row and conf_i is finite and >= 0 (-0 counts as +0), otherwise w = 0. The
+ *     survivor of a voxel is its in-range point with the largest w; among equals the smallest input index wins. On the
+ *     device this is one atomicMax of the word (bits(w) << 32) | (0xFFFFFFFF - i): the bit pattern of a non-negative finite
+ *     f32 is monotone in its value.
+ *   weight = the number of in-range points of the survivor's voxel (an integer atomicAdd).
+ *   output: the survivors in ascending input index, so the (view, row, column) order of the point path is kept; every given
+ *     row is copied unchanged; index = the source row, weight as above. count[b] = the survivors of view b, count[B] = their
+ *     total M, also when M exceeds `capacity`: then only the first `capacity` rows are written and the memory behind them
+ *     stays untouched. All views of a call are one scene: they share the voxel grid.
+ *   f32 denormals are outside the contract.
+ * The table is open addressing with linear probing over a power of two >= 2 N slots of 20 bytes in device memory, reset on
+ * the stream inside every call; the hash is a fixed 64-bit mixer and cannot influence the result. */
+typedef struct md_points_voxel {
+  float voxel;      /* voxel side; 0 = no thinning (md_infer_points_voxel), finite and >= 0 */
+  int32_t* index;   /* int32 [capacity]: the source row of every output row; needs count. NULL = skip */
+  int32_t* weight;  /* int32 [capacity]: in-range points in the output row's voxel; needs count. NULL = skip */
+  int32_t* dropped; /* int32 [1]: rows not finite or out of range. NULL = skip */
+} md_points_voxel;
+
+/* The stand-alone operator on caller device lists: the N rows are one view. Of `out` the fields xyz, rgb, conf, count
+ * (int32 [2]: M twice, the point path's [B+1] with B = 1) and capacity are used, the others must be NULL; normals_out
+ * [capacity,3] takes the normals rows. Everything is enqueued on `stream`; the call returns after the stream has drained,
+ * because its table is freed on return. Errors, before any launch: dev / vox / out NULL, xyz_dev NULL with N > 0, voxel not
+ * finite or <= 0, N < 0, capacity < 0, a compacted output (xyz, rgb, conf, normals_out, index, weight) without count, an
+ * rgb / conf / normals output without that input row, a dense output or out->depth set -> MD_ERR_INVALID_ARG;
+ * N >= 2^30 -> MD_ERR_SHAPE. A probe loop that ran out of table (impossible at load <= 0.5) -> MD_ERR_HIP after the launches. */
+int md_op_voxel_thin(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                     int64_t N, const md_points_voxel* vox, const md_points_outputs* out, float* normals_out, void* stream);
+/* md_infer_points_normals with the thinning behind the scatter: the unthinned list (at most B ceil(H/stride) ceil(W/stride)
+ * rows) goes to a grow-only buffer of the model, as does the table; the thinned list goes to out->xyz / rgb / conf and
+ * nrm->normals, and out->count receives the thinned counts. The confidence row is the model's confidence map where it has
+ * one (dual head), whether or not out->conf is set. The dense outputs are those of the call without thinning. vox's
+ * pointers are of out_kind. vox NULL or voxel == 0 (index, weight and dropped then NULL): md_infer_points_normals on the
+ * same arguments, the same launches and bits; a call without out->count thins nothing. The graph key contains vox's four
+ * fields. Errors as md_infer_points_normals', plus, before any launch: voxel not finite or negative, index / weight without
+ * count, index / weight / dropped with voxel == 0 -> MD_ERR_INVALID_ARG; B ceil(H/stride) ceil(W/stride) >= 2^30 ->
+ * MD_ERR_SHAPE. With host outputs a probe loop that ran out of table -> MD_ERR_HIP; with device outputs the call does not
+ * wait for the device and md_model_query(m, "voxel_overflow") reads the flag of the last call (it waits for the
+ * device). After the first call of a shape nothing is allocated. */
+int md_infer_points_voxel(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                          const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                          const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                          const md_points_voxel* vox, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

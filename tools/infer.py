@@ -21,6 +21,9 @@ through `infer_views` (cross-view attention, `md_da3_infer_views`), so depths an
 view is written beside `--output` (`depth_v0.png`, ...). With `--ply` the device outputs go to `ops.filter_views` (`--view-rtol`,
 `--min-views`, `--conf-percentile`) and `ops.unproject` with the model's own extrinsics and intrinsics: one world-space cloud.
 
+`--voxel X` (with `--ply`): the cloud is thinned on the device to one point per occupied voxel of side X, the most confident one
+(`md_infer_points_voxel`; with `--views`, `ops.voxel_thin` over the cloud of all views, which share the grid).
+
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
 restored to the original size, min-max normalised and written as an 8-bit PNG (example/inference.rs:103-199)."""
@@ -81,8 +84,17 @@ def run_views(a) -> int:
         rgb = torch.from_numpy(np.stack([p.rgb for p in preps])).to(depth.device)
         pc = ops.unproject(dev, depth, intrinsics=K, extrinsics=E, conf=out.depth_confidence, rgb=rgb, dense=False, conf_min=a.conf_min,
                            edge_rtol=a.edge_rtol, stride=a.stride, world=True, normals=a.normals, normal_min_cos=a.normal_min_cos)
-        xyz, col, _ = pc.points()
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None)
+        xyz, col, conf = pc.points()
+        nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.voxel > 0:  # one point per occupied voxel over all views: the most confident one
+            try:
+                pc = ops.voxel_thin(dev, xyz, a.voxel, conf=conf, rgb=col, normals=nrm)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            xyz, col, _ = pc.points()
+            nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None)
         print(f"Model `{a.model}` wrote {xyz.shape[0]} points of {len(imgs)} views to {a.ply}")
     return 0
 
@@ -107,6 +119,8 @@ def main(argv=None) -> int:
     ap.add_argument("--normals", action="store_true", help="--ply: also write the surface normals (nx ny nz; md_infer_points_normals)")
     ap.add_argument("--normal-min-cos", type=float, default=0.0,
                     help="--ply: drop pixels whose surface is seen at a cosine below this (grazing angles; 0 = off, at most 1)")
+    ap.add_argument("--voxel", type=float, default=0.0,
+                    help="--ply: keep one point per occupied voxel of this side, the most confident one (md_infer_points_voxel; 0 = off)")
     a = ap.parse_args(argv)
     if a.focal_px is not None and a.model != "depth-pro":
         print(f"--focal-px applies to Depth Pro only, not to `{a.model}`", file=sys.stderr)
@@ -148,7 +162,7 @@ def main(argv=None) -> int:
             pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
                                     dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
                                     world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
-                                    normal_min_cos=a.normal_min_cos)
+                                    normal_min_cos=a.normal_min_cos, voxel=a.voxel)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
