@@ -455,12 +455,12 @@ void md_points_opts_default(md_points_opts* o) {
 
 int md_op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
                     const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, void* stream) {
-  return op_unproject(dev, depth_dev, conf_dev, rgb_dev, B, H, W, cam, o, out, (hipStream_t)stream);
+  return op_unproject(dev, DepthMaps{depth_dev, conf_dev, rgb_dev, B, H, W}, cam, o, out, nullptr, (hipStream_t)stream);
 }
 
 int md_infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                     const md_points_opts* o, const md_points_outputs* out, int out_kind, void* stream) {
-  return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream);
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, nullptr, nullptr, nullptr, false}, (hipStream_t)stream);
 }
 
 void md_view_filter_opts_default(md_view_filter_opts* o) {
@@ -474,36 +474,36 @@ void md_view_filter_opts_default(md_view_filter_opts* o) {
 
 int md_op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_dev, int B, int H, int W, const md_points_cameras* cam,
                        const md_view_filter_opts* o, const md_view_filter_outputs* out, void* stream) {
-  return op_filter_views(dev, depth_dev, conf_dev, B, H, W, cam, o, out, (hipStream_t)stream);
+  return op_filter_views(dev, DepthMaps{depth_dev, conf_dev, nullptr, B, H, W}, cam, o, out, (hipStream_t)stream);
 }
 
 int md_infer_points_filtered(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
                              const md_points_cameras* cam, const md_view_filter_opts* fo, const md_points_opts* o,
                              const md_points_outputs* out, int out_kind, void* stream) {
-  return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, true);
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nullptr, nullptr, true}, (hipStream_t)stream);
 }
 
 int md_op_unproject_normals(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
                             const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                             void* stream) {
-  return op_unproject(dev, depth_dev, conf_dev, rgb_dev, B, H, W, cam, o, out, (hipStream_t)stream, nrm);
+  return op_unproject(dev, DepthMaps{depth_dev, conf_dev, rgb_dev, B, H, W}, cam, o, out, nrm, (hipStream_t)stream);
 }
 
 int md_infer_points_normals(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                             const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                             int out_kind, void* stream) {
-  return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, false, nrm);
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, nullptr, false}, (hipStream_t)stream);
 }
 
 int md_op_voxel_thin(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
                      int64_t N, const md_points_voxel* vox, const md_points_outputs* out, float* normals_out, void* stream) {
-  return op_voxel_thin(dev, xyz_dev, conf_dev, rgb_dev, normals_dev, N, vox, out, normals_out, (hipStream_t)stream);
+  return op_voxel_thin(dev, PointList{xyz_dev, conf_dev, rgb_dev, normals_dev, N}, vox, out, normals_out, (hipStream_t)stream);
 }
 
 int md_infer_points_voxel(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
                           const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                           const md_points_voxel* vox, int out_kind, void* stream) {
-  return infer_points(m, nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, (hipStream_t)stream, fo, false, nrm, vox);
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false}, (hipStream_t)stream);
 }
 
 int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {

@@ -356,23 +356,46 @@ int process_frame(md_model_t m, const uint8_t* rgb, int B, int w, int h, int in_
                   int out_kind, hipStream_t stream);
 // crop (cx, cy, cw, ch) of a [B,h,w] map, restored to ow x oh (no restore at the crop's own size)
 DisplayGeom display_geom(int B, int h, int w, int cx, int cy, int cw, int ch, int ow, int oh);
-// the point path (md_points.hip): the stand-alone operator on caller tensors, the model -> points call and its state
-int op_unproject(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
-                 const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, hipStream_t stream,
-                 const md_points_normals* nrm = nullptr);
-// filtered = the md_infer_points_filtered entry: `fo` is required and the view filter runs between the model and the unprojection.
-// nrm (md_op_unproject_normals / md_infer_points_normals): null or all zero = the call without normals
-int infer_points(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
-                 const md_points_opts* o, const md_points_outputs* out, int out_kind, hipStream_t stream,
-                 const md_view_filter_opts* fo = nullptr, bool filtered = false, const md_points_normals* nrm = nullptr,
-                 const md_points_voxel* vox = nullptr);
-// voxel thinning (md_op_voxel_thin; md_infer_points_voxel = infer_points with `vox`): vox null or voxel == 0 = the call without it
-int op_voxel_thin(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev, int64_t N,
-                  const md_points_voxel* vox, const md_points_outputs* out, float* normals_out, hipStream_t stream);
+// the point path (md_points.hip): the stand-alone operators on caller tensors, the model -> points call and its state
+struct DepthMaps {  // an operator's input maps on the device: depth [B,H,W], conf [B,H,W] or null, u8 rgb [B,H,W,3] or null
+  const float* depth = nullptr;
+  const float* conf = nullptr;
+  const uint8_t* rgb = nullptr;
+  int B = 0, H = 0, W = 0;
+};
+struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], conf [N] / u8 rgb [N,3] / normals [N,3] or null
+  const float* xyz = nullptr;
+  const float* conf = nullptr;
+  const uint8_t* rgb = nullptr;
+  const float* normals = nullptr;
+  int64_t N = 0;
+};
+// One md_infer_points* request: what the widest entry (md_infer_points_voxel) takes. A narrower entry leaves the parts it lacks
+// null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
+struct PointsCall {
+  const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
+  int B = 0, H = 0, W = 0;
+  int in_kind = MD_MEM_DEVICE;
+  const uint8_t* rgb = nullptr;  // of in_kind
+  const md_points_cameras* cam = nullptr;
+  const md_points_opts* o = nullptr;
+  const md_points_outputs* out = nullptr;  // pointers of out_kind, as are nrm's and vox's
+  int out_kind = MD_MEM_DEVICE;
+  const md_view_filter_opts* fo = nullptr;  // given: the view filter runs between the model and the unprojection
+  const md_points_normals* nrm = nullptr;
+  const md_points_voxel* vox = nullptr;
+  bool need_filter = false;  // the md_infer_points_filtered entry: a null `fo` is refused
+};
+// nrm (md_op_unproject_normals): null or all zero = md_op_unproject
+int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
+                 const md_points_normals* nrm, hipStream_t stream);
+int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream);
+int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* vox, const md_points_outputs* out, float* normals_out,
+                  hipStream_t stream);
 // the probe-loop flag of the model's last md_infer_points_voxel (waits for its stream); 0 when it never ran
 int points_voxel_overflow(md_model_t m, int64_t* out);
-int op_filter_views(md_device_t dev, const float* depth_dev, const float* conf_dev, int B, int H, int W, const md_points_cameras* cam,
-                    const md_view_filter_opts* o, const md_view_filter_outputs* out, hipStream_t stream);
+int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_view_filter_opts* o,
+                    const md_view_filter_outputs* out, hipStream_t stream);
 void points_destroy_state(md_model_t m);
 int pack_weight(const float* src, const PackEntry& e, int prec, hipStream_t s);
 // number of values of w[0..n) that are not exactly representable as an IEEE half (synchronises the stream)

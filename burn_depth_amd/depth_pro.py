@@ -106,6 +106,10 @@ class PointCloud:
         return cut(self.xyz), cut(self.rgb), cut(self.conf)
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
 def _points_opts(pixel_offset=0.0, depth_min=0.0, depth_max=0.0, conf_min=0.0, edge_rtol=0.0, stride=1, world=False) -> "_lib.MdPointsOpts":
     return _lib.MdPointsOpts(float(pixel_offset), float(depth_min), float(depth_max), float(conf_min), float(edge_rtol), int(stride),
                              int(bool(world)))
@@ -131,9 +135,8 @@ def _points_outputs(dev, B: int, H: int, W: int, dense: bool, compact: bool, cap
             out.conf = f(cap) if want_conf else None
         if want_depth:
             out.depth = f(B, H, W)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    c = _lib.MdPointsOutputs(ptr(out.point_map), ptr(out.mask), ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count),
-                             int(out.xyz.shape[0]) if out.xyz is not None else 0, ptr(out.depth))
+    c = _lib.MdPointsOutputs(_ptr(out.point_map), _ptr(out.mask), _ptr(out.xyz), _ptr(out.rgb), _ptr(out.conf), _ptr(out.count),
+                             int(out.xyz.shape[0]) if out.xyz is not None else 0, _ptr(out.depth))
     return out, c
 
 
@@ -148,8 +151,7 @@ def _points_normals(dev, B: int, H: int, W: int, normals: bool, min_cos: float, 
             out.normal_map = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
         if out.xyz is not None:
             out.normals = torch.empty((int(out.xyz.shape[0]), 3), dtype=torch.float32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    return _lib.MdPointsNormals(ptr(out.normal_map), ptr(out.normals), float(min_cos))
+    return _lib.MdPointsNormals(_ptr(out.normal_map), _ptr(out.normals), float(min_cos))
 
 
 def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
@@ -160,8 +162,7 @@ def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
         out.index = torch.empty(cap, dtype=torch.int32, device=dev)
         out.weight = torch.empty(cap, dtype=torch.int32, device=dev)
         out.dropped = torch.empty(1, dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    return _lib.MdPointsVoxel(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped))
+    return _lib.MdPointsVoxel(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped))
 
 
 def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
@@ -182,6 +183,28 @@ def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None
         return t.data_ptr()
 
     return _lib.MdPointsCameras(put(intrinsics, B * 9), put(extrinsics, B * 12), put(focal_px, B)), keep
+
+
+def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrinsics, focal_px, want_rgb: bool, want_conf: bool,
+                    want_depth: bool, dense: bool, compact: bool, capacity: Optional[int], out: Optional[PointCloud], normals: bool,
+                    normal_min_cos: float, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
+                    voxel: Optional[float] = None):
+    """The keyword set of `infer_points` / `ops.unproject` as the structs of the widest entry -> (cloud, opts, outs, cam, fo, nrm,
+    vox, keep-alive). fo, nrm and vox are None for the parts not asked for (an `out` that carries normal or thinning tensors asks
+    for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless `out` is given. Positional
+    arguments and a plain tuple back: this sits on the host path of every call. opts: the fields of `md_points_opts`; want_rgb /
+    want_conf / want_depth: the call can fill those outputs."""
+    o = _points_opts(**opts)
+    res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
+    cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
+    fo = nrm = vox = None
+    if conf_percentile or view_rtol or min_views:
+        fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
+    if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
+        nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
+    if voxel is not None and (voxel or res.index is not None or res.weight is not None or res.dropped is not None):
+        vox = _points_voxel(dev, voxel, res, out is None)
+    return res, o, outs, cam, fo, nrm, vox, keep
 
 
 @dataclass
@@ -567,19 +590,20 @@ class DepthPro:
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
                      normal_min_cos: float = 0.0, voxel: float = 0.0, **opts) -> PointCloud:
-        """`md_infer_points`: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the caller's
-        (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True). rgb: u8
-        [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
+        """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
+        caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
+        rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the call is
-        `md_infer_points_filtered`, which drops the lowest conf_percentile % of the confidences of the call and the pixels fewer
-        than min_views other views confirm within view_rtol before the unprojection; `depth` is then the filtered depth.
-        normals / normal_min_cos (`md_points_normals`): the call is `md_infer_points_normals`, which also returns the surface normals
-        (`normal_map`, `normals`) and, with normal_min_cos > 0, drops the pixels seen at a grazing angle; it composes with the view
-        filter.
-        voxel > 0 (`md_points_voxel`): the call is `md_infer_points_voxel`, which thins the list to one point per occupied voxel of
-        that side (the most confident one, ties to the first) and returns `index`, `weight` and `dropped` beside it; the B views
-        share one grid. It composes with the view filter and the normals."""
+        Every form runs through the widest entry, `md_infer_points_voxel`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` on the same arguments:
+        conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
+        conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
+        before the unprojection; `depth` is then the filtered depth.
+        normals / normal_min_cos (`md_points_normals`): also returns the surface normals (`normal_map`, `normals`) and, with
+        normal_min_cos > 0, drops the pixels seen at a grazing angle; it composes with the view filter.
+        voxel > 0 (`md_points_voxel`): thins the list to one point per occupied voxel of that side (the most confident one, ties to
+        the first) and returns `index`, `weight` and `dropped` beside it; the B views share one grid. It composes with the view
+        filter and the normals."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -587,35 +611,15 @@ class DepthPro:
         B, _, H, W = (int(v) for v in x.shape)
         if rgb is not None:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
-        o = _points_opts(**opts)
         has_conf = bool(getattr(self.config, "dual_head", False))
-        res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, rgb is not None, has_conf, True, out)
-        cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, f_px)
-        rgb_p = C.c_void_p(rgb.data_ptr()) if rgb is not None else None
-        filtered = bool(conf_percentile or view_rtol or min_views)
-        if voxel or res.index is not None or res.weight is not None or res.dropped is not None:
-            want_nrm = bool(normals or normal_min_cos or res.normal_map is not None or res.normals is not None)
-            nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None) if want_nrm else None
-            vox = _points_voxel(dev, voxel, res, out is None)
-            fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views) if filtered else None
-            _lib.check(self._lib.md_infer_points_voxel(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
-                                                       C.byref(fo) if filtered else None, C.byref(o), C.byref(outs),
-                                                       C.byref(nrm) if want_nrm else None, C.byref(vox), _lib.MD_MEM_DEVICE,
-                                                       _stream_ptr(self.device.ordinal)))
-        elif normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
-            nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
-            fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views) if filtered else None
-            _lib.check(self._lib.md_infer_points_normals(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
-                                                         C.byref(fo) if filtered else None, C.byref(o), C.byref(outs), C.byref(nrm),
-                                                         _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
-        elif filtered:
-            fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
-            _lib.check(self._lib.md_infer_points_filtered(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
-                                                          C.byref(fo), C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE,
-                                                          _stream_ptr(self.device.ordinal)))
-        else:
-            _lib.check(self._lib.md_infer_points(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, rgb_p, C.byref(cam),
-                                                 C.byref(o), C.byref(outs), _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        res, o, outs, cam, fo, nrm, vox, keep = _points_request(
+            dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
+            normal_min_cos, conf_percentile, view_rtol, min_views, voxel)
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        _lib.check(self._lib.md_infer_points_voxel(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                   C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                   C.byref(o), C.byref(outs), ref(nrm), ref(vox), _lib.MD_MEM_DEVICE,
+                                                   _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import Device, PointCloud, _points_cameras, _points_normals, _points_opts, _points_outputs, _stream_ptr, _view_filter_opts
+from .depth_pro import Device, PointCloud, _points_cameras, _points_request, _stream_ptr, _view_filter_opts
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -435,25 +435,19 @@ def conv2d_direct_ex(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Option
 def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None, focal_px=None, conf: Optional[torch.Tensor] = None,
               rgb: Optional[torch.Tensor] = None, dense: bool = True, compact: bool = True, capacity: Optional[int] = None,
               out: Optional[PointCloud] = None, normals: bool = False, normal_min_cos: float = 0.0, **opts) -> PointCloud:
-    """md_op_unproject: depth [B,H,W] (+ conf [B,H,W], + u8 rgb [B,H,W,3]) and pinhole cameras (intrinsics [B,3,3] or focal_px [B];
-    extrinsics [B,3,4] world-to-camera for world=True) -> `PointCloud`. opts: the fields of `md_points_opts`. normals / normal_min_cos
-    (or an `out` that carries normal tensors): md_op_unproject_normals, the surface normals beside the points and the grazing-angle
-    test. Bit-identical to `pipeline.unproject_depth`."""
+    """md_op_unproject_normals: depth [B,H,W] (+ conf [B,H,W], + u8 rgb [B,H,W,3]) and pinhole cameras (intrinsics [B,3,3] or focal_px
+    [B]; extrinsics [B,3,4] world-to-camera for world=True) -> `PointCloud`. opts: the fields of `md_points_opts`. normals /
+    normal_min_cos (or an `out` that carries normal tensors): the surface normals beside the points and the grazing-angle test;
+    without them the entry gets NULL normals, which is md_op_unproject. Bit-identical to `pipeline.unproject_depth`."""
     depth = _f32c(depth)
     B, H, W = (int(v) for v in depth.shape)
     conf = _f32c(conf) if conf is not None else None
     rgb = rgb.contiguous() if rgb is not None else None
     assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
-    o = _points_opts(**opts)
-    res, outs = _points_outputs(depth.device, B, H, W, dense, compact, capacity, max(o.stride, 1), rgb is not None, conf is not None, False, out)
-    cam, keep = _points_cameras(depth.device, B, intrinsics, extrinsics, focal_px)
-    if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
-        nrm = _points_normals(depth.device, B, H, W, normals, normal_min_cos, res, out is None)
-        _lib.check(_lib.load().md_op_unproject_normals(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o),
-                                                       C.byref(outs), C.byref(nrm), _stream_ptr(dev.ordinal)))
-    else:
-        _lib.check(_lib.load().md_op_unproject(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
-                                               _stream_ptr(dev.ordinal)))
+    res, o, outs, cam, _, nrm, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
+                                                         conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos)
+    _lib.check(_lib.load().md_op_unproject_normals(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
+                                                   C.byref(nrm) if nrm is not None else None, _stream_ptr(dev.ordinal)))
     del keep
     return res
 

@@ -18,43 +18,11 @@ if ROOT not in sys.path:
 
 from burn_depth_amd import _lib  # noqa: E402
 from burn_depth_amd import pipeline as P  # noqa: E402
+from points_util import _bits, _cameras, _cloud_np, _da3, _da3_subset, _image, _pro, _rotation, _same_cloud, _t, dev, lib  # noqa: E402,F401
 
 f32 = np.float32
 U = 2.0 ** -24  # unit roundoff of f32
 NEW_ENTRIES = ("md_points_opts_default", "md_op_unproject", "md_infer_points")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from burn_depth_amd.depth_pro import Device
-    return Device(0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def _rotation(rng):
-    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
-    q = q * np.sign(np.diag(r))
-    if np.linalg.det(q) < 0:
-        q[:, 0] = -q[:, 0]
-    return q
-
-
-def _cameras(rng, B, H, W):
-    K = np.zeros((B, 3, 3), f32)
-    E = np.zeros((B, 3, 4), f32)
-    for b in range(B):
-        K[b] = [[0.9 * W + b, 0, W / 2 + 0.3], [0, 0.8 * W + 2 * b, H / 2 - 0.7], [0, 0, 1]]
-        E[b, :, :3] = _rotation(rng)
-        E[b, :, 3] = rng.uniform(-2, 2, 3)
-    return K, E
 
 
 def _noise_scene(B, H, W, seed=7):
@@ -279,10 +247,6 @@ def test_point_argument_errors_without_a_gpu(lib):
 POISON = 123456.0
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda() if a is not None else None
-
-
 def _run_op(dev, d, K=None, E=None, focal=None, conf=None, rgb=None, capacity=None, **opts):
     """ops.unproject on poisoned outputs -> numpy dict."""
     from burn_depth_amd import ops
@@ -438,56 +402,10 @@ def test_four_views_of_a_plane_fuse_onto_it(dev):
 
 
 # ---- the model call ----
-def _da3(dev, variant, precision, max_batch=2):
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthAnything3Config, Precision
-    from burn_depth_amd.depth_anything3 import DepthAnything3
-    cfg = {"tiny": DepthAnything3Config.tiny_test, "tiny_dual": DepthAnything3Config.tiny_dual_test}[variant]()
-    cfg.max_batch, cfg.precision = max_batch, getattr(Precision, precision)
-    return DepthAnything3.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _pro(dev, precision, max_batch=2):
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthProConfig, Precision
-    from burn_depth_amd.depth_pro import DepthPro
-    cfg = DepthProConfig.tiny_test()
-    cfg.max_batch, cfg.precision = max_batch, getattr(Precision, precision)
-    return DepthPro.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _image(B, S, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(B, 3, S, S, generator=g) - 0.45) / 0.225
 
 
 def _rgb(B, S):
     return np.random.default_rng(4).integers(0, 256, (B, S, S, 3), dtype=np.uint8)
-
-
-def _cloud_np(pc):
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in vars(pc).items()}
-
-
-def _same_cloud(a, b, what=""):
-    for k in ("count", "mask", "point_map", "depth"):
-        if a[k] is not None and b.get(k) is not None:
-            assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
-    n = min(int(a["count"][-1]), a["xyz"].shape[0])
-    for k in ("xyz", "rgb", "conf"):
-        if a[k] is not None:
-            assert b[k] is not None and np.array_equal(a[k][:n].view(np.uint8), b[k][:n].view(np.uint8)), (what, k)
-
-
-def _da3_subset(m, x):
-    """md_da3_infer_ex with the outputs md_infer_points asks the model for: depth, confidence, extrinsics, intrinsics."""
-    B, _, H, W = x.shape
-    f = lambda *s: torch.empty(s, dtype=torch.float32, device="cuda")  # noqa: E731
-    depth, conf, extr, intr = f(B, H, W), f(B, H, W), f(B, 1, 3, 4), f(B, 1, 3, 3)
-    o = _lib.MdDa3Outputs(depth.data_ptr(), conf.data_ptr(), None, None, None, extr.data_ptr(), intr.data_ptr())
-    _lib.check(_lib.load().md_da3_infer_ex(m._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, C.byref(o), _lib.MD_MEM_DEVICE,
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return depth, conf, extr, intr
 
 
 OPTS = dict(pixel_offset=0.5, stride=2, edge_rtol=0.5)
@@ -571,7 +489,7 @@ def test_infer_points_da3_mono_needs_the_callers_cameras(dev):
 @pytest.mark.parametrize("precision", ["F32", "BF16"])
 def test_infer_points_depth_pro_equals_infer_then_unproject(dev, precision):
     from burn_depth_amd import ops
-    m = _pro(dev, precision)
+    m = _pro(dev, "tiny", precision)
     fork = None
     try:
         x = _image(2, 512).cuda()
@@ -616,7 +534,7 @@ def test_infer_points_depth_pro_equals_infer_then_unproject(dev, precision):
 @pytest.mark.gpu
 @pytest.mark.parametrize("model", ["da3", "pro"])
 def test_infer_points_graph_replay_and_allocations(dev, model):
-    m = _da3(dev, "tiny_dual", "BF16") if model == "da3" else _pro(dev, "BF16")
+    m = _da3(dev, "tiny_dual", "BF16") if model == "da3" else _pro(dev, "tiny", "BF16")
     S = 70 if model == "da3" else 512
     try:
         x = _image(2, S).cuda()

@@ -4,6 +4,7 @@ the kernels.
 
 The CPU tests need no GPU; the others run with `-m gpu` on an MI355X."""
 import ctypes as C
+import functools
 import importlib.util
 import os
 import re
@@ -19,44 +20,15 @@ if ROOT not in sys.path:
 
 from burn_depth_amd import _lib  # noqa: E402
 from burn_depth_amd import pipeline as P  # noqa: E402
+import points_util  # noqa: E402
+from points_util import _bits, _cameras, _cloud_np, _da3, _da3_subset, _image, _pro, _t, dev, lib  # noqa: E402,F401
+
+_same_cloud = functools.partial(points_util._same_cloud, normals=True)
 
 f32 = np.float32
 U = 2.0 ** -24  # unit roundoff of f32
 NEW_ENTRIES = ("md_op_unproject_normals", "md_infer_points_normals")
 MIN_COS = 0.5
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from burn_depth_amd.depth_pro import Device
-    return Device(0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def _rotation(rng):
-    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
-    q = q * np.sign(np.diag(r))
-    if np.linalg.det(q) < 0:
-        q[:, 0] = -q[:, 0]
-    return q
-
-
-def _cameras(rng, B, H, W):
-    K = np.zeros((B, 3, 3), f32)
-    E = np.zeros((B, 3, 4), f32)
-    for b in range(B):
-        K[b] = [[0.9 * W + b, 0, W / 2 + 0.3], [0, 0.8 * W + 2 * b, H / 2 - 0.7], [0, 0, 1]]
-        E[b, :, :3] = _rotation(rng)
-        E[b, :, 3] = rng.uniform(-2, 2, 3)
-    return K, E
 
 
 def _scene(B, H, W, seed=11):
@@ -426,10 +398,6 @@ POISON = 123456.0
 CANARY = 16  # elements behind the end of every output buffer
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda() if a is not None else None
-
-
 def _guarded(shape, fill, dtype=torch.float32):
     """(a tensor of `shape` filled with `fill`, its backing store with CANARY more elements behind it)"""
     n = int(np.prod(shape))
@@ -589,51 +557,6 @@ def test_two_views_of_a_tilted_plane_agree_on_its_world_normal(dev):
 
 
 # ---- the model call ----
-def _da3(dev, precision, max_batch=2):
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthAnything3Config, Precision
-    from burn_depth_amd.depth_anything3 import DepthAnything3
-    cfg = DepthAnything3Config.tiny_dual_test()
-    cfg.max_batch, cfg.precision = max_batch, getattr(Precision, precision)
-    return DepthAnything3.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _pro(dev, precision, max_batch=2):
-    """Depth Pro at the small preset (128-pixel windows, a 512 x 512 input)"""
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthProConfig, Precision
-    from burn_depth_amd.depth_pro import DepthPro
-    cfg = DepthProConfig.small_test()
-    cfg.max_batch, cfg.precision = max_batch, getattr(Precision, precision)
-    return DepthPro.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _image(B, S, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(B, 3, S, S, generator=g) - 0.45) / 0.225
-
-
-def _cloud_np(pc):
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in vars(pc).items()}
-
-
-def _same_cloud(a, b, what=""):
-    for k in ("count", "mask", "point_map", "normal_map"):
-        assert a[k] is not None and b[k] is not None and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
-    n = min(int(a["count"][-1]), a["xyz"].shape[0])
-    for k in ("xyz", "rgb", "conf", "normals"):
-        if a[k] is not None:
-            assert b[k] is not None and np.array_equal(a[k][:n].view(np.uint8), b[k][:n].view(np.uint8)), (what, k)
-
-
-def _da3_subset(m, x):
-    B, _, H, W = x.shape
-    f = lambda *s: torch.empty(s, dtype=torch.float32, device="cuda")  # noqa: E731
-    depth, conf, extr, intr = f(B, H, W), f(B, H, W), f(B, 1, 3, 4), f(B, 1, 3, 3)
-    o = _lib.MdDa3Outputs(depth.data_ptr(), conf.data_ptr(), None, None, None, extr.data_ptr(), intr.data_ptr())
-    _lib.check(_lib.load().md_da3_infer_ex(m._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, C.byref(o), _lib.MD_MEM_DEVICE,
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return depth, conf, extr, intr
 
 
 OPTS = dict(pixel_offset=0.5, stride=2, edge_rtol=0.5)
@@ -665,7 +588,7 @@ def _host_call(m, x, opts, min_cos, want_conf):
 @pytest.mark.parametrize("precision", ["F32", "BF16"])
 def test_infer_points_normals_da3_equals_infer_filter_unproject(dev, precision):
     from burn_depth_amd import ops
-    m = _da3(dev, precision)
+    m = _da3(dev, precision=precision)
     try:
         x = _image(2, 70).cuda()
         depth, conf, extr, intr = _da3_subset(m, x)
@@ -691,7 +614,7 @@ def test_infer_points_normals_da3_equals_infer_filter_unproject(dev, precision):
 @pytest.mark.gpu
 def test_infer_points_normals_depth_pro_equals_infer_then_unproject(dev):
     from burn_depth_amd import ops
-    m = _pro(dev, "BF16")
+    m = _pro(dev, "small", "BF16")
     fork = None
     try:
         x = _image(2, 512).cuda()
@@ -716,7 +639,7 @@ def test_infer_points_normals_depth_pro_equals_infer_then_unproject(dev):
 
 @pytest.mark.gpu
 def test_infer_points_normals_graph_replay_and_allocations(dev):
-    m = _da3(dev, "BF16")
+    m = _da3(dev, precision="BF16")
     try:
         x = _image(2, 70).cuda()
         kw = dict(conf_min=1.0, world=True, **OPTS, **NRM)
@@ -790,7 +713,7 @@ def test_normal_refusals_leave_the_outputs_untouched(dev):
         ops.unproject(dev, _t(d), intrinsics=_t(K), out=out, stride=0)
     assert e.value.code == _lib.MD_ERR_INVALID_ARG
     untouched(out, stores)
-    m = _da3(dev, "BF16", max_batch=1)
+    m = _da3(dev, precision="BF16", max_batch=1)
     try:
         for kw in (dict(normal_min_cos=2.0), dict(normal_min_cos=float("nan"))):
             out, stores = _fresh(1, 70, 70, 70 * 70, False, True)

@@ -1,6 +1,7 @@
 """Model -> thinned cloud in one call: `infer_points(voxel=...)` (md_infer_points_voxel) against `ops.voxel_thin`
 (md_op_voxel_thin) applied to the unthinned `infer_points()` of the same call. include/mi_depth.h states the contract,
 DESIGN 12.3 the kernels. Runs with `-m gpu` on an MI355X."""
+import ctypes as C
 import os
 import sys
 
@@ -14,42 +15,12 @@ if ROOT not in sys.path:
 
 from burn_depth_amd import _lib  # noqa: E402
 from burn_depth_amd import pipeline as P  # noqa: E402
+from points_util import _da3, _da3_subset, _image, _pro, dev  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 POISON = 123456.0
 OPTS = dict(pixel_offset=0.5, stride=2, edge_rtol=0.5)
 NRM = dict(normals=True, normal_min_cos=0.05)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from burn_depth_amd.depth_pro import Device
-    return Device(0)
-
-
-def _da3(dev, precision="BF16", max_batch=3):
-    """the reduced dual-head preset (70 x 70)"""
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthAnything3Config, Precision
-    from burn_depth_amd.depth_anything3 import DepthAnything3
-    cfg = DepthAnything3Config.tiny_dual_test()
-    cfg.max_batch, cfg.precision = max_batch, getattr(Precision, precision)
-    return DepthAnything3.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _pro(dev, precision="BF16", max_batch=2):
-    """Depth Pro at the small preset (128-pixel windows, a 512 x 512 input)"""
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthProConfig, Precision
-    from burn_depth_amd.depth_pro import DepthPro
-    cfg = DepthProConfig.small_test()
-    cfg.max_batch, cfg.precision = max_batch, getattr(Precision, precision)
-    return DepthPro.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _image(B, S, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(B, 3, S, S, generator=g) - 0.45) / 0.225
 
 
 def _np(pc):
@@ -109,7 +80,7 @@ def _poisoned(m, x, **kw):
 
 
 def test_da3_three_views_thinned_equals_thinning_the_unthinned_cloud(dev):
-    m = _da3(dev)
+    m = _da3(dev, max_batch=3)
     try:
         x = _image(3, 70).cuda()
         rgb = torch.randint(0, 256, (3, 70, 70, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1)).cuda()
@@ -146,7 +117,7 @@ def test_da3_three_views_thinned_equals_thinning_the_unthinned_cloud(dev):
 
 
 def test_depth_pro_thinned_equals_thinning_the_unthinned_cloud(dev):
-    m = _pro(dev)
+    m = _pro(dev, "small")
     try:
         x = _image(2, 512).cuda()
         kw = dict(**OPTS, **NRM)
@@ -168,7 +139,7 @@ def test_depth_pro_thinned_equals_thinning_the_unthinned_cloud(dev):
 
 
 def test_thinned_graph_replay_and_allocations(dev):
-    m = _da3(dev)
+    m = _da3(dev, max_batch=3)
     try:
         x = _image(3, 70).cuda()
         kw = dict(conf_min=1.0, world=True, **OPTS, **NRM)
@@ -203,4 +174,144 @@ def test_thinned_graph_replay_and_allocations(dev):
         assert m.query("allocs") == before == allocs
     finally:
         m.enable_graph(False)
+        m.destroy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the entries themselves, through ctypes: `infer_points` and `ops.unproject` only reach the widest ones
+# ---------------------------------------------------------------------------------------------------------------------------------
+FILL = dict(point_map=POISON, mask=77, xyz=POISON, rgb=77, conf=POISON, count=-7, depth=POISON, normal_map=POISON, normals=POISON, index=-7,
+            weight=-7, dropped=-7)
+LISTS = ("xyz", "rgb", "conf", "normals", "index", "weight")
+
+
+def _buffers(B, H, W, cap, host=False, normals=False, thinning=False, depth=True):
+    """Poisoned outputs of one call, numpy (host) or device tensors -> (dict, pointer of a name or None, md_points_outputs)"""
+    f, u8, i32 = np.float32, np.uint8, np.int32
+    shapes = dict(point_map=((B, H, W, 3), f), mask=((B, H, W), u8), xyz=((cap, 3), f), rgb=((cap, 3), u8), conf=((cap,), f), count=((B + 1,), i32))
+    if depth:
+        shapes.update(depth=((B, H, W), f))
+    if normals:
+        shapes.update(normal_map=((B, H, W, 3), f), normals=((cap, 3), f))
+    if thinning:
+        shapes.update(index=((cap,), i32), weight=((cap,), i32), dropped=((1,), i32))
+    t = {k: np.full(shape, FILL[k], dt) for k, (shape, dt) in shapes.items()}
+    if not host:
+        t = {k: torch.from_numpy(v).cuda() for k, v in t.items()}
+    ptr = lambda k: (t[k].ctypes.data if host else t[k].data_ptr()) if k in t else None  # noqa: E731
+    outs = _lib.MdPointsOutputs(ptr("point_map"), ptr("mask"), ptr("xyz"), ptr("rgb"), ptr("conf"), ptr("count"), cap, ptr("depth"))
+    return t, ptr, outs
+
+
+def _read(t):
+    torch.cuda.synchronize()
+    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in t.items()}
+
+
+def _same_bytes(a, b, what):
+    """every output of b is a's, byte for byte; of the list outputs, the rows that hold points -> their number"""
+    assert a.keys() == b.keys(), (what, sorted(a), sorted(b))
+    n = min(int(a["count"][-1]), a["xyz"].shape[0])
+    assert n > 0, what
+    for k in a:
+        rows = n if k in LISTS else None
+        assert np.array_equal(a[k][:rows].view(np.uint8), b[k][:rows].view(np.uint8)), (what, k)
+    return n
+
+
+def test_narrow_entries_are_the_widest_entry_with_nulls(dev):
+    """md_infer_points, _filtered and _normals against md_infer_points_voxel, md_op_unproject against md_op_unproject_normals: the
+    same request, with NULL and with all-zero structs for the parts the narrower entry lacks, gives the same bytes."""
+    from burn_depth_amd.depth_pro import _points_opts, _view_filter_opts
+    lib = _lib.load()
+    m = _da3(dev)
+    try:
+        B, S = 2, 70
+        cap = B * 35 * 35
+        x = _image(B, S).cuda()
+        rgb = torch.randint(0, 256, (B, S, S, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1)).cuda()
+        o = _points_opts(world=True, **OPTS)
+        fo = _view_filter_opts(o.pixel_offset, 0.0, 0.0, 30)  # the percentile alone: two views of seeded weights confirm no pixel of each other
+        DEV, st = _lib.MD_MEM_DEVICE, C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        head = (m._h, C.c_void_p(x.data_ptr()), B, S, S, DEV, C.c_void_p(rgb.data_ptr()), None)
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        zero_nrm, zero_vox = _lib.MdPointsNormals(None, None, 0.0), _lib.MdPointsVoxel(0.0, None, None, None)
+
+        def call(entry, filt, normals, zero=False):
+            t, ptr, outs = _buffers(B, S, S, cap, normals=normals)
+            nrm = _lib.MdPointsNormals(ptr("normal_map"), ptr("normals"), NRM["normal_min_cos"]) if normals else None
+            f = fo if filt else None
+            if entry == "points":
+                rc = lib.md_infer_points(*head, C.byref(o), C.byref(outs), DEV, st)
+            elif entry == "filtered":
+                rc = lib.md_infer_points_filtered(*head, ref(f), C.byref(o), C.byref(outs), DEV, st)
+            elif entry == "normals":
+                rc = lib.md_infer_points_normals(*head, ref(f), C.byref(o), C.byref(outs), ref(nrm or (zero_nrm if zero else None)), DEV, st)
+            else:
+                rc = lib.md_infer_points_voxel(*head, ref(f), C.byref(o), C.byref(outs), ref(nrm or (zero_nrm if zero else None)),
+                                               ref(zero_vox if zero else None), DEV, st)
+            _lib.check(rc)
+            return _read(t)
+
+        counts = {}
+        for zero in (False, True):
+            for entry, filt, normals in (("points", False, False), ("filtered", True, False), ("normals", False, False),
+                                         ("normals", False, True), ("normals", True, True)):
+                what = (entry, filt, normals, zero)
+                counts[what] = _same_bytes(call("voxel", filt, normals, zero), call(entry, filt, normals, zero), what)
+        # the filtered request is another request: the percentile removes points
+        assert counts[("filtered", True, False, False)] < counts[("points", False, False, False)] < cap
+        # the operators, on the model's own depth and cameras
+        depth, conf, extr, intr = _da3_subset(m, x)
+        cam = _lib.MdPointsCameras(intr.data_ptr(), extr.data_ptr(), None)
+
+        def op(entry, nrm=None):
+            t, _, outs = _buffers(B, S, S, cap, depth=False)
+            args = (dev.handle, depth.data_ptr(), conf.data_ptr(), rgb.data_ptr(), B, S, S, C.byref(cam), C.byref(o), C.byref(outs))
+            _lib.check(lib.md_op_unproject(*args, st) if entry == "plain" else lib.md_op_unproject_normals(*args, ref(nrm), st))
+            return _read(t)
+
+        plain = op("plain")
+        assert _same_bytes(op("normals"), plain, "op, null") == _same_bytes(op("normals", zero_nrm), plain, "op, zero") == counts[("points", False, False, False)]
+    finally:
+        m.destroy()
+
+
+def test_host_in_host_out_with_filter_normals_and_thinning(dev):
+    """md_infer_points_voxel with the image, rgb and every output in host memory, the view filter, the normals and the thinning all
+    on: each output is the device-memory call's, byte for byte, and nothing behind the surviving rows is written."""
+    from burn_depth_amd.depth_pro import _points_opts, _view_filter_opts
+    lib = _lib.load()
+    m = _da3(dev)
+    try:
+        B, S = 2, 70
+        cap = B * 35 * 35
+        x = _image(B, S)
+        rgb = torch.randint(0, 256, (B, S, S, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1))
+        fkw = dict(conf_percentile=30)  # the percentile alone: two views of seeded weights confirm no pixel of each other
+        full = _np(m.infer_points(x.cuda(), rgb=rgb.cuda(), world=True, **fkw, **OPTS, **NRM))
+        n_full = int(full["count"][-1])
+        voxel = _voxel_for(full["xyz"][:n_full], 0.5)
+        o = _points_opts(world=True, **OPTS)
+        fo = _view_filter_opts(o.pixel_offset, 0.0, 0.0, fkw["conf_percentile"])
+
+        def call(host):
+            t, ptr, outs = _buffers(B, S, S, cap, host=host, normals=True, thinning=True)
+            nrm = _lib.MdPointsNormals(ptr("normal_map"), ptr("normals"), NRM["normal_min_cos"])
+            vox = _lib.MdPointsVoxel(voxel, ptr("index"), ptr("weight"), ptr("dropped"))
+            xin, cin = (x.numpy(), rgb.numpy()) if host else (x.cuda(), rgb.cuda())
+            px, pc = (xin.ctypes.data, cin.ctypes.data) if host else (xin.data_ptr(), cin.data_ptr())
+            kind = _lib.MD_MEM_HOST if host else _lib.MD_MEM_DEVICE
+            _lib.check(lib.md_infer_points_voxel(m._h, C.c_void_p(px), B, S, S, kind, C.c_void_p(pc), None, C.byref(fo), C.byref(o),
+                                                 C.byref(outs), C.byref(nrm), C.byref(vox), kind,
+                                                 None if host else C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            return _read(t)
+
+        on_device, on_host = call(False), call(True)
+        n = _same_bytes(on_device, on_host, "host against device")
+        assert 0.25 * n_full < n < 0.75 * n_full  # about half survive
+        assert on_host["weight"][:n].sum() + int(on_host["dropped"][0]) == n_full
+        for k in LISTS:
+            assert (on_host[k][n:] == np.asarray(FILL[k], on_host[k].dtype)).all(), k
+    finally:
         m.destroy()

@@ -19,25 +19,11 @@ if ROOT not in sys.path:
 
 from burn_depth_amd import _lib  # noqa: E402
 from burn_depth_amd import pipeline as P  # noqa: E402
+from points_util import _bits, _cloud_np, _da3, _da3_subset, _image, _pro, _same_cloud, _t, dev, lib  # noqa: E402,F401
 
 f32 = np.float32
 NEW_ENTRIES = ("md_view_filter_opts_default", "md_op_filter_views", "md_infer_points_filtered")
 POISON = 123456.0
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from burn_depth_amd.depth_pro import Device
-    return Device(0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -291,8 +277,6 @@ def test_filter_argument_errors_without_a_gpu(lib):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # GPU: the operator
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _t(a):
-    return torch.from_numpy(np.array(a)).cuda() if a is not None else None  # a copy: the shared scenes are read-only
 
 
 def _poisoned(B, H, W):
@@ -433,52 +417,6 @@ def test_filter_refusals_leave_the_outputs_untouched(dev, lib):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # GPU: the model call
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _da3(dev, max_batch=3):
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthAnything3Config, Precision
-    from burn_depth_amd.depth_anything3 import DepthAnything3
-    cfg = DepthAnything3Config.tiny_dual_test()
-    cfg.max_batch, cfg.precision = max_batch, Precision.BF16
-    return DepthAnything3.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _pro(dev, max_batch=2):
-    from burn_depth_amd import weights as Wt
-    from burn_depth_amd.config import DepthProConfig, Precision
-    from burn_depth_amd.depth_pro import DepthPro
-    cfg = DepthProConfig.tiny_test()
-    cfg.max_batch, cfg.precision = max_batch, Precision.BF16
-    return DepthPro.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
-
-
-def _image(B, S, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(B, 3, S, S, generator=g) - 0.45) / 0.225
-
-
-def _cloud_np(pc):
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in vars(pc).items()}
-
-
-def _same_cloud(a, b, what=""):
-    for k in ("count", "mask", "point_map", "depth"):
-        if a[k] is not None and b.get(k) is not None:
-            assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
-    n = min(int(a["count"][-1]), a["xyz"].shape[0])
-    for k in ("xyz", "rgb", "conf"):
-        if a[k] is not None:
-            assert b[k] is not None and np.array_equal(a[k][:n].view(np.uint8), b[k][:n].view(np.uint8)), (what, k)
-
-
-def _da3_subset(m, x):
-    """md_da3_infer_ex with the outputs md_infer_points_filtered asks the model for: depth, confidence, extrinsics, intrinsics."""
-    B, _, H, W = x.shape
-    f = lambda *s: torch.empty(s, dtype=torch.float32, device="cuda")  # noqa: E731
-    depth, conf, extr, intr = f(B, H, W), f(B, H, W), f(B, 1, 3, 4), f(B, 1, 3, 3)
-    o = _lib.MdDa3Outputs(depth.data_ptr(), conf.data_ptr(), None, None, None, extr.data_ptr(), intr.data_ptr())
-    _lib.check(_lib.load().md_da3_infer_ex(m._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE, C.byref(o), _lib.MD_MEM_DEVICE,
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return depth, conf, extr, intr
 
 
 def _composition(dev, depth, conf, intr, extr, fkw, pkw, focal=None):
@@ -493,7 +431,7 @@ def _composition(dev, depth, conf, intr, extr, fkw, pkw, focal=None):
 
 @pytest.mark.gpu
 def test_infer_points_filtered_da3_equals_the_composition(dev):
-    m = _da3(dev)
+    m = _da3(dev, max_batch=3)
     try:
         x = _image(3, 70).cuda()
         depth, conf, extr, intr = _da3_subset(m, x)
@@ -542,7 +480,7 @@ def test_infer_points_filtered_da3_equals_the_composition(dev):
 
 @pytest.mark.gpu
 def test_infer_points_filtered_graph_replay_and_allocations(dev):
-    m = _da3(dev)
+    m = _da3(dev, max_batch=3)
     try:
         x = _image(3, 70).cuda()
         kw = dict(conf_percentile=40, view_rtol=0.5, min_views=1, pixel_offset=0.5, world=True)

@@ -18,25 +18,11 @@ if ROOT not in sys.path:
 
 from burn_depth_amd import _lib  # noqa: E402
 from burn_depth_amd import pipeline as P  # noqa: E402
+from points_util import _bits, _t, dev, lib  # noqa: E402,F401
 
 f32 = np.float32
 NEW_ENTRIES = ("md_op_voxel_thin", "md_infer_points_voxel")
 HALF = 1 << 20
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from burn_depth_amd.depth_pro import Device
-    return Device(0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
 
 
 def _dict_thin(xyz, voxel, conf=None):
@@ -203,10 +189,6 @@ def test_voxel_argument_errors_without_a_gpu(lib):
 POISON = 123456.0
 CANARY = 16  # elements behind the end of every output buffer
 FILLS = dict(xyz=POISON, conf=POISON, rgb=77, normals=POISON, index=-7, weight=-7, count=-5, dropped=-5)
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda() if a is not None else None
 
 
 def _fresh(cap, conf, rgb, normals):
