@@ -74,6 +74,21 @@ class MdPointsVoxel(C.Structure):
     _fields_ = [("voxel", C.c_float), ("index", C.c_void_p), ("weight", C.c_void_p), ("dropped", C.c_void_p)]
 
 
+class MdRenderOpts(C.Structure):
+    """md_render_opts (include/mi_depth.h)."""
+    _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
+
+
+class MdRenderOutputs(C.Structure):
+    """md_render_outputs (include/mi_depth.h)."""
+    _fields_ = [("depth", C.c_void_p), ("index", C.c_void_p), ("rgb", C.c_void_p), ("filled", C.c_void_p)]
+
+
+class MdPointsRender(C.Structure):
+    """md_points_render (include/mi_depth.h)."""
+    _fields_ = [("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cam", MdPointsCameras), ("opts", MdRenderOpts), ("out", MdRenderOutputs)]
+
+
 class MdViewFilterOpts(C.Structure):
     """md_view_filter_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_percentile", C.c_int),
@@ -181,6 +196,12 @@ SYMBOLS = {
     "md_infer_points_voxel": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
                                    C.POINTER(MdPointsVoxel), _I, _P]),
+    "md_render_opts_default": (None, [C.POINTER(MdRenderOpts)]),
+    "md_op_render_points": (_I, [_P, _P, _P, C.c_int64, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdRenderOpts),
+                                 C.POINTER(MdRenderOutputs), _P]),
+    "md_infer_points_render": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                    C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

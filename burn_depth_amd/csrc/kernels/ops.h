@@ -120,6 +120,30 @@ size_t voxel_scratch_bytes(int n);
 int launch_voxel_thin(const VoxelParams& p, void* scratch, hipStream_t s);
 const int32_t* voxel_flags(const void* scratch, int n);
 
+// ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
+// A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour
+// image: clear, splat (atomicMin of (bits(p.z) << 32) | row over the footprint), resolve. Every pointer is a device pointer.
+// Selection only: nothing depends on the order of arrival.
+struct RenderParams {
+  const float* xyz = nullptr;
+  const uint8_t* rgb = nullptr;       // gathered to rgb_out
+  const int32_t* count = nullptr;     // one word, read on the device: the live rows are min(max(*count, 0), n); null: n rows
+  int n = 0;                          // rows the splat launch covers
+  int T = 0, H = 0, W = 0;            // targets and their size
+  const float *K = nullptr, *E = nullptr, *focal = nullptr;  // [T,3,3] or [T]; [T,3,4] world-to-camera, null: p = X
+  float off = 0.f, znear = 0.f, zfar = 0.f;                  // znear / zfar already resolved
+  int radius = 0;
+  float* depth = nullptr;      // [T,H,W]
+  int32_t* index = nullptr;    // [T,H,W]
+  uint8_t* rgb_out = nullptr;  // [T,H,W,3]
+  int32_t* filled = nullptr;   // [T + 1]
+};
+constexpr int kRenderMaxRadius = 16;
+// bytes of the key buffer: 8 per pixel, 256-byte aligned
+size_t render_scratch_bytes(int T, int H, int W);
+// three launches on s (the splat is skipped when n == 0)
+int launch_render_points(const RenderParams& p, void* scratch, hipStream_t s);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

@@ -506,6 +506,24 @@ int md_infer_points_voxel(md_model_t m, const float* nchw, int B, int H, int W, 
   return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false}, (hipStream_t)stream);
 }
 
+void md_render_opts_default(md_render_opts* o) {
+  if (!o) return;
+  o->pixel_offset = 0.f;
+  o->z_near = o->z_far = 0.f;
+  o->radius = 0;
+}
+
+int md_op_render_points(md_device_t dev, const float* xyz_dev, const uint8_t* rgb_dev, int64_t N, const int32_t* count_dev, int T, int H,
+                        int W, const md_points_cameras* cam, const md_render_opts* opts, const md_render_outputs* out, void* stream) {
+  return op_render_points(dev, PointList{xyz_dev, nullptr, rgb_dev, nullptr, N}, count_dev, T, H, W, cam, opts, out, (hipStream_t)stream);
+}
+
+int md_infer_points_render(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                           const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, int out_kind, void* stream) {
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd}, (hipStream_t)stream);
+}
+
 int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {
   if (!left || !count) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (in_len <= 0 || out_len <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid pass %d -> %d", in_len, out_len);

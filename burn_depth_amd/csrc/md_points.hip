@@ -6,7 +6,9 @@
 // support) in front of those launches: it hands them a depth in which rejected pixels are 0.
 // md_op_voxel_thin / md_infer_points_voxel put the voxel thinning (kernels/voxel.hip) behind them: the scatter then fills a list
 // of the model's own, and the thinned list goes to the caller.
-// The four md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
+// md_op_render_points / md_infer_points_render put the rendering (kernels/render.hip) behind those: the list the call ends with,
+// thinned or not, is z-buffered into the caller's target cameras.
+// The five md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -29,6 +31,8 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> out;          // device homes of host outputs
   md::GrowBuf<void> vlist;        // md_infer_points_voxel: the unthinned list (xyz | conf | rgb | normals | count)
   md::GrowBuf<void> vtable;       // its hash table and compaction scratch (voxel_scratch_bytes)
+  md::GrowBuf<void> rkeys;        // md_infer_points_render: the z-buffer keys (render_scratch_bytes)
+  md::GrowBuf<float> rcams;       // the device copy of host target cameras: K [T,9] | E [T,12] | focal [T]
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
@@ -160,6 +164,31 @@ int check_voxel(const md_points_voxel* vox, const md_points_outputs* out, bool o
   return MD_OK;
 }
 
+// the rendering part of the operator and of the model call; has_rgb: there is an rgb row to gather from
+int check_render(int T, int H, int W, const md_points_cameras* cam, const md_render_opts* o, const md_render_outputs* out, bool has_rgb) {
+  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "render options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "render outputs are null");
+  if (!cam) MD_FAIL(MD_ERR_INVALID_ARG, "target cameras are null");
+  if (!out->depth && !out->index && !out->rgb && !out->filled) MD_FAIL(MD_ERR_INVALID_ARG, "every render output is null");
+  if (out->rgb && !has_rgb) MD_FAIL(MD_ERR_INVALID_ARG, "a rendered rgb output needs an rgb row");
+  if (!cam->intrinsics && !cam->focal_px) MD_FAIL(MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras");
+  if (o->radius < 0 || o->radius > kRenderMaxRadius) MD_FAIL(MD_ERR_INVALID_ARG, "radius %d outside 0..%d", o->radius, kRenderMaxRadius);
+  MD_TRY(check_offset(o->pixel_offset));
+  MD_TRY(check_nonneg("z_near", o->z_near));
+  MD_TRY(check_nonneg("z_far", o->z_far));
+  if (o->z_near > 0.f && o->z_far > 0.f && o->z_far < o->z_near) MD_FAIL(MD_ERR_INVALID_ARG, "z_far %g < z_near %g", (double)o->z_far, (double)o->z_near);
+  if (T <= 0 || H <= 0 || W <= 0 || (long)T * H * W >= (1l << 31) || H >= (1 << 24) || W >= (1 << 24))
+    MD_FAIL(MD_ERR_SHAPE, "invalid render target shape [%d,%d,%d]", T, H, W);
+  return MD_OK;
+}
+
+RenderParams make_render(int T, int H, int W, const md_render_opts& o) {
+  RenderParams r;
+  r.T = T; r.H = H; r.W = W;
+  r.off = o.pixel_offset; r.znear = depth_min_of(o.z_near); r.zfar = depth_max_of(o.z_far); r.radius = o.radius;
+  return r;
+}
+
 uint32_t fbits(float v) {
   uint32_t u;
   memcpy(&u, &v, 4);
@@ -275,6 +304,23 @@ int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* v
   return MD_OK;
 }
 
+int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
+                     const md_render_opts* o, const md_render_outputs* out, hipStream_t stream) {
+  MD_TRY(check_render(T, H, W, cam, o, out, in.rgb != nullptr));
+  if (in.N < 0 || in.N >= (1ll << 31)) MD_FAIL(MD_ERR_SHAPE, "rendering takes 0 .. 2^31 - 1 rows, got %lld", (long long)in.N);
+  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  RenderParams r = make_render(T, H, W, *o);
+  r.xyz = in.xyz; r.rgb = in.rgb; r.count = count; r.n = (int)in.N;
+  r.K = cam->intrinsics; r.focal = cam->intrinsics ? nullptr : cam->focal_px; r.E = cam->extrinsics;
+  r.depth = out->depth; r.index = out->index; r.rgb_out = out->rgb; r.filled = out->filled;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(render_scratch_bytes(T, H, W)));
+  return scratch.finish(launch_render_points(r, scratch.p, st));
+}
+
 int points_voxel_overflow(md_model_t m, int64_t* out) {
   *out = 0;
   md_model_s::PointsState* f = m->points;
@@ -309,6 +355,7 @@ struct PointsPlan {
   PointsParams p;   // launch_unproject's; the device inputs gather in p.rgb / K / E / focal (all kept until run_unproject)
   NormalsParams q;
   VoxelParams v;    // thin: launch_voxel_thin's, from the model's own list that `p` then fills to the list outputs of the call
+  RenderParams r;   // c.rnd given: launch_render_points', from the list outputs of the call
   std::vector<OutSlot> slots;
 };
 
@@ -350,6 +397,14 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   slot(c.nrm ? c.nrm->normals : no_f, thin ? v.normals_out : q.normals, 12, cap, true);
   slot(thin ? c.vox->index : no_i, v.index, 4, cap, true);
   slot(thin ? c.vox->weight : no_i, v.weight, 4, cap, true);
+  if (c.rnd) {  // rendered images are dense outputs: they travel whole
+    RenderParams& r = pl.r;
+    const size_t rpx = (size_t)r.T * r.H * r.W;
+    slot(c.rnd->out.depth, r.depth, 4, rpx, false);
+    slot(c.rnd->out.index, r.index, 4, rpx, false);
+    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, false);
+    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, false);
+  }
   return total;
 }
 
@@ -380,6 +435,11 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   p.capacity = out.capacity;
   pl.q = make_normals(c.nrm);
   pl.thin = voxel_on(c.vox) && out.count;  // without the list there is nothing to thin
+  if (c.rnd) {
+    pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
+    MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
+    if (c.in_kind == MD_MEM_HOST) MD_TRY(grow(m, st, f->rcams, (size_t)c.rnd->T * 22 * 4));
+  }
   if (const size_t total = place_outputs(c, pl, nullptr)) {
     MD_TRY(grow(m, st, f->out, total));
     place_outputs(c, pl, (char*)f->out.p);
@@ -409,6 +469,10 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   PointsParams& p = pl.p;
   pl.x = c.nchw;
   p.rgb = c.rgb; p.K = c.cam->intrinsics; p.E = c.cam->extrinsics; p.focal = c.cam->focal_px;
+  if (c.rnd) {
+    const md_points_cameras& t = c.rnd->cam;
+    pl.r.K = t.intrinsics; pl.r.focal = t.intrinsics ? nullptr : t.focal_px; pl.r.E = t.extrinsics;
+  }
   if (c.in_kind != MD_MEM_HOST) return MD_OK;
   MD_TRY(grow(m, pl.st, f->x, pl.npx * 3 * 4));
   if (c.rgb) MD_TRY(grow(m, pl.st, f->rgb, pl.npx * 3));
@@ -422,7 +486,14 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(h2d(p.rgb, f->rgb.p, pl.npx * 3));
   MD_TRY(h2d(p.K, f->k_home(), (size_t)c.B * 36));
   MD_TRY(h2d(p.E, f->e_home(c.B), (size_t)c.B * 48));
-  return h2d(p.focal, f->f_home(c.B), (size_t)c.B * 4);
+  MD_TRY(h2d(p.focal, f->f_home(c.B), (size_t)c.B * 4));
+  if (c.rnd) {
+    const size_t T = (size_t)c.rnd->T;
+    MD_TRY(h2d(pl.r.K, f->rcams.p, T * 36));
+    MD_TRY(h2d(pl.r.E, f->rcams.p + T * 9, T * 48));
+    MD_TRY(h2d(pl.r.focal, f->rcams.p + T * 21, T * 4));
+  }
+  return MD_OK;
 }
 
 // The model: its cameras land in the homes of those the caller did not give.
@@ -468,6 +539,18 @@ int run_thin(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   return MD_OK;
 }
 
+// Rendering: the list outputs of the call, thinned or not, and their device count -> the target images.
+int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
+  RenderParams& r = pl.r;
+  const PointsParams& p = pl.p;
+  const VoxelParams& v = pl.v;
+  r.xyz = pl.thin ? v.xyz_out : p.xyz;
+  r.rgb = pl.thin ? v.rgb_out : p.rgb_out;
+  r.count = (pl.thin ? v.count : p.count) + c.B;
+  r.n = (int)std::min<long>((long)c.out->capacity, list_rows(c.B, c.H, c.W, c.o->stride));
+  return launch_render_points(r, m->points->rkeys.p, pl.st);
+}
+
 // Host outputs, complete when the call returns: the depth, the dense maps and the counts first, then, once `count` is known,
 // only the list rows that hold points: the caller's memory beyond them stays as it was.
 int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
@@ -508,6 +591,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (c.fo) MD_TRY(timed("points_view_filter", run_filter));
   MD_TRY(timed("points_unproject", run_unproject));
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
+  if (c.rnd) MD_TRY(timed("points_render", run_render));
   return copy_outputs(m, c, pl);
 }
 
@@ -538,6 +622,10 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   MD_TRY(check_voxel(c.vox, out, false));
   if (voxel_on(c.vox) && list_rows(B, H, W, o->stride) >= (1l << 30))
     MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
+  if (c.rnd) {
+    MD_TRY(check_render(c.rnd->T, c.rnd->H, c.rnd->W, &c.rnd->cam, &c.rnd->opts, &c.rnd->out, out->rgb != nullptr));
+    if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rendering needs the list outputs `xyz` and `count`");
+  }
   if (c.fo) {
     MD_TRY(check_filter(c.fo, s, B, H, W));
     if (fbits(c.fo->pixel_offset) != fbits(o->pixel_offset) || depth_min_of(c.fo->depth_min) != depth_min_of(o->depth_min) ||
@@ -573,6 +661,11 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     key_add(key, 0x4e524d4cu, c.nrm->normal_map, c.nrm->normals, c.nrm->min_cos);
   if (voxel_on(c.vox))  // voxel == 0: the key, and the graph, of the call without thinning
     key_add(key, 0x564f584cu, c.vox->voxel, c.vox->index, c.vox->weight, c.vox->dropped);
+  if (c.rnd) {
+    const md_points_render& r = *c.rnd;
+    key_add(key, 0x524e4452u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px);
+    key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.radius, r.out.depth, r.out.index, r.out.rgb, r.out.filled);
+  }
   return run_with_graph(m, st, key, eligible, body);
 }
 

@@ -78,6 +78,16 @@ class FrameResult:
 
 
 @dataclass
+class RenderedPoints:
+    """What `md_op_render_points` / `md_infer_points_render` return (include/mi_depth.h). Device tensors: depth f32 [T,H,W] (0 at
+    holes), index int32 [T,H,W] (the winner's row, -1 at holes), rgb u8 [T,H,W,3] (with an rgb row), filled int32 [T+1]."""
+    depth: Optional[torch.Tensor] = None
+    index: Optional[torch.Tensor] = None
+    rgb: Optional[torch.Tensor] = None
+    filled: Optional[torch.Tensor] = None
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -85,7 +95,8 @@ class PointCloud:
     With normals (`md_op_unproject_normals` / `md_infer_points_normals`): normal_map [B,H,W,3] and normals [capacity,3], rows
     parallel to xyz. With voxel thinning (`md_op_voxel_thin` / `md_infer_points_voxel`): the list holds one row per occupied
     voxel, index int32 [capacity] is the source row of every output row in the unthinned list, weight int32 [capacity] the
-    points of its voxel, dropped int32 [1] the rows outside the grid."""
+    points of its voxel, dropped int32 [1] the rows outside the grid. With `infer_points(render=...)`
+    (`md_infer_points_render`): render = the `RenderedPoints` of the list."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -98,6 +109,7 @@ class PointCloud:
     index: Optional[torch.Tensor] = None
     weight: Optional[torch.Tensor] = None
     dropped: Optional[torch.Tensor] = None
+    render: Optional["RenderedPoints"] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -165,6 +177,24 @@ def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
     return _lib.MdPointsVoxel(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped))
 
 
+def _render_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
+                    radius=0, want_rgb=False, out: Optional[RenderedPoints] = None):
+    """The target cameras, options and outputs of a rendering -> (T, cameras, md_render_opts, RenderedPoints, md_render_outputs,
+    keep-alive). T is the number of cameras given; fresh output tensors are allocated unless `out` is given."""
+    src = intrinsics if intrinsics is not None else focal_px
+    if src is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras")
+    n = src.numel() if isinstance(src, torch.Tensor) else int(np.asarray(src).size)
+    T = max(n // 9 if intrinsics is not None else n, 1)
+    cam, keep = _points_cameras(dev, T, intrinsics, extrinsics, focal_px)
+    if out is None:
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        out = RenderedPoints(f(T, H, W), f(T, H, W, dt=torch.int32), f(T, H, W, 3, dt=torch.uint8) if want_rgb else None,
+                             f(T + 1, dt=torch.int32))
+    o = _lib.MdRenderOpts(float(pixel_offset), float(z_near), float(z_far), int(radius))
+    return T, cam, o, out, _lib.MdRenderOutputs(_ptr(out.depth), _ptr(out.index), _ptr(out.rgb), _ptr(out.filled)), keep
+
+
 def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
     """md_points_cameras of device fp32 tensors ([B,3,3] / [B,1,3,3], [B,3,4] / [B,1,3,4], [B] or a float). Returns (struct, keep-alive)."""
     keep = []
@@ -188,10 +218,12 @@ def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None
 def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrinsics, focal_px, want_rgb: bool, want_conf: bool,
                     want_depth: bool, dense: bool, compact: bool, capacity: Optional[int], out: Optional[PointCloud], normals: bool,
                     normal_min_cos: float, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
-                    voxel: Optional[float] = None):
+                    voxel: Optional[float] = None, render: Optional[dict] = None):
     """The keyword set of `infer_points` / `ops.unproject` as the structs of the widest entry -> (cloud, opts, outs, cam, fo, nrm,
-    vox, keep-alive). fo, nrm and vox are None for the parts not asked for (an `out` that carries normal or thinning tensors asks
-    for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless `out` is given. Positional
+    vox, rnd, keep-alive). fo, nrm, vox and rnd are None for the parts not asked for (an `out` that carries normal or thinning
+    tensors asks for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless `out` is given.
+    render: the keywords of `_render_request` (H, W, the target cameras, pixel_offset, z_near, z_far, radius); the images go to
+    fresh tensors, or to the `render` that `out` carries. Positional
     arguments and a plain tuple back: this sits on the host path of every call. opts: the fields of `md_points_opts`; want_rgb /
     want_conf / want_depth: the call can fill those outputs."""
     o = _points_opts(**opts)
@@ -204,7 +236,12 @@ def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrins
         nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
     if voxel is not None and (voxel or res.index is not None or res.weight is not None or res.dropped is not None):
         vox = _points_voxel(dev, voxel, res, out is None)
-    return res, o, outs, cam, fo, nrm, vox, keep
+    rnd = None
+    if render is not None:
+        T, tcam, ro, res.render, routs, tkeep = _render_request(dev, **render, want_rgb=res.rgb is not None, out=res.render)
+        rnd = _lib.MdPointsRender(T, int(render["H"]), int(render["W"]), tcam, ro, routs)
+        keep = keep + tkeep
+    return res, o, outs, cam, fo, nrm, vox, rnd, keep
 
 
 @dataclass
@@ -589,13 +626,13 @@ class DepthPro:
     def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
-                     normal_min_cos: float = 0.0, voxel: float = 0.0, **opts) -> PointCloud:
+                     normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        Every form runs through the widest entry, `md_infer_points_voxel`, with NULL for the parts not asked for, which is
-        `md_infer_points` / `_filtered` / `_normals` on the same arguments:
+        Every form runs through the widest entry, `md_infer_points_render`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` / `_voxel` on the same arguments:
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
         conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
         before the unprojection; `depth` is then the filtered depth.
@@ -603,7 +640,10 @@ class DepthPro:
         normal_min_cos > 0, drops the pixels seen at a grazing angle; it composes with the view filter.
         voxel > 0 (`md_points_voxel`): thins the list to one point per occupied voxel of that side (the most confident one, ties to
         the first) and returns `index`, `weight` and `dropped` beside it; the B views share one grid. It composes with the view
-        filter and the normals."""
+        filter and the normals.
+        render (`md_points_render`): a dict with H, W, the target cameras (intrinsics [T,3,3] or focal_px [T]; extrinsics [T,3,4]
+        world-to-camera or None) and optionally pixel_offset, z_near, z_far, radius: the list the call ends with is z-buffered into
+        those cameras in the same call; the images come back as `render` (`RenderedPoints`). Needs compact=True."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -612,14 +652,14 @@ class DepthPro:
         if rgb is not None:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
         has_conf = bool(getattr(self.config, "dual_head", False))
-        res, o, outs, cam, fo, nrm, vox, keep = _points_request(
+        res, o, outs, cam, fo, nrm, vox, rnd, keep = _points_request(
             dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
-            normal_min_cos, conf_percentile, view_rtol, min_views, voxel)
+            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        _lib.check(self._lib.md_infer_points_voxel(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                   C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                   C.byref(o), C.byref(outs), ref(nrm), ref(vox), _lib.MD_MEM_DEVICE,
-                                                   _stream_ptr(self.device.ordinal)))
+        _lib.check(self._lib.md_infer_points_render(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                    C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), _lib.MD_MEM_DEVICE,
+                                                    _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import Device, PointCloud, _points_cameras, _points_request, _stream_ptr, _view_filter_opts
+from .depth_pro import Device, PointCloud, RenderedPoints, _points_cameras, _points_request, _render_request, _stream_ptr, _view_filter_opts
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -444,7 +444,7 @@ def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None
     conf = _f32c(conf) if conf is not None else None
     rgb = rgb.contiguous() if rgb is not None else None
     assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
-    res, o, outs, cam, _, nrm, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
+    res, o, outs, cam, _, nrm, _, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
                                                          conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos)
     _lib.check(_lib.load().md_op_unproject_normals(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
                                                    C.byref(nrm) if nrm is not None else None, _stream_ptr(dev.ordinal)))
@@ -498,6 +498,30 @@ def voxel_thin(dev: Device, xyz: torch.Tensor, voxel: float, conf: Optional[torc
     vox = _lib.MdPointsVoxel(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped))
     _lib.check(_lib.load().md_op_voxel_thin(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(vox), C.byref(outs),
                                             _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def render_points(dev: Device, xyz: torch.Tensor, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None,
+                  rgb: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, *, pixel_offset: float = 0.0, z_near: float = 0.0,
+                  z_far: float = 0.0, radius: int = 0, out: Optional[RenderedPoints] = None) -> RenderedPoints:
+    """md_op_render_points: a point list xyz [N,3] (+ u8 rgb [N,3]) z-buffered into T target cameras (intrinsics [T,3,3] or focal_px
+    [T]; extrinsics [T,3,4] world-to-camera, None = the points are in the camera's frame) -> `RenderedPoints` of H x W images.
+    count: a device int32 tensor whose first word is the number of rows to render (what `unproject` / `voxel_thin` left in
+    `count[-1:]`), read on the device. `out`: a RenderedPoints to write into again; a None field skips that output. Bit-identical
+    to `pipeline.render_points`."""
+    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    xyz = _f32c(xyz)
+    N = int(xyz.shape[0])
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if rgb is not None and N == 0:  # an empty tensor has no address: one row that is never read stands for the rgb input
+        rgb = torch.zeros((1, 3), dtype=torch.uint8, device=xyz.device)
+    assert count is None or (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() >= 1)
+    T, cam, o, out, outs, keep = _render_request(xyz.device, int(H), int(W), intrinsics, extrinsics, focal_px, pixel_offset=pixel_offset,
+                                                 z_near=z_near, z_far=z_far, radius=radius, want_rgb=rgb is not None, out=out)
+    _lib.check(_lib.load().md_op_render_points(dev.handle, _p(xyz), _p(rgb), N, _p(count), T, int(H), int(W), C.byref(cam), C.byref(o),
+                                               C.byref(outs), _stream_ptr(dev.ordinal)))
+    del keep
     return out
 
 

@@ -14,6 +14,8 @@
   device kernels of `md_op_unproject` / `md_infer_points` are bit-identical to, and a binary little-endian PLY writer / reader
 * `filter_views`                              -- the host reference of `md_op_filter_views` / `md_infer_points_filtered`: the exact
   confidence percentile and the cross-view support test in front of the point path
+* `render_points`                             -- the host reference of `md_op_render_points` / `md_infer_points_render`: the cloud
+  z-buffered into target cameras on 64-bit keys
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
   stands in (8-bit grayscale, filter 0), `read_gray_png` reads it back for the tests.
 JPEG decoding stays out of scope: images come in as uint8 arrays."""
@@ -545,6 +547,81 @@ def voxel_thin(xyz, voxel, conf=None, rgb=None, normals=None, counts=None) -> Ho
                       weight, count, int(N - ok.sum()))
 
 
+@dataclass
+class HostRender:
+    depth: np.ndarray                # f32 [T,H,W]: the winner's p.z, 0 at holes
+    index: np.ndarray                # int32 [T,H,W]: the winner's row, -1 at holes
+    rgb: Optional[np.ndarray]        # uint8 [T,H,W,3]: the winner's colour, 0 at holes
+    filled: np.ndarray               # int32 [T+1]: filled pixels per target, then their total
+
+
+def render_points(xyz, H, W, intrinsics=None, extrinsics=None, focal_px=None, rgb=None, count=None, *, pixel_offset=0.0, z_near=0.0,
+                  z_far=0.0, radius=0) -> HostRender:
+    """The host reference of md_op_render_points / md_infer_points_render (include/mi_depth.h states the contract): the list xyz
+    [N,3] (its first min(max(count, 0), N) rows) projected into T target cameras (intrinsics [T,3,3] or focal_px [T]; extrinsics
+    [T,3,4] world-to-camera, None = the points are in the camera's frame) and z-buffered over the (2 radius + 1)^2 footprint:
+    a pixel keeps the smallest key (bits(p.z) << 32) | row. f32, one rounded operation per step: the device kernels
+    (kernels/render.hip) give the same bits."""
+    T32 = np.float32
+    p = np.ascontiguousarray(xyz, dtype=T32).reshape(-1, 3)
+    N = len(p)
+    H, W, radius = int(H), int(W), int(radius)
+    if intrinsics is not None:
+        K = np.asarray(intrinsics, dtype=T32).reshape(-1, 3, 3)
+        fx, fy, cx, cy = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    elif focal_px is not None:
+        fx = fy = np.asarray(focal_px, dtype=T32).reshape(-1)
+        cx, cy = np.full(len(fx), T32(W) / T32(2), T32), np.full(len(fx), T32(H) / T32(2), T32)
+    else:
+        raise ValueError("neither intrinsics nor a focal length")
+    T = len(fx)
+    E = None if extrinsics is None else np.asarray(extrinsics, dtype=T32).reshape(T, 3, 4)
+    if T <= 0 or H <= 0 or W <= 0 or T * H * W >= 1 << 31 or H >= 1 << 24 or W >= 1 << 24 or N >= 1 << 31:
+        raise ValueError("invalid shape")
+    if not 0 <= radius <= 16:
+        raise ValueError("radius outside 0..16")
+    if not all(np.isfinite(v) for v in (pixel_offset, z_near, z_far)) or z_near < 0 or z_far < 0 or (z_near > 0 and 0 < z_far < z_near):
+        raise ValueError("pixel_offset and the bounds must be finite, the bounds >= 0 and z_far >= z_near")
+    f32i = np.finfo(np.float32)
+    zn = T32(z_near) if z_near > 0 else T32(f32i.tiny)
+    zf = T32(z_far) if z_far > 0 else T32(f32i.max)
+    n = N if count is None else min(max(int(count), 0), N)
+    x, y, z = p[:n, 0], p[:n, 1], p[:n, 2]
+    row = np.arange(n, dtype=np.uint64)
+    off, half = T32(pixel_offset), T32(0.5)
+    empty = np.uint64(0xFFFFFFFFFFFFFFFF)
+    keys = np.full((T, H * W), empty, np.uint64)
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(p[:n]).all(1)
+        for j in range(T):
+            if E is None:
+                px, py, pz = x, y, z
+            else:
+                px, py, pz = [((E[j, a, 0] * x + E[j, a, 1] * y) + E[j, a, 2] * z) + E[j, a, 3] for a in range(3)]
+            uf = ((fx[j] * (px / pz)) + cx[j]) - off
+            vf = ((fy[j] * (py / pz)) + cy[j]) - off
+            uu, vv = np.floor(uf + half), np.floor(vf + half)
+            seen = fin & np.isfinite(pz) & (pz >= zn) & (pz <= zf) & (uu >= 0) & (uu < T32(W)) & (vv >= 0) & (vv < T32(H))
+            ui, vi = uu[seen].astype(np.int64), vv[seen].astype(np.int64)
+            key = (np.ascontiguousarray(pz[seen], dtype=T32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | row[seen]
+            for dv in range(-radius, radius + 1):
+                for du in range(-radius, radius + 1):
+                    vy, ux = vi + dv, ui + du
+                    ok = (vy >= 0) & (vy < H) & (ux >= 0) & (ux < W)
+                    np.minimum.at(keys[j], vy[ok] * W + ux[ok], key[ok])
+    keys = keys.reshape(T, H, W)
+    hit = keys != empty
+    depth = np.where(hit, (keys >> np.uint64(32)).astype(np.uint32).view(T32), T32(0)).astype(T32)
+    index = np.where(hit, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+    color = None
+    if rgb is not None:
+        c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(N, 3)
+        color = np.zeros((T, H, W, 3), np.uint8)
+        color[hit] = c[index[hit]]
+    filled = np.concatenate([hit.reshape(T, -1).sum(1), [hit.sum()]]).astype(np.int32)
+    return HostRender(depth, index, color, filled)
+
+
 def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None) -> None:
     """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
@@ -651,8 +728,8 @@ class AnyDepthModel:
     def infer_points(self, x, **kw):
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
-        filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`) and voxel= (`md_infer_points_voxel`)
-        included."""
+        filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
+        and render= (`md_infer_points_render`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

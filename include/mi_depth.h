@@ -470,6 +470,65 @@ int md_infer_points_voxel(md_model_t m, const float* nchw, int B, int H, int W, 
                           const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                           const md_points_voxel* vox, int out_kind, void* stream);
 
+/* ---- point path: render a point list into target cameras -------------------------------------------------------------------
+ * The inverse direction: a list xyz f32 [N,3] with an optional parallel row rgb u8 [N,3] -> for each of T target cameras
+ * (md_points_cameras with T in place of B: intrinsics [T,3,3] or focal_px [T], K = (f, f, W/2, H/2); extrinsics [T,3,4]
+ * world-to-camera, NULL = the points are already in the camera's frame) a z-buffered H x W image. Selection, not blending: a
+ * pixel shows one input row, and nothing depends on the order in which threads arrive. f32, one rounded operation per step,
+ * no fused multiply-add (pipeline.render_points restates it in numpy bit for bit):
+ *   rows: n = min(max(*count, 0), N) with a device count word (int32), n = N without: the list md_op_unproject or
+ *     md_op_voxel_thin wrote is rendered without a host read. Point i < n is skipped when a coordinate is not finite.
+ *   projection into target j, the view filter's: p = R_j X + t_j, each coordinate ((Rk0 x + Rk1 y) + Rk2 z) + tk (extrinsics
+ *     NULL: p = X). The target sees the point when p.z is finite and z_near <= p.z <= z_far (0 = the default of that bound,
+ *     resolved as md_points_opts resolves depth_min / depth_max, so p.z > 0) and, with uf = ((fx (p.x / p.z)) + cx) - off,
+ *     uu = floorf(uf + 0.5f) (vf, vv likewise), 0 <= uu < W and 0 <= vv < H compared in float before any conversion: a NaN
+ *     or an infinity from the division is never in the image.
+ *   footprint: the (2 radius + 1)^2 pixel square around (vv, uu), clipped to the image. For each of its pixels the candidate
+ *     key is ((uint64)bits(p.z) << 32) | (uint32)i, and the pixel keeps the minimum key: the nearest p.z (for p.z > 0 the bit
+ *     order is the value order), among equal p.z the smallest row. An empty pixel's key is all ones, which no candidate equals.
+ *   outputs: depth = the winner's p.z, 0 at holes; index = the winner's row, -1 at holes; rgb = the winner's rgb row, 0 at
+ *     holes; filled[j] = the pixels of target j that are no holes, filled[T] = their total (integer adds).
+ * The keys take 8 bytes per pixel of device memory; they are cleared on the stream inside every call. */
+typedef struct md_render_opts {
+  float pixel_offset;  /* as md_points_opts */
+  float z_near, z_far; /* bounds of p.z; 0 = the default of that bound (smallest positive normal f32 / FLT_MAX) */
+  int radius;          /* 0..16: the footprint is the (2 radius + 1)^2 pixel square around the hit pixel */
+} md_render_opts;
+typedef struct md_render_outputs {
+  float* depth;    /* f32 [T,H,W]; NULL = skip */
+  int32_t* index;  /* int32 [T,H,W]; NULL = skip */
+  uint8_t* rgb;    /* u8 [T,H,W,3]; needs the rgb row. NULL = skip */
+  int32_t* filled; /* int32 [T+1]; NULL = skip */
+} md_render_outputs;
+typedef struct md_points_render { /* the rendering part of md_infer_points_render */
+  int T, H, W;                    /* target cameras and their image size */
+  md_points_cameras cam;          /* [T, ..] pointers of in_kind */
+  md_render_opts opts;
+  md_render_outputs out;          /* pointers of out_kind; rgb needs the list output out->rgb */
+} md_points_render;
+
+/* everything 0: integer grid, default bounds, one pixel per point */
+void md_render_opts_default(md_render_opts* o);
+/* The stand-alone operator on caller device tensors (cameras included); rgb_dev and count_dev may be NULL. Everything is
+ * enqueued on `stream`; the call returns after the stream has drained, because its key buffer is freed on return. N = 0 is
+ * legal: every pixel is a hole. Errors, before any launch: dev / opts / out / cam NULL, every output NULL, an rgb output
+ * without rgb_dev, xyz_dev NULL with N > 0, neither intrinsics nor focal_px, radius < 0 or > 16, pixel_offset or a bound not
+ * finite, a bound negative, z_far < z_near (both given) -> MD_ERR_INVALID_ARG; N < 0, N >= 2^31, T, H, W <= 0,
+ * T*H*W >= 2^31, H or W >= 2^24 -> MD_ERR_SHAPE. */
+int md_op_render_points(md_device_t dev, const float* xyz_dev, const uint8_t* rgb_dev, int64_t N, const int32_t* count_dev, int T,
+                        int H, int W, const md_points_cameras* cam, const md_render_opts* opts, const md_render_outputs* out,
+                        void* stream);
+/* md_infer_points_voxel with the rendering behind it: the list the call ends with (thinned or not; its first
+ * min(count[B], capacity) rows, read from the device count) is rendered into rnd's targets in the same call and graph. The
+ * keys and, for host cameras, their device copies live in grow-only buffers of the model. rnd NULL: md_infer_points_voxel on
+ * the same arguments, the same launches and bits. The graph key contains rnd's fields. Errors as md_infer_points_voxel's and
+ * md_op_render_points', plus: rnd without the list outputs out->xyz and out->count, rnd->out.rgb without out->rgb ->
+ * MD_ERR_INVALID_ARG. After the first call of a shape nothing is allocated. */
+int md_infer_points_render(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                           const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                           const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

@@ -24,6 +24,13 @@ view is written beside `--output` (`depth_v0.png`, ...). With `--ply` the device
 `--voxel X` (with `--ply`): the cloud is thinned on the device to one point per occupied voxel of side X, the most confident one
 (`md_infer_points_voxel`; with `--views`, `ops.voxel_thin` over the cloud of all views, which share the grid).
 
+`--render-pose E.npy --render-out view.png` (with `--ply`): the cloud is also z-buffered on the device into a virtual camera with the
+world-to-camera pose E ([3,4], or [T,3,4] of which every pose is rendered and the first written) and its depth image written as a
+normalised PNG, holes black (`md_infer_points_render`; with `--views`, `ops.render_points` on the cloud of all views).
+`--render-size H W` (default: the view's size), `--render-radius R` (the (2R+1)^2 pixel footprint of a point),
+`--render-intrinsics K.npy` ([3,3]; default: the first view's, scaled to the render size: with `--views` the model's, for one Depth
+Pro image `--focal-px`).
+
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
 restored to the original size, min-max normalised and written as an 8-bit PNG (example/inference.rs:103-199)."""
@@ -34,6 +41,31 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def render_request(a, h, w, K=None, focal=None):
+    """--render-*: the keywords of a rendering into the pose file's cameras, or a message. K [3,3] / focal: the first view's at h x w."""
+    E = np.asarray(np.load(a.render_pose), np.float32)
+    if E.shape[-2:] != (3, 4) or E.ndim not in (2, 3):
+        return None, f"--render-pose must be [3,4] or [T,3,4], got {E.shape}"
+    E = E.reshape(-1, 3, 4)
+    H, W = a.render_size or (h, w)
+    if a.render_intrinsics:
+        K = np.asarray(np.load(a.render_intrinsics), np.float32).reshape(3, 3)
+    elif K is not None:
+        K = np.asarray(K, np.float32).reshape(3, 3) * np.array([[W / w], [H / h], [1.0]], np.float32)
+    elif focal is not None:
+        K = np.array([[focal * W / w, 0, W / 2], [0, focal * H / h, H / 2], [0, 0, 1]], np.float32)
+    else:
+        return None, "--render-pose needs --render-intrinsics (or, for one Depth Pro image, --focal-px)"
+    return dict(H=int(H), W=int(W), intrinsics=np.broadcast_to(K, (len(E), 3, 3)).copy(), extrinsics=E, radius=a.render_radius), None
+
+
+def write_render(a, P, r) -> None:
+    import torch
+    torch.cuda.synchronize()
+    P.save_depth_map(r.depth[:1].cpu().numpy(), a.render_out, None, None)
+    print(f"Rendered {int(r.filled[0])} pixels of the first pose to {a.render_out}")
 
 
 def run_views(a) -> int:
@@ -96,6 +128,16 @@ def run_views(a) -> int:
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
         P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None)
         print(f"Model `{a.model}` wrote {xyz.shape[0]} points of {len(imgs)} views to {a.ply}")
+        if a.render_pose:
+            req, why = render_request(a, preps[0].height, preps[0].width, K=K[0].cpu().numpy())
+            if why:
+                print(why, file=sys.stderr)
+                return 2
+            try:
+                write_render(a, P, ops.render_points(dev, pc.xyz, req.pop("H"), req.pop("W"), rgb=pc.rgb, count=pc.count[-1:], **req))
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
     return 0
 
 
@@ -121,7 +163,15 @@ def main(argv=None) -> int:
                     help="--ply: drop pixels whose surface is seen at a cosine below this (grazing angles; 0 = off, at most 1)")
     ap.add_argument("--voxel", type=float, default=0.0,
                     help="--ply: keep one point per occupied voxel of this side, the most confident one (md_infer_points_voxel; 0 = off)")
+    ap.add_argument("--render-pose", default="", help="--ply: also render the cloud into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
+    ap.add_argument("--render-size", type=int, nargs=2, metavar=("H", "W"), default=None, help="--render-pose: image size (default: the view's)")
+    ap.add_argument("--render-radius", type=int, default=0, help="--render-pose: a point covers the (2R+1)^2 pixels around its pixel")
+    ap.add_argument("--render-intrinsics", default="", help="--render-pose: [3,3] .npy (default: the first view's, scaled to the render size)")
+    ap.add_argument("--render-out", default="", help="--render-pose: the rendered depth of the first pose as a normalised PNG")
     a = ap.parse_args(argv)
+    if bool(a.render_pose) != bool(a.render_out) or (a.render_pose and not a.ply):
+        print("--render-pose and --render-out go together, and with --ply", file=sys.stderr)
+        return 2
     if a.focal_px is not None and a.model != "depth-pro":
         print(f"--focal-px applies to Depth Pro only, not to `{a.model}`", file=sys.stderr)
         return 2
@@ -158,17 +208,25 @@ def main(argv=None) -> int:
         from burn_depth_amd.inference import rgb_to_input_tensor
         prep = model.prepare_input_image(rgb)
         x = rgb_to_input_tensor(prep.rgb.tobytes(), prep.width, prep.height, model.model.device)
+        render = None
+        if a.render_pose:
+            render, why = render_request(a, prep.height, prep.width, focal=a.focal_px)
+            if why:
+                print(why, file=sys.stderr)
+                return 2
         try:
             pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
                                     dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
                                     world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
-                                    normal_min_cos=a.normal_min_cos, voxel=a.voxel)
+                                    normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
         xyz, col, _ = pc.points()
         P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None)
         print(f"Model `{kind.value}` wrote {xyz.shape[0]} points to {a.ply}")
+        if render is not None:
+            write_render(a, P, pc.render)
         if not a.output:
             return 0
     oh, ow = rgb.shape[:2]
