@@ -89,6 +89,12 @@ class MdPointsRender(C.Structure):
     _fields_ = [("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cam", MdPointsCameras), ("opts", MdRenderOpts), ("out", MdRenderOutputs)]
 
 
+class MdPointsMesh(C.Structure):
+    """md_points_mesh (include/mi_depth.h)."""
+    _fields_ = [("max_rtol", C.c_float), ("faces", C.c_void_p), ("face_count", C.c_void_p), ("face_capacity", C.c_int64),
+                ("pixel_index", C.c_void_p)]
+
+
 class MdViewFilterOpts(C.Structure):
     """md_view_filter_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_percentile", C.c_int),
@@ -202,6 +208,12 @@ SYMBOLS = {
     "md_infer_points_render": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
                                     C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
                                     C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), _I, _P]),
+    "md_op_mesh_grid": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_int64, C.POINTER(MdPointsMesh), _P]),
+    "md_op_unproject_mesh": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
+                                  C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), C.POINTER(MdPointsMesh), _P]),
+    "md_infer_points_mesh": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                  C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                  C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh), _I, _P]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

@@ -144,6 +144,27 @@ size_t render_scratch_bytes(int T, int H, int W);
 // three launches on s (the splat is skipped when n == 0)
 int launch_render_points(const RenderParams& p, void* scratch, hipStream_t s);
 
+// ---- triangle mesh of the depth grid (kernels/mesh.hip; md_op_mesh_grid, md_op_unproject_mesh, md_infer_points_mesh) ----
+// depth [B,H,W] and the map pixel -> list row [B,H,W] -> the faces of the strided lattice as rows of the list, ordered by
+// (view, row, column, triangle): classify (two ballot words per wave and step), scan, scatter. Every pointer is a device
+// pointer. Selection only: no atomics, no float sums.
+struct MeshParams {
+  const float* depth = nullptr;
+  const int32_t* pixel_index = nullptr;  // [B,H,W]: the list row of a pixel, -1 = not in the list
+  int B = 0, H = 0, W = 0, stride = 1;
+  long limit = 0;                        // a corner is usable when 0 <= index < limit (already resolved: no 0 = none here)
+  float max_rtol = 0.f;                  // 0 = every edge passes
+  int32_t* faces = nullptr;              // [face_capacity,3]
+  int32_t* face_count = nullptr;         // [B + 1]; null = no face launches
+  long face_capacity = 0;
+};
+// bytes of the face scratch (ballot word pairs, block counts, block offsets); 256-byte aligned parts
+size_t mesh_scratch_bytes(int B, int H, int W, int stride);
+// one launch: pixel_index [B,H,W] from the bits and offsets launch_unproject (with p.count) left in `points_scratch` for this shape
+int launch_mesh_index(int B, int H, int W, const void* points_scratch, int32_t* pixel_index, hipStream_t s);
+// classify (skipped on a lattice without quads), scan, scatter (skipped without p.faces); nothing without p.face_count
+int launch_mesh_grid(const MeshParams& p, void* scratch, hipStream_t s);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

@@ -524,6 +524,23 @@ int md_infer_points_render(md_model_t m, const float* nchw, int B, int H, int W,
   return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd}, (hipStream_t)stream);
 }
 
+int md_op_mesh_grid(md_device_t dev, const float* depth_dev, const int32_t* pixel_index_dev, int B, int H, int W, int stride,
+                    int64_t vertex_limit, const md_points_mesh* mesh, void* stream) {
+  return op_mesh_grid(dev, DepthMaps{depth_dev, nullptr, nullptr, B, H, W}, pixel_index_dev, stride, vertex_limit, mesh, (hipStream_t)stream);
+}
+
+int md_op_unproject_mesh(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
+                         const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                         const md_points_mesh* mesh, void* stream) {
+  return op_unproject(dev, DepthMaps{depth_dev, conf_dev, rgb_dev, B, H, W}, cam, o, out, nrm, (hipStream_t)stream, mesh);
+}
+
+int md_infer_points_mesh(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                         const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                         const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, int out_kind, void* stream) {
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh}, (hipStream_t)stream);
+}
+
 int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {
   if (!left || !count) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (in_len <= 0 || out_len <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid pass %d -> %d", in_len, out_len);

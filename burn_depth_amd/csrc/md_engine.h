@@ -370,7 +370,7 @@ struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], c
   const float* normals = nullptr;
   int64_t N = 0;
 };
-// One md_infer_points* request: what the widest entry (md_infer_points_render) takes. A narrower entry leaves the parts it lacks
+// One md_infer_points* request: what the widest entry (md_infer_points_mesh) takes. A narrower entry leaves the parts it lacks
 // null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
 struct PointsCall {
   const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
@@ -386,10 +386,14 @@ struct PointsCall {
   const md_points_voxel* vox = nullptr;
   bool need_filter = false;  // the md_infer_points_filtered entry: a null `fo` is refused
   const md_points_render* rnd = nullptr;  // given: the list the call ends with is rendered into its targets (cameras of in_kind)
+  const md_points_mesh* mesh = nullptr;   // given: the faces of the depth grid over the list's rows (pointers of out_kind)
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
-                 const md_points_normals* nrm, hipStream_t stream);
+                 const md_points_normals* nrm, hipStream_t stream, const md_points_mesh* mesh = nullptr);
+// the face kernels alone: in.depth and pixel_index [B,H,W] on the device
+int op_mesh_grid(md_device_t dev, const DepthMaps& in, const int32_t* pixel_index, int stride, int64_t vertex_limit, const md_points_mesh* mesh,
+                 hipStream_t stream);
 int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream);
 int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* vox, const md_points_outputs* out, float* normals_out,
                   hipStream_t stream);

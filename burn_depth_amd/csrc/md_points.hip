@@ -8,9 +8,12 @@
 // of the model's own, and the thinned list goes to the caller.
 // md_op_render_points / md_infer_points_render put the rendering (kernels/render.hip) behind those: the list the call ends with,
 // thinned or not, is z-buffered into the caller's target cameras.
-// The five md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
+// md_op_mesh_grid / md_op_unproject_mesh / md_infer_points_mesh put the depth-grid mesh (kernels/mesh.hip) directly behind the
+// unprojection: the map pixel -> list row from the scratch the list's launches left, then the faces over the list's rows.
+// The six md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -32,6 +35,7 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> vlist;        // md_infer_points_voxel: the unthinned list (xyz | conf | rgb | normals | count)
   md::GrowBuf<void> vtable;       // its hash table and compaction scratch (voxel_scratch_bytes)
   md::GrowBuf<void> rkeys;        // md_infer_points_render: the z-buffer keys (render_scratch_bytes)
+  md::GrowBuf<void> mesh;         // md_infer_points_mesh: the face scratch (mesh_scratch_bytes) | pixel_index when the caller takes none
   md::GrowBuf<float> rcams;       // the device copy of host target cameras: K [T,9] | E [T,12] | focal [T]
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
   float* k_home() const { return cams.p; }
@@ -189,6 +193,48 @@ RenderParams make_render(int T, int H, int W, const md_render_opts& o) {
   return r;
 }
 
+// a mesh part whose three outputs are null is the call without it
+bool mesh_on(const md_points_mesh* g) { return g && (g->faces || g->face_count || g->pixel_index); }
+
+// the mesh part of the operators and of the model call. has_count: the list's `count` is written (md_op_mesh_grid has no list:
+// true); thin: voxel thinning is on. The shape is check_shape's, which every caller runs first.
+int check_mesh(const md_points_mesh* g, bool has_count, bool thin, int B, int H, int W) {
+  if (!g) return MD_OK;
+  MD_TRY(check_nonneg("max_rtol", g->max_rtol));
+  if (g->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)g->face_capacity);
+  if (g->faces && !g->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces need `face_count`");
+  if (!mesh_on(g)) return MD_OK;
+  if (!has_count) MD_FAIL(MD_ERR_INVALID_ARG, "a mesh needs the list's `count`");
+  if (thin) MD_FAIL(MD_ERR_INVALID_ARG, "a mesh together with voxel thinning: the rows its faces name no longer exist");
+  if ((long)B * H * W >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "a mesh takes fewer than 2^30 pixels, got [%d,%d,%d]", B, H, W);
+  return MD_OK;
+}
+
+// limit: a corner is usable below it (the list's capacity, or md_op_mesh_grid's vertex_limit with 0 already resolved)
+MeshParams make_mesh(int B, int H, int W, int stride, long limit, const md_points_mesh& g) {
+  MeshParams q;
+  q.B = B; q.H = H; q.W = W; q.stride = stride; q.limit = limit; q.max_rtol = g.max_rtol;
+  q.faces = g.faces; q.face_count = g.face_count; q.face_capacity = (long)g.face_capacity;
+  return q;
+}
+
+// bytes behind the list's scratch that the mesh stage needs: the face scratch, and a pixel_index home when faces are wanted and
+// the caller takes no map
+size_t mesh_home_bytes(const md_points_mesh& g, int B, int H, int W, int stride) {
+  if (!g.face_count) return 0;
+  return mesh_scratch_bytes(B, H, W, stride) + (g.pixel_index ? 0 : align_up((size_t)B * H * W * 4, 256));
+}
+
+// The mesh stage: pixel_index from the bits and offsets the list's launches left in `points_scratch`, then the faces. q.depth is
+// set; `pix`: where the map goes (null: the tail of `home`, behind the face scratch).
+int launch_mesh(MeshParams q, int32_t* pix, const void* points_scratch, void* home, hipStream_t st) {
+  if (!pix && !q.face_count) return MD_OK;
+  if (!pix) pix = (int32_t*)((char*)home + mesh_scratch_bytes(q.B, q.H, q.W, q.stride));
+  MD_TRY(launch_mesh_index(q.B, q.H, q.W, points_scratch, pix, st));
+  q.pixel_index = pix;
+  return launch_mesh_grid(q, home, st);
+}
+
 uint32_t fbits(float v) {
   uint32_t u;
   memcpy(&u, &v, 4);
@@ -228,11 +274,12 @@ struct OpScratch {
 }  // namespace
 
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
-                 const md_points_normals* nrm, hipStream_t stream) {
+                 const md_points_normals* nrm, hipStream_t stream, const md_points_mesh* mesh) {
   if (!cam) MD_FAIL(MD_ERR_INVALID_ARG, "cameras are null");
   const Sources s{in.rgb != nullptr, in.conf != nullptr, cam->intrinsics != nullptr, cam->focal_px != nullptr, cam->extrinsics != nullptr};
   MD_TRY(check_points(o, out, nrm, s));
   MD_TRY(check_shape(in.B, in.H, in.W));
+  MD_TRY(check_mesh(mesh, out->count != nullptr, false, in.B, in.H, in.W));
   if (!in.depth) MD_FAIL(MD_ERR_INVALID_ARG, "depth pointer is null");
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
   MD_HIP(hipSetDevice(dev->ordinal));
@@ -243,9 +290,38 @@ int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* 
   p.point_map = out->point_map; p.mask = out->mask;
   p.xyz = out->xyz; p.rgb_out = out->rgb; p.conf_out = out->conf; p.count = out->count; p.capacity = out->capacity;
   OpScratch scratch(st);
-  if (p.count) MD_TRY(scratch.alloc(points_scratch_bytes(in.B, in.H, in.W)));
+  const size_t b_list = p.count ? points_scratch_bytes(in.B, in.H, in.W) : 0;
+  const size_t b_mesh = mesh_on(mesh) ? mesh_home_bytes(*mesh, in.B, in.H, in.W, o->stride) : 0;
+  if (b_list) MD_TRY(scratch.alloc(b_list + b_mesh));
   const NormalsParams q = make_normals(nrm);
-  return scratch.finish(launch_unproject(p, scratch.p, st, &q));
+  int rc = launch_unproject(p, scratch.p, st, &q);
+  if (rc == MD_OK && mesh_on(mesh)) {  // the vertices are the rows the list outputs hold
+    MeshParams g = make_mesh(in.B, in.H, in.W, o->stride, (long)out->capacity, *mesh);
+    g.depth = in.depth;
+    rc = launch_mesh(g, mesh->pixel_index, scratch.p, (char*)scratch.p + b_list, st);
+  }
+  return scratch.finish(rc);
+}
+
+int op_mesh_grid(md_device_t dev, const DepthMaps& in, const int32_t* pixel_index, int stride, int64_t vertex_limit, const md_points_mesh* mesh,
+                 hipStream_t stream) {
+  if (!mesh) MD_FAIL(MD_ERR_INVALID_ARG, "mesh is null");
+  if (stride < 1) MD_FAIL(MD_ERR_INVALID_ARG, "stride %d: at least 1", stride);
+  if (vertex_limit < 0) MD_FAIL(MD_ERR_INVALID_ARG, "vertex_limit %lld is negative", (long long)vertex_limit);
+  if (!in.depth || !pixel_index) MD_FAIL(MD_ERR_INVALID_ARG, "depth or pixel_index pointer is null");
+  MD_TRY(check_shape(in.B, in.H, in.W));
+  md_points_mesh faces_only = *mesh;
+  faces_only.pixel_index = nullptr;
+  MD_TRY(check_mesh(&faces_only, true, false, in.B, in.H, in.W));
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  if (!mesh->face_count) return MD_OK;
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  MeshParams g = make_mesh(in.B, in.H, in.W, stride, vertex_limit ? (long)vertex_limit : LONG_MAX, *mesh);
+  g.depth = in.depth; g.pixel_index = pixel_index;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(mesh_scratch_bytes(in.B, in.H, in.W, stride)));
+  return scratch.finish(launch_mesh_grid(g, scratch.p, st));
 }
 
 int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_view_filter_opts* o,
@@ -342,13 +418,14 @@ struct OutSlot {  // a host output's way back: `rows` rows of `row_bytes` from i
   void* caller;
   const void* home;
   size_t row_bytes, rows;
-  bool list;  // a list output: it travels once `count` is known, and only the rows that hold points
+  int list;  // 0: it travels whole. 1: a list output: it travels once `count` is known, and only the rows that hold points.
+             // 2: the faces: likewise with `face_count` and `face_capacity`
 };
 
 // What the stages of one call share: its device pointers, resolved by plan_homes, stage_inputs and run_model.
 struct PointsPlan {
   hipStream_t st;
-  bool dual, thin;
+  bool dual, thin, mesh;
   size_t npx;
   float *depth = nullptr, *raw = nullptr, *conf = nullptr;  // depth: what is unprojected; raw: what the model writes
   const float* x = nullptr;                                 // the image on the device
@@ -356,6 +433,8 @@ struct PointsPlan {
   NormalsParams q;
   VoxelParams v;    // thin: launch_voxel_thin's, from the model's own list that `p` then fills to the list outputs of the call
   RenderParams r;   // c.rnd given: launch_render_points', from the list outputs of the call
+  MeshParams g;     // mesh: launch_mesh's, from the depth that is unprojected and the scratch of `p`'s launches
+  int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   std::vector<OutSlot> slots;
 };
 
@@ -377,7 +456,7 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   int32_t* const no_i = nullptr;
   size_t total = 0;
   pl.slots.clear();
-  auto slot = [&](auto* caller, auto*& param, size_t row_bytes, size_t rows, bool list) {
+  auto slot = [&](auto* caller, auto*& param, size_t row_bytes, size_t rows, int list) {
     param = caller;
     if (!caller || !host) return;
     if (base) {
@@ -386,24 +465,29 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     }
     total += align_up(row_bytes * rows, 256);
   };
-  slot(out.point_map, p.point_map, 12, pl.npx, false);
-  slot(out.mask, p.mask, 1, pl.npx, false);
-  slot(c.nrm ? c.nrm->normal_map : no_f, q.normal_map, 12, pl.npx, false);
-  slot(out.count, thin ? v.count : p.count, 4, (size_t)c.B + 1, false);
-  slot(thin ? c.vox->dropped : no_i, v.dropped, 4, 1, false);
-  slot(out.xyz, thin ? v.xyz_out : p.xyz, 12, cap, true);
-  slot(out.rgb, thin ? v.rgb_out : p.rgb_out, 3, cap, true);
-  slot(out.conf, thin ? v.conf_out : p.conf_out, 4, cap, true);
-  slot(c.nrm ? c.nrm->normals : no_f, thin ? v.normals_out : q.normals, 12, cap, true);
-  slot(thin ? c.vox->index : no_i, v.index, 4, cap, true);
-  slot(thin ? c.vox->weight : no_i, v.weight, 4, cap, true);
+  slot(out.point_map, p.point_map, 12, pl.npx, 0);
+  slot(out.mask, p.mask, 1, pl.npx, 0);
+  slot(c.nrm ? c.nrm->normal_map : no_f, q.normal_map, 12, pl.npx, 0);
+  slot(out.count, thin ? v.count : p.count, 4, (size_t)c.B + 1, 0);
+  slot(thin ? c.vox->dropped : no_i, v.dropped, 4, 1, 0);
+  slot(out.xyz, thin ? v.xyz_out : p.xyz, 12, cap, 1);
+  slot(out.rgb, thin ? v.rgb_out : p.rgb_out, 3, cap, 1);
+  slot(out.conf, thin ? v.conf_out : p.conf_out, 4, cap, 1);
+  slot(c.nrm ? c.nrm->normals : no_f, thin ? v.normals_out : q.normals, 12, cap, 1);
+  slot(thin ? c.vox->index : no_i, v.index, 4, cap, 1);
+  slot(thin ? c.vox->weight : no_i, v.weight, 4, cap, 1);
   if (c.rnd) {  // rendered images are dense outputs: they travel whole
     RenderParams& r = pl.r;
     const size_t rpx = (size_t)r.T * r.H * r.W;
-    slot(c.rnd->out.depth, r.depth, 4, rpx, false);
-    slot(c.rnd->out.index, r.index, 4, rpx, false);
-    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, false);
-    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, false);
+    slot(c.rnd->out.depth, r.depth, 4, rpx, 0);
+    slot(c.rnd->out.index, r.index, 4, rpx, 0);
+    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, 0);
+    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, 0);
+  }
+  if (pl.mesh) {
+    slot(c.mesh->pixel_index, pl.pix, 4, pl.npx, 0);
+    slot(c.mesh->face_count, pl.g.face_count, 4, (size_t)c.B + 1, 0);
+    slot(c.mesh->faces, pl.g.faces, 12, (size_t)c.mesh->face_capacity, 2);
   }
   return total;
 }
@@ -439,6 +523,11 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
     if (c.in_kind == MD_MEM_HOST) MD_TRY(grow(m, st, f->rcams, (size_t)c.rnd->T * 22 * 4));
+  }
+  pl.mesh = mesh_on(c.mesh);
+  if (pl.mesh) {
+    pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
+    if (const size_t bytes = mesh_home_bytes(*c.mesh, B, H, W, c.o->stride)) MD_TRY(grow(m, st, f->mesh, bytes));
   }
   if (const size_t total = place_outputs(c, pl, nullptr)) {
     MD_TRY(grow(m, st, f->out, total));
@@ -532,6 +621,12 @@ int run_unproject(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   return launch_unproject(p, m->points->scratch.p, pl.st, &pl.q);
 }
 
+// The mesh of the list: needs the scratch of run_unproject's launches before anything reuses it.
+int run_mesh(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+  pl.g.depth = pl.depth;
+  return launch_mesh(pl.g, pl.pix, m->points->scratch.p, m->points->mesh.p, pl.st);
+}
+
 // Voxel thinning: the model's own list -> the list outputs of the call.
 int run_thin(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   MD_TRY(launch_voxel_thin(pl.v, m->points->vtable.p, pl.st));
@@ -561,15 +656,16 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
   };
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
-    if (!s.list) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
+    if (s.list == 0) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
   int32_t overflow = 0;
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
   MD_HIP(hipStreamSynchronize(pl.st));
   if (overflow) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
   if (!c.out->count) return MD_OK;
   const size_t n = std::min((size_t)c.out->count[c.B], (size_t)c.out->capacity);
+  const size_t nf = pl.mesh && c.mesh->faces ? std::min((size_t)c.mesh->face_count[c.B], (size_t)c.mesh->face_capacity) : 0;
   for (const OutSlot& s : pl.slots)
-    if (s.list) MD_TRY(d2h(s.caller, s.home, n * s.row_bytes));
+    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 2 ? nf : n) * s.row_bytes));
   MD_HIP(hipStreamSynchronize(pl.st));
   return MD_OK;
 }
@@ -577,7 +673,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
 // The stages in the order a captured graph bakes: every grow of the device path before anything is enqueued, then the work.
 int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) {
   if (!m->points) m->points = new md_model_s::PointsState();
-  PointsPlan pl{st, dual, false, (size_t)c.B * c.H * c.W};
+  PointsPlan pl{st, dual, false, false, (size_t)c.B * c.H * c.W};
   auto timed = [&](const char* name, int (*stage)(md_model_s*, const PointsCall&, PointsPlan&)) -> int {
     Run r{m, st, c.B};
     r.begin(name);
@@ -590,6 +686,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   MD_TRY(run_model(m, c, pl));
   if (c.fo) MD_TRY(timed("points_view_filter", run_filter));
   MD_TRY(timed("points_unproject", run_unproject));
+  if (pl.mesh) MD_TRY(timed("points_mesh", run_mesh));
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   return copy_outputs(m, c, pl);
@@ -622,6 +719,7 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   MD_TRY(check_voxel(c.vox, out, false));
   if (voxel_on(c.vox) && list_rows(B, H, W, o->stride) >= (1l << 30))
     MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
+  MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   if (c.rnd) {
     MD_TRY(check_render(c.rnd->T, c.rnd->H, c.rnd->W, &c.rnd->cam, &c.rnd->opts, &c.rnd->out, out->rgb != nullptr));
     if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rendering needs the list outputs `xyz` and `count`");
@@ -666,6 +764,8 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     key_add(key, 0x524e4452u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px);
     key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.radius, r.out.depth, r.out.index, r.out.rgb, r.out.filled);
   }
+  if (mesh_on(c.mesh))  // every output null: the key, and the graph, of the call without a mesh
+    key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
   return run_with_graph(m, st, key, eligible, body);
 }
 

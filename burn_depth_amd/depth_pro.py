@@ -96,7 +96,10 @@ class PointCloud:
     parallel to xyz. With voxel thinning (`md_op_voxel_thin` / `md_infer_points_voxel`): the list holds one row per occupied
     voxel, index int32 [capacity] is the source row of every output row in the unthinned list, weight int32 [capacity] the
     points of its voxel, dropped int32 [1] the rows outside the grid. With `infer_points(render=...)`
-    (`md_infer_points_render`): render = the `RenderedPoints` of the list."""
+    (`md_infer_points_render`): render = the `RenderedPoints` of the list. With `mesh=` (`md_op_unproject_mesh` /
+    `md_infer_points_mesh`): faces int32 [face_capacity,3] name rows of xyz, in (view, row, column, triangle) order, of which
+    the first min(face_count[B], face_capacity) are faces; face_count int32 [B+1]; pixel_index int32 [B,H,W] is the row of
+    every pixel in the list, -1 where it is not in it. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -110,6 +113,9 @@ class PointCloud:
     weight: Optional[torch.Tensor] = None
     dropped: Optional[torch.Tensor] = None
     render: Optional["RenderedPoints"] = None
+    faces: Optional[torch.Tensor] = None
+    face_count: Optional[torch.Tensor] = None
+    pixel_index: Optional[torch.Tensor] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -177,6 +183,28 @@ def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
     return _lib.MdPointsVoxel(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped))
 
 
+def _points_mesh(dev, B: int, H: int, W: int, stride: int, mesh, out: PointCloud, fresh: bool):
+    """md_points_mesh for `out`. mesh: True, or a dict with any of max_rtol (0 = no discontinuity cut), face_capacity (default:
+    two faces per quad of the strided lattice) and pixel_index (default True: also return the map). With `fresh` the tensors
+    are created; otherwise the ones `out` carries are written again."""
+    kw = dict(mesh) if isinstance(mesh, dict) else {}
+    unknown = set(kw) - {"max_rtol", "face_capacity", "pixel_index"}
+    if unknown:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown mesh keywords {sorted(unknown)}")
+    if mesh and not fresh and out.faces is None and out.face_count is None and out.pixel_index is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "mesh= with an `out` that carries neither `faces`, `face_count` nor `pixel_index`")
+    cap = int(out.faces.shape[0]) if out.faces is not None else 0
+    if fresh:
+        stride = max(int(stride), 1)  # a bad stride, like a negative capacity, is the library's to refuse
+        cap = kw.get("face_capacity")
+        cap = 2 * B * ((H + stride - 1) // stride - 1) * ((W + stride - 1) // stride - 1) if cap is None else int(cap)
+        out.faces = torch.empty((max(cap, 0), 3), dtype=torch.int32, device=dev)
+        out.face_count = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        if kw.get("pixel_index", True):
+            out.pixel_index = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    return _lib.MdPointsMesh(float(kw.get("max_rtol", 0.0)), _ptr(out.faces) or None, _ptr(out.face_count), cap, _ptr(out.pixel_index))
+
+
 def _render_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
                     radius=0, want_rgb=False, out: Optional[RenderedPoints] = None):
     """The target cameras, options and outputs of a rendering -> (T, cameras, md_render_opts, RenderedPoints, md_render_outputs,
@@ -218,10 +246,11 @@ def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None
 def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrinsics, focal_px, want_rgb: bool, want_conf: bool,
                     want_depth: bool, dense: bool, compact: bool, capacity: Optional[int], out: Optional[PointCloud], normals: bool,
                     normal_min_cos: float, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
-                    voxel: Optional[float] = None, render: Optional[dict] = None):
+                    voxel: Optional[float] = None, render: Optional[dict] = None, mesh=None):
     """The keyword set of `infer_points` / `ops.unproject` as the structs of the widest entry -> (cloud, opts, outs, cam, fo, nrm,
-    vox, rnd, keep-alive). fo, nrm, vox and rnd are None for the parts not asked for (an `out` that carries normal or thinning
-    tensors asks for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless `out` is given.
+    vox, rnd, msh, keep-alive). fo, nrm, vox, rnd and msh are None for the parts not asked for (an `out` that carries normal,
+    thinning or mesh tensors asks for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless
+    `out` is given. mesh: the argument of `_points_mesh`.
     render: the keywords of `_render_request` (H, W, the target cameras, pixel_offset, z_near, z_far, radius); the images go to
     fresh tensors, or to the `render` that `out` carries. Positional
     arguments and a plain tuple back: this sits on the host path of every call. opts: the fields of `md_points_opts`; want_rgb /
@@ -241,7 +270,10 @@ def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrins
         T, tcam, ro, res.render, routs, tkeep = _render_request(dev, **render, want_rgb=res.rgb is not None, out=res.render)
         rnd = _lib.MdPointsRender(T, int(render["H"]), int(render["W"]), tcam, ro, routs)
         keep = keep + tkeep
-    return res, o, outs, cam, fo, nrm, vox, rnd, keep
+    msh = None
+    if mesh or res.faces is not None or res.face_count is not None or res.pixel_index is not None:
+        msh = _points_mesh(dev, B, H, W, o.stride, mesh, res, out is None)
+    return res, o, outs, cam, fo, nrm, vox, rnd, msh, keep
 
 
 @dataclass
@@ -626,13 +658,13 @@ class DepthPro:
     def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
-                     normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, **opts) -> PointCloud:
+                     normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        Every form runs through the widest entry, `md_infer_points_render`, with NULL for the parts not asked for, which is
-        `md_infer_points` / `_filtered` / `_normals` / `_voxel` on the same arguments:
+        Every form runs through the widest entry, `md_infer_points_mesh`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` on the same arguments:
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
         conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
         before the unprojection; `depth` is then the filtered depth.
@@ -643,7 +675,10 @@ class DepthPro:
         filter and the normals.
         render (`md_points_render`): a dict with H, W, the target cameras (intrinsics [T,3,3] or focal_px [T]; extrinsics [T,3,4]
         world-to-camera or None) and optionally pixel_offset, z_near, z_far, radius: the list the call ends with is z-buffered into
-        those cameras in the same call; the images come back as `render` (`RenderedPoints`). Needs compact=True."""
+        those cameras in the same call; the images come back as `render` (`RenderedPoints`). Needs compact=True.
+        mesh (`md_points_mesh`): True, or a dict with any of max_rtol, face_capacity, pixel_index: the triangle mesh of the depth
+        grid over the rows of the list, cut where neighbouring depths differ by more than max_rtol of the nearer one; comes back
+        as `faces`, `face_count` and `pixel_index`. Needs compact=True; not with voxel > 0."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -652,14 +687,14 @@ class DepthPro:
         if rgb is not None:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
         has_conf = bool(getattr(self.config, "dual_head", False))
-        res, o, outs, cam, fo, nrm, vox, rnd, keep = _points_request(
+        res, o, outs, cam, fo, nrm, vox, rnd, msh, keep = _points_request(
             dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
-            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render)
+            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, mesh)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        _lib.check(self._lib.md_infer_points_render(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                    C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), _lib.MD_MEM_DEVICE,
-                                                    _stream_ptr(self.device.ordinal)))
+        _lib.check(self._lib.md_infer_points_mesh(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                  C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                  C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), _lib.MD_MEM_DEVICE,
+                                                  _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

@@ -434,20 +434,25 @@ def conv2d_direct_ex(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Option
 
 def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None, focal_px=None, conf: Optional[torch.Tensor] = None,
               rgb: Optional[torch.Tensor] = None, dense: bool = True, compact: bool = True, capacity: Optional[int] = None,
-              out: Optional[PointCloud] = None, normals: bool = False, normal_min_cos: float = 0.0, **opts) -> PointCloud:
-    """md_op_unproject_normals: depth [B,H,W] (+ conf [B,H,W], + u8 rgb [B,H,W,3]) and pinhole cameras (intrinsics [B,3,3] or focal_px
+              out: Optional[PointCloud] = None, normals: bool = False, normal_min_cos: float = 0.0, mesh=None, **opts) -> PointCloud:
+    """md_op_unproject_mesh: depth [B,H,W] (+ conf [B,H,W], + u8 rgb [B,H,W,3]) and pinhole cameras (intrinsics [B,3,3] or focal_px
     [B]; extrinsics [B,3,4] world-to-camera for world=True) -> `PointCloud`. opts: the fields of `md_points_opts`. normals /
     normal_min_cos (or an `out` that carries normal tensors): the surface normals beside the points and the grazing-angle test;
-    without them the entry gets NULL normals, which is md_op_unproject. Bit-identical to `pipeline.unproject_depth`."""
+    without them the entry gets NULL normals, which is md_op_unproject. mesh: True, or a dict with any of max_rtol, face_capacity,
+    pixel_index (or an `out` that carries mesh tensors): `faces`, `face_count` and `pixel_index` of the depth grid over the list's
+    rows; without it the entry gets a NULL mesh, which is md_op_unproject_normals. Bit-identical to `pipeline.unproject_depth`,
+    `pipeline.pixel_index` and `pipeline.mesh_grid`."""
     depth = _f32c(depth)
     B, H, W = (int(v) for v in depth.shape)
     conf = _f32c(conf) if conf is not None else None
     rgb = rgb.contiguous() if rgb is not None else None
     assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
-    res, o, outs, cam, _, nrm, _, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
-                                                         conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos)
-    _lib.check(_lib.load().md_op_unproject_normals(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
-                                                   C.byref(nrm) if nrm is not None else None, _stream_ptr(dev.ordinal)))
+    res, o, outs, cam, _, nrm, _, _, msh, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
+                                                              conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos,
+                                                              mesh=mesh)
+    _lib.check(_lib.load().md_op_unproject_mesh(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
+                                                C.byref(nrm) if nrm is not None else None, C.byref(msh) if msh is not None else None,
+                                                _stream_ptr(dev.ordinal)))
     del keep
     return res
 
@@ -523,6 +528,31 @@ def render_points(dev: Device, xyz: torch.Tensor, H: int, W: int, intrinsics=Non
                                                C.byref(outs), _stream_ptr(dev.ordinal)))
     del keep
     return out
+
+
+def mesh_grid(dev: Device, depth: torch.Tensor, pixel_index: torch.Tensor, stride: int = 1, max_rtol: float = 0.0, vertex_limit: int = 0,
+              face_capacity: Optional[int] = None, faces: Optional[torch.Tensor] = None, face_count: Optional[torch.Tensor] = None):
+    """md_op_mesh_grid: depth f32 [B,H,W] and a map pixel_index int32 [B,H,W] (the list row of a pixel, -1 = none) -> (faces int32
+    [face_capacity,3], face_count int32 [B+1]): the triangles of the strided lattice whose corners have an index in
+    [0, vertex_limit) (0 = no limit) and whose edges pass the max_rtol test, in (view, row, column, triangle) order.
+    face_capacity defaults to two faces per quad; `faces` / `face_count`: tensors to write into again. Bit-identical to
+    `pipeline.mesh_grid`."""
+    assert depth.is_cuda and depth.dim() == 3 and pixel_index.is_cuda and pixel_index.dtype == torch.int32
+    depth, pixel_index = _f32c(depth), pixel_index.contiguous()
+    B, H, W = (int(v) for v in depth.shape)
+    assert tuple(pixel_index.shape) == (B, H, W)
+    s = max(int(stride), 1)  # a bad stride is the library's to refuse
+    if faces is None:
+        cap = 2 * B * ((H + s - 1) // s - 1) * ((W + s - 1) // s - 1) if face_capacity is None else int(face_capacity)
+        faces = torch.empty((max(cap, 0), 3), dtype=torch.int32, device=depth.device)
+    else:
+        cap = int(faces.shape[0]) if face_capacity is None else int(face_capacity)
+    if face_count is None:
+        face_count = torch.empty(B + 1, dtype=torch.int32, device=depth.device)
+    msh = _lib.MdPointsMesh(float(max_rtol), _p(faces) if faces.numel() else None, _p(face_count), cap, None)
+    _lib.check(_lib.load().md_op_mesh_grid(dev.handle, _p(depth), _p(pixel_index), B, H, W, int(stride), int(vertex_limit), C.byref(msh),
+                                           _stream_ptr(dev.ordinal)))
+    return faces, face_count
 
 
 def fov_to_focal(fovx_deg: float, H: int, W: int) -> Tuple[float, float]:

@@ -14,6 +14,8 @@
   device kernels of `md_op_unproject` / `md_infer_points` are bit-identical to, and a binary little-endian PLY writer / reader
 * `filter_views`                              -- the host reference of `md_op_filter_views` / `md_infer_points_filtered`: the exact
   confidence percentile and the cross-view support test in front of the point path
+* `pixel_index`, `mesh_grid`                  -- the host reference of `md_op_mesh_grid` / `md_infer_points_mesh`: the map pixel -> list
+  row and the triangle mesh of the depth grid over the list's rows, bit-identical to the device's
 * `render_points`                             -- the host reference of `md_op_render_points` / `md_infer_points_render`: the cloud
   z-buffered into target cameras on 64-bit keys
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
@@ -622,8 +624,69 @@ def render_points(xyz, H, W, intrinsics=None, extrinsics=None, focal_px=None, rg
     return HostRender(depth, index, color, filled)
 
 
-def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None) -> None:
-    """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar."""
+def pixel_index(mask, stride: int = 1) -> np.ndarray:
+    """The host reference of `pixel_index` (md_points_mesh, include/mi_depth.h): mask [B,H,W] (the validity mask of the point path,
+    or a `HostPoints`) -> int32 [B,H,W], the row of every pixel in the compacted list (valid pixels of the strided lattice in
+    (view, row, column) order), -1 where the pixel is not in it."""
+    m = np.asarray(mask.mask if isinstance(mask, HostPoints) else mask)
+    if m.ndim != 3:
+        raise ValueError(f"expected a mask [B,H,W], got {m.shape}")
+    if stride < 1:
+        raise ValueError("stride must be at least 1")
+    sel = np.zeros(m.shape, bool)
+    sel[:, ::stride, ::stride] = m[:, ::stride, ::stride] != 0
+    flat = sel.reshape(-1)
+    return np.where(flat, np.cumsum(flat, dtype=np.int64) - 1, -1).astype(np.int32).reshape(m.shape)
+
+
+def mesh_grid(depth, pixel_index, stride: int = 1, max_rtol: float = 0.0, vertex_limit: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The host reference of md_op_mesh_grid / md_op_unproject_mesh / md_infer_points_mesh (include/mi_depth.h states the
+    contract): depth [B,H,W] and the map pixel -> list row int32 [B,H,W] -> (faces int32 [F,3], face_count int32 [B+1]). The
+    quads of the strided lattice, each split along the diagonal with the smaller depth difference (or the one its usable corners
+    allow) into two triangles of camera-facing winding; a triangle is emitted when its corners have an index in [0, vertex_limit)
+    (0 = no limit) and, with max_rtol > 0, |dx - dy| <= max_rtol * min(dx, dy) holds on its three edges. The comparisons are f32,
+    one rounded operation per step, so the faces are the device's bit for bit; the order is (view, row, column, triangle)."""
+    d = np.asarray(depth, dtype=np.float32)
+    pi = np.asarray(pixel_index)
+    if d.ndim != 3 or pi.shape != d.shape:
+        raise ValueError(f"expected depth and pixel_index [B,H,W], got {d.shape} and {pi.shape}")
+    if not np.issubdtype(pi.dtype, np.integer):
+        raise ValueError("pixel_index must be an integer map")
+    if stride < 1:
+        raise ValueError("stride must be at least 1")
+    if not np.isfinite(max_rtol) or max_rtol < 0:
+        raise ValueError("max_rtol must be finite and >= 0")
+    if vertex_limit < 0:
+        raise ValueError("vertex_limit must be >= 0")
+    B = d.shape[0]
+    dn, pn = d[:, ::stride, ::stride], pi[:, ::stride, ::stride].astype(np.int64)
+    corner = lambda a: (a[:, :-1, :-1], a[:, :-1, 1:], a[:, 1:, :-1], a[:, 1:, 1:])  # noqa: E731  a, b, c, d
+    ia, ib, ic, id_ = corner(pn)
+    da, db, dc, dd = corner(dn)
+    use = lambda i: (i >= 0) & ((i < vertex_limit) if vertex_limit else True)  # noqa: E731
+    ua, ub, uc, ud = use(ia), use(ib), use(ic), use(id_)
+    rt = np.float32(max_rtol)
+    with np.errstate(all="ignore"):
+        def edge(dx, dy):
+            if max_rtol == 0:
+                return np.ones(dx.shape, bool)
+            return np.abs(dx - dy) <= rt * np.fmin(dx, dy)
+
+        ad = np.where(ua & ub & uc & ud, np.abs(da - dd) <= np.abs(db - dc), ua & ud)
+        # a-d: (a, c, d), (a, d, b); b-c: (a, c, b), (b, c, d)
+        first = np.where(ad, ua & uc & ud & edge(da, dc) & edge(dc, dd) & edge(dd, da), ua & uc & ub & edge(da, dc) & edge(dc, db) & edge(db, da))
+        second = np.where(ad, ua & ud & ub & edge(da, dd) & edge(dd, db) & edge(db, da), ub & uc & ud & edge(db, dc) & edge(dc, dd) & edge(dd, db))
+    tri = np.stack([np.stack([ia, ic, np.where(ad, id_, ib)], -1),
+                    np.stack([np.where(ad, ia, ib), np.where(ad, id_, ic), np.where(ad, ib, id_)], -1)], -2)  # [B,Hq,Wq,2,3]
+    emit = np.stack([first, second], -1)
+    count = np.concatenate([emit.reshape(B, -1).sum(1), [emit.sum()]]).astype(np.int32)
+    return tri[emit].astype(np.int32).reshape(-1, 3), count
+
+
+def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None,
+              faces: Optional[np.ndarray] = None) -> None:
+    """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar; with `faces` int [F,3]
+    an `element face` of `uchar int` vertex_indices lists behind the vertices (faces=None: the file without it)."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     if normals is not None:
@@ -645,12 +708,22 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, norm
         for i, n in enumerate(("red", "green", "blue")):
             rec[n] = rgb[:, i]
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(xyz)}"]
-    head += [f"property {'float' if t == '<f4' else 'uchar'} {n}" for n, t in fields] + ["end_header"]
+    head += [f"property {'float' if t == '<f4' else 'uchar'} {n}" for n, t in fields]
+    tail = b""
+    if faces is not None:
+        faces = np.asarray(faces).reshape(-1, 3)
+        if len(faces) and (faces.min() < 0 or faces.max() >= len(xyz)):
+            raise ValueError(f"a face names a vertex outside 0..{len(xyz) - 1}")
+        frec = np.empty(len(faces), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+        frec["n"], frec["v"] = 3, faces
+        head += [f"element face {len(faces)}", "property list uchar int vertex_indices"]
+        tail = frec.tobytes()
+    head += ["end_header"]
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
     with open(path, "wb") as f:
-        f.write(("\n".join(head) + "\n").encode("ascii") + rec.tobytes())
+        f.write(("\n".join(head) + "\n").encode("ascii") + rec.tobytes() + tail)
 
 
 def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
@@ -666,12 +739,30 @@ def read_ply_normals(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], Optio
     lines = b[:end].decode("ascii").split("\n")
     assert lines[0] == "ply" and lines[1] == "format binary_little_endian 1.0"
     n = int(next(l for l in lines if l.startswith("element vertex")).split()[2])
-    fields = [(l.split()[2], "<f4" if l.split()[1] == "float" else "u1") for l in lines if l.startswith("property")]
+    fields = [(l.split()[2], "<f4" if l.split()[1] == "float" else "u1") for l in lines if l.startswith("property") and l.split()[1] != "list"]
     rec = np.frombuffer(b, dtype=np.dtype(fields), count=n, offset=end)
     xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float32)
     rgb = np.stack([rec["red"], rec["green"], rec["blue"]], axis=-1) if "red" in rec.dtype.names else None
     nrm = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=-1).astype(np.float32) if "nx" in rec.dtype.names else None
     return xyz, rgb, nrm
+
+
+def read_ply_faces(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
+    """`read_ply_normals` with the faces -> (xyz, rgb or None, normals or None, faces int32 [F,3] or None when the file has no
+    face element)."""
+    xyz, rgb, nrm = read_ply_normals(path)
+    b = open(path, "rb").read()
+    end = b.index(b"end_header\n") + len(b"end_header\n")
+    lines = b[:end].decode("ascii").split("\n")
+    face = [l for l in lines if l.startswith("element face")]
+    if not face:
+        return xyz, rgb, nrm, None
+    assert "property list uchar int vertex_indices" in lines
+    size = {"float": 4, "uchar": 1}
+    vertex_bytes = sum(size[l.split()[1]] for l in lines if l.startswith("property") and l.split()[1] != "list") * len(xyz)
+    frec = np.frombuffer(b, dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]), count=int(face[0].split()[2]), offset=end + vertex_bytes)
+    assert (frec["n"] == 3).all()
+    return xyz, rgb, nrm, frec["v"].astype(np.int32)
 
 
 def save_depth_map(depth: np.ndarray, path: str, crop: Optional[ImageCropRegion] = None,
@@ -729,7 +820,7 @@ class AnyDepthModel:
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
-        and render= (`md_infer_points_render`) included."""
+        render= (`md_infer_points_render`) and mesh= (`md_infer_points_mesh`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

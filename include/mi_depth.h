@@ -529,6 +529,65 @@ int md_infer_points_render(md_model_t m, const float* nchw, int B, int H, int W,
                            const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                            const md_points_voxel* vox, const md_points_render* rnd, int out_kind, void* stream);
 
+/* ---- point path: triangle mesh of the depth grid ---------------------------------------------------------------------------
+ * A surface over the list: neighbouring lattice pixels are joined into triangles, which are cut at depth discontinuities. The
+ * vertices are the rows of the compacted list, a face is three of them. Selection with integer outputs: a face is emitted or
+ * not from f32 comparisons, one rounded operation per step, no fused multiply-add, no atomics (pipeline.pixel_index and
+ * pipeline.mesh_grid restate it in numpy bit for bit):
+ *   lattice: with stride = md_points_opts.stride, node (i, j) is pixel (v, u) = (i stride, j stride), 0 <= i < Hs =
+ *     ceil(H / stride), 0 <= j < Ws = ceil(W / stride). Quad (b, i, j) exists for i < Hs - 1, j < Ws - 1; its corners are
+ *     a = (i, j), b = (i, j+1), c = (i+1, j), d = (i+1, j+1).
+ *   pixel_index int32 [B,H,W]: the row of a pixel in the compacted list as xyz orders it: its true rank, global over the
+ *     views, also beyond `capacity`; -1 where the pixel did not enter the list.
+ *   usable corner: its index is >= 0 and below the vertex limit: `capacity` of the list in the combined calls, vertex_limit in
+ *     md_op_mesh_grid (0 = no limit).
+ *   edge (x, y) between usable corners with depths dx, dy: max_rtol == 0: it passes; otherwise it passes when
+ *     fabsf(dx - dy) <= max_rtol * fminf(dx, dy) (subtract, abs, min, multiply, compare).
+ *   diagonal: all four corners usable: a-d when fabsf(da - dd) <= fabsf(db - dc), otherwise b-c; a or d unusable: b-c;
+ *     otherwise a-d.
+ *   triangles, in this order inside a quad: diagonal a-d: (a, c, d), (a, d, b); diagonal b-c: (a, c, b), (b, c, d). A triangle
+ *     is emitted when its three corners are usable and its three edges pass. All four windings face the camera: with x right,
+ *     y down, z forward, (p1 - p0) x (p2 - p0) has negative z in the image plane, the orientation of md_points_normals.
+ *   faces int32 [face_capacity,3]: list rows, ordered by (b, i, j, triangle). face_count int32 [B+1]: the true totals per view
+ *     and overall, also when they exceed face_capacity: then only the first face_capacity faces are written and the memory
+ *     behind them stays untouched, as count / capacity behave. */
+typedef struct md_points_mesh {
+  float max_rtol;          /* 0 = no discontinuity cut; finite and >= 0 */
+  int32_t* faces;          /* int32 [face_capacity,3]; needs face_count. NULL = skip */
+  int32_t* face_count;     /* int32 [B+1]; NULL = skip */
+  int64_t face_capacity;   /* faces that `faces` holds */
+  int32_t* pixel_index;    /* int32 [B,H,W]; NULL = skip */
+} md_points_mesh;
+
+/* The face kernels alone on caller device tensors: depth_dev f32 [B,H,W], pixel_index_dev int32 [B,H,W] (any map: it need
+ * not come from a list). mesh->pixel_index is ignored. Everything is enqueued on `stream`; the call returns after the stream
+ * has drained, because its scratch is freed on return. A lattice without quads (Hs or Ws = 1): face_count all zero, faces
+ * untouched. Errors, before any launch: dev / mesh / depth_dev / pixel_index_dev NULL, stride < 1, vertex_limit < 0, max_rtol
+ * not finite or negative, face_capacity < 0, faces without face_count -> MD_ERR_INVALID_ARG; B, H, W <= 0 or
+ * B*H*W >= 2^30 (two faces per quad must fit int32) -> MD_ERR_SHAPE. */
+int md_op_mesh_grid(md_device_t dev, const float* depth_dev, const int32_t* pixel_index_dev, int B, int H, int W, int stride,
+                    int64_t vertex_limit, const md_points_mesh* mesh, void* stream);
+/* md_op_unproject_normals with the mesh of its list: one launch writes pixel_index (into a scratch of the call when the
+ * caller takes none and asks for faces), three write the faces. The depths of the edge test are depth_dev's. mesh NULL (or
+ * its three outputs NULL): md_op_unproject_normals on the same arguments, the same launches and bits. The call returns after
+ * the stream has drained. Errors as md_op_unproject_normals' and md_op_mesh_grid's, plus: a mesh output without out->count
+ * -> MD_ERR_INVALID_ARG; B*H*W >= 2^30 with a mesh output -> MD_ERR_SHAPE. */
+int md_op_unproject_mesh(md_device_t dev, const float* depth_dev, const float* conf_dev, const uint8_t* rgb_dev, int B, int H, int W,
+                         const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
+                         const md_points_normals* nrm, const md_points_mesh* mesh, void* stream);
+/* md_infer_points_render with the mesh of the list: the mesh stage runs directly behind the unprojection, on the depth that
+ * was unprojected (out->depth). mesh's pointers are of out_kind; with host outputs only the first
+ * min(face_count[B], face_capacity) rows of faces travel. The face scratch and a pixel_index the caller does not take live in
+ * a grow-only buffer of the model. mesh NULL (or its three outputs NULL): md_infer_points_render on the same arguments, the
+ * same launches and bits. The graph key contains mesh's fields. Errors as md_infer_points_render's and md_op_unproject_mesh's,
+ * plus: a mesh output together with voxel thinning (the rows the faces name no longer exist) -> MD_ERR_INVALID_ARG. After the
+ * first call of a shape nothing is allocated. */
+int md_infer_points_mesh(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                         const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                         const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                         const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, int out_kind,
+                         void* stream);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

@@ -31,6 +31,10 @@ normalised PNG, holes black (`md_infer_points_render`; with `--views`, `ops.rend
 `--render-intrinsics K.npy` ([3,3]; default: the first view's, scaled to the render size: with `--views` the model's, for one Depth
 Pro image `--focal-px`).
 
+`--mesh [--mesh-rtol X]` (with `--ply`): the file also carries the triangle mesh of the depth grid over its points (`element face`),
+cut where neighbouring depths differ by more than X of the nearer one (default 0.05; 0 = no cut), computed on the device
+(`md_infer_points_mesh`; with `--views`, `ops.unproject(mesh=)`: one mesh per view, not merged). Not together with `--voxel`.
+
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
 restored to the original size, min-max normalised and written as an 8-bit PNG (example/inference.rs:103-199)."""
@@ -115,7 +119,9 @@ def run_views(a) -> int:
                                               view_rtol=a.view_rtol, min_views=a.min_views)
         rgb = torch.from_numpy(np.stack([p.rgb for p in preps])).to(depth.device)
         pc = ops.unproject(dev, depth, intrinsics=K, extrinsics=E, conf=out.depth_confidence, rgb=rgb, dense=False, conf_min=a.conf_min,
-                           edge_rtol=a.edge_rtol, stride=a.stride, world=True, normals=a.normals, normal_min_cos=a.normal_min_cos)
+                           edge_rtol=a.edge_rtol, stride=a.stride, world=True, normals=a.normals, normal_min_cos=a.normal_min_cos,
+                           mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None)
+        faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy() if a.mesh else None
         xyz, col, conf = pc.points()
         nrm = pc.normals[:xyz.shape[0]] if a.normals else None
         if a.voxel > 0:  # one point per occupied voxel over all views: the most confident one
@@ -126,8 +132,8 @@ def run_views(a) -> int:
                 return 1
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None)
-        print(f"Model `{a.model}` wrote {xyz.shape[0]} points of {len(imgs)} views to {a.ply}")
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces)
+        print(f"Model `{a.model}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} of {len(imgs)} views to {a.ply}")
         if a.render_pose:
             req, why = render_request(a, preps[0].height, preps[0].width, K=K[0].cpu().numpy())
             if why:
@@ -168,7 +174,13 @@ def main(argv=None) -> int:
     ap.add_argument("--render-radius", type=int, default=0, help="--render-pose: a point covers the (2R+1)^2 pixels around its pixel")
     ap.add_argument("--render-intrinsics", default="", help="--render-pose: [3,3] .npy (default: the first view's, scaled to the render size)")
     ap.add_argument("--render-out", default="", help="--render-pose: the rendered depth of the first pose as a normalised PNG")
+    ap.add_argument("--mesh", action="store_true", help="--ply: also write the triangle mesh of the depth grid over the points (md_infer_points_mesh)")
+    ap.add_argument("--mesh-rtol", type=float, default=0.05,
+                    help="--mesh: cut an edge whose depths differ by more than this fraction of the nearer one (0 = no cut)")
     a = ap.parse_args(argv)
+    if a.mesh and (not a.ply or a.voxel > 0):
+        print("--mesh goes with --ply, and not with --voxel (a thinned list has no grid)", file=sys.stderr)
+        return 2
     if bool(a.render_pose) != bool(a.render_out) or (a.render_pose and not a.ply):
         print("--render-pose and --render-out go together, and with --ply", file=sys.stderr)
         return 2
@@ -218,13 +230,15 @@ def main(argv=None) -> int:
             pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
                                     dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
                                     world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
-                                    normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render)
+                                    normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render,
+                                    mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
         xyz, col, _ = pc.points()
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None)
-        print(f"Model `{kind.value}` wrote {xyz.shape[0]} points to {a.ply}")
+        faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy() if a.mesh else None
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None, faces=faces)
+        print(f"Model `{kind.value}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} to {a.ply}")
         if render is not None:
             write_render(a, P, pc.render)
         if not a.output:
