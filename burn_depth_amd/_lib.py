@@ -95,6 +95,21 @@ class MdPointsMesh(C.Structure):
                 ("pixel_index", C.c_void_p)]
 
 
+class MdRasterOpts(C.Structure):
+    """md_raster_opts (include/mi_depth.h)."""
+    _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("cull", C.c_int), ("max_extent", C.c_int)]
+
+
+class MdRasterOutputs(C.Structure):
+    """md_raster_outputs (include/mi_depth.h)."""
+    _fields_ = [("depth", C.c_void_p), ("face", C.c_void_p), ("rgb", C.c_void_p), ("filled", C.c_void_p), ("skipped", C.c_void_p)]
+
+
+class MdPointsRaster(C.Structure):
+    """md_points_raster (include/mi_depth.h)."""
+    _fields_ = [("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cam", MdPointsCameras), ("opts", MdRasterOpts), ("out", MdRasterOutputs)]
+
+
 class MdViewFilterOpts(C.Structure):
     """md_view_filter_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_percentile", C.c_int),
@@ -214,6 +229,15 @@ SYMBOLS = {
     "md_infer_points_mesh": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
                                   C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
                                   C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh), _I, _P]),
+    "md_raster_opts_default": (None, [C.POINTER(MdRasterOpts)]),
+    "md_op_render_mesh": (_I, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdRasterOpts),
+                               C.POINTER(MdRasterOutputs), _P]),
+    "md_infer_points_raster": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                    C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
+                                    C.POINTER(MdPointsRaster), _I, _P]),
+    "md_raster_inline_pixels": (_I, []),
+    "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
     "md_da3_create": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_uint64, _I, C.POINTER(_P)]),
     "md_da3_load": (_I, [_P, C.POINTER(MdDa3Cfg), C.c_char_p, C.POINTER(_P)]),

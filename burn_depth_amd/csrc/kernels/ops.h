@@ -165,6 +165,39 @@ int launch_mesh_index(int B, int H, int W, const void* points_scratch, int32_t* 
 // classify (skipped on a lattice without quads), scan, scatter (skipped without p.faces); nothing without p.face_count
 int launch_mesh_grid(const MeshParams& p, void* scratch, hipStream_t s);
 
+// ---- mesh rasterisation (kernels/raster.hip; md_op_render_mesh, md_infer_points_raster) ----
+// A vertex list xyz [n,3] (+ u8 rgb [n,3]), faces [nf,3] over its rows and T pinhole target cameras -> per target a z-buffered
+// depth / face / colour image: clear, setup (small faces drawn in place, larger ones queued), large (the queue), resolve. Every
+// pointer is a device pointer. Selection only: nothing depends on the order of arrival.
+struct RasterParams {
+  const float* xyz = nullptr;
+  const uint8_t* rgb = nullptr;       // interpolated to rgb_out
+  const int32_t* faces = nullptr;     // [nf,3] rows of xyz; an index outside 0..n-1 skips the face (tested on the device)
+  const int32_t* count = nullptr;     // one word, read on the device: the live faces are min(max(*count, 0), nf); null: nf faces
+  int n = 0, nf = 0;                  // rows of xyz; faces the setup launch covers
+  int T = 0, H = 0, W = 0;            // targets and their size
+  const float *K = nullptr, *E = nullptr, *focal = nullptr;  // [T,3,3] or [T]; [T,3,4] world-to-camera, null: p = X
+  float off = 0.f, znear = 0.f, zfar = 0.f;                  // znear / zfar already resolved
+  int cull = 0, max_extent = 64;                             // max_extent already resolved: 1..kRasterMaxExtent
+  float* depth = nullptr;      // [T,H,W]
+  int32_t* face = nullptr;     // [T,H,W]
+  uint8_t* rgb_out = nullptr;  // [T,H,W,3]
+  int32_t* filled = nullptr;   // [T + 1]
+  int32_t* skipped = nullptr;  // [T + 1]
+};
+constexpr int kRasterMaxExtent = 1024;
+constexpr int kRasterDefaultExtent = 64;
+// the box size up to which the setup kernel draws a face in its own thread (a compile-time constant of kernels/raster.hip)
+int raster_inline_pixels();
+// md_debug_raster_queue: sets the queue capacity of later calls (0 = the default; negative: no change) -> the previous setting
+int raster_queue_capacity(int capacity);
+// the capacity in force, in (face, target) pairs
+int raster_queue_entries();
+// bytes of keys (8 per pixel) | queue counter | queue (8 per entry); 256-byte aligned parts
+size_t raster_scratch_bytes(int T, int H, int W, int queue_entries);
+// four launches on s (setup and large are skipped when nf == 0); queue_entries: what the scratch was sized for
+int launch_render_mesh(const RasterParams& p, void* scratch, int queue_entries, hipStream_t s);
+
 // a2  bilinear resize, fp32 NCHW (interpolate.rs:54-121). method: MD_INTERP_*.
 // post: 0 none, 1 = 1/clamp(v,1e-4,1e4) (DepthPro::infer tail, mod.rs:356).
 int launch_resize_bilinear(const float* in, int planes, int H, int W, float* out, int OH, int OW, int method,

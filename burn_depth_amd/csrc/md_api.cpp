@@ -541,6 +541,31 @@ int md_infer_points_mesh(md_model_t m, const float* nchw, int B, int H, int W, i
   return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh}, (hipStream_t)stream);
 }
 
+void md_raster_opts_default(md_raster_opts* o) {
+  if (!o) return;
+  o->pixel_offset = 0.f;
+  o->z_near = o->z_far = 0.f;
+  o->cull = 0;
+  o->max_extent = 0;
+}
+
+int md_op_render_mesh(md_device_t dev, const float* xyz_dev, const uint8_t* rgb_dev, int64_t N, const int32_t* faces_dev, int64_t F,
+                      const int32_t* face_count_dev, int T, int H, int W, const md_points_cameras* cam, const md_raster_opts* opts,
+                      const md_raster_outputs* out, void* stream) {
+  return op_render_mesh(dev, PointList{xyz_dev, nullptr, rgb_dev, nullptr, N}, faces_dev, F, face_count_dev, T, H, W, cam, opts, out,
+                        (hipStream_t)stream);
+}
+
+int md_infer_points_raster(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                           const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, const md_points_raster* rst,
+                           int out_kind, void* stream) {
+  return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh, rst}, (hipStream_t)stream);
+}
+
+int md_raster_inline_pixels(void) { return md::raster_inline_pixels(); }
+int md_debug_raster_queue(int capacity) { return capacity < 0 ? MD_ERR_INVALID_ARG : md::raster_queue_capacity(capacity); }
+
 int md_catmull_rom_taps(int in_len, int out_len, int index, int* left, int* count, float* weights) {
   if (!left || !count) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (in_len <= 0 || out_len <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid pass %d -> %d", in_len, out_len);

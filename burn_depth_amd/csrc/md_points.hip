@@ -10,7 +10,9 @@
 // thinned or not, is z-buffered into the caller's target cameras.
 // md_op_mesh_grid / md_op_unproject_mesh / md_infer_points_mesh put the depth-grid mesh (kernels/mesh.hip) directly behind the
 // unprojection: the map pixel -> list row from the scratch the list's launches left, then the faces over the list's rows.
-// The six md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
+// md_op_render_mesh / md_infer_points_raster put the mesh rasterisation (kernels/raster.hip) behind the rendering: the faces of the
+// mesh stage over the list's rows are drawn into the caller's target cameras.
+// The seven md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -37,6 +39,8 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> rkeys;        // md_infer_points_render: the z-buffer keys (render_scratch_bytes)
   md::GrowBuf<void> mesh;         // md_infer_points_mesh: the face scratch (mesh_scratch_bytes) | pixel_index when the caller takes none
   md::GrowBuf<float> rcams;       // the device copy of host target cameras: K [T,9] | E [T,12] | focal [T]
+  md::GrowBuf<void> skeys;        // md_infer_points_raster: the z-buffer keys and the face queue (raster_scratch_bytes)
+  md::GrowBuf<float> scams;       // the device copy of its host target cameras, laid out as rcams
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
@@ -190,6 +194,34 @@ RenderParams make_render(int T, int H, int W, const md_render_opts& o) {
   RenderParams r;
   r.T = T; r.H = H; r.W = W;
   r.off = o.pixel_offset; r.znear = depth_min_of(o.z_near); r.zfar = depth_max_of(o.z_far); r.radius = o.radius;
+  return r;
+}
+
+// the shared part of md_op_render_mesh's and md_infer_points_raster's refusals: check_render's, with the raster's own options
+int check_raster(int T, int H, int W, const md_points_cameras* cam, const md_raster_opts* o, const md_raster_outputs* out, bool has_rgb) {
+  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "raster options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "raster outputs are null");
+  if (!cam) MD_FAIL(MD_ERR_INVALID_ARG, "target cameras are null");
+  if (!out->depth && !out->face && !out->rgb && !out->filled && !out->skipped) MD_FAIL(MD_ERR_INVALID_ARG, "every raster output is null");
+  if (out->rgb && !has_rgb) MD_FAIL(MD_ERR_INVALID_ARG, "a rasterised rgb output needs an rgb row");
+  if (!cam->intrinsics && !cam->focal_px) MD_FAIL(MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras");
+  if (o->cull != 0 && o->cull != 1) MD_FAIL(MD_ERR_INVALID_ARG, "cull %d: 0 or 1", o->cull);
+  if (o->max_extent < 0 || o->max_extent > kRasterMaxExtent) MD_FAIL(MD_ERR_INVALID_ARG, "max_extent %d outside 0..%d", o->max_extent, kRasterMaxExtent);
+  MD_TRY(check_offset(o->pixel_offset));
+  MD_TRY(check_nonneg("z_near", o->z_near));
+  MD_TRY(check_nonneg("z_far", o->z_far));
+  if (o->z_near > 0.f && o->z_far > 0.f && o->z_far < o->z_near) MD_FAIL(MD_ERR_INVALID_ARG, "z_far %g < z_near %g", (double)o->z_far, (double)o->z_near);
+  if (T <= 0 || H <= 0 || W <= 0 || (long)T * H * W >= (1l << 31) || H >= (1 << 24) || W >= (1 << 24))
+    MD_FAIL(MD_ERR_SHAPE, "invalid raster target shape [%d,%d,%d]", T, H, W);
+  return MD_OK;
+}
+
+RasterParams make_raster(int T, int H, int W, const md_raster_opts& o, const md_raster_outputs& out) {
+  RasterParams r;
+  r.T = T; r.H = H; r.W = W;
+  r.off = o.pixel_offset; r.znear = depth_min_of(o.z_near); r.zfar = depth_max_of(o.z_far);
+  r.cull = o.cull; r.max_extent = o.max_extent ? o.max_extent : kRasterDefaultExtent;
+  r.depth = out.depth; r.face = out.face; r.rgb_out = out.rgb; r.filled = out.filled; r.skipped = out.skipped;
   return r;
 }
 
@@ -397,6 +429,25 @@ int op_render_points(md_device_t dev, const PointList& in, const int32_t* count,
   return scratch.finish(launch_render_points(r, scratch.p, st));
 }
 
+int op_render_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const int32_t* face_count, int T, int H, int W,
+                   const md_points_cameras* cam, const md_raster_opts* o, const md_raster_outputs* out, hipStream_t stream) {
+  MD_TRY(check_raster(T, H, W, cam, o, out, in.rgb != nullptr));
+  if (in.N < 0 || in.N >= (1ll << 31)) MD_FAIL(MD_ERR_SHAPE, "rasterising takes 0 .. 2^31 - 1 rows, got %lld", (long long)in.N);
+  if (F < 0 || F >= (1ll << 31)) MD_FAIL(MD_ERR_SHAPE, "rasterising takes 0 .. 2^31 - 1 faces, got %lld", (long long)F);
+  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  RasterParams r = make_raster(T, H, W, *o, *out);
+  r.xyz = in.xyz; r.rgb = in.rgb; r.n = (int)in.N; r.faces = faces; r.nf = (int)F; r.count = face_count;
+  r.K = cam->intrinsics; r.focal = cam->intrinsics ? nullptr : cam->focal_px; r.E = cam->extrinsics;
+  const int entries = raster_queue_entries();
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(raster_scratch_bytes(T, H, W, entries)));
+  return scratch.finish(launch_render_mesh(r, scratch.p, entries, st));
+}
+
 int points_voxel_overflow(md_model_t m, int64_t* out) {
   *out = 0;
   md_model_s::PointsState* f = m->points;
@@ -434,6 +485,8 @@ struct PointsPlan {
   VoxelParams v;    // thin: launch_voxel_thin's, from the model's own list that `p` then fills to the list outputs of the call
   RenderParams r;   // c.rnd given: launch_render_points', from the list outputs of the call
   MeshParams g;     // mesh: launch_mesh's, from the depth that is unprojected and the scratch of `p`'s launches
+  RasterParams s;   // c.rst given: launch_render_mesh's, from the list outputs and the faces of the call
+  int queue = 0;    // its queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   std::vector<OutSlot> slots;
 };
@@ -484,6 +537,15 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, 0);
     slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, 0);
   }
+  if (c.rst) {  // as the rendered images
+    RasterParams& s = pl.s;
+    const size_t spx = (size_t)s.T * s.H * s.W;
+    slot(c.rst->out.depth, s.depth, 4, spx, 0);
+    slot(c.rst->out.face, s.face, 4, spx, 0);
+    slot(c.rst->out.rgb, s.rgb_out, 3, spx, 0);
+    slot(c.rst->out.filled, s.filled, 4, (size_t)s.T + 1, 0);
+    slot(c.rst->out.skipped, s.skipped, 4, (size_t)s.T + 1, 0);
+  }
   if (pl.mesh) {
     slot(c.mesh->pixel_index, pl.pix, 4, pl.npx, 0);
     slot(c.mesh->face_count, pl.g.face_count, 4, (size_t)c.B + 1, 0);
@@ -524,6 +586,12 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
     if (c.in_kind == MD_MEM_HOST) MD_TRY(grow(m, st, f->rcams, (size_t)c.rnd->T * 22 * 4));
   }
+  if (c.rst) {
+    pl.s = make_raster(c.rst->T, c.rst->H, c.rst->W, c.rst->opts, c.rst->out);
+    pl.queue = raster_queue_entries();
+    MD_TRY(grow(m, st, f->skeys, raster_scratch_bytes(c.rst->T, c.rst->H, c.rst->W, pl.queue)));
+    if (c.in_kind == MD_MEM_HOST) MD_TRY(grow(m, st, f->scams, (size_t)c.rst->T * 22 * 4));
+  }
   pl.mesh = mesh_on(c.mesh);
   if (pl.mesh) {
     pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
@@ -562,6 +630,10 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     const md_points_cameras& t = c.rnd->cam;
     pl.r.K = t.intrinsics; pl.r.focal = t.intrinsics ? nullptr : t.focal_px; pl.r.E = t.extrinsics;
   }
+  if (c.rst) {
+    const md_points_cameras& t = c.rst->cam;
+    pl.s.K = t.intrinsics; pl.s.focal = t.intrinsics ? nullptr : t.focal_px; pl.s.E = t.extrinsics;
+  }
   if (c.in_kind != MD_MEM_HOST) return MD_OK;
   MD_TRY(grow(m, pl.st, f->x, pl.npx * 3 * 4));
   if (c.rgb) MD_TRY(grow(m, pl.st, f->rgb, pl.npx * 3));
@@ -581,6 +653,12 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(h2d(pl.r.K, f->rcams.p, T * 36));
     MD_TRY(h2d(pl.r.E, f->rcams.p + T * 9, T * 48));
     MD_TRY(h2d(pl.r.focal, f->rcams.p + T * 21, T * 4));
+  }
+  if (c.rst) {
+    const size_t T = (size_t)c.rst->T;
+    MD_TRY(h2d(pl.s.K, f->scams.p, T * 36));
+    MD_TRY(h2d(pl.s.E, f->scams.p + T * 9, T * 48));
+    MD_TRY(h2d(pl.s.focal, f->scams.p + T * 21, T * 4));
   }
   return MD_OK;
 }
@@ -646,6 +724,19 @@ int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   return launch_render_points(r, m->points->rkeys.p, pl.st);
 }
 
+// Rasterising: the list outputs of the call as vertices, the faces of its mesh stage and their device count -> the target images.
+// The rows beyond min(count[B], capacity) are never named: the mesh stage emits no face with a corner at or above `capacity`.
+int run_raster(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
+  RasterParams& s = pl.s;
+  s.xyz = pl.p.xyz;
+  s.rgb = pl.p.rgb_out;
+  s.n = (int)std::min<long>((long)c.out->capacity, list_rows(c.B, c.H, c.W, c.o->stride));
+  s.faces = pl.g.faces;
+  s.count = pl.g.face_count + c.B;
+  s.nf = (int)std::min<long>((long)c.mesh->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
+  return launch_render_mesh(s, m->points->skeys.p, pl.queue, pl.st);
+}
+
 // Host outputs, complete when the call returns: the depth, the dense maps and the counts first, then, once `count` is known,
 // only the list rows that hold points: the caller's memory beyond them stays as it was.
 int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
@@ -689,6 +780,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (pl.mesh) MD_TRY(timed("points_mesh", run_mesh));
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
+  if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
 }
 
@@ -723,6 +815,11 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (c.rnd) {
     MD_TRY(check_render(c.rnd->T, c.rnd->H, c.rnd->W, &c.rnd->cam, &c.rnd->opts, &c.rnd->out, out->rgb != nullptr));
     if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rendering needs the list outputs `xyz` and `count`");
+  }
+  if (c.rst) {
+    MD_TRY(check_raster(c.rst->T, c.rst->H, c.rst->W, &c.rst->cam, &c.rst->opts, &c.rst->out, out->rgb != nullptr));
+    if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the list outputs `xyz` and `count`");
+    if (!c.mesh || !c.mesh->faces || !c.mesh->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the mesh outputs `faces` and `face_count`");
   }
   if (c.fo) {
     MD_TRY(check_filter(c.fo, s, B, H, W));
@@ -766,6 +863,12 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   }
   if (mesh_on(c.mesh))  // every output null: the key, and the graph, of the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
+  if (c.rst) {
+    const md_points_raster& r = *c.rst;
+    key_add(key, 0x52415354u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px, raster_queue_entries());
+    key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.cull, r.opts.max_extent);
+    key_add(key, r.out.depth, r.out.face, r.out.rgb, r.out.filled, r.out.skipped);
+  }
   return run_with_graph(m, st, key, eligible, body);
 }
 

@@ -88,6 +88,18 @@ class RenderedPoints:
 
 
 @dataclass
+class RasterisedMesh:
+    """What `md_op_render_mesh` / `md_infer_points_raster` return (include/mi_depth.h). Device tensors: depth f32 [T,H,W] (0 at
+    holes), face int32 [T,H,W] (the winning face, -1 at holes), rgb u8 [T,H,W,3] (with an rgb row; affine in screen space), filled
+    int32 [T+1], skipped int32 [T+1] (faces dropped for a box beyond max_extent)."""
+    depth: Optional[torch.Tensor] = None
+    face: Optional[torch.Tensor] = None
+    rgb: Optional[torch.Tensor] = None
+    filled: Optional[torch.Tensor] = None
+    skipped: Optional[torch.Tensor] = None
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -99,7 +111,8 @@ class PointCloud:
     (`md_infer_points_render`): render = the `RenderedPoints` of the list. With `mesh=` (`md_op_unproject_mesh` /
     `md_infer_points_mesh`): faces int32 [face_capacity,3] name rows of xyz, in (view, row, column, triangle) order, of which
     the first min(face_count[B], face_capacity) are faces; face_count int32 [B+1]; pixel_index int32 [B,H,W] is the row of
-    every pixel in the list, -1 where it is not in it. None when not asked for."""
+    every pixel in the list, -1 where it is not in it. With `raster=` (`md_infer_points_raster`): raster = the `RasterisedMesh` of
+    those faces. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -116,6 +129,7 @@ class PointCloud:
     faces: Optional[torch.Tensor] = None
     face_count: Optional[torch.Tensor] = None
     pixel_index: Optional[torch.Tensor] = None
+    raster: Optional["RasterisedMesh"] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -223,6 +237,24 @@ def _render_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal
     return T, cam, o, out, _lib.MdRenderOutputs(_ptr(out.depth), _ptr(out.index), _ptr(out.rgb), _ptr(out.filled)), keep
 
 
+def _raster_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
+                    cull=0, max_extent=0, want_rgb=False, out: Optional[RasterisedMesh] = None):
+    """`_render_request` for a mesh rasterisation -> (T, cameras, md_raster_opts, RasterisedMesh, md_raster_outputs, keep-alive)."""
+    src = intrinsics if intrinsics is not None else focal_px
+    if src is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras")
+    n = src.numel() if isinstance(src, torch.Tensor) else int(np.asarray(src).size)
+    T = max(n // 9 if intrinsics is not None else n, 1)
+    cam, keep = _points_cameras(dev, T, intrinsics, extrinsics, focal_px)
+    if out is None:
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        out = RasterisedMesh(f(T, H, W), f(T, H, W, dt=torch.int32), f(T, H, W, 3, dt=torch.uint8) if want_rgb else None,
+                             f(T + 1, dt=torch.int32), f(T + 1, dt=torch.int32))
+    o = _lib.MdRasterOpts(float(pixel_offset), float(z_near), float(z_far), int(cull), int(max_extent))
+    outs = _lib.MdRasterOutputs(_ptr(out.depth), _ptr(out.face), _ptr(out.rgb), _ptr(out.filled), _ptr(out.skipped))
+    return T, cam, o, out, outs, keep
+
+
 def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
     """md_points_cameras of device fp32 tensors ([B,3,3] / [B,1,3,3], [B,3,4] / [B,1,3,4], [B] or a float). Returns (struct, keep-alive)."""
     keep = []
@@ -246,9 +278,9 @@ def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None
 def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrinsics, focal_px, want_rgb: bool, want_conf: bool,
                     want_depth: bool, dense: bool, compact: bool, capacity: Optional[int], out: Optional[PointCloud], normals: bool,
                     normal_min_cos: float, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
-                    voxel: Optional[float] = None, render: Optional[dict] = None, mesh=None):
+                    voxel: Optional[float] = None, render: Optional[dict] = None, mesh=None, raster: Optional[dict] = None):
     """The keyword set of `infer_points` / `ops.unproject` as the structs of the widest entry -> (cloud, opts, outs, cam, fo, nrm,
-    vox, rnd, msh, keep-alive). fo, nrm, vox, rnd and msh are None for the parts not asked for (an `out` that carries normal,
+    vox, rnd, msh, rst, keep-alive). raster: the keywords of `_raster_request`, as render's. fo, nrm, vox, rnd, msh and rst are None for the parts not asked for (an `out` that carries normal,
     thinning or mesh tensors asks for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless
     `out` is given. mesh: the argument of `_points_mesh`.
     render: the keywords of `_render_request` (H, W, the target cameras, pixel_offset, z_near, z_far, radius); the images go to
@@ -273,7 +305,12 @@ def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrins
     msh = None
     if mesh or res.faces is not None or res.face_count is not None or res.pixel_index is not None:
         msh = _points_mesh(dev, B, H, W, o.stride, mesh, res, out is None)
-    return res, o, outs, cam, fo, nrm, vox, rnd, msh, keep
+    rst = None
+    if raster is not None:
+        T, tcam, so, res.raster, souts, tkeep = _raster_request(dev, **raster, want_rgb=res.rgb is not None, out=res.raster)
+        rst = _lib.MdPointsRaster(T, int(raster["H"]), int(raster["W"]), tcam, so, souts)
+        keep = keep + tkeep
+    return res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, keep
 
 
 @dataclass
@@ -658,13 +695,14 @@ class DepthPro:
     def infer_points(self, x: torch.Tensor, f_px=None, intrinsics=None, extrinsics=None, rgb: Optional[torch.Tensor] = None,
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
-                     normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None, **opts) -> PointCloud:
+                     normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
+                     raster: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        Every form runs through the widest entry, `md_infer_points_mesh`, with NULL for the parts not asked for, which is
-        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` on the same arguments:
+        Every form runs through the widest entry, `md_infer_points_raster`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` on the same arguments:
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
         conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
         before the unprojection; `depth` is then the filtered depth.
@@ -678,7 +716,10 @@ class DepthPro:
         those cameras in the same call; the images come back as `render` (`RenderedPoints`). Needs compact=True.
         mesh (`md_points_mesh`): True, or a dict with any of max_rtol, face_capacity, pixel_index: the triangle mesh of the depth
         grid over the rows of the list, cut where neighbouring depths differ by more than max_rtol of the nearer one; comes back
-        as `faces`, `face_count` and `pixel_index`. Needs compact=True; not with voxel > 0."""
+        as `faces`, `face_count` and `pixel_index`. Needs compact=True; not with voxel > 0.
+        raster (`md_points_raster`): a dict as render's with cull and max_extent in place of radius: the faces of `mesh=` are
+        rasterised into those cameras in the same call, a render without holes; the images come back as `raster`
+        (`RasterisedMesh`). Needs mesh= with faces."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -687,14 +728,14 @@ class DepthPro:
         if rgb is not None:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
         has_conf = bool(getattr(self.config, "dual_head", False))
-        res, o, outs, cam, fo, nrm, vox, rnd, msh, keep = _points_request(
+        res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, keep = _points_request(
             dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
-            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, mesh)
+            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, mesh, raster)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        _lib.check(self._lib.md_infer_points_mesh(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                  C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                  C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), _lib.MD_MEM_DEVICE,
-                                                  _stream_ptr(self.device.ordinal)))
+        _lib.check(self._lib.md_infer_points_raster(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                    C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
+                                                    _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

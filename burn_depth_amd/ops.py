@@ -8,7 +8,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import Device, PointCloud, RenderedPoints, _points_cameras, _points_request, _render_request, _stream_ptr, _view_filter_opts
+from .depth_pro import (Device, PointCloud, RasterisedMesh, RenderedPoints, _points_cameras, _points_request, _raster_request, _render_request,
+                        _stream_ptr, _view_filter_opts)
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -447,7 +448,7 @@ def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None
     conf = _f32c(conf) if conf is not None else None
     rgb = rgb.contiguous() if rgb is not None else None
     assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
-    res, o, outs, cam, _, nrm, _, _, msh, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
+    res, o, outs, cam, _, nrm, _, _, msh, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
                                                               conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos,
                                                               mesh=mesh)
     _lib.check(_lib.load().md_op_unproject_mesh(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
@@ -553,6 +554,37 @@ def mesh_grid(dev: Device, depth: torch.Tensor, pixel_index: torch.Tensor, strid
     _lib.check(_lib.load().md_op_mesh_grid(dev.handle, _p(depth), _p(pixel_index), B, H, W, int(stride), int(vertex_limit), C.byref(msh),
                                            _stream_ptr(dev.ordinal)))
     return faces, face_count
+
+
+def render_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None,
+                rgb: Optional[torch.Tensor] = None, face_count: Optional[torch.Tensor] = None, *, pixel_offset: float = 0.0,
+                z_near: float = 0.0, z_far: float = 0.0, cull: int = 0, max_extent: int = 0,
+                out: Optional[RasterisedMesh] = None) -> RasterisedMesh:
+    """md_op_render_mesh: the faces int32 [F,3] over the rows of xyz [N,3] (+ u8 rgb [N,3]) rasterised into T target cameras
+    (intrinsics [T,3,3] or focal_px [T]; extrinsics [T,3,4] world-to-camera, None = the points are in the camera's frame) ->
+    `RasterisedMesh` of H x W images. face_count: a device int32 tensor whose first word is the number of faces to draw (what
+    `mesh_grid` / `unproject(mesh=)` left in `face_count[-1:]`), read on the device. `out`: a RasterisedMesh to write into again; a
+    None field skips that output. Bit-identical to `pipeline.render_mesh`."""
+    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
+    xyz, faces = _f32c(xyz), faces.contiguous()
+    N, F = int(xyz.shape[0]), int(faces.shape[0])
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if rgb is not None and N == 0:  # an empty tensor has no address: one row that is never read stands for the rgb input
+        rgb = torch.zeros((1, 3), dtype=torch.uint8, device=xyz.device)
+    assert face_count is None or (face_count.is_cuda and face_count.dtype == torch.int32 and face_count.is_contiguous() and face_count.numel() >= 1)
+    T, cam, o, out, outs, keep = _raster_request(xyz.device, int(H), int(W), intrinsics, extrinsics, focal_px, pixel_offset=pixel_offset,
+                                                 z_near=z_near, z_far=z_far, cull=cull, max_extent=max_extent, want_rgb=rgb is not None, out=out)
+    _lib.check(_lib.load().md_op_render_mesh(dev.handle, _p(xyz) if N else None, _p(rgb), N, _p(faces) if F else None, F, _p(face_count), T,
+                                             int(H), int(W), C.byref(cam), C.byref(o), C.byref(outs), _stream_ptr(dev.ordinal)))
+    del keep
+    return out
+
+
+def raster_inline_pixels() -> int:
+    """md_raster_inline_pixels: the largest box, in pixels, that the setup kernel of `render_mesh` draws in the face's own thread."""
+    return int(_lib.load().md_raster_inline_pixels())
 
 
 def fov_to_focal(fovx_deg: float, H: int, W: int) -> Tuple[float, float]:

@@ -18,6 +18,8 @@
   row and the triangle mesh of the depth grid over the list's rows, bit-identical to the device's
 * `render_points`                             -- the host reference of `md_op_render_points` / `md_infer_points_render`: the cloud
   z-buffered into target cameras on 64-bit keys
+* `render_mesh`                               -- the host reference of `md_op_render_mesh` / `md_infer_points_raster`: the faces of the
+  mesh rasterised into target cameras, integer coverage at 1/256 pixel and 64-bit keys
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
   stands in (8-bit grayscale, filter 0), `read_gray_png` reads it back for the tests.
 JPEG decoding stays out of scope: images come in as uint8 arrays."""
@@ -683,6 +685,136 @@ def mesh_grid(depth, pixel_index, stride: int = 1, max_rtol: float = 0.0, vertex
     return tri[emit].astype(np.int32).reshape(-1, 3), count
 
 
+@dataclass
+class HostRaster:
+    depth: np.ndarray                # f32 [T,H,W]: the winner's interpolated z, 0 at holes
+    face: np.ndarray                 # int32 [T,H,W]: the winning face, -1 at holes
+    rgb: Optional[np.ndarray]        # uint8 [T,H,W,3]: the winner's colour, affine in screen space, 0 at holes
+    filled: np.ndarray               # int32 [T+1]: filled pixels per target, then their total
+    skipped: np.ndarray              # int32 [T+1]: faces dropped for a box beyond max_extent per target, then their total
+
+
+def render_mesh(xyz, faces, H, W, intrinsics=None, extrinsics=None, focal_px=None, rgb=None, face_count=None, *, pixel_offset=0.0,
+                z_near=0.0, z_far=0.0, cull=0, max_extent=0) -> HostRaster:
+    """The host reference of md_op_render_mesh / md_infer_points_raster (include/mi_depth.h states the contract, step by step): the
+    faces int [F,3] (the first min(max(face_count, 0), F)) over the rows of xyz [N,3] rasterised into T target cameras (intrinsics
+    [T,3,3] or focal_px [T]; extrinsics [T,3,4] world-to-camera, None = the points are in the camera's frame). The vertices are
+    projected as `render_points` projects, snapped to 1/256 pixel, covered pixels found in int64, their depth from one f64 division
+    and rounded f32 operations; a pixel keeps the smallest key (bits(z) << 32) | face. The colour is affine in screen space. The
+    device kernels (kernels/raster.hip) give the same bits."""
+    T32, I64 = np.float32, np.int64
+    p = np.ascontiguousarray(xyz, dtype=T32).reshape(-1, 3)
+    fc = np.asarray(faces).reshape(-1, 3).astype(I64)
+    N, F = len(p), len(fc)
+    H, W, max_extent = int(H), int(W), int(max_extent)
+    if intrinsics is not None:
+        K = np.asarray(intrinsics, dtype=T32).reshape(-1, 3, 3)
+        fx, fy, cx, cy = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    elif focal_px is not None:
+        fx = fy = np.asarray(focal_px, dtype=T32).reshape(-1)
+        cx, cy = np.full(len(fx), T32(W) / T32(2), T32), np.full(len(fx), T32(H) / T32(2), T32)
+    else:
+        raise ValueError("neither intrinsics nor a focal length")
+    T = len(fx)
+    E = None if extrinsics is None else np.asarray(extrinsics, dtype=T32).reshape(T, 3, 4)
+    if T <= 0 or H <= 0 or W <= 0 or T * H * W >= 1 << 31 or H >= 1 << 24 or W >= 1 << 24 or N >= 1 << 31 or F >= 1 << 31:
+        raise ValueError("invalid shape")
+    if cull not in (0, 1):
+        raise ValueError("cull is 0 or 1")
+    if not 0 <= max_extent <= 1024:
+        raise ValueError("max_extent outside 0..1024")
+    if not all(np.isfinite(v) for v in (pixel_offset, z_near, z_far)) or z_near < 0 or z_far < 0 or (z_near > 0 and 0 < z_far < z_near):
+        raise ValueError("pixel_offset and the bounds must be finite, the bounds >= 0 and z_far >= z_near")
+    extent = max_extent or 64
+    f32i = np.finfo(np.float32)
+    zn = T32(z_near) if z_near > 0 else T32(f32i.tiny)
+    zf = T32(z_far) if z_far > 0 else T32(f32i.max)
+    n = F if face_count is None else min(max(int(face_count), 0), F)
+    fc = fc[:n]
+    off, half, sub, one, guard = T32(pixel_offset), T32(0.5), T32(256), T32(1), T32(16777216)
+    empty = np.uint64(0xFFFFFFFFFFFFFFFF)
+    keys = np.full((T, H * W), empty, np.uint64)
+    skipped = np.zeros(T + 1, np.int64)
+    col = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.uint8).reshape(N, 3)
+    setups = []
+
+    def weights(X, Y, sign, px, py):  # step 6: int64 [m] each
+        e = lambda a, b: (X[:, b] - X[:, a]) * (py - Y[:, a]) - (Y[:, b] - Y[:, a]) * (px - X[:, a])  # noqa: E731
+        return sign * e(1, 2), sign * e(2, 0), sign * e(0, 1)
+
+    with np.errstate(all="ignore"):
+        inside = ((fc >= 0) & (fc < N)).all(1)                                  # step 1
+        rows = np.where(inside[:, None], fc, 0)
+        v = p[rows] if N else np.zeros((n, 3, 3), T32)                          # [n, vertex, xyz]
+        ok0 = inside & np.isfinite(v).all((1, 2))
+        x, y, z = v[..., 0], v[..., 1], v[..., 2]
+        for j in range(T):
+            if E is None:                                                       # step 2
+                px, py, pz = x, y, z
+            else:
+                px, py, pz = [((E[j, a, 0] * x + E[j, a, 1] * y) + E[j, a, 2] * z) + E[j, a, 3] for a in range(3)]
+            ok = ok0 & (np.isfinite(pz) & (pz >= zn) & (pz <= zf)).all(1)
+            uf = ((fx[j] * (px / pz)) + cx[j]) - off
+            vf = ((fy[j] * (py / pz)) + cy[j]) - off
+            sx, sy = np.floor(uf * sub + half), np.floor(vf * sub + half)        # step 3
+            ok &= ((np.abs(sx) < guard) & (np.abs(sy) < guard)).all(1)
+            X, Y = np.where(ok[:, None], sx, 0).astype(I64), np.where(ok[:, None], sy, 0).astype(I64)
+            iz = one / np.where(ok[:, None], pz, one).astype(T32)
+            A = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])  # step 4
+            ok &= A != 0
+            if cull:
+                ok &= A < 0
+            sign = np.where(A < 0, -1, 1).astype(I64)
+            A = A * sign
+            u0, u1 = np.maximum(0, (X.min(1) + 255) >> 8), np.minimum(W - 1, X.max(1) >> 8)  # step 5
+            v0, v1 = np.maximum(0, (Y.min(1) + 255) >> 8), np.minimum(H - 1, Y.max(1) >> 8)
+            bw, bh = u1 - u0 + 1, v1 - v0 + 1
+            ok &= (bw > 0) & (bh > 0)
+            big = ok & ((bw > extent) | (bh > extent))
+            skipped[j] = big.sum()
+            ok &= ~big
+            setups.append((X, Y, sign, A, iz))
+            d = np.nonzero(ok)[0]
+            if not len(d):
+                continue
+            for dv in range(int(bh[d].max())):
+                for du in range(int(bw[d].max())):
+                    s = d[(dv < bh[d]) & (du < bw[d])]
+                    if not len(s):
+                        continue
+                    pu, pv = u0[s] + du, v0[s] + dv
+                    w0, w1, w2 = weights(X[s], Y[s], sign[s], 256 * pu, 256 * pv)
+                    cov = (w0 >= 0) & (w1 >= 0) & (w2 >= 0)
+                    a = A[s].astype(np.float64)
+                    b0, b1, b2 = [(w.astype(np.float64) / a).astype(T32) for w in (w0, w1, w2)]   # step 7
+                    zi = (b0 * iz[s, 0] + b1 * iz[s, 1]) + b2 * iz[s, 2]
+                    zz = (one / zi).astype(T32)
+                    cov &= np.isfinite(zz) & (zz >= zn) & (zz <= zf)
+                    key = (np.ascontiguousarray(zz[cov]).view(np.uint32).astype(np.uint64) << np.uint64(32)) | s[cov].astype(np.uint64)
+                    np.minimum.at(keys[j], pv[cov] * W + pu[cov], key)                           # step 8
+        skipped[T] = skipped[:T].sum()
+        keys = keys.reshape(T, H, W)
+        hit = keys != empty
+        depth = np.where(hit, (keys >> np.uint64(32)).astype(np.uint32).view(T32), T32(0)).astype(T32)
+        face = np.where(hit, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+        color = None
+        if col is not None:
+            color = np.zeros((T, H, W, 3), np.uint8)
+            for j in range(T):
+                pv, pu = np.nonzero(hit[j])
+                if not len(pv):
+                    continue
+                s = face[j][pv, pu].astype(I64)
+                X, Y, sign, A, _ = setups[j]
+                w = weights(X[s], Y[s], sign[s], 256 * pu.astype(I64), 256 * pv.astype(I64))
+                a = A[s].astype(np.float64)
+                b0, b1, b2 = [(k.astype(np.float64) / a).astype(T32)[:, None] for k in w]
+                c0, c1, c2 = [col[fc[s, k]].astype(T32) for k in range(3)]
+                color[j][pv, pu] = np.minimum(np.floor(((b0 * c0 + b1 * c1) + b2 * c2) + half), T32(255)).astype(np.uint8)
+    filled = np.concatenate([hit.reshape(T, -1).sum(1), [hit.sum()]]).astype(np.int32)
+    return HostRaster(depth, face, color, filled, skipped.astype(np.int32))
+
+
 def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None,
               faces: Optional[np.ndarray] = None) -> None:
     """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar; with `faces` int [F,3]
@@ -820,7 +952,7 @@ class AnyDepthModel:
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
-        render= (`md_infer_points_render`) and mesh= (`md_infer_points_mesh`) included."""
+        render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`) and raster= (`md_infer_points_raster`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

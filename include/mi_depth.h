@@ -588,6 +588,95 @@ int md_infer_points_mesh(md_model_t m, const float* nchw, int B, int H, int W, i
                          const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, int out_kind,
                          void* stream);
 
+/* ---- point path: rasterise the mesh into target cameras ---------------------------------------------------------------------
+ * A render without holes: the faces md_op_mesh_grid / md_infer_points_mesh wrote over the list are drawn into T target cameras
+ * (md_points_cameras with T in place of B, as md_op_render_points takes them; extrinsics NULL = the points are already in the
+ * camera's frame). Inputs: xyz f32 [N,3], faces int32 [F,3] (rows of xyz), optionally rgb u8 [N,3] and a device face-count
+ * word: the live faces are n = min(max(*count, 0), F), which is face_count[B] of the mesh stage read without a host round
+ * trip. Selection, not blending: a pixel shows one face, chosen by the minimum of a 64-bit key, so nothing depends on the order
+ * in which threads arrive. Per face f < n and target j (pipeline.render_mesh restates every step bit for bit):
+ *   1 indices: the face is skipped when a vertex row lies outside 0..N-1 (tested on the device: a bad index never becomes a
+ *     read) or a vertex coordinate is not finite.
+ *   2 projection, md_op_render_points' step for step, for each vertex: p = ((Rk0 x + Rk1 y) + Rk2 z) + tk (extrinsics NULL:
+ *     p = X); the vertex is visible when p.z is finite and z_near <= p.z <= z_far (0 = the default of that bound, resolved as
+ *     md_render_opts does); uf = ((fx (p.x / p.z)) + cx) - off, vf likewise. All three vertices must be visible: there is no
+ *     near-plane clipping, a triangle that crosses a bound is dropped.
+ *   3 snap to 1/256 pixel: sx = floorf(uf * 256.f + 0.5f), sy likewise; the face is skipped unless fabsf(sx) < 16777216.f and
+ *     fabsf(sy) < 16777216.f for all three vertices, compared in float before any conversion (a NaN or an infinity fails);
+ *     then X = (int64)sx, Y = (int64)sy. From here coverage is integer arithmetic.
+ *   4 area: A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) in int64. A == 0: skipped. cull = 1: a face with A > 0 is skipped (with x
+ *     right and y down the faces md_op_mesh_grid emits have A < 0 in their own camera). For A < 0 the three weights of step 6
+ *     and A are negated.
+ *   5 bounding box in ints, clipped to the image: u0 = max(0, (min X + 255) >> 8), u1 = min(W-1, max X >> 8) (arithmetic
+ *     shifts), v0, v1 likewise. An empty box: skipped. A box wider or taller than max_extent pixels: skipped and counted in
+ *     skipped[j] and skipped[T]. The cap is part of the contract: it bounds the work one face can cause, and it drops the
+ *     rubber sheets a stretched depth edge makes.
+ *   6 coverage of pixel (u, v) of the box, P = (256 u, 256 v): w0 = edge(V1,V2,P), w1 = edge(V2,V0,P), w2 = edge(V0,V1,P) with
+ *     edge(a,b,P) = (bx-ax)(Py-ay) - (by-ay)(Px-ax); covered when all three are >= 0. The test is inclusive on every edge: two
+ *     faces that share an edge compute the same integers with opposite signs, so no pixel falls between them; a pixel on the
+ *     edge belongs to both and the key decides.
+ *   7 depth: b_i = (float)((double)w_i / (double)A) (the ints are below 2^51, so exact in f64: one f64 division, one rounding
+ *     to f32); iz = (b0 * (1.f/z0) + b1 * (1.f/z1)) + b2 * (1.f/z2) with z_i = p.z of vertex i; z = 1.f / iz. The candidate
+ *     is dropped unless z is finite and z_near <= z <= z_far, which makes the bit order of z its value order.
+ *   8 key: ((uint64)bits(z) << 32) | (uint32)f; the pixel keeps the minimum: the nearest face, among equal z the smallest
+ *     face. All ones marks an empty pixel.
+ * Outputs: depth = the winner's z, 0 at holes; face = the winner, -1 at holes; rgb channel = fminf(floorf(((b0 c0 + b1 c1)
+ * + b2 c2) + 0.5f), 255.f) with the b's of the winning face recomputed at that pixel and c_i the channel of vertex i as f32,
+ * 0 at holes: the colour is affine in screen space, not perspective-correct; filled[j] = the pixels of target j that are no
+ * holes, filled[T] their total; skipped[j] = the faces step 5 dropped for their extent, skipped[T] their total.
+ * Device memory: 8 bytes per pixel of keys and a fixed queue of (face, target) pairs for the faces with larger boxes; a full
+ * queue changes the schedule, never the image. */
+typedef struct md_raster_opts {
+  float pixel_offset;  /* as md_points_opts */
+  float z_near, z_far; /* bounds of p.z and of the interpolated z; 0 = the default of that bound, as md_render_opts */
+  int cull;            /* 0: both sides are drawn; 1: only the winding md_op_mesh_grid emits (A < 0) */
+  int max_extent;      /* 0 = 64; 1..1024: a face whose clipped box is wider or taller is skipped and counted */
+} md_raster_opts;
+typedef struct md_raster_outputs {
+  float* depth;     /* f32 [T,H,W]; NULL = skip */
+  int32_t* face;    /* int32 [T,H,W]; NULL = skip */
+  uint8_t* rgb;     /* u8 [T,H,W,3]; needs the rgb row. NULL = skip */
+  int32_t* filled;  /* int32 [T+1]; NULL = skip */
+  int32_t* skipped; /* int32 [T+1]; NULL = skip */
+} md_raster_outputs;
+typedef struct md_points_raster { /* the rasterising part of md_infer_points_raster */
+  int T, H, W;                    /* target cameras and their image size */
+  md_points_cameras cam;          /* [T, ..] pointers of in_kind */
+  md_raster_opts opts;
+  md_raster_outputs out;          /* pointers of out_kind; rgb needs the list output out->rgb */
+} md_points_raster;
+
+/* everything 0: integer grid, default bounds, both sides, max_extent 64 */
+void md_raster_opts_default(md_raster_opts* o);
+/* The stand-alone operator on caller device tensors (cameras included); rgb_dev and face_count_dev may be NULL. Everything is
+ * enqueued on `stream`; the call returns after the stream has drained, because its scratch is freed on return. F = 0 is
+ * legal: every pixel is a hole. Errors, before any launch (the outputs stay untouched): dev / opts / out / cam NULL, every
+ * output NULL, an rgb output without rgb_dev, xyz_dev NULL with N > 0, faces_dev NULL with F > 0, neither intrinsics nor
+ * focal_px, cull not 0 or 1, max_extent < 0 or > 1024, pixel_offset or a bound not finite, a bound negative, z_far < z_near
+ * (both given) -> MD_ERR_INVALID_ARG; N or F < 0 or >= 2^31, T, H, W <= 0, T*H*W >= 2^31, H or W >= 2^24 -> MD_ERR_SHAPE. */
+int md_op_render_mesh(md_device_t dev, const float* xyz_dev, const uint8_t* rgb_dev, int64_t N, const int32_t* faces_dev, int64_t F,
+                      const int32_t* face_count_dev, int T, int H, int W, const md_points_cameras* cam, const md_raster_opts* opts,
+                      const md_raster_outputs* out, void* stream);
+/* md_infer_points_mesh with the rasterising behind the rendering: the faces of the mesh stage (their first
+ * min(face_count[B], face_capacity), read from the device count) over the list's xyz / rgb are drawn into rst's targets in the
+ * same call and graph. The keys, the queue and, for host cameras, their device copies live in grow-only buffers of the model.
+ * rst NULL: md_infer_points_mesh on the same arguments, the same launches and bits. The graph key contains rst's fields.
+ * Errors as md_infer_points_mesh's and md_op_render_mesh's, plus: rst without the list outputs out->xyz and out->count or
+ * without mesh->faces and mesh->face_count, rst->out.rgb without out->rgb -> MD_ERR_INVALID_ARG (voxel thinning already
+ * excludes the mesh). After the first call of a shape nothing is allocated. */
+int md_infer_points_raster(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                           const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                           const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                           const md_points_raster* rst, int out_kind, void* stream);
+/* The largest clipped box, in pixels, that the setup kernel draws in the face's own thread; a larger one goes through the
+ * queue (a compile-time constant of kernels/raster.hip). The image does not depend on it. */
+int md_raster_inline_pixels(void);
+/* PROCESS-WIDE (returns the previous setting): the capacity of the (face, target) queue of later md_op_render_mesh /
+ * md_infer_points_raster calls, 0 = the default (2^20 pairs). A push that finds the queue full draws the face in place: same
+ * bits at every capacity; for the test of that branch. MD_ERR_INVALID_ARG (< 0) for a negative capacity. */
+int md_debug_raster_queue(int capacity);
+
 /* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

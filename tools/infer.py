@@ -35,6 +35,11 @@ Pro image `--focal-px`).
 cut where neighbouring depths differ by more than X of the nearer one (default 0.05; 0 = no cut), computed on the device
 (`md_infer_points_mesh`; with `--views`, `ops.unproject(mesh=)`: one mesh per view, not merged). Not together with `--voxel`.
 
+`--raster-pose E.npy --raster-out view.png` (with `--ply --mesh`): the mesh is also rasterised on the device into a virtual camera with
+the world-to-camera pose E ([3,4], or [T,3,4] of which every pose is drawn and the first written), a render without holes, and its
+depth image written as a normalised PNG (`md_infer_points_raster`; with `--views`, `ops.render_mesh` on the meshes of all views).
+`--render-size` and `--render-intrinsics` apply to it as to `--render-pose`.
+
 `--image`: uint8 RGB [H,W,3] as .npy (JPEG decoding is out of scope). Depth-Anything-v3 inputs are resized on the
 shortest side (Catmull-Rom) and centre-cropped to the model resolution (src/model/mod.rs:162-210); the depth map is
 restored to the original size, min-max normalised and written as an 8-bit PNG (example/inference.rs:103-199)."""
@@ -65,11 +70,19 @@ def render_request(a, h, w, K=None, focal=None):
     return dict(H=int(H), W=int(W), intrinsics=np.broadcast_to(K, (len(E), 3, 3)).copy(), extrinsics=E, radius=a.render_radius), None
 
 
-def write_render(a, P, r) -> None:
+def write_render(a, P, r, path=None) -> None:
     import torch
     torch.cuda.synchronize()
-    P.save_depth_map(r.depth[:1].cpu().numpy(), a.render_out, None, None)
-    print(f"Rendered {int(r.filled[0])} pixels of the first pose to {a.render_out}")
+    P.save_depth_map(r.depth[:1].cpu().numpy(), path or a.render_out, None, None)
+    print(f"Rendered {int(r.filled[0])} pixels of the first pose to {path or a.render_out}")
+
+
+def raster_request(a, h, w, K=None, focal=None):
+    """--raster-pose: `render_request` on its pose file, without the point footprint"""
+    req, why = render_request(argparse.Namespace(**dict(vars(a), render_pose=a.raster_pose)), h, w, K=K, focal=focal)
+    if req:
+        del req["radius"]
+    return req, why
 
 
 def run_views(a) -> int:
@@ -144,6 +157,20 @@ def run_views(a) -> int:
             except _lib.MdError as e:
                 print(str(e), file=sys.stderr)
                 return 1
+        if a.raster_pose:
+            req, why = raster_request(a, preps[0].height, preps[0].width, K=K[0].cpu().numpy())
+            if why:
+                print(why, file=sys.stderr)
+                return 2
+            if a.voxel > 0:
+                print("--raster-pose with --views takes no --voxel (the faces name rows of the unthinned list)", file=sys.stderr)
+                return 2
+            try:
+                r = ops.render_mesh(dev, pc.xyz, pc.faces, req.pop("H"), req.pop("W"), rgb=pc.rgb, face_count=pc.face_count[-1:], **req)
+                write_render(a, P, r, a.raster_out)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
     return 0
 
 
@@ -177,7 +204,12 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh", action="store_true", help="--ply: also write the triangle mesh of the depth grid over the points (md_infer_points_mesh)")
     ap.add_argument("--mesh-rtol", type=float, default=0.05,
                     help="--mesh: cut an edge whose depths differ by more than this fraction of the nearer one (0 = no cut)")
+    ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
+    ap.add_argument("--raster-out", default="", help="--raster-pose: the rasterised depth of the first pose as a normalised PNG")
     a = ap.parse_args(argv)
+    if bool(a.raster_pose) != bool(a.raster_out) or (a.raster_pose and not (a.ply and a.mesh)):
+        print("--raster-pose and --raster-out go together, and with --ply --mesh", file=sys.stderr)
+        return 2
     if a.mesh and (not a.ply or a.voxel > 0):
         print("--mesh goes with --ply, and not with --voxel (a thinned list has no grid)", file=sys.stderr)
         return 2
@@ -226,12 +258,18 @@ def main(argv=None) -> int:
             if why:
                 print(why, file=sys.stderr)
                 return 2
+        raster = None
+        if a.raster_pose:
+            raster, why = raster_request(a, prep.height, prep.width, focal=a.focal_px)
+            if why:
+                print(why, file=sys.stderr)
+                return 2
         try:
             pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
                                     dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
                                     world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
                                     normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render,
-                                    mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None)
+                                    mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None, raster=raster)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
@@ -241,6 +279,8 @@ def main(argv=None) -> int:
         print(f"Model `{kind.value}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} to {a.ply}")
         if render is not None:
             write_render(a, P, pc.render)
+        if raster is not None:
+            write_render(a, P, pc.raster, a.raster_out)
         if not a.output:
             return 0
     oh, ow = rgb.shape[:2]
