@@ -119,6 +119,44 @@ size_t voxel_scratch_bytes(int n);
 // five launches on s. flags (device, inside the scratch): voxel_flags(scratch, n)[0] != 0 after the launches = the probe loop ran out
 int launch_voxel_thin(const VoxelParams& p, void* scratch, hipStream_t s);
 const int32_t* voxel_flags(const void* scratch, int n);
+// the tail of launch_voxel_thin, for any keep decision in its ballot layout (row = tile * 4096 + step * 256 + thread, word =
+// step * 4 + wave; counts[tile] = the set bits of the tile): scan (offsets, p.count per view) and scatter (the rows, p.index;
+// p.weight from cnt[slot[i]], both may be null without it). Nothing is launched without p.count; counts only without a row output.
+int launch_list_compact(const VoxelParams& p, const unsigned* cnt, const int* slot, const unsigned long long* bits, const int* counts,
+                        int* offsets, hipStream_t s);
+
+// ---- radius outlier removal (kernels/outlier.hip; md_op_radius_outliers, md_infer_points_outlier) ----
+// A point list xyz [n,3] (+ conf, rgb, normals rows) -> the rows with at least k other rows within `radius`, in ascending input
+// index: reset, insert (voxel thinning's table with a count per slot), bucket allocation, fill (the positions bucket by
+// bucket), search (27 cells around the row's, saturating at k; ballot words), then launch_list_compact. Every pointer is a
+// device pointer. Selection only: integer counts of an f32 predicate, nothing depends on the order of arrival.
+struct OutlierParams {
+  const float* xyz = nullptr;
+  const float* conf = nullptr;        // carried to conf_out
+  const uint8_t* rgb = nullptr;       // carried to rgb_out
+  const float* normals = nullptr;     // carried to normals_out
+  const int32_t* in_count = nullptr;  // as VoxelParams::in_count
+  int n = 0;                          // rows the launches cover: the live count is min(in_count[B], n)
+  int B = 1;
+  float radius = 0.f;
+  int k = 1;                          // min_neighbours
+  float* xyz_out = nullptr;
+  float* conf_out = nullptr;
+  uint8_t* rgb_out = nullptr;
+  float* normals_out = nullptr;
+  int32_t* index = nullptr;       // [capacity] source row
+  int32_t* neighbours = nullptr;  // [n] min(neighbours, k) of every live input row, -1 out of range
+  int32_t* count = nullptr;       // [B + 1] survivors per view, then their total
+  int32_t* dropped = nullptr;     // [1] rows that are not finite or out of range
+  long capacity = 0;
+};
+constexpr int kOutlierMaxNeighbours = 1 << 20;
+// bytes of the scratch (table 20 B per slot | slot and bucket position of every row | buckets 12 n | ballot words | block counts |
+// block offsets | flags)
+size_t outlier_scratch_bytes(int n);
+// flags[0] != 0 after the launches = a probe loop ran out of table
+int launch_radius_outliers(const OutlierParams& p, void* scratch, hipStream_t s);
+const int32_t* outlier_flags(const void* scratch, int n);
 
 // ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
 // A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour

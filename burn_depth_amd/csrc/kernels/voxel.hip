@@ -17,18 +17,15 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ops.h"
+#include "voxel_math.h"
 
 namespace md {
 
 namespace {
 
-constexpr int kThreads = 256;             // 4 waves of 64
-constexpr int kSteps = 16;                // rows per thread in select / scatter
-constexpr int kTile = kThreads * kSteps;  // 4096 rows per workgroup
-constexpr int kWords = kTile / 64;        // 64 ballot words per workgroup
-constexpr unsigned long long kEmpty = ~0ull;
-constexpr float kHalfGrid = 1048576.f;    // 2^20 cells on either side of the origin, 21 bits per axis
+// the tile layout, the cell key and the probe are shared with the outlier removal (voxel_math.h)
+constexpr int kThreads = kGridThreads, kSteps = kGridSteps, kTile = kGridTile, kWords = kGridWords;
+constexpr unsigned long long kEmpty = kGridEmpty;
 
 struct VoxelScratch {  // the parts of the scratch buffer, 256-byte aligned
   unsigned long long* keys;
@@ -73,14 +70,6 @@ __device__ __forceinline__ int live_rows(const VoxelParams& p) {
   return t < 0 ? 0 : (t < p.n ? t : p.n);
 }
 
-// splitmix64's finaliser: spreads neighbouring cells over the table. It decides where a key lives, never which row survives.
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-
 // slots is a multiple of 1024: every thread writes four slots with 16-byte stores
 __global__ void __launch_bounds__(kThreads) voxel_reset_kernel(ulonglong2* __restrict__ keys, ulonglong2* __restrict__ rank,
                                                                uint4* __restrict__ cnt, size_t quads, int* __restrict__ flags,
@@ -107,9 +96,8 @@ __global__ void __launch_bounds__(kThreads) voxel_insert_kernel(VoxelParams p, u
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= live_rows(p)) return;
   const float x = p.xyz[i * 3], y = p.xyz[i * 3 + 1], z = p.xyz[i * 3 + 2];
-  const float cx = floorf(x / p.voxel), cy = floorf(y / p.voxel), cz = floorf(z / p.voxel);
-  const bool in_range = isfinite(x) && isfinite(y) && isfinite(z) && cx >= -kHalfGrid && cx < kHalfGrid && cy >= -kHalfGrid &&
-                        cy < kHalfGrid && cz >= -kHalfGrid && cz < kHalfGrid;
+  unsigned long long key = 0ull;
+  const bool in_range = grid_cell_key(x, y, z, p.voxel, &key);
   const unsigned long long out_of_range = __ballot(!in_range);  // the lanes of the wave that are still here
   if (out_of_range && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1))
     atomicAdd(p.dropped ? p.dropped : flags + 1, (int)__popcll(out_of_range));
@@ -117,8 +105,6 @@ __global__ void __launch_bounds__(kThreads) voxel_insert_kernel(VoxelParams p, u
     slot[i] = -1;
     return;
   }
-  const unsigned long long key = ((unsigned long long)((int)cx + 1048576) << 42) | ((unsigned long long)((int)cy + 1048576) << 21) |
-                                 (unsigned long long)((int)cz + 1048576);
   unsigned wbits = 0u;
   if (p.conf) {
     const float c = p.conf[i];
@@ -126,20 +112,15 @@ __global__ void __launch_bounds__(kThreads) voxel_insert_kernel(VoxelParams p, u
     if (wbits == 0x80000000u) wbits = 0u;  // -0 counts as +0
   }
   const unsigned long long word = ((unsigned long long)wbits << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
-  unsigned long long h = mix64(key) & mask;
-  for (unsigned long long probe = 0; probe <= mask; ++probe) {
-    unsigned long long cur = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEmpty) cur = atomicCAS(keys + h, kEmpty, key);  // returns what was there: all ones = this thread claimed the slot
-    if (cur == kEmpty || cur == key) {
-      atomicMax(rank + h, word);
-      atomicAdd(cnt + h, 1u);
-      slot[i] = (int)h;
-      return;
-    }
-    h = (h + 1) & mask;
+  const long h = grid_claim(keys, mask, key);
+  if (h < 0) {
+    flags[0] = 1;  // every slot holds another key: cannot happen at load <= 0.5
+    slot[i] = -1;
+    return;
   }
-  flags[0] = 1;  // every slot holds another key: cannot happen at load <= 0.5
-  slot[i] = -1;
+  atomicMax(rank + h, word);
+  atomicAdd(cnt + h, 1u);
+  slot[i] = (int)h;
 }
 
 // grid tiles. A row is kept when its slot's rank word names it.
@@ -296,11 +277,17 @@ int launch_voxel_thin(const VoxelParams& p, void* scratch, hipStream_t s) {
     hipLaunchKernelGGL(voxel_select_kernel, dim3(nb), dim3(kThreads), 0, s, p, v.rank, v.slot, v.bits, v.counts);
     MD_HIP(hipGetLastError());
   }
+  return launch_list_compact(p, v.cnt, v.slot, v.bits, v.counts, v.offsets, s);
+}
+
+int launch_list_compact(const VoxelParams& p, const unsigned* cnt, const int* slot, const unsigned long long* bits, const int* counts,
+                        int* offsets, hipStream_t s) {
+  const int nb = tiles_of(p.n);
   if (!p.count) return MD_OK;  // dropped only
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(kThreads), 0, s, p, v.counts, nb, v.bits, v.offsets);
+  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(kThreads), 0, s, p, counts, nb, bits, offsets);
   MD_HIP(hipGetLastError());
   if (p.n == 0 || (!p.xyz_out && !p.conf_out && !p.rgb_out && !p.normals_out && !p.index && !p.weight)) return MD_OK;  // counts only
-  hipLaunchKernelGGL(voxel_scatter_kernel, dim3(nb), dim3(kThreads), 0, s, p, v.cnt, v.slot, v.bits, v.offsets);
+  hipLaunchKernelGGL(voxel_scatter_kernel, dim3(nb), dim3(kThreads), 0, s, p, cnt, slot, bits, offsets);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

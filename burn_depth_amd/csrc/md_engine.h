@@ -370,7 +370,7 @@ struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], c
   const float* normals = nullptr;
   int64_t N = 0;
 };
-// One md_infer_points* request: what the widest entry (md_infer_points_raster) takes. A narrower entry leaves the parts it lacks
+// One md_infer_points* request: what the widest entry (md_infer_points_outlier) takes. A narrower entry leaves the parts it lacks
 // null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
 struct PointsCall {
   const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
@@ -388,6 +388,7 @@ struct PointsCall {
   const md_points_render* rnd = nullptr;  // given: the list the call ends with is rendered into its targets (cameras of in_kind)
   const md_points_mesh* mesh = nullptr;   // given: the faces of the depth grid over the list's rows (pointers of out_kind)
   const md_points_raster* rst = nullptr;  // given: those faces are rasterised into its targets (cameras of in_kind)
+  const md_points_outlier* outl = nullptr;  // given: radius outlier removal between the unprojection and the thinning (pointers of out_kind)
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
@@ -398,6 +399,8 @@ int op_mesh_grid(md_device_t dev, const DepthMaps& in, const int32_t* pixel_inde
 int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream);
 int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* vox, const md_points_outputs* out, float* normals_out,
                   hipStream_t stream);
+int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_outlier* outl, const md_points_outputs* out, float* normals_out,
+                       hipStream_t stream);
 // in.xyz / in.rgb: the list; count: its device count word or null
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream);
@@ -406,6 +409,8 @@ int op_render_mesh(md_device_t dev, const PointList& in, const int32_t* faces, i
                    const md_points_cameras* cam, const md_raster_opts* o, const md_raster_outputs* out, hipStream_t stream);
 // the probe-loop flag of the model's last md_infer_points_voxel (waits for its stream); 0 when it never ran
 int points_voxel_overflow(md_model_t m, int64_t* out);
+// likewise for the outlier removal of the model's last md_infer_points_outlier
+int points_outlier_overflow(md_model_t m, int64_t* out);
 int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_view_filter_opts* o,
                     const md_view_filter_outputs* out, hipStream_t stream);
 void points_destroy_state(md_model_t m);

@@ -12,7 +12,9 @@
 // unprojection: the map pixel -> list row from the scratch the list's launches left, then the faces over the list's rows.
 // md_op_render_mesh / md_infer_points_raster put the mesh rasterisation (kernels/raster.hip) behind the rendering: the faces of the
 // mesh stage over the list's rows are drawn into the caller's target cameras.
-// The seven md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
+// md_op_radius_outliers / md_infer_points_outlier put the radius outlier removal (kernels/outlier.hip) between the scatter and the
+// thinning: the scatter fills a list of the model's own, the filter writes the caller's, or with thinning a second list of the model's.
+// The eight md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -36,12 +38,15 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> out;          // device homes of host outputs
   md::GrowBuf<void> vlist;        // md_infer_points_voxel: the unthinned list (xyz | conf | rgb | normals | count)
   md::GrowBuf<void> vtable;       // its hash table and compaction scratch (voxel_scratch_bytes)
+  md::GrowBuf<void> flist;        // md_infer_points_outlier with thinning: the filtered list, laid out as vlist (without it vlist holds the unfiltered one)
+  md::GrowBuf<void> otable;       // its table, buckets and ballot words (outlier_scratch_bytes)
   md::GrowBuf<void> rkeys;        // md_infer_points_render: the z-buffer keys (render_scratch_bytes)
   md::GrowBuf<void> mesh;         // md_infer_points_mesh: the face scratch (mesh_scratch_bytes) | pixel_index when the caller takes none
   md::GrowBuf<float> rcams;       // the device copy of host target cameras: K [T,9] | E [T,12] | focal [T]
   md::GrowBuf<void> skeys;        // md_infer_points_raster: the z-buffer keys and the face queue (raster_scratch_bytes)
   md::GrowBuf<float> scams;       // the device copy of its host target cameras, laid out as rcams
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
+  int outl_rows = 0;              // likewise for the outlier removal and otable
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
   float* f_home(int B) const { return cams.p + (size_t)B * 21; }
@@ -169,6 +174,24 @@ int check_voxel(const md_points_voxel* vox, const md_points_outputs* out, bool o
   MD_TRY(need_count(vox->index || vox->weight, out, "index / weight"));
   if (vox->voxel == 0.f && (vox->index || vox->weight || vox->dropped))
     MD_FAIL(MD_ERR_INVALID_ARG, "index / weight / dropped without a voxel size");
+  return MD_OK;
+}
+
+bool outlier_on(const md_points_outlier* q) { return q && q->radius != 0.f; }
+
+// model call: radius == 0 is the call without outlier removal and takes none of its outputs. The operator's `neighbours` covers
+// the input rows and needs no list; in the model call nothing is filtered without `count`.
+int check_outlier(const md_points_outlier* q, const md_points_outputs* out, bool op) {
+  if (!q) return MD_OK;
+  if (!std::isfinite(q->radius) || q->radius < 0.f || (op && q->radius == 0.f))
+    MD_FAIL(MD_ERR_INVALID_ARG, "radius = %g: must be finite and %s 0", (double)q->radius, op ? ">" : ">=");
+  if (q->radius == 0.f) {
+    if (q->neighbours || q->index || q->dropped) MD_FAIL(MD_ERR_INVALID_ARG, "neighbours / index / dropped without a radius");
+    return MD_OK;
+  }
+  if (q->min_neighbours < 1 || q->min_neighbours > kOutlierMaxNeighbours)
+    MD_FAIL(MD_ERR_INVALID_ARG, "min_neighbours %d outside 1..%d", q->min_neighbours, kOutlierMaxNeighbours);
+  MD_TRY(need_count(q->index || (!op && q->neighbours), out, op ? "index" : "neighbours / index"));
   return MD_OK;
 }
 
@@ -412,6 +435,39 @@ int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* v
   return MD_OK;
 }
 
+int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_outlier* outl, const md_points_outputs* out, float* normals_out,
+                       hipStream_t stream) {
+  if (!outl) MD_FAIL(MD_ERR_INVALID_ARG, "outlier options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  MD_TRY(check_outlier(outl, out, true));
+  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
+  MD_TRY(check_capacity(out));
+  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "outlier removal has no dense output");
+  MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out, out, "the compacted outputs"));
+  if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
+  if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
+  if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "outlier removal takes fewer than 2^30 rows, got %lld", (long long)in.N);
+  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  OutlierParams p;
+  p.xyz = in.xyz; p.conf = in.conf; p.rgb = in.rgb; p.normals = in.normals;
+  p.n = (int)in.N; p.B = 1; p.radius = outl->radius; p.k = outl->min_neighbours;
+  p.xyz_out = out->xyz; p.conf_out = out->conf; p.rgb_out = out->rgb; p.normals_out = normals_out;
+  p.index = outl->index; p.neighbours = outl->neighbours; p.count = out->count; p.dropped = outl->dropped; p.capacity = out->capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(outlier_scratch_bytes(p.n)));
+  const int rc = launch_radius_outliers(p, scratch.p, st);
+  int32_t flag = 0;
+  hipError_t copy = hipSuccess;  // the flag is read before the scratch it lies in is freed
+  if (rc == MD_OK) copy = hipMemcpyAsync(&flag, outlier_flags(scratch.p, p.n), 4, hipMemcpyDeviceToHost, st);
+  MD_TRY(scratch.finish(rc, copy));
+  if (flag) MD_FAIL(MD_ERR_HIP, "outlier removal: a probe loop ran out of table slots");
+  return MD_OK;
+}
+
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream) {
   MD_TRY(check_render(T, H, W, cam, o, out, in.rgb != nullptr));
@@ -460,6 +516,18 @@ int points_voxel_overflow(md_model_t m, int64_t* out) {
   return MD_OK;
 }
 
+int points_outlier_overflow(md_model_t m, int64_t* out) {
+  *out = 0;
+  md_model_s::PointsState* f = m->points;
+  if (!f || !f->outl_rows || !f->otable.p) return MD_OK;
+  MD_HIP(hipSetDevice(m->dev->ordinal));
+  MD_HIP(hipDeviceSynchronize());  // the call may have run on any stream
+  int32_t flag = 0;
+  MD_HIP(hipMemcpy(&flag, outlier_flags(f->otable.p, f->outl_rows), 4, hipMemcpyDeviceToHost));
+  *out = flag;
+  return MD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the model call
 // ------------------------------------------------------------------------------------------------
@@ -471,18 +539,21 @@ struct OutSlot {  // a host output's way back: `rows` rows of `row_bytes` from i
   size_t row_bytes, rows;
   int list;  // 0: it travels whole. 1: a list output: it travels once `count` is known, and only the rows that hold points.
              // 2: the faces: likewise with `face_count` and `face_capacity`
+             // 3: rows parallel to the unfiltered list (outl->neighbours): likewise with its device count
 };
 
 // What the stages of one call share: its device pointers, resolved by plan_homes, stage_inputs and run_model.
 struct PointsPlan {
   hipStream_t st;
-  bool dual, thin, mesh;
+  bool dual, thin, mesh, filt;
   size_t npx;
   float *depth = nullptr, *raw = nullptr, *conf = nullptr;  // depth: what is unprojected; raw: what the model writes
   const float* x = nullptr;                                 // the image on the device
   PointsParams p;   // launch_unproject's; the device inputs gather in p.rgb / K / E / focal (all kept until run_unproject)
   NormalsParams q;
   VoxelParams v;    // thin: launch_voxel_thin's, from the model's own list that `p` then fills to the list outputs of the call
+  OutlierParams u;  // filt: launch_radius_outliers', from the model's own list that `p` then fills to the list outputs of the call,
+                    // or with thin to the second list of the model that `v` then reads
   RenderParams r;   // c.rnd given: launch_render_points', from the list outputs of the call
   MeshParams g;     // mesh: launch_mesh's, from the depth that is unprojected and the scratch of `p`'s launches
   RasterParams s;   // c.rst given: launch_render_mesh's, from the list outputs and the faces of the call
@@ -503,7 +574,8 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   PointsParams& p = pl.p;
   NormalsParams& q = pl.q;
   VoxelParams& v = pl.v;
-  const bool host = c.out_kind == MD_MEM_HOST, thin = pl.thin;
+  OutlierParams& u = pl.u;
+  const bool host = c.out_kind == MD_MEM_HOST, thin = pl.thin, filt = pl.filt;
   const size_t cap = (size_t)out.capacity;
   float* const no_f = nullptr;
   int32_t* const no_i = nullptr;
@@ -521,14 +593,18 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   slot(out.point_map, p.point_map, 12, pl.npx, 0);
   slot(out.mask, p.mask, 1, pl.npx, 0);
   slot(c.nrm ? c.nrm->normal_map : no_f, q.normal_map, 12, pl.npx, 0);
-  slot(out.count, thin ? v.count : p.count, 4, (size_t)c.B + 1, 0);
+  // the list rows name the outputs of the last stage that writes a list: the thinning, else the outlier removal, else the scatter
+  slot(out.count, thin ? v.count : filt ? u.count : p.count, 4, (size_t)c.B + 1, 0);
   slot(thin ? c.vox->dropped : no_i, v.dropped, 4, 1, 0);
-  slot(out.xyz, thin ? v.xyz_out : p.xyz, 12, cap, 1);
-  slot(out.rgb, thin ? v.rgb_out : p.rgb_out, 3, cap, 1);
-  slot(out.conf, thin ? v.conf_out : p.conf_out, 4, cap, 1);
-  slot(c.nrm ? c.nrm->normals : no_f, thin ? v.normals_out : q.normals, 12, cap, 1);
+  slot(filt ? c.outl->dropped : no_i, u.dropped, 4, 1, 0);
+  slot(out.xyz, thin ? v.xyz_out : filt ? u.xyz_out : p.xyz, 12, cap, 1);
+  slot(out.rgb, thin ? v.rgb_out : filt ? u.rgb_out : p.rgb_out, 3, cap, 1);
+  slot(out.conf, thin ? v.conf_out : filt ? u.conf_out : p.conf_out, 4, cap, 1);
+  slot(c.nrm ? c.nrm->normals : no_f, thin ? v.normals_out : filt ? u.normals_out : q.normals, 12, cap, 1);
   slot(thin ? c.vox->index : no_i, v.index, 4, cap, 1);
   slot(thin ? c.vox->weight : no_i, v.weight, 4, cap, 1);
+  slot(filt && !thin ? c.outl->index : no_i, u.index, 4, cap, 1);
+  slot(filt ? c.outl->neighbours : no_i, u.neighbours, 4, (size_t)list_rows(c.B, c.H, c.W, c.o->stride), 3);
   if (c.rnd) {  // rendered images are dense outputs: they travel whole
     RenderParams& r = pl.r;
     const size_t rpx = (size_t)r.T * r.H * r.W;
@@ -581,6 +657,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   p.capacity = out.capacity;
   pl.q = make_normals(c.nrm);
   pl.thin = voxel_on(c.vox) && out.count;  // without the list there is nothing to thin
+  pl.filt = outlier_on(c.outl) && out.count;
   if (c.rnd) {
     pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
@@ -601,22 +678,42 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, f->out, total));
     place_outputs(c, pl, (char*)f->out.p);
   }
-  if (!pl.thin) return MD_OK;
-  // voxel thinning: the scatter fills the model's own list, the thinning writes where the list would have gone
+  if (!pl.thin && !pl.filt) return MD_OK;
+  // voxel thinning / outlier removal: the scatter fills the model's own list, the last of the two writes where the list would
+  // have gone; with both, the outlier removal writes a second list of the model that the thinning reads
   VoxelParams& v = pl.v;
+  OutlierParams& u = pl.u;
+  const bool want_rgb = out.rgb != nullptr, want_nrm = c.nrm && c.nrm->normals;
   const long rows = list_rows(B, H, W, c.o->stride);
   const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = pl.dual ? align_up((size_t)rows * 4, 256) : 0;
-  const size_t b_rgb = v.rgb_out ? align_up((size_t)rows * 3, 256) : 0, b_nrm = v.normals_out ? b_xyz : 0;
-  MD_TRY(grow(m, st, f->vlist, b_xyz + b_conf + b_rgb + b_nrm + align_up((size_t)(B + 1) * 4, 256)));
-  MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
-  char* base = (char*)f->vlist.p;
-  v.xyz = p.xyz = (float*)base;
-  v.conf = p.conf_out = pl.dual ? (float*)(base + b_xyz) : nullptr;  // the rank reads the confidence whether or not the caller takes it
-  v.rgb = p.rgb_out = v.rgb_out ? (uint8_t*)(base + b_xyz + b_conf) : nullptr;
-  v.normals = pl.q.normals = v.normals_out ? (float*)(base + b_xyz + b_conf + b_rgb) : nullptr;
-  v.in_count = p.count = (int32_t*)(base + b_xyz + b_conf + b_rgb + b_nrm);
-  v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = out.capacity;
+  const size_t b_rgb = want_rgb ? align_up((size_t)rows * 3, 256) : 0, b_nrm = want_nrm ? b_xyz : 0;
+  const size_t b_list = b_xyz + b_conf + b_rgb + b_nrm + align_up((size_t)(B + 1) * 4, 256);
+  struct Rows { float* xyz; float* conf; uint8_t* rgb; float* normals; int32_t* count; };
+  auto rows_of = [&](void* home) {  // the rank reads the confidence whether or not the caller takes it
+    char* base = (char*)home;
+    return Rows{(float*)base, pl.dual ? (float*)(base + b_xyz) : nullptr, want_rgb ? (uint8_t*)(base + b_xyz + b_conf) : nullptr,
+                want_nrm ? (float*)(base + b_xyz + b_conf + b_rgb) : nullptr, (int32_t*)(base + b_xyz + b_conf + b_rgb + b_nrm)};
+  };
+  MD_TRY(grow(m, st, f->vlist, b_list));
+  if (pl.thin) MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
+  if (pl.filt) MD_TRY(grow(m, st, f->otable, outlier_scratch_bytes((int)rows)));
+  if (pl.filt && pl.thin) MD_TRY(grow(m, st, f->flist, b_list));
+  Rows l = rows_of(f->vlist.p);
+  p.xyz = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; pl.q.normals = l.normals; p.count = l.count;
   p.capacity = rows;
+  if (pl.filt) {
+    u.xyz = l.xyz; u.conf = l.conf; u.rgb = l.rgb; u.normals = l.normals; u.in_count = l.count;
+    u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = out.capacity;
+    if (pl.thin) {
+      l = rows_of(f->flist.p);
+      u.xyz_out = l.xyz; u.conf_out = l.conf; u.rgb_out = l.rgb; u.normals_out = l.normals; u.count = l.count;
+      u.capacity = rows;
+    }
+  }
+  if (pl.thin) {
+    v.xyz = l.xyz; v.conf = l.conf; v.rgb = l.rgb; v.normals = l.normals; v.in_count = l.count;
+    v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = out.capacity;
+  }
   return MD_OK;
 }
 
@@ -705,6 +802,13 @@ int run_mesh(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   return launch_mesh(pl.g, pl.pix, m->points->scratch.p, m->points->mesh.p, pl.st);
 }
 
+// Outlier removal: the model's own list -> the list outputs of the call, or the list the thinning reads.
+int run_outlier(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+  MD_TRY(launch_radius_outliers(pl.u, m->points->otable.p, pl.st));
+  m->points->outl_rows = pl.u.n;  // only a launched run has flags to read (points_outlier_overflow)
+  return MD_OK;
+}
+
 // Voxel thinning: the model's own list -> the list outputs of the call.
 int run_thin(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   MD_TRY(launch_voxel_thin(pl.v, m->points->vtable.p, pl.st));
@@ -717,9 +821,10 @@ int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
   const PointsParams& p = pl.p;
   const VoxelParams& v = pl.v;
-  r.xyz = pl.thin ? v.xyz_out : p.xyz;
-  r.rgb = pl.thin ? v.rgb_out : p.rgb_out;
-  r.count = (pl.thin ? v.count : p.count) + c.B;
+  const OutlierParams& u = pl.u;
+  r.xyz = pl.thin ? v.xyz_out : pl.filt ? u.xyz_out : p.xyz;
+  r.rgb = pl.thin ? v.rgb_out : pl.filt ? u.rgb_out : p.rgb_out;
+  r.count = (pl.thin ? v.count : pl.filt ? u.count : p.count) + c.B;
   r.n = (int)std::min<long>((long)c.out->capacity, list_rows(c.B, c.H, c.W, c.o->stride));
   return launch_render_points(r, m->points->rkeys.p, pl.st);
 }
@@ -748,15 +853,18 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
     if (s.list == 0) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
-  int32_t overflow = 0;
+  int32_t overflow = 0, outl_overflow = 0, unfiltered = 0;
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
+  if (pl.filt) MD_TRY(d2h(&outl_overflow, outlier_flags(m->points->otable.p, pl.u.n), 4));
+  if (pl.filt) MD_TRY(d2h(&unfiltered, pl.u.in_count + c.B, 4));
   MD_HIP(hipStreamSynchronize(pl.st));
+  if (outl_overflow) MD_FAIL(MD_ERR_HIP, "outlier removal: a probe loop ran out of table slots");
   if (overflow) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
   if (!c.out->count) return MD_OK;
   const size_t n = std::min((size_t)c.out->count[c.B], (size_t)c.out->capacity);
   const size_t nf = pl.mesh && c.mesh->faces ? std::min((size_t)c.mesh->face_count[c.B], (size_t)c.mesh->face_capacity) : 0;
   for (const OutSlot& s : pl.slots)
-    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 2 ? nf : n) * s.row_bytes));
+    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 3 ? std::min((size_t)std::max(unfiltered, 0), s.rows) : s.list == 2 ? nf : n) * s.row_bytes));
   MD_HIP(hipStreamSynchronize(pl.st));
   return MD_OK;
 }
@@ -764,7 +872,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
 // The stages in the order a captured graph bakes: every grow of the device path before anything is enqueued, then the work.
 int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) {
   if (!m->points) m->points = new md_model_s::PointsState();
-  PointsPlan pl{st, dual, false, false, (size_t)c.B * c.H * c.W};
+  PointsPlan pl{st, dual, false, false, false, (size_t)c.B * c.H * c.W};
   auto timed = [&](const char* name, int (*stage)(md_model_s*, const PointsCall&, PointsPlan&)) -> int {
     Run r{m, st, c.B};
     r.begin(name);
@@ -778,6 +886,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (c.fo) MD_TRY(timed("points_view_filter", run_filter));
   MD_TRY(timed("points_unproject", run_unproject));
   if (pl.mesh) MD_TRY(timed("points_mesh", run_mesh));
+  if (pl.filt) MD_TRY(timed("points_outlier", run_outlier));
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
@@ -812,6 +921,14 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (voxel_on(c.vox) && list_rows(B, H, W, o->stride) >= (1l << 30))
     MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
+  MD_TRY(check_outlier(c.outl, out, false));
+  if (outlier_on(c.outl)) {
+    if (mesh_on(c.mesh)) MD_FAIL(MD_ERR_INVALID_ARG, "a mesh together with outlier removal: the rows its faces name no longer exist");
+    if (c.outl->index && voxel_on(c.vox))
+      MD_FAIL(MD_ERR_INVALID_ARG, "the outlier removal's index together with voxel thinning: the rows it is parallel to are not returned");
+    if (list_rows(B, H, W, o->stride) >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "outlier removal takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
+  }
   if (c.rnd) {
     MD_TRY(check_render(c.rnd->T, c.rnd->H, c.rnd->W, &c.rnd->cam, &c.rnd->opts, &c.rnd->out, out->rgb != nullptr));
     if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rendering needs the list outputs `xyz` and `count`");
@@ -856,6 +973,8 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     key_add(key, 0x4e524d4cu, c.nrm->normal_map, c.nrm->normals, c.nrm->min_cos);
   if (voxel_on(c.vox))  // voxel == 0: the key, and the graph, of the call without thinning
     key_add(key, 0x564f584cu, c.vox->voxel, c.vox->index, c.vox->weight, c.vox->dropped);
+  if (outlier_on(c.outl))  // radius == 0: the key, and the graph, of the call without outlier removal
+    key_add(key, 0x4f55544cu, c.outl->radius, c.outl->min_neighbours, c.outl->neighbours, c.outl->index, c.outl->dropped);
   if (c.rnd) {
     const md_points_render& r = *c.rnd;
     key_add(key, 0x524e4452u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px);

@@ -112,7 +112,10 @@ class PointCloud:
     `md_infer_points_mesh`): faces int32 [face_capacity,3] name rows of xyz, in (view, row, column, triangle) order, of which
     the first min(face_count[B], face_capacity) are faces; face_count int32 [B+1]; pixel_index int32 [B,H,W] is the row of
     every pixel in the list, -1 where it is not in it. With `raster=` (`md_infer_points_raster`): raster = the `RasterisedMesh` of
-    those faces. None when not asked for."""
+    those faces. With `outlier=` (`md_op_radius_outliers` / `md_infer_points_outlier`): the list holds the rows with at least
+    min_neighbours other rows within radius; neighbours int32 [rows of the unfiltered list] is min(neighbours, min_neighbours) of
+    every unfiltered row (-1 outside the grid); without voxel thinning index is the source row of every output row in the
+    unfiltered list and dropped the rows outside the grid. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -130,6 +133,7 @@ class PointCloud:
     face_count: Optional[torch.Tensor] = None
     pixel_index: Optional[torch.Tensor] = None
     raster: Optional["RasterisedMesh"] = None
+    neighbours: Optional[torch.Tensor] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -195,6 +199,24 @@ def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
         out.weight = torch.empty(cap, dtype=torch.int32, device=dev)
         out.dropped = torch.empty(1, dtype=torch.int32, device=dev)
     return _lib.MdPointsVoxel(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped))
+
+
+def _points_outlier(dev, rows: int, outlier: dict, thin: bool, out: PointCloud, fresh: bool):
+    """md_points_outlier for `out`. outlier: a dict with radius and min_neighbours. rows: the rows the unfiltered list can have.
+    With `fresh` neighbours (and, without thinning, index and dropped, which are the thinning's otherwise) are created beside the
+    list it has; otherwise the ones it carries are written again. radius == 0 is the call without the filter and takes no tensor."""
+    unknown = set(outlier) - {"radius", "min_neighbours"}
+    if unknown:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown outlier keywords {sorted(unknown)}")
+    radius, k = float(outlier.get("radius", 0.0)), int(outlier.get("min_neighbours", 1))
+    if not radius:
+        return _lib.MdPointsOutlier(radius, k, None, None, None)
+    if fresh and out.xyz is not None:
+        out.neighbours = torch.empty(rows, dtype=torch.int32, device=dev)
+        if not thin:
+            out.index = torch.empty(int(out.xyz.shape[0]), dtype=torch.int32, device=dev)
+            out.dropped = torch.empty(1, dtype=torch.int32, device=dev)
+    return _lib.MdPointsOutlier(radius, k, _ptr(out.neighbours), None if thin else _ptr(out.index), None if thin else _ptr(out.dropped))
 
 
 def _points_mesh(dev, B: int, H: int, W: int, stride: int, mesh, out: PointCloud, fresh: bool):
@@ -278,9 +300,10 @@ def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None
 def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrinsics, focal_px, want_rgb: bool, want_conf: bool,
                     want_depth: bool, dense: bool, compact: bool, capacity: Optional[int], out: Optional[PointCloud], normals: bool,
                     normal_min_cos: float, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
-                    voxel: Optional[float] = None, render: Optional[dict] = None, mesh=None, raster: Optional[dict] = None):
+                    voxel: Optional[float] = None, render: Optional[dict] = None, mesh=None, raster: Optional[dict] = None,
+                    outlier: Optional[dict] = None):
     """The keyword set of `infer_points` / `ops.unproject` as the structs of the widest entry -> (cloud, opts, outs, cam, fo, nrm,
-    vox, rnd, msh, rst, keep-alive). raster: the keywords of `_raster_request`, as render's. fo, nrm, vox, rnd, msh and rst are None for the parts not asked for (an `out` that carries normal,
+    vox, rnd, msh, rst, outl, keep-alive). outlier: dict(radius=, min_neighbours=), the argument of `_points_outlier`. raster: the keywords of `_raster_request`, as render's. fo, nrm, vox, rnd, msh and rst are None for the parts not asked for (an `out` that carries normal,
     thinning or mesh tensors asks for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless
     `out` is given. mesh: the argument of `_points_mesh`.
     render: the keywords of `_render_request` (H, W, the target cameras, pixel_offset, z_near, z_far, radius); the images go to
@@ -295,7 +318,9 @@ def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrins
         fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
     if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
         nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
-    if voxel is not None and (voxel or res.index is not None or res.weight is not None or res.dropped is not None):
+    # without thinning, the index and dropped that `out` carries beside `neighbours` are the outlier removal's
+    theirs = bool(outlier) and bool(outlier.get("radius")) and not voxel
+    if voxel is not None and (voxel or (not theirs and (res.index is not None or res.weight is not None or res.dropped is not None))):
         vox = _points_voxel(dev, voxel, res, out is None)
     rnd = None
     if render is not None:
@@ -310,7 +335,12 @@ def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrins
         T, tcam, so, res.raster, souts, tkeep = _raster_request(dev, **raster, want_rgb=res.rgb is not None, out=res.raster)
         rst = _lib.MdPointsRaster(T, int(raster["H"]), int(raster["W"]), tcam, so, souts)
         keep = keep + tkeep
-    return res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, keep
+    outl = None
+    if outlier is not None:
+        stride = max(int(o.stride), 1)
+        rows = B * ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
+        outl = _points_outlier(dev, rows, outlier, bool(voxel), res, out is None)
+    return res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, outl, keep
 
 
 @dataclass
@@ -696,13 +726,13 @@ class DepthPro:
                      dense: bool = True, compact: bool = True, capacity: Optional[int] = None, out: Optional[PointCloud] = None,
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
-                     raster: Optional[dict] = None, **opts) -> PointCloud:
+                     raster: Optional[dict] = None, outlier: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        Every form runs through the widest entry, `md_infer_points_raster`, with NULL for the parts not asked for, which is
-        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` on the same arguments:
+        Every form runs through the widest entry, `md_infer_points_outlier`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` / `_raster` on the same arguments:
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
         conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
         before the unprojection; `depth` is then the filtered depth.
@@ -719,7 +749,10 @@ class DepthPro:
         as `faces`, `face_count` and `pixel_index`. Needs compact=True; not with voxel > 0.
         raster (`md_points_raster`): a dict as render's with cull and max_extent in place of radius: the faces of `mesh=` are
         rasterised into those cameras in the same call, a render without holes; the images come back as `raster`
-        (`RasterisedMesh`). Needs mesh= with faces."""
+        (`RasterisedMesh`). Needs mesh= with faces.
+        outlier (`md_points_outlier`): dict(radius=, min_neighbours=): the rows with fewer than min_neighbours other rows within
+        radius leave the list before the thinning and the render see it; returns `neighbours` over the rows of the unfiltered list
+        and, without voxel > 0, `index` and `dropped`. The B views share one grid. Needs compact=True; not with mesh=."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -728,14 +761,14 @@ class DepthPro:
         if rgb is not None:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
         has_conf = bool(getattr(self.config, "dual_head", False))
-        res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, keep = _points_request(
+        res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, outl, keep = _points_request(
             dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
-            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, mesh, raster)
+            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, mesh, raster, outlier)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        _lib.check(self._lib.md_infer_points_raster(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                    C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
-                                                    _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        _lib.check(self._lib.md_infer_points_outlier(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                     C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                     C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
+                                                     ref(outl), _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

@@ -448,7 +448,7 @@ def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None
     conf = _f32c(conf) if conf is not None else None
     rgb = rgb.contiguous() if rgb is not None else None
     assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
-    res, o, outs, cam, _, nrm, _, _, msh, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
+    res, o, outs, cam, _, nrm, _, _, msh, _, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
                                                               conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos,
                                                               mesh=mesh)
     _lib.check(_lib.load().md_op_unproject_mesh(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
@@ -504,6 +504,37 @@ def voxel_thin(dev: Device, xyz: torch.Tensor, voxel: float, conf: Optional[torc
     vox = _lib.MdPointsVoxel(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped))
     _lib.check(_lib.load().md_op_voxel_thin(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(vox), C.byref(outs),
                                             _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def radius_outliers(dev: Device, xyz: torch.Tensor, radius: float, min_neighbours: int, conf: Optional[torch.Tensor] = None,
+                    rgb: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+                    out: Optional[PointCloud] = None) -> PointCloud:
+    """md_op_radius_outliers: a point list xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) -> `PointCloud` with the rows that have
+    at least min_neighbours other rows within radius, in input order: xyz / conf / rgb / normals [capacity, ..], index int32
+    [capacity], neighbours int32 [N] (min(neighbours, min_neighbours) of every input row, -1 outside the grid), count int32 [2] (the
+    survivors, twice: one view), dropped int32 [1]. capacity defaults to N. `out`: a PointCloud of an earlier call to write into
+    again. Bit-identical to `pipeline.radius_outliers`."""
+    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    xyz = _f32c(xyz)
+    N = int(xyz.shape[0])
+    conf = _f32c(conf).reshape(N) if conf is not None else None
+    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if out is None:
+        cap = N if capacity is None else int(capacity)
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=xyz.device)  # noqa: E731
+        out = PointCloud(xyz=f(cap, 3), conf=f(cap) if conf is not None else None, rgb=f(cap, 3, dt=torch.uint8) if rgb is not None else None,
+                         normals=f(cap, 3) if normals is not None else None, count=f(2, dt=torch.int32), index=f(cap, dt=torch.int32),
+                         neighbours=f(N, dt=torch.int32), dropped=f(1, dt=torch.int32))
+    assert out.neighbours is None or int(out.neighbours.shape[0]) >= N, "neighbours covers the input rows"
+    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index) if t is not None]
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
+    outl = _lib.MdPointsOutlier(float(radius), int(min_neighbours), ptr(out.neighbours), ptr(out.index), ptr(out.dropped))
+    _lib.check(_lib.load().md_op_radius_outliers(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(outl), C.byref(outs),
+                                                 _p(out.normals), _stream_ptr(dev.ordinal)))
     return out
 
 

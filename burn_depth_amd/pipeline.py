@@ -20,6 +20,8 @@
   z-buffered into target cameras on 64-bit keys
 * `render_mesh`                               -- the host reference of `md_op_render_mesh` / `md_infer_points_raster`: the faces of the
   mesh rasterised into target cameras, integer coverage at 1/256 pixel and 64-bit keys
+* `radius_outliers`                           -- the host reference of `md_op_radius_outliers` / `md_infer_points_outlier`: the rows
+  with enough neighbours in the 27 cells around their own, bit-identical to the device's
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
   stands in (8-bit grayscale, filter 0), `read_gray_png` reads it back for the tests.
 JPEG decoding stays out of scope: images come in as uint8 arrays."""
@@ -552,6 +554,77 @@ def voxel_thin(xyz, voxel, conf=None, rgb=None, normals=None, counts=None) -> Ho
 
 
 @dataclass
+class HostOutliers:
+    xyz: np.ndarray                  # f32 [M,3]: the surviving input rows, in ascending input index
+    conf: Optional[np.ndarray]       # f32 [M]
+    rgb: Optional[np.ndarray]        # uint8 [M,3]
+    normals: Optional[np.ndarray]    # f32 [M,3]
+    index: np.ndarray                # int32 [M]: the source row
+    neighbours: np.ndarray           # int32 [N] over the input rows: min(neighbours, min_neighbours), -1 outside the grid
+    count: np.ndarray                # int32 [B+1]: survivors per view, then their total
+    dropped: int                     # rows that are not finite or outside the grid
+
+
+def radius_outliers(xyz, radius, min_neighbours, conf=None, rgb=None, normals=None, counts=None) -> HostOutliers:
+    """The host reference of md_op_radius_outliers / md_infer_points_outlier (include/mi_depth.h states the contract): a row survives
+    when at least min_neighbours other rows lie in the 27 cells of side `radius` around its own AND within `radius` of it,
+    d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius in f32, one rounded operation per step; the count saturates at min_neighbours. The
+    survivors keep the input order and every row is copied unchanged: the device kernels (kernels/outlier.hip) give the same bits.
+    A lexsort by cell key, then the 27 shifted lookups. counts: the rows of every view of the input, [B] (default: one view)."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    N = len(p)
+    rs = np.float32(radius)
+    k = int(min_neighbours)
+    if not np.isfinite(rs) or not rs > 0:
+        raise ValueError("radius must be finite and > 0")
+    if k != min_neighbours or k < 1 or k > 1 << 20:
+        raise ValueError("min_neighbours must be an integer in 1 .. 2^20")
+    if N >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows")
+    half = np.float32(1 << 20)
+    with np.errstate(all="ignore"):
+        c = np.floor(p / rs)
+        ok = np.isfinite(p).all(1) & (c >= -half).all(1) & (c < half).all(1)
+    rows = np.nonzero(ok)[0]
+    cell = c[ok].astype(np.int64) + (1 << 20)  # biased: 0 .. 2^21 - 1 on every axis
+    key = (cell[:, 0] << 42) | (cell[:, 1] << 21) | cell[:, 2]
+    order = np.argsort(key, kind="stable")
+    ks, ps = key[order], p[ok][order]  # the in-range points, cell by cell
+    r2 = rs * rs
+    found = np.zeros(len(ks), np.int64)
+    for d in np.ndindex(3, 3, 3):
+        q = cell[order] + (np.array(d, np.int64) - 1)
+        inside = ((q >= 0) & (q < (1 << 21))).all(1)  # a key with a coordinate outside the grid is skipped
+        qk = (q[:, 0] << 42) | (q[:, 1] << 21) | q[:, 2]
+        lo = np.searchsorted(ks, qk, side="left")
+        hi = np.where(inside, np.searchsorted(ks, qk, side="right"), lo)
+        at = lo.copy()
+        while True:  # step t of every bucket walk at once; rows that are saturated or through their bucket have left
+            live = np.nonzero((at < hi) & (found < k))[0]
+            if not len(live):
+                break
+            j = at[live]
+            with np.errstate(all="ignore"):
+                dx, dy, dz = (ps[j, a] - ps[live, a] for a in range(3))
+                d2 = (dx * dx + dy * dy) + dz * dz
+                hit = (d2 <= r2) & (j != live)  # the row's own entry, by position: duplicates count
+            found[live] += hit
+            at[live] += 1
+    neighbours = np.full(N, -1, np.int32)
+    neighbours[rows[order]] = np.minimum(found, k).astype(np.int32)
+    index = np.nonzero(neighbours == k)[0].astype(np.int32)
+    if counts is None:
+        bounds = np.array([0, N], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64).reshape(-1))]), N)
+    per_view = np.diff(np.searchsorted(index, bounds, side="left"))
+    count = np.concatenate([per_view, [len(index)]]).astype(np.int32)
+    take = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)[index]  # noqa: E731
+    return HostOutliers(p[index], take(conf, np.float32, (N,)), take(rgb, np.uint8, (N, 3)), take(normals, np.float32, (N, 3)), index,
+                        neighbours, count, int(N - ok.sum()))
+
+
+@dataclass
 class HostRender:
     depth: np.ndarray                # f32 [T,H,W]: the winner's p.z, 0 at holes
     index: np.ndarray                # int32 [T,H,W]: the winner's row, -1 at holes
@@ -952,7 +1025,8 @@ class AnyDepthModel:
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
-        render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`) and raster= (`md_infer_points_raster`) included."""
+        render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`) and outlier=
+        (`md_infer_points_outlier`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

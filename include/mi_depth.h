@@ -672,6 +672,71 @@ int md_infer_points_raster(md_model_t m, const float* nchw, int B, int H, int W,
 /* The largest clipped box, in pixels, that the setup kernel draws in the face's own thread; a larger one goes through the
  * queue (a compile-time constant of kernels/raster.hip). The image does not depend on it. */
 int md_raster_inline_pixels(void);
+
+/* ---- point path: radius outlier removal of a point list -------------------------------------------------------------------
+ * A list xyz f32 [N,3] with optional parallel rows conf f32 [N], rgb u8 [N,3] and normals f32 [N,3] -> the rows that have at
+ * least k = min_neighbours other rows within `radius` > 0 (1 <= k <= 2^20). Selection: a row survives or it does not, and the
+ * decision is an integer count of a deterministic f32 predicate, so nothing depends on the order in which threads arrive.
+ * f32, one rounded operation per step, no fused multiply-add (pipeline.radius_outliers restates it in numpy bit for bit):
+ *   cell: c_a = floorf(p_a / radius). In range, key and the empty mark are voxel thinning's with `radius` as the side: the
+ *     coordinates finite, -2^20 <= c_a < 2^20 on every axis (compared in float), key = ((c_x + 2^20) << 42) |
+ *     ((c_y + 2^20) << 21) | (c_z + 2^20), all ones = an empty slot. Rows out of range are dropped and counted (`dropped`).
+ *   neighbour: in-range row j != i is a neighbour of in-range row i when |c_a(j) - c_a(i)| <= 1 on all three axes AND
+ *     d2 <= r2, with dx = p_j.x - p_i.x (dy, dz likewise), d2 = (dx*dx + dy*dy) + dz*dz and r2 = radius*radius. The test is
+ *     inclusive; rows with equal coordinates are neighbours of each other; a row is never its own neighbour. The predicate
+ *     is symmetric (f32 subtraction is antisymmetric).
+ *   The cell condition is part of the definition, not an optimisation. In exact arithmetic d <= radius implies it; in f32 the
+ *     quotient p_a / radius and the difference p_j.a - p_i.a are rounded, and a pair within rounding of the radius along one
+ *     axis can pass d2 <= r2 and yet sit two cells apart: p_i.x = -1e-30 lies in cell -1, p_j.x = radius in cell 1, and dx
+ *     rounds to the radius. Such a pair is NOT a neighbour pair here. This is the only deviation from the pure radius test:
+ *     it needs |p_j.a - p_i.a| within an ulp of `radius` on one axis, so the other two differences are about 0. Making the
+ *     27-cell search the definition keeps the device and the host identical.
+ *   neighbours[i] = min(n_i, k) with n_i the number of neighbours of row i: the count saturates at k (a search may stop at
+ *     the k-th hit). Rows out of range get -1. int32 over the INPUT rows [N].
+ *   survivors: neighbours[i] == k. Output: the survivors in ascending input index, so the (view, row, column) order is kept;
+ *     every given row is copied unchanged; index = the source row. count[b] = the survivors of view b, count[B] = their total
+ *     M, also when M exceeds `capacity`: then only the first `capacity` rows are written and the memory behind them stays
+ *     untouched. All views of a call share the grid.
+ *   f32 denormals are outside the contract.
+ * The grid is voxel thinning's table (linear probing over the power of two >= max(2 N, 1024) slots) extended to cell buckets:
+ * per slot a count and a start, and the in-range positions stored bucket by bucket in 12 N bytes. The order of the buckets and
+ * of the rows inside one varies from run to run; it is layout and reaches no output. Reset on the stream inside every call. */
+typedef struct md_points_outlier {
+  float radius;        /* 0 = no outlier removal (md_infer_points_outlier), finite and >= 0 */
+  int min_neighbours;  /* k, 1 .. 2^20 */
+  int32_t* neighbours; /* int32 [N] over the rows of the unfiltered list: min(n_i, k), -1 out of range. NULL = skip */
+  int32_t* index;      /* int32 [capacity]: the source row of every output row; needs count. NULL = skip */
+  int32_t* dropped;    /* int32 [1]: rows not finite or out of range. NULL = skip */
+} md_points_outlier;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_voxel_thin: the N rows are one view. Of `out` the fields
+ * xyz, rgb, conf, count (int32 [2]: M twice) and capacity are used, the others must be NULL; normals_out [capacity,3] takes
+ * the normals rows. Everything is enqueued on `stream`; the call returns after the stream has drained, because its scratch is
+ * freed on return. Errors, before any launch: dev / outl / out NULL, xyz_dev NULL with N > 0, radius not finite or <= 0,
+ * min_neighbours < 1 or > 2^20, N < 0, capacity < 0, a compacted output (xyz, rgb, conf, normals_out, index) without count,
+ * an rgb / conf / normals output without that input row, a dense output or out->depth set -> MD_ERR_INVALID_ARG;
+ * N >= 2^30 -> MD_ERR_SHAPE. A probe loop that ran out of table (impossible at load <= 0.5) -> MD_ERR_HIP after the launches. */
+int md_op_radius_outliers(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev,
+                          const float* normals_dev, int64_t N, const md_points_outlier* outl, const md_points_outputs* out,
+                          float* normals_out, void* stream);
+/* md_infer_points_raster with the outlier removal between the unprojection and the thinning: the unfiltered list goes to a
+ * grow-only buffer of the model, as do the table, the buckets and the ballot words; thinning and the point render see the
+ * filtered list (with thinning the filter writes a second grow-only list and the thinning writes the caller's). out->count
+ * receives the counts of the list the call ends with. outl->neighbours is int32 over the rows of the unfiltered list (at most
+ * B ceil(H/stride) ceil(W/stride); the first unfiltered-total rows are written); outl->index names rows of the unfiltered
+ * list and is written only without thinning (with it, vox->index names rows of the filtered list). outl's pointers are of
+ * out_kind. outl NULL or radius == 0 (its pointers then NULL): md_infer_points_raster on the same arguments, the same
+ * launches and bits; a call without out->count filters nothing. The graph key contains outl's fields. Errors as
+ * md_infer_points_raster's, plus, before any launch: radius not finite or negative, min_neighbours < 1 or > 2^20 with
+ * radius > 0, neighbours / index without count, any of outl's pointers with radius == 0, outlier removal together with a
+ * mesh (the rows its faces name no longer exist) -> MD_ERR_INVALID_ARG; a list of >= 2^30 rows -> MD_ERR_SHAPE. With host
+ * outputs a probe loop that ran out of table -> MD_ERR_HIP; with device outputs md_model_query(m, "outlier_overflow") reads
+ * the flag of the last call (it waits for the device). After the first call of a shape nothing is allocated. */
+int md_infer_points_outlier(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                            const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                            const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                            const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                            const md_points_raster* rst, const md_points_outlier* outl, int out_kind, void* stream);
 /* PROCESS-WIDE (returns the previous setting): the capacity of the (face, target) queue of later md_op_render_mesh /
  * md_infer_points_raster calls, 0 = the default (2^20 pairs). A push that finds the queue full draws the face in place: same
  * bits at every capacity; for the test of that branch. MD_ERR_INVALID_ARG (< 0) for a negative capacity. */

@@ -24,6 +24,10 @@ view is written beside `--output` (`depth_v0.png`, ...). With `--ply` the device
 `--voxel X` (with `--ply`): the cloud is thinned on the device to one point per occupied voxel of side X, the most confident one
 (`md_infer_points_voxel`; with `--views`, `ops.voxel_thin` over the cloud of all views, which share the grid).
 
+`--outlier-radius R [--outlier-min K]` (with `--ply`): the points with fewer than K (default 8) other points within R leave the cloud
+on the device before the thinning and the render see it (`md_infer_points_outlier`; with `--views`, `ops.radius_outliers` in front of
+`ops.voxel_thin`, over the cloud of all views). Not together with `--mesh`.
+
 `--render-pose E.npy --render-out view.png` (with `--ply`): the cloud is also z-buffered on the device into a virtual camera with the
 world-to-camera pose E ([3,4], or [T,3,4] of which every pose is rendered and the first written) and its depth image written as a
 normalised PNG, holes black (`md_infer_points_render`; with `--views`, `ops.render_points` on the cloud of all views).
@@ -137,6 +141,14 @@ def run_views(a) -> int:
         faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy() if a.mesh else None
         xyz, col, conf = pc.points()
         nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.outlier_radius > 0:  # the points without enough neighbours over all views leave first
+            try:
+                pc = ops.radius_outliers(dev, xyz, a.outlier_radius, a.outlier_min, conf=conf, rgb=col, normals=nrm)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            xyz, col, conf = pc.points()
+            nrm = pc.normals[:xyz.shape[0]] if a.normals else None
         if a.voxel > 0:  # one point per occupied voxel over all views: the most confident one
             try:
                 pc = ops.voxel_thin(dev, xyz, a.voxel, conf=conf, rgb=col, normals=nrm)
@@ -196,6 +208,9 @@ def main(argv=None) -> int:
                     help="--ply: drop pixels whose surface is seen at a cosine below this (grazing angles; 0 = off, at most 1)")
     ap.add_argument("--voxel", type=float, default=0.0,
                     help="--ply: keep one point per occupied voxel of this side, the most confident one (md_infer_points_voxel; 0 = off)")
+    ap.add_argument("--outlier-radius", type=float, default=0.0,
+                    help="--ply: drop the points with fewer than --outlier-min others within this radius (md_infer_points_outlier; 0 = off)")
+    ap.add_argument("--outlier-min", type=int, default=8, help="--outlier-radius: the neighbours a point needs to stay")
     ap.add_argument("--render-pose", default="", help="--ply: also render the cloud into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
     ap.add_argument("--render-size", type=int, nargs=2, metavar=("H", "W"), default=None, help="--render-pose: image size (default: the view's)")
     ap.add_argument("--render-radius", type=int, default=0, help="--render-pose: a point covers the (2R+1)^2 pixels around its pixel")
@@ -212,6 +227,9 @@ def main(argv=None) -> int:
         return 2
     if a.mesh and (not a.ply or a.voxel > 0):
         print("--mesh goes with --ply, and not with --voxel (a thinned list has no grid)", file=sys.stderr)
+        return 2
+    if a.outlier_radius != 0 and (not a.ply or a.mesh):
+        print("--outlier-radius goes with --ply, and not with --mesh (the faces name rows of the unfiltered list)", file=sys.stderr)
         return 2
     if bool(a.render_pose) != bool(a.render_out) or (a.render_pose and not a.ply):
         print("--render-pose and --render-out go together, and with --ply", file=sys.stderr)
@@ -269,7 +287,8 @@ def main(argv=None) -> int:
                                     dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
                                     world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
                                     normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render,
-                                    mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None, raster=raster)
+                                    mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None, raster=raster,
+                                    outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
