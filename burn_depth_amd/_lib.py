@@ -79,6 +79,13 @@ class MdPointsOutlier(C.Structure):
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int), ("neighbours", C.c_void_p), ("index", C.c_void_p), ("dropped", C.c_void_p)]
 
 
+class MdPointsDecimate(C.Structure):
+    """md_points_decimate (include/mi_depth.h)."""
+    _fields_ = [("voxel", C.c_float), ("index", C.c_void_p), ("weight", C.c_void_p), ("dropped", C.c_void_p), ("remap", C.c_void_p),
+                ("faces", C.c_void_p), ("face_index", C.c_void_p), ("face_count", C.c_void_p), ("face_capacity", C.c_int64),
+                ("faces_dropped", C.c_void_p)]
+
+
 class MdRenderOpts(C.Structure):
     """md_render_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
@@ -246,6 +253,11 @@ SYMBOLS = {
                                      C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
                                      C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
                                      C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), _I, _P]),
+    "md_infer_points_decimate": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                      C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                      C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
+                                      C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate), _I, _P]),
+    "md_op_decimate_mesh": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsDecimate), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),

@@ -124,6 +124,43 @@ const int32_t* voxel_flags(const void* scratch, int n);
 // p.weight from cnt[slot[i]], both may be null without it). Nothing is launched without p.count; counts only without a row output.
 int launch_list_compact(const VoxelParams& p, const unsigned* cnt, const int* slot, const unsigned long long* bits, const int* counts,
                         int* offsets, hipStream_t s);
+// what launch_voxel_thin (with p.count) left in its scratch about every row, for the decimation's remap: the slot of a live row
+// (-1 out of range), the rank word of a slot (its low word names the survivor), the keep bits and the tile offsets
+struct VoxelRanks {
+  const int* slot;
+  const unsigned long long* rank;
+  const unsigned long long* bits;
+  const int* offsets;
+};
+VoxelRanks voxel_ranks(const void* scratch, int n);
+
+// ---- vertex-clustering decimation (kernels/decimate.hip; md_op_decimate_mesh) ----
+// Vertices: launch_voxel_thin on `v`, unchanged, then remap [n] from the scratch it leaves (two launches). Faces [nf,3] over the
+// input rows -> mapped through remap and classified, a hash set of oriented triangles that holds face ids, select (ballot
+// words), scan (launch_list_compact's), scatter. Every pointer is a device pointer. Selection only: integer atomics, nothing
+// depends on the order of arrival.
+struct DecimateParams {
+  VoxelParams v;                           // the vertex side; v.count null: the counts go to the scratch
+  int32_t* remap = nullptr;                // [v.n]; null: it lives in the scratch
+  const int32_t* faces = nullptr;          // [nf,3]
+  const int32_t* in_face_count = nullptr;  // [v.B + 1] per-view faces of the input, then their total = the live faces; null: nf faces, one view
+  int nf = 0;                              // faces the launches cover: the live count is min(in_face_count[B], nf)
+  int32_t* faces_out = nullptr;            // [face_capacity,3]
+  int32_t* face_index = nullptr;           // [face_capacity]
+  int32_t* face_count = nullptr;           // [v.B + 1]; null: no select / scan / scatter
+  int32_t* faces_dropped = nullptr;        // [3]
+  long face_capacity = 0;
+};
+// bytes of the scratch: voxel thinning's for n rows, then counts / remap homes, the face table (4 B per slot), the mapped
+// triples 12 nf, the slot of every face, ballot words, block counts, block offsets, flags
+size_t decimate_scratch_bytes(int n, int nf, int B);
+// flags[0] != 0 after the launches = a probe loop of the face table ran out (the vertex table's flag: voxel_flags(scratch, n))
+int launch_decimate_mesh(const DecimateParams& p, void* scratch, hipStream_t s);
+const int32_t* decimate_flags(const void* scratch, int n, int nf, int B);
+// one launch: a face list [rows,3] with its device counts [B + 1] copied to a caller's buffers: the counts, and the
+// first min(count[B], rows, capacity) faces; the memory behind them stays untouched. Nothing without count_out; faces_out may be null
+int launch_copy_faces(const int32_t* faces, const int32_t* count, int B, long rows, int32_t* faces_out, int32_t* count_out, long capacity,
+                      hipStream_t s);
 
 // ---- radius outlier removal (kernels/outlier.hip; md_op_radius_outliers, md_infer_points_outlier) ----
 // A point list xyz [n,3] (+ conf, rgb, normals rows) -> the rows with at least k other rows within `radius`, in ascending input

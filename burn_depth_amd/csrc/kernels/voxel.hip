@@ -257,6 +257,11 @@ size_t voxel_scratch_bytes(int n) { return carve(nullptr, n > 0 ? n : 0).bytes; 
 
 const int32_t* voxel_flags(const void* scratch, int n) { return carve((void*)scratch, n > 0 ? n : 0).flags; }
 
+VoxelRanks voxel_ranks(const void* scratch, int n) {
+  const VoxelScratch v = carve((void*)scratch, n > 0 ? n : 0);
+  return VoxelRanks{v.slot, v.rank, v.bits, v.offsets};
+}
+
 int launch_voxel_thin(const VoxelParams& p, void* scratch, hipStream_t s) {
   if (!scratch) MD_FAIL(MD_ERR_INVALID_ARG, "voxel thinning needs its scratch buffer");
   if (p.n < 0 || p.n >= (1 << 30)) MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, got %d", p.n);

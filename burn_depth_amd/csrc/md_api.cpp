@@ -314,6 +314,7 @@ int md_model_query(md_model_t m, const char* key, int64_t* out) {
   else if (k == "allocs") *out = m->alloc_count;
   else if (k == "voxel_overflow") return points_voxel_overflow(m, out);
   else if (k == "outlier_overflow") return points_outlier_overflow(m, out);
+  else if (k == "decimate_overflow") return points_decimate_overflow(m, out);
   else if (k == "da3_shape_builds") *out = da3_shape_builds(m);
   else if (k == "batch_invariant") *out = m->batch_invariant ? 1 : 0;
   else if (k == "ln_fold") *out = m->ln_fold_opt;
@@ -575,6 +576,21 @@ int md_infer_points_outlier(md_model_t m, const float* nchw, int B, int H, int W
                             const md_points_outlier* outl, int out_kind, void* stream) {
   return infer_points(m, PointsCall{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh, rst, outl},
                       (hipStream_t)stream);
+}
+
+int md_infer_points_decimate(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                             const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                             const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, const md_points_raster* rst,
+                             const md_points_outlier* outl, const md_points_decimate* dec, int out_kind, void* stream) {
+  PointsCall c{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh, rst};
+  c.outl = outl; c.dec = dec;
+  return infer_points(m, c, (hipStream_t)stream);
+}
+
+int md_op_decimate_mesh(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                        int64_t N, const int32_t* faces_dev, int64_t F, const md_points_decimate* dec, const md_points_outputs* out,
+                        float* normals_out, void* stream) {
+  return op_decimate_mesh(dev, PointList{xyz_dev, conf_dev, rgb_dev, normals_dev, N}, faces_dev, F, dec, out, normals_out, (hipStream_t)stream);
 }
 
 int md_raster_inline_pixels(void) { return md::raster_inline_pixels(); }

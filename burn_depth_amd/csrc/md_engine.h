@@ -370,7 +370,7 @@ struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], c
   const float* normals = nullptr;
   int64_t N = 0;
 };
-// One md_infer_points* request: what the widest entry (md_infer_points_outlier) takes. A narrower entry leaves the parts it lacks
+// One md_infer_points* request: what the widest entry (md_infer_points_decimate) takes. A narrower entry leaves the parts it lacks
 // null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
 struct PointsCall {
   const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
@@ -389,6 +389,7 @@ struct PointsCall {
   const md_points_mesh* mesh = nullptr;   // given: the faces of the depth grid over the list's rows (pointers of out_kind)
   const md_points_raster* rst = nullptr;  // given: those faces are rasterised into its targets (cameras of in_kind)
   const md_points_outlier* outl = nullptr;  // given: radius outlier removal between the unprojection and the thinning (pointers of out_kind)
+  const md_points_decimate* dec = nullptr;  // given: vertex-clustering decimation behind the mesh (pointers of out_kind); needs `mesh`
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
@@ -401,6 +402,9 @@ int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* v
                   hipStream_t stream);
 int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_outlier* outl, const md_points_outputs* out, float* normals_out,
                        hipStream_t stream);
+// in: the vertices; faces [F,3] over their rows
+int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
+                     const md_points_outputs* out, float* normals_out, hipStream_t stream);
 // in.xyz / in.rgb: the list; count: its device count word or null
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream);
@@ -411,6 +415,8 @@ int op_render_mesh(md_device_t dev, const PointList& in, const int32_t* faces, i
 int points_voxel_overflow(md_model_t m, int64_t* out);
 // likewise for the outlier removal of the model's last md_infer_points_outlier
 int points_outlier_overflow(md_model_t m, int64_t* out);
+// likewise for the decimation of the model's last md_infer_points_decimate (the vertex table's flag or the face table's)
+int points_decimate_overflow(md_model_t m, int64_t* out);
 int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_view_filter_opts* o,
                     const md_view_filter_outputs* out, hipStream_t stream);
 void points_destroy_state(md_model_t m);

@@ -45,6 +45,10 @@ struct md_model_s::PointsState {
   md::GrowBuf<float> rcams;       // the device copy of host target cameras: K [T,9] | E [T,12] | focal [T]
   md::GrowBuf<void> skeys;        // md_infer_points_raster: the z-buffer keys and the face queue (raster_scratch_bytes)
   md::GrowBuf<float> scams;       // the device copy of its host target cameras, laid out as rcams
+  md::GrowBuf<void> dtable;       // md_infer_points_decimate: the decimation's scratch (decimate_scratch_bytes)
+  md::GrowBuf<void> dfaces;       // its input: the faces of the unthinned list [2 rows,3] | their face_count [B+1]
+  int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
+                                                   // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
   int outl_rows = 0;              // likewise for the outlier removal and otable
   float* k_home() const { return cams.p; }
@@ -174,6 +178,23 @@ int check_voxel(const md_points_voxel* vox, const md_points_outputs* out, bool o
   MD_TRY(need_count(vox->index || vox->weight, out, "index / weight"));
   if (vox->voxel == 0.f && (vox->index || vox->weight || vox->dropped))
     MD_FAIL(MD_ERR_INVALID_ARG, "index / weight / dropped without a voxel size");
+  return MD_OK;
+}
+
+bool decimate_on(const md_points_decimate* d) { return d && d->voxel != 0.f; }
+
+// model call: voxel == 0 is the call without decimation and takes none of its outputs
+int check_decimate_part(const md_points_decimate* d, const md_points_outputs* out) {
+  if (!d) return MD_OK;
+  if (!std::isfinite(d->voxel) || d->voxel < 0.f) MD_FAIL(MD_ERR_INVALID_ARG, "voxel = %g: must be finite and >= 0", (double)d->voxel);
+  if (d->voxel == 0.f) {
+    if (d->index || d->weight || d->dropped || d->remap || d->faces || d->face_index || d->face_count || d->faces_dropped)
+      MD_FAIL(MD_ERR_INVALID_ARG, "decimation outputs without a voxel size");
+    return MD_OK;
+  }
+  if (d->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)d->face_capacity);
+  if ((d->faces || d->face_index) && !d->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
+  MD_TRY(need_count(d->index || d->weight, out, "index / weight"));
   return MD_OK;
 }
 
@@ -468,6 +489,57 @@ int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_out
   return MD_OK;
 }
 
+// the refusals of the decimation's own part, in check_voxel's and check_mesh's style
+int check_decimate(const md_points_decimate* dec, const md_points_outputs* out) {
+  if (!std::isfinite(dec->voxel) || dec->voxel <= 0.f) MD_FAIL(MD_ERR_INVALID_ARG, "voxel = %g: must be finite and > 0", (double)dec->voxel);
+  if (dec->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)dec->face_capacity);
+  if ((dec->faces || dec->face_index) && !dec->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
+  MD_TRY(need_count(dec->index || dec->weight, out, "index / weight"));
+  return MD_OK;
+}
+
+int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
+                     const md_points_outputs* out, float* normals_out, hipStream_t stream) {
+  if (!dec) MD_FAIL(MD_ERR_INVALID_ARG, "decimation options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  MD_TRY(check_decimate(dec, out));
+  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
+  if (F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)F);
+  MD_TRY(check_capacity(out));
+  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "decimation has no dense output");
+  MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out, out, "the compacted outputs"));
+  if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
+  if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
+  if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 rows, got %lld", (long long)in.N);
+  if (F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 faces, got %lld", (long long)F);
+  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  DecimateParams p;
+  p.v.xyz = in.xyz; p.v.conf = in.conf; p.v.rgb = in.rgb; p.v.normals = in.normals;
+  p.v.n = (int)in.N; p.v.B = 1; p.v.voxel = dec->voxel;
+  p.v.xyz_out = out->xyz; p.v.conf_out = out->conf; p.v.rgb_out = out->rgb; p.v.normals_out = normals_out;
+  p.v.index = dec->index; p.v.weight = dec->weight; p.v.count = out->count; p.v.dropped = dec->dropped; p.v.capacity = out->capacity;
+  p.remap = dec->remap; p.faces = faces; p.nf = (int)F;
+  p.faces_out = dec->faces; p.face_index = dec->face_index; p.face_count = dec->face_count; p.faces_dropped = dec->faces_dropped;
+  p.face_capacity = (long)dec->face_capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(decimate_scratch_bytes(p.v.n, p.nf, 1)));
+  const int rc = launch_decimate_mesh(p, scratch.p, st);
+  int32_t flag[2] = {0, 0};
+  hipError_t copy = hipSuccess;  // the flags are read before the scratch they lie in is freed
+  if (rc == MD_OK) copy = hipMemcpyAsync(&flag[0], voxel_flags(scratch.p, p.v.n), 4, hipMemcpyDeviceToHost, st);
+  const bool face_side = p.faces_out || p.face_index || p.face_count || p.faces_dropped;  // otherwise the face table was never reset
+  if (rc == MD_OK && copy == hipSuccess && face_side)
+    copy = hipMemcpyAsync(&flag[1], decimate_flags(scratch.p, p.v.n, p.nf, 1), 4, hipMemcpyDeviceToHost, st);
+  MD_TRY(scratch.finish(rc, copy));
+  if (flag[0] || flag[1]) MD_FAIL(MD_ERR_HIP, "decimation: a probe loop ran out of table slots");
+  return MD_OK;
+}
+
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream) {
   MD_TRY(check_render(T, H, W, cam, o, out, in.rgb != nullptr));
@@ -516,6 +588,19 @@ int points_voxel_overflow(md_model_t m, int64_t* out) {
   return MD_OK;
 }
 
+int points_decimate_overflow(md_model_t m, int64_t* out) {
+  *out = 0;
+  md_model_s::PointsState* f = m->points;
+  if (!f || !f->dec_views || !f->dtable.p) return MD_OK;
+  MD_HIP(hipSetDevice(m->dev->ordinal));
+  MD_HIP(hipDeviceSynchronize());  // the call may have run on any stream
+  int32_t flag[2] = {0, 0};
+  MD_HIP(hipMemcpy(&flag[0], voxel_flags(f->dtable.p, f->dec_rows), 4, hipMemcpyDeviceToHost));
+  MD_HIP(hipMemcpy(&flag[1], decimate_flags(f->dtable.p, f->dec_rows, f->dec_faces, f->dec_views), 4, hipMemcpyDeviceToHost));
+  *out = flag[0] || flag[1];
+  return MD_OK;
+}
+
 int points_outlier_overflow(md_model_t m, int64_t* out) {
   *out = 0;
   md_model_s::PointsState* f = m->points;
@@ -540,12 +625,13 @@ struct OutSlot {  // a host output's way back: `rows` rows of `row_bytes` from i
   int list;  // 0: it travels whole. 1: a list output: it travels once `count` is known, and only the rows that hold points.
              // 2: the faces: likewise with `face_count` and `face_capacity`
              // 3: rows parallel to the unfiltered list (outl->neighbours): likewise with its device count
+             // 4: the decimated faces: as 2 with dec's `face_count` and `face_capacity`
 };
 
 // What the stages of one call share: its device pointers, resolved by plan_homes, stage_inputs and run_model.
 struct PointsPlan {
   hipStream_t st;
-  bool dual, thin, mesh, filt;
+  bool dual, thin, mesh, filt, deci;
   size_t npx;
   float *depth = nullptr, *raw = nullptr, *conf = nullptr;  // depth: what is unprojected; raw: what the model writes
   const float* x = nullptr;                                 // the image on the device
@@ -557,12 +643,73 @@ struct PointsPlan {
   RenderParams r;   // c.rnd given: launch_render_points', from the list outputs of the call
   MeshParams g;     // mesh: launch_mesh's, from the depth that is unprojected and the scratch of `p`'s launches
   RasterParams s;   // c.rst given: launch_render_mesh's, from the list outputs and the faces of the call
+  DecimateParams d; // deci: launch_decimate_mesh's, from the model's own list and the faces `gd` wrote; d.v fills the list outputs of the call
+  MeshParams gd;    // deci: the mesh stage's second set of face outputs, the model's own, complete and with the true count
   int queue = 0;    // its queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   std::vector<OutSlot> slots;
 };
 
 bool views_on(const PointsCall& c) { return c.fo && c.fo->view_rtol > 0.f; }
+
+// place_outputs with the decimation on (no thinning, no outlier removal): the list rows name d.v's outputs, the caller's mesh
+// outputs name `g`'s as ever, and dec's own follow
+size_t place_outputs_decimated(const PointsCall& c, PointsPlan& pl, char* base) {
+  const md_points_outputs& out = *c.out;
+  const md_points_decimate& dec = *c.dec;
+  VoxelParams& v = pl.d.v;
+  const bool host = c.out_kind == MD_MEM_HOST;
+  const size_t cap = (size_t)out.capacity, fcap = (size_t)dec.face_capacity;
+  float* const no_f = nullptr;
+  size_t total = 0;
+  pl.slots.clear();
+  auto slot = [&](auto* caller, auto*& param, size_t row_bytes, size_t rows, int list) {
+    param = caller;
+    if (!caller || !host) return;
+    if (base) {
+      param = (decltype(caller))(base + total);
+      pl.slots.push_back(OutSlot{caller, param, row_bytes, rows, list});
+    }
+    total += align_up(row_bytes * rows, 256);
+  };
+  slot(out.point_map, pl.p.point_map, 12, pl.npx, 0);
+  slot(out.mask, pl.p.mask, 1, pl.npx, 0);
+  slot(c.nrm ? c.nrm->normal_map : no_f, pl.q.normal_map, 12, pl.npx, 0);
+  slot(out.count, v.count, 4, (size_t)c.B + 1, 0);
+  slot(dec.dropped, v.dropped, 4, 1, 0);
+  slot(dec.face_count, pl.d.face_count, 4, (size_t)c.B + 1, 0);
+  slot(dec.faces_dropped, pl.d.faces_dropped, 4, 3, 0);
+  slot(dec.remap, pl.d.remap, 4, (size_t)list_rows(c.B, c.H, c.W, c.o->stride), 0);
+  slot(out.xyz, v.xyz_out, 12, cap, 1);
+  slot(out.rgb, v.rgb_out, 3, cap, 1);
+  slot(out.conf, v.conf_out, 4, cap, 1);
+  slot(c.nrm ? c.nrm->normals : no_f, v.normals_out, 12, cap, 1);
+  slot(dec.index, v.index, 4, cap, 1);
+  slot(dec.weight, v.weight, 4, cap, 1);
+  slot(dec.faces, pl.d.faces_out, 12, fcap, 4);
+  slot(dec.face_index, pl.d.face_index, 4, fcap, 4);
+  if (c.rnd) {
+    RenderParams& r = pl.r;
+    const size_t rpx = (size_t)r.T * r.H * r.W;
+    slot(c.rnd->out.depth, r.depth, 4, rpx, 0);
+    slot(c.rnd->out.index, r.index, 4, rpx, 0);
+    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, 0);
+    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, 0);
+  }
+  if (c.rst) {
+    RasterParams& s = pl.s;
+    const size_t spx = (size_t)s.T * s.H * s.W;
+    slot(c.rst->out.depth, s.depth, 4, spx, 0);
+    slot(c.rst->out.face, s.face, 4, spx, 0);
+    slot(c.rst->out.rgb, s.rgb_out, 3, spx, 0);
+    slot(c.rst->out.filled, s.filled, 4, (size_t)s.T + 1, 0);
+    slot(c.rst->out.skipped, s.skipped, 4, (size_t)s.T + 1, 0);
+  }
+  slot(c.mesh->pixel_index, pl.pix, 4, pl.npx, 0);
+  slot(c.mesh->face_count, pl.g.face_count, 4, (size_t)c.B + 1, 0);
+  slot(c.mesh->faces, pl.g.faces, 12, (size_t)c.mesh->face_capacity, 2);
+  return total;
+}
 
 // The outputs a caller may hold in host memory, in the order they travel: the dense maps and the counts, then the list. Device
 // outputs: the kernel parameter takes the caller's pointer. Host outputs: it takes a home inside `base` (PointsState::out, at
@@ -575,6 +722,7 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   NormalsParams& q = pl.q;
   VoxelParams& v = pl.v;
   OutlierParams& u = pl.u;
+  if (pl.deci) return place_outputs_decimated(c, pl, base);
   const bool host = c.out_kind == MD_MEM_HOST, thin = pl.thin, filt = pl.filt;
   const size_t cap = (size_t)out.capacity;
   float* const no_f = nullptr;
@@ -669,8 +817,13 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, f->skeys, raster_scratch_bytes(c.rst->T, c.rst->H, c.rst->W, pl.queue)));
     if (c.in_kind == MD_MEM_HOST) MD_TRY(grow(m, st, f->scams, (size_t)c.rst->T * 22 * 4));
   }
-  pl.mesh = mesh_on(c.mesh);
-  if (pl.mesh) {
+  pl.deci = decimate_on(c.dec);
+  pl.mesh = mesh_on(c.mesh) || pl.deci;
+  if (pl.deci) {  // the faces name rows of the model's own, unthinned list: every row of it is usable; the map always has a home
+    const long rows = list_rows(B, H, W, c.o->stride);
+    pl.g = make_mesh(B, H, W, c.o->stride, rows, *c.mesh);
+    MD_TRY(grow(m, st, f->mesh, mesh_scratch_bytes(B, H, W, c.o->stride) + align_up(pl.npx * 4, 256)));
+  } else if (pl.mesh) {
     pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
     if (const size_t bytes = mesh_home_bytes(*c.mesh, B, H, W, c.o->stride)) MD_TRY(grow(m, st, f->mesh, bytes));
   }
@@ -678,7 +831,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, f->out, total));
     place_outputs(c, pl, (char*)f->out.p);
   }
-  if (!pl.thin && !pl.filt) return MD_OK;
+  if (!pl.thin && !pl.filt && !pl.deci) return MD_OK;
   // voxel thinning / outlier removal: the scatter fills the model's own list, the last of the two writes where the list would
   // have gone; with both, the outlier removal writes a second list of the model that the thinning reads
   VoxelParams& v = pl.v;
@@ -713,6 +866,18 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.thin) {
     v.xyz = l.xyz; v.conf = l.conf; v.rgb = l.rgb; v.normals = l.normals; v.in_count = l.count;
     v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = out.capacity;
+  }
+  if (pl.deci) {  // the decimation is the thinning: d.v reads the model's list as `v` would, the faces come from the model's face home
+    DecimateParams& d = pl.d;
+    const long nf = 2 * rows;
+    const size_t b_faces = align_up((size_t)nf * 12, 256);
+    MD_TRY(grow(m, st, f->dfaces, b_faces + align_up((size_t)(B + 1) * 4, 256)));
+    MD_TRY(grow(m, st, f->dtable, decimate_scratch_bytes((int)rows, (int)nf, B)));
+    pl.gd = pl.g;
+    pl.gd.faces = (int32_t*)f->dfaces.p; pl.gd.face_count = (int32_t*)((char*)f->dfaces.p + b_faces); pl.gd.face_capacity = nf;
+    d.v.xyz = l.xyz; d.v.conf = l.conf; d.v.rgb = l.rgb; d.v.normals = l.normals; d.v.in_count = l.count;
+    d.v.n = (int)rows; d.v.B = B; d.v.voxel = c.dec->voxel; d.v.capacity = out.capacity;
+    d.faces = pl.gd.faces; d.in_face_count = pl.gd.face_count; d.nf = (int)nf; d.face_capacity = (long)c.dec->face_capacity;
   }
   return MD_OK;
 }
@@ -797,8 +962,17 @@ int run_unproject(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
 }
 
 // The mesh of the list: needs the scratch of run_unproject's launches before anything reuses it.
-int run_mesh(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+int run_mesh(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.g.depth = pl.depth;
+  if (pl.deci) {  // the map, then the model's own faces, complete, for the decimation; the caller's, if it takes them, are a copy:
+                  // both have every row of the list as a usable corner, so they are the same faces
+    void* home = m->points->mesh.p;
+    int32_t* pix = pl.pix ? pl.pix : (int32_t*)((char*)home + mesh_scratch_bytes(c.B, c.H, c.W, c.o->stride));
+    MD_TRY(launch_mesh_index(c.B, c.H, c.W, m->points->scratch.p, pix, pl.st));
+    pl.gd.depth = pl.depth; pl.gd.pixel_index = pix;
+    MD_TRY(launch_mesh_grid(pl.gd, home, pl.st));
+    return launch_copy_faces(pl.gd.faces, pl.gd.face_count, c.B, pl.gd.face_capacity, pl.g.faces, pl.g.face_count, pl.g.face_capacity, pl.st);
+  }
   return launch_mesh(pl.g, pl.pix, m->points->scratch.p, m->points->mesh.p, pl.st);
 }
 
@@ -816,15 +990,22 @@ int run_thin(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   return MD_OK;
 }
 
+// Decimation: the model's own list and faces -> the list outputs of the call and dec's face outputs.
+int run_decimate(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+  MD_TRY(launch_decimate_mesh(pl.d, m->points->dtable.p, pl.st));
+  m->points->dec_rows = pl.d.v.n; m->points->dec_faces = pl.d.nf; m->points->dec_views = pl.d.v.B;  // points_decimate_overflow
+  return MD_OK;
+}
+
 // Rendering: the list outputs of the call, thinned or not, and their device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
   const PointsParams& p = pl.p;
   const VoxelParams& v = pl.v;
   const OutlierParams& u = pl.u;
-  r.xyz = pl.thin ? v.xyz_out : pl.filt ? u.xyz_out : p.xyz;
-  r.rgb = pl.thin ? v.rgb_out : pl.filt ? u.rgb_out : p.rgb_out;
-  r.count = (pl.thin ? v.count : pl.filt ? u.count : p.count) + c.B;
+  r.xyz = pl.deci ? pl.d.v.xyz_out : pl.thin ? v.xyz_out : pl.filt ? u.xyz_out : p.xyz;
+  r.rgb = pl.deci ? pl.d.v.rgb_out : pl.thin ? v.rgb_out : pl.filt ? u.rgb_out : p.rgb_out;
+  r.count = (pl.deci ? pl.d.v.count : pl.thin ? v.count : pl.filt ? u.count : p.count) + c.B;
   r.n = (int)std::min<long>((long)c.out->capacity, list_rows(c.B, c.H, c.W, c.o->stride));
   return launch_render_points(r, m->points->rkeys.p, pl.st);
 }
@@ -839,6 +1020,10 @@ int run_raster(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   s.faces = pl.g.faces;
   s.count = pl.g.face_count + c.B;
   s.nf = (int)std::min<long>((long)c.mesh->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
+  if (pl.deci) {  // the decimated list and the decimated faces: no kept face names a row at or above `capacity`
+    s.xyz = pl.d.v.xyz_out; s.rgb = pl.d.v.rgb_out; s.faces = pl.d.faces_out; s.count = pl.d.face_count + c.B;
+    s.nf = (int)std::min<long>((long)c.dec->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
+  }
   return launch_render_mesh(s, m->points->skeys.p, pl.queue, pl.st);
 }
 
@@ -853,18 +1038,22 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
     if (s.list == 0) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
-  int32_t overflow = 0, outl_overflow = 0, unfiltered = 0;
+  int32_t overflow = 0, outl_overflow = 0, unfiltered = 0, dec_overflow[2] = {0, 0};
+  if (pl.deci) MD_TRY(d2h(&dec_overflow[0], voxel_flags(m->points->dtable.p, pl.d.v.n), 4));
+  if (pl.deci) MD_TRY(d2h(&dec_overflow[1], decimate_flags(m->points->dtable.p, pl.d.v.n, pl.d.nf, pl.d.v.B), 4));
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
   if (pl.filt) MD_TRY(d2h(&outl_overflow, outlier_flags(m->points->otable.p, pl.u.n), 4));
   if (pl.filt) MD_TRY(d2h(&unfiltered, pl.u.in_count + c.B, 4));
   MD_HIP(hipStreamSynchronize(pl.st));
+  if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "decimation: a probe loop ran out of table slots");
   if (outl_overflow) MD_FAIL(MD_ERR_HIP, "outlier removal: a probe loop ran out of table slots");
   if (overflow) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
   if (!c.out->count) return MD_OK;
   const size_t n = std::min((size_t)c.out->count[c.B], (size_t)c.out->capacity);
   const size_t nf = pl.mesh && c.mesh->faces ? std::min((size_t)c.mesh->face_count[c.B], (size_t)c.mesh->face_capacity) : 0;
+  const size_t nd = pl.deci && c.dec->face_count ? std::min((size_t)c.dec->face_count[c.B], (size_t)c.dec->face_capacity) : 0;
   for (const OutSlot& s : pl.slots)
-    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 3 ? std::min((size_t)std::max(unfiltered, 0), s.rows) : s.list == 2 ? nf : n) * s.row_bytes));
+    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 4 ? nd : s.list == 3 ? std::min((size_t)std::max(unfiltered, 0), s.rows) : s.list == 2 ? nf : n) * s.row_bytes));
   MD_HIP(hipStreamSynchronize(pl.st));
   return MD_OK;
 }
@@ -872,7 +1061,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
 // The stages in the order a captured graph bakes: every grow of the device path before anything is enqueued, then the work.
 int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) {
   if (!m->points) m->points = new md_model_s::PointsState();
-  PointsPlan pl{st, dual, false, false, false, (size_t)c.B * c.H * c.W};
+  PointsPlan pl{st, dual, false, false, false, false, (size_t)c.B * c.H * c.W};
   auto timed = [&](const char* name, int (*stage)(md_model_s*, const PointsCall&, PointsPlan&)) -> int {
     Run r{m, st, c.B};
     r.begin(name);
@@ -888,6 +1077,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (pl.mesh) MD_TRY(timed("points_mesh", run_mesh));
   if (pl.filt) MD_TRY(timed("points_outlier", run_outlier));
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
+  if (pl.deci) MD_TRY(timed("points_decimate", run_decimate));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
@@ -920,6 +1110,15 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   MD_TRY(check_voxel(c.vox, out, false));
   if (voxel_on(c.vox) && list_rows(B, H, W, o->stride) >= (1l << 30))
     MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
+  MD_TRY(check_decimate_part(c.dec, out));
+  if (decimate_on(c.dec)) {
+    if (!c.mesh) MD_FAIL(MD_ERR_INVALID_ARG, "decimation needs a mesh request");
+    if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "decimation needs the list's `count`");
+    if (voxel_on(c.vox)) MD_FAIL(MD_ERR_INVALID_ARG, "decimation together with voxel thinning: two grids; the decimation is the thinning");
+    if (outlier_on(c.outl)) MD_FAIL(MD_ERR_INVALID_ARG, "decimation together with outlier removal: the rows the faces name no longer exist");
+    if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
+  }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));
   if (outlier_on(c.outl)) {
@@ -936,7 +1135,9 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (c.rst) {
     MD_TRY(check_raster(c.rst->T, c.rst->H, c.rst->W, &c.rst->cam, &c.rst->opts, &c.rst->out, out->rgb != nullptr));
     if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the list outputs `xyz` and `count`");
-    if (!c.mesh || !c.mesh->faces || !c.mesh->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the mesh outputs `faces` and `face_count`");
+    if (decimate_on(c.dec)) {
+      if (!c.dec->faces || !c.dec->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the decimation outputs `faces` and `face_count`");
+    } else if (!c.mesh || !c.mesh->faces || !c.mesh->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the mesh outputs `faces` and `face_count`");
   }
   if (c.fo) {
     MD_TRY(check_filter(c.fo, s, B, H, W));
@@ -979,6 +1180,11 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     const md_points_render& r = *c.rnd;
     key_add(key, 0x524e4452u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px);
     key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.radius, r.out.depth, r.out.index, r.out.rgb, r.out.filled);
+  }
+  if (decimate_on(c.dec)) {  // voxel == 0: the key, and the graph, of the call without decimation
+    const md_points_decimate& d = *c.dec;
+    key_add(key, 0x44454349u, d.voxel, d.index, d.weight, d.dropped, d.remap, d.faces, d.face_index, d.face_count, d.face_capacity, d.faces_dropped);
+    key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
   }
   if (mesh_on(c.mesh))  // every output null: the key, and the graph, of the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);

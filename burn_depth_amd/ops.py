@@ -538,6 +538,43 @@ def radius_outliers(dev: Device, xyz: torch.Tensor, radius: float, min_neighbour
     return out
 
 
+def decimate_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, voxel: float, conf: Optional[torch.Tensor] = None,
+                  rgb: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+                  face_capacity: Optional[int] = None, out: Optional[PointCloud] = None) -> PointCloud:
+    """md_op_decimate_mesh: vertices xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) and faces int32 [F,3] over them -> `PointCloud`
+    with one vertex per occupied voxel of side `voxel` (every vertex output is `voxel_thin`'s), remap int32 [N], the kept faces
+    int32 [face_capacity,3] over the output rows with face_index int32 [face_capacity], face_count int32 [2] and faces_dropped
+    int32 [3] (invalid, degenerate, duplicate). capacity defaults to N, face_capacity to F. `out`: a PointCloud of an earlier call
+    to write into again. Bit-identical to `pipeline.decimate_mesh`."""
+    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
+    xyz, faces = _f32c(xyz), faces.contiguous()
+    N, F = int(xyz.shape[0]), int(faces.shape[0])
+    conf = _f32c(conf).reshape(N) if conf is not None else None
+    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if out is None:
+        cap = N if capacity is None else int(capacity)
+        fcap = F if face_capacity is None else int(face_capacity)
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=xyz.device)  # noqa: E731
+        out = PointCloud(xyz=f(cap, 3), conf=f(cap) if conf is not None else None, rgb=f(cap, 3, dt=torch.uint8) if rgb is not None else None,
+                         normals=f(cap, 3) if normals is not None else None, count=f(2, dt=torch.int32), index=f(cap, dt=torch.int32),
+                         weight=f(cap, dt=torch.int32), dropped=f(1, dt=torch.int32), remap=f(N, dt=torch.int32),
+                         faces=f(fcap, 3, dt=torch.int32), face_index=f(fcap, dt=torch.int32), face_count=f(2, dt=torch.int32),
+                         faces_dropped=f(3, dt=torch.int32))
+    assert out.remap is None or int(out.remap.shape[0]) >= N, "remap covers the input rows"
+    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index, out.weight) if t is not None]
+    frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
+    dec = _lib.MdPointsDecimate(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped), ptr(out.remap), ptr(out.faces),
+                                ptr(out.face_index), ptr(out.face_count), min(frows) if frows else 0, ptr(out.faces_dropped))
+    _lib.check(_lib.load().md_op_decimate_mesh(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, _p(faces), F, C.byref(dec),
+                                               C.byref(outs), _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
 def render_points(dev: Device, xyz: torch.Tensor, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None,
                   rgb: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, *, pixel_offset: float = 0.0, z_near: float = 0.0,
                   z_far: float = 0.0, radius: int = 0, out: Optional[RenderedPoints] = None) -> RenderedPoints:

@@ -20,6 +20,8 @@
   z-buffered into target cameras on 64-bit keys
 * `render_mesh`                               -- the host reference of `md_op_render_mesh` / `md_infer_points_raster`: the faces of the
   mesh rasterised into target cameras, integer coverage at 1/256 pixel and 64-bit keys
+* `decimate_mesh`                             -- the host reference of `md_op_decimate_mesh`: voxel thinning's vertices, the faces
+  re-indexed to them, collapsed faces and later copies of an oriented triangle dropped
 * `radius_outliers`                           -- the host reference of `md_op_radius_outliers` / `md_infer_points_outlier`: the rows
   with enough neighbours in the 27 cells around their own, bit-identical to the device's
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
@@ -554,6 +556,71 @@ def voxel_thin(xyz, voxel, conf=None, rgb=None, normals=None, counts=None) -> Ho
 
 
 @dataclass
+class HostDecimated:
+    vertices: HostVoxels             # exactly voxel_thin's outputs on the same rows
+    remap: np.ndarray                # int32 [N]: the output row of the survivor of every input row's voxel (the true rank), -1 outside the grid
+    faces: np.ndarray                # int32 [K,3]: the kept faces over the output rows, in ascending source face, winding unchanged
+    face_index: np.ndarray           # int32 [K]: the source face
+    face_count: np.ndarray           # int32 [B+1]: kept faces per view of their source face, then their total
+    faces_dropped: np.ndarray        # int32 [3]: invalid, degenerate, duplicate faces
+
+
+def decimate_mesh(xyz, faces, voxel, conf=None, rgb=None, normals=None, counts=None, face_counts=None, capacity=None) -> HostDecimated:
+    """The host reference of md_op_decimate_mesh (include/mi_depth.h states the contract): vertex clustering. The vertices are
+    voxel_thin's; face (p, q, r) maps to (remap[p], remap[q], remap[r]) and is, in this order, invalid (a corner outside 0..N-1, a
+    remap of -1 or one >= capacity), degenerate (two mapped corners equal), a duplicate (an earlier live face has the same triple
+    after both are rotated so that the smallest index comes first; the reversed triple is another face) or kept, as its mapped
+    triple in the input's rotation. capacity: the rows the vertex outputs hold (default N); the returned lists are not cut to it.
+    counts / face_counts: the rows / faces of every view of the input, [B] (default: one view). Selection only: the device
+    kernels (kernels/decimate.hip) give the same bits."""
+    v = voxel_thin(xyz, voxel, conf, rgb, normals, counts)
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    N = len(p)
+    fc = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    F = len(fc)
+    if F >= 1 << 30:
+        raise ValueError("fewer than 2^30 faces")
+    cap = N if capacity is None else int(capacity)
+    if cap < 0:
+        raise ValueError("capacity is negative")
+    vs, half = np.float32(voxel), np.float32(1 << 20)
+    with np.errstate(all="ignore"):
+        c = np.floor(p / vs)
+        ok = np.isfinite(p).all(1) & (c >= -half).all(1) & (c < half).all(1)
+    cell = (c[ok].astype(np.int64) + (1 << 20)).astype(np.uint64)
+    key = (cell[:, 0] << np.uint64(42)) | (cell[:, 1] << np.uint64(21)) | cell[:, 2]
+    full = np.zeros(N, np.uint64)
+    full[ok] = key
+    skey = full[v.index]  # one key per output row; every in-range row's key is among them
+    by_key = np.argsort(skey)
+    remap = np.full(N, -1, np.int32)
+    remap[ok] = by_key[np.searchsorted(skey[by_key], key)].astype(np.int32)
+    inside = ((fc >= 0) & (fc < N)).all(1)
+    padded = np.append(remap, np.int32(-1))  # a corner outside the list reads the -1 behind it
+    m = padded[np.where(inside[:, None], fc, N)]
+    invalid = ~inside | (m < 0).any(1) | (m >= cap).any(1)
+    degenerate = ~invalid & ((m[:, 0] == m[:, 1]) | (m[:, 1] == m[:, 2]) | (m[:, 0] == m[:, 2]))
+    live = np.nonzero(~invalid & ~degenerate)[0]
+    lm = m[live]
+    k = np.argmin(lm, axis=1)  # distinct corners: the smallest is unique
+    at = np.arange(len(lm))
+    rot = np.stack([lm[at, k], lm[at, (k + 1) % 3], lm[at, (k + 2) % 3]], axis=1)
+    if len(rot):
+        _, first = np.unique(rot, axis=0, return_index=True)  # the first occurrence = the smallest source face
+        kept = live[np.sort(first)]
+    else:
+        kept = live
+    if face_counts is None:
+        bounds = np.array([0, F], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(face_counts, np.int64).reshape(-1))]), F)
+    per_view = np.diff(np.searchsorted(kept, bounds, side="left"))
+    face_count = np.concatenate([per_view, [len(kept)]]).astype(np.int32)
+    dropped = np.array([invalid.sum(), degenerate.sum(), len(live) - len(kept)], np.int32)
+    return HostDecimated(v, remap, m[kept], kept.astype(np.int32), face_count, dropped)
+
+
+@dataclass
 class HostOutliers:
     xyz: np.ndarray                  # f32 [M,3]: the surviving input rows, in ascending input index
     conf: Optional[np.ndarray]       # f32 [M]
@@ -1025,8 +1092,8 @@ class AnyDepthModel:
         """`md_infer_points`: the model, then its depth (and cameras) as a point cloud, in one device call -> `PointCloud`.
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
-        render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`) and outlier=
-        (`md_infer_points_outlier`) included."""
+        render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`), outlier=
+        (`md_infer_points_outlier`) and decimate= (`md_infer_points_decimate`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

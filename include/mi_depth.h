@@ -737,6 +737,88 @@ int md_infer_points_outlier(md_model_t m, const float* nchw, int B, int H, int W
                             const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
                             const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
                             const md_points_raster* rst, const md_points_outlier* outl, int out_kind, void* stream);
+
+/* ---- point path: vertex-clustering decimation of a mesh ---------------------------------------------------------------------
+ * A vertex list xyz f32 [N,3] with optional parallel rows conf f32 [N], rgb u8 [N,3] and normals f32 [N,3], and faces int32
+ * [F,3] over its rows -> one vertex per occupied voxel of side `voxel` > 0 and the faces re-indexed to those vertices.
+ * Selection only: a vertex is an input row, a face is an input face with new indices; nothing is averaged, no float is summed
+ * and nothing depends on the order in which threads arrive (pipeline.decimate_mesh restates it in numpy bit for bit).
+ *   vertices: exactly voxel thinning's. Cell, range test, key and rank w are md_points_voxel's; the survivor of a voxel is its
+ *     in-range row with the largest w, among equals the smallest index; the survivors come in ascending input index; index,
+ *     weight, count [B+1], dropped and capacity behave as there, so every vertex output is bitwise md_op_voxel_thin's on the
+ *     same rows. A vertex that no face names stays in the list.
+ *   remap int32 [N]: remap[i] = the output row of the survivor of row i's voxel, -1 for a row out of range. It is the true
+ *     rank, also when it is >= capacity (that row was not written).
+ *   faces: face f with the corners (p, q, r) maps to (remap[p], remap[q], remap[r]) and falls into exactly one class, tested
+ *     in this order:
+ *       1 invalid     a corner is < 0 or >= N, or its remap is -1, or its remap is >= capacity: no kept face names a row that
+ *                     was not written;
+ *       2 degenerate  two of the mapped corners are equal;
+ *       3 duplicate   some face g < f that is neither invalid nor degenerate has the same ORIENTED triangle: its mapped triple
+ *                     equals f's after each is rotated so that its smallest index comes first. The three cyclic rotations
+ *                     of a triple are one face. The reversed triple is a DIFFERENT face and is kept: it is the other side of
+ *                     a fold, and the winding of a face carries meaning for the rasteriser's culling and for normals;
+ *       4 kept        otherwise.
+ *     The kept faces come in ascending f, each written as its mapped triple in the rotation the input had, so the winding is
+ *     unchanged. face_index = the source face. face_count[b] = the kept faces whose source face belongs to view b (the views
+ *     of the faces are the prefix of the INPUT face counts; the stand-alone operator has one view), face_count[B] = their
+ *     total, also beyond face_capacity: then only the first face_capacity rows are written and the memory behind them stays
+ *     untouched. faces_dropped [3] = the sizes of classes 1, 2, 3.
+ *   limits: N < 2^30 and F < 2^30.
+ * The duplicate test is a hash set over oriented triangles in device memory: the power of two >= max(2 F, 1024) int32 slots
+ * that hold a face id (-1 = empty), linear probing, a fixed 64-bit mixer over the rotated triple. The identity of a slot is the
+ * triple of whichever id it holds, all ids that ever sit in one slot have the same triple, and the slot ends as the smallest of
+ * them (atomicMin), so the hash and the order of arrival decide where a triangle lives and never which face is kept. Table and
+ * counters are reset on the stream inside every call. */
+typedef struct md_points_decimate {
+  float voxel;            /* voxel side, finite and > 0; 0 = no decimation (md_infer_points_decimate) */
+  int32_t* index;         /* int32 [capacity]: the source row of every vertex; needs count. NULL = skip */
+  int32_t* weight;        /* int32 [capacity]: in-range rows of the vertex's voxel; needs count. NULL = skip */
+  int32_t* dropped;       /* int32 [1]: rows not finite or out of range. NULL = skip */
+  int32_t* remap;         /* int32 [N]: the output row of every input row's voxel, -1 out of range. NULL = skip */
+  int32_t* faces;         /* int32 [face_capacity,3]: the kept faces over the output rows; needs face_count. NULL = skip */
+  int32_t* face_index;    /* int32 [face_capacity]: the source face of every kept face; needs face_count. NULL = skip */
+  int32_t* face_count;    /* int32 [B+1]: kept faces per view, then their total. NULL = skip */
+  int64_t face_capacity;  /* rows of faces / face_index, >= 0 */
+  int32_t* faces_dropped; /* int32 [3]: invalid, degenerate, duplicate faces. NULL = skip */
+} md_points_decimate;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_voxel_thin: the N rows and the F faces are one view. Of
+ * `out` the fields xyz, rgb, conf, count (int32 [2]: M twice) and capacity are used, the others must be NULL; normals_out
+ * [capacity,3] takes the normals rows; dec->face_count is int32 [2]. Everything is enqueued on `stream`; the call returns after
+ * the stream has drained, because its scratch is freed on return. Errors, before any launch: dev / dec / out NULL, xyz_dev
+ * NULL with N > 0, faces_dev NULL with F > 0, voxel not finite or <= 0, N < 0, F < 0, capacity < 0, face_capacity < 0, a
+ * compacted output (xyz, rgb, conf, normals_out, index, weight) without count, faces / face_index without face_count, an
+ * rgb / conf / normals output without that input row, a dense output or out->depth set -> MD_ERR_INVALID_ARG; N >= 2^30 or
+ * F >= 2^30 -> MD_ERR_SHAPE. A probe loop that ran out of table (impossible at load <= 0.5) -> MD_ERR_HIP after the launches;
+ * the outputs and the class counts of such a call are unspecified. */
+int md_op_decimate_mesh(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                        int64_t N, const int32_t* faces_dev, int64_t F, const md_points_decimate* dec, const md_points_outputs* out,
+                        float* normals_out, void* stream);
+/* md_infer_points_outlier with the decimation behind the mesh stage and in front of the point render and the rasteriser. With it
+ * on, the scatter fills a grow-only list of the model (at most R = B ceil(H/stride) ceil(W/stride) rows), the mesh stage writes
+ * all faces of that list (every row of it is usable as a corner) with their true count to a grow-only home of the model, and the
+ * decimation writes the caller's list (out->xyz / rgb / conf, nrm->normals, out->count) and dec's face outputs; the confidence
+ * row is the model's confidence map where it has one, whether or not out->conf is set. dec->remap is int32 [R]: rows behind the
+ * undecimated total hold -1. dec->face_count is int32 [B+1], by the view of the source face. mesh must be given (its max_rtol
+ * sets the edge test; its outputs may all be NULL): mesh->faces and mesh->face_count, if taken, still receive the undecimated
+ * mesh of the undecimated list, mesh->pixel_index names rows of that list and dec->remap carries them over. The point render and
+ * the rasteriser see the decimated list and the decimated faces; rasterising then needs dec->faces and dec->face_count. dec's
+ * pointers are of out_kind. dec NULL or voxel == 0 (its pointers then NULL): md_infer_points_outlier on the same arguments, the
+ * same launches and bits. The graph key contains dec's fields. Errors as md_infer_points_outlier's, plus, before any launch:
+ * voxel not finite or negative, face_capacity < 0, faces / face_index without face_count, index / weight without count, any of
+ * dec's pointers with voxel == 0, decimation without a mesh request or without count, together with voxel thinning (two grids:
+ * the decimation is the thinning) or with outlier removal -> MD_ERR_INVALID_ARG; 2 R >= 2^30 -> MD_ERR_SHAPE. With host
+ * outputs a probe loop that ran out of table -> MD_ERR_HIP; with device outputs md_model_query(m, "decimate_overflow") reads
+ * the flags of the last call that was launched or captured (it waits for the device); as with "voxel_overflow" and
+ * "outlier_overflow", a replay of a graph captured for another shape does not move that record, so query after a call of the
+ * shape that was enqueued last outside a replay. After the first call of a shape nothing is allocated. */
+int md_infer_points_decimate(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                             const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                             const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                             const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                             const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec, int out_kind,
+                             void* stream);
 /* PROCESS-WIDE (returns the previous setting): the capacity of the (face, target) queue of later md_op_render_mesh /
  * md_infer_points_raster calls, 0 = the default (2^20 pairs). A push that finds the queue full draws the face in place: same
  * bits at every capacity; for the test of that branch. MD_ERR_INVALID_ARG (< 0) for a negative capacity. */

@@ -39,6 +39,11 @@ Pro image `--focal-px`).
 cut where neighbouring depths differ by more than X of the nearer one (default 0.05; 0 = no cut), computed on the device
 (`md_infer_points_mesh`; with `--views`, `ops.unproject(mesh=)`: one mesh per view, not merged). Not together with `--voxel`.
 
+`--decimate V` (with `--ply --mesh`): the mesh is decimated on the device by vertex clustering at voxel side V: one vertex per
+occupied voxel (the most confident one), the faces re-indexed, collapsed faces and later copies of a face dropped; the file then
+holds the decimated list and faces (`md_infer_points_decimate`; with `--views`, `ops.decimate_mesh` behind the per-view meshes, which
+welds the sheets of overlapping views). Not together with `--voxel` or `--outlier-radius`.
+
 `--raster-pose E.npy --raster-out view.png` (with `--ply --mesh`): the mesh is also rasterised on the device into a virtual camera with
 the world-to-camera pose E ([3,4], or [T,3,4] of which every pose is drawn and the first written), a render without holes, and its
 depth image written as a normalised PNG (`md_infer_points_raster`; with `--views`, `ops.render_mesh` on the meshes of all views).
@@ -149,6 +154,15 @@ def run_views(a) -> int:
                 return 1
             xyz, col, conf = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.decimate > 0:  # vertex clustering over the meshes of all views: the sheets are welded where they share a voxel
+            try:
+                pc = ops.decimate_mesh(dev, xyz, pc.faces[:len(faces)], a.decimate, conf=conf, rgb=col, normals=nrm)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy()
+            xyz, col, _ = pc.points()
+            nrm = pc.normals[:xyz.shape[0]] if a.normals else None
         if a.voxel > 0:  # one point per occupied voxel over all views: the most confident one
             try:
                 pc = ops.voxel_thin(dev, xyz, a.voxel, conf=conf, rgb=col, normals=nrm)
@@ -219,6 +233,9 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh", action="store_true", help="--ply: also write the triangle mesh of the depth grid over the points (md_infer_points_mesh)")
     ap.add_argument("--mesh-rtol", type=float, default=0.05,
                     help="--mesh: cut an edge whose depths differ by more than this fraction of the nearer one (0 = no cut)")
+    ap.add_argument("--decimate", type=float, default=0.0,
+                    help="--ply --mesh: vertex-clustering decimation at this voxel side: one vertex per voxel, collapsed and doubled faces dropped "
+                         "(md_infer_points_decimate; 0 = off)")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
     ap.add_argument("--raster-out", default="", help="--raster-pose: the rasterised depth of the first pose as a normalised PNG")
     a = ap.parse_args(argv)
@@ -227,6 +244,9 @@ def main(argv=None) -> int:
         return 2
     if a.mesh and (not a.ply or a.voxel > 0):
         print("--mesh goes with --ply, and not with --voxel (a thinned list has no grid)", file=sys.stderr)
+        return 2
+    if a.decimate != 0 and (not (a.ply and a.mesh) or a.voxel > 0 or a.outlier_radius != 0):
+        print("--decimate goes with --ply --mesh, and not with --voxel or --outlier-radius (the decimation is the thinning)", file=sys.stderr)
         return 2
     if a.outlier_radius != 0 and (not a.ply or a.mesh):
         print("--outlier-radius goes with --ply, and not with --mesh (the faces name rows of the unfiltered list)", file=sys.stderr)
@@ -288,7 +308,8 @@ def main(argv=None) -> int:
                                     world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
                                     normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render,
                                     mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None, raster=raster,
-                                    outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None)
+                                    outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None,
+                                    decimate=dict(voxel=a.decimate) if a.decimate else None)
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
