@@ -86,6 +86,13 @@ class MdPointsDecimate(C.Structure):
                 ("faces_dropped", C.c_void_p)]
 
 
+class MdPointsComponents(C.Structure):
+    """md_points_components (include/mi_depth.h)."""
+    _fields_ = [("min_faces", C.c_int32), ("compact", C.c_int32), ("label", C.c_void_p), ("component_faces", C.c_void_p), ("index", C.c_void_p),
+                ("remap", C.c_void_p), ("faces", C.c_void_p), ("face_index", C.c_void_p), ("face_count", C.c_void_p),
+                ("face_capacity", C.c_int64), ("stats", C.c_void_p)]
+
+
 class MdRenderOpts(C.Structure):
     """md_render_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
@@ -258,6 +265,12 @@ SYMBOLS = {
                                       C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
                                       C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate), _I, _P]),
     "md_op_decimate_mesh": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsDecimate), C.POINTER(MdPointsOutputs), _P, _P]),
+    "md_infer_points_components": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                        C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                        C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
+                                        C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate),
+                                        C.POINTER(MdPointsComponents), _I, _P]),
+    "md_op_mesh_components": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsComponents), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),

@@ -288,6 +288,14 @@ int launch_copy_faces(const int32_t* faces, const int32_t* count, int B, long ro
   return MD_OK;
 }
 
+int launch_rank_rows(const unsigned long long* bits, const int* offsets, int n, int32_t* remap, hipStream_t s) {
+  if (n <= 0) return MD_OK;
+  if (!bits || !offsets || !remap) MD_FAIL(MD_ERR_INVALID_ARG, "rank step: a null argument");
+  hipLaunchKernelGGL(decimate_rank_kernel, dim3(tiles_of(n)), dim3(kThreads), 0, s, bits, offsets, remap);
+  MD_HIP(hipGetLastError());
+  return MD_OK;
+}
+
 size_t decimate_scratch_bytes(int n, int nf, int B) { return carve(nullptr, n > 0 ? n : 0, nf > 0 ? nf : 0, B > 0 ? B : 1).bytes; }
 
 const int32_t* decimate_flags(const void* scratch, int n, int nf, int B) {

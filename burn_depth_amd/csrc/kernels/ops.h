@@ -161,6 +161,35 @@ const int32_t* decimate_flags(const void* scratch, int n, int nf, int B);
 // first min(count[B], rows, capacity) faces; the memory behind them stays untouched. Nothing without count_out; faces_out may be null
 int launch_copy_faces(const int32_t* faces, const int32_t* count, int B, long rows, int32_t* faces_out, int32_t* count_out, long capacity,
                       hipStream_t s);
+// the decimation's rank step for any keep bits in the ballot layout with the tile offsets of their scan: remap[i] = the output
+// row of every kept row i < n; the other rows of remap are not written
+int launch_rank_rows(const unsigned long long* bits, const int* offsets, int n, int32_t* remap, hipStream_t s);
+
+// ---- connected components of a mesh, island removal (kernels/components.hip, kernels/components_math.h; md_op_mesh_components) ----
+// Faces [nf,3] over n rows -> label (the smallest row of every row's component, by a lock-free union-find), the valid faces of
+// every component, and the faces of the components with at least min_faces faces, in input order. With `compact` the rows those
+// faces name are compacted through launch_list_compact (v's row outputs, v.index, v.count) and the faces are written through
+// remap. Every pointer is a device pointer. Integers only: nothing depends on the order of arrival.
+struct ComponentsParams {
+  VoxelParams v;                           // the rows: v.n, v.B, v.in_count; with `compact` also the row inputs / outputs, v.index, v.count, v.capacity
+  const int32_t* faces = nullptr;          // [nf,3]
+  const int32_t* in_face_count = nullptr;  // [v.B + 1] per-view faces of the input, then their total = the live faces; null: nf faces, one view
+  int nf = 0;                              // faces the launches cover: the live count is min(in_face_count[B], nf)
+  int min_faces = 1;
+  int compact = 0;
+  int32_t* label = nullptr;                // [v.n]; rows behind the live count: -1
+  int32_t* component_faces = nullptr;      // [v.n]; rows behind the live count: 0
+  int32_t* remap = nullptr;                // [v.n], compact only; null: it lives in the scratch
+  int32_t* faces_out = nullptr;            // [face_capacity,3]
+  int32_t* face_index = nullptr;           // [face_capacity]
+  int32_t* face_count = nullptr;           // [v.B + 1]; null: no face scan / scatter
+  int32_t* stats = nullptr;                // [5] invalid, dropped, clipped, components, components kept; null: they go to the scratch
+  long face_capacity = 0;
+};
+// bytes of the scratch: parent and size 4 B per row each, a remap and row count home, ballot words / tile counts / tile offsets of
+// the faces and of the rows, the counters
+size_t components_scratch_bytes(int n, int nf, int B);
+int launch_mesh_components(const ComponentsParams& p, void* scratch, hipStream_t s);
 
 // ---- radius outlier removal (kernels/outlier.hip; md_op_radius_outliers, md_infer_points_outlier) ----
 // A point list xyz [n,3] (+ conf, rgb, normals rows) -> the rows with at least k other rows within `radius`, in ascending input

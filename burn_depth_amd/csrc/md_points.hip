@@ -47,6 +47,8 @@ struct md_model_s::PointsState {
   md::GrowBuf<float> scams;       // the device copy of its host target cameras, laid out as rcams
   md::GrowBuf<void> dtable;       // md_infer_points_decimate: the decimation's scratch (decimate_scratch_bytes)
   md::GrowBuf<void> dfaces;       // its input: the faces of the unthinned list [2 rows,3] | their face_count [B+1]
+                                  // (md_infer_points_components: the unfiltered faces of the call's list, likewise)
+  md::GrowBuf<void> ctable;       // md_infer_points_components: the components' scratch (components_scratch_bytes)
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
@@ -195,6 +197,24 @@ int check_decimate_part(const md_points_decimate* d, const md_points_outputs* ou
   if (d->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)d->face_capacity);
   if ((d->faces || d->face_index) && !d->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
   MD_TRY(need_count(d->index || d->weight, out, "index / weight"));
+  return MD_OK;
+}
+
+bool components_on(const md_points_components* k) { return k && k->min_faces != 0; }
+
+// model call: min_faces == 0 is the call without the stage and takes none of its outputs; the in-call stage is face-only
+int check_components_part(const md_points_components* k) {
+  if (!k) return MD_OK;
+  if (k->min_faces < 0) MD_FAIL(MD_ERR_INVALID_ARG, "min_faces = %d: must be >= 0", k->min_faces);
+  if (k->compact) MD_FAIL(MD_ERR_INVALID_ARG, "the model call does not compact the list: `compact` must be 0");
+  if (k->index || k->remap) MD_FAIL(MD_ERR_INVALID_ARG, "index / remap without `compact`");
+  if (k->min_faces == 0) {
+    if (k->label || k->component_faces || k->faces || k->face_index || k->face_count || k->stats)
+      MD_FAIL(MD_ERR_INVALID_ARG, "component outputs without min_faces");
+    return MD_OK;
+  }
+  if (k->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)k->face_capacity);
+  if ((k->faces || k->face_index) && !k->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
   return MD_OK;
 }
 
@@ -540,6 +560,50 @@ int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces,
   return MD_OK;
 }
 
+int op_mesh_components(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_components* comp,
+                       const md_points_outputs* out, float* normals_out, hipStream_t stream) {
+  if (!comp) MD_FAIL(MD_ERR_INVALID_ARG, "component options are null");
+  if (comp->min_faces < 1) MD_FAIL(MD_ERR_INVALID_ARG, "min_faces = %d: must be >= 1", comp->min_faces);
+  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
+  if (F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)F);
+  if (comp->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)comp->face_capacity);
+  if ((comp->faces || comp->face_index) && !comp->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
+  if (out && (out->point_map || out->mask || out->depth)) MD_FAIL(MD_ERR_INVALID_ARG, "components have no dense output");
+  if (!comp->compact) {
+    if (comp->index || comp->remap || normals_out || (out && (out->xyz || out->rgb || out->conf || out->count)))
+      MD_FAIL(MD_ERR_INVALID_ARG, "vertex outputs, index, remap and count need `compact`");
+  } else {
+    if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+    MD_TRY(check_capacity(out));
+    MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out || comp->index, out, "the compacted outputs"));
+    if (out->xyz && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "an xyz output needs the xyz rows");
+    if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
+    if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
+    if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+  }
+  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 rows, got %lld", (long long)in.N);
+  if (F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 faces, got %lld", (long long)F);
+  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  ComponentsParams p;
+  p.v.n = (int)in.N; p.v.B = 1;
+  if (comp->compact) {
+    p.v.xyz = in.xyz; p.v.conf = in.conf; p.v.rgb = in.rgb; p.v.normals = in.normals;
+    p.v.xyz_out = out->xyz; p.v.conf_out = out->conf; p.v.rgb_out = out->rgb; p.v.normals_out = normals_out;
+    p.v.index = comp->index; p.v.count = out->count; p.v.capacity = out->capacity;
+    p.compact = 1; p.remap = comp->remap;
+  }
+  p.faces = faces; p.nf = (int)F; p.min_faces = comp->min_faces;
+  p.label = comp->label; p.component_faces = comp->component_faces;
+  p.faces_out = comp->faces; p.face_index = comp->face_index; p.face_count = comp->face_count; p.stats = comp->stats;
+  p.face_capacity = (long)comp->face_capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(components_scratch_bytes(p.v.n, p.nf, 1)));
+  return scratch.finish(launch_mesh_components(p, scratch.p, st));
+}
+
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream) {
   MD_TRY(check_render(T, H, W, cam, o, out, in.rgb != nullptr));
@@ -626,12 +690,13 @@ struct OutSlot {  // a host output's way back: `rows` rows of `row_bytes` from i
              // 2: the faces: likewise with `face_count` and `face_capacity`
              // 3: rows parallel to the unfiltered list (outl->neighbours): likewise with its device count
              // 4: the decimated faces: as 2 with dec's `face_count` and `face_capacity`
+             // 5: the faces of the kept components: as 2 with comp's `face_count` and `face_capacity`
 };
 
 // What the stages of one call share: its device pointers, resolved by plan_homes, stage_inputs and run_model.
 struct PointsPlan {
   hipStream_t st;
-  bool dual, thin, mesh, filt, deci;
+  bool dual, thin, mesh, filt, deci, comp;
   size_t npx;
   float *depth = nullptr, *raw = nullptr, *conf = nullptr;  // depth: what is unprojected; raw: what the model writes
   const float* x = nullptr;                                 // the image on the device
@@ -644,7 +709,8 @@ struct PointsPlan {
   MeshParams g;     // mesh: launch_mesh's, from the depth that is unprojected and the scratch of `p`'s launches
   RasterParams s;   // c.rst given: launch_render_mesh's, from the list outputs and the faces of the call
   DecimateParams d; // deci: launch_decimate_mesh's, from the model's own list and the faces `gd` wrote; d.v fills the list outputs of the call
-  MeshParams gd;    // deci: the mesh stage's second set of face outputs, the model's own, complete and with the true count
+  MeshParams gd;    // deci / comp: the mesh stage's second set of face outputs, the model's own, complete and with the true count
+  ComponentsParams k;  // comp: launch_mesh_components', from the list's count and the faces `gd` wrote
   int queue = 0;    // its queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   std::vector<OutSlot> slots;
@@ -775,6 +841,16 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(c.mesh->face_count, pl.g.face_count, 4, (size_t)c.B + 1, 0);
     slot(c.mesh->faces, pl.g.faces, 12, (size_t)c.mesh->face_capacity, 2);
   }
+  if (pl.comp) {
+    const md_points_components& k = *c.comp;
+    const size_t rows = (size_t)list_rows(c.B, c.H, c.W, c.o->stride);
+    slot(k.label, pl.k.label, 4, rows, 0);
+    slot(k.component_faces, pl.k.component_faces, 4, rows, 0);
+    slot(k.face_count, pl.k.face_count, 4, (size_t)c.B + 1, 0);
+    slot(k.stats, pl.k.stats, 4, 5, 0);
+    slot(k.faces, pl.k.faces_out, 12, (size_t)k.face_capacity, 5);
+    slot(k.face_index, pl.k.face_index, 4, (size_t)k.face_capacity, 5);
+  }
   return total;
 }
 
@@ -818,8 +894,12 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     if (c.in_kind == MD_MEM_HOST) MD_TRY(grow(m, st, f->scams, (size_t)c.rst->T * 22 * 4));
   }
   pl.deci = decimate_on(c.dec);
-  pl.mesh = mesh_on(c.mesh) || pl.deci;
-  if (pl.deci) {  // the faces name rows of the model's own, unthinned list: every row of it is usable; the map always has a home
+  pl.comp = components_on(c.comp);
+  pl.mesh = mesh_on(c.mesh) || pl.deci || pl.comp;
+  if (pl.comp) {  // the caller's list as ever (a corner is usable below its capacity); the map always has a home
+    pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
+    MD_TRY(grow(m, st, f->mesh, mesh_scratch_bytes(B, H, W, c.o->stride) + align_up(pl.npx * 4, 256)));
+  } else if (pl.deci) {  // the faces name rows of the model's own, unthinned list: every row of it is usable; the map always has a home
     const long rows = list_rows(B, H, W, c.o->stride);
     pl.g = make_mesh(B, H, W, c.o->stride, rows, *c.mesh);
     MD_TRY(grow(m, st, f->mesh, mesh_scratch_bytes(B, H, W, c.o->stride) + align_up(pl.npx * 4, 256)));
@@ -830,6 +910,18 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (const size_t total = place_outputs(c, pl, nullptr)) {
     MD_TRY(grow(m, st, f->out, total));
     place_outputs(c, pl, (char*)f->out.p);
+  }
+  if (pl.comp) {  // all faces of the call's list go to the model's face home; the stage reads them and the list's device count
+    ComponentsParams& k = pl.k;
+    const long rows = list_rows(B, H, W, c.o->stride), nf = 2 * rows;
+    const size_t b_faces = align_up((size_t)nf * 12, 256);
+    MD_TRY(grow(m, st, f->dfaces, b_faces + align_up((size_t)(B + 1) * 4, 256)));
+    MD_TRY(grow(m, st, f->ctable, components_scratch_bytes((int)rows, (int)nf, B)));
+    pl.gd = pl.g;
+    pl.gd.faces = (int32_t*)f->dfaces.p; pl.gd.face_count = (int32_t*)((char*)f->dfaces.p + b_faces); pl.gd.face_capacity = nf;
+    k.v.in_count = p.count; k.v.n = (int)rows; k.v.B = B;
+    k.faces = pl.gd.faces; k.in_face_count = pl.gd.face_count; k.nf = (int)nf;
+    k.min_faces = c.comp->min_faces; k.face_capacity = (long)c.comp->face_capacity;
   }
   if (!pl.thin && !pl.filt && !pl.deci) return MD_OK;
   // voxel thinning / outlier removal: the scatter fills the model's own list, the last of the two writes where the list would
@@ -964,8 +1056,9 @@ int run_unproject(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
 // The mesh of the list: needs the scratch of run_unproject's launches before anything reuses it.
 int run_mesh(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.g.depth = pl.depth;
-  if (pl.deci) {  // the map, then the model's own faces, complete, for the decimation; the caller's, if it takes them, are a copy:
-                  // both have every row of the list as a usable corner, so they are the same faces
+  if (pl.deci || pl.comp) {  // the map, then the model's own faces, complete, for the decimation / the components; the caller's,
+                             // if it takes them, are a copy: both have the same rows of the list as usable corners, so they are
+                             // the same faces
     void* home = m->points->mesh.p;
     int32_t* pix = pl.pix ? pl.pix : (int32_t*)((char*)home + mesh_scratch_bytes(c.B, c.H, c.W, c.o->stride));
     MD_TRY(launch_mesh_index(c.B, c.H, c.W, m->points->scratch.p, pix, pl.st));
@@ -997,6 +1090,9 @@ int run_decimate(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   return MD_OK;
 }
 
+// Island removal: the faces the mesh stage left in the model's home -> comp's outputs. The list is not touched.
+int run_components(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_mesh_components(pl.k, m->points->ctable.p, pl.st); }
+
 // Rendering: the list outputs of the call, thinned or not, and their device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
@@ -1023,6 +1119,10 @@ int run_raster(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.deci) {  // the decimated list and the decimated faces: no kept face names a row at or above `capacity`
     s.xyz = pl.d.v.xyz_out; s.rgb = pl.d.v.rgb_out; s.faces = pl.d.faces_out; s.count = pl.d.face_count + c.B;
     s.nf = (int)std::min<long>((long)c.dec->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
+  }
+  if (pl.comp) {  // the list as ever, the faces of the kept components
+    s.faces = pl.k.faces_out; s.count = pl.k.face_count + c.B;
+    s.nf = (int)std::min<long>((long)c.comp->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
   }
   return launch_render_mesh(s, m->points->skeys.p, pl.queue, pl.st);
 }
@@ -1052,8 +1152,9 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
   const size_t n = std::min((size_t)c.out->count[c.B], (size_t)c.out->capacity);
   const size_t nf = pl.mesh && c.mesh->faces ? std::min((size_t)c.mesh->face_count[c.B], (size_t)c.mesh->face_capacity) : 0;
   const size_t nd = pl.deci && c.dec->face_count ? std::min((size_t)c.dec->face_count[c.B], (size_t)c.dec->face_capacity) : 0;
+  const size_t nk = pl.comp && c.comp->face_count ? std::min((size_t)c.comp->face_count[c.B], (size_t)c.comp->face_capacity) : 0;
   for (const OutSlot& s : pl.slots)
-    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 4 ? nd : s.list == 3 ? std::min((size_t)std::max(unfiltered, 0), s.rows) : s.list == 2 ? nf : n) * s.row_bytes));
+    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 5 ? nk : s.list == 4 ? nd : s.list == 3 ? std::min((size_t)std::max(unfiltered, 0), s.rows) : s.list == 2 ? nf : n) * s.row_bytes));
   MD_HIP(hipStreamSynchronize(pl.st));
   return MD_OK;
 }
@@ -1061,7 +1162,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
 // The stages in the order a captured graph bakes: every grow of the device path before anything is enqueued, then the work.
 int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) {
   if (!m->points) m->points = new md_model_s::PointsState();
-  PointsPlan pl{st, dual, false, false, false, false, (size_t)c.B * c.H * c.W};
+  PointsPlan pl{st, dual, false, false, false, false, false, (size_t)c.B * c.H * c.W};
   auto timed = [&](const char* name, int (*stage)(md_model_s*, const PointsCall&, PointsPlan&)) -> int {
     Run r{m, st, c.B};
     r.begin(name);
@@ -1078,6 +1179,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (pl.filt) MD_TRY(timed("points_outlier", run_outlier));
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
   if (pl.deci) MD_TRY(timed("points_decimate", run_decimate));
+  if (pl.comp) MD_TRY(timed("points_components", run_components));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
@@ -1119,6 +1221,16 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
       MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
   }
+  MD_TRY(check_components_part(c.comp));
+  if (components_on(c.comp)) {
+    if (!c.mesh) MD_FAIL(MD_ERR_INVALID_ARG, "components need a mesh request");
+    if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "components need the list's `count`");
+    if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "components together with decimation: the components of the decimated mesh are not built");
+    if (voxel_on(c.vox) || outlier_on(c.outl))
+      MD_FAIL(MD_ERR_INVALID_ARG, "components together with voxel thinning or outlier removal: the rows the faces name no longer exist");
+    if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
+  }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));
   if (outlier_on(c.outl)) {
@@ -1137,6 +1249,8 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (!out->xyz || !out->count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the list outputs `xyz` and `count`");
     if (decimate_on(c.dec)) {
       if (!c.dec->faces || !c.dec->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the decimation outputs `faces` and `face_count`");
+    } else if (components_on(c.comp)) {
+      if (!c.comp->faces || !c.comp->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the component outputs `faces` and `face_count`");
     } else if (!c.mesh || !c.mesh->faces || !c.mesh->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising needs the mesh outputs `faces` and `face_count`");
   }
   if (c.fo) {
@@ -1184,6 +1298,11 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (decimate_on(c.dec)) {  // voxel == 0: the key, and the graph, of the call without decimation
     const md_points_decimate& d = *c.dec;
     key_add(key, 0x44454349u, d.voxel, d.index, d.weight, d.dropped, d.remap, d.faces, d.face_index, d.face_count, d.face_capacity, d.faces_dropped);
+    key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
+  }
+  if (components_on(c.comp)) {  // min_faces == 0: the key, and the graph, of the call without the stage
+    const md_points_components& k = *c.comp;
+    key_add(key, 0x434f4d50u, k.min_faces, k.label, k.component_faces, k.faces, k.face_index, k.face_count, k.face_capacity, k.stats);
     key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
   }
   if (mesh_on(c.mesh))  // every output null: the key, and the graph, of the call without a mesh

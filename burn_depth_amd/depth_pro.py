@@ -118,7 +118,11 @@ class PointCloud:
     unfiltered list and dropped the rows outside the grid. With `ops.decimate_mesh` (`md_op_decimate_mesh`): the list is voxel
     thinning's, remap int32 [input rows] the output row of every input row's voxel (-1 outside the grid), faces / face_count the
     kept faces over the output rows, face_index int32 [face_capacity] their source faces, faces_dropped int32 [3] the invalid,
-    degenerate and duplicate faces. None when not asked for."""
+    degenerate and duplicate faces. With `components=` (`md_op_mesh_components` / `md_infer_points_components`): label int32 [rows
+    of the list] the smallest row of every row's component (-1 behind the list's total), component_faces int32 [rows] its valid
+    faces, faces / face_count the faces of the components that are large enough, face_index their source faces, component_stats
+    int32 [5] the invalid, dropped and clipped faces and the components with a face and kept; with the operator's compact also
+    index and remap. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -140,6 +144,9 @@ class PointCloud:
     remap: Optional[torch.Tensor] = None
     face_index: Optional[torch.Tensor] = None
     faces_dropped: Optional[torch.Tensor] = None
+    label: Optional[torch.Tensor] = None
+    component_faces: Optional[torch.Tensor] = None
+    component_stats: Optional[torch.Tensor] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -272,6 +279,33 @@ def _points_decimate(dev, B: int, H: int, W: int, stride: int, mesh, decimate: d
                                 _ptr(out.faces) or None, _ptr(out.face_index) or None, _ptr(out.face_count), min(frows) if frows else 0,
                                 _ptr(out.faces_dropped))
     return msh, dec
+
+
+def _points_components(dev, B: int, H: int, W: int, stride: int, mesh, components: dict, out: PointCloud, fresh: bool):
+    """(md_points_mesh, md_points_components) for `out` with the island removal on. mesh: True, or a dict with max_rtol /
+    pixel_index; components: dict(min_faces=, face_capacity=). The faces and face_count of `out` are those of the kept components,
+    so the mesh part carries only its edge test and the map. With `fresh` the tensors are created; otherwise the ones `out`
+    carries are written again."""
+    kw = dict(mesh) if isinstance(mesh, dict) else {}
+    unknown = (set(kw) - {"max_rtol", "pixel_index"}) | (set(components) - {"min_faces", "face_capacity"})
+    if unknown:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown mesh / components keywords {sorted(unknown)}")
+    if fresh:
+        stride = max(int(stride), 1)
+        h, w = (H + stride - 1) // stride, (W + stride - 1) // stride
+        fcap = components.get("face_capacity")
+        fcap = max(2 * B * (h - 1) * (w - 1) if fcap is None else int(fcap), 0)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        out.label, out.component_faces, out.component_stats = i32(B * h * w), i32(B * h * w), i32(5)
+        out.faces, out.face_index, out.face_count = i32(fcap, 3), i32(fcap), i32(B + 1)
+        if kw.get("pixel_index", True):
+            out.pixel_index = i32(B, H, W)
+    frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
+    msh = _lib.MdPointsMesh(float(kw.get("max_rtol", 0.0)), None, None, 0, _ptr(out.pixel_index))
+    comp = _lib.MdPointsComponents(int(components["min_faces"]), 0, _ptr(out.label), _ptr(out.component_faces), None, None,
+                                   _ptr(out.faces) or None, _ptr(out.face_index) or None, _ptr(out.face_count), min(frows) if frows else 0,
+                                   _ptr(out.component_stats))
+    return msh, comp
 
 
 def _render_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
@@ -760,13 +794,14 @@ class DepthPro:
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
                      raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
-                     **opts) -> PointCloud:
+                     components: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        Every form runs through the widest entry, `md_infer_points_decimate`, with NULL for the parts not asked for, which is
-        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` / `_raster` / `_outlier` on the same arguments:
+        Every form runs through the widest entry, `md_infer_points_components`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` / `_raster` / `_outlier` / `_decimate` on the
+        same arguments:
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
         conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
         before the unprojection; `depth` is then the filtered depth.
@@ -791,7 +826,12 @@ class DepthPro:
         then voxel thinning's at that side (`index`, `weight`, `dropped`), `faces` / `face_count` are the decimated ones over its
         rows, `face_index` their source faces in the undecimated mesh, `faces_dropped` the invalid, degenerate and duplicate faces,
         and `remap` carries `pixel_index` (rows of the undecimated list) over to the list returned. render= and raster= see the
-        decimated list and faces. voxel 0 or None: the call without it. Not with voxel > 0 or outlier=."""
+        decimated list and faces. voxel 0 or None: the call without it. Not with voxel > 0 or outlier=.
+        components (`md_points_components`): dict(min_faces=, face_capacity=) beside mesh=: island removal behind the mesh. The list
+        is unchanged; `faces` / `face_count` are the faces of the components with at least min_faces faces, `face_index` their
+        source faces in the unfiltered mesh, `label` / `component_faces` the component of every row of the list and
+        `component_stats` the counters. raster= sees the filtered faces. min_faces 0 or None: the call without it. Not with
+        decimate=, voxel > 0 or outlier=."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -801,10 +841,17 @@ class DepthPro:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
         has_conf = bool(getattr(self.config, "dual_head", False))
         deci = bool(decimate) and bool(decimate.get("voxel"))
+        isl = bool(components) and bool(components.get("min_faces"))
         res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, outl, keep = _points_request(
             dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
-            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, None if deci else mesh, raster, outlier)
-        dec = None
+            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, None if deci or isl else mesh, raster, outlier)
+        dec = comp = None
+        if isl:
+            if not mesh:
+                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "components= needs mesh=")
+            msh, comp = _points_components(dev, B, H, W, o.stride, mesh, components, res, out is None)
+        elif components is not None:
+            comp = _lib.MdPointsComponents(0, 0, None, None, None, None, None, None, None, 0, None)
         if deci:
             if not mesh:
                 raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "decimate= needs mesh=")
@@ -814,10 +861,11 @@ class DepthPro:
         elif decimate is not None:
             dec = _lib.MdPointsDecimate(0.0, None, None, None, None, None, None, None, 0, None)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        _lib.check(self._lib.md_infer_points_decimate(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                      C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                      C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
-                                                      ref(outl), ref(dec), _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        _lib.check(self._lib.md_infer_points_components(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                        C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                        C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
+                                                        ref(outl), ref(dec), ref(comp), _lib.MD_MEM_DEVICE,
+                                                        _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

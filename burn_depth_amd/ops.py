@@ -575,6 +575,55 @@ def decimate_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, voxel: fl
     return out
 
 
+def mesh_components(dev: Device, faces: torch.Tensor, n_rows: int, min_faces: int, xyz: Optional[torch.Tensor] = None,
+                    conf: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                    compact: bool = False, capacity: Optional[int] = None, face_capacity: Optional[int] = None,
+                    out: Optional[PointCloud] = None) -> PointCloud:
+    """md_op_mesh_components: faces int32 [F,3] over n_rows vertex rows -> `PointCloud` with label int32 [N] (the smallest row of
+    every row's component), component_faces int32 [N], the faces of the components with at least min_faces faces, int32
+    [face_capacity,3], with face_index int32 [face_capacity], face_count int32 [2] and component_stats int32 [5] (invalid, dropped,
+    clipped faces, components with a face, components kept). compact: the rows those faces name are compacted too, in ascending
+    order: xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) -> the rows of the survivors, index int32 [capacity], count int32 [2],
+    remap int32 [N], and the faces are written through remap. capacity defaults to N, face_capacity to F. `out`: a PointCloud of an
+    earlier call to write into again. Bit-identical to `pipeline.mesh_components`."""
+    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
+    faces = faces.contiguous()
+    N, F = int(n_rows), int(faces.shape[0])
+    if not compact:
+        assert xyz is None and conf is None and rgb is None and normals is None and capacity is None, "vertex rows are carried only with compact"
+    else:
+        assert xyz is not None and xyz.is_cuda and tuple(xyz.shape) == (N, 3), "compact needs xyz, a device tensor [n_rows,3]"
+        xyz = _f32c(xyz)
+    conf = _f32c(conf).reshape(N) if conf is not None else None
+    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if out is None:
+        cap = N if capacity is None else int(capacity)
+        fcap = F if face_capacity is None else int(face_capacity)
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=faces.device)  # noqa: E731
+        i32 = torch.int32
+        out = PointCloud(label=f(N, dt=i32), component_faces=f(N, dt=i32), faces=f(fcap, 3, dt=i32), face_index=f(fcap, dt=i32),
+                         face_count=f(2, dt=i32), component_stats=f(5, dt=i32))
+        if compact:
+            out.xyz, out.count, out.index, out.remap = f(cap, 3), f(2, dt=i32), f(cap, dt=i32), f(N, dt=i32)
+            out.conf = f(cap) if conf is not None else None
+            out.rgb = f(cap, 3, dt=torch.uint8) if rgb is not None else None
+            out.normals = f(cap, 3) if normals is not None else None
+    for t in (out.label, out.component_faces, out.remap):
+        assert t is None or int(t.shape[0]) >= N, "label / component_faces / remap cover the input rows"
+    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index) if t is not None]
+    frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
+    comp = _lib.MdPointsComponents(int(min_faces), 1 if compact else 0, ptr(out.label), ptr(out.component_faces), ptr(out.index), ptr(out.remap),
+                                   ptr(out.faces), ptr(out.face_index), ptr(out.face_count), min(frows) if frows else 0,
+                                   ptr(out.component_stats))
+    _lib.check(_lib.load().md_op_mesh_components(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, _p(faces), F, C.byref(comp),
+                                                 C.byref(outs), _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
 def render_points(dev: Device, xyz: torch.Tensor, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None,
                   rgb: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, *, pixel_offset: float = 0.0, z_near: float = 0.0,
                   z_far: float = 0.0, radius: int = 0, out: Optional[RenderedPoints] = None) -> RenderedPoints:

@@ -22,6 +22,8 @@
   mesh rasterised into target cameras, integer coverage at 1/256 pixel and 64-bit keys
 * `decimate_mesh`                             -- the host reference of `md_op_decimate_mesh`: voxel thinning's vertices, the faces
   re-indexed to them, collapsed faces and later copies of an oriented triangle dropped
+* `mesh_components`                           -- the host reference of `md_op_mesh_components` / `md_infer_points_components`: the
+  connected components of the faces (the smallest row of each as its label) and the faces of those with enough faces
 * `radius_outliers`                           -- the host reference of `md_op_radius_outliers` / `md_infer_points_outlier`: the rows
   with enough neighbours in the 27 cells around their own, bit-identical to the device's
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
@@ -621,6 +623,103 @@ def decimate_mesh(xyz, faces, voxel, conf=None, rgb=None, normals=None, counts=N
 
 
 @dataclass
+class HostComponents:
+    label: np.ndarray                # int32 [N]: the smallest row of every row's component
+    component_faces: np.ndarray      # int32 [N]: the valid faces of every row's component, 0 for a row no valid face names
+    faces: np.ndarray                # int32 [K,3]: the kept faces in ascending source face, winding unchanged (through remap with compact)
+    face_index: np.ndarray           # int32 [K]: the source face
+    face_count: np.ndarray           # int32 [B+1]: kept faces per view of their source face, then their total
+    stats: np.ndarray                # int32 [5]: invalid, dropped, clipped faces, components with a face, components kept
+    index: Optional[np.ndarray] = None   # compact: int32 [M] the surviving rows in ascending order
+    remap: Optional[np.ndarray] = None   # compact: int32 [N] the output row of a surviving row, -1 otherwise
+    xyz: Optional[np.ndarray] = None     # compact: the carried rows of the survivors
+    conf: Optional[np.ndarray] = None
+    rgb: Optional[np.ndarray] = None
+    normals: Optional[np.ndarray] = None
+
+
+def mesh_components(faces, n_rows, min_faces=1, face_counts=None, compact=False, capacity=None, xyz=None, conf=None, rgb=None,
+                    normals=None, face_capacity=None) -> HostComponents:
+    """The host reference of md_op_mesh_components (include/mi_depth.h states the contract): connected components of the faces
+    int32 [F,3] over `n_rows` rows and island removal. A face is invalid when a corner is < 0 or >= n_rows: it joins nothing and
+    is never kept. Two rows are connected when a valid face names both (sharing one vertex joins; a degenerate face joins what
+    it names); label[i] = the smallest row of row i's component; component_faces[i] = its valid faces. A valid face is kept iff
+    its component has at least min_faces >= 1 faces; the kept faces come in ascending f. face_counts: the faces of every view of
+    the input, [B] (default: one view). compact: the rows that a face of a kept component names survive in ascending order
+    (index, remap, the carried rows), the faces are written through remap, and a face of a kept component with a mapped corner
+    >= capacity (default n_rows) is clipped: dropped and counted. face_capacity: the rows faces / face_index hold (default: all);
+    face_count stays the true total. The vertex lists are not cut to `capacity`. Integers only:
+    the device kernels (kernels/components.hip) give the same bits."""
+    N, min_faces = int(n_rows), int(min_faces)
+    fc = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    F = len(fc)
+    if N < 0 or N >= 1 << 30 or F >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows and faces")
+    if min_faces < 1:
+        raise ValueError("min_faces >= 1")
+    valid = ((fc >= 0) & (fc < N)).all(1)
+    vf = fc[valid].astype(np.int64)
+    # label propagation that keeps lab[i] <= i and lab[i] inside i's component: hook the corners and their labels under the
+    # face's smallest label, jump until lab[lab] == lab; at the fixed point a label is constant on a component, a member of it
+    # and <= every member
+    lab = np.arange(N, dtype=np.int64)
+    while len(vf):
+        la = lab[vf]
+        m = np.repeat(la.min(1), 3)
+        new = lab.copy()
+        np.minimum.at(new, la.ravel(), m)
+        np.minimum.at(new, vf.ravel(), m)
+        while True:
+            jump = new[new]
+            if np.array_equal(jump, new):
+                break
+            new = jump
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    size = np.bincount(lab[vf[:, 0]], minlength=N) if len(vf) else np.zeros(N, np.int64)
+    component_faces = size[lab] if N else np.zeros(0, np.int64)
+    roots = (lab == np.arange(N)) & (size > 0)
+    big = np.zeros(F, bool)
+    big[valid] = size[lab[vf[:, 0]]] >= min_faces
+    stats = np.zeros(5, np.int32)
+    stats[0], stats[1] = F - valid.sum(), (valid & ~big).sum()
+    stats[3], stats[4] = roots.sum(), (roots & (size >= min_faces)).sum()
+    res = HostComponents(lab.astype(np.int32), component_faces.astype(np.int32), None, None, None, stats)
+    keep = big
+    if compact:
+        cap = N if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError("capacity is negative")
+        survive = component_faces >= min_faces
+        res.index = np.nonzero(survive)[0].astype(np.int32)
+        res.remap = np.full(N, -1, np.int32)
+        res.remap[res.index] = np.arange(len(res.index), dtype=np.int32)
+        mapped = res.remap[np.where(big[:, None], fc, 0)] if N else np.zeros((F, 3), np.int32)
+        clipped = big & (mapped >= cap).any(1)
+        stats[2] = clipped.sum()
+        keep = big & ~clipped
+        res.faces = np.ascontiguousarray(mapped[keep], dtype=np.int32)
+        carry = lambda a, dt, w: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape((N, w) if w else (N,))[res.index]  # noqa: E731
+        res.xyz, res.conf, res.rgb, res.normals = carry(xyz, np.float32, 3), carry(conf, np.float32, 0), carry(rgb, np.uint8, 3), carry(normals, np.float32, 3)
+    else:
+        res.faces = fc[keep]
+    kept = np.nonzero(keep)[0]
+    if face_counts is None:
+        bounds = np.array([0, F], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(face_counts, np.int64).reshape(-1))]), F)
+    per_view = np.diff(np.searchsorted(kept, bounds, side="left"))
+    res.face_index = kept.astype(np.int32)
+    res.face_count = np.concatenate([per_view, [len(kept)]]).astype(np.int32)
+    if face_capacity is not None:
+        if int(face_capacity) < 0:
+            raise ValueError("face_capacity is negative")
+        res.faces, res.face_index = res.faces[:int(face_capacity)], res.face_index[:int(face_capacity)]
+    return res
+
+
+@dataclass
 class HostOutliers:
     xyz: np.ndarray                  # f32 [M,3]: the surviving input rows, in ascending input index
     conf: Optional[np.ndarray]       # f32 [M]
@@ -1093,7 +1192,8 @@ class AnyDepthModel:
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
         render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`), outlier=
-        (`md_infer_points_outlier`) and decimate= (`md_infer_points_decimate`) included."""
+        (`md_infer_points_outlier`), decimate= (`md_infer_points_decimate`) and components= (`md_infer_points_components`)
+        included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

@@ -819,6 +819,78 @@ int md_infer_points_decimate(md_model_t m, const float* nchw, int B, int H, int 
                              const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
                              const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec, int out_kind,
                              void* stream);
+
+/* ---- point path: connected components of a mesh, island removal ------------------------------------------------------------
+ * N vertex rows and faces int32 [F,3] over them -> the component of every row and the faces of the components that are large
+ * enough. Integers only: nothing here computes a float, nothing is averaged and nothing depends on the order in which threads
+ * arrive (pipeline.mesh_components restates it in numpy bit for bit).
+ *   validity: a face is INVALID when a corner is < 0 or >= N. Invalid faces join nothing, are never kept, and are counted. A
+ *     degenerate face (two corners equal) is valid: it joins what it names.
+ *   components: two rows are connected when a valid face names both (vertex connectivity: sharing one vertex joins, a shared
+ *     edge is not required). label int32 [N]: label[i] = the smallest row index of row i's component; a row that no valid face
+ *     names is a component of its own, label[i] = i. component_faces int32 [N]: the number of valid faces in row i's component,
+ *     0 for a row that no valid face names.
+ *   selection: a valid face is kept iff its component has at least min_faces >= 1 faces. The kept faces come in ascending f
+ *     with unchanged corners and unchanged winding; face_index = the source face. face_count[b] = the kept faces whose source
+ *     face belongs to view b (the views of the faces are the prefix of the INPUT face counts; the stand-alone operator has one
+ *     view), face_count[B] = their true total, also beyond face_capacity: then only the first face_capacity rows are written
+ *     and the memory behind them stays untouched.
+ *   stats int32 [5]: invalid faces; faces of dropped components; clipped faces (compact, below; 0 without it); components that
+ *     have at least one face; components kept.
+ *   compact != 0 (stand-alone operator only): the vertex list is compacted too. A row survives iff a face of a KEPT COMPONENT
+ *     names it; the survivors come in ascending input index into out->xyz / rgb / conf, normals_out, index (the source row) and
+ *     out->count (int32 [2]: M twice); capacity and the memory behind the rows behave as in md_op_voxel_thin. remap int32 [N] =
+ *     the true output rank of a surviving row, also when it is >= capacity, and -1 otherwise. The faces are written through
+ *     remap, and a face of a kept component with a mapped corner >= capacity is CLIPPED: dropped and counted, so no written face
+ *     names an unwritten row. Vertex survival does not depend on clipping. With compact == 0 the vertex outputs, index and remap
+ *     must be NULL, and the faces keep the input's indices.
+ *   limits: N < 2^30 and F < 2^30.
+ * The labelling is a lock-free union-find in device memory (kernels/components_math.h): parent[v] <= v at all times, a root is
+ * only ever hooked under a smaller row by compare-and-swap, so the root of a finished component is its smallest row whatever
+ * the order of arrival. The forest and the counters are set on the stream inside every call. */
+typedef struct md_points_components {
+  int32_t min_faces;        /* faces a component needs to be kept, >= 1; 0 = the stage is off (md_infer_points_components) */
+  int32_t compact;          /* != 0: compact the vertex list too (md_op_mesh_components only) */
+  int32_t* label;           /* int32 [N]: the smallest row of every row's component. NULL = skip */
+  int32_t* component_faces; /* int32 [N]: the valid faces of every row's component. NULL = skip */
+  int32_t* index;           /* int32 [capacity]: the source row of every surviving row (compact); needs count. NULL = skip */
+  int32_t* remap;           /* int32 [N]: the output row of every surviving row, -1 otherwise (compact). NULL = skip */
+  int32_t* faces;           /* int32 [face_capacity,3]: the kept faces; needs face_count. NULL = skip */
+  int32_t* face_index;      /* int32 [face_capacity]: the source face of every kept face; needs face_count. NULL = skip */
+  int32_t* face_count;      /* int32 [B+1]: kept faces per view, then their total. NULL = skip */
+  int64_t face_capacity;    /* rows of faces / face_index, >= 0 */
+  int32_t* stats;           /* int32 [5]: invalid, dropped, clipped faces, components with a face, components kept. NULL = skip */
+} md_points_components;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_decimate_mesh: the N rows and the F faces are one view.
+ * The vertex rows are optional: xyz_dev may be NULL with compact == 0 (N still bounds the corners). Of `out` the fields xyz,
+ * rgb, conf, count (int32 [2]) and capacity are used, and only with compact; the others must be NULL; out itself may be NULL
+ * with compact == 0. comp->face_count is int32 [2]. Everything is enqueued on `stream`; the call returns after the stream has
+ * drained, because its scratch is freed on return. Errors, before any launch: dev / comp NULL, min_faces < 1, N < 0, F < 0,
+ * faces_dev NULL with F > 0, face_capacity < 0, faces / face_index without face_count; with compact == 0: a vertex output,
+ * index, remap or count set; with compact != 0: out NULL, capacity < 0, a compacted output (xyz, rgb, conf, normals_out, index)
+ * without count, an xyz / rgb / conf / normals output without that input row; a dense output or out->depth set
+ * -> MD_ERR_INVALID_ARG; N >= 2^30 or F >= 2^30 -> MD_ERR_SHAPE. */
+int md_op_mesh_components(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                          int64_t N, const int32_t* faces_dev, int64_t F, const md_points_components* comp, const md_points_outputs* out,
+                          float* normals_out, void* stream);
+/* md_infer_points_decimate with the island removal behind the mesh stage and in front of the point render and the rasteriser
+ * (launch-order name "points_components"). With it on, the mesh stage writes all faces of the call's list with their true
+ * per-view counts to a grow-only home of the model; mesh->faces and mesh->face_count, if taken, still receive the unfiltered
+ * mesh; the stage writes comp's outputs, and the rasteriser reads those: rasterising then needs comp->faces and
+ * comp->face_count. label and component_faces are int32 [R] over the call's list, R = B ceil(H/stride) ceil(W/stride); rows
+ * behind its total hold -1 and 0. The in-call stage is face-only: the list and the point render are unchanged. comp's pointers
+ * are of out_kind. comp NULL or min_faces == 0 (its pointers then NULL): md_infer_points_decimate on the same arguments, the
+ * same launches, bits and launch-order names. The graph key contains comp's fields. Errors as md_infer_points_decimate's, plus,
+ * before any launch: min_faces < 0, compact != 0, face_capacity < 0, faces / face_index without face_count, any of comp's
+ * pointers with min_faces == 0, the stage without a mesh request or without the list's count, or together with dec on, voxel thinning or
+ * outlier removal (the rows the faces name no longer exist) -> MD_ERR_INVALID_ARG; 2 R >= 2^30 -> MD_ERR_SHAPE. After the first call of a shape nothing is allocated. */
+int md_infer_points_components(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                               const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                               const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                               const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                               const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                               const md_points_components* comp, int out_kind, void* stream);
 /* PROCESS-WIDE (returns the previous setting): the capacity of the (face, target) queue of later md_op_render_mesh /
  * md_infer_points_raster calls, 0 = the default (2^20 pairs). A push that finds the queue full draws the face in place: same
  * bits at every capacity; for the test of that branch. MD_ERR_INVALID_ARG (< 0) for a negative capacity. */

@@ -44,6 +44,12 @@ occupied voxel (the most confident one), the faces re-indexed, collapsed faces a
 holds the decimated list and faces (`md_infer_points_decimate`; with `--views`, `ops.decimate_mesh` behind the per-view meshes, which
 welds the sheets of overlapping views). Not together with `--voxel` or `--outlier-radius`.
 
+`--min-component-faces K` (with `--ply --mesh`): the islands of the mesh leave on the device: the faces of the connected components
+with fewer than K faces are dropped (`md_infer_points_components`, so `--raster-pose` sees the filtered faces), and before the file
+is written `ops.mesh_components(compact=True)` drops the vertices that only they named, so the file holds no floater; the images of
+`--raster-pose` / `--render-pose` stay those of the model call, over its uncompacted list. With `--views`
+the operator runs behind the per-view meshes, and behind `ops.decimate_mesh` when `--decimate` is given.
+
 `--raster-pose E.npy --raster-out view.png` (with `--ply --mesh`): the mesh is also rasterised on the device into a virtual camera with
 the world-to-camera pose E ([3,4], or [T,3,4] of which every pose is drawn and the first written), a render without holes, and its
 depth image written as a normalised PNG (`md_infer_points_raster`; with `--views`, `ops.render_mesh` on the meshes of all views).
@@ -163,6 +169,16 @@ def run_views(a) -> int:
             faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy()
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.min_component_faces > 0:  # the islands of the (decimated) mesh leave, and the vertices only they named with them
+            try:
+                pc = ops.mesh_components(dev, pc.faces[:len(faces)], int(xyz.shape[0]), a.min_component_faces, xyz=xyz, rgb=col, normals=nrm,
+                                         compact=True)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy()
+            xyz, col, _ = pc.points()
+            nrm = pc.normals[:xyz.shape[0]] if a.normals else None
         if a.voxel > 0:  # one point per occupied voxel over all views: the most confident one
             try:
                 pc = ops.voxel_thin(dev, xyz, a.voxel, conf=conf, rgb=col, normals=nrm)
@@ -236,6 +252,9 @@ def main(argv=None) -> int:
     ap.add_argument("--decimate", type=float, default=0.0,
                     help="--ply --mesh: vertex-clustering decimation at this voxel side: one vertex per voxel, collapsed and doubled faces dropped "
                          "(md_infer_points_decimate; 0 = off)")
+    ap.add_argument("--min-component-faces", type=int, default=0,
+                    help="--ply --mesh: drop the connected components of the mesh with fewer faces than this, and the vertices only they "
+                         "named (md_infer_points_components, ops.mesh_components; 0 = off)")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
     ap.add_argument("--raster-out", default="", help="--raster-pose: the rasterised depth of the first pose as a normalised PNG")
     a = ap.parse_args(argv)
@@ -247,6 +266,9 @@ def main(argv=None) -> int:
         return 2
     if a.decimate != 0 and (not (a.ply and a.mesh) or a.voxel > 0 or a.outlier_radius != 0):
         print("--decimate goes with --ply --mesh, and not with --voxel or --outlier-radius (the decimation is the thinning)", file=sys.stderr)
+        return 2
+    if a.min_component_faces != 0 and (a.min_component_faces < 0 or not (a.ply and a.mesh)):
+        print("--min-component-faces is a positive face count and goes with --ply --mesh", file=sys.stderr)
         return 2
     if a.outlier_radius != 0 and (not a.ply or a.mesh):
         print("--outlier-radius goes with --ply, and not with --mesh (the faces name rows of the unfiltered list)", file=sys.stderr)
@@ -286,7 +308,7 @@ def main(argv=None) -> int:
         return 2
     if a.ply:
         import torch
-        from burn_depth_amd import _lib
+        from burn_depth_amd import _lib, ops
         from burn_depth_amd.inference import rgb_to_input_tensor
         prep = model.prepare_input_image(rgb)
         x = rgb_to_input_tensor(prep.rgb.tobytes(), prep.width, prep.height, model.model.device)
@@ -309,13 +331,21 @@ def main(argv=None) -> int:
                                     normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render,
                                     mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None, raster=raster,
                                     outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None,
-                                    decimate=dict(voxel=a.decimate) if a.decimate else None)
+                                    decimate=dict(voxel=a.decimate) if a.decimate else None,
+                                    components=dict(min_faces=a.min_component_faces) if a.min_component_faces and not a.decimate else None)
+            xyz, col, _ = pc.points()
+            nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+            flt = pc  # what the file holds; `pc` stays the model call's result, whose images are written below
+            if a.min_component_faces:  # the file holds no floater vertex: the list is compacted to the rows the kept faces name
+                flt = ops.mesh_components(Device(0), pc.faces[:int(pc.face_count[-1])], int(xyz.shape[0]), a.min_component_faces, xyz=xyz,
+                                          rgb=col, normals=nrm, compact=True)
+                xyz, col, _ = flt.points()
+                nrm = flt.normals[:xyz.shape[0]] if a.normals else None
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
-        xyz, col, _ = pc.points()
-        faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy() if a.mesh else None
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), pc.normals[:xyz.shape[0]].cpu().numpy() if a.normals else None, faces=faces)
+        faces = flt.faces[:int(flt.face_count[-1])].cpu().numpy() if a.mesh else None
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces)
         print(f"Model `{kind.value}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} to {a.ply}")
         if render is not None:
             write_render(a, P, pc.render)
