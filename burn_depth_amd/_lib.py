@@ -18,6 +18,7 @@ MD_MEM_HOST, MD_MEM_DEVICE = 0, 1
 MD_COMM_ID_BYTES = 128
 MD_FRAME_U8_GRAY, MD_FRAME_RGBA_F32 = 0, 1
 VIT_GEMM_RESID, VIT_GEMM_QKV, VIT_GEMM_FC1, VIT_GEMM_PATCH_EMBED = 0, 1, 2, 3
+DECODER_GEMM_CONV3, DECODER_GEMM_CONV3_S2, DECODER_GEMM_PIXSHUF, DECODER_GEMM_HEAD, DECODER_GEMM_HEAD_UP2 = 0, 1, 2, 3, 4
 TILE_256x256, TILE_128x128, TILE_256x32, TILE_128x64, TILE_64x64, TILE_AUTO = 0, 1, 2, 3, 4, 99
 
 
@@ -158,6 +159,21 @@ class MdVitGemm(C.Structure):
                 ("x_out", C.c_void_p), ("ln_out", C.c_void_p), ("ln_stats_out", C.c_void_p), ("ln_stats", C.c_void_p), ("ln_raw", C.c_int),
                 ("ln_eps", C.c_float), ("ln_inv_n", C.c_float), ("S", C.c_int), ("D", C.c_int), ("P", C.c_int), ("qk", C.c_void_p),
                 ("vT", C.c_void_p), ("out", C.c_void_p)]
+
+
+class MdDecoderGemmHeadCh(C.Structure):
+    """md_decoder_gemm_head_ch (include/mi_depth.h)."""
+    _fields_ = [("w", C.c_void_p), ("b", C.c_float), ("act", C.c_int), ("out", C.c_void_p), ("bstride", C.c_int64)]
+
+
+class MdDecoderGemm(C.Structure):
+    """md_decoder_gemm (include/mi_depth.h)."""
+    _fields_ = [("kind", C.c_int), ("precision", C.c_int), ("tile", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int),
+                ("Cin_p", C.c_int), ("Cout", C.c_int), ("ngroups", C.c_int), ("in_shared", C.c_int), ("res1_shared", C.c_int),
+                ("w", C.c_void_p * 2), ("bias", C.c_void_p * 2), ("in_", C.c_void_p), ("act", C.c_int), ("res1", C.c_void_p), ("res2", C.c_void_p),
+                ("res_mod", C.c_int), ("out", C.c_void_p), ("out2", C.c_void_p), ("ldo", C.c_int), ("out_f32", C.c_int), ("ps_f", C.c_int),
+                ("ps_coff", C.c_int), ("head_nch", C.c_int), ("ch", MdDecoderGemmHeadCh * 8), ("head_w", C.c_void_p), ("head_b", C.c_float),
+                ("head_act", C.c_int), ("Cmid", C.c_int), ("w2", C.c_void_p), ("bias2", C.c_void_p)]
 
 
 class MdNchwView(C.Structure):
@@ -333,6 +349,8 @@ SYMBOLS = {
     "md_op_ln_finish": (_I, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
     "md_op_vit_gemm": (_I, [_P, C.POINTER(MdVitGemm), _P]),
     "md_debug_gemm_last_form": (_I, [C.POINTER(_I * 8)]),
+    "md_debug_gemm_last_launch": (_I, [C.POINTER(_I * 4)]),
+    "md_op_decoder_gemm": (_I, [_P, C.POINTER(MdDecoderGemm), _P]),
     "md_op_conv2d_direct_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_fov_to_focal": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_op_focal_to_fov": (_I, [C.c_float, _I, _I, _F, _F]),

@@ -239,6 +239,12 @@ Form256 gemm256_form(const GemmParams& p, int amode, int prec, int cus, std::str
 void gemm_record_form(const Form256& f);
 void gemm_forget_form();
 Form256 gemm_last_form();
+// What launch_gemm resolved for the calling host thread's last launch, whichever kernel of the family took it: the tile (TILE_AUTO's choice, the
+// tiles the head epilogues force) and the launcher-set GemmParams::ps_fast. tile = -1: no launch since gemm_forget_form() (md_debug_gemm_last_launch).
+struct LaunchNote {
+  int tile = -1, ps_fast = 0;
+};
+LaunchNote gemm_last_launch();
 
 enum GemmTile : int { TILE_256x256 = 0, TILE_128x128 = 1, TILE_256x32 = 2, TILE_128x64 = 3, TILE_64x64 = 4, TILE_AUTO = 99 };
 

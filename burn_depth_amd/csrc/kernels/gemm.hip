@@ -218,8 +218,10 @@ static constexpr Form256 no_form() {
 }
 static thread_local Form256 g_last_form = no_form();  // constant-initialised: recording a launch is one plain thread-local store
 void gemm_record_form(const Form256& f) { g_last_form = f; }
-void gemm_forget_form() { g_last_form = no_form(); }
+static thread_local LaunchNote g_last_launch;
+void gemm_forget_form() { g_last_form = no_form(); g_last_launch = LaunchNote(); }
 Form256 gemm_last_form() { return g_last_form; }
+LaunchNote gemm_last_launch() { return g_last_launch; }
 
 int launch_gemm(GemmParams p, int amode, int prec, int tile, hipStream_t stream) {
   const int ke = prec == MD_PREC_F32 ? 32 : (prec == MD_PREC_FP8 ? 128 : 64);
@@ -312,6 +314,7 @@ int launch_gemm(GemmParams p, int amode, int prec, int tile, hipStream_t stream)
 #endif
   }
   if (p.epi == EPI_HEAD) tile = TILE_256x32;
+  g_last_launch.tile = tile; g_last_launch.ps_fast = p.ps_fast;
   if (prec == MD_PREC_F32) return launch_gemm_f32(p, amode, tile, stream);
   if (prec == MD_PREC_FP8) {
     if (p.out_fp8 && !(p.epi == EPI_STORE && p.act == ACT_GELU)) MD_FAIL(MD_ERR_UNSUPPORTED, "fp8 output is built for the GELU store only");

@@ -1404,6 +1404,138 @@ int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* d, void* stream) {
   return MD_OK;
 }
 
+// ---- the GEMM forms of the convolutional decoders and heads alone ----
+int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* d, void* stream) {
+  if (!dev || !d || !d->in || !d->out || !d->w[0]) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  const int prec = d->precision, kind = d->kind;
+  if (!token_op_prec(prec)) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: the decoders run in bf16, f16, f16x2 and f32, not in precision %d", prec);
+  if (kind < MD_DECODER_GEMM_CONV3 || kind > MD_DECODER_GEMM_HEAD_UP2) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: kind %d", kind);
+  const bool conv = kind == MD_DECODER_GEMM_CONV3, s2 = kind == MD_DECODER_GEMM_CONV3_S2, ps = kind == MD_DECODER_GEMM_PIXSHUF;
+  const bool head = kind == MD_DECODER_GEMM_HEAD, up2 = kind == MD_DECODER_GEMM_HEAD_UP2;
+  const int B = d->B, H = d->H, W = d->W, Cin = d->Cin, Cin_p = d->Cin_p, Cout = d->Cout, G = conv ? d->ngroups : 1;
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) MD_FAIL(MD_ERR_SHAPE, "decoder_gemm: [%d,%d,%d] %d -> %d channels", B, H, W, Cin, Cout);
+  if (Cin_p < Cin || Cin_p % ke_of(prec) != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "decoder_gemm: Cin_p=%d must hold Cin=%d in whole k-tiles of %d", Cin_p, Cin, ke_of(prec));
+  if (Cout % 4 != 0 || ((head || up2) && Cout != 32)) MD_FAIL(MD_ERR_UNSUPPORTED, "decoder_gemm: Cout=%d (x4; the head tails: 32)", Cout);
+  if (G < 1 || G > 2 || (G == 2 && !d->w[1])) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: %d weight groups (1 or 2, each with a weight)", G);
+  if (!conv && (d->res1 || d->res2 || d->res_mod)) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: residual inputs belong to CONV3");
+  if (!conv && !ps && d->out2) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: a second output belongs to CONV3 and PIXSHUF");
+  if (conv && d->res_mod && (G != 1 || !d->res1 || d->res_mod < 0)) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: res_mod wraps res1 of a one-group launch");
+  if (conv && d->act != ACT_NONE && d->act != ACT_RELU) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: act %d", d->act);
+  if ((conv || s2 || ps) && !(s2 && d->out_f32) && d->ldo < (ps ? d->ps_coff : 0) + Cout) MD_FAIL(MD_ERR_SHAPE, "decoder_gemm: %d channels at %d do not fit a pixel of %d", Cout, ps ? d->ps_coff : 0, d->ldo);
+  if (d->out_f32 && !s2) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: the fp32 store is CONV3_S2's");
+  if (ps && ((d->ps_f != 2 && d->ps_f != 4) || d->ps_coff < 0 || !d->bias[0])) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: pixel shuffle f=%d coff=%d (+ bias)", d->ps_f, d->ps_coff);
+  if ((head || up2 || s2) && !d->bias[0]) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: bias missing");
+  if (head && (d->head_nch < 0 || d->head_nch > 8)) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: %d head channels (0 .. 8)", d->head_nch);
+  if (up2 && (d->Cmid <= 0 || !d->w2 || !d->bias2 || !d->head_w)) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: HEAD_UP2 needs Cmid, w2, bias2, head_w");
+  if ((long)G * B * H * W * (ps ? d->ps_f * d->ps_f : 1) >= (1L << 31)) MD_FAIL(MD_ERR_UNSUPPORTED, "decoder_gemm: tensors of this size are not a test");
+  const KsplitScope ksplit(1);  // (the Depth-Anything-v3 engine, whose head these forms are, runs with the k-split form allowed)
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  const bool split = prec == MD_PREC_F16X2;
+
+  // the operand geometry the launch helpers of md_engine_util.h read (OperandGeom: all they read of a model): the precision's k-tile and
+  // planes, the split-half term count of plain weights as model_commit decides it (two when every weight of the launch is an exact
+  // half) and the zero page
+  DevBuf zp, wa[2], composed, bias9;
+  MD_TRY(zp.alloc(4096));
+  OperandGeom geom{ke_of(prec), split ? 2 : 1, 1, zp.p};
+  const int taps = ps ? d->ps_f * d->ps_f : 9;
+  if (split) {
+    geom.wterms = 2;
+    for (int g = 0; g < G && !up2; ++g) {
+      int t = 2;
+      MD_TRY(split_terms_of(d->w[g], (long)Cout * Cin * taps, st, &t));
+      geom.wterms = std::max(geom.wterms, t);
+    }
+  }
+  const int terms = up2 ? 3 : 0;  // (the composed head weight is a sum of products, never f16-exact: model_commit packs it in three terms)
+  const int wt = split_terms(geom, terms);
+  ConvW cw[2];
+  for (int g = 0; g < G; ++g) {
+    PackEntry e;
+    e.kp = Cin_p; e.terms = wt;
+    if (ps) { e.kind = PACK_DECONV; e.d0 = Cin; e.d1 = Cout; e.k = d->ps_f; }
+    else { e.kind = PACK_CONV3; e.d0 = up2 ? 4 * Cout : Cout; e.d1 = Cin; e.k = 3; }
+    MD_TRY(wa[g].alloc(pack_elems(e, wt) * esz_of(prec)));
+    e.dst = wa[g].p;
+    const float* src = d->w[g];
+    if (up2) {  // add_pack_fused(PACK_HEAD_W) as model_commit runs it: the product in fp32, then packed as a 3x3 convolution of 4 x 32 columns; PACK_HEAD_B: nine bias classes
+      MD_TRY(composed.alloc((size_t)4 * Cout * Cin * 9 * 4));
+      MD_TRY(bias9.alloc((size_t)9 * Cout * 4));
+      MD_TRY(compose_head(d->w[0], d->w2, Cin, d->Cmid, Cout, (float*)composed.p, st));
+      MD_TRY(compose_head_bias(d->w2, d->bias[0], d->bias2, d->Cmid, Cout, (float*)bias9.p, st));
+      src = (const float*)composed.p;
+    }
+    MD_TRY(pack_weight(src, e, prec, st));
+    cw[g] = ConvW{wa[g].p, up2 ? (const float*)bias9.p : d->bias[g]};
+  }
+
+  GemmParams p;
+  int amode = A_CONV3;
+  if (conv) {
+    // md_engine_util.h conv3(): residual_unit's second convolution (res1 = x, res2 = the skip, out2 = the relu'd copy, two groups with
+    // the shared input / residual), its first (ACT_RELU), the layerN_rn maps (md_da3.hip da3_prepare_stages: out2 only)
+    p = conv3_params(geom, B, d->in, H, W, Cin_p, cw, Cout, d->out, d->ldo, d->act, d->res1, d->res2, d->out2, terms, G, d->in_shared != 0,
+                     d->res1_shared != 0);
+    if (d->res_mod) p.res_mod = d->res_mod;  // md_da3.hip da3_prepare_stages, the stage projection: `p.res_mod = P`, a table per image
+  } else if (s2) {
+    const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
+    p.N = Cout; p.ngroups = 1; p.g_rows[0] = B * OH * OW;
+    p.W[0] = cw[0].w; p.bias[0] = cw[0].b;
+    p.A = d->in; p.cH = H; p.cW = W; p.cOH = OH; p.cOW = OW; p.cstride = 2; p.zero_page = geom.zero_page;
+    split_conv_a(geom, p, Cin_p, 0);
+    if (d->out_f32) {  // md_engine.hip run_fov, the downsampling convolution of the FOV head: ReLU, fp32 rows of Cout
+      p.epi = EPI_STORE; p.act = ACT_RELU; p.out_f32 = 1; p.out = d->out; p.ldo = Cout;
+    } else {           // md_da3.hip da3_prepare_stages, stage 3's resize
+      p.epi = EPI_STORE; p.out = d->out;
+      split_out(geom, p, d->ldo, true);
+    }
+  } else if (ps) {
+    // md_engine_util.h deconv2(): the decoder's upsampling (f = 2, into a channel slice, with the relu'd copy) and the stage resizes of
+    // md_da3.hip da3_prepare_stages (f = 4 | 2)
+    p = deconv2_params(geom, B, d->in, Cin_p, nullptr, H, W, cw[0].w, Cin_p, Cout, cw[0].b, d->out, d->ldo, d->ps_coff, d->out2, d->ps_f, terms);
+    amode = A_DENSE;
+  } else if (head) {
+    // md_da3.hip tail(): `nch` channels in one launch; head_nch == 0: the one-channel form of the same epilogue (GemmParams::head_w)
+    p.N = 32; p.ngroups = 1; p.g_rows[0] = B * H * W; p.W[0] = cw[0].w;
+    p.A = d->in; p.cH = H; p.cW = W; p.zero_page = geom.zero_page;
+    split_conv_a(geom, p, Cin_p, 0);
+    p.epi = EPI_HEAD; p.bias[0] = cw[0].b; p.head_nch = d->head_nch; p.head_plane = H * W;
+    for (int i = 0; i < d->head_nch; ++i) {
+      const md_decoder_gemm_head_ch& c = d->ch[i];
+      if (!c.w || !c.out || c.bstride < (int64_t)H * W) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: head channel %d", i);
+      p.head_wc[i] = c.w; p.head_bs[i] = c.b; p.head_acts[i] = c.act; p.head_out[i] = c.out; p.head_bstride[i] = (long)c.bstride;
+    }
+    if (d->head_nch == 0) {
+      if (!d->head_w) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: head_w missing");
+      p.head_w = d->head_w; p.head_b = d->head_b; p.head_act = d->head_act; p.out = d->out;
+    }
+  } else {
+    // md_engine.hip run_decoder_head, "head_tail_fused": deconv k2s2 -> conv1 3x3 -> relu -> conv_out 1x1 -> relu on conv0's output
+    p.N = 4 * 32; p.ngroups = 1; p.g_rows[0] = B * H * W; p.W[0] = cw[0].w;
+    p.A = d->in; p.cH = H; p.cW = W; p.zero_page = geom.zero_page;
+    split_conv_a(geom, p, Cin_p, 3);
+    p.epi = EPI_HEAD_UP2; p.bias[0] = cw[0].b; p.head_w = d->head_w;
+    p.head_b = d->head_b;
+    p.out = d->out;
+  }
+  // the tiles the call sites fix: tail() launches TILE_256x32, the composed head TILE_128x128; everything else TILE_AUTO
+  int tile = d->tile;
+  if (tile == TILE_AUTO && head) tile = TILE_256x32;
+  if (tile == TILE_AUTO && up2) tile = TILE_128x128;
+  gemm_forget_form();
+  MD_TRY(launch_gemm(p, amode, prec, tile, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_debug_gemm_last_launch(int out[4]) {
+  if (!out) return MD_ERR_INVALID_ARG;
+  const LaunchNote n = gemm_last_launch();
+  out[0] = n.tile; out[1] = n.ps_fast; out[2] = 0; out[3] = 0;
+  return MD_OK;
+}
+
 int md_debug_gemm_last_form(int out[8]) {
   if (!out) return MD_ERR_INVALID_ARG;
   const Form256 f = gemm_last_form();

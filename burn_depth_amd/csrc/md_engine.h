@@ -425,6 +425,10 @@ int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_camera
                     const md_view_filter_outputs* out, hipStream_t stream);
 void points_destroy_state(md_model_t m);
 int pack_weight(const float* src, const PackEntry& e, int prec, hipStream_t s);
+// PACK_HEAD_W / PACK_HEAD_B as model_commit composes them: `out` fp32 [4 * cout][cin][3][3] (pack_weight's PACK_CONV3 source) and
+// fp32 [9][cout]
+int compose_head(const float* wd, const float* w1, int cin, int cmid, int cout, float* out, hipStream_t s);
+int compose_head_bias(const float* w1, const float* bd, const float* b1, int cmid, int cout, float* out, hipStream_t s);
 // number of values of w[0..n) that are not exactly representable as an IEEE half (synchronises the stream)
 int count_inexact_f16(const float* w, long n, hipStream_t s, unsigned* out);
 void fov_scalar_host(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad);

@@ -209,28 +209,41 @@ inline int cpad(const md_model_s* m, int ch) { return (ch + m->ke - 1) / m->ke *
 // (md_model_s::wterms); the products composed at commit are never f16-exact and pass 3.
 // (a fork reads its ROOT's term count: a re-commit on the root may change it while the fork lives, and the packed rows the
 // fork's launches read are the root's)
-inline int split_terms(const md_model_s* m, int terms) { return m->xm == 1 ? 1 : (terms > 0 ? terms : (m->parent ? m->parent : m)->wterms); }
+// What these helpers and the launch-parameter builders below read of a model, and ALL they read: the operand geometry of its
+// precision. The engines pass geom_of(model); md_op_decoder_gemm builds one for a precision alone.
+struct OperandGeom {
+  int ke = 64;      // contraction elements per 128-byte LDS row
+  int xm = 1;       // planes per activation element (2: split-half)
+  int wterms = 1;   // split-half: MFMA terms of a product with a plain weight (md_model_s::wterms of the ROOT model)
+  void* zero_page = nullptr;
+};
+inline OperandGeom geom_of(const md_model_s* m) { return OperandGeom{m->ke, m->xm, (m->parent ? m->parent : m)->wterms, m->zero_page}; }
+inline int split_terms(const OperandGeom& o, int terms) { return o.xm == 1 ? 1 : (terms > 0 ? terms : o.wterms); }
+inline int split_terms(const md_model_s* m, int terms) { return split_terms(geom_of(m), terms); }
 // dense / indexed A operand of `kp` logical channels per row
-inline void split_dense_a(const md_model_s* m, GemmParams& p, int kp, long lda, int terms) {
-  const int t = split_terms(m, terms);
+inline void split_dense_a(const OperandGeom& o, GemmParams& p, int kp, long lda, int terms) {
+  const int t = split_terms(o, terms);
   p.K = kp * t;
-  p.lda = lda * m->xm;
-  p.a_wrap = t == 3 ? 2 * kp / m->ke : 0;
+  p.lda = lda * o.xm;
+  p.a_wrap = t == 3 ? 2 * kp / o.ke : 0;
 }
+inline void split_dense_a(const md_model_s* m, GemmParams& p, int kp, long lda, int terms) { split_dense_a(geom_of(m), p, kp, lda, terms); }
 // 3x3-convolution A operand: NHWC pixels of `cin_p` logical channels
-inline void split_conv_a(const md_model_s* m, GemmParams& p, int cin_p, int terms) {
-  const int t = split_terms(m, terms);
-  p.cC = cin_p * m->xm;
-  p.cCk = m->xm == 1 ? 0 : cin_p * t;
+inline void split_conv_a(const OperandGeom& o, GemmParams& p, int cin_p, int terms) {
+  const int t = split_terms(o, terms);
+  p.cC = cin_p * o.xm;
+  p.cCk = o.xm == 1 ? 0 : cin_p * t;
   p.K = 9 * cin_p * t;
-  p.a_wrap = t == 3 ? 2 * cin_p / m->ke : 0;
+  p.a_wrap = t == 3 ? 2 * cin_p / o.ke : 0;
 }
+inline void split_conv_a(const md_model_s* m, GemmParams& p, int cin_p, int terms) { split_conv_a(geom_of(m), p, cin_p, terms); }
 // T-typed output (and residual inputs) with `ldo` logical channels per row
-inline void split_out(const md_model_s* m, GemmParams& p, long ldo, bool t_out) {
+inline void split_out(const OperandGeom& o, GemmParams& p, long ldo, bool t_out) {
   if (!t_out) { p.ldo = ldo; return; }
-  p.ldo = ldo * m->xm;
-  p.o_plane = m->xm == 2 ? ldo : 0;
+  p.ldo = ldo * o.xm;
+  p.o_plane = o.xm == 2 ? ldo : 0;
 }
+inline void split_out(const md_model_s* m, GemmParams& p, long ldo, bool t_out) { split_out(geom_of(m), p, ldo, t_out); }
 
 // 1x1 conv / linear over NHWC rows.  A may be gathered through `idx`.
 inline int gemm_rows(Run& r, const char* name, const void* A, long lda, const int* idx, long M, const void* W, int N, int K,
@@ -248,15 +261,21 @@ inline int gemm_rows(Run& r, const char* name, const void* A, long lda, const in
 }
 
 // ConvTranspose2d k=2 s=2 as GEMM + pixel shuffle (encoder.rs:61-69, decoder.rs:100-105, mod.rs:81-84)
+// (the launch parameters apart from the launch: md_op_decoder_gemm launches the very same ones on a caller's buffers)
+inline GemmParams deconv2_params(const OperandGeom& m, int B, const void* A, long lda, const int* idx, int h, int w, const void* W, int Cin_p,
+                                 int Cout, const float* bias, void* out, long ldo, int coff, void* out2 = nullptr, int f = 2, int terms = 0) {
+  GemmParams p;
+  p.N = f * f * Cout; p.ngroups = 1; p.g_rows[0] = B * h * w; p.W[0] = W; p.ps_f = f;
+  p.A = A; p.a_index = idx;
+  split_dense_a(m, p, Cin_p, lda, terms);
+  p.epi = EPI_PIXSHUF; p.bias[0] = bias; p.out = out; p.out2 = out2;
+  split_out(m, p, ldo, true);
+  p.psH = h; p.psW = w; p.psC = Cout; p.ps_coff = coff;
+  return p;
+}
 inline int deconv2(Run& r, const char* name, const void* A, long lda, const int* idx, int h, int w, const void* W, int Cin_p,
             int Cout, const float* bias, void* out, long ldo, int coff, void* out2 = nullptr, int f = 2, int terms = 0) {
-  GemmParams p;
-  p.N = f * f * Cout; p.ngroups = 1; p.g_rows[0] = r.B * h * w; p.W[0] = W; p.ps_f = f;
-  p.A = A; p.a_index = idx;
-  split_dense_a(r.m, p, Cin_p, lda, terms);
-  p.epi = EPI_PIXSHUF; p.bias[0] = bias; p.out = out; p.out2 = out2;
-  split_out(r.m, p, ldo, true);
-  p.psH = h; p.psW = w; p.psC = Cout; p.ps_coff = coff;
+  const GemmParams p = deconv2_params(geom_of(r.m), r.B, A, lda, idx, h, w, W, Cin_p, Cout, bias, out, ldo, coff, out2, f, terms);
   r.begin(name);
   int s = launch_gemm(p, idx ? A_INDEXED : A_DENSE, r.m->prec, TILE_AUTO, r.st);
   r.end();
@@ -265,22 +284,28 @@ inline int deconv2(Run& r, const char* name, const void* A, long lda, const int*
 
 // Conv2d 3x3 s1 p1 over NHWC as implicit GEMM (decoder.rs:55-72,167-175; mod.rs:78-87). G > 1: weight set w[g] over images
 // [g*B, (g+1)*B) of `in` / `out` (`in_shared`: every group reads images [0, B) of `in`; `res1_shared`: the same for res1)
-inline int conv3(Run& r, const char* name, const void* in, int H, int W, int Cin_p, const ConvW* w, int Cout, void* out, long ldo,
-                 int act, const void* res1, const void* res2, void* out2, int terms = 0, int G = 1, bool in_shared = false,
-                 bool res1_shared = false) {
+inline GemmParams conv3_params(const OperandGeom& m, int B, const void* in, int H, int W, int Cin_p, const ConvW* w, int Cout, void* out,
+                                long ldo, int act, const void* res1, const void* res2, void* out2, int terms = 0, int G = 1,
+                                bool in_shared = false, bool res1_shared = false) {
   GemmParams p;
-  const int M = r.B * H * W;
+  const int M = B * H * W;
   p.N = Cout; p.ngroups = G;
   for (int g = 0; g < G; ++g) {
     p.g_rows[g] = M; p.g_row0[g] = g * M; p.g_arow0[g] = in_shared ? 0 : g * M;
     p.W[g] = w[g].w; p.bias[g] = w[g].b;
   }
-  p.A = in; p.cH = H; p.cW = W; p.zero_page = r.m->zero_page;
-  split_conv_a(r.m, p, Cin_p, terms);
+  p.A = in; p.cH = H; p.cW = W; p.zero_page = m.zero_page;
+  split_conv_a(m, p, Cin_p, terms);
   p.epi = EPI_STORE; p.act = act; p.out = out; p.out2 = out2;
-  split_out(r.m, p, ldo, true);
+  split_out(m, p, ldo, true);
   p.res1 = res1; p.res2 = res2; p.ldr = p.ldo; p.r_plane = (res1 || res2) ? p.o_plane : 0;
   if (res1 && res1_shared && G > 1) p.res_mod = M;
+  return p;
+}
+inline int conv3(Run& r, const char* name, const void* in, int H, int W, int Cin_p, const ConvW* w, int Cout, void* out, long ldo,
+                 int act, const void* res1, const void* res2, void* out2, int terms = 0, int G = 1, bool in_shared = false,
+                 bool res1_shared = false) {
+  const GemmParams p = conv3_params(geom_of(r.m), r.B, in, H, W, Cin_p, w, Cout, out, ldo, act, res1, res2, out2, terms, G, in_shared, res1_shared);
   r.begin(name);
   int s = launch_gemm(p, A_CONV3, r.m->prec, TILE_AUTO, r.st);
   r.end();

@@ -411,10 +411,81 @@ def vit_gemm(dev: Device, kind: int, a: torch.Tensor, groups, precision: int, ti
 
 
 def gemm_last_form() -> dict:
-    """md_debug_gemm_last_form: what this thread's last 256 x 256 GEMM launch ran (family -1: md_op_vit_gemm took another tile)."""
-    v = (C.c_int * 8)()
+    """md_debug_gemm_last_form + md_debug_gemm_last_launch: what this thread's last 256 x 256 GEMM launch ran (family -1: the operator
+    entry took another tile), and the tile and pixel-shuffle form (`tile`, `ps_fast`) launch_gemm resolved for the entry's launch."""
+    v, n = (C.c_int * 8)(), (C.c_int * 4)()
     _lib.check(_lib.load().md_debug_gemm_last_form(C.byref(v)))
-    return dict(zip(("family", "ek", "fold", "qkv", "conv", "diag", "blocks", "grid"), list(v)))
+    _lib.check(_lib.load().md_debug_gemm_last_launch(C.byref(n)))
+    return dict(zip(("family", "ek", "fold", "qkv", "conv", "diag", "blocks", "grid", "tile", "ps_fast"), list(v) + list(n)[:2]))
+
+
+def decoder_gemm(dev: Device, kind: int, x: torch.Tensor, w, bias, precision: int, tile: int = _lib.TILE_AUTO, *, B: int, H: int, W: int, Cin: int,
+                 Cin_p: int, Cout: int, out: Optional[torch.Tensor] = None, ldo: int = 0, act: int = 0, res1: Optional[torch.Tensor] = None,
+                 res2: Optional[torch.Tensor] = None, res_mod: int = 0, out2: Optional[torch.Tensor] = None, in_shared: bool = False,
+                 res1_shared: bool = False, out_f32: bool = False, ps_f: int = 2, ps_coff: int = 0, head=None, head_w: Optional[torch.Tensor] = None,
+                 head_b: float = 0.0, head_act: int = 0, Cmid: int = 0, w2: Optional[torch.Tensor] = None, bias2: Optional[torch.Tensor] = None) -> None:
+    """md_op_decoder_gemm: one GEMM form of the convolutional decoders / heads (kind = _lib.DECODER_GEMM_*) on the CALLER's buffers,
+    updated in place. x, res1, res2, out, out2: raw storage tensors (`store_rows` / `nchw_to_nhwc`), fp32 where the form stores fp32;
+    w, bias: fp32 masters, lists of two for two weight groups; head: dicts with w [32], b, act, out (fp32), bstride."""
+    ws = list(w) if isinstance(w, (list, tuple)) else [w]
+    bs = list(bias) if isinstance(bias, (list, tuple)) else [bias] * len(ws)
+    G, xm, raw = len(ws), (2 if precision == 4 else 1), _RAW_DTYPE.get(precision)
+    conv, s2, ps, hd, up2 = (kind == k for k in range(5))
+    assert 1 <= G <= 2 and len(bs) == G and (G == 1 or conv)
+    OH, OW = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if s2 else ((ps_f * H, ps_f * W) if ps else (H, W))
+    f32s = [t for t in ws + bs + [head_w, w2, bias2] if t is not None]
+    for t in f32s:
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32, "weights and biases are contiguous fp32 device tensors"
+    taps = ps_f * ps_f if ps else (4 if up2 else 9)
+    for t in ws:
+        assert t.numel() == Cin * (Cmid if up2 else Cout) * taps, "weight shape"
+    for t in bs:
+        assert t is None or t.numel() == (Cmid if up2 else Cout), "bias shape"
+
+    def holds(t, elems, dtype, what):   # (an output may be longer: rows behind the launch's are the caller's)
+        ok = t.numel() >= elems if what.startswith("out") else t.numel() == elems
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and ok, f"{what}: {tuple(t.shape)} {t.dtype}, expected {elems} of {dtype}"
+
+    holds(x, (1 if in_shared else G) * B * H * W * Cin_p * xm, raw, "x")
+    d = _lib.MdDecoderGemm()
+    d.kind, d.precision, d.tile, d.B, d.H, d.W, d.Cin, d.Cin_p, d.Cout, d.ngroups = kind, precision, tile, B, H, W, Cin, Cin_p, Cout, G
+    d.in_shared, d.res1_shared, d.act, d.res_mod, d.ldo, d.out_f32, d.ps_f, d.ps_coff = int(in_shared), int(res1_shared), act, res_mod, ldo, int(out_f32), ps_f, ps_coff
+    for g in range(G):
+        d.w[g], d.bias[g] = ws[g].data_ptr(), (bs[g].data_ptr() if bs[g] is not None else None)
+    d.in_ = x.data_ptr()
+    if conv or s2 or ps:
+        if out_f32:
+            holds(out, B * OH * OW * Cout, torch.float32, "out")
+        else:
+            assert ldo >= (ps_coff if ps else 0) + Cout
+            holds(out, G * B * OH * OW * ldo * xm, raw, "out")
+        if out2 is not None:
+            holds(out2, G * B * OH * OW * ldo * xm, raw, "out2")
+        if res1 is not None:
+            holds(res1, (res_mod if res_mod else (1 if res1_shared else G) * B * OH * OW) * ldo * xm, raw, "res1")
+        if res2 is not None:
+            holds(res2, G * B * OH * OW * ldo * xm, raw, "res2")
+        d.out, d.out2 = out.data_ptr(), (out2.data_ptr() if out2 is not None else None)
+        d.res1, d.res2 = (res1.data_ptr() if res1 is not None else None), (res2.data_ptr() if res2 is not None else None)
+    elif hd:
+        chans = list(head or [])
+        d.head_nch = len(chans)
+        assert len(chans) <= 8
+        for i, c in enumerate(chans):
+            o, stride = c["out"], int(c["bstride"])
+            assert o.is_cuda and o.dtype == torch.float32 and stride >= H * W and c["w"].numel() == 32 and c["w"].dtype == torch.float32 and c["w"].is_cuda
+            assert o.numel() >= (B - 1) * stride + H * W, "head plane outside its tensor"   # (a view into a wider tensor: storage behind it is the caller's)
+            d.ch[i].w, d.ch[i].b, d.ch[i].act, d.ch[i].out, d.ch[i].bstride = c["w"].data_ptr(), float(c["b"]), int(c["act"]), o.data_ptr(), stride
+        if not chans:
+            holds(out, B * H * W, torch.float32, "out")
+            assert head_w is not None and head_w.numel() == 32
+            d.head_w, d.head_b, d.head_act = head_w.data_ptr(), float(head_b), head_act
+        d.out = out.data_ptr() if out is not None else chans[0]["out"].data_ptr()
+    else:
+        holds(out, B * 4 * H * W, torch.float32, "out")
+        assert head_w.numel() == 32 and w2.numel() == 32 * Cmid * 9 and bias2.numel() == 32
+        d.out, d.head_w, d.head_b, d.Cmid, d.w2, d.bias2 = out.data_ptr(), head_w.data_ptr(), float(head_b), Cmid, w2.data_ptr(), bias2.data_ptr()
+    _lib.check(_lib.load().md_op_decoder_gemm(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
 
 
 def conv2d_direct_ex(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor], stride: int,

@@ -1212,6 +1212,60 @@ int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* desc, void* stream);
  * 1 the fc1 / QKV / lean-convolution tile loop, 2 the read-modify-write tile loop; -1: md_op_vit_gemm launched another tile), epilogue kind
  * (the one-tile kernel's EK; for a loop the kind it replaces), fold, qkv, conv, diag, tiles, workgroups. */
 int md_debug_gemm_last_form(int out[8]);
+/* Host-only: what the calling thread's last GEMM launch through md_op_vit_gemm / md_op_decoder_gemm resolved, whichever kernel of the
+ * family took it -- out[4] = tile (0 = 256x256, 1 = 128x128, 2 = 256x32, 3 = 128x64, 4 = 64x64; -1: no launch), the launcher-set fast
+ * form of the pixel shuffle (16-byte stores of whole 8-column groups), 0, 0. */
+int md_debug_gemm_last_launch(int out[4]);
+/* ---- the GEMM forms of the convolutional decoders and heads alone (test-only): one launch of the GEMM family with the parameters the
+ * engines' call sites give it, on buffers the CALLER owns. Activations, residual inputs and T-typed outputs are raw device tensors of
+ * `precision`'s storage type in the engine's layout: NHWC pixels of `ld` logical channels, split-half pixels [hi: ld | lo: ld]
+ * (md_op_nchw_to_nhwc / md_op_store_rows write them, md_op_load_rows / md_op_nhwc_to_nchw read them); fp32 outputs are float tensors.
+ * Weights and biases are fp32 masters, packed per call as the engine packs them at commit (split-half: two terms when every weight
+ * of the launch is an exact half, else three; the composed head weight always three). The entry allocates no output and pre-fills
+ * nothing; it launches and synchronises. MD_PREC_BF16 / F16 / F16X2 / F32; anything else is MD_ERR_INVALID_ARG. ---- */
+typedef enum md_decoder_gemm_kind {
+  MD_DECODER_GEMM_CONV3 = 0,    /* 3x3 s1 p1, EPI_STORE: out = act(conv + bias + res1 + res2), out2 = relu(out); 1 or 2 weight groups */
+  MD_DECODER_GEMM_CONV3_S2 = 1, /* 3x3 s2 p1, EPI_STORE: T-typed NHWC output, or (out_f32) fp32 rows of Cout with a ReLU */
+  MD_DECODER_GEMM_PIXSHUF = 2,  /* ConvTranspose2d k = s = f (2 or 4) into channels [ps_coff, ps_coff + Cout) of NHWC pixels of ldo */
+  MD_DECODER_GEMM_HEAD = 3,     /* 3x3 s1 p1 to 32 channels -> relu -> 1x1 to head_nch channels (0: one, `head_w`) -> act, fp32 planes */
+  MD_DECODER_GEMM_HEAD_UP2 = 4  /* deconv k2s2 -> conv 3x3 to 32 -> relu -> 1x1 -> relu composed into one launch, fp32 [B, 2H, 2W] */
+} md_decoder_gemm_kind;
+typedef struct md_decoder_gemm_head_ch {
+  const float* w; /* [32] */
+  float b;
+  int act;        /* 0 relu, 1 exp, 2 linear, 3 exp + 1 */
+  float* out;     /* pixel (img, y, x) at out[img * bstride + y * W + x] */
+  int64_t bstride;
+} md_decoder_gemm_head_ch;
+typedef struct md_decoder_gemm {
+  int kind, precision, tile; /* tile: 99 = the launcher's choice, else 0 .. 4 as md_debug_gemm_last_launch names them */
+  int B, H, W;               /* input pixel grid of ONE weight group */
+  int Cin, Cin_p;            /* weight input channels; logical channels per input pixel (the contraction runs over all Cin_p, weights zero-padded) */
+  int Cout;                  /* HEAD / HEAD_UP2: 32 */
+  int ngroups;               /* CONV3: 1 or 2 -- group g = weights g on images [g B, (g + 1) B) of out / out2 / res2 */
+  int in_shared, res1_shared;/* CONV3, two groups: both read images [0, B) of in / of res1 (else group g reads its own images) */
+  const float* w[2];         /* CONV3*, HEAD: [Cout, Cin, 3, 3]; PIXSHUF: [Cin, Cout, f, f]; HEAD_UP2: the deconvolution [Cin, Cmid, 2, 2] */
+  const float* bias[2];      /* [Cout]; may be NULL for CONV3; HEAD_UP2: the deconvolution's [Cmid] */
+  const void* in;            /* [images, H, W, Cin_p] T */
+  int act;                   /* CONV3: 0 none, 1 relu */
+  const void* res1;          /* CONV3, optional: [.., OH, OW, ldo] T */
+  const void* res2;
+  int res_mod;               /* CONV3, one group, > 0: res1 row = m % res_mod (a table the images share) */
+  void* out;                 /* T: [images, OH, OW, ldo]; out_f32: float [M, Cout]; HEAD: one-channel plane float [M]; HEAD_UP2: float [B, 2H, 2W] */
+  void* out2;                /* CONV3 / PIXSHUF, optional: relu(out), same layout */
+  int ldo;                   /* logical channels per output pixel */
+  int out_f32;               /* CONV3_S2: the fp32 form (ldo = Cout) */
+  int ps_f, ps_coff;         /* PIXSHUF */
+  int head_nch;              /* HEAD: 0 = the one-channel form (head_w, head_b, head_act, out), else 1 .. 8 channels `ch` in one launch */
+  md_decoder_gemm_head_ch ch[8];
+  const float* head_w;       /* HEAD one-channel form, HEAD_UP2: [32] */
+  float head_b;
+  int head_act;              /* HEAD one-channel form */
+  int Cmid;                  /* HEAD_UP2: channels between the deconvolution and the 3x3 convolution */
+  const float* w2;           /* HEAD_UP2: the 3x3 convolution [32, Cmid, 3, 3] */
+  const float* bias2;        /* HEAD_UP2: [32] */
+} md_decoder_gemm;
+int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* desc, void* stream);
 /* md_op_conv2d_direct as the FOV head runs it: the input held in `in_precision`'s storage type, add = optional fp32 NHWC tensor added
  * to the input, out = fp32 NHWC [B, OH, OW, out_ld] (out_ld 0 = Cout; columns Cout .. out_ld are not written). */
 int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* add_dev, int B,
