@@ -94,6 +94,12 @@ class MdPointsComponents(C.Structure):
                 ("face_capacity", C.c_int64), ("stats", C.c_void_p)]
 
 
+class MdPointsSmooth(C.Structure):
+    """md_points_smooth (include/mi_depth.h)."""
+    _fields_ = [("step", C.c_float), ("lam", C.c_float), ("mu", C.c_float), ("iterations", C.c_int32), ("pin_boundary", C.c_int32),
+                ("xyz", C.c_void_p), ("normals", C.c_void_p), ("stats", C.c_void_p)]
+
+
 class MdRenderOpts(C.Structure):
     """md_render_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
@@ -287,6 +293,12 @@ SYMBOLS = {
                                         C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate),
                                         C.POINTER(MdPointsComponents), _I, _P]),
     "md_op_mesh_components": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsComponents), C.POINTER(MdPointsOutputs), _P, _P]),
+    "md_infer_points_smooth": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
+                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
+                                    C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
+                                    C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate),
+                                    C.POINTER(MdPointsComponents), C.POINTER(MdPointsSmooth), _I, _P]),
+    "md_op_smooth_mesh": (_I, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsSmooth), C.c_int64, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),

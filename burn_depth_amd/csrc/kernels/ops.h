@@ -191,6 +191,29 @@ struct ComponentsParams {
 size_t components_scratch_bytes(int n, int nf, int B);
 int launch_mesh_components(const ComponentsParams& p, void* scratch, hipStream_t s);
 
+// ---- Taubin / Laplacian smoothing of a mesh and its vertex normals (kernels/smooth.hip, kernels/smooth_math.h; md_op_smooth_mesh) ----
+// Rows xyz [n,3] and faces [nf,3] over them -> the smoothed rows and the area-weighted normals of the smoothed faces. The rows
+// move on an integer lattice of side `step` and every sum is an int64 sum, so nothing depends on the order of arrival
+// (include/mi_depth.h states the contract, pipeline.smooth_mesh restates it). Every pointer is a device pointer.
+struct SmoothParams {
+  const float* xyz = nullptr;              // [n,3]
+  const int32_t* in_count = nullptr;       // [B + 1] the list's device count: the live rows are min(in_count[B], n); null: n rows
+  int n = 0;                               // rows the launches cover
+  int B = 1;
+  const int32_t* faces = nullptr;          // [nf,3]
+  const int32_t* in_face_count = nullptr;  // [B + 1] likewise for the faces; null: nf faces
+  int nf = 0;
+  float step = 0.f, lambda = 0.f, mu = 0.f;
+  int iterations = 0, pin_boundary = 0;
+  float* xyz_out = nullptr;                // [capacity,3]; null: skip
+  float* normals_out = nullptr;            // [capacity,3]; null: no normal launches
+  int32_t* stats = nullptr;                // [5] invalid faces, degenerate faces, rows not in range, open rows, moved rows; null: scratch
+  long capacity = 0;                       // rows of the outputs that may be written
+};
+// bytes of the scratch: per row the lattice position and the accumulator (3 int64 each), open (uint64), deg and the range flag
+size_t smooth_scratch_bytes(int n);
+int launch_smooth_mesh(const SmoothParams& p, void* scratch, hipStream_t s);
+
 // ---- radius outlier removal (kernels/outlier.hip; md_op_radius_outliers, md_infer_points_outlier) ----
 // A point list xyz [n,3] (+ conf, rgb, normals rows) -> the rows with at least k other rows within `radius`, in ascending input
 // index: reset, insert (voxel thinning's table with a count per slot), bucket allocation, fill (the positions bucket by

@@ -609,6 +609,21 @@ int md_op_mesh_components(md_device_t dev, const float* xyz_dev, const float* co
   return op_mesh_components(dev, PointList{xyz_dev, conf_dev, rgb_dev, normals_dev, N}, faces_dev, F, comp, out, normals_out, (hipStream_t)stream);
 }
 
+int md_infer_points_smooth(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                           const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, const md_points_raster* rst,
+                           const md_points_outlier* outl, const md_points_decimate* dec, const md_points_components* comp,
+                           const md_points_smooth* smooth, int out_kind, void* stream) {
+  PointsCall c{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh, rst};
+  c.outl = outl; c.dec = dec; c.comp = comp; c.smooth = smooth;
+  return infer_points(m, c, (hipStream_t)stream);
+}
+
+int md_op_smooth_mesh(md_device_t dev, const float* xyz_dev, int64_t N, const int32_t* faces_dev, int64_t F, const md_points_smooth* smooth,
+                      int64_t capacity, void* stream) {
+  return op_smooth_mesh(dev, xyz_dev, N, faces_dev, F, smooth, capacity, (hipStream_t)stream);
+}
+
 int md_raster_inline_pixels(void) { return md::raster_inline_pixels(); }
 int md_debug_raster_queue(int capacity) { return capacity < 0 ? MD_ERR_INVALID_ARG : md::raster_queue_capacity(capacity); }
 

@@ -49,6 +49,7 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> dfaces;       // its input: the faces of the unthinned list [2 rows,3] | their face_count [B+1]
                                   // (md_infer_points_components: the unfiltered faces of the call's list, likewise)
   md::GrowBuf<void> ctable;       // md_infer_points_components: the components' scratch (components_scratch_bytes)
+  md::GrowBuf<void> stable;       // md_infer_points_smooth: the smoothing's scratch (smooth_scratch_bytes)
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
@@ -216,6 +217,27 @@ int check_components_part(const md_points_components* k) {
   if (k->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)k->face_capacity);
   if ((k->faces || k->face_index) && !k->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
   return MD_OK;
+}
+
+bool smooth_on(const md_points_smooth* s) { return s && s->iterations != 0; }
+
+// the contract's limits of a stage that is on; the negated forms refuse a NaN
+int check_smooth_values(const md_points_smooth* s) {
+  if (!(s->step > 0.f) || !std::isfinite(s->step)) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing: step = %g must be finite and > 0", (double)s->step);
+  if (!(s->lambda > 0.f && s->lambda <= 1.f)) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing: lambda = %g must lie in (0, 1]", (double)s->lambda);
+  if (!(s->mu >= -1.f && s->mu <= 0.f)) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing: mu = %g must lie in [-1, 0]", (double)s->mu);
+  if (s->iterations < 1 || s->iterations > 1024) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing: iterations = %d must lie in 1..1024", s->iterations);
+  return MD_OK;
+}
+
+// model call: iterations == 0 is the call without the stage and takes none of its outputs
+int check_smooth_part(const md_points_smooth* s) {
+  if (!s) return MD_OK;
+  if (s->iterations == 0) {
+    if (s->xyz || s->normals || s->stats) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing outputs without iterations");
+    return MD_OK;
+  }
+  return check_smooth_values(s);
 }
 
 bool outlier_on(const md_points_outlier* q) { return q && q->radius != 0.f; }
@@ -604,6 +626,29 @@ int op_mesh_components(md_device_t dev, const PointList& in, const int32_t* face
   return scratch.finish(launch_mesh_components(p, scratch.p, st));
 }
 
+int op_smooth_mesh(md_device_t dev, const float* xyz, int64_t N, const int32_t* faces, int64_t F, const md_points_smooth* smooth, int64_t capacity,
+                   hipStream_t stream) {
+  if (!smooth) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing options are null");
+  MD_TRY(check_smooth_values(smooth));
+  if (N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)N);
+  if (F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)F);
+  if (capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "capacity %lld is negative", (long long)capacity);
+  if (N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 rows, got %lld", (long long)N);
+  if (F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 faces, got %lld", (long long)F);
+  if (N > 0 && !xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = stream ? stream : dev->stream;
+  SmoothParams p;
+  p.xyz = xyz; p.n = (int)N; p.faces = faces; p.nf = (int)F;
+  p.step = smooth->step; p.lambda = smooth->lambda; p.mu = smooth->mu; p.iterations = smooth->iterations; p.pin_boundary = smooth->pin_boundary;
+  p.xyz_out = smooth->xyz; p.normals_out = smooth->normals; p.stats = smooth->stats; p.capacity = (long)capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(smooth_scratch_bytes(p.n)));
+  return scratch.finish(launch_smooth_mesh(p, scratch.p, st));
+}
+
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream) {
   MD_TRY(check_render(T, H, W, cam, o, out, in.rgb != nullptr));
@@ -711,6 +756,8 @@ struct PointsPlan {
   DecimateParams d; // deci: launch_decimate_mesh's, from the model's own list and the faces `gd` wrote; d.v fills the list outputs of the call
   MeshParams gd;    // deci / comp: the mesh stage's second set of face outputs, the model's own, complete and with the true count
   ComponentsParams k;  // comp: launch_mesh_components', from the list's count and the faces `gd` wrote
+  bool smo = false;    // the smoothing is on
+  SmoothParams sm;     // smo: launch_smooth_mesh's, from the list outputs of the call and the faces of `k`, or else those `gd` wrote
   int queue = 0;    // its queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   std::vector<OutSlot> slots;
@@ -851,6 +898,11 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(k.faces, pl.k.faces_out, 12, (size_t)k.face_capacity, 5);
     slot(k.face_index, pl.k.face_index, 4, (size_t)k.face_capacity, 5);
   }
+  if (pl.smo) {  // rows parallel to the list: they travel as its rows do
+    slot(c.smooth->xyz, pl.sm.xyz_out, 12, cap, 1);
+    slot(c.smooth->normals, pl.sm.normals_out, 12, cap, 1);
+    slot(c.smooth->stats, pl.sm.stats, 4, 5, 0);
+  }
   return total;
 }
 
@@ -895,8 +947,9 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   }
   pl.deci = decimate_on(c.dec);
   pl.comp = components_on(c.comp);
-  pl.mesh = mesh_on(c.mesh) || pl.deci || pl.comp;
-  if (pl.comp) {  // the caller's list as ever (a corner is usable below its capacity); the map always has a home
+  pl.smo = smooth_on(c.smooth);
+  pl.mesh = mesh_on(c.mesh) || pl.deci || pl.comp || pl.smo;
+  if (pl.comp || pl.smo) {  // the caller's list as ever (a corner is usable below its capacity); the map always has a home
     pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
     MD_TRY(grow(m, st, f->mesh, mesh_scratch_bytes(B, H, W, c.o->stride) + align_up(pl.npx * 4, 256)));
   } else if (pl.deci) {  // the faces name rows of the model's own, unthinned list: every row of it is usable; the map always has a home
@@ -911,17 +964,29 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, f->out, total));
     place_outputs(c, pl, (char*)f->out.p);
   }
-  if (pl.comp) {  // all faces of the call's list go to the model's face home; the stage reads them and the list's device count
-    ComponentsParams& k = pl.k;
+  if (pl.comp || pl.smo) {  // all faces of the call's list go to the model's face home; the stages read them and the list's device count
     const long rows = list_rows(B, H, W, c.o->stride), nf = 2 * rows;
     const size_t b_faces = align_up((size_t)nf * 12, 256);
     MD_TRY(grow(m, st, f->dfaces, b_faces + align_up((size_t)(B + 1) * 4, 256)));
-    MD_TRY(grow(m, st, f->ctable, components_scratch_bytes((int)rows, (int)nf, B)));
     pl.gd = pl.g;
     pl.gd.faces = (int32_t*)f->dfaces.p; pl.gd.face_count = (int32_t*)((char*)f->dfaces.p + b_faces); pl.gd.face_capacity = nf;
-    k.v.in_count = p.count; k.v.n = (int)rows; k.v.B = B;
-    k.faces = pl.gd.faces; k.in_face_count = pl.gd.face_count; k.nf = (int)nf;
-    k.min_faces = c.comp->min_faces; k.face_capacity = (long)c.comp->face_capacity;
+    if (pl.comp) {
+      ComponentsParams& k = pl.k;
+      MD_TRY(grow(m, st, f->ctable, components_scratch_bytes((int)rows, (int)nf, B)));
+      k.v.in_count = p.count; k.v.n = (int)rows; k.v.B = B;
+      k.faces = pl.gd.faces; k.in_face_count = pl.gd.face_count; k.nf = (int)nf;
+      k.min_faces = c.comp->min_faces; k.face_capacity = (long)c.comp->face_capacity;
+    }
+    if (pl.smo) {  // the rows of the call's list below its capacity; the faces the rasteriser reads
+      SmoothParams& sm = pl.sm;
+      const md_points_smooth& o = *c.smooth;
+      sm.xyz = p.xyz; sm.in_count = p.count; sm.B = B; sm.n = (int)std::min<long>((long)out.capacity, rows);
+      sm.faces = pl.comp ? pl.k.faces_out : pl.gd.faces; sm.in_face_count = pl.comp ? pl.k.face_count : pl.gd.face_count;
+      sm.nf = (int)(pl.comp ? std::min<long>((long)c.comp->face_capacity, nf) : nf);
+      sm.step = o.step; sm.lambda = o.lambda; sm.mu = o.mu; sm.iterations = o.iterations; sm.pin_boundary = o.pin_boundary;
+      sm.capacity = (long)out.capacity;
+      MD_TRY(grow(m, st, f->stable, smooth_scratch_bytes(sm.n)));
+    }
   }
   if (!pl.thin && !pl.filt && !pl.deci) return MD_OK;
   // voxel thinning / outlier removal: the scatter fills the model's own list, the last of the two writes where the list would
@@ -1056,7 +1121,7 @@ int run_unproject(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
 // The mesh of the list: needs the scratch of run_unproject's launches before anything reuses it.
 int run_mesh(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.g.depth = pl.depth;
-  if (pl.deci || pl.comp) {  // the map, then the model's own faces, complete, for the decimation / the components; the caller's,
+  if (pl.deci || pl.comp || pl.smo) {  // the map, then the model's own faces, complete, for the decimation / the components / the smoothing; the caller's,
                              // if it takes them, are a copy: both have the same rows of the list as usable corners, so they are
                              // the same faces
     void* home = m->points->mesh.p;
@@ -1093,6 +1158,9 @@ int run_decimate(md_model_s* m, const PointsCall&, PointsPlan& pl) {
 // Island removal: the faces the mesh stage left in the model's home -> comp's outputs. The list is not touched.
 int run_components(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_mesh_components(pl.k, m->points->ctable.p, pl.st); }
 
+// Smoothing: the list of the call and the faces the rasteriser reads -> smooth's outputs. The list is not touched.
+int run_smooth(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_smooth_mesh(pl.sm, m->points->stable.p, pl.st); }
+
 // Rendering: the list outputs of the call, thinned or not, and their device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
@@ -1124,6 +1192,7 @@ int run_raster(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     s.faces = pl.k.faces_out; s.count = pl.k.face_count + c.B;
     s.nf = (int)std::min<long>((long)c.comp->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
   }
+  if (pl.smo) s.xyz = pl.sm.xyz_out;  // the smoothed rows of the same list
   return launch_render_mesh(s, m->points->skeys.p, pl.queue, pl.st);
 }
 
@@ -1180,6 +1249,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (pl.thin) MD_TRY(timed("points_voxel", run_thin));
   if (pl.deci) MD_TRY(timed("points_decimate", run_decimate));
   if (pl.comp) MD_TRY(timed("points_components", run_components));
+  if (pl.smo) MD_TRY(timed("points_smooth", run_smooth));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
@@ -1230,6 +1300,19 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
       MD_FAIL(MD_ERR_INVALID_ARG, "components together with voxel thinning or outlier removal: the rows the faces name no longer exist");
     if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
       MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
+  }
+  MD_TRY(check_smooth_part(c.smooth));
+  if (smooth_on(c.smooth)) {
+    if (!c.mesh) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing needs a mesh request");
+    if (!out->count || !out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing needs the list outputs `xyz` and `count`");
+    if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing together with decimation: md_op_smooth_mesh serves the decimated mesh");
+    if (voxel_on(c.vox) || outlier_on(c.outl))
+      MD_FAIL(MD_ERR_INVALID_ARG, "smoothing together with voxel thinning or outlier removal: the rows the faces name no longer exist");
+    if (components_on(c.comp) && (!c.comp->faces || !c.comp->face_count))
+      MD_FAIL(MD_ERR_INVALID_ARG, "smoothing behind the components needs their outputs `faces` and `face_count`");
+    if (c.rst && !c.smooth->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising the smoothed mesh needs the smoothing output `xyz`");
+    if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
   }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));
@@ -1303,6 +1386,11 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (components_on(c.comp)) {  // min_faces == 0: the key, and the graph, of the call without the stage
     const md_points_components& k = *c.comp;
     key_add(key, 0x434f4d50u, k.min_faces, k.label, k.component_faces, k.faces, k.face_index, k.face_count, k.face_capacity, k.stats);
+    key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
+  }
+  if (smooth_on(c.smooth)) {  // iterations == 0: the key, and the graph, of the call without the stage
+    const md_points_smooth& q = *c.smooth;
+    key_add(key, 0x534d5448u, q.step, q.lambda, q.mu, q.iterations, q.pin_boundary, q.xyz, q.normals, q.stats);
     key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
   }
   if (mesh_on(c.mesh))  // every output null: the key, and the graph, of the call without a mesh

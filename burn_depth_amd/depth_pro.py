@@ -100,6 +100,17 @@ class RasterisedMesh:
 
 
 @dataclass
+class SmoothedMesh:
+    """What `md_op_smooth_mesh` / `md_infer_points_smooth` return (include/mi_depth.h). Device tensors: xyz f32 [capacity,3] the
+    smoothed rows (the input bits of a row that did not move), normals f32 [capacity,3] the area-weighted vertex normals of the
+    smoothed faces (None when not asked for), stats int32 [5] the invalid and degenerate faces, the rows not in range, the open
+    rows and the moved rows."""
+    xyz: Optional[torch.Tensor] = None
+    normals: Optional[torch.Tensor] = None
+    stats: Optional[torch.Tensor] = None
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -122,7 +133,8 @@ class PointCloud:
     of the list] the smallest row of every row's component (-1 behind the list's total), component_faces int32 [rows] its valid
     faces, faces / face_count the faces of the components that are large enough, face_index their source faces, component_stats
     int32 [5] the invalid, dropped and clipped faces and the components with a face and kept; with the operator's compact also
-    index and remap. None when not asked for."""
+    index and remap. With `smooth=` (`md_infer_points_smooth`): smooth = the `SmoothedMesh` of the list over the faces the
+    rasteriser reads; the list itself is unchanged. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -147,6 +159,7 @@ class PointCloud:
     label: Optional[torch.Tensor] = None
     component_faces: Optional[torch.Tensor] = None
     component_stats: Optional[torch.Tensor] = None
+    smooth: Optional["SmoothedMesh"] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -306,6 +319,24 @@ def _points_components(dev, B: int, H: int, W: int, stride: int, mesh, component
                                    _ptr(out.faces) or None, _ptr(out.face_index) or None, _ptr(out.face_count), min(frows) if frows else 0,
                                    _ptr(out.component_stats))
     return msh, comp
+
+
+def _points_smooth(dev, smooth: dict, out: PointCloud, fresh: bool):
+    """md_points_smooth for `out` with the smoothing on. smooth: dict(step=, iterations=, lam=, mu=, pin_boundary=, normals=). With
+    `fresh` the tensors of `out.smooth` are created, rows parallel to the list; otherwise the ones `out` carries are written again."""
+    unknown = set(smooth) - {"step", "iterations", "lam", "mu", "pin_boundary", "normals"}
+    if unknown or "step" not in smooth or "lam" not in smooth:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"smooth= takes step, iterations, lam, mu, pin_boundary, normals; unknown {sorted(unknown)}")
+    if out.xyz is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "smooth= needs the compacted list")
+    if fresh or out.smooth is None:
+        cap = int(out.xyz.shape[0])
+        out.smooth = SmoothedMesh(xyz=torch.empty((cap, 3), dtype=torch.float32, device=dev),
+                                  normals=torch.empty((cap, 3), dtype=torch.float32, device=dev) if smooth.get("normals") else None,
+                                  stats=torch.empty(5, dtype=torch.int32, device=dev))
+    s = out.smooth
+    return _lib.MdPointsSmooth(float(smooth["step"]), float(smooth["lam"]), float(smooth.get("mu", 0.0)), int(smooth["iterations"]),
+                               1 if smooth.get("pin_boundary", True) else 0, _ptr(s.xyz), _ptr(s.normals), _ptr(s.stats))
 
 
 def _render_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
@@ -794,14 +825,14 @@ class DepthPro:
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
                      raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
-                     components: Optional[dict] = None, **opts) -> PointCloud:
+                     components: Optional[dict] = None, smooth: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
         world (`md_points_opts`). `out`: a PointCloud of an earlier call to write into again (what a captured graph replays).
-        Every form runs through the widest entry, `md_infer_points_components`, with NULL for the parts not asked for, which is
-        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` / `_raster` / `_outlier` / `_decimate` on the
-        same arguments:
+        Every form runs through the widest entry, `md_infer_points_smooth`, with NULL for the parts not asked for, which is
+        `md_infer_points` / `_filtered` / `_normals` / `_voxel` / `_render` / `_mesh` / `_raster` / `_outlier` / `_decimate` /
+        `_components` on the same arguments:
         conf_percentile / view_rtol / min_views (`md_view_filter_opts`): when one of them is set the view filter drops the lowest
         conf_percentile % of the confidences of the call and the pixels fewer than min_views other views confirm within view_rtol
         before the unprojection; `depth` is then the filtered depth.
@@ -831,7 +862,12 @@ class DepthPro:
         is unchanged; `faces` / `face_count` are the faces of the components with at least min_faces faces, `face_index` their
         source faces in the unfiltered mesh, `label` / `component_faces` the component of every row of the list and
         `component_stats` the counters. raster= sees the filtered faces. min_faces 0 or None: the call without it. Not with
-        decimate=, voxel > 0 or outlier=."""
+        decimate=, voxel > 0 or outlier=.
+        smooth (`md_points_smooth`): dict(step=, iterations=, lam=, mu=0.0, pin_boundary=True, normals=False) beside mesh=: Taubin
+        (lam | mu) or Laplacian smoothing of the list over the faces the rasteriser reads (those of components= when given), on
+        the integer lattice of side step. The list, `normals` and render= are unchanged; the smoothed rows, the vertex normals of
+        the smoothed faces and the counters come back as `smooth` (`SmoothedMesh`), and raster= draws the smoothed rows.
+        iterations 0 or None: the call without it. Not with decimate=, voxel > 0 or outlier= (`ops.smooth_mesh` serves those)."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -860,12 +896,19 @@ class DepthPro:
                 vox = None
         elif decimate is not None:
             dec = _lib.MdPointsDecimate(0.0, None, None, None, None, None, None, None, 0, None)
+        smo = None
+        if smooth and smooth.get("iterations"):
+            if not mesh:
+                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "smooth= needs mesh=")
+            smo = _points_smooth(dev, smooth, res, out is None)
+        elif smooth is not None:
+            smo = _lib.MdPointsSmooth(0.0, 0.0, 0.0, 0, 0, None, None, None)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        _lib.check(self._lib.md_infer_points_components(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                        C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                        C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
-                                                        ref(outl), ref(dec), ref(comp), _lib.MD_MEM_DEVICE,
-                                                        _stream_ptr(self.device.ordinal)))
+        _lib.check(self._lib.md_infer_points_smooth(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
+                                                    C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
+                                                    ref(outl), ref(dec), ref(comp), ref(smo), _lib.MD_MEM_DEVICE,
+                                                    _stream_ptr(self.device.ordinal)))
         del keep
         return res
 

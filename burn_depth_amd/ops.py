@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import (Device, PointCloud, RasterisedMesh, RenderedPoints, _points_cameras, _points_request, _raster_request, _render_request,
+from .depth_pro import (Device, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _points_cameras, _points_request, _raster_request, _render_request,
                         _stream_ptr, _view_filter_opts)
 
 
@@ -692,6 +692,32 @@ def mesh_components(dev: Device, faces: torch.Tensor, n_rows: int, min_faces: in
                                    ptr(out.component_stats))
     _lib.check(_lib.load().md_op_mesh_components(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, _p(faces), F, C.byref(comp),
                                                  C.byref(outs), _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def smooth_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, step: float, iterations: int, lam: float, mu: float = 0.0,
+                pin_boundary: bool = True, normals: bool = False, capacity: Optional[int] = None,
+                out: Optional[SmoothedMesh] = None) -> SmoothedMesh:
+    """md_op_smooth_mesh: xyz f32 [N,3] and faces int32 [F,3] over its rows -> `SmoothedMesh`: Taubin (lam | mu) or, with mu == 0,
+    Laplacian smoothing on the integer lattice of side `step`, 2 * iterations (iterations) Jacobi steps, rows with an open fan
+    pinned with pin_boundary; xyz f32 [capacity,3], with normals=True the area-weighted vertex normals f32 [capacity,3] of the
+    smoothed faces, stats int32 [5] (invalid and degenerate faces, rows not in range, open rows, moved rows). capacity defaults to
+    N: rows behind it are not written. `out`: a SmoothedMesh of an earlier call to write into again. Bit-identical to
+    `pipeline.smooth_mesh`."""
+    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
+    xyz, faces = _f32c(xyz), faces.contiguous()
+    N, F = int(xyz.shape[0]), int(faces.shape[0])
+    if out is None:
+        cap = N if capacity is None else int(capacity)
+        out = SmoothedMesh(xyz=torch.empty((max(cap, 0), 3), dtype=torch.float32, device=xyz.device),
+                           normals=torch.empty((max(cap, 0), 3), dtype=torch.float32, device=xyz.device) if normals else None,
+                           stats=torch.empty(5, dtype=torch.int32, device=xyz.device))
+    else:
+        cap = min(int(t.shape[0]) for t in (out.xyz, out.normals) if t is not None) if capacity is None else int(capacity)
+    smooth = _lib.MdPointsSmooth(float(step), float(lam), float(mu), int(iterations), 1 if pin_boundary else 0, _p(out.xyz), _p(out.normals),
+                                 _p(out.stats))
+    _lib.check(_lib.load().md_op_smooth_mesh(dev.handle, _p(xyz), N, _p(faces), F, C.byref(smooth), cap, _stream_ptr(dev.ordinal)))
     return out
 
 

@@ -24,6 +24,8 @@
   re-indexed to them, collapsed faces and later copies of an oriented triangle dropped
 * `mesh_components`                           -- the host reference of `md_op_mesh_components` / `md_infer_points_components`: the
   connected components of the faces (the smallest row of each as its label) and the faces of those with enough faces
+* `smooth_mesh`                               -- the host reference of `md_op_smooth_mesh` / `md_infer_points_smooth`: Taubin /
+  Laplacian smoothing on an integer lattice with int64 sums, and the area-weighted vertex normals of the smoothed faces
 * `radius_outliers`                           -- the host reference of `md_op_radius_outliers` / `md_infer_points_outlier`: the rows
   with enough neighbours in the 27 cells around their own, bit-identical to the device's
 * `write_gray_png`                            -- the reference uses `image::GrayImage::save`; a stdlib-zlib PNG writer
@@ -720,6 +722,92 @@ def mesh_components(faces, n_rows, min_faces=1, face_counts=None, compact=False,
 
 
 @dataclass
+class HostSmoothed:
+    xyz: np.ndarray                      # f32 [min(N, capacity),3]: the smoothed rows; the input bits of a row that did not move
+    normals: Optional[np.ndarray]        # f32 [min(N, capacity),3]: the area-weighted normals of the smoothed faces; None when not asked for
+    stats: np.ndarray                    # int32 [5]: invalid faces, degenerate faces, rows not in range, open rows, moved rows
+
+
+def _smooth_mix64(x: np.ndarray) -> np.ndarray:
+    """splitmix64's finaliser on a uint64 array, modulo 2^64 (kernels/smooth_math.h: smooth_mix64)."""
+    x = x.astype(np.uint64)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+    return x ^ (x >> np.uint64(31))
+
+
+def smooth_mesh(xyz, faces, step, iterations, lam, mu=0.0, pin_boundary=True, normals=False, capacity=None) -> HostSmoothed:
+    """The host reference of md_op_smooth_mesh / md_infer_points_smooth (include/mi_depth.h states the contract): Taubin (lam | mu)
+    or, with mu == 0, Laplacian smoothing of the rows xyz f32 [N,3] over the faces int32 [F,3] with the face-weighted umbrella
+    operator, on an integer lattice of side `step`: k = rint(p / step) in f32; a face with a corner outside 0..N-1 or on a row
+    that is not in range (non-finite, or |k| > 2^22) is invalid, a valid face with two equal corners degenerate, the others are
+    live; deg[v] += 2 and open[v] += mix(next) - mix(prev) per corner of a live face; a row is pinned with deg == 0, out of range,
+    or pin_boundary and open != 0; every step adds k[next] + k[prev] to S[v] in int64 and moves an unpinned row by
+    rint(factor * (S / deg - k)) in f64, clamped to +-2^62. A row that ends where it began returns its input bits, any other
+    k * step in f64 rounded to f32. normals: the int64 cross products of the final lattice positions summed per corner and
+    normalised in f64. capacity: the rows the outputs hold (default N); every row takes part all the same. Integer sums only, in
+    any order: the device kernels (kernels/smooth.hip) give the same bits."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    N, F, iterations = len(p), len(fc), int(iterations)
+    step, lam, mu = np.float32(step), np.float32(lam), np.float32(mu)
+    if N >= 1 << 30 or F >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows and faces")
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("step is finite and > 0")
+    if not (0 < lam <= 1) or not (-1 <= mu <= 0):
+        raise ValueError("0 < lam <= 1 and -1 <= mu <= 0")
+    if not 1 <= iterations <= 1024:
+        raise ValueError("1 <= iterations <= 1024")
+    cap = N if capacity is None else int(capacity)
+    if cap < 0:
+        raise ValueError("capacity is negative")
+    with np.errstate(all="ignore"):
+        kf = np.rint(p / step)  # f32
+        in_range = np.isfinite(p).all(1) & (np.abs(kf) <= np.float32(4194304.0)).all(1)
+        k0 = np.where(in_range[:, None], kf, np.float32(0)).astype(np.int64)
+    inside = ((fc >= 0) & (fc < N)).all(1)
+    valid = inside.copy()
+    valid[inside] = in_range[fc[inside]].all(1)
+    degenerate = valid & ((fc[:, 0] == fc[:, 1]) | (fc[:, 1] == fc[:, 2]) | (fc[:, 0] == fc[:, 2]))
+    lf = fc[valid & ~degenerate].astype(np.int64)
+    v, nxt, prv = lf.ravel(), lf[:, [1, 2, 0]].ravel(), lf[:, [2, 0, 1]].ravel()
+    deg = np.zeros(N, np.int64)
+    np.add.at(deg, v, 2)
+    opened = np.zeros(N, np.uint64)
+    np.add.at(opened, v, _smooth_mix64(nxt) - _smooth_mix64(prv))
+    free = ~((deg == 0) | ~in_range | (bool(pin_boundary) & (opened != 0)))
+    degf = deg[free].astype(np.float64)[:, None]
+    k = k0.copy()
+    for t in range(2 * iterations if mu != 0 else iterations):
+        factor = np.float64(mu if (mu != 0 and t & 1) else lam)
+        S = np.zeros((N, 3), np.int64)
+        np.add.at(S, v, k[nxt] + k[prv])
+        d = S[free].astype(np.float64) / degf - k[free].astype(np.float64)
+        r = np.clip(np.rint(factor * d), -2.0 ** 62, 2.0 ** 62)
+        k[free] = k[free] + r.astype(np.int64)
+    moved = (k != k0).any(1)
+    out = p.copy()
+    out[moved] = (k[moved].astype(np.float64) * np.float64(step)).astype(np.float32)
+    nrm = None
+    if normals:
+        ka, kb, kc = k[lf[:, 0]], k[lf[:, 1]], k[lf[:, 2]]
+        u, w = kb - ka, kc - ka
+        cross = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], 1)
+        acc = np.zeros((N, 3), np.int64)
+        for j in range(3):
+            np.add.at(acc, lf[:, j], cross)
+        nz = (deg > 0) & (acc != 0).any(1)
+        x = acc[nz].astype(np.float64)
+        length = np.sqrt((x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1]) + x[:, 2] * x[:, 2])
+        nrm = np.zeros((N, 3), np.float32)
+        nrm[nz] = (x / length[:, None]).astype(np.float32)
+        nrm = nrm[:cap]
+    stats = np.array([F - valid.sum(), degenerate.sum(), (~in_range).sum(), ((deg > 0) & (opened != 0)).sum(), moved.sum()], np.int32)
+    return HostSmoothed(out[:cap], nrm, stats)
+
+
+@dataclass
 class HostOutliers:
     xyz: np.ndarray                  # f32 [M,3]: the surviving input rows, in ascending input index
     conf: Optional[np.ndarray]       # f32 [M]
@@ -1192,8 +1280,8 @@ class AnyDepthModel:
         Keywords as `DepthPro.infer_points` / `DepthAnything3.infer_points`, conf_percentile= / view_rtol= / min_views= (the view
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
         render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`), outlier=
-        (`md_infer_points_outlier`), decimate= (`md_infer_points_decimate`) and components= (`md_infer_points_components`)
-        included."""
+        (`md_infer_points_outlier`), decimate= (`md_infer_points_decimate`), components= (`md_infer_points_components`) and
+        smooth= (`md_infer_points_smooth`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

@@ -896,7 +896,72 @@ int md_infer_points_components(md_model_t m, const float* nchw, int B, int H, in
  * bits at every capacity; for the test of that branch. MD_ERR_INVALID_ARG (< 0) for a negative capacity. */
 int md_debug_raster_queue(int capacity);
 
-/* ---- Depth-Anything-v3 ---------------------------------------------------------------------------------
+/* ---- point path: Taubin smoothing of a mesh and its vertex normals -----------------------------------------------------------
+ * N vertex rows xyz [N,3] and faces int32 [F,3] over them -> the smoothed rows and the area-weighted normals of the smoothed
+ * faces. This stage averages, and still nothing depends on the order in which threads arrive: the rows are rounded to an integer
+ * lattice once and every sum is an integer sum modulo 2^64 (pipeline.smooth_mesh restates it in numpy bit for bit).
+ *   lattice: step is an f32, finite and > 0. Per axis k = rintf(p / step): one f32 division, round half to even. A row is IN
+ *     RANGE when its coordinates are finite and |k| <= 2^22 on every axis, compared in float.
+ *   faces: a face is INVALID when a corner is < 0 or >= N or names a row that is not in range. A valid face is DEGENERATE when
+ *     two of its corners are equal. Both kinds contribute nothing and are counted. The other faces are LIVE.
+ *   topology, once, from the faces alone: for a live face (a,b,c) and each corner v with successor n and predecessor p in the
+ *     winding, deg[v] += 2 and open[v] += mix(n) - mix(p) in uint64 modulo 2^64, mix = splitmix64's finaliser (x ^= x >> 30;
+ *     x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31). Around a closed, consistently oriented fan
+ *     every neighbour is once a successor and once a predecessor and open == 0; an open fan leaves mix(last) - mix(first). The
+ *     contract is this formula, not "boundary": a collision is part of it and is bit-identical too.
+ *   pinned rows: deg == 0, or the row is not in range, or pin_boundary != 0 and open != 0.
+ *   steps: Jacobi updates, every row reads the positions of the step before. mu != 0: 2 * iterations steps with the factor
+ *     lambda on the even and mu on the odd ones (Taubin); mu == 0: iterations steps with lambda (Laplacian). In a step a live
+ *     face adds k[n] + k[p] per axis to S[v] (int64) for each of its corners, and a row that is not pinned then does per axis
+ *     d = (double)S / (double)deg - (double)k;  r = rint((double)factor * d), clamped to [-2^62, 2^62];  k += (int64)r
+ *     in f64 with one rounded operation each, rint half to even, no fused multiply-add. Integer arithmetic wraps modulo 2^64.
+ *   positions: a row whose final lattice position equals its first one on all axes returns its INPUT BITS (every pinned row
+ *     does); any other row returns (float)((double)k * (double)step) per axis.
+ *   normals: every live face adds the int64 cross product (k_b - k_a) x (k_c - k_a) of the final lattice positions to Nrm of
+ *     its three corners. A row with deg == 0 or Nrm == 0 gets (0,0,0); any other, per axis, (float)((double)Nrm_a / l) with
+ *     l = sqrt((x*x + y*y) + z*z) in f64. The sign follows the winding.
+ *   stats int32 [5]: invalid faces; degenerate faces; rows not in range; rows with deg > 0 and open != 0 (pinned or not); rows
+ *     that moved.
+ *   limits: 0 < lambda <= 1, -1 <= mu <= 0, 1 <= iterations <= 1024, N < 2^30 and F < 2^30.
+ * Integer global atomics and vector stores only; the lattice, the accumulators and the counters are set on the stream inside
+ * every call. */
+typedef struct md_points_smooth {
+  float step;           /* the lattice side, finite and > 0 */
+  float lambda;         /* the factor of the even steps, in (0, 1] */
+  float mu;             /* the factor of the odd steps, in [-1, 0]; 0 = Laplacian smoothing, no odd steps */
+  int32_t iterations;   /* 1..1024; 0 = the stage is off (md_infer_points_smooth) */
+  int32_t pin_boundary; /* != 0: rows with open != 0 do not move */
+  float* xyz;           /* float [capacity,3]: the smoothed rows. NULL = skip */
+  float* normals;       /* float [capacity,3]: the vertex normals of the smoothed mesh. NULL = skip */
+  int32_t* stats;       /* int32 [5]: invalid and degenerate faces, rows not in range, open rows, moved rows. NULL = skip */
+} md_points_smooth;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_mesh_components: all N rows take part, rows >= capacity are
+ * not written and the memory behind them stays untouched. Everything is enqueued on `stream`; the call returns after the stream
+ * has drained, because its scratch is freed on return. Errors, before any launch: dev / smooth NULL, step not finite or <= 0,
+ * lambda, mu or iterations outside their limits (NaN included), N < 0, F < 0, capacity < 0, xyz_dev NULL with N > 0, faces_dev
+ * NULL with F > 0 -> MD_ERR_INVALID_ARG; N >= 2^30 or F >= 2^30 -> MD_ERR_SHAPE. */
+int md_op_smooth_mesh(md_device_t dev, const float* xyz_dev, int64_t N, const int32_t* faces_dev, int64_t F, const md_points_smooth* smooth,
+                      int64_t capacity, void* stream);
+/* md_infer_points_components with the smoothing behind the mesh stage and the island removal and in front of the rasteriser
+ * (launch-order name "points_smooth"). The stage works on the call's list, N = min(count, capacity) read on the device, and on
+ * the faces the rasteriser would read: comp's kept faces when that stage is on (smoothing then needs comp->faces and
+ * comp->face_count), the mesh stage's otherwise (written, complete, to a grow-only home of the model; mesh->faces, if taken, are
+ * a copy). It writes smooth->xyz, normals [out->capacity,3] (rows >= N are not written) and stats, of out_kind. The caller's
+ * list, nrm's per-pixel normals and the point render are unchanged; the rasteriser reads the smoothed positions when the stage
+ * is on. smooth NULL or iterations == 0 (its pointers then NULL): md_infer_points_components on the same arguments, the same
+ * launches, bits and launch-order names. The graph key contains smooth's fields. Errors as md_infer_points_components', plus,
+ * before any launch: a limit of the contract broken, a pointer set with iterations == 0, the stage without a mesh request or
+ * without the list's count, or together with dec on, voxel thinning or outlier removal (md_op_smooth_mesh serves those routes)
+ * -> MD_ERR_INVALID_ARG; 2 R >= 2^30 -> MD_ERR_SHAPE. After the first call of a shape nothing is allocated. */
+int md_infer_points_smooth(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                           const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                           const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                           const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                           const md_points_components* comp, const md_points_smooth* smooth, int out_kind, void* stream);
+
+/* ---- Depth-Anything-v3---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).
  * "small" = `DepthAnything3Config::small()` (mod.rs:158-171): ViT-S/14 with QK-norm / 2-D RoPE / camera token /

@@ -50,6 +50,13 @@ is written `ops.mesh_components(compact=True)` drops the vertices that only they
 `--raster-pose` / `--render-pose` stay those of the model call, over its uncompacted list. With `--views`
 the operator runs behind the per-view meshes, and behind `ops.decimate_mesh` when `--decimate` is given.
 
+`--smooth ITER [--smooth-step S] [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]` (with `--ply --mesh`): Taubin smoothing
+of the mesh on the device, ITER lambda | mu step pairs (`--smooth-mu 0`: ITER Laplacian steps) on an integer lattice of side S, the open
+boundary pinned unless freed. The file holds the smoothed positions and, with `--normals`, the vertex normals of the smoothed faces. One
+image: the stage runs inside the model call (`md_infer_points_smooth`, so `--raster-pose` draws the smoothed mesh); with `--views`, or
+behind `--decimate` / `--min-component-faces`, `ops.smooth_mesh` runs on the final vertices and faces. S defaults to the largest finite
+|coordinate| of the list / 2^21, computed on the host (one image: from a first call without the stage).
+
 `--raster-pose E.npy --raster-out view.png` (with `--ply --mesh`): the mesh is also rasterised on the device into a virtual camera with
 the world-to-camera pose E ([3,4], or [T,3,4] of which every pose is drawn and the first written), a render without holes, and its
 depth image written as a normalised PNG (`md_infer_points_raster`; with `--views`, `ops.render_mesh` on the meshes of all views).
@@ -98,6 +105,21 @@ def raster_request(a, h, w, K=None, focal=None):
     if req:
         del req["radius"]
     return req, why
+
+
+def smooth_step(a, xyz) -> float:
+    """--smooth-step, or the default lattice side: the largest finite |coordinate| of the list over 2^21"""
+    if a.smooth_step > 0:
+        return a.smooth_step
+    import torch
+    v = xyz.abs()
+    v = v[torch.isfinite(v)]
+    top = float(v.max().item()) if v.numel() else 0.0
+    return float(np.float32(top / 2097152.0)) if top > 0 else 1.0
+
+
+def smooth_request(a, step: float) -> dict:
+    return dict(step=step, iterations=a.smooth, lam=a.smooth_lambda, mu=a.smooth_mu, pin_boundary=not a.smooth_free_boundary, normals=a.normals)
 
 
 def run_views(a) -> int:
@@ -179,6 +201,13 @@ def run_views(a) -> int:
             faces = pc.faces[:int(pc.face_count[-1])].cpu().numpy()
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.smooth > 0:  # the final vertices move; the faces, the colours and the row order stay
+            try:
+                sm = ops.smooth_mesh(dev, xyz, pc.faces[:len(faces)], **smooth_request(a, smooth_step(a, xyz)))
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            xyz, nrm = sm.xyz, sm.normals
         if a.voxel > 0:  # one point per occupied voxel over all views: the most confident one
             try:
                 pc = ops.voxel_thin(dev, xyz, a.voxel, conf=conf, rgb=col, normals=nrm)
@@ -255,6 +284,12 @@ def main(argv=None) -> int:
     ap.add_argument("--min-component-faces", type=int, default=0,
                     help="--ply --mesh: drop the connected components of the mesh with fewer faces than this, and the vertices only they "
                          "named (md_infer_points_components, ops.mesh_components; 0 = off)")
+    ap.add_argument("--smooth", type=int, default=0,
+                    help="--ply --mesh: Taubin smoothing of the mesh, this many lambda | mu step pairs (md_infer_points_smooth, ops.smooth_mesh; 0 = off)")
+    ap.add_argument("--smooth-step", type=float, default=0.0, help="--smooth: the lattice side (0 = the largest finite |coordinate| of the list / 2^21)")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5, help="--smooth: the factor of the shrinking steps, in (0, 1]")
+    ap.add_argument("--smooth-mu", type=float, default=-0.53, help="--smooth: the factor of the inflating steps, in [-1, 0]; 0 = Laplacian smoothing")
+    ap.add_argument("--smooth-free-boundary", action="store_true", help="--smooth: let the open boundary of the mesh move too")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
     ap.add_argument("--raster-out", default="", help="--raster-pose: the rasterised depth of the first pose as a normalised PNG")
     a = ap.parse_args(argv)
@@ -269,6 +304,9 @@ def main(argv=None) -> int:
         return 2
     if a.min_component_faces != 0 and (a.min_component_faces < 0 or not (a.ply and a.mesh)):
         print("--min-component-faces is a positive face count and goes with --ply --mesh", file=sys.stderr)
+        return 2
+    if a.smooth != 0 and (not 1 <= a.smooth <= 1024 or not (a.ply and a.mesh)):
+        print("--smooth is a step count in 1..1024 and goes with --ply --mesh", file=sys.stderr)
         return 2
     if a.outlier_radius != 0 and (not a.ply or a.mesh):
         print("--outlier-radius goes with --ply, and not with --mesh (the faces name rows of the unfiltered list)", file=sys.stderr)
@@ -324,23 +362,34 @@ def main(argv=None) -> int:
             if why:
                 print(why, file=sys.stderr)
                 return 2
+        in_call = bool(a.smooth) and not a.decimate and not a.min_component_faces  # the stage of the model call; else the operator below
         try:
-            pc = model.infer_points(x, **({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
-                                    dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
-                                    world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals,
-                                    normal_min_cos=a.normal_min_cos, voxel=a.voxel, render=render,
+            call = dict(**({"f_px": a.focal_px} if a.focal_px is not None else {}), rgb=torch.from_numpy(prep.rgb[None]),
+                        dense=False, conf_min=a.conf_min, conf_percentile=a.conf_percentile, edge_rtol=a.edge_rtol, stride=a.stride,
+                        world=bool(getattr(model.model.config, "dual_head", False)), normals=a.normals, normal_min_cos=a.normal_min_cos)
+            smooth = None
+            if in_call:  # without --smooth-step a first call gives the list, whose extent sets the lattice
+                smooth = smooth_request(a, a.smooth_step if a.smooth_step > 0 else smooth_step(a, model.infer_points(x, **call).points()[0]))
+            pc = model.infer_points(x, **call, voxel=a.voxel, render=render,
                                     mesh=dict(max_rtol=a.mesh_rtol, pixel_index=False) if a.mesh else None, raster=raster,
                                     outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None,
                                     decimate=dict(voxel=a.decimate) if a.decimate else None,
-                                    components=dict(min_faces=a.min_component_faces) if a.min_component_faces and not a.decimate else None)
+                                    components=dict(min_faces=a.min_component_faces) if a.min_component_faces and not a.decimate else None,
+                                    smooth=smooth)
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+            if in_call:
+                xyz = pc.smooth.xyz[:xyz.shape[0]]
+                nrm = pc.smooth.normals[:xyz.shape[0]] if a.normals else None
             flt = pc  # what the file holds; `pc` stays the model call's result, whose images are written below
             if a.min_component_faces:  # the file holds no floater vertex: the list is compacted to the rows the kept faces name
                 flt = ops.mesh_components(Device(0), pc.faces[:int(pc.face_count[-1])], int(xyz.shape[0]), a.min_component_faces, xyz=xyz,
                                           rgb=col, normals=nrm, compact=True)
                 xyz, col, _ = flt.points()
                 nrm = flt.normals[:xyz.shape[0]] if a.normals else None
+            if a.smooth and not in_call:  # behind the decimation / the compaction: the operator on the vertices and faces of the file
+                sm = ops.smooth_mesh(Device(0), xyz, flt.faces[:int(flt.face_count[-1])], **smooth_request(a, smooth_step(a, xyz)))
+                xyz, nrm = sm.xyz, sm.normals
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
