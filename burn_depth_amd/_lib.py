@@ -167,6 +167,16 @@ class MdVitGemm(C.Structure):
                 ("vT", C.c_void_p), ("out", C.c_void_p)]
 
 
+class MdAttentionOp(C.Structure):
+    """md_attention_op (include/mi_depth.h)."""
+    _fields_ = [("T", C.c_int), ("V", C.c_int), ("N", C.c_int), ("heads", C.c_int), ("precision", C.c_int), ("seq_stride", C.c_int),
+                ("kpad", C.c_int), ("out_fp8_inv", C.c_float), ("small", C.c_int), ("poison_pad", C.c_int), ("qkv", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
+ATTN_FORMS = {-1: "none", 0: "plain", 1: "key-split", 2: "assembly", 3: "views", 4: "fp8-out", 5: "fp32-path"}  # md_attention_form
+
+
 class MdDecoderGemmHeadCh(C.Structure):
     """md_decoder_gemm_head_ch (include/mi_depth.h)."""
     _fields_ = [("w", C.c_void_p), ("b", C.c_float), ("act", C.c_int), ("out", C.c_void_p), ("bstride", C.c_int64)]
@@ -340,6 +350,8 @@ SYMBOLS = {
     "md_op_linear_tile": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_attention": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "md_op_attention_views": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "md_op_attention_ex": (_I, [_P, C.POINTER(MdAttentionOp), _P]),
+    "md_debug_attention_last_form": (_I, [C.POINTER(_I * 4)]),
     "md_op_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_deconv2x2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_conv2d_direct": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),

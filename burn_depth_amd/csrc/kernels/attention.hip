@@ -670,6 +670,15 @@ int attention_allow_small(int on) {
   return prev;
 }
 
+static thread_local AttnForm g_attn_last_form;
+void attention_note_form(int form, long grid, int qw, int ks) {
+  g_attn_last_form.form = form;
+  g_attn_last_form.grid = (int)(grid < 0x7fffffffL ? grid : 0x7fffffffL);
+  g_attn_last_form.qw = qw;
+  g_attn_last_form.ks = ks;
+}
+AttnForm attention_last_form() { return g_attn_last_form; }
+
 // ---- the assembly-owned Depth Pro form (kernels/attn577_gfx950.s, generated by tools/attn_asm/gen_attn577.py) ----
 // bf16, exactly 577 tokens (576 patches + the class token), head_dim 64: one workgroup of four waves per (sequence, head), one wave
 // per SIMD with the whole register file. Its code object is embedded in this library (attn577_blob.S) and loaded per device by
@@ -762,6 +771,7 @@ static int launch_attention_asm(const void* qk, const void* vT, void* out, int n
   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   MD_HIP(hipModuleLaunchKernel(g_asm[ordinal].fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, s, nullptr, extra));
   g_attn_asm_launches.fetch_add(1, std::memory_order_relaxed);
+  attention_note_form(ATTN_FORM_ASM, grid, 4, 1);
   // the units it flagged (a row sum outside [2^-64, 2^100)) run again in the running-maximum body: compacted, then four workgroups per CU
   const int qblocks = (n_tokens + 127) / 128;
   hipLaunchKernelGGL(attention_redo_scan_kernel, dim3(1), dim3(1024), 0, s, redo, nunits, redo_cap, g_asm[ordinal].stats);
@@ -842,6 +852,8 @@ int launch_attention(const void* qk, const void* vT, void* out, int nseq, int S,
                        n_tokens, heads, D, kpad, qblocks, out_fp8_inv, 0L);
   }
   MD_HIP(hipGetLastError());
+  if (small) attention_note_form(ATTN_FORM_KEYSPLIT, grid_s.x, 2, 2);
+  else attention_note_form(out_fp8_inv > 0.f ? ATTN_FORM_FP8OUT : ATTN_FORM_PLAIN, grid.x, 4, 1);
   return MD_OK;
 }
 
@@ -889,6 +901,7 @@ int launch_attention_views(const void* qk, const void* vT, void* out, int nseq, 
                        kpad, qblocks, 0L, views);
   }
   MD_HIP(hipGetLastError());
+  attention_note_form(ATTN_FORM_VIEWS, grid.x, 4, 1);
   return MD_OK;
 }
 

@@ -533,5 +533,14 @@ struct AttnSmallScope {
  private:
   int prev_;
 };
+// Host-only, per host thread: the form the thread's last attention launch took (md_debug_attention_last_form). launch_attention,
+// launch_attention_views and the fp32 three-launch path note it with one thread-local store; no kernel reads it.
+enum { ATTN_FORM_NONE = -1, ATTN_FORM_PLAIN = 0, ATTN_FORM_KEYSPLIT = 1, ATTN_FORM_ASM = 2, ATTN_FORM_VIEWS = 3, ATTN_FORM_FP8OUT = 4, ATTN_FORM_F32 = 5 };
+struct AttnForm {
+  int form = ATTN_FORM_NONE;
+  int grid = 0, qw = 0, ks = 0;  // workgroups of the main launch, query waves and key groups per workgroup (fp32 path: units, 0, 0)
+};
+void attention_note_form(int form, long grid, int qw, int ks);
+AttnForm attention_last_form();
 
 }  // namespace md

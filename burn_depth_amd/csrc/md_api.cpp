@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "md_engine.h"
@@ -850,20 +851,32 @@ int md_op_linear_tile(md_device_t dev, const float* x_dev, const float* w_dev, c
   return MD_OK;
 }
 
-// md_op_attention (V = 1) and md_op_attention_views: one staging, one launcher
-static int op_attention(md_device_t dev, const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev, void* stream) {
-  if (!dev || !qkv_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+// md_op_attention (V = 1), md_op_attention_views and md_op_attention_ex: one staging, one launcher
+static int op_attention(md_device_t dev, const md_attention_op& d, void* stream) {
+  const float* qkv_dev = d.qkv;
+  const int T = d.T, V = d.V, N = d.N, heads = d.heads;
+  if (!dev || !qkv_dev || !d.out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (T <= 0 || N <= 0 || heads <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid shape");
   if (V < 1 || T % V != 0) MD_FAIL(MD_ERR_SHAPE, "%d sequences in groups of %d views", T, V);
-  // MD_OP_POISON_PAD: whatever the staging does not write (rows N .. S of every sequence, the slack rows, columns N .. kpad of V^T)
-  // holds a large finite value (0x7000: 8192 as a half, 1.6e29 as bf16) instead of zero
-  const bool poison = (precision & MD_OP_POISON_PAD) != 0;
-  precision &= ~MD_OP_POISON_PAD;
+  // MD_OP_POISON_PAD / poison_pad: whatever the staging does not write (rows N .. S of every sequence, the slack rows, columns N .. kpad
+  // of V^T) holds a large finite value (0x7000: 8192 as a half, 1.6e29 as bf16) instead of zero
+  const bool poison = (d.precision & MD_OP_POISON_PAD) != 0 || d.poison_pad != 0;
+  const int precision = d.precision & ~MD_OP_POISON_PAD;
   if (poison && precision == MD_PREC_F32) MD_FAIL(MD_ERR_UNSUPPORTED, "MD_OP_POISON_PAD fills 16-bit staging tensors");
   if (V > 1 && precision == MD_PREC_F32) MD_FAIL(MD_ERR_UNSUPPORTED, "cross-view attention runs in the bf16, f16 and f16x2 modes");
+  const bool fp8_out = d.out_fp8_inv > 0.f;
+  if (!(d.out_fp8_inv >= 0.f)) MD_FAIL(MD_ERR_INVALID_ARG, "out_fp8_inv must be >= 0");
+  if (fp8_out && precision != MD_PREC_BF16) MD_FAIL(MD_ERR_UNSUPPORTED, "attention: e4m3 output rows are built for bf16 operands");
+  if (fp8_out && V > 1) MD_FAIL(MD_ERR_UNSUPPORTED, "cross-view attention writes plain output rows");
+  if (d.small != -1 && d.small != 0) MD_FAIL(MD_ERR_INVALID_ARG, "small: -1 (the launcher's rule) or 0 (off)");
+  // the strides, validated as the launchers validate them (the buffers below are sized from them before any launcher sees them)
+  const int D = heads * 64, SS = d.seq_stride ? d.seq_stride : (N + 3) / 4 * 4, kpad = d.kpad ? d.kpad : (N + 63) / 64 * 64;
+  if (SS < N) MD_FAIL(MD_ERR_SHAPE, "attention: %d tokens in sequences of %d rows", N, SS);
+  if (kpad % 64 != 0 || kpad < (N + 63) / 64 * 64) MD_FAIL(MD_ERR_INVALID_ARG, "attention: kpad=%d must be a multiple of 64 covering %d keys", kpad, N);
+  // the fp32 path's score GEMM writes S columns into rows of kpad floats
+  if (precision == MD_PREC_F32 && (SS % 4 != 0 || SS > kpad)) MD_FAIL(MD_ERR_INVALID_ARG, "attention (fp32): seq_stride=%d must be a multiple of 4 within kpad=%d", SS, kpad);
   MD_HIP(hipSetDevice(dev->ordinal));
   hipStream_t st = pick_stream(dev, stream);
-  const int D = heads * 64, SS = (N + 3) / 4 * 4, kpad = (N + 63) / 64 * 64;
   const size_t es = esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1);  // split-half: two planes per element
   DevBuf qk, vT, ao, sc;
   MD_TRY(qk.alloc(((size_t)T * SS + 64) * 2 * D * es));
@@ -874,27 +887,55 @@ static int op_attention(md_device_t dev, const float* qkv_dev, int T, int V, int
     MD_HIP(hipMemsetD16Async((hipDeviceptr_t)vT.p, 0x7000, (size_t)T * heads * 64 * kpad * es / 2, st));
   }
   MD_TRY(launch_qkv_split(qkv_dev, T, N, heads, SS, kpad, qk.p, vT.p, attn_qscale(precision), precision, st));
+  attention_note_form(ATTN_FORM_NONE, 0, 0, 0);
   if (precision != MD_PREC_F32) {
     DevBuf redo;  // zeroed flags: 577-token bf16 launches take the assembly kernel, like the model's
     MD_TRY(redo.alloc((size_t)attention_redo_ints(T * heads) * 4));
     if (precision == MD_PREC_BF16) MD_TRY(attention_asm_prepare());
-    MD_TRY(launch_attention_views(qk.p, vT.p, ao.p, T, V, SS, N, heads, D, kpad, precision, st, (long)T * heads * 64 * kpad, (int*)redo.p));
+    const long v_plane = (long)T * heads * 64 * kpad;
+    std::optional<AttnSmallScope> small_off;  // small = -1: the thread's own setting stays
+    if (d.small == 0) small_off.emplace(0);
+    if (fp8_out) MD_TRY(launch_attention(qk.p, vT.p, ao.p, T, SS, N, heads, D, kpad, precision, st, d.out_fp8_inv, v_plane, (int*)redo.p));
+    else MD_TRY(launch_attention_views(qk.p, vT.p, ao.p, T, V, SS, N, heads, D, kpad, precision, st, v_plane, (int*)redo.p));
     MD_HIP(hipStreamSynchronize(st));  // `redo` is released at the end of this scope
   } else {
     MD_TRY(sc.alloc((size_t)T * heads * SS * kpad * 4));
     MD_TRY(attention_f32(nullptr, st, qk.p, vT.p, ao.p, (float*)sc.p, T, SS, N, heads, kpad));
   }
-  MD_TRY(launch_unpad_rows(ao.p, T, N, SS, D, out_dev, precision, st));
+  if (fp8_out)  // e4m3 rows of D bytes: the N valid rows of every sequence, as they are
+    MD_HIP(hipMemcpy2DAsync(d.out, (size_t)N * D, ao.p, (size_t)SS * D, (size_t)N * D, (size_t)T, hipMemcpyDeviceToDevice, st));
+  else
+    MD_TRY(launch_unpad_rows(ao.p, T, N, SS, D, (float*)d.out, precision, st));
   MD_HIP(hipStreamSynchronize(st));
   return MD_OK;
 }
 
+static md_attention_op attention_op_of(const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev) {
+  md_attention_op d;
+  memset(&d, 0, sizeof(d));
+  d.T = T; d.V = V; d.N = N; d.heads = heads; d.precision = precision; d.small = -1;
+  d.qkv = qkv_dev; d.out = out_dev;
+  return d;
+}
+
 int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int heads, int precision, float* out_dev, void* stream) {
-  return op_attention(dev, qkv_dev, T, 1, N, heads, precision, out_dev, stream);
+  return op_attention(dev, attention_op_of(qkv_dev, T, 1, N, heads, precision, out_dev), stream);
 }
 
 int md_op_attention_views(md_device_t dev, const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev, void* stream) {
-  return op_attention(dev, qkv_dev, T, V, N, heads, precision, out_dev, stream);
+  return op_attention(dev, attention_op_of(qkv_dev, T, V, N, heads, precision, out_dev), stream);
+}
+
+int md_op_attention_ex(md_device_t dev, const md_attention_op* desc, void* stream) {
+  if (!desc) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  return op_attention(dev, *desc, stream);
+}
+
+int md_debug_attention_last_form(int out[4]) {
+  if (!out) return MD_ERR_INVALID_ARG;
+  const AttnForm f = attention_last_form();
+  out[0] = f.form; out[1] = f.grid; out[2] = f.qw; out[3] = f.ks;
+  return MD_OK;
 }
 
 int md_op_conv3x3(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B, int Cin, int H, int W,

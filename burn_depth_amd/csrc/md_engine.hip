@@ -984,6 +984,7 @@ int attention_f32(Run* r, hipStream_t st, const void* qk, const void* vT, void* 
   if (r) r->begin("attn_pv_f32");
   MD_TRY(launch_gemm(q, A_DENSE, MD_PREC_F32, TILE_128x128, st));
   if (r) r->end();
+  attention_note_form(ATTN_FORM_F32, (long)nseq * heads, 0, 0);
   return MD_OK;
 }
 

@@ -151,6 +151,26 @@ def attention_views(dev: Device, qkv: torch.Tensor, views: int, heads: int, prec
     return out
 
 
+def attention_ex(dev: Device, qkv: torch.Tensor, heads: int, precision: int = 0, *, views: int = 1, seq_stride: int = 0, kpad: int = 0,
+                 out_fp8_inv: float = 0.0, small: int = -1, poison_pad: bool = False) -> torch.Tensor:
+    """`md_op_attention_ex`: `attention` / `attention_views` with the launch parameters of the descriptor (include/mi_depth.h
+    md_attention_op). out_fp8_inv > 0: the e4m3-output form, returned as the raw bytes, uint8 [T, N, heads*64]."""
+    qkv = _f32c(qkv)
+    T, N, _ = qkv.shape
+    out = torch.empty((T, N, heads * 64), dtype=torch.uint8 if out_fp8_inv > 0 else torch.float32, device=qkv.device)
+    d = _lib.MdAttentionOp(T, int(views), N, heads, precision, int(seq_stride), int(kpad), float(out_fp8_inv), int(small), int(poison_pad),
+                           qkv.data_ptr(), out.data_ptr())
+    _lib.check(_lib.load().md_op_attention_ex(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def attention_last_form() -> dict:
+    """md_debug_attention_last_form: what this thread's last attention launch ran -- form (a name of _lib.ATTN_FORMS), grid, QW, KS."""
+    v = (C.c_int * 4)()
+    _lib.check(_lib.load().md_debug_attention_last_form(C.byref(v)))
+    return {"form": _lib.ATTN_FORMS[v[0]], "grid": v[1], "QW": v[2], "KS": v[3]}
+
+
 def conv3x3(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], pre_relu: bool = False,
             precision: int = 0, storage_out: bool = False) -> torch.Tensor:
     precision |= STORAGE_OUT if storage_out else 0

@@ -1164,6 +1164,28 @@ int md_op_attention(md_device_t dev, const float* qkv_dev, int T, int N, int hea
  * MD_ERR_UNSUPPORTED for V > 1). V = 1 is md_op_attention: the same launch, the same bits. */
 int md_op_attention_views(md_device_t dev, const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev,
                           void* stream);
+/* The same entry with every launch parameter in a descriptor (test-only): md_op_attention and md_op_attention_views are this call with
+ * seq_stride = kpad = 0, out_fp8_inv = 0, small = -1. */
+typedef struct md_attention_op {
+  int T, V, N, heads;  /* T sequences in groups of V views (1: single-view), N tokens, head_dim 64 */
+  int precision;       /* MD_PREC_*, optionally | MD_OP_POISON_PAD */
+  int seq_stride;      /* rows per sequence of the staged q | k and output rows; 0 = N rounded up to 4. < N: MD_ERR_SHAPE */
+  int kpad;            /* columns per row of the staged V^T; 0 = N rounded up to 64. Not a multiple of 64 covering N: MD_ERR_INVALID_ARG */
+  float out_fp8_inv;   /* > 0: the e4m3-output form (bf16, V = 1; else MD_ERR_UNSUPPORTED): out = uint8 [T, N, heads*64], the OCP e4m3 bytes of
+                        * clamp(value * out_fp8_inv, +-448) */
+  int small;           /* -1: the launcher's own rule for the small-launch (key-split) form; 0: that form off for this call */
+  int poison_pad;      /* != 0: as MD_OP_POISON_PAD -- rows N .. seq_stride, the slack rows and the V^T columns N .. kpad hold 0x7000 */
+  const float* qkv;    /* [T, N, 3*heads*64] fp32 (timm layout) */
+  void* out;           /* fp32 [T, N, heads*64], or the e4m3 bytes (see out_fp8_inv) */
+} md_attention_op;
+int md_op_attention_ex(md_device_t dev, const md_attention_op* desc, void* stream);
+/* Host-only: the form the calling thread's last attention launch took -- out[4] = form, workgroups of the main launch, query waves and
+ * key groups per workgroup. md_op_attention_ex resets it to MD_ATTN_FORM_NONE before it launches. */
+typedef enum md_attention_form {
+  MD_ATTN_FORM_NONE = -1, MD_ATTN_FORM_PLAIN = 0, MD_ATTN_FORM_KEY_SPLIT = 1, MD_ATTN_FORM_ASSEMBLY = 2, MD_ATTN_FORM_VIEWS = 3,
+  MD_ATTN_FORM_FP8_OUT = 4, MD_ATTN_FORM_F32_PATH = 5
+} md_attention_form;
+int md_debug_attention_last_form(int out[4]);
 /* Conv2d 3x3 stride 1 pad 1 (burn nn::Conv2d): fp32 NCHW in/out, w [Cout,Cin,3,3]. */
 int md_op_conv3x3(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B, int Cin,
                   int H, int W, int Cout, int pre_relu, int precision, float* out_dev, void* stream);
