@@ -1827,7 +1827,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 // ring slots 2 - 3 so that slots 0 - 1 can take the next tile's first k-tile meanwhile; V^T tiles (a third of the launch) staged transposed in
 // the OUTPUT type (8.5 KB per wave in slots 2 - 4; the one-tile kernel's fp32 staging covers the whole ring), so they overlap the same way.
 // CONV = true (with QKV = true: the plain W image and the lean staged store): the implicit 3 x 3 GEMM with bias (+ ReLU) and one 2-byte
-// output -- the first convolution of the decoder's residual units; the tile setup adds the pixel decomposition and the nine taps' border masks.
+// output -- the first convolution of the decoder's residual units. The tile setup decomposes the staged rows into pixels and keeps, per row, one
+// 32-bit offset from p.A and four border flags; the k-tiles are walked as 9 taps x cblocks in the flat order kt = tap * cblocks + cb, the tap's
+// offset and the flags it needs clear live in SGPRs, and a request inside a tap costs one scalar add. A wave none of whose 32 rows touches the
+// border at a tap (decided per tile by four ballots) issues the four requests without a per-lane select; the others select the zero page per row
+// as before -- four requests either way, so the counted waits hold. No scratch, 9 SGPR spills (bf16; 59 before: the raster and the group
+// tables are constants here, one group and one n-tile).
 template <typename T, bool FOLD, bool QKV = false, bool CONV = false>
 __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmParams p) {
   constexpr int BM = 256, BN = 256, NW = 8, WGN = 4, WTM = 128, WTN = 64, HALF_BYTES = 256 * 128, NSLOT = 5, LPH = 4, KE = 64, PLN = kPlanes<T>;
@@ -1855,24 +1860,41 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmParams p) {
 
   int m_base, m_end, n0, g;
   const char* Wg;
-  const char* srcA[LPH];
+  const char* srcA[LPH];  // dense A: the staged rows' addresses
   unsigned offW[LPH];
-  unsigned maskA[LPH];  // CONV: the nine taps' validity per staged row (3 row bits x 3 column bits)
+  // CONV: a staged row is ONE 32-bit byte offset of its centre pixel from p.A (launch_256 checks that the activation fits 4 GB), the four
+  // rows' border flags share one register (4 bits per row: 1 = row y - 1, 2 = row y + 1, 4 = column x - 1, 8 = column x + 1 lies outside
+  // the image), and everything a tap decides is wave-uniform: its offset, the flags it needs clear, the channel block inside it
+  unsigned offA[LPH], flA = 0;
+  int a_tap = 0, a_cb = 0, a_delta = 0;
+  unsigned a_need = 0, wave_fl = 0;  // wave_fl: the flags any lane of this wave has set in this tile
+  auto set_tap = [&](int tap) __attribute__((always_inline)) {
+    const int ky = (tap * 11) >> 5, kx = tap - ky * 3;  // tap / 3 for tap < 9
+    a_tap = tap;
+    a_cb = 0;
+    a_delta = ((ky - 1) * p.cW + (kx - 1)) * (p.cC * 2);
+    a_need = (ky == 0 ? 1u : 0u) | (ky == 2 ? 2u : 0u) | (kx == 0 ? 4u : 0u) | (kx == 2 ? 8u : 0u);
+  };
   auto locate = [&](int id) __attribute__((always_inline)) {
     int tile_n, tile_mg;
-    if (id < p.map_full_gsz) {
-      const int ng = fdiv(id, p.fd_map_gsz), r = id - ng * p.map_gsz;
-      tile_mg = fdiv(r, p.fd_map_gn);
-      tile_n = ng * p.map_gn + (r - tile_mg * p.map_gn);
-    } else {
-      const int r = id - p.map_full_gsz;
-      tile_mg = fdiv(r, p.fd_map_rn);
-      tile_n = p.map_full * p.map_gn + (r - tile_mg * p.map_rn);
-    }
     g = 0;
+    if constexpr (CONV) {  // one weight group, one 256-column tile in n (gemm256_form): the raster is the m-tiles in order
+      tile_mg = id;
+      tile_n = 0;
+    } else {
+      if (id < p.map_full_gsz) {
+        const int ng = fdiv(id, p.fd_map_gsz), r = id - ng * p.map_gsz;
+        tile_mg = fdiv(r, p.fd_map_gn);
+        tile_n = ng * p.map_gn + (r - tile_mg * p.map_gn);
+      } else {
+        const int r = id - p.map_full_gsz;
+        tile_mg = fdiv(r, p.fd_map_rn);
+        tile_n = p.map_full * p.map_gn + (r - tile_mg * p.map_rn);
+      }
 #pragma unroll
-    for (int i = 1; i < kMaxGroups; ++i)
-      if (i < p.ngroups && tile_mg >= p.g_tile0[i]) g = i;
+      for (int i = 1; i < kMaxGroups; ++i)
+        if (i < p.ngroups && tile_mg >= p.g_tile0[i]) g = i;
+    }
     const int g_row0 = MD_SEL_G(p.g_row0, g), g_arow0 = MD_SEL_G(p.g_arow0, g);
     m_base = g_row0 + (tile_mg - MD_SEL_G(p.g_tile0, g)) * BM;
     m_end = g_row0 + MD_SEL_G(p.g_rows, g);
@@ -1897,20 +1919,22 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmParams p) {
         const int bimg = fdiv(t2, p.fd_oh);
         const int oy = t2 - bimg * oh;
         const int x = ox * p.cstride, y = oy * p.cstride;
-        unsigned c3 = 0, mk = 0;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) c3 |= ((unsigned)(x + kx - 1) < (unsigned)p.cW ? 1u : 0u) << kx;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) mk |= ((unsigned)(y + ky - 1) < (unsigned)p.cH ? c3 : 0u) << (3 * ky);
-        maskA[i] = mk;
+        // (the centre tap is inside the image: launch_256 checks the output grid against the stride)
+        const unsigned fl = (y == 0 ? 1u : 0u) | (y + 1 >= p.cH ? 2u : 0u) | (x == 0 ? 4u : 0u) | (x + 1 >= p.cW ? 8u : 0u);
+        flA = i == 0 ? fl : flA | (fl << (4 * i));
         const int pix = (bimg * p.cH + y) * p.cW + x;
-        srcA[i] = (const char*)p.A + (long)pix * (long)(p.cC * 2) + lc * 16;
+        offA[i] = (unsigned)pix * (unsigned)(p.cC * 2) + (unsigned)(lc * 16);
       } else {
-        maskA[i] = 0;
         srcA[i] = (const char*)p.A + (long)(int)am * (long)(int)(p.lda * 2) + lc * 16;
       }
       const int rp = QKV ? r : ((r & ~63) | (((r >> 5) & 1) << 5) | (((r >> 2) & 3) << 3) | (((r >> 4) & 1) << 2) | (r & 3));  // fc1: the direct-store image
       offW[i] = (unsigned)(n0 + rp) * (unsigned)(ldw * 2) + (unsigned)(lc * 16);
+    }
+    if constexpr (CONV) {  // which border flags occur in this wave's 32 staged rows at all (interior tiles: none), and the walk starts at tap 0
+      const unsigned any = flA | (flA >> 4) | (flA >> 8) | (flA >> 12);
+      wave_fl = (__builtin_amdgcn_ballot_w64((any & 1u) != 0) != 0 ? 1u : 0u) | (__builtin_amdgcn_ballot_w64((any & 2u) != 0) != 0 ? 2u : 0u) |
+                (__builtin_amdgcn_ballot_w64((any & 4u) != 0) != 0 ? 4u : 0u) | (__builtin_amdgcn_ballot_w64((any & 8u) != 0) != 0 ? 8u : 0u);
+      set_tap(0);
     }
   };
   auto issue_W = [&](int kt, int slot) __attribute__((always_inline)) {
@@ -1923,15 +1947,20 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmParams p) {
   auto issue_A = [&](int kt, int slot) __attribute__((always_inline)) {
     char* sbase = smem + slot * HALF_BYTES;
     if constexpr (CONV) {
-      const int tap = fdiv(kt, p.fd_cblocks);
-      const int cb = kt - tap * cblocks;
-      const int ky = (tap * 11) >> 5, kx = tap - ky * 3;  // tap / 3 for tap < 9
-      const long a_delta = ((long)(ky - 1) * p.cW + (kx - 1)) * p.cC * 2 + (long)cb * 128;
-      int pc_o = lane;
-      asm volatile("" : "+v"(pc_o));
-      const char* zsrc = (const char*)p.zero_page + (pc_o & 7) * 16;
+      // the k-tiles of a tile are requested in order (0, 1, 2, ..): kt = a_tap * cblocks + a_cb, walked as 9 taps x cblocks. Inside a tap a request
+      // costs one scalar add of a_cb * 128 to the tap's base; the rows' offsets stay what locate() made them
+      const char* ab = (const char*)p.A + ((long)a_delta + (long)(a_cb * 128));
+      if ((wave_fl & a_need) == 0) {  // no lane of this wave is outside the image at this tap: every interior tile, most border tiles
 #pragma unroll
-      for (int i = 0; i < LPH; ++i) glds16(((maskA[i] >> tap) & 1u) ? srcA[i] + a_delta : zsrc, sbase + (i * NW + wave) * 1024);
+        for (int i = 0; i < LPH; ++i) glds16(ab + offA[i], sbase + (i * NW + wave) * 1024);
+      } else {  // the same four requests, the rows outside the image from the zero page
+        int pc_o = lane;
+        asm volatile("" : "+v"(pc_o));
+        const char* zsrc = (const char*)p.zero_page + (pc_o & 7) * 16;
+#pragma unroll
+        for (int i = 0; i < LPH; ++i) glds16(((flA >> (4 * i)) & a_need) == 0 ? ab + offA[i] : zsrc, sbase + (i * NW + wave) * 1024);
+      }
+      if (++a_cb == cblocks) set_tap(a_tap + 1);
     } else {
       const int kta = (p.a_wrap > 0 && kt >= p.a_wrap) ? kt - p.a_wrap : kt;
 #pragma unroll
@@ -2262,7 +2291,9 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmParams p) {
 // kernel's fp32 staging (17 KB per wave) covers the whole ring; here a wave stages 32 rows at a time (8.5 KB per wave in ring slots 2 - 4), so
 // that slots 0 - 1 can take the next tile's first k-tile under the 12 - 16 us of this epilogue. Same arithmetic, same bits.
 // CONVR = true: the implicit 3 x 3 GEMM whose 2-byte store epilogue has residual inputs and / or a relu'd second output (the second convolution of
-// the decoder's residual units) on the same skeleton: gemm256_kernel's arithmetic of that form in the 32-row passes.
+// the decoder's residual units) on the same skeleton: gemm256_kernel's arithmetic of that form in the 32-row passes; tile setup and tap walk as
+// in gemm256p_kernel's CONV form. Its epilogue LOADS (the residual vectors, requested behind the next tile's k-tile 0), and hipcc waits vmcnt(0)
+// in front of the first pass's use of them: the next tile's first requests have landed by then by construction.
 template <typename T, bool EMIT, bool CONVR = false>
 __global__ __launch_bounds__(512) void gemm256r_kernel(const GemmParams p) {
   constexpr bool FOLD = false, QKV = true;  // (QKV = true below only selects the plain W image)
@@ -2291,24 +2322,41 @@ __global__ __launch_bounds__(512) void gemm256r_kernel(const GemmParams p) {
 
   int m_base, m_end, n0, g;
   const char* Wg;
-  const char* srcA[LPH];
+  const char* srcA[LPH];  // dense A: the staged rows' addresses
   unsigned offW[LPH];
-  unsigned maskA[LPH];  // CONVR: the nine taps' validity per staged row
+  // CONVR: a staged row is ONE 32-bit byte offset of its centre pixel from p.A (launch_256 checks that the activation fits 4 GB), the four
+  // rows' border flags share one register (4 bits per row: 1 = row y - 1, 2 = row y + 1, 4 = column x - 1, 8 = column x + 1 lies outside
+  // the image), and everything a tap decides is wave-uniform: its offset, the flags it needs clear, the channel block inside it
+  unsigned offA[LPH], flA = 0;
+  int a_tap = 0, a_cb = 0, a_delta = 0;
+  unsigned a_need = 0, wave_fl = 0;  // wave_fl: the flags any lane of this wave has set in this tile
+  auto set_tap = [&](int tap) __attribute__((always_inline)) {
+    const int ky = (tap * 11) >> 5, kx = tap - ky * 3;  // tap / 3 for tap < 9
+    a_tap = tap;
+    a_cb = 0;
+    a_delta = ((ky - 1) * p.cW + (kx - 1)) * (p.cC * 2);
+    a_need = (ky == 0 ? 1u : 0u) | (ky == 2 ? 2u : 0u) | (kx == 0 ? 4u : 0u) | (kx == 2 ? 8u : 0u);
+  };
   auto locate = [&](int id) __attribute__((always_inline)) {
     int tile_n, tile_mg;
-    if (id < p.map_full_gsz) {
-      const int ng = fdiv(id, p.fd_map_gsz), r = id - ng * p.map_gsz;
-      tile_mg = fdiv(r, p.fd_map_gn);
-      tile_n = ng * p.map_gn + (r - tile_mg * p.map_gn);
-    } else {
-      const int r = id - p.map_full_gsz;
-      tile_mg = fdiv(r, p.fd_map_rn);
-      tile_n = p.map_full * p.map_gn + (r - tile_mg * p.map_rn);
-    }
     g = 0;
+    if constexpr (CONVR) {  // one weight group, one 256-column tile in n (gemm256_form): the raster is the m-tiles in order
+      tile_mg = id;
+      tile_n = 0;
+    } else {
+      if (id < p.map_full_gsz) {
+        const int ng = fdiv(id, p.fd_map_gsz), r = id - ng * p.map_gsz;
+        tile_mg = fdiv(r, p.fd_map_gn);
+        tile_n = ng * p.map_gn + (r - tile_mg * p.map_gn);
+      } else {
+        const int r = id - p.map_full_gsz;
+        tile_mg = fdiv(r, p.fd_map_rn);
+        tile_n = p.map_full * p.map_gn + (r - tile_mg * p.map_rn);
+      }
 #pragma unroll
-    for (int i = 1; i < kMaxGroups; ++i)
-      if (i < p.ngroups && tile_mg >= p.g_tile0[i]) g = i;
+      for (int i = 1; i < kMaxGroups; ++i)
+        if (i < p.ngroups && tile_mg >= p.g_tile0[i]) g = i;
+    }
     const int g_row0 = MD_SEL_G(p.g_row0, g), g_arow0 = MD_SEL_G(p.g_arow0, g);
     m_base = g_row0 + (tile_mg - MD_SEL_G(p.g_tile0, g)) * BM;
     m_end = g_row0 + MD_SEL_G(p.g_rows, g);
@@ -2333,20 +2381,22 @@ __global__ __launch_bounds__(512) void gemm256r_kernel(const GemmParams p) {
         const int bimg = fdiv(t2, p.fd_oh);
         const int oy = t2 - bimg * oh;
         const int x = ox * p.cstride, y = oy * p.cstride;
-        unsigned c3 = 0, mk = 0;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) c3 |= ((unsigned)(x + kx - 1) < (unsigned)p.cW ? 1u : 0u) << kx;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) mk |= ((unsigned)(y + ky - 1) < (unsigned)p.cH ? c3 : 0u) << (3 * ky);
-        maskA[i] = mk;
+        // (the centre tap is inside the image: launch_256 checks the output grid against the stride)
+        const unsigned fl = (y == 0 ? 1u : 0u) | (y + 1 >= p.cH ? 2u : 0u) | (x == 0 ? 4u : 0u) | (x + 1 >= p.cW ? 8u : 0u);
+        flA = i == 0 ? fl : flA | (fl << (4 * i));
         const int pix = (bimg * p.cH + y) * p.cW + x;
-        srcA[i] = (const char*)p.A + (long)pix * (long)(p.cC * 2) + lc * 16;
+        offA[i] = (unsigned)pix * (unsigned)(p.cC * 2) + (unsigned)(lc * 16);
       } else {
-        maskA[i] = 0;
         srcA[i] = (const char*)p.A + (long)(int)am * (long)(int)(p.lda * 2) + lc * 16;
       }
       const int rp = QKV ? r : ((r & ~63) | (((r >> 5) & 1) << 5) | (((r >> 2) & 3) << 3) | (((r >> 4) & 1) << 2) | (r & 3));  // fc1: the direct-store image
       offW[i] = (unsigned)(n0 + rp) * (unsigned)(ldw * 2) + (unsigned)(lc * 16);
+    }
+    if constexpr (CONVR) {  // which border flags occur in this wave's 32 staged rows at all (interior tiles: none), and the walk starts at tap 0
+      const unsigned any = flA | (flA >> 4) | (flA >> 8) | (flA >> 12);
+      wave_fl = (__builtin_amdgcn_ballot_w64((any & 1u) != 0) != 0 ? 1u : 0u) | (__builtin_amdgcn_ballot_w64((any & 2u) != 0) != 0 ? 2u : 0u) |
+                (__builtin_amdgcn_ballot_w64((any & 4u) != 0) != 0 ? 4u : 0u) | (__builtin_amdgcn_ballot_w64((any & 8u) != 0) != 0 ? 8u : 0u);
+      set_tap(0);
     }
   };
   auto issue_W = [&](int kt, int slot) __attribute__((always_inline)) {
@@ -2359,15 +2409,20 @@ __global__ __launch_bounds__(512) void gemm256r_kernel(const GemmParams p) {
   auto issue_A = [&](int kt, int slot) __attribute__((always_inline)) {
     char* sbase = smem + slot * HALF_BYTES;
     if constexpr (CONVR) {
-      const int tap = fdiv(kt, p.fd_cblocks);
-      const int cb = kt - tap * cblocks;
-      const int ky = (tap * 11) >> 5, kx = tap - ky * 3;  // tap / 3 for tap < 9
-      const long a_delta = ((long)(ky - 1) * p.cW + (kx - 1)) * p.cC * 2 + (long)cb * 128;
-      int pc_z = lane;
-      asm volatile("" : "+v"(pc_z));
-      const char* zsrc = (const char*)p.zero_page + (pc_z & 7) * 16;
+      // the k-tiles of a tile are requested in order (0, 1, 2, ..): kt = a_tap * cblocks + a_cb, walked as 9 taps x cblocks. Inside a tap a request
+      // costs one scalar add of a_cb * 128 to the tap's base; the rows' offsets stay what locate() made them
+      const char* ab = (const char*)p.A + ((long)a_delta + (long)(a_cb * 128));
+      if ((wave_fl & a_need) == 0) {  // no lane of this wave is outside the image at this tap: every interior tile, most border tiles
 #pragma unroll
-      for (int i = 0; i < LPH; ++i) glds16(((maskA[i] >> tap) & 1u) ? srcA[i] + a_delta : zsrc, sbase + (i * NW + wave) * 1024);
+        for (int i = 0; i < LPH; ++i) glds16(ab + offA[i], sbase + (i * NW + wave) * 1024);
+      } else {  // the same four requests, the rows outside the image from the zero page
+        int pc_z = lane;
+        asm volatile("" : "+v"(pc_z));
+        const char* zsrc = (const char*)p.zero_page + (pc_z & 7) * 16;
+#pragma unroll
+        for (int i = 0; i < LPH; ++i) glds16(((flA >> (4 * i)) & a_need) == 0 ? ab + offA[i] : zsrc, sbase + (i * NW + wave) * 1024);
+      }
+      if (++a_cb == cblocks) set_tap(a_tap + 1);
     } else {
       const int kta = (p.a_wrap > 0 && kt >= p.a_wrap) ? kt - p.a_wrap : kt;
 #pragma unroll
@@ -2648,6 +2703,15 @@ __global__ __launch_bounds__(512) void gemm256r_kernel(const GemmParams p) {
 }
 
 
+// What the convolution tile loops assume of a launch beyond gemm256_form's conditions: a staged row is a 32-bit byte offset of its centre pixel from
+// p.A, so the images the launch reads must end below 4 GB (the decoder's largest activation, 8 x 768^2 x 256 x 2 B, is 2.4 GB), and the centre
+// tap of every output pixel lies inside the image (the border flags cover the eight outer taps only).
+static inline bool conv_loop_fits(const GemmParams& p) {
+  const long ow = p.cOW > 0 ? p.cOW : p.cW, oh = p.cOH > 0 ? p.cOH : p.cH;
+  const long rows = (long)p.g_arow0[0] + p.g_rows[0], imgs = (rows + ow * oh - 1) / (ow * oh);
+  return (ow - 1) * p.cstride < p.cW && (oh - 1) * p.cstride < p.cH && imgs * p.cH * p.cW * p.cC * 2 <= 0xffffffffL;
+}
+
 // host side of map_tile: n-tiles are walked in groups of gn (L2-aware raster), the last group may be narrower
 static inline void prep_tile_map(GemmParams& p, int tiles_m, int tiles_n) {
   const int gn = p.raster_gn > 0 ? p.raster_gn : tiles_n;
@@ -2711,9 +2775,13 @@ static int launch_256(GemmParams& p, hipStream_t stream) {
   MD_HIP(hipGetDevice(&ordinal));
   MD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ordinal));
   std::string why_not;
-  const Form256 f = gemm256_form(p, AMODE, kPrecOf<T>, cus, &why_not);
+  Form256 f = gemm256_form(p, AMODE, kPrecOf<T>, cus, &why_not);
   if (f.err != MD_OK) MD_FAIL(f.err, "%s", why_not.c_str());
   if (f.blocks <= 0) return MD_OK;
+  if (f.family != F256_ONE_TILE && f.conv && !conv_loop_fits(p)) {  // the one-tile kernel's 64-bit row addresses instead: same bits
+    f.family = F256_ONE_TILE, f.fold = f.qkv = f.conv = false;
+    f.grid = (int)f.blocks, f.ptiles = 0, f.stagger = 0;
+  }
   gemm_record_form(f);
   prep_tile_map(p, tiles_m, cdiv(p.N, BN));
   if (f.family != F256_ONE_TILE) p.ptiles = f.ptiles, p.stagger = f.stagger;
