@@ -14,7 +14,11 @@
 // mesh stage over the list's rows are drawn into the caller's target cameras.
 // md_op_radius_outliers / md_infer_points_outlier put the radius outlier removal (kernels/outlier.hip) between the scatter and the
 // thinning: the scatter fills a list of the model's own, the filter writes the caller's, or with thinning a second list of the model's.
-// The eight md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan).
+// md_op_decimate_mesh / md_infer_points_decimate (kernels/decimate.hip), md_op_mesh_components / md_infer_points_components
+// (kernels/components.hip) and md_op_smooth_mesh / md_infer_points_smooth (kernels/smooth.hip) work on the mesh stage's faces:
+// the decimation writes the list and the faces the call ends with, the other two leave the list as it is.
+// The eleven md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
+// which holds the list the call ends with once (PointsPlan::fin, wired to the last list stage in plan_homes).
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -187,9 +191,10 @@ int check_voxel(const md_points_voxel* vox, const md_points_outputs* out, bool o
 bool decimate_on(const md_points_decimate* d) { return d && d->voxel != 0.f; }
 
 // model call: voxel == 0 is the call without decimation and takes none of its outputs
-int check_decimate_part(const md_points_decimate* d, const md_points_outputs* out) {
+int check_decimate(const md_points_decimate* d, const md_points_outputs* out, bool op) {
   if (!d) return MD_OK;
-  if (!std::isfinite(d->voxel) || d->voxel < 0.f) MD_FAIL(MD_ERR_INVALID_ARG, "voxel = %g: must be finite and >= 0", (double)d->voxel);
+  if (!std::isfinite(d->voxel) || d->voxel < 0.f || (op && d->voxel == 0.f))
+    MD_FAIL(MD_ERR_INVALID_ARG, "voxel = %g: must be finite and %s 0", (double)d->voxel, op ? ">" : ">=");
   if (d->voxel == 0.f) {
     if (d->index || d->weight || d->dropped || d->remap || d->faces || d->face_index || d->face_count || d->faces_dropped)
       MD_FAIL(MD_ERR_INVALID_ARG, "decimation outputs without a voxel size");
@@ -258,22 +263,36 @@ int check_outlier(const md_points_outlier* q, const md_points_outputs* out, bool
   return MD_OK;
 }
 
-// the rendering part of the operator and of the model call; has_rgb: there is an rgb row to gather from
-int check_render(int T, int H, int W, const md_points_cameras* cam, const md_render_opts* o, const md_render_outputs* out, bool has_rgb) {
-  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "render options are null");
-  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "render outputs are null");
+// The refusals the rendering and the rasterising share, in two halves around the options of their own. what / done: "render" /
+// "rendered" or "raster" / "rasterised"; has_rgb: there is an rgb row to gather from
+bool any_output(const md_render_outputs& o) { return o.depth || o.index || o.rgb || o.filled; }
+bool any_output(const md_raster_outputs& o) { return o.depth || o.face || o.rgb || o.filled || o.skipped; }
+template <typename Opts, typename Outs>
+int check_target_args(const char* what, const char* done, const md_points_cameras* cam, const Opts* o, const Outs* out, bool has_rgb) {
+  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "%s options are null", what);
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "%s outputs are null", what);
   if (!cam) MD_FAIL(MD_ERR_INVALID_ARG, "target cameras are null");
-  if (!out->depth && !out->index && !out->rgb && !out->filled) MD_FAIL(MD_ERR_INVALID_ARG, "every render output is null");
-  if (out->rgb && !has_rgb) MD_FAIL(MD_ERR_INVALID_ARG, "a rendered rgb output needs an rgb row");
+  if (!any_output(*out)) MD_FAIL(MD_ERR_INVALID_ARG, "every %s output is null", what);
+  if (out->rgb && !has_rgb) MD_FAIL(MD_ERR_INVALID_ARG, "a %s rgb output needs an rgb row", done);
   if (!cam->intrinsics && !cam->focal_px) MD_FAIL(MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras");
-  if (o->radius < 0 || o->radius > kRenderMaxRadius) MD_FAIL(MD_ERR_INVALID_ARG, "radius %d outside 0..%d", o->radius, kRenderMaxRadius);
-  MD_TRY(check_offset(o->pixel_offset));
-  MD_TRY(check_nonneg("z_near", o->z_near));
-  MD_TRY(check_nonneg("z_far", o->z_far));
-  if (o->z_near > 0.f && o->z_far > 0.f && o->z_far < o->z_near) MD_FAIL(MD_ERR_INVALID_ARG, "z_far %g < z_near %g", (double)o->z_far, (double)o->z_near);
-  if (T <= 0 || H <= 0 || W <= 0 || (long)T * H * W >= (1l << 31) || H >= (1 << 24) || W >= (1 << 24))
-    MD_FAIL(MD_ERR_SHAPE, "invalid render target shape [%d,%d,%d]", T, H, W);
   return MD_OK;
+}
+template <typename Opts>
+int check_target_view(const char* what, int T, int H, int W, const Opts& o) {
+  MD_TRY(check_offset(o.pixel_offset));
+  MD_TRY(check_nonneg("z_near", o.z_near));
+  MD_TRY(check_nonneg("z_far", o.z_far));
+  if (o.z_near > 0.f && o.z_far > 0.f && o.z_far < o.z_near) MD_FAIL(MD_ERR_INVALID_ARG, "z_far %g < z_near %g", (double)o.z_far, (double)o.z_near);
+  if (T <= 0 || H <= 0 || W <= 0 || (long)T * H * W >= (1l << 31) || H >= (1 << 24) || W >= (1 << 24))
+    MD_FAIL(MD_ERR_SHAPE, "invalid %s target shape [%d,%d,%d]", what, T, H, W);
+  return MD_OK;
+}
+
+// the rendering part of the operator and of the model call
+int check_render(int T, int H, int W, const md_points_cameras* cam, const md_render_opts* o, const md_render_outputs* out, bool has_rgb) {
+  MD_TRY(check_target_args("render", "rendered", cam, o, out, has_rgb));
+  if (o->radius < 0 || o->radius > kRenderMaxRadius) MD_FAIL(MD_ERR_INVALID_ARG, "radius %d outside 0..%d", o->radius, kRenderMaxRadius);
+  return check_target_view("render", T, H, W, *o);
 }
 
 RenderParams make_render(int T, int H, int W, const md_render_opts& o) {
@@ -283,23 +302,12 @@ RenderParams make_render(int T, int H, int W, const md_render_opts& o) {
   return r;
 }
 
-// the shared part of md_op_render_mesh's and md_infer_points_raster's refusals: check_render's, with the raster's own options
+// the rasterising part of md_op_render_mesh and of the model call
 int check_raster(int T, int H, int W, const md_points_cameras* cam, const md_raster_opts* o, const md_raster_outputs* out, bool has_rgb) {
-  if (!o) MD_FAIL(MD_ERR_INVALID_ARG, "raster options are null");
-  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "raster outputs are null");
-  if (!cam) MD_FAIL(MD_ERR_INVALID_ARG, "target cameras are null");
-  if (!out->depth && !out->face && !out->rgb && !out->filled && !out->skipped) MD_FAIL(MD_ERR_INVALID_ARG, "every raster output is null");
-  if (out->rgb && !has_rgb) MD_FAIL(MD_ERR_INVALID_ARG, "a rasterised rgb output needs an rgb row");
-  if (!cam->intrinsics && !cam->focal_px) MD_FAIL(MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras");
+  MD_TRY(check_target_args("raster", "rasterised", cam, o, out, has_rgb));
   if (o->cull != 0 && o->cull != 1) MD_FAIL(MD_ERR_INVALID_ARG, "cull %d: 0 or 1", o->cull);
   if (o->max_extent < 0 || o->max_extent > kRasterMaxExtent) MD_FAIL(MD_ERR_INVALID_ARG, "max_extent %d outside 0..%d", o->max_extent, kRasterMaxExtent);
-  MD_TRY(check_offset(o->pixel_offset));
-  MD_TRY(check_nonneg("z_near", o->z_near));
-  MD_TRY(check_nonneg("z_far", o->z_far));
-  if (o->z_near > 0.f && o->z_far > 0.f && o->z_far < o->z_near) MD_FAIL(MD_ERR_INVALID_ARG, "z_far %g < z_near %g", (double)o->z_far, (double)o->z_near);
-  if (T <= 0 || H <= 0 || W <= 0 || (long)T * H * W >= (1l << 31) || H >= (1 << 24) || W >= (1 << 24))
-    MD_FAIL(MD_ERR_SHAPE, "invalid raster target shape [%d,%d,%d]", T, H, W);
-  return MD_OK;
+  return check_target_view("raster", T, H, W, *o);
 }
 
 RasterParams make_raster(int T, int H, int W, const md_raster_opts& o, const md_raster_outputs& out) {
@@ -387,7 +395,62 @@ struct OpScratch {
     MD_HIP(sync);
     return MD_OK;
   }
+  // finish() behind launches that leave probe-loop flags in the scratch: the words at `a` and `b` (null: never reset, not read)
+  // are read before the scratch they lie in is freed; a set one is the refusal `ran_out`
+  int finish_flags(int rc, const int32_t* a, const int32_t* b, const char* ran_out) {
+    int32_t flag[2] = {0, 0};
+    hipError_t copy = hipSuccess;
+    if (rc == MD_OK && a) copy = hipMemcpyAsync(&flag[0], a, 4, hipMemcpyDeviceToHost, st);
+    if (rc == MD_OK && copy == hipSuccess && b) copy = hipMemcpyAsync(&flag[1], b, 4, hipMemcpyDeviceToHost, st);
+    MD_TRY(finish(rc, copy));
+    if (flag[0] || flag[1]) MD_FAIL(MD_ERR_HIP, "%s", ran_out);
+    return MD_OK;
+  }
 };
+
+// a set probe-loop flag, as the operators and the model call report it
+const char kVoxelRanOut[] = "voxel thinning: the probe loop ran out of table slots";
+const char kOutlierRanOut[] = "outlier removal: a probe loop ran out of table slots";
+const char kDecimateRanOut[] = "decimation: a probe loop ran out of table slots";
+
+// Every operator's last refusal and first act: the device, made current, and the stream its launches take.
+int op_begin(md_device_t dev, hipStream_t stream, hipStream_t* st) {
+  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
+  MD_HIP(hipSetDevice(dev->ordinal));
+  *st = stream ? stream : dev->stream;
+  return MD_OK;
+}
+
+// The refusals of the operators that take a list (and faces over its rows: F given) and write a list, in the order all of them
+// keep: the sizes, the outputs, the limits. `noun` names the operator; the components, a plural with outputs of their own
+// between these, call the parts.
+int check_list_sizes(const PointList& in, const int64_t* F) {
+  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
+  if (F && *F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)*F);
+  return MD_OK;
+}
+int check_list_rows(const PointList& in, const md_points_outputs* out, const float* normals_out) {
+  if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
+  if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
+  if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+  return MD_OK;
+}
+int check_list_limits(const char* noun, const char* takes, const PointList& in, bool reads_xyz, const int32_t* faces, const int64_t* F) {
+  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "%s %s fewer than 2^30 rows, got %lld", noun, takes, (long long)in.N);
+  if (F && *F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "%s %s fewer than 2^30 faces, got %lld", noun, takes, (long long)*F);
+  if (reads_xyz && in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  if (F && *F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
+  return MD_OK;
+}
+int check_list_op(const char* noun, const PointList& in, const md_points_outputs* out, const float* normals_out,
+                  const int32_t* faces = nullptr, const int64_t* F = nullptr) {
+  MD_TRY(check_list_sizes(in, F));
+  MD_TRY(check_capacity(out));
+  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "%s has no dense output", noun);
+  MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out, out, "the compacted outputs"));
+  MD_TRY(check_list_rows(in, out, normals_out));
+  return check_list_limits(noun, "takes", in, true, faces, F);
+}
 
 }  // namespace
 
@@ -399,9 +462,8 @@ int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* 
   MD_TRY(check_shape(in.B, in.H, in.W));
   MD_TRY(check_mesh(mesh, out->count != nullptr, false, in.B, in.H, in.W));
   if (!in.depth) MD_FAIL(MD_ERR_INVALID_ARG, "depth pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   PointsParams p = make_params(in.B, in.H, in.W, *o);
   p.depth = in.depth; p.conf = in.conf; p.rgb = in.rgb;
   p.K = cam->intrinsics; p.focal = cam->focal_px; p.E = cam->extrinsics;
@@ -432,9 +494,9 @@ int op_mesh_grid(md_device_t dev, const DepthMaps& in, const int32_t* pixel_inde
   faces_only.pixel_index = nullptr;
   MD_TRY(check_mesh(&faces_only, true, false, in.B, in.H, in.W));
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  if (!mesh->face_count) return MD_OK;
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  if (!mesh->face_count) return MD_OK;  // nothing to launch: the device stays as it was
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   MeshParams g = make_mesh(in.B, in.H, in.W, stride, vertex_limit ? (long)vertex_limit : LONG_MAX, *mesh);
   g.depth = in.depth; g.pixel_index = pixel_index;
   OpScratch scratch(st);
@@ -453,9 +515,8 @@ int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_camera
   const Sources s{false, in.conf != nullptr, c.intrinsics != nullptr, c.focal_px != nullptr, c.extrinsics != nullptr};
   MD_TRY(check_filter(o, s, in.B, in.H, in.W));
   if (!in.depth) MD_FAIL(MD_ERR_INVALID_ARG, "depth pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   ViewFilterParams p = make_filter_params(in.B, in.H, in.W, *o);
   p.depth = in.depth; p.conf = in.conf;
   p.K = c.intrinsics; p.focal = c.intrinsics ? nullptr : c.focal_px; p.E = c.extrinsics;
@@ -470,18 +531,9 @@ int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* v
   if (!vox) MD_FAIL(MD_ERR_INVALID_ARG, "voxel options are null");
   if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
   MD_TRY(check_voxel(vox, out, true));
-  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
-  MD_TRY(check_capacity(out));
-  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "voxel thinning has no dense output");
-  MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out, out, "the compacted outputs"));
-  if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
-  if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
-  if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
-  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, got %lld", (long long)in.N);
-  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  MD_TRY(check_list_op("voxel thinning", in, out, normals_out));
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   VoxelParams p;
   p.xyz = in.xyz; p.conf = in.conf; p.rgb = in.rgb; p.normals = in.normals;
   p.n = (int)in.N; p.B = 1; p.voxel = vox->voxel;
@@ -489,13 +541,7 @@ int op_voxel_thin(md_device_t dev, const PointList& in, const md_points_voxel* v
   p.index = vox->index; p.weight = vox->weight; p.count = out->count; p.dropped = vox->dropped; p.capacity = out->capacity;
   OpScratch scratch(st);
   MD_TRY(scratch.alloc(voxel_scratch_bytes(p.n)));
-  const int rc = launch_voxel_thin(p, scratch.p, st);
-  int32_t flag = 0;
-  hipError_t copy = hipSuccess;  // the flag is read before the scratch it lies in is freed
-  if (rc == MD_OK) copy = hipMemcpyAsync(&flag, voxel_flags(scratch.p, p.n), 4, hipMemcpyDeviceToHost, st);
-  MD_TRY(scratch.finish(rc, copy));
-  if (flag) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
-  return MD_OK;
+  return scratch.finish_flags(launch_voxel_thin(p, scratch.p, st), voxel_flags(scratch.p, p.n), nullptr, kVoxelRanOut);
 }
 
 int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_outlier* outl, const md_points_outputs* out, float* normals_out,
@@ -503,18 +549,9 @@ int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_out
   if (!outl) MD_FAIL(MD_ERR_INVALID_ARG, "outlier options are null");
   if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
   MD_TRY(check_outlier(outl, out, true));
-  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
-  MD_TRY(check_capacity(out));
-  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "outlier removal has no dense output");
-  MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out, out, "the compacted outputs"));
-  if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
-  if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
-  if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
-  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "outlier removal takes fewer than 2^30 rows, got %lld", (long long)in.N);
-  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  MD_TRY(check_list_op("outlier removal", in, out, normals_out));
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   OutlierParams p;
   p.xyz = in.xyz; p.conf = in.conf; p.rgb = in.rgb; p.normals = in.normals;
   p.n = (int)in.N; p.B = 1; p.radius = outl->radius; p.k = outl->min_neighbours;
@@ -522,44 +559,17 @@ int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_out
   p.index = outl->index; p.neighbours = outl->neighbours; p.count = out->count; p.dropped = outl->dropped; p.capacity = out->capacity;
   OpScratch scratch(st);
   MD_TRY(scratch.alloc(outlier_scratch_bytes(p.n)));
-  const int rc = launch_radius_outliers(p, scratch.p, st);
-  int32_t flag = 0;
-  hipError_t copy = hipSuccess;  // the flag is read before the scratch it lies in is freed
-  if (rc == MD_OK) copy = hipMemcpyAsync(&flag, outlier_flags(scratch.p, p.n), 4, hipMemcpyDeviceToHost, st);
-  MD_TRY(scratch.finish(rc, copy));
-  if (flag) MD_FAIL(MD_ERR_HIP, "outlier removal: a probe loop ran out of table slots");
-  return MD_OK;
-}
-
-// the refusals of the decimation's own part, in check_voxel's and check_mesh's style
-int check_decimate(const md_points_decimate* dec, const md_points_outputs* out) {
-  if (!std::isfinite(dec->voxel) || dec->voxel <= 0.f) MD_FAIL(MD_ERR_INVALID_ARG, "voxel = %g: must be finite and > 0", (double)dec->voxel);
-  if (dec->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)dec->face_capacity);
-  if ((dec->faces || dec->face_index) && !dec->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
-  MD_TRY(need_count(dec->index || dec->weight, out, "index / weight"));
-  return MD_OK;
+  return scratch.finish_flags(launch_radius_outliers(p, scratch.p, st), outlier_flags(scratch.p, p.n), nullptr, kOutlierRanOut);
 }
 
 int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
                      const md_points_outputs* out, float* normals_out, hipStream_t stream) {
   if (!dec) MD_FAIL(MD_ERR_INVALID_ARG, "decimation options are null");
   if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
-  MD_TRY(check_decimate(dec, out));
-  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
-  if (F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)F);
-  MD_TRY(check_capacity(out));
-  if (out->point_map || out->mask || out->depth) MD_FAIL(MD_ERR_INVALID_ARG, "decimation has no dense output");
-  MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out, out, "the compacted outputs"));
-  if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
-  if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
-  if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
-  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 rows, got %lld", (long long)in.N);
-  if (F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 faces, got %lld", (long long)F);
-  if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
-  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  MD_TRY(check_decimate(dec, out, true));
+  MD_TRY(check_list_op("decimation", in, out, normals_out, faces, &F));
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   DecimateParams p;
   p.v.xyz = in.xyz; p.v.conf = in.conf; p.v.rgb = in.rgb; p.v.normals = in.normals;
   p.v.n = (int)in.N; p.v.B = 1; p.v.voxel = dec->voxel;
@@ -570,24 +580,16 @@ int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces,
   p.face_capacity = (long)dec->face_capacity;
   OpScratch scratch(st);
   MD_TRY(scratch.alloc(decimate_scratch_bytes(p.v.n, p.nf, 1)));
-  const int rc = launch_decimate_mesh(p, scratch.p, st);
-  int32_t flag[2] = {0, 0};
-  hipError_t copy = hipSuccess;  // the flags are read before the scratch they lie in is freed
-  if (rc == MD_OK) copy = hipMemcpyAsync(&flag[0], voxel_flags(scratch.p, p.v.n), 4, hipMemcpyDeviceToHost, st);
   const bool face_side = p.faces_out || p.face_index || p.face_count || p.faces_dropped;  // otherwise the face table was never reset
-  if (rc == MD_OK && copy == hipSuccess && face_side)
-    copy = hipMemcpyAsync(&flag[1], decimate_flags(scratch.p, p.v.n, p.nf, 1), 4, hipMemcpyDeviceToHost, st);
-  MD_TRY(scratch.finish(rc, copy));
-  if (flag[0] || flag[1]) MD_FAIL(MD_ERR_HIP, "decimation: a probe loop ran out of table slots");
-  return MD_OK;
+  return scratch.finish_flags(launch_decimate_mesh(p, scratch.p, st), voxel_flags(scratch.p, p.v.n),
+                              face_side ? decimate_flags(scratch.p, p.v.n, p.nf, 1) : nullptr, kDecimateRanOut);
 }
 
 int op_mesh_components(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_components* comp,
                        const md_points_outputs* out, float* normals_out, hipStream_t stream) {
   if (!comp) MD_FAIL(MD_ERR_INVALID_ARG, "component options are null");
   if (comp->min_faces < 1) MD_FAIL(MD_ERR_INVALID_ARG, "min_faces = %d: must be >= 1", comp->min_faces);
-  if (in.N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)in.N);
-  if (F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)F);
+  MD_TRY(check_list_sizes(in, &F));
   if (comp->face_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face_capacity %lld is negative", (long long)comp->face_capacity);
   if ((comp->faces || comp->face_index) && !comp->face_count) MD_FAIL(MD_ERR_INVALID_ARG, "faces / face_index need `face_count`");
   if (out && (out->point_map || out->mask || out->depth)) MD_FAIL(MD_ERR_INVALID_ARG, "components have no dense output");
@@ -599,16 +601,11 @@ int op_mesh_components(md_device_t dev, const PointList& in, const int32_t* face
     MD_TRY(check_capacity(out));
     MD_TRY(need_count(out->xyz || out->rgb || out->conf || normals_out || comp->index, out, "the compacted outputs"));
     if (out->xyz && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "an xyz output needs the xyz rows");
-    if (out->rgb && !in.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "an rgb output needs an rgb row");
-    if (out->conf && !in.conf) MD_FAIL(MD_ERR_INVALID_ARG, "a conf output needs a confidence row");
-    if (normals_out && !in.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+    MD_TRY(check_list_rows(in, out, normals_out));
   }
-  if (in.N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 rows, got %lld", (long long)in.N);
-  if (F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 faces, got %lld", (long long)F);
-  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  MD_TRY(check_list_limits("components", "take", in, false, faces, &F));  // in.N bounds the corners: the rows themselves may be absent
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   ComponentsParams p;
   p.v.n = (int)in.N; p.v.B = 1;
   if (comp->compact) {
@@ -630,16 +627,13 @@ int op_smooth_mesh(md_device_t dev, const float* xyz, int64_t N, const int32_t* 
                    hipStream_t stream) {
   if (!smooth) MD_FAIL(MD_ERR_INVALID_ARG, "smoothing options are null");
   MD_TRY(check_smooth_values(smooth));
-  if (N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)N);
-  if (F < 0) MD_FAIL(MD_ERR_INVALID_ARG, "F = %lld is negative", (long long)F);
+  PointList in;
+  in.xyz = xyz; in.N = N;
+  MD_TRY(check_list_sizes(in, &F));
   if (capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "capacity %lld is negative", (long long)capacity);
-  if (N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 rows, got %lld", (long long)N);
-  if (F >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 faces, got %lld", (long long)F);
-  if (N > 0 && !xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
-  if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  MD_TRY(check_list_limits("smoothing", "takes", in, true, faces, &F));
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   SmoothParams p;
   p.xyz = xyz; p.n = (int)N; p.faces = faces; p.nf = (int)F;
   p.step = smooth->step; p.lambda = smooth->lambda; p.mu = smooth->mu; p.iterations = smooth->iterations; p.pin_boundary = smooth->pin_boundary;
@@ -654,9 +648,8 @@ int op_render_points(md_device_t dev, const PointList& in, const int32_t* count,
   MD_TRY(check_render(T, H, W, cam, o, out, in.rgb != nullptr));
   if (in.N < 0 || in.N >= (1ll << 31)) MD_FAIL(MD_ERR_SHAPE, "rendering takes 0 .. 2^31 - 1 rows, got %lld", (long long)in.N);
   if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   RenderParams r = make_render(T, H, W, *o);
   r.xyz = in.xyz; r.rgb = in.rgb; r.count = count; r.n = (int)in.N;
   r.K = cam->intrinsics; r.focal = cam->intrinsics ? nullptr : cam->focal_px; r.E = cam->extrinsics;
@@ -673,9 +666,8 @@ int op_render_mesh(md_device_t dev, const PointList& in, const int32_t* faces, i
   if (F < 0 || F >= (1ll << 31)) MD_FAIL(MD_ERR_SHAPE, "rasterising takes 0 .. 2^31 - 1 faces, got %lld", (long long)F);
   if (in.N > 0 && !in.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
   if (F > 0 && !faces) MD_FAIL(MD_ERR_INVALID_ARG, "faces pointer is null");
-  if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = stream ? stream : dev->stream;
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
   RasterParams r = make_raster(T, H, W, *o, *out);
   r.xyz = in.xyz; r.rgb = in.rgb; r.n = (int)in.N; r.faces = faces; r.nf = (int)F; r.count = face_count;
   r.K = cam->intrinsics; r.focal = cam->intrinsics ? nullptr : cam->focal_px; r.E = cam->extrinsics;
@@ -685,41 +677,38 @@ int op_render_mesh(md_device_t dev, const PointList& in, const int32_t* faces, i
   return scratch.finish(launch_render_mesh(r, scratch.p, entries, st));
 }
 
-int points_voxel_overflow(md_model_t m, int64_t* out) {
-  *out = 0;
-  md_model_s::PointsState* f = m->points;
-  if (!f || !f->vox_rows || !f->vtable.p) return MD_OK;
-  MD_HIP(hipSetDevice(m->dev->ordinal));
-  MD_HIP(hipDeviceSynchronize());  // the call may have run on any stream
-  int32_t flag = 0;
-  MD_HIP(hipMemcpy(&flag, voxel_flags(f->vtable.p, f->vox_rows), 4, hipMemcpyDeviceToHost));
-  *out = flag;
-  return MD_OK;
-}
+namespace {
 
-int points_decimate_overflow(md_model_t m, int64_t* out) {
+// The probe-loop flags the model's last call of a stage left in its table: the word at `a`, and with `b` whether either is set.
+// a null: the stage never ran, 0.
+int read_overflow(md_model_t m, const int32_t* a, const int32_t* b, int64_t* out) {
   *out = 0;
-  md_model_s::PointsState* f = m->points;
-  if (!f || !f->dec_views || !f->dtable.p) return MD_OK;
+  if (!a) return MD_OK;
   MD_HIP(hipSetDevice(m->dev->ordinal));
   MD_HIP(hipDeviceSynchronize());  // the call may have run on any stream
   int32_t flag[2] = {0, 0};
-  MD_HIP(hipMemcpy(&flag[0], voxel_flags(f->dtable.p, f->dec_rows), 4, hipMemcpyDeviceToHost));
-  MD_HIP(hipMemcpy(&flag[1], decimate_flags(f->dtable.p, f->dec_rows, f->dec_faces, f->dec_views), 4, hipMemcpyDeviceToHost));
-  *out = flag[0] || flag[1];
+  MD_HIP(hipMemcpy(&flag[0], a, 4, hipMemcpyDeviceToHost));
+  if (b) MD_HIP(hipMemcpy(&flag[1], b, 4, hipMemcpyDeviceToHost));
+  *out = b ? (flag[0] || flag[1]) : flag[0];
   return MD_OK;
 }
 
+}  // namespace
+
+int points_voxel_overflow(md_model_t m, int64_t* out) {
+  const md_model_s::PointsState* f = m->points;
+  return read_overflow(m, f && f->vox_rows && f->vtable.p ? voxel_flags(f->vtable.p, f->vox_rows) : nullptr, nullptr, out);
+}
+
 int points_outlier_overflow(md_model_t m, int64_t* out) {
-  *out = 0;
-  md_model_s::PointsState* f = m->points;
-  if (!f || !f->outl_rows || !f->otable.p) return MD_OK;
-  MD_HIP(hipSetDevice(m->dev->ordinal));
-  MD_HIP(hipDeviceSynchronize());  // the call may have run on any stream
-  int32_t flag = 0;
-  MD_HIP(hipMemcpy(&flag, outlier_flags(f->otable.p, f->outl_rows), 4, hipMemcpyDeviceToHost));
-  *out = flag;
-  return MD_OK;
+  const md_model_s::PointsState* f = m->points;
+  return read_overflow(m, f && f->outl_rows && f->otable.p ? outlier_flags(f->otable.p, f->outl_rows) : nullptr, nullptr, out);
+}
+
+int points_decimate_overflow(md_model_t m, int64_t* out) {
+  const md_model_s::PointsState* f = m->points;
+  if (!f || !f->dec_views || !f->dtable.p) return read_overflow(m, nullptr, nullptr, out);
+  return read_overflow(m, voxel_flags(f->dtable.p, f->dec_rows), decimate_flags(f->dtable.p, f->dec_rows, f->dec_faces, f->dec_views), out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -727,191 +716,177 @@ int points_outlier_overflow(md_model_t m, int64_t* out) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct OutSlot {  // a host output's way back: `rows` rows of `row_bytes` from its device home to the caller
+// A list's rows on the device: what one list stage writes and the next one, or the caller, reads.
+struct ListRows {
+  float* xyz = nullptr;
+  float* conf = nullptr;
+  uint8_t* rgb = nullptr;
+  float* normals = nullptr;
+  int32_t* count = nullptr;  // [B + 1]
+};
+
+// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too) and OutlierParams
+template <typename P>
+void reads(P& p, const ListRows& l) { p.xyz = l.xyz; p.conf = l.conf; p.rgb = l.rgb; p.normals = l.normals; p.in_count = l.count; }
+template <typename P>
+void writes(P& p, const ListRows& l) { p.xyz_out = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; p.normals_out = l.normals; p.count = l.count; }
+
+struct OutSlot {  // a host output's way back: rows of `row_bytes` from its device home to the caller
   void* caller;
   const void* home;
   size_t row_bytes, rows;
-  int list;  // 0: it travels whole. 1: a list output: it travels once `count` is known, and only the rows that hold points.
-             // 2: the faces: likewise with `face_count` and `face_capacity`
-             // 3: rows parallel to the unfiltered list (outl->neighbours): likewise with its device count
-             // 4: the decimated faces: as 2 with dec's `face_count` and `face_capacity`
-             // 5: the faces of the kept components: as 2 with comp's `face_count` and `face_capacity`
+  const int32_t* live;  // null: all `rows` travel, with the dense maps and the counts. Else the host word that holds the live
+                        // rows once those have arrived (a count's last word): min(*live, rows) rows travel behind them
 };
 
-// What the stages of one call share: its device pointers, resolved by plan_homes, stage_inputs and run_model.
+// What the stages of one call share: its device pointers, resolved by plan_homes, stage_inputs and run_model. It lives in
+// points_eager and is never copied: a slot may point at `unfiltered`.
 struct PointsPlan {
-  hipStream_t st;
-  bool dual, thin, mesh, filt, deci, comp;
-  size_t npx;
+  hipStream_t st = nullptr;
+  bool dual = false;
+  bool thin = false, mesh = false, filt = false, deci = false, comp = false, smo = false;  // the stages that are on
+  bool own_faces = false;  // deci / comp / smo: a later stage reads the faces, so the mesh stage writes the model's own (`gd`)
+  size_t npx = 0;
+  long rows = 0;  // rows the unthinned list of the call can have (list_rows); its mesh has at most 2 * rows faces
   float *depth = nullptr, *raw = nullptr, *conf = nullptr;  // depth: what is unprojected; raw: what the model writes
   const float* x = nullptr;                                 // the image on the device
+  ListRows fin;     // the list the call ends with: the caller's pointers or their host-output homes (place_outputs). plan_homes
+                    // hands it to the last stage that writes a list; the rendering and the rasterising read it
+  const int32_t* faces = nullptr;       // mesh: the faces the call ends with, which the rasterising reads: the mesh stage's,
+  const int32_t* face_count = nullptr;  // the decimated or those of the kept components (the caller's pointers or their homes)
+  long face_capacity = 0;
   PointsParams p;   // launch_unproject's; the device inputs gather in p.rgb / K / E / focal (all kept until run_unproject)
   NormalsParams q;
-  VoxelParams v;    // thin: launch_voxel_thin's, from the model's own list that `p` then fills to the list outputs of the call
-  OutlierParams u;  // filt: launch_radius_outliers', from the model's own list that `p` then fills to the list outputs of the call,
-                    // or with thin to the second list of the model that `v` then reads
-  RenderParams r;   // c.rnd given: launch_render_points', from the list outputs of the call
+  VoxelParams v;    // thin: launch_voxel_thin's
+  OutlierParams u;  // filt: launch_radius_outliers'
+  RenderParams r;   // c.rnd given: launch_render_points', from `fin`
   MeshParams g;     // mesh: launch_mesh's, from the depth that is unprojected and the scratch of `p`'s launches
-  RasterParams s;   // c.rst given: launch_render_mesh's, from the list outputs and the faces of the call
-  DecimateParams d; // deci: launch_decimate_mesh's, from the model's own list and the faces `gd` wrote; d.v fills the list outputs of the call
-  MeshParams gd;    // deci / comp: the mesh stage's second set of face outputs, the model's own, complete and with the true count
+  RasterParams s;   // c.rst given: launch_render_mesh's, from `fin` and `faces`
+  DecimateParams d; // deci: launch_decimate_mesh's, from the model's own list and the faces `gd` wrote
+  MeshParams gd;    // own_faces: the mesh stage's second set of face outputs, the model's own, complete and with the true count
   ComponentsParams k;  // comp: launch_mesh_components', from the list's count and the faces `gd` wrote
-  bool smo = false;    // the smoothing is on
-  SmoothParams sm;     // smo: launch_smooth_mesh's, from the list outputs of the call and the faces of `k`, or else those `gd` wrote
-  int queue = 0;    // its queue entries: what skeys was sized for
+  SmoothParams sm;     // smo: launch_smooth_mesh's, from `fin` and the faces of `k`, or else those `gd` wrote
+  int queue = 0;    // the raster's queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
+  int32_t unfiltered = 0;  // filt with host outputs: the rows of the unfiltered list, read back for outl->neighbours' slot
   std::vector<OutSlot> slots;
 };
 
 bool views_on(const PointsCall& c) { return c.fo && c.fo->view_rtol > 0.f; }
 
-// place_outputs with the decimation on (no thinning, no outlier removal): the list rows name d.v's outputs, the caller's mesh
-// outputs name `g`'s as ever, and dec's own follow
-size_t place_outputs_decimated(const PointsCall& c, PointsPlan& pl, char* base) {
-  const md_points_outputs& out = *c.out;
-  const md_points_decimate& dec = *c.dec;
-  VoxelParams& v = pl.d.v;
-  const bool host = c.out_kind == MD_MEM_HOST;
-  const size_t cap = (size_t)out.capacity, fcap = (size_t)dec.face_capacity;
-  float* const no_f = nullptr;
-  size_t total = 0;
-  pl.slots.clear();
-  auto slot = [&](auto* caller, auto*& param, size_t row_bytes, size_t rows, int list) {
-    param = caller;
-    if (!caller || !host) return;
-    if (base) {
-      param = (decltype(caller))(base + total);
-      pl.slots.push_back(OutSlot{caller, param, row_bytes, rows, list});
-    }
-    total += align_up(row_bytes * rows, 256);
-  };
-  slot(out.point_map, pl.p.point_map, 12, pl.npx, 0);
-  slot(out.mask, pl.p.mask, 1, pl.npx, 0);
-  slot(c.nrm ? c.nrm->normal_map : no_f, pl.q.normal_map, 12, pl.npx, 0);
-  slot(out.count, v.count, 4, (size_t)c.B + 1, 0);
-  slot(dec.dropped, v.dropped, 4, 1, 0);
-  slot(dec.face_count, pl.d.face_count, 4, (size_t)c.B + 1, 0);
-  slot(dec.faces_dropped, pl.d.faces_dropped, 4, 3, 0);
-  slot(dec.remap, pl.d.remap, 4, (size_t)list_rows(c.B, c.H, c.W, c.o->stride), 0);
-  slot(out.xyz, v.xyz_out, 12, cap, 1);
-  slot(out.rgb, v.rgb_out, 3, cap, 1);
-  slot(out.conf, v.conf_out, 4, cap, 1);
-  slot(c.nrm ? c.nrm->normals : no_f, v.normals_out, 12, cap, 1);
-  slot(dec.index, v.index, 4, cap, 1);
-  slot(dec.weight, v.weight, 4, cap, 1);
-  slot(dec.faces, pl.d.faces_out, 12, fcap, 4);
-  slot(dec.face_index, pl.d.face_index, 4, fcap, 4);
-  if (c.rnd) {
-    RenderParams& r = pl.r;
-    const size_t rpx = (size_t)r.T * r.H * r.W;
-    slot(c.rnd->out.depth, r.depth, 4, rpx, 0);
-    slot(c.rnd->out.index, r.index, 4, rpx, 0);
-    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, 0);
-    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, 0);
-  }
-  if (c.rst) {
-    RasterParams& s = pl.s;
-    const size_t spx = (size_t)s.T * s.H * s.W;
-    slot(c.rst->out.depth, s.depth, 4, spx, 0);
-    slot(c.rst->out.face, s.face, 4, spx, 0);
-    slot(c.rst->out.rgb, s.rgb_out, 3, spx, 0);
-    slot(c.rst->out.filled, s.filled, 4, (size_t)s.T + 1, 0);
-    slot(c.rst->out.skipped, s.skipped, 4, (size_t)s.T + 1, 0);
-  }
-  slot(c.mesh->pixel_index, pl.pix, 4, pl.npx, 0);
-  slot(c.mesh->face_count, pl.g.face_count, 4, (size_t)c.B + 1, 0);
-  slot(c.mesh->faces, pl.g.faces, 12, (size_t)c.mesh->face_capacity, 2);
-  return total;
-}
-
 // The outputs a caller may hold in host memory, in the order they travel: the dense maps and the counts, then the list. Device
 // outputs: the kernel parameter takes the caller's pointer. Host outputs: it takes a home inside `base` (PointsState::out, at
 // 256-byte steps) and a slot records the way back; base null = the sizes only, so plan_homes runs the table twice around the
-// grow. A row's second argument is the parameter itself, by reference: with thinning the list rows name launch_voxel_thin's
-// outputs (`thin ? v.x : p.x` picks one of two lvalues), since the scatter then fills the model's own list. -> bytes of the homes
+// grow. A row's second argument is the parameter itself, by reference. The list rows name `fin`, whichever stage writes it; a
+// stage's own outputs follow under its flag. -> bytes of the homes
 size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   const md_points_outputs& out = *c.out;
-  PointsParams& p = pl.p;
-  NormalsParams& q = pl.q;
-  VoxelParams& v = pl.v;
-  OutlierParams& u = pl.u;
-  if (pl.deci) return place_outputs_decimated(c, pl, base);
-  const bool host = c.out_kind == MD_MEM_HOST, thin = pl.thin, filt = pl.filt;
-  const size_t cap = (size_t)out.capacity;
+  const bool host = c.out_kind == MD_MEM_HOST;
+  const size_t cap = (size_t)out.capacity, views = (size_t)c.B + 1, list = (size_t)pl.rows;
   float* const no_f = nullptr;
-  int32_t* const no_i = nullptr;
+  auto total_of = [&](const int32_t* count) { return count ? count + c.B : nullptr; };  // the live rows of all views
+  const int32_t* const n = total_of(out.count);
   size_t total = 0;
   pl.slots.clear();
-  auto slot = [&](auto* caller, auto*& param, size_t row_bytes, size_t rows, int list) {
+  auto slot = [&](auto* caller, auto*& param, size_t row_bytes, size_t rows, const int32_t* live = nullptr) {
     param = caller;
     if (!caller || !host) return;
     if (base) {
       param = (decltype(caller))(base + total);
-      pl.slots.push_back(OutSlot{caller, param, row_bytes, rows, list});
+      pl.slots.push_back(OutSlot{caller, param, row_bytes, rows, live});
     }
     total += align_up(row_bytes * rows, 256);
   };
-  slot(out.point_map, p.point_map, 12, pl.npx, 0);
-  slot(out.mask, p.mask, 1, pl.npx, 0);
-  slot(c.nrm ? c.nrm->normal_map : no_f, q.normal_map, 12, pl.npx, 0);
-  // the list rows name the outputs of the last stage that writes a list: the thinning, else the outlier removal, else the scatter
-  slot(out.count, thin ? v.count : filt ? u.count : p.count, 4, (size_t)c.B + 1, 0);
-  slot(thin ? c.vox->dropped : no_i, v.dropped, 4, 1, 0);
-  slot(filt ? c.outl->dropped : no_i, u.dropped, 4, 1, 0);
-  slot(out.xyz, thin ? v.xyz_out : filt ? u.xyz_out : p.xyz, 12, cap, 1);
-  slot(out.rgb, thin ? v.rgb_out : filt ? u.rgb_out : p.rgb_out, 3, cap, 1);
-  slot(out.conf, thin ? v.conf_out : filt ? u.conf_out : p.conf_out, 4, cap, 1);
-  slot(c.nrm ? c.nrm->normals : no_f, thin ? v.normals_out : filt ? u.normals_out : q.normals, 12, cap, 1);
-  slot(thin ? c.vox->index : no_i, v.index, 4, cap, 1);
-  slot(thin ? c.vox->weight : no_i, v.weight, 4, cap, 1);
-  slot(filt && !thin ? c.outl->index : no_i, u.index, 4, cap, 1);
-  slot(filt ? c.outl->neighbours : no_i, u.neighbours, 4, (size_t)list_rows(c.B, c.H, c.W, c.o->stride), 3);
+  slot(out.point_map, pl.p.point_map, 12, pl.npx);
+  slot(out.mask, pl.p.mask, 1, pl.npx);
+  slot(c.nrm ? c.nrm->normal_map : no_f, pl.q.normal_map, 12, pl.npx);
+  slot(out.count, pl.fin.count, 4, views);
+  if (pl.thin) slot(c.vox->dropped, pl.v.dropped, 4, 1);
+  if (pl.filt) slot(c.outl->dropped, pl.u.dropped, 4, 1);
+  if (pl.deci) {
+    slot(c.dec->dropped, pl.d.v.dropped, 4, 1);
+    slot(c.dec->face_count, pl.d.face_count, 4, views);
+    slot(c.dec->faces_dropped, pl.d.faces_dropped, 4, 3);
+    slot(c.dec->remap, pl.d.remap, 4, list);
+  }
+  slot(out.xyz, pl.fin.xyz, 12, cap, n);
+  slot(out.rgb, pl.fin.rgb, 3, cap, n);
+  slot(out.conf, pl.fin.conf, 4, cap, n);
+  slot(c.nrm ? c.nrm->normals : no_f, pl.fin.normals, 12, cap, n);
+  if (pl.thin) {
+    slot(c.vox->index, pl.v.index, 4, cap, n);
+    slot(c.vox->weight, pl.v.weight, 4, cap, n);
+  }
+  if (pl.filt) {  // index: rows parallel to the filtered list, which the thinning replaces; neighbours: to the unfiltered one
+    if (!pl.thin) slot(c.outl->index, pl.u.index, 4, cap, n);
+    slot(c.outl->neighbours, pl.u.neighbours, 4, list, &pl.unfiltered);
+  }
+  if (pl.deci) {
+    const size_t fcap = (size_t)c.dec->face_capacity;
+    slot(c.dec->index, pl.d.v.index, 4, cap, n);
+    slot(c.dec->weight, pl.d.v.weight, 4, cap, n);
+    slot(c.dec->faces, pl.d.faces_out, 12, fcap, total_of(c.dec->face_count));
+    slot(c.dec->face_index, pl.d.face_index, 4, fcap, total_of(c.dec->face_count));
+  }
   if (c.rnd) {  // rendered images are dense outputs: they travel whole
     RenderParams& r = pl.r;
     const size_t rpx = (size_t)r.T * r.H * r.W;
-    slot(c.rnd->out.depth, r.depth, 4, rpx, 0);
-    slot(c.rnd->out.index, r.index, 4, rpx, 0);
-    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx, 0);
-    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1, 0);
+    slot(c.rnd->out.depth, r.depth, 4, rpx);
+    slot(c.rnd->out.index, r.index, 4, rpx);
+    slot(c.rnd->out.rgb, r.rgb_out, 3, rpx);
+    slot(c.rnd->out.filled, r.filled, 4, (size_t)r.T + 1);
   }
   if (c.rst) {  // as the rendered images
     RasterParams& s = pl.s;
     const size_t spx = (size_t)s.T * s.H * s.W;
-    slot(c.rst->out.depth, s.depth, 4, spx, 0);
-    slot(c.rst->out.face, s.face, 4, spx, 0);
-    slot(c.rst->out.rgb, s.rgb_out, 3, spx, 0);
-    slot(c.rst->out.filled, s.filled, 4, (size_t)s.T + 1, 0);
-    slot(c.rst->out.skipped, s.skipped, 4, (size_t)s.T + 1, 0);
+    slot(c.rst->out.depth, s.depth, 4, spx);
+    slot(c.rst->out.face, s.face, 4, spx);
+    slot(c.rst->out.rgb, s.rgb_out, 3, spx);
+    slot(c.rst->out.filled, s.filled, 4, (size_t)s.T + 1);
+    slot(c.rst->out.skipped, s.skipped, 4, (size_t)s.T + 1);
   }
   if (pl.mesh) {
-    slot(c.mesh->pixel_index, pl.pix, 4, pl.npx, 0);
-    slot(c.mesh->face_count, pl.g.face_count, 4, (size_t)c.B + 1, 0);
-    slot(c.mesh->faces, pl.g.faces, 12, (size_t)c.mesh->face_capacity, 2);
+    slot(c.mesh->pixel_index, pl.pix, 4, pl.npx);
+    slot(c.mesh->face_count, pl.g.face_count, 4, views);
+    slot(c.mesh->faces, pl.g.faces, 12, (size_t)c.mesh->face_capacity, total_of(c.mesh->face_count));
   }
   if (pl.comp) {
     const md_points_components& k = *c.comp;
-    const size_t rows = (size_t)list_rows(c.B, c.H, c.W, c.o->stride);
-    slot(k.label, pl.k.label, 4, rows, 0);
-    slot(k.component_faces, pl.k.component_faces, 4, rows, 0);
-    slot(k.face_count, pl.k.face_count, 4, (size_t)c.B + 1, 0);
-    slot(k.stats, pl.k.stats, 4, 5, 0);
-    slot(k.faces, pl.k.faces_out, 12, (size_t)k.face_capacity, 5);
-    slot(k.face_index, pl.k.face_index, 4, (size_t)k.face_capacity, 5);
+    slot(k.label, pl.k.label, 4, list);
+    slot(k.component_faces, pl.k.component_faces, 4, list);
+    slot(k.face_count, pl.k.face_count, 4, views);
+    slot(k.stats, pl.k.stats, 4, 5);
+    slot(k.faces, pl.k.faces_out, 12, (size_t)k.face_capacity, total_of(k.face_count));
+    slot(k.face_index, pl.k.face_index, 4, (size_t)k.face_capacity, total_of(k.face_count));
   }
   if (pl.smo) {  // rows parallel to the list: they travel as its rows do
-    slot(c.smooth->xyz, pl.sm.xyz_out, 12, cap, 1);
-    slot(c.smooth->normals, pl.sm.normals_out, 12, cap, 1);
-    slot(c.smooth->stats, pl.sm.stats, 4, 5, 0);
+    slot(c.smooth->xyz, pl.sm.xyz_out, 12, cap, n);
+    slot(c.smooth->normals, pl.sm.normals_out, 12, cap, n);
+    slot(c.smooth->stats, pl.sm.stats, 4, 5);
   }
   return total;
 }
 
-// Device homes, grow-only and before anything is enqueued: the maps, the cameras, the scratch, the host outputs, the unthinned list.
+// The model's face home, carved from dfaces: every face the mesh of the unthinned list can have [2 rows,3] and their counts
+// [B + 1]. `gd` is `g` writing there.
+int carve_faces(md_model_s* m, PointsPlan& pl, int B) {
+  md_model_s::PointsState* f = m->points;
+  const long nf = 2 * pl.rows;
+  const size_t b_faces = align_up((size_t)nf * 12, 256);
+  MD_TRY(grow(m, pl.st, f->dfaces, b_faces + align_up((size_t)(B + 1) * 4, 256)));
+  pl.gd = pl.g;
+  pl.gd.faces = (int32_t*)f->dfaces.p; pl.gd.face_count = (int32_t*)((char*)f->dfaces.p + b_faces); pl.gd.face_capacity = nf;
+  return MD_OK;
+}
+
+// Device homes, grow-only, in a fixed order and before anything is enqueued: the maps, the cameras, the scratch, the host
+// outputs, the model's own lists and faces. Then the wiring of the list stages.
 int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   md_model_s::PointsState* f = m->points;
   hipStream_t st = pl.st;
   const md_points_outputs& out = *c.out;
-  const int B = c.B, H = c.H, W = c.W;
+  const int B = c.B, H = c.H, W = c.W, stride = c.o->stride;
+  const long rows = pl.rows, nf = 2 * rows;
   pl.depth = out.depth;
   if (!pl.depth || c.out_kind == MD_MEM_HOST) {
     MD_TRY(grow(m, st, f->depth, pl.npx * 4));
@@ -948,39 +923,43 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.deci = decimate_on(c.dec);
   pl.comp = components_on(c.comp);
   pl.smo = smooth_on(c.smooth);
-  pl.mesh = mesh_on(c.mesh) || pl.deci || pl.comp || pl.smo;
-  if (pl.comp || pl.smo) {  // the caller's list as ever (a corner is usable below its capacity); the map always has a home
-    pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
-    MD_TRY(grow(m, st, f->mesh, mesh_scratch_bytes(B, H, W, c.o->stride) + align_up(pl.npx * 4, 256)));
-  } else if (pl.deci) {  // the faces name rows of the model's own, unthinned list: every row of it is usable; the map always has a home
-    const long rows = list_rows(B, H, W, c.o->stride);
-    pl.g = make_mesh(B, H, W, c.o->stride, rows, *c.mesh);
-    MD_TRY(grow(m, st, f->mesh, mesh_scratch_bytes(B, H, W, c.o->stride) + align_up(pl.npx * 4, 256)));
-  } else if (pl.mesh) {
-    pl.g = make_mesh(B, H, W, c.o->stride, (long)out.capacity, *c.mesh);
-    if (const size_t bytes = mesh_home_bytes(*c.mesh, B, H, W, c.o->stride)) MD_TRY(grow(m, st, f->mesh, bytes));
+  pl.own_faces = pl.deci || pl.comp || pl.smo;
+  pl.mesh = mesh_on(c.mesh) || pl.own_faces;
+  if (pl.mesh) {
+    // a corner is usable below the capacity of the list the faces name: the caller's, or with the decimation the model's own,
+    // unthinned, of which every row is. Faces that a later stage reads: the map always has a home
+    pl.g = make_mesh(B, H, W, stride, pl.deci ? rows : (long)out.capacity, *c.mesh);
+    const size_t bytes = pl.own_faces ? mesh_scratch_bytes(B, H, W, stride) + align_up(pl.npx * 4, 256) : mesh_home_bytes(*c.mesh, B, H, W, stride);
+    if (bytes) MD_TRY(grow(m, st, f->mesh, bytes));
   }
   if (const size_t total = place_outputs(c, pl, nullptr)) {
     MD_TRY(grow(m, st, f->out, total));
     place_outputs(c, pl, (char*)f->out.p);
   }
+  if (pl.mesh) {  // the faces the call ends with: those of the kept components, the decimated ones, else the mesh stage's
+    auto ends_with = [&](const int32_t* faces, const int32_t* count, int64_t capacity) {
+      pl.faces = faces; pl.face_count = count; pl.face_capacity = (long)capacity;
+    };
+    if (pl.comp) ends_with(pl.k.faces_out, pl.k.face_count, c.comp->face_capacity);
+    else if (pl.deci) ends_with(pl.d.faces_out, pl.d.face_count, c.dec->face_capacity);
+    else ends_with(pl.g.faces, pl.g.face_count, c.mesh->face_capacity);
+  }
+  const bool own_list = pl.thin || pl.filt || pl.deci;  // the scatter fills a list of the model's own: a later stage writes `fin`
+  auto scatter_to = [&](const ListRows& l) { p.xyz = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; pl.q.normals = l.normals; p.count = l.count; };
+  if (!own_list) scatter_to(pl.fin);
   if (pl.comp || pl.smo) {  // all faces of the call's list go to the model's face home; the stages read them and the list's device count
-    const long rows = list_rows(B, H, W, c.o->stride), nf = 2 * rows;
-    const size_t b_faces = align_up((size_t)nf * 12, 256);
-    MD_TRY(grow(m, st, f->dfaces, b_faces + align_up((size_t)(B + 1) * 4, 256)));
-    pl.gd = pl.g;
-    pl.gd.faces = (int32_t*)f->dfaces.p; pl.gd.face_count = (int32_t*)((char*)f->dfaces.p + b_faces); pl.gd.face_capacity = nf;
+    MD_TRY(carve_faces(m, pl, B));
     if (pl.comp) {
       ComponentsParams& k = pl.k;
       MD_TRY(grow(m, st, f->ctable, components_scratch_bytes((int)rows, (int)nf, B)));
-      k.v.in_count = p.count; k.v.n = (int)rows; k.v.B = B;
+      k.v.in_count = pl.fin.count; k.v.n = (int)rows; k.v.B = B;
       k.faces = pl.gd.faces; k.in_face_count = pl.gd.face_count; k.nf = (int)nf;
       k.min_faces = c.comp->min_faces; k.face_capacity = (long)c.comp->face_capacity;
     }
     if (pl.smo) {  // the rows of the call's list below its capacity; the faces the rasteriser reads
       SmoothParams& sm = pl.sm;
       const md_points_smooth& o = *c.smooth;
-      sm.xyz = p.xyz; sm.in_count = p.count; sm.B = B; sm.n = (int)std::min<long>((long)out.capacity, rows);
+      sm.xyz = pl.fin.xyz; sm.in_count = pl.fin.count; sm.B = B; sm.n = (int)std::min<long>((long)out.capacity, rows);
       sm.faces = pl.comp ? pl.k.faces_out : pl.gd.faces; sm.in_face_count = pl.comp ? pl.k.face_count : pl.gd.face_count;
       sm.nf = (int)(pl.comp ? std::min<long>((long)c.comp->face_capacity, nf) : nf);
       sm.step = o.step; sm.lambda = o.lambda; sm.mu = o.mu; sm.iterations = o.iterations; sm.pin_boundary = o.pin_boundary;
@@ -988,51 +967,45 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
       MD_TRY(grow(m, st, f->stable, smooth_scratch_bytes(sm.n)));
     }
   }
-  if (!pl.thin && !pl.filt && !pl.deci) return MD_OK;
-  // voxel thinning / outlier removal: the scatter fills the model's own list, the last of the two writes where the list would
-  // have gone; with both, the outlier removal writes a second list of the model that the thinning reads
-  VoxelParams& v = pl.v;
-  OutlierParams& u = pl.u;
+  if (!own_list) return MD_OK;
   const bool want_rgb = out.rgb != nullptr, want_nrm = c.nrm && c.nrm->normals;
-  const long rows = list_rows(B, H, W, c.o->stride);
   const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = pl.dual ? align_up((size_t)rows * 4, 256) : 0;
   const size_t b_rgb = want_rgb ? align_up((size_t)rows * 3, 256) : 0, b_nrm = want_nrm ? b_xyz : 0;
   const size_t b_list = b_xyz + b_conf + b_rgb + b_nrm + align_up((size_t)(B + 1) * 4, 256);
-  struct Rows { float* xyz; float* conf; uint8_t* rgb; float* normals; int32_t* count; };
   auto rows_of = [&](void* home) {  // the rank reads the confidence whether or not the caller takes it
     char* base = (char*)home;
-    return Rows{(float*)base, pl.dual ? (float*)(base + b_xyz) : nullptr, want_rgb ? (uint8_t*)(base + b_xyz + b_conf) : nullptr,
-                want_nrm ? (float*)(base + b_xyz + b_conf + b_rgb) : nullptr, (int32_t*)(base + b_xyz + b_conf + b_rgb + b_nrm)};
+    return ListRows{(float*)base, pl.dual ? (float*)(base + b_xyz) : nullptr, want_rgb ? (uint8_t*)(base + b_xyz + b_conf) : nullptr,
+                    want_nrm ? (float*)(base + b_xyz + b_conf + b_rgb) : nullptr, (int32_t*)(base + b_xyz + b_conf + b_rgb + b_nrm)};
   };
   MD_TRY(grow(m, st, f->vlist, b_list));
   if (pl.thin) MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
   if (pl.filt) MD_TRY(grow(m, st, f->otable, outlier_scratch_bytes((int)rows)));
   if (pl.filt && pl.thin) MD_TRY(grow(m, st, f->flist, b_list));
-  Rows l = rows_of(f->vlist.p);
-  p.xyz = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; pl.q.normals = l.normals; p.count = l.count;
+  // The chain scatter -> outlier removal -> voxel thinning, or scatter -> decimation (the decimation is the thinning, with the
+  // faces of the model's face home): every stage but the last writes a list of the model's own, of which every row is usable;
+  // the last one writes `fin` below the caller's capacity. Nothing else knows which stage that is.
+  ListRows l = rows_of(f->vlist.p);
+  scatter_to(l);
   p.capacity = rows;
   if (pl.filt) {
-    u.xyz = l.xyz; u.conf = l.conf; u.rgb = l.rgb; u.normals = l.normals; u.in_count = l.count;
-    u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = out.capacity;
-    if (pl.thin) {
-      l = rows_of(f->flist.p);
-      u.xyz_out = l.xyz; u.conf_out = l.conf; u.rgb_out = l.rgb; u.normals_out = l.normals; u.count = l.count;
-      u.capacity = rows;
-    }
+    OutlierParams& u = pl.u;
+    reads(u, l);
+    if (pl.thin) l = rows_of(f->flist.p);
+    writes(u, pl.thin ? l : pl.fin);
+    u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = pl.thin ? rows : (long)out.capacity;
   }
   if (pl.thin) {
-    v.xyz = l.xyz; v.conf = l.conf; v.rgb = l.rgb; v.normals = l.normals; v.in_count = l.count;
+    VoxelParams& v = pl.v;
+    reads(v, l);
+    writes(v, pl.fin);
     v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = out.capacity;
   }
-  if (pl.deci) {  // the decimation is the thinning: d.v reads the model's list as `v` would, the faces come from the model's face home
+  if (pl.deci) {
     DecimateParams& d = pl.d;
-    const long nf = 2 * rows;
-    const size_t b_faces = align_up((size_t)nf * 12, 256);
-    MD_TRY(grow(m, st, f->dfaces, b_faces + align_up((size_t)(B + 1) * 4, 256)));
+    MD_TRY(carve_faces(m, pl, B));
     MD_TRY(grow(m, st, f->dtable, decimate_scratch_bytes((int)rows, (int)nf, B)));
-    pl.gd = pl.g;
-    pl.gd.faces = (int32_t*)f->dfaces.p; pl.gd.face_count = (int32_t*)((char*)f->dfaces.p + b_faces); pl.gd.face_capacity = nf;
-    d.v.xyz = l.xyz; d.v.conf = l.conf; d.v.rgb = l.rgb; d.v.normals = l.normals; d.v.in_count = l.count;
+    reads(d.v, l);
+    writes(d.v, pl.fin);
     d.v.n = (int)rows; d.v.B = B; d.v.voxel = c.dec->voxel; d.v.capacity = out.capacity;
     d.faces = pl.gd.faces; d.in_face_count = pl.gd.face_count; d.nf = (int)nf; d.face_capacity = (long)c.dec->face_capacity;
   }
@@ -1121,9 +1094,9 @@ int run_unproject(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
 // The mesh of the list: needs the scratch of run_unproject's launches before anything reuses it.
 int run_mesh(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.g.depth = pl.depth;
-  if (pl.deci || pl.comp || pl.smo) {  // the map, then the model's own faces, complete, for the decimation / the components / the smoothing; the caller's,
-                             // if it takes them, are a copy: both have the same rows of the list as usable corners, so they are
-                             // the same faces
+  if (pl.own_faces) {  // the map, then the model's own faces, complete, for the decimation / the components / the smoothing; the
+                       // caller's, if it takes them, are a copy: both have the same rows of the list as usable corners, so
+                       // they are the same faces
     void* home = m->points->mesh.p;
     int32_t* pix = pl.pix ? pl.pix : (int32_t*)((char*)home + mesh_scratch_bytes(c.B, c.H, c.W, c.o->stride));
     MD_TRY(launch_mesh_index(c.B, c.H, c.W, m->points->scratch.p, pix, pl.st));
@@ -1161,44 +1134,29 @@ int run_components(md_model_s* m, const PointsCall&, PointsPlan& pl) { return la
 // Smoothing: the list of the call and the faces the rasteriser reads -> smooth's outputs. The list is not touched.
 int run_smooth(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_smooth_mesh(pl.sm, m->points->stable.p, pl.st); }
 
-// Rendering: the list outputs of the call, thinned or not, and their device count -> the target images.
+// Rendering: the list the call ends with and its device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
-  const PointsParams& p = pl.p;
-  const VoxelParams& v = pl.v;
-  const OutlierParams& u = pl.u;
-  r.xyz = pl.deci ? pl.d.v.xyz_out : pl.thin ? v.xyz_out : pl.filt ? u.xyz_out : p.xyz;
-  r.rgb = pl.deci ? pl.d.v.rgb_out : pl.thin ? v.rgb_out : pl.filt ? u.rgb_out : p.rgb_out;
-  r.count = (pl.deci ? pl.d.v.count : pl.thin ? v.count : pl.filt ? u.count : p.count) + c.B;
-  r.n = (int)std::min<long>((long)c.out->capacity, list_rows(c.B, c.H, c.W, c.o->stride));
+  r.xyz = pl.fin.xyz; r.rgb = pl.fin.rgb; r.count = pl.fin.count + c.B;
+  r.n = (int)std::min<long>((long)c.out->capacity, pl.rows);
   return launch_render_points(r, m->points->rkeys.p, pl.st);
 }
 
-// Rasterising: the list outputs of the call as vertices, the faces of its mesh stage and their device count -> the target images.
-// The rows beyond min(count[B], capacity) are never named: the mesh stage emits no face with a corner at or above `capacity`.
+// Rasterising: the list the call ends with as vertices (smoothed: the smoothed rows of the same list), the faces it ends with
+// and their device count -> the target images. The rows beyond min(count[B], capacity) are never named: neither the mesh stage
+// nor the decimation emits a face with a corner at or above `capacity`.
 int run_raster(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RasterParams& s = pl.s;
-  s.xyz = pl.p.xyz;
-  s.rgb = pl.p.rgb_out;
-  s.n = (int)std::min<long>((long)c.out->capacity, list_rows(c.B, c.H, c.W, c.o->stride));
-  s.faces = pl.g.faces;
-  s.count = pl.g.face_count + c.B;
-  s.nf = (int)std::min<long>((long)c.mesh->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
-  if (pl.deci) {  // the decimated list and the decimated faces: no kept face names a row at or above `capacity`
-    s.xyz = pl.d.v.xyz_out; s.rgb = pl.d.v.rgb_out; s.faces = pl.d.faces_out; s.count = pl.d.face_count + c.B;
-    s.nf = (int)std::min<long>((long)c.dec->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
-  }
-  if (pl.comp) {  // the list as ever, the faces of the kept components
-    s.faces = pl.k.faces_out; s.count = pl.k.face_count + c.B;
-    s.nf = (int)std::min<long>((long)c.comp->face_capacity, 2 * list_rows(c.B, c.H, c.W, c.o->stride));
-  }
-  if (pl.smo) s.xyz = pl.sm.xyz_out;  // the smoothed rows of the same list
+  s.xyz = pl.smo ? pl.sm.xyz_out : pl.fin.xyz; s.rgb = pl.fin.rgb;
+  s.n = (int)std::min<long>((long)c.out->capacity, pl.rows);
+  s.faces = pl.faces; s.count = pl.face_count + c.B;
+  s.nf = (int)std::min<long>(pl.face_capacity, 2 * pl.rows);
   return launch_render_mesh(s, m->points->skeys.p, pl.queue, pl.st);
 }
 
 // Host outputs, complete when the call returns: the depth, the dense maps and the counts first, then, once `count` is known,
-// only the list rows that hold points: the caller's memory beyond them stays as it was.
-int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
+// only the live rows of each list output: the caller's memory beyond them stays as it was.
+int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (c.out_kind != MD_MEM_HOST) return MD_OK;
   auto d2h = [&](void* dst, const void* src, size_t bytes) -> int {
     if (dst && bytes) MD_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, pl.st));
@@ -1206,32 +1164,29 @@ int copy_outputs(md_model_s* m, const PointsCall& c, const PointsPlan& pl) {
   };
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
-    if (s.list == 0) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
-  int32_t overflow = 0, outl_overflow = 0, unfiltered = 0, dec_overflow[2] = {0, 0};
+    if (!s.live) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
+  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0};
   if (pl.deci) MD_TRY(d2h(&dec_overflow[0], voxel_flags(m->points->dtable.p, pl.d.v.n), 4));
   if (pl.deci) MD_TRY(d2h(&dec_overflow[1], decimate_flags(m->points->dtable.p, pl.d.v.n, pl.d.nf, pl.d.v.B), 4));
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
   if (pl.filt) MD_TRY(d2h(&outl_overflow, outlier_flags(m->points->otable.p, pl.u.n), 4));
-  if (pl.filt) MD_TRY(d2h(&unfiltered, pl.u.in_count + c.B, 4));
+  if (pl.filt) MD_TRY(d2h(&pl.unfiltered, pl.u.in_count + c.B, 4));
   MD_HIP(hipStreamSynchronize(pl.st));
-  if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "decimation: a probe loop ran out of table slots");
-  if (outl_overflow) MD_FAIL(MD_ERR_HIP, "outlier removal: a probe loop ran out of table slots");
-  if (overflow) MD_FAIL(MD_ERR_HIP, "voxel thinning: the probe loop ran out of table slots");
-  if (!c.out->count) return MD_OK;
-  const size_t n = std::min((size_t)c.out->count[c.B], (size_t)c.out->capacity);
-  const size_t nf = pl.mesh && c.mesh->faces ? std::min((size_t)c.mesh->face_count[c.B], (size_t)c.mesh->face_capacity) : 0;
-  const size_t nd = pl.deci && c.dec->face_count ? std::min((size_t)c.dec->face_count[c.B], (size_t)c.dec->face_capacity) : 0;
-  const size_t nk = pl.comp && c.comp->face_count ? std::min((size_t)c.comp->face_count[c.B], (size_t)c.comp->face_capacity) : 0;
+  if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "%s", kDecimateRanOut);
+  if (outl_overflow) MD_FAIL(MD_ERR_HIP, "%s", kOutlierRanOut);
+  if (overflow) MD_FAIL(MD_ERR_HIP, "%s", kVoxelRanOut);
+  if (!c.out->count) return MD_OK;  // no list: nothing has live rows
   for (const OutSlot& s : pl.slots)
-    if (s.list) MD_TRY(d2h(s.caller, s.home, (s.list == 5 ? nk : s.list == 4 ? nd : s.list == 3 ? std::min((size_t)std::max(unfiltered, 0), s.rows) : s.list == 2 ? nf : n) * s.row_bytes));
+    if (s.live) MD_TRY(d2h(s.caller, s.home, std::min((size_t)std::max(*s.live, 0), s.rows) * s.row_bytes));
   MD_HIP(hipStreamSynchronize(pl.st));
   return MD_OK;
 }
 
 // The stages in the order a captured graph bakes: every grow of the device path before anything is enqueued, then the work.
-int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) {
+int points_eager(md_model_s* m, const PointsCall& c, bool dual, long rows, hipStream_t st) {
   if (!m->points) m->points = new md_model_s::PointsState();
-  PointsPlan pl{st, dual, false, false, false, false, false, (size_t)c.B * c.H * c.W};
+  PointsPlan pl;
+  pl.st = st; pl.dual = dual; pl.npx = (size_t)c.B * c.H * c.W; pl.rows = rows;
   auto timed = [&](const char* name, int (*stage)(md_model_s*, const PointsCall&, PointsPlan&)) -> int {
     Run r{m, st, c.B};
     r.begin(name);
@@ -1253,6 +1208,53 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, hipStream_t st) 
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
+}
+
+// The graph replay key of a call: stream, shape, every option, every in / out pointer and the commit generation
+// (md_frame.hip). A part that is off adds nothing: the key, and the graph, of the call without it. c.cam is not null.
+std::vector<uintptr_t> points_graph_key(md_model_t m, const PointsCall& c, hipStream_t st) {
+  const md_points_cameras& cam = *c.cam;
+  const md_points_opts* o = c.o;
+  const md_points_outputs* out = c.out;
+  std::vector<uintptr_t> key;
+  key_add(key, 0x504f494eu, st, c.B, c.H, c.W, c.nchw, c.rgb, cam.intrinsics, cam.extrinsics, cam.focal_px);
+  key_add(key, o->pixel_offset, o->depth_min, o->depth_max, o->conf_min, o->edge_rtol, o->stride, o->world ? 1 : 0);
+  key_add(key, out->point_map, out->mask, out->xyz, out->rgb, out->conf, out->count, out->capacity, out->depth, model_root(m)->commit_gen);
+  if (c.fo) key_add(key, 0x56464c54u, c.fo->conf_percentile, c.fo->view_rtol, c.fo->min_views);
+  if (c.nrm && (c.nrm->normal_map || c.nrm->normals || c.nrm->min_cos > 0.f))  // all zero: the call without normals
+    key_add(key, 0x4e524d4cu, c.nrm->normal_map, c.nrm->normals, c.nrm->min_cos);
+  if (voxel_on(c.vox)) key_add(key, 0x564f584cu, c.vox->voxel, c.vox->index, c.vox->weight, c.vox->dropped);
+  if (outlier_on(c.outl)) key_add(key, 0x4f55544cu, c.outl->radius, c.outl->min_neighbours, c.outl->neighbours, c.outl->index, c.outl->dropped);
+  if (c.rnd) {
+    const md_points_render& r = *c.rnd;
+    key_add(key, 0x524e4452u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px);
+    key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.radius, r.out.depth, r.out.index, r.out.rgb, r.out.filled);
+  }
+  // the three stages behind the mesh each add its max_rtol: a mesh request without outputs still sets the edge test
+  if (decimate_on(c.dec)) {
+    const md_points_decimate& d = *c.dec;
+    key_add(key, 0x44454349u, d.voxel, d.index, d.weight, d.dropped, d.remap, d.faces, d.face_index, d.face_count, d.face_capacity, d.faces_dropped);
+    key_add(key, c.mesh->max_rtol);
+  }
+  if (components_on(c.comp)) {
+    const md_points_components& k = *c.comp;
+    key_add(key, 0x434f4d50u, k.min_faces, k.label, k.component_faces, k.faces, k.face_index, k.face_count, k.face_capacity, k.stats);
+    key_add(key, c.mesh->max_rtol);
+  }
+  if (smooth_on(c.smooth)) {
+    const md_points_smooth& q = *c.smooth;
+    key_add(key, 0x534d5448u, q.step, q.lambda, q.mu, q.iterations, q.pin_boundary, q.xyz, q.normals, q.stats);
+    key_add(key, c.mesh->max_rtol);
+  }
+  if (mesh_on(c.mesh))  // every output null: the call without a mesh
+    key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
+  if (c.rst) {
+    const md_points_raster& r = *c.rst;
+    key_add(key, 0x52415354u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px, raster_queue_entries());
+    key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.cull, r.opts.max_extent);
+    key_add(key, r.out.depth, r.out.face, r.out.rgb, r.out.filled, r.out.skipped);
+  }
+  return key;
 }
 
 }  // namespace
@@ -1279,17 +1281,18 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   const Sources s{c.rgb != nullptr, dual, cam.intrinsics != nullptr || dual, cam.focal_px != nullptr || m->kind == 0, cam.extrinsics != nullptr || dual};
   MD_TRY(check_points(o, out, c.nrm, s));
   MD_TRY(check_shape(B, H, W));
+  const long rows = list_rows(B, H, W, o->stride);  // the stride is check_points'
   MD_TRY(check_voxel(c.vox, out, false));
-  if (voxel_on(c.vox) && list_rows(B, H, W, o->stride) >= (1l << 30))
-    MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
-  MD_TRY(check_decimate_part(c.dec, out));
+  if (voxel_on(c.vox) && rows >= (1l << 30))
+    MD_FAIL(MD_ERR_SHAPE, "voxel thinning takes fewer than 2^30 rows, the list may have %ld", rows);
+  MD_TRY(check_decimate(c.dec, out, false));
   if (decimate_on(c.dec)) {
     if (!c.mesh) MD_FAIL(MD_ERR_INVALID_ARG, "decimation needs a mesh request");
     if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "decimation needs the list's `count`");
     if (voxel_on(c.vox)) MD_FAIL(MD_ERR_INVALID_ARG, "decimation together with voxel thinning: two grids; the decimation is the thinning");
     if (outlier_on(c.outl)) MD_FAIL(MD_ERR_INVALID_ARG, "decimation together with outlier removal: the rows the faces name no longer exist");
-    if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
-      MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
+    if (2 * rows >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "decimation takes fewer than 2^30 faces, the mesh may have %ld", 2 * rows);
   }
   MD_TRY(check_components_part(c.comp));
   if (components_on(c.comp)) {
@@ -1298,8 +1301,8 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "components together with decimation: the components of the decimated mesh are not built");
     if (voxel_on(c.vox) || outlier_on(c.outl))
       MD_FAIL(MD_ERR_INVALID_ARG, "components together with voxel thinning or outlier removal: the rows the faces name no longer exist");
-    if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
-      MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
+    if (2 * rows >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "components take fewer than 2^30 faces, the mesh may have %ld", 2 * rows);
   }
   MD_TRY(check_smooth_part(c.smooth));
   if (smooth_on(c.smooth)) {
@@ -1311,8 +1314,8 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (components_on(c.comp) && (!c.comp->faces || !c.comp->face_count))
       MD_FAIL(MD_ERR_INVALID_ARG, "smoothing behind the components needs their outputs `faces` and `face_count`");
     if (c.rst && !c.smooth->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising the smoothed mesh needs the smoothing output `xyz`");
-    if (2 * list_rows(B, H, W, o->stride) >= (1l << 30))
-      MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 faces, the mesh may have %ld", 2 * list_rows(B, H, W, o->stride));
+    if (2 * rows >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 faces, the mesh may have %ld", 2 * rows);
   }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));
@@ -1320,8 +1323,8 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (mesh_on(c.mesh)) MD_FAIL(MD_ERR_INVALID_ARG, "a mesh together with outlier removal: the rows its faces name no longer exist");
     if (c.outl->index && voxel_on(c.vox))
       MD_FAIL(MD_ERR_INVALID_ARG, "the outlier removal's index together with voxel thinning: the rows it is parallel to are not returned");
-    if (list_rows(B, H, W, o->stride) >= (1l << 30))
-      MD_FAIL(MD_ERR_SHAPE, "outlier removal takes fewer than 2^30 rows, the list may have %ld", list_rows(B, H, W, o->stride));
+    if (rows >= (1l << 30))
+      MD_FAIL(MD_ERR_SHAPE, "outlier removal takes fewer than 2^30 rows, the list may have %ld", rows);
   }
   if (c.rnd) {
     MD_TRY(check_render(c.rnd->T, c.rnd->H, c.rnd->W, &c.rnd->cam, &c.rnd->opts, &c.rnd->out, out->rgb != nullptr));
@@ -1350,10 +1353,9 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (!model_root(m)->committed) MD_FAIL(MD_ERR_INVALID_ARG, "weights were modified; call md_model_commit_weights first");
   MD_HIP(hipSetDevice(m->dev->ordinal));
   hipStream_t st = model_stream(m, stream);
-  auto body = [&]() { return points_eager(m, c, dual, st); };
+  auto body = [&]() { return points_eager(m, c, dual, rows, st); };
   if (!m->graph_enabled) return body();
-  // the key: stream, shape, every option, every in / out pointer and the commit generation (md_frame.hip); a graph only
-  // replays at the model's current input size (its workspace plan)
+  // a graph only replays at the model's current input size (its workspace plan)
   bool eligible = c.in_kind == MD_MEM_DEVICE && c.out_kind == MD_MEM_DEVICE;
   if (m->kind == 1) {
     int ps = 0, ch = 0, cw = 0;
@@ -1362,46 +1364,7 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   } else {
     eligible = eligible && H == m->S && W == m->S;
   }
-  std::vector<uintptr_t> key;
-  key_add(key, 0x504f494eu, st, B, H, W, c.nchw, c.rgb, cam.intrinsics, cam.extrinsics, cam.focal_px);
-  key_add(key, o->pixel_offset, o->depth_min, o->depth_max, o->conf_min, o->edge_rtol, o->stride, o->world ? 1 : 0);
-  key_add(key, out->point_map, out->mask, out->xyz, out->rgb, out->conf, out->count, out->capacity, out->depth, model_root(m)->commit_gen);
-  if (c.fo) key_add(key, 0x56464c54u, c.fo->conf_percentile, c.fo->view_rtol, c.fo->min_views);
-  if (c.nrm && (c.nrm->normal_map || c.nrm->normals || c.nrm->min_cos > 0.f))  // all zero: the key, and the graph, of the call without normals
-    key_add(key, 0x4e524d4cu, c.nrm->normal_map, c.nrm->normals, c.nrm->min_cos);
-  if (voxel_on(c.vox))  // voxel == 0: the key, and the graph, of the call without thinning
-    key_add(key, 0x564f584cu, c.vox->voxel, c.vox->index, c.vox->weight, c.vox->dropped);
-  if (outlier_on(c.outl))  // radius == 0: the key, and the graph, of the call without outlier removal
-    key_add(key, 0x4f55544cu, c.outl->radius, c.outl->min_neighbours, c.outl->neighbours, c.outl->index, c.outl->dropped);
-  if (c.rnd) {
-    const md_points_render& r = *c.rnd;
-    key_add(key, 0x524e4452u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px);
-    key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.radius, r.out.depth, r.out.index, r.out.rgb, r.out.filled);
-  }
-  if (decimate_on(c.dec)) {  // voxel == 0: the key, and the graph, of the call without decimation
-    const md_points_decimate& d = *c.dec;
-    key_add(key, 0x44454349u, d.voxel, d.index, d.weight, d.dropped, d.remap, d.faces, d.face_index, d.face_count, d.face_capacity, d.faces_dropped);
-    key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
-  }
-  if (components_on(c.comp)) {  // min_faces == 0: the key, and the graph, of the call without the stage
-    const md_points_components& k = *c.comp;
-    key_add(key, 0x434f4d50u, k.min_faces, k.label, k.component_faces, k.faces, k.face_index, k.face_count, k.face_capacity, k.stats);
-    key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
-  }
-  if (smooth_on(c.smooth)) {  // iterations == 0: the key, and the graph, of the call without the stage
-    const md_points_smooth& q = *c.smooth;
-    key_add(key, 0x534d5448u, q.step, q.lambda, q.mu, q.iterations, q.pin_boundary, q.xyz, q.normals, q.stats);
-    key_add(key, c.mesh->max_rtol);  // a mesh request without outputs still sets the edge test
-  }
-  if (mesh_on(c.mesh))  // every output null: the key, and the graph, of the call without a mesh
-    key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
-  if (c.rst) {
-    const md_points_raster& r = *c.rst;
-    key_add(key, 0x52415354u, r.T, r.H, r.W, r.cam.intrinsics, r.cam.extrinsics, r.cam.focal_px, raster_queue_entries());
-    key_add(key, r.opts.pixel_offset, r.opts.z_near, r.opts.z_far, r.opts.cull, r.opts.max_extent);
-    key_add(key, r.out.depth, r.out.face, r.out.rgb, r.out.filled, r.out.skipped);
-  }
-  return run_with_graph(m, st, key, eligible, body);
+  return run_with_graph(m, st, points_graph_key(m, c, st), eligible, body);
 }
 
 }  // namespace md
