@@ -13,7 +13,7 @@
 //   count    size[label[p]] += 1 per valid face: ONE add of the popcount by the first lane when every valid lane of the wave
 //            names the same root (the neighbouring faces of a depth-grid mesh mostly share a component), per-lane adds otherwise
 //   rows     grid tiles of the rows: label, component_faces, the components (rows with label[i] == i and size > 0) counted in
-//            total and kept, remap preset to -1, and the keep bits of the ROWS in the ballot layout: a row that a valid face
+//            total and kept, remap preset to -1, and the keep bits of the ROWS in the ballot layout (tile_compact.h): a row that a valid face
 //            names lies in a component with size > 0 and a row that none names is alone with size 0, so "a face of a kept
 //            component names row i" is size[label[i]] >= min_faces. No mark launch over the faces and no atomicOr is needed
 //   (compact) launch_list_compact's scan and scatter on those bits, then the decimation's rank step for remap
@@ -25,13 +25,11 @@
 #include <algorithm>
 
 #include "components_math.h"
-#include "voxel_math.h"
+#include "tile_compact.h"
 
 namespace md {
 
 namespace {
-
-constexpr int kThreads = kGridThreads, kSteps = kGridSteps, kTile = kGridTile, kWords = kGridWords;
 
 struct DeviceAtomics {  // components_math.h's policy on device memory: relaxed, agent scope (served by L2)
   static __host__ __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -56,59 +54,31 @@ struct ComponentsScratch {  // 256-byte aligned parts
   size_t bytes;
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-inline int tiles_of(int n) { return (n + kTile - 1) / kTile; }
-
 ComponentsScratch carve(void* base, int n, int nf, int B) {
   const size_t nbf = (size_t)tiles_of(nf), nbv = (size_t)tiles_of(n);
   ComponentsScratch s;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* at = p;
-    p += up256(bytes);
-    return at;
-  };
-  s.parent = (int*)take((size_t)n * 4);
-  s.size = (int*)take((size_t)n * 4);
-  s.remap = (int32_t*)take((size_t)n * 4);
-  s.vcount = (int32_t*)take((size_t)(B + 1) * 4);
-  s.fbits = (unsigned long long*)take(nbf * kWords * 8);
-  s.fcounts = (int*)take(nbf * 4);
-  s.foffsets = (int*)take((nbf + 1) * 4);
-  s.vbits = (unsigned long long*)take(nbv * kWords * 8);
-  s.vcounts = (int*)take(nbv * 4);
-  s.voffsets = (int*)take((nbv + 1) * 4);
-  s.stats = (int32_t*)take(256);
-  s.bytes = (size_t)(p - (char*)base);
+  Carver c(base);
+  s.parent = c.take<int>((size_t)n);
+  s.size = c.take<int>((size_t)n);
+  s.remap = c.take<int32_t>((size_t)n);
+  s.vcount = c.take<int32_t>((size_t)(B + 1));
+  s.fbits = c.take<unsigned long long>(nbf * kTileWords);
+  s.fcounts = c.take<int>(nbf);
+  s.foffsets = c.take<int>(nbf + 1);
+  s.vbits = c.take<unsigned long long>(nbv * kTileWords);
+  s.vcounts = c.take<int>(nbv);
+  s.voffsets = c.take<int>(nbv + 1);
+  s.stats = c.take<int32_t>(64);
+  s.bytes = c.bytes;
   return s;
-}
-
-__device__ __forceinline__ int live_of(const int32_t* __restrict__ count, int B, int n) {
-  if (!count) return n;
-  const int t = count[B];
-  return t < 0 ? 0 : (t < n ? t : n);
 }
 
 __device__ __forceinline__ bool valid_face(int a, int b, int c, int n) { return a >= 0 && a < n && b >= 0 && b < n && c >= 0 && c < n; }
 
-// exclusive scan of the 64 word popcounts of a tile by wave 0 (word order = row order)
-__device__ __forceinline__ void scan_words(const unsigned long long* __restrict__ words, int tid, int* word_off) {
-  if (tid < kWords) {
-    const int c = __popcll(words[tid]);
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (tid >= d) incl += up;
-    }
-    word_off[tid] = incl - c;
-  }
-}
-
 // grid max(ceil(n / 256), 1)
-__global__ void __launch_bounds__(kThreads) components_init_kernel(int n, int* __restrict__ parent, int* __restrict__ size,
+__global__ void __launch_bounds__(kTileThreads) components_init_kernel(int n, int* __restrict__ parent, int* __restrict__ size,
                                                                    int32_t* __restrict__ stats) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
   if (i < n) {
     parent[i] = (int)i;
     size[i] = 0;
@@ -117,12 +87,12 @@ __global__ void __launch_bounds__(kThreads) components_init_kernel(int n, int* _
 }
 
 // grid ceil(nf / 256); no thread leaves before the ballot
-__global__ void __launch_bounds__(kThreads) components_hook_kernel(ComponentsParams p, int* parent, int32_t* __restrict__ stats) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
-  const bool live = f < live_of(p.in_face_count, p.v.B, p.nf);
+__global__ void __launch_bounds__(kTileThreads) components_hook_kernel(ComponentsParams p, int* parent, int32_t* __restrict__ stats) {
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  const bool live = f < live_count(p.in_face_count, p.v.B, p.nf);
   bool invalid = false;
   if (live) {
-    const int n = live_of(p.v.in_count, p.v.B, p.v.n);
+    const int n = live_count(p.v.in_count, p.v.B, p.v.n);
     const int a = p.faces[f * 3], b = p.faces[f * 3 + 1], c = p.faces[f * 3 + 2];
     invalid = !valid_face(a, b, c, n);
     if (!invalid) {
@@ -130,27 +100,26 @@ __global__ void __launch_bounds__(kThreads) components_hook_kernel(ComponentsPar
       components_hook<DeviceAtomics>(parent, b, c);
     }
   }
-  const unsigned long long inv = __ballot(invalid);
-  if ((threadIdx.x & 63) == 0 && inv) atomicAdd(stats, (int)__popcll(inv));
+  wave_count_add(invalid, stats);
 }
 
 // grid ceil(n / 256). In place, while other threads of this launch walk the same chains: the walk compresses nothing, so the
 // only stores of the launch are roots and parent[i] ends as the root of i whichever store comes last.
-__global__ void __launch_bounds__(kThreads) components_flatten_kernel(int n, int* parent) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+__global__ void __launch_bounds__(kTileThreads) components_flatten_kernel(int n, int* parent) {
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
   if (i >= n) return;
   const int root = components_root<DeviceAtomics>(parent, (int)i);
   DeviceAtomics::store(parent + i, root);
 }
 
 // grid ceil(nf / 256); no thread leaves before the ballots
-__global__ void __launch_bounds__(kThreads) components_count_kernel(ComponentsParams p, const int* __restrict__ label, int* __restrict__ size) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
+__global__ void __launch_bounds__(kTileThreads) components_count_kernel(ComponentsParams p, const int* __restrict__ label, int* __restrict__ size) {
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool valid = false;
   int root = -1;
-  if (f < live_of(p.in_face_count, p.v.B, p.nf)) {
-    const int n = live_of(p.v.in_count, p.v.B, p.v.n);
+  if (f < live_count(p.in_face_count, p.v.B, p.nf)) {
+    const int n = live_count(p.v.in_count, p.v.B, p.v.n);
     const int a = p.faces[f * 3], b = p.faces[f * 3 + 1], c = p.faces[f * 3 + 2];
     valid = valid_face(a, b, c, n);
     if (valid) root = label[a];
@@ -168,15 +137,15 @@ __global__ void __launch_bounds__(kThreads) components_count_kernel(ComponentsPa
 }
 
 // grid tiles of the rows
-__global__ void __launch_bounds__(kThreads) components_rows_kernel(ComponentsParams p, const int* __restrict__ parent, const int* __restrict__ size,
+__global__ void __launch_bounds__(kTileThreads) components_rows_kernel(ComponentsParams p, const int* __restrict__ parent, const int* __restrict__ size,
                                                                    int32_t* __restrict__ remap, unsigned long long* __restrict__ bits,
                                                                    int* __restrict__ counts, int32_t* __restrict__ stats) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int live = live_of(p.v.in_count, p.v.B, p.v.n);
+  __shared__ int wave_n[kTileWaves];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int live = live_count(p.v.in_count, p.v.B, p.v.n);
   int n = 0, total = 0, kept = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long i = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long i = tile_item(tile, s);
     bool keep = false, root = false;
     if (i < p.v.n) {
       int l = -1, sz = 0;
@@ -190,31 +159,28 @@ __global__ void __launch_bounds__(kThreads) components_rows_kernel(ComponentsPar
       if (p.component_faces) p.component_faces[i] = sz;
       if (remap) remap[i] = -1;  // the rank step overwrites the kept rows
     }
-    const unsigned long long word = __ballot(keep);
-    if (lane == 0) bits[(long)tile * kWords + s * (kThreads / 64) + wave] = word;
-    n += __popcll(word);
+    n += ballot_step(keep, bits + (long)tile * kTileWords + tile_word(s));
     total += __popcll(__ballot(root));
     kept += __popcll(__ballot(root && keep));
   }
   if (lane == 0) {
-    wave_n[wave] = n;
     if (total) atomicAdd(stats + 3, total);
     if (kept) atomicAdd(stats + 4, kept);
   }
-  __syncthreads();
-  if (tid == 0) counts[tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0) counts[tile] = sum;
 }
 
 // grid tiles of the faces. remap: null without compact.
-__global__ void __launch_bounds__(kThreads) components_select_kernel(ComponentsParams p, const int* __restrict__ label, const int* __restrict__ size,
+__global__ void __launch_bounds__(kTileThreads) components_select_kernel(ComponentsParams p, const int* __restrict__ label, const int* __restrict__ size,
                                                                      const int32_t* __restrict__ remap, unsigned long long* __restrict__ bits,
                                                                      int* __restrict__ counts, int32_t* __restrict__ stats) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int live = live_of(p.in_face_count, p.v.B, p.nf), rows = live_of(p.v.in_count, p.v.B, p.v.n);
+  __shared__ int wave_n[kTileWaves];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int live = live_count(p.in_face_count, p.v.B, p.nf), rows = live_count(p.v.in_count, p.v.B, p.v.n);
   int n = 0, dropped = 0, clipped = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long f = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long f = tile_item(tile, s);
     bool keep = false, drop = false, clip = false;
     if (f < live) {
       const int a = p.faces[f * 3], b = p.faces[f * 3 + 1], c = p.faces[f * 3 + 2];
@@ -227,38 +193,34 @@ __global__ void __launch_bounds__(kThreads) components_select_kernel(ComponentsP
         }
       }
     }
-    const unsigned long long word = __ballot(keep);
-    if (lane == 0) bits[(long)tile * kWords + s * (kThreads / 64) + wave] = word;
-    n += __popcll(word);
+    n += ballot_step(keep, bits + (long)tile * kTileWords + tile_word(s));
     dropped += __popcll(__ballot(drop));
     clipped += __popcll(__ballot(clip));
   }
   if (lane == 0) {
-    wave_n[wave] = n;
     if (dropped) atomicAdd(stats + 1, dropped);
     if (clipped) atomicAdd(stats + 2, clipped);
   }
-  __syncthreads();
-  if (tid == 0) counts[tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0) counts[tile] = sum;
 }
 
-__global__ void __launch_bounds__(kThreads) components_scatter_kernel(ComponentsParams p, const int32_t* __restrict__ remap,
+__global__ void __launch_bounds__(kTileThreads) components_scatter_kernel(ComponentsParams p, const int32_t* __restrict__ remap,
                                                                       const unsigned long long* __restrict__ bits, const int* __restrict__ offsets) {
-  __shared__ int word_off[kWords];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const unsigned long long* words = bits + (long)tile * kWords;
-  scan_words(words, tid, word_off);
+  __shared__ int word_off[kTileWords];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const unsigned long long* words = bits + (long)tile * kTileWords;
+  if (tid < kTileWords) scan_word_counts(__popcll(words[tid]), word_off);
   __syncthreads();
   const long base = offsets[tile];
   if (base >= p.face_capacity) return;  // everything of this workgroup lies beyond the capacity
-  for (int s = 0; s < kSteps; ++s) {
-    const int w = s * (kThreads / 64) + wave;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const int w = tile_word(s);
     const unsigned long long word = words[w];
     if (!((word >> lane) & 1ull)) continue;
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
-    const long idx = base + word_off[w] + below;
+    const long idx = base + word_off[w] + lane_rank(word);
     if (idx >= p.face_capacity) continue;
-    const long f = (long)tile * kTile + s * kThreads + tid;  // a live, valid face: the bit is only ever set for one
+    const long f = tile_item(tile, s);  // a live, valid face: the bit is only ever set for one
     if (p.faces_out) {
       const int32_t* src = p.faces + f * 3;
       int32_t* dst = p.faces_out + idx * 3;
@@ -292,21 +254,21 @@ int launch_mesh_components(const ComponentsParams& p, void* scratch, hipStream_t
   const ComponentsScratch c = carve(scratch, n, nf, p.v.B);
   int32_t* stats = p.stats ? p.stats : c.stats;
   int32_t* remap = p.compact ? (p.remap ? p.remap : c.remap) : nullptr;
-  const unsigned rows_grid = (unsigned)((n + kThreads - 1) / kThreads), faces_grid = (unsigned)((nf + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(components_init_kernel, dim3(std::max(rows_grid, 1u)), dim3(kThreads), 0, s, n, c.parent, c.size, stats);
+  const unsigned rows_grid = (unsigned)((n + kTileThreads - 1) / kTileThreads), faces_grid = (unsigned)((nf + kTileThreads - 1) / kTileThreads);
+  hipLaunchKernelGGL(components_init_kernel, dim3(std::max(rows_grid, 1u)), dim3(kTileThreads), 0, s, n, c.parent, c.size, stats);
   MD_HIP(hipGetLastError());
   if (nf > 0) {
-    hipLaunchKernelGGL(components_hook_kernel, dim3(faces_grid), dim3(kThreads), 0, s, p, c.parent, stats);
+    hipLaunchKernelGGL(components_hook_kernel, dim3(faces_grid), dim3(kTileThreads), 0, s, p, c.parent, stats);
     MD_HIP(hipGetLastError());
   }
   if (n > 0 && nf > 0) {
-    hipLaunchKernelGGL(components_flatten_kernel, dim3(rows_grid), dim3(kThreads), 0, s, n, c.parent);
+    hipLaunchKernelGGL(components_flatten_kernel, dim3(rows_grid), dim3(kTileThreads), 0, s, n, c.parent);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(components_count_kernel, dim3(faces_grid), dim3(kThreads), 0, s, p, c.parent, c.size);
+    hipLaunchKernelGGL(components_count_kernel, dim3(faces_grid), dim3(kTileThreads), 0, s, p, c.parent, c.size);
     MD_HIP(hipGetLastError());
   }
   if (n > 0) {
-    hipLaunchKernelGGL(components_rows_kernel, dim3(tiles_of(n)), dim3(kThreads), 0, s, p, c.parent, c.size, remap, c.vbits, c.vcounts, stats);
+    hipLaunchKernelGGL(components_rows_kernel, dim3(tiles_of(n)), dim3(kTileThreads), 0, s, p, c.parent, c.size, remap, c.vbits, c.vcounts, stats);
     MD_HIP(hipGetLastError());
   }
   if (p.compact) {  // the rows: scan and scatter on the row bits, then the true rank of every kept row
@@ -316,7 +278,7 @@ int launch_mesh_components(const ComponentsParams& p, void* scratch, hipStream_t
     MD_TRY(launch_rank_rows(c.vbits, c.voffsets, n, remap, s));
   }
   if (nf > 0) {
-    hipLaunchKernelGGL(components_select_kernel, dim3(tiles_of(nf)), dim3(kThreads), 0, s, p, c.parent, c.size, remap, c.fbits, c.fcounts, stats);
+    hipLaunchKernelGGL(components_select_kernel, dim3(tiles_of(nf)), dim3(kTileThreads), 0, s, p, c.parent, c.size, remap, c.fbits, c.fcounts, stats);
     MD_HIP(hipGetLastError());
   }
   if (!p.face_count) return MD_OK;
@@ -324,7 +286,7 @@ int launch_mesh_components(const ComponentsParams& p, void* scratch, hipStream_t
   fc.in_count = p.in_face_count; fc.n = nf; fc.B = p.v.B; fc.count = p.face_count;
   MD_TRY(launch_list_compact(fc, nullptr, nullptr, c.fbits, c.fcounts, c.foffsets, s));
   if (nf == 0 || (!p.faces_out && !p.face_index)) return MD_OK;
-  hipLaunchKernelGGL(components_scatter_kernel, dim3(tiles_of(nf)), dim3(kThreads), 0, s, p, remap, c.fbits, c.foffsets);
+  hipLaunchKernelGGL(components_scatter_kernel, dim3(tiles_of(nf)), dim3(kTileThreads), 0, s, p, remap, c.fbits, c.foffsets);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

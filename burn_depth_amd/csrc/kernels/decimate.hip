@@ -5,7 +5,7 @@
 //
 // The vertex side is launch_voxel_thin, unchanged, then two launches for remap[i] = the output row of the survivor of row i's
 // voxel, from the scratch the thinning leaves:
-//   rank     grid tiles: a kept row's output row = tile offset + popcounts below its bit (mesh_index_kernel's step)
+//   rank     grid tiles: a kept row's output row = tile offset + popcounts below its bit (the scatter step of tile_compact.h)
 //   remap    one thread per row that is not kept: the low word of its slot's rank names the survivor s; remap[i] = remap[s]
 // The face side, six launches:
 //   reset    table slots to -1, the class counters and the flag to 0
@@ -17,7 +17,7 @@
 //            map launch wrote (a plain load); on a match atomicMin(slot, f), otherwise the next slot. Every id that ever sits in
 //            a slot has the same triple, so the slot's identity never changes and it ends as the smallest f of that triangle.
 //            The face's slot is recorded
-//   select   keep[f] = live and its slot holds f; ballot words in voxel_select_kernel's layout; duplicates counted per wave
+//   select   keep[f] = live and its slot holds f; ballot words in tile_compact.h's layout; duplicates counted per wave
 //   scan     launch_list_compact's scan on those words: tile offsets and face_count per view of the input faces
 //   scatter  12-byte rows and face_index with plain stores
 // No thread waits on another: the probe loop is bounded by the table size and a lost compare-and-swap hands back the winner's
@@ -29,8 +29,6 @@
 namespace md {
 
 namespace {
-
-constexpr int kThreads = kGridThreads, kSteps = kGridSteps, kTile = kGridTile, kWords = kGridWords;
 
 struct DecimateScratch {  // the parts behind voxel thinning's scratch, 256-byte aligned
   int32_t* count;     // [B + 1] the vertex counts when the caller takes none (the scan that leaves the tile offsets needs a home)
@@ -45,77 +43,48 @@ struct DecimateScratch {  // the parts behind voxel thinning's scratch, 256-byte
   size_t bytes;
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-inline int tiles_of(int n) { return (n + kTile - 1) / kTile; }
-
 // The two homes are carved whether or not the caller brings its own count and remap: the layout then depends on the shape alone,
 // which is what decimate_flags and a model's grow-only buffer need. Untouched bytes of a scratch cost an allocation, no traffic.
 DecimateScratch carve(void* base, int n, int nf, int B) {
   const size_t slots = voxel_table_slots(nf), nb = (size_t)tiles_of(nf);
   DecimateScratch s;
-  char* p = (char*)base + voxel_scratch_bytes(n);
-  auto take = [&](size_t bytes) {
-    char* at = p;
-    p += up256(bytes);
-    return at;
-  };
-  s.count = (int32_t*)take((size_t)(B + 1) * 4);
-  s.remap = (int32_t*)take((size_t)n * 4);
-  s.table = (int*)take(slots * 4);
-  s.mapped = (int32_t*)take((size_t)nf * 12);
-  s.fslot = (int*)take((size_t)nf * 4);
-  s.bits = (unsigned long long*)take(nb * kWords * 8);
-  s.counts = (int*)take(nb * 4);
-  s.offsets = (int*)take((nb + 1) * 4);
-  s.flags = (int*)take(256);
-  s.bytes = (size_t)(p - (char*)base);
+  Carver c(base, voxel_scratch_bytes(n));
+  s.count = c.take<int32_t>((size_t)(B + 1));
+  s.remap = c.take<int32_t>((size_t)n);
+  s.table = c.take<int>(slots);
+  s.mapped = c.take<int32_t>((size_t)nf * 3);
+  s.fslot = c.take<int>((size_t)nf);
+  s.bits = c.take<unsigned long long>(nb * kTileWords);
+  s.counts = c.take<int>(nb);
+  s.offsets = c.take<int>(nb + 1);
+  s.flags = c.take<int>(64);
+  s.bytes = c.bytes;
   return s;
 }
 
-__device__ __forceinline__ int live_of(const int32_t* __restrict__ count, int B, int n) {
-  if (!count) return n;
-  const int t = count[B];
-  return t < 0 ? 0 : (t < n ? t : n);
-}
-
-// exclusive scan of the 64 word popcounts of a tile by wave 0 (word order = row order)
-__device__ __forceinline__ void scan_words(const unsigned long long* __restrict__ words, int tid, int* word_off) {
-  if (tid < kWords) {
-    const int c = __popcll(words[tid]);
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (tid >= d) incl += up;
-    }
-    word_off[tid] = incl - c;
-  }
-}
-
 // grid tiles of the rows. The output row of every kept row; the other rows are the next launch's.
-__global__ void __launch_bounds__(kThreads) decimate_rank_kernel(const unsigned long long* __restrict__ bits, const int* __restrict__ offsets,
+__global__ void __launch_bounds__(kTileThreads) decimate_rank_kernel(const unsigned long long* __restrict__ bits, const int* __restrict__ offsets,
                                                                  int32_t* __restrict__ remap) {
-  __shared__ int word_off[kWords];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const unsigned long long* words = bits + (long)tile * kWords;
-  scan_words(words, tid, word_off);
+  __shared__ int word_off[kTileWords];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const unsigned long long* words = bits + (long)tile * kTileWords;
+  if (tid < kTileWords) scan_word_counts(__popcll(words[tid]), word_off);
   __syncthreads();
   const int base = offsets[tile];
-  for (int s = 0; s < kSteps; ++s) {
-    const int w = s * (kThreads / 64) + wave;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const int w = tile_word(s);
     const unsigned long long word = words[w];
     if (!((word >> lane) & 1ull)) continue;  // the bit is only ever set for a live row
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
-    remap[(long)tile * kTile + s * kThreads + tid] = base + word_off[w] + (int)below;
+    remap[tile_item(tile, s)] = base + word_off[w] + (int)lane_rank(word);
   }
 }
 
 // grid ceil(n / 256). A kept row keeps what the rank launch wrote; this launch reads only such rows and writes only the others.
-__global__ void __launch_bounds__(kThreads) decimate_remap_kernel(const int32_t* __restrict__ in_count, int B, int n, const int* __restrict__ slot,
+__global__ void __launch_bounds__(kTileThreads) decimate_remap_kernel(const int32_t* __restrict__ in_count, int B, int n, const int* __restrict__ slot,
                                                                   const unsigned long long* __restrict__ rank, int32_t* remap) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
   if (i >= n) return;
-  if (i >= live_of(in_count, B, n)) {
+  if (i >= live_count(in_count, B, n)) {
     remap[i] = -1;
     return;
   }
@@ -129,10 +98,10 @@ __global__ void __launch_bounds__(kThreads) decimate_remap_kernel(const int32_t*
 }
 
 // slots is a multiple of 1024: every thread writes four slots with one 16-byte store
-__global__ void __launch_bounds__(kThreads) decimate_reset_kernel(int4* __restrict__ table, size_t quads, int* __restrict__ flags,
+__global__ void __launch_bounds__(kTileThreads) decimate_reset_kernel(int4* __restrict__ table, size_t quads, int* __restrict__ flags,
                                                                   int32_t* __restrict__ dropped) {
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x; q < quads; q += stride) table[q] = make_int4(-1, -1, -1, -1);
+  const size_t stride = (size_t)gridDim.x * kTileThreads;
+  for (size_t q = (size_t)blockIdx.x * kTileThreads + threadIdx.x; q < quads; q += stride) table[q] = make_int4(-1, -1, -1, -1);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     flags[0] = 0;
     dropped[0] = 0;
@@ -142,13 +111,13 @@ __global__ void __launch_bounds__(kThreads) decimate_reset_kernel(int4* __restri
 }
 
 // grid ceil(nf / 256); no thread leaves before the ballots. n: the live rows, cap: the rows the vertex outputs hold.
-__global__ void __launch_bounds__(kThreads) decimate_map_kernel(DecimateParams p, const int32_t* __restrict__ remap, int32_t* __restrict__ mapped,
+__global__ void __launch_bounds__(kTileThreads) decimate_map_kernel(DecimateParams p, const int32_t* __restrict__ remap, int32_t* __restrict__ mapped,
                                                                 int32_t* __restrict__ dropped) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
-  const bool live = f < live_of(p.in_face_count, p.v.B, p.nf);
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  const bool live = f < live_count(p.in_face_count, p.v.B, p.nf);
   bool invalid = false, degenerate = false;
   if (live) {
-    const int n = live_of(p.v.in_count, p.v.B, p.v.n);
+    const int n = live_count(p.v.in_count, p.v.B, p.v.n);
     const int a = p.faces[f * 3], b = p.faces[f * 3 + 1], c = p.faces[f * 3 + 2];
     int ma = -1, mb = -1, mc = -1;
     if (a >= 0 && a < n && b >= 0 && b < n && c >= 0 && c < n) {
@@ -159,11 +128,8 @@ __global__ void __launch_bounds__(kThreads) decimate_map_kernel(DecimateParams p
     int32_t* dst = mapped + f * 3;
     dst[0] = (invalid || degenerate) ? -1 : ma; dst[1] = mb; dst[2] = mc;
   }
-  const unsigned long long inv = __ballot(invalid), deg = __ballot(degenerate);
-  if ((threadIdx.x & 63) == 0) {
-    if (inv) atomicAdd(dropped, (int)__popcll(inv));
-    if (deg) atomicAdd(dropped + 1, (int)__popcll(deg));
-  }
+  wave_count_add(invalid, dropped);
+  wave_count_add(degenerate, dropped + 1);
 }
 
 // the triple with its smallest index first; the three are distinct
@@ -174,10 +140,10 @@ __device__ __forceinline__ void rotate_min_first(int a, int b, int c, int* x, in
 }
 
 // grid ceil(nf / 256). mask = slots - 1.
-__global__ void __launch_bounds__(kThreads) decimate_insert_kernel(DecimateParams p, const int32_t* __restrict__ mapped, int* table,
+__global__ void __launch_bounds__(kTileThreads) decimate_insert_kernel(DecimateParams p, const int32_t* __restrict__ mapped, int* table,
                                                                    unsigned long long mask, int* __restrict__ fslot, int* __restrict__ flags) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (f >= live_of(p.in_face_count, p.v.B, p.nf)) return;
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  if (f >= live_count(p.in_face_count, p.v.B, p.nf)) return;
   if (mapped[f * 3] < 0) {
     fslot[f] = -1;
     return;
@@ -206,51 +172,45 @@ __global__ void __launch_bounds__(kThreads) decimate_insert_kernel(DecimateParam
 }
 
 // grid tiles of the faces. A face is kept when it is live and the slot it ended in holds it.
-__global__ void __launch_bounds__(kThreads) decimate_select_kernel(DecimateParams p, const int32_t* __restrict__ mapped, const int* __restrict__ table,
+__global__ void __launch_bounds__(kTileThreads) decimate_select_kernel(DecimateParams p, const int32_t* __restrict__ mapped, const int* __restrict__ table,
                                                                    const int* __restrict__ fslot, unsigned long long* __restrict__ bits,
                                                                    int* __restrict__ counts, int32_t* __restrict__ dropped) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int live = live_of(p.in_face_count, p.v.B, p.nf);
+  __shared__ int wave_n[kTileWaves];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int live = live_count(p.in_face_count, p.v.B, p.nf);
   int n = 0, dup = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long f = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long f = tile_item(tile, s);
     bool keep = false, copy = false;
     if (f < live && mapped[f * 3] >= 0) {
       const int h = fslot[f];
       keep = h >= 0 && table[h] == (int)f;
       copy = h >= 0 && !keep;
     }
-    const unsigned long long word = __ballot(keep);
-    if (lane == 0) bits[(long)tile * kWords + s * (kThreads / 64) + wave] = word;
-    n += __popcll(word);
+    n += ballot_step(keep, bits + (long)tile * kTileWords + tile_word(s));
     dup += __popcll(__ballot(copy));
   }
-  if (lane == 0) {
-    wave_n[wave] = n;
-    if (dup) atomicAdd(dropped + 2, dup);
-  }
-  __syncthreads();
-  if (tid == 0) counts[tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+  if (lane == 0 && dup) atomicAdd(dropped + 2, dup);
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0) counts[tile] = sum;
 }
 
-__global__ void __launch_bounds__(kThreads) decimate_scatter_kernel(DecimateParams p, const int32_t* __restrict__ mapped,
+__global__ void __launch_bounds__(kTileThreads) decimate_scatter_kernel(DecimateParams p, const int32_t* __restrict__ mapped,
                                                                     const unsigned long long* __restrict__ bits, const int* __restrict__ offsets) {
-  __shared__ int word_off[kWords];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const unsigned long long* words = bits + (long)tile * kWords;
-  scan_words(words, tid, word_off);
+  __shared__ int word_off[kTileWords];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const unsigned long long* words = bits + (long)tile * kTileWords;
+  if (tid < kTileWords) scan_word_counts(__popcll(words[tid]), word_off);
   __syncthreads();
   const long base = offsets[tile];
   if (base >= p.face_capacity) return;  // everything of this workgroup lies beyond the capacity
-  for (int s = 0; s < kSteps; ++s) {
-    const int w = s * (kThreads / 64) + wave;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const int w = tile_word(s);
     const unsigned long long word = words[w];
     if (!((word >> lane) & 1ull)) continue;
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
-    const long idx = base + word_off[w] + below;
+    const long idx = base + word_off[w] + lane_rank(word);
     if (idx >= p.face_capacity) continue;
-    const long f = (long)tile * kTile + s * kThreads + tid;  // a live face: the bit is only ever set for one
+    const long f = tile_item(tile, s);  // a live face: the bit is only ever set for one
     if (p.faces_out) {
       const int32_t* src = mapped + f * 3;
       int32_t* dst = p.faces_out + idx * 3;
@@ -261,12 +221,12 @@ __global__ void __launch_bounds__(kThreads) decimate_scatter_kernel(DecimatePara
 }
 
 // grid ceil(rows / 256), at least one workgroup: the first min(count[B], capacity) faces and the B + 1 counts, nothing behind them
-__global__ void __launch_bounds__(kThreads) decimate_copy_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ count, int B,
+__global__ void __launch_bounds__(kTileThreads) decimate_copy_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ count, int B,
                                                                        long rows, int32_t* __restrict__ faces_out, int32_t* __restrict__ count_out,
                                                                        long capacity) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
   if (blockIdx.x == 0)
-    for (int b = threadIdx.x; b <= B; b += kThreads) count_out[b] = count[b];
+    for (int b = threadIdx.x; b <= B; b += kTileThreads) count_out[b] = count[b];
   if (!faces_out) return;
   long live = count[B];
   live = live < rows ? live : rows;
@@ -282,8 +242,8 @@ int launch_copy_faces(const int32_t* faces, const int32_t* count, int B, long ro
   if (!count_out) return MD_OK;
   if (!faces || !count || B < 1 || rows < 0 || capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "face copy: a bad argument");
   const long covered = faces_out ? std::min(rows, capacity) : 0;
-  const unsigned grid = (unsigned)std::max<long>((covered + kThreads - 1) / kThreads, 1);
-  hipLaunchKernelGGL(decimate_copy_faces_kernel, dim3(grid), dim3(kThreads), 0, s, faces, count, B, rows, faces_out, count_out, capacity);
+  const unsigned grid = (unsigned)std::max<long>((covered + kTileThreads - 1) / kTileThreads, 1);
+  hipLaunchKernelGGL(decimate_copy_faces_kernel, dim3(grid), dim3(kTileThreads), 0, s, faces, count, B, rows, faces_out, count_out, capacity);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }
@@ -291,7 +251,7 @@ int launch_copy_faces(const int32_t* faces, const int32_t* count, int B, long ro
 int launch_rank_rows(const unsigned long long* bits, const int* offsets, int n, int32_t* remap, hipStream_t s) {
   if (n <= 0) return MD_OK;
   if (!bits || !offsets || !remap) MD_FAIL(MD_ERR_INVALID_ARG, "rank step: a null argument");
-  hipLaunchKernelGGL(decimate_rank_kernel, dim3(tiles_of(n)), dim3(kThreads), 0, s, bits, offsets, remap);
+  hipLaunchKernelGGL(decimate_rank_kernel, dim3(tiles_of(n)), dim3(kTileThreads), 0, s, bits, offsets, remap);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }
@@ -319,9 +279,9 @@ int launch_decimate_mesh(const DecimateParams& p, void* scratch, hipStream_t s) 
   int32_t* remap = p.remap ? p.remap : d.remap;
   if (p.v.n > 0) {
     const VoxelRanks r = voxel_ranks(scratch, p.v.n);
-    hipLaunchKernelGGL(decimate_rank_kernel, dim3(tiles_of(p.v.n)), dim3(kThreads), 0, s, r.bits, r.offsets, remap);
+    hipLaunchKernelGGL(decimate_rank_kernel, dim3(tiles_of(p.v.n)), dim3(kTileThreads), 0, s, r.bits, r.offsets, remap);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(decimate_remap_kernel, dim3((p.v.n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, p.v.in_count, p.v.B, p.v.n, r.slot,
+    hipLaunchKernelGGL(decimate_remap_kernel, dim3((p.v.n + kTileThreads - 1) / kTileThreads), dim3(kTileThreads), 0, s, p.v.in_count, p.v.B, p.v.n, r.slot,
                        r.rank, remap);
     MD_HIP(hipGetLastError());
   }
@@ -329,17 +289,17 @@ int launch_decimate_mesh(const DecimateParams& p, void* scratch, hipStream_t s) 
   const size_t slots = voxel_table_slots(p.nf), quads = slots / 4;
   const int nb = tiles_of(p.nf);
   int32_t* dropped = p.faces_dropped ? p.faces_dropped : d.flags + 1;
-  const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kThreads - 1) / kThreads, 256 * 32);
-  hipLaunchKernelGGL(decimate_reset_kernel, dim3(reset_grid), dim3(kThreads), 0, s, (int4*)d.table, quads, d.flags, dropped);
+  const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kTileThreads - 1) / kTileThreads, 256 * 32);
+  hipLaunchKernelGGL(decimate_reset_kernel, dim3(reset_grid), dim3(kTileThreads), 0, s, (int4*)d.table, quads, d.flags, dropped);
   MD_HIP(hipGetLastError());
   if (p.nf > 0) {
-    const unsigned faces_grid = (unsigned)((p.nf + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(decimate_map_kernel, dim3(faces_grid), dim3(kThreads), 0, s, q, remap, d.mapped, dropped);
+    const unsigned faces_grid = (unsigned)((p.nf + kTileThreads - 1) / kTileThreads);
+    hipLaunchKernelGGL(decimate_map_kernel, dim3(faces_grid), dim3(kTileThreads), 0, s, q, remap, d.mapped, dropped);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(decimate_insert_kernel, dim3(faces_grid), dim3(kThreads), 0, s, q, d.mapped, d.table, (unsigned long long)(slots - 1),
+    hipLaunchKernelGGL(decimate_insert_kernel, dim3(faces_grid), dim3(kTileThreads), 0, s, q, d.mapped, d.table, (unsigned long long)(slots - 1),
                        d.fslot, d.flags);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(decimate_select_kernel, dim3(nb), dim3(kThreads), 0, s, q, d.mapped, d.table, d.fslot, d.bits, d.counts, dropped);
+    hipLaunchKernelGGL(decimate_select_kernel, dim3(nb), dim3(kTileThreads), 0, s, q, d.mapped, d.table, d.fslot, d.bits, d.counts, dropped);
     MD_HIP(hipGetLastError());
   }
   if (!p.face_count) return MD_OK;
@@ -347,7 +307,7 @@ int launch_decimate_mesh(const DecimateParams& p, void* scratch, hipStream_t s) 
   c.in_count = p.in_face_count; c.n = p.nf; c.B = p.v.B; c.count = p.face_count;
   MD_TRY(launch_list_compact(c, nullptr, nullptr, d.bits, d.counts, d.offsets, s));
   if (p.nf == 0 || (!p.faces_out && !p.face_index)) return MD_OK;
-  hipLaunchKernelGGL(decimate_scatter_kernel, dim3(nb), dim3(kThreads), 0, s, q, d.mapped, d.bits, d.offsets);
+  hipLaunchKernelGGL(decimate_scatter_kernel, dim3(nb), dim3(kTileThreads), 0, s, q, d.mapped, d.bits, d.offsets);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

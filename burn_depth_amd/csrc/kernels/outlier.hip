@@ -27,8 +27,6 @@ namespace md {
 
 namespace {
 
-constexpr int kThreads = kGridThreads, kSteps = kGridSteps, kTile = kGridTile, kWords = kGridWords;
-
 struct OutlierScratch {  // the parts of the scratch buffer, 256-byte aligned
   unsigned long long* keys;
   unsigned* cnt;    // in-range rows of the slot's cell
@@ -44,48 +42,32 @@ struct OutlierScratch {  // the parts of the scratch buffer, 256-byte aligned
   size_t bytes;
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-inline int tiles_of(int n) { return (n + kTile - 1) / kTile; }
-
 OutlierScratch carve(void* base, int n) {
   const size_t slots = voxel_table_slots(n), nb = (size_t)tiles_of(n);
   OutlierScratch s;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* at = p;
-    p += up256(bytes);
-    return at;
-  };
-  s.keys = (unsigned long long*)take(slots * 8);
-  s.cnt = (unsigned*)take(slots * 4);
-  s.start = (unsigned*)take(slots * 4);
-  s.fill = (unsigned*)take(slots * 4);
-  s.slot = (int*)take((size_t)n * 4);
-  s.pos = (int*)take((size_t)n * 4);
-  s.bucket = (float*)take((size_t)n * 12);
-  s.bits = (unsigned long long*)take(nb * kWords * 8);
-  s.counts = (int*)take(nb * 4);
-  s.offsets = (int*)take((nb + 1) * 4);
-  s.flags = (int*)take(256);
-  s.bytes = (size_t)(p - (char*)base);
+  Carver c(base);
+  s.keys = c.take<unsigned long long>(slots);
+  s.cnt = c.take<unsigned>(slots);
+  s.start = c.take<unsigned>(slots);
+  s.fill = c.take<unsigned>(slots);
+  s.slot = c.take<int>((size_t)n);
+  s.pos = c.take<int>((size_t)n);
+  s.bucket = c.take<float>((size_t)n * 3);
+  s.bits = c.take<unsigned long long>(nb * kTileWords);
+  s.counts = c.take<int>(nb);
+  s.offsets = c.take<int>(nb + 1);
+  s.flags = c.take<int>(64);
+  s.bytes = c.bytes;
   return s;
 }
 
-// the live rows of the call: the device total of the input list, never more than the rows the launches cover
-__device__ __forceinline__ int live_rows(const OutlierParams& p) {
-  if (!p.in_count) return p.n;
-  const int t = p.in_count[p.B];
-  return t < 0 ? 0 : (t < p.n ? t : p.n);
-}
-
 // slots is a multiple of 1024: every thread writes four slots with 16-byte stores
-__global__ void __launch_bounds__(kThreads) outlier_reset_kernel(ulonglong2* __restrict__ keys, uint4* __restrict__ cnt, uint4* __restrict__ start,
+__global__ void __launch_bounds__(kTileThreads) outlier_reset_kernel(ulonglong2* __restrict__ keys, uint4* __restrict__ cnt, uint4* __restrict__ start,
                                                                  uint4* __restrict__ fill, size_t quads, int* __restrict__ flags,
                                                                  int32_t* __restrict__ dropped) {
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x; q < quads; q += stride) {
-    keys[2 * q] = make_ulonglong2(kGridEmpty, kGridEmpty);
-    keys[2 * q + 1] = make_ulonglong2(kGridEmpty, kGridEmpty);
+  fill_keys(keys, 2 * quads);
+  const size_t stride = (size_t)gridDim.x * kTileThreads;
+  for (size_t q = (size_t)blockIdx.x * kTileThreads + threadIdx.x; q < quads; q += stride) {
     cnt[q] = make_uint4(0u, 0u, 0u, 0u);
     start[q] = make_uint4(0u, 0u, 0u, 0u);
     fill[q] = make_uint4(0u, 0u, 0u, 0u);
@@ -99,16 +81,14 @@ __global__ void __launch_bounds__(kThreads) outlier_reset_kernel(ulonglong2* __r
 }
 
 // grid ceil(n / 256). mask = slots - 1.
-__global__ void __launch_bounds__(kThreads) outlier_insert_kernel(OutlierParams p, unsigned long long* __restrict__ keys, unsigned* __restrict__ cnt,
+__global__ void __launch_bounds__(kTileThreads) outlier_insert_kernel(OutlierParams p, unsigned long long* __restrict__ keys, unsigned* __restrict__ cnt,
                                                                   int* __restrict__ slot, unsigned long long mask, int* __restrict__ flags) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= live_rows(p)) return;
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  if (i >= live_count(p.in_count, p.B, p.n)) return;
   const float x = p.xyz[i * 3], y = p.xyz[i * 3 + 1], z = p.xyz[i * 3 + 2];
   unsigned long long key = 0ull;
   const bool in_range = grid_cell_key(x, y, z, p.radius, &key);
-  const unsigned long long out_of_range = __ballot(!in_range);  // the lanes of the wave that are still here
-  if (out_of_range && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1))
-    atomicAdd(p.dropped ? p.dropped : flags + 1, (int)__popcll(out_of_range));
+  wave_count_add(!in_range, p.dropped ? p.dropped : flags + 1);  // lanes have already left: the first active one adds
   if (!in_range) {
     slot[i] = -1;
     return;
@@ -124,9 +104,9 @@ __global__ void __launch_bounds__(kThreads) outlier_insert_kernel(OutlierParams 
 }
 
 // grid slots / 256 (slots is a multiple of 1024: every wave is full). The buckets of a wave's 64 slots lie behind one another.
-__global__ void __launch_bounds__(kThreads) outlier_alloc_kernel(const unsigned* __restrict__ cnt, unsigned* __restrict__ start,
+__global__ void __launch_bounds__(kTileThreads) outlier_alloc_kernel(const unsigned* __restrict__ cnt, unsigned* __restrict__ start,
                                                                  int* __restrict__ flags) {
-  const size_t h = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  const size_t h = (size_t)blockIdx.x * kTileThreads + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const unsigned c = cnt[h];
   unsigned incl = c;
@@ -145,11 +125,11 @@ __global__ void __launch_bounds__(kThreads) outlier_alloc_kernel(const unsigned*
 
 // grid ceil(n / 256). The in-range rows are at most n, so is every bucket row; a row beyond that would mean the counts changed
 // under the launches and raises the flag instead of being written.
-__global__ void __launch_bounds__(kThreads) outlier_fill_kernel(OutlierParams p, const unsigned* __restrict__ start, unsigned* __restrict__ fill,
+__global__ void __launch_bounds__(kTileThreads) outlier_fill_kernel(OutlierParams p, const unsigned* __restrict__ start, unsigned* __restrict__ fill,
                                                                 const int* __restrict__ slot, int* __restrict__ pos, float* __restrict__ bucket,
                                                                 int* __restrict__ flags) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= live_rows(p)) return;
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  if (i >= live_count(p.in_count, p.B, p.n)) return;
   const int h = slot[i];
   if (h < 0) return;
   const unsigned at = start[h] + atomicAdd(fill + h, 1u);
@@ -164,20 +144,20 @@ __global__ void __launch_bounds__(kThreads) outlier_fill_kernel(OutlierParams p,
   pos[i] = (int)at;
 }
 
-// grid tiles, voxel_select_kernel's layout. The table and the buckets no longer change: loads only.
-__global__ void __launch_bounds__(kThreads) outlier_search_kernel(OutlierParams p, const unsigned long long* __restrict__ keys,
+// grid tiles, the classify side of tile_compact.h. The table and the buckets no longer change: loads only.
+__global__ void __launch_bounds__(kTileThreads) outlier_search_kernel(OutlierParams p, const unsigned long long* __restrict__ keys,
                                                                   const unsigned* __restrict__ cnt, const unsigned* __restrict__ start,
                                                                   const int* __restrict__ slot, const int* __restrict__ pos,
                                                                   const float* __restrict__ bucket, unsigned long long mask,
                                                                   unsigned long long* __restrict__ bits, int* __restrict__ counts) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int live = live_rows(p);
+  __shared__ int wave_n[kTileWaves];
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int live = live_count(p.in_count, p.B, p.n);
   const float r2 = p.radius * p.radius;
   const int k = p.k;
   int kept = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long i = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long i = tile_item(tile, s);
     bool keep = false;
     if (i < live) {
       const int h = slot[i];
@@ -206,13 +186,10 @@ __global__ void __launch_bounds__(kThreads) outlier_search_kernel(OutlierParams 
       }
       if (p.neighbours) p.neighbours[i] = n;
     }
-    const unsigned long long word = __ballot(keep);
-    if (lane == 0) bits[(long)tile * kWords + s * (kThreads / 64) + wave] = word;
-    kept += __popcll(word);
+    kept += ballot_step(keep, bits + (long)tile * kTileWords + tile_word(s));
   }
-  if (lane == 0) wave_n[wave] = kept;
-  __syncthreads();
-  if (tid == 0) counts[tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+  const int sum = tile_sum(kept, wave_n);
+  if (tid == 0) counts[tile] = sum;
 }
 
 }  // namespace
@@ -232,19 +209,19 @@ int launch_radius_outliers(const OutlierParams& p, void* scratch, hipStream_t s)
   const int nb = tiles_of(p.n);
   const size_t quads = slots / 4;
   const unsigned long long mask = (unsigned long long)(slots - 1);
-  const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kThreads - 1) / kThreads, 256 * 32);
-  hipLaunchKernelGGL(outlier_reset_kernel, dim3(reset_grid), dim3(kThreads), 0, s, (ulonglong2*)v.keys, (uint4*)v.cnt, (uint4*)v.start,
+  const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kTileThreads - 1) / kTileThreads, 256 * 32);
+  hipLaunchKernelGGL(outlier_reset_kernel, dim3(reset_grid), dim3(kTileThreads), 0, s, (ulonglong2*)v.keys, (uint4*)v.cnt, (uint4*)v.start,
                      (uint4*)v.fill, quads, v.flags, p.dropped);
   MD_HIP(hipGetLastError());
   if (p.n > 0) {
-    const unsigned rows_grid = (unsigned)((p.n + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(outlier_insert_kernel, dim3(rows_grid), dim3(kThreads), 0, s, p, v.keys, v.cnt, v.slot, mask, v.flags);
+    const unsigned rows_grid = (unsigned)((p.n + kTileThreads - 1) / kTileThreads);
+    hipLaunchKernelGGL(outlier_insert_kernel, dim3(rows_grid), dim3(kTileThreads), 0, s, p, v.keys, v.cnt, v.slot, mask, v.flags);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(outlier_alloc_kernel, dim3((unsigned)(slots / kThreads)), dim3(kThreads), 0, s, v.cnt, v.start, v.flags);
+    hipLaunchKernelGGL(outlier_alloc_kernel, dim3((unsigned)(slots / kTileThreads)), dim3(kTileThreads), 0, s, v.cnt, v.start, v.flags);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(outlier_fill_kernel, dim3(rows_grid), dim3(kThreads), 0, s, p, v.start, v.fill, v.slot, v.pos, v.bucket, v.flags);
+    hipLaunchKernelGGL(outlier_fill_kernel, dim3(rows_grid), dim3(kTileThreads), 0, s, p, v.start, v.fill, v.slot, v.pos, v.bucket, v.flags);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(outlier_search_kernel, dim3(nb), dim3(kThreads), 0, s, p, v.keys, v.cnt, v.start, v.slot, v.pos, v.bucket, mask, v.bits,
+    hipLaunchKernelGGL(outlier_search_kernel, dim3(nb), dim3(kTileThreads), 0, s, p, v.keys, v.cnt, v.start, v.slot, v.pos, v.bucket, mask, v.bits,
                        v.counts);
     MD_HIP(hipGetLastError());
   }

@@ -7,24 +7,17 @@
 // the surface normal of the pixel's one ring (pixel_normal) and the grazing-angle test in them. The forms without normals are
 // the kernels they were before and compile to the same instructions.
 //
-// The list keeps the (view, row, column) order without atomics: classify leaves one 64-bit ballot word per wave and step
-// (bit l = lane l's pixel enters the list) and one count per workgroup; scan turns the counts into exclusive offsets and
-// the per-view totals; scatter ranks a pixel by the popcount of the lower bits of its word, the words before it in the
-// workgroup and the workgroup's offset.
+// The list keeps the (view, row, column) order without atomics: tile_compact.h's ordered compaction (classify, scan, scatter)
+// over a grid of (tiles, B) workgroups, a tile's words at bits + (b * tiles + tile) * 64.
 #include <cfloat>
 #include <cmath>
 
-#include "ops.h"
 #include "points_math.h"
+#include "tile_compact.h"
 
 namespace md {
 
 namespace {
-
-constexpr int kThreads = 256;                // 4 waves of 64
-constexpr int kSteps = 16;                   // pixels per thread
-constexpr int kTile = kThreads * kSteps;     // 4096 pixels per workgroup: pixel = tile * 4096 + step * 256 + thread
-constexpr int kWords = kTile / 64;           // 64 ballot words per workgroup: word = step * 4 + wave
 
 // a neighbour that is not finite or <= 0 is ignored
 __device__ __forceinline__ bool edge_ok(float d, float dn, float rtol) {
@@ -130,13 +123,13 @@ __device__ __forceinline__ NormalsParams normals_of(const NormalsParams& q) { re
 // Q = {NormalsParams}: the normals form (q.min_cos enters the validity, q.normal_map is written beside the point map).
 // Q = {}: the form without normals, with the arguments, and so the instructions, the kernel had before the normals existed.
 template <class... Q>
-__global__ void __launch_bounds__(kThreads) points_classify_kernel(PointsParams p, unsigned long long* __restrict__ bits,
+__global__ void __launch_bounds__(kTileThreads) points_classify_kernel(PointsParams p, unsigned long long* __restrict__ bits,
                                                                    int* __restrict__ counts, Q... qs) {
   constexpr bool kN = sizeof...(Q) == 1;
   const NormalsParams q = normals_of(qs...);
-  __shared__ int wave_n[kThreads / 64];
-  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const long hw = (long)p.H * p.W;
+  __shared__ int wave_n[kTileWaves];
+  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+  const long hw = (long)p.H * p.W, blk = (long)b * gridDim.x + tile;
   const float* dv = p.depth + (long)b * hw;
   const float* cv = p.conf ? p.conf + (long)b * hw : nullptr;
   const bool dense = p.point_map || p.mask || (kN && q.normal_map);
@@ -144,8 +137,8 @@ __global__ void __launch_bounds__(kThreads) points_classify_kernel(PointsParams 
   Camera cam;
   if (kN || p.point_map) cam = load_camera(p.K, p.focal, p.world ? p.E : nullptr, p.H, p.W, b);
   int n = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long i = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long i = tile_item(tile, s);
     bool ok = false, in_list = false;
     if (i < hw) {
       const int v = (int)(i / p.W), u = (int)(i % p.W);
@@ -178,81 +171,46 @@ __global__ void __launch_bounds__(kThreads) points_classify_kernel(PointsParams 
         }
       }
     }
-    if (list) {
-      const unsigned long long word = __ballot(in_list);
-      if (lane == 0) bits[((long)b * gridDim.x + tile) * kWords + s * (kThreads / 64) + wave] = word;
-      n += __popcll(word);  // the same in every lane of the wave
-    }
+    if (list) n += ballot_step(in_list, bits + blk * kTileWords + tile_word(s));
   }
   if (!list) return;
-  if (lane == 0) wave_n[wave] = n;
-  __syncthreads();
-  if (tid == 0) counts[(long)b * gridDim.x + tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0) counts[blk] = sum;
 }
 
 // one workgroup: offsets[i] = sum of counts[0 .. i), offsets[n] = the total; count[b] = points of view b, count[B] = total
-__global__ void __launch_bounds__(kThreads) points_scan_kernel(const int* __restrict__ counts, int n, int tiles, int B,
+__global__ void __launch_bounds__(kTileThreads) points_scan_kernel(const int* __restrict__ counts, int n, int tiles, int B,
                                                                int* __restrict__ offsets, int32_t* __restrict__ count) {
-  __shared__ int part[kThreads];
-  const int tid = threadIdx.x;
-  const int per = (n + kThreads - 1) / kThreads;
-  const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += counts[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < kThreads; d <<= 1) {  // inclusive scan of the 256 chunk sums
-    const int v = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - sum;
-  for (int i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  if (tid == kThreads - 1) offsets[n] = part[tid];
-  __syncthreads();  // the offsets this workgroup wrote are visible to all of it
-  for (int b = tid; b < B; b += kThreads) count[b] = offsets[(b + 1) * tiles] - offsets[b * tiles];
-  if (tid == 0) count[B] = offsets[n];
+  __shared__ int part[kTileThreads];
+  scan_tile_counts(counts, n, offsets, part);
+  view_totals(offsets, n, tiles, B, count);
 }
 
 // Q = {NormalsParams}: the normals form writes q.normals; it recomputes the normal of a listed pixel with classify's own function, so a list
 // row equals the dense map at its pixel
 template <class... Q>
-__global__ void __launch_bounds__(kThreads) points_scatter_kernel(PointsParams p, const unsigned long long* __restrict__ bits,
+__global__ void __launch_bounds__(kTileThreads) points_scatter_kernel(PointsParams p, const unsigned long long* __restrict__ bits,
                                                                   const int* __restrict__ offsets, Q... qs) {
   constexpr bool kN = sizeof...(Q) == 1;
   const NormalsParams q = normals_of(qs...);
-  __shared__ int word_off[kWords];
-  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  __shared__ int word_off[kTileWords];
+  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const long blk = (long)b * gridDim.x + tile;
-  const unsigned long long* words = bits + blk * kWords;
-  if (tid < kWords) {  // wave 0: exclusive scan of the 64 word popcounts (word order = pixel order)
-    const int c = __popcll(words[tid]);
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    word_off[tid] = incl - c;
-  }
+  const unsigned long long* words = bits + blk * kTileWords;
+  if (tid < kTileWords) scan_word_counts(__popcll(words[tid]), word_off);
   __syncthreads();
   const long base = offsets[blk];
   if (base >= p.capacity) return;  // everything of this workgroup lies beyond the capacity
   const long hw = (long)p.H * p.W;
   const float* dv = p.depth + (long)b * hw;
   const Camera cam = load_camera(p.K, p.focal, p.world ? p.E : nullptr, p.H, p.W, b);
-  for (int s = 0; s < kSteps; ++s) {
-    const int w = s * (kThreads / 64) + wave;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const int w = tile_word(s);
     const unsigned long long word = words[w];
     if (!((word >> lane) & 1ull)) continue;
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
-    const long idx = base + word_off[w] + below;
+    const long idx = base + word_off[w] + lane_rank(word);
     if (idx >= p.capacity) continue;
-    const long i = (long)tile * kTile + s * kThreads + tid;  // < hw: the bit is only ever set for a pixel of the image
+    const long i = tile_item(tile, s);  // < hw: the bit is only ever set for a pixel of the image
     const int v = (int)(i / p.W), u = (int)(i % p.W);
     if (p.xyz) {
       float q[3];
@@ -278,14 +236,11 @@ __global__ void __launch_bounds__(kThreads) points_scatter_kernel(PointsParams p
   }
 }
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-inline int tiles_of(int H, int W) { return (int)(((long)H * W + kTile - 1) / kTile); }
-
 }  // namespace
 
 size_t points_scratch_bytes(int B, int H, int W) {
-  const size_t nb = (size_t)B * tiles_of(H, W);
-  return up256(nb * kWords * 8) + up256(nb * 4) + up256((nb + 1) * 4);
+  const size_t nb = (size_t)B * tiles_of((long)H * W);
+  return up256(nb * kTileWords * 8) + up256(nb * 4) + up256((nb + 1) * 4);
 }
 
 int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s, const NormalsParams* nrm) {
@@ -296,21 +251,21 @@ int launch_unproject(const PointsParams& p, void* scratch, hipStream_t s, const 
   const bool dense = p.point_map || p.mask || q.normal_map, list = p.count != nullptr;
   if (!dense && !list) return MD_OK;
   if (list && !scratch) MD_FAIL(MD_ERR_INVALID_ARG, "unproject: the list needs its scratch buffer");
-  const int tiles = tiles_of(p.H, p.W);
+  const int tiles = tiles_of((long)p.H * p.W);
   const size_t nb = (size_t)p.B * tiles;
   unsigned long long* bits = (unsigned long long*)scratch;
-  int* counts = list ? (int*)((char*)scratch + up256(nb * kWords * 8)) : nullptr;
+  int* counts = list ? (int*)((char*)scratch + up256(nb * kTileWords * 8)) : nullptr;
   int* offsets = list ? (int*)((char*)counts + up256(nb * 4)) : nullptr;
   const dim3 grid(tiles, p.B);
-  if (classify_normals) hipLaunchKernelGGL(points_classify_kernel<NormalsParams>, grid, dim3(kThreads), 0, s, p, bits, counts, q);
-  else hipLaunchKernelGGL(points_classify_kernel<>, grid, dim3(kThreads), 0, s, p, bits, counts);
+  if (classify_normals) hipLaunchKernelGGL(points_classify_kernel<NormalsParams>, grid, dim3(kTileThreads), 0, s, p, bits, counts, q);
+  else hipLaunchKernelGGL(points_classify_kernel<>, grid, dim3(kTileThreads), 0, s, p, bits, counts);
   MD_HIP(hipGetLastError());
   if (!list) return MD_OK;
-  hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kThreads), 0, s, counts, (int)nb, tiles, p.B, offsets, p.count);
+  hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kTileThreads), 0, s, counts, (int)nb, tiles, p.B, offsets, p.count);
   MD_HIP(hipGetLastError());
   if (!p.xyz && !p.rgb_out && !p.conf_out && !q.normals) return MD_OK;  // counts only
-  if (q.normals) hipLaunchKernelGGL(points_scatter_kernel<NormalsParams>, grid, dim3(kThreads), 0, s, p, bits, offsets, q);
-  else hipLaunchKernelGGL(points_scatter_kernel<>, grid, dim3(kThreads), 0, s, p, bits, offsets);
+  if (q.normals) hipLaunchKernelGGL(points_scatter_kernel<NormalsParams>, grid, dim3(kTileThreads), 0, s, p, bits, offsets, q);
+  else hipLaunchKernelGGL(points_scatter_kernel<>, grid, dim3(kTileThreads), 0, s, p, bits, offsets);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

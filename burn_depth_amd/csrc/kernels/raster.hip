@@ -22,8 +22,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ops.h"
 #include "points_math.h"
+#include "tile_compact.h"
 
 #ifndef MD_RASTER_INLINE_PIXELS
 #define MD_RASTER_INLINE_PIXELS 64  // the best of 4, 16 and 64
@@ -33,10 +33,7 @@ namespace md {
 
 namespace {
 
-constexpr int kThreads = 256;  // 4 waves of 64
-constexpr int kCams = 64;      // target cameras of one setup workgroup (4 KiB of LDS)
-constexpr int kSteps = 16;     // pixels per thread of the resolve kernel
-constexpr int kTile = kThreads * kSteps;
+constexpr int kCams = 64;  // target cameras of one setup workgroup (4 KiB of LDS)
 constexpr int kMaxGridY = 65535;
 constexpr int kInlinePixels = MD_RASTER_INLINE_PIXELS;
 constexpr int kLargeBlocks = 1024;               // the fixed grid of the large kernel: 4096 waves
@@ -44,15 +41,6 @@ constexpr int kDefaultQueue = 1 << 20;           // (face, target) pairs, 8 byte
 constexpr unsigned long long kEmpty = ~0ull;
 
 int g_queue_capacity = 0;  // md_debug_raster_queue: 0 = kDefaultQueue
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-// the live faces of the call: the device count word, never more than the faces the launch covers
-__device__ __forceinline__ int live_faces(const RasterParams& p) {
-  if (!p.count) return p.nf;
-  const int t = p.count[0];
-  return t < 0 ? 0 : (t < p.nf ? t : p.nf);
-}
 
 struct Face {
   long X[3], Y[3];  // the vertices, snapped to 1/256 pixel
@@ -137,12 +125,11 @@ __device__ __forceinline__ void draw_pixel(const RasterParams& p, const Face& s,
 }
 
 // pairs = ceil(T*H*W / 2): the key buffer is a multiple of 16 bytes (raster_scratch_bytes)
-__global__ void __launch_bounds__(kThreads) raster_clear_kernel(ulonglong2* __restrict__ keys, size_t pairs, int32_t* __restrict__ filled,
+__global__ void __launch_bounds__(kTileThreads) raster_clear_kernel(ulonglong2* __restrict__ keys, size_t pairs, int32_t* __restrict__ filled,
                                                                 int32_t* __restrict__ skipped, int* __restrict__ queue_n, int T) {
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x; q < pairs; q += stride) keys[q] = make_ulonglong2(kEmpty, kEmpty);
+  fill_keys(keys, pairs);
   if (blockIdx.x != 0) return;
-  for (int t = threadIdx.x; t <= T; t += kThreads) {
+  for (int t = threadIdx.x; t <= T; t += kTileThreads) {
     if (filled) filled[t] = 0;
     if (skipped) skipped[t] = 0;
   }
@@ -150,7 +137,7 @@ __global__ void __launch_bounds__(kThreads) raster_clear_kernel(ulonglong2* __re
 }
 
 // grid (ceil(nf / 256), groups of 64 targets); t0 = the first target of group 0 of this launch
-__global__ void __launch_bounds__(kThreads) raster_setup_kernel(RasterParams p, unsigned long long* __restrict__ keys, int* __restrict__ queue_n,
+__global__ void __launch_bounds__(kTileThreads) raster_setup_kernel(RasterParams p, unsigned long long* __restrict__ keys, int* __restrict__ queue_n,
                                                                 int2* __restrict__ queue, int capacity, int t0) {
   __shared__ Camera cams[kCams];
   __shared__ int skip_n[kCams];
@@ -162,9 +149,9 @@ __global__ void __launch_bounds__(kThreads) raster_setup_kernel(RasterParams p, 
     skip_n[tid] = 0;
   }
   __syncthreads();
-  const long f = (long)blockIdx.x * kThreads + tid;
+  const long f = (long)blockIdx.x * kTileThreads + tid;
   const long hw = (long)p.H * p.W;
-  if (f < live_faces(p)) {
+  if (f < live_count(p.count, 0, p.nf)) {
     for (int j = 0; j < nt; ++j) {
       Face s;
       const int rc = setup_face(p, cams[j], (int)f, s);
@@ -192,10 +179,10 @@ __global__ void __launch_bounds__(kThreads) raster_setup_kernel(RasterParams p, 
 }
 
 // grid kLargeBlocks: wave w of the grid takes the queue entries w, w + waves, ...
-__global__ void __launch_bounds__(kThreads) raster_large_kernel(RasterParams p, unsigned long long* __restrict__ keys, const int* __restrict__ queue_n,
+__global__ void __launch_bounds__(kTileThreads) raster_large_kernel(RasterParams p, unsigned long long* __restrict__ keys, const int* __restrict__ queue_n,
                                                                 const int2* __restrict__ queue, int capacity) {
   const int lane = threadIdx.x & 63;
-  const int wave = (int)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), waves = (int)gridDim.x * (kThreads / 64);
+  const int wave = (int)blockIdx.x * kTileWaves + (threadIdx.x >> 6), waves = (int)gridDim.x * kTileWaves;
   int n = *queue_n;  // pushes beyond the capacity were drawn in place
   n = n < capacity ? n : capacity;
   const long hw = (long)p.H * p.W;
@@ -212,16 +199,16 @@ __global__ void __launch_bounds__(kThreads) raster_large_kernel(RasterParams p, 
 }
 
 // grid T * ceil(H W / 4096): a workgroup lies inside one target
-__global__ void __launch_bounds__(kThreads) raster_resolve_kernel(RasterParams p, const unsigned long long* __restrict__ keys, int per_target) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+__global__ void __launch_bounds__(kTileThreads) raster_resolve_kernel(RasterParams p, const unsigned long long* __restrict__ keys, int per_target) {
+  __shared__ int wave_n[kTileWaves];
+  const int tid = threadIdx.x;
   const int t = (int)(blockIdx.x / (unsigned)per_target);
   const long hw = (long)p.H * p.W;
   Camera c = {};
   if (p.rgb_out) c = load_camera(p.K, p.focal, p.E, p.H, p.W, t);
   int n = 0;
-  for (int st = 0; st < kSteps; ++st) {
-    const long px = (long)(blockIdx.x % (unsigned)per_target) * kTile + st * kThreads + tid;
+  for (int st = 0; st < kTileSteps; ++st) {
+    const long px = tile_item(blockIdx.x % (unsigned)per_target, st);
     bool hit = false;
     if (px < hw) {
       const long o = (long)t * hw + px;
@@ -250,14 +237,10 @@ __global__ void __launch_bounds__(kThreads) raster_resolve_kernel(RasterParams p
     if (p.filled) n += __popcll(__ballot(hit));  // the same in every lane of the wave
   }
   if (!p.filled) return;
-  if (lane == 0) wave_n[wave] = n;
-  __syncthreads();
-  if (tid == 0) {
-    const int sum = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-    if (sum) {
-      atomicAdd(&p.filled[t], sum);
-      atomicAdd(&p.filled[p.T], sum);
-    }
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0 && sum) {
+    atomicAdd(&p.filled[t], sum);
+    atomicAdd(&p.filled[p.T], sum);
   }
 }
 
@@ -293,22 +276,22 @@ int launch_render_mesh(const RasterParams& p, void* scratch, int queue_entries, 
   int* queue_n = (int*)((char*)scratch + keys_bytes(p.T, p.H, p.W));
   int2* queue = (int2*)((char*)queue_n + 256);
   const size_t total = (size_t)p.T * p.H * p.W, pairs = (total + 1) / 2;
-  const unsigned clear_grid = (unsigned)std::min<size_t>((pairs + kThreads - 1) / kThreads, 256 * 32);
-  hipLaunchKernelGGL(raster_clear_kernel, dim3(clear_grid), dim3(kThreads), 0, s, (ulonglong2*)keys, pairs, p.filled, p.skipped, queue_n, p.T);
+  const unsigned clear_grid = (unsigned)std::min<size_t>((pairs + kTileThreads - 1) / kTileThreads, 256 * 32);
+  hipLaunchKernelGGL(raster_clear_kernel, dim3(clear_grid), dim3(kTileThreads), 0, s, (ulonglong2*)keys, pairs, p.filled, p.skipped, queue_n, p.T);
   MD_HIP(hipGetLastError());
   if (p.nf > 0) {
-    const unsigned blocks = (unsigned)(((long)p.nf + kThreads - 1) / kThreads);
+    const unsigned blocks = (unsigned)(((long)p.nf + kTileThreads - 1) / kTileThreads);
     const long groups = ((long)p.T + kCams - 1) / kCams;
     for (long g = 0; g < groups; g += kMaxGridY) {
       const unsigned gy = (unsigned)std::min<long>(groups - g, kMaxGridY);
-      hipLaunchKernelGGL(raster_setup_kernel, dim3(blocks, gy), dim3(kThreads), 0, s, p, keys, queue_n, queue, queue_entries, (int)(g * kCams));
+      hipLaunchKernelGGL(raster_setup_kernel, dim3(blocks, gy), dim3(kTileThreads), 0, s, p, keys, queue_n, queue, queue_entries, (int)(g * kCams));
       MD_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(raster_large_kernel, dim3(kLargeBlocks), dim3(kThreads), 0, s, p, keys, queue_n, queue, queue_entries);
+    hipLaunchKernelGGL(raster_large_kernel, dim3(kLargeBlocks), dim3(kTileThreads), 0, s, p, keys, queue_n, queue, queue_entries);
     MD_HIP(hipGetLastError());
   }
-  const int per_target = (int)(((long)p.H * p.W + kTile - 1) / kTile);
-  hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)((long)p.T * per_target)), dim3(kThreads), 0, s, p, keys, per_target);
+  const int per_target = tiles_of((long)p.H * p.W);
+  hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)((long)p.T * per_target)), dim3(kTileThreads), 0, s, p, keys, per_target);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

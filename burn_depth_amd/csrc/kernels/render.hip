@@ -16,8 +16,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ops.h"
 #include "points_math.h"
+#include "tile_compact.h"
 
 #ifndef MD_RENDER_PEEK
 #define MD_RENDER_PEEK 1  // 1: load the pixel's key first and skip the atomic when the candidate cannot win
@@ -27,39 +27,28 @@ namespace md {
 
 namespace {
 
-constexpr int kThreads = 256;  // 4 waves of 64
-constexpr int kCams = 64;      // target cameras of one splat workgroup (4 KiB of LDS)
-constexpr int kSteps = 16;     // pixels per thread of the resolve kernel
-constexpr int kTile = kThreads * kSteps;
+constexpr int kCams = 64;  // target cameras of one splat workgroup (4 KiB of LDS)
 constexpr int kMaxGridY = 65535;
 constexpr unsigned long long kEmpty = ~0ull;
 
-// the live rows of the call: the device count word, never more than the rows the launch covers
-__device__ __forceinline__ int live_rows(const RenderParams& p) {
-  if (!p.count) return p.n;
-  const int t = p.count[0];
-  return t < 0 ? 0 : (t < p.n ? t : p.n);
-}
-
 // pairs = ceil(T*H*W / 2): the key buffer is a multiple of 16 bytes (render_scratch_bytes)
-__global__ void __launch_bounds__(kThreads) render_clear_kernel(ulonglong2* __restrict__ keys, size_t pairs, int32_t* __restrict__ filled,
+__global__ void __launch_bounds__(kTileThreads) render_clear_kernel(ulonglong2* __restrict__ keys, size_t pairs, int32_t* __restrict__ filled,
                                                                 int T) {
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x; q < pairs; q += stride) keys[q] = make_ulonglong2(kEmpty, kEmpty);
+  fill_keys(keys, pairs);
   if (filled && blockIdx.x == 0)
-    for (int t = threadIdx.x; t <= T; t += kThreads) filled[t] = 0;
+    for (int t = threadIdx.x; t <= T; t += kTileThreads) filled[t] = 0;
 }
 
 // grid (ceil(n / 256), groups of 64 targets); t0 = the first target of group 0 of this launch
-__global__ void __launch_bounds__(kThreads) render_splat_kernel(RenderParams p, unsigned long long* __restrict__ keys, int t0) {
+__global__ void __launch_bounds__(kTileThreads) render_splat_kernel(RenderParams p, unsigned long long* __restrict__ keys, int t0) {
   __shared__ Camera cams[kCams];
   const int tid = threadIdx.x;
   const int tbase = t0 + (int)blockIdx.y * kCams;
   const int nt = p.T - tbase < kCams ? p.T - tbase : kCams;
   if (tid < nt) cams[tid] = load_camera(p.K, p.focal, p.E, p.H, p.W, tbase + tid);
   __syncthreads();
-  const long i = (long)blockIdx.x * kThreads + tid;
-  if (i >= live_rows(p)) return;
+  const long i = (long)blockIdx.x * kTileThreads + tid;
+  if (i >= live_count(p.count, 0, p.n)) return;
   const float x = p.xyz[i * 3], y = p.xyz[i * 3 + 1], z = p.xyz[i * 3 + 2];
   if (!(isfinite(x) && isfinite(y) && isfinite(z))) return;
   const float fw = (float)p.W, fh = (float)p.H;
@@ -94,14 +83,14 @@ __global__ void __launch_bounds__(kThreads) render_splat_kernel(RenderParams p, 
 }
 
 // grid T * ceil(H W / 4096): a workgroup lies inside one target
-__global__ void __launch_bounds__(kThreads) render_resolve_kernel(RenderParams p, const unsigned long long* __restrict__ keys, int per_target) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+__global__ void __launch_bounds__(kTileThreads) render_resolve_kernel(RenderParams p, const unsigned long long* __restrict__ keys, int per_target) {
+  __shared__ int wave_n[kTileWaves];
+  const int tid = threadIdx.x;
   const int t = (int)(blockIdx.x / (unsigned)per_target);
   const long hw = (long)p.H * p.W;
   int n = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long px = (long)(blockIdx.x % (unsigned)per_target) * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long px = tile_item(blockIdx.x % (unsigned)per_target, s);
     bool hit = false;
     if (px < hw) {
       const long o = (long)t * hw + px;
@@ -123,20 +112,16 @@ __global__ void __launch_bounds__(kThreads) render_resolve_kernel(RenderParams p
     if (p.filled) n += __popcll(__ballot(hit));  // the same in every lane of the wave
   }
   if (!p.filled) return;
-  if (lane == 0) wave_n[wave] = n;
-  __syncthreads();
-  if (tid == 0) {
-    const int sum = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-    if (sum) {
-      atomicAdd(&p.filled[t], sum);
-      atomicAdd(&p.filled[p.T], sum);
-    }
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0 && sum) {
+    atomicAdd(&p.filled[t], sum);
+    atomicAdd(&p.filled[p.T], sum);
   }
 }
 
 }  // namespace
 
-size_t render_scratch_bytes(int T, int H, int W) { return ((size_t)T * H * W * 8 + 255) / 256 * 256; }
+size_t render_scratch_bytes(int T, int H, int W) { return up256((size_t)T * H * W * 8); }
 
 int launch_render_points(const RenderParams& p, void* scratch, hipStream_t s) {
   if (!scratch) MD_FAIL(MD_ERR_INVALID_ARG, "render_points: no scratch buffer");
@@ -148,20 +133,20 @@ int launch_render_points(const RenderParams& p, void* scratch, hipStream_t s) {
   if (p.rgb_out && !p.rgb) MD_FAIL(MD_ERR_INVALID_ARG, "render_points: an rgb output needs an rgb row");
   unsigned long long* keys = (unsigned long long*)scratch;
   const size_t total = (size_t)p.T * p.H * p.W, pairs = (total + 1) / 2;
-  const unsigned clear_grid = (unsigned)std::min<size_t>((pairs + kThreads - 1) / kThreads, 256 * 32);
-  hipLaunchKernelGGL(render_clear_kernel, dim3(clear_grid), dim3(kThreads), 0, s, (ulonglong2*)keys, pairs, p.filled, p.T);
+  const unsigned clear_grid = (unsigned)std::min<size_t>((pairs + kTileThreads - 1) / kTileThreads, 256 * 32);
+  hipLaunchKernelGGL(render_clear_kernel, dim3(clear_grid), dim3(kTileThreads), 0, s, (ulonglong2*)keys, pairs, p.filled, p.T);
   MD_HIP(hipGetLastError());
   if (p.n > 0) {
-    const unsigned blocks = (unsigned)(((long)p.n + kThreads - 1) / kThreads);
+    const unsigned blocks = (unsigned)(((long)p.n + kTileThreads - 1) / kTileThreads);
     const long groups = ((long)p.T + kCams - 1) / kCams;
     for (long g = 0; g < groups; g += kMaxGridY) {
       const unsigned gy = (unsigned)std::min<long>(groups - g, kMaxGridY);
-      hipLaunchKernelGGL(render_splat_kernel, dim3(blocks, gy), dim3(kThreads), 0, s, p, keys, (int)(g * kCams));
+      hipLaunchKernelGGL(render_splat_kernel, dim3(blocks, gy), dim3(kTileThreads), 0, s, p, keys, (int)(g * kCams));
       MD_HIP(hipGetLastError());
     }
   }
-  const int per_target = (int)(((long)p.H * p.W + kTile - 1) / kTile);
-  hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((long)p.T * per_target)), dim3(kThreads), 0, s, p, keys, per_target);
+  const int per_target = tiles_of((long)p.H * p.W);
+  hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((long)p.T * per_target)), dim3(kTileThreads), 0, s, p, keys, per_target);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

@@ -19,13 +19,12 @@
 #include <algorithm>
 
 #include "smooth_math.h"
-#include "voxel_math.h"
+#include "tile_compact.h"
 
 namespace md {
 
 namespace {
 
-constexpr int kThreads = kGridThreads;
 typedef unsigned long long u64;
 
 struct SmoothScratch {  // 256-byte aligned parts
@@ -38,42 +37,24 @@ struct SmoothScratch {  // 256-byte aligned parts
   size_t bytes;
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 SmoothScratch carve(void* base, int n) {
   SmoothScratch s;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* at = p;
-    p += up256(bytes);
-    return at;
-  };
-  s.k = (int64_t*)take((size_t)n * 24);
-  s.S = (u64*)take((size_t)n * 24);
-  s.open = (u64*)take((size_t)n * 8);
-  s.deg = (uint32_t*)take((size_t)n * 4);
-  s.flag = (int32_t*)take((size_t)n * 4);
-  s.stats = (int32_t*)take(256);
-  s.bytes = (size_t)(p - (char*)base);
+  Carver c(base);
+  s.k = c.take<int64_t>((size_t)n * 3);
+  s.S = c.take<u64>((size_t)n * 3);
+  s.open = c.take<u64>((size_t)n);
+  s.deg = c.take<uint32_t>((size_t)n);
+  s.flag = c.take<int32_t>((size_t)n);
+  s.stats = c.take<int32_t>(64);
+  s.bytes = c.bytes;
   return s;
 }
 
-__device__ __forceinline__ int live_of(const int32_t* __restrict__ count, int B, int n) {
-  if (!count) return n;
-  const int t = count[B];
-  return t < 0 ? 0 : (t < n ? t : n);
-}
-
-__device__ __forceinline__ void count_wave(bool bit, int32_t* counter) {
-  const u64 word = __ballot(bit);
-  if ((threadIdx.x & 63) == 0 && word) atomicAdd(counter, (int)__popcll(word));
-}
-
 // grid max(ceil(n / 256), 1)
-__global__ void __launch_bounds__(kThreads) smooth_quantise_kernel(SmoothParams p, SmoothScratch c, int32_t* __restrict__ stats) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+__global__ void __launch_bounds__(kTileThreads) smooth_quantise_kernel(SmoothParams p, SmoothScratch c, int32_t* __restrict__ stats) {
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < 5) stats[threadIdx.x] = 0;
-  if (i >= live_of(p.in_count, p.B, p.n)) return;
+  if (i >= live_count(p.in_count, p.B, p.n)) return;
   int64_t k[3] = {0, 0, 0};
   const bool in_range = smooth_quantise(p.xyz[i * 3], p.xyz[i * 3 + 1], p.xyz[i * 3 + 2], p.step, k);
   c.flag[i] = in_range ? 1 : 0;
@@ -87,11 +68,11 @@ __global__ void __launch_bounds__(kThreads) smooth_quantise_kernel(SmoothParams 
 }
 
 // grid ceil(nf / 256); no thread leaves before the ballots
-__global__ void __launch_bounds__(kThreads) smooth_topology_kernel(SmoothParams p, SmoothScratch c, int32_t* __restrict__ stats) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
+__global__ void __launch_bounds__(kTileThreads) smooth_topology_kernel(SmoothParams p, SmoothScratch c, int32_t* __restrict__ stats) {
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
   int kind = 0;
-  if (f < live_of(p.in_face_count, p.B, p.nf)) {
-    const int n = live_of(p.in_count, p.B, p.n);
+  if (f < live_count(p.in_face_count, p.B, p.nf)) {
+    const int n = live_count(p.in_count, p.B, p.n);
     const int v[3] = {p.faces[f * 3], p.faces[f * 3 + 1], p.faces[f * 3 + 2]};
     kind = smooth_face_kind(v[0], v[1], v[2], n, c.flag);
     if (kind == 0) {
@@ -102,8 +83,8 @@ __global__ void __launch_bounds__(kThreads) smooth_topology_kernel(SmoothParams 
       }
     }
   }
-  count_wave(kind == 1, stats);
-  count_wave(kind == 2, stats + 1);
+  wave_count_add(kind == 1, stats);
+  wave_count_add(kind == 2, stats + 1);
 }
 
 // the sum of x over the wave, in every lane
@@ -115,14 +96,14 @@ __device__ __forceinline__ u64 wave_sum(u64 x) {
 
 // grid ceil(nf / 256). kCross: the summed face normals instead of the neighbour sums. No thread leaves before the ballots.
 template <bool kCross>
-__global__ void __launch_bounds__(kThreads) smooth_accumulate_kernel(SmoothParams p, SmoothScratch c) {
-  const long f = (long)blockIdx.x * kThreads + threadIdx.x;
+__global__ void __launch_bounds__(kTileThreads) smooth_accumulate_kernel(SmoothParams p, SmoothScratch c) {
+  const long f = (long)blockIdx.x * kTileThreads + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool live = false;
   int v[3] = {-1, -1, -1};
   u64 add[3][3] = {};  // [corner][axis]
-  if (f < live_of(p.in_face_count, p.B, p.nf)) {
-    const int n = live_of(p.in_count, p.B, p.n);
+  if (f < live_count(p.in_face_count, p.B, p.nf)) {
+    const int n = live_count(p.in_count, p.B, p.n);
     v[0] = p.faces[f * 3]; v[1] = p.faces[f * 3 + 1]; v[2] = p.faces[f * 3 + 2];
     live = smooth_face_kind(v[0], v[1], v[2], n, c.flag) == 0;
     if (live) {
@@ -167,9 +148,9 @@ __global__ void __launch_bounds__(kThreads) smooth_accumulate_kernel(SmoothParam
 }
 
 // grid ceil(n / 256)
-__global__ void __launch_bounds__(kThreads) smooth_update_kernel(SmoothParams p, SmoothScratch c, double factor) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= live_of(p.in_count, p.B, p.n)) return;
+__global__ void __launch_bounds__(kTileThreads) smooth_update_kernel(SmoothParams p, SmoothScratch c, double factor) {
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  if (i >= live_count(p.in_count, p.B, p.n)) return;
   const uint32_t deg = c.deg[i];
   const bool pinned = smooth_pinned(deg, c.open[i], c.flag[i] != 0, p.pin_boundary);
 #pragma unroll
@@ -180,10 +161,10 @@ __global__ void __launch_bounds__(kThreads) smooth_update_kernel(SmoothParams p,
 }
 
 // grid ceil(n / 256); no thread leaves before the ballots
-__global__ void __launch_bounds__(kThreads) smooth_write_kernel(SmoothParams p, SmoothScratch c, int32_t* __restrict__ stats) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+__global__ void __launch_bounds__(kTileThreads) smooth_write_kernel(SmoothParams p, SmoothScratch c, int32_t* __restrict__ stats) {
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
   bool outside = false, open = false, moved = false;
-  if (i < live_of(p.in_count, p.B, p.n)) {
+  if (i < live_count(p.in_count, p.B, p.n)) {
     const float x[3] = {p.xyz[i * 3], p.xyz[i * 3 + 1], p.xyz[i * 3 + 2]};
     int64_t k0[3] = {0, 0, 0}, k[3];
     const bool in_range = smooth_quantise(x[0], x[1], x[2], p.step, k0);
@@ -207,9 +188,9 @@ __global__ void __launch_bounds__(kThreads) smooth_write_kernel(SmoothParams p, 
       }
     }
   }
-  count_wave(outside, stats + 2);
-  count_wave(open, stats + 3);
-  count_wave(moved, stats + 4);
+  wave_count_add(outside, stats + 2);
+  wave_count_add(open, stats + 3);
+  wave_count_add(moved, stats + 4);
 }
 
 }  // namespace
@@ -231,11 +212,11 @@ int launch_smooth_mesh(const SmoothParams& p, void* scratch, hipStream_t s) {
   const int n = p.n, nf = p.nf;
   const SmoothScratch c = carve(scratch, n);
   int32_t* stats = p.stats ? p.stats : c.stats;
-  const unsigned rows_grid = (unsigned)((n + kThreads - 1) / kThreads), faces_grid = (unsigned)((nf + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(smooth_quantise_kernel, dim3(std::max(rows_grid, 1u)), dim3(kThreads), 0, s, p, c, stats);
+  const unsigned rows_grid = (unsigned)((n + kTileThreads - 1) / kTileThreads), faces_grid = (unsigned)((nf + kTileThreads - 1) / kTileThreads);
+  hipLaunchKernelGGL(smooth_quantise_kernel, dim3(std::max(rows_grid, 1u)), dim3(kTileThreads), 0, s, p, c, stats);
   MD_HIP(hipGetLastError());
   if (nf > 0) {
-    hipLaunchKernelGGL(smooth_topology_kernel, dim3(faces_grid), dim3(kThreads), 0, s, p, c, stats);
+    hipLaunchKernelGGL(smooth_topology_kernel, dim3(faces_grid), dim3(kTileThreads), 0, s, p, c, stats);
     MD_HIP(hipGetLastError());
   }
   if (n == 0) return MD_OK;
@@ -243,17 +224,17 @@ int launch_smooth_mesh(const SmoothParams& p, void* scratch, hipStream_t s) {
     const int steps = p.mu != 0.f ? 2 * p.iterations : p.iterations;
     for (int t = 0; t < steps; ++t) {
       const double factor = (double)((p.mu != 0.f && (t & 1)) ? p.mu : p.lambda);
-      hipLaunchKernelGGL(smooth_accumulate_kernel<false>, dim3(faces_grid), dim3(kThreads), 0, s, p, c);
+      hipLaunchKernelGGL(smooth_accumulate_kernel<false>, dim3(faces_grid), dim3(kTileThreads), 0, s, p, c);
       MD_HIP(hipGetLastError());
-      hipLaunchKernelGGL(smooth_update_kernel, dim3(rows_grid), dim3(kThreads), 0, s, p, c, factor);
+      hipLaunchKernelGGL(smooth_update_kernel, dim3(rows_grid), dim3(kTileThreads), 0, s, p, c, factor);
       MD_HIP(hipGetLastError());
     }
     if (p.normals_out) {
-      hipLaunchKernelGGL(smooth_accumulate_kernel<true>, dim3(faces_grid), dim3(kThreads), 0, s, p, c);
+      hipLaunchKernelGGL(smooth_accumulate_kernel<true>, dim3(faces_grid), dim3(kTileThreads), 0, s, p, c);
       MD_HIP(hipGetLastError());
     }
   }
-  hipLaunchKernelGGL(smooth_write_kernel, dim3(rows_grid), dim3(kThreads), 0, s, p, c, stats);
+  hipLaunchKernelGGL(smooth_write_kernel, dim3(rows_grid), dim3(kTileThreads), 0, s, p, c, stats);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

@@ -12,18 +12,15 @@
 #include <cfloat>
 #include <cmath>
 
-#include "ops.h"
 #include "points_math.h"
+#include "tile_compact.h"
 
 namespace md {
 
 namespace {
 
-constexpr int kThreads = 256;             // 4 waves of 64
-constexpr int kSteps = 16;                // pixels per thread of the support kernel: the grid of points_classify_kernel
-constexpr int kTile = kThreads * kSteps;
 constexpr int kBins = 256;
-constexpr int kHistBlocks = 1024;         // 4 workgroups per CU: at most 1024 x 256 global adds per pass
+constexpr int kHistBlocks = 1024;  // 4 workgroups per CU: at most 1024 x 256 global adds per pass
 
 struct SelectState {
   unsigned prefix, mask;  // the bits of tau's pattern fixed so far
@@ -37,14 +34,14 @@ __device__ __forceinline__ bool conf_ok(float c) { return isfinite(c) && c >= 0.
 // -0 orders with +0
 __device__ __forceinline__ unsigned conf_key(float c) { return c == 0.f ? 0u : __float_as_uint(c); }
 
-__global__ void __launch_bounds__(kThreads) view_filter_hist_kernel(ViewFilterParams p, long total, int shift, unsigned* __restrict__ table,
+__global__ void __launch_bounds__(kTileThreads) view_filter_hist_kernel(ViewFilterParams p, long total, int shift, unsigned* __restrict__ table,
                                                                     const SelectState* __restrict__ st) {
   __shared__ unsigned bins[kBins];
   const int tid = threadIdx.x, lane = tid & 63;
   bins[tid] = 0u;
   __syncthreads();
   const unsigned prefix = st->prefix, mask = st->mask;
-  for (long base = (long)blockIdx.x * kThreads; base < total; base += (long)gridDim.x * kThreads) {  // uniform per workgroup
+  for (long base = (long)blockIdx.x * kTileThreads; base < total; base += (long)gridDim.x * kTileThreads) {  // uniform per workgroup
     const long i = base + tid;
     bool act = false;
     unsigned bin = 0u;
@@ -76,7 +73,7 @@ __global__ void __launch_bounds__(kThreads) view_filter_hist_kernel(ViewFilterPa
 }
 
 // one workgroup: the bin that holds rank k, then the table is cleared for the next pass. shift = 24 also counts N and derives k.
-__global__ void __launch_bounds__(kThreads) view_filter_select_kernel(unsigned* __restrict__ table, SelectState* __restrict__ st, int shift,
+__global__ void __launch_bounds__(kTileThreads) view_filter_select_kernel(unsigned* __restrict__ table, SelectState* __restrict__ st, int shift,
                                                                       int q, float* __restrict__ tau_out) {
   __shared__ long long incl[kBins];
   const int tid = threadIdx.x;
@@ -119,11 +116,11 @@ __device__ __forceinline__ bool survivor(const ViewFilterParams& p, long o, floa
   return conf_ok(c) && c >= tau;
 }
 
-// grid (tiles, B). The B cameras sit in LDS; a thread walks its 16 pixels and, for each survivor, the B - 1 other views.
-__global__ void __launch_bounds__(kThreads) view_filter_support_kernel(ViewFilterParams p, const SelectState* __restrict__ st) {
+// grid (tiles, B), the grid of points_classify_kernel. The B cameras sit in LDS; a thread walks its 16 pixels and, for each survivor, the B - 1 other views.
+__global__ void __launch_bounds__(kTileThreads) view_filter_support_kernel(ViewFilterParams p, const SelectState* __restrict__ st) {
   __shared__ Camera cams[kViewFilterMaxViews];
-  __shared__ int wave_n[kThreads / 64];
-  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  __shared__ int wave_n[kTileWaves];
+  const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
   const bool views = p.rtol > 0.f;
   if (views && tid < p.B) cams[tid] = load_camera(p.K, p.focal, p.E, p.H, p.W, tid);
   __syncthreads();
@@ -131,8 +128,8 @@ __global__ void __launch_bounds__(kThreads) view_filter_support_kernel(ViewFilte
   const long hw = (long)p.H * p.W;
   const float fw = (float)p.W, fh = (float)p.H;
   int n = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long i = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long i = tile_item(tile, s);
     bool keep = false;
     if (i < hw) {
       const long o = (long)b * hw + i;
@@ -167,12 +164,8 @@ __global__ void __launch_bounds__(kThreads) view_filter_support_kernel(ViewFilte
     if (p.kept) n += __popcll(__ballot(keep));  // the same in every lane of the wave
   }
   if (!p.kept) return;
-  if (lane == 0) wave_n[wave] = n;
-  __syncthreads();
-  if (tid == 0) {
-    const int sum = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-    if (sum) atomicAdd(&p.kept[b], sum);
-  }
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0 && sum) atomicAdd(&p.kept[b], sum);
 }
 
 __global__ void view_filter_total_kernel(int32_t* __restrict__ kept, int B) {
@@ -198,19 +191,19 @@ int launch_view_filter(const ViewFilterParams& p, void* scratch, hipStream_t s) 
   MD_HIP(hipMemsetAsync(scratch, 0, view_filter_scratch_bytes(), s));
   if (p.kept) MD_HIP(hipMemsetAsync(p.kept, 0, (size_t)(p.B + 1) * 4, s));
   if (p.q > 0) {
-    const int blocks = (int)std::min<long>((total + kThreads - 1) / kThreads, kHistBlocks);
+    const int blocks = (int)std::min<long>((total + kTileThreads - 1) / kTileThreads, kHistBlocks);
     for (int shift = 24; shift >= 0; shift -= 8) {
-      hipLaunchKernelGGL(view_filter_hist_kernel, dim3(blocks), dim3(kThreads), 0, s, p, total, shift, table, st);
+      hipLaunchKernelGGL(view_filter_hist_kernel, dim3(blocks), dim3(kTileThreads), 0, s, p, total, shift, table, st);
       MD_HIP(hipGetLastError());
-      hipLaunchKernelGGL(view_filter_select_kernel, dim3(1), dim3(kThreads), 0, s, table, st, shift, p.q, p.tau);
+      hipLaunchKernelGGL(view_filter_select_kernel, dim3(1), dim3(kTileThreads), 0, s, table, st, shift, p.q, p.tau);
       MD_HIP(hipGetLastError());
     }
   } else if (p.tau) {
     MD_HIP(hipMemsetAsync(p.tau, 0, 4, s));
   }
   if (!p.depth_out && !p.support && !p.kept) return MD_OK;  // tau only
-  const int tiles = (int)(((long)p.H * p.W + kTile - 1) / kTile);
-  hipLaunchKernelGGL(view_filter_support_kernel, dim3(tiles, p.B), dim3(kThreads), 0, s, p, st);
+  const int tiles = tiles_of((long)p.H * p.W);
+  hipLaunchKernelGGL(view_filter_support_kernel, dim3(tiles, p.B), dim3(kTileThreads), 0, s, p, st);
   MD_HIP(hipGetLastError());
   if (p.kept) {
     hipLaunchKernelGGL(view_filter_total_kernel, dim3(1), dim3(64), 0, s, p.kept, p.B);

@@ -10,9 +10,9 @@
 //   select   keep[i] = the low word of the slot's rank names i; one 64-bit ballot word per wave and step, one count per workgroup
 //   scan     one workgroup: exclusive offsets of the workgroup counts; the survivors of every view from the ballot words at
 //            the view boundaries of the input (the unthinned count[] prefix)
-//   scatter  output row = offset + popcounts below (mbcnt), as points.hip's scatter; copies the rows, index and weight
-// The tile layout of select / scatter is points.hip's (row = tile * 4096 + step * 256 + thread, word = step * 4 + wave), so the
-// words of a tile are in row order. No thread waits on another: a probe claims a slot, finds its key or moves on, and the loop
+//   scatter  output row = offset + popcounts below; copies the rows, index and weight
+// select, scan and scatter are tile_compact.h's ordered compaction over a one-dimensional grid of tiles; decimate.hip and
+// components.hip read the words and offsets it leaves. No thread waits on another: a probe claims a slot, finds its key or moves on, and the loop
 // is bounded by the table size.
 #include <algorithm>
 #include <cmath>
@@ -23,9 +23,7 @@ namespace md {
 
 namespace {
 
-// the tile layout, the cell key and the probe are shared with the outlier removal (voxel_math.h)
-constexpr int kThreads = kGridThreads, kSteps = kGridSteps, kTile = kGridTile, kWords = kGridWords;
-constexpr unsigned long long kEmpty = kGridEmpty;
+// the cell key and the probe are shared with the outlier removal (voxel_math.h)
 
 struct VoxelScratch {  // the parts of the scratch buffer, 256-byte aligned
   unsigned long long* keys;
@@ -39,45 +37,29 @@ struct VoxelScratch {  // the parts of the scratch buffer, 256-byte aligned
   size_t bytes;
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-inline int tiles_of(int n) { return (n + kTile - 1) / kTile; }
-
 VoxelScratch carve(void* base, int n) {
   const size_t slots = voxel_table_slots(n), nb = (size_t)tiles_of(n);
   VoxelScratch s;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* at = p;
-    p += up256(bytes);
-    return at;
-  };
-  s.keys = (unsigned long long*)take(slots * 8);
-  s.rank = (unsigned long long*)take(slots * 8);
-  s.cnt = (unsigned*)take(slots * 4);
-  s.slot = (int*)take((size_t)n * 4);
-  s.bits = (unsigned long long*)take(nb * kWords * 8);
-  s.counts = (int*)take(nb * 4);
-  s.offsets = (int*)take((nb + 1) * 4);
-  s.flags = (int*)take(256);
-  s.bytes = (size_t)(p - (char*)base);
+  Carver c(base);
+  s.keys = c.take<unsigned long long>(slots);
+  s.rank = c.take<unsigned long long>(slots);
+  s.cnt = c.take<unsigned>(slots);
+  s.slot = c.take<int>((size_t)n);
+  s.bits = c.take<unsigned long long>(nb * kTileWords);
+  s.counts = c.take<int>(nb);
+  s.offsets = c.take<int>(nb + 1);
+  s.flags = c.take<int>(64);
+  s.bytes = c.bytes;
   return s;
 }
 
-// the live rows of the call: the device total of the input list, never more than the rows the launches cover
-__device__ __forceinline__ int live_rows(const VoxelParams& p) {
-  if (!p.in_count) return p.n;
-  const int t = p.in_count[p.B];
-  return t < 0 ? 0 : (t < p.n ? t : p.n);
-}
-
 // slots is a multiple of 1024: every thread writes four slots with 16-byte stores
-__global__ void __launch_bounds__(kThreads) voxel_reset_kernel(ulonglong2* __restrict__ keys, ulonglong2* __restrict__ rank,
+__global__ void __launch_bounds__(kTileThreads) voxel_reset_kernel(ulonglong2* __restrict__ keys, ulonglong2* __restrict__ rank,
                                                                uint4* __restrict__ cnt, size_t quads, int* __restrict__ flags,
                                                                int32_t* __restrict__ dropped) {
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x; q < quads; q += stride) {
-    keys[2 * q] = make_ulonglong2(kEmpty, kEmpty);
-    keys[2 * q + 1] = make_ulonglong2(kEmpty, kEmpty);
+  fill_keys(keys, 2 * quads);
+  const size_t stride = (size_t)gridDim.x * kTileThreads;
+  for (size_t q = (size_t)blockIdx.x * kTileThreads + threadIdx.x; q < quads; q += stride) {
     rank[2 * q] = make_ulonglong2(0ull, 0ull);
     rank[2 * q + 1] = make_ulonglong2(0ull, 0ull);
     cnt[q] = make_uint4(0u, 0u, 0u, 0u);
@@ -90,17 +72,15 @@ __global__ void __launch_bounds__(kThreads) voxel_reset_kernel(ulonglong2* __res
 }
 
 // grid ceil(n / 256). mask = slots - 1.
-__global__ void __launch_bounds__(kThreads) voxel_insert_kernel(VoxelParams p, unsigned long long* __restrict__ keys,
+__global__ void __launch_bounds__(kTileThreads) voxel_insert_kernel(VoxelParams p, unsigned long long* __restrict__ keys,
                                                                 unsigned long long* __restrict__ rank, unsigned* __restrict__ cnt,
                                                                 int* __restrict__ slot, unsigned long long mask, int* __restrict__ flags) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= live_rows(p)) return;
+  const long i = (long)blockIdx.x * kTileThreads + threadIdx.x;
+  if (i >= live_count(p.in_count, p.B, p.n)) return;
   const float x = p.xyz[i * 3], y = p.xyz[i * 3 + 1], z = p.xyz[i * 3 + 2];
   unsigned long long key = 0ull;
   const bool in_range = grid_cell_key(x, y, z, p.voxel, &key);
-  const unsigned long long out_of_range = __ballot(!in_range);  // the lanes of the wave that are still here
-  if (out_of_range && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1))
-    atomicAdd(p.dropped ? p.dropped : flags + 1, (int)__popcll(out_of_range));
+  wave_count_add(!in_range, p.dropped ? p.dropped : flags + 1);  // lanes have already left: the first active one adds
   if (!in_range) {
     slot[i] = -1;
     return;
@@ -124,69 +104,36 @@ __global__ void __launch_bounds__(kThreads) voxel_insert_kernel(VoxelParams p, u
 }
 
 // grid tiles. A row is kept when its slot's rank word names it.
-__global__ void __launch_bounds__(kThreads) voxel_select_kernel(VoxelParams p, const unsigned long long* __restrict__ rank,
+__global__ void __launch_bounds__(kTileThreads) voxel_select_kernel(VoxelParams p, const unsigned long long* __restrict__ rank,
                                                                 const int* __restrict__ slot, unsigned long long* __restrict__ bits,
                                                                 int* __restrict__ counts) {
-  __shared__ int wave_n[kThreads / 64];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int live = live_rows(p);
+  __shared__ int wave_n[kTileWaves];
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int live = live_count(p.in_count, p.B, p.n);
   int n = 0;
-  for (int s = 0; s < kSteps; ++s) {
-    const long i = (long)tile * kTile + s * kThreads + tid;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long i = tile_item(tile, s);
     bool keep = false;
     if (i < live) {
       const int h = slot[i];
       if (h >= 0) keep = (0xFFFFFFFFu - (unsigned)rank[h]) == (unsigned)i;
     }
-    const unsigned long long word = __ballot(keep);
-    if (lane == 0) bits[(long)tile * kWords + s * (kThreads / 64) + wave] = word;
-    n += __popcll(word);
+    n += ballot_step(keep, bits + (long)tile * kTileWords + tile_word(s));
   }
-  if (lane == 0) wave_n[wave] = n;
-  __syncthreads();
-  if (tid == 0) counts[tile] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+  const int sum = tile_sum(n, wave_n);
+  if (tid == 0) counts[tile] = sum;
 }
 
-// survivors among rows [0, r), r <= nb * kTile: the offset of r's tile and the popcounts of the words before r in it
-__device__ __forceinline__ int rank_of_row(const unsigned long long* __restrict__ bits, const int* __restrict__ offsets, long r) {
-  const long t = r / kTile;
-  const int in_tile = (int)(r % kTile);
-  int sum = offsets[t];
-  if (in_tile == 0) return sum;
-  const unsigned long long* words = bits + t * kWords;
-  for (int w = 0; w < in_tile / 64; ++w) sum += __popcll(words[w]);
-  if (in_tile % 64) sum += __popcll(words[in_tile / 64] & ((1ull << (in_tile % 64)) - 1ull));
-  return sum;
-}
-
-// one workgroup: offsets[i] = sum of counts[0 .. i), offsets[nb] = the total (points.hip's scan); then count[b] = the survivors
-// among the rows of view b, count[B] = the total
-__global__ void __launch_bounds__(kThreads) voxel_scan_kernel(VoxelParams p, const int* __restrict__ counts, int nb,
+// one workgroup: offsets[i] = sum of counts[0 .. i), offsets[nb] = the total (scan_tile_counts, the scan of points_scan_kernel);
+// then count[b] = the survivors among the rows of view b, count[B] = the total
+__global__ void __launch_bounds__(kTileThreads) voxel_scan_kernel(VoxelParams p, const int* __restrict__ counts, int nb,
                                                               const unsigned long long* __restrict__ bits, int* __restrict__ offsets) {
-  __shared__ int part[kThreads];
+  __shared__ int part[kTileThreads];
   const int tid = threadIdx.x;
-  const int per = (nb + kThreads - 1) / kThreads;
-  const int lo = tid * per < nb ? tid * per : nb, hi = lo + per < nb ? lo + per : nb;
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += counts[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < kThreads; d <<= 1) {
-    const int v = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - sum;
-  for (int i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  if (tid == kThreads - 1) offsets[nb] = part[tid];
-  __syncthreads();  // the offsets this workgroup wrote are visible to all of it
+  scan_tile_counts(counts, nb, offsets, part);
   if (!p.count) return;
-  const int live = live_rows(p);
-  for (int b = tid; b < p.B; b += kThreads) {
+  const int live = live_count(p.in_count, p.B, p.n);
+  for (int b = tid; b < p.B; b += kTileThreads) {
     long first = 0;  // rows of the views before b
     if (p.in_count)
       for (int k = 0; k < b; ++k) first += p.in_count[k];
@@ -198,32 +145,22 @@ __global__ void __launch_bounds__(kThreads) voxel_scan_kernel(VoxelParams p, con
   if (tid == 0) p.count[p.B] = offsets[nb];
 }
 
-__global__ void __launch_bounds__(kThreads) voxel_scatter_kernel(VoxelParams p, const unsigned* __restrict__ cnt, const int* __restrict__ slot,
+__global__ void __launch_bounds__(kTileThreads) voxel_scatter_kernel(VoxelParams p, const unsigned* __restrict__ cnt, const int* __restrict__ slot,
                                                                  const unsigned long long* __restrict__ bits, const int* __restrict__ offsets) {
-  __shared__ int word_off[kWords];
-  const int tile = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const unsigned long long* words = bits + (long)tile * kWords;
-  if (tid < kWords) {  // wave 0: exclusive scan of the 64 word popcounts (word order = row order)
-    const int c = __popcll(words[tid]);
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    word_off[tid] = incl - c;
-  }
+  __shared__ int word_off[kTileWords];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const unsigned long long* words = bits + (long)tile * kTileWords;
+  if (tid < kTileWords) scan_word_counts(__popcll(words[tid]), word_off);
   __syncthreads();
   const long base = offsets[tile];
   if (base >= p.capacity) return;  // everything of this workgroup lies beyond the capacity
-  for (int s = 0; s < kSteps; ++s) {
-    const int w = s * (kThreads / 64) + wave;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const int w = tile_word(s);
     const unsigned long long word = words[w];
     if (!((word >> lane) & 1ull)) continue;
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
-    const long idx = base + word_off[w] + below;
+    const long idx = base + word_off[w] + lane_rank(word);
     if (idx >= p.capacity) continue;
-    const long i = (long)tile * kTile + s * kThreads + tid;  // a live row: the bit is only ever set for one
+    const long i = tile_item(tile, s);  // a live row: the bit is only ever set for one
     if (p.xyz_out) {
       const float* src = p.xyz + i * 3;
       float* dst = p.xyz_out + idx * 3;
@@ -271,15 +208,15 @@ int launch_voxel_thin(const VoxelParams& p, void* scratch, hipStream_t s) {
   const size_t slots = voxel_table_slots(p.n);
   const int nb = tiles_of(p.n);
   const size_t quads = slots / 4;
-  const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kThreads - 1) / kThreads, 256 * 32);
-  hipLaunchKernelGGL(voxel_reset_kernel, dim3(reset_grid), dim3(kThreads), 0, s, (ulonglong2*)v.keys, (ulonglong2*)v.rank, (uint4*)v.cnt,
+  const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kTileThreads - 1) / kTileThreads, 256 * 32);
+  hipLaunchKernelGGL(voxel_reset_kernel, dim3(reset_grid), dim3(kTileThreads), 0, s, (ulonglong2*)v.keys, (ulonglong2*)v.rank, (uint4*)v.cnt,
                      quads, v.flags, p.dropped);
   MD_HIP(hipGetLastError());
   if (p.n > 0) {
-    hipLaunchKernelGGL(voxel_insert_kernel, dim3((p.n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, p, v.keys, v.rank, v.cnt, v.slot,
+    hipLaunchKernelGGL(voxel_insert_kernel, dim3((p.n + kTileThreads - 1) / kTileThreads), dim3(kTileThreads), 0, s, p, v.keys, v.rank, v.cnt, v.slot,
                        (unsigned long long)(slots - 1), v.flags);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(voxel_select_kernel, dim3(nb), dim3(kThreads), 0, s, p, v.rank, v.slot, v.bits, v.counts);
+    hipLaunchKernelGGL(voxel_select_kernel, dim3(nb), dim3(kTileThreads), 0, s, p, v.rank, v.slot, v.bits, v.counts);
     MD_HIP(hipGetLastError());
   }
   return launch_list_compact(p, v.cnt, v.slot, v.bits, v.counts, v.offsets, s);
@@ -289,10 +226,10 @@ int launch_list_compact(const VoxelParams& p, const unsigned* cnt, const int* sl
                         int* offsets, hipStream_t s) {
   const int nb = tiles_of(p.n);
   if (!p.count) return MD_OK;  // dropped only
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(kThreads), 0, s, p, counts, nb, bits, offsets);
+  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(kTileThreads), 0, s, p, counts, nb, bits, offsets);
   MD_HIP(hipGetLastError());
   if (p.n == 0 || (!p.xyz_out && !p.conf_out && !p.rgb_out && !p.normals_out && !p.index && !p.weight)) return MD_OK;  // counts only
-  hipLaunchKernelGGL(voxel_scatter_kernel, dim3(nb), dim3(kThreads), 0, s, p, cnt, slot, bits, offsets);
+  hipLaunchKernelGGL(voxel_scatter_kernel, dim3(nb), dim3(kTileThreads), 0, s, p, cnt, slot, bits, offsets);
   MD_HIP(hipGetLastError());
   return MD_OK;
 }

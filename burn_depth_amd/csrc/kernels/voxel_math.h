@@ -1,16 +1,12 @@
 // What the hash-grid kernels share (kernels/voxel.hip, kernels/outlier.hip): the cell and key of a point, the table's hash and
-// its two probes, and the tile layout of the ballot words. include/mi_depth.h states the contract of the cell and the key; the
-// files that include this compile with contraction off (Makefile).
+// its two probes. include/mi_depth.h states the contract of the cell and the key; the files that compute a cell compile with
+// contraction off (Makefile). The tile layout of the ballot words is tile_compact.h's.
 #pragma once
 
-#include "ops.h"
+#include "tile_compact.h"
 
 namespace md {
 
-constexpr int kGridThreads = 256;                     // 4 waves of 64
-constexpr int kGridSteps = 16;                        // rows per thread in the ballot kernels
-constexpr int kGridTile = kGridThreads * kGridSteps;  // 4096 rows per workgroup
-constexpr int kGridWords = kGridTile / 64;            // 64 ballot words per workgroup
 constexpr unsigned long long kGridEmpty = ~0ull;
 constexpr float kGridHalf = 1048576.f;                // 2^20 cells on either side of the origin, 21 bits per axis
 constexpr int kGridHalfInt = 1048576;

@@ -334,6 +334,24 @@ def test_capacity_below_the_survivors_keeps_the_true_count(dev):
 
 
 @pytest.mark.gpu
+def test_more_tiles_than_scan_threads_with_a_capacity_inside_the_list(dev):
+    """256 * 4096 + 1 rows are 257 tiles, one more than the one-workgroup scan has threads: every thread of scan_tile_counts
+    (kernels/tile_compact.h) sums and writes a chunk of two tile counts, the branch the cases up to 4097 rows (two tiles) never
+    take. About a ninth of the rows survive; half the survivors as capacity ends inside a tile near the middle of the list, so
+    that tile takes the per-row capacity check and every tile behind it the early-out. One view: md_op_voxel_thin takes no
+    per-view input counts (only the model call has them; test_points_voxel.py checks its three-view counts at its own sizes)."""
+    n = 256 * 4096 + 1
+    xyz, conf = _cloud(n, 47, 13)  # 48^3 = 110592 cells
+    ref = P.voxel_thin(xyz, 0.25, conf)
+    total = int(ref.count[-1])
+    assert n // 12 < total < n // 8
+    _assert_same(_run(dev, xyz, 0.25, conf), ref, "whole")  # the offsets of all 257 tiles
+    cap = total // 2
+    assert 0 < ref.index[cap] % 4096 and ref.index[cap] // 4096 < 256  # the capacity ends inside a tile, tiles lie behind it
+    _assert_same(_run(dev, xyz, 0.25, conf, capacity=cap), ref, "half")
+
+
+@pytest.mark.gpu
 def test_survivor_set_is_invariant_under_a_shuffle_and_runs_repeat(dev):
     xyz, conf = _cloud(8000, 10, 10)  # distinct confidences
     a = _run(dev, xyz, 0.25, conf)
