@@ -253,61 +253,24 @@ SYMBOLS = {
     "md_process_frame": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(MdFrameOpts), C.POINTER(MdFrameOutputs), _I, _P]),
     "md_points_opts_default": (None, [C.POINTER(MdPointsOpts)]),
     "md_op_unproject": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), _P]),
-    "md_infer_points": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
-                             C.POINTER(MdPointsOutputs), _I, _P]),
     "md_view_filter_opts_default": (None, [C.POINTER(MdViewFilterOpts)]),
     "md_op_filter_views": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
                                 C.POINTER(MdViewFilterOutputs), _P]),
-    "md_infer_points_filtered": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                      C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), _I, _P]),
     "md_op_unproject_normals": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
                                      C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), _P]),
-    "md_infer_points_normals": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                     C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), _I, _P]),
     "md_op_voxel_thin": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsVoxel), C.POINTER(MdPointsOutputs), _P, _P]),
-    "md_infer_points_voxel": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                   C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                   C.POINTER(MdPointsVoxel), _I, _P]),
     "md_render_opts_default": (None, [C.POINTER(MdRenderOpts)]),
     "md_op_render_points": (_I, [_P, _P, _P, C.c_int64, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdRenderOpts),
                                  C.POINTER(MdRenderOutputs), _P]),
-    "md_infer_points_render": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                    C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), _I, _P]),
     "md_op_mesh_grid": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_int64, C.POINTER(MdPointsMesh), _P]),
     "md_op_unproject_mesh": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdPointsOpts),
                                   C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals), C.POINTER(MdPointsMesh), _P]),
-    "md_infer_points_mesh": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                  C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                  C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh), _I, _P]),
     "md_raster_opts_default": (None, [C.POINTER(MdRasterOpts)]),
     "md_op_render_mesh": (_I, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, _I, _I, _I, C.POINTER(MdPointsCameras), C.POINTER(MdRasterOpts),
                                C.POINTER(MdRasterOutputs), _P]),
-    "md_infer_points_raster": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                    C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
-                                    C.POINTER(MdPointsRaster), _I, _P]),
     "md_op_radius_outliers": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsOutlier), C.POINTER(MdPointsOutputs), _P, _P]),
-    "md_infer_points_outlier": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                     C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                     C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
-                                     C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), _I, _P]),
-    "md_infer_points_decimate": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                      C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                      C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
-                                      C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate), _I, _P]),
     "md_op_decimate_mesh": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsDecimate), C.POINTER(MdPointsOutputs), _P, _P]),
-    "md_infer_points_components": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                        C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                        C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
-                                        C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate),
-                                        C.POINTER(MdPointsComponents), _I, _P]),
     "md_op_mesh_components": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsComponents), C.POINTER(MdPointsOutputs), _P, _P]),
-    "md_infer_points_smooth": (_I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), C.POINTER(MdViewFilterOpts),
-                                    C.POINTER(MdPointsOpts), C.POINTER(MdPointsOutputs), C.POINTER(MdPointsNormals),
-                                    C.POINTER(MdPointsVoxel), C.POINTER(MdPointsRender), C.POINTER(MdPointsMesh),
-                                    C.POINTER(MdPointsRaster), C.POINTER(MdPointsOutlier), C.POINTER(MdPointsDecimate),
-                                    C.POINTER(MdPointsComponents), C.POINTER(MdPointsSmooth), _I, _P]),
     "md_op_smooth_mesh": (_I, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsSmooth), C.c_int64, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
@@ -401,6 +364,22 @@ SYMBOLS = {
     "md_split_geometry": (_I, [_I, _I, C.c_float, C.POINTER(_I), C.POINTER(_I)]),
     "md_feature_padding": (_I, [_I, _I, _I]),
 }
+
+
+def _infer_points(*parts):
+    """An md_infer_points* entry: (model, image, B, H, W, in_kind, rgb, cameras, its parts, out_kind, stream)."""
+    return _I, [_P, _P, _I, _I, _I, _I, _P, C.POINTER(MdPointsCameras), *(C.POINTER(p) for p in parts), _I, _P]
+
+
+# every entry behind `_filtered` takes the widest entry's parts up to its own; md_infer_points has no view filter
+_POINTS_HEAD = [MdViewFilterOpts, MdPointsOpts, MdPointsOutputs]
+_POINTS_PARTS = [("normals", MdPointsNormals), ("voxel", MdPointsVoxel), ("render", MdPointsRender), ("mesh", MdPointsMesh),
+                 ("raster", MdPointsRaster), ("outlier", MdPointsOutlier), ("decimate", MdPointsDecimate), ("components", MdPointsComponents),
+                 ("smooth", MdPointsSmooth)]
+SYMBOLS["md_infer_points"] = _infer_points(*_POINTS_HEAD[1:])
+SYMBOLS["md_infer_points_filtered"] = _infer_points(*_POINTS_HEAD)
+SYMBOLS.update({f"md_infer_points_{name}": _infer_points(*_POINTS_HEAD, *(p for _, p in _POINTS_PARTS[:i + 1]))
+                for i, (name, _) in enumerate(_POINTS_PARTS)})
 
 _lib = None
 

@@ -27,8 +27,9 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, points
 from .config import DepthProConfig, InterpolationMethod, Precision
+from .points import PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
 
 
 class Device:
@@ -75,370 +76,6 @@ class FrameResult:
     prepared: Optional[torch.Tensor] = None
     focallength_px: Optional[torch.Tensor] = None
     fovy_rad: Optional[torch.Tensor] = None
-
-
-@dataclass
-class RenderedPoints:
-    """What `md_op_render_points` / `md_infer_points_render` return (include/mi_depth.h). Device tensors: depth f32 [T,H,W] (0 at
-    holes), index int32 [T,H,W] (the winner's row, -1 at holes), rgb u8 [T,H,W,3] (with an rgb row), filled int32 [T+1]."""
-    depth: Optional[torch.Tensor] = None
-    index: Optional[torch.Tensor] = None
-    rgb: Optional[torch.Tensor] = None
-    filled: Optional[torch.Tensor] = None
-
-
-@dataclass
-class RasterisedMesh:
-    """What `md_op_render_mesh` / `md_infer_points_raster` return (include/mi_depth.h). Device tensors: depth f32 [T,H,W] (0 at
-    holes), face int32 [T,H,W] (the winning face, -1 at holes), rgb u8 [T,H,W,3] (with an rgb row; affine in screen space), filled
-    int32 [T+1], skipped int32 [T+1] (faces dropped for a box beyond max_extent)."""
-    depth: Optional[torch.Tensor] = None
-    face: Optional[torch.Tensor] = None
-    rgb: Optional[torch.Tensor] = None
-    filled: Optional[torch.Tensor] = None
-    skipped: Optional[torch.Tensor] = None
-
-
-@dataclass
-class SmoothedMesh:
-    """What `md_op_smooth_mesh` / `md_infer_points_smooth` return (include/mi_depth.h). Device tensors: xyz f32 [capacity,3] the
-    smoothed rows (the input bits of a row that did not move), normals f32 [capacity,3] the area-weighted vertex normals of the
-    smoothed faces (None when not asked for), stats int32 [5] the invalid and degenerate faces, the rows not in range, the open
-    rows and the moved rows."""
-    xyz: Optional[torch.Tensor] = None
-    normals: Optional[torch.Tensor] = None
-    stats: Optional[torch.Tensor] = None
-
-
-@dataclass
-class PointCloud:
-    """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
-    mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
-    which the first min(count[B], capacity) rows are points; count int32 [B+1] (per view, then the total); the depth [B,H,W].
-    With normals (`md_op_unproject_normals` / `md_infer_points_normals`): normal_map [B,H,W,3] and normals [capacity,3], rows
-    parallel to xyz. With voxel thinning (`md_op_voxel_thin` / `md_infer_points_voxel`): the list holds one row per occupied
-    voxel, index int32 [capacity] is the source row of every output row in the unthinned list, weight int32 [capacity] the
-    points of its voxel, dropped int32 [1] the rows outside the grid. With `infer_points(render=...)`
-    (`md_infer_points_render`): render = the `RenderedPoints` of the list. With `mesh=` (`md_op_unproject_mesh` /
-    `md_infer_points_mesh`): faces int32 [face_capacity,3] name rows of xyz, in (view, row, column, triangle) order, of which
-    the first min(face_count[B], face_capacity) are faces; face_count int32 [B+1]; pixel_index int32 [B,H,W] is the row of
-    every pixel in the list, -1 where it is not in it. With `raster=` (`md_infer_points_raster`): raster = the `RasterisedMesh` of
-    those faces. With `outlier=` (`md_op_radius_outliers` / `md_infer_points_outlier`): the list holds the rows with at least
-    min_neighbours other rows within radius; neighbours int32 [rows of the unfiltered list] is min(neighbours, min_neighbours) of
-    every unfiltered row (-1 outside the grid); without voxel thinning index is the source row of every output row in the
-    unfiltered list and dropped the rows outside the grid. With `ops.decimate_mesh` (`md_op_decimate_mesh`): the list is voxel
-    thinning's, remap int32 [input rows] the output row of every input row's voxel (-1 outside the grid), faces / face_count the
-    kept faces over the output rows, face_index int32 [face_capacity] their source faces, faces_dropped int32 [3] the invalid,
-    degenerate and duplicate faces. With `components=` (`md_op_mesh_components` / `md_infer_points_components`): label int32 [rows
-    of the list] the smallest row of every row's component (-1 behind the list's total), component_faces int32 [rows] its valid
-    faces, faces / face_count the faces of the components that are large enough, face_index their source faces, component_stats
-    int32 [5] the invalid, dropped and clipped faces and the components with a face and kept; with the operator's compact also
-    index and remap. With `smooth=` (`md_infer_points_smooth`): smooth = the `SmoothedMesh` of the list over the faces the
-    rasteriser reads; the list itself is unchanged. None when not asked for."""
-    point_map: Optional[torch.Tensor] = None
-    mask: Optional[torch.Tensor] = None
-    xyz: Optional[torch.Tensor] = None
-    rgb: Optional[torch.Tensor] = None
-    conf: Optional[torch.Tensor] = None
-    count: Optional[torch.Tensor] = None
-    depth: Optional[torch.Tensor] = None
-    normal_map: Optional[torch.Tensor] = None
-    normals: Optional[torch.Tensor] = None
-    index: Optional[torch.Tensor] = None
-    weight: Optional[torch.Tensor] = None
-    dropped: Optional[torch.Tensor] = None
-    render: Optional["RenderedPoints"] = None
-    faces: Optional[torch.Tensor] = None
-    face_count: Optional[torch.Tensor] = None
-    pixel_index: Optional[torch.Tensor] = None
-    raster: Optional["RasterisedMesh"] = None
-    neighbours: Optional[torch.Tensor] = None
-    remap: Optional[torch.Tensor] = None
-    face_index: Optional[torch.Tensor] = None
-    faces_dropped: Optional[torch.Tensor] = None
-    label: Optional[torch.Tensor] = None
-    component_faces: Optional[torch.Tensor] = None
-    component_stats: Optional[torch.Tensor] = None
-    smooth: Optional["SmoothedMesh"] = None
-
-    def points(self):
-        """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
-        n = min(int(self.count[-1].item()), int(self.xyz.shape[0]))
-        cut = lambda t: t[:n] if t is not None else None  # noqa: E731
-        return cut(self.xyz), cut(self.rgb), cut(self.conf)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return t.data_ptr() if t is not None else None
-
-
-def _points_opts(pixel_offset=0.0, depth_min=0.0, depth_max=0.0, conf_min=0.0, edge_rtol=0.0, stride=1, world=False) -> "_lib.MdPointsOpts":
-    return _lib.MdPointsOpts(float(pixel_offset), float(depth_min), float(depth_max), float(conf_min), float(edge_rtol), int(stride),
-                             int(bool(world)))
-
-
-def _view_filter_opts(pixel_offset=0.0, depth_min=0.0, depth_max=0.0, conf_percentile=0, view_rtol=0.0, min_views=0) -> "_lib.MdViewFilterOpts":
-    return _lib.MdViewFilterOpts(float(pixel_offset), float(depth_min), float(depth_max), int(conf_percentile), float(view_rtol), int(min_views))
-
-
-def _points_outputs(dev, B: int, H: int, W: int, dense: bool, compact: bool, capacity: Optional[int], stride: int, want_rgb: bool,
-                    want_conf: bool, want_depth: bool, out: Optional[PointCloud]):
-    """A PointCloud of fresh device tensors (or `out`, to write into again) and its md_points_outputs."""
-    if out is None:
-        stride = max(int(stride), 1)  # a bad stride is the library's to refuse
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
-        out = PointCloud()
-        if dense:
-            out.point_map, out.mask = f(B, H, W, 3), f(B, H, W, dt=torch.uint8)
-        if compact:
-            cap = int(capacity) if capacity is not None else B * ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
-            out.xyz, out.count = f(cap, 3), f(B + 1, dt=torch.int32)
-            out.rgb = f(cap, 3, dt=torch.uint8) if want_rgb else None
-            out.conf = f(cap) if want_conf else None
-        if want_depth:
-            out.depth = f(B, H, W)
-    c = _lib.MdPointsOutputs(_ptr(out.point_map), _ptr(out.mask), _ptr(out.xyz), _ptr(out.rgb), _ptr(out.conf), _ptr(out.count),
-                             int(out.xyz.shape[0]) if out.xyz is not None else 0, _ptr(out.depth))
-    return out, c
-
-
-def _points_normals(dev, B: int, H: int, W: int, normals: bool, min_cos: float, out: PointCloud, fresh: bool):
-    """md_points_normals for `out`: with `fresh` (the PointCloud was made for this call) the normal tensors are created beside the
-    dense map and the list it has; otherwise the ones it carries are written again, and asking for normals with an `out` that
-    carries none is refused."""
-    if normals and not fresh and out.normal_map is None and out.normals is None:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "normals=True with an `out` that carries neither `normal_map` nor `normals`")
-    if fresh and normals:
-        if out.point_map is not None:
-            out.normal_map = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
-        if out.xyz is not None:
-            out.normals = torch.empty((int(out.xyz.shape[0]), 3), dtype=torch.float32, device=dev)
-    return _lib.MdPointsNormals(_ptr(out.normal_map), _ptr(out.normals), float(min_cos))
-
-
-def _points_voxel(dev, voxel: float, out: PointCloud, fresh: bool):
-    """md_points_voxel for `out`: with `fresh` index, weight and dropped are created beside the list it has; otherwise the ones it
-    carries are written again."""
-    if fresh and voxel and out.xyz is not None:
-        cap = int(out.xyz.shape[0])
-        out.index = torch.empty(cap, dtype=torch.int32, device=dev)
-        out.weight = torch.empty(cap, dtype=torch.int32, device=dev)
-        out.dropped = torch.empty(1, dtype=torch.int32, device=dev)
-    return _lib.MdPointsVoxel(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped))
-
-
-def _points_outlier(dev, rows: int, outlier: dict, thin: bool, out: PointCloud, fresh: bool):
-    """md_points_outlier for `out`. outlier: a dict with radius and min_neighbours. rows: the rows the unfiltered list can have.
-    With `fresh` neighbours (and, without thinning, index and dropped, which are the thinning's otherwise) are created beside the
-    list it has; otherwise the ones it carries are written again. radius == 0 is the call without the filter and takes no tensor."""
-    unknown = set(outlier) - {"radius", "min_neighbours"}
-    if unknown:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown outlier keywords {sorted(unknown)}")
-    radius, k = float(outlier.get("radius", 0.0)), int(outlier.get("min_neighbours", 1))
-    if not radius:
-        return _lib.MdPointsOutlier(radius, k, None, None, None)
-    if fresh and out.xyz is not None:
-        out.neighbours = torch.empty(rows, dtype=torch.int32, device=dev)
-        if not thin:
-            out.index = torch.empty(int(out.xyz.shape[0]), dtype=torch.int32, device=dev)
-            out.dropped = torch.empty(1, dtype=torch.int32, device=dev)
-    return _lib.MdPointsOutlier(radius, k, _ptr(out.neighbours), None if thin else _ptr(out.index), None if thin else _ptr(out.dropped))
-
-
-def _points_mesh(dev, B: int, H: int, W: int, stride: int, mesh, out: PointCloud, fresh: bool):
-    """md_points_mesh for `out`. mesh: True, or a dict with any of max_rtol (0 = no discontinuity cut), face_capacity (default:
-    two faces per quad of the strided lattice) and pixel_index (default True: also return the map). With `fresh` the tensors
-    are created; otherwise the ones `out` carries are written again."""
-    kw = dict(mesh) if isinstance(mesh, dict) else {}
-    unknown = set(kw) - {"max_rtol", "face_capacity", "pixel_index"}
-    if unknown:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown mesh keywords {sorted(unknown)}")
-    if mesh and not fresh and out.faces is None and out.face_count is None and out.pixel_index is None:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "mesh= with an `out` that carries neither `faces`, `face_count` nor `pixel_index`")
-    cap = int(out.faces.shape[0]) if out.faces is not None else 0
-    if fresh:
-        stride = max(int(stride), 1)  # a bad stride, like a negative capacity, is the library's to refuse
-        cap = kw.get("face_capacity")
-        cap = 2 * B * ((H + stride - 1) // stride - 1) * ((W + stride - 1) // stride - 1) if cap is None else int(cap)
-        out.faces = torch.empty((max(cap, 0), 3), dtype=torch.int32, device=dev)
-        out.face_count = torch.empty(B + 1, dtype=torch.int32, device=dev)
-        if kw.get("pixel_index", True):
-            out.pixel_index = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-    return _lib.MdPointsMesh(float(kw.get("max_rtol", 0.0)), _ptr(out.faces) or None, _ptr(out.face_count), cap, _ptr(out.pixel_index))
-
-
-def _points_decimate(dev, B: int, H: int, W: int, stride: int, mesh, decimate: dict, out: PointCloud, fresh: bool):
-    """(md_points_mesh, md_points_decimate) for `out` with the decimation on. mesh: True, or a dict with max_rtol / pixel_index;
-    decimate: dict(voxel=, face_capacity=). The faces and face_count of `out` are the decimated ones, so the mesh part carries
-    only its edge test and the map. With `fresh` the tensors are created beside the list `out` has; otherwise the ones it carries
-    are written again."""
-    kw = dict(mesh) if isinstance(mesh, dict) else {}
-    unknown = (set(kw) - {"max_rtol", "pixel_index"}) | (set(decimate) - {"voxel", "face_capacity"})
-    if unknown:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown mesh / decimate keywords {sorted(unknown)}")
-    if fresh and out.xyz is not None:
-        stride = max(int(stride), 1)
-        h, w = (H + stride - 1) // stride, (W + stride - 1) // stride
-        cap, fcap = int(out.xyz.shape[0]), decimate.get("face_capacity")
-        fcap = max(2 * B * (h - 1) * (w - 1) if fcap is None else int(fcap), 0)
-        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-        out.index, out.weight, out.dropped, out.remap = i32(cap), i32(cap), i32(1), i32(B * h * w)
-        out.faces, out.face_index, out.face_count, out.faces_dropped = i32(fcap, 3), i32(fcap), i32(B + 1), i32(3)
-        if kw.get("pixel_index", True):
-            out.pixel_index = i32(B, H, W)
-    frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
-    msh = _lib.MdPointsMesh(float(kw.get("max_rtol", 0.0)), None, None, 0, _ptr(out.pixel_index))
-    dec = _lib.MdPointsDecimate(float(decimate["voxel"]), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped), _ptr(out.remap),
-                                _ptr(out.faces) or None, _ptr(out.face_index) or None, _ptr(out.face_count), min(frows) if frows else 0,
-                                _ptr(out.faces_dropped))
-    return msh, dec
-
-
-def _points_components(dev, B: int, H: int, W: int, stride: int, mesh, components: dict, out: PointCloud, fresh: bool):
-    """(md_points_mesh, md_points_components) for `out` with the island removal on. mesh: True, or a dict with max_rtol /
-    pixel_index; components: dict(min_faces=, face_capacity=). The faces and face_count of `out` are those of the kept components,
-    so the mesh part carries only its edge test and the map. With `fresh` the tensors are created; otherwise the ones `out`
-    carries are written again."""
-    kw = dict(mesh) if isinstance(mesh, dict) else {}
-    unknown = (set(kw) - {"max_rtol", "pixel_index"}) | (set(components) - {"min_faces", "face_capacity"})
-    if unknown:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"unknown mesh / components keywords {sorted(unknown)}")
-    if fresh:
-        stride = max(int(stride), 1)
-        h, w = (H + stride - 1) // stride, (W + stride - 1) // stride
-        fcap = components.get("face_capacity")
-        fcap = max(2 * B * (h - 1) * (w - 1) if fcap is None else int(fcap), 0)
-        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-        out.label, out.component_faces, out.component_stats = i32(B * h * w), i32(B * h * w), i32(5)
-        out.faces, out.face_index, out.face_count = i32(fcap, 3), i32(fcap), i32(B + 1)
-        if kw.get("pixel_index", True):
-            out.pixel_index = i32(B, H, W)
-    frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
-    msh = _lib.MdPointsMesh(float(kw.get("max_rtol", 0.0)), None, None, 0, _ptr(out.pixel_index))
-    comp = _lib.MdPointsComponents(int(components["min_faces"]), 0, _ptr(out.label), _ptr(out.component_faces), None, None,
-                                   _ptr(out.faces) or None, _ptr(out.face_index) or None, _ptr(out.face_count), min(frows) if frows else 0,
-                                   _ptr(out.component_stats))
-    return msh, comp
-
-
-def _points_smooth(dev, smooth: dict, out: PointCloud, fresh: bool):
-    """md_points_smooth for `out` with the smoothing on. smooth: dict(step=, iterations=, lam=, mu=, pin_boundary=, normals=). With
-    `fresh` the tensors of `out.smooth` are created, rows parallel to the list; otherwise the ones `out` carries are written again."""
-    unknown = set(smooth) - {"step", "iterations", "lam", "mu", "pin_boundary", "normals"}
-    if unknown or "step" not in smooth or "lam" not in smooth:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"smooth= takes step, iterations, lam, mu, pin_boundary, normals; unknown {sorted(unknown)}")
-    if out.xyz is None:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "smooth= needs the compacted list")
-    if fresh or out.smooth is None:
-        cap = int(out.xyz.shape[0])
-        out.smooth = SmoothedMesh(xyz=torch.empty((cap, 3), dtype=torch.float32, device=dev),
-                                  normals=torch.empty((cap, 3), dtype=torch.float32, device=dev) if smooth.get("normals") else None,
-                                  stats=torch.empty(5, dtype=torch.int32, device=dev))
-    s = out.smooth
-    return _lib.MdPointsSmooth(float(smooth["step"]), float(smooth["lam"]), float(smooth.get("mu", 0.0)), int(smooth["iterations"]),
-                               1 if smooth.get("pin_boundary", True) else 0, _ptr(s.xyz), _ptr(s.normals), _ptr(s.stats))
-
-
-def _render_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
-                    radius=0, want_rgb=False, out: Optional[RenderedPoints] = None):
-    """The target cameras, options and outputs of a rendering -> (T, cameras, md_render_opts, RenderedPoints, md_render_outputs,
-    keep-alive). T is the number of cameras given; fresh output tensors are allocated unless `out` is given."""
-    src = intrinsics if intrinsics is not None else focal_px
-    if src is None:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras")
-    n = src.numel() if isinstance(src, torch.Tensor) else int(np.asarray(src).size)
-    T = max(n // 9 if intrinsics is not None else n, 1)
-    cam, keep = _points_cameras(dev, T, intrinsics, extrinsics, focal_px)
-    if out is None:
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
-        out = RenderedPoints(f(T, H, W), f(T, H, W, dt=torch.int32), f(T, H, W, 3, dt=torch.uint8) if want_rgb else None,
-                             f(T + 1, dt=torch.int32))
-    o = _lib.MdRenderOpts(float(pixel_offset), float(z_near), float(z_far), int(radius))
-    return T, cam, o, out, _lib.MdRenderOutputs(_ptr(out.depth), _ptr(out.index), _ptr(out.rgb), _ptr(out.filled)), keep
-
-
-def _raster_request(dev, H: int, W: int, intrinsics=None, extrinsics=None, focal_px=None, *, pixel_offset=0.0, z_near=0.0, z_far=0.0,
-                    cull=0, max_extent=0, want_rgb=False, out: Optional[RasterisedMesh] = None):
-    """`_render_request` for a mesh rasterisation -> (T, cameras, md_raster_opts, RasterisedMesh, md_raster_outputs, keep-alive)."""
-    src = intrinsics if intrinsics is not None else focal_px
-    if src is None:
-        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "neither intrinsics nor a focal length for the target cameras")
-    n = src.numel() if isinstance(src, torch.Tensor) else int(np.asarray(src).size)
-    T = max(n // 9 if intrinsics is not None else n, 1)
-    cam, keep = _points_cameras(dev, T, intrinsics, extrinsics, focal_px)
-    if out is None:
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
-        out = RasterisedMesh(f(T, H, W), f(T, H, W, dt=torch.int32), f(T, H, W, 3, dt=torch.uint8) if want_rgb else None,
-                             f(T + 1, dt=torch.int32), f(T + 1, dt=torch.int32))
-    o = _lib.MdRasterOpts(float(pixel_offset), float(z_near), float(z_far), int(cull), int(max_extent))
-    outs = _lib.MdRasterOutputs(_ptr(out.depth), _ptr(out.face), _ptr(out.rgb), _ptr(out.filled), _ptr(out.skipped))
-    return T, cam, o, out, outs, keep
-
-
-def _points_cameras(dev, B: int, intrinsics=None, extrinsics=None, focal_px=None):
-    """md_points_cameras of device fp32 tensors ([B,3,3] / [B,1,3,3], [B,3,4] / [B,1,3,4], [B] or a float). Returns (struct, keep-alive)."""
-    keep = []
-
-    def put(t, n):
-        if t is None:
-            return None
-        if not isinstance(t, torch.Tensor):
-            t = torch.as_tensor(np.asarray(t, dtype=np.float32))
-        if t.numel() == 1 and n == B:
-            t = t.reshape(1).expand(B)
-        t = t.to(device=dev, dtype=torch.float32).contiguous()
-        if t.numel() != n:
-            raise _lib.MdError(_lib.MD_ERR_SHAPE, f"camera tensor of {t.numel()} values, expected {n}")
-        keep.append(t)
-        return t.data_ptr()
-
-    return _lib.MdPointsCameras(put(intrinsics, B * 9), put(extrinsics, B * 12), put(focal_px, B)), keep
-
-
-def _points_request(dev, B: int, H: int, W: int, opts: dict, intrinsics, extrinsics, focal_px, want_rgb: bool, want_conf: bool,
-                    want_depth: bool, dense: bool, compact: bool, capacity: Optional[int], out: Optional[PointCloud], normals: bool,
-                    normal_min_cos: float, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
-                    voxel: Optional[float] = None, render: Optional[dict] = None, mesh=None, raster: Optional[dict] = None,
-                    outlier: Optional[dict] = None):
-    """The keyword set of `infer_points` / `ops.unproject` as the structs of the widest entry -> (cloud, opts, outs, cam, fo, nrm,
-    vox, rnd, msh, rst, outl, keep-alive). outlier: dict(radius=, min_neighbours=), the argument of `_points_outlier`. raster: the keywords of `_raster_request`, as render's. fo, nrm, vox, rnd, msh and rst are None for the parts not asked for (an `out` that carries normal,
-    thinning or mesh tensors asks for them; voxel=None: the entry has no thinning part), and fresh tensors are allocated unless
-    `out` is given. mesh: the argument of `_points_mesh`.
-    render: the keywords of `_render_request` (H, W, the target cameras, pixel_offset, z_near, z_far, radius); the images go to
-    fresh tensors, or to the `render` that `out` carries. Positional
-    arguments and a plain tuple back: this sits on the host path of every call. opts: the fields of `md_points_opts`; want_rgb /
-    want_conf / want_depth: the call can fill those outputs."""
-    o = _points_opts(**opts)
-    res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
-    cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
-    fo = nrm = vox = None
-    if conf_percentile or view_rtol or min_views:
-        fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
-    if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
-        nrm = _points_normals(dev, B, H, W, normals, normal_min_cos, res, out is None)
-    # without thinning, the index and dropped that `out` carries beside `neighbours` are the outlier removal's
-    theirs = bool(outlier) and bool(outlier.get("radius")) and not voxel
-    if voxel is not None and (voxel or (not theirs and (res.index is not None or res.weight is not None or res.dropped is not None))):
-        vox = _points_voxel(dev, voxel, res, out is None)
-    rnd = None
-    if render is not None:
-        T, tcam, ro, res.render, routs, tkeep = _render_request(dev, **render, want_rgb=res.rgb is not None, out=res.render)
-        rnd = _lib.MdPointsRender(T, int(render["H"]), int(render["W"]), tcam, ro, routs)
-        keep = keep + tkeep
-    msh = None
-    if mesh or res.faces is not None or res.face_count is not None or res.pixel_index is not None:
-        msh = _points_mesh(dev, B, H, W, o.stride, mesh, res, out is None)
-    rst = None
-    if raster is not None:
-        T, tcam, so, res.raster, souts, tkeep = _raster_request(dev, **raster, want_rgb=res.rgb is not None, out=res.raster)
-        rst = _lib.MdPointsRaster(T, int(raster["H"]), int(raster["W"]), tcam, so, souts)
-        keep = keep + tkeep
-    outl = None
-    if outlier is not None:
-        stride = max(int(o.stride), 1)
-        rows = B * ((H + stride - 1) // stride) * ((W + stride - 1) // stride)
-        outl = _points_outlier(dev, rows, outlier, bool(voxel), res, out is None)
-    return res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, outl, keep
 
 
 @dataclass
@@ -875,42 +512,16 @@ class DepthPro:
         B, _, H, W = (int(v) for v in x.shape)
         if rgb is not None:
             rgb = rgb.to(device=dev, dtype=torch.uint8).contiguous()
-        has_conf = bool(getattr(self.config, "dual_head", False))
-        deci = bool(decimate) and bool(decimate.get("voxel"))
-        isl = bool(components) and bool(components.get("min_faces"))
-        res, o, outs, cam, fo, nrm, vox, rnd, msh, rst, outl, keep = _points_request(
-            dev, B, H, W, opts, intrinsics, extrinsics, f_px, rgb is not None, has_conf, True, dense, compact, capacity, out, normals,
-            normal_min_cos, conf_percentile, view_rtol, min_views, voxel, render, None if deci or isl else mesh, raster, outlier)
-        dec = comp = None
-        if isl:
-            if not mesh:
-                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "components= needs mesh=")
-            msh, comp = _points_components(dev, B, H, W, o.stride, mesh, components, res, out is None)
-        elif components is not None:
-            comp = _lib.MdPointsComponents(0, 0, None, None, None, None, None, None, None, 0, None)
-        if deci:
-            if not mesh:
-                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "decimate= needs mesh=")
-            msh, dec = _points_decimate(dev, B, H, W, o.stride, mesh, decimate, res, out is None)
-            if not voxel:  # the index, weight and dropped an `out` carries are the decimation's
-                vox = None
-        elif decimate is not None:
-            dec = _lib.MdPointsDecimate(0.0, None, None, None, None, None, None, None, 0, None)
-        smo = None
-        if smooth and smooth.get("iterations"):
-            if not mesh:
-                raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "smooth= needs mesh=")
-            smo = _points_smooth(dev, smooth, res, out is None)
-        elif smooth is not None:
-            smo = _lib.MdPointsSmooth(0.0, 0.0, 0.0, 0, 0, None, None, None)
-        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        rq = points._points_request(
+            dev, B, H, W, want_rgb=rgb is not None, want_conf=bool(getattr(self.config, "dual_head", False)), want_depth=True,
+            intrinsics=intrinsics, extrinsics=extrinsics, focal_px=f_px, dense=dense, compact=compact, capacity=capacity, out=out,
+            conf_percentile=conf_percentile, view_rtol=view_rtol, min_views=min_views, normals=normals, normal_min_cos=normal_min_cos,
+            voxel=voxel, render=render, mesh=mesh, raster=raster, outlier=outlier, decimate=decimate, components=components,
+            smooth=smooth, opts=opts)
         _lib.check(self._lib.md_infer_points_smooth(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, C.byref(cam), ref(fo),
-                                                    C.byref(o), C.byref(outs), ref(nrm), ref(vox), ref(rnd), ref(msh), ref(rst),
-                                                    ref(outl), ref(dec), ref(comp), ref(smo), _lib.MD_MEM_DEVICE,
-                                                    _stream_ptr(self.device.ordinal)))
-        del keep
-        return res
+                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, *rq.args(),
+                                                    _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+        return rq.cloud
 
     # ---- debug taps / timing --------------------------------------------------------------
     def enable_taps(self, enable: bool = True) -> None:

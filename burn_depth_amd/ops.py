@@ -8,8 +8,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .depth_pro import (Device, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _points_cameras, _points_request, _raster_request, _render_request,
-                        _stream_ptr, _view_filter_opts)
+from .depth_pro import Device, _stream_ptr
+from .points import (PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _f32, _i32, _lattice, _points_cameras, _points_request, _ptr,
+                     _raster_request, _render_request, _u8, _view_filter_opts)
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -539,14 +540,13 @@ def unproject(dev: Device, depth: torch.Tensor, intrinsics=None, extrinsics=None
     conf = _f32c(conf) if conf is not None else None
     rgb = rgb.contiguous() if rgb is not None else None
     assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8)
-    res, o, outs, cam, _, nrm, _, _, msh, _, _, keep = _points_request(depth.device, B, H, W, opts, intrinsics, extrinsics, focal_px, rgb is not None,
-                                                              conf is not None, False, dense, compact, capacity, out, normals, normal_min_cos,
-                                                              mesh=mesh)
-    _lib.check(_lib.load().md_op_unproject_mesh(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(cam), C.byref(o), C.byref(outs),
-                                                C.byref(nrm) if nrm is not None else None, C.byref(msh) if msh is not None else None,
+    rq = _points_request(depth.device, B, H, W, want_rgb=rgb is not None, want_conf=conf is not None, want_depth=False, intrinsics=intrinsics,
+                         extrinsics=extrinsics, focal_px=focal_px, dense=dense, compact=compact, capacity=capacity, out=out, normals=normals,
+                         normal_min_cos=normal_min_cos, mesh=mesh, opts=opts)
+    _lib.check(_lib.load().md_op_unproject_mesh(dev.handle, _p(depth), _p(conf), _p(rgb), B, H, W, C.byref(rq.cam), C.byref(rq.opts), C.byref(rq.outs),
+                                                C.byref(rq.nrm) if rq.nrm is not None else None, C.byref(rq.msh) if rq.msh is not None else None,
                                                 _stream_ptr(dev.ordinal)))
-    del keep
-    return res
+    return rq.cloud
 
 
 def filter_views(dev: Device, depth: torch.Tensor, conf: Optional[torch.Tensor] = None, intrinsics=None, extrinsics=None, focal_px=None,
@@ -570,29 +570,51 @@ def filter_views(dev: Device, depth: torch.Tensor, conf: Optional[torch.Tensor] 
     return out.get("depth"), out.get("support"), out.get("tau"), out.get("kept")
 
 
+def _list_inputs(xyz, faces=None, conf=None, rgb=None, normals=None, n_rows: Optional[int] = None, standin: bool = False):
+    """What the list operators take, checked and staged -> (xyz, faces, conf, rgb, normals, N, F): xyz f32 [N,3], faces int32 [F,3],
+    conf [N], u8 rgb [N,3], normals [N,3]. n_rows: `mesh_components` names its rows and has checked xyz, which may be None.
+    standin: for N == 0 one row that is never read stands for the rgb input."""
+    if n_rows is None:
+        assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
+    if faces is not None:
+        assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
+        faces = faces.contiguous()
+    xyz = _f32c(xyz) if xyz is not None else None
+    N, F = int(xyz.shape[0]) if n_rows is None else int(n_rows), int(faces.shape[0]) if faces is not None else 0
+    conf = _f32c(conf).reshape(N) if conf is not None else None
+    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
+    rgb = rgb.contiguous() if rgb is not None else None
+    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
+    if standin and rgb is not None and N == 0:  # an empty tensor has no address
+        rgb = torch.zeros((1, 3), dtype=torch.uint8, device=xyz.device)
+    return xyz, faces, conf, rgb, normals, N, F
+
+
+def _list_outputs(out: Optional[PointCloud], dev, cap: int, conf, rgb, normals, carried=("index",), vertex: bool = True, **i32):
+    """The outputs of a list operator -> (`out`, or a fresh PointCloud; its md_points_outputs). Fresh: every `i32` keyword is an
+    int32 tensor of that shape and, with `vertex`, the list rows [cap, ..] of the inputs given come with count [2] and index [cap].
+    The capacity is the fewest rows among the list rows and the `carried` tensors that the PointCloud has."""
+    if out is None:
+        out = PointCloud(**{k: _i32(dev, *shape) for k, shape in i32.items()})
+        if vertex:
+            out.xyz, out.count, out.index = _f32(dev, cap, 3), _i32(dev, 2), _i32(dev, cap)
+            out.conf = _f32(dev, cap) if conf is not None else None
+            out.rgb = _u8(dev, cap, 3) if rgb is not None else None
+            out.normals = _f32(dev, cap, 3) if normals is not None else None
+    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, *(getattr(out, k) for k in carried)) if t is not None]
+    return out, _lib.MdPointsOutputs(None, None, _ptr(out.xyz), _ptr(out.rgb), _ptr(out.conf), _ptr(out.count), min(rows) if rows else 0, None)
+
+
 def voxel_thin(dev: Device, xyz: torch.Tensor, voxel: float, conf: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None,
                normals: Optional[torch.Tensor] = None, capacity: Optional[int] = None, out: Optional[PointCloud] = None) -> PointCloud:
     """md_op_voxel_thin: a point list xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) -> `PointCloud` with one input row per
     occupied voxel of side `voxel`, in input order: xyz / conf / rgb / normals [capacity, ..], index and weight int32 [capacity],
     count int32 [2] (the survivors, twice: one view), dropped int32 [1]. capacity defaults to N. `out`: a PointCloud of an
     earlier call to write into again. Bit-identical to `pipeline.voxel_thin`."""
-    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
-    xyz = _f32c(xyz)
-    N = int(xyz.shape[0])
-    conf = _f32c(conf).reshape(N) if conf is not None else None
-    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
-    rgb = rgb.contiguous() if rgb is not None else None
-    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
-    if out is None:
-        cap = N if capacity is None else int(capacity)
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=xyz.device)  # noqa: E731
-        out = PointCloud(xyz=f(cap, 3), conf=f(cap) if conf is not None else None, rgb=f(cap, 3, dt=torch.uint8) if rgb is not None else None,
-                         normals=f(cap, 3) if normals is not None else None, count=f(2, dt=torch.int32), index=f(cap, dt=torch.int32),
-                         weight=f(cap, dt=torch.int32), dropped=f(1, dt=torch.int32))
-    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index, out.weight) if t is not None]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
-    vox = _lib.MdPointsVoxel(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped))
+    xyz, _, conf, rgb, normals, N, _ = _list_inputs(xyz, None, conf, rgb, normals)
+    cap = N if capacity is None else int(capacity)
+    out, outs = _list_outputs(out, xyz.device, cap, conf, rgb, normals, ("index", "weight"), weight=(cap,), dropped=(1,))
+    vox = _lib.MdPointsVoxel(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped))
     _lib.check(_lib.load().md_op_voxel_thin(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(vox), C.byref(outs),
                                             _p(out.normals), _stream_ptr(dev.ordinal)))
     return out
@@ -606,24 +628,11 @@ def radius_outliers(dev: Device, xyz: torch.Tensor, radius: float, min_neighbour
     [capacity], neighbours int32 [N] (min(neighbours, min_neighbours) of every input row, -1 outside the grid), count int32 [2] (the
     survivors, twice: one view), dropped int32 [1]. capacity defaults to N. `out`: a PointCloud of an earlier call to write into
     again. Bit-identical to `pipeline.radius_outliers`."""
-    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
-    xyz = _f32c(xyz)
-    N = int(xyz.shape[0])
-    conf = _f32c(conf).reshape(N) if conf is not None else None
-    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
-    rgb = rgb.contiguous() if rgb is not None else None
-    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
-    if out is None:
-        cap = N if capacity is None else int(capacity)
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=xyz.device)  # noqa: E731
-        out = PointCloud(xyz=f(cap, 3), conf=f(cap) if conf is not None else None, rgb=f(cap, 3, dt=torch.uint8) if rgb is not None else None,
-                         normals=f(cap, 3) if normals is not None else None, count=f(2, dt=torch.int32), index=f(cap, dt=torch.int32),
-                         neighbours=f(N, dt=torch.int32), dropped=f(1, dt=torch.int32))
+    xyz, _, conf, rgb, normals, N, _ = _list_inputs(xyz, None, conf, rgb, normals)
+    cap = N if capacity is None else int(capacity)
+    out, outs = _list_outputs(out, xyz.device, cap, conf, rgb, normals, neighbours=(N,), dropped=(1,))
     assert out.neighbours is None or int(out.neighbours.shape[0]) >= N, "neighbours covers the input rows"
-    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index) if t is not None]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
-    outl = _lib.MdPointsOutlier(float(radius), int(min_neighbours), ptr(out.neighbours), ptr(out.index), ptr(out.dropped))
+    outl = _lib.MdPointsOutlier(float(radius), int(min_neighbours), _ptr(out.neighbours), _ptr(out.index), _ptr(out.dropped))
     _lib.check(_lib.load().md_op_radius_outliers(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(outl), C.byref(outs),
                                                  _p(out.normals), _stream_ptr(dev.ordinal)))
     return out
@@ -637,30 +646,14 @@ def decimate_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, voxel: fl
     int32 [face_capacity,3] over the output rows with face_index int32 [face_capacity], face_count int32 [2] and faces_dropped
     int32 [3] (invalid, degenerate, duplicate). capacity defaults to N, face_capacity to F. `out`: a PointCloud of an earlier call
     to write into again. Bit-identical to `pipeline.decimate_mesh`."""
-    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
-    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
-    xyz, faces = _f32c(xyz), faces.contiguous()
-    N, F = int(xyz.shape[0]), int(faces.shape[0])
-    conf = _f32c(conf).reshape(N) if conf is not None else None
-    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
-    rgb = rgb.contiguous() if rgb is not None else None
-    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
-    if out is None:
-        cap = N if capacity is None else int(capacity)
-        fcap = F if face_capacity is None else int(face_capacity)
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=xyz.device)  # noqa: E731
-        out = PointCloud(xyz=f(cap, 3), conf=f(cap) if conf is not None else None, rgb=f(cap, 3, dt=torch.uint8) if rgb is not None else None,
-                         normals=f(cap, 3) if normals is not None else None, count=f(2, dt=torch.int32), index=f(cap, dt=torch.int32),
-                         weight=f(cap, dt=torch.int32), dropped=f(1, dt=torch.int32), remap=f(N, dt=torch.int32),
-                         faces=f(fcap, 3, dt=torch.int32), face_index=f(fcap, dt=torch.int32), face_count=f(2, dt=torch.int32),
-                         faces_dropped=f(3, dt=torch.int32))
+    xyz, faces, conf, rgb, normals, N, F = _list_inputs(xyz, faces, conf, rgb, normals)
+    cap, fcap = N if capacity is None else int(capacity), F if face_capacity is None else int(face_capacity)
+    out, outs = _list_outputs(out, xyz.device, cap, conf, rgb, normals, ("index", "weight"), weight=(cap,), dropped=(1,), remap=(N,),
+                              faces=(fcap, 3), face_index=(fcap,), face_count=(2,), faces_dropped=(3,))
     assert out.remap is None or int(out.remap.shape[0]) >= N, "remap covers the input rows"
-    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index, out.weight) if t is not None]
     frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
-    dec = _lib.MdPointsDecimate(float(voxel), ptr(out.index), ptr(out.weight), ptr(out.dropped), ptr(out.remap), ptr(out.faces),
-                                ptr(out.face_index), ptr(out.face_count), min(frows) if frows else 0, ptr(out.faces_dropped))
+    dec = _lib.MdPointsDecimate(float(voxel), _ptr(out.index), _ptr(out.weight), _ptr(out.dropped), _ptr(out.remap), _ptr(out.faces),
+                                _ptr(out.face_index), _ptr(out.face_count), min(frows) if frows else 0, _ptr(out.faces_dropped))
     _lib.check(_lib.load().md_op_decimate_mesh(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, _p(faces), F, C.byref(dec),
                                                C.byref(outs), _p(out.normals), _stream_ptr(dev.ordinal)))
     return out
@@ -678,38 +671,21 @@ def mesh_components(dev: Device, faces: torch.Tensor, n_rows: int, min_faces: in
     remap int32 [N], and the faces are written through remap. capacity defaults to N, face_capacity to F. `out`: a PointCloud of an
     earlier call to write into again. Bit-identical to `pipeline.mesh_components`."""
     assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
-    faces = faces.contiguous()
-    N, F = int(n_rows), int(faces.shape[0])
+    N = int(n_rows)
     if not compact:
         assert xyz is None and conf is None and rgb is None and normals is None and capacity is None, "vertex rows are carried only with compact"
     else:
         assert xyz is not None and xyz.is_cuda and tuple(xyz.shape) == (N, 3), "compact needs xyz, a device tensor [n_rows,3]"
-        xyz = _f32c(xyz)
-    conf = _f32c(conf).reshape(N) if conf is not None else None
-    normals = _f32c(normals).reshape(N, 3) if normals is not None else None
-    rgb = rgb.contiguous() if rgb is not None else None
-    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
-    if out is None:
-        cap = N if capacity is None else int(capacity)
-        fcap = F if face_capacity is None else int(face_capacity)
-        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=faces.device)  # noqa: E731
-        i32 = torch.int32
-        out = PointCloud(label=f(N, dt=i32), component_faces=f(N, dt=i32), faces=f(fcap, 3, dt=i32), face_index=f(fcap, dt=i32),
-                         face_count=f(2, dt=i32), component_stats=f(5, dt=i32))
-        if compact:
-            out.xyz, out.count, out.index, out.remap = f(cap, 3), f(2, dt=i32), f(cap, dt=i32), f(N, dt=i32)
-            out.conf = f(cap) if conf is not None else None
-            out.rgb = f(cap, 3, dt=torch.uint8) if rgb is not None else None
-            out.normals = f(cap, 3) if normals is not None else None
+    xyz, faces, conf, rgb, normals, _, F = _list_inputs(xyz, faces, conf, rgb, normals, n_rows=N)  # xyz, when there is one, is checked above
+    cap, fcap = N if capacity is None else int(capacity), F if face_capacity is None else int(face_capacity)
+    out, outs = _list_outputs(out, faces.device, cap, conf, rgb, normals, vertex=compact, label=(N,), component_faces=(N,), faces=(fcap, 3),
+                              face_index=(fcap,), face_count=(2,), component_stats=(5,), **(dict(remap=(N,)) if compact else {}))
     for t in (out.label, out.component_faces, out.remap):
         assert t is None or int(t.shape[0]) >= N, "label / component_faces / remap cover the input rows"
-    rows = [int(t.shape[0]) for t in (out.xyz, out.conf, out.rgb, out.normals, out.index) if t is not None]
     frows = [int(t.shape[0]) for t in (out.faces, out.face_index) if t is not None]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    outs = _lib.MdPointsOutputs(None, None, ptr(out.xyz), ptr(out.rgb), ptr(out.conf), ptr(out.count), min(rows) if rows else 0, None)
-    comp = _lib.MdPointsComponents(int(min_faces), 1 if compact else 0, ptr(out.label), ptr(out.component_faces), ptr(out.index), ptr(out.remap),
-                                   ptr(out.faces), ptr(out.face_index), ptr(out.face_count), min(frows) if frows else 0,
-                                   ptr(out.component_stats))
+    comp = _lib.MdPointsComponents(int(min_faces), 1 if compact else 0, _ptr(out.label), _ptr(out.component_faces), _ptr(out.index), _ptr(out.remap),
+                                   _ptr(out.faces), _ptr(out.face_index), _ptr(out.face_count), min(frows) if frows else 0,
+                                   _ptr(out.component_stats))
     _lib.check(_lib.load().md_op_mesh_components(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, _p(faces), F, C.byref(comp),
                                                  C.byref(outs), _p(out.normals), _stream_ptr(dev.ordinal)))
     return out
@@ -724,10 +700,7 @@ def smooth_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, step: float
     smoothed faces, stats int32 [5] (invalid and degenerate faces, rows not in range, open rows, moved rows). capacity defaults to
     N: rows behind it are not written. `out`: a SmoothedMesh of an earlier call to write into again. Bit-identical to
     `pipeline.smooth_mesh`."""
-    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
-    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
-    xyz, faces = _f32c(xyz), faces.contiguous()
-    N, F = int(xyz.shape[0]), int(faces.shape[0])
+    xyz, faces, _, _, _, N, F = _list_inputs(xyz, faces)
     if out is None:
         cap = N if capacity is None else int(capacity)
         out = SmoothedMesh(xyz=torch.empty((max(cap, 0), 3), dtype=torch.float32, device=xyz.device),
@@ -749,13 +722,7 @@ def render_points(dev: Device, xyz: torch.Tensor, H: int, W: int, intrinsics=Non
     count: a device int32 tensor whose first word is the number of rows to render (what `unproject` / `voxel_thin` left in
     `count[-1:]`), read on the device. `out`: a RenderedPoints to write into again; a None field skips that output. Bit-identical
     to `pipeline.render_points`."""
-    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
-    xyz = _f32c(xyz)
-    N = int(xyz.shape[0])
-    rgb = rgb.contiguous() if rgb is not None else None
-    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
-    if rgb is not None and N == 0:  # an empty tensor has no address: one row that is never read stands for the rgb input
-        rgb = torch.zeros((1, 3), dtype=torch.uint8, device=xyz.device)
+    xyz, _, _, rgb, _, N, _ = _list_inputs(xyz, rgb=rgb, standin=True)
     assert count is None or (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() >= 1)
     T, cam, o, out, outs, keep = _render_request(xyz.device, int(H), int(W), intrinsics, extrinsics, focal_px, pixel_offset=pixel_offset,
                                                  z_near=z_near, z_far=z_far, radius=radius, want_rgb=rgb is not None, out=out)
@@ -776,9 +743,8 @@ def mesh_grid(dev: Device, depth: torch.Tensor, pixel_index: torch.Tensor, strid
     depth, pixel_index = _f32c(depth), pixel_index.contiguous()
     B, H, W = (int(v) for v in depth.shape)
     assert tuple(pixel_index.shape) == (B, H, W)
-    s = max(int(stride), 1)  # a bad stride is the library's to refuse
     if faces is None:
-        cap = 2 * B * ((H + s - 1) // s - 1) * ((W + s - 1) // s - 1) if face_capacity is None else int(face_capacity)
+        cap = _lattice(B, H, W, stride)[2] if face_capacity is None else int(face_capacity)
         faces = torch.empty((max(cap, 0), 3), dtype=torch.int32, device=depth.device)
     else:
         cap = int(faces.shape[0]) if face_capacity is None else int(face_capacity)
@@ -799,14 +765,7 @@ def render_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, H: int, W: 
     `RasterisedMesh` of H x W images. face_count: a device int32 tensor whose first word is the number of faces to draw (what
     `mesh_grid` / `unproject(mesh=)` left in `face_count[-1:]`), read on the device. `out`: a RasterisedMesh to write into again; a
     None field skips that output. Bit-identical to `pipeline.render_mesh`."""
-    assert xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3, "xyz is a device tensor [N,3]"
-    assert faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces is a device int32 tensor [F,3]"
-    xyz, faces = _f32c(xyz), faces.contiguous()
-    N, F = int(xyz.shape[0]), int(faces.shape[0])
-    rgb = rgb.contiguous() if rgb is not None else None
-    assert rgb is None or (rgb.is_cuda and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (N, 3))
-    if rgb is not None and N == 0:  # an empty tensor has no address: one row that is never read stands for the rgb input
-        rgb = torch.zeros((1, 3), dtype=torch.uint8, device=xyz.device)
+    xyz, faces, _, rgb, _, N, F = _list_inputs(xyz, faces, rgb=rgb, standin=True)
     assert face_count is None or (face_count.is_cuda and face_count.dtype == torch.int32 and face_count.is_contiguous() and face_count.numel() >= 1)
     T, cam, o, out, outs, keep = _raster_request(xyz.device, int(H), int(W), intrinsics, extrinsics, focal_px, pixel_offset=pixel_offset,
                                                  z_near=z_near, z_far=z_far, cull=cull, max_extent=max_extent, want_rgb=rgb is not None, out=out)

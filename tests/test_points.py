@@ -443,7 +443,7 @@ def test_infer_points_da3_equals_infer_then_unproject(dev, precision):
 
 def _host_call(m, x, rgb, cams, opts, want_conf):
     """md_infer_points with every input and output in host memory -> numpy dict (poisoned beyond the points)."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     B, _, H, W = x.shape
     cap = B * H * W
     x = np.ascontiguousarray(x, f32)

@@ -188,7 +188,7 @@ def test_entries_through_ctypes_null_parts_refusals_and_host_memory(dev):
     """The narrower entries equal the widest with a null part; compact, comp's pointers with min_faces 0, faces without face_count and
     comp without a mesh are refused by the library itself; the caller's mesh outputs still hold the unfiltered mesh; the
     host-memory call equals the device-memory one."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     m = _da3(dev)
     try:

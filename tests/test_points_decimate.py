@@ -204,7 +204,7 @@ def test_null_and_zero_voxel_are_the_call_without_it_and_the_refusals_leave_the_
 def test_entries_through_ctypes_null_parts_refusals_and_host_memory(dev):
     """The narrower entries equal the widest with a null part; dec's pointers with voxel 0 and dec without a mesh are refused by the
     library itself; the host-memory call equals the device-memory one."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     m = _da3(dev)
     try:

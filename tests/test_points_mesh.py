@@ -118,7 +118,7 @@ def test_each_mesh_output_alone_and_a_short_face_capacity(dev):
 
 def _op_bytes(dev, entry, d, K, mesh):
     """md_op_unproject_normals or md_op_unproject_mesh (mesh: None, or an all-null md_points_mesh) on poisoned outputs -> bytes"""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     B, H, W = d.shape
     t = dict(point_map=torch.full((B, H, W, 3), 123456.0, device="cuda"), mask=torch.full((B, H, W), 77, dtype=torch.uint8, device="cuda"),
              xyz=torch.full((B * H * W, 3), 123456.0, device="cuda"), count=torch.full((B + 1,), -5, dtype=torch.int32, device="cuda"),
@@ -211,7 +211,7 @@ CANARY = 64
 def _call(m, entry, x, host, face_cap, mesh=True, thin=0.0, max_rtol=0.2, faces=True, face_count=True, face_capacity=None):
     """md_infer_points_render or md_infer_points_mesh through ctypes, everything in host or in device memory -> (rc, outputs).
     face_cap: the faces the buffer holds, and the struct's face_capacity unless that is given."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     B, S = x.shape[0], x.shape[2]
     cap = B * 35 * 35

@@ -487,7 +487,8 @@ def test_null_and_all_zero_normals_are_the_call_without_them(dev, lib):
     kw = dict(pixel_offset=0.5, stride=2, world=True, **_scene_opts(True, True))
     want = _run_op(dev, d, K=K, E=E, conf=c, rgb=rgb, normals=False, **kw)
     assert want["count"][-1] > 0
-    from burn_depth_amd.depth_pro import _points_cameras, _points_opts, _points_outputs, _stream_ptr
+    from burn_depth_amd.depth_pro import _stream_ptr
+    from burn_depth_amd.points import _points_cameras, _points_opts, _points_outputs
     td, tc, trgb = _t(d), _t(c), _t(rgb)
     for nrm in (None, _lib.MdPointsNormals(None, None, 0.0)):
         out, stores = _fresh(B, H, W, B * H * W, True, True, normals=False)
@@ -565,7 +566,7 @@ NRM = dict(normals=True, normal_min_cos=0.05)
 
 def _host_call(m, x, opts, min_cos, want_conf):
     """md_infer_points_normals with every input and output in host memory -> numpy dict (poisoned beyond the points)."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     B, _, H, W = x.shape
     cap = B * H * W
     x = np.ascontiguousarray(x, f32)

@@ -297,7 +297,7 @@ def _read(t):
 def test_narrower_entries_are_the_widest_entry_with_a_null_part_and_host_outputs_match(dev):
     """md_infer_points_raster and md_infer_points_voxel against md_infer_points_outlier with outl NULL and with radius 0: the same
     bytes. Then the widest entry with everything in host memory against the device-memory call."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     m = _da3(dev)
     try:

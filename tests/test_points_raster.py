@@ -114,7 +114,7 @@ CANARY = 64
 def _call(m, entry, x, host, cams, rst=True, thin=0.0, faces=True, xyz=True, cull=0, max_extent=0, z_near=0.0, T=2):
     """md_infer_points_mesh or md_infer_points_raster through ctypes, everything in host or in device memory -> (rc, outputs);
     cams: K [T,3,3], E [T,3,4] of the targets; the raster outputs lie between canaries"""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     B, S = x.shape[0], x.shape[2]
     cap, fcap, px = B * 35 * 35, 2 * B * 34 * 34, T * TH * TW

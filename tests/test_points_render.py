@@ -149,7 +149,7 @@ def _same_bytes(a, b, what, keys=None):
 
 def _call(m, entry, x, rgb, host, T, H, W, cams, render=True):
     """md_infer_points_voxel or md_infer_points_render through ctypes, everything in host or in device memory -> outputs"""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     B, S = x.shape[0], x.shape[2]
     t, outs, routs = _buffers(B, S, B * 35 * 35, T, H, W, host)

@@ -177,7 +177,7 @@ def test_entries_through_ctypes_stray_pointers_missing_list_and_host_memory(dev)
     """A pointer with iterations == 0, the stage without a mesh request, without the list's count, with outlier removal, and
     behind components without their faces are refused by the library itself with nothing written; the narrower entry equals the
     widest with a null part; the host-memory call equals the device-memory one."""
-    from burn_depth_amd.depth_pro import _points_opts
+    from burn_depth_amd.points import _points_opts
     lib = _lib.load()
     m = _da3(dev)
     try:

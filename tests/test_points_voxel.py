@@ -222,7 +222,7 @@ def _same_bytes(a, b, what):
 def test_narrow_entries_are_the_widest_entry_with_nulls(dev):
     """md_infer_points, _filtered and _normals against md_infer_points_voxel, md_op_unproject against md_op_unproject_normals: the
     same request, with NULL and with all-zero structs for the parts the narrower entry lacks, gives the same bytes."""
-    from burn_depth_amd.depth_pro import _points_opts, _view_filter_opts
+    from burn_depth_amd.points import _points_opts, _view_filter_opts
     lib = _lib.load()
     m = _da3(dev)
     try:
@@ -280,7 +280,7 @@ def test_narrow_entries_are_the_widest_entry_with_nulls(dev):
 def test_host_in_host_out_with_filter_normals_and_thinning(dev):
     """md_infer_points_voxel with the image, rgb and every output in host memory, the view filter, the normals and the thinning all
     on: each output is the device-memory call's, byte for byte, and nothing behind the surviving rows is written."""
-    from burn_depth_amd.depth_pro import _points_opts, _view_filter_opts
+    from burn_depth_amd.points import _points_opts, _view_filter_opts
     lib = _lib.load()
     m = _da3(dev)
     try:

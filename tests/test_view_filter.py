@@ -467,7 +467,7 @@ def test_infer_points_filtered_da3_equals_the_composition(dev):
                 m.infer_points(x, **kw)
             assert e.value.code == _lib.MD_ERR_INVALID_ARG, kw
         # the option structs must agree on pixel_offset and the depth bounds
-        from burn_depth_amd.depth_pro import _points_cameras, _points_opts, _points_outputs, _view_filter_opts
+        from burn_depth_amd.points import _points_cameras, _points_opts, _points_outputs, _view_filter_opts
         res, outs = _points_outputs(x.device, 3, 70, 70, True, True, None, 1, False, True, True, None)
         cam, _ = _points_cameras(x.device, 3)
         for fo in (_view_filter_opts(0.5, 0, 0, 40), _view_filter_opts(0, 1.0, 0, 40), _view_filter_opts(0, 0, 9.0, 40)):
