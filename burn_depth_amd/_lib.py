@@ -100,6 +100,14 @@ class MdPointsSmooth(C.Structure):
                 ("xyz", C.c_void_p), ("normals", C.c_void_p), ("stats", C.c_void_p)]
 
 
+class MdPointsPlanes(C.Structure):
+    """md_points_planes (include/mi_depth.h)."""
+    _fields_ = [("planes", C.c_int32), ("hypotheses", C.c_int32), ("tol", C.c_float), ("min_inliers", C.c_int32), ("seed", C.c_uint32),
+                ("normal_min_cos", C.c_float), ("axis", C.c_float * 3), ("axis_min_cos", C.c_float), ("mode", C.c_int32),
+                ("plane", C.c_void_p), ("plane_count", C.c_void_p), ("hypothesis", C.c_void_p), ("label", C.c_void_p), ("index", C.c_void_p),
+                ("dropped", C.c_void_p)]
+
+
 class MdRenderOpts(C.Structure):
     """md_render_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
@@ -272,6 +280,7 @@ SYMBOLS = {
     "md_op_decimate_mesh": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsDecimate), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_op_mesh_components": (_I, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsComponents), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_op_smooth_mesh": (_I, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(MdPointsSmooth), C.c_int64, _P]),
+    "md_op_fit_planes": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsPlanes), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
@@ -375,7 +384,7 @@ def _infer_points(*parts):
 _POINTS_HEAD = [MdViewFilterOpts, MdPointsOpts, MdPointsOutputs]
 _POINTS_PARTS = [("normals", MdPointsNormals), ("voxel", MdPointsVoxel), ("render", MdPointsRender), ("mesh", MdPointsMesh),
                  ("raster", MdPointsRaster), ("outlier", MdPointsOutlier), ("decimate", MdPointsDecimate), ("components", MdPointsComponents),
-                 ("smooth", MdPointsSmooth)]
+                 ("smooth", MdPointsSmooth), ("planes", MdPointsPlanes)]
 SYMBOLS["md_infer_points"] = _infer_points(*_POINTS_HEAD[1:])
 SYMBOLS["md_infer_points_filtered"] = _infer_points(*_POINTS_HEAD)
 SYMBOLS.update({f"md_infer_points_{name}": _infer_points(*_POINTS_HEAD, *(p for _, p in _POINTS_PARTS[:i + 1]))

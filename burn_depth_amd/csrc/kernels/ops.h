@@ -247,6 +247,43 @@ size_t outlier_scratch_bytes(int n);
 int launch_radius_outliers(const OutlierParams& p, void* scratch, hipStream_t s);
 const int32_t* outlier_flags(const void* scratch, int n);
 
+// ---- RANSAC plane extraction (kernels/planes.hip, kernels/planes_math.h; md_op_fit_planes, md_infer_points_planes) ----
+// A point list xyz [n,3] (+ conf, rgb, normals rows) -> up to `planes` planes, one per round: the live rows are indexed in row
+// order (classify / scan / scatter), `hypotheses` triples are drawn from them by a fixed mixer, every live row is tested against
+// every hypothesis (the count kernel), the largest count wins (ties: the smallest hypothesis) and its inliers get the round as
+// label and leave the live set. mode 1 / 2 then compacts the rows without / with a plane through launch_list_compact. Every
+// pointer is a device pointer. Selection only: integer counts of an f32 predicate, nothing depends on the order of arrival.
+struct PlanesParams {
+  const float* xyz = nullptr;
+  const float* conf = nullptr;        // carried to conf_out
+  const uint8_t* rgb = nullptr;       // carried to rgb_out
+  const float* normals = nullptr;     // the normals predicate (normal_min_cos > 0); carried to normals_out
+  const int32_t* in_count = nullptr;  // as VoxelParams::in_count
+  int n = 0;                          // rows the launches cover: the live count is min(in_count[B], n)
+  int B = 1;
+  int planes = 0, hypotheses = 0, min_inliers = 0, mode = 0;
+  unsigned seed = 0u;
+  float tol = 0.f, normal_min_cos = 0.f, axis_min_cos = 0.f;
+  float axis[3] = {0.f, 0.f, 0.f};
+  float* plane = nullptr;          // [planes,4]; null: skip
+  int32_t* plane_count = nullptr;  // [planes + 1]; null: skip
+  int32_t* hypothesis = nullptr;   // [planes]; null: skip
+  int32_t* label = nullptr;        // [n]; null: it lives in the scratch
+  int32_t* dropped = nullptr;      // [1]; null: skip
+  float* xyz_out = nullptr;        // mode 1 / 2: the compacted rows
+  float* conf_out = nullptr;
+  uint8_t* rgb_out = nullptr;
+  float* normals_out = nullptr;
+  int32_t* index = nullptr;  // [capacity] source row
+  int32_t* count = nullptr;  // [B + 1] survivors per view, then their total
+  long capacity = 0;
+};
+constexpr int kPlaneCountRows = 8;   // rows a thread of the count kernel keeps in registers
+constexpr int kPlaneCountChunk = 4;  // hypotheses of one trip of its loop: their planes are loaded together; a tail loop takes the rest
+// bytes of the scratch (label home | ballot words | tile counts | tile offsets | live index 4 n | hypotheses 16 B + count 4 B | state)
+size_t planes_scratch_bytes(int n, int hypotheses);
+int launch_fit_planes(const PlanesParams& p, void* scratch, hipStream_t s);
+
 // ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
 // A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour
 // image: clear, splat (atomicMin of (bits(p.z) << 32) | row over the footprint), resolve. Every pointer is a device pointer.

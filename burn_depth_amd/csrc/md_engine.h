@@ -370,7 +370,7 @@ struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], c
   const float* normals = nullptr;
   int64_t N = 0;
 };
-// One md_infer_points* request: what the widest entry (md_infer_points_smooth) takes. A narrower entry leaves the parts it lacks
+// One md_infer_points* request: what the widest entry (md_infer_points_planes) takes. A narrower entry leaves the parts it lacks
 // null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
 struct PointsCall {
   const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
@@ -392,6 +392,7 @@ struct PointsCall {
   const md_points_decimate* dec = nullptr;  // given: vertex-clustering decimation behind the mesh (pointers of out_kind); needs `mesh`
   const md_points_components* comp = nullptr;  // given: island removal behind the mesh, face-only (pointers of out_kind); needs `mesh`
   const md_points_smooth* smooth = nullptr;    // given: smoothing of the list over the faces the rasteriser reads (pointers of out_kind); needs `mesh`
+  const md_points_planes* pln = nullptr;       // given: plane extraction from the list the call ends with (pointers of out_kind); mode 1 / 2 writes that list
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
@@ -413,6 +414,9 @@ int op_mesh_components(md_device_t dev, const PointList& in, const int32_t* face
 // xyz [N,3] and faces [F,3] over its rows; rows >= capacity of smooth's outputs are not written
 int op_smooth_mesh(md_device_t dev, const float* xyz, int64_t N, const int32_t* faces, int64_t F, const md_points_smooth* smooth, int64_t capacity,
                    hipStream_t stream);
+// in: the rows, one view; out's list fields and normals_out with pln->mode 1 / 2 only
+int op_fit_planes(md_device_t dev, const PointList& in, const md_points_planes* pln, const md_points_outputs* out, float* normals_out,
+                  hipStream_t stream);
 // in.xyz / in.rgb: the list; count: its device count word or null
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream);

@@ -17,7 +17,9 @@
 // md_op_decimate_mesh / md_infer_points_decimate (kernels/decimate.hip), md_op_mesh_components / md_infer_points_components
 // (kernels/components.hip) and md_op_smooth_mesh / md_infer_points_smooth (kernels/smooth.hip) work on the mesh stage's faces:
 // the decimation writes the list and the faces the call ends with, the other two leave the list as it is.
-// The eleven md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
+// md_op_fit_planes / md_infer_points_planes (kernels/planes.hip) label the rows of the list the call ends with by the planes a RANSAC
+// finds in it; with mode 1 / 2 the stage is the last one that writes a list.
+// The twelve md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
 // which holds the list the call ends with once (PointsPlan::fin, wired to the last list stage in plan_homes).
 #include <algorithm>
 #include <cfloat>
@@ -28,6 +30,7 @@
 
 #include "md_engine.h"
 #include "md_engine_util.h"
+#include "kernels/planes_math.h"  // the limits of the plane stage
 
 // Device homes of what the call needs on the device and the caller did not hand over there. Grow-only (md::grow): a captured
 // graph bakes their addresses.
@@ -54,6 +57,8 @@ struct md_model_s::PointsState {
                                   // (md_infer_points_components: the unfiltered faces of the call's list, likewise)
   md::GrowBuf<void> ctable;       // md_infer_points_components: the components' scratch (components_scratch_bytes)
   md::GrowBuf<void> stable;       // md_infer_points_smooth: the smoothing's scratch (smooth_scratch_bytes)
+  md::GrowBuf<void> ptable;       // md_infer_points_planes: the plane extraction's scratch (planes_scratch_bytes)
+  md::GrowBuf<void> plist;        // its input with mode 1 / 2 behind the thinning: the thinned list, laid out as vlist
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
@@ -243,6 +248,41 @@ int check_smooth_part(const md_points_smooth* s) {
     return MD_OK;
   }
   return check_smooth_values(s);
+}
+
+bool planes_on(const md_points_planes* f) { return f && f->planes != 0; }
+
+// model call: planes == 0 is the call without the stage and takes none of its outputs. has_normals: there is a normals row
+int check_planes(const md_points_planes* f, const md_points_outputs* out, bool has_normals, bool op) {
+  if (!f) return MD_OK;
+  if (f->planes == 0 && !op) {
+    if (f->plane || f->plane_count || f->hypothesis || f->label || f->index || f->dropped) MD_FAIL(MD_ERR_INVALID_ARG, "plane outputs without planes");
+    return MD_OK;
+  }
+  if (f->planes < 1 || f->planes > kPlanesMax) MD_FAIL(MD_ERR_INVALID_ARG, "planes = %d: must lie in 1..%d", f->planes, kPlanesMax);
+  if (f->hypotheses < 1 || f->hypotheses > kPlaneHypothesesMax)
+    MD_FAIL(MD_ERR_INVALID_ARG, "hypotheses = %d: must lie in 1..%d", f->hypotheses, kPlaneHypothesesMax);
+  if (!(f->tol > 0.f) || !std::isfinite(f->tol)) MD_FAIL(MD_ERR_INVALID_ARG, "tol = %g: must be finite and > 0", (double)f->tol);
+  if (f->min_inliers < 3) MD_FAIL(MD_ERR_INVALID_ARG, "min_inliers = %d: must be >= 3", f->min_inliers);
+  if (!(f->normal_min_cos >= 0.f && f->normal_min_cos <= 1.f)) MD_FAIL(MD_ERR_INVALID_ARG, "normal_min_cos = %g: must lie in [0, 1]", (double)f->normal_min_cos);
+  if (!(f->axis_min_cos >= 0.f && f->axis_min_cos <= 1.f)) MD_FAIL(MD_ERR_INVALID_ARG, "axis_min_cos = %g: must lie in [0, 1]", (double)f->axis_min_cos);
+  if (f->mode < 0 || f->mode > 2) MD_FAIL(MD_ERR_INVALID_ARG, "mode = %d: 0, 1 or 2", f->mode);
+  if (f->normal_min_cos > 0.f && !has_normals) MD_FAIL(MD_ERR_INVALID_ARG, "normal_min_cos > 0 needs the normals rows");
+  if (f->axis_min_cos > 0.f && !(std::isfinite(f->axis[0]) && std::isfinite(f->axis[1]) && std::isfinite(f->axis[2])))
+    MD_FAIL(MD_ERR_INVALID_ARG, "axis_min_cos > 0 needs a finite axis");
+  if (f->index && f->mode == 0) MD_FAIL(MD_ERR_INVALID_ARG, "index needs mode 1 or 2");
+  MD_TRY(need_count(f->index, out, "index"));
+  return MD_OK;
+}
+
+// the options and the outputs of the stage's own; the caller adds the rows
+PlanesParams make_planes(const md_points_planes& f) {
+  PlanesParams q;
+  q.planes = f.planes; q.hypotheses = f.hypotheses; q.min_inliers = f.min_inliers; q.mode = f.mode; q.seed = f.seed;
+  q.tol = f.tol; q.normal_min_cos = f.normal_min_cos; q.axis_min_cos = f.axis_min_cos;
+  q.axis[0] = f.axis[0]; q.axis[1] = f.axis[1]; q.axis[2] = f.axis[2];
+  q.plane = f.plane; q.plane_count = f.plane_count; q.hypothesis = f.hypothesis; q.label = f.label; q.dropped = f.dropped; q.index = f.index;
+  return q;
 }
 
 bool outlier_on(const md_points_outlier* q) { return q && q->radius != 0.f; }
@@ -562,6 +602,25 @@ int op_radius_outliers(md_device_t dev, const PointList& in, const md_points_out
   return scratch.finish_flags(launch_radius_outliers(p, scratch.p, st), outlier_flags(scratch.p, p.n), nullptr, kOutlierRanOut);
 }
 
+int op_fit_planes(md_device_t dev, const PointList& in, const md_points_planes* pln, const md_points_outputs* out, float* normals_out,
+                  hipStream_t stream) {
+  if (!pln) MD_FAIL(MD_ERR_INVALID_ARG, "plane options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  MD_TRY(check_planes(pln, out, in.normals != nullptr, true));
+  MD_TRY(check_list_op("plane extraction", in, out, normals_out));
+  if (pln->mode == 0 && (out->xyz || out->rgb || out->conf || normals_out)) MD_FAIL(MD_ERR_INVALID_ARG, "mode 0 writes no list: the compacted outputs need mode 1 or 2");
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
+  PlanesParams p = make_planes(*pln);
+  p.xyz = in.xyz; p.conf = in.conf; p.rgb = in.rgb; p.normals = in.normals;
+  p.n = (int)in.N; p.B = 1;
+  p.xyz_out = out->xyz; p.conf_out = out->conf; p.rgb_out = out->rgb; p.normals_out = normals_out;
+  p.count = pln->mode ? out->count : nullptr; p.capacity = out->capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(planes_scratch_bytes(p.n, p.hypotheses)));
+  return scratch.finish(launch_fit_planes(p, scratch.p, st));
+}
+
 int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
                      const md_points_outputs* out, float* normals_out, hipStream_t stream) {
   if (!dec) MD_FAIL(MD_ERR_INVALID_ARG, "decimation options are null");
@@ -725,7 +784,7 @@ struct ListRows {
   int32_t* count = nullptr;  // [B + 1]
 };
 
-// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too) and OutlierParams
+// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too), OutlierParams and PlanesParams
 template <typename P>
 void reads(P& p, const ListRows& l) { p.xyz = l.xyz; p.conf = l.conf; p.rgb = l.rgb; p.normals = l.normals; p.in_count = l.count; }
 template <typename P>
@@ -744,7 +803,8 @@ struct OutSlot {  // a host output's way back: rows of `row_bytes` from its devi
 struct PointsPlan {
   hipStream_t st = nullptr;
   bool dual = false;
-  bool thin = false, mesh = false, filt = false, deci = false, comp = false, smo = false;  // the stages that are on
+  bool thin = false, mesh = false, filt = false, deci = false, comp = false, smo = false, pln = false;  // the stages that are on
+  bool pcut = false;  // pln with mode 1 / 2: the plane stage is the last one that writes a list
   bool own_faces = false;  // deci / comp / smo: a later stage reads the faces, so the mesh stage writes the model's own (`gd`)
   size_t npx = 0;
   long rows = 0;  // rows the unthinned list of the call can have (list_rows); its mesh has at most 2 * rows faces
@@ -766,9 +826,11 @@ struct PointsPlan {
   MeshParams gd;    // own_faces: the mesh stage's second set of face outputs, the model's own, complete and with the true count
   ComponentsParams k;  // comp: launch_mesh_components', from the list's count and the faces `gd` wrote
   SmoothParams sm;     // smo: launch_smooth_mesh's, from `fin` and the faces of `k`, or else those `gd` wrote
+  PlanesParams pn;     // pln: launch_fit_planes', from `fin` (mode 0) or the model's own list in front of it (pcut)
   int queue = 0;    // the raster's queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   int32_t unfiltered = 0;  // filt with host outputs: the rows of the unfiltered list, read back for outl->neighbours' slot
+  int32_t plane_rows = 0;  // pcut with host outputs: the rows of the plane stage's input list, read back for pln->label's slot
   std::vector<OutSlot> slots;
 };
 
@@ -803,6 +865,13 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
   slot(out.count, pl.fin.count, 4, views);
   if (pl.thin) slot(c.vox->dropped, pl.v.dropped, 4, 1);
   if (pl.filt) slot(c.outl->dropped, pl.u.dropped, 4, 1);
+  if (pl.pln) {
+    const size_t P = (size_t)c.pln->planes;
+    slot(c.pln->plane, pl.pn.plane, 16, P);
+    slot(c.pln->plane_count, pl.pn.plane_count, 4, P + 1);
+    slot(c.pln->hypothesis, pl.pn.hypothesis, 4, P);
+    slot(c.pln->dropped, pl.pn.dropped, 4, 1);
+  }
   if (pl.deci) {
     slot(c.dec->dropped, pl.d.v.dropped, 4, 1);
     slot(c.dec->face_count, pl.d.face_count, 4, views);
@@ -859,6 +928,11 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(k.faces, pl.k.faces_out, 12, (size_t)k.face_capacity, total_of(k.face_count));
     slot(k.face_index, pl.k.face_index, 4, (size_t)k.face_capacity, total_of(k.face_count));
   }
+  if (pl.pln) {  // label: rows parallel to the stage's input, which is the list of the call (mode 0) or the list in front of it
+    if (pl.pcut) slot(c.pln->label, pl.pn.label, 4, list, &pl.plane_rows);
+    else slot(c.pln->label, pl.pn.label, 4, cap, n);
+    slot(c.pln->index, pl.pn.index, 4, cap, n);
+  }
   if (pl.smo) {  // rows parallel to the list: they travel as its rows do
     slot(c.smooth->xyz, pl.sm.xyz_out, 12, cap, n);
     slot(c.smooth->normals, pl.sm.normals_out, 12, cap, n);
@@ -909,6 +983,9 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.q = make_normals(c.nrm);
   pl.thin = voxel_on(c.vox) && out.count;  // without the list there is nothing to thin
   pl.filt = outlier_on(c.outl) && out.count;
+  pl.pln = planes_on(c.pln);  // the count is there: infer_points refuses the stage without it
+  pl.pcut = pl.pln && c.pln->mode != 0;
+  if (pl.pln) pl.pn = make_planes(*c.pln);
   if (c.rnd) {
     pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
@@ -944,7 +1021,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     else if (pl.deci) ends_with(pl.d.faces_out, pl.d.face_count, c.dec->face_capacity);
     else ends_with(pl.g.faces, pl.g.face_count, c.mesh->face_capacity);
   }
-  const bool own_list = pl.thin || pl.filt || pl.deci;  // the scatter fills a list of the model's own: a later stage writes `fin`
+  const bool own_list = pl.thin || pl.filt || pl.deci || pl.pcut;  // the scatter fills a list of the model's own: a later stage writes `fin`
   auto scatter_to = [&](const ListRows& l) { p.xyz = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; pl.q.normals = l.normals; p.count = l.count; };
   if (!own_list) scatter_to(pl.fin);
   if (pl.comp || pl.smo) {  // all faces of the call's list go to the model's face home; the stages read them and the list's device count
@@ -967,6 +1044,12 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
       MD_TRY(grow(m, st, f->stable, smooth_scratch_bytes(sm.n)));
     }
   }
+  if (pl.pln) {
+    PlanesParams& f = pl.pn;
+    f.B = B; f.n = (int)(pl.pcut ? rows : std::min<long>((long)out.capacity, rows));
+    MD_TRY(grow(m, st, m->points->ptable, planes_scratch_bytes(f.n, f.hypotheses)));
+    if (!pl.pcut) reads(f, pl.fin);  // mode 0: the rows of the call's list below its capacity
+  }
   if (!own_list) return MD_OK;
   const bool want_rgb = out.rgb != nullptr, want_nrm = c.nrm && c.nrm->normals;
   const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = pl.dual ? align_up((size_t)rows * 4, 256) : 0;
@@ -980,8 +1063,9 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(grow(m, st, f->vlist, b_list));
   if (pl.thin) MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
   if (pl.filt) MD_TRY(grow(m, st, f->otable, outlier_scratch_bytes((int)rows)));
-  if (pl.filt && pl.thin) MD_TRY(grow(m, st, f->flist, b_list));
-  // The chain scatter -> outlier removal -> voxel thinning, or scatter -> decimation (the decimation is the thinning, with the
+  if (pl.filt && (pl.thin || pl.pcut)) MD_TRY(grow(m, st, f->flist, b_list));
+  if (pl.thin && pl.pcut) MD_TRY(grow(m, st, f->plist, b_list));
+  // The chain scatter -> outlier removal -> voxel thinning -> plane extraction (mode 1 / 2), or scatter -> decimation (the decimation is the thinning, with the
   // faces of the model's face home): every stage but the last writes a list of the model's own, of which every row is usable;
   // the last one writes `fin` below the caller's capacity. Nothing else knows which stage that is.
   ListRows l = rows_of(f->vlist.p);
@@ -990,15 +1074,22 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.filt) {
     OutlierParams& u = pl.u;
     reads(u, l);
-    if (pl.thin) l = rows_of(f->flist.p);
-    writes(u, pl.thin ? l : pl.fin);
-    u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = pl.thin ? rows : (long)out.capacity;
+    const bool last = !pl.thin && !pl.pcut;
+    if (!last) l = rows_of(f->flist.p);
+    writes(u, last ? pl.fin : l);
+    u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = last ? (long)out.capacity : rows;
   }
   if (pl.thin) {
     VoxelParams& v = pl.v;
     reads(v, l);
-    writes(v, pl.fin);
-    v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = out.capacity;
+    if (pl.pcut) l = rows_of(f->plist.p);
+    writes(v, pl.pcut ? l : pl.fin);
+    v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = pl.pcut ? rows : (long)out.capacity;
+  }
+  if (pl.pcut) {
+    reads(pl.pn, l);
+    writes(pl.pn, pl.fin);
+    pl.pn.capacity = (long)out.capacity;
   }
   if (pl.deci) {
     DecimateParams& d = pl.d;
@@ -1134,6 +1225,9 @@ int run_components(md_model_s* m, const PointsCall&, PointsPlan& pl) { return la
 // Smoothing: the list of the call and the faces the rasteriser reads -> smooth's outputs. The list is not touched.
 int run_smooth(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_smooth_mesh(pl.sm, m->points->stable.p, pl.st); }
 
+// Plane extraction: the list of the call -> pln's outputs; with mode 1 / 2 the model's own list -> the list outputs of the call.
+int run_planes(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_fit_planes(pl.pn, m->points->ptable.p, pl.st); }
+
 // Rendering: the list the call ends with and its device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
@@ -1171,6 +1265,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
   if (pl.filt) MD_TRY(d2h(&outl_overflow, outlier_flags(m->points->otable.p, pl.u.n), 4));
   if (pl.filt) MD_TRY(d2h(&pl.unfiltered, pl.u.in_count + c.B, 4));
+  if (pl.pcut) MD_TRY(d2h(&pl.plane_rows, pl.pn.in_count + c.B, 4));
   MD_HIP(hipStreamSynchronize(pl.st));
   if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "%s", kDecimateRanOut);
   if (outl_overflow) MD_FAIL(MD_ERR_HIP, "%s", kOutlierRanOut);
@@ -1205,6 +1300,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, long rows, hipSt
   if (pl.deci) MD_TRY(timed("points_decimate", run_decimate));
   if (pl.comp) MD_TRY(timed("points_components", run_components));
   if (pl.smo) MD_TRY(timed("points_smooth", run_smooth));
+  if (pl.pln) MD_TRY(timed("points_planes", run_planes));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
@@ -1245,6 +1341,11 @@ std::vector<uintptr_t> points_graph_key(md_model_t m, const PointsCall& c, hipSt
     const md_points_smooth& q = *c.smooth;
     key_add(key, 0x534d5448u, q.step, q.lambda, q.mu, q.iterations, q.pin_boundary, q.xyz, q.normals, q.stats);
     key_add(key, c.mesh->max_rtol);
+  }
+  if (planes_on(c.pln)) {
+    const md_points_planes& f = *c.pln;
+    key_add(key, 0x504c414eu, f.planes, f.hypotheses, f.tol, f.min_inliers, f.seed, f.normal_min_cos, f.axis[0], f.axis[1], f.axis[2], f.axis_min_cos, f.mode);
+    key_add(key, f.plane, f.plane_count, f.hypothesis, f.label, f.index, f.dropped);
   }
   if (mesh_on(c.mesh))  // every output null: the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
@@ -1316,6 +1417,20 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (c.rst && !c.smooth->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "rasterising the smoothed mesh needs the smoothing output `xyz`");
     if (2 * rows >= (1l << 30))
       MD_FAIL(MD_ERR_SHAPE, "smoothing takes fewer than 2^30 faces, the mesh may have %ld", 2 * rows);
+  }
+  MD_TRY(check_planes(c.pln, out, c.nrm && c.nrm->normals, false));
+  if (planes_on(c.pln)) {
+    if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "plane extraction needs the list's `count`");
+    if (c.pln->mode != 0) {
+      if (mesh_on(c.mesh) || decimate_on(c.dec) || components_on(c.comp) || smooth_on(c.smooth))
+        MD_FAIL(MD_ERR_INVALID_ARG, "plane extraction with mode 1 / 2 together with a mesh stage: the rows the faces name would vanish");
+      if ((voxel_on(c.vox) && (c.vox->index || c.vox->weight)) || (outlier_on(c.outl) && c.outl->index))
+        MD_FAIL(MD_ERR_INVALID_ARG, "plane extraction with mode 1 / 2 together with index / weight of an earlier stage: the rows they are parallel to are not returned");
+    } else {
+      if (!out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "plane extraction with mode 0 needs the list output `xyz`");
+      if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "plane extraction together with decimation: the rows are renumbered; md_op_fit_planes serves the decimated list");
+    }
+    if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "plane extraction takes fewer than 2^30 rows, the list may have %ld", rows);
   }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));

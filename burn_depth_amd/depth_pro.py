@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, points
 from .config import DepthProConfig, InterpolationMethod, Precision
-from .points import PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
+from .points import FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
 
 
 class Device:
@@ -462,7 +462,7 @@ class DepthPro:
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
                      raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
-                     components: Optional[dict] = None, smooth: Optional[dict] = None, **opts) -> PointCloud:
+                     components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
@@ -504,7 +504,13 @@ class DepthPro:
         (lam | mu) or Laplacian smoothing of the list over the faces the rasteriser reads (those of components= when given), on
         the integer lattice of side step. The list, `normals` and render= are unchanged; the smoothed rows, the vertex normals of
         the smoothed faces and the counters come back as `smooth` (`SmoothedMesh`), and raster= draws the smoothed rows.
-        iterations 0 or None: the call without it. Not with decimate=, voxel > 0 or outlier= (`ops.smooth_mesh` serves those)."""
+        iterations 0 or None: the call without it. Not with decimate=, voxel > 0 or outlier= (`ops.smooth_mesh` serves those).
+        planes (`md_points_planes`, the one form that runs through `md_infer_points_planes`): dict(planes=1, hypotheses=256, tol=,
+        min_inliers=3, seed=0, normal_min_cos=0, axis=(x, y, z), axis_min_cos=0, mode="label"): RANSAC plane extraction from the
+        list behind every other list stage; the equations, the inlier counts and the label of every row come back as `planes`
+        (`FittedPlanes`). mode "drop" / "keep": the list the call returns (and render= sees) holds the rows without / of a plane
+        and `index` names their rows in the list in front of the stage; not with mesh=. normal_min_cos > 0 needs normals=True.
+        planes 0 or None: the call without it."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -517,10 +523,10 @@ class DepthPro:
             intrinsics=intrinsics, extrinsics=extrinsics, focal_px=f_px, dense=dense, compact=compact, capacity=capacity, out=out,
             conf_percentile=conf_percentile, view_rtol=view_rtol, min_views=min_views, normals=normals, normal_min_cos=normal_min_cos,
             voxel=voxel, render=render, mesh=mesh, raster=raster, outlier=outlier, decimate=decimate, components=components,
-            smooth=smooth, opts=opts)
-        _lib.check(self._lib.md_infer_points_smooth(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
-                                                    C.c_void_p(rgb.data_ptr()) if rgb is not None else None, *rq.args(),
-                                                    _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
+            smooth=smooth, planes=planes, opts=opts)
+        entry, parts = (self._lib.md_infer_points_planes, rq.planes_args()) if rq.pln is not None else (self._lib.md_infer_points_smooth, rq.args())
+        _lib.check(entry(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
+                         C.c_void_p(rgb.data_ptr()) if rgb is not None else None, *parts, _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
         return rq.cloud
 
     # ---- debug taps / timing --------------------------------------------------------------

@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from .depth_pro import Device, _stream_ptr
-from .points import (PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _f32, _i32, _lattice, _points_cameras, _points_request, _ptr,
+from .points import (FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _f32, _i32, _lattice, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
                      _raster_request, _render_request, _u8, _view_filter_opts)
 
 
@@ -635,6 +635,34 @@ def radius_outliers(dev: Device, xyz: torch.Tensor, radius: float, min_neighbour
     outl = _lib.MdPointsOutlier(float(radius), int(min_neighbours), _ptr(out.neighbours), _ptr(out.index), _ptr(out.dropped))
     _lib.check(_lib.load().md_op_radius_outliers(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(outl), C.byref(outs),
                                                  _p(out.normals), _stream_ptr(dev.ordinal)))
+    return out
+
+
+def fit_planes(dev: Device, xyz: torch.Tensor, planes: int = 1, hypotheses: int = 256, tol: float = 0.0, min_inliers: int = 3, seed: int = 0,
+               normals: Optional[torch.Tensor] = None, normal_min_cos: float = 0.0, axis=(0.0, 0.0, 0.0), axis_min_cos: float = 0.0,
+               mode=0, conf: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None, out: Optional[PointCloud] = None,
+               capacity: Optional[int] = None) -> PointCloud:
+    """md_op_fit_planes: a point list xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) -> `PointCloud` whose `planes`
+    (`FittedPlanes`) holds up to `planes` RANSAC planes of `hypotheses` triples each (plane f32 [P,4], plane_count int32 [P+1],
+    hypothesis int32 [P]), label int32 [N] (the plane of every input row, -1 none, -2 not finite) and dropped int32 [1]. mode
+    "label" / 0: nothing else. "drop" / 1, "keep" / 2: also the rows without / of a plane in input order, xyz / conf / rgb /
+    normals [capacity, ..], index int32 [capacity] and count int32 [2]; capacity defaults to N. `out`: a PointCloud of an earlier
+    call to write into again. Bit-identical to `pipeline.fit_planes`."""
+    xyz, _, conf, rgb, normals, N, _ = _list_inputs(xyz, None, conf, rgb, normals)
+    opts = dict(planes=planes, hypotheses=hypotheses, tol=tol, min_inliers=min_inliers, seed=seed, normal_min_cos=normal_min_cos, axis=axis,
+                axis_min_cos=axis_min_cos, mode=mode)
+    cut = _plane_mode(opts) != 0
+    cap = N if capacity is None else int(capacity)
+    fresh = out is None
+    out, outs = _list_outputs(out, xyz.device, cap, conf, rgb, normals, vertex=cut)
+    if fresh:
+        P = max(int(planes), 0)
+        out.planes = FittedPlanes(plane=_f32(xyz.device, P, 4), plane_count=_i32(xyz.device, P + 1), hypothesis=_i32(xyz.device, P),
+                                  label=_i32(xyz.device, N), dropped=_i32(xyz.device, 1))
+    assert out.planes is not None and (out.planes.label is None or int(out.planes.label.shape[0]) >= N), "label covers the input rows"
+    pln = _planes_struct(opts, out.planes, out.index)
+    _lib.check(_lib.load().md_op_fit_planes(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(pln), C.byref(outs),
+                                            _p(out.normals) if cut else None, _stream_ptr(dev.ordinal)))
     return out
 
 

@@ -879,6 +879,123 @@ def radius_outliers(xyz, radius, min_neighbours, conf=None, rgb=None, normals=No
 
 
 @dataclass
+class HostPlanes:
+    plane: np.ndarray                # f32 [P,4]: n.x n.y n.z d of every plane found, zero rows behind them
+    plane_count: np.ndarray          # int32 [P+1]: the inliers of every plane, then the planes found
+    hypothesis: np.ndarray           # int32 [P]: the winning hypothesis, -1 behind the planes found
+    label: np.ndarray                # int32 [N] over the input rows: the plane, -1 none, -2 a coordinate that is not finite
+    dropped: int                     # rows with a coordinate that is not finite
+    xyz: Optional[np.ndarray]        # mode 1 / 2: f32 [M,3] the rows without / of a plane, in ascending input row; None with mode 0
+    conf: Optional[np.ndarray]       # f32 [M]
+    rgb: Optional[np.ndarray]        # uint8 [M,3]
+    normals: Optional[np.ndarray]    # f32 [M,3]
+    index: Optional[np.ndarray]      # int32 [M]: the source row
+    count: Optional[np.ndarray]      # int32 [B+1]: survivors per view, then their total
+
+
+def _plane_of_rows(p0, p1, p2, axis, axis_min_cos):
+    """The plane through three rows (f32 [3] each) -> f32 [4] n.x n.y n.z d, or None for an invalid triple (kernels/planes_math.h:
+    plane_of_rows, line by line; every operation is one f32 operation)."""
+    T = np.float32
+    with np.errstate(all="ignore"):
+        e1, e2 = p1 - p0, p2 - p0
+        nx = e1[1] * e2[2] - e1[2] * e2[1]
+        ny = e1[2] * e2[0] - e1[0] * e2[2]
+        nz = e1[0] * e2[1] - e1[1] * e2[0]
+        len2 = (nx * nx + ny * ny) + nz * nz
+        if not (np.isfinite(len2) and len2 > T(1e-30)):
+            return None
+        s = np.sqrt(len2)
+        nx, ny, nz = nx / s, ny / s, nz / s
+        d = -((nx * p0[0] + ny * p0[1]) + nz * p0[2])
+        flip = d < 0
+        if d == 0:  # either zero: the first non-zero component of n decides
+            first = nx if nx != 0 else (ny if ny != 0 else nz)
+            flip = first < 0
+        if flip:
+            nx, ny, nz, d = -nx, -ny, -nz, -d
+        if axis_min_cos > 0 and not np.abs((nx * axis[0] + ny * axis[1]) + nz * axis[2]) >= axis_min_cos:
+            return None
+    return np.array([nx, ny, nz, d], np.float32)
+
+
+def fit_planes(xyz, planes=1, hypotheses=256, tol=0.0, min_inliers=3, seed=0, normals=None, normal_min_cos=0.0, axis=(0.0, 0.0, 0.0),
+               axis_min_cos=0.0, mode=0, conf=None, rgb=None, counts=None) -> HostPlanes:
+    """The host reference of md_op_fit_planes / md_infer_points_planes (include/mi_depth.h states the contract): `planes` rounds of
+    RANSAC over the live rows of xyz f32 [N,3]. A round draws `hypotheses` triples from the live index with splitmix64's finaliser
+    (`_smooth_mix64`), builds every triple's plane in f32, one rounded operation per step, counts the live rows within `tol` of it
+    (and, with normal_min_cos > 0, with a normal within that cosine of the plane's), and the largest count, ties to the smallest
+    hypothesis, takes its inliers out of the live set when it reaches min_inliers; a round that fails ends the call. Vectorised
+    over the rows, one hypothesis at a time: the device kernels (kernels/planes.hip) give the same bits. mode 0 / "label": the
+    labels only; 1 / "drop", 2 / "keep": also the rows without / of a plane, every given row copied unchanged. counts: the rows of
+    every view of the input, [B] (default: one view)."""
+    T = np.float32
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    N = len(p)
+    P, Hh, k = int(planes), int(hypotheses), int(min_inliers)
+    mode = {"label": 0, "drop": 1, "keep": 2}.get(mode, mode)
+    tol, ncos, acos = T(tol), T(normal_min_cos), T(axis_min_cos)
+    a = np.asarray(axis, np.float32).reshape(3)
+    if not 1 <= P <= 8 or not 1 <= Hh <= 4096 or k < 3 or mode not in (0, 1, 2):
+        raise ValueError("planes in 1..8, hypotheses in 1..4096, min_inliers >= 3, mode 0, 1 or 2")
+    if not np.isfinite(tol) or not tol > 0 or not 0 <= ncos <= 1 or not 0 <= acos <= 1:
+        raise ValueError("tol finite and > 0, normal_min_cos and axis_min_cos in [0, 1]")
+    if ncos > 0 and normals is None:
+        raise ValueError("normal_min_cos > 0 needs normals")
+    if acos > 0 and not np.isfinite(a).all():
+        raise ValueError("axis_min_cos > 0 needs a finite axis")
+    if N >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows")
+    m = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(N, 3)
+    ok = np.isfinite(p).all(1)
+    label = np.where(ok, -1, -2).astype(np.int32)
+    plane, plane_count, hypothesis = np.zeros((P, 4), np.float32), np.zeros(P + 1, np.int32), np.full(P, -1, np.int32)
+    for r in range(P):
+        live = np.nonzero(label == -1)[0]
+        M = len(live)
+        if M < 3:
+            break
+        word = (np.uint64(int(seed) & 0xFFFFFFFF) << np.uint64(32)) | (np.uint64(r) << np.uint64(28))
+        h3 = (np.arange(Hh, dtype=np.uint64)[:, None] << np.uint64(2)) | np.arange(3, dtype=np.uint64)[None, :]
+        pick = live[(_smooth_mix64(word | h3) % np.uint64(M)).astype(np.int64)]  # [Hh,3] rows
+        q = p[live]
+        qm = m[live] if ncos > 0 else None
+        best, best_h, best_w, best_in = 0, -1, None, None
+        for h in range(Hh):
+            i0, i1, i2 = (int(v) for v in pick[h])
+            if i0 == i1 or i0 == i2 or i1 == i2:
+                continue
+            w = _plane_of_rows(p[i0], p[i1], p[i2], a, acos)
+            if w is None:
+                continue
+            with np.errstate(all="ignore"):
+                inl = np.abs(((w[0] * q[:, 0] + w[1] * q[:, 1]) + w[2] * q[:, 2]) + w[3]) <= tol
+                if ncos > 0:
+                    inl &= np.abs((w[0] * qm[:, 0] + w[1] * qm[:, 1]) + w[2] * qm[:, 2]) >= ncos
+            c = int(inl.sum())
+            if c > best:  # ties: the smallest h stays
+                best, best_h, best_w, best_in = c, h, w, inl
+        if best < k:
+            break
+        plane[r], plane_count[r], hypothesis[r] = best_w, best, best_h
+        plane_count[P] = r + 1
+        label[live[best_in]] = r
+    dropped = int(N - ok.sum())
+    if mode == 0:
+        return HostPlanes(plane, plane_count, hypothesis, label, dropped, None, None, None, None, None, None)
+    index = np.nonzero(label == -1 if mode == 1 else label >= 0)[0].astype(np.int32)
+    if counts is None:
+        bounds = np.array([0, N], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64).reshape(-1))]), N)
+    per_view = np.diff(np.searchsorted(index, bounds, side="left"))
+    count = np.concatenate([per_view, [len(index)]]).astype(np.int32)
+    take = lambda v, dt, shape: None if v is None else np.ascontiguousarray(v, dtype=dt).reshape(shape)[index]  # noqa: E731
+    return HostPlanes(plane, plane_count, hypothesis, label, dropped, p[index], take(conf, np.float32, (N,)), take(rgb, np.uint8, (N, 3)),
+                      take(normals, np.float32, (N, 3)), index, count)
+
+
+@dataclass
 class HostRender:
     depth: np.ndarray                # f32 [T,H,W]: the winner's p.z, 0 at holes
     index: np.ndarray                # int32 [T,H,W]: the winner's row, -1 at holes
@@ -1143,9 +1260,10 @@ def render_mesh(xyz, faces, H, W, intrinsics=None, extrinsics=None, focal_px=Non
 
 
 def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, normals: Optional[np.ndarray] = None,
-              faces: Optional[np.ndarray] = None) -> None:
-    """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar; with `faces` int [F,3]
-    an `element face` of `uchar int` vertex_indices lists behind the vertices (faces=None: the file without it)."""
+              faces: Optional[np.ndarray] = None, label: Optional[np.ndarray] = None) -> None:
+    """Binary little-endian PLY: `x y z` float, optional `nx ny nz` float, optional `red green blue` uchar, optional `label` int
+    (the plane of every point, `fit_planes`; label=None: the file without it); with `faces` int [F,3] an `element face` of
+    `uchar int` vertex_indices lists behind the vertices (faces=None: the file without it)."""
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     if normals is not None:
@@ -1158,6 +1276,11 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, norm
         if len(rgb) != len(xyz):
             raise ValueError(f"{len(rgb)} colours for {len(xyz)} points")
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if label is not None:
+        label = np.ascontiguousarray(label, dtype="<i4").reshape(-1)
+        if len(label) != len(xyz):
+            raise ValueError(f"{len(label)} labels for {len(xyz)} points")
+        fields += [("label", "<i4")]
     rec = np.empty(len(xyz), dtype=np.dtype(fields))
     for i, n in enumerate("xyz"):
         rec[n] = xyz[:, i]
@@ -1166,8 +1289,11 @@ def write_ply(path: str, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, norm
     if rgb is not None:
         for i, n in enumerate(("red", "green", "blue")):
             rec[n] = rgb[:, i]
+    if label is not None:
+        rec["label"] = label
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(xyz)}"]
-    head += [f"property {'float' if t == '<f4' else 'uchar'} {n}" for n, t in fields]
+    names = {"<f4": "float", "u1": "uchar", "<i4": "int"}
+    head += [f"property {names[t]} {n}" for n, t in fields]
     tail = b""
     if faces is not None:
         faces = np.asarray(faces).reshape(-1, 3)
@@ -1191,6 +1317,21 @@ def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     return xyz, rgb
 
 
+def _ply_vertex_fields(lines):
+    kinds = {"float": "<f4", "uchar": "u1", "int": "<i4"}
+    return [(l.split()[2], kinds[l.split()[1]]) for l in lines if l.startswith("property") and l.split()[1] != "list"]
+
+
+def read_ply_label(path: str) -> Optional[np.ndarray]:
+    """The `label` column of a file `write_ply(label=)` produced -> int32 [N], or None when the file has none."""
+    b = open(path, "rb").read()
+    end = b.index(b"end_header\n") + len(b"end_header\n")
+    lines = b[:end].decode("ascii").split("\n")
+    n = int(next(l for l in lines if l.startswith("element vertex")).split()[2])
+    rec = np.frombuffer(b, dtype=np.dtype(_ply_vertex_fields(lines)), count=n, offset=end)
+    return rec["label"].astype(np.int32) if "label" in rec.dtype.names else None
+
+
 def read_ply_normals(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
     """`read_ply` with the normals -> (xyz f32 [N,3], rgb uint8 [N,3] or None, normals f32 [N,3] or None)."""
     b = open(path, "rb").read()
@@ -1198,8 +1339,7 @@ def read_ply_normals(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], Optio
     lines = b[:end].decode("ascii").split("\n")
     assert lines[0] == "ply" and lines[1] == "format binary_little_endian 1.0"
     n = int(next(l for l in lines if l.startswith("element vertex")).split()[2])
-    fields = [(l.split()[2], "<f4" if l.split()[1] == "float" else "u1") for l in lines if l.startswith("property") and l.split()[1] != "list"]
-    rec = np.frombuffer(b, dtype=np.dtype(fields), count=n, offset=end)
+    rec = np.frombuffer(b, dtype=np.dtype(_ply_vertex_fields(lines)), count=n, offset=end)
     xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float32)
     rgb = np.stack([rec["red"], rec["green"], rec["blue"]], axis=-1) if "red" in rec.dtype.names else None
     nrm = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=-1).astype(np.float32) if "nx" in rec.dtype.names else None
@@ -1217,7 +1357,7 @@ def read_ply_faces(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], Optiona
     if not face:
         return xyz, rgb, nrm, None
     assert "property list uchar int vertex_indices" in lines
-    size = {"float": 4, "uchar": 1}
+    size = {"float": 4, "uchar": 1, "int": 4}
     vertex_bytes = sum(size[l.split()[1]] for l in lines if l.startswith("property") and l.split()[1] != "list") * len(xyz)
     frec = np.frombuffer(b, dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]), count=int(face[0].split()[2]), offset=end + vertex_bytes)
     assert (frec["n"] == 3).all()
@@ -1281,7 +1421,7 @@ class AnyDepthModel:
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
         render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`), outlier=
         (`md_infer_points_outlier`), decimate= (`md_infer_points_decimate`), components= (`md_infer_points_components`) and
-        smooth= (`md_infer_points_smooth`) included."""
+        smooth= (`md_infer_points_smooth`) and planes= (`md_infer_points_planes`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

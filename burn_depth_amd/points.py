@@ -50,6 +50,19 @@ class SmoothedMesh:
 
 
 @dataclass
+class FittedPlanes:
+    """What `md_op_fit_planes` / `md_infer_points_planes` return (include/mi_depth.h). Device tensors: plane f32 [P,4] (n.x n.y n.z d
+    of every plane found, the normal facing the origin, zero rows behind them), plane_count int32 [P+1] (the inliers of every
+    plane, then the planes found), hypothesis int32 [P] (the winning hypothesis, -1 behind the planes found), label int32 [rows
+    of the input list] (the plane of every row, -1 none, -2 a coordinate that is not finite), dropped int32 [1]."""
+    plane: Optional[torch.Tensor] = None
+    plane_count: Optional[torch.Tensor] = None
+    hypothesis: Optional[torch.Tensor] = None
+    label: Optional[torch.Tensor] = None
+    dropped: Optional[torch.Tensor] = None
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -73,7 +86,9 @@ class PointCloud:
     faces, faces / face_count the faces of the components that are large enough, face_index their source faces, component_stats
     int32 [5] the invalid, dropped and clipped faces and the components with a face and kept; with the operator's compact also
     index and remap. With `smooth=` (`md_infer_points_smooth`): smooth = the `SmoothedMesh` of the list over the faces the
-    rasteriser reads; the list itself is unchanged. None when not asked for."""
+    rasteriser reads; the list itself is unchanged. With `planes=` (`md_op_fit_planes` / `md_infer_points_planes`): planes = the
+    `FittedPlanes` of the list; with its mode "drop" / "keep" the list holds the rows without / of a plane and index is the
+    source row of every output row in the list in front of the stage. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -99,6 +114,7 @@ class PointCloud:
     component_faces: Optional[torch.Tensor] = None
     component_stats: Optional[torch.Tensor] = None
     smooth: Optional["SmoothedMesh"] = None
+    planes: Optional["FittedPlanes"] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -307,6 +323,54 @@ def _points_smooth(dev, smooth: dict, out: PointCloud, fresh: bool):
                                1 if smooth.get("pin_boundary", True) else 0, _ptr(s.xyz), _ptr(s.normals), _ptr(s.stats))
 
 
+PLANE_MODES = {"label": 0, "drop": 1, "keep": 2}
+_PLANE_KEYWORDS = {"planes", "hypotheses", "tol", "min_inliers", "seed", "normal_min_cos", "axis", "axis_min_cos", "mode"}
+
+
+def _planes_struct(planes: dict, fitted: "FittedPlanes", index: Optional[torch.Tensor]) -> "_lib.MdPointsPlanes":
+    """md_points_planes of the keywords planes= (P), hypotheses=, tol=, min_inliers=, seed=, normal_min_cos=, axis=, axis_min_cos=,
+    mode= ("label" / "drop" / "keep" or 0 / 1 / 2) writing into `fitted` and `index`. The ranges are the library's to refuse."""
+    unknown = set(planes) - _PLANE_KEYWORDS
+    if unknown or "tol" not in planes:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"planes= takes {sorted(_PLANE_KEYWORDS)} and needs tol; unknown {sorted(unknown)}")
+    mode = planes.get("mode", 0)
+    if isinstance(mode, str):
+        if mode not in PLANE_MODES:
+            raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"plane mode {mode!r}: one of {sorted(PLANE_MODES)}")
+        mode = PLANE_MODES[mode]
+    axis = [float(v) for v in planes.get("axis", (0.0, 0.0, 0.0))]
+    if len(axis) != 3:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "the plane axis has three components")
+    return _lib.MdPointsPlanes(int(planes.get("planes", 1)), int(planes.get("hypotheses", 256)), float(planes["tol"]),
+                               int(planes.get("min_inliers", 3)), int(planes.get("seed", 0)) & 0xFFFFFFFF,
+                               float(planes.get("normal_min_cos", 0.0)), (C.c_float * 3)(*axis), float(planes.get("axis_min_cos", 0.0)),
+                               int(mode), _ptr(fitted.plane), _ptr(fitted.plane_count), _ptr(fitted.hypothesis), _ptr(fitted.label),
+                               _ptr(index) if mode else None, _ptr(fitted.dropped))
+
+
+def _plane_mode(planes: Optional[dict]) -> int:
+    """0 label, 1 drop, 2 keep; 0 also for a request that is off or whose mode the builder will refuse."""
+    mode = (planes or {}).get("mode", 0) if planes and planes.get("planes", 1) else 0
+    return PLANE_MODES.get(mode, 0) if isinstance(mode, str) else int(mode)
+
+
+def _points_planes(dev, rows: int, planes: dict, out: PointCloud, fresh: bool):
+    """md_points_planes for `out` with the stage on. rows: the rows the list in front of the stage can have. With `fresh` the
+    tensors of `out.planes` are created, label over the rows of the list the stage reads (the list of the call, or with mode
+    "drop" / "keep" the one in front of it) and, with those modes, index beside the list; otherwise the ones `out` carries are
+    written again."""
+    if out.xyz is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "planes= needs the compacted list")
+    cut = _plane_mode(planes) != 0
+    if fresh or out.planes is None:
+        P, cap = max(int(planes.get("planes", 1)), 0), int(out.xyz.shape[0])
+        out.planes = FittedPlanes(plane=_f32(dev, P, 4), plane_count=_i32(dev, P + 1), hypothesis=_i32(dev, P),
+                                  label=_i32(dev, rows if cut else cap), dropped=_i32(dev, 1))
+        if cut:
+            out.index = _i32(dev, cap)
+    return _planes_struct(planes, out.planes, out.index)
+
+
 def _target_cameras(dev, intrinsics, extrinsics, focal_px):
     """The target cameras of a rendering or a rasterisation -> (T, md_points_cameras, keep-alive). T is the number of cameras given."""
     src = intrinsics if intrinsics is not None else focal_px
@@ -358,10 +422,15 @@ class PointsRequest(NamedTuple):
     comp: Optional["_lib.MdPointsComponents"]
     smo: Optional["_lib.MdPointsSmooth"]
     keep: list
+    pln: Optional["_lib.MdPointsPlanes"] = None  # behind `keep`: `md_infer_points_planes` takes it behind `args()`
 
     def args(self) -> list:
         """The struct arguments of `md_infer_points_smooth`, by reference, NULL for the parts not asked for."""
-        return [C.byref(s) if s is not None else None for s in self[1:-1]]
+        return [C.byref(s) if s is not None else None for s in self[1:14]]
+
+    def planes_args(self) -> list:
+        """The struct arguments of `md_infer_points_planes`: those of `args()`, then the plane part."""
+        return self.args() + [C.byref(self.pln) if self.pln is not None else None]
 
 
 def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: bool, want_depth: bool, intrinsics=None, extrinsics=None,
@@ -369,7 +438,8 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
                     out: Optional[PointCloud] = None, conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0,
                     normals: bool = False, normal_min_cos: float = 0.0, voxel: Optional[float] = None, render: Optional[dict] = None,
                     mesh=None, raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
-                    components: Optional[dict] = None, smooth: Optional[dict] = None, opts: Optional[dict] = None) -> PointsRequest:
+                    components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None,
+                    opts: Optional[dict] = None) -> PointsRequest:
     """The keyword set of `infer_points` / `ops.unproject` (their docstrings say what each means) as a `PointsRequest`. opts: the
     fields of `md_points_opts`; want_rgb / want_conf / want_depth: the call can fill those outputs. A part is None when it was
     not asked for, by keyword or by an `out` that carries its tensors; fresh tensors are allocated unless `out` is given.
@@ -383,7 +453,8 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     o = _points_opts(**(opts or {}))
     res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
     cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
-    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = None
+    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = None
+    cut = _plane_mode(planes) != 0  # the plane stage writes the list: index is its own, an earlier stage's is not returned
     if conf_percentile or view_rtol or min_views:
         fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
     if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
@@ -393,6 +464,9 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     filt = bool(outlier) and bool(outlier.get("radius"))
     if voxel is not None and (voxel or (not deci and not filt and (res.index is not None or res.weight is not None or res.dropped is not None))):
         vox = _points_voxel(dev, voxel, res, fresh)
+        if cut:
+            vox.index = vox.weight = None
+            res.weight = None
     if render is not None:
         T, tcam, ro, res.render, routs, tkeep = _render_request(dev, **render, want_rgb=res.rgb is not None, out=res.render)
         rnd = _lib.MdPointsRender(T, int(render["H"]), int(render["W"]), tcam, ro, routs)
@@ -406,7 +480,7 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
         rst = _lib.MdPointsRaster(T, int(raster["H"]), int(raster["W"]), tcam, so, souts)
         keep = keep + tkeep
     if outlier is not None:
-        outl = _points_outlier(dev, _lattice(B, H, W, o.stride)[1], outlier, bool(voxel), res, fresh)
+        outl = _points_outlier(dev, _lattice(B, H, W, o.stride)[1], outlier, bool(voxel) or cut, res, fresh)
     if isl:
         if not mesh:
             raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "components= needs mesh=")
@@ -425,4 +499,8 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
         smo = _points_smooth(dev, smooth, res, fresh)
     elif smooth is not None:
         smo = _lib.MdPointsSmooth()
-    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep)
+    if planes and planes.get("planes", 1):
+        pln = _points_planes(dev, _lattice(B, H, W, o.stride)[1], planes, res, fresh)
+    elif planes is not None:
+        pln = _lib.MdPointsPlanes()
+    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln)

@@ -961,6 +961,88 @@ int md_infer_points_smooth(md_model_t m, const float* nchw, int B, int H, int W,
                            const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
                            const md_points_components* comp, const md_points_smooth* smooth, int out_kind, void* stream);
 
+/* ---- point path: RANSAC plane extraction from a point list ---------------------------------------------------------------------
+ * A list xyz f32 [N,3] with optional parallel rows conf f32 [N], rgb u8 [N,3] and normals f32 [N,3] -> up to P = `planes` planes
+ * (1..8), the label of every row, and with mode 1 / 2 the list without / of the plane rows. The decision is an integer inlier
+ * count of a deterministic f32 predicate and the winner an arg-max with a fixed tie rule, so nothing depends on the order in
+ * which threads arrive. f32, one rounded operation per step, no fused multiply-add, in exactly the order written (sqrtf and /
+ * are the correctly rounded ones); pipeline.fit_planes restates it in numpy bit for bit. Denormals are outside the contract.
+ *   live rows: a row with a coordinate that is not finite is dropped: label -2, counted in `dropped`. Before round 0 every other
+ *     row is live (label -1). Rows at and beyond the device count of the list are not rows.
+ *   round p = 0 .. P-1:
+ *   1 live index: the live rows in ascending row order are live[0 .. M_p). M_p < 3: the round fails.
+ *   2 sampling: hypothesis h = 0 .. Hh-1 (Hh = `hypotheses`, 1..4096) draws corner j = 0, 1, 2 as row live[mix64(x) mod M_p],
+ *     x = (u64)seed << 32 | (u64)p << 28 | (u64)h << 2 | j, the modulo unsigned 64-bit, mix64 splitmix64's finaliser
+ *     (x ^= x >> 30, x *= 0xbf58476d1ce4e5b9, x ^= x >> 27, x *= 0x94d049bb133111eb, x ^= x >> 31). Two equal rows among the
+ *     three make the hypothesis invalid.
+ *   3 plane: e1 = p1 - p0, e2 = p2 - p0; n.x = e1.y*e2.z - e1.z*e2.y, n.y = e1.z*e2.x - e1.x*e2.z, n.z = e1.x*e2.y - e1.y*e2.x
+ *     (two products, one subtraction each); len2 = (n.x*n.x + n.y*n.y) + n.z*n.z; invalid unless len2 is finite and > 1e-30f;
+ *     s = sqrtf(len2), n = n / s (three divisions); d = -((n.x*p0.x + n.y*p0.y) + n.z*p0.z). Orientation: d < 0 negates n and d;
+ *     d == 0 (either zero) negates both when the first non-zero component of n is negative: the normal faces the origin, the
+ *     camera of a single view. With axis_min_cos > 0 the hypothesis is invalid unless
+ *     fabsf((n.x*a.x + n.y*a.y) + n.z*a.z) >= axis_min_cos; the axis is used as given, not normalised.
+ *   4 inliers: live row q is an inlier of a valid hypothesis when fabsf(((n.x*q.x + n.y*q.y) + n.z*q.z) + d) <= tol (inclusive)
+ *     and, with normal_min_cos > 0, fabsf((n.x*m.x + n.y*m.y) + n.z*m.z) >= normal_min_cos for its normal m (an all-zero normal
+ *     fails). count[h] = the inliers, 0 for an invalid hypothesis. The winner is the largest count, among equal counts the
+ *     smallest h. The round succeeds when that count >= min_inliers (>= 3).
+ *   5 outcome: success: plane[p] = (n, d) of the winner, hypothesis[p] = h, plane_count[p] = count; its inliers get label p and
+ *     leave the live set. Failure: this and every later round write nothing: plane[p..] = 0, hypothesis = -1, plane_count = 0.
+ *     All P rounds are enqueued regardless (a round behind a failed one finds a device flag set), so the launch sequence is
+ *     static. plane_count[P] = the planes found.
+ *   mode 0: labels only. mode 1 keeps the rows with label -1, mode 2 the rows with label >= 0: the survivors in ascending input
+ *     row, every given row copied unchanged, index = the source row; count[b] = the survivors of view b, count[B] = their total
+ *     M, also when M exceeds `capacity`: then only the first `capacity` rows are written and the memory behind them stays
+ *     untouched. All views of a call share the planes.
+ *   The plane is the winning hypothesis's: there is no least-squares refit (it would need float sums in a fixed order). */
+typedef struct md_points_planes {
+  int32_t planes;       /* P, 1..8; 0 = the stage is off (md_infer_points_planes) */
+  int32_t hypotheses;   /* Hh per plane, 1..4096 */
+  float tol;            /* finite and > 0 */
+  int32_t min_inliers;  /* >= 3 */
+  uint32_t seed;
+  float normal_min_cos; /* in [0, 1]; 0 = normals not used, > 0 needs normals */
+  float axis[3];        /* finite when axis_min_cos > 0 */
+  float axis_min_cos;   /* in [0, 1]; 0 = no axis constraint */
+  int32_t mode;         /* 0 = label only, 1 = drop the plane rows, 2 = keep only the plane rows */
+  float* plane;         /* float [P,4]: n.x n.y n.z d. NULL = skip */
+  int32_t* plane_count; /* int32 [P+1]: the inliers of every plane, then the planes found. NULL = skip */
+  int32_t* hypothesis;  /* int32 [P]: the winning h, -1 for a round that did not succeed. NULL = skip */
+  int32_t* label;       /* int32 [N] over the INPUT rows: the plane, -1 none, -2 dropped. NULL = skip */
+  int32_t* index;       /* int32 [capacity], mode 1 / 2: the source row of every output row; needs count. NULL = skip */
+  int32_t* dropped;     /* int32 [1]: rows with a coordinate that is not finite. NULL = skip */
+} md_points_planes;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_radius_outliers: the N rows are one view. Of `out` the
+ * fields xyz, rgb, conf, count (int32 [2]: M twice) and capacity are used, with mode 1 / 2 only; the others must be NULL;
+ * normals_out [capacity,3] takes the normals rows. Everything is enqueued on `stream`; the call returns after the stream has
+ * drained, because its scratch is freed on return. Errors, before any launch: dev / pln / out NULL, xyz_dev NULL with N > 0, an
+ * option outside its range (planes 0 included), normal_min_cos > 0 without normals_dev, axis_min_cos > 0 with an axis that is not
+ * finite, N < 0, capacity < 0, a compacted output (xyz, rgb, conf, normals_out, index) without count or with mode 0, an rgb /
+ * conf / normals output without that input row, a dense output or out->depth set -> MD_ERR_INVALID_ARG; N >= 2^30 -> MD_ERR_SHAPE. */
+int md_op_fit_planes(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                     int64_t N, const md_points_planes* pln, const md_points_outputs* out, float* normals_out, void* stream);
+/* md_infer_points_smooth with the plane extraction behind every other list and mesh stage and in front of the point render and the
+ * rasteriser (launch-order name "points_planes"). It reads the list the mesh stages read, behind view filter, outlier removal
+ * and thinning; the normals predicate reads nrm's list normals (normal_min_cos > 0 needs nrm->normals). mode 0: the caller's
+ * list is unchanged and pln->label is int32 over its rows, [out->capacity], of which the first min(count[B], capacity) are
+ * written. mode 1 / 2: the stage writes the caller's list and out->count (the stage before it then fills a grow-only list of the
+ * model), pln->label is int32 over the rows of that input list (at most B ceil(H/stride) ceil(W/stride)) and pln->index names
+ * its rows; the point render sees the list the call ends with. pln's pointers are of out_kind. The scratch comes from grow-only
+ * buffers of the model: after the first call of a shape nothing is allocated. pln NULL or planes == 0 (its pointers then NULL):
+ * md_infer_points_smooth on the same arguments, the same launches and bits. The graph key contains pln's fields. Errors as
+ * md_infer_points_smooth's, plus, before any launch: an option outside its range, normal_min_cos > 0 without the list normals,
+ * axis_min_cos > 0 with an axis that is not finite, the stage without the list's count, index without mode 1 / 2, any of pln's
+ * pointers with planes == 0, mode 1 / 2 together with a mesh, decimation, components or smoothing (the rows the faces name would
+ * vanish) or with voxel thinning's or the outlier removal's index (the rows they are parallel to are not returned), mode 0
+ * together with decimation -> MD_ERR_INVALID_ARG; a list of >= 2^30 rows -> MD_ERR_SHAPE. */
+int md_infer_points_planes(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                           const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                           const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                           const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                           const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                           const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
+                           int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

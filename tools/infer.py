@@ -50,6 +50,12 @@ is written `ops.mesh_components(compact=True)` drops the vertices that only they
 `--raster-pose` / `--render-pose` stay those of the model call, over its uncompacted list. With `--views`
 the operator runs behind the per-view meshes, and behind `ops.decimate_mesh` when `--decimate` is given.
 
+`--planes P [--plane-tol T] [--plane-hypotheses H] [--plane-min-inliers K] [--plane-seed S] [--plane-mode label|drop|keep]
+[--plane-up X Y Z --plane-up-cos C]` (with `--ply`): RANSAC extraction of up to P planes from the cloud on the device; the plane equations
+n.x n.y n.z d and their inlier counts are printed. `label` writes the plane of every point as the int property `label` of the file (-1 none),
+`drop` / `keep` write the cloud without / of the plane points (not with `--mesh`). `--plane-up` keeps only planes whose normal lies within
+the cosine C of that axis (the floor with the up axis). One image without `--mesh`: the stage runs inside the model call
+(`md_infer_points_planes`); with `--views` or `--mesh`, `ops.fit_planes` runs on the final points. T defaults to 1 % of the cloud's extent.
 `--smooth ITER [--smooth-step S] [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]` (with `--ply --mesh`): Taubin smoothing
 of the mesh on the device, ITER lambda | mu step pairs (`--smooth-mu 0`: ITER Laplacian steps) on an integer lattice of side S, the open
 boundary pinned unless freed. The file holds the smoothed positions and, with `--normals`, the vertex normals of the smoothed faces. One
@@ -116,6 +122,24 @@ def smooth_step(a, xyz) -> float:
     v = v[torch.isfinite(v)]
     top = float(v.max().item()) if v.numel() else 0.0
     return float(np.float32(top / 2097152.0)) if top > 0 else 1.0
+
+
+def planes_request(a, xyz) -> dict:
+    """the planes= keywords of --planes; without --plane-tol the tolerance is 1 % of the largest finite extent of the list"""
+    tol = a.plane_tol
+    if not tol > 0:
+        fin = xyz[xyz.isfinite().all(1)]
+        tol = 0.01 * float((fin.max(0).values - fin.min(0).values).max()) if len(fin) else 1.0
+    up = dict(axis=tuple(a.plane_up), axis_min_cos=a.plane_up_cos) if a.plane_up else {}
+    return dict(planes=a.planes, hypotheses=a.plane_hypotheses, tol=tol, min_inliers=a.plane_min_inliers, seed=a.plane_seed, mode=a.plane_mode, **up)
+
+
+def print_planes(fitted) -> None:
+    found = int(fitted.plane_count[-1])
+    for i, (w, c) in enumerate(zip(fitted.plane[:found].cpu().tolist(), fitted.plane_count[:found].cpu().tolist())):
+        print(f"Plane {i}: {w[0]:+.6f} x {w[1]:+.6f} y {w[2]:+.6f} z {w[3]:+.6f} = 0  ({c} inliers)")
+    if not found:
+        print("No plane found")
 
 
 def smooth_request(a, step: float) -> dict:
@@ -216,7 +240,21 @@ def run_views(a) -> int:
                 return 1
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces)
+        label = None
+        if a.planes > 0:  # on the points of the file
+            try:
+                pc = ops.fit_planes(dev, xyz, **planes_request(a, xyz), rgb=col, normals=nrm)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            print_planes(pc.planes)
+            if a.plane_mode == "label":
+                label = pc.planes.label.cpu().numpy()
+                pc.xyz, pc.rgb, pc.count = xyz, col, torch.tensor([xyz.shape[0]], dtype=torch.int32, device=xyz.device)  # what --render-pose draws
+            else:
+                xyz, col, _ = pc.points()
+                nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces, label=label)
         print(f"Model `{a.model}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} of {len(imgs)} views to {a.ply}")
         if a.render_pose:
             req, why = render_request(a, preps[0].height, preps[0].width, K=K[0].cpu().numpy())
@@ -290,6 +328,15 @@ def main(argv=None) -> int:
     ap.add_argument("--smooth-lambda", type=float, default=0.5, help="--smooth: the factor of the shrinking steps, in (0, 1]")
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="--smooth: the factor of the inflating steps, in [-1, 0]; 0 = Laplacian smoothing")
     ap.add_argument("--smooth-free-boundary", action="store_true", help="--smooth: let the open boundary of the mesh move too")
+    ap.add_argument("--planes", type=int, default=0, help="--ply: extract up to this many planes (1..8) from the cloud (md_infer_points_planes, ops.fit_planes; 0 = off)")
+    ap.add_argument("--plane-tol", type=float, default=0.0, help="--planes: the inlier distance (0 = 1 %% of the cloud's extent)")
+    ap.add_argument("--plane-hypotheses", type=int, default=1024, help="--planes: three-point hypotheses per plane, 1..4096")
+    ap.add_argument("--plane-min-inliers", type=int, default=100, help="--planes: the inliers a plane needs, at least 3")
+    ap.add_argument("--plane-seed", type=int, default=0, help="--planes: the seed of the samples")
+    ap.add_argument("--plane-mode", choices=["label", "drop", "keep"], default="label",
+                    help="--planes: write the plane of every point as the PLY property `label`, or the cloud without / of the plane points")
+    ap.add_argument("--plane-up", type=float, nargs=3, metavar=("X", "Y", "Z"), help="--planes: only planes whose normal lies within --plane-up-cos of this axis")
+    ap.add_argument("--plane-up-cos", type=float, default=0.9, help="--plane-up: the smallest |cosine| between a plane's normal and the axis")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
     ap.add_argument("--raster-out", default="", help="--raster-pose: the rasterised depth of the first pose as a normalised PNG")
     a = ap.parse_args(argv)
@@ -307,6 +354,9 @@ def main(argv=None) -> int:
         return 2
     if a.smooth != 0 and (not 1 <= a.smooth <= 1024 or not (a.ply and a.mesh)):
         print("--smooth is a step count in 1..1024 and goes with --ply --mesh", file=sys.stderr)
+        return 2
+    if a.planes != 0 and (not 1 <= a.planes <= 8 or not a.ply or (a.mesh and a.plane_mode != "label")):
+        print("--planes is a plane count in 1..8 and goes with --ply; --plane-mode drop / keep not with --mesh (the faces name the rows)", file=sys.stderr)
         return 2
     if a.outlier_radius != 0 and (not a.ply or a.mesh):
         print("--outlier-radius goes with --ply, and not with --mesh (the faces name rows of the unfiltered list)", file=sys.stderr)
@@ -376,6 +426,10 @@ def main(argv=None) -> int:
                                     decimate=dict(voxel=a.decimate) if a.decimate else None,
                                     components=dict(min_faces=a.min_component_faces) if a.min_component_faces and not a.decimate else None,
                                     smooth=smooth)
+            planes_in_call = bool(a.planes) and not a.mesh
+            if planes_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stage then runs inside the call
+                pc = model.infer_points(x, **call, voxel=a.voxel, render=render, planes=planes_request(a, pc.points()[0]),
+                                        outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None)
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
             if in_call:
@@ -390,11 +444,17 @@ def main(argv=None) -> int:
             if a.smooth and not in_call:  # behind the decimation / the compaction: the operator on the vertices and faces of the file
                 sm = ops.smooth_mesh(Device(0), xyz, flt.faces[:int(flt.face_count[-1])], **smooth_request(a, smooth_step(a, xyz)))
                 xyz, nrm = sm.xyz, sm.normals
+            label = None
+            if a.planes:  # beside a mesh: the operator labels the vertices of the file
+                fitted = pc.planes if planes_in_call else ops.fit_planes(Device(0), xyz, **planes_request(a, xyz)).planes
+                print_planes(fitted)
+                if a.plane_mode == "label":
+                    label = fitted.label[:xyz.shape[0]].cpu().numpy()
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
         faces = flt.faces[:int(flt.face_count[-1])].cpu().numpy() if a.mesh else None
-        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces)
+        P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces, label=label)
         print(f"Model `{kind.value}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} to {a.ply}")
         if render is not None:
             write_render(a, P, pc.render)
