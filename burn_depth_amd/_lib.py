@@ -200,6 +200,19 @@ class MdDecoderGemm(C.Structure):
                 ("head_act", C.c_int), ("Cmid", C.c_int), ("w2", C.c_void_p), ("bias2", C.c_void_p)]
 
 
+class MdCameraEncode(C.Structure):
+    """md_camera_encode (include/mi_depth.h)."""
+    _fields_ = [("B", C.c_int), ("V", C.c_int), ("D", C.c_int), ("heads", C.c_int), ("depth", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("eps_tok", C.c_float), ("eps_blk", C.c_float), ("w", C.c_void_p * 8), ("blk", (C.c_void_p * 14) * 8), ("extr", C.c_void_p),
+                ("intr", C.c_void_p), ("out", C.c_void_p), ("pose_out", C.c_void_p)]
+
+
+class MdCameraDecode(C.Structure):
+    """md_camera_decode (include/mi_depth.h)."""
+    _fields_ = [("B", C.c_int), ("din", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cam", C.c_void_p), ("w", C.c_void_p * 10),
+                ("pose", C.c_void_p), ("extr", C.c_void_p), ("intr", C.c_void_p)]
+
+
 class MdNchwView(C.Structure):
     """md_nchw_view (include/mi_depth.h): one NCHW fp32 tensor with its shape."""
     _fields_ = [("data", C.c_void_p), ("channels", C.c_int), ("height", C.c_int), ("width", C.c_int)]
@@ -347,6 +360,9 @@ SYMBOLS = {
     "md_debug_gemm_last_form": (_I, [C.POINTER(_I * 8)]),
     "md_debug_gemm_last_launch": (_I, [C.POINTER(_I * 4)]),
     "md_op_decoder_gemm": (_I, [_P, C.POINTER(MdDecoderGemm), _P]),
+    "md_op_camera_encode": (_I, [_P, C.POINTER(MdCameraEncode), _P]),
+    "md_op_camera_decode": (_I, [_P, C.POINTER(MdCameraDecode), _P]),
+    "md_op_pose_to_camera": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "md_op_conv2d_direct_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "md_op_fov_to_focal": (_I, [C.c_float, _I, _I, _F, _F]),
     "md_op_focal_to_fov": (_I, [C.c_float, _I, _I, _F, _F]),

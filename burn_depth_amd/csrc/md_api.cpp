@@ -1600,6 +1600,82 @@ int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* d, void* stream) 
   return MD_OK;
 }
 
+// ---- the camera path alone ----
+namespace {
+// launcher scratch of the camera entries: allocated, not cleared (the kernels write every word they read), so that a call the launcher
+// refuses has started no device work
+struct RawBuf {
+  float* p = nullptr;
+  ~RawBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int alloc(size_t floats) {
+    if (hipMalloc((void**)&p, floats * 4 + 4096) != hipSuccess) {
+      set_error("hipMalloc(%zu) failed", floats * 4);
+      return MD_ERR_OOM;
+    }
+    return MD_OK;
+  }
+};
+}  // namespace
+
+int md_op_camera_encode(md_device_t dev, const md_camera_encode* d, void* stream) {
+  if (!dev || !d || !d->extr || !d->intr || !d->out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  const int B = d->B, V = d->V, D = d->D;
+  if (B <= 0 || D <= 0 || d->H <= 0 || d->W <= 0) MD_FAIL(MD_ERR_SHAPE, "camera_encode: B=%d D=%d image %dx%d", B, D, d->H, d->W);
+  CamEncW w{};
+  w.fc1_w = d->w[0]; w.fc1_b = d->w[1]; w.fc2_w = d->w[2]; w.fc2_b = d->w[3];
+  w.tn_g = d->w[4]; w.tn_b = d->w[5]; w.on_g = d->w[6]; w.on_b = d->w[7];
+  w.depth = d->depth;
+  for (int i = 0; i < 8; ++i)
+    if (!d->w[i]) MD_FAIL(MD_ERR_INVALID_ARG, "camera_encode: weight %d missing", i);
+  for (int i = 0; i < std::min(std::max(d->depth, 0), (int)CamEncW::kMaxDepth); ++i) {
+    const float* const* b = d->blk[i];
+    for (int j = 0; j < 14; ++j)
+      if (!b[j]) MD_FAIL(MD_ERR_INVALID_ARG, "camera_encode: block %d weight %d missing", i, j);
+    w.blk[i] = CamEncW::Blk{b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12], b[13]};
+  }
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  RawBuf scratch;
+  MD_TRY(scratch.alloc(V > 0 ? camera_encoder_scratch_floats(B, V, D) : 0));
+  MD_TRY(launch_camera_encoder(d->extr, d->intr, B, V, D, d->heads, d->H, d->W, d->eps_tok, d->eps_blk, w, scratch.p, d->out, st));
+  if (d->pose_out) {  // camera_encoder_kernel: per image `pose [V][12]` leads the scratch
+    const size_t per_image = camera_encoder_scratch_floats(1, V, D);
+    for (int b = 0; b < B; ++b)
+      MD_HIP(hipMemcpy2DAsync(d->pose_out + (size_t)b * V * 9, 9 * 4, scratch.p + b * per_image, 12 * 4, 9 * 4, V, hipMemcpyDeviceToDevice, st));
+  }
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_camera_decode(md_device_t dev, const md_camera_decode* d, void* stream) {
+  if (!dev || !d || !d->cam || !d->pose) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  for (int i = 0; i < 10; ++i)
+    if (!d->w[i]) MD_FAIL(MD_ERR_INVALID_ARG, "camera_decode: weight %d missing", i);
+  const int B = d->B, din = d->din;
+  if (din <= 0 || d->H <= 0 || d->W <= 0) MD_FAIL(MD_ERR_SHAPE, "camera_decode: din=%d image %dx%d", din, d->H, d->W);
+  const CamDecW w{d->w[0], d->w[1], d->w[2], d->w[3], d->w[4], d->w[5], d->w[6], d->w[7], d->w[8], d->w[9]};
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  RawBuf h;  // h1 | h2
+  const size_t n = B > 0 ? (size_t)B * din : 0;
+  MD_TRY(h.alloc(2 * n));
+  MD_TRY(launch_camera_decoder(d->cam, B, din, w, d->H, d->W, h.p, h.p + n, d->pose, d->extr, d->intr, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+int md_op_pose_to_camera(md_device_t dev, const float* pose, int B, int H, int W, float* extr, float* intr, void* stream) {
+  if (!dev || !pose) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (B <= 0 || H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "pose_to_camera: B=%d image %dx%d", B, H, W);
+  MD_HIP(hipSetDevice(dev->ordinal));
+  hipStream_t st = pick_stream(dev, stream);
+  MD_TRY(launch_pose_to_camera(pose, B, H, W, extr, intr, st));
+  MD_HIP(hipStreamSynchronize(st));
+  return MD_OK;
+}
+
 int md_debug_gemm_last_launch(int out[4]) {
   if (!out) return MD_ERR_INVALID_ARG;
   const LaunchNote n = gemm_last_launch();

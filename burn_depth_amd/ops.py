@@ -509,6 +509,53 @@ def decoder_gemm(dev: Device, kind: int, x: torch.Tensor, w, bias, precision: in
     _lib.check(_lib.load().md_op_decoder_gemm(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
 
 
+def _f32_dev(*tensors) -> None:
+    for t in tensors:
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32), "the camera entries take contiguous fp32 device tensors"
+
+
+def camera_encode(dev: Device, extr: torch.Tensor, intr: torch.Tensor, top, blocks, *, heads: int, H: int, W: int, eps_tok: float, eps_blk: float,
+                  out: torch.Tensor, pose_out: Optional[torch.Tensor] = None, V: Optional[int] = None, depth: Optional[int] = None) -> None:
+    """md_op_camera_encode: extr [B, V, 3, 4], intr [B, V, 3, 3] -> out [B, D] (+ pose_out [B, V, 9]), the CALLER's tensors, written in
+    place. top: the 8 tensors of md_camera_encode.w in its order; blocks: per trunk block the 14 tensors of md_camera_encode.blk.
+    V / depth: what the descriptor states when it is not what the tensors have (the refusal tests)."""
+    _f32_dev(extr, intr, out, pose_out, *top, *(t for b in blocks for t in b))
+    d = _lib.MdCameraEncode()
+    d.B, d.V, d.D, d.heads, d.depth = out.shape[0], (extr.shape[1] if V is None else V), out.shape[1], heads, (len(blocks) if depth is None else depth)
+    d.H, d.W, d.eps_tok, d.eps_blk = H, W, eps_tok, eps_blk
+    assert len(top) == 8 and len(blocks) <= 8 and all(len(b) == 14 for b in blocks)
+    for i, t in enumerate(top):
+        d.w[i] = t.data_ptr()
+    for i, b in enumerate(blocks):
+        for j, t in enumerate(b):
+            d.blk[i][j] = t.data_ptr()
+    d.extr, d.intr, d.out, d.pose_out = extr.data_ptr(), intr.data_ptr(), out.data_ptr(), (pose_out.data_ptr() if pose_out is not None else None)
+    _lib.check(_lib.load().md_op_camera_encode(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
+
+
+def camera_decode(dev: Device, cam: torch.Tensor, weights, H: int, W: int, pose: torch.Tensor, extr: Optional[torch.Tensor] = None,
+                  intr: Optional[torch.Tensor] = None, *, B: Optional[int] = None) -> None:
+    """md_op_camera_decode: cam [B, din] -> pose [B, 9] (+ extr [B, 12], intr [B, 9]), the CALLER's tensors, written in place. weights:
+    the 10 tensors of md_camera_decode.w in its order. B: what the descriptor states when it is not cam's row count (the refusal tests)."""
+    _f32_dev(cam, pose, extr, intr, *weights)
+    assert len(weights) == 10
+    d = _lib.MdCameraDecode()
+    d.B, d.din, d.H, d.W = (cam.shape[0] if B is None else B), cam.shape[1], H, W
+    for i, t in enumerate(weights):
+        d.w[i] = t.data_ptr()
+    d.cam, d.pose = cam.data_ptr(), pose.data_ptr()
+    d.extr, d.intr = (extr.data_ptr() if extr is not None else None), (intr.data_ptr() if intr is not None else None)
+    _lib.check(_lib.load().md_op_camera_decode(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
+
+
+def pose_to_camera(dev: Device, pose: torch.Tensor, H: int, W: int, extr: Optional[torch.Tensor] = None, intr: Optional[torch.Tensor] = None,
+                   *, B: Optional[int] = None) -> None:
+    """md_op_pose_to_camera: pose [B, 9] -> extr [B, 12] world-to-camera, intr [B, 9] (either may be None), written in place."""
+    _f32_dev(pose, extr, intr)
+    _lib.check(_lib.load().md_op_pose_to_camera(dev.handle, _p(pose), pose.shape[0] if B is None else B, H, W, _p(extr), _p(intr),
+                                                _stream_ptr(dev.ordinal)))
+
+
 def conv2d_direct_ex(dev: Device, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor], stride: int,
                      pad: int, relu: bool, in_precision: int, out_ld: int, out: torch.Tensor) -> torch.Tensor:
     """md_op_conv2d_direct_ex: x [B, Cin, H, W], w [Cout, Cin, k, k], add fp32 NHWC or None -> a copy of the pre-filled fp32

@@ -1435,6 +1435,34 @@ typedef struct md_decoder_gemm {
   const float* bias2;        /* HEAD_UP2: [32] */
 } md_decoder_gemm;
 int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* desc, void* stream);
+/* ---- the Depth-Anything-v3 camera path alone (test-only): the camera encoder, the camera decoder and the pose -> matrices tail as the
+ * engine launches them, on fp32 device tensors the CALLER owns. The entries allocate only the launchers' scratch, pre-fill nothing,
+ * launch and synchronise. What a launcher refuses (views outside 1..16, width % 8, width % heads, depth outside 0..8; decoder width % 4,
+ * batch < 1) returns with the launcher's code before any device work. ---- */
+typedef struct md_camera_encode {
+  int B, V, D, heads, depth; /* images, views per image (1..16), token width, attention heads, trunk blocks (0..8) */
+  int H, W;                  /* image size the intrinsics refer to */
+  float eps_tok, eps_blk;    /* LayerNorm eps of token_norm / trunk_norm, and of the blocks' norm1 / norm2 */
+  const float* w[8];         /* pose_branch fc1 [D/2, 9], its bias, fc2 [D, D/2], its bias, token_norm gamma, beta, trunk_norm gamma, beta */
+  const float* blk[8][14];   /* block i: norm1 gamma, beta, norm2 gamma, beta, qkv [3D, D], bias, proj [D, D], bias, ls1, fc1 [4D, D], bias,
+                              * fc2 [D, 4D], bias, ls2 */
+  const float* extr;         /* [B, V, 3, 4] world-to-camera */
+  const float* intr;         /* [B, V, 3, 3] */
+  float* out;                /* [B, D] */
+  float* pose_out;           /* optional [B, V, 9]: the pose encoding the kernel fed to pose_branch (t3 | quat xyzw | fov_h fov_w) */
+} md_camera_encode;
+int md_op_camera_encode(md_device_t dev, const md_camera_encode* desc, void* stream);
+typedef struct md_camera_decode {
+  int B, din, H, W;
+  const float* cam;   /* [B, din] */
+  const float* w[10]; /* backbone_1 [din, din], bias, backbone_2 [din, din], bias, fc_t [3, din], bias, fc_qvec [4, din], bias, fc_fov [2, din], bias */
+  float* pose;        /* [B, 9] */
+  float* extr;        /* optional [B, 12] world-to-camera */
+  float* intr;        /* optional [B, 9] */
+} md_camera_decode;
+int md_op_camera_decode(md_device_t dev, const md_camera_decode* desc, void* stream);
+/* pose [B, 9] -> extr [B, 12] world-to-camera, intr [B, 9]; either output may be NULL. The same device function as the decoder's tail. */
+int md_op_pose_to_camera(md_device_t dev, const float* pose, int B, int H, int W, float* extr, float* intr, void* stream);
 /* md_op_conv2d_direct as the FOV head runs it: the input held in `in_precision`'s storage type, add = optional fp32 NHWC tensor added
  * to the input, out = fp32 NHWC [B, OH, OW, out_ld] (out_ld 0 = Cout; columns Cout .. out_ld are not written). */
 int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, const float* add_dev, int B,
