@@ -12,17 +12,19 @@
 using namespace md;
 
 namespace {
-struct DevBuf {  // scoped device allocation for the stand-alone test operators
+// scoped device allocation of the stand-alone operators, with 4 KiB of slack. Zeroed, or `raw`: launcher scratch whose kernels write
+// every word they read is allocated, not cleared, so that a call the launcher refuses has started no device work
+struct DevBuf {
   void* p = nullptr;
   ~DevBuf() {
     if (p) (void)hipFree(p);
   }
-  int alloc(size_t bytes) {
+  int alloc(size_t bytes, bool raw = false) {
     if (hipMalloc(&p, bytes + 4096) != hipSuccess) {
       set_error("hipMalloc(%zu) failed", bytes);
       return MD_ERR_OOM;
     }
-    return hipMemset(p, 0, bytes + 4096) == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return raw || hipMemset(p, 0, bytes + 4096) == hipSuccess ? MD_OK : MD_ERR_HIP;
   }
 };
 hipStream_t pick_stream(md_device_t dev, void* stream) { return stream ? (hipStream_t)stream : dev->stream; }
@@ -35,6 +37,101 @@ int split_terms_of(const float* w_dev, long n, hipStream_t st, int* terms) {
   return MD_OK;
 }
 size_t esz_of(int prec) { return prec == MD_PREC_F32 ? 4 : (prec == MD_PREC_FP8 ? 1 : 2); }
+size_t storage_bytes(int precision) { return esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1); }  // split-half: two planes per element
+bool token_op_prec(int precision) {
+  return precision == MD_PREC_BF16 || precision == MD_PREC_F32 || precision == MD_PREC_F16 || precision == MD_PREC_F16X2;
+}
+
+// A storage-typed output of a stand-alone launch: narrowed from the caller's fp32 values before the launch, widened back behind it, so
+// the bytes the launch leaves alone return as they came. `narrow` = false: the launch writes every element it returns, and what it
+// leaves alone reads back as the zeroed buffer's
+struct StorageOut {
+  DevBuf buf;
+  float* user = nullptr;
+  long count = 0;
+  int width = 0, prec = MD_PREC_BF16;
+  int open(float* u, long n, int w, int precision, hipStream_t st, bool narrow = true) {
+    user = u; count = n; width = w; prec = precision;
+    MD_TRY(buf.alloc((size_t)n * storage_bytes(prec)));
+    return narrow ? launch_f32_to_rows(u, n, buf.p, prec, st, w) : MD_OK;
+  }
+  int close(hipStream_t st) { return user ? launch_rows_to_f32(buf.p, count, user, prec, st, width) : MD_OK; }  // (never opened: nothing)
+};
+
+// The staging of one stand-alone launch, opened once per entry behind its argument checks: the device, the stream, the precision and
+// the operand geometry the launch-parameter builders of md_engine_util.h read (OperandGeom: all they read of a model), here built
+// for a precision alone. Weight buffers are the entry's own allocations: three terms where it allocates before the count is known.
+struct OpStage {
+  hipStream_t st = nullptr;
+  int prec = MD_PREC_F32;
+  bool split = false;
+  OperandGeom geom;
+  DevBuf zp;
+  int open(md_device_t dev, void* stream, int precision = MD_PREC_F32) {
+    MD_HIP(hipSetDevice(dev->ordinal));
+    st = pick_stream(dev, stream);
+    prec = precision;
+    split = precision == MD_PREC_F16X2;
+    geom = OperandGeom{ke_of(prec), split ? 2 : 1, split ? 2 : 1, nullptr};
+    return MD_OK;
+  }
+  size_t es() const { return storage_bytes(prec); }
+  int zero_page() {  // geom.zero_page, allocated at the first call
+    if (!zp.p) MD_TRY(zp.alloc(4096));
+    geom.zero_page = zp.p;
+    return MD_OK;
+  }
+  // geom.wterms over the weight groups of the launch, one call per group of n values: the split-half term count of plain weights as
+  // model_commit decides it. One K for the launch: three terms as soon as one group's weights are not exact halves
+  int terms_of(const float* w_dev, long n) {
+    if (!split) return MD_OK;
+    int t = 2;
+    MD_TRY(split_terms_of(w_dev, n, st, &t));
+    geom.wterms = std::max(geom.wterms, t);
+    return MD_OK;
+  }
+  // the A operand of a dense GEMM in the precision's storage: split-half rows [hi | lo]; e4m3 on the static scale 8 / 448 (the
+  // engine's LayerNorm-output scale), which *ascale then holds
+  int dense_a(const float* src, long rows, int K, DevBuf& buf, float* ascale) {
+    const long n = rows * K;
+    if (prec == MD_PREC_FP8 && n % 4 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "e4m3 A operand: rows * K = %ld must be a multiple of 4", n);
+    MD_TRY(buf.alloc((size_t)n * es()));
+    if (prec != MD_PREC_FP8) return launch_f32_to_rows(src, n, buf.p, prec, st, split ? K : 0);
+    *ascale = 8.0f / 448.0f;
+    return launch_f32_to_fp8(src, n, 1.0f / *ascale, buf.p, st);
+  }
+  // W [N][K] of a dense GEMM into `buf`: split-half rows [W | W] or [Wh | Wh | Wl] by the launch's terms, e4m3 rows with their
+  // per-row scales in `scale_buf`, or plain rows
+  int dense_w(const float* src, int N, int K, DevBuf& buf, DevBuf& scale_buf) {
+    if (split) {
+      PackEntry e;
+      e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; e.kp = K;
+      return conv_w(src, e, buf);
+    }
+    if (prec != MD_PREC_FP8) return launch_f32_to_rows(src, (long)N * K, buf.p, prec, st);
+    MD_TRY(scale_buf.alloc((size_t)N * 4));
+    return launch_pack_fp8_rows(src, N, K, K, buf.p, (float*)scale_buf.p, st);
+  }
+  // the NHWC A operand of a convolution from the caller's NCHW values
+  int nhwc_a(const float* src_nchw, int B, int C, int H, int W, int relu, DevBuf& buf) {
+    MD_TRY(buf.alloc((size_t)B * H * W * C * es()));
+    return launch_nchw_to_nhwc(src_nchw, B, C, H, W, buf.p, prec, relu, st);
+  }
+  // `e` packed into `buf`; terms == 0: in the launch's plain-weight form (split_terms)
+  int conv_w(const float* src, PackEntry e, DevBuf& buf, int terms = 0) {
+    e.terms = split_terms(geom, terms);
+    e.dst = buf.p;
+    return pack_weight(src, e, prec, st);
+  }
+  // the NHWC result `buf` of C channels back to the caller's NCHW: fp32 values, or (t_out) the precision's storage
+  int nchw_out(const DevBuf& buf, int B, int C, int H, int W, bool t_out, float* out_nchw) {
+    return launch_nhwc_to_nchw(buf.p, B, C, H, W, C, 0, out_nchw, t_out ? prec : MD_PREC_F32, st);
+  }
+  int finish() {  // the buffers of the call are freed on return
+    MD_HIP(hipStreamSynchronize(st));
+    return MD_OK;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -657,8 +754,8 @@ int md_op_resize_catmull_rom(md_device_t dev, const uint8_t* rgb_dev, int B, int
   if (B <= 0 || h <= 0 || w <= 0 || sw <= 0 || sh <= 0 || tw <= 0 || th <= 0 || cx < 0 || cy < 0 || cx + tw > sw || cy + th > sh)
     MD_FAIL(MD_ERR_SHAPE, "invalid resize %dx%d -> %dx%d, crop %dx%d at (%d, %d)", w, h, sw, sh, tw, th, cx, cy);
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
   // tables of the two passes (identity when the size stays), uploaded for this call only
   const bool crop_only = sw == w && sh == h;
   std::vector<int> left[2], count[2];
@@ -693,9 +790,8 @@ int md_op_resize_catmull_rom(md_device_t dev, const uint8_t* rgb_dev, int B, int
   MD_TRY(tmp.alloc((size_t)B * th * nq * 16));
   MD_TRY(launch_resize_catmull_rom(rgb_dev, B, h, w, CrAxis{(const int2*)tab[0].p, (const float*)wbuf[0].p, maxc[0]}, cy, th,
                                    CrAxis{(const int2*)tab[1].p, (const float*)wbuf[1].p, maxc[1]}, cx, tw, xb0, nq, (float*)tmp.p, out_u8,
-                                   out_nchw, st));
-  MD_HIP(hipStreamSynchronize(st));  // the tables and the intermediate are freed on return
-  return MD_OK;
+                                   out_nchw, s.st));
+  return s.finish();
 }
 
 int md_op_depth_display(md_device_t dev, const float* depth_dev, int B, int h, int w, int crop_x, int crop_y, int crop_w, int crop_h, int ow,
@@ -712,14 +808,13 @@ int md_op_depth_display(md_device_t dev, const float* depth_dev, int B, int h, i
       crop_y + crop_h > h)
     MD_FAIL(MD_ERR_SHAPE, "invalid display of [%d,%d,%d]: crop %dx%d at (%d, %d) -> %dx%d", B, h, w, crop_w, crop_h, crop_x, crop_y, ow, oh);
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "device is null");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
   const DisplayGeom g = display_geom(B, h, w, crop_x, crop_y, crop_w, crop_h, ow, oh);
   DevBuf parts;
   MD_TRY(parts.alloc((size_t)B * display_parts(g) * sizeof(float2)));
-  MD_TRY(launch_depth_display(depth_dev, g, normalize, format, out, range, (float2*)parts.p, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  MD_TRY(launch_depth_display(depth_dev, g, normalize, format, out, range, (float2*)parts.p, s.st));
+  return s.finish();
 }
 
 int md_op_resize_bilinear(md_device_t dev, const float* in_dev, int B, int C, int H, int W, float* out_dev, int OH, int OW,
@@ -735,7 +830,7 @@ int md_op_pyramid_patchify(md_device_t dev, const float* x_dev, int B, int S, in
                            int force_generic, void* out_dev, int* rows_out, int* cols_out, void* stream) {
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || S <= 0 || window <= 0 || patch <= 0 || S != 4 * window || window % patch != 0) MD_FAIL(MD_ERR_SHAPE, "pyramid: S must be 4 * window and window a multiple of the patch size");
-  if (precision != MD_PREC_BF16 && precision != MD_PREC_F32 && precision != MD_PREC_F16 && precision != MD_PREC_F16X2) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   PyramidGeom g;
   g.B = B; g.S = S; g.win = window; g.ps = patch; g.method = method;
   split_geometry(S, window, 0.25f, &g.stride0, &g.steps0);      // encoder.rs:329
@@ -821,49 +916,28 @@ int md_op_linear_tile(md_device_t dev, const float* x_dev, const float* w_dev, c
   const KsplitScope ksplit(1);  // the stand-alone operator exercises the k-split form of the 64 x 64 kernel (what the DA3 engine runs)
   const bool storage_out = (precision & MD_OP_STORAGE_OUT) && (precision & 0xff) != MD_PREC_F32;
   precision &= 0xff;
-  if (precision != MD_PREC_BF16 && precision != MD_PREC_F32 && precision != MD_PREC_FP8 && precision != MD_PREC_F16 && precision != MD_PREC_F16X2) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (!token_op_prec(precision) && precision != MD_PREC_FP8) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (K % ke_of(precision) != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "K=%d must be a multiple of %d", K, ke_of(precision));
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const bool split = precision == MD_PREC_F16X2;
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
   DevBuf xa, wa, ws;
-  MD_TRY(xa.alloc((size_t)M * K * esz_of(precision) * (split ? 2 : 1)));
-  MD_TRY(wa.alloc((size_t)N * K * esz_of(precision) * (split ? 3 : 1)));
+  StorageOut ob;
   GemmParams p;
-  int terms = 1;
-  if (split) {
-    // split-half operands: x rows [hi | lo], w rows [W | W] when every weight is an exact half, else [Wh | Wh | Wl]
-    MD_TRY(split_terms_of(w_dev, (long)N * K, st, &terms));
-    MD_TRY(launch_f32_to_rows(x_dev, (long)M * K, xa.p, precision, st, K));
-    PackEntry e;
-    e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; e.kp = K; e.terms = terms; e.dst = wa.p;
-    MD_TRY(pack_weight(w_dev, e, precision, st));
-  } else if (precision == MD_PREC_FP8) {
-    // stand-alone fp8 check: activations on the static scale 8/448 (the engine's LayerNorm-output scale), weights
-    // per output row
-    const float xs = 8.0f / 448.0f;
-    MD_TRY(ws.alloc((size_t)N * 4));
-    MD_TRY(launch_f32_to_fp8(x_dev, (long)M * K, 1.0f / xs, xa.p, st));
-    MD_TRY(launch_pack_fp8_rows(w_dev, N, K, K, wa.p, (float*)ws.p, st));
-    p.wscale[0] = (const float*)ws.p;
-    p.ascale = xs;
-  } else {
-    MD_TRY(launch_f32_to_rows(x_dev, (long)M * K, xa.p, precision, st));
-    MD_TRY(launch_f32_to_rows(w_dev, (long)N * K, wa.p, precision, st));
+  MD_TRY(wa.alloc((size_t)N * K * esz_of(precision) * (s.split ? 3 : 1)));
+  MD_TRY(s.terms_of(w_dev, (long)N * K));
+  MD_TRY(s.dense_a(x_dev, M, K, xa, &p.ascale));
+  MD_TRY(s.dense_w(w_dev, N, K, wa, ws));
+  p.N = N; p.ngroups = 1; p.g_rows[0] = M; p.W[0] = wa.p; p.wscale[0] = (const float*)ws.p; p.A = xa.p;
+  split_dense_a(s.geom, p, K, K, 0);
+  p.epi = EPI_STORE; p.act = act; p.out_f32 = storage_out ? 0 : 1; p.bias[0] = bias_dev; p.out = out_dev;
+  if (storage_out) {  // (fp8 operands store bf16) every element is the launch's: nothing to narrow
+    MD_TRY(ob.open(out_dev, (long)M * N, N, precision == MD_PREC_FP8 ? MD_PREC_BF16 : precision, s.st, false));
+    p.out = ob.buf.p;
   }
-  p.N = N; p.K = K * terms; p.ngroups = 1; p.g_rows[0] = M; p.W[0] = wa.p; p.A = xa.p; p.lda = split ? 2 * K : K;
-  p.a_wrap = terms == 3 ? 2 * K / ke_of(precision) : 0;
-  p.epi = EPI_STORE; p.act = act; p.out_f32 = 1; p.bias[0] = bias_dev; p.out = out_dev; p.ldo = N;
-  DevBuf ob;
-  if (storage_out) {
-    MD_TRY(ob.alloc((size_t)M * N * 2 * (split ? 2 : 1)));
-    p.out_f32 = 0; p.out = ob.p;
-    if (split) { p.ldo = 2 * N; p.o_plane = N; }
-  }
-  MD_TRY(launch_gemm(p, A_DENSE, precision, tile, st));
-  if (storage_out) MD_TRY(launch_rows_to_f32(ob.p, (long)M * N, out_dev, (precision == MD_PREC_F16 || split) ? precision : MD_PREC_BF16, st, N));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  split_out(s.geom, p, N, storage_out);
+  MD_TRY(launch_gemm(p, A_DENSE, precision, tile, s.st));
+  MD_TRY(ob.close(s.st));
+  return s.finish();
 }
 
 // md_op_attention (V = 1), md_op_attention_views and md_op_attention_ex: one staging, one launcher
@@ -890,9 +964,10 @@ static int op_attention(md_device_t dev, const md_attention_op& d, void* stream)
   if (kpad % 64 != 0 || kpad < (N + 63) / 64 * 64) MD_FAIL(MD_ERR_INVALID_ARG, "attention: kpad=%d must be a multiple of 64 covering %d keys", kpad, N);
   // the fp32 path's score GEMM writes S columns into rows of kpad floats
   if (precision == MD_PREC_F32 && (SS % 4 != 0 || SS > kpad)) MD_FAIL(MD_ERR_INVALID_ARG, "attention (fp32): seq_stride=%d must be a multiple of 4 within kpad=%d", SS, kpad);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const size_t es = esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1);  // split-half: two planes per element
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
+  hipStream_t st = s.st;
+  const size_t es = s.es();
   DevBuf qk, vT, ao, sc;
   MD_TRY(qk.alloc(((size_t)T * SS + 64) * 2 * D * es));
   MD_TRY(vT.alloc((size_t)T * heads * 64 * kpad * es));
@@ -921,8 +996,7 @@ static int op_attention(md_device_t dev, const md_attention_op& d, void* stream)
     MD_HIP(hipMemcpy2DAsync(d.out, (size_t)N * D, ao.p, (size_t)SS * D, (size_t)N * D, (size_t)T, hipMemcpyDeviceToDevice, st));
   else
     MD_TRY(launch_unpad_rows(ao.p, T, N, SS, D, (float*)d.out, precision, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  return s.finish();
 }
 
 static md_attention_op attention_op_of(const float* qkv_dev, int T, int V, int N, int heads, int precision, float* out_dev) {
@@ -961,30 +1035,23 @@ int md_op_conv3x3(md_device_t dev, const float* x_dev, const float* w_dev, const
   precision &= 0xff;
   if (Cin % ke_of(precision) != 0 || Cout % 4 != 0)
     MD_FAIL(MD_ERR_UNSUPPORTED, "conv3x3: Cin=%d must be a multiple of %d and Cout=%d of 4", Cin, ke_of(precision), Cout);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const size_t es = esz_of(precision);
-  const bool split = precision == MD_PREC_F16X2;
-  DevBuf xa, wa, oa, zp;
-  MD_TRY(xa.alloc((size_t)B * H * W * Cin * es * (split ? 2 : 1)));
-  MD_TRY(wa.alloc((size_t)Cout * 9 * Cin * es * (split ? 3 : 1)));
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
+  DevBuf xa, wa, oa;
+  MD_TRY(wa.alloc((size_t)Cout * 9 * Cin * esz_of(precision) * (s.split ? 3 : 1)));
   MD_TRY(oa.alloc((size_t)B * H * W * Cout * 4));
-  MD_TRY(zp.alloc(4096));
-  MD_TRY(launch_nchw_to_nhwc(x_dev, B, Cin, H, W, xa.p, precision, pre_relu, st));
+  MD_TRY(s.zero_page());
+  MD_TRY(s.nhwc_a(x_dev, B, Cin, H, W, pre_relu, xa));
+  MD_TRY(s.terms_of(w_dev, (long)Cout * Cin * 9));
   PackEntry e;
-  e.kind = PACK_CONV3; e.d0 = Cout; e.d1 = Cin; e.k = 3; e.kp = Cin; e.dst = wa.p;
-  if (split) MD_TRY(split_terms_of(w_dev, (long)Cout * Cin * 9, st, &e.terms));
-  MD_TRY(pack_weight(w_dev, e, precision, st));
-  GemmParams p;
-  p.N = Cout; p.K = 9 * Cin * e.terms; p.ngroups = 1; p.g_rows[0] = B * H * W; p.W[0] = wa.p;
-  p.A = xa.p; p.cH = H; p.cW = W; p.cC = split ? 2 * Cin : Cin; p.cCk = split ? e.terms * Cin : 0; p.zero_page = zp.p;
-  p.a_wrap = e.terms == 3 ? 2 * Cin / ke_of(precision) : 0;
-  p.epi = EPI_STORE; p.out_f32 = storage_out ? 0 : 1; p.bias[0] = bias_dev; p.out = oa.p; p.ldo = Cout;
-  if (split && storage_out) { p.ldo = 2 * Cout; p.o_plane = Cout; }
-  MD_TRY(launch_gemm(p, A_CONV3, precision, TILE_AUTO, st));
-  MD_TRY(launch_nhwc_to_nchw(oa.p, B, Cout, H, W, Cout, 0, out_dev, storage_out ? precision : MD_PREC_F32, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  e.kind = PACK_CONV3; e.d0 = Cout; e.d1 = Cin; e.k = 3; e.kp = Cin;
+  MD_TRY(s.conv_w(w_dev, e, wa));
+  const ConvW cw{wa.p, bias_dev};
+  GemmParams p = conv3_params(s.geom, B, xa.p, H, W, Cin, &cw, Cout, oa.p, Cout, ACT_NONE, nullptr, nullptr, nullptr);
+  if (!storage_out) { p.out_f32 = 1; p.ldo = Cout; p.o_plane = 0; }  // an fp32 destination: one plane of Cout floats per pixel
+  MD_TRY(launch_gemm(p, A_CONV3, precision, TILE_AUTO, s.st));
+  MD_TRY(s.nchw_out(oa, B, Cout, H, W, storage_out, out_dev));
+  return s.finish();
 }
 
 int md_op_deconv2x2(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B, int Cin, int H,
@@ -995,29 +1062,21 @@ int md_op_deconv2x2(md_device_t dev, const float* x_dev, const float* w_dev, con
   precision &= 0xff;
   if (Cin % ke_of(precision) != 0 || Cout % 4 != 0)
     MD_FAIL(MD_ERR_UNSUPPORTED, "deconv: Cin=%d must be a multiple of %d and Cout=%d of 4", Cin, ke_of(precision), Cout);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const size_t es = esz_of(precision);
-  const bool split = precision == MD_PREC_F16X2;
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
   DevBuf xa, wa, oa;
-  MD_TRY(xa.alloc((size_t)B * H * W * Cin * es * (split ? 2 : 1)));
-  MD_TRY(wa.alloc((size_t)4 * Cout * Cin * es * (split ? 3 : 1)));
+  MD_TRY(wa.alloc((size_t)4 * Cout * Cin * esz_of(precision) * (s.split ? 3 : 1)));
   MD_TRY(oa.alloc((size_t)B * 4 * H * W * Cout * 4));
-  MD_TRY(launch_nchw_to_nhwc(x_dev, B, Cin, H, W, xa.p, precision, 0, st));
+  MD_TRY(s.nhwc_a(x_dev, B, Cin, H, W, 0, xa));
+  MD_TRY(s.terms_of(w_dev, (long)Cin * Cout * 4));
   PackEntry e;
-  e.kind = PACK_DECONV; e.d0 = Cin; e.d1 = Cout; e.k = 2; e.kp = Cin; e.dst = wa.p;
-  if (split) MD_TRY(split_terms_of(w_dev, (long)Cin * Cout * 4, st, &e.terms));
-  MD_TRY(pack_weight(w_dev, e, precision, st));
-  GemmParams p;
-  p.N = 4 * Cout; p.K = Cin * e.terms; p.ngroups = 1; p.g_rows[0] = B * H * W; p.W[0] = wa.p; p.A = xa.p; p.lda = split ? 2 * Cin : Cin;
-  p.a_wrap = e.terms == 3 ? 2 * Cin / ke_of(precision) : 0;
-  p.epi = EPI_PIXSHUF; p.out_f32 = storage_out ? 0 : 1; p.bias[0] = bias_dev; p.out = oa.p; p.ldo = Cout;
-  if (split && storage_out) { p.ldo = 2 * Cout; p.o_plane = Cout; }
-  p.psH = H; p.psW = W; p.psC = Cout; p.ps_coff = 0;
-  MD_TRY(launch_gemm(p, A_DENSE, precision, TILE_AUTO, st));
-  MD_TRY(launch_nhwc_to_nchw(oa.p, B, Cout, 2 * H, 2 * W, Cout, 0, out_dev, storage_out ? precision : MD_PREC_F32, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  e.kind = PACK_DECONV; e.d0 = Cin; e.d1 = Cout; e.k = 2; e.kp = Cin;
+  MD_TRY(s.conv_w(w_dev, e, wa));
+  GemmParams p = deconv2_params(s.geom, B, xa.p, Cin, nullptr, H, W, wa.p, Cin, Cout, bias_dev, oa.p, Cout, 0);
+  if (!storage_out) { p.out_f32 = 1; p.ldo = Cout; p.o_plane = 0; }  // an fp32 destination: one plane of Cout floats per pixel
+  MD_TRY(launch_gemm(p, A_DENSE, precision, TILE_AUTO, s.st));
+  MD_TRY(s.nchw_out(oa, B, Cout, 2 * H, 2 * W, storage_out, out_dev));
+  return s.finish();
 }
 
 int md_op_conv2d_direct(md_device_t dev, const float* x_dev, const float* w_dev, const float* bias_dev, int B, int Cin, int H,
@@ -1026,28 +1085,23 @@ int md_op_conv2d_direct(md_device_t dev, const float* x_dev, const float* w_dev,
   if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0) MD_FAIL(MD_ERR_SHAPE, "invalid shape");
   const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
   if (H + 2 * pad < k || W + 2 * pad < k) MD_FAIL(MD_ERR_SHAPE, "input %dx%d smaller than kernel %d", H, W, k);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
+  OpStage s;
+  MD_TRY(s.open(dev, stream, MD_PREC_F32));
   DevBuf xa, wa, oa;
-  MD_TRY(xa.alloc((size_t)B * H * W * Cin * 4));
   MD_TRY(wa.alloc((size_t)Cout * k * k * Cin * 4));
   MD_TRY(oa.alloc((size_t)B * OH * OW * Cout * 4));
-  MD_TRY(launch_nchw_to_nhwc(x_dev, B, Cin, H, W, xa.p, MD_PREC_F32, 0, st));
+  MD_TRY(s.nhwc_a(x_dev, B, Cin, H, W, 0, xa));
   PackEntry e;
-  e.kind = PACK_DIRECT; e.d0 = Cout; e.d1 = Cin; e.k = k; e.kp = Cin; e.f32 = 1; e.dst = wa.p;
-  MD_TRY(pack_weight(w_dev, e, MD_PREC_F32, st));
+  e.kind = PACK_DIRECT; e.d0 = Cout; e.d1 = Cin; e.k = k; e.kp = Cin; e.f32 = 1;
+  MD_TRY(s.conv_w(w_dev, e, wa));
   MD_TRY(launch_conv_direct(xa.p, MD_PREC_F32, nullptr, B, H, W, Cin, (const float*)wa.p, bias_dev, Cout, k, stride, pad, relu,
-                            (float*)oa.p, st));
-  MD_TRY(launch_nhwc_to_nchw(oa.p, B, Cout, OH, OW, Cout, 0, out_dev, MD_PREC_F32, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+                            (float*)oa.p, s.st));
+  MD_TRY(s.nchw_out(oa, B, Cout, OH, OW, false, out_dev));
+  return s.finish();
 }
 
 // ---- the Depth-Anything-v3 token kernels alone ----
 namespace {
-bool token_op_prec(int precision) {
-  return precision == MD_PREC_BF16 || precision == MD_PREC_F32 || precision == MD_PREC_F16 || precision == MD_PREC_F16X2;
-}
 struct RopeDev {  // the model's tables of one grid, uploaded for one call
   DevBuf cos, sin;
   int build(int n_tokens, int pw, float base) {
@@ -1080,36 +1134,27 @@ int md_op_qkv_norm_rope(md_device_t dev, const float* x_dev, const float* w_dev,
   // no k-split: the fused epilogue never runs it (pick_ksplit), so the plain GEMM of form 0 keeps the same summation order and the
   // V tiles of the two forms can be compared bit for bit
   const KsplitScope ksplit(0);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const bool split = precision == MD_PREC_F16X2;
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
+  hipStream_t st = s.st;
   const int heads = D / 64, kpad = (S + 63) / 64 * 64, N = 3 * D;
   const long rows = (long)T * S;
-  const size_t es = esz_of(precision) * (split ? 2 : 1), vt_elems = (size_t)T * heads * 64 * kpad;
+  const size_t es = s.es(), vt_elems = (size_t)T * heads * 64 * kpad;
   if (vt_elems >= ((size_t)1 << 31) || rows * 2 * D >= (1L << 31)) MD_FAIL(MD_ERR_UNSUPPORTED, "qkv_norm_rope: tensors of this size are not a test");
-  DevBuf xa, wa, qk, vT;
+  DevBuf xa, wa, ws, qk, vT;  // (ws: the e4m3 scales of OpStage::dense_w, never filled here)
   RopeDev rope;
-  MD_TRY(xa.alloc((size_t)rows * K * es));
-  MD_TRY(wa.alloc((size_t)N * K * esz_of(precision) * (split ? 3 : 1)));
+  GemmParams p;
+  MD_TRY(wa.alloc((size_t)N * K * esz_of(precision) * (s.split ? 3 : 1)));
   MD_TRY(qk.alloc(((size_t)rows + 64) * 2 * D * es));
   MD_TRY(vT.alloc(vt_elems * es));
   MD_TRY(rope.build(n_tokens, pw, rope_frequency));
-  int terms = 1;
-  if (split) {  // x rows [hi | lo], w rows [W | W] or [Wh | Wh | Wl] (md_op_linear_tile)
-    MD_TRY(split_terms_of(w_dev, (long)N * K, st, &terms));
-    MD_TRY(launch_f32_to_rows(x_dev, rows * K, xa.p, precision, st, K));
-    PackEntry e;
-    e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; e.kp = K; e.terms = terms; e.dst = wa.p;
-    MD_TRY(pack_weight(w_dev, e, precision, st));
-  } else {
-    MD_TRY(launch_f32_to_rows(x_dev, rows * K, xa.p, precision, st));
-    MD_TRY(launch_f32_to_rows(w_dev, (long)N * K, wa.p, precision, st));
-  }
-  GemmParams p;
-  p.N = N; p.K = K * terms; p.ngroups = 1; p.g_rows[0] = (int)rows; p.W[0] = wa.p; p.A = xa.p; p.lda = split ? 2 * K : K;
-  p.a_wrap = terms == 3 ? 2 * K / ke_of(precision) : 0;
+  MD_TRY(s.terms_of(w_dev, (long)N * K));
+  MD_TRY(s.dense_a(x_dev, rows, K, xa, &p.ascale));
+  MD_TRY(s.dense_w(w_dev, N, K, wa, ws));
+  p.N = N; p.ngroups = 1; p.g_rows[0] = (int)rows; p.W[0] = wa.p; p.A = xa.p;
+  split_dense_a(s.geom, p, K, K, 0);
   p.bias[0] = bias_dev;
-  p.v_plane = split ? (long)vt_elems : 0;
+  p.v_plane = s.split ? (long)vt_elems : 0;
   p.epi = EPI_QKV; p.out = qk.p; p.vT = vT.p; p.seq_stride = S; p.embed = D; p.heads = heads; p.kpad = kpad; p.qscale = attn_qscale(precision);
   if (form == 1) {
     p.qkn_g[0] = q_gamma; p.qkn_b[0] = q_beta; p.qkn_g[1] = k_gamma; p.qkn_b[1] = k_beta;
@@ -1125,8 +1170,7 @@ int md_op_qkv_norm_rope(md_device_t dev, const float* x_dev, const float* w_dev,
   // q | k rows: split-half [q_hi | q_lo | k_hi | k_lo] reads as 2 * rows rows of [hi: D | lo: D]
   MD_TRY(launch_rows_to_f32(qk.p, rows * 2 * D, qk_out, precision, st, D));
   MD_TRY(launch_rows_to_f32(vT.p, (long)vt_elems, vt_out, precision, st, (int)vt_elems));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  return s.finish();
 }
 
 int md_op_qk_norm_rope(md_device_t dev, const float* qk_in, const float* q_gamma, const float* q_beta, const float* k_gamma,
@@ -1135,19 +1179,18 @@ int md_op_qk_norm_rope(md_device_t dev, const float* qk_in, const float* q_gamma
   if (!dev || !qk_in || !q_gamma || !q_beta || !k_gamma || !k_beta || !qk_out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   MD_TRY(check_token_grid("qk_norm_rope", T, S, n_tokens, D, pw));
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
   const long rows = (long)T * S;
   DevBuf qk;
   RopeDev rope;
-  MD_TRY(qk.alloc((size_t)rows * 2 * D * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
+  MD_TRY(qk.alloc((size_t)rows * 2 * D * s.es()));
   MD_TRY(rope.build(n_tokens, pw, rope_frequency));
-  MD_TRY(launch_f32_to_rows(qk_in, rows * 2 * D, qk.p, precision, st, D));
+  MD_TRY(launch_f32_to_rows(qk_in, rows * 2 * D, qk.p, precision, s.st, D));
   MD_TRY(launch_qk_norm_rope(qk.p, rows, S, n_tokens, D, D / 64, pw, q_gamma, q_beta, k_gamma, k_beta, eps, (const float*)rope.cos.p,
-                             (const float*)rope.sin.p, global_pos ? 1 : 0, attn_qscale(precision), precision, st));
-  MD_TRY(launch_rows_to_f32(qk.p, rows * 2 * D, qk_out, precision, st, D));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+                             (const float*)rope.sin.p, global_pos ? 1 : 0, attn_qscale(precision), precision, s.st));
+  MD_TRY(launch_rows_to_f32(qk.p, rows * 2 * D, qk_out, precision, s.st, D));
+  return s.finish();
 }
 
 int md_op_hook_cat_ln(md_device_t dev, const float* x_local, const float* x, int T, int S, int n_tokens, int D, const float* norm_g,
@@ -1156,16 +1199,14 @@ int md_op_hook_cat_ln(md_device_t dev, const float* x_local, const float* x, int
   if (!dev || !x_local || !x || !norm_g || !norm_b || !head_g || !head_b || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (T <= 0 || n_tokens <= 0 || S < n_tokens || D <= 0) MD_FAIL(MD_ERR_SHAPE, "hook_cat_ln: T=%d S=%d n_tokens=%d D=%d", T, S, n_tokens, D);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
   const long rows = (long)T * S;
-  DevBuf ob;
-  MD_TRY(ob.alloc((size_t)rows * 2 * D * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
-  MD_TRY(launch_f32_to_rows(out, rows * 2 * D, ob.p, precision, st, 2 * D));
-  MD_TRY(launch_hook_cat_ln(x_local, x, rows, S, n_tokens, D, norm_g, norm_b, eps_final, head_g, head_b, eps_head, ob.p, cam_out, precision, st));
-  MD_TRY(launch_rows_to_f32(ob.p, rows * 2 * D, out, precision, st, 2 * D));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  StorageOut ob;
+  MD_TRY(ob.open(out, rows * 2 * D, 2 * D, precision, s.st));
+  MD_TRY(launch_hook_cat_ln(x_local, x, rows, S, n_tokens, D, norm_g, norm_b, eps_final, head_g, head_b, eps_head, ob.buf.p, cam_out, precision, s.st));
+  MD_TRY(ob.close(s.st));
+  return s.finish();
 }
 
 int md_op_patchify(md_device_t dev, const float* x_dev, int B, int H, int W, int ps, int Kp, int precision, float* out, float* cls_x,
@@ -1174,48 +1215,38 @@ int md_op_patchify(md_device_t dev, const float* x_dev, int B, int H, int W, int
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (B <= 0 || H <= 0 || W <= 0 || ps <= 0 || H % ps || W % ps || Kp < 3 * ps * ps) MD_FAIL(MD_ERR_SHAPE, "patchify: %dx%d / patch %d / K %d", H, W, ps, Kp);
   if (cls_x && n_tokens != 1 + (H / ps) * (W / ps)) MD_FAIL(MD_ERR_SHAPE, "patchify: n_tokens = %d for a %dx%d grid", n_tokens, H / ps, W / ps);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const long count = (long)B * (H / ps) * (W / ps) * Kp;
-  DevBuf ob;
-  MD_TRY(ob.alloc((size_t)count * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
-  MD_TRY(launch_patchify(x_dev, B, H, W, ps, Kp, ob.p, precision, st, cls_x, S, n_tokens, D, cls, pos0));
-  MD_TRY(launch_rows_to_f32(ob.p, count, out, precision, st, Kp));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
+  StorageOut ob;  // every element is the launch's: nothing to narrow
+  MD_TRY(ob.open(out, (long)B * (H / ps) * (W / ps) * Kp, Kp, precision, s.st, false));
+  MD_TRY(launch_patchify(x_dev, B, H, W, ps, Kp, ob.buf.p, precision, s.st, cls_x, S, n_tokens, D, cls, pos0));
+  MD_TRY(ob.close(s.st));
+  return s.finish();
 }
 
 int md_op_set_token0(md_device_t dev, float* x, int nseq, int S, int D, const float* src, int src_stride, void* stream) {
   if (!dev || !x || !src) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (nseq <= 0 || S <= 0 || D <= 0 || src_stride < 0) MD_FAIL(MD_ERR_SHAPE, "set_token0: nseq=%d S=%d D=%d stride=%d", nseq, S, D, src_stride);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_set_token0(x, nseq, S, D, src, st, src_stride));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_set_token0(x, nseq, S, D, src, s.st, src_stride));
+  return s.finish();
 }
 
 int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int C, int ld, const float* bias9, int precision, void* stream) {
   if (!dev || !map || !bias9) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (B <= 0 || H < 2 || W < 2 || C <= 0 || ld < C) MD_FAIL(MD_ERR_SHAPE, "border_bias_fix: [%d,%d,%d] C=%d ld=%d", B, H, W, C, ld);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const long count = (long)B * H * W * ld;
-  DevBuf mb;
-  MD_TRY(mb.alloc((size_t)count * esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1)));
-  MD_TRY(launch_f32_to_rows(map, count, mb.p, precision, st, ld));
-  MD_TRY(launch_border_bias_fix(mb.p, B, H, W, C, ld, bias9, precision, st));
-  MD_TRY(launch_rows_to_f32(mb.p, count, map, precision, st, ld));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
+  StorageOut mb;
+  MD_TRY(mb.open(map, (long)B * H * W * ld, ld, precision, s.st));
+  MD_TRY(launch_border_bias_fix(mb.buf.p, B, H, W, C, ld, bias9, precision, s.st));
+  MD_TRY(mb.close(s.st));
+  return s.finish();
 }
 
 // ---- the kernels that write MFMA operands, alone: the caller's buffers hold the stored bytes (no widened copy) ----
-namespace {
-size_t storage_bytes(int precision) { return esz_of(precision) * (precision == MD_PREC_F16X2 ? 2 : 1); }
-}  // namespace
-
 int md_op_layernorm_ex(md_device_t dev, float* x, int rows, int D, int S, int ngroups, const int* seq0, const int* nseq,
                        const float* const* gamma, const float* const* beta, float eps, int precision, int out_f32, float fp8_inv_scale,
                        const float* tok0, int tok0_stride, void* out, void* stream) {
@@ -1234,53 +1265,48 @@ int md_op_layernorm_ex(md_device_t dev, float* x, int rows, int D, int S, int ng
     next += nseq[i];
   }
   if ((long)next * S < rows) MD_FAIL(MD_ERR_SHAPE, "layernorm_ex: %d sequences of %d rows do not cover %d rows", next, S, rows);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_layernorm(x, out, rows, D, eps, S, g, precision, out_f32, st, fp8_inv_scale, tok0, tok0_stride, tok0 ? x : nullptr));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_layernorm(x, out, rows, D, eps, S, g, precision, out_f32, s.st, fp8_inv_scale, tok0, tok0_stride, tok0 ? x : nullptr));
+  return s.finish();
 }
 
 int md_op_store_rows(md_device_t dev, const float* in, int64_t count, int width, int precision, void* out, void* stream) {
   if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (count <= 0 || width < 0) MD_FAIL(MD_ERR_SHAPE, "store_rows: count=%lld width=%d", (long long)count, width);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_f32_to_rows(in, (long)count, out, precision, st, width));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_f32_to_rows(in, (long)count, out, precision, s.st, width));
+  return s.finish();
 }
 
 int md_op_load_rows(md_device_t dev, const void* in, int64_t count, int width, int precision, float* out, void* stream) {
   if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (count <= 0 || width < 0) MD_FAIL(MD_ERR_SHAPE, "load_rows: count=%lld width=%d", (long long)count, width);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_rows_to_f32(in, (long)count, out, precision, st, width));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_rows_to_f32(in, (long)count, out, precision, s.st, width));
+  return s.finish();
 }
 
 int md_op_f32_to_fp8(md_device_t dev, const float* in, int64_t count, float inv_scale, void* out, void* stream) {
   if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (count <= 0) MD_FAIL(MD_ERR_SHAPE, "f32_to_fp8: count=%lld", (long long)count);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_f32_to_fp8(in, (long)count, inv_scale, out, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_f32_to_fp8(in, (long)count, inv_scale, out, s.st));
+  return s.finish();
 }
 
 int md_op_pack_fp8_rows(md_device_t dev, const float* w, int N, int K, int Kp, void* out, float* scale, void* stream) {
   if (!dev || !w || !out || !scale) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (N <= 0 || K <= 0) MD_FAIL(MD_ERR_SHAPE, "pack_fp8_rows: N=%d K=%d", N, K);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_pack_fp8_rows(w, N, K, Kp, out, scale, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_pack_fp8_rows(w, N, K, Kp, out, scale, s.st));
+  return s.finish();
 }
 
 int md_op_nchw_to_nhwc(md_device_t dev, const float* in, int B, int C, int H, int W, int precision, int relu, int ld, void* out,
@@ -1288,11 +1314,10 @@ int md_op_nchw_to_nhwc(md_device_t dev, const float* in, int B, int C, int H, in
   if (!dev || !in || !out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ld < 0) MD_FAIL(MD_ERR_SHAPE, "nchw_to_nhwc: [%d,%d,%d,%d] ld=%d", B, C, H, W, ld);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_nchw_to_nhwc(in, B, C, H, W, out, precision, relu ? 1 : 0, st, ld));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_nchw_to_nhwc(in, B, C, H, W, out, precision, relu ? 1 : 0, s.st, ld));
+  return s.finish();
 }
 
 int md_op_nhwc_to_nchw(md_device_t dev, const void* in, int B, int C, int H, int W, int ld, int coff, int precision, float* out,
@@ -1301,51 +1326,31 @@ int md_op_nhwc_to_nchw(md_device_t dev, const void* in, int B, int C, int H, int
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "nhwc_to_nchw: [%d,%d,%d,%d]", B, C, H, W);
   if (coff < 0 || ld < coff + C) MD_FAIL(MD_ERR_INVALID_ARG, "nhwc_to_nchw: channels [%d, %d) outside a pixel of %d", coff, coff + C, ld);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_nhwc_to_nchw(in, B, C, H, W, ld, coff, out, precision, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_nhwc_to_nchw(in, B, C, H, W, ld, coff, out, precision, s.st));
+  return s.finish();
 }
 
 int md_op_ln_fold_vectors(md_device_t dev, const float* w, const float* gamma, const float* beta, const float* bias, int N, int K,
                           int precision, float* c, float* d, void* stream) {
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_ln_fold_vectors(w, gamma, beta, bias, N, K, precision, c, d, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_ln_fold_vectors(w, gamma, beta, bias, N, K, precision, c, d, s.st));
+  return s.finish();
 }
 
 int md_op_ln_finish(md_device_t dev, const float* parts, int64_t rows, float inv_n, float eps, float* ab, void* stream) {
   if (!dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_ln_finish(parts, ab, (long)rows, inv_n, eps, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_ln_finish(parts, ab, (long)rows, inv_n, eps, s.st));
+  return s.finish();
 }
 
 // ---- the GEMM forms of the ViT token stream alone ----
-namespace {
-// a storage-typed output of md_op_vit_gemm: narrowed from the caller's fp32 values before the launch, widened back behind it, so the
-// bytes the launch leaves alone return as they came
-struct StorageOut {
-  DevBuf buf;
-  float* user = nullptr;
-  long count = 0;
-  int width = 0;
-  int open(float* u, long n, int w, int prec, hipStream_t st) {
-    user = u; count = n; width = w;
-    MD_TRY(buf.alloc((size_t)n * storage_bytes(prec)));
-    return launch_f32_to_rows(u, n, buf.p, prec, st, w);
-  }
-  int close(int prec, hipStream_t st) { return launch_rows_to_f32(buf.p, count, user, prec, st, width); }
-};
-}  // namespace
-
 int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* d, void* stream) {
   if (!dev || !d || !d->a) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   const int prec = d->precision, kind = d->kind, N = d->N, K = d->K, G = d->ngroups;
@@ -1390,51 +1395,28 @@ int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* d, void* stream) {
     if (vt_elems >= ((size_t)1 << 31) || (long)d->out_rows * 2 * D >= (1L << 31)) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: tensors of this size are not a test");
   }
   const KsplitScope ksplit(1);  // as md_op_linear_tile: the k-split form of the 64 x 64 kernel is what the DA3 engine runs
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const bool split = prec == MD_PREC_F16X2, f8 = prec == MD_PREC_FP8;
-  const int xm = split ? 2 : 1;
+  OpStage s;
+  MD_TRY(s.open(dev, stream, prec));
+  hipStream_t st = s.st;
+  const bool split = s.split;
+  const int xm = s.geom.xm;
 
-  // ---- operands, staged as md_op_linear_tile stages them ----
+  // ---- operands ----
   DevBuf xa, wa[kMaxGroups], ws[kMaxGroups];
   GemmParams p;
-  int terms = 1;
-  MD_TRY(xa.alloc((size_t)d->a_rows * K * esz_of(prec) * xm));
-  if (split) {
-    for (int g = 0; g < G; ++g) {  // one K for the launch: three terms as soon as one group's weights are not exact halves
-      int t = 2;
-      MD_TRY(split_terms_of(d->g[g].w, (long)N * K, st, &t));
-      terms = std::max(terms, t);
-    }
-    MD_TRY(launch_f32_to_rows(d->a, (long)d->a_rows * K, xa.p, prec, st, K));
-  } else if (f8) {
-    if (((long)d->a_rows * K) % 4 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "vit_gemm: e4m3 A operand: a_rows * K must be a multiple of 4");
-    p.ascale = 8.0f / 448.0f;
-    MD_TRY(launch_f32_to_fp8(d->a, (long)d->a_rows * K, 1.0f / p.ascale, xa.p, st));
-  } else {
-    MD_TRY(launch_f32_to_rows(d->a, (long)d->a_rows * K, xa.p, prec, st));
-  }
+  for (int g = 0; g < G; ++g) MD_TRY(s.terms_of(d->g[g].w, (long)N * K));
+  MD_TRY(s.dense_a(d->a, d->a_rows, K, xa, &p.ascale));
   for (int g = 0; g < G; ++g) {
     const md_vit_gemm_group& q = d->g[g];
-    MD_TRY(wa[g].alloc((size_t)N * K * esz_of(prec) * (split ? terms : 1)));
-    if (split) {
-      PackEntry e;
-      e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; e.kp = K; e.terms = terms; e.dst = wa[g].p;
-      MD_TRY(pack_weight(q.w, e, prec, st));
-    } else if (f8) {
-      MD_TRY(ws[g].alloc((size_t)N * 4));
-      MD_TRY(launch_pack_fp8_rows(q.w, N, K, K, wa[g].p, (float*)ws[g].p, st));
-      p.wscale[g] = (const float*)ws[g].p;
-    } else {
-      MD_TRY(launch_f32_to_rows(q.w, (long)N * K, wa[g].p, prec, st));
-    }
+    MD_TRY(wa[g].alloc((size_t)N * K * esz_of(prec) * split_terms(s.geom, 0)));
+    MD_TRY(s.dense_w(q.w, N, K, wa[g], ws[g]));
     p.g_row0[g] = q.row0; p.g_rows[g] = q.rows; p.g_arow0[g] = q.arow0;
-    p.W[g] = wa[g].p; p.bias[g] = q.bias; p.scale[g] = q.scale; p.pos[g] = q.pos;
+    p.W[g] = wa[g].p; p.wscale[g] = (const float*)ws[g].p; p.bias[g] = q.bias; p.scale[g] = q.scale; p.pos[g] = q.pos;
     if (producer) p.ln_gamma[g] = q.gamma_next;
     if (consumer) p.ln_c[g] = q.c;
   }
-  p.N = N; p.K = K * terms; p.ngroups = G; p.A = xa.p; p.lda = (long)K * xm;
-  p.a_wrap = terms == 3 ? 2 * K / ke_of(prec) : 0;
+  p.N = N; p.ngroups = G; p.A = xa.p;
+  split_dense_a(s.geom, p, K, K, 0);
   if (consumer) {
     p.ln_stats = d->ln_stats; p.ln_raw = d->ln_raw ? 1 : 0; p.ln_parts = K / 256; p.ln_inv_n = d->ln_inv_n; p.ln_eps = d->ln_eps;
   }
@@ -1443,7 +1425,8 @@ int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* d, void* stream) {
   StorageOut o1, o2;
   const long rows = d->out_rows;
   if (resid) {
-    p.epi = EPI_RESID_LS; p.ldo = N;
+    p.epi = EPI_RESID_LS;
+    split_out(s.geom, p, N, false);
     p.out = d->x_out ? d->x_out : d->x;
     p.resid_src = d->x_out ? d->x : nullptr;
     if (producer) {
@@ -1457,22 +1440,23 @@ int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* d, void* stream) {
     p.epi = EPI_QKV; p.out = o1.buf.p; p.vT = o2.buf.p; p.v_plane = split ? (long)vt_elems : 0;
     p.seq_stride = S; p.embed = D; p.heads = heads; p.kpad = kpad; p.qscale = attn_qscale(prec);
   } else if (kind == MD_VIT_GEMM_FC1) {
-    p.epi = EPI_STORE; p.act = ACT_GELU; p.ldo = N;
+    p.epi = EPI_STORE; p.act = ACT_GELU;
     if (prec == MD_PREC_F32) {
       p.out_f32 = 1; p.out = d->out;
     } else {
       MD_TRY(o1.open(d->out, rows * N, N, prec, st));
-      p.out = o1.buf.p; p.ldo = (long)N * xm; p.o_plane = split ? N : 0;
+      p.out = o1.buf.p;
     }
+    split_out(s.geom, p, N, !p.out_f32);
   } else {
-    p.epi = EPI_PATCH_EMBED; p.out = d->x; p.ldo = N; p.seq_stride = S; p.seq_patches = d->P; p.embed = N;
+    p.epi = EPI_PATCH_EMBED; p.out = d->x; p.seq_stride = S; p.seq_patches = d->P; p.embed = N;
+    split_out(s.geom, p, N, false);
   }
   gemm_forget_form();
   MD_TRY(launch_gemm(p, A_DENSE, prec, d->tile, st));
-  if (o1.user) MD_TRY(o1.close(prec, st));
-  if (o2.user) MD_TRY(o2.close(prec, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  MD_TRY(o1.close(st));
+  MD_TRY(o2.close(st));
+  return s.finish();
 }
 
 // ---- the GEMM forms of the convolutional decoders and heads alone ----
@@ -1500,35 +1484,22 @@ int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* d, void* stream) 
   if (up2 && (d->Cmid <= 0 || !d->w2 || !d->bias2 || !d->head_w)) MD_FAIL(MD_ERR_INVALID_ARG, "decoder_gemm: HEAD_UP2 needs Cmid, w2, bias2, head_w");
   if ((long)G * B * H * W * (ps ? d->ps_f * d->ps_f : 1) >= (1L << 31)) MD_FAIL(MD_ERR_UNSUPPORTED, "decoder_gemm: tensors of this size are not a test");
   const KsplitScope ksplit(1);  // (the Depth-Anything-v3 engine, whose head these forms are, runs with the k-split form allowed)
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  const bool split = prec == MD_PREC_F16X2;
-
-  // the operand geometry the launch helpers of md_engine_util.h read (OperandGeom: all they read of a model): the precision's k-tile and
-  // planes, the split-half term count of plain weights as model_commit decides it (two when every weight of the launch is an exact
-  // half) and the zero page
-  DevBuf zp, wa[2], composed, bias9;
-  MD_TRY(zp.alloc(4096));
-  OperandGeom geom{ke_of(prec), split ? 2 : 1, 1, zp.p};
+  OpStage s;
+  MD_TRY(s.open(dev, stream, prec));
+  hipStream_t st = s.st;
+  const OperandGeom& geom = s.geom;  // (the term count: two when every plain weight of the launch is an exact half)
+  DevBuf wa[2], composed, bias9;
+  MD_TRY(s.zero_page());
   const int taps = ps ? d->ps_f * d->ps_f : 9;
-  if (split) {
-    geom.wterms = 2;
-    for (int g = 0; g < G && !up2; ++g) {
-      int t = 2;
-      MD_TRY(split_terms_of(d->w[g], (long)Cout * Cin * taps, st, &t));
-      geom.wterms = std::max(geom.wterms, t);
-    }
-  }
+  for (int g = 0; g < G && !up2; ++g) MD_TRY(s.terms_of(d->w[g], (long)Cout * Cin * taps));
   const int terms = up2 ? 3 : 0;  // (the composed head weight is a sum of products, never f16-exact: model_commit packs it in three terms)
-  const int wt = split_terms(geom, terms);
   ConvW cw[2];
   for (int g = 0; g < G; ++g) {
     PackEntry e;
-    e.kp = Cin_p; e.terms = wt;
+    e.kp = Cin_p;
     if (ps) { e.kind = PACK_DECONV; e.d0 = Cin; e.d1 = Cout; e.k = d->ps_f; }
     else { e.kind = PACK_CONV3; e.d0 = up2 ? 4 * Cout : Cout; e.d1 = Cin; e.k = 3; }
-    MD_TRY(wa[g].alloc(pack_elems(e, wt) * esz_of(prec)));
-    e.dst = wa[g].p;
+    MD_TRY(wa[g].alloc(pack_elems(e, split_terms(geom, terms)) * esz_of(prec)));
     const float* src = d->w[g];
     if (up2) {  // add_pack_fused(PACK_HEAD_W) as model_commit runs it: the product in fp32, then packed as a 3x3 convolution of 4 x 32 columns; PACK_HEAD_B: nine bias classes
       MD_TRY(composed.alloc((size_t)4 * Cout * Cin * 9 * 4));
@@ -1537,7 +1508,7 @@ int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* d, void* stream) 
       MD_TRY(compose_head_bias(d->w2, d->bias[0], d->bias2, d->Cmid, Cout, (float*)bias9.p, st));
       src = (const float*)composed.p;
     }
-    MD_TRY(pack_weight(src, e, prec, st));
+    MD_TRY(s.conv_w(src, e, wa[g], terms));
     cw[g] = ConvW{wa[g].p, up2 ? (const float*)bias9.p : d->bias[g]};
   }
 
@@ -1596,29 +1567,10 @@ int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* d, void* stream) 
   if (tile == TILE_AUTO && up2) tile = TILE_128x128;
   gemm_forget_form();
   MD_TRY(launch_gemm(p, amode, prec, tile, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  return s.finish();
 }
 
-// ---- the camera path alone ----
-namespace {
-// launcher scratch of the camera entries: allocated, not cleared (the kernels write every word they read), so that a call the launcher
-// refuses has started no device work
-struct RawBuf {
-  float* p = nullptr;
-  ~RawBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t floats) {
-    if (hipMalloc((void**)&p, floats * 4 + 4096) != hipSuccess) {
-      set_error("hipMalloc(%zu) failed", floats * 4);
-      return MD_ERR_OOM;
-    }
-    return MD_OK;
-  }
-};
-}  // namespace
-
+// ---- the camera path alone (launcher scratch: raw DevBufs, so that a call the launcher refuses has started no device work) ----
 int md_op_camera_encode(md_device_t dev, const md_camera_encode* d, void* stream) {
   if (!dev || !d || !d->extr || !d->intr || !d->out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   const int B = d->B, V = d->V, D = d->D;
@@ -1635,18 +1587,17 @@ int md_op_camera_encode(md_device_t dev, const md_camera_encode* d, void* stream
       if (!b[j]) MD_FAIL(MD_ERR_INVALID_ARG, "camera_encode: block %d weight %d missing", i, j);
     w.blk[i] = CamEncW::Blk{b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12], b[13]};
   }
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  RawBuf scratch;
-  MD_TRY(scratch.alloc(V > 0 ? camera_encoder_scratch_floats(B, V, D) : 0));
-  MD_TRY(launch_camera_encoder(d->extr, d->intr, B, V, D, d->heads, d->H, d->W, d->eps_tok, d->eps_blk, w, scratch.p, d->out, st));
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  DevBuf scratch;
+  MD_TRY(scratch.alloc((V > 0 ? camera_encoder_scratch_floats(B, V, D) : 0) * 4, true));
+  MD_TRY(launch_camera_encoder(d->extr, d->intr, B, V, D, d->heads, d->H, d->W, d->eps_tok, d->eps_blk, w, (float*)scratch.p, d->out, s.st));
   if (d->pose_out) {  // camera_encoder_kernel: per image `pose [V][12]` leads the scratch
     const size_t per_image = camera_encoder_scratch_floats(1, V, D);
     for (int b = 0; b < B; ++b)
-      MD_HIP(hipMemcpy2DAsync(d->pose_out + (size_t)b * V * 9, 9 * 4, scratch.p + b * per_image, 12 * 4, 9 * 4, V, hipMemcpyDeviceToDevice, st));
+      MD_HIP(hipMemcpy2DAsync(d->pose_out + (size_t)b * V * 9, 9 * 4, (float*)scratch.p + b * per_image, 12 * 4, 9 * 4, V, hipMemcpyDeviceToDevice, s.st));
   }
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  return s.finish();
 }
 
 int md_op_camera_decode(md_device_t dev, const md_camera_decode* d, void* stream) {
@@ -1656,24 +1607,22 @@ int md_op_camera_decode(md_device_t dev, const md_camera_decode* d, void* stream
   const int B = d->B, din = d->din;
   if (din <= 0 || d->H <= 0 || d->W <= 0) MD_FAIL(MD_ERR_SHAPE, "camera_decode: din=%d image %dx%d", din, d->H, d->W);
   const CamDecW w{d->w[0], d->w[1], d->w[2], d->w[3], d->w[4], d->w[5], d->w[6], d->w[7], d->w[8], d->w[9]};
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  RawBuf h;  // h1 | h2
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  DevBuf h;  // h1 | h2
   const size_t n = B > 0 ? (size_t)B * din : 0;
-  MD_TRY(h.alloc(2 * n));
-  MD_TRY(launch_camera_decoder(d->cam, B, din, w, d->H, d->W, h.p, h.p + n, d->pose, d->extr, d->intr, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  MD_TRY(h.alloc(2 * n * 4, true));
+  MD_TRY(launch_camera_decoder(d->cam, B, din, w, d->H, d->W, (float*)h.p, (float*)h.p + n, d->pose, d->extr, d->intr, s.st));
+  return s.finish();
 }
 
 int md_op_pose_to_camera(md_device_t dev, const float* pose, int B, int H, int W, float* extr, float* intr, void* stream) {
   if (!dev || !pose) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "pose_to_camera: B=%d image %dx%d", B, H, W);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
-  MD_TRY(launch_pose_to_camera(pose, B, H, W, extr, intr, st));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  MD_TRY(launch_pose_to_camera(pose, B, H, W, extr, intr, s.st));
+  return s.finish();
 }
 
 int md_debug_gemm_last_launch(int out[4]) {
@@ -1698,19 +1647,17 @@ int md_op_conv2d_direct_ex(md_device_t dev, const float* x_dev, const float* w_d
   if (!token_op_prec(in_precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", in_precision);
   if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0) MD_FAIL(MD_ERR_SHAPE, "invalid shape");
   if (H + 2 * pad < k || W + 2 * pad < k) MD_FAIL(MD_ERR_SHAPE, "input %dx%d smaller than kernel %d", H, W, k);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = pick_stream(dev, stream);
+  OpStage s;
+  MD_TRY(s.open(dev, stream, in_precision));
   DevBuf xa, wa;
-  MD_TRY(xa.alloc((size_t)B * H * W * Cin * storage_bytes(in_precision)));
   MD_TRY(wa.alloc((size_t)Cout * k * k * Cin * 4));
-  MD_TRY(launch_nchw_to_nhwc(x_dev, B, Cin, H, W, xa.p, in_precision, 0, st));
+  MD_TRY(s.nhwc_a(x_dev, B, Cin, H, W, 0, xa));
   PackEntry e;
-  e.kind = PACK_DIRECT; e.d0 = Cout; e.d1 = Cin; e.k = k; e.kp = Cin; e.f32 = 1; e.dst = wa.p;
-  MD_TRY(pack_weight(w_dev, e, MD_PREC_F32, st));
-  MD_TRY(launch_conv_direct(xa.p, in_precision, add_dev, B, H, W, Cin, (const float*)wa.p, bias_dev, Cout, k, stride, pad, relu, out_dev, st,
+  e.kind = PACK_DIRECT; e.d0 = Cout; e.d1 = Cin; e.k = k; e.kp = Cin; e.f32 = 1;
+  MD_TRY(s.conv_w(w_dev, e, wa));
+  MD_TRY(launch_conv_direct(xa.p, in_precision, add_dev, B, H, W, Cin, (const float*)wa.p, bias_dev, Cout, k, stride, pad, relu, out_dev, s.st,
                             out_ld));
-  MD_HIP(hipStreamSynchronize(st));
-  return MD_OK;
+  return s.finish();
 }
 
 int md_op_fov_to_focal(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad) {
@@ -1770,15 +1717,16 @@ int md_bench_gemm(md_device_t dev, int mode, int M, int N, int K, int aux0, int 
   const int dbg = tile >> 8;  // timing-only ablation flags ride in the upper bits of `tile`
   tile &= 0xff;
   if (!dev || !avg_ms || M <= 0 || N <= 0 || K <= 0 || iters <= 0) MD_FAIL(MD_ERR_INVALID_ARG, "invalid argument");
-  MD_HIP(hipSetDevice(dev->ordinal));
-  hipStream_t st = dev->stream;
+  OpStage s;
+  MD_TRY(s.open(dev, nullptr, precision));
+  hipStream_t st = s.st;
   const size_t es = esz_of(precision);
-  DevBuf a, w, o, zp;
+  DevBuf a, w, o;
   const size_t kw = mode == 1 ? (size_t)9 * K : (size_t)K;
   MD_TRY(a.alloc((size_t)M * K * es));
   MD_TRY(w.alloc((size_t)N * kw * es));
   MD_TRY(o.alloc((size_t)M * N * (es < 2 ? 2 : es)));
-  MD_TRY(zp.alloc(4096));
+  MD_TRY(s.zero_page());
   MD_TRY(fill_random(a.p, (size_t)M * K, precision, 1, 1.0f, st));
   MD_TRY(fill_random(w.p, (size_t)N * kw, precision, 2, 0.05f, st));
   GemmParams p;
@@ -1806,7 +1754,7 @@ int md_bench_gemm(md_device_t dev, int mode, int M, int N, int K, int aux0, int 
   int amode = A_DENSE;
   if (mode == 1) {
     if ((long)aux0 * aux1 != M) MD_FAIL(MD_ERR_SHAPE, "conv bench: H*W must equal M");
-    amode = A_CONV3; p.K = 9 * K; p.cH = aux0; p.cW = aux1; p.cC = K; p.zero_page = zp.p;
+    amode = A_CONV3; p.K = 9 * K; p.cH = aux0; p.cW = aux1; p.cC = K; p.zero_page = s.geom.zero_page;
   } else {
     p.K = K; p.lda = K;
   }
@@ -1973,8 +1921,7 @@ int parse_da3_cfg(const md_da3_cfg* c, Da3Cfg* out) {
   d.precision = c->precision;
   d.max_batch = c->max_batch > 0 ? c->max_batch : 1;
   d.ln_eps = c->ln_eps > 0.f ? c->ln_eps : 1e-6f;
-  if (d.precision != MD_PREC_BF16 && d.precision != MD_PREC_F32 && d.precision != MD_PREC_FP8 && d.precision != MD_PREC_F16 && d.precision != MD_PREC_F16X2)
-    MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", d.precision);
+  if (!token_op_prec(d.precision) && d.precision != MD_PREC_FP8) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", d.precision);
   *out = d;
   return MD_OK;
 }

@@ -210,7 +210,7 @@ inline int cpad(const md_model_s* m, int ch) { return (ch + m->ke - 1) / m->ke *
 // (a fork reads its ROOT's term count: a re-commit on the root may change it while the fork lives, and the packed rows the
 // fork's launches read are the root's)
 // What these helpers and the launch-parameter builders below read of a model, and ALL they read: the operand geometry of its
-// precision. The engines pass geom_of(model); md_op_decoder_gemm builds one for a precision alone.
+// precision. The engines pass geom_of(model); the stand-alone operator entries (md_api.cpp, OpStage) build one for a precision alone.
 struct OperandGeom {
   int ke = 64;      // contraction elements per 128-byte LDS row
   int xm = 1;       // planes per activation element (2: split-half)
@@ -261,7 +261,7 @@ inline int gemm_rows(Run& r, const char* name, const void* A, long lda, const in
 }
 
 // ConvTranspose2d k=2 s=2 as GEMM + pixel shuffle (encoder.rs:61-69, decoder.rs:100-105, mod.rs:81-84)
-// (the launch parameters apart from the launch: md_op_decoder_gemm launches the very same ones on a caller's buffers)
+// (the launch parameters apart from the launch: md_op_deconv2x2 / md_op_conv3x3 / md_op_decoder_gemm launch the very same ones)
 inline GemmParams deconv2_params(const OperandGeom& m, int B, const void* A, long lda, const int* idx, int h, int w, const void* W, int Cin_p,
                                  int Cout, const float* bias, void* out, long ldo, int coff, void* out2 = nullptr, int f = 2, int terms = 0) {
   GemmParams p;
