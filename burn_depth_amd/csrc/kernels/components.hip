@@ -31,14 +31,6 @@ namespace md {
 
 namespace {
 
-struct DeviceAtomics {  // components_math.h's policy on device memory: relaxed, agent scope (served by L2)
-  static __host__ __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  static __host__ __device__ __forceinline__ void store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  static __host__ __device__ __forceinline__ bool cas(int* p, int expected, int desired) {
-    return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-};
-
 struct ComponentsScratch {  // 256-byte aligned parts
   int* parent;  // [n] the union-find; after flatten the label of every row
   int* size;    // [n] valid faces of the component, at its root

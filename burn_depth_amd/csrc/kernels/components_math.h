@@ -63,4 +63,14 @@ MD_COMPONENTS_HD void components_hook(int* parent, int u, int v) {
   }
 }
 
+#if defined(__HIPCC__)
+struct DeviceAtomics {  // the policy on device memory (kernels/components.hip, kernels/clusters.hip): relaxed, agent scope (served by L2)
+  static MD_COMPONENTS_HD int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static MD_COMPONENTS_HD void store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static MD_COMPONENTS_HD bool cas(int* p, int expected, int desired) {
+    return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+#endif
+
 }  // namespace md

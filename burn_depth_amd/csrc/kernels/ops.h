@@ -284,6 +284,49 @@ constexpr int kPlaneCountChunk = 4;  // hypotheses of one trip of its loop: thei
 size_t planes_scratch_bytes(int n, int hypotheses);
 int launch_fit_planes(const PlanesParams& p, void* scratch, hipStream_t s);
 
+// ---- DBSCAN / Euclidean clustering (kernels/clusters.hip; md_op_cluster_points, md_infer_points_clusters) ----
+// A point list xyz [n,3] (+ conf, rgb, normals rows) -> the cluster of every row: the outlier removal's cell buckets with the
+// source row beside xyz (16-byte entries), count (core rows: at least k neighbours), union (a lock-free union-find over the core
+// rows, one hook per neighbour pair of core rows), flatten, border (a non-core row takes the smallest label among its core
+// neighbours), sizes, the size filter, dense ids by the ordered compaction, boxes by integer atomics on ordered keys. mode 1
+// then compacts the rows of kept clusters through launch_list_compact. Every pointer is a device pointer. Integers on an f32
+// predicate: nothing depends on the order of arrival.
+struct ClustersParams {
+  const float* xyz = nullptr;
+  const float* conf = nullptr;        // carried to conf_out
+  const uint8_t* rgb = nullptr;       // carried to rgb_out
+  const float* normals = nullptr;     // carried to normals_out
+  const int32_t* in_count = nullptr;  // as VoxelParams::in_count
+  int n = 0;                          // rows the launches cover: the live count is min(in_count[B], n)
+  int B = 1;
+  float radius = 0.f;
+  int k = 0, min_points = 1, max_points = 0, mode = 0;
+  int32_t* label = nullptr;         // [n]; null: skip
+  int32_t* cluster_size = nullptr;  // [n]; null: skip
+  int32_t* cluster = nullptr;       // [n]; null: skip
+  int32_t* table_label = nullptr;   // [table_capacity]; null: skip
+  int32_t* table_size = nullptr;    // [table_capacity]; null: skip
+  float* box = nullptr;             // [table_capacity,6]; null: skip
+  long table_capacity = 0;
+  int32_t* stats = nullptr;    // [4] clusters found, clusters kept, noise rows, rows in kept clusters; null: they live in the scratch
+  int32_t* dropped = nullptr;  // [1]; null: skip
+  float* xyz_out = nullptr;    // mode 1: the compacted rows
+  float* conf_out = nullptr;
+  uint8_t* rgb_out = nullptr;
+  float* normals_out = nullptr;
+  int32_t* index = nullptr;  // [capacity] source row
+  int32_t* count = nullptr;  // [B + 1] survivors per view, then their total
+  long capacity = 0;
+};
+constexpr int kClusterMaxNeighbours = 1 << 20;
+constexpr int kClusterStatsFlag = 8;  // clusters_flags(..)[8 .. 12): the four counters when `stats` is null
+// bytes of the scratch (table 20 B per slot | slot, bucket row, parent, size, rank, dense id of every row | buckets 16 n |
+// box keys 24 B per table row | ballot words | tile counts | tile offsets | flags)
+size_t clusters_scratch_bytes(int n, long table_capacity);
+// flags[0] != 0 after the launches = a probe loop ran out of table
+int launch_cluster_points(const ClustersParams& p, void* scratch, hipStream_t s);
+const int32_t* clusters_flags(const void* scratch, int n, long table_capacity);
+
 // ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
 // A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour
 // image: clear, splat (atomicMin of (bits(p.z) << 32) | row over the footprint), resolve. Every pointer is a device pointer.

@@ -19,7 +19,9 @@
 // the decimation writes the list and the faces the call ends with, the other two leave the list as it is.
 // md_op_fit_planes / md_infer_points_planes (kernels/planes.hip) label the rows of the list the call ends with by the planes a RANSAC
 // finds in it; with mode 1 / 2 the stage is the last one that writes a list.
-// The twelve md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
+// md_op_cluster_points / md_infer_points_clusters (kernels/clusters.hip) label the rows of the list the plane stage ends with by
+// their DBSCAN cluster; with mode 1 the stage is the last one that writes a list.
+// The thirteen md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
 // which holds the list the call ends with once (PointsPlan::fin, wired to the last list stage in plan_homes).
 #include <algorithm>
 #include <cfloat>
@@ -59,10 +61,14 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> stable;       // md_infer_points_smooth: the smoothing's scratch (smooth_scratch_bytes)
   md::GrowBuf<void> ptable;       // md_infer_points_planes: the plane extraction's scratch (planes_scratch_bytes)
   md::GrowBuf<void> plist;        // its input with mode 1 / 2 behind the thinning: the thinned list, laid out as vlist
+  md::GrowBuf<void> ktable;       // md_infer_points_clusters: the clustering's scratch (clusters_scratch_bytes)
+  md::GrowBuf<void> klist;        // its input with mode 1 behind a plane stage that cuts: that stage's list, laid out as vlist
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
   int outl_rows = 0;              // likewise for the outlier removal and otable
+  int clu_rows = 0;               // likewise for the clustering and ktable,
+  long clu_table = 0;             // with the table capacity its scratch was carved for
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
   float* f_home(int B) const { return cams.p + (size_t)B * 21; }
@@ -285,6 +291,40 @@ PlanesParams make_planes(const md_points_planes& f) {
   return q;
 }
 
+bool clusters_on(const md_points_clusters* q) { return q && q->radius != 0.f; }
+
+// model call: radius == 0 is the call without the stage and takes none of its outputs
+int check_clusters(const md_points_clusters* q, const md_points_outputs* out, bool op) {
+  if (!q) return MD_OK;
+  if (!std::isfinite(q->radius) || q->radius < 0.f || (op && q->radius == 0.f))
+    MD_FAIL(MD_ERR_INVALID_ARG, "radius = %g: must be finite and %s 0", (double)q->radius, op ? ">" : ">=");
+  if (q->radius == 0.f) {
+    if (q->label || q->cluster_size || q->cluster || q->table_label || q->table_size || q->box || q->stats || q->index || q->dropped)
+      MD_FAIL(MD_ERR_INVALID_ARG, "cluster outputs without a radius");
+    return MD_OK;
+  }
+  if (q->min_neighbours < 0 || q->min_neighbours > kClusterMaxNeighbours)
+    MD_FAIL(MD_ERR_INVALID_ARG, "min_neighbours %d outside 0..%d", q->min_neighbours, kClusterMaxNeighbours);
+  if (q->min_points < 1) MD_FAIL(MD_ERR_INVALID_ARG, "min_points = %d: must be >= 1", q->min_points);
+  if (q->max_points < 0 || (q->max_points > 0 && q->max_points < q->min_points))
+    MD_FAIL(MD_ERR_INVALID_ARG, "max_points = %d: 0 or >= min_points = %d", q->max_points, q->min_points);
+  if (q->mode < 0 || q->mode > 1) MD_FAIL(MD_ERR_INVALID_ARG, "mode = %d: 0 or 1", q->mode);
+  if (q->table_capacity < 0) MD_FAIL(MD_ERR_INVALID_ARG, "table_capacity = %lld is negative", (long long)q->table_capacity);
+  if (q->index && q->mode == 0) MD_FAIL(MD_ERR_INVALID_ARG, "index needs mode 1");
+  MD_TRY(need_count(q->index, out, "index"));
+  return MD_OK;
+}
+
+// the options and the outputs of the stage's own; the caller adds the rows
+ClustersParams make_clusters(const md_points_clusters& f) {
+  ClustersParams q;
+  q.radius = f.radius; q.k = f.min_neighbours; q.min_points = f.min_points; q.max_points = f.max_points; q.mode = f.mode;
+  q.label = f.label; q.cluster_size = f.cluster_size; q.cluster = f.cluster;
+  q.table_label = f.table_label; q.table_size = f.table_size; q.box = f.box; q.table_capacity = (long)f.table_capacity;
+  q.stats = f.stats; q.index = f.index; q.dropped = f.dropped;
+  return q;
+}
+
 bool outlier_on(const md_points_outlier* q) { return q && q->radius != 0.f; }
 
 // model call: radius == 0 is the call without outlier removal and takes none of its outputs. The operator's `neighbours` covers
@@ -452,6 +492,7 @@ struct OpScratch {
 const char kVoxelRanOut[] = "voxel thinning: the probe loop ran out of table slots";
 const char kOutlierRanOut[] = "outlier removal: a probe loop ran out of table slots";
 const char kDecimateRanOut[] = "decimation: a probe loop ran out of table slots";
+const char kClustersRanOut[] = "clustering: a probe loop ran out of table slots";
 
 // Every operator's last refusal and first act: the device, made current, and the stream its launches take.
 int op_begin(md_device_t dev, hipStream_t stream, hipStream_t* st) {
@@ -621,6 +662,25 @@ int op_fit_planes(md_device_t dev, const PointList& in, const md_points_planes* 
   return scratch.finish(launch_fit_planes(p, scratch.p, st));
 }
 
+int op_cluster_points(md_device_t dev, const PointList& in, const md_points_clusters* clu, const md_points_outputs* out, float* normals_out,
+                      hipStream_t stream) {
+  if (!clu) MD_FAIL(MD_ERR_INVALID_ARG, "cluster options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  MD_TRY(check_clusters(clu, out, true));
+  MD_TRY(check_list_op("clustering", in, out, normals_out));
+  if (clu->mode == 0 && (out->xyz || out->rgb || out->conf || normals_out)) MD_FAIL(MD_ERR_INVALID_ARG, "mode 0 writes no list: the compacted outputs need mode 1");
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
+  ClustersParams p = make_clusters(*clu);
+  p.xyz = in.xyz; p.conf = in.conf; p.rgb = in.rgb; p.normals = in.normals;
+  p.n = (int)in.N; p.B = 1;
+  p.xyz_out = out->xyz; p.conf_out = out->conf; p.rgb_out = out->rgb; p.normals_out = normals_out;
+  p.count = clu->mode ? out->count : nullptr; p.capacity = out->capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(clusters_scratch_bytes(p.n, p.table_capacity)));
+  return scratch.finish_flags(launch_cluster_points(p, scratch.p, st), clusters_flags(scratch.p, p.n, p.table_capacity), nullptr, kClustersRanOut);
+}
+
 int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
                      const md_points_outputs* out, float* normals_out, hipStream_t stream) {
   if (!dec) MD_FAIL(MD_ERR_INVALID_ARG, "decimation options are null");
@@ -764,6 +824,11 @@ int points_outlier_overflow(md_model_t m, int64_t* out) {
   return read_overflow(m, f && f->outl_rows && f->otable.p ? outlier_flags(f->otable.p, f->outl_rows) : nullptr, nullptr, out);
 }
 
+int points_clusters_overflow(md_model_t m, int64_t* out) {
+  const md_model_s::PointsState* f = m->points;
+  return read_overflow(m, f && f->clu_rows && f->ktable.p ? clusters_flags(f->ktable.p, f->clu_rows, f->clu_table) : nullptr, nullptr, out);
+}
+
 int points_decimate_overflow(md_model_t m, int64_t* out) {
   const md_model_s::PointsState* f = m->points;
   if (!f || !f->dec_views || !f->dtable.p) return read_overflow(m, nullptr, nullptr, out);
@@ -784,7 +849,7 @@ struct ListRows {
   int32_t* count = nullptr;  // [B + 1]
 };
 
-// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too), OutlierParams and PlanesParams
+// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too), OutlierParams, PlanesParams and ClustersParams
 template <typename P>
 void reads(P& p, const ListRows& l) { p.xyz = l.xyz; p.conf = l.conf; p.rgb = l.rgb; p.normals = l.normals; p.in_count = l.count; }
 template <typename P>
@@ -804,7 +869,8 @@ struct PointsPlan {
   hipStream_t st = nullptr;
   bool dual = false;
   bool thin = false, mesh = false, filt = false, deci = false, comp = false, smo = false, pln = false;  // the stages that are on
-  bool pcut = false;  // pln with mode 1 / 2: the plane stage is the last one that writes a list
+  bool pcut = false;  // pln with mode 1 / 2: the plane stage writes a list
+  bool clu = false, ccut = false;  // the clustering is on; with mode 1: it is the last stage that writes a list
   bool own_faces = false;  // deci / comp / smo: a later stage reads the faces, so the mesh stage writes the model's own (`gd`)
   size_t npx = 0;
   long rows = 0;  // rows the unthinned list of the call can have (list_rows); its mesh has at most 2 * rows faces
@@ -827,10 +893,13 @@ struct PointsPlan {
   ComponentsParams k;  // comp: launch_mesh_components', from the list's count and the faces `gd` wrote
   SmoothParams sm;     // smo: launch_smooth_mesh's, from `fin` and the faces of `k`, or else those `gd` wrote
   PlanesParams pn;     // pln: launch_fit_planes', from `fin` (mode 0) or the model's own list in front of it (pcut)
+  ClustersParams cn;   // clu: launch_cluster_points', from `fin` (mode 0) or the model's own list in front of it (ccut)
   int queue = 0;    // the raster's queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   int32_t unfiltered = 0;  // filt with host outputs: the rows of the unfiltered list, read back for outl->neighbours' slot
   int32_t plane_rows = 0;  // pcut with host outputs: the rows of the plane stage's input list, read back for pln->label's slot
+  int32_t cluster_rows = 0;  // ccut with host outputs: the rows of the clustering's input list, for the slots of its row outputs
+  int32_t clusters_kept = 0; // clu with host outputs: the kept clusters, for the slots of the table
   std::vector<OutSlot> slots;
 };
 
@@ -933,6 +1002,25 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     else slot(c.pln->label, pl.pn.label, 4, cap, n);
     slot(c.pln->index, pl.pn.index, 4, cap, n);
   }
+  if (pl.clu) {  // the row outputs as the plane stage's label; the table's rows that exist
+    const md_points_clusters& k = *c.clu;
+    const size_t tcap = (size_t)k.table_capacity;
+    slot(k.stats, pl.cn.stats, 4, 4);
+    slot(k.dropped, pl.cn.dropped, 4, 1);
+    if (pl.ccut) {
+      slot(k.label, pl.cn.label, 4, list, &pl.cluster_rows);
+      slot(k.cluster_size, pl.cn.cluster_size, 4, list, &pl.cluster_rows);
+      slot(k.cluster, pl.cn.cluster, 4, list, &pl.cluster_rows);
+    } else {
+      slot(k.label, pl.cn.label, 4, cap, n);
+      slot(k.cluster_size, pl.cn.cluster_size, 4, cap, n);
+      slot(k.cluster, pl.cn.cluster, 4, cap, n);
+    }
+    slot(k.index, pl.cn.index, 4, cap, n);
+    slot(k.table_label, pl.cn.table_label, 4, tcap, &pl.clusters_kept);
+    slot(k.table_size, pl.cn.table_size, 4, tcap, &pl.clusters_kept);
+    slot(k.box, pl.cn.box, 24, tcap, &pl.clusters_kept);
+  }
   if (pl.smo) {  // rows parallel to the list: they travel as its rows do
     slot(c.smooth->xyz, pl.sm.xyz_out, 12, cap, n);
     slot(c.smooth->normals, pl.sm.normals_out, 12, cap, n);
@@ -986,6 +1074,9 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.pln = planes_on(c.pln);  // the count is there: infer_points refuses the stage without it
   pl.pcut = pl.pln && c.pln->mode != 0;
   if (pl.pln) pl.pn = make_planes(*c.pln);
+  pl.clu = clusters_on(c.clu);
+  pl.ccut = pl.clu && c.clu->mode != 0;
+  if (pl.clu) pl.cn = make_clusters(*c.clu);
   if (c.rnd) {
     pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
@@ -1021,7 +1112,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     else if (pl.deci) ends_with(pl.d.faces_out, pl.d.face_count, c.dec->face_capacity);
     else ends_with(pl.g.faces, pl.g.face_count, c.mesh->face_capacity);
   }
-  const bool own_list = pl.thin || pl.filt || pl.deci || pl.pcut;  // the scatter fills a list of the model's own: a later stage writes `fin`
+  const bool own_list = pl.thin || pl.filt || pl.deci || pl.pcut || pl.ccut;  // the scatter fills a list of the model's own: a later stage writes `fin`
   auto scatter_to = [&](const ListRows& l) { p.xyz = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; pl.q.normals = l.normals; p.count = l.count; };
   if (!own_list) scatter_to(pl.fin);
   if (pl.comp || pl.smo) {  // all faces of the call's list go to the model's face home; the stages read them and the list's device count
@@ -1050,6 +1141,12 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, m->points->ptable, planes_scratch_bytes(f.n, f.hypotheses)));
     if (!pl.pcut) reads(f, pl.fin);  // mode 0: the rows of the call's list below its capacity
   }
+  if (pl.clu) {
+    ClustersParams& k = pl.cn;
+    k.B = B; k.n = (int)(pl.ccut ? rows : std::min<long>((long)out.capacity, rows));
+    MD_TRY(grow(m, st, m->points->ktable, clusters_scratch_bytes(k.n, k.table_capacity)));
+    if (!pl.ccut) reads(k, pl.fin);  // mode 0: the rows of the call's list below its capacity
+  }
   if (!own_list) return MD_OK;
   const bool want_rgb = out.rgb != nullptr, want_nrm = c.nrm && c.nrm->normals;
   const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = pl.dual ? align_up((size_t)rows * 4, 256) : 0;
@@ -1063,9 +1160,10 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(grow(m, st, f->vlist, b_list));
   if (pl.thin) MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
   if (pl.filt) MD_TRY(grow(m, st, f->otable, outlier_scratch_bytes((int)rows)));
-  if (pl.filt && (pl.thin || pl.pcut)) MD_TRY(grow(m, st, f->flist, b_list));
-  if (pl.thin && pl.pcut) MD_TRY(grow(m, st, f->plist, b_list));
-  // The chain scatter -> outlier removal -> voxel thinning -> plane extraction (mode 1 / 2), or scatter -> decimation (the decimation is the thinning, with the
+  if (pl.filt && (pl.thin || pl.pcut || pl.ccut)) MD_TRY(grow(m, st, f->flist, b_list));
+  if (pl.thin && (pl.pcut || pl.ccut)) MD_TRY(grow(m, st, f->plist, b_list));
+  if (pl.pcut && pl.ccut) MD_TRY(grow(m, st, f->klist, b_list));
+  // The chain scatter -> outlier removal -> voxel thinning -> plane extraction (mode 1 / 2) -> clustering (mode 1), or scatter -> decimation (the decimation is the thinning, with the
   // faces of the model's face home): every stage but the last writes a list of the model's own, of which every row is usable;
   // the last one writes `fin` below the caller's capacity. Nothing else knows which stage that is.
   ListRows l = rows_of(f->vlist.p);
@@ -1074,7 +1172,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.filt) {
     OutlierParams& u = pl.u;
     reads(u, l);
-    const bool last = !pl.thin && !pl.pcut;
+    const bool last = !pl.thin && !pl.pcut && !pl.ccut;
     if (!last) l = rows_of(f->flist.p);
     writes(u, last ? pl.fin : l);
     u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = last ? (long)out.capacity : rows;
@@ -1082,14 +1180,21 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.thin) {
     VoxelParams& v = pl.v;
     reads(v, l);
-    if (pl.pcut) l = rows_of(f->plist.p);
-    writes(v, pl.pcut ? l : pl.fin);
-    v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = pl.pcut ? rows : (long)out.capacity;
+    const bool last = !pl.pcut && !pl.ccut;
+    if (!last) l = rows_of(f->plist.p);
+    writes(v, last ? pl.fin : l);
+    v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = last ? (long)out.capacity : rows;
   }
   if (pl.pcut) {
     reads(pl.pn, l);
-    writes(pl.pn, pl.fin);
-    pl.pn.capacity = (long)out.capacity;
+    if (pl.ccut) l = rows_of(f->klist.p);
+    writes(pl.pn, pl.ccut ? l : pl.fin);
+    pl.pn.capacity = pl.ccut ? rows : (long)out.capacity;
+  }
+  if (pl.ccut) {
+    reads(pl.cn, l);
+    writes(pl.cn, pl.fin);
+    pl.cn.capacity = (long)out.capacity;
   }
   if (pl.deci) {
     DecimateParams& d = pl.d;
@@ -1228,6 +1333,13 @@ int run_smooth(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch
 // Plane extraction: the list of the call -> pln's outputs; with mode 1 / 2 the model's own list -> the list outputs of the call.
 int run_planes(md_model_s* m, const PointsCall&, PointsPlan& pl) { return launch_fit_planes(pl.pn, m->points->ptable.p, pl.st); }
 
+// Clustering: the list of the call -> clu's outputs; with mode 1 the model's own list -> the list outputs of the call.
+int run_clusters(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+  MD_TRY(launch_cluster_points(pl.cn, m->points->ktable.p, pl.st));
+  m->points->clu_rows = pl.cn.n; m->points->clu_table = pl.cn.table_capacity;  // only a launched run has flags to read (points_clusters_overflow)
+  return MD_OK;
+}
+
 // Rendering: the list the call ends with and its device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
@@ -1259,14 +1371,21 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
     if (!s.live) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
-  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0};
+  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0}, clu_overflow = 0;
   if (pl.deci) MD_TRY(d2h(&dec_overflow[0], voxel_flags(m->points->dtable.p, pl.d.v.n), 4));
   if (pl.deci) MD_TRY(d2h(&dec_overflow[1], decimate_flags(m->points->dtable.p, pl.d.v.n, pl.d.nf, pl.d.v.B), 4));
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
   if (pl.filt) MD_TRY(d2h(&outl_overflow, outlier_flags(m->points->otable.p, pl.u.n), 4));
   if (pl.filt) MD_TRY(d2h(&pl.unfiltered, pl.u.in_count + c.B, 4));
   if (pl.pcut) MD_TRY(d2h(&pl.plane_rows, pl.pn.in_count + c.B, 4));
+  if (pl.clu) {
+    const int32_t* flags = clusters_flags(m->points->ktable.p, pl.cn.n, pl.cn.table_capacity);
+    MD_TRY(d2h(&clu_overflow, flags, 4));
+    MD_TRY(d2h(&pl.clusters_kept, (pl.cn.stats ? pl.cn.stats : flags + kClusterStatsFlag) + 1, 4));
+    if (pl.ccut) MD_TRY(d2h(&pl.cluster_rows, pl.cn.in_count + c.B, 4));
+  }
   MD_HIP(hipStreamSynchronize(pl.st));
+  if (clu_overflow) MD_FAIL(MD_ERR_HIP, "%s", kClustersRanOut);
   if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "%s", kDecimateRanOut);
   if (outl_overflow) MD_FAIL(MD_ERR_HIP, "%s", kOutlierRanOut);
   if (overflow) MD_FAIL(MD_ERR_HIP, "%s", kVoxelRanOut);
@@ -1301,6 +1420,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, long rows, hipSt
   if (pl.comp) MD_TRY(timed("points_components", run_components));
   if (pl.smo) MD_TRY(timed("points_smooth", run_smooth));
   if (pl.pln) MD_TRY(timed("points_planes", run_planes));
+  if (pl.clu) MD_TRY(timed("points_clusters", run_clusters));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
   return copy_outputs(m, c, pl);
@@ -1346,6 +1466,11 @@ std::vector<uintptr_t> points_graph_key(md_model_t m, const PointsCall& c, hipSt
     const md_points_planes& f = *c.pln;
     key_add(key, 0x504c414eu, f.planes, f.hypotheses, f.tol, f.min_inliers, f.seed, f.normal_min_cos, f.axis[0], f.axis[1], f.axis[2], f.axis_min_cos, f.mode);
     key_add(key, f.plane, f.plane_count, f.hypothesis, f.label, f.index, f.dropped);
+  }
+  if (clusters_on(c.clu)) {
+    const md_points_clusters& k = *c.clu;
+    key_add(key, 0x434c5553u, k.radius, k.min_neighbours, k.min_points, k.max_points, k.mode, k.table_capacity);
+    key_add(key, k.label, k.cluster_size, k.cluster, k.table_label, k.table_size, k.box, k.stats, k.index, k.dropped);
   }
   if (mesh_on(c.mesh))  // every output null: the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
@@ -1431,6 +1556,22 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
       if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "plane extraction together with decimation: the rows are renumbered; md_op_fit_planes serves the decimated list");
     }
     if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "plane extraction takes fewer than 2^30 rows, the list may have %ld", rows);
+  }
+  MD_TRY(check_clusters(c.clu, out, false));
+  if (clusters_on(c.clu)) {
+    if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "clustering needs the list's `count`");
+    if (c.clu->mode != 0) {
+      if (mesh_on(c.mesh) || decimate_on(c.dec) || components_on(c.comp) || smooth_on(c.smooth))
+        MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 together with a mesh stage: the rows the faces name would vanish");
+      if ((voxel_on(c.vox) && (c.vox->index || c.vox->weight)) || (outlier_on(c.outl) && c.outl->index) || (planes_on(c.pln) && c.pln->index))
+        MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 together with index / weight of an earlier stage: the rows they are parallel to are not returned");
+      if (planes_on(c.pln) && c.pln->mode == 0)
+        MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 behind plane extraction with mode 0: the rows its label is parallel to are not returned");
+    } else {
+      if (!out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 0 needs the list output `xyz`");
+      if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "clustering together with decimation: the rows are renumbered; md_op_cluster_points serves the decimated list");
+    }
+    if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "clustering takes fewer than 2^30 rows, the list may have %ld", rows);
   }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, points
 from .config import DepthProConfig, InterpolationMethod, Precision
-from .points import FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
+from .points import FittedPlanes, PointCloud, PointClusters, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
 
 
 class Device:
@@ -462,7 +462,8 @@ class DepthPro:
                      conf_percentile: int = 0, view_rtol: float = 0.0, min_views: int = 0, normals: bool = False,
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
                      raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
-                     components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None, **opts) -> PointCloud:
+                     components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None, clusters: Optional[dict] = None,
+                     **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
@@ -510,7 +511,14 @@ class DepthPro:
         list behind every other list stage; the equations, the inlier counts and the label of every row come back as `planes`
         (`FittedPlanes`). mode "drop" / "keep": the list the call returns (and render= sees) holds the rows without / of a plane
         and `index` names their rows in the list in front of the stage; not with mesh=. normal_min_cos > 0 needs normals=True.
-        planes 0 or None: the call without it."""
+        planes 0 or None: the call without it.
+        clusters (`md_points_clusters`, the one form that runs through `md_infer_points_clusters`): dict(radius=, min_neighbours=0,
+        min_points=1, max_points=0, mode="label", table=256): DBSCAN (min_neighbours 0: Euclidean cluster extraction) of the list
+        the plane stage ends with, so planes=dict(mode="drop") followed by clusters= labels what is not on a plane; the labels,
+        sizes, dense ids, the table of kept clusters with their boxes and the counters come back as `clusters` (`PointClusters`).
+        mode "keep": the list the call returns (and render= sees) holds the rows of kept clusters and `index` names their rows in
+        the list in front of the stage; not with mesh=, and behind planes= only with its mode "drop" / "keep". radius 0 or None:
+        the call without it."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -523,8 +531,11 @@ class DepthPro:
             intrinsics=intrinsics, extrinsics=extrinsics, focal_px=f_px, dense=dense, compact=compact, capacity=capacity, out=out,
             conf_percentile=conf_percentile, view_rtol=view_rtol, min_views=min_views, normals=normals, normal_min_cos=normal_min_cos,
             voxel=voxel, render=render, mesh=mesh, raster=raster, outlier=outlier, decimate=decimate, components=components,
-            smooth=smooth, planes=planes, opts=opts)
-        entry, parts = (self._lib.md_infer_points_planes, rq.planes_args()) if rq.pln is not None else (self._lib.md_infer_points_smooth, rq.args())
+            smooth=smooth, planes=planes, clusters=clusters, opts=opts)
+        if rq.clu is not None:
+            entry, parts = self._lib.md_infer_points_clusters, rq.clusters_args()
+        else:
+            entry, parts = (self._lib.md_infer_points_planes, rq.planes_args()) if rq.pln is not None else (self._lib.md_infer_points_smooth, rq.args())
         _lib.check(entry(self._h, C.c_void_p(x.data_ptr()), B, H, W, _lib.MD_MEM_DEVICE,
                          C.c_void_p(rgb.data_ptr()) if rgb is not None else None, *parts, _lib.MD_MEM_DEVICE, _stream_ptr(self.device.ordinal)))
         return rq.cloud

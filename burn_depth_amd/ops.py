@@ -9,7 +9,8 @@ import torch
 
 from . import _lib
 from .depth_pro import Device, _stream_ptr
-from .points import (FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _f32, _i32, _lattice, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
+from .points import (FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _cluster_mode_of, _clusters_struct, _f32, _i32, _lattice,
+                     _new_clusters, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
                      _raster_request, _render_request, _u8, _view_filter_opts)
 
 
@@ -710,6 +711,32 @@ def fit_planes(dev: Device, xyz: torch.Tensor, planes: int = 1, hypotheses: int 
     pln = _planes_struct(opts, out.planes, out.index)
     _lib.check(_lib.load().md_op_fit_planes(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(pln), C.byref(outs),
                                             _p(out.normals) if cut else None, _stream_ptr(dev.ordinal)))
+    return out
+
+
+def cluster_points(dev: Device, xyz: torch.Tensor, radius: float, min_neighbours: int = 0, min_points: int = 1, max_points: int = 0, mode=0,
+                   table: Optional[int] = None, conf: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None,
+                   normals: Optional[torch.Tensor] = None, out: Optional[PointCloud] = None, capacity: Optional[int] = None) -> PointCloud:
+    """md_op_cluster_points: a point list xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) -> `PointCloud` whose `clusters`
+    (`PointClusters`) holds the DBSCAN clusters of the rows (min_neighbours 0: Euclidean cluster extraction): label, cluster_size
+    and cluster int32 [N], the table of kept clusters (table rows, default N; the first min(stats[1], table) are written), stats
+    int32 [4] and dropped int32 [1]. mode "label" / 0: nothing else. "keep" / 1: also the rows of kept clusters in input order,
+    xyz / conf / rgb / normals [capacity, ..], index int32 [capacity] and count int32 [2]; capacity defaults to N. `out`: a
+    PointCloud of an earlier call to write into again. Bit-identical to `pipeline.cluster_points`."""
+    xyz, _, conf, rgb, normals, N, _ = _list_inputs(xyz, None, conf, rgb, normals)
+    opts = dict(radius=radius, min_neighbours=min_neighbours, min_points=min_points, max_points=max_points, mode=mode)
+    if table is not None:
+        opts["table"] = table
+    cut = _cluster_mode_of(mode) != 0
+    cap = N if capacity is None else int(capacity)
+    fresh = out is None
+    out, outs = _list_outputs(out, xyz.device, cap, conf, rgb, normals, vertex=cut)
+    if fresh:
+        out.clusters = _new_clusters(xyz.device, N, N if table is None else table)
+    assert out.clusters is not None and (out.clusters.label is None or int(out.clusters.label.shape[0]) >= N), "label covers the input rows"
+    clu = _clusters_struct(opts, out.clusters, out.index)
+    _lib.check(_lib.load().md_op_cluster_points(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(clu), C.byref(outs),
+                                                _p(out.normals) if cut else None, _stream_ptr(dev.ordinal)))
     return out
 
 

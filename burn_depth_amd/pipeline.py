@@ -1003,6 +1003,160 @@ class HostRender:
     filled: np.ndarray               # int32 [T+1]: filled pixels per target, then their total
 
 
+@dataclass
+class HostClusters:
+    label: np.ndarray                # int32 [N] over the input rows: the smallest core row of the row's cluster, -1 noise, -2 dropped
+    cluster_size: np.ndarray         # int32 [N]: core + border rows of the row's cluster, 0 for noise and dropped rows
+    cluster: np.ndarray              # int32 [N]: the dense id of a kept cluster, -1 every other in-range row, -2 dropped
+    table_label: np.ndarray          # int32 [min(C, table)]: the label of every kept cluster, ascending
+    table_size: np.ndarray           # int32 [min(C, table)]
+    box: np.ndarray                  # f32 [min(C, table),6]: min xyz, max xyz over the cluster's rows (-0 below +0)
+    stats: np.ndarray                # int32 [4]: clusters found, clusters kept, noise rows, rows in kept clusters
+    dropped: int                     # rows that are not finite or outside the grid
+    xyz: Optional[np.ndarray]        # mode 1: f32 [M,3] the rows of kept clusters, in ascending input row; None with mode 0
+    conf: Optional[np.ndarray]       # f32 [M]
+    rgb: Optional[np.ndarray]        # uint8 [M,3]
+    normals: Optional[np.ndarray]    # f32 [M,3]
+    index: Optional[np.ndarray]      # int32 [M]: the source row
+    count: Optional[np.ndarray]      # int32 [B+1]: survivors per view, then their total
+
+
+def _neighbour_pairs(ks, cells, ps, r2):
+    """The neighbour pairs of the in-range points sorted by cell key (ks keys, cells biased cells, ps positions), as a stream of
+    (i, j) index arrays into that order, every ordered pair once: the 27 shifted lookups of `radius_outliers`, each bucket walked
+    to its end."""
+    for d in np.ndindex(3, 3, 3):
+        q = cells + (np.array(d, np.int64) - 1)
+        inside = ((q >= 0) & (q < (1 << 21))).all(1)  # a key with a coordinate outside the grid is skipped
+        qk = (q[:, 0] << 42) | (q[:, 1] << 21) | q[:, 2]
+        lo = np.searchsorted(ks, qk, side="left")
+        hi = np.where(inside, np.searchsorted(ks, qk, side="right"), lo)
+        live = np.nonzero(lo < hi)[0]
+        at = lo[live]
+        while len(live):  # step t of every bucket walk at once
+            with np.errstate(all="ignore"):
+                dx, dy, dz = (ps[at, a] - ps[live, a] for a in range(3))
+                d2 = (dx * dx + dy * dy) + dz * dz
+                hit = (d2 <= r2) & (at != live)  # the row's own entry, by position: duplicates are neighbours
+            yield live[hit], at[hit]
+            at = at + 1
+            go = at < hi[live]
+            live, at = live[go], at[go]
+
+
+def _ordered_keys(v: np.ndarray) -> np.ndarray:
+    """The usual ordered key of an f32: the unsigned order of the keys is the numeric order of the floats, -0 below +0."""
+    b = np.ascontiguousarray(v, np.float32).view(np.uint32)
+    return np.where(b & np.uint32(0x80000000), ~b, b ^ np.uint32(0x80000000))
+
+
+def cluster_points(xyz, radius, min_neighbours=0, min_points=1, max_points=0, mode=0, table=None, conf=None, rgb=None, normals=None,
+                   counts=None) -> HostClusters:
+    """The host reference of md_op_cluster_points / md_infer_points_clusters (include/mi_depth.h states the contract): DBSCAN on
+    the neighbour relation of `radius_outliers` (the 27 cells of side `radius` around a row's own AND d2 <= radius*radius in f32).
+    A core row has at least min_neighbours neighbours; a cluster is a connected component of the core rows and is named by its
+    smallest core row; a non-core row with a core neighbour takes the smallest label among them; the rest is noise (-1); rows
+    that are not finite or outside the grid are dropped (-2). Kept clusters (min_points <= size, and size <= max_points unless
+    that is 0) get dense ids in ascending label. mode 1 also returns the rows of kept clusters in input order. table: rows of
+    the cluster table (default: all). The device kernels (kernels/clusters.hip) give the same bits. A sort by cell key for the
+    pairs, labels by min-propagation with pointer jumping. counts: the rows of every view of the input, [B] (default: one view)."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    N = len(p)
+    rs = np.float32(radius)
+    k = int(min_neighbours)
+    if not np.isfinite(rs) or not rs > 0:
+        raise ValueError("radius must be finite and > 0")
+    if k != min_neighbours or k < 0 or k > 1 << 20:
+        raise ValueError("min_neighbours must be an integer in 0 .. 2^20")
+    if int(min_points) != min_points or min_points < 1:
+        raise ValueError("min_points must be an integer >= 1")
+    if int(max_points) != max_points or max_points < 0 or 0 < max_points < min_points:
+        raise ValueError("max_points must be 0 or an integer >= min_points")
+    if mode not in (0, 1):
+        raise ValueError("mode is 0 or 1")
+    if table is not None and table < 0:
+        raise ValueError("a negative table capacity")
+    if N >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows")
+    half = np.float32(1 << 20)
+    with np.errstate(all="ignore"):
+        c = np.floor(p / rs)
+        ok = np.isfinite(p).all(1) & (c >= -half).all(1) & (c < half).all(1)
+    cell = c[ok].astype(np.int64) + (1 << 20)  # biased: 0 .. 2^21 - 1 on every axis
+    key = (cell[:, 0] << 42) | (cell[:, 1] << 21) | cell[:, 2]
+    order = np.argsort(key, kind="stable")
+    row = np.nonzero(ok)[0][order]  # the input row of every sorted point
+    ks, cells, ps = key[order], cell[order], p[ok][order]
+    r2 = rs * rs
+    M = len(ks)
+    core = np.ones(M, bool)
+    if k > 0:
+        found = np.zeros(M, np.int64)
+        for i, _ in _neighbour_pairs(ks, cells, ps, r2):
+            found += np.bincount(i, minlength=M)
+        core = found >= k
+    ei, ej = [], []  # the edges of the core graph, each once, in input rows
+    for i, j in _neighbour_pairs(ks, cells, ps, r2):
+        e = core[i] & core[j] & (row[j] < row[i])
+        ei.append(row[i[e]])
+        ej.append(row[j[e]])
+    ei, ej = (np.concatenate(a) if a else np.zeros(0, np.int64) for a in (ei, ej))
+    lab = np.arange(N, dtype=np.int64)  # over the input rows; only core rows are read
+    while True:
+        before = lab.copy()
+        np.minimum.at(lab, ei, lab[ej])
+        np.minimum.at(lab, ej, lab[ei])
+        while True:  # pointer jumping: every row to the label of its label
+            nxt = lab[lab]
+            if (nxt == lab).all():
+                break
+            lab = nxt
+        if (lab == before).all():
+            break
+    label = np.full(N, -2, np.int64)
+    label[row] = np.where(core, lab[row], -1)
+    if k > 0:
+        best = np.full(M, N, np.int64)
+        for i, j in _neighbour_pairs(ks, cells, ps, r2):
+            e = ~core[i] & core[j]
+            np.minimum.at(best, i[e], lab[row[j[e]]])
+        border = ~core & (best < N)
+        label[row[border]] = best[border]
+    size_at = np.bincount(label[label >= 0], minlength=N) if N else np.zeros(0, np.int64)
+    cluster_size = np.where(label >= 0, size_at[np.maximum(label, 0)], 0)
+    kept_row = (cluster_size >= min_points) & ((max_points == 0) | (cluster_size <= max_points))
+    roots = np.nonzero(label == np.arange(N))[0]
+    kept_roots = roots[kept_row[roots]]  # ascending label
+    dense = np.full(N, -1, np.int64)
+    dense[kept_roots] = np.arange(len(kept_roots))
+    cluster = np.where(label >= 0, np.where(kept_row, dense[np.maximum(label, 0)], -1), np.where(label == -2, -2, -1))
+    stats = np.array([len(roots), len(kept_roots), (label == -1).sum(), kept_row.sum()], np.int32)
+    T = len(kept_roots) if table is None else min(int(table), len(kept_roots))
+    lo = np.full((T, 3), 0xFFFFFFFF, np.uint32)
+    hi = np.zeros((T, 3), np.uint32)
+    boxed = np.nonzero((cluster >= 0) & (cluster < T))[0]
+    keys = _ordered_keys(p[boxed])
+    for a in range(3):
+        np.minimum.at(lo[:, a], cluster[boxed], keys[:, a])
+        np.maximum.at(hi[:, a], cluster[boxed], keys[:, a])
+    bk = np.concatenate([lo, hi], 1)
+    box = np.where(bk & np.uint32(0x80000000), bk ^ np.uint32(0x80000000), ~bk).astype(np.uint32).view(np.float32)
+    out = HostClusters(label.astype(np.int32), cluster_size.astype(np.int32), cluster.astype(np.int32), kept_roots[:T].astype(np.int32),
+                       size_at[kept_roots[:T]].astype(np.int32), box, stats, int(N - ok.sum()), None, None, None, None, None, None)
+    if mode == 0:
+        return out
+    index = np.nonzero(cluster >= 0)[0].astype(np.int32)
+    if counts is None:
+        bounds = np.array([0, N], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64).reshape(-1))]), N)
+    per_view = np.diff(np.searchsorted(index, bounds, side="left"))
+    take = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)[index]  # noqa: E731
+    out.xyz, out.conf, out.rgb, out.normals = p[index], take(conf, np.float32, (N,)), take(rgb, np.uint8, (N, 3)), take(normals, np.float32, (N, 3))
+    out.index, out.count = index, np.concatenate([per_view, [len(index)]]).astype(np.int32)
+    return out
+
+
 def render_points(xyz, H, W, intrinsics=None, extrinsics=None, focal_px=None, rgb=None, count=None, *, pixel_offset=0.0, z_near=0.0,
                   z_far=0.0, radius=0) -> HostRender:
     """The host reference of md_op_render_points / md_infer_points_render (include/mi_depth.h states the contract): the list xyz
@@ -1421,7 +1575,7 @@ class AnyDepthModel:
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
         render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`), outlier=
         (`md_infer_points_outlier`), decimate= (`md_infer_points_decimate`), components= (`md_infer_points_components`) and
-        smooth= (`md_infer_points_smooth`) and planes= (`md_infer_points_planes`) included."""
+        smooth= (`md_infer_points_smooth`), planes= (`md_infer_points_planes`) and clusters= (`md_infer_points_clusters`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

@@ -63,6 +63,23 @@ class FittedPlanes:
 
 
 @dataclass
+class PointClusters:
+    """What `md_op_cluster_points` / `md_infer_points_clusters` return (include/mi_depth.h). Device tensors: label, cluster_size and
+    cluster int32 [rows of the input list] (the smallest core row of the row's cluster, -1 noise, -2 dropped; the rows of that
+    cluster; the dense id of a kept cluster, else -1 / -2), table_label / table_size int32 [table] and box f32 [table,6] (min xyz,
+    max xyz) of the kept clusters in ascending label, of which the first min(stats[1], table) are written, stats int32 [4]
+    (clusters found, clusters kept, noise rows, rows in kept clusters), dropped int32 [1]."""
+    label: Optional[torch.Tensor] = None
+    cluster_size: Optional[torch.Tensor] = None
+    cluster: Optional[torch.Tensor] = None
+    table_label: Optional[torch.Tensor] = None
+    table_size: Optional[torch.Tensor] = None
+    box: Optional[torch.Tensor] = None
+    stats: Optional[torch.Tensor] = None
+    dropped: Optional[torch.Tensor] = None
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -88,7 +105,9 @@ class PointCloud:
     index and remap. With `smooth=` (`md_infer_points_smooth`): smooth = the `SmoothedMesh` of the list over the faces the
     rasteriser reads; the list itself is unchanged. With `planes=` (`md_op_fit_planes` / `md_infer_points_planes`): planes = the
     `FittedPlanes` of the list; with its mode "drop" / "keep" the list holds the rows without / of a plane and index is the
-    source row of every output row in the list in front of the stage. None when not asked for."""
+    source row of every output row in the list in front of the stage. With `clusters=` (`md_op_cluster_points` /
+    `md_infer_points_clusters`): clusters = the `PointClusters` of the list the plane stage ends with; with its mode "keep" the
+    list holds the rows of kept clusters and index is their source row likewise. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -115,6 +134,7 @@ class PointCloud:
     component_stats: Optional[torch.Tensor] = None
     smooth: Optional["SmoothedMesh"] = None
     planes: Optional["FittedPlanes"] = None
+    clusters: Optional["PointClusters"] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -371,6 +391,67 @@ def _points_planes(dev, rows: int, planes: dict, out: PointCloud, fresh: bool):
     return _planes_struct(planes, out.planes, out.index)
 
 
+CLUSTER_MODES = {"label": 0, "keep": 1}
+_CLUSTER_KEYWORDS = {"radius", "min_neighbours", "min_points", "max_points", "mode", "table"}
+CLUSTER_TABLE_DEFAULT = 256
+
+
+def _cluster_mode_of(mode) -> int:
+    """0 label, 1 keep, by name or number; 0 also for a name the builder will refuse."""
+    return CLUSTER_MODES.get(mode, 0) if isinstance(mode, str) else int(mode)
+
+
+def _cluster_mode(clusters: Optional[dict]) -> int:
+    """The mode of a clusters= request; 0 for one that is off."""
+    return _cluster_mode_of(clusters.get("mode", 0)) if clusters and clusters.get("radius") else 0
+
+
+def _new_clusters(dev, rows: int, table: int) -> "PointClusters":
+    """Fresh tensors for a list of `rows` rows and a table of `table` rows."""
+    table = max(int(table), 0)
+    return PointClusters(label=_i32(dev, rows), cluster_size=_i32(dev, rows), cluster=_i32(dev, rows), table_label=_i32(dev, table),
+                         table_size=_i32(dev, table), box=_f32(dev, table, 6), stats=_i32(dev, 4), dropped=_i32(dev, 1))
+
+
+def _clusters_struct(clusters: dict, found: "PointClusters", index: Optional[torch.Tensor]) -> "_lib.MdPointsClusters":
+    """md_points_clusters of the keywords radius=, min_neighbours= (k), min_points=, max_points=, mode= ("label" / "keep" or 0 / 1),
+    table= (rows of the cluster table) writing into `found` and `index`. The ranges are the library's to refuse."""
+    unknown = set(clusters) - _CLUSTER_KEYWORDS
+    if unknown or "radius" not in clusters:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"clusters= takes {sorted(_CLUSTER_KEYWORDS)} and needs radius; unknown {sorted(unknown)}")
+    mode = clusters.get("mode", 0)
+    if isinstance(mode, str):
+        if mode not in CLUSTER_MODES:
+            raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"cluster mode {mode!r}: one of {sorted(CLUSTER_MODES)}")
+        mode = CLUSTER_MODES[mode]
+    held, table = (int(found.table_label.shape[0]) if found.table_label is not None else None), clusters.get("table")
+    if table is None:
+        table = CLUSTER_TABLE_DEFAULT if held is None else held
+    elif table >= 0 and held is not None:  # a negative one is the library's to refuse
+        table = min(int(table), held)
+    return _lib.MdPointsClusters(float(clusters["radius"]), int(clusters.get("min_neighbours", 0)), int(clusters.get("min_points", 1)),
+                                 int(clusters.get("max_points", 0)), int(mode), _ptr(found.label), _ptr(found.cluster_size), _ptr(found.cluster),
+                                 _ptr(found.table_label), _ptr(found.table_size), _ptr(found.box), int(table), _ptr(found.stats),
+                                 _ptr(index) if mode else None, _ptr(found.dropped))
+
+
+def _points_clusters(dev, rows: int, clusters: dict, out: PointCloud, fresh: bool):
+    """md_points_clusters for `out` with the stage on. rows: the rows the list in front of the stage can have. With `fresh` the
+    tensors of `out.clusters` are created, the row outputs over the rows of the list the stage reads (the list of the call, or
+    with mode "keep" the one in front of it) and, with that mode, index beside the list; otherwise the ones `out` carries are
+    written again."""
+    if out.xyz is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "clusters= needs the compacted list")
+    cut = _cluster_mode(clusters) != 0
+    if fresh or out.clusters is None:
+        cap = int(out.xyz.shape[0])
+        table = clusters.get("table")
+        out.clusters = _new_clusters(dev, rows if cut else cap, CLUSTER_TABLE_DEFAULT if table is None else table)
+        if cut:
+            out.index = _i32(dev, cap)
+    return _clusters_struct(clusters, out.clusters, out.index)
+
+
 def _target_cameras(dev, intrinsics, extrinsics, focal_px):
     """The target cameras of a rendering or a rasterisation -> (T, md_points_cameras, keep-alive). T is the number of cameras given."""
     src = intrinsics if intrinsics is not None else focal_px
@@ -423,10 +504,15 @@ class PointsRequest(NamedTuple):
     smo: Optional["_lib.MdPointsSmooth"]
     keep: list
     pln: Optional["_lib.MdPointsPlanes"] = None  # behind `keep`: `md_infer_points_planes` takes it behind `args()`
+    clu: Optional["_lib.MdPointsClusters"] = None  # `md_infer_points_clusters` takes it behind `planes_args()`
 
     def args(self) -> list:
         """The struct arguments of `md_infer_points_smooth`, by reference, NULL for the parts not asked for."""
         return [C.byref(s) if s is not None else None for s in self[1:14]]
+
+    def clusters_args(self) -> list:
+        """The struct arguments of `md_infer_points_clusters`: those of `planes_args()`, then the cluster part."""
+        return self.planes_args() + [C.byref(self.clu) if self.clu is not None else None]
 
     def planes_args(self) -> list:
         """The struct arguments of `md_infer_points_planes`: those of `args()`, then the plane part."""
@@ -439,7 +525,7 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
                     normals: bool = False, normal_min_cos: float = 0.0, voxel: Optional[float] = None, render: Optional[dict] = None,
                     mesh=None, raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
                     components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None,
-                    opts: Optional[dict] = None) -> PointsRequest:
+                    clusters: Optional[dict] = None, opts: Optional[dict] = None) -> PointsRequest:
     """The keyword set of `infer_points` / `ops.unproject` (their docstrings say what each means) as a `PointsRequest`. opts: the
     fields of `md_points_opts`; want_rgb / want_conf / want_depth: the call can fill those outputs. A part is None when it was
     not asked for, by keyword or by an `out` that carries its tensors; fresh tensors are allocated unless `out` is given.
@@ -453,8 +539,9 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     o = _points_opts(**(opts or {}))
     res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
     cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
-    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = None
-    cut = _plane_mode(planes) != 0  # the plane stage writes the list: index is its own, an earlier stage's is not returned
+    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = None
+    keep_rows = _cluster_mode(clusters) != 0  # the clustering writes the list: index is its own
+    cut = _plane_mode(planes) != 0 or keep_rows  # a later stage writes the list: an earlier stage's index is not returned
     if conf_percentile or view_rtol or min_views:
         fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
     if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
@@ -501,6 +588,12 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
         smo = _lib.MdPointsSmooth()
     if planes and planes.get("planes", 1):
         pln = _points_planes(dev, _lattice(B, H, W, o.stride)[1], planes, res, fresh)
+        if keep_rows:
+            pln.index = None
     elif planes is not None:
         pln = _lib.MdPointsPlanes()
-    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln)
+    if clusters and clusters.get("radius"):
+        clu = _points_clusters(dev, _lattice(B, H, W, o.stride)[1], clusters, res, fresh)
+    elif clusters is not None:
+        clu = _lib.MdPointsClusters()
+    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu)

@@ -1043,6 +1043,91 @@ int md_infer_points_planes(md_model_t m, const float* nchw, int B, int H, int W,
                            const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
                            int out_kind, void* stream);
 
+/* ---- point path: DBSCAN / Euclidean clustering of a point list ---------------------------------------------------------------
+ * A list xyz f32 [N,3] with optional parallel rows conf f32 [N], rgb u8 [N,3] and normals f32 [N,3] -> the cluster of every row,
+ * a table of the clusters and, with mode 1, the rows of the kept clusters. Every output is integers on a deterministic f32
+ * predicate (or a selection among the input coordinates), so nothing depends on the order in which threads arrive;
+ * pipeline.cluster_points restates it in numpy bit for bit. f32, one rounded operation per step, no fused multiply-add.
+ * Denormals are outside the contract.
+ *   cells and neighbours: the outlier removal's (md_points_outlier above), word for word: cell c_a = floorf(p_a / radius), the
+ *     same range test and 63-bit key; rows out of range or not finite get label -2 and are counted in `dropped`; in-range rows
+ *     i != j are neighbours when their cells differ by at most 1 on every axis AND (dx*dx + dy*dy) + dz*dz <= radius*radius,
+ *     inclusive. The cell condition is part of the definition. Rows with equal coordinates are neighbours of each other.
+ *   core rows: k = min_neighbours, 0 <= k <= 2^20. An in-range row is a core row when it has at least k neighbours (the count
+ *     saturates at k). k = 0: every in-range row is a core row and the stage is plain Euclidean cluster extraction.
+ *   clusters: the connected components of the graph whose vertices are the core rows and whose edges are the neighbour pairs of
+ *     core rows. The label of a cluster is its smallest core row.
+ *   border rows: an in-range row that is not core but has a core neighbour takes the smallest label among its core neighbours'
+ *     clusters: a fixed rule, where textbook DBSCAN depends on the order of the visit. A border row never joins two clusters.
+ *   noise: an in-range row that is neither gets label -1.
+ *   sizes: the size of a cluster is its core rows plus its border rows. A cluster is kept when min_points <= size and
+ *     (max_points == 0 or size <= max_points), min_points >= 1. Kept clusters get the dense ids 0 .. C-1 in ascending label.
+ *   label / cluster_size / cluster, int32 over the INPUT rows [N]: the label before the size filter; the size of the row's cluster
+ *     (0 for noise and dropped rows); the dense id of a kept cluster, -1 for every other in-range row, -2 for a dropped row.
+ *   the table, `table_capacity` rows: table_label, table_size, and box f32 [6] = min x y z, max x y z over the cluster's rows,
+ *     under the total order of the usual ordered key of an f32 (bits ^ 0x80000000 for a clear sign bit, ~bits for a set one:
+ *     -0 lies below +0); each value is the bit pattern of an input coordinate. Ids at or beyond table_capacity are not written
+ *     and the memory behind the clusters that exist stays untouched.
+ *   stats int32 [4]: clusters found, clusters kept, noise rows, rows in kept clusters: true counts whatever the capacities.
+ *   mode 0: labels only. mode 1 keeps the rows of kept clusters: the survivors in ascending input row, every given row copied
+ *     unchanged, index = the source row; count[b] = the survivors of view b, count[B] = their total M, also when M exceeds
+ *     `capacity`: then only the first `capacity` rows are written and the memory behind them stays untouched. All views of a
+ *     call share the grid and the clusters. N < 2^30.
+ * The grid is the outlier removal's with 16-byte bucket entries (xyz and the source row); the labelling is the lock-free
+ * union-find of the mesh components (parent[v] <= v: the root of a finished tree is its smallest row). */
+typedef struct md_points_clusters {
+  float radius;           /* 0 = the stage is off (md_infer_points_clusters), finite and >= 0 */
+  int32_t min_neighbours; /* k, 0 .. 2^20 */
+  int32_t min_points;     /* >= 1 */
+  int32_t max_points;     /* 0 = no upper limit, else >= min_points */
+  int32_t mode;           /* 0 = label only, 1 = keep the rows of kept clusters */
+  int32_t* label;         /* int32 [N] over the INPUT rows. NULL = skip */
+  int32_t* cluster_size;  /* int32 [N]. NULL = skip */
+  int32_t* cluster;       /* int32 [N]. NULL = skip */
+  int32_t* table_label;   /* int32 [table_capacity]. NULL = skip */
+  int32_t* table_size;    /* int32 [table_capacity]. NULL = skip */
+  float* box;             /* float [table_capacity,6]. NULL = skip */
+  int64_t table_capacity; /* >= 0 */
+  int32_t* stats;         /* int32 [4]. NULL = skip */
+  int32_t* index;         /* int32 [capacity], mode 1: the source row of every output row; needs count. NULL = skip */
+  int32_t* dropped;       /* int32 [1]. NULL = skip */
+} md_points_clusters;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_fit_planes: the N rows are one view. Of `out` the fields
+ * xyz, rgb, conf, count (int32 [2]: M twice) and capacity are used, with mode 1 only; the others must be NULL; normals_out
+ * [capacity,3] takes the normals rows. Everything is enqueued on `stream`; the call returns after the stream has drained,
+ * because its scratch is freed on return. Errors, before any launch: dev / clu / out NULL, xyz_dev NULL with N > 0, radius not
+ * finite or <= 0, min_neighbours < 0 or > 2^20, min_points < 1, max_points < 0 or 0 < max_points < min_points, mode outside 0
+ * and 1, N < 0, capacity or table_capacity < 0, a compacted output (xyz, rgb, conf, normals_out, index) without count or with
+ * mode 0, an rgb / conf / normals output without that input row, a dense output or out->depth set -> MD_ERR_INVALID_ARG;
+ * N >= 2^30 -> MD_ERR_SHAPE. A probe loop that ran out of table (impossible at load <= 0.5) -> MD_ERR_HIP after the launches. */
+int md_op_cluster_points(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                         int64_t N, const md_points_clusters* clu, const md_points_outputs* out, float* normals_out, void* stream);
+/* md_infer_points_planes with the clustering behind the plane extraction and in front of the point render and the rasteriser
+ * (launch-order name "points_clusters"). It reads the list the plane stage ends with, so planes with mode 1 followed by
+ * clustering is one call. mode 0: the caller's list is unchanged and label / cluster_size / cluster are int32 over its rows,
+ * [out->capacity], of which the first min(count[B], capacity) are written. mode 1: the stage writes the caller's list and
+ * out->count (the stage before it then fills a grow-only list of the model), the three row outputs are int32 over the rows of
+ * that input list (at most B ceil(H/stride) ceil(W/stride)) and clu->index names its rows; the point render sees the list the
+ * call ends with. clu's pointers are of out_kind. The scratch comes from grow-only buffers of the model: after the first call
+ * of a shape nothing is allocated. clu NULL or radius == 0 (its pointers then NULL): md_infer_points_planes on the same
+ * arguments, the same launches and bits. The graph key contains clu's fields. Errors as md_infer_points_planes's, plus, before
+ * any launch: an option outside its range (radius negative or not finite), the stage without the list's count, index without
+ * mode 1, any of clu's pointers with radius == 0, mode 1 together with a mesh, decimation, components or smoothing (the rows
+ * the faces name would vanish) or with an earlier stage's index (voxel thinning's, the outlier removal's, the plane stage's:
+ * the rows they are parallel to are not returned) or behind a plane stage with mode 0 (its label would be parallel to rows that
+ * are not returned), mode 0 without the list output out->xyz or together with decimation -> MD_ERR_INVALID_ARG; a list of
+ * >= 2^30 rows -> MD_ERR_SHAPE. With host outputs a probe loop that ran out of table -> MD_ERR_HIP; with device outputs
+ * md_model_query(m, "clusters_overflow") reads the flag of the last call that was launched or captured (it waits for the
+ * device), as "outlier_overflow" does. */
+int md_infer_points_clusters(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                             const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                             const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                             const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                             const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                             const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
+                             const md_points_clusters* clu, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

@@ -56,6 +56,12 @@ n.x n.y n.z d and their inlier counts are printed. `label` writes the plane of e
 `drop` / `keep` write the cloud without / of the plane points (not with `--mesh`). `--plane-up` keeps only planes whose normal lies within
 the cosine C of that axis (the floor with the up axis). One image without `--mesh`: the stage runs inside the model call
 (`md_infer_points_planes`); with `--views` or `--mesh`, `ops.fit_planes` runs on the final points. T defaults to 1 % of the cloud's extent.
+`--cluster-radius R [--cluster-min-neighbours K] [--cluster-min-points A] [--cluster-max-points B] [--cluster-mode label|keep]` (with
+`--ply`): DBSCAN (K = 0: Euclidean cluster extraction) of the cloud on the device, behind `--planes` when both are given, so `--planes P
+--plane-mode drop --cluster-radius R` clusters what is not on a plane; the table of kept clusters (size, label, box) is printed. `label`
+writes the dense cluster id of every point as the int property `label` of the file (-1 none; it replaces the plane labels), `keep` writes
+the points of kept clusters (not with `--mesh`, nor behind `--plane-mode label`). One image without `--mesh` runs inside the model call
+(`md_infer_points_clusters`); with `--views` or `--mesh`, `ops.cluster_points` runs on the final points.
 `--smooth ITER [--smooth-step S] [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]` (with `--ply --mesh`): Taubin smoothing
 of the mesh on the device, ITER lambda | mu step pairs (`--smooth-mu 0`: ITER Laplacian steps) on an integer lattice of side S, the open
 boundary pinned unless freed. The file holds the smoothed positions and, with `--normals`, the vertex normals of the smoothed faces. One
@@ -132,6 +138,23 @@ def planes_request(a, xyz) -> dict:
         tol = 0.01 * float((fin.max(0).values - fin.min(0).values).max()) if len(fin) else 1.0
     up = dict(axis=tuple(a.plane_up), axis_min_cos=a.plane_up_cos) if a.plane_up else {}
     return dict(planes=a.planes, hypotheses=a.plane_hypotheses, tol=tol, min_inliers=a.plane_min_inliers, seed=a.plane_seed, mode=a.plane_mode, **up)
+
+
+CLUSTER_TABLE = 256  # rows of the printed table
+
+
+def clusters_request(a) -> dict:
+    """the clusters= keywords of --cluster-radius"""
+    return dict(radius=a.cluster_radius, min_neighbours=a.cluster_min_neighbours, min_points=a.cluster_min_points,
+                max_points=a.cluster_max_points, mode=a.cluster_mode, table=CLUSTER_TABLE)
+
+
+def print_clusters(found) -> None:
+    stats = found.stats.cpu().tolist()
+    rows = min(stats[1], int(found.table_label.shape[0]))
+    for i, (l, n, b) in enumerate(zip(found.table_label[:rows].cpu().tolist(), found.table_size[:rows].cpu().tolist(), found.box[:rows].cpu().tolist())):
+        print(f"Cluster {i}: {n} points, label {l}, box {b[0]:.6g} {b[1]:.6g} {b[2]:.6g} .. {b[3]:.6g} {b[4]:.6g} {b[5]:.6g}")
+    print(f"Clusters: {stats[0]} found, {stats[1]} kept, {stats[2]} noise points, {stats[3]} points in kept clusters")
 
 
 def print_planes(fitted) -> None:
@@ -254,6 +277,19 @@ def run_views(a) -> int:
             else:
                 xyz, col, _ = pc.points()
                 nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.cluster_radius > 0:  # on the points the plane step left
+            try:
+                pc = ops.cluster_points(dev, xyz, **clusters_request(a), rgb=col, normals=nrm)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            print_clusters(pc.clusters)
+            if a.cluster_mode == "label":
+                label = pc.clusters.cluster.cpu().numpy()
+                pc.xyz, pc.rgb, pc.count = xyz, col, torch.tensor([xyz.shape[0]], dtype=torch.int32, device=xyz.device)  # what --render-pose draws
+            else:
+                xyz, col, _ = pc.points()
+                nrm = pc.normals[:xyz.shape[0]] if a.normals else None
         P.write_ply(a.ply, xyz.cpu().numpy(), col.cpu().numpy(), nrm.cpu().numpy() if a.normals else None, faces=faces, label=label)
         print(f"Model `{a.model}` wrote {xyz.shape[0]} points{f' and {len(faces)} faces' if a.mesh else ''} of {len(imgs)} views to {a.ply}")
         if a.render_pose:
@@ -335,6 +371,12 @@ def main(argv=None) -> int:
     ap.add_argument("--plane-seed", type=int, default=0, help="--planes: the seed of the samples")
     ap.add_argument("--plane-mode", choices=["label", "drop", "keep"], default="label",
                     help="--planes: write the plane of every point as the PLY property `label`, or the cloud without / of the plane points")
+    ap.add_argument("--cluster-radius", type=float, default=0.0, help="--ply: DBSCAN of the cloud with this neighbour radius (md_infer_points_clusters, ops.cluster_points; 0 = off)")
+    ap.add_argument("--cluster-min-neighbours", type=int, default=0, help="--cluster-radius: the neighbours a core point needs, 0..2^20 (0 = Euclidean cluster extraction)")
+    ap.add_argument("--cluster-min-points", type=int, default=1, help="--cluster-radius: the points a kept cluster has at least")
+    ap.add_argument("--cluster-max-points", type=int, default=0, help="--cluster-radius: the points a kept cluster has at most (0 = no limit)")
+    ap.add_argument("--cluster-mode", choices=["label", "keep"], default="label",
+                    help="--cluster-radius: write the dense cluster id of every point as the PLY property `label`, or the points of kept clusters")
     ap.add_argument("--plane-up", type=float, nargs=3, metavar=("X", "Y", "Z"), help="--planes: only planes whose normal lies within --plane-up-cos of this axis")
     ap.add_argument("--plane-up-cos", type=float, default=0.9, help="--plane-up: the smallest |cosine| between a plane's normal and the axis")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
@@ -354,6 +396,10 @@ def main(argv=None) -> int:
         return 2
     if a.smooth != 0 and (not 1 <= a.smooth <= 1024 or not (a.ply and a.mesh)):
         print("--smooth is a step count in 1..1024 and goes with --ply --mesh", file=sys.stderr)
+        return 2
+    if a.cluster_radius != 0 and (not a.cluster_radius > 0 or not a.ply or (a.cluster_mode == "keep" and (a.mesh or (a.planes and a.plane_mode == "label")))):
+        print("--cluster-radius is > 0 and goes with --ply; --cluster-mode keep not with --mesh (the faces name the rows) nor behind --plane-mode label",
+              file=sys.stderr)
         return 2
     if a.planes != 0 and (not 1 <= a.planes <= 8 or not a.ply or (a.mesh and a.plane_mode != "label")):
         print("--planes is a plane count in 1..8 and goes with --ply; --plane-mode drop / keep not with --mesh (the faces name the rows)", file=sys.stderr)
@@ -427,8 +473,10 @@ def main(argv=None) -> int:
                                     components=dict(min_faces=a.min_component_faces) if a.min_component_faces and not a.decimate else None,
                                     smooth=smooth)
             planes_in_call = bool(a.planes) and not a.mesh
-            if planes_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stage then runs inside the call
-                pc = model.infer_points(x, **call, voxel=a.voxel, render=render, planes=planes_request(a, pc.points()[0]),
+            clusters_in_call = a.cluster_radius > 0 and not a.mesh
+            if planes_in_call or clusters_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stages then run inside the call
+                pc = model.infer_points(x, **call, voxel=a.voxel, render=render, planes=planes_request(a, pc.points()[0]) if planes_in_call else None,
+                                        clusters=clusters_request(a) if clusters_in_call else None,
                                         outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None)
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
@@ -450,6 +498,11 @@ def main(argv=None) -> int:
                 print_planes(fitted)
                 if a.plane_mode == "label":
                     label = fitted.label[:xyz.shape[0]].cpu().numpy()
+            if a.cluster_radius > 0:  # beside a mesh: the operator labels the vertices of the file
+                found = pc.clusters if clusters_in_call else ops.cluster_points(Device(0), xyz, **clusters_request(a)).clusters
+                print_clusters(found)
+                if a.cluster_mode == "label":
+                    label = found.cluster[:xyz.shape[0]].cpu().numpy()
         except _lib.MdError as e:
             print(str(e), file=sys.stderr)
             return 1
