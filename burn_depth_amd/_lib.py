@@ -19,6 +19,7 @@ MD_COMM_ID_BYTES = 128
 MD_FRAME_U8_GRAY, MD_FRAME_RGBA_F32 = 0, 1
 VIT_GEMM_RESID, VIT_GEMM_QKV, VIT_GEMM_FC1, VIT_GEMM_PATCH_EMBED = 0, 1, 2, 3
 DECODER_GEMM_CONV3, DECODER_GEMM_CONV3_S2, DECODER_GEMM_PIXSHUF, DECODER_GEMM_HEAD, DECODER_GEMM_HEAD_UP2 = 0, 1, 2, 3, 4
+INDEXED_GEMM_ROWS, INDEXED_GEMM_ROWS_RES, INDEXED_GEMM_PIXSHUF = 0, 1, 2
 TILE_256x256, TILE_128x128, TILE_256x32, TILE_128x64, TILE_64x64, TILE_AUTO = 0, 1, 2, 3, 4, 99
 
 
@@ -208,6 +209,14 @@ class MdDecoderGemm(C.Structure):
                 ("head_act", C.c_int), ("Cmid", C.c_int), ("w2", C.c_void_p), ("bias2", C.c_void_p)]
 
 
+class MdIndexedGemm(C.Structure):
+    """md_indexed_gemm (include/mi_depth.h)."""
+    _fields_ = [("kind", C.c_int), ("precision", C.c_int), ("tile", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("rows_a", C.c_int),
+                ("a", C.c_void_p), ("index", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("res1", C.c_void_p), ("res_mod", C.c_int),
+                ("out", C.c_void_p), ("out_rows", C.c_int64), ("ldo", C.c_int), ("out_f32", C.c_int), ("B", C.c_int),
+                ("ph", C.c_int), ("pw", C.c_int), ("ps_f", C.c_int), ("ps_coff", C.c_int)]
+
+
 class MdCameraEncode(C.Structure):
     """md_camera_encode (include/mi_depth.h)."""
     _fields_ = [("B", C.c_int), ("V", C.c_int), ("D", C.c_int), ("heads", C.c_int), ("depth", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -369,6 +378,9 @@ SYMBOLS = {
     "md_debug_gemm_last_form": (_I, [C.POINTER(_I * 8)]),
     "md_debug_gemm_last_launch": (_I, [C.POINTER(_I * 4)]),
     "md_op_decoder_gemm": (_I, [_P, C.POINTER(MdDecoderGemm), _P]),
+    "md_op_indexed_gemm": (_I, [_P, C.POINTER(MdIndexedGemm), _P]),
+    "md_op_merge_index_table": (_I, [_I, _I, _I, _I, _I, _I, _P, C.c_int64]),
+    "md_op_token_index_table": (_I, [_I, _I, _I, _I, _P, C.c_int64]),
     "md_op_camera_encode": (_I, [_P, C.POINTER(MdCameraEncode), _P]),
     "md_op_camera_decode": (_I, [_P, C.POINTER(MdCameraDecode), _P]),
     "md_op_pose_to_camera": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),

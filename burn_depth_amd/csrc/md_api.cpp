@@ -1587,6 +1587,86 @@ int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* d, void* stream) 
   return s.finish();
 }
 
+// ---- the gathered-row GEMM forms alone (A_INDEXED; index == NULL: the same parameters as A_DENSE) ----
+int md_op_indexed_gemm(md_device_t dev, const md_indexed_gemm* d, void* stream) {
+  if (!dev || !d || !d->a || !d->w || !d->out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  const int prec = d->precision, kind = d->kind, M = d->M, N = d->N, K = d->K;
+  if (!token_op_prec(prec)) MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: gathered rows run in bf16, f16, f16x2 and f32, not in precision %d", prec);
+  if (kind < MD_INDEXED_GEMM_ROWS || kind > MD_INDEXED_GEMM_PIXSHUF) MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: kind %d", kind);
+  const bool res = kind == MD_INDEXED_GEMM_ROWS_RES, ps = kind == MD_INDEXED_GEMM_PIXSHUF;
+  const int f = ps ? d->ps_f : 1, coff = ps ? d->ps_coff : 0;
+  if (M <= 0 || N <= 0 || K <= 0 || (d->index && d->rows_a <= 0)) MD_FAIL(MD_ERR_SHAPE, "indexed_gemm: M=%d N=%d K=%d over %d rows", M, N, K, d->rows_a);
+  if (K % ke_of(prec) != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "indexed_gemm: K=%d must be whole k-tiles of %d", K, ke_of(prec));
+  if (N % 4 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "indexed_gemm: N=%d (x4)", N);
+  if (ps && ((f != 2 && f != 4) || coff < 0 || !d->bias || d->B <= 0 || d->ph <= 0 || d->pw <= 0 || (long)d->B * d->ph * d->pw != M))
+    MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: pixel shuffle f=%d coff=%d (+ bias) of a [%d, %d, %d] map of %d rows", f, coff, d->B, d->ph, d->pw, M);
+  if (ps && d->out_f32) MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: the pixel shuffle stores T");
+  if (res && (!d->res1 || d->res_mod <= 0 || d->out_f32)) MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: ROWS_RES needs a T-typed output and res1 [res_mod, ldo]");
+  if (!res && (d->res1 || d->res_mod)) MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: a residual table belongs to ROWS_RES");
+  if (d->ldo < coff + N) MD_FAIL(MD_ERR_SHAPE, "indexed_gemm: %d channels at %d do not fit a row of %d", N, coff, d->ldo);
+  const long rows_out = (long)M * f * f;
+  if (rows_out >= (1L << 31) || d->out_rows < rows_out || (double)d->out_rows * d->ldo >= 2147483648.0)
+    MD_FAIL(MD_ERR_SHAPE, "indexed_gemm: the launch writes %ld rows, out holds %ld of %d", rows_out, (long)d->out_rows, d->ldo);
+  const KsplitScope ksplit(res ? 1 : 0);  // (the stage projection is Depth-Anything-v3's, whose engine allows the k-split form; Depth Pro's does not)
+  OpStage s;
+  MD_TRY(s.open(dev, stream, prec));
+  // every table entry inside a, checked on the host: a test's mistake must not become a stray device read
+  if (d->index) {
+    std::vector<int32_t> h((size_t)M);
+    MD_HIP(hipStreamSynchronize(s.st));  // (the caller's table may still be in flight on its stream)
+    MD_HIP(hipMemcpy(h.data(), d->index, (size_t)M * 4, hipMemcpyDeviceToHost));
+    for (int m = 0; m < M; ++m)
+      if (h[m] < 0 || h[m] >= d->rows_a) MD_FAIL(MD_ERR_INVALID_ARG, "indexed_gemm: index[%d] = %d outside [0, %d)", m, h[m], d->rows_a);
+  }
+  DevBuf xa, wa, ws, r1;
+  StorageOut ob;
+  float unused_scale = 0.f;
+  MD_TRY(s.terms_of(d->w, (long)N * K * f * f));
+  MD_TRY(s.dense_a(d->a, d->index ? d->rows_a : M, K, xa, &unused_scale));
+  PackEntry e;
+  e.kp = K;
+  if (ps) { e.kind = PACK_DECONV; e.d0 = K; e.d1 = N; e.k = f; }
+  else { e.kind = PACK_NK; e.d0 = N; e.d1 = K; e.k = 1; }
+  MD_TRY(wa.alloc(pack_elems(e, split_terms(s.geom, 0)) * esz_of(prec)));
+  MD_TRY(s.conv_w(d->w, e, wa));
+  void* out = d->out;
+  if (!d->out_f32) {
+    MD_TRY(ob.open(d->out, (long)d->out_rows * d->ldo, d->ldo, prec, s.st));
+    out = ob.buf.p;
+  }
+  if (res) {
+    MD_TRY(r1.alloc((size_t)d->res_mod * d->ldo * s.es()));
+    MD_TRY(launch_f32_to_rows(d->res1, (long)d->res_mod * d->ldo, r1.p, prec, s.st, d->ldo));
+  }
+  // lda == K in every engine launch of this mode (token rows of the ViT width)
+  const GemmParams p = ps ? deconv2_params(s.geom, d->B, xa.p, K, d->index, d->ph, d->pw, wa.p, K, N, d->bias, out, d->ldo, coff, nullptr, f)
+                          : rows_params(s.geom, xa.p, K, d->index, M, wa.p, N, K, d->bias, out, d->ldo, d->out_f32 ? 1 : 0, ACT_NONE, 0, r1.p, d->res_mod);
+  gemm_forget_form();
+  MD_TRY(launch_gemm(p, d->index ? A_INDEXED : A_DENSE, prec, d->tile, s.st));
+  MD_TRY(ob.close(s.st));
+  return s.finish();
+}
+
+int md_op_merge_index_table(int B, int g, int steps, int pad, int SS, int seq0, int32_t* out, int64_t capacity) {
+  if (B <= 0 || g <= 0 || steps <= 0 || pad < 0 || seq0 < 0 || SS < 1 + g * g || (steps > 1 && 2 * pad >= g))
+    MD_FAIL(MD_ERR_SHAPE, "merge_index_table: B=%d g=%d steps=%d pad=%d SS=%d seq0=%d", B, g, steps, pad, SS, seq0);
+  const int E = merged_extent(g, steps, pad);
+  const double n = (double)B * E * E;
+  if (n >= 2147483648.0 || ((double)seq0 + (double)steps * steps * B) * SS >= 2147483648.0) MD_FAIL(MD_ERR_UNSUPPORTED, "merge_index_table: rows beyond 2^31");
+  if (out && capacity < (int64_t)n) MD_FAIL(MD_ERR_SHAPE, "merge_index_table: %ld entries, capacity %ld", (long)n, (long)capacity);
+  if (out) merge_index_table(B, g, steps, pad, SS, seq0, out);
+  return (int)n;
+}
+
+int md_op_token_index_table(int B, int P, int SS, int seq0, int32_t* out, int64_t capacity) {
+  if (B <= 0 || P <= 0 || seq0 < 0 || SS < 1 + P) MD_FAIL(MD_ERR_SHAPE, "token_index_table: B=%d P=%d SS=%d seq0=%d", B, P, SS, seq0);
+  if (((double)seq0 + B) * SS >= 2147483648.0) MD_FAIL(MD_ERR_UNSUPPORTED, "token_index_table: rows beyond 2^31");
+  const int64_t n = (int64_t)B * P;
+  if (out && capacity < n) MD_FAIL(MD_ERR_SHAPE, "token_index_table: %ld entries, capacity %ld", (long)n, (long)capacity);
+  if (out) token_index_table(B, P, SS, seq0, out);
+  return (int)n;
+}
+
 // ---- the camera path alone (launcher scratch: raw DevBufs, so that a call the launcher refuses has started no device work) ----
 int md_op_camera_encode(md_device_t dev, const md_camera_encode* d, void* stream) {
   if (!dev || !d || !d->extr || !d->intr || !d->out) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");

@@ -662,8 +662,7 @@ static int da3_tok_index(md_model_s* m, int B, int** out) {
     return MD_OK;
   }
   std::vector<int> h((size_t)B * d->P);
-  for (int b = 0; b < B; ++b)
-    for (int p = 0; p < d->P; ++p) h[(size_t)b * d->P + p] = b * d->SS + 1 + p;
+  token_index_table(B, d->P, d->SS, 0, h.data());
   int* dev = nullptr;
   MD_HIP(hipMalloc((void**)&dev, h.size() * 4));
   MD_HIP(hipMemcpy(dev, h.data(), h.size() * 4, hipMemcpyHostToDevice));
@@ -922,13 +921,8 @@ static int da3_prepare_stages(Run& r, const Da3Call& k) {
   for (int s = 0; s < 4; ++s) {
     const int ocp = cpad(m, oc[s]);
     {  // 1x1 projection over gathered patch tokens + 0.1 * UV position table
-      GemmParams p;
-      p.N = oc[s]; p.ngroups = 1; p.g_rows[0] = B * P; p.W[0] = d->proj[s].w; p.bias[0] = d->proj[s].b;
-      p.A = d->hookn[s]; p.a_index = tok_idx;
-      split_dense_a(m, p, d->din, d->din, 0);
-      p.epi = EPI_STORE; p.out = d->sp[s];
-      split_out(m, p, ocp, true);
-      p.res1 = d->pos_stage[s]; p.ldr = p.ldo; p.r_plane = p.o_plane; p.res_mod = P;
+      const GemmParams p = rows_params(geom_of(m), d->hookn[s], d->din, tok_idx, (long)B * P, d->proj[s].w, oc[s], d->din, d->proj[s].b,
+                                       d->sp[s], ocp, 0, ACT_NONE, 0, d->pos_stage[s], P);
       r.begin("head_proj");
       MD_TRY(launch_gemm(p, A_INDEXED, m->prec, TILE_AUTO, r.st));
       r.end();

@@ -37,6 +37,12 @@ int feature_padding(int patch_size, int stride, int feature_patch_size);
 // merged-map pixel -> (tile j, tile i, ty, tx) (encoder.rs:234-282 inverted)
 void merge_source(int Y, int X, int h, int w, int steps, int pad, int* j, int* i, int* ty, int* tx);
 int merged_extent(int h, int steps, int pad);
+// The gather tables of the encoder tail, pure host functions. merge_index_table: the [B, E, E] merged map (E = merged_extent(g, steps,
+// pad)) of g x g token grids in sequences of SS rows (row 0: cls), tile (j, i) of image b being sequence seq0 + (j steps + i) B + b:
+// entry = (seq0 + (j steps + i) B + b) SS + 1 + ty g + tx. token_index_table: the P patch rows of sequences seq0 .. seq0 + B - 1,
+// entry b P + p = (seq0 + b) SS + 1 + p.
+void merge_index_table(int B, int g, int steps, int pad, int SS, int seq0, int32_t* out);
+void token_index_table(int B, int P, int SS, int seq0, int32_t* out);
 
 // PACK_HEAD_W / PACK_HEAD_B: the depth head's `deconv k2s2 (+bias) -> conv 3x3` pair (mod.rs:105-108, nothing between
 // them) composed at commit into ONE 3x3 convolution on the deconv's input grid with 4 x Cout output columns (one group

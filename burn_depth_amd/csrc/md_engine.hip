@@ -56,6 +56,23 @@ void merge_source(int Y, int X, int h, int w, int steps, int pad, int* j, int* i
   *i = ii;
 }
 
+void merge_index_table(int B, int g, int steps, int pad, int SS, int seq0, int32_t* out) {
+  const int E = merged_extent(g, steps, pad);
+  size_t o = 0;
+  for (int b = 0; b < B; ++b)
+    for (int Y = 0; Y < E; ++Y)
+      for (int X = 0; X < E; ++X) {
+        int j, i, ty, tx;
+        merge_source(Y, X, g, g, steps, pad, &j, &i, &ty, &tx);
+        out[o++] = (seq0 + (j * steps + i) * B + b) * SS + 1 + ty * g + tx;
+      }
+}
+
+void token_index_table(int B, int P, int SS, int seq0, int32_t* out) {
+  for (int b = 0; b < B; ++b)
+    for (int p = 0; p < P; ++p) out[(size_t)b * P + p] = (seq0 + b) * SS + 1 + p;
+}
+
 // ------------------------------------------------------------------------------------------------
 // weight packing kernels: fp32 master -> MFMA operand layouts
 // ------------------------------------------------------------------------------------------------
@@ -919,27 +936,10 @@ static int get_index_set(md_model_s* m, int B, md_model_s::IndexSet* out) {
   const int nseq_p = n0 + n1 + B;
   const size_t nhi = (size_t)B * m->mh_hi * m->mh_hi, nmid = (size_t)B * m->mh_mid * m->mh_mid, nlo = (size_t)B * P;
   std::vector<int> h(nhi + nmid + 3 * nlo);
-  size_t o = 0;
-  for (int b = 0; b < B; ++b)
-    for (int Y = 0; Y < m->mh_hi; ++Y)
-      for (int X = 0; X < m->mh_hi; ++X) {
-        int j, i, ty, tx;
-        merge_source(Y, X, g, g, m->steps0, m->pad_hi, &j, &i, &ty, &tx);
-        h[o++] = ((j * m->steps0 + i) * B + b) * SS + 1 + ty * g + tx;
-      }
-  for (int b = 0; b < B; ++b)
-    for (int Y = 0; Y < m->mh_mid; ++Y)
-      for (int X = 0; X < m->mh_mid; ++X) {
-        int j, i, ty, tx;
-        merge_source(Y, X, g, g, m->steps1, m->pad_mid, &j, &i, &ty, &tx);
-        h[o++] = (n0 + (j * m->steps1 + i) * B + b) * SS + 1 + ty * g + tx;
-      }
-  for (int which = 0; which < 3; ++which)
-    for (int b = 0; b < B; ++b)
-      for (int p = 0; p < P; ++p) {
-        const int seq = which == 0 ? n0 + n1 + b : which == 1 ? nseq_p + b : nseq_p + B + b;
-        h[o++] = seq * SS + 1 + p;
-      }
+  merge_index_table(B, g, m->steps0, m->pad_hi, SS, 0, h.data());
+  merge_index_table(B, g, m->steps1, m->pad_mid, SS, n0, h.data() + nhi);
+  const int seq0[3] = {n0 + n1, nseq_p, nseq_p + B};  // x2 (the patch encoder's low-resolution image), img, fov
+  for (int which = 0; which < 3; ++which) token_index_table(B, P, SS, seq0[which], h.data() + nhi + nmid + which * nlo);
   int* d = nullptr;
   MD_HIP(hipMalloc((void**)&d, h.size() * 4));
   m->alloc_count += 1;

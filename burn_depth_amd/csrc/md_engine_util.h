@@ -245,15 +245,24 @@ inline void split_out(const OperandGeom& o, GemmParams& p, long ldo, bool t_out)
 }
 inline void split_out(const md_model_s* m, GemmParams& p, long ldo, bool t_out) { split_out(geom_of(m), p, ldo, t_out); }
 
-// 1x1 conv / linear over NHWC rows.  A may be gathered through `idx`.
-inline int gemm_rows(Run& r, const char* name, const void* A, long lda, const int* idx, long M, const void* W, int N, int K,
-              const float* bias, void* out, long ldo, int out_f32 = 0, int act = ACT_NONE, int terms = 0) {
+// 1x1 conv / linear over NHWC rows.  A may be gathered through `idx`. `res1` (T-typed rows of ldo): a residual table whose row is
+// m % res_mod (the Depth-Anything-v3 stage projection's position table, one per image)
+// (the launch parameters apart from the launch: md_op_indexed_gemm launches the very same ones)
+inline GemmParams rows_params(const OperandGeom& m, const void* A, long lda, const int* idx, long M, const void* W, int N, int K,
+                              const float* bias, void* out, long ldo, int out_f32 = 0, int act = ACT_NONE, int terms = 0,
+                              const void* res1 = nullptr, int res_mod = 0) {
   GemmParams p;
   p.N = N; p.ngroups = 1; p.g_rows[0] = (int)M; p.W[0] = W;
   p.A = A; p.a_index = idx;
-  split_dense_a(r.m, p, K, lda, terms);
+  split_dense_a(m, p, K, lda, terms);
   p.epi = EPI_STORE; p.act = act; p.out_f32 = out_f32; p.bias[0] = bias; p.out = out;
-  split_out(r.m, p, ldo, !out_f32);
+  split_out(m, p, ldo, !out_f32);
+  if (res1) { p.res1 = res1; p.ldr = p.ldo; p.r_plane = p.o_plane; p.res_mod = res_mod; }
+  return p;
+}
+inline int gemm_rows(Run& r, const char* name, const void* A, long lda, const int* idx, long M, const void* W, int N, int K,
+              const float* bias, void* out, long ldo, int out_f32 = 0, int act = ACT_NONE, int terms = 0) {
+  const GemmParams p = rows_params(geom_of(r.m), A, lda, idx, M, W, N, K, bias, out, ldo, out_f32, act, terms);
   r.begin(name);
   int s = launch_gemm(p, idx ? A_INDEXED : A_DENSE, r.m->prec, TILE_AUTO, r.st);
   r.end();

@@ -510,6 +510,51 @@ def decoder_gemm(dev: Device, kind: int, x: torch.Tensor, w, bias, precision: in
     _lib.check(_lib.load().md_op_decoder_gemm(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
 
 
+def _index_table(entry, *args) -> torch.Tensor:
+    """A host-only table entry: the count first (out = NULL), then the entries into an int32 host tensor."""
+    n = entry(*args, None, 0)
+    _lib.check(min(n, 0))
+    out = torch.empty(n, dtype=torch.int32)
+    assert entry(*args, C.c_void_p(out.data_ptr()), n) == n
+    return out
+
+
+def merge_index_table(B: int, g: int, steps: int, pad: int, SS: int, seq0: int = 0) -> torch.Tensor:
+    """md_op_merge_index_table (no device): the gather table [B * E * E] of the merged map of g x g token tiles."""
+    return _index_table(_lib.load().md_op_merge_index_table, B, g, steps, pad, SS, seq0)
+
+
+def token_index_table(B: int, P: int, SS: int, seq0: int = 0) -> torch.Tensor:
+    """md_op_token_index_table (no device): the patch rows (seq0 + b) SS + 1 + p of B sequences."""
+    return _index_table(_lib.load().md_op_token_index_table, B, P, SS, seq0)
+
+
+def indexed_gemm(dev: Device, kind: int, a: torch.Tensor, index: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor], precision: int,
+                 tile: int = _lib.TILE_AUTO, *, out: torch.Tensor, ldo: int, M: Optional[int] = None, out_f32: bool = False,
+                 res1: Optional[torch.Tensor] = None, res_mod: int = 0, B: int = 0, ph: int = 0, pw: int = 0, ps_f: int = 2, ps_coff: int = 0) -> None:
+    """md_op_indexed_gemm: one gathered-row GEMM form (kind = _lib.INDEXED_GEMM_*) on the CALLER's contiguous fp32 device tensors; `out`
+    [rows, ldo] is updated in place. a [rows_a, K]; index int32 [M] (None: the dense launch over a [M, K]); w [N, K], for the pixel
+    shuffle [K, N, f, f]; res1 [res_mod, ldo]."""
+    for t in (a, w, bias, res1, out):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32), "indexed_gemm takes contiguous fp32 device tensors"
+    assert index is None or (index.is_cuda and index.is_contiguous() and index.dtype == torch.int32 and index.dim() == 1)
+    ps = kind == _lib.INDEXED_GEMM_PIXSHUF
+    d = _lib.MdIndexedGemm()
+    d.kind, d.precision, d.tile = kind, precision, tile
+    d.rows_a, d.K = a.shape
+    d.M = index.numel() if index is not None else (a.shape[0] if M is None else M)
+    d.N = w.shape[1] if ps else w.shape[0]
+    assert a.dim() == 2 and (w.shape == (d.K, d.N, ps_f, ps_f) if ps else w.shape == (d.N, d.K)), "weight shape"
+    assert bias is None or bias.shape == (d.N,)
+    assert res1 is None or res1.shape == (res_mod, ldo)
+    assert out.dim() == 2 and out.shape[1] == ldo
+    d.a, d.index, d.w, d.bias, d.res1, d.out = a.data_ptr(), (index.data_ptr() if index is not None else None), w.data_ptr(), \
+        (bias.data_ptr() if bias is not None else None), (res1.data_ptr() if res1 is not None else None), out.data_ptr()
+    d.res_mod, d.out_rows, d.ldo, d.out_f32 = res_mod, out.shape[0], ldo, int(out_f32)
+    d.B, d.ph, d.pw, d.ps_f, d.ps_coff = B, ph, pw, (ps_f if ps else 0), (ps_coff if ps else 0)
+    _lib.check(_lib.load().md_op_indexed_gemm(dev.handle, C.byref(d), _stream_ptr(dev.ordinal)))
+
+
 def _f32_dev(*tensors) -> None:
     for t in tensors:
         assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32), "the camera entries take contiguous fp32 device tensors"

@@ -1520,6 +1520,42 @@ typedef struct md_decoder_gemm {
   const float* bias2;        /* HEAD_UP2: [32] */
 } md_decoder_gemm;
 int md_op_decoder_gemm(md_device_t dev, const md_decoder_gemm* desc, void* stream);
+/* ---- the gathered-row GEMM forms alone (test-only): logical row m of A reads physical row index[m], as the Depth Pro encoder tail
+ * (enc_proj, the low-resolution deconvolution, fov_proj) and the Depth-Anything-v3 stage projection launch it, with the engines' own
+ * launch-parameter builders. Every tensor is the CALLER's fp32 device tensor: `a`, `w`, `res1` are narrowed to `precision`'s storage
+ * per call (weights packed as at commit; split-half: two terms when every weight is an exact half, else three); a T-typed `out` is
+ * narrowed before and widened behind the launch, so what the launch leaves alone returns bit for bit when it is exact in the type.
+ * `index` is copied to the host and every entry must lie in [0, rows_a): MD_ERR_INVALID_ARG otherwise, before any launch.
+ * index == NULL: the same parameters as a dense launch over a [M, K]. MD_PREC_BF16 / F16 / F16X2 / F32. ---- */
+typedef enum md_indexed_gemm_kind {
+  MD_INDEXED_GEMM_ROWS = 0,     /* out[m, :N] = a[index[m]] . w^T + bias; bias may be NULL; T-typed rows of ldo, or (out_f32) fp32 */
+  MD_INDEXED_GEMM_ROWS_RES = 1, /* ROWS + res1[m % res_mod], a T-typed table [res_mod, ldo]; T-typed output */
+  MD_INDEXED_GEMM_PIXSHUF = 2   /* ConvTranspose2d k = s = ps_f of the gathered [B, ph, pw] map into channels [ps_coff, ps_coff + N) */
+} md_indexed_gemm_kind;
+typedef struct md_indexed_gemm {
+  int kind, precision, tile; /* tile: 99 = the launcher's choice, else 0 .. 4 as md_debug_gemm_last_launch names them */
+  int M, N, K;               /* logical rows; output channels (PIXSHUF: of one pixel); contraction = row width of a */
+  int rows_a;                /* rows of a */
+  const float* a;            /* [rows_a, K]; index == NULL: [M, K] */
+  const int32_t* index;      /* [M] device, or NULL */
+  const float* w;            /* ROWS*: [N, K]; PIXSHUF: [K, N, ps_f, ps_f] */
+  const float* bias;         /* [N]; ROWS: may be NULL */
+  const float* res1;         /* ROWS_RES: [res_mod, ldo] */
+  int res_mod;
+  float* out;                /* [out_rows, ldo]; PIXSHUF: pixels [B, ps_f ph, ps_f pw] of ldo */
+  int64_t out_rows;          /* rows of out the caller owns, >= the launch's */
+  int ldo, out_f32;          /* logical channels per output row; ROWS: the fp32 store */
+  int B, ph, pw;             /* PIXSHUF: M = B ph pw */
+  int ps_f, ps_coff;         /* PIXSHUF: 2 | 4; first channel of the slice */
+} md_indexed_gemm;
+int md_op_indexed_gemm(md_device_t dev, const md_indexed_gemm* desc, void* stream);
+/* Host-only, no device: the gather tables of the Depth Pro encoder tail. md_op_merge_index_table: the merged map of a g x g token grid
+ * split into steps x steps tiles with `pad` halo tokens (the reference's merge as a gather) -- entry ((b Y) X) of the [B, E, E] map, E =
+ * steps (g - 2 pad) + 2 pad (steps == 1: g), is the token row (seq0 + (j steps + i) B + b) SS + 1 + ty g + tx of sequences of SS rows.
+ * md_op_token_index_table: entry b P + p = (seq0 + b) SS + 1 + p, the patch rows of B whole sequences. Both return the number of
+ * entries (negative: an error code); out == NULL returns the count only, else capacity must hold it. */
+int md_op_merge_index_table(int B, int g, int steps, int pad, int SS, int seq0, int32_t* out, int64_t capacity);
+int md_op_token_index_table(int B, int P, int SS, int seq0, int32_t* out, int64_t capacity);
 /* ---- the Depth-Anything-v3 camera path alone (test-only): the camera encoder, the camera decoder and the pose -> matrices tail as the
  * engine launches them, on fp32 device tensors the CALLER owns. The entries allocate only the launchers' scratch, pre-fill nothing,
  * launch and synchronise. What a launcher refuses (views outside 1..16, width % 8, width % heads, depth outside 0..8; decoder width % 4,
