@@ -327,6 +327,45 @@ size_t clusters_scratch_bytes(int n, long table_capacity);
 int launch_cluster_points(const ClustersParams& p, void* scratch, hipStream_t s);
 const int32_t* clusters_flags(const void* scratch, int n, long table_capacity);
 
+// ---- nearest row of a reference cloud (kernels/match.hip; md_op_match_points, md_infer_points_match) ----
+// A point list xyz [n,3] (+ conf, rgb, normals rows) and a target list [t,3] -> the nearest target row of every row: the
+// clustering's cell buckets with 16-byte entries, built from the target and sized by it, then one launch over the tiles of the
+// source: 27 probes with loads only, the running minimum of (bits(d2) << 32) | target row, the ballot bit of the mode and the
+// counters. mode 1 / 2 then compacts the matched / unmatched rows through launch_list_compact. Every pointer is a device pointer.
+// A selection on a deterministic f32 value: nothing depends on the order of arrival.
+struct MatchParams {
+  const float* xyz = nullptr;
+  const float* conf = nullptr;        // carried to conf_out
+  const uint8_t* rgb = nullptr;       // carried to rgb_out
+  const float* normals = nullptr;     // carried to normals_out
+  const int32_t* in_count = nullptr;  // as VoxelParams::in_count
+  int n = 0;                          // rows the launches cover: the live count is min(in_count[B], n)
+  int B = 1;
+  const float* target = nullptr;  // [t,3]
+  int t = 0;
+  float radius = 0.f;
+  float tol[4] = {0.f, 0.f, 0.f, 0.f};  // 0: unused
+  int mode = 0;
+  int32_t* nearest = nullptr;  // [n]; null: skip
+  float* dist2 = nullptr;      // [n]; null: skip
+  int32_t* stats = nullptr;    // [8] in-range rows, matched rows, target rows in the grid, 0, rows within tol[0..4); null: they live in the scratch
+  int32_t* dropped = nullptr;  // [1]; null: skip
+  float* xyz_out = nullptr;    // mode 1 / 2: the compacted rows
+  float* conf_out = nullptr;
+  uint8_t* rgb_out = nullptr;
+  float* normals_out = nullptr;
+  int32_t* index = nullptr;  // [capacity] source row
+  int32_t* count = nullptr;  // [B + 1] survivors per view, then their total
+  long capacity = 0;
+};
+constexpr int kMatchStatsFlag = 8;  // match_flags(..)[8 .. 16): the eight counters when `stats` is null
+// bytes of the scratch (table 20 B per slot of the target's table | slot of every target row | buckets 16 t | ballot words |
+// tile counts | tile offsets of the source | flags)
+size_t match_scratch_bytes(int n, int t);
+// flags[0] != 0 after the launches = a probe loop ran out of table
+int launch_match_points(const MatchParams& p, void* scratch, hipStream_t s);
+const int32_t* match_flags(const void* scratch, int n, int t);
+
 // ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
 // A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour
 // image: clear, splat (atomicMin of (bits(p.z) << 32) | row over the footprint), resolve. Every pointer is a device pointer.

@@ -376,7 +376,7 @@ struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], c
   const float* normals = nullptr;
   int64_t N = 0;
 };
-// One md_infer_points* request: what the widest entry (md_infer_points_clusters) takes. A narrower entry leaves the parts it lacks
+// One md_infer_points* request: what the widest entry (md_infer_points_match) takes. A narrower entry leaves the parts it lacks
 // null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
 struct PointsCall {
   const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
@@ -400,6 +400,7 @@ struct PointsCall {
   const md_points_smooth* smooth = nullptr;    // given: smoothing of the list over the faces the rasteriser reads (pointers of out_kind); needs `mesh`
   const md_points_planes* pln = nullptr;       // given: plane extraction from the list the call ends with (pointers of out_kind); mode 1 / 2 writes that list
   const md_points_clusters* clu = nullptr;     // given: clustering of the list behind the plane stage (pointers of out_kind); mode 1 writes that list
+  const md_points_match* mat = nullptr;        // given: matching against a reference cloud between the plane stage and the clustering (pointers of out_kind, the target of its own kind); mode 1 / 2 writes the list
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
@@ -427,6 +428,9 @@ int op_fit_planes(md_device_t dev, const PointList& in, const md_points_planes* 
 // in: the rows, one view; out's list fields and normals_out with clu->mode 1 only
 int op_cluster_points(md_device_t dev, const PointList& in, const md_points_clusters* clu, const md_points_outputs* out, float* normals_out,
                       hipStream_t stream);
+// in: the rows, one view; out's list fields and normals_out with mat->mode 1 / 2 only
+int op_match_points(md_device_t dev, const PointList& in, const md_points_match* mat, const md_points_outputs* out, float* normals_out,
+                    hipStream_t stream);
 // in.xyz / in.rgb: the list; count: its device count word or null
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream);
@@ -438,6 +442,7 @@ int points_voxel_overflow(md_model_t m, int64_t* out);
 // likewise for the outlier removal of the model's last md_infer_points_outlier
 int points_outlier_overflow(md_model_t m, int64_t* out);
 int points_clusters_overflow(md_model_t m, int64_t* out);
+int points_match_overflow(md_model_t m, int64_t* out);
 // likewise for the decimation of the model's last md_infer_points_decimate (the vertex table's flag or the face table's)
 int points_decimate_overflow(md_model_t m, int64_t* out);
 int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_view_filter_opts* o,

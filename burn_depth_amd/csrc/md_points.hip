@@ -21,7 +21,9 @@
 // finds in it; with mode 1 / 2 the stage is the last one that writes a list.
 // md_op_cluster_points / md_infer_points_clusters (kernels/clusters.hip) label the rows of the list the plane stage ends with by
 // their DBSCAN cluster; with mode 1 the stage is the last one that writes a list.
-// The thirteen md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
+// md_op_match_points / md_infer_points_match (kernels/match.hip) give every row of the list the plane stage ends with its nearest
+// row of a reference cloud; with mode 1 / 2 the stage is a link of the list chain, between the plane stage and the clustering.
+// The fourteen md_infer_points* entries are one request (PointsCall); its stages share one plan of device pointers (PointsPlan),
 // which holds the list the call ends with once (PointsPlan::fin, wired to the last list stage in plan_homes).
 #include <algorithm>
 #include <cfloat>
@@ -63,12 +65,17 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> plist;        // its input with mode 1 / 2 behind the thinning: the thinned list, laid out as vlist
   md::GrowBuf<void> ktable;       // md_infer_points_clusters: the clustering's scratch (clusters_scratch_bytes)
   md::GrowBuf<void> klist;        // its input with mode 1 behind a plane stage that cuts: that stage's list, laid out as vlist
+  md::GrowBuf<void> mtable;       // md_infer_points_match: the matching's scratch (match_scratch_bytes)
+  md::GrowBuf<void> mlist;        // the list it writes with mode 1 / 2 when the clustering (mode 1) follows, laid out as vlist
+  md::GrowBuf<float> mtarget;     // the device copy of a host target [T,3]
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
   int outl_rows = 0;              // likewise for the outlier removal and otable
   int clu_rows = 0;               // likewise for the clustering and ktable,
   long clu_table = 0;             // with the table capacity its scratch was carved for
+  int mat_rows = 0, mat_target = 0;  // likewise for the matching and mtable: the source rows and the target rows; mat_ran: a call ran
+  bool mat_ran = false;
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
   float* f_home(int B) const { return cams.p + (size_t)B * 21; }
@@ -325,6 +332,40 @@ ClustersParams make_clusters(const md_points_clusters& f) {
   return q;
 }
 
+bool match_on(const md_points_match* q) { return q && q->radius != 0.f; }
+
+// model call: radius == 0 is the call without the stage and takes none of its outputs; the operator takes a device target only
+int check_match(const md_points_match* q, const md_points_outputs* out, bool op) {
+  if (!q) return MD_OK;
+  if (!std::isfinite(q->radius) || q->radius < 0.f || (op && q->radius == 0.f) || !std::isfinite(q->radius * q->radius))
+    MD_FAIL(MD_ERR_INVALID_ARG, "radius = %g: it and its square must be finite and %s 0", (double)q->radius, op ? ">" : ">=");
+  if (q->radius == 0.f) {
+    if (q->nearest || q->dist2 || q->stats || q->index || q->dropped) MD_FAIL(MD_ERR_INVALID_ARG, "match outputs without a radius");
+    return MD_OK;
+  }
+  for (int t = 0; t < 4; ++t)
+    if (!(q->tol[t] >= 0.f) || !(q->tol[t] <= q->radius))
+      MD_FAIL(MD_ERR_INVALID_ARG, "tol[%d] = %g: 0 or in (0, radius = %g]", t, (double)q->tol[t], (double)q->radius);
+  if (q->mode < 0 || q->mode > 2) MD_FAIL(MD_ERR_INVALID_ARG, "mode = %d: 0, 1 or 2", q->mode);
+  if (q->target_rows < 0) MD_FAIL(MD_ERR_INVALID_ARG, "target_rows = %lld is negative", (long long)q->target_rows);
+  if (q->target_rows > 0 && !q->target) MD_FAIL(MD_ERR_INVALID_ARG, "target pointer is null");
+  if (q->target_kind != MD_MEM_DEVICE && (op || q->target_kind != MD_MEM_HOST))
+    MD_FAIL(MD_ERR_INVALID_ARG, "target_kind = %d: %s", q->target_kind, op ? "the operator takes a device target" : "unknown memory kind");
+  if (q->index && q->mode == 0) MD_FAIL(MD_ERR_INVALID_ARG, "index needs mode 1 or 2");
+  MD_TRY(need_count(q->index, out, "index"));
+  if (q->target_rows >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "matching takes fewer than 2^30 target rows, got %lld", (long long)q->target_rows);
+  return MD_OK;
+}
+
+// the options and the outputs of the stage's own; the caller adds the rows (and a host target's device copy)
+MatchParams make_match(const md_points_match& f) {
+  MatchParams q;
+  q.radius = f.radius; q.target = f.target; q.t = (int)f.target_rows; q.mode = f.mode;
+  for (int t = 0; t < 4; ++t) q.tol[t] = f.tol[t];
+  q.nearest = f.nearest; q.dist2 = f.dist2; q.stats = f.stats; q.index = f.index; q.dropped = f.dropped;
+  return q;
+}
+
 bool outlier_on(const md_points_outlier* q) { return q && q->radius != 0.f; }
 
 // model call: radius == 0 is the call without outlier removal and takes none of its outputs. The operator's `neighbours` covers
@@ -493,6 +534,7 @@ const char kVoxelRanOut[] = "voxel thinning: the probe loop ran out of table slo
 const char kOutlierRanOut[] = "outlier removal: a probe loop ran out of table slots";
 const char kDecimateRanOut[] = "decimation: a probe loop ran out of table slots";
 const char kClustersRanOut[] = "clustering: a probe loop ran out of table slots";
+const char kMatchRanOut[] = "matching: a probe loop ran out of table slots";
 
 // Every operator's last refusal and first act: the device, made current, and the stream its launches take.
 int op_begin(md_device_t dev, hipStream_t stream, hipStream_t* st) {
@@ -681,6 +723,25 @@ int op_cluster_points(md_device_t dev, const PointList& in, const md_points_clus
   return scratch.finish_flags(launch_cluster_points(p, scratch.p, st), clusters_flags(scratch.p, p.n, p.table_capacity), nullptr, kClustersRanOut);
 }
 
+int op_match_points(md_device_t dev, const PointList& in, const md_points_match* mat, const md_points_outputs* out, float* normals_out,
+                    hipStream_t stream) {
+  if (!mat) MD_FAIL(MD_ERR_INVALID_ARG, "match options are null");
+  if (!out) MD_FAIL(MD_ERR_INVALID_ARG, "point outputs are null");
+  MD_TRY(check_match(mat, out, true));
+  MD_TRY(check_list_op("matching", in, out, normals_out));
+  if (mat->mode == 0 && (out->xyz || out->rgb || out->conf || normals_out)) MD_FAIL(MD_ERR_INVALID_ARG, "mode 0 writes no list: the compacted outputs need mode 1 or 2");
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
+  MatchParams p = make_match(*mat);
+  p.xyz = in.xyz; p.conf = in.conf; p.rgb = in.rgb; p.normals = in.normals;
+  p.n = (int)in.N; p.B = 1;
+  p.xyz_out = out->xyz; p.conf_out = out->conf; p.rgb_out = out->rgb; p.normals_out = normals_out;
+  p.count = mat->mode ? out->count : nullptr; p.capacity = out->capacity;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(match_scratch_bytes(p.n, p.t)));
+  return scratch.finish_flags(launch_match_points(p, scratch.p, st), match_flags(scratch.p, p.n, p.t), nullptr, kMatchRanOut);
+}
+
 int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
                      const md_points_outputs* out, float* normals_out, hipStream_t stream) {
   if (!dec) MD_FAIL(MD_ERR_INVALID_ARG, "decimation options are null");
@@ -829,6 +890,11 @@ int points_clusters_overflow(md_model_t m, int64_t* out) {
   return read_overflow(m, f && f->clu_rows && f->ktable.p ? clusters_flags(f->ktable.p, f->clu_rows, f->clu_table) : nullptr, nullptr, out);
 }
 
+int points_match_overflow(md_model_t m, int64_t* out) {
+  const md_model_s::PointsState* f = m->points;
+  return read_overflow(m, f && f->mat_ran && f->mtable.p ? match_flags(f->mtable.p, f->mat_rows, f->mat_target) : nullptr, nullptr, out);
+}
+
 int points_decimate_overflow(md_model_t m, int64_t* out) {
   const md_model_s::PointsState* f = m->points;
   if (!f || !f->dec_views || !f->dtable.p) return read_overflow(m, nullptr, nullptr, out);
@@ -849,7 +915,7 @@ struct ListRows {
   int32_t* count = nullptr;  // [B + 1]
 };
 
-// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too), OutlierParams, PlanesParams and ClustersParams
+// the launch parameters that read a list and write one: VoxelParams (the decimation's vertex side too), OutlierParams, PlanesParams, MatchParams and ClustersParams
 template <typename P>
 void reads(P& p, const ListRows& l) { p.xyz = l.xyz; p.conf = l.conf; p.rgb = l.rgb; p.normals = l.normals; p.in_count = l.count; }
 template <typename P>
@@ -871,6 +937,7 @@ struct PointsPlan {
   bool thin = false, mesh = false, filt = false, deci = false, comp = false, smo = false, pln = false;  // the stages that are on
   bool pcut = false;  // pln with mode 1 / 2: the plane stage writes a list
   bool clu = false, ccut = false;  // the clustering is on; with mode 1: it is the last stage that writes a list
+  bool mat = false, mcut = false;  // the matching is on; with mode 1 / 2: it writes a list, between the plane stage and the clustering
   bool own_faces = false;  // deci / comp / smo: a later stage reads the faces, so the mesh stage writes the model's own (`gd`)
   size_t npx = 0;
   long rows = 0;  // rows the unthinned list of the call can have (list_rows); its mesh has at most 2 * rows faces
@@ -894,12 +961,15 @@ struct PointsPlan {
   SmoothParams sm;     // smo: launch_smooth_mesh's, from `fin` and the faces of `k`, or else those `gd` wrote
   PlanesParams pn;     // pln: launch_fit_planes', from `fin` (mode 0) or the model's own list in front of it (pcut)
   ClustersParams cn;   // clu: launch_cluster_points', from `fin` (mode 0) or the model's own list in front of it (ccut)
+  MatchParams mn;      // mat: launch_match_points', from `fin` (mode 0) or the model's own list in front of it (mcut)
+  const float* host_target = nullptr;  // mat with a host target: the caller's rows, which stage_inputs copies to mtarget
   int queue = 0;    // the raster's queue entries: what skeys was sized for
   int32_t* pix = nullptr;  // where pixel_index goes: the caller's map or its home; null: behind the face scratch
   int32_t unfiltered = 0;  // filt with host outputs: the rows of the unfiltered list, read back for outl->neighbours' slot
   int32_t plane_rows = 0;  // pcut with host outputs: the rows of the plane stage's input list, read back for pln->label's slot
   int32_t cluster_rows = 0;  // ccut with host outputs: the rows of the clustering's input list, for the slots of its row outputs
   int32_t clusters_kept = 0; // clu with host outputs: the kept clusters, for the slots of the table
+  int32_t match_rows = 0;    // mcut with host outputs: the rows of the matching's input list, for the slots of its row outputs
   std::vector<OutSlot> slots;
 };
 
@@ -1021,6 +1091,19 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(k.table_size, pl.cn.table_size, 4, tcap, &pl.clusters_kept);
     slot(k.box, pl.cn.box, 24, tcap, &pl.clusters_kept);
   }
+  if (pl.mat) {  // the row outputs as the plane stage's label
+    const md_points_match& q = *c.mat;
+    slot(q.stats, pl.mn.stats, 4, 8);
+    slot(q.dropped, pl.mn.dropped, 4, 1);
+    if (pl.mcut) {
+      slot(q.nearest, pl.mn.nearest, 4, list, &pl.match_rows);
+      slot(q.dist2, pl.mn.dist2, 4, list, &pl.match_rows);
+    } else {
+      slot(q.nearest, pl.mn.nearest, 4, cap, n);
+      slot(q.dist2, pl.mn.dist2, 4, cap, n);
+    }
+    slot(q.index, pl.mn.index, 4, cap, n);
+  }
   if (pl.smo) {  // rows parallel to the list: they travel as its rows do
     slot(c.smooth->xyz, pl.sm.xyz_out, 12, cap, n);
     slot(c.smooth->normals, pl.sm.normals_out, 12, cap, n);
@@ -1077,6 +1160,16 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   pl.clu = clusters_on(c.clu);
   pl.ccut = pl.clu && c.clu->mode != 0;
   if (pl.clu) pl.cn = make_clusters(*c.clu);
+  pl.mat = match_on(c.mat);
+  pl.mcut = pl.mat && c.mat->mode != 0;
+  if (pl.mat) {
+    pl.mn = make_match(*c.mat);
+    if (c.mat->target_kind == MD_MEM_HOST && pl.mn.t > 0) {
+      MD_TRY(grow(m, st, f->mtarget, (size_t)pl.mn.t * 12));
+      pl.host_target = c.mat->target;
+      pl.mn.target = f->mtarget.p;
+    }
+  }
   if (c.rnd) {
     pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
@@ -1112,7 +1205,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     else if (pl.deci) ends_with(pl.d.faces_out, pl.d.face_count, c.dec->face_capacity);
     else ends_with(pl.g.faces, pl.g.face_count, c.mesh->face_capacity);
   }
-  const bool own_list = pl.thin || pl.filt || pl.deci || pl.pcut || pl.ccut;  // the scatter fills a list of the model's own: a later stage writes `fin`
+  const bool own_list = pl.thin || pl.filt || pl.deci || pl.pcut || pl.mcut || pl.ccut;  // the scatter fills a list of the model's own: a later stage writes `fin`
   auto scatter_to = [&](const ListRows& l) { p.xyz = l.xyz; p.conf_out = l.conf; p.rgb_out = l.rgb; pl.q.normals = l.normals; p.count = l.count; };
   if (!own_list) scatter_to(pl.fin);
   if (pl.comp || pl.smo) {  // all faces of the call's list go to the model's face home; the stages read them and the list's device count
@@ -1147,6 +1240,12 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, m->points->ktable, clusters_scratch_bytes(k.n, k.table_capacity)));
     if (!pl.ccut) reads(k, pl.fin);  // mode 0: the rows of the call's list below its capacity
   }
+  if (pl.mat) {
+    MatchParams& q = pl.mn;
+    q.B = B; q.n = (int)(pl.mcut ? rows : std::min<long>((long)out.capacity, rows));
+    MD_TRY(grow(m, st, m->points->mtable, match_scratch_bytes(q.n, q.t)));
+    if (!pl.mcut) reads(q, pl.fin);  // mode 0: the rows of the call's list below its capacity
+  }
   if (!own_list) return MD_OK;
   const bool want_rgb = out.rgb != nullptr, want_nrm = c.nrm && c.nrm->normals;
   const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = pl.dual ? align_up((size_t)rows * 4, 256) : 0;
@@ -1160,10 +1259,11 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(grow(m, st, f->vlist, b_list));
   if (pl.thin) MD_TRY(grow(m, st, f->vtable, voxel_scratch_bytes((int)rows)));
   if (pl.filt) MD_TRY(grow(m, st, f->otable, outlier_scratch_bytes((int)rows)));
-  if (pl.filt && (pl.thin || pl.pcut || pl.ccut)) MD_TRY(grow(m, st, f->flist, b_list));
-  if (pl.thin && (pl.pcut || pl.ccut)) MD_TRY(grow(m, st, f->plist, b_list));
-  if (pl.pcut && pl.ccut) MD_TRY(grow(m, st, f->klist, b_list));
-  // The chain scatter -> outlier removal -> voxel thinning -> plane extraction (mode 1 / 2) -> clustering (mode 1), or scatter -> decimation (the decimation is the thinning, with the
+  if (pl.filt && (pl.thin || pl.pcut || pl.mcut || pl.ccut)) MD_TRY(grow(m, st, f->flist, b_list));
+  if (pl.thin && (pl.pcut || pl.mcut || pl.ccut)) MD_TRY(grow(m, st, f->plist, b_list));
+  if (pl.pcut && (pl.mcut || pl.ccut)) MD_TRY(grow(m, st, f->klist, b_list));
+  if (pl.mcut && pl.ccut) MD_TRY(grow(m, st, f->mlist, b_list));
+  // The chain scatter -> outlier removal -> voxel thinning -> plane extraction (mode 1 / 2) -> matching (mode 1 / 2) -> clustering (mode 1), or scatter -> decimation (the decimation is the thinning, with the
   // faces of the model's face home): every stage but the last writes a list of the model's own, of which every row is usable;
   // the last one writes `fin` below the caller's capacity. Nothing else knows which stage that is.
   ListRows l = rows_of(f->vlist.p);
@@ -1172,7 +1272,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.filt) {
     OutlierParams& u = pl.u;
     reads(u, l);
-    const bool last = !pl.thin && !pl.pcut && !pl.ccut;
+    const bool last = !pl.thin && !pl.pcut && !pl.mcut && !pl.ccut;
     if (!last) l = rows_of(f->flist.p);
     writes(u, last ? pl.fin : l);
     u.n = (int)rows; u.B = B; u.radius = c.outl->radius; u.k = c.outl->min_neighbours; u.capacity = last ? (long)out.capacity : rows;
@@ -1180,16 +1280,23 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   if (pl.thin) {
     VoxelParams& v = pl.v;
     reads(v, l);
-    const bool last = !pl.pcut && !pl.ccut;
+    const bool last = !pl.pcut && !pl.mcut && !pl.ccut;
     if (!last) l = rows_of(f->plist.p);
     writes(v, last ? pl.fin : l);
     v.n = (int)rows; v.B = B; v.voxel = c.vox->voxel; v.capacity = last ? (long)out.capacity : rows;
   }
   if (pl.pcut) {
     reads(pl.pn, l);
-    if (pl.ccut) l = rows_of(f->klist.p);
-    writes(pl.pn, pl.ccut ? l : pl.fin);
-    pl.pn.capacity = pl.ccut ? rows : (long)out.capacity;
+    const bool last = !pl.mcut && !pl.ccut;
+    if (!last) l = rows_of(f->klist.p);
+    writes(pl.pn, last ? pl.fin : l);
+    pl.pn.capacity = last ? (long)out.capacity : rows;
+  }
+  if (pl.mcut) {
+    reads(pl.mn, l);
+    if (pl.ccut) l = rows_of(f->mlist.p);
+    writes(pl.mn, pl.ccut ? l : pl.fin);
+    pl.mn.capacity = pl.ccut ? rows : (long)out.capacity;
   }
   if (pl.ccut) {
     reads(pl.cn, l);
@@ -1222,6 +1329,8 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     const md_points_cameras& t = c.rst->cam;
     pl.s.K = t.intrinsics; pl.s.focal = t.intrinsics ? nullptr : t.focal_px; pl.s.E = t.extrinsics;
   }
+  if (pl.host_target)  // the target has a kind of its own
+    MD_HIP(hipMemcpyAsync(f->mtarget.p, pl.host_target, (size_t)pl.mn.t * 12, hipMemcpyHostToDevice, pl.st));
   if (c.in_kind != MD_MEM_HOST) return MD_OK;
   MD_TRY(grow(m, pl.st, f->x, pl.npx * 3 * 4));
   if (c.rgb) MD_TRY(grow(m, pl.st, f->rgb, pl.npx * 3));
@@ -1340,6 +1449,14 @@ int run_clusters(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   return MD_OK;
 }
 
+// Matching: the list of the call -> mat's outputs; with mode 1 / 2 the model's own list -> the list outputs of the call, or the
+// list the clustering reads.
+int run_match(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+  MD_TRY(launch_match_points(pl.mn, m->points->mtable.p, pl.st));
+  m->points->mat_rows = pl.mn.n; m->points->mat_target = pl.mn.t; m->points->mat_ran = true;  // only a launched run has flags to read (points_match_overflow)
+  return MD_OK;
+}
+
 // Rendering: the list the call ends with and its device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
@@ -1371,7 +1488,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
     if (!s.live) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
-  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0}, clu_overflow = 0;
+  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0}, clu_overflow = 0, mat_overflow = 0;
   if (pl.deci) MD_TRY(d2h(&dec_overflow[0], voxel_flags(m->points->dtable.p, pl.d.v.n), 4));
   if (pl.deci) MD_TRY(d2h(&dec_overflow[1], decimate_flags(m->points->dtable.p, pl.d.v.n, pl.d.nf, pl.d.v.B), 4));
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
@@ -1384,7 +1501,12 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(d2h(&pl.clusters_kept, (pl.cn.stats ? pl.cn.stats : flags + kClusterStatsFlag) + 1, 4));
     if (pl.ccut) MD_TRY(d2h(&pl.cluster_rows, pl.cn.in_count + c.B, 4));
   }
+  if (pl.mat) {
+    MD_TRY(d2h(&mat_overflow, match_flags(m->points->mtable.p, pl.mn.n, pl.mn.t), 4));
+    if (pl.mcut) MD_TRY(d2h(&pl.match_rows, pl.mn.in_count + c.B, 4));
+  }
   MD_HIP(hipStreamSynchronize(pl.st));
+  if (mat_overflow) MD_FAIL(MD_ERR_HIP, "%s", kMatchRanOut);
   if (clu_overflow) MD_FAIL(MD_ERR_HIP, "%s", kClustersRanOut);
   if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "%s", kDecimateRanOut);
   if (outl_overflow) MD_FAIL(MD_ERR_HIP, "%s", kOutlierRanOut);
@@ -1420,6 +1542,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, long rows, hipSt
   if (pl.comp) MD_TRY(timed("points_components", run_components));
   if (pl.smo) MD_TRY(timed("points_smooth", run_smooth));
   if (pl.pln) MD_TRY(timed("points_planes", run_planes));
+  if (pl.mat) MD_TRY(timed("points_match", run_match));
   if (pl.clu) MD_TRY(timed("points_clusters", run_clusters));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
   if (c.rst) MD_TRY(timed("points_raster", run_raster));
@@ -1471,6 +1594,11 @@ std::vector<uintptr_t> points_graph_key(md_model_t m, const PointsCall& c, hipSt
     const md_points_clusters& k = *c.clu;
     key_add(key, 0x434c5553u, k.radius, k.min_neighbours, k.min_points, k.max_points, k.mode, k.table_capacity);
     key_add(key, k.label, k.cluster_size, k.cluster, k.table_label, k.table_size, k.box, k.stats, k.index, k.dropped);
+  }
+  if (match_on(c.mat)) {
+    const md_points_match& q = *c.mat;
+    key_add(key, 0x4d415443u, q.radius, q.target, q.target_rows, q.target_kind, q.mode, q.tol[0], q.tol[1], q.tol[2], q.tol[3]);
+    key_add(key, q.nearest, q.dist2, q.stats, q.index, q.dropped);
   }
   if (mesh_on(c.mesh))  // every output null: the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
@@ -1563,15 +1691,34 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (c.clu->mode != 0) {
       if (mesh_on(c.mesh) || decimate_on(c.dec) || components_on(c.comp) || smooth_on(c.smooth))
         MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 together with a mesh stage: the rows the faces name would vanish");
-      if ((voxel_on(c.vox) && (c.vox->index || c.vox->weight)) || (outlier_on(c.outl) && c.outl->index) || (planes_on(c.pln) && c.pln->index))
+      if ((voxel_on(c.vox) && (c.vox->index || c.vox->weight)) || (outlier_on(c.outl) && c.outl->index) || (planes_on(c.pln) && c.pln->index) ||
+          (match_on(c.mat) && c.mat->index))
         MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 together with index / weight of an earlier stage: the rows they are parallel to are not returned");
       if (planes_on(c.pln) && c.pln->mode == 0)
         MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 behind plane extraction with mode 0: the rows its label is parallel to are not returned");
+      if (match_on(c.mat) && c.mat->mode == 0)
+        MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 1 behind matching with mode 0: the rows `nearest` is parallel to are not returned");
     } else {
       if (!out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "clustering with mode 0 needs the list output `xyz`");
       if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "clustering together with decimation: the rows are renumbered; md_op_cluster_points serves the decimated list");
     }
     if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "clustering takes fewer than 2^30 rows, the list may have %ld", rows);
+  }
+  MD_TRY(check_match(c.mat, out, false));
+  if (match_on(c.mat)) {
+    if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "matching needs the list's `count`");
+    if (c.mat->mode != 0) {
+      if (mesh_on(c.mesh) || decimate_on(c.dec) || components_on(c.comp) || smooth_on(c.smooth))
+        MD_FAIL(MD_ERR_INVALID_ARG, "matching with mode 1 / 2 together with a mesh stage: the rows the faces name would vanish");
+      if ((voxel_on(c.vox) && (c.vox->index || c.vox->weight)) || (outlier_on(c.outl) && c.outl->index) || (planes_on(c.pln) && c.pln->index))
+        MD_FAIL(MD_ERR_INVALID_ARG, "matching with mode 1 / 2 together with index / weight of an earlier stage: the rows they are parallel to are not returned");
+      if (planes_on(c.pln) && c.pln->mode == 0)
+        MD_FAIL(MD_ERR_INVALID_ARG, "matching with mode 1 / 2 behind plane extraction with mode 0: the rows its label is parallel to are not returned");
+    } else {
+      if (!out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "matching with mode 0 needs the list output `xyz`");
+      if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "matching together with decimation: the rows are renumbered; md_op_match_points serves the decimated list");
+    }
+    if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "matching takes fewer than 2^30 rows, the list may have %ld", rows);
   }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));
@@ -1613,6 +1760,7 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   if (!m->graph_enabled) return body();
   // a graph only replays at the model's current input size (its workspace plan)
   bool eligible = c.in_kind == MD_MEM_DEVICE && c.out_kind == MD_MEM_DEVICE;
+  if (match_on(c.mat) && c.mat->target_kind == MD_MEM_HOST) eligible = false;  // a host target is copied with every call
   if (m->kind == 1) {
     int ps = 0, ch = 0, cw = 0;
     da3_frame_info(m, &ps, &ch, &cw);

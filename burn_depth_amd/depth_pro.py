@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, points
 from .config import DepthProConfig, InterpolationMethod, Precision
-from .points import FittedPlanes, PointCloud, PointClusters, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
+from .points import FittedPlanes, PointCloud, PointClusters, PointMatch, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
 
 
 class Device:
@@ -463,7 +463,7 @@ class DepthPro:
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
                      raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
                      components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None, clusters: Optional[dict] = None,
-                     **opts) -> PointCloud:
+                     match: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
@@ -518,7 +518,16 @@ class DepthPro:
         sizes, dense ids, the table of kept clusters with their boxes and the counters come back as `clusters` (`PointClusters`).
         mode "keep": the list the call returns (and render= sees) holds the rows of kept clusters and `index` names their rows in
         the list in front of the stage; not with mesh=, and behind planes= only with its mode "drop" / "keep". radius 0 or None:
-        the call without it."""
+        the call without it.
+        match (`md_points_match`, the one form that runs through `md_infer_points_match`): dict(target=, radius=, tol=(), mode="label"):
+        the nearest row of the reference cloud `target` ([T,3]; a tensor on the GPU is read where it lies, a numpy array or CPU
+        tensor is copied with every call) within `radius` for every row of the list the plane stage ends with, in front of
+        clusters=, so planes=dict(mode="drop"), match=dict(mode="unmatched"), clusters= drops the floor and what the reference
+        scan already holds and clusters the rest in one call; nearest, dist2, the counters (also the rows within each of up to four
+        tolerances) come back as `match` (`PointMatch`). mode "matched" / "unmatched": the list the call returns holds the rows
+        with / without a counterpart and `index` names their rows in the list in front of the stage; not with mesh=, and behind
+        planes= only with its mode "drop" / "keep"; clusters=dict(mode="keep") only behind these two modes. radius 0 or None: the
+        call without it."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -531,8 +540,10 @@ class DepthPro:
             intrinsics=intrinsics, extrinsics=extrinsics, focal_px=f_px, dense=dense, compact=compact, capacity=capacity, out=out,
             conf_percentile=conf_percentile, view_rtol=view_rtol, min_views=min_views, normals=normals, normal_min_cos=normal_min_cos,
             voxel=voxel, render=render, mesh=mesh, raster=raster, outlier=outlier, decimate=decimate, components=components,
-            smooth=smooth, planes=planes, clusters=clusters, opts=opts)
-        if rq.clu is not None:
+            smooth=smooth, planes=planes, clusters=clusters, match=match, opts=opts)
+        if rq.mat is not None:
+            entry, parts = self._lib.md_infer_points_match, rq.match_args()
+        elif rq.clu is not None:
             entry, parts = self._lib.md_infer_points_clusters, rq.clusters_args()
         else:
             entry, parts = (self._lib.md_infer_points_planes, rq.planes_args()) if rq.pln is not None else (self._lib.md_infer_points_smooth, rq.args())

@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .depth_pro import Device, _stream_ptr
 from .points import (FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _cluster_mode_of, _clusters_struct, _f32, _i32, _lattice,
-                     _new_clusters, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
+                     _match_mode_of, _match_struct, _new_clusters, _new_match, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
                      _raster_request, _render_request, _u8, _view_filter_opts)
 
 
@@ -783,6 +783,50 @@ def cluster_points(dev: Device, xyz: torch.Tensor, radius: float, min_neighbours
     _lib.check(_lib.load().md_op_cluster_points(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(clu), C.byref(outs),
                                                 _p(out.normals) if cut else None, _stream_ptr(dev.ordinal)))
     return out
+
+
+def match_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius: float, tol=(), mode=0, conf: Optional[torch.Tensor] = None,
+                 rgb: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, out: Optional[PointCloud] = None,
+                 capacity: Optional[int] = None) -> PointCloud:
+    """md_op_match_points: a point list xyz [N,3] (+ conf [N], u8 rgb [N,3], normals [N,3]) and a reference cloud target [T,3], both
+    on the device -> `PointCloud` whose `match` (`PointMatch`) holds, for every row, the nearest target row within `radius`
+    (nearest int32 [N]: -1 none, -2 dropped; dist2 f32 [N]), stats int32 [8] (in-range rows, matched rows, target rows in the
+    grid, 0, rows within each of up to four tolerances `tol`) and dropped int32 [1]. mode "label" / 0: nothing else. "matched" /
+    1, "unmatched" / 2: also the rows with / without a counterpart in input order, xyz / conf / rgb / normals [capacity, ..],
+    index int32 [capacity] and count int32 [2]; capacity defaults to N. `out`: a PointCloud of an earlier call to write into
+    again. Bit-identical to `pipeline.match_points`."""
+    xyz, _, conf, rgb, normals, N, _ = _list_inputs(xyz, None, conf, rgb, normals)
+    target = target.to(device=xyz.device, dtype=torch.float32).contiguous().reshape(-1, 3)
+    cut = _match_mode_of(mode) != 0
+    cap = N if capacity is None else int(capacity)
+    fresh = out is None
+    out, outs = _list_outputs(out, xyz.device, cap, conf, rgb, normals, vertex=cut)
+    if fresh:
+        out.match = _new_match(xyz.device, N)
+    assert out.match is not None and (out.match.nearest is None or int(out.match.nearest.shape[0]) >= N), "nearest covers the input rows"
+    out.match.index = out.index if cut else None
+    mat = _match_struct(dict(radius=radius, tol=tol, mode=mode), _p(target), int(target.shape[0]), _lib.MD_MEM_DEVICE, out.match, out.index)
+    _lib.check(_lib.load().md_op_match_points(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(mat), C.byref(outs),
+                                              _p(out.normals) if cut else None, _stream_ptr(dev.ordinal)))
+    return out
+
+
+def cloud_distance(dev: Device, a: torch.Tensor, b: torch.Tensor, radius: float, tol=()) -> dict:
+    """Precision, recall, F-score and Chamfer distance of cloud a [N,3] against the reference b [T,3] within `radius`: two
+    `match_points` calls, a against b and b against a. -> dict(stats_ab, stats_ba: the two int32 [8] count sets as lists;
+    precision, recall, fscore: one float per tolerance, precision = rows of a within tol of b / N, recall = rows of b within tol
+    of a / T; chamfer: the mean distance of the matched rows of a plus that of b (nan for a direction without a match)). The
+    counts are the operator's and bit-identical to the host reference; the Chamfer mean is a torch float reduction over sqrt(dist2)
+    and lies outside the bit contract."""
+    ab = match_points(dev, a, b, radius, tol=tol).match
+    ba = match_points(dev, b, a, radius, tol=tol).match
+    sa, sb = ab.stats.cpu().tolist(), ba.stats.cpu().tolist()
+    N, T = int(ab.nearest.shape[0]), int(ba.nearest.shape[0])
+    precision = [sa[4 + t] / N if N else 0.0 for t in range(len(tol))]
+    recall = [sb[4 + t] / T if T else 0.0 for t in range(len(tol))]
+    fscore = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(precision, recall)]
+    mean = lambda m: float(m.dist2[m.nearest >= 0].double().sqrt().mean()) if bool((m.nearest >= 0).any()) else float("nan")  # noqa: E731
+    return dict(stats_ab=sa, stats_ba=sb, precision=precision, recall=recall, fscore=fscore, chamfer=mean(ab) + mean(ba))
 
 
 def decimate_mesh(dev: Device, xyz: torch.Tensor, faces: torch.Tensor, voxel: float, conf: Optional[torch.Tensor] = None,

@@ -1157,6 +1157,112 @@ def cluster_points(xyz, radius, min_neighbours=0, min_points=1, max_points=0, mo
     return out
 
 
+@dataclass
+class HostMatch:
+    nearest: np.ndarray              # int32 [N] over the input rows: the nearest target row within the radius, -1 none, -2 dropped
+    dist2: np.ndarray                # f32 [N]: its squared distance; the bit pattern 0x7F800000 for -1 and -2 rows
+    stats: np.ndarray                # int32 [8]: in-range rows, matched rows, target rows in the grid, 0, rows within tol[0..4)
+    dropped: int                     # source rows that are not finite or outside the grid
+    xyz: Optional[np.ndarray]        # mode 1 / 2: f32 [M,3] the matched / unmatched rows, in ascending input row; None with mode 0
+    conf: Optional[np.ndarray]       # f32 [M]
+    rgb: Optional[np.ndarray]        # uint8 [M,3]
+    normals: Optional[np.ndarray]    # f32 [M,3]
+    index: Optional[np.ndarray]      # int32 [M]: the source row
+    count: Optional[np.ndarray]      # int32 [B+1]: survivors per view, then their total
+
+
+def _grid_cells(p, rs):
+    """The outlier removal's cells of the rows p f32 [N,3] at side rs -> (in range [N] bool, biased cells of the in-range rows
+    int64 [M,3], their keys int64 [M])."""
+    half = np.float32(1 << 20)
+    with np.errstate(all="ignore"):
+        c = np.floor(p / rs)
+        ok = np.isfinite(p).all(1) & (c >= -half).all(1) & (c < half).all(1)
+    cell = c[ok].astype(np.int64) + (1 << 20)  # biased: 0 .. 2^21 - 1 on every axis
+    return ok, cell, (cell[:, 0] << 42) | (cell[:, 1] << 21) | cell[:, 2]
+
+
+def match_points(xyz, target, radius, tol=(), mode=0, conf=None, rgb=None, normals=None, counts=None) -> HostMatch:
+    """The host reference of md_op_match_points / md_infer_points_match (include/mi_depth.h states the contract): for every row of
+    xyz [N,3] the nearest row of target [T,3] among its candidates: the target rows whose cell (side `radius`, the cells of
+    `radius_outliers`) differs from the row's by at most 1 on every axis AND whose d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius
+    in f32. The nearest has the smallest key (bits(d2) << 32) | target row; -1 without a candidate, -2 for a row that is not
+    finite or outside the grid. tol: up to four tolerances in (0, radius] (0: unused); stats[4 + t] counts the matched rows with
+    d2 <= tol[t]*tol[t]. mode 1 / 2 also returns the matched / unmatched in-range rows in input order. The device kernels
+    (kernels/match.hip) give the same bits. The target is sorted by cell key; every source row makes 27 lookups and walks the
+    buckets, all rows at once. counts: the rows of every view of the input, [B] (default: one view)."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 3)
+    N, T = len(p), len(q)
+    rs = np.float32(radius)
+    with np.errstate(all="ignore"):
+        r2 = rs * rs
+    if not np.isfinite(rs) or not rs > 0 or not np.isfinite(r2):
+        raise ValueError("radius and its square must be finite and > 0")
+    tols = np.zeros(4, np.float32)
+    if len(tol) > 4:
+        raise ValueError("at most four tolerances")
+    tols[:len(tol)] = np.asarray(tol, np.float32)
+    if not (tols >= 0).all() or not (tols <= rs).all():
+        raise ValueError("a tolerance is 0 or lies in (0, radius]")
+    if mode not in (0, 1, 2):
+        raise ValueError("mode is 0, 1 or 2")
+    if N >= 1 << 30 or T >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows")
+    ok, cells, _ = _grid_cells(p, rs)
+    t_ok, _, t_key = _grid_cells(q, rs)
+    order = np.argsort(t_key, kind="stable")
+    trow = np.nonzero(t_ok)[0][order].astype(np.uint64)  # the target row of every sorted entry
+    ks, ts = t_key[order], q[t_ok][order]
+    src = np.nonzero(ok)[0]
+    ps = p[src]
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    best = np.full(len(src), none, np.uint64)
+    for d in np.ndindex(3, 3, 3):
+        c = cells + (np.array(d, np.int64) - 1)
+        inside = ((c >= 0) & (c < (1 << 21))).all(1)  # a key with a coordinate outside the grid is skipped
+        qk = (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
+        lo = np.searchsorted(ks, qk, side="left")
+        hi = np.where(inside, np.searchsorted(ks, qk, side="right"), lo)
+        live = np.nonzero(lo < hi)[0]
+        at = lo[live]
+        while len(live):  # step t of every bucket walk at once
+            with np.errstate(all="ignore"):
+                dx, dy, dz = (ts[at, a] - ps[live, a] for a in range(3))
+                d2 = ((dx * dx + dy * dy) + dz * dz).astype(np.float32)
+            hit = d2 <= r2
+            key = (d2[hit].view(np.uint32).astype(np.uint64) << np.uint64(32)) | trow[at[hit]]
+            best[live[hit]] = np.minimum(best[live[hit]], key)  # a row appears once per step
+            at = at + 1
+            go = at < hi[live]
+            live, at = live[go], at[go]
+    found = best != none
+    nearest = np.full(N, -2, np.int32)
+    nearest[src] = np.where(found, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+    bits = np.full(N, 0x7F800000, np.uint32)
+    bits[src] = np.where(found, (best >> np.uint64(32)).astype(np.uint32), np.uint32(0x7F800000))
+    dist2 = bits.view(np.float32)
+    stats = np.zeros(8, np.int32)
+    stats[0], stats[1], stats[2] = len(src), int(found.sum()), int(t_ok.sum())
+    matched = nearest >= 0
+    for t in range(4):
+        if tols[t] > 0:
+            stats[4 + t] = int((matched & (dist2 <= tols[t] * tols[t])).sum())
+    out = HostMatch(nearest, dist2, stats, int(N - ok.sum()), None, None, None, None, None, None)
+    if mode == 0:
+        return out
+    index = np.nonzero(matched if mode == 1 else nearest == -1)[0].astype(np.int32)
+    if counts is None:
+        bounds = np.array([0, N], np.int64)
+    else:
+        bounds = np.minimum(np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64).reshape(-1))]), N)
+    per_view = np.diff(np.searchsorted(index, bounds, side="left"))
+    take = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)[index]  # noqa: E731
+    out.xyz, out.conf, out.rgb, out.normals = p[index], take(conf, np.float32, (N,)), take(rgb, np.uint8, (N, 3)), take(normals, np.float32, (N, 3))
+    out.index, out.count = index, np.concatenate([per_view, [len(index)]]).astype(np.int32)
+    return out
+
+
 def render_points(xyz, H, W, intrinsics=None, extrinsics=None, focal_px=None, rgb=None, count=None, *, pixel_offset=0.0, z_near=0.0,
                   z_far=0.0, radius=0) -> HostRender:
     """The host reference of md_op_render_points / md_infer_points_render (include/mi_depth.h states the contract): the list xyz
@@ -1575,7 +1681,8 @@ class AnyDepthModel:
         filter, `md_infer_points_filtered`), normals= / normal_min_cos= (`md_infer_points_normals`), voxel= (`md_infer_points_voxel`)
         render= (`md_infer_points_render`), mesh= (`md_infer_points_mesh`), raster= (`md_infer_points_raster`), outlier=
         (`md_infer_points_outlier`), decimate= (`md_infer_points_decimate`), components= (`md_infer_points_components`) and
-        smooth= (`md_infer_points_smooth`), planes= (`md_infer_points_planes`) and clusters= (`md_infer_points_clusters`) included."""
+        smooth= (`md_infer_points_smooth`), planes= (`md_infer_points_planes`), clusters= (`md_infer_points_clusters`) and match=
+        (`md_infer_points_match`) included."""
         return self.model.infer_points(x, **kw)
 
     def infer_views(self, x):

@@ -80,6 +80,19 @@ class PointClusters:
 
 
 @dataclass
+class PointMatch:
+    """What `md_op_match_points` / `md_infer_points_match` return (include/mi_depth.h). Device tensors: nearest int32 and dist2 f32
+    [rows of the input list] (the nearest target row within the radius, -1 none, -2 dropped; its squared distance, +inf for -1 and
+    -2 rows), stats int32 [8] (in-range rows, matched rows, target rows in the grid, 0, rows within tol[0..4)), dropped int32 [1].
+    `index` is the source row of every row the call kept (modes "matched" / "unmatched"): the same tensor as the cloud's `index`."""
+    nearest: Optional[torch.Tensor] = None
+    dist2: Optional[torch.Tensor] = None
+    stats: Optional[torch.Tensor] = None
+    dropped: Optional[torch.Tensor] = None
+    index: Optional[torch.Tensor] = None
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -107,7 +120,9 @@ class PointCloud:
     `FittedPlanes` of the list; with its mode "drop" / "keep" the list holds the rows without / of a plane and index is the
     source row of every output row in the list in front of the stage. With `clusters=` (`md_op_cluster_points` /
     `md_infer_points_clusters`): clusters = the `PointClusters` of the list the plane stage ends with; with its mode "keep" the
-    list holds the rows of kept clusters and index is their source row likewise. None when not asked for."""
+    list holds the rows of kept clusters and index is their source row likewise. With `match=` (`md_op_match_points` /
+    `md_infer_points_match`): match = the `PointMatch` of the list the plane stage ends with against the reference cloud; with
+    its mode "matched" / "unmatched" the list holds those rows and index is their source row likewise. None when not asked for."""
     point_map: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
@@ -135,6 +150,7 @@ class PointCloud:
     smooth: Optional["SmoothedMesh"] = None
     planes: Optional["FittedPlanes"] = None
     clusters: Optional["PointClusters"] = None
+    match: Optional["PointMatch"] = None
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -452,6 +468,77 @@ def _points_clusters(dev, rows: int, clusters: dict, out: PointCloud, fresh: boo
     return _clusters_struct(clusters, out.clusters, out.index)
 
 
+MATCH_MODES = {"label": 0, "matched": 1, "unmatched": 2}
+_MATCH_KEYWORDS = {"target", "radius", "tol", "mode"}
+
+
+def _match_mode_of(mode) -> int:
+    """0 label, 1 matched, 2 unmatched, by name or number; 0 also for a name the builder will refuse."""
+    return MATCH_MODES.get(mode, 0) if isinstance(mode, str) else int(mode)
+
+
+def _match_mode(match: Optional[dict]) -> int:
+    """The mode of a match= request; 0 for one that is off."""
+    return _match_mode_of(match.get("mode", 0)) if match and match.get("radius") else 0
+
+
+def _new_match(dev, rows: int) -> "PointMatch":
+    """Fresh tensors for a list of `rows` rows."""
+    return PointMatch(nearest=_i32(dev, rows), dist2=_f32(dev, rows), stats=_i32(dev, 8), dropped=_i32(dev, 1))
+
+
+def _match_target(dev, target):
+    """The target of a match= request -> (pointer, rows, memory kind, keep-alive): a tensor on `dev` is read where it lies, by
+    address; a numpy array or a CPU tensor is a host target, which the model call copies."""
+    if isinstance(target, torch.Tensor) and target.is_cuda:
+        t = target
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != torch.device(dev):
+            t = t.to(device=dev, dtype=torch.float32).contiguous()
+        t = t.reshape(-1, 3)
+        return _ptr(t), int(t.shape[0]), _lib.MD_MEM_DEVICE, t
+    host = np.ascontiguousarray(target.numpy() if isinstance(target, torch.Tensor) else target, dtype=np.float32).reshape(-1, 3)
+    return (C.c_void_p(host.ctypes.data) if len(host) else None), len(host), _lib.MD_MEM_HOST, host
+
+
+def _match_struct(match: dict, target, target_rows: int, target_kind: int, found: "PointMatch", index: Optional[torch.Tensor]) -> "_lib.MdPointsMatch":
+    """md_points_match of the keywords target=, radius=, tol= (up to four tolerances), mode= ("label" / "matched" / "unmatched" or
+    0 / 1 / 2) writing into `found` and `index`. The ranges are the library's to refuse."""
+    unknown = set(match) - _MATCH_KEYWORDS
+    if unknown or "radius" not in match:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"match= takes {sorted(_MATCH_KEYWORDS)} and needs radius; unknown {sorted(unknown)}")
+    mode = match.get("mode", 0)
+    if isinstance(mode, str):
+        if mode not in MATCH_MODES:
+            raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"match mode {mode!r}: one of {sorted(MATCH_MODES)}")
+        mode = MATCH_MODES[mode]
+    tol = [float(v) for v in (match.get("tol") or ())]
+    if len(tol) > 4:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "match= takes at most four tolerances")
+    return _lib.MdPointsMatch(float(match["radius"]), target, int(target_rows), int(target_kind), int(mode), (C.c_float * 4)(*tol),
+                              _ptr(found.nearest), _ptr(found.dist2), _ptr(found.stats), _ptr(index) if mode else None, _ptr(found.dropped))
+
+
+def _points_match(dev, rows: int, match: dict, out: PointCloud, fresh: bool, keep: list):
+    """md_points_match for `out` with the stage on. rows: the rows the list in front of the stage can have. With `fresh` the
+    tensors of `out.match` are created, the row outputs over the rows of the list the stage reads (the list of the call, or with
+    mode "matched" / "unmatched" the one in front of it) and, with those modes, index beside the list; otherwise the ones `out`
+    carries are written again. The target's keep-alive joins `keep`."""
+    if out.xyz is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "match= needs the compacted list")
+    if match.get("target") is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "match= needs target")
+    cut = _match_mode(match) != 0
+    if fresh or out.match is None:
+        cap = int(out.xyz.shape[0])
+        out.match = _new_match(dev, rows if cut else cap)
+        if cut:
+            out.index = _i32(dev, cap)
+    ptr, T, kind, alive = _match_target(dev, match["target"])
+    keep.append(alive)
+    out.match.index = out.index if cut else None
+    return _match_struct(match, ptr, T, kind, out.match, out.index)
+
+
 def _target_cameras(dev, intrinsics, extrinsics, focal_px):
     """The target cameras of a rendering or a rasterisation -> (T, md_points_cameras, keep-alive). T is the number of cameras given."""
     src = intrinsics if intrinsics is not None else focal_px
@@ -505,6 +592,7 @@ class PointsRequest(NamedTuple):
     keep: list
     pln: Optional["_lib.MdPointsPlanes"] = None  # behind `keep`: `md_infer_points_planes` takes it behind `args()`
     clu: Optional["_lib.MdPointsClusters"] = None  # `md_infer_points_clusters` takes it behind `planes_args()`
+    mat: Optional["_lib.MdPointsMatch"] = None  # `md_infer_points_match` takes it behind `clusters_args()`
 
     def args(self) -> list:
         """The struct arguments of `md_infer_points_smooth`, by reference, NULL for the parts not asked for."""
@@ -513,6 +601,10 @@ class PointsRequest(NamedTuple):
     def clusters_args(self) -> list:
         """The struct arguments of `md_infer_points_clusters`: those of `planes_args()`, then the cluster part."""
         return self.planes_args() + [C.byref(self.clu) if self.clu is not None else None]
+
+    def match_args(self) -> list:
+        """The struct arguments of `md_infer_points_match`: those of `clusters_args()`, then the match part."""
+        return self.clusters_args() + [C.byref(self.mat) if self.mat is not None else None]
 
     def planes_args(self) -> list:
         """The struct arguments of `md_infer_points_planes`: those of `args()`, then the plane part."""
@@ -525,7 +617,7 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
                     normals: bool = False, normal_min_cos: float = 0.0, voxel: Optional[float] = None, render: Optional[dict] = None,
                     mesh=None, raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
                     components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None,
-                    clusters: Optional[dict] = None, opts: Optional[dict] = None) -> PointsRequest:
+                    clusters: Optional[dict] = None, match: Optional[dict] = None, opts: Optional[dict] = None) -> PointsRequest:
     """The keyword set of `infer_points` / `ops.unproject` (their docstrings say what each means) as a `PointsRequest`. opts: the
     fields of `md_points_opts`; want_rgb / want_conf / want_depth: the call can fill those outputs. A part is None when it was
     not asked for, by keyword or by an `out` that carries its tensors; fresh tensors are allocated unless `out` is given.
@@ -539,9 +631,10 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     o = _points_opts(**(opts or {}))
     res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
     cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
-    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = None
+    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = mat = None
     keep_rows = _cluster_mode(clusters) != 0  # the clustering writes the list: index is its own
-    cut = _plane_mode(planes) != 0 or keep_rows  # a later stage writes the list: an earlier stage's index is not returned
+    match_rows = _match_mode(match) != 0  # the matching writes the list, in front of the clustering
+    cut = _plane_mode(planes) != 0 or match_rows or keep_rows  # a later stage writes the list: an earlier stage's index is not returned
     if conf_percentile or view_rtol or min_views:
         fo = _view_filter_opts(o.pixel_offset, o.depth_min, o.depth_max, conf_percentile, view_rtol, min_views)
     if normals or normal_min_cos or res.normal_map is not None or res.normals is not None:
@@ -588,12 +681,20 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
         smo = _lib.MdPointsSmooth()
     if planes and planes.get("planes", 1):
         pln = _points_planes(dev, _lattice(B, H, W, o.stride)[1], planes, res, fresh)
-        if keep_rows:
+        if keep_rows or match_rows:
             pln.index = None
     elif planes is not None:
         pln = _lib.MdPointsPlanes()
+    if match and match.get("radius"):  # in front of the clustering, whose index replaces this one
+        keep = list(keep)
+        mat = _points_match(dev, _lattice(B, H, W, o.stride)[1], match, res, fresh, keep)
+        if keep_rows:
+            mat.index = None
+            res.match.index = None
+    elif match is not None:
+        mat = _lib.MdPointsMatch()
     if clusters and clusters.get("radius"):
         clu = _points_clusters(dev, _lattice(B, H, W, o.stride)[1], clusters, res, fresh)
     elif clusters is not None:
         clu = _lib.MdPointsClusters()
-    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu)
+    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu, mat)

@@ -1128,6 +1128,84 @@ int md_infer_points_clusters(md_model_t m, const float* nchw, int B, int H, int 
                              const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
                              const md_points_clusters* clu, int out_kind, void* stream);
 
+/* ---- point path: the nearest row of a reference cloud for every row of a point list -------------------------------------------
+ * A source list xyz f32 [N,3] with optional parallel rows conf f32 [N], rgb u8 [N,3] and normals f32 [N,3], and a target list
+ * f32 [T,3] -> for every source row the nearest target row within `radius`, counters for precision / recall, and, with mode 1 /
+ * 2, the source rows with / without a counterpart. Every output is a selection on a deterministic f32 value, so nothing depends
+ * on the order in which threads arrive; pipeline.match_points restates it in numpy bit for bit. N and T < 2^30. f32, one
+ * rounded operation per step, no fused multiply-add. Denormals are outside the contract.
+ *   cells: the outlier removal's (md_points_outlier above), word for word, on both lists: cell c_a = floorf(p_a / radius), the
+ *     same range test and 63-bit key. Target rows that are not finite or out of range are not in the grid. Source rows that are
+ *     not finite or out of range are dropped: nearest = -2, counted in `dropped`.
+ *   candidates: target row j is a candidate of in-range source row i when their cells differ by at most 1 on every axis AND
+ *     d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius, inclusive, with dx = t_x - s_x and so on. The cell condition is part of the
+ *     definition.
+ *   nearest: the candidate with the smallest 64-bit key (bits(d2) << 32) | j. d2 >= +0 and is never NaN here, so the bit order
+ *     is the numeric order; ties go to the smallest target row; duplicate target rows are legal. No candidate: nearest = -1.
+ *   nearest int32 [N] / dist2 f32 [N] over the INPUT rows: the target row (-1 none, -2 dropped) and its d2, the bit pattern
+ *     0x7F800000 for -1 and -2 rows.
+ *   tol[4]: each entry 0 (unused) or in (0, radius]. A matched row is within tol[t] when d2 <= tol[t]*tol[t].
+ *   stats int32 [8], true counts whatever the capacities: [0] in-range source rows, [1] matched rows, [2] target rows in the
+ *     grid, [3] 0, [4..8) rows within tol[0..4), 0 for an unused entry. Precision at tol[t] is stats[4+t] / N; recall is the same
+ *     figure of the swapped call.
+ *   mode 0: labels only. mode 1 keeps the matched rows, mode 2 the in-range rows without a match; dropped rows leave in both.
+ *     Compaction is the cluster stage's mode 1: the survivors in ascending input row, every given row copied unchanged, index =
+ *     the source row; count[b] = the survivors of view b, count[B] = their total M, also when M exceeds `capacity`: then only the
+ *     first `capacity` rows are written and the memory behind them stays untouched. All views of a call share the target.
+ * The grid is the clustering's, 16-byte bucket entries (xyz and the target row), built from the target and sized by T. */
+typedef struct md_points_match {
+  float radius;          /* 0 = the stage is off (md_infer_points_match) */
+  const float* target;   /* f32 [target_rows,3] */
+  int64_t target_rows;
+  int32_t target_kind;   /* MD_MEM_HOST | MD_MEM_DEVICE; the operator takes device only */
+  int32_t mode;          /* 0 label, 1 keep matched, 2 keep unmatched */
+  float tol[4];
+  int32_t* nearest;      /* int32 [N] over the INPUT rows. NULL = skip */
+  float* dist2;          /* f32 [N]. NULL = skip */
+  int32_t* stats;        /* int32 [8]. NULL = skip */
+  int32_t* index;        /* int32 [capacity], modes 1 / 2; needs count. NULL = skip */
+  int32_t* dropped;      /* int32 [1]. NULL = skip */
+} md_points_match;
+
+/* The stand-alone operator on caller device lists, modelled on md_op_cluster_points: the N rows are one view. Of `out` the fields
+ * xyz, rgb, conf, count (int32 [2]: M twice) and capacity are used, with mode 1 / 2 only; the others must be NULL; normals_out
+ * [capacity,3] takes the normals rows. Everything is enqueued on `stream`; the call returns after the stream has drained,
+ * because its scratch is freed on return. T == 0 is legal: every in-range row gets -1. Errors, before any launch: dev / mat /
+ * out NULL, xyz_dev NULL with N > 0, radius not finite or <= 0 or radius*radius not finite, a tol entry negative, not finite or
+ * above radius, mode outside 0..2, target_rows < 0, target NULL with target_rows > 0, target_kind not MD_MEM_DEVICE, N < 0,
+ * capacity < 0, a compacted output (xyz, rgb, conf, normals_out, index) without count or with mode 0, an rgb / conf / normals
+ * output without that input row, a dense output or out->depth set -> MD_ERR_INVALID_ARG; N or target_rows >= 2^30 ->
+ * MD_ERR_SHAPE. A probe loop that ran out of table (impossible at load <= 0.5) -> MD_ERR_HIP after the launches. */
+int md_op_match_points(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev,
+                       int64_t N, const md_points_match* mat, const md_points_outputs* out, float* normals_out, void* stream);
+/* md_infer_points_clusters with the matching behind the plane extraction and in front of the clustering (launch-order name
+ * "points_match"), so "drop the floor, drop what the reference scan already holds, cluster the rest" is one call. mode 0: the
+ * caller's list is unchanged and nearest / dist2 are over its rows, [out->capacity], of which the first min(count[B], capacity)
+ * are written; it needs out->xyz and the list's count. mode 1 / 2: the stage is a link of the list chain scatter -> outlier
+ * removal -> thinning -> planes (mode 1 / 2) -> match (mode 1 / 2) -> clusters (mode 1): the last link writes the caller's list
+ * and out->count, every other one a grow-only list of the model; nearest / dist2 are over the rows of the stage's input list
+ * (at most B ceil(H/stride) ceil(W/stride)) and mat->index names its rows. mat's pointers are of out_kind; the target is of
+ * target_kind, and a host target is copied into a grow-only buffer of the model with every call. A device target is read by
+ * address: a graph replay sees its current contents. The scratch comes from grow-only buffers of the model: after the first
+ * call of a shape nothing is allocated. mat NULL or radius == 0 (its pointers then NULL): md_infer_points_clusters on the same
+ * arguments, the same launches and bits. The graph key contains every field of mat. Errors as md_infer_points_clusters's,
+ * plus, before any launch: the operator's refusals of radius (0 allowed), tol, mode and the target (target_kind may be
+ * MD_MEM_HOST), the stage without the list's count, index without mode 1 / 2, any of mat's pointers with radius == 0, mode 1 / 2
+ * together with a mesh, decimation, components or smoothing (the rows the faces name would vanish) or with an earlier stage's
+ * index (voxel thinning's, the outlier removal's, the plane stage's) or behind a plane stage with mode 0, mode 0 without the
+ * list output out->xyz or together with decimation, clustering with mode 1 behind matching with mode 0 (its rows would not be
+ * the rows `nearest` is parallel to) or together with mat->index -> MD_ERR_INVALID_ARG; a list or a target of >= 2^30 rows ->
+ * MD_ERR_SHAPE. With host outputs a probe loop that ran out of table -> MD_ERR_HIP; with device outputs
+ * md_model_query(m, "match_overflow") reads the flag of the last call that was launched or captured, as "clusters_overflow"
+ * does. */
+int md_infer_points_match(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                          const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                          const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                          const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                          const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                          const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
+                          const md_points_clusters* clu, const md_points_match* mat, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

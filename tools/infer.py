@@ -62,6 +62,14 @@ the cosine C of that axis (the floor with the up axis). One image without `--mes
 writes the dense cluster id of every point as the int property `label` of the file (-1 none; it replaces the plane labels), `keep` writes
 the points of kept clusters (not with `--mesh`, nor behind `--plane-mode label`). One image without `--mesh` runs inside the model call
 (`md_infer_points_clusters`); with `--views` or `--mesh`, `ops.cluster_points` runs on the final points.
+`--match-ply REF.ply --match-radius R [--match-tol T ...] [--match-mode label|matched|unmatched]` (with `--ply`): the nearest point of the
+reference cloud REF.ply within R for every point of the cloud, on the device, behind `--planes` and in front of `--cluster-radius`, so
+`--planes P --plane-mode drop --match-ply REF.ply --match-radius R --match-mode unmatched --cluster-radius C` drops the floor and what the
+reference scan already holds and clusters the rest; the counters and, per tolerance T (up to four, each at most R), the precision (points
+within T of the reference / all points) are printed. `label` writes "has a counterpart" (1 / 0) as the int property `label` of the file
+(`--cluster-radius` replaces it), `matched` / `unmatched` write the points with / without a counterpart (not with `--mesh`, nor behind
+`--plane-mode label`, nor `label` in front of `--cluster-mode keep`). One image without `--mesh` runs inside the model call
+(`md_infer_points_match`); with `--views` or `--mesh`, `ops.match_points` runs on the final points.
 `--smooth ITER [--smooth-step S] [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]` (with `--ply --mesh`): Taubin smoothing
 of the mesh on the device, ITER lambda | mu step pairs (`--smooth-mu 0`: ITER Laplacian steps) on an integer lattice of side S, the open
 boundary pinned unless freed. The file holds the smoothed positions and, with `--normals`, the vertex normals of the smoothed faces. One
@@ -155,6 +163,21 @@ def print_clusters(found) -> None:
     for i, (l, n, b) in enumerate(zip(found.table_label[:rows].cpu().tolist(), found.table_size[:rows].cpu().tolist(), found.box[:rows].cpu().tolist())):
         print(f"Cluster {i}: {n} points, label {l}, box {b[0]:.6g} {b[1]:.6g} {b[2]:.6g} .. {b[3]:.6g} {b[4]:.6g} {b[5]:.6g}")
     print(f"Clusters: {stats[0]} found, {stats[1]} kept, {stats[2]} noise points, {stats[3]} points in kept clusters")
+
+
+def match_request(a, dev) -> dict:
+    """the match= keywords of --match-ply: the reference cloud goes to the device once"""
+    import torch
+    from burn_depth_amd import pipeline as P
+    ref = np.ascontiguousarray(P.read_ply(a.match_ply)[0], dtype=np.float32)
+    return dict(target=torch.from_numpy(ref).to(dev), radius=a.match_radius, tol=tuple(a.match_tol), mode=a.match_mode)
+
+
+def print_match(found, a, rows: int) -> None:
+    stats = found.stats.cpu().tolist()
+    print(f"Match: {stats[0]} points in range, {stats[1]} with a counterpart within {a.match_radius:.6g}, {stats[2]} reference points in the grid")
+    for t, tol in enumerate(a.match_tol):
+        print(f"Precision at {tol:.6g}: {stats[4 + t] / rows if rows else 0.0:.6f} ({stats[4 + t]} of {rows} points)")
 
 
 def print_planes(fitted) -> None:
@@ -277,7 +300,21 @@ def run_views(a) -> int:
             else:
                 xyz, col, _ = pc.points()
                 nrm = pc.normals[:xyz.shape[0]] if a.normals else None
-        if a.cluster_radius > 0:  # on the points the plane step left
+        if a.match_ply:  # on the points the plane step left
+            try:
+                req = match_request(a, xyz.device)
+                pc = ops.match_points(dev, xyz, req.pop("target"), **req, rgb=col, normals=nrm)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            print_match(pc.match, a, int(xyz.shape[0]))
+            if a.match_mode == "label":
+                label = (pc.match.nearest >= 0).to(torch.int32).cpu().numpy()
+                pc.xyz, pc.rgb, pc.count = xyz, col, torch.tensor([xyz.shape[0]], dtype=torch.int32, device=xyz.device)  # what --render-pose draws
+            else:
+                xyz, col, _ = pc.points()
+                nrm = pc.normals[:xyz.shape[0]] if a.normals else None
+        if a.cluster_radius > 0:  # on the points the match step left
             try:
                 pc = ops.cluster_points(dev, xyz, **clusters_request(a), rgb=col, normals=nrm)
             except _lib.MdError as e:
@@ -377,6 +414,11 @@ def main(argv=None) -> int:
     ap.add_argument("--cluster-max-points", type=int, default=0, help="--cluster-radius: the points a kept cluster has at most (0 = no limit)")
     ap.add_argument("--cluster-mode", choices=["label", "keep"], default="label",
                     help="--cluster-radius: write the dense cluster id of every point as the PLY property `label`, or the points of kept clusters")
+    ap.add_argument("--match-ply", default="", help="--ply: match the cloud against the points of this reference .ply (md_infer_points_match, ops.match_points)")
+    ap.add_argument("--match-radius", type=float, default=0.0, help="--match-ply: the search radius, > 0")
+    ap.add_argument("--match-tol", type=float, nargs="+", default=[], metavar="T", help="--match-ply: up to four tolerances in (0, radius] whose precision is printed")
+    ap.add_argument("--match-mode", choices=["label", "matched", "unmatched"], default="label",
+                    help="--match-ply: write `has a counterpart` as the PLY property `label`, or the points with / without a counterpart")
     ap.add_argument("--plane-up", type=float, nargs=3, metavar=("X", "Y", "Z"), help="--planes: only planes whose normal lies within --plane-up-cos of this axis")
     ap.add_argument("--plane-up-cos", type=float, default=0.9, help="--plane-up: the smallest |cosine| between a plane's normal and the axis")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
@@ -400,6 +442,12 @@ def main(argv=None) -> int:
     if a.cluster_radius != 0 and (not a.cluster_radius > 0 or not a.ply or (a.cluster_mode == "keep" and (a.mesh or (a.planes and a.plane_mode == "label")))):
         print("--cluster-radius is > 0 and goes with --ply; --cluster-mode keep not with --mesh (the faces name the rows) nor behind --plane-mode label",
               file=sys.stderr)
+        return 2
+    if a.match_ply and (not a.match_radius > 0 or not a.ply or len(a.match_tol) > 4 or
+                        (a.match_mode != "label" and (a.mesh or (a.planes and a.plane_mode == "label"))) or
+                        (a.match_mode == "label" and a.cluster_radius > 0 and a.cluster_mode == "keep")):
+        print("--match-ply goes with --ply and --match-radius > 0 and takes at most four --match-tol; --match-mode matched / unmatched not with --mesh "
+              "(the faces name the rows) nor behind --plane-mode label; --match-mode label not in front of --cluster-mode keep", file=sys.stderr)
         return 2
     if a.planes != 0 and (not 1 <= a.planes <= 8 or not a.ply or (a.mesh and a.plane_mode != "label")):
         print("--planes is a plane count in 1..8 and goes with --ply; --plane-mode drop / keep not with --mesh (the faces name the rows)", file=sys.stderr)
@@ -474,9 +522,11 @@ def main(argv=None) -> int:
                                     smooth=smooth)
             planes_in_call = bool(a.planes) and not a.mesh
             clusters_in_call = a.cluster_radius > 0 and not a.mesh
-            if planes_in_call or clusters_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stages then run inside the call
+            match_in_call = bool(a.match_ply) and not a.mesh
+            if planes_in_call or clusters_in_call or match_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stages then run inside the call
                 pc = model.infer_points(x, **call, voxel=a.voxel, render=render, planes=planes_request(a, pc.points()[0]) if planes_in_call else None,
                                         clusters=clusters_request(a) if clusters_in_call else None,
+                                        match=match_request(a, x.device) if match_in_call else None,
                                         outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None)
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
@@ -498,6 +548,16 @@ def main(argv=None) -> int:
                 print_planes(fitted)
                 if a.plane_mode == "label":
                     label = fitted.label[:xyz.shape[0]].cpu().numpy()
+            if a.match_ply:  # beside a mesh: the operator labels the vertices of the file
+                if match_in_call:
+                    near = pc.match
+                else:
+                    req = match_request(a, xyz.device)
+                    near = ops.match_points(Device(0), xyz, req.pop("target"), **req).match
+                rows = int(near.stats[0] + near.dropped[0]) if match_in_call else int(xyz.shape[0])  # the rows the stage read
+                print_match(near, a, rows)
+                if a.match_mode == "label":
+                    label = (near.nearest[:xyz.shape[0]] >= 0).to(torch.int32).cpu().numpy()
             if a.cluster_radius > 0:  # beside a mesh: the operator labels the vertices of the file
                 found = pc.clusters if clusters_in_call else ops.cluster_points(Device(0), xyz, **clusters_request(a)).clusters
                 print_clusters(found)
