@@ -124,6 +124,14 @@ class MdPointsMatch(C.Structure):
                 ("dropped", C.c_void_p)]
 
 
+class MdPointsRegister(C.Structure):
+    """md_points_register (include/mi_depth.h)."""
+    _fields_ = [("radius", C.c_float), ("target", C.c_void_p), ("target_rows", C.c_int64), ("target_kind", C.c_int32),
+                ("iterations", C.c_int32), ("min_pairs", C.c_int32), ("apply", C.c_int32), ("rot_eps", C.c_double), ("trans_eps", C.c_double),
+                ("init", C.c_void_p), ("transform", C.c_void_p), ("pairs", C.c_void_p), ("sum_d2", C.c_void_p), ("stats", C.c_void_p),
+                ("dropped", C.c_void_p), ("nearest", C.c_void_p), ("dist2", C.c_void_p)]
+
+
 class MdRenderOpts(C.Structure):
     """md_render_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
@@ -320,6 +328,7 @@ SYMBOLS = {
     "md_op_fit_planes": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsPlanes), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_op_cluster_points": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsClusters), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_op_match_points": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsMatch), C.POINTER(MdPointsOutputs), _P, _P]),
+    "md_op_register_points": (_I, [_P, _P, _P, C.c_int64, C.POINTER(MdPointsRegister), _P, _P, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
@@ -430,7 +439,7 @@ _POINTS_HEAD = [MdViewFilterOpts, MdPointsOpts, MdPointsOutputs]
 _POINTS_PARTS = [("normals", MdPointsNormals), ("voxel", MdPointsVoxel), ("render", MdPointsRender), ("mesh", MdPointsMesh),
                  ("raster", MdPointsRaster), ("outlier", MdPointsOutlier), ("decimate", MdPointsDecimate), ("components", MdPointsComponents),
                  ("smooth", MdPointsSmooth), ("planes", MdPointsPlanes), ("clusters", MdPointsClusters),
-                 ("match", MdPointsMatch)]
+                 ("match", MdPointsMatch), ("register", MdPointsRegister)]
 SYMBOLS["md_infer_points"] = _infer_points(*_POINTS_HEAD[1:])
 SYMBOLS["md_infer_points_filtered"] = _infer_points(*_POINTS_HEAD)
 SYMBOLS.update({f"md_infer_points_{name}": _infer_points(*_POINTS_HEAD, *(p for _, p in _POINTS_PARTS[:i + 1]))

@@ -5,7 +5,8 @@
 // on a deterministic f32 value: nothing depends on the order of arrival. Contraction is off in the whole file (Makefile); the
 // float steps are outlier.hip's and pipeline.match_points restates them in numpy.
 //
-// The grid is built from the TARGET and sized by it; the source rows only read it. The launches:
+// The grid is built from the TARGET and sized by it; the source rows only read it. The build kernels' bodies and the 27-cell
+// walk live in match_grid.h, which kernels/register.hip shares. The launches:
 //   reset    table keys to all ones, per-slot count / start / fill to 0, the flags, the eight counters and `dropped`
 //   insert, alloc   as in outlier.hip, over the target rows: the cell table and the start of every cell's bucket. A target row
 //            that is not finite or out of range is in no bucket
@@ -19,7 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "voxel_math.h"
+#include "match_grid.h"
 
 namespace md {
 
@@ -29,12 +30,7 @@ constexpr int kFlagWords = 64;
 constexpr unsigned kNoDistance = 0x7F800000u;  // dist2 of a row without a nearest
 
 struct MatchScratch {  // the parts of the scratch buffer, 256-byte aligned
-  unsigned long long* keys;
-  unsigned* cnt;    // target rows of the slot's cell
-  unsigned* start;  // first bucket row of the cell
-  unsigned* fill;   // rows of the cell placed so far
-  int* slot;        // [t] the target row's slot, -1 not in the grid
-  uint4* bucket;    // [t] x y z bits and the target row, cell by cell
+  MatchGrid g;
   unsigned long long* bits;
   int* counts;
   int* offsets;
@@ -43,15 +39,10 @@ struct MatchScratch {  // the parts of the scratch buffer, 256-byte aligned
 };
 
 MatchScratch carve(void* base, int n, int t) {
-  const size_t slots = voxel_table_slots(t), nb = (size_t)tiles_of(n);
+  const size_t nb = (size_t)tiles_of(n);
   MatchScratch s;
   Carver c(base);
-  s.keys = c.take<unsigned long long>(slots);
-  s.cnt = c.take<unsigned>(slots);
-  s.start = c.take<unsigned>(slots);
-  s.fill = c.take<unsigned>(slots);
-  s.slot = c.take<int>((size_t)t);
-  s.bucket = c.take<uint4>((size_t)t);
+  s.g = carve_match_grid(c, t);
   s.bits = c.take<unsigned long long>(nb * kTileWords);
   s.counts = c.take<int>(nb);
   s.offsets = c.take<int>(nb + 1);
@@ -60,17 +51,11 @@ MatchScratch carve(void* base, int n, int t) {
   return s;
 }
 
-// slots is a multiple of 1024: every thread writes four slots with 16-byte stores
+// The four build kernels are match_grid.h's bodies with this file's flag words.
 __global__ void __launch_bounds__(kTileThreads) match_reset_kernel(ulonglong2* __restrict__ keys, uint4* __restrict__ cnt, uint4* __restrict__ start,
                                                                uint4* __restrict__ fill, size_t quads, int* __restrict__ flags,
                                                                int32_t* __restrict__ stats, int32_t* __restrict__ dropped) {
-  fill_keys(keys, 2 * quads);
-  const size_t stride = (size_t)gridDim.x * kTileThreads;
-  for (size_t q = (size_t)blockIdx.x * kTileThreads + threadIdx.x; q < quads; q += stride) {
-    cnt[q] = make_uint4(0u, 0u, 0u, 0u);
-    start[q] = make_uint4(0u, 0u, 0u, 0u);
-    fill[q] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  match_grid_reset(keys, cnt, start, fill, quads);
   if (blockIdx.x == 0 && threadIdx.x < 8) stats[threadIdx.x] = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     flags[0] = 0;
@@ -80,62 +65,23 @@ __global__ void __launch_bounds__(kTileThreads) match_reset_kernel(ulonglong2* _
   }
 }
 
-// grid ceil(t / 256) over the target rows. mask = slots - 1. stats[2] counts the rows that enter the grid.
+// stats[2] counts the rows that enter the grid
 __global__ void __launch_bounds__(kTileThreads) match_insert_kernel(const float* __restrict__ target, int t, float radius,
                                                                 unsigned long long* __restrict__ keys, unsigned* __restrict__ cnt,
                                                                 int* __restrict__ slot, unsigned long long mask, int* __restrict__ flags,
                                                                 int32_t* __restrict__ stats) {
-  const long j = (long)blockIdx.x * kTileThreads + threadIdx.x;
-  if (j >= t) return;
-  const float x = target[j * 3], y = target[j * 3 + 1], z = target[j * 3 + 2];
-  unsigned long long key = 0ull;
-  const bool in_range = grid_cell_key(x, y, z, radius, &key);
-  long h = -1;
-  if (in_range) {
-    h = grid_claim(keys, mask, key);
-    if (h < 0) flags[0] = 1;  // every slot holds another key: cannot happen at load <= 0.5
-  }
-  wave_count_add(h >= 0, stats + 2);  // lanes have already left: the first active one adds
-  if (h >= 0) atomicAdd(cnt + h, 1u);
-  slot[j] = (int)h;
+  match_grid_insert(target, t, radius, keys, cnt, slot, mask, flags, stats + 2);
 }
 
-// grid slots / 256 (slots is a multiple of 1024: every wave is full). The buckets of a wave's 64 slots lie behind one another.
 __global__ void __launch_bounds__(kTileThreads) match_alloc_kernel(const unsigned* __restrict__ cnt, unsigned* __restrict__ start,
                                                                int* __restrict__ flags) {
-  const size_t h = (size_t)blockIdx.x * kTileThreads + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const unsigned c = cnt[h];
-  unsigned incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
-  const unsigned total = __shfl(incl, 63, 64);
-  if (total == 0u) return;  // the whole wave
-  unsigned base = 0u;
-  if (lane == 0) base = (unsigned)atomicAdd(flags + 2, (int)total);
-  base = __shfl(base, 0, 64);
-  if (c) start[h] = base + (incl - c);
+  match_grid_alloc(cnt, start, flags + 2);
 }
 
-// grid ceil(t / 256). A bucket row at or beyond t would mean the counts changed under the launches: the flag, and the row is
-// in no bucket (the cell's count then names a row nobody wrote, so the call is refused by its flag).
 __global__ void __launch_bounds__(kTileThreads) match_fill_kernel(const float* __restrict__ target, int t, const unsigned* __restrict__ start,
                                                               unsigned* __restrict__ fill, const int* __restrict__ slot,
                                                               uint4* __restrict__ bucket, int* __restrict__ flags) {
-  const long j = (long)blockIdx.x * kTileThreads + threadIdx.x;
-  if (j >= t) return;
-  const int h = slot[j];
-  if (h < 0) return;
-  const unsigned at = start[h] + atomicAdd(fill + h, 1u);
-  if (at >= (unsigned)t) {
-    flags[0] = 1;
-    return;
-  }
-  const float* src = target + j * 3;
-  bucket[at] = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), (unsigned)j);
+  match_grid_fill(target, t, start, fill, slot, bucket, flags);
 }
 
 // grid tiles of the source, the classify side of tile_compact.h. The table and the buckets no longer change: loads only.
@@ -164,27 +110,7 @@ __global__ void __launch_bounds__(kTileThreads) match_nearest_kernel(MatchParams
       unsigned long long own = 0ull;
       in_range = grid_cell_key(x, y, z, p.radius, &own);
       unsigned long long best = ~0ull;
-      if (in_range) {
-        const int bx = (int)(own >> 42), by = (int)((own >> 21) & 0x1FFFFFull), bz = (int)(own & 0x1FFFFFull);
-        for (int c = 0; c < 27; ++c) {
-          const int qx = bx + c / 9 - 1, qy = by + (c / 3) % 3 - 1, qz = bz + c % 3 - 1;
-          if ((unsigned)qx >= 2u * kGridHalfInt || (unsigned)qy >= 2u * kGridHalfInt || (unsigned)qz >= 2u * kGridHalfInt) continue;
-          const long g = grid_find(keys, mask, grid_key(qx, qy, qz));
-          if (g < 0) continue;
-          const unsigned first = start[g];
-          unsigned last = first + cnt[g];
-          last = last < bucket_rows ? last : bucket_rows;
-          for (unsigned at = first; at < last; ++at) {
-            const uint4 e = bucket[at];
-            const float dx = __uint_as_float(e.x) - x, dy = __uint_as_float(e.y) - y, dz = __uint_as_float(e.z) - z;
-            const float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 <= r2) {  // d2 >= +0 and not NaN: the bit order is the numeric order
-              const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)e.w;
-              best = key < best ? key : best;
-            }
-          }
-        }
-      }
+      if (in_range) best = match_grid_nearest(x, y, z, own, r2, keys, cnt, start, bucket, mask, bucket_rows);
       hit = best != ~0ull;
       best_d2 = __uint_as_float(hit ? (unsigned)(best >> 32) : kNoDistance);
       if (p.nearest) p.nearest[i] = hit ? (int32_t)(unsigned)(best & 0xFFFFFFFFull) : (in_range ? -1 : -2);
@@ -237,21 +163,21 @@ int launch_match_points(const MatchParams& p, void* scratch, hipStream_t s) {
   const unsigned reset_grid = (unsigned)std::min<size_t>((quads + kTileThreads - 1) / kTileThreads, 256 * 32);
   int32_t* stats = p.stats ? p.stats : v.flags + kMatchStatsFlag;
   int32_t* dropped = p.dropped ? p.dropped : v.flags + 1;
-  hipLaunchKernelGGL(match_reset_kernel, dim3(reset_grid), dim3(kTileThreads), 0, s, (ulonglong2*)v.keys, (uint4*)v.cnt, (uint4*)v.start,
-                     (uint4*)v.fill, quads, v.flags, stats, p.dropped);
+  hipLaunchKernelGGL(match_reset_kernel, dim3(reset_grid), dim3(kTileThreads), 0, s, (ulonglong2*)v.g.keys, (uint4*)v.g.cnt, (uint4*)v.g.start,
+                     (uint4*)v.g.fill, quads, v.flags, stats, p.dropped);
   MD_HIP(hipGetLastError());
   if (p.t > 0) {
     const unsigned target_grid = (unsigned)((p.t + kTileThreads - 1) / kTileThreads);
-    hipLaunchKernelGGL(match_insert_kernel, dim3(target_grid), dim3(kTileThreads), 0, s, p.target, p.t, p.radius, v.keys, v.cnt, v.slot, mask, v.flags,
+    hipLaunchKernelGGL(match_insert_kernel, dim3(target_grid), dim3(kTileThreads), 0, s, p.target, p.t, p.radius, v.g.keys, v.g.cnt, v.g.slot, mask, v.flags,
                        stats);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(match_alloc_kernel, dim3((unsigned)(slots / kTileThreads)), dim3(kTileThreads), 0, s, v.cnt, v.start, v.flags);
+    hipLaunchKernelGGL(match_alloc_kernel, dim3((unsigned)(slots / kTileThreads)), dim3(kTileThreads), 0, s, v.g.cnt, v.g.start, v.flags);
     MD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(match_fill_kernel, dim3(target_grid), dim3(kTileThreads), 0, s, p.target, p.t, v.start, v.fill, v.slot, v.bucket, v.flags);
+    hipLaunchKernelGGL(match_fill_kernel, dim3(target_grid), dim3(kTileThreads), 0, s, p.target, p.t, v.g.start, v.g.fill, v.g.slot, v.g.bucket, v.flags);
     MD_HIP(hipGetLastError());
   }
   if (p.n > 0) {
-    hipLaunchKernelGGL(match_nearest_kernel, dim3(nb), dim3(kTileThreads), 0, s, p, v.keys, v.cnt, v.start, v.bucket, mask, v.bits, v.counts, stats,
+    hipLaunchKernelGGL(match_nearest_kernel, dim3(nb), dim3(kTileThreads), 0, s, p, v.g.keys, v.g.cnt, v.g.start, v.g.bucket, mask, v.bits, v.counts, stats,
                        dropped);
     MD_HIP(hipGetLastError());
   }

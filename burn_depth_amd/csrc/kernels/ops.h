@@ -366,6 +366,42 @@ size_t match_scratch_bytes(int n, int t);
 int launch_match_points(const MatchParams& p, void* scratch, hipStream_t s);
 const int32_t* match_flags(const void* scratch, int n, int t);
 
+// ---- rigid ICP registration onto a reference cloud (kernels/register.hip; md_op_register_points) ----
+// A source list xyz [n,3] (+ normals rows) and a target list [t,3] -> the 3x4 transform (R row-major, then t; f64) that moves the
+// source onto the target: the matching's grid (match_grid.h) built once from the target, then `iterations` times a step launch
+// (move every row under A, walk the 27 cells, fold the sixteen f64 leaves of every pair into fixed-shape tile sums) and a
+// one-workgroup reduce-and-solve launch (register_math.h), then an evaluation step under the final A and its reduce without a
+// solve. The sums have a fixed tree shape: nothing depends on the order of arrival. Every pointer is a device pointer.
+struct RegisterParams {
+  const float* xyz = nullptr;
+  const float* normals = nullptr;     // rotated into normals_out
+  const int32_t* in_count = nullptr;  // as VoxelParams::in_count
+  int n = 0;                          // rows the launches cover: the live count is min(in_count[B], n)
+  int B = 1;
+  const float* target = nullptr;  // [t,3]
+  int t = 0;
+  float radius = 0.f;
+  int iterations = 0;  // K, 1..64
+  int min_pairs = 3;
+  double rot_eps = 0., trans_eps = 0.;  // both 0: no stop test
+  double init[12] = {1., 0., 0., 0., 1., 0., 0., 0., 1., 0., 0., 0.};  // A_0
+  double* transform = nullptr;  // [12]; null: skip
+  int32_t* pairs = nullptr;     // [K + 1]; null: skip
+  double* sum_d2 = nullptr;     // [K + 1]; null: skip
+  int32_t* stats = nullptr;     // [8] solves done, status, in-range rows and pairs of the evaluation pass, target rows in the grid, 0, 0, 0; null: they live in the scratch
+  int32_t* dropped = nullptr;   // [1]; null: skip
+  float* xyz_out = nullptr;     // [n,3] the moved rows of the evaluation pass; may be xyz; null: skip
+  float* normals_out = nullptr; // [n,3]; null: skip
+  int32_t* nearest = nullptr;   // [n] as MatchParams::nearest under the final transform; null: skip
+  float* dist2 = nullptr;       // [n]; null: skip
+};
+// bytes of the scratch (the matching's table and buckets of the target | 128 B of tile sums and 4 B of pair count per source
+// tile | the transform | flags)
+size_t register_scratch_bytes(int n, int t);
+// flags[0] != 0 after the launches = a probe loop ran out of table
+int launch_register_points(const RegisterParams& p, void* scratch, hipStream_t s);
+const int32_t* register_flags(const void* scratch, int n, int t);
+
 // ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
 // A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour
 // image: clear, splat (atomicMin of (bits(p.z) << 32) | row over the footprint), resolve. Every pointer is a device pointer.

@@ -414,6 +414,7 @@ int md_model_query(md_model_t m, const char* key, int64_t* out) {
   else if (k == "outlier_overflow") return points_outlier_overflow(m, out);
   else if (k == "clusters_overflow") return points_clusters_overflow(m, out);
   else if (k == "match_overflow") return points_match_overflow(m, out);
+  else if (k == "register_overflow") return points_register_overflow(m, out);
   else if (k == "decimate_overflow") return points_decimate_overflow(m, out);
   else if (k == "da3_shape_builds") *out = da3_shape_builds(m);
   else if (k == "batch_invariant") *out = m->batch_invariant ? 1 : 0;
@@ -769,6 +770,22 @@ int md_infer_points_match(md_model_t m, const float* nchw, int B, int H, int W, 
 int md_op_match_points(md_device_t dev, const float* xyz_dev, const float* conf_dev, const uint8_t* rgb_dev, const float* normals_dev, int64_t N,
                        const md_points_match* mat, const md_points_outputs* out, float* normals_out, void* stream) {
   return op_match_points(dev, PointList{xyz_dev, conf_dev, rgb_dev, normals_dev, N}, mat, out, normals_out, (hipStream_t)stream);
+}
+
+int md_infer_points_register(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb, const md_points_cameras* cam,
+                             const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                             const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh, const md_points_raster* rst,
+                             const md_points_outlier* outl, const md_points_decimate* dec, const md_points_components* comp,
+                             const md_points_smooth* smooth, const md_points_planes* pln, const md_points_clusters* clu, const md_points_match* mat,
+                             const md_points_register* reg, int out_kind, void* stream) {
+  PointsCall c{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh, rst};
+  c.outl = outl; c.dec = dec; c.comp = comp; c.smooth = smooth; c.pln = pln; c.clu = clu; c.mat = mat; c.reg = reg;
+  return infer_points(m, c, (hipStream_t)stream);
+}
+
+int md_op_register_points(md_device_t dev, const float* xyz_dev, const float* normals_dev, int64_t N, const md_points_register* reg,
+                           float* xyz_out, float* normals_out, void* stream) {
+  return op_register_points(dev, xyz_dev, normals_dev, N, reg, xyz_out, normals_out, (hipStream_t)stream);
 }
 
 int md_raster_inline_pixels(void) { return md::raster_inline_pixels(); }

@@ -401,6 +401,7 @@ struct PointsCall {
   const md_points_planes* pln = nullptr;       // given: plane extraction from the list the call ends with (pointers of out_kind); mode 1 / 2 writes that list
   const md_points_clusters* clu = nullptr;     // given: clustering of the list behind the plane stage (pointers of out_kind); mode 1 writes that list
   const md_points_match* mat = nullptr;        // given: matching against a reference cloud between the plane stage and the clustering (pointers of out_kind, the target of its own kind); mode 1 / 2 writes the list
+  const md_points_register* reg = nullptr;     // given: rigid registration onto a reference cloud directly in front of the matching, on the list it reads; apply moves that list in place
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
@@ -431,6 +432,9 @@ int op_cluster_points(md_device_t dev, const PointList& in, const md_points_clus
 // in: the rows, one view; out's list fields and normals_out with mat->mode 1 / 2 only
 int op_match_points(md_device_t dev, const PointList& in, const md_points_match* mat, const md_points_outputs* out, float* normals_out,
                     hipStream_t stream);
+// xyz [N,3] (+ normals): the rows, one view; xyz_out (may be xyz) / normals_out [N,3] or null
+int op_register_points(md_device_t dev, const float* xyz, const float* normals, int64_t N, const md_points_register* reg, float* xyz_out,
+                       float* normals_out, hipStream_t stream);
 // in.xyz / in.rgb: the list; count: its device count word or null
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream);
@@ -443,6 +447,7 @@ int points_voxel_overflow(md_model_t m, int64_t* out);
 int points_outlier_overflow(md_model_t m, int64_t* out);
 int points_clusters_overflow(md_model_t m, int64_t* out);
 int points_match_overflow(md_model_t m, int64_t* out);
+int points_register_overflow(md_model_t m, int64_t* out);
 // likewise for the decimation of the model's last md_infer_points_decimate (the vertex table's flag or the face table's)
 int points_decimate_overflow(md_model_t m, int64_t* out);
 int op_filter_views(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_view_filter_opts* o,

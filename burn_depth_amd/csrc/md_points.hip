@@ -68,6 +68,8 @@ struct md_model_s::PointsState {
   md::GrowBuf<void> mtable;       // md_infer_points_match: the matching's scratch (match_scratch_bytes)
   md::GrowBuf<void> mlist;        // the list it writes with mode 1 / 2 when the clustering (mode 1) follows, laid out as vlist
   md::GrowBuf<float> mtarget;     // the device copy of a host target [T,3]
+  md::GrowBuf<void> rtable;       // md_infer_points_register: the registration's scratch (register_scratch_bytes)
+  md::GrowBuf<float> rtarget;     // the device copy of its host target [T,3]
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
@@ -76,6 +78,8 @@ struct md_model_s::PointsState {
   long clu_table = 0;             // with the table capacity its scratch was carved for
   int mat_rows = 0, mat_target = 0;  // likewise for the matching and mtable: the source rows and the target rows; mat_ran: a call ran
   bool mat_ran = false;
+  int reg_rows = 0, reg_target = 0;  // likewise for the registration and rtable
+  bool reg_ran = false;
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
   float* f_home(int B) const { return cams.p + (size_t)B * 21; }
@@ -333,6 +337,7 @@ ClustersParams make_clusters(const md_points_clusters& f) {
 }
 
 bool match_on(const md_points_match* q) { return q && q->radius != 0.f; }
+bool register_on(const md_points_register* q) { return q && q->radius != 0.f; }
 
 // model call: radius == 0 is the call without the stage and takes none of its outputs; the operator takes a device target only
 int check_match(const md_points_match* q, const md_points_outputs* out, bool op) {
@@ -490,6 +495,11 @@ uint32_t fbits(float v) {
 
 // A graph replay key grows word by word: pointers by address, integers by value, floats by bit pattern.
 uintptr_t key_word(float v) { return fbits(v); }
+uintptr_t key_word(double v) {
+  uint64_t u;
+  memcpy(&u, &v, 8);
+  return (uintptr_t)u;
+}
 template <typename T>
 uintptr_t key_word(T v) { return (uintptr_t)v; }
 template <typename... T>
@@ -535,6 +545,7 @@ const char kOutlierRanOut[] = "outlier removal: a probe loop ran out of table sl
 const char kDecimateRanOut[] = "decimation: a probe loop ran out of table slots";
 const char kClustersRanOut[] = "clustering: a probe loop ran out of table slots";
 const char kMatchRanOut[] = "matching: a probe loop ran out of table slots";
+const char kRegisterRanOut[] = "registration: a probe loop ran out of table slots";
 
 // Every operator's last refusal and first act: the device, made current, and the stream its launches take.
 int op_begin(md_device_t dev, hipStream_t stream, hipStream_t* st) {
@@ -742,6 +753,66 @@ int op_match_points(md_device_t dev, const PointList& in, const md_points_match*
   return scratch.finish_flags(launch_match_points(p, scratch.p, st), match_flags(scratch.p, p.n, p.t), nullptr, kMatchRanOut);
 }
 
+namespace {
+
+// The refusals of md_points_register before any launch: the matching's of radius, target and sizes, then the stage's own.
+int check_register(const md_points_register* q, bool op) {
+  if (!q) return MD_OK;
+  if (!std::isfinite(q->radius) || q->radius < 0.f || (op && q->radius == 0.f) || !std::isfinite(q->radius * q->radius))
+    MD_FAIL(MD_ERR_INVALID_ARG, "radius = %g: it and its square must be finite and %s 0", (double)q->radius, op ? ">" : ">=");
+  if (q->radius == 0.f) {
+    if (q->transform || q->pairs || q->sum_d2 || q->stats || q->dropped || q->nearest || q->dist2)
+      MD_FAIL(MD_ERR_INVALID_ARG, "register outputs without a radius");
+    return MD_OK;
+  }
+  if (q->target_rows < 0) MD_FAIL(MD_ERR_INVALID_ARG, "target_rows = %lld is negative", (long long)q->target_rows);
+  if (q->target_rows > 0 && !q->target) MD_FAIL(MD_ERR_INVALID_ARG, "target pointer is null");
+  if (q->target_kind != MD_MEM_DEVICE && (op || q->target_kind != MD_MEM_HOST))
+    MD_FAIL(MD_ERR_INVALID_ARG, "target_kind = %d: %s", q->target_kind, op ? "the operator takes a device target" : "unknown memory kind");
+  if (q->apply != 0 && q->apply != 1) MD_FAIL(MD_ERR_INVALID_ARG, "apply = %d: 0 or 1", q->apply);
+  if (q->target_rows >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "registration takes fewer than 2^30 target rows, got %lld", (long long)q->target_rows);
+  if (q->iterations < 1 || q->iterations > 64) MD_FAIL(MD_ERR_INVALID_ARG, "iterations = %d outside 1..64", q->iterations);
+  if (q->min_pairs < 3) MD_FAIL(MD_ERR_INVALID_ARG, "min_pairs = %d: at least 3", q->min_pairs);
+  if (!(q->rot_eps >= 0.) || !std::isfinite(q->rot_eps) || !(q->trans_eps >= 0.) || !std::isfinite(q->trans_eps))
+    MD_FAIL(MD_ERR_INVALID_ARG, "rot_eps = %g, trans_eps = %g: finite and >= 0", q->rot_eps, q->trans_eps);
+  if (q->init)
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(q->init[i])) MD_FAIL(MD_ERR_INVALID_ARG, "init[%d] = %g is not finite", i, q->init[i]);
+  return MD_OK;
+}
+
+// the options and the outputs of the stage's own; the caller adds the rows
+RegisterParams make_register(const md_points_register& f) {
+  RegisterParams q;
+  q.radius = f.radius; q.target = f.target; q.t = (int)f.target_rows;
+  q.iterations = f.iterations; q.min_pairs = f.min_pairs; q.rot_eps = f.rot_eps; q.trans_eps = f.trans_eps;
+  if (f.init)
+    for (int i = 0; i < 12; ++i) q.init[i] = f.init[i];
+  q.transform = f.transform; q.pairs = f.pairs; q.sum_d2 = f.sum_d2; q.stats = f.stats; q.dropped = f.dropped;
+  q.nearest = f.nearest; q.dist2 = f.dist2;
+  return q;
+}
+
+}  // namespace
+
+int op_register_points(md_device_t dev, const float* xyz, const float* normals, int64_t N, const md_points_register* reg, float* xyz_out,
+                       float* normals_out, hipStream_t stream) {
+  if (!reg) MD_FAIL(MD_ERR_INVALID_ARG, "register options are null");
+  MD_TRY(check_register(reg, true));
+  if (N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)N);
+  if (normals_out && !normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
+  if (N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "registration takes fewer than 2^30 rows, got %lld", (long long)N);
+  if (N > 0 && !xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
+  hipStream_t st;
+  MD_TRY(op_begin(dev, stream, &st));
+  RegisterParams p = make_register(*reg);
+  p.xyz = xyz; p.normals = normals; p.n = (int)N; p.B = 1;
+  p.xyz_out = xyz_out; p.normals_out = normals_out;
+  OpScratch scratch(st);
+  MD_TRY(scratch.alloc(register_scratch_bytes(p.n, p.t)));
+  return scratch.finish_flags(launch_register_points(p, scratch.p, st), register_flags(scratch.p, p.n, p.t), nullptr, kRegisterRanOut);
+}
+
 int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
                      const md_points_outputs* out, float* normals_out, hipStream_t stream) {
   if (!dec) MD_FAIL(MD_ERR_INVALID_ARG, "decimation options are null");
@@ -890,6 +961,11 @@ int points_clusters_overflow(md_model_t m, int64_t* out) {
   return read_overflow(m, f && f->clu_rows && f->ktable.p ? clusters_flags(f->ktable.p, f->clu_rows, f->clu_table) : nullptr, nullptr, out);
 }
 
+int points_register_overflow(md_model_t m, int64_t* out) {
+  const md_model_s::PointsState* f = m->points;
+  return read_overflow(m, f && f->reg_ran && f->rtable.p ? register_flags(f->rtable.p, f->reg_rows, f->reg_target) : nullptr, nullptr, out);
+}
+
 int points_match_overflow(md_model_t m, int64_t* out) {
   const md_model_s::PointsState* f = m->points;
   return read_overflow(m, f && f->mat_ran && f->mtable.p ? match_flags(f->mtable.p, f->mat_rows, f->mat_target) : nullptr, nullptr, out);
@@ -969,6 +1045,10 @@ struct PointsPlan {
   int32_t plane_rows = 0;  // pcut with host outputs: the rows of the plane stage's input list, read back for pln->label's slot
   int32_t cluster_rows = 0;  // ccut with host outputs: the rows of the clustering's input list, for the slots of its row outputs
   int32_t clusters_kept = 0; // clu with host outputs: the kept clusters, for the slots of the table
+  bool reg = false;          // the registration is on, directly in front of the matching
+  RegisterParams rg;         // reg: launch_register_points', on the list the matching reads (or would read)
+  const float* host_reg_target = nullptr;  // reg with a host target: the caller's rows, which stage_inputs copies to rtarget
+  int32_t register_rows = 0; // reg on a list of the model's own, with host outputs: its rows, for the slots of nearest / dist2
   int32_t match_rows = 0;    // mcut with host outputs: the rows of the matching's input list, for the slots of its row outputs
   std::vector<OutSlot> slots;
 };
@@ -1091,6 +1171,22 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(k.table_size, pl.cn.table_size, 4, tcap, &pl.clusters_kept);
     slot(k.box, pl.cn.box, 24, tcap, &pl.clusters_kept);
   }
+  if (pl.reg) {  // nearest / dist2 lie over the rows of the list the stage reads, as the matching's
+    const md_points_register& q = *c.reg;
+    const size_t history = (size_t)q.iterations + 1;
+    slot(q.transform, pl.rg.transform, 8, 12);
+    slot(q.pairs, pl.rg.pairs, 4, history);
+    slot(q.sum_d2, pl.rg.sum_d2, 8, history);
+    slot(q.stats, pl.rg.stats, 4, 8);
+    slot(q.dropped, pl.rg.dropped, 4, 1);
+    if (pl.mcut || pl.ccut) {
+      slot(q.nearest, pl.rg.nearest, 4, list, &pl.register_rows);
+      slot(q.dist2, pl.rg.dist2, 4, list, &pl.register_rows);
+    } else {
+      slot(q.nearest, pl.rg.nearest, 4, cap, n);
+      slot(q.dist2, pl.rg.dist2, 4, cap, n);
+    }
+  }
   if (pl.mat) {  // the row outputs as the plane stage's label
     const md_points_match& q = *c.mat;
     slot(q.stats, pl.mn.stats, 4, 8);
@@ -1170,6 +1266,15 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
       pl.mn.target = f->mtarget.p;
     }
   }
+  pl.reg = register_on(c.reg);
+  if (pl.reg) {
+    pl.rg = make_register(*c.reg);
+    if (c.reg->target_kind == MD_MEM_HOST && pl.rg.t > 0) {
+      MD_TRY(grow(m, st, f->rtarget, (size_t)pl.rg.t * 12));
+      pl.host_reg_target = c.reg->target;
+      pl.rg.target = f->rtarget.p;
+    }
+  }
   if (c.rnd) {
     pl.r = make_render(c.rnd->T, c.rnd->H, c.rnd->W, c.rnd->opts);
     MD_TRY(grow(m, st, f->rkeys, render_scratch_bytes(c.rnd->T, c.rnd->H, c.rnd->W)));
@@ -1246,6 +1351,19 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(grow(m, st, m->points->mtable, match_scratch_bytes(q.n, q.t)));
     if (!pl.mcut) reads(q, pl.fin);  // mode 0: the rows of the call's list below its capacity
   }
+  // The registration reads the list the matching reads: the call's list below its capacity, or, when the matching or the
+  // clustering cuts, the model's own list in front of them, of which every row is usable. apply: the moved rows replace it.
+  auto registers = [&](const ListRows& l, bool own) -> int {
+    RegisterParams& q = pl.rg;
+    q.B = B; q.n = (int)(own ? rows : std::min<long>((long)out.capacity, rows));
+    q.xyz = l.xyz; q.normals = l.normals; q.in_count = l.count;
+    if (c.reg->apply) {
+      q.xyz_out = l.xyz;
+      q.normals_out = l.normals;
+    }
+    return grow(m, st, m->points->rtable, register_scratch_bytes(q.n, q.t));
+  };
+  if (pl.reg && !(pl.mcut || pl.ccut)) MD_TRY(registers(pl.fin, false));
   if (!own_list) return MD_OK;
   const bool want_rgb = out.rgb != nullptr, want_nrm = c.nrm && c.nrm->normals;
   const size_t b_xyz = align_up((size_t)rows * 12, 256), b_conf = pl.dual ? align_up((size_t)rows * 4, 256) : 0;
@@ -1292,6 +1410,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     writes(pl.pn, last ? pl.fin : l);
     pl.pn.capacity = last ? (long)out.capacity : rows;
   }
+  if (pl.reg && (pl.mcut || pl.ccut)) MD_TRY(registers(l, true));
   if (pl.mcut) {
     reads(pl.mn, l);
     if (pl.ccut) l = rows_of(f->mlist.p);
@@ -1329,6 +1448,8 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     const md_points_cameras& t = c.rst->cam;
     pl.s.K = t.intrinsics; pl.s.focal = t.intrinsics ? nullptr : t.focal_px; pl.s.E = t.extrinsics;
   }
+  if (pl.host_reg_target)
+    MD_HIP(hipMemcpyAsync(f->rtarget.p, pl.host_reg_target, (size_t)pl.rg.t * 12, hipMemcpyHostToDevice, pl.st));
   if (pl.host_target)  // the target has a kind of its own
     MD_HIP(hipMemcpyAsync(f->mtarget.p, pl.host_target, (size_t)pl.mn.t * 12, hipMemcpyHostToDevice, pl.st));
   if (c.in_kind != MD_MEM_HOST) return MD_OK;
@@ -1457,6 +1578,13 @@ int run_match(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   return MD_OK;
 }
 
+// Registration: the list the matching reads -> reg's outputs; with apply the moved rows replace that list's in place.
+int run_register(md_model_s* m, const PointsCall&, PointsPlan& pl) {
+  MD_TRY(launch_register_points(pl.rg, m->points->rtable.p, pl.st));
+  m->points->reg_rows = pl.rg.n; m->points->reg_target = pl.rg.t; m->points->reg_ran = true;  // only a launched run has flags to read (points_register_overflow)
+  return MD_OK;
+}
+
 // Rendering: the list the call ends with and its device count -> the target images.
 int run_render(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   RenderParams& r = pl.r;
@@ -1488,7 +1616,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   MD_TRY(d2h(c.out->depth, pl.depth, pl.npx * 4));
   for (const OutSlot& s : pl.slots)
     if (!s.live) MD_TRY(d2h(s.caller, s.home, s.rows * s.row_bytes));
-  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0}, clu_overflow = 0, mat_overflow = 0;
+  int32_t overflow = 0, outl_overflow = 0, dec_overflow[2] = {0, 0}, clu_overflow = 0, mat_overflow = 0, reg_overflow = 0;
   if (pl.deci) MD_TRY(d2h(&dec_overflow[0], voxel_flags(m->points->dtable.p, pl.d.v.n), 4));
   if (pl.deci) MD_TRY(d2h(&dec_overflow[1], decimate_flags(m->points->dtable.p, pl.d.v.n, pl.d.nf, pl.d.v.B), 4));
   if (pl.thin) MD_TRY(d2h(&overflow, voxel_flags(m->points->vtable.p, pl.v.n), 4));
@@ -1501,11 +1629,16 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     MD_TRY(d2h(&pl.clusters_kept, (pl.cn.stats ? pl.cn.stats : flags + kClusterStatsFlag) + 1, 4));
     if (pl.ccut) MD_TRY(d2h(&pl.cluster_rows, pl.cn.in_count + c.B, 4));
   }
+  if (pl.reg) {
+    MD_TRY(d2h(&reg_overflow, register_flags(m->points->rtable.p, pl.rg.n, pl.rg.t), 4));
+    if (pl.mcut || pl.ccut) MD_TRY(d2h(&pl.register_rows, pl.rg.in_count + c.B, 4));
+  }
   if (pl.mat) {
     MD_TRY(d2h(&mat_overflow, match_flags(m->points->mtable.p, pl.mn.n, pl.mn.t), 4));
     if (pl.mcut) MD_TRY(d2h(&pl.match_rows, pl.mn.in_count + c.B, 4));
   }
   MD_HIP(hipStreamSynchronize(pl.st));
+  if (reg_overflow) MD_FAIL(MD_ERR_HIP, "%s", kRegisterRanOut);
   if (mat_overflow) MD_FAIL(MD_ERR_HIP, "%s", kMatchRanOut);
   if (clu_overflow) MD_FAIL(MD_ERR_HIP, "%s", kClustersRanOut);
   if (dec_overflow[0] || dec_overflow[1]) MD_FAIL(MD_ERR_HIP, "%s", kDecimateRanOut);
@@ -1542,6 +1675,7 @@ int points_eager(md_model_s* m, const PointsCall& c, bool dual, long rows, hipSt
   if (pl.comp) MD_TRY(timed("points_components", run_components));
   if (pl.smo) MD_TRY(timed("points_smooth", run_smooth));
   if (pl.pln) MD_TRY(timed("points_planes", run_planes));
+  if (pl.reg) MD_TRY(timed("points_register", run_register));
   if (pl.mat) MD_TRY(timed("points_match", run_match));
   if (pl.clu) MD_TRY(timed("points_clusters", run_clusters));
   if (c.rnd) MD_TRY(timed("points_render", run_render));
@@ -1599,6 +1733,13 @@ std::vector<uintptr_t> points_graph_key(md_model_t m, const PointsCall& c, hipSt
     const md_points_match& q = *c.mat;
     key_add(key, 0x4d415443u, q.radius, q.target, q.target_rows, q.target_kind, q.mode, q.tol[0], q.tol[1], q.tol[2], q.tol[3]);
     key_add(key, q.nearest, q.dist2, q.stats, q.index, q.dropped);
+  }
+  if (register_on(c.reg)) {
+    const md_points_register& q = *c.reg;
+    key_add(key, 0x52454753u, q.radius, q.target, q.target_rows, q.target_kind, q.iterations, q.min_pairs, q.apply, q.rot_eps, q.trans_eps);
+    key_add(key, q.init != nullptr, q.transform, q.pairs, q.sum_d2, q.stats, q.dropped, q.nearest, q.dist2);
+    if (q.init)
+      for (int i = 0; i < 12; ++i) key_add(key, q.init[i]);  // init travels by value: its values are part of the captured launches
   }
   if (mesh_on(c.mesh))  // every output null: the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
@@ -1720,6 +1861,15 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     }
     if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "matching takes fewer than 2^30 rows, the list may have %ld", rows);
   }
+  MD_TRY(check_register(c.reg, false));
+  if (register_on(c.reg)) {
+    if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "registration needs the list's `count`");
+    if (!out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "registration needs the list output `xyz`");
+    if (decimate_on(c.dec)) MD_FAIL(MD_ERR_INVALID_ARG, "registration together with decimation: the rows are renumbered; md_op_register_points serves the decimated list");
+    if (c.reg->apply && (mesh_on(c.mesh) || components_on(c.comp) || smooth_on(c.smooth)))
+      MD_FAIL(MD_ERR_INVALID_ARG, "registration with apply together with a mesh stage: its faces and smoothed rows belong to the rows before they moved");
+    if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "registration takes fewer than 2^30 rows, the list may have %ld", rows);
+  }
   MD_TRY(check_mesh(c.mesh, out->count != nullptr, voxel_on(c.vox), B, H, W));
   MD_TRY(check_outlier(c.outl, out, false));
   if (outlier_on(c.outl)) {
@@ -1761,6 +1911,7 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
   // a graph only replays at the model's current input size (its workspace plan)
   bool eligible = c.in_kind == MD_MEM_DEVICE && c.out_kind == MD_MEM_DEVICE;
   if (match_on(c.mat) && c.mat->target_kind == MD_MEM_HOST) eligible = false;  // a host target is copied with every call
+  if (register_on(c.reg) && c.reg->target_kind == MD_MEM_HOST) eligible = false;
   if (m->kind == 1) {
     int ps = 0, ch = 0, cw = 0;
     da3_frame_info(m, &ps, &ch, &cw);

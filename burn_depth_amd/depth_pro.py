@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, points
 from .config import DepthProConfig, InterpolationMethod, Precision
-from .points import FittedPlanes, PointCloud, PointClusters, PointMatch, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
+from .points import FittedPlanes, PointCloud, PointClusters, PointMatch, PointRegistration, RasterisedMesh, RenderedPoints, SmoothedMesh  # noqa: F401 -- the point path's results, re-exported
 
 
 class Device:
@@ -463,7 +463,7 @@ class DepthPro:
                      normal_min_cos: float = 0.0, voxel: float = 0.0, render: Optional[dict] = None, mesh=None,
                      raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
                      components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None, clusters: Optional[dict] = None,
-                     match: Optional[dict] = None, **opts) -> PointCloud:
+                     match: Optional[dict] = None, register: Optional[dict] = None, **opts) -> PointCloud:
         """The model -> point cloud call: x [B,3,H,W] fp32 on this GPU -> the model's depth unprojected with its own cameras, or the
         caller's (Depth Pro: f_px = the known-focal call; intrinsics [B,3,3]; extrinsics [B,3,4] world-to-camera for world=True).
         rgb: u8 [B,H,W,3] device tensor to gather colours from. opts: pixel_offset, depth_min, depth_max, conf_min, edge_rtol, stride,
@@ -527,7 +527,13 @@ class DepthPro:
         tolerances) come back as `match` (`PointMatch`). mode "matched" / "unmatched": the list the call returns holds the rows
         with / without a counterpart and `index` names their rows in the list in front of the stage; not with mesh=, and behind
         planes= only with its mode "drop" / "keep"; clusters=dict(mode="keep") only behind these two modes. radius 0 or None: the
-        call without it."""
+        call without it.
+        register (`md_points_register`, the one form that runs through `md_infer_points_register`): dict(target=, radius=,
+        iterations=10, init=None, min_pairs=3, rot_eps=0, trans_eps=0, apply=False): rigid point-to-point ICP of the list match=
+        reads onto the reference cloud `target` (as match='s), directly in front of match=; the transform, the histories, the
+        counters, nearest and dist2 come back as `registration` (`PointRegistration`). apply=True: the moved rows (and normals)
+        replace that list in place, so match= and clusters= see the aligned cloud; not with mesh=. radius 0 or None: the call
+        without it."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -540,8 +546,10 @@ class DepthPro:
             intrinsics=intrinsics, extrinsics=extrinsics, focal_px=f_px, dense=dense, compact=compact, capacity=capacity, out=out,
             conf_percentile=conf_percentile, view_rtol=view_rtol, min_views=min_views, normals=normals, normal_min_cos=normal_min_cos,
             voxel=voxel, render=render, mesh=mesh, raster=raster, outlier=outlier, decimate=decimate, components=components,
-            smooth=smooth, planes=planes, clusters=clusters, match=match, opts=opts)
-        if rq.mat is not None:
+            smooth=smooth, planes=planes, clusters=clusters, match=match, register=register, opts=opts)
+        if rq.reg is not None:
+            entry, parts = self._lib.md_infer_points_register, rq.register_args()
+        elif rq.mat is not None:
             entry, parts = self._lib.md_infer_points_match, rq.match_args()
         elif rq.clu is not None:
             entry, parts = self._lib.md_infer_points_clusters, rq.clusters_args()

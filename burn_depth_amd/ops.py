@@ -9,9 +9,9 @@ import torch
 
 from . import _lib
 from .depth_pro import Device, _stream_ptr
-from .points import (FittedPlanes, PointCloud, RasterisedMesh, RenderedPoints, SmoothedMesh, _cluster_mode_of, _clusters_struct, _f32, _i32, _lattice,
-                     _match_mode_of, _match_struct, _new_clusters, _new_match, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
-                     _raster_request, _render_request, _u8, _view_filter_opts)
+from .points import (FittedPlanes, PointCloud, PointRegistration, RasterisedMesh, RenderedPoints, SmoothedMesh, _cluster_mode_of, _clusters_struct, _f32, _i32, _lattice,
+                     _match_mode_of, _match_struct, _new_clusters, _new_match, _new_registration, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
+                     _raster_request, _register_struct, _render_request, _u8, _view_filter_opts)
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -809,6 +809,35 @@ def match_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius: f
     _lib.check(_lib.load().md_op_match_points(dev.handle, _p(xyz), _p(conf), _p(rgb), _p(normals), N, C.byref(mat), C.byref(outs),
                                               _p(out.normals) if cut else None, _stream_ptr(dev.ordinal)))
     return out
+
+
+def register_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius: float, iterations: int = 10, init=None, min_pairs: int = 3,
+                    rot_eps: float = 0.0, trans_eps: float = 0.0, normals: Optional[torch.Tensor] = None, apply: bool = False,
+                    xyz_out: Optional[torch.Tensor] = None) -> PointRegistration:
+    """md_op_register_points: rigid point-to-point ICP of the list xyz [N,3] onto the reference cloud target [T,3], both on the
+    device, pairing within `radius` for `iterations` rounds from the transform `init` (twelve f64, R row-major then t, or a 3x4 /
+    4x4 matrix; None: the identity) -> `PointRegistration`: transform f64 [12], the per-pass pairs / sum_d2 histories, stats,
+    dropped, nearest / dist2 under the final transform. rot_eps / trans_eps > 0 stop the rounds once a solve changes R and t by no
+    more than that. apply: also xyz, the moved rows, and (with normals=) the rotated normals; xyz_out: the tensor the moved rows
+    go to, which may be `xyz` itself. Bit-identical to `pipeline.register_points`."""
+    xyz, _, _, _, normals, N, _ = _list_inputs(xyz, None, None, None, normals)
+    target = target.to(device=xyz.device, dtype=torch.float32).contiguous().reshape(-1, 3)
+    K = int(iterations)
+    d = xyz.device
+    res = _new_registration(d, N, K)
+    if xyz_out is not None:
+        assert xyz_out.is_cuda and xyz_out.dtype == torch.float32 and xyz_out.is_contiguous() and xyz_out.numel() == 3 * N, "xyz_out is f32 [N,3]"
+        res.xyz = xyz_out
+    elif apply:
+        res.xyz = _f32(d, N, 3)
+    if (apply or xyz_out is not None) and normals is not None:
+        res.normals = _f32(d, N, 3)
+    keep: list = []
+    reg = _register_struct(dict(radius=radius, iterations=K, init=init, min_pairs=min_pairs, rot_eps=rot_eps, trans_eps=trans_eps), _p(target),
+                           int(target.shape[0]), _lib.MD_MEM_DEVICE, res, keep)
+    _lib.check(_lib.load().md_op_register_points(dev.handle, _p(xyz), _p(normals), N, C.byref(reg), _p(res.xyz), _p(res.normals),
+                                                 _stream_ptr(dev.ordinal)))
+    return res
 
 
 def cloud_distance(dev: Device, a: torch.Tensor, b: torch.Tensor, radius: float, tol=()) -> dict:

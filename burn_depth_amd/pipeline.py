@@ -1182,6 +1182,46 @@ def _grid_cells(p, rs):
     return ok, cell, (cell[:, 0] << 42) | (cell[:, 1] << 21) | cell[:, 2]
 
 
+def _match_grid(q, rs):
+    """The matching's grid of the target q f32 [T,3] at cell side rs -> (in range [T] bool, sorted cell keys, the rows in that
+    order, their target rows uint64). The target is sorted by cell key."""
+    t_ok, _, t_key = _grid_cells(q, rs)
+    order = np.argsort(t_key, kind="stable")
+    trow = np.nonzero(t_ok)[0][order].astype(np.uint64)  # the target row of every sorted entry
+    return t_ok, t_key[order], q[t_ok][order], trow
+
+
+def _match_nearest(p, grid, rs, r2):
+    """The matching's walk of the rows p f32 [N,3] through `grid` -> (in range [N] bool, the in-range rows, their smallest key
+    (bits(d2) << 32) | target row over the candidates within r2, all ones without one). Every row makes 27 lookups and walks
+    the buckets, all rows at once."""
+    _, ks, ts, trow = grid
+    ok, cells, _ = _grid_cells(p, rs)
+    src = np.nonzero(ok)[0]
+    ps = p[src]
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    best = np.full(len(src), none, np.uint64)
+    for d in np.ndindex(3, 3, 3):
+        c = cells + (np.array(d, np.int64) - 1)
+        inside = ((c >= 0) & (c < (1 << 21))).all(1)  # a key with a coordinate outside the grid is skipped
+        qk = (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
+        lo = np.searchsorted(ks, qk, side="left")
+        hi = np.where(inside, np.searchsorted(ks, qk, side="right"), lo)
+        live = np.nonzero(lo < hi)[0]
+        at = lo[live]
+        while len(live):  # step t of every bucket walk at once
+            with np.errstate(all="ignore"):
+                dx, dy, dz = (ts[at, a] - ps[live, a] for a in range(3))
+                d2 = ((dx * dx + dy * dy) + dz * dz).astype(np.float32)
+            hit = d2 <= r2
+            key = (d2[hit].view(np.uint32).astype(np.uint64) << np.uint64(32)) | trow[at[hit]]
+            best[live[hit]] = np.minimum(best[live[hit]], key)  # a row appears once per step
+            at = at + 1
+            go = at < hi[live]
+            live, at = live[go], at[go]
+    return ok, src, best
+
+
 def match_points(xyz, target, radius, tol=(), mode=0, conf=None, rgb=None, normals=None, counts=None) -> HostMatch:
     """The host reference of md_op_match_points / md_infer_points_match (include/mi_depth.h states the contract): for every row of
     xyz [N,3] the nearest row of target [T,3] among its candidates: the target rows whose cell (side `radius`, the cells of
@@ -1209,33 +1249,10 @@ def match_points(xyz, target, radius, tol=(), mode=0, conf=None, rgb=None, norma
         raise ValueError("mode is 0, 1 or 2")
     if N >= 1 << 30 or T >= 1 << 30:
         raise ValueError("fewer than 2^30 rows")
-    ok, cells, _ = _grid_cells(p, rs)
-    t_ok, _, t_key = _grid_cells(q, rs)
-    order = np.argsort(t_key, kind="stable")
-    trow = np.nonzero(t_ok)[0][order].astype(np.uint64)  # the target row of every sorted entry
-    ks, ts = t_key[order], q[t_ok][order]
-    src = np.nonzero(ok)[0]
-    ps = p[src]
+    grid = _match_grid(q, rs)
+    t_ok = grid[0]
+    ok, src, best = _match_nearest(p, grid, rs, r2)
     none = np.uint64(0xFFFFFFFFFFFFFFFF)
-    best = np.full(len(src), none, np.uint64)
-    for d in np.ndindex(3, 3, 3):
-        c = cells + (np.array(d, np.int64) - 1)
-        inside = ((c >= 0) & (c < (1 << 21))).all(1)  # a key with a coordinate outside the grid is skipped
-        qk = (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
-        lo = np.searchsorted(ks, qk, side="left")
-        hi = np.where(inside, np.searchsorted(ks, qk, side="right"), lo)
-        live = np.nonzero(lo < hi)[0]
-        at = lo[live]
-        while len(live):  # step t of every bucket walk at once
-            with np.errstate(all="ignore"):
-                dx, dy, dz = (ts[at, a] - ps[live, a] for a in range(3))
-                d2 = ((dx * dx + dy * dy) + dz * dz).astype(np.float32)
-            hit = d2 <= r2
-            key = (d2[hit].view(np.uint32).astype(np.uint64) << np.uint64(32)) | trow[at[hit]]
-            best[live[hit]] = np.minimum(best[live[hit]], key)  # a row appears once per step
-            at = at + 1
-            go = at < hi[live]
-            live, at = live[go], at[go]
     found = best != none
     nearest = np.full(N, -2, np.int32)
     nearest[src] = np.where(found, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
@@ -1261,6 +1278,202 @@ def match_points(xyz, target, radius, tol=(), mode=0, conf=None, rgb=None, norma
     out.xyz, out.conf, out.rgb, out.normals = p[index], take(conf, np.float32, (N,)), take(rgb, np.uint8, (N, 3)), take(normals, np.float32, (N, 3))
     out.index, out.count = index, np.concatenate([per_view, [len(index)]]).astype(np.int32)
     return out
+
+
+@dataclass
+class HostRegistration:
+    transform: np.ndarray            # f64 [12]: R row-major, then t
+    pairs: np.ndarray                # int32 [K+1]: the pair count of every pass, entry K the evaluation pass; 0 for skipped iterations
+    sum_d2: np.ndarray               # f64 [K+1]: the sum of squared distances likewise
+    stats: np.ndarray                # int32 [8]: solves done, status, in-range rows and pairs of the evaluation pass, target rows in the grid
+    dropped: int                     # rows whose moved row is not finite or outside the grid in the evaluation pass
+    nearest: np.ndarray              # int32 [N]: match_points' nearest of the moved rows of the evaluation pass
+    dist2: np.ndarray                # f32 [N]
+    xyz: np.ndarray                  # f32 [N,3]: the moved rows of the evaluation pass
+    normals: Optional[np.ndarray]    # f32 [N,3]: the rotated normals
+
+
+REG_SWEEPS = 8     # kRegSweeps of kernels/register_math.h
+_REG_TILE = 4096   # tile_compact.h: item = tile * 4096 + step * 256 + thread
+
+
+def _reg_workgroup(v):
+    """The value of a 256-thread workgroup, v f64 [.., 256, 16] -> [.., 16]: the halving tree over the 64 lanes of every wave,
+    then (W0 + W1) + (W2 + W3)."""
+    w = v.reshape(v.shape[:-2] + (4, 64, 16))
+    h = 32
+    while h >= 1:
+        w = w[..., :h, :] + w[..., h:2 * h, :]
+        h //= 2
+    w = w[..., 0, :]
+    return (w[..., 0, :] + w[..., 1, :]) + (w[..., 2, :] + w[..., 3, :])
+
+
+def _reg_sums(leaves):
+    """The sixteen sums of a pass in the contract's fixed shape. leaves f64 [tiles * 4096, 16] in item order, +0.0 where an item
+    has no pair."""
+    tiles = len(leaves) // _REG_TILE
+    v = leaves.reshape(tiles, 16, 256, 16)
+    acc = np.zeros((tiles, 256, 16), np.float64)
+    for s in range(16):  # a thread's left fold over its steps
+        acc = acc + v[:, s]
+    tile = _reg_workgroup(acc)
+    rounds = (tiles + 255) // 256
+    part = np.zeros((max(rounds, 1) * 256, 16), np.float64)
+    part[:tiles] = tile
+    part = part.reshape(-1, 256, 16)
+    acc = np.zeros((256, 16), np.float64)
+    for r in range(len(part)):  # thread u folds the tiles u, u + 256, ..
+        acc = acc + part[r]
+    return _reg_workgroup(acc)
+
+
+def _reg_rotate(a, v, p, q):
+    """reg_jacobi_rotate of kernels/register_math.h, line for line, on lists of np.float64."""
+    f = np.float64
+    apq = a[p][q]
+    if apq == 0.0:
+        return
+    theta = (a[q][q] - a[p][p]) / (f(2.0) * apq)
+    sign = f(1.0) if theta >= 0.0 else f(-1.0)
+    t = sign / (np.abs(theta) + np.sqrt(theta * theta + f(1.0)))
+    c = f(1.0) / np.sqrt(t * t + f(1.0))
+    s = t * c
+    for k in range(4):
+        akp, akq = a[k][p], a[k][q]
+        a[k][p] = c * akp - s * akq
+        a[k][q] = s * akp + c * akq
+    for k in range(4):
+        apk, aqk = a[p][k], a[q][k]
+        a[p][k] = c * apk - s * aqk
+        a[q][k] = s * apk + c * aqk
+    for k in range(4):
+        vkp, vkq = v[k][p], v[k][q]
+        v[k][p] = c * vkp - s * vkq
+        v[k][q] = s * vkp + c * vkq
+
+
+def register_solve(n, S, sweeps=REG_SWEEPS):
+    """reg_solve of kernels/register_math.h, line for line: the pair count n and the sixteen sums S -> the transform f64 [12]."""
+    f = np.float64
+    S = [f(x) for x in S]
+    with np.errstate(all="ignore"):
+        dn = f(n)
+        pbar = [S[a] / dn for a in range(3)]
+        qbar = [S[3 + b] / dn for b in range(3)]
+        H = [[S[6 + 3 * a + b] - S[a] * qbar[b] for b in range(3)] for a in range(3)]
+        m = [[f(0.0)] * 4 for _ in range(4)]
+        m[0][0] = (H[0][0] + H[1][1]) + H[2][2]
+        m[1][1] = (H[0][0] - H[1][1]) - H[2][2]
+        m[2][2] = (H[1][1] - H[0][0]) - H[2][2]
+        m[3][3] = (H[2][2] - H[0][0]) - H[1][1]
+        m[0][1] = m[1][0] = H[1][2] - H[2][1]
+        m[0][2] = m[2][0] = H[2][0] - H[0][2]
+        m[0][3] = m[3][0] = H[0][1] - H[1][0]
+        m[1][2] = m[2][1] = H[0][1] + H[1][0]
+        m[1][3] = m[3][1] = H[2][0] + H[0][2]
+        m[2][3] = m[3][2] = H[1][2] + H[2][1]
+        v = [[f(1.0) if i == j else f(0.0) for j in range(4)] for i in range(4)]
+        for _ in range(sweeps):
+            for p in range(3):
+                for q in range(p + 1, 4):
+                    _reg_rotate(m, v, p, q)
+        top = 0
+        for k in range(1, 4):
+            if m[k][k] > m[top][top]:
+                top = k
+        w, x, y, z = v[0][top], v[1][top], v[2][top], v[3][top]
+        ln = np.sqrt(((w * w + x * x) + y * y) + z * z)
+        w, x, y, z = w / ln, x / ln, y / ln, z / ln
+        if w < 0.0:
+            w, x, y, z = -w, -x, -y, -z
+        ww, xx, yy, zz = w * w, x * x, y * y, z * z
+        xy, xz, yz, wx, wy, wz = x * y, x * z, y * z, w * x, w * y, w * z
+        two = f(2.0)
+        A = [((ww + xx) - yy) - zz, two * (xy - wz), two * (xz + wy),
+             two * (xy + wz), ((ww - xx) + yy) - zz, two * (yz - wx),
+             two * (xz - wy), two * (yz + wx), ((ww - xx) - yy) + zz]
+        A += [qbar[a] - ((A[3 * a] * pbar[0] + A[3 * a + 1] * pbar[1]) + A[3 * a + 2] * pbar[2]) for a in range(3)]
+    return np.array(A, np.float64)
+
+
+def _reg_turn(A, v, shift):
+    """(float)(((R_a0 x + R_a1 y) + R_a2 z) [+ t_a]) of the rows v f32 [N,3], a NaN written as 0x7FC00000."""
+    x, y, z = (v[:, a].astype(np.float64) for a in range(3))
+    out = np.empty((len(v), 3), np.float32)
+    with np.errstate(all="ignore"):
+        for a in range(3):
+            r = (A[3 * a] * x + A[3 * a + 1] * y) + A[3 * a + 2] * z
+            out[:, a] = ((r + A[9 + a]) if shift else r).astype(np.float32)
+    bits = out.view(np.uint32)
+    bits[np.isnan(out)] = 0x7FC00000
+    return out
+
+
+def register_points(xyz, target, radius, iterations=10, init=None, min_pairs=3, rot_eps=0.0, trans_eps=0.0, normals=None) -> HostRegistration:
+    """The host reference of md_op_register_points (include/mi_depth.h states the contract, kernels/register_math.h its arithmetic):
+    rigid point-to-point ICP of xyz [N,3] onto target [T,3]. Every pass moves the rows under the running transform in f64 with one
+    cast to f32, pairs them through `match_points`' grid and walk, and sums the sixteen leaves of every pair in the fixed tree of
+    the tile layout; `register_solve` restates the Jacobi solve. init: twelve f64, R row-major then t (None: the identity). The
+    device kernels (kernels/register.hip) give the same bits."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 3)
+    N, T, K = len(p), len(q), int(iterations)
+    rs = np.float32(radius)
+    with np.errstate(all="ignore"):
+        r2 = rs * rs
+    if not np.isfinite(rs) or not rs > 0 or not np.isfinite(r2):
+        raise ValueError("radius and its square must be finite and > 0")
+    if not 1 <= K <= 64:
+        raise ValueError("iterations outside 1..64")
+    if min_pairs < 3:
+        raise ValueError("min_pairs is at least 3")
+    if not (np.isfinite(rot_eps) and rot_eps >= 0 and np.isfinite(trans_eps) and trans_eps >= 0):
+        raise ValueError("rot_eps and trans_eps are finite and >= 0")
+    A = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float64) if init is None else np.asarray(init, np.float64).reshape(12).copy()
+    if not np.isfinite(A).all():
+        raise ValueError("init is not finite")
+    if N >= 1 << 30 or T >= 1 << 30:
+        raise ValueError("fewer than 2^30 rows")
+    grid = _match_grid(q, rs)
+    items = (N + _REG_TILE - 1) // _REG_TILE * _REG_TILE
+    p64, q64 = p.astype(np.float64), q.astype(np.float64)
+
+    def one_pass(A):
+        moved = _reg_turn(A, p, True)
+        ok, src, best = _match_nearest(moved, grid, rs, r2)
+        found = best != np.uint64(0xFFFFFFFFFFFFFFFF)
+        rows, j = src[found], (best[found] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        d2 = (best[found] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        leaves = np.zeros((items, 16), np.float64)
+        leaves[rows, 0:3], leaves[rows, 3:6] = p64[rows], q64[j]
+        leaves[rows, 6:15] = (p64[rows][:, :, None] * q64[j][:, None, :]).reshape(-1, 9)
+        leaves[rows, 15] = d2.astype(np.float64)
+        return moved, ok, src, best, found, len(rows), _reg_sums(leaves)
+
+    pairs, sum_d2, stats = np.zeros(K + 1, np.int32), np.zeros(K + 1, np.float64), np.zeros(8, np.int32)
+    for k in range(K):
+        if stats[1] != 0:
+            break
+        n, S = one_pass(A)[5:]
+        pairs[k], sum_d2[k] = n, S[15]
+        if n < min_pairs:
+            stats[1] = 2
+            break
+        A_new = register_solve(n, S)
+        stats[0] += 1
+        if (rot_eps > 0 or trans_eps > 0) and np.abs(A_new[:9] - A[:9]).max() <= rot_eps and np.abs(A_new[9:] - A[9:]).max() <= trans_eps:
+            stats[1] = 1
+        A = A_new
+    moved, ok, src, best, found, n, S = one_pass(A)
+    pairs[K], sum_d2[K] = n, S[15]
+    stats[2], stats[3], stats[4] = len(src), n, int(grid[0].sum())
+    nearest = np.full(N, -2, np.int32)
+    nearest[src] = np.where(found, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+    bits = np.full(N, 0x7F800000, np.uint32)
+    bits[src] = np.where(found, (best >> np.uint64(32)).astype(np.uint32), np.uint32(0x7F800000))
+    turned = None if normals is None else _reg_turn(A, np.ascontiguousarray(normals, dtype=np.float32).reshape(N, 3), False)
+    return HostRegistration(A, pairs, sum_d2, stats, int(N - ok.sum()), nearest, bits.view(np.float32), moved, turned)
 
 
 def render_points(xyz, H, W, intrinsics=None, extrinsics=None, focal_px=None, rgb=None, count=None, *, pixel_offset=0.0, z_near=0.0,

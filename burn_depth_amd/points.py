@@ -93,6 +93,33 @@ class PointMatch:
 
 
 @dataclass
+class PointRegistration:
+    """What `md_op_register_points` returns (include/mi_depth.h). Device tensors: transform f64 [12] (R row-major, then t: a row p
+    moves to R p + t), pairs int32 and sum_d2 f64 [iterations + 1] (the pair count and the sum of squared distances of every
+    pass; entry `iterations` is the evaluation pass under the final transform, skipped iterations are 0), stats int32 [8] (solves
+    done, status 0 ran all / 1 converged / 2 too few pairs, in-range rows and pairs of the evaluation pass, target rows in the
+    grid), dropped int32 [1], nearest int32 and dist2 f32 [N] (`PointMatch`'s, for the moved rows), xyz f32 [N,3] the moved rows
+    and normals f32 [N,3] the rotated normals (None when not asked for)."""
+    transform: Optional[torch.Tensor] = None
+    pairs: Optional[torch.Tensor] = None
+    sum_d2: Optional[torch.Tensor] = None
+    stats: Optional[torch.Tensor] = None
+    dropped: Optional[torch.Tensor] = None
+    nearest: Optional[torch.Tensor] = None
+    dist2: Optional[torch.Tensor] = None
+    xyz: Optional[torch.Tensor] = None
+    normals: Optional[torch.Tensor] = None
+
+    def matrix(self) -> torch.Tensor:
+        """The transform as a 4x4 f64 matrix on the host (synchronises)."""
+        a = self.transform.cpu()
+        m = torch.eye(4, dtype=torch.float64)
+        m[:3, :3] = a[:9].reshape(3, 3)
+        m[:3, 3] = a[9:]
+        return m
+
+
+@dataclass
 class PointCloud:
     """What `md_op_unproject` / `md_infer_points` return (include/mi_depth.h). Device tensors: the dense point map [B,H,W,3] and
     mask u8 [B,H,W]; the compacted list xyz [capacity,3] (rgb u8 [capacity,3], conf [capacity]) in (view, row, column) order, of
@@ -151,6 +178,7 @@ class PointCloud:
     planes: Optional["FittedPlanes"] = None
     clusters: Optional["PointClusters"] = None
     match: Optional["PointMatch"] = None
+    registration: Optional["PointRegistration"] = None  # `register=` (`md_infer_points_register`): with apply the list itself holds the moved rows
 
     def points(self):
         """(xyz, rgb, conf) cut to the points that exist (reads `count`: synchronises)."""
@@ -539,6 +567,61 @@ def _points_match(dev, rows: int, match: dict, out: PointCloud, fresh: bool, kee
     return _match_struct(match, ptr, T, kind, out.match, out.index)
 
 
+_REGISTER_KEYWORDS = {"target", "radius", "iterations", "init", "min_pairs", "rot_eps", "trans_eps", "apply"}
+
+
+def _register_init(init):
+    """init= of a registration -> a ctypes array of twelve doubles (R row-major, then t), or None: twelve values, or a 3x4 / 4x4 matrix."""
+    if init is None:
+        return None
+    m = torch.as_tensor(init, dtype=torch.float64).cpu()
+    if m.numel() == 16:
+        m = m.reshape(4, 4)[:3]
+    if m.dim() == 2:
+        m = torch.cat([m[:, :3].reshape(9), m[:, 3]])
+    if m.numel() != 12:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "init holds twelve values, or is a 3x4 / 4x4 matrix")
+    return (C.c_double * 12)(*[float(v) for v in m.reshape(12)])
+
+
+def _register_struct(reg: dict, target, target_rows: int, target_kind: int, found: "PointRegistration", keep: list) -> "_lib.MdPointsRegister":
+    """md_points_register of the keywords radius=, iterations=, init=, min_pairs=, rot_eps=, trans_eps=, apply= writing into `found`.
+    The ranges are the library's to refuse. The init array joins `keep`."""
+    start = _register_init(reg.get("init"))
+    keep.append(start)
+    return _lib.MdPointsRegister(float(reg["radius"]), target, int(target_rows), int(target_kind), int(reg.get("iterations", 10)),
+                                 int(reg.get("min_pairs", 3)), int(bool(reg.get("apply", False))), float(reg.get("rot_eps", 0.0)),
+                                 float(reg.get("trans_eps", 0.0)), C.cast(start, C.c_void_p) if start is not None else None,
+                                 _ptr(found.transform), _ptr(found.pairs), _ptr(found.sum_d2), _ptr(found.stats), _ptr(found.dropped),
+                                 _ptr(found.nearest), _ptr(found.dist2))
+
+
+def _new_registration(dev, rows: int, iterations: int) -> "PointRegistration":
+    """Fresh tensors for a list of `rows` rows and `iterations` rounds."""
+    f64 = lambda n: torch.empty(n, dtype=torch.float64, device=dev)  # noqa: E731
+    history = max(int(iterations), 0) + 1
+    return PointRegistration(transform=f64(12), pairs=_i32(dev, history), sum_d2=f64(history), stats=_i32(dev, 8), dropped=_i32(dev, 1),
+                             nearest=_i32(dev, rows), dist2=_f32(dev, rows))
+
+
+def _points_register(dev, rows: int, reg: dict, own_list: bool, out: PointCloud, fresh: bool, keep: list):
+    """md_points_register for `out` with the stage on. rows: the rows the list in front of the stage can have; own_list: the
+    matching or the clustering cuts, so the stage reads that list and nearest / dist2 lie over its rows, otherwise over the
+    list of the call. The target's keep-alive joins `keep`."""
+    unknown = set(reg) - _REGISTER_KEYWORDS
+    if unknown or "radius" not in reg:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, f"register= takes {sorted(_REGISTER_KEYWORDS)} and needs radius; unknown {sorted(unknown)}")
+    if out.xyz is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "register= needs the compacted list")
+    if reg.get("target") is None:
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "register= needs target")
+    if fresh or out.registration is None:
+        out.registration = _new_registration(dev, rows if own_list else int(out.xyz.shape[0]), reg.get("iterations", 10))
+    ptr, T, kind, alive = _match_target(dev, reg["target"])
+    keep.append(alive)
+    return _register_struct(reg, ptr, T, kind, out.registration, keep)
+
+
 def _target_cameras(dev, intrinsics, extrinsics, focal_px):
     """The target cameras of a rendering or a rasterisation -> (T, md_points_cameras, keep-alive). T is the number of cameras given."""
     src = intrinsics if intrinsics is not None else focal_px
@@ -593,6 +676,7 @@ class PointsRequest(NamedTuple):
     pln: Optional["_lib.MdPointsPlanes"] = None  # behind `keep`: `md_infer_points_planes` takes it behind `args()`
     clu: Optional["_lib.MdPointsClusters"] = None  # `md_infer_points_clusters` takes it behind `planes_args()`
     mat: Optional["_lib.MdPointsMatch"] = None  # `md_infer_points_match` takes it behind `clusters_args()`
+    reg: Optional["_lib.MdPointsRegister"] = None  # `md_infer_points_register` takes it behind `match_args()`
 
     def args(self) -> list:
         """The struct arguments of `md_infer_points_smooth`, by reference, NULL for the parts not asked for."""
@@ -606,6 +690,10 @@ class PointsRequest(NamedTuple):
         """The struct arguments of `md_infer_points_match`: those of `clusters_args()`, then the match part."""
         return self.clusters_args() + [C.byref(self.mat) if self.mat is not None else None]
 
+    def register_args(self) -> list:
+        """The struct arguments of `md_infer_points_register`: those of `match_args()`, then the register part."""
+        return self.match_args() + [C.byref(self.reg) if self.reg is not None else None]
+
     def planes_args(self) -> list:
         """The struct arguments of `md_infer_points_planes`: those of `args()`, then the plane part."""
         return self.args() + [C.byref(self.pln) if self.pln is not None else None]
@@ -617,7 +705,8 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
                     normals: bool = False, normal_min_cos: float = 0.0, voxel: Optional[float] = None, render: Optional[dict] = None,
                     mesh=None, raster: Optional[dict] = None, outlier: Optional[dict] = None, decimate: Optional[dict] = None,
                     components: Optional[dict] = None, smooth: Optional[dict] = None, planes: Optional[dict] = None,
-                    clusters: Optional[dict] = None, match: Optional[dict] = None, opts: Optional[dict] = None) -> PointsRequest:
+                    clusters: Optional[dict] = None, match: Optional[dict] = None, register: Optional[dict] = None,
+                    opts: Optional[dict] = None) -> PointsRequest:
     """The keyword set of `infer_points` / `ops.unproject` (their docstrings say what each means) as a `PointsRequest`. opts: the
     fields of `md_points_opts`; want_rgb / want_conf / want_depth: the call can fill those outputs. A part is None when it was
     not asked for, by keyword or by an `out` that carries its tensors; fresh tensors are allocated unless `out` is given.
@@ -631,7 +720,7 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     o = _points_opts(**(opts or {}))
     res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
     cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
-    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = mat = None
+    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = mat = reg = None
     keep_rows = _cluster_mode(clusters) != 0  # the clustering writes the list: index is its own
     match_rows = _match_mode(match) != 0  # the matching writes the list, in front of the clustering
     cut = _plane_mode(planes) != 0 or match_rows or keep_rows  # a later stage writes the list: an earlier stage's index is not returned
@@ -693,8 +782,13 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
             res.match.index = None
     elif match is not None:
         mat = _lib.MdPointsMatch()
+    if register and register.get("radius"):  # directly in front of the matching, on the list it reads
+        keep = list(keep)
+        reg = _points_register(dev, _lattice(B, H, W, o.stride)[1], register, match_rows or keep_rows, res, fresh, keep)
+    elif register is not None:
+        reg = _lib.MdPointsRegister()
     if clusters and clusters.get("radius"):
         clu = _points_clusters(dev, _lattice(B, H, W, o.stride)[1], clusters, res, fresh)
     elif clusters is not None:
         clu = _lib.MdPointsClusters()
-    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu, mat)
+    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu, mat, reg)

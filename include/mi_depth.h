@@ -1206,6 +1206,101 @@ int md_infer_points_match(md_model_t m, const float* nchw, int B, int H, int W, 
                           const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
                           const md_points_clusters* clu, const md_points_match* mat, int out_kind, void* stream);
 
+/* ---- point path: rigid ICP registration of a point list onto a reference cloud ---------------------------------------------------
+ * A source list xyz f32 [N,3] (optional normals f32 [N,3]) and a target list f32 [T,3] -> the rigid transform (rotation and
+ * translation, no scale) that moves the source onto the target by point-to-point ICP, with per-iteration pair counts and
+ * squared-distance sums and, optionally, the moved rows. The arithmetic is held once in kernels/register_math.h, which compiles
+ * for the device and the host; pipeline.register_points restates it in numpy bit for bit. Denormals are outside the contract.
+ *   transform A: twelve f64, R row-major in A[0..9), then t in A[9..12). A_0 = init, or the identity.
+ *   one pass under A, for every source row i below the live count:
+ *     moved row m_a = (float)(((R_a0*x + R_a1*y) + R_a2*z) + t_a): the f32 inputs widened to f64, every operation rounded once,
+ *       one final cast to f32 (round to nearest even).
+ *     nearest target row j of m: md_points_match's definition word for word with cell side `radius`: the 27 cells, the gate
+ *       (dx*dx + dy*dy) + dz*dz <= radius*radius in f32, the smallest key (bits(d2) << 32) | j. A moved row that is not finite
+ *       or out of the grid's range is dropped and has no pair.
+ *     a paired row contributes sixteen f64 leaves built from the ORIGINAL source row p and the target row q, widened exactly:
+ *       p_a (leaves 0..2), q_a (3..5), p_a * q_b (6 + 3a + b), (double)d2 (15). So the solve gives the full transform and
+ *       nothing is composed. Every other item contributes +0.0. The pair count is an integer.
+ *   the sums have a fixed shape over the tile layout item = tile*4096 + step*256 + thread: a thread's value is the left fold,
+ *     from +0.0, of its leaves over step = 0..15; a wave's value the halving tree over its lanes (v[l] += v[l+h] for l < h, h =
+ *     32, 16, .., 1); a tile's value (W0 + W1) + (W2 + W3). The call's value: thread u of one 256-thread workgroup left-folds,
+ *     from +0.0, the tile values u, u+256, u+512, .. in ascending order; the 256 thread values go through the same wave tree and
+ *     four-wave combine. All leaves are finite, so nothing depends on the order of arrival.
+ *   the solve (register_math.h, reg_solve; one thread, f64, only + - * /, sqrt and comparisons): centroids pbar = S_p / n,
+ *     qbar = S_q / n; H_ab = S_pq_ab - S_p_a * qbar_b; Horn's symmetric 4x4 matrix of H; a fixed number of cyclic Jacobi sweeps
+ *     (kRegSweeps; theta = (a_qq - a_pp) / (2 a_pq), t = sign / (|theta| + sqrt(theta*theta + 1)), c = 1 / sqrt(t*t + 1), s = t*c;
+ *     a pivot that is exactly 0 is skipped); the eigenvector of the largest eigenvalue (ties: smallest index), normalised, w >= 0;
+ *     R from the quaternion; t = qbar - R pbar. The operation order is the header's.
+ *   iteration k = 0..K-1: a pass under A_k, the sums, then: n < min_pairs -> status 2, A stays, every later iteration changes
+ *     nothing; otherwise A_{k+1} = the solve's result, and with the stop test on (rot_eps > 0 or trans_eps > 0) and
+ *     max |R'_ab - R_ab| <= rot_eps and max |t'_a - t_a| <= trans_eps -> status 1, likewise. All K iterations are always
+ *     enqueued. Then one evaluation pass under the final A, without a solve: entry K of the histories and the row outputs.
+ *   pairs int32 [K+1] / sum_d2 f64 [K+1]: the pair count and the sum of d2 of the pass at entry k; 0 for skipped iterations.
+ *   stats int32 [8]: [0] solves done, [1] status (0 ran all K, 1 converged, 2 too few pairs), [2] in-range rows and [3] pairs of
+ *     the evaluation pass, [4] target rows in the grid, [5..8) 0. dropped int32 [1]: rows whose moved row is not finite or out of
+ *     range in the evaluation pass.
+ *   nearest int32 [N] / dist2 f32 [N]: md_points_match's mode 0 outputs for the moved rows of the evaluation pass.
+ *   moved rows (the operator's xyz_out) f32 [N,3], written for every row, and rotated normals (float)((R_a0*nx + R_a1*ny) +
+ *     R_a2*nz); a NaN component is written as the bit pattern 0x7FC00000. */
+typedef struct md_points_register {
+  float radius;          /* pairing radius and cell side; 0 = the stage is off (md_infer_points_register) */
+  const float* target;   /* f32 [target_rows,3] */
+  int64_t target_rows;
+  int32_t target_kind;   /* MD_MEM_HOST | MD_MEM_DEVICE; the operator takes device only */
+  int32_t iterations;    /* K, 1..64 */
+  int32_t min_pairs;     /* >= 3 */
+  int32_t apply;         /* md_infer_points_register: 1 = the moved rows (and normals) replace the list's in place; 0 = estimate
+                          * only. The operator reads only its range: its moved rows go to xyz_out / normals_out */
+  double rot_eps;        /* both 0 = no stop test */
+  double trans_eps;
+  const double* init;    /* HOST memory, f64 [12]; NULL = identity */
+  double* transform;     /* f64 [12]. NULL = skip */
+  int32_t* pairs;        /* int32 [iterations + 1]. NULL = skip */
+  double* sum_d2;        /* f64 [iterations + 1]. NULL = skip */
+  int32_t* stats;        /* int32 [8]. NULL = skip */
+  int32_t* dropped;      /* int32 [1]. NULL = skip */
+  int32_t* nearest;      /* int32 [N]. NULL = skip */
+  float* dist2;          /* f32 [N]. NULL = skip */
+} md_points_register;
+
+/* The stand-alone operator on caller device lists: the N rows are one view; every pointer but reg->init is a device pointer.
+ * xyz_out f32 [N,3] (NULL = skip) takes the moved rows and may be xyz_dev itself: a thread reads only its own row;
+ * normals_out f32 [N,3] (NULL = skip) the rotated normals. Launches: reset, insert, alloc, fill (the matching's grid, built
+ * once from the target), K times (step, solve), the evaluation step and its reduce. Everything is enqueued on `stream`; the
+ * call returns after the stream has drained, because its scratch is freed on return. T == 0 and N == 0 are legal: status 2.
+ * Errors, before any launch: dev / reg NULL, xyz_dev NULL with N > 0, radius not finite or <= 0 or radius*radius not finite,
+ * target_rows < 0, target NULL with target_rows > 0, target_kind not MD_MEM_DEVICE, iterations outside 1..64, min_pairs < 3,
+ * an eps negative or not finite, a value of init not finite, N < 0, normals_out without normals_dev -> MD_ERR_INVALID_ARG;
+ * N or target_rows >= 2^30 -> MD_ERR_SHAPE. A probe loop that ran out of table (impossible at load <= 0.5) -> MD_ERR_HIP
+ * after the launches. */
+int md_op_register_points(md_device_t dev, const float* xyz_dev, const float* normals_dev, int64_t N, const md_points_register* reg,
+                          float* xyz_out, float* normals_out, void* stream);
+/* md_infer_points_match with the registration directly in front of the matching (launch-order name "points_register"), on the
+ * list the matching reads: the call's list below its capacity (nearest / dist2 then [out->capacity], of which the first
+ * min(count[B], capacity) are written), or, when the matching (mode 1 / 2) or the clustering (mode 1) cuts, the model's own list
+ * in front of them (nearest / dist2 then over its rows, at most B ceil(H/stride) ceil(W/stride)). apply = 0 only estimates.
+ * apply = 1 replaces that list's rows, and its normals when the call carries them, by the moved ones in place, so the matching
+ * and the clustering see the aligned cloud: "align to the reference, drop what the reference already holds, cluster the rest" is
+ * one call. reg's output pointers are of out_kind; init is host memory and its values are read during the call; the target is
+ * of target_kind: a host target is copied into a grow-only buffer of the model with every call (such a call is not captured
+ * into a graph), a device target is read by address, so a graph replay sees its current contents. The scratch is a grow-only
+ * buffer of the model. reg NULL or radius == 0 (its output pointers then NULL): md_infer_points_match on the same arguments, the
+ * same launches and bits. The graph key contains every field of reg and the values of init. Errors as md_infer_points_match's,
+ * plus, before any launch: the operator's refusals of radius (0 allowed), the target (target_kind may be MD_MEM_HOST),
+ * iterations, min_pairs, the eps and init, apply outside 0 and 1, an output pointer with radius == 0, the stage without the
+ * list's count or without the list output out->xyz, together with decimation, apply = 1 together with a mesh, components or
+ * smoothing (their faces and rows belong to the cloud before it moved) -> MD_ERR_INVALID_ARG; a list or a target of >= 2^30
+ * rows -> MD_ERR_SHAPE. The dense maps (point_map, normal_map) are written before the stage and keep the model's frame. With host outputs a probe loop that ran out of table -> MD_ERR_HIP; with device
+ * outputs md_model_query(m, "register_overflow") reads the flag as "match_overflow" does. */
+int md_infer_points_register(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                             const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                             const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                             const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                             const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                             const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
+                             const md_points_clusters* clu, const md_points_match* mat, const md_points_register* reg,
+                             int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

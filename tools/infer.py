@@ -62,6 +62,11 @@ the cosine C of that axis (the floor with the up axis). One image without `--mes
 writes the dense cluster id of every point as the int property `label` of the file (-1 none; it replaces the plane labels), `keep` writes
 the points of kept clusters (not with `--mesh`, nor behind `--plane-mode label`). One image without `--mesh` runs inside the model call
 (`md_infer_points_clusters`); with `--views` or `--mesh`, `ops.cluster_points` runs on the final points.
+`--register-ply REF.ply --register-radius R [--register-iterations K] [--register-apply]` (with `--ply`): rigid point-to-point ICP of
+the cloud onto the points of REF.ply, in front of the match step; prints the 4x4 transform, the solves, the pairs and the RMS distance of
+the first and the last pass. `--register-apply` writes the aligned cloud, and `--match-ply` / `--cluster-radius` then see it (not with
+`--mesh`). One image: the stage of the model call (`md_infer_points_register`); with `--views` or `--mesh`, `ops.register_points` on the
+final points.
 `--match-ply REF.ply --match-radius R [--match-tol T ...] [--match-mode label|matched|unmatched]` (with `--ply`): the nearest point of the
 reference cloud REF.ply within R for every point of the cloud, on the device, behind `--planes` and in front of `--cluster-radius`, so
 `--planes P --plane-mode drop --match-ply REF.ply --match-radius R --match-mode unmatched --cluster-radius C` drops the floor and what the
@@ -171,6 +176,26 @@ def match_request(a, dev) -> dict:
     from burn_depth_amd import pipeline as P
     ref = np.ascontiguousarray(P.read_ply(a.match_ply)[0], dtype=np.float32)
     return dict(target=torch.from_numpy(ref).to(dev), radius=a.match_radius, tol=tuple(a.match_tol), mode=a.match_mode)
+
+
+def register_request(a, dev) -> dict:
+    """the register= keywords of --register-ply: the reference cloud goes to the device once"""
+    import torch
+    from burn_depth_amd import pipeline as P
+    ref = np.ascontiguousarray(P.read_ply(a.register_ply)[0], dtype=np.float32)
+    return dict(target=torch.from_numpy(ref).to(dev), radius=a.register_radius, iterations=a.register_iterations)
+
+
+def print_registration(found) -> None:
+    """the 4x4 of the transform, then the pairs and the RMS distance of the first and of the evaluation pass"""
+    stats, pairs, sums = found.stats.cpu().tolist(), found.pairs.cpu().tolist(), found.sum_d2.cpu().tolist()
+    print("Registration:")
+    for row in found.matrix().tolist():
+        print("  " + " ".join(f"{v:+.9e}" for v in row))
+    rms = lambda k: (sums[k] / pairs[k]) ** 0.5 if pairs[k] else float("nan")  # noqa: E731
+    state = {0: "ran every round", 1: "converged", 2: "too few pairs"}[stats[1]]
+    print(f"Registration: {stats[0]} solves ({state}), {pairs[0]} -> {pairs[-1]} pairs, RMS distance {rms(0):.6g} -> {rms(-1):.6g}, "
+          f"{stats[4]} reference points in the grid")
 
 
 def print_match(found, a, rows: int) -> None:
@@ -300,7 +325,18 @@ def run_views(a) -> int:
             else:
                 xyz, col, _ = pc.points()
                 nrm = pc.normals[:xyz.shape[0]] if a.normals else None
-        if a.match_ply:  # on the points the plane step left
+        if a.register_ply:  # on the points the plane step left, in front of the match step
+            try:
+                req = register_request(a, xyz.device)
+                found = ops.register_points(dev, xyz, req.pop("target"), **req, normals=nrm, apply=a.register_apply)
+            except _lib.MdError as e:
+                print(str(e), file=sys.stderr)
+                return 1
+            print_registration(found)
+            if a.register_apply:  # the file, the later steps and --render-pose see the aligned cloud
+                xyz, nrm = found.xyz, found.normals if a.normals else None
+                pc.xyz, pc.rgb, pc.count = xyz, col, torch.tensor([xyz.shape[0]], dtype=torch.int32, device=xyz.device)
+        if a.match_ply:  # on the points the register step left
             try:
                 req = match_request(a, xyz.device)
                 pc = ops.match_points(dev, xyz, req.pop("target"), **req, rgb=col, normals=nrm)
@@ -419,6 +455,11 @@ def main(argv=None) -> int:
     ap.add_argument("--match-tol", type=float, nargs="+", default=[], metavar="T", help="--match-ply: up to four tolerances in (0, radius] whose precision is printed")
     ap.add_argument("--match-mode", choices=["label", "matched", "unmatched"], default="label",
                     help="--match-ply: write `has a counterpart` as the PLY property `label`, or the points with / without a counterpart")
+    ap.add_argument("--register-ply", default="", help="--ply: rigid ICP of the cloud onto the points of this reference .ply, in front of --match-ply "
+                    "(md_infer_points_register, ops.register_points); prints the 4x4 transform")
+    ap.add_argument("--register-radius", type=float, default=0.0, help="--register-ply: the pairing radius, > 0")
+    ap.add_argument("--register-iterations", type=int, default=10, help="--register-ply: the rounds, 1..64")
+    ap.add_argument("--register-apply", action="store_true", help="--register-ply: write the aligned cloud; the match and cluster steps see it (not with --mesh)")
     ap.add_argument("--plane-up", type=float, nargs=3, metavar=("X", "Y", "Z"), help="--planes: only planes whose normal lies within --plane-up-cos of this axis")
     ap.add_argument("--plane-up-cos", type=float, default=0.9, help="--plane-up: the smallest |cosine| between a plane's normal and the axis")
     ap.add_argument("--raster-pose", default="", help="--ply --mesh: also rasterise the mesh into the world-to-camera pose(s) of this .npy ([3,4] or [T,3,4])")
@@ -448,6 +489,13 @@ def main(argv=None) -> int:
                         (a.match_mode == "label" and a.cluster_radius > 0 and a.cluster_mode == "keep")):
         print("--match-ply goes with --ply and --match-radius > 0 and takes at most four --match-tol; --match-mode matched / unmatched not with --mesh "
               "(the faces name the rows) nor behind --plane-mode label; --match-mode label not in front of --cluster-mode keep", file=sys.stderr)
+        return 2
+    if a.register_ply and (not a.register_radius > 0 or not a.ply or not 1 <= a.register_iterations <= 64 or (a.register_apply and a.mesh)):
+        print("--register-ply goes with --ply, --register-radius > 0 and --register-iterations in 1..64; --register-apply not with --mesh "
+              "(the faces and the smoothed rows belong to the cloud before it moved)", file=sys.stderr)
+        return 2
+    if a.register_apply and not a.register_ply:
+        print("--register-apply goes with --register-ply", file=sys.stderr)
         return 2
     if a.planes != 0 and (not 1 <= a.planes <= 8 or not a.ply or (a.mesh and a.plane_mode != "label")):
         print("--planes is a plane count in 1..8 and goes with --ply; --plane-mode drop / keep not with --mesh (the faces name the rows)", file=sys.stderr)
@@ -523,10 +571,12 @@ def main(argv=None) -> int:
             planes_in_call = bool(a.planes) and not a.mesh
             clusters_in_call = a.cluster_radius > 0 and not a.mesh
             match_in_call = bool(a.match_ply) and not a.mesh
-            if planes_in_call or clusters_in_call or match_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stages then run inside the call
+            register_in_call = bool(a.register_ply) and not a.mesh
+            if planes_in_call or clusters_in_call or match_in_call or register_in_call:  # a first call gives the list, whose extent sets the default tolerance; the stages then run inside the call
                 pc = model.infer_points(x, **call, voxel=a.voxel, render=render, planes=planes_request(a, pc.points()[0]) if planes_in_call else None,
                                         clusters=clusters_request(a) if clusters_in_call else None,
                                         match=match_request(a, x.device) if match_in_call else None,
+                                        register=dict(register_request(a, x.device), apply=a.register_apply) if register_in_call else None,
                                         outlier=dict(radius=a.outlier_radius, min_neighbours=a.outlier_min) if a.outlier_radius else None)
             xyz, col, _ = pc.points()
             nrm = pc.normals[:xyz.shape[0]] if a.normals else None
@@ -548,6 +598,12 @@ def main(argv=None) -> int:
                 print_planes(fitted)
                 if a.plane_mode == "label":
                     label = fitted.label[:xyz.shape[0]].cpu().numpy()
+            if a.register_ply:  # beside a mesh: the operator estimates on the vertices of the file, which stay
+                if register_in_call:
+                    print_registration(pc.registration)
+                else:
+                    req = register_request(a, xyz.device)
+                    print_registration(ops.register_points(Device(0), xyz, req.pop("target"), **req))
             if a.match_ply:  # beside a mesh: the operator labels the vertices of the file
                 if match_in_call:
                     near = pc.match
