@@ -360,8 +360,10 @@ SYMBOLS = {
     "md_op_resize_catmull_rom": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "md_op_depth_display": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "md_op_resize_bilinear": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "md_op_resize_bilinear_ex": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "md_op_pyramid_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I), _P]),
     "md_op_resize_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "md_op_resize_nhwc_ex": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     "md_op_resize_output_size": (_I, [_I, _I, C.c_float, C.c_float, C.POINTER(_I), C.POINTER(_I)]),
     "md_op_split": (_I, [_P, _P, _I, _I, _I, _I, C.c_float, _P, C.POINTER(_I), _P]),
     "md_op_merge": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I), _P]),

@@ -303,6 +303,8 @@ __global__ __launch_bounds__(256) void pyramid_patchify_blocks_kernel(const floa
 int launch_pyramid_patchify(const float* x, const PyramidGeom& g, void* patches, int prec, hipStream_t s, bool force_generic) {
   if (g.ps % 8 != 0 || g.win % g.ps != 0 || g.S % 4 != 0)
     MD_FAIL(MD_ERR_UNSUPPORTED, "pyramid: patch %d / window %d / size %d unsupported", g.ps, g.win, g.S);
+  // the level-0 copies of the generic kernel are 16-byte reads at X = i * stride0 + (a multiple of 8)
+  if (g.stride0 % 4 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "pyramid: level-0 tile stride %d must be a multiple of 4", g.stride0);
   // one-read block kernel: patch 16, whole 64-pixel blocks, tile strides on the patch grid, align_corners=False taps
   const bool blocks_ok = !force_generic && g.method == MD_INTERP_CUSTOM && g.ps == 16 && g.S % 64 == 0 && g.S == 4 * g.win && g.stride0 % 16 == 0 &&
                          g.stride1 % 16 == 0 && (g.steps0 - 1) * g.stride0 + g.win == g.S && (g.steps1 - 1) * g.stride1 + g.win == g.S / 2;

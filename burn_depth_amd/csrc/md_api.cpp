@@ -870,11 +870,17 @@ int md_op_depth_display(md_device_t dev, const float* depth_dev, int B, int h, i
 
 int md_op_resize_bilinear(md_device_t dev, const float* in_dev, int B, int C, int H, int W, float* out_dev, int OH, int OW,
                           int method, void* stream) {
+  return md_op_resize_bilinear_ex(dev, in_dev, B, C, H, W, out_dev, OH, OW, method, 0, stream);
+}
+
+int md_op_resize_bilinear_ex(md_device_t dev, const float* in_dev, int B, int C, int H, int W, float* out_dev, int OH, int OW,
+                             int method, int post, void* stream) {
   if (!dev || !in_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid input shape");
   if (method != MD_INTERP_CUSTOM && method != MD_INTERP_BURN) MD_FAIL(MD_ERR_INVALID_ARG, "unknown interpolation method %d", method);
+  if (post != 0 && post != 1) MD_FAIL(MD_ERR_INVALID_ARG, "post: 0 (none) or 1 (the final depth 1 / clamp), got %d", post);
   MD_HIP(hipSetDevice(dev->ordinal));
-  return launch_resize_bilinear(in_dev, B * C, H, W, out_dev, OH, OW, method, 0, pick_stream(dev, stream));
+  return launch_resize_bilinear(in_dev, B * C, H, W, out_dev, OH, OW, method, post, pick_stream(dev, stream));
 }
 
 int md_op_pyramid_patchify(md_device_t dev, const float* x_dev, int B, int S, int window, int patch, int method, int precision,
@@ -897,11 +903,26 @@ int md_op_pyramid_patchify(md_device_t dev, const float* x_dev, int B, int S, in
 int md_op_resize_nhwc(md_device_t dev, const void* in_dev, int B, int H, int W, int C, void* out_dev, int OH, int OW, int method,
                       int precision, void* stream) {
   if (!dev || !in_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
+  if (precision != MD_PREC_BF16 && precision != MD_PREC_F32 && precision != MD_PREC_F16) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  return md_op_resize_nhwc_ex(dev, in_dev, B, H, W, C, C, out_dev, OH, OW, C, method, nullptr, precision, stream);
+}
+
+// The forms the engines launch: padded pixel strides, the fp32 addend table [OH][OW][C], split-half pixels [hi: ld | lo: ld]. The
+// caller's buffers hold the stored bytes. No staging buffer lives in the call, so it stays ordered on the stream like
+// md_op_resize_nhwc (which the benchmark times) and does not synchronise.
+int md_op_resize_nhwc_ex(md_device_t dev, const void* in_dev, int B, int H, int W, int C, int ld_in, void* out_dev, int OH, int OW,
+                         int ld_out, int method, const float* addend_dev, int precision, void* stream) {
+  if (!dev || !in_dev || !out_dev) MD_FAIL(MD_ERR_INVALID_ARG, "null argument");
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) MD_FAIL(MD_ERR_SHAPE, "invalid shape");
   if (method != MD_INTERP_CUSTOM && method != MD_INTERP_BURN) MD_FAIL(MD_ERR_INVALID_ARG, "unknown interpolation method %d", method);
-  if (precision != MD_PREC_BF16 && precision != MD_PREC_F32 && precision != MD_PREC_F16) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
-  MD_HIP(hipSetDevice(dev->ordinal));
-  return launch_resize_nhwc(in_dev, B, H, W, C, C, out_dev, OH, OW, C, method, nullptr, precision, pick_stream(dev, stream));
+  if (!token_op_prec(precision)) MD_FAIL(MD_ERR_INVALID_ARG, "unknown precision %d", precision);
+  if (C % 8 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "resize_nhwc: C=%d must be a multiple of 8", C);
+  if (ld_in < C || ld_out < C) MD_FAIL(MD_ERR_INVALID_ARG, "resize_nhwc: %d channels in pixels of %d / %d", C, ld_in, ld_out);
+  // the kernel moves 8 elements (16 bytes of a 2-byte type) per access at channel offsets that are multiples of 8
+  if (ld_in % 8 != 0 || ld_out % 8 != 0) MD_FAIL(MD_ERR_UNSUPPORTED, "resize_nhwc: pixel strides %d / %d must be multiples of 8", ld_in, ld_out);
+  OpStage s;
+  MD_TRY(s.open(dev, stream, precision));
+  return launch_resize_nhwc(in_dev, B, H, W, C, ld_in, out_dev, OH, OW, ld_out, method, addend_dev, precision, s.st);
 }
 
 int md_op_resize_output_size(int H, int W, float scale_h, float scale_w, int* oh, int* ow) {

@@ -23,12 +23,13 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().to(torch.float32)
 
 
-def resize_bilinear(dev: Device, x: torch.Tensor, out_hw: Tuple[int, int], method: int = 0) -> torch.Tensor:
+def resize_bilinear(dev: Device, x: torch.Tensor, out_hw: Tuple[int, int], method: int = 0, post: int = 0) -> torch.Tensor:
+    """post = 1: the final-depth step 1 / clamp(blend, 1e-4, 1e4) of the last resize (md_op_resize_bilinear_ex)."""
     x = _f32c(x)
     B, Cn, H, W = x.shape
     out = torch.empty((B, Cn, int(out_hw[0]), int(out_hw[1])), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().md_op_resize_bilinear(dev.handle, _p(x), B, Cn, H, W, _p(out), int(out_hw[0]), int(out_hw[1]),
-                                                 int(method), _stream_ptr(dev.ordinal)))
+    _lib.check(_lib.load().md_op_resize_bilinear_ex(dev.handle, _p(x), B, Cn, H, W, _p(out), int(out_hw[0]), int(out_hw[1]),
+                                                    int(method), int(post), _stream_ptr(dev.ordinal)))
     return out
 
 
@@ -56,7 +57,23 @@ def resize_nhwc(dev: Device, x: torch.Tensor, out_hw: Tuple[int, int], method: i
     return out
 
 
-_PREC_DTYPE = {0: torch.bfloat16, 1: torch.float32, 3: torch.float16}
+def resize_nhwc_ex(dev: Device, x: torch.Tensor, Cn: int, out: torch.Tensor, method: int, precision: int,
+                   addend: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """md_op_resize_nhwc_ex on raw storage: x [B, H, W, ld_in (x 2 for split-half)] -> a copy of the pre-filled raw buffer `out`
+    [B, OH, OW, ld_out (x 2)] with channels 0 .. Cn of every pixel written; addend: fp32 [OH, OW, Cn] or None."""
+    planes = 2 if precision == 4 else 1
+    assert x.is_cuda and out.is_cuda and x.is_contiguous() and x.dtype == out.dtype == _RAW_DTYPE[precision]
+    assert x.shape[3] % planes == 0 and out.shape[3] % planes == 0 and out.shape[0] == x.shape[0]
+    out = out.contiguous().clone()
+    B, H, W, _ = x.shape
+    OH, OW = int(out.shape[1]), int(out.shape[2])
+    if addend is not None:
+        addend = _f32c(addend)
+        assert tuple(addend.shape) == (OH, OW, Cn)
+    _lib.check(_lib.load().md_op_resize_nhwc_ex(dev.handle, _p(x), B, H, W, Cn, x.shape[3] // planes, _p(out), OH, OW, out.shape[3] // planes,
+                                                int(method), _p(addend), precision, _stream_ptr(dev.ordinal)))
+    return out
+
 
 
 def pyramid_patchify(dev: Device, x: torch.Tensor, window: int, patch: int = 16, method: int = 0, precision: int = 1,
@@ -69,7 +86,7 @@ def pyramid_patchify(dev: Device, x: torch.Tensor, window: int, patch: int = 16,
     lib = _lib.load()
     _lib.check(lib.md_op_pyramid_patchify(dev.handle, None, B, S, window, patch, method, precision, 0, None, C.byref(rows), C.byref(cols), None))
     if out is None:
-        out = torch.empty((rows.value, cols.value), dtype=_PREC_DTYPE[precision], device=x.device)
+        out = _raw_empty((rows.value,), cols.value, precision, x.device)   # split-half rows: [hi: cols | lo: cols]
     _lib.check(lib.md_op_pyramid_patchify(dev.handle, _p(x), B, S, window, patch, method, precision, int(force_generic), _p(out),
                                           C.byref(rows), C.byref(cols), _stream_ptr(dev.ordinal)))
     return out

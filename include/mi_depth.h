@@ -1446,12 +1446,17 @@ int md_op_rgb_to_input(md_device_t dev, const uint8_t* rgb_dev, size_t rgb_len, 
 /* `resize_bilinear_align_corners_false(x, [oh,ow], method)` (interpolate.rs:123-134), fp32 NCHW. */
 int md_op_resize_bilinear(md_device_t dev, const float* in_dev, int B, int C, int H, int W, float* out_dev,
                           int OH, int OW, int method, void* stream);
+/* The same with the post step of the last resize of `DepthPro::infer`: post = 1 writes the final depth
+ * 1 / clamp(blend, 1e-4, 1e4) (at equal input and output size: of the input itself); post = 0 is md_op_resize_bilinear. */
+int md_op_resize_bilinear_ex(md_device_t dev, const float* in_dev, int B, int C, int H, int W, float* out_dev,
+                             int OH, int OW, int method, int post, void* stream);
 /* The front of `DepthProEncoder::forward` as the engine runs it (encoder.rs:326-344): pyramid x1 = resize(x, 0.5),
  * x2 = resize(x, 0.25); split(x0, 0.25) | split(x1, 0.5) | x2 concatenated on dim 0 ([35B,3,win,win]); and the ViT's
  * patch extraction, written as the A matrix of the patch-embed GEMM: out[(tile * P + py * g + px)][c * ps^2 + ky * ps + kx]
  * in `precision`'s storage type. x [B,3,S,S] fp32 with S = 4 * window. rows_out / cols_out receive the matrix shape (pass
  * x_dev = out_dev = NULL to query it). force_generic != 0 selects the grid-stride kernel that serves
- * InterpolationMethod::Burn also for Custom (the one-read LDS-staged kernel is the default for Custom, patch 16). */
+ * InterpolationMethod::Burn also for Custom (the one-read LDS-staged kernel is the default for Custom, patch 16). A level-0
+ * tile stride (floor(0.75 * window)) that is no multiple of 4 is MD_ERR_UNSUPPORTED: level 0 is copied in 16-byte reads. */
 int md_op_pyramid_patchify(md_device_t dev, const float* x_dev, int B, int S, int window, int patch, int method, int precision,
                            int force_generic, void* out_dev, int* rows_out, int* cols_out, void* stream);
 /* `resize_bilinear(tensor, [oh, ow], _)` of the Depth-Anything-v3 head (depth_anything3/interpolate.rs:7-47) on the
@@ -1459,6 +1464,13 @@ int md_op_pyramid_patchify(md_device_t dev, const float* x_dev, int B, int S, in
  * / f32), C a multiple of 8. method MD_INTERP_BURN = align_corners=True (what that head uses), MD_INTERP_CUSTOM = False. */
 int md_op_resize_nhwc(md_device_t dev, const void* in_dev, int B, int H, int W, int C, void* out_dev, int OH, int OW,
                       int method, int precision, void* stream);
+/* The same launch in the forms the engines give it: pixels of ld_in / ld_out >= C logical channels (multiples of 8; columns
+ * C .. ld_out of `out` are not written), an optional fp32 addend table [OH, OW, C] shared by all batch items (NULL: none), and
+ * MD_PREC_F16X2 besides bf16 / f16 / f32. Both buffers hold the STORED bytes of `precision`'s storage type; a split-half pixel
+ * is [hi: ld | lo: ld]. Ordered on the stream like md_op_resize_nhwc (no synchronisation). ld < C or an unknown method /
+ * precision -> MD_ERR_INVALID_ARG; C % 8 != 0 or ld % 8 != 0 -> MD_ERR_UNSUPPORTED. */
+int md_op_resize_nhwc_ex(md_device_t dev, const void* in_dev, int B, int H, int W, int C, int ld_in, void* out_dev, int OH, int OW,
+                         int ld_out, int method, const float* addend_dev, int precision, void* stream);
 /* The frame path's Catmull-Rom taps (pipeline._catmull_rom / _sample_axis, host only): the window [left, left + count) of
  * output `index` of an in_len -> out_len pass and its normalised weights (capacity: count, at most 4 * in_len / out_len + 6;
  * weights may be NULL to query the window). */
