@@ -20,6 +20,7 @@ MD_FRAME_U8_GRAY, MD_FRAME_RGBA_F32 = 0, 1
 VIT_GEMM_RESID, VIT_GEMM_QKV, VIT_GEMM_FC1, VIT_GEMM_PATCH_EMBED = 0, 1, 2, 3
 DECODER_GEMM_CONV3, DECODER_GEMM_CONV3_S2, DECODER_GEMM_PIXSHUF, DECODER_GEMM_HEAD, DECODER_GEMM_HEAD_UP2 = 0, 1, 2, 3, 4
 INDEXED_GEMM_ROWS, INDEXED_GEMM_ROWS_RES, INDEXED_GEMM_PIXSHUF = 0, 1, 2
+COMPOSE_DECONV_CONV, COMPOSE_DECONV_PAIR, COMPOSE_C1C3, COMPOSE_HEAD = 0, 1, 2, 3
 TILE_256x256, TILE_128x128, TILE_256x32, TILE_128x64, TILE_64x64, TILE_AUTO = 0, 1, 2, 3, 4, 99
 
 
@@ -383,6 +384,7 @@ SYMBOLS = {
     "md_op_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "md_op_set_token0": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "md_op_border_bias_fix": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "md_op_compose_weights": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "md_op_layernorm_ex": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_P), C.POINTER(_P), C.c_float, _I, _I,
                                 C.c_float, _P, _I, _P, _P]),
     "md_op_store_rows": (_I, [_P, _P, C.c_int64, _I, _I, _P, _P]),

@@ -240,9 +240,11 @@ void gemm_record_form(const Form256& f);
 void gemm_forget_form();
 Form256 gemm_last_form();
 // What launch_gemm resolved for the calling host thread's last launch, whichever kernel of the family took it: the tile (TILE_AUTO's choice, the
-// tiles the head epilogues force) and the launcher-set GemmParams::ps_fast. tile = -1: no launch since gemm_forget_form() (md_debug_gemm_last_launch).
+// tiles the head epilogues force), the launcher-set GemmParams::ps_fast and the contraction length GemmParams::K (split-half: the padded
+// channels times the term count, so a test can tell a two-term from a three-term launch). tile = -1: no launch since gemm_forget_form()
+// (md_debug_gemm_last_launch).
 struct LaunchNote {
-  int tile = -1, ps_fast = 0;
+  int tile = -1, ps_fast = 0, K = 0;
 };
 LaunchNote gemm_last_launch();
 

@@ -314,7 +314,7 @@ int launch_gemm(GemmParams p, int amode, int prec, int tile, hipStream_t stream)
 #endif
   }
   if (p.epi == EPI_HEAD) tile = TILE_256x32;
-  g_last_launch.tile = tile; g_last_launch.ps_fast = p.ps_fast;
+  g_last_launch.tile = tile; g_last_launch.ps_fast = p.ps_fast; g_last_launch.K = p.K;
   if (prec == MD_PREC_F32) return launch_gemm_f32(p, amode, tile, stream);
   if (prec == MD_PREC_FP8) {
     if (p.out_fp8 && !(p.epi == EPI_STORE && p.act == ACT_GELU)) MD_FAIL(MD_ERR_UNSUPPORTED, "fp8 output is built for the GELU store only");

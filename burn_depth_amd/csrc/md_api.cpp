@@ -1318,6 +1318,33 @@ int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int 
   return s.finish();
 }
 
+// ---- the layer compositions of model_commit alone: the fp32 product a pack is made from, before pack_weight rounds it ----
+int md_op_compose_weights(md_device_t dev, int kind, int cin, int cmid, int cout, const float* w_first, const float* w_second,
+                          const float* bias_first, const float* bias_second, float* out, float* bias9_out, void* stream) {
+  if (!dev || !w_first || !w_second || !out) MD_FAIL(MD_ERR_INVALID_ARG, "compose_weights: null argument");
+  if (kind < MD_COMPOSE_DECONV_CONV || kind > MD_COMPOSE_HEAD) MD_FAIL(MD_ERR_INVALID_ARG, "compose_weights: kind %d", kind);
+  if (cin <= 0 || cmid <= 0 || cout <= 0) MD_FAIL(MD_ERR_SHAPE, "compose_weights: channels %d -> %d -> %d", cin, cmid, cout);
+  const bool any_bias = bias_first || bias_second || bias9_out;
+  if (any_bias && (kind == MD_COMPOSE_DECONV_CONV || kind == MD_COMPOSE_DECONV_PAIR))
+    MD_FAIL(MD_ERR_INVALID_ARG, "compose_weights: kind %d has no bias classes (the first layer is bias-free, the 1x1's bias rides on the launch)", kind);
+  if (any_bias && !(bias_first && bias_second && bias9_out))
+    MD_FAIL(MD_ERR_INVALID_ARG, "compose_weights: the bias classes need both layers' biases and bias9_out");
+  const int taps = kind == MD_COMPOSE_DECONV_CONV ? 4 : (kind == MD_COMPOSE_DECONV_PAIR ? 16 : (kind == MD_COMPOSE_C1C3 ? 9 : 36));
+  if ((long)cin * cout * taps >= (1L << 31) || (long)cin * cmid * 4 >= (1L << 31) || (long)cmid * cout * 9 >= (1L << 31))
+    MD_FAIL(MD_ERR_UNSUPPORTED, "compose_weights: tensors of this size are not a test");
+  OpStage s;
+  MD_TRY(s.open(dev, stream));
+  switch (kind) {
+    case MD_COMPOSE_DECONV_CONV: MD_TRY(compose_deconv_conv(w_first, w_second, cin, cmid, cout, out, s.st)); break;
+    case MD_COMPOSE_DECONV_PAIR: MD_TRY(compose_deconv_pair(w_first, w_second, cin, cmid, cout, out, s.st)); break;
+    case MD_COMPOSE_C1C3: MD_TRY(compose_c1c3(w_first, w_second, cin, cmid, cout, out, s.st)); break;
+    default: MD_TRY(compose_head(w_first, w_second, cin, cmid, cout, out, s.st)); break;
+  }
+  // PACK_C1C3_B / PACK_HEAD_B: the second layer's 3x3 weight, the first layer's bias, the second layer's bias
+  if (bias9_out) MD_TRY(compose_head_bias(w_second, bias_first, bias_second, cmid, cout, bias9_out, s.st));
+  return s.finish();
+}
+
 // ---- the kernels that write MFMA operands, alone: the caller's buffers hold the stored bytes (no widened copy) ----
 int md_op_layernorm_ex(md_device_t dev, float* x, int rows, int D, int S, int ngroups, const int* seq0, const int* nseq,
                        const float* const* gamma, const float* const* beta, float eps, int precision, int out_f32, float fp8_inv_scale,
@@ -1780,7 +1807,7 @@ int md_op_pose_to_camera(md_device_t dev, const float* pose, int B, int H, int W
 int md_debug_gemm_last_launch(int out[4]) {
   if (!out) return MD_ERR_INVALID_ARG;
   const LaunchNote n = gemm_last_launch();
-  out[0] = n.tile; out[1] = n.ps_fast; out[2] = 0; out[3] = 0;
+  out[0] = n.tile; out[1] = n.ps_fast; out[2] = n.K; out[3] = 0;
   return MD_OK;
 }
 

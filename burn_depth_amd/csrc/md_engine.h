@@ -458,6 +458,12 @@ int pack_weight(const float* src, const PackEntry& e, int prec, hipStream_t s);
 // fp32 [9][cout]
 int compose_head(const float* wd, const float* w1, int cin, int cmid, int cout, float* out, hipStream_t s);
 int compose_head_bias(const float* w1, const float* bd, const float* b1, int cmid, int cout, float* out, hipStream_t s);
+// The other compositions of model_commit (md_op_compose_weights launches them alone): deconv k2s2 [cin, cmid, 2, 2] -> conv 1x1 [cout, cmid]
+// as `out` [cin, cout, 2, 2]; two bias-free deconvolutions k2s2 [cin, cmid, 2, 2], [cmid, cout, 2, 2] as `out` [cin, cout, 4, 4]; conv 1x1
+// [cmid, cin] -> conv 3x3 [cout, cmid, 3, 3] as `out` [cout, cin, 3, 3] (its bias classes: compose_head_bias(w3, b of the 1x1, b of the 3x3))
+int compose_deconv_conv(const float* wd, const float* wo, int cin, int cmid, int cout, float* out, hipStream_t s);
+int compose_deconv_pair(const float* wa, const float* wb, int cin, int cmid, int cout, float* out, hipStream_t s);
+int compose_c1c3(const float* w1, const float* w3, int cin, int cmid, int cout, float* out, hipStream_t s);
 // number of values of w[0..n) that are not exactly representable as an IEEE half (synchronises the stream)
 int count_inexact_f16(const float* w, long n, hipStream_t s, unsigned* out);
 void fov_scalar_host(float fovx_deg, int H, int W, float* focal_px, float* fovy_rad);

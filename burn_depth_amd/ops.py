@@ -309,6 +309,36 @@ def border_bias_fix(dev: Device, fmap: torch.Tensor, C_: int, bias9: torch.Tenso
     return fmap
 
 
+_COMPOSE_SHAPES = {  # kind -> (first weight, second weight, product) of (cin, cmid, cout)
+    _lib.COMPOSE_DECONV_CONV: (lambda i, m, o: (i, m, 2, 2), lambda i, m, o: (o, m), lambda i, m, o: (i, o, 2, 2)),
+    _lib.COMPOSE_DECONV_PAIR: (lambda i, m, o: (i, m, 2, 2), lambda i, m, o: (m, o, 2, 2), lambda i, m, o: (i, o, 4, 4)),
+    _lib.COMPOSE_C1C3: (lambda i, m, o: (m, i), lambda i, m, o: (o, m, 3, 3), lambda i, m, o: (o, i, 3, 3)),
+    _lib.COMPOSE_HEAD: (lambda i, m, o: (i, m, 2, 2), lambda i, m, o: (o, m, 3, 3), lambda i, m, o: (4 * o, i, 3, 3)),
+}
+
+
+def compose_weights(dev: Device, kind: int, cin: int, cmid: int, cout: int, w_first: torch.Tensor, w_second: torch.Tensor,
+                    bias_first: Optional[torch.Tensor] = None, bias_second: Optional[torch.Tensor] = None, tail: int = 0, fill: float = 0.0):
+    """md_op_compose_weights: the fp32 weight product of two layers as the commit composes it (kind = _lib.COMPOSE_*) -> (product, bias9
+    [9, cout] or None). With biases (C1C3, HEAD) the nine position-class bias vectors come with it. `tail` extra elements behind both
+    outputs hold `fill`, as does every element the launch does not write: the caller checks that they come back."""
+    first, second, prod = (f(cin, cmid, cout) for f in _COMPOSE_SHAPES[kind])
+    w_first, w_second = _f32c(w_first), _f32c(w_second)
+    assert tuple(w_first.shape) == first and tuple(w_second.shape) == second, "weight shapes"
+    n = cin * cout * {0: 4, 1: 16, 2: 9, 3: 36}[kind]
+    out = torch.full((n + tail,), fill, dtype=torch.float32, device=w_first.device)
+    with_bias = bias_first is not None or bias_second is not None
+    if with_bias:
+        bias_first, bias_second = _f32c(bias_first), _f32c(bias_second)
+        assert bias_first.numel() == cmid and bias_second.numel() == cout, "bias shapes"
+    b9 = torch.full((9 * cout + tail,), fill, dtype=torch.float32, device=w_first.device) if with_bias else None
+    _lib.check(_lib.load().md_op_compose_weights(dev.handle, kind, cin, cmid, cout, _p(w_first), _p(w_second), _p(bias_first), _p(bias_second),
+                                                 _p(out), _p(b9), _stream_ptr(dev.ordinal)))
+    if tail:
+        return out, b9
+    return out.reshape(prod), (b9.reshape(9, cout) if b9 is not None else None)
+
+
 # ---- the kernels that write MFMA operands, alone: outputs are the STORED bytes (bf16 / f16 / fp32 tensors, split-half rows as f16
 # [.., 2 * width] = hi | lo, e4m3 as uint8) ----
 _RAW_DTYPE = {0: torch.bfloat16, 1: torch.float32, 2: torch.uint8, 3: torch.float16, 4: torch.float16}
@@ -451,11 +481,12 @@ def vit_gemm(dev: Device, kind: int, a: torch.Tensor, groups, precision: int, ti
 
 def gemm_last_form() -> dict:
     """md_debug_gemm_last_form + md_debug_gemm_last_launch: what this thread's last 256 x 256 GEMM launch ran (family -1: the operator
-    entry took another tile), and the tile and pixel-shuffle form (`tile`, `ps_fast`) launch_gemm resolved for the entry's launch."""
+    entry took another tile), and the tile, the pixel-shuffle form and the contraction length (`tile`, `ps_fast`, `K`) launch_gemm resolved
+    for the entry's launch."""
     v, n = (C.c_int * 8)(), (C.c_int * 4)()
     _lib.check(_lib.load().md_debug_gemm_last_form(C.byref(v)))
     _lib.check(_lib.load().md_debug_gemm_last_launch(C.byref(n)))
-    return dict(zip(("family", "ek", "fold", "qkv", "conv", "diag", "blocks", "grid", "tile", "ps_fast"), list(v) + list(n)[:2]))
+    return dict(zip(("family", "ek", "fold", "qkv", "conv", "diag", "blocks", "grid", "tile", "ps_fast", "K"), list(v) + list(n)[:3]))
 
 
 def decoder_gemm(dev: Device, kind: int, x: torch.Tensor, w, bias, precision: int, tile: int = _lib.TILE_AUTO, *, B: int, H: int, W: int, Cin: int,

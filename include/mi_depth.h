@@ -1579,6 +1579,27 @@ int md_op_set_token0(md_device_t dev, float* x, int nseq, int S, int D, const fl
 /* Adds bias9[class] - bias9[4] to the border pixels of the NHWC map [B,H,W,ld] (columns 0 .. C-1; in place), bias9 [9, C]. */
 int md_op_border_bias_fix(md_device_t dev, float* map, int B, int H, int W, int C, int ld, const float* bias9, int precision,
                           void* stream);
+/* ---- the layer compositions of the commit alone (test-only): two layers with nothing between them are packed as ONE layer on the
+ * product of their fp32 weights; this entry runs the commit's own composition launches on fp32 device tensors of the CALLER and
+ * returns the fp32 product before it is rounded and packed. cin -> cmid -> cout are the channels of the first and second layer.
+ *   DECONV_CONV  w_first [cin, cmid, 2, 2] (ConvTranspose2d k2 s2, no bias), w_second [cout, cmid] (Conv2d 1x1)
+ *                -> out [cin, cout, 2, 2], one k2 s2 deconvolution. The 1x1's bias is NOT composed: the deconvolution in front of it
+ *                has no bias, so W2 (deconv(x)) + b2 = deconv'(x) + b2 on every output pixel, and the engine hands b2 [cout] unchanged
+ *                to the pixel-shuffle launch as its bias (one value per output channel, the same for the four parities).
+ *   DECONV_PAIR  w_first [cin, cmid, 2, 2], w_second [cmid, cout, 2, 2] (both ConvTranspose2d k2 s2, no bias)
+ *                -> out [cin, cout, 4, 4], one k4 s4 deconvolution, tap (2 dy1 + dy2, 2 dx1 + dx2).
+ *   C1C3         w_first [cmid, cin] (Conv2d 1x1, bias_first [cmid]), w_second [cout, cmid, 3, 3] (Conv2d 3x3 pad 1, bias_second [cout])
+ *                -> out [cout, cin, 3, 3]; bias9_out [9, cout].
+ *   HEAD         w_first [cin, cmid, 2, 2] (ConvTranspose2d k2 s2, bias_first [cmid]), w_second [cout, cmid, 3, 3] (Conv2d 3x3 pad 1,
+ *                bias_second [cout]) -> out [4 cout, cin, 3, 3] on the deconvolution's input grid, column group 2 py + px = the output
+ *                pixel's parity; bias9_out [9, cout].
+ * bias9_out[3 ry + rx] = bias_second + the first layer's bias through the taps of the 3x3 that lie inside the map at an output pixel of
+ * row class ry (0 first row, 1 interior, 2 last row) and column class rx. bias_first, bias_second and bias9_out come all three or not at
+ * all (the weight alone). Refused before any launch, MD_ERR_INVALID_ARG unless noted: a null weight or `out`; an unknown kind; a channel
+ * count <= 0 (MD_ERR_SHAPE); any bias pointer with DECONV_CONV or DECONV_PAIR; one or two of the three bias pointers. ---- */
+typedef enum md_compose_kind { MD_COMPOSE_DECONV_CONV = 0, MD_COMPOSE_DECONV_PAIR = 1, MD_COMPOSE_C1C3 = 2, MD_COMPOSE_HEAD = 3 } md_compose_kind;
+int md_op_compose_weights(md_device_t dev, int kind, int cin, int cmid, int cout, const float* w_first, const float* w_second,
+                          const float* bias_first, const float* bias_second, float* out, float* bias9_out, void* stream);
 /* ---- the kernels that write MFMA operands, alone (test-only). Every output buffer is the caller's device memory and receives the
  * STORED bytes of `precision`'s storage type -- bf16, f16, fp32, split-half rows [hi: width | lo: width] of f16, e4m3 bytes --, no
  * widened copy, so a test can compare roundings bit for bit. Each call synchronises its stream before it returns. ---- */
@@ -1653,7 +1674,8 @@ int md_op_vit_gemm(md_device_t dev, const md_vit_gemm* desc, void* stream);
 int md_debug_gemm_last_form(int out[8]);
 /* Host-only: what the calling thread's last GEMM launch through md_op_vit_gemm / md_op_decoder_gemm resolved, whichever kernel of the
  * family took it -- out[4] = tile (0 = 256x256, 1 = 128x128, 2 = 256x32, 3 = 128x64, 4 = 64x64; -1: no launch), the launcher-set fast
- * form of the pixel shuffle (16-byte stores of whole 8-column groups), 0, 0. */
+ * form of the pixel shuffle (16-byte stores of whole 8-column groups), the contraction length K of the launch (split-half operands:
+ * the padded channels -- times 9 for a 3x3 convolution -- times the two or three terms of the weight), 0. */
 int md_debug_gemm_last_launch(int out[4]);
 /* ---- the GEMM forms of the convolutional decoders and heads alone (test-only): one launch of the GEMM family with the parameters the
  * engines' call sites give it, on buffers the CALLER owns. Activations, residual inputs and T-typed outputs are raw device tensors of

@@ -1,7 +1,9 @@
 """The two commit-time layer compositions of the depth head, restated in PyTorch on the CPU and checked against the
 uncomposed layers (Burn = PyTorch conv semantics). The index conventions below are the ones of `compose_head_kernel`,
-`compose_head_bias_kernel` and `compose_c1c3_kernel` (burn_depth_amd/csrc/md_engine.hip); the GPU parity tests then check
-the kernels themselves end to end.
+`compose_head_bias_kernel` and `compose_c1c3_kernel` (burn_depth_amd/csrc/md_engine.hip). This file checks the algebra
+alone; the kernels themselves are checked per element against fp64 by tests/test_compose_ops.py (md_op_compose_weights),
+which reuses `compose_head`, `bias_classes` and `class_map` from here. The end-to-end parity tests only see them through
+24 blocks and a decoder, at equal channel counts.
 
   * head.deconv (ConvTranspose2d k2 s2, bias) -> head.conv1 (Conv2d 3x3 pad 1, bias), mod.rs:106-107: one 3x3 convolution
     with 4 x Cout columns (one group per output parity) on the deconv's input grid + nine position-class bias vectors;
