@@ -133,6 +133,11 @@ class MdPointsRegister(C.Structure):
                 ("dropped", C.c_void_p), ("nearest", C.c_void_p), ("dist2", C.c_void_p)]
 
 
+class MdPointsRegisterPlane(C.Structure):
+    """md_points_register_plane (include/mi_depth.h)."""
+    _fields_ = [("target_normals", C.c_void_p), ("sum_r2", C.c_void_p)]
+
+
 class MdRenderOpts(C.Structure):
     """md_render_opts (include/mi_depth.h)."""
     _fields_ = [("pixel_offset", C.c_float), ("z_near", C.c_float), ("z_far", C.c_float), ("radius", C.c_int)]
@@ -330,6 +335,7 @@ SYMBOLS = {
     "md_op_cluster_points": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsClusters), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_op_match_points": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(MdPointsMatch), C.POINTER(MdPointsOutputs), _P, _P]),
     "md_op_register_points": (_I, [_P, _P, _P, C.c_int64, C.POINTER(MdPointsRegister), _P, _P, _P]),
+    "md_op_register_points_plane": (_I, [_P, _P, _P, C.c_int64, C.POINTER(MdPointsRegister), C.POINTER(MdPointsRegisterPlane), _P, _P, _P]),
     "md_raster_inline_pixels": (_I, []),
     "md_debug_raster_queue": (_I, [_I]),
     "md_da3_cfg_default": (None, [C.POINTER(MdDa3Cfg)]),
@@ -443,7 +449,7 @@ _POINTS_HEAD = [MdViewFilterOpts, MdPointsOpts, MdPointsOutputs]
 _POINTS_PARTS = [("normals", MdPointsNormals), ("voxel", MdPointsVoxel), ("render", MdPointsRender), ("mesh", MdPointsMesh),
                  ("raster", MdPointsRaster), ("outlier", MdPointsOutlier), ("decimate", MdPointsDecimate), ("components", MdPointsComponents),
                  ("smooth", MdPointsSmooth), ("planes", MdPointsPlanes), ("clusters", MdPointsClusters),
-                 ("match", MdPointsMatch), ("register", MdPointsRegister)]
+                 ("match", MdPointsMatch), ("register", MdPointsRegister), ("register_plane", MdPointsRegisterPlane)]
 SYMBOLS["md_infer_points"] = _infer_points(*_POINTS_HEAD[1:])
 SYMBOLS["md_infer_points_filtered"] = _infer_points(*_POINTS_HEAD)
 SYMBOLS.update({f"md_infer_points_{name}": _infer_points(*_POINTS_HEAD, *(p for _, p in _POINTS_PARTS[:i + 1]))

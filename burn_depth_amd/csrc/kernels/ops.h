@@ -394,13 +394,20 @@ struct RegisterParams {
   float* normals_out = nullptr; // [n,3]; null: skip
   int32_t* nearest = nullptr;   // [n] as MatchParams::nearest under the final transform; null: skip
   float* dist2 = nullptr;       // [n]; null: skip
+  // the point-to-plane form: off by default, and then nothing of it is read
+  bool plane = false;                     // the step sums the 29 leaves of every usable pair, the solve is reg_solve_plane
+  const float* target_normals = nullptr;  // [t,3]; plane: required with t > 0
+  double* sum_r2 = nullptr;               // [K + 1] the sum of squared point-to-plane residuals; plane only; null: skip
 };
 // bytes of the scratch (the matching's table and buckets of the target | 128 B of tile sums and 4 B of pair count per source
 // tile | the transform | flags)
 size_t register_scratch_bytes(int n, int t);
-// flags[0] != 0 after the launches = a probe loop ran out of table
+// the same for the point-to-plane form: 232 B of tile sums per source tile
+size_t register_plane_scratch_bytes(int n, int t);
+// flags[0] != 0 after the launches = a probe loop ran out of table. p.plane picks the form; the scratch is that form's.
 int launch_register_points(const RegisterParams& p, void* scratch, hipStream_t s);
 const int32_t* register_flags(const void* scratch, int n, int t);
+const int32_t* register_plane_flags(const void* scratch, int n, int t);
 
 // ---- point rendering (kernels/render.hip; md_op_render_points, md_infer_points_render) ----
 // A point list xyz [n,3] (+ u8 rgb [n,3]) and T pinhole target cameras -> per target a z-buffered depth / source row / colour

@@ -21,6 +21,9 @@
 //            entry K of the histories, the last counters and `transform`
 // All K iterations are always enqueued: the sequence is static. No float atomics; integer atomics for counters, one per wave.
 // No thread waits on another: every loop is bounded by the table size, a bucket size or the tile count. Vector stores only.
+//
+// The point-to-plane form (RegisterParams::plane) runs the same launches on sibling step and reduce kernels at the
+// end of this file: 29 leaves of every pair whose target normal is usable, reg_solve_plane, status 3 for a degenerate system.
 #include <algorithm>
 #include <cmath>
 
@@ -37,19 +40,19 @@ constexpr unsigned kNoDistance = 0x7F800000u;  // dist2 of a row without a neare
 
 struct RegisterScratch {  // the parts of the scratch buffer, 256-byte aligned
   MatchGrid g;
-  double* sums;  // [tiles, 16] the tile sums of the last step
+  double* sums;  // [tiles, 16] the tile sums of the last step ([tiles, 29] in the point-to-plane form)
   int* pairs;    // [tiles] its pair counts
   double* A;     // [12] the running transform
   int* flags;    // [0] a probe loop ran out, [1] dropped (when the caller takes none), [2] the bucket cursor, [8..16) the counters
   size_t bytes;
 };
 
-RegisterScratch carve(void* base, int n, int t) {
+RegisterScratch carve(void* base, int n, int t, int leaves = kRegLeaves) {
   const size_t nb = (size_t)tiles_of(n);
   RegisterScratch s;
   Carver c(base);
   s.g = carve_match_grid(c, t);
-  s.sums = c.take<double>(nb * kRegLeaves);
+  s.sums = c.take<double>(nb * (size_t)leaves);
   s.pairs = c.take<int>(nb);
   s.A = c.take<double>(12);
   s.flags = c.take<int>(kFlagWords);
@@ -237,7 +240,165 @@ __global__ void __launch_bounds__(kTileThreads) register_reduce_kernel(RegisterP
   }
 }
 
+// ---- the point-to-plane form: sibling kernels, so the point form's code above is what it was ----
+// The same tree over kRegPlaneLeaves = 29 values: a pair enters only when its target normal is usable (finite, not all zero), so
+// every leaf is finite -- a usable pair has finite q and n, and m of a paired row is finite -- and the butterfly argument of the
+// point form holds unchanged: the addition commutes bit for bit and lane 0 sees the halving tree's operand order. LDS 4 x 29 x 8
+// bytes. No float atomics, integer atomics for the per-wave counters only, vector stores only, no thread waits on another.
+__device__ __forceinline__ int plane_workgroup_sums(double* acc, int n, double (*wave_sum)[kRegPlaneLeaves], int* wave_n, double* leaf) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int h = 32; h >= 1; h >>= 1) {
+#pragma unroll
+    for (int l = 0; l < kRegPlaneLeaves; ++l) acc[l] = acc[l] + __shfl_xor(acc[l], h, 64);
+    n += __shfl_xor(n, h, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int l = 0; l < kRegPlaneLeaves; ++l) wave_sum[wave][l] = acc[l];
+    wave_n[wave] = n;
+  }
+  __syncthreads();
+  if (tid < kRegPlaneLeaves) *leaf = (wave_sum[0][tid] + wave_sum[1][tid]) + (wave_sum[2][tid] + wave_sum[3][tid]);
+  return (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+}
+
+// register_step_kernel with the winner's normal loaded behind its row (12 more bytes per paired row) and the 29 leaves of the
+// MOVED row. nearest / dist2 report the pair whatever its normal; only usable pairs are summed and counted.
+template <bool kEval>
+__global__ void __launch_bounds__(kTileThreads) register_plane_step_kernel(RegisterParams p, const double* __restrict__ A_dev,
+                                                                       const unsigned long long* __restrict__ keys,
+                                                                       const unsigned* __restrict__ cnt, const unsigned* __restrict__ start,
+                                                                       const uint4* __restrict__ bucket, unsigned long long mask,
+                                                                       double* __restrict__ sums, int* __restrict__ pairs, int32_t* stats,
+                                                                       int32_t* dropped) {
+  __shared__ double wave_sum[kTileWaves][kRegPlaneLeaves];
+  __shared__ int wave_n[kTileWaves];
+  if (!kEval && stats[1] != 0) return;  // the whole grid
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  double A[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) A[i] = A_dev[i];
+  const int live = live_count(p.in_count, p.B, p.n);
+  const float r2 = p.radius * p.radius;
+  const unsigned bucket_rows = (unsigned)p.t;
+  double acc[kRegPlaneLeaves];
+#pragma unroll
+  for (int l = 0; l < kRegPlaneLeaves; ++l) acc[l] = 0.;
+  int n_pair = 0, n_in = 0, n_out = 0;
+  for (int s = 0; s < kTileSteps; ++s) {
+    const long i = tile_item(tile, s);
+    bool in_range = false, hit = false, row = false, usable = false;
+    if (i < live) {
+      row = true;
+      const float x = p.xyz[i * 3], y = p.xyz[i * 3 + 1], z = p.xyz[i * 3 + 2];
+      const float m[3] = {reg_move_axis(A, 0, x, y, z), reg_move_axis(A, 1, x, y, z), reg_move_axis(A, 2, x, y, z)};
+      unsigned long long own = 0ull, best = ~0ull;
+      in_range = grid_cell_key(m[0], m[1], m[2], p.radius, &own);
+      if (in_range) best = match_grid_nearest(m[0], m[1], m[2], own, r2, keys, cnt, start, bucket, mask, bucket_rows);
+      hit = best != ~0ull;
+      const unsigned d2_bits = hit ? (unsigned)(best >> 32) : kNoDistance;
+      if (hit) {
+        const long j = (long)(unsigned)(best & 0xFFFFFFFFull) * 3;
+        const float nrm[3] = {p.target_normals[j], p.target_normals[j + 1], p.target_normals[j + 2]};
+        usable = reg_normal_usable(nrm);
+        if (usable) {
+          const float dst[3] = {p.target[j], p.target[j + 1], p.target[j + 2]};
+          reg_add_plane_leaves(acc, m, dst, nrm, __uint_as_float(d2_bits));
+        }
+      }
+      if (kEval) {
+        if (p.normals_out) {
+          const float nx = p.normals[i * 3], ny = p.normals[i * 3 + 1], nz = p.normals[i * 3 + 2];
+          unsigned* o = (unsigned*)p.normals_out + i * 3;
+          o[0] = reg_out_bits(reg_turn_axis(A, 0, nx, ny, nz));
+          o[1] = reg_out_bits(reg_turn_axis(A, 1, nx, ny, nz));
+          o[2] = reg_out_bits(reg_turn_axis(A, 2, nx, ny, nz));
+        }
+        if (p.xyz_out) {  // may be xyz: this thread has read its row
+          unsigned* o = (unsigned*)p.xyz_out + i * 3;
+          o[0] = reg_out_bits(m[0]);
+          o[1] = reg_out_bits(m[1]);
+          o[2] = reg_out_bits(m[2]);
+        }
+        if (p.nearest) p.nearest[i] = hit ? (int32_t)(unsigned)(best & 0xFFFFFFFFull) : (in_range ? -1 : -2);
+        if (p.dist2) ((unsigned*)p.dist2)[i] = d2_bits;
+      }
+    }
+    n_pair += usable ? 1 : 0;
+    if (kEval) {
+      n_in += __popcll(__ballot(in_range));
+      n_out += __popcll(__ballot(row && !in_range));
+    }
+  }
+  if (kEval && lane == 0) {  // one add per wave and counter
+    if (n_in) atomicAdd(stats + 2, n_in);
+    if (n_out) atomicAdd(dropped, n_out);
+  }
+  double leaf = 0.;
+  const int n = plane_workgroup_sums(acc, n_pair, wave_sum, wave_n, &leaf);
+  if (tid < kRegPlaneLeaves) sums[(long)tile * kRegPlaneLeaves + tid] = leaf;
+  if (tid == 0) pairs[tile] = n;
+}
+
+// register_reduce_kernel over 29 sums with reg_solve_plane; a degenerate system is status 3 and A stays. An iteration that a
+// set status skips writes its 0 into sum_r2 here, so the reset kernel is the point form's.
+template <bool kSolve>
+__global__ void __launch_bounds__(kTileThreads) register_plane_reduce_kernel(RegisterParams p, int k, int tiles, const double* __restrict__ sums,
+                                                                         const int* __restrict__ pairs, double* A_dev, int32_t* stats) {
+  __shared__ double wave_sum[kTileWaves][kRegPlaneLeaves];
+  __shared__ int wave_n[kTileWaves];
+  __shared__ double S[kRegPlaneLeaves];
+  const int tid = threadIdx.x;
+  if (kSolve && stats[1] != 0) {  // the whole workgroup
+    if (tid == 0 && p.sum_r2) p.sum_r2[k] = 0.;
+    return;
+  }
+  double acc[kRegPlaneLeaves];
+#pragma unroll
+  for (int l = 0; l < kRegPlaneLeaves; ++l) acc[l] = 0.;
+  int n_thread = 0;
+  for (int tile = tid; tile < tiles; tile += kTileThreads) {
+#pragma unroll
+    for (int l = 0; l < kRegPlaneLeaves; ++l) acc[l] = acc[l] + sums[(long)tile * kRegPlaneLeaves + l];
+    n_thread += pairs[tile];
+  }
+  double leaf = 0.;
+  const int n = plane_workgroup_sums(acc, n_thread, wave_sum, wave_n, &leaf);
+  if (tid < kRegPlaneLeaves) S[tid] = leaf;
+  __syncthreads();
+  if (tid != 0) return;
+  if (p.pairs) p.pairs[k] = n;
+  if (p.sum_d2) p.sum_d2[k] = S[28];
+  if (p.sum_r2) p.sum_r2[k] = S[27];
+  if (kSolve) {
+    if (n < p.min_pairs) {
+      stats[1] = 2;
+      return;
+    }
+    double A_old[12], A_new[12];
+    for (int i = 0; i < 12; ++i) A_old[i] = A_dev[i];
+    if (!reg_solve_plane(n, S, A_old, A_new)) {
+      stats[1] = 3;
+      return;
+    }
+    for (int i = 0; i < 12; ++i) A_dev[i] = A_new[i];
+    stats[0] = stats[0] + 1;
+    if ((p.rot_eps > 0. || p.trans_eps > 0.) && reg_converged(A_new, A_old, p.rot_eps, p.trans_eps)) stats[1] = 1;
+  } else {
+    stats[3] = n;
+    if (p.transform)
+      for (int i = 0; i < 12; ++i) p.transform[i] = A_dev[i];
+  }
+}
+
 }  // namespace
+
+size_t register_plane_scratch_bytes(int n, int t) { return carve(nullptr, n > 0 ? n : 0, t > 0 ? t : 0, kRegPlaneLeaves).bytes; }
+
+const int32_t* register_plane_flags(const void* scratch, int n, int t) {
+  return carve((void*)scratch, n > 0 ? n : 0, t > 0 ? t : 0, kRegPlaneLeaves).flags;
+}
 
 size_t register_scratch_bytes(int n, int t) { return carve(nullptr, n > 0 ? n : 0, t > 0 ? t : 0).bytes; }
 
@@ -251,6 +412,9 @@ int launch_register_points(const RegisterParams& p, void* scratch, hipStream_t s
     MD_FAIL(MD_ERR_INVALID_ARG, "radius = %g: it and its square must be finite and > 0", (double)p.radius);
   if (p.iterations < 1 || p.iterations > 64) MD_FAIL(MD_ERR_INVALID_ARG, "iterations = %d outside 1..64", p.iterations);
   if (p.min_pairs < 3) MD_FAIL(MD_ERR_INVALID_ARG, "min_pairs = %d: at least 3", p.min_pairs);
+  if (p.plane && p.min_pairs < 6) MD_FAIL(MD_ERR_INVALID_ARG, "min_pairs = %d: the point-to-plane form takes at least 6", p.min_pairs);
+  if (p.plane && p.t > 0 && !p.target_normals) MD_FAIL(MD_ERR_INVALID_ARG, "the point-to-plane form needs the target's normals");
+  if (!p.plane && p.sum_r2) MD_FAIL(MD_ERR_INVALID_ARG, "sum_r2 is the point-to-plane form's");
   if (!(p.rot_eps >= 0.) || !std::isfinite(p.rot_eps) || !(p.trans_eps >= 0.) || !std::isfinite(p.trans_eps))
     MD_FAIL(MD_ERR_INVALID_ARG, "rot_eps = %g, trans_eps = %g: finite and >= 0", p.rot_eps, p.trans_eps);
   for (int i = 0; i < 12; ++i)
@@ -259,7 +423,7 @@ int launch_register_points(const RegisterParams& p, void* scratch, hipStream_t s
   if (p.n > 0 && !p.xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
   if (p.normals_out && !p.normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
   if (p.B < 1) MD_FAIL(MD_ERR_SHAPE, "registration of %d views", p.B);
-  const RegisterScratch v = carve(scratch, p.n, p.t);
+  const RegisterScratch v = carve(scratch, p.n, p.t, p.plane ? kRegPlaneLeaves : kRegLeaves);
   const size_t slots = voxel_table_slots(p.t);
   const int nb = tiles_of(p.n);
   const size_t quads = slots / 4;
@@ -280,6 +444,25 @@ int launch_register_points(const RegisterParams& p, void* scratch, hipStream_t s
     hipLaunchKernelGGL(register_fill_kernel, dim3(target_grid), dim3(kTileThreads), 0, s, p.target, p.t, v.g.start, v.g.fill, v.g.slot, v.g.bucket,
                        v.flags);
     MD_HIP(hipGetLastError());
+  }
+  if (p.plane) {  // the same sequence on the sibling kernels
+    for (int k = 0; k < p.iterations; ++k) {
+      if (nb > 0) {
+        hipLaunchKernelGGL(register_plane_step_kernel<false>, dim3(nb), dim3(kTileThreads), 0, s, p, v.A, v.g.keys, v.g.cnt, v.g.start, v.g.bucket,
+                           mask, v.sums, v.pairs, stats, dropped);
+        MD_HIP(hipGetLastError());
+      }
+      hipLaunchKernelGGL(register_plane_reduce_kernel<true>, dim3(1), dim3(kTileThreads), 0, s, p, k, nb, v.sums, v.pairs, v.A, stats);
+      MD_HIP(hipGetLastError());
+    }
+    if (nb > 0) {
+      hipLaunchKernelGGL(register_plane_step_kernel<true>, dim3(nb), dim3(kTileThreads), 0, s, p, v.A, v.g.keys, v.g.cnt, v.g.start, v.g.bucket, mask,
+                         v.sums, v.pairs, stats, dropped);
+      MD_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(register_plane_reduce_kernel<false>, dim3(1), dim3(kTileThreads), 0, s, p, p.iterations, nb, v.sums, v.pairs, v.A, stats);
+    MD_HIP(hipGetLastError());
+    return MD_OK;
   }
   for (int k = 0; k < p.iterations; ++k) {
     if (nb > 0) {

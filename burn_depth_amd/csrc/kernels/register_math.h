@@ -19,6 +19,7 @@
 namespace md {
 
 constexpr int kRegLeaves = 16;  // per pair: p (3), q (3), p_a * q_b (9, at 6 + 3 a + b), d2 (1)
+constexpr int kRegPlaneLeaves = 29;  // per usable pair of the point-to-plane form: J J^T (21), J r (6), r r (1), d2 (1)
 // Cyclic Jacobi sweeps of the 4x4 solve. Convergence is quadratic; tests/test_register_host.py measures the distance to an SVD
 // solve of the same sums at this count (DESIGN 12.14 records it).
 constexpr int kRegSweeps = 8;
@@ -77,6 +78,15 @@ MD_REG_HD void reg_jacobi_rotate(double a[4][4], double v[4][4], int p, int q) {
   }
 }
 
+// The rotation matrix of the unit quaternion (w, x, y, z), row-major into R[0..9). Both solves end in these lines.
+MD_REG_HD void reg_quat_matrix(double w, double x, double y, double z, double* R) {
+  const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+  const double xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+  R[0] = ((ww + xx) - yy) - zz; R[1] = 2.0 * (xy - wz);       R[2] = 2.0 * (xz + wy);
+  R[3] = 2.0 * (xy + wz);       R[4] = ((ww - xx) + yy) - zz; R[5] = 2.0 * (yz - wx);
+  R[6] = 2.0 * (xz - wy);       R[7] = 2.0 * (yz + wx);       R[8] = ((ww - xx) - yy) + zz;
+}
+
 // The transform that moves the n paired source rows onto their target rows in the least-squares sense (Horn's quaternion
 // solve), from the pair count n >= 1 and the sixteen sums S. Writes A[0..12).
 MD_REG_HD void reg_solve(int n, const double* S, double* A) {
@@ -111,11 +121,7 @@ MD_REG_HD void reg_solve(int n, const double* S, double* A) {
   if (w < 0.0) {
     w = -w; x = -x; y = -y; z = -z;
   }
-  const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-  const double xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-  A[0] = ((ww + xx) - yy) - zz; A[1] = 2.0 * (xy - wz);       A[2] = 2.0 * (xz + wy);
-  A[3] = 2.0 * (xy + wz);       A[4] = ((ww - xx) + yy) - zz; A[5] = 2.0 * (yz - wx);
-  A[6] = 2.0 * (xz - wy);       A[7] = 2.0 * (yz + wx);       A[8] = ((ww - xx) - yy) + zz;
+  reg_quat_matrix(w, x, y, z, A);
   for (int a = 0; a < 3; ++a) A[9 + a] = qbar[a] - ((A[3 * a] * pbar[0] + A[3 * a + 1] * pbar[1]) + A[3 * a + 2] * pbar[2]);
 }
 
@@ -131,6 +137,83 @@ MD_REG_HD bool reg_converged(const double* A_new, const double* A_old, double ro
     dt = d > dt ? d : dt;
   }
   return dr <= rot_eps && dt <= trans_eps;
+}
+
+// ---- the point-to-plane form ----
+// A usable pair is a pair whose target normal has three finite components that are not all zero.
+MD_REG_HD bool reg_normal_usable(const float* n) {
+  const bool finite = n[0] - n[0] == 0.f && n[1] - n[1] == 0.f && n[2] - n[2] == 0.f;
+  return finite && (n[0] != 0.f || n[1] != 0.f || n[2] != 0.f);
+}
+
+// acc[0..29) += the leaves of the usable pair (moved source row m, target row q, its normal n, squared distance d2):
+// J = (m x n, n), leaves 0..20 the upper triangle of J J^T in row-major order, 21..26 J_i * r with r = (q - m) . n, 27 r * r,
+// 28 d2. The products of widened f32 are exact; every other operation rounds once.
+MD_REG_HD void reg_add_plane_leaves(double* acc, const float* m, const float* q, const float* n, float d2) {
+  const double m0 = (double)m[0], m1 = (double)m[1], m2 = (double)m[2];
+  const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
+  double J[6];
+  J[0] = m1 * n2 - m2 * n1;
+  J[1] = m2 * n0 - m0 * n2;
+  J[2] = m0 * n1 - m1 * n0;
+  J[3] = n0; J[4] = n1; J[5] = n2;
+  const double d0 = (double)q[0] - m0, d1 = (double)q[1] - m1, dd2 = (double)q[2] - m2;
+  const double r = (d0 * n0 + d1 * n1) + dd2 * n2;
+  int l = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j, ++l) acc[l] = acc[l] + J[i] * J[j];
+  for (int i = 0; i < 6; ++i) acc[21 + i] = acc[21 + i] + J[i] * r;
+  acc[27] = acc[27] + r * r;
+  acc[28] = acc[28] + (double)d2;
+}
+
+// The increment of the point-to-plane step from the 29 sums S, composed onto A_old: M x = b with M the symmetric 6x6 of leaves
+// 0..20 and b leaves 21..26, by a Cholesky factorisation in the order j = 0..5 and the two substitutions; x = (w, tau). The
+// rotation of the increment is that of the quaternion (1, w/2) normalised. -> false when the system is degenerate (a pivot that
+// is not > 0, or a component of x that is not finite); A_new is then not written. n is the usable pair count (>= 1; unused by
+// the arithmetic: the normal equations carry no mean).
+MD_REG_HD bool reg_solve_plane(int n, const double* S, const double* A_old, double* A_new) {
+  (void)n;
+  double M[6][6], L[6][6], x[6], y[6];
+  int l = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j, ++l) M[i][j] = M[j][i] = S[l];
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) L[i][j] = 0.0;
+  for (int j = 0; j < 6; ++j) {
+    double s = M[j][j];
+    for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
+    if (!(s > 0.0)) return false;
+    L[j][j] = sqrt(s);
+    for (int i = j + 1; i < 6; ++i) {
+      double v = M[i][j];
+      for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
+      L[i][j] = v / L[j][j];
+    }
+  }
+  for (int i = 0; i < 6; ++i) {  // L y = b
+    double v = S[21 + i];
+    for (int k = 0; k < i; ++k) v = v - L[i][k] * y[k];
+    y[i] = v / L[i][i];
+  }
+  for (int i = 5; i >= 0; --i) {  // L^T x = y
+    double v = y[i];
+    for (int k = i + 1; k < 6; ++k) v = v - L[k][i] * x[k];
+    x[i] = v / L[i][i];
+  }
+  for (int i = 0; i < 6; ++i)
+    if (!(x[i] - x[i] == 0.0)) return false;
+  double qx = 0.5 * x[0], qy = 0.5 * x[1], qz = 0.5 * x[2];
+  const double len = sqrt(((1.0 + qx * qx) + qy * qy) + qz * qz);
+  const double qw = 1.0 / len;
+  qx = qx / len; qy = qy / len; qz = qz / len;
+  double dR[9];
+  reg_quat_matrix(qw, qx, qy, qz, dR);
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) A_new[3 * a + b] = (dR[3 * a] * A_old[b] + dR[3 * a + 1] * A_old[3 + b]) + dR[3 * a + 2] * A_old[6 + b];
+    A_new[9 + a] = ((dR[3 * a] * A_old[9] + dR[3 * a + 1] * A_old[10]) + dR[3 * a + 2] * A_old[11]) + x[3 + a];
+  }
+  return true;
 }
 
 }  // namespace md

@@ -788,6 +788,23 @@ int md_op_register_points(md_device_t dev, const float* xyz_dev, const float* no
   return op_register_points(dev, xyz_dev, normals_dev, N, reg, xyz_out, normals_out, (hipStream_t)stream);
 }
 
+int md_infer_points_register_plane(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                                   const md_points_cameras* cam, const md_view_filter_opts* fo, const md_points_opts* o, const md_points_outputs* out,
+                                   const md_points_normals* nrm, const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                                   const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                                   const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
+                                   const md_points_clusters* clu, const md_points_match* mat, const md_points_register* reg,
+                                   const md_points_register_plane* plane, int out_kind, void* stream) {
+  PointsCall c{nchw, B, H, W, in_kind, rgb, cam, o, out, out_kind, fo, nrm, vox, false, rnd, mesh, rst};
+  c.outl = outl; c.dec = dec; c.comp = comp; c.smooth = smooth; c.pln = pln; c.clu = clu; c.mat = mat; c.reg = reg; c.rpl = plane;
+  return infer_points(m, c, (hipStream_t)stream);
+}
+
+int md_op_register_points_plane(md_device_t dev, const float* xyz_dev, const float* normals_dev, int64_t N, const md_points_register* reg,
+                                const md_points_register_plane* plane, float* xyz_out, float* normals_out, void* stream) {
+  return op_register_points(dev, xyz_dev, normals_dev, N, reg, xyz_out, normals_out, (hipStream_t)stream, plane);
+}
+
 int md_raster_inline_pixels(void) { return md::raster_inline_pixels(); }
 int md_debug_raster_queue(int capacity) { return capacity < 0 ? MD_ERR_INVALID_ARG : md::raster_queue_capacity(capacity); }
 

@@ -376,7 +376,7 @@ struct PointList {  // md_op_voxel_thin's input rows on the device: xyz [N,3], c
   const float* normals = nullptr;
   int64_t N = 0;
 };
-// One md_infer_points* request: what the widest entry (md_infer_points_match) takes. A narrower entry leaves the parts it lacks
+// One md_infer_points* request: what the widest entry (md_infer_points_register_plane) takes. A narrower entry leaves the parts it lacks
 // null, and a null part is the call without it (nrm all zero and voxel == 0 likewise).
 struct PointsCall {
   const float* nchw = nullptr;  // the image [B,3,H,W], of in_kind
@@ -402,6 +402,7 @@ struct PointsCall {
   const md_points_clusters* clu = nullptr;     // given: clustering of the list behind the plane stage (pointers of out_kind); mode 1 writes that list
   const md_points_match* mat = nullptr;        // given: matching against a reference cloud between the plane stage and the clustering (pointers of out_kind, the target of its own kind); mode 1 / 2 writes the list
   const md_points_register* reg = nullptr;     // given: rigid registration onto a reference cloud directly in front of the matching, on the list it reads; apply moves that list in place
+  const md_points_register_plane* rpl = nullptr;  // given with target_normals: `reg` runs in the point-to-plane form (normals of reg's target_kind, sum_r2 of out_kind)
 };
 // nrm (md_op_unproject_normals): null or all zero = md_op_unproject
 int op_unproject(md_device_t dev, const DepthMaps& in, const md_points_cameras* cam, const md_points_opts* o, const md_points_outputs* out,
@@ -433,8 +434,9 @@ int op_cluster_points(md_device_t dev, const PointList& in, const md_points_clus
 int op_match_points(md_device_t dev, const PointList& in, const md_points_match* mat, const md_points_outputs* out, float* normals_out,
                     hipStream_t stream);
 // xyz [N,3] (+ normals): the rows, one view; xyz_out (may be xyz) / normals_out [N,3] or null
+// plane with target_normals: the point-to-plane form (md_op_register_points_plane)
 int op_register_points(md_device_t dev, const float* xyz, const float* normals, int64_t N, const md_points_register* reg, float* xyz_out,
-                       float* normals_out, hipStream_t stream);
+                       float* normals_out, hipStream_t stream, const md_points_register_plane* plane = nullptr);
 // in.xyz / in.rgb: the list; count: its device count word or null
 int op_render_points(md_device_t dev, const PointList& in, const int32_t* count, int T, int H, int W, const md_points_cameras* cam,
                      const md_render_opts* o, const md_render_outputs* out, hipStream_t stream);

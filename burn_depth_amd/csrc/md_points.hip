@@ -70,6 +70,7 @@ struct md_model_s::PointsState {
   md::GrowBuf<float> mtarget;     // the device copy of a host target [T,3]
   md::GrowBuf<void> rtable;       // md_infer_points_register: the registration's scratch (register_scratch_bytes)
   md::GrowBuf<float> rtarget;     // the device copy of its host target [T,3]
+  md::GrowBuf<float> rnormals;    // md_infer_points_register_plane: the device copy of the host target's normals [T,3]
   int dec_rows = 0, dec_faces = 0, dec_views = 0;  // what the last decimation covered (where its flags lie in dtable); 0 = none ran.
                                                    // Like vox_rows / outl_rows it is set where the stage is enqueued: a graph replay does not move it
   int vox_rows = 0;               // rows the last thinning call covered (where its flags lie in vtable); 0 = none ran
@@ -80,6 +81,7 @@ struct md_model_s::PointsState {
   bool mat_ran = false;
   int reg_rows = 0, reg_target = 0;  // likewise for the registration and rtable
   bool reg_ran = false;
+  bool reg_plane = false;  // that registration ran in the point-to-plane form: its flags lie behind 29-leaf tile sums
   float* k_home() const { return cams.p; }
   float* e_home(int B) const { return cams.p + (size_t)B * 9; }
   float* f_home(int B) const { return cams.p + (size_t)B * 21; }
@@ -338,6 +340,7 @@ ClustersParams make_clusters(const md_points_clusters& f) {
 
 bool match_on(const md_points_match* q) { return q && q->radius != 0.f; }
 bool register_on(const md_points_register* q) { return q && q->radius != 0.f; }
+bool register_plane_on(const md_points_register_plane* q) { return q && q->target_normals; }
 
 // model call: radius == 0 is the call without the stage and takes none of its outputs; the operator takes a device target only
 int check_match(const md_points_match* q, const md_points_outputs* out, bool op) {
@@ -781,9 +784,21 @@ int check_register(const md_points_register* q, bool op) {
   return MD_OK;
 }
 
-// the options and the outputs of the stage's own; the caller adds the rows
-RegisterParams make_register(const md_points_register& f) {
+// The refusals of md_points_register_plane before any launch, behind check_register's. Without target_normals the part is off
+// and nothing of it is read.
+int check_register_plane(const md_points_register* q, const md_points_register_plane* pl) {
+  if (!register_plane_on(pl)) return MD_OK;
+  if (!register_on(q) || !q->target) MD_FAIL(MD_ERR_INVALID_ARG, "target_normals without a target");
+  if (q->min_pairs < 6) MD_FAIL(MD_ERR_INVALID_ARG, "min_pairs = %d: the point-to-plane form takes at least 6", q->min_pairs);
+  return MD_OK;
+}
+
+// the options and the outputs of the stage's own; the caller adds the rows. pl on: the point-to-plane form
+RegisterParams make_register(const md_points_register& f, const md_points_register_plane* pl = nullptr) {
   RegisterParams q;
+  if (register_plane_on(pl)) {
+    q.plane = true; q.target_normals = pl->target_normals; q.sum_r2 = pl->sum_r2;
+  }
   q.radius = f.radius; q.target = f.target; q.t = (int)f.target_rows;
   q.iterations = f.iterations; q.min_pairs = f.min_pairs; q.rot_eps = f.rot_eps; q.trans_eps = f.trans_eps;
   if (f.init)
@@ -796,21 +811,23 @@ RegisterParams make_register(const md_points_register& f) {
 }  // namespace
 
 int op_register_points(md_device_t dev, const float* xyz, const float* normals, int64_t N, const md_points_register* reg, float* xyz_out,
-                       float* normals_out, hipStream_t stream) {
+                       float* normals_out, hipStream_t stream, const md_points_register_plane* plane) {
   if (!reg) MD_FAIL(MD_ERR_INVALID_ARG, "register options are null");
   MD_TRY(check_register(reg, true));
+  MD_TRY(check_register_plane(reg, plane));
   if (N < 0) MD_FAIL(MD_ERR_INVALID_ARG, "N = %lld is negative", (long long)N);
   if (normals_out && !normals) MD_FAIL(MD_ERR_INVALID_ARG, "a normals output needs a normals row");
   if (N >= (1ll << 30)) MD_FAIL(MD_ERR_SHAPE, "registration takes fewer than 2^30 rows, got %lld", (long long)N);
   if (N > 0 && !xyz) MD_FAIL(MD_ERR_INVALID_ARG, "xyz pointer is null");
   hipStream_t st;
   MD_TRY(op_begin(dev, stream, &st));
-  RegisterParams p = make_register(*reg);
+  RegisterParams p = make_register(*reg, plane);
   p.xyz = xyz; p.normals = normals; p.n = (int)N; p.B = 1;
   p.xyz_out = xyz_out; p.normals_out = normals_out;
   OpScratch scratch(st);
-  MD_TRY(scratch.alloc(register_scratch_bytes(p.n, p.t)));
-  return scratch.finish_flags(launch_register_points(p, scratch.p, st), register_flags(scratch.p, p.n, p.t), nullptr, kRegisterRanOut);
+  MD_TRY(scratch.alloc(p.plane ? register_plane_scratch_bytes(p.n, p.t) : register_scratch_bytes(p.n, p.t)));
+  const int32_t* flags = p.plane ? register_plane_flags(scratch.p, p.n, p.t) : register_flags(scratch.p, p.n, p.t);
+  return scratch.finish_flags(launch_register_points(p, scratch.p, st), flags, nullptr, kRegisterRanOut);
 }
 
 int op_decimate_mesh(md_device_t dev, const PointList& in, const int32_t* faces, int64_t F, const md_points_decimate* dec,
@@ -963,7 +980,9 @@ int points_clusters_overflow(md_model_t m, int64_t* out) {
 
 int points_register_overflow(md_model_t m, int64_t* out) {
   const md_model_s::PointsState* f = m->points;
-  return read_overflow(m, f && f->reg_ran && f->rtable.p ? register_flags(f->rtable.p, f->reg_rows, f->reg_target) : nullptr, nullptr, out);
+  if (!f || !f->reg_ran || !f->rtable.p) return read_overflow(m, nullptr, nullptr, out);
+  return read_overflow(m, f->reg_plane ? register_plane_flags(f->rtable.p, f->reg_rows, f->reg_target) : register_flags(f->rtable.p, f->reg_rows, f->reg_target),
+                       nullptr, out);
 }
 
 int points_match_overflow(md_model_t m, int64_t* out) {
@@ -1048,6 +1067,7 @@ struct PointsPlan {
   bool reg = false;          // the registration is on, directly in front of the matching
   RegisterParams rg;         // reg: launch_register_points', on the list the matching reads (or would read)
   const float* host_reg_target = nullptr;  // reg with a host target: the caller's rows, which stage_inputs copies to rtarget
+  const float* host_reg_normals = nullptr; // reg in the point-to-plane form with a host target: its normals, copied to rnormals
   int32_t register_rows = 0; // reg on a list of the model's own, with host outputs: its rows, for the slots of nearest / dist2
   int32_t match_rows = 0;    // mcut with host outputs: the rows of the matching's input list, for the slots of its row outputs
   std::vector<OutSlot> slots;
@@ -1177,6 +1197,7 @@ size_t place_outputs(const PointsCall& c, PointsPlan& pl, char* base) {
     slot(q.transform, pl.rg.transform, 8, 12);
     slot(q.pairs, pl.rg.pairs, 4, history);
     slot(q.sum_d2, pl.rg.sum_d2, 8, history);
+    if (pl.rg.plane) slot(c.rpl->sum_r2, pl.rg.sum_r2, 8, history);
     slot(q.stats, pl.rg.stats, 4, 8);
     slot(q.dropped, pl.rg.dropped, 4, 1);
     if (pl.mcut || pl.ccut) {
@@ -1268,11 +1289,16 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   }
   pl.reg = register_on(c.reg);
   if (pl.reg) {
-    pl.rg = make_register(*c.reg);
+    pl.rg = make_register(*c.reg, c.rpl);
     if (c.reg->target_kind == MD_MEM_HOST && pl.rg.t > 0) {
       MD_TRY(grow(m, st, f->rtarget, (size_t)pl.rg.t * 12));
       pl.host_reg_target = c.reg->target;
       pl.rg.target = f->rtarget.p;
+      if (pl.rg.plane) {  // the normals are of the target's kind
+        MD_TRY(grow(m, st, f->rnormals, (size_t)pl.rg.t * 12));
+        pl.host_reg_normals = c.rpl->target_normals;
+        pl.rg.target_normals = f->rnormals.p;
+      }
     }
   }
   if (c.rnd) {
@@ -1361,7 +1387,7 @@ int plan_homes(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
       q.xyz_out = l.xyz;
       q.normals_out = l.normals;
     }
-    return grow(m, st, m->points->rtable, register_scratch_bytes(q.n, q.t));
+    return grow(m, st, m->points->rtable, q.plane ? register_plane_scratch_bytes(q.n, q.t) : register_scratch_bytes(q.n, q.t));
   };
   if (pl.reg && !(pl.mcut || pl.ccut)) MD_TRY(registers(pl.fin, false));
   if (!own_list) return MD_OK;
@@ -1450,6 +1476,8 @@ int stage_inputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
   }
   if (pl.host_reg_target)
     MD_HIP(hipMemcpyAsync(f->rtarget.p, pl.host_reg_target, (size_t)pl.rg.t * 12, hipMemcpyHostToDevice, pl.st));
+  if (pl.host_reg_normals)
+    MD_HIP(hipMemcpyAsync(f->rnormals.p, pl.host_reg_normals, (size_t)pl.rg.t * 12, hipMemcpyHostToDevice, pl.st));
   if (pl.host_target)  // the target has a kind of its own
     MD_HIP(hipMemcpyAsync(f->mtarget.p, pl.host_target, (size_t)pl.mn.t * 12, hipMemcpyHostToDevice, pl.st));
   if (c.in_kind != MD_MEM_HOST) return MD_OK;
@@ -1581,7 +1609,7 @@ int run_match(md_model_s* m, const PointsCall&, PointsPlan& pl) {
 // Registration: the list the matching reads -> reg's outputs; with apply the moved rows replace that list's in place.
 int run_register(md_model_s* m, const PointsCall&, PointsPlan& pl) {
   MD_TRY(launch_register_points(pl.rg, m->points->rtable.p, pl.st));
-  m->points->reg_rows = pl.rg.n; m->points->reg_target = pl.rg.t; m->points->reg_ran = true;  // only a launched run has flags to read (points_register_overflow)
+  m->points->reg_rows = pl.rg.n; m->points->reg_target = pl.rg.t; m->points->reg_plane = pl.rg.plane; m->points->reg_ran = true;  // only a launched run has flags to read (points_register_overflow)
   return MD_OK;
 }
 
@@ -1630,7 +1658,7 @@ int copy_outputs(md_model_s* m, const PointsCall& c, PointsPlan& pl) {
     if (pl.ccut) MD_TRY(d2h(&pl.cluster_rows, pl.cn.in_count + c.B, 4));
   }
   if (pl.reg) {
-    MD_TRY(d2h(&reg_overflow, register_flags(m->points->rtable.p, pl.rg.n, pl.rg.t), 4));
+    MD_TRY(d2h(&reg_overflow, pl.rg.plane ? register_plane_flags(m->points->rtable.p, pl.rg.n, pl.rg.t) : register_flags(m->points->rtable.p, pl.rg.n, pl.rg.t), 4));
     if (pl.mcut || pl.ccut) MD_TRY(d2h(&pl.register_rows, pl.rg.in_count + c.B, 4));
   }
   if (pl.mat) {
@@ -1740,6 +1768,7 @@ std::vector<uintptr_t> points_graph_key(md_model_t m, const PointsCall& c, hipSt
     key_add(key, q.init != nullptr, q.transform, q.pairs, q.sum_d2, q.stats, q.dropped, q.nearest, q.dist2);
     if (q.init)
       for (int i = 0; i < 12; ++i) key_add(key, q.init[i]);  // init travels by value: its values are part of the captured launches
+    if (register_plane_on(c.rpl)) key_add(key, 0x5245474eu, c.rpl->target_normals, c.rpl->sum_r2);
   }
   if (mesh_on(c.mesh))  // every output null: the call without a mesh
     key_add(key, 0x4d455348u, c.mesh->max_rtol, c.mesh->faces, c.mesh->face_count, c.mesh->face_capacity, c.mesh->pixel_index);
@@ -1862,6 +1891,7 @@ int infer_points(md_model_t m, const PointsCall& call, hipStream_t stream) {
     if (rows >= (1l << 30)) MD_FAIL(MD_ERR_SHAPE, "matching takes fewer than 2^30 rows, the list may have %ld", rows);
   }
   MD_TRY(check_register(c.reg, false));
+  MD_TRY(check_register_plane(c.reg, c.rpl));
   if (register_on(c.reg)) {
     if (!out->count) MD_FAIL(MD_ERR_INVALID_ARG, "registration needs the list's `count`");
     if (!out->xyz) MD_FAIL(MD_ERR_INVALID_ARG, "registration needs the list output `xyz`");

@@ -533,7 +533,8 @@ class DepthPro:
         reads onto the reference cloud `target` (as match='s), directly in front of match=; the transform, the histories, the
         counters, nearest and dist2 come back as `registration` (`PointRegistration`). apply=True: the moved rows (and normals)
         replace that list in place, so match= and clusters= see the aligned cloud; not with mesh=. radius 0 or None: the call
-        without it."""
+        without it. target_normals= [T,3] where `target` lies: the point-to-plane form through `md_infer_points_register_plane`
+        (min_pairs at least 6, status 3 a degenerate system, `registration.sum_r2`); without it the call is the one above."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.MdError(_lib.MD_ERR_SHAPE, f"expected [B,3,H,W], got {tuple(x.shape)}")
         dev = torch.device("cuda", self.device.ordinal)
@@ -547,7 +548,9 @@ class DepthPro:
             conf_percentile=conf_percentile, view_rtol=view_rtol, min_views=min_views, normals=normals, normal_min_cos=normal_min_cos,
             voxel=voxel, render=render, mesh=mesh, raster=raster, outlier=outlier, decimate=decimate, components=components,
             smooth=smooth, planes=planes, clusters=clusters, match=match, register=register, opts=opts)
-        if rq.reg is not None:
+        if rq.rpl is not None:
+            entry, parts = self._lib.md_infer_points_register_plane, rq.register_plane_args()
+        elif rq.reg is not None:
             entry, parts = self._lib.md_infer_points_register, rq.register_args()
         elif rq.mat is not None:
             entry, parts = self._lib.md_infer_points_match, rq.match_args()

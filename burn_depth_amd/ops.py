@@ -11,7 +11,7 @@ from . import _lib
 from .depth_pro import Device, _stream_ptr
 from .points import (FittedPlanes, PointCloud, PointRegistration, RasterisedMesh, RenderedPoints, SmoothedMesh, _cluster_mode_of, _clusters_struct, _f32, _i32, _lattice,
                      _match_mode_of, _match_struct, _new_clusters, _new_match, _new_registration, _plane_mode, _planes_struct, _points_cameras, _points_request, _ptr,
-                     _raster_request, _register_struct, _render_request, _u8, _view_filter_opts)
+                     _raster_request, _register_plane_struct, _register_struct, _render_request, _u8, _view_filter_opts)
 
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -859,15 +859,18 @@ def match_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius: f
     return out
 
 
-def register_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius: float, iterations: int = 10, init=None, min_pairs: int = 3,
-                    rot_eps: float = 0.0, trans_eps: float = 0.0, normals: Optional[torch.Tensor] = None, apply: bool = False,
-                    xyz_out: Optional[torch.Tensor] = None) -> PointRegistration:
+def register_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius: float, iterations: int = 10, init=None,
+                    min_pairs: Optional[int] = None, rot_eps: float = 0.0, trans_eps: float = 0.0, normals: Optional[torch.Tensor] = None, apply: bool = False,
+                    xyz_out: Optional[torch.Tensor] = None, target_normals: Optional[torch.Tensor] = None) -> PointRegistration:
     """md_op_register_points: rigid point-to-point ICP of the list xyz [N,3] onto the reference cloud target [T,3], both on the
     device, pairing within `radius` for `iterations` rounds from the transform `init` (twelve f64, R row-major then t, or a 3x4 /
     4x4 matrix; None: the identity) -> `PointRegistration`: transform f64 [12], the per-pass pairs / sum_d2 histories, stats,
     dropped, nearest / dist2 under the final transform. rot_eps / trans_eps > 0 stop the rounds once a solve changes R and t by no
     more than that. apply: also xyz, the moved rows, and (with normals=) the rotated normals; xyz_out: the tensor the moved rows
-    go to, which may be `xyz` itself. Bit-identical to `pipeline.register_points`."""
+    go to, which may be `xyz` itself. target_normals [T,3] on the device: the point-to-plane form (`md_op_register_points_plane`):
+    the residual of a pair is measured along its target normal, pairs with a normal that is not finite or all zero are left out,
+    min_pairs is at least 6 (the default then), status 3 is a degenerate system and `sum_r2` holds the squared residuals of every pass.
+    Bit-identical to `pipeline.register_points`."""
     xyz, _, _, _, normals, N, _ = _list_inputs(xyz, None, None, None, normals)
     target = target.to(device=xyz.device, dtype=torch.float32).contiguous().reshape(-1, 3)
     K = int(iterations)
@@ -881,10 +884,17 @@ def register_points(dev: Device, xyz: torch.Tensor, target: torch.Tensor, radius
     if (apply or xyz_out is not None) and normals is not None:
         res.normals = _f32(d, N, 3)
     keep: list = []
-    reg = _register_struct(dict(radius=radius, iterations=K, init=init, min_pairs=min_pairs, rot_eps=rot_eps, trans_eps=trans_eps), _p(target),
+    reg = _register_struct(dict(radius=radius, iterations=K, init=init, min_pairs=min_pairs, rot_eps=rot_eps, trans_eps=trans_eps,
+                                target_normals=target_normals), _p(target),
                            int(target.shape[0]), _lib.MD_MEM_DEVICE, res, keep)
-    _lib.check(_lib.load().md_op_register_points(dev.handle, _p(xyz), _p(normals), N, C.byref(reg), _p(res.xyz), _p(res.normals),
-                                                 _stream_ptr(dev.ordinal)))
+    if target_normals is None:
+        _lib.check(_lib.load().md_op_register_points(dev.handle, _p(xyz), _p(normals), N, C.byref(reg), _p(res.xyz), _p(res.normals),
+                                                     _stream_ptr(dev.ordinal)))
+        return res
+    target_normals = target_normals.to(device=xyz.device, dtype=torch.float32).contiguous().reshape(-1, 3)
+    plane = _register_plane_struct(d, target_normals, int(target.shape[0]), _lib.MD_MEM_DEVICE, res, keep)
+    _lib.check(_lib.load().md_op_register_points_plane(dev.handle, _p(xyz), _p(normals), N, C.byref(reg), C.byref(plane), _p(res.xyz),
+                                                       _p(res.normals), _stream_ptr(dev.ordinal)))
     return res
 
 

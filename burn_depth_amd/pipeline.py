@@ -1291,6 +1291,7 @@ class HostRegistration:
     dist2: np.ndarray                # f32 [N]
     xyz: np.ndarray                  # f32 [N,3]: the moved rows of the evaluation pass
     normals: Optional[np.ndarray]    # f32 [N,3]: the rotated normals
+    sum_r2: Optional[np.ndarray] = None  # f64 [K+1]: the sum of squared point-to-plane residuals; with target_normals only
 
 
 REG_SWEEPS = 8     # kRegSweeps of kernels/register_math.h
@@ -1298,9 +1299,9 @@ _REG_TILE = 4096   # tile_compact.h: item = tile * 4096 + step * 256 + thread
 
 
 def _reg_workgroup(v):
-    """The value of a 256-thread workgroup, v f64 [.., 256, 16] -> [.., 16]: the halving tree over the 64 lanes of every wave,
+    """The value of a 256-thread workgroup, v f64 [.., 256, L] -> [.., L]: the halving tree over the 64 lanes of every wave,
     then (W0 + W1) + (W2 + W3)."""
-    w = v.reshape(v.shape[:-2] + (4, 64, 16))
+    w = v.reshape(v.shape[:-2] + (4, 64, v.shape[-1]))
     h = 32
     while h >= 1:
         w = w[..., :h, :] + w[..., h:2 * h, :]
@@ -1310,19 +1311,19 @@ def _reg_workgroup(v):
 
 
 def _reg_sums(leaves):
-    """The sixteen sums of a pass in the contract's fixed shape. leaves f64 [tiles * 4096, 16] in item order, +0.0 where an item
-    has no pair."""
-    tiles = len(leaves) // _REG_TILE
-    v = leaves.reshape(tiles, 16, 256, 16)
-    acc = np.zeros((tiles, 256, 16), np.float64)
+    """The L sums of a pass in the contract's fixed shape (L = 16, or 29 in the point-to-plane form). leaves f64 [tiles * 4096, L]
+    in item order, +0.0 where an item has no pair."""
+    tiles, L = len(leaves) // _REG_TILE, leaves.shape[1]
+    v = leaves.reshape(tiles, 16, 256, L)
+    acc = np.zeros((tiles, 256, L), np.float64)
     for s in range(16):  # a thread's left fold over its steps
         acc = acc + v[:, s]
     tile = _reg_workgroup(acc)
     rounds = (tiles + 255) // 256
-    part = np.zeros((max(rounds, 1) * 256, 16), np.float64)
+    part = np.zeros((max(rounds, 1) * 256, L), np.float64)
     part[:tiles] = tile
-    part = part.reshape(-1, 256, 16)
-    acc = np.zeros((256, 16), np.float64)
+    part = part.reshape(-1, 256, L)
+    acc = np.zeros((256, L), np.float64)
     for r in range(len(part)):  # thread u folds the tiles u, u + 256, ..
         acc = acc + part[r]
     return _reg_workgroup(acc)
@@ -1351,6 +1352,72 @@ def _reg_rotate(a, v, p, q):
         vkp, vkq = v[k][p], v[k][q]
         v[k][p] = c * vkp - s * vkq
         v[k][q] = s * vkp + c * vkq
+
+
+def _reg_quat_matrix(w, x, y, z):
+    """reg_quat_matrix of kernels/register_math.h, line for line: the unit quaternion -> R row-major, a list of nine np.float64."""
+    ww, xx, yy, zz = w * w, x * x, y * y, z * z
+    xy, xz, yz, wx, wy, wz = x * y, x * z, y * z, w * x, w * y, w * z
+    two = np.float64(2.0)
+    return [((ww + xx) - yy) - zz, two * (xy - wz), two * (xz + wy),
+            two * (xy + wz), ((ww - xx) + yy) - zz, two * (yz - wx),
+            two * (xz - wy), two * (yz + wx), ((ww - xx) - yy) + zz]
+
+
+REG_PLANE_LEAVES = 29  # kRegPlaneLeaves of kernels/register_math.h
+
+
+def register_solve_plane(n, S, A_old):
+    """reg_solve_plane of kernels/register_math.h, line for line: the usable pair count n, the 29 sums S and the transform the
+    pass ran under -> the composed transform f64 [12], or None when the system is degenerate (a Cholesky pivot that is not > 0,
+    or a component of the solution that is not finite)."""
+    f = np.float64
+    S = [f(v) for v in S]
+    A_old = [f(v) for v in A_old]
+    with np.errstate(all="ignore"):
+        M = [[f(0.0)] * 6 for _ in range(6)]
+        L = [[f(0.0)] * 6 for _ in range(6)]
+        at = 0
+        for i in range(6):
+            for j in range(i, 6):
+                M[i][j] = M[j][i] = S[at]
+                at += 1
+        for j in range(6):
+            s = M[j][j]
+            for k in range(j):
+                s = s - L[j][k] * L[j][k]
+            if not s > 0.0:
+                return None
+            L[j][j] = np.sqrt(s)
+            for i in range(j + 1, 6):
+                v = M[i][j]
+                for k in range(j):
+                    v = v - L[i][k] * L[j][k]
+                L[i][j] = v / L[j][j]
+        x, y = [f(0.0)] * 6, [f(0.0)] * 6
+        for i in range(6):
+            v = S[21 + i]
+            for k in range(i):
+                v = v - L[i][k] * y[k]
+            y[i] = v / L[i][i]
+        for i in range(5, -1, -1):
+            v = y[i]
+            for k in range(i + 1, 6):
+                v = v - L[k][i] * x[k]
+            x[i] = v / L[i][i]
+        if not all(np.isfinite(v) for v in x):
+            return None
+        qx, qy, qz = f(0.5) * x[0], f(0.5) * x[1], f(0.5) * x[2]
+        ln = np.sqrt(((f(1.0) + qx * qx) + qy * qy) + qz * qz)
+        qw = f(1.0) / ln
+        qx, qy, qz = qx / ln, qy / ln, qz / ln
+        dR = _reg_quat_matrix(qw, qx, qy, qz)
+        A = [f(0.0)] * 12
+        for a in range(3):
+            for b in range(3):
+                A[3 * a + b] = (dR[3 * a] * A_old[b] + dR[3 * a + 1] * A_old[3 + b]) + dR[3 * a + 2] * A_old[6 + b]
+            A[9 + a] = ((dR[3 * a] * A_old[9] + dR[3 * a + 1] * A_old[10]) + dR[3 * a + 2] * A_old[11]) + x[3 + a]
+    return np.array(A, np.float64)
 
 
 def register_solve(n, S, sweeps=REG_SWEEPS):
@@ -1387,12 +1454,7 @@ def register_solve(n, S, sweeps=REG_SWEEPS):
         w, x, y, z = w / ln, x / ln, y / ln, z / ln
         if w < 0.0:
             w, x, y, z = -w, -x, -y, -z
-        ww, xx, yy, zz = w * w, x * x, y * y, z * z
-        xy, xz, yz, wx, wy, wz = x * y, x * z, y * z, w * x, w * y, w * z
-        two = f(2.0)
-        A = [((ww + xx) - yy) - zz, two * (xy - wz), two * (xz + wy),
-             two * (xy + wz), ((ww - xx) + yy) - zz, two * (yz - wx),
-             two * (xz - wy), two * (yz + wx), ((ww - xx) - yy) + zz]
+        A = _reg_quat_matrix(w, x, y, z)
         A += [qbar[a] - ((A[3 * a] * pbar[0] + A[3 * a + 1] * pbar[1]) + A[3 * a + 2] * pbar[2]) for a in range(3)]
     return np.array(A, np.float64)
 
@@ -1410,15 +1472,30 @@ def _reg_turn(A, v, shift):
     return out
 
 
-def register_points(xyz, target, radius, iterations=10, init=None, min_pairs=3, rot_eps=0.0, trans_eps=0.0, normals=None) -> HostRegistration:
+def register_points(xyz, target, radius, iterations=10, init=None, min_pairs=None, rot_eps=0.0, trans_eps=0.0, normals=None,
+                    target_normals=None) -> HostRegistration:
     """The host reference of md_op_register_points (include/mi_depth.h states the contract, kernels/register_math.h its arithmetic):
     rigid point-to-point ICP of xyz [N,3] onto target [T,3]. Every pass moves the rows under the running transform in f64 with one
     cast to f32, pairs them through `match_points`' grid and walk, and sums the sixteen leaves of every pair in the fixed tree of
     the tile layout; `register_solve` restates the Jacobi solve. init: twelve f64, R row-major then t (None: the identity). The
-    device kernels (kernels/register.hip) give the same bits."""
+    device kernels (kernels/register.hip) give the same bits. min_pairs: None is the smallest the form takes, 3, or 6 with
+    target_normals. target_normals [T,3]: the point-to-plane form of md_op_register_points_plane: the 29 leaves of every usable
+    pair (a target normal that is finite and not all zero) from the MOVED row, `register_solve_plane`, status 3 for a degenerate
+    system, `sum_r2`; pairs, sum_d2 and stats[3] then cover the usable pairs only."""
     p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
     q = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 3)
     N, T, K = len(p), len(q), int(iterations)
+    plane = target_normals is not None
+    if min_pairs is None:
+        min_pairs = 6 if plane else 3
+    if plane:
+        tn = np.ascontiguousarray(target_normals, dtype=np.float32).reshape(-1, 3)
+        if len(tn) != T:
+            raise ValueError("target_normals is [T,3]")
+        if min_pairs < 6:
+            raise ValueError("min_pairs is at least 6 in the point-to-plane form")
+        tn_ok = np.isfinite(tn).all(1) & (tn != 0).any(1)
+        tn64 = tn.astype(np.float64)
     rs = np.float32(radius)
     with np.errstate(all="ignore"):
         r2 = rs * rs
@@ -1445,6 +1522,28 @@ def register_points(xyz, target, radius, iterations=10, init=None, min_pairs=3, 
         found = best != np.uint64(0xFFFFFFFFFFFFFFFF)
         rows, j = src[found], (best[found] & np.uint64(0xFFFFFFFF)).astype(np.int64)
         d2 = (best[found] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        if plane:  # reg_add_plane_leaves, one rounded operation per step
+            use = tn_ok[j]
+            rows, j, d2 = rows[use], j[use], d2[use]
+            leaves = np.zeros((items, REG_PLANE_LEAVES), np.float64)
+            with np.errstate(all="ignore"):
+                m, n = moved[rows].astype(np.float64), tn64[j]
+                J = np.empty((len(rows), 6), np.float64)
+                J[:, 0] = m[:, 1] * n[:, 2] - m[:, 2] * n[:, 1]
+                J[:, 1] = m[:, 2] * n[:, 0] - m[:, 0] * n[:, 2]
+                J[:, 2] = m[:, 0] * n[:, 1] - m[:, 1] * n[:, 0]
+                J[:, 3:] = n
+                d = q64[j] - m
+                r = (d[:, 0] * n[:, 0] + d[:, 1] * n[:, 1]) + d[:, 2] * n[:, 2]
+                at = 0
+                for a in range(6):
+                    for b in range(a, 6):
+                        leaves[rows, at] = J[:, a] * J[:, b]
+                        at += 1
+                leaves[rows, 21:27] = J * r[:, None]
+                leaves[rows, 27] = r * r
+            leaves[rows, 28] = d2.astype(np.float64)
+            return moved, ok, src, best, found, len(rows), _reg_sums(leaves)
         leaves = np.zeros((items, 16), np.float64)
         leaves[rows, 0:3], leaves[rows, 3:6] = p64[rows], q64[j]
         leaves[rows, 6:15] = (p64[rows][:, :, None] * q64[j][:, None, :]).reshape(-1, 9)
@@ -1452,28 +1551,36 @@ def register_points(xyz, target, radius, iterations=10, init=None, min_pairs=3, 
         return moved, ok, src, best, found, len(rows), _reg_sums(leaves)
 
     pairs, sum_d2, stats = np.zeros(K + 1, np.int32), np.zeros(K + 1, np.float64), np.zeros(8, np.int32)
+    sum_r2 = np.zeros(K + 1, np.float64) if plane else None
     for k in range(K):
         if stats[1] != 0:
             break
         n, S = one_pass(A)[5:]
-        pairs[k], sum_d2[k] = n, S[15]
+        pairs[k], sum_d2[k] = n, S[28 if plane else 15]
+        if plane:
+            sum_r2[k] = S[27]
         if n < min_pairs:
             stats[1] = 2
             break
-        A_new = register_solve(n, S)
+        A_new = register_solve_plane(n, S, A) if plane else register_solve(n, S)
+        if A_new is None:
+            stats[1] = 3
+            break
         stats[0] += 1
         if (rot_eps > 0 or trans_eps > 0) and np.abs(A_new[:9] - A[:9]).max() <= rot_eps and np.abs(A_new[9:] - A[9:]).max() <= trans_eps:
             stats[1] = 1
         A = A_new
     moved, ok, src, best, found, n, S = one_pass(A)
-    pairs[K], sum_d2[K] = n, S[15]
+    pairs[K], sum_d2[K] = n, S[28 if plane else 15]
+    if plane:
+        sum_r2[K] = S[27]
     stats[2], stats[3], stats[4] = len(src), n, int(grid[0].sum())
     nearest = np.full(N, -2, np.int32)
     nearest[src] = np.where(found, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
     bits = np.full(N, 0x7F800000, np.uint32)
     bits[src] = np.where(found, (best >> np.uint64(32)).astype(np.uint32), np.uint32(0x7F800000))
     turned = None if normals is None else _reg_turn(A, np.ascontiguousarray(normals, dtype=np.float32).reshape(N, 3), False)
-    return HostRegistration(A, pairs, sum_d2, stats, int(N - ok.sum()), nearest, bits.view(np.float32), moved, turned)
+    return HostRegistration(A, pairs, sum_d2, stats, int(N - ok.sum()), nearest, bits.view(np.float32), moved, turned, sum_r2)
 
 
 def render_points(xyz, H, W, intrinsics=None, extrinsics=None, focal_px=None, rgb=None, count=None, *, pixel_offset=0.0, z_near=0.0,

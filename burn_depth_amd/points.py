@@ -99,7 +99,9 @@ class PointRegistration:
     pass; entry `iterations` is the evaluation pass under the final transform, skipped iterations are 0), stats int32 [8] (solves
     done, status 0 ran all / 1 converged / 2 too few pairs, in-range rows and pairs of the evaluation pass, target rows in the
     grid), dropped int32 [1], nearest int32 and dist2 f32 [N] (`PointMatch`'s, for the moved rows), xyz f32 [N,3] the moved rows
-    and normals f32 [N,3] the rotated normals (None when not asked for)."""
+    and normals f32 [N,3] the rotated normals (None when not asked for). With target_normals= (the point-to-plane form,
+    `md_points_register_plane`): pairs and sum_d2 cover the usable pairs only, status 3 is a degenerate system, and sum_r2 f64
+    [iterations + 1] holds the sum of squared point-to-plane residuals of every pass (None in the point-to-point form)."""
     transform: Optional[torch.Tensor] = None
     pairs: Optional[torch.Tensor] = None
     sum_d2: Optional[torch.Tensor] = None
@@ -109,6 +111,7 @@ class PointRegistration:
     dist2: Optional[torch.Tensor] = None
     xyz: Optional[torch.Tensor] = None
     normals: Optional[torch.Tensor] = None
+    sum_r2: Optional[torch.Tensor] = None
 
     def matrix(self) -> torch.Tensor:
         """The transform as a 4x4 f64 matrix on the host (synchronises)."""
@@ -567,7 +570,7 @@ def _points_match(dev, rows: int, match: dict, out: PointCloud, fresh: bool, kee
     return _match_struct(match, ptr, T, kind, out.match, out.index)
 
 
-_REGISTER_KEYWORDS = {"target", "radius", "iterations", "init", "min_pairs", "rot_eps", "trans_eps", "apply"}
+_REGISTER_KEYWORDS = {"target", "radius", "iterations", "init", "min_pairs", "rot_eps", "trans_eps", "apply", "target_normals"}
 
 
 def _register_init(init):
@@ -584,16 +587,35 @@ def _register_init(init):
     return (C.c_double * 12)(*[float(v) for v in m.reshape(12)])
 
 
+def _register_min_pairs(reg: dict) -> int:
+    """min_pairs= of a registration; not given: the smallest its form takes, 3, or 6 with target_normals=."""
+    given = reg.get("min_pairs")
+    return given if given is not None else (6 if reg.get("target_normals") is not None else 3)
+
+
 def _register_struct(reg: dict, target, target_rows: int, target_kind: int, found: "PointRegistration", keep: list) -> "_lib.MdPointsRegister":
     """md_points_register of the keywords radius=, iterations=, init=, min_pairs=, rot_eps=, trans_eps=, apply= writing into `found`.
     The ranges are the library's to refuse. The init array joins `keep`."""
     start = _register_init(reg.get("init"))
     keep.append(start)
     return _lib.MdPointsRegister(float(reg["radius"]), target, int(target_rows), int(target_kind), int(reg.get("iterations", 10)),
-                                 int(reg.get("min_pairs", 3)), int(bool(reg.get("apply", False))), float(reg.get("rot_eps", 0.0)),
+                                 int(_register_min_pairs(reg)), int(bool(reg.get("apply", False))), float(reg.get("rot_eps", 0.0)),
                                  float(reg.get("trans_eps", 0.0)), C.cast(start, C.c_void_p) if start is not None else None,
                                  _ptr(found.transform), _ptr(found.pairs), _ptr(found.sum_d2), _ptr(found.stats), _ptr(found.dropped),
                                  _ptr(found.nearest), _ptr(found.dist2))
+
+
+def _register_plane_struct(dev, normals, target_rows: int, target_kind: int, found: "PointRegistration", keep: list) -> "_lib.MdPointsRegisterPlane":
+    """md_points_register_plane of target_normals= [T,3], which is of the target's memory kind (a device tensor beside a device
+    target, a numpy array or a CPU tensor beside a host target), writing sum_r2 into `found` (created here when it has none). The
+    normals' keep-alive joins `keep`."""
+    ptr, T, kind, alive = _match_target(dev, normals)
+    if T != int(target_rows) or kind != int(target_kind):
+        raise _lib.MdError(_lib.MD_ERR_INVALID_ARG, "target_normals is [target rows, 3] and lies where target lies (device or host)")
+    keep.append(alive)
+    if found.sum_r2 is None:  # zeros: a target without rows has no normals to point at, and the library then writes none
+        found.sum_r2 = torch.zeros(int(found.pairs.shape[0]), dtype=torch.float64, device=dev)
+    return _lib.MdPointsRegisterPlane(ptr, _ptr(found.sum_r2))
 
 
 def _new_registration(dev, rows: int, iterations: int) -> "PointRegistration":
@@ -620,6 +642,13 @@ def _points_register(dev, rows: int, reg: dict, own_list: bool, out: PointCloud,
     ptr, T, kind, alive = _match_target(dev, reg["target"])
     keep.append(alive)
     return _register_struct(reg, ptr, T, kind, out.registration, keep)
+
+
+def _points_register_plane(dev, reg: dict, part: "_lib.MdPointsRegister", out: PointCloud, keep: list):
+    """md_points_register_plane for `out` behind `_points_register`'s `part`, or None without target_normals=."""
+    if reg.get("target_normals") is None:
+        return None
+    return _register_plane_struct(dev, reg["target_normals"], part.target_rows, part.target_kind, out.registration, keep)
 
 
 def _target_cameras(dev, intrinsics, extrinsics, focal_px):
@@ -677,6 +706,7 @@ class PointsRequest(NamedTuple):
     clu: Optional["_lib.MdPointsClusters"] = None  # `md_infer_points_clusters` takes it behind `planes_args()`
     mat: Optional["_lib.MdPointsMatch"] = None  # `md_infer_points_match` takes it behind `clusters_args()`
     reg: Optional["_lib.MdPointsRegister"] = None  # `md_infer_points_register` takes it behind `match_args()`
+    rpl: Optional["_lib.MdPointsRegisterPlane"] = None  # `md_infer_points_register_plane` takes it behind `register_args()`
 
     def args(self) -> list:
         """The struct arguments of `md_infer_points_smooth`, by reference, NULL for the parts not asked for."""
@@ -693,6 +723,10 @@ class PointsRequest(NamedTuple):
     def register_args(self) -> list:
         """The struct arguments of `md_infer_points_register`: those of `match_args()`, then the register part."""
         return self.match_args() + [C.byref(self.reg) if self.reg is not None else None]
+
+    def register_plane_args(self) -> list:
+        """The struct arguments of `md_infer_points_register_plane`: those of `register_args()`, then the plane part."""
+        return self.register_args() + [C.byref(self.rpl) if self.rpl is not None else None]
 
     def planes_args(self) -> list:
         """The struct arguments of `md_infer_points_planes`: those of `args()`, then the plane part."""
@@ -720,7 +754,7 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     o = _points_opts(**(opts or {}))
     res, outs = _points_outputs(dev, B, H, W, dense, compact, capacity, o.stride, want_rgb, want_conf, want_depth, out)
     cam, keep = _points_cameras(dev, B, intrinsics, extrinsics, focal_px)
-    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = mat = reg = None
+    fo = nrm = vox = rnd = msh = rst = outl = dec = comp = smo = pln = clu = mat = reg = rpl = None
     keep_rows = _cluster_mode(clusters) != 0  # the clustering writes the list: index is its own
     match_rows = _match_mode(match) != 0  # the matching writes the list, in front of the clustering
     cut = _plane_mode(planes) != 0 or match_rows or keep_rows  # a later stage writes the list: an earlier stage's index is not returned
@@ -785,10 +819,11 @@ def _points_request(dev, B: int, H: int, W: int, *, want_rgb: bool, want_conf: b
     if register and register.get("radius"):  # directly in front of the matching, on the list it reads
         keep = list(keep)
         reg = _points_register(dev, _lattice(B, H, W, o.stride)[1], register, match_rows or keep_rows, res, fresh, keep)
+        rpl = _points_register_plane(dev, register, reg, res, keep)
     elif register is not None:
         reg = _lib.MdPointsRegister()
     if clusters and clusters.get("radius"):
         clu = _points_clusters(dev, _lattice(B, H, W, o.stride)[1], clusters, res, fresh)
     elif clusters is not None:
         clu = _lib.MdPointsClusters()
-    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu, mat, reg)
+    return PointsRequest(res, cam, fo, o, outs, nrm, vox, rnd, msh, rst, outl, dec, comp, smo, keep, pln, clu, mat, reg, rpl)

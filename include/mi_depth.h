@@ -1301,6 +1301,59 @@ int md_infer_points_register(md_model_t m, const float* nchw, int B, int H, int 
                              const md_points_clusters* clu, const md_points_match* mat, const md_points_register* reg,
                              int out_kind, void* stream);
 
+/* ---- point path: point-to-plane ICP against the reference cloud's normals ----------------------------------------------------
+ * md_points_register_plane rides beside the unchanged md_points_register and switches its ICP to the point-to-plane metric
+ * (Chen & Medioni): the distance of a pair is measured along the target row's normal, so a surface may slide along itself.
+ * Transform, histories, stats, dropped, nearest, dist2, the moved rows, init, the stop test and the evaluation pass mean what
+ * md_points_register says; the arithmetic is held once in kernels/register_math.h (reg_add_plane_leaves, reg_solve_plane) and
+ * pipeline.register_points(target_normals=) restates it in numpy bit for bit. The differences:
+ *   pairing: unchanged. The row is moved in f64 and cast once to m; the nearest target row j within radius is md_points_match's;
+ *     nearest / dist2 report that pair whatever its normal.
+ *   usable pair: the three components of n = target_normals[j] are finite and not all zero (the point path writes (0,0,0) where
+ *     a pixel has no normal). Only usable pairs enter the sums; pairs[k], stats[3] and sum_d2[k] count or sum usable pairs only.
+ *   leaves per usable pair: 29 f64, from m, q = target[j] and n widened exactly, one rounded operation per step, contraction off:
+ *     c = m x n (c0 = m1*n2 - m2*n1, ..: exact products, the subtraction rounds once); d_a = (double)q_a - (double)m_a;
+ *     r = ((d0*n0 + d1*n1) + d2*n2); J = (c0, c1, c2, n0, n1, n2); leaves 0..20 the upper triangle of J J^T in row-major order
+ *     (J_i * J_j, i <= j), 21..26 J_i * r, 27 r * r, 28 (double)d2 of the pair. The sum tree is md_points_register's over 29
+ *     leaves; all leaves are finite, so nothing depends on the order of arrival.
+ *   the solve (reg_solve_plane; one thread, f64, only + - * /, sqrt and comparisons): the symmetric 6x6 M and b from the sums;
+ *     Cholesky in the order j = 0..5: s = M_jj - sum_{k<j} L_jk^2 as a left fold in ascending k, !(s > 0) -> degenerate,
+ *     L_jj = sqrt(s), L_ij = (M_ij - sum_k L_ik L_jk) / L_jj for i > j; forward then backward substitution for
+ *     x = (w0, w1, w2, t0, t1, t2); a component of x that is not finite -> degenerate. The increment's rotation dR is that of the
+ *     quaternion (1, w0/2, w1/2, w2/2), normalised by len = sqrt(((1 + x*x) + y*y) + z*z) and four divisions, through the
+ *     quaternion-to-matrix lines of reg_solve. R'_ab = (dR_a0*R_0b + dR_a1*R_1b) + dR_a2*R_2b;
+ *     t'_a = ((dR_a0*t_0 + dR_a1*t_1) + dR_a2*t_2) + tau_a.
+ *   iteration: n < min_pairs -> status 2 as before (n counts usable pairs; min_pairs >= 6). A degenerate system -> status 3: A
+ *     stays and every later iteration changes nothing (a target with one normal direction only, all rows paired with one target
+ *     row). The test is the exact !(s > 0): a deficiency that rounding hides is not detected, and nothing is damped. Otherwise
+ *     A_{k+1} is the composed transform, then the stop test.
+ *   sum_r2 f64 [K+1]: leaf 27 of the pass at entry k; 0 for skipped iterations. */
+typedef struct md_points_register_plane {
+  const float* target_normals; /* f32 [target_rows,3], of the memory kind of reg->target. NULL = the part is off: the call IS the
+                                * point-to-point entry on the same arguments, bit for bit, and sum_r2 is not written */
+  double* sum_r2;              /* f64 [iterations + 1]. NULL = skip */
+} md_points_register_plane;
+
+/* md_op_register_points in the point-to-plane form; plane NULL or plane->target_normals NULL: md_op_register_points on the same
+ * arguments, the same launches and bits. Launches: as the operator's, on the plane forms of the step and reduce kernels. Errors,
+ * before any launch: the operator's, plus target_normals with reg->target NULL and min_pairs < 6 -> MD_ERR_INVALID_ARG. */
+int md_op_register_points_plane(md_device_t dev, const float* xyz_dev, const float* normals_dev, int64_t N, const md_points_register* reg,
+                                const md_points_register_plane* plane, float* xyz_out, float* normals_out, void* stream);
+/* md_infer_points_register with `plane` behind `reg`: the widest entry. plane NULL or target_normals NULL: md_infer_points_register
+ * on the same arguments. The normals are of reg->target_kind: a host target's normals are copied into a grow-only buffer beside
+ * the target's with every call (such a call is not captured into a graph), device normals are read by address, so a graph replay
+ * sees their current contents. sum_r2 is of out_kind. The graph key contains both fields. Errors as md_infer_points_register's,
+ * plus, before any launch: target_normals while the registration is off (reg NULL, radius == 0) or its target NULL, and
+ * min_pairs < 6 -> MD_ERR_INVALID_ARG. */
+int md_infer_points_register_plane(md_model_t m, const float* nchw, int B, int H, int W, int in_kind, const uint8_t* rgb,
+                                   const md_points_cameras* cam, const md_view_filter_opts* fo /* NULL = no view filter */,
+                                   const md_points_opts* o, const md_points_outputs* out, const md_points_normals* nrm,
+                                   const md_points_voxel* vox, const md_points_render* rnd, const md_points_mesh* mesh,
+                                   const md_points_raster* rst, const md_points_outlier* outl, const md_points_decimate* dec,
+                                   const md_points_components* comp, const md_points_smooth* smooth, const md_points_planes* pln,
+                                   const md_points_clusters* clu, const md_points_match* mat, const md_points_register* reg,
+                                   const md_points_register_plane* plane, int out_kind, void* stream);
+
 /* ---- Depth-Anything-v3---------------------------------------------------------------------------------
  * "metric_large" = `DepthAnything3Config::metric_large()` (depth_anything3/mod.rs:153-156): ViT-L/14, 518x518,
  * hooks [4,11,17,23], mono head `DepthAnything3HeadConfig::metric_large` (dpt.rs:41-58).

@@ -66,7 +66,8 @@ the points of kept clusters (not with `--mesh`, nor behind `--plane-mode label`)
 the cloud onto the points of REF.ply, in front of the match step; prints the 4x4 transform, the solves, the pairs and the RMS distance of
 the first and the last pass. `--register-apply` writes the aligned cloud, and `--match-ply` / `--cluster-radius` then see it (not with
 `--mesh`). One image: the stage of the model call (`md_infer_points_register`); with `--views` or `--mesh`, `ops.register_points` on the
-final points.
+final points. `--register-metric plane` measures every pair along the normal of its reference point (point-to-plane ICP; REF.ply must hold
+nx ny nz, as `--normals` writes them) and also prints the status and the RMS point-to-plane residual of the first and the last pass.
 `--match-ply REF.ply --match-radius R [--match-tol T ...] [--match-mode label|matched|unmatched]` (with `--ply`): the nearest point of the
 reference cloud REF.ply within R for every point of the cloud, on the device, behind `--planes` and in front of `--cluster-radius`, so
 `--planes P --plane-mode drop --match-ply REF.ply --match-radius R --match-mode unmatched --cluster-radius C` drops the floor and what the
@@ -182,6 +183,10 @@ def register_request(a, dev) -> dict:
     """the register= keywords of --register-ply: the reference cloud goes to the device once"""
     import torch
     from burn_depth_amd import pipeline as P
+    if a.register_metric == "plane":  # the normals of the file, which main() has seen to be there
+        ref, _, nrm = P.read_ply_normals(a.register_ply)
+        return dict(target=torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)).to(dev), radius=a.register_radius,
+                    iterations=a.register_iterations, target_normals=torch.from_numpy(np.ascontiguousarray(nrm, dtype=np.float32)).to(dev))
     ref = np.ascontiguousarray(P.read_ply(a.register_ply)[0], dtype=np.float32)
     return dict(target=torch.from_numpy(ref).to(dev), radius=a.register_radius, iterations=a.register_iterations)
 
@@ -193,9 +198,13 @@ def print_registration(found) -> None:
     for row in found.matrix().tolist():
         print("  " + " ".join(f"{v:+.9e}" for v in row))
     rms = lambda k: (sums[k] / pairs[k]) ** 0.5 if pairs[k] else float("nan")  # noqa: E731
-    state = {0: "ran every round", 1: "converged", 2: "too few pairs"}[stats[1]]
+    state = {0: "ran every round", 1: "converged", 2: "too few pairs", 3: "degenerate system"}[stats[1]]
     print(f"Registration: {stats[0]} solves ({state}), {pairs[0]} -> {pairs[-1]} pairs, RMS distance {rms(0):.6g} -> {rms(-1):.6g}, "
           f"{stats[4]} reference points in the grid")
+    if found.sum_r2 is not None:  # --register-metric plane: the pairs above are the usable ones
+        r2 = found.sum_r2.cpu().tolist()
+        res = lambda k: (r2[k] / pairs[k]) ** 0.5 if pairs[k] else float("nan")  # noqa: E731
+        print(f"Registration (plane): status {stats[1]}, RMS point-to-plane residual {res(0):.6g} -> {res(-1):.6g}")
 
 
 def print_match(found, a, rows: int) -> None:
@@ -459,6 +468,8 @@ def main(argv=None) -> int:
                     "(md_infer_points_register, ops.register_points); prints the 4x4 transform")
     ap.add_argument("--register-radius", type=float, default=0.0, help="--register-ply: the pairing radius, > 0")
     ap.add_argument("--register-iterations", type=int, default=10, help="--register-ply: the rounds, 1..64")
+    ap.add_argument("--register-metric", choices=["point", "plane"], default="point", help="--register-ply: plane measures a pair along the normal of its "
+                    "reference point (nx ny nz of REF.ply, which must hold them; md_infer_points_register_plane)")
     ap.add_argument("--register-apply", action="store_true", help="--register-ply: write the aligned cloud; the match and cluster steps see it (not with --mesh)")
     ap.add_argument("--plane-up", type=float, nargs=3, metavar=("X", "Y", "Z"), help="--planes: only planes whose normal lies within --plane-up-cos of this axis")
     ap.add_argument("--plane-up-cos", type=float, default=0.9, help="--plane-up: the smallest |cosine| between a plane's normal and the axis")
@@ -497,6 +508,11 @@ def main(argv=None) -> int:
     if a.register_apply and not a.register_ply:
         print("--register-apply goes with --register-ply", file=sys.stderr)
         return 2
+    if a.register_metric == "plane":
+        from burn_depth_amd import pipeline as P
+        if not a.register_ply or (os.path.exists(a.register_ply) and P.read_ply_normals(a.register_ply)[2] is None):
+            print("--register-metric plane goes with --register-ply REF.ply, and REF.ply holds the normals nx ny nz", file=sys.stderr)
+            return 2
     if a.planes != 0 and (not 1 <= a.planes <= 8 or not a.ply or (a.mesh and a.plane_mode != "label")):
         print("--planes is a plane count in 1..8 and goes with --ply; --plane-mode drop / keep not with --mesh (the faces name the rows)", file=sys.stderr)
         return 2

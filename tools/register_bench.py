@@ -9,6 +9,11 @@ bit-equal.
 
   python tools/register_bench.py [--steps 10] [--warmup 2] [--case da3_3x518] [--no-host] [--out profiles/register_bench.json]
 
+--metric plane (written to profiles/register_plane_bench.json): the point-to-plane form on the same lists,
+radii and K against the perturbed target with that target's own normals (the list's normals under the target's rotation), and the
+point-to-point call measured in the same run as the yardstick: milliseconds per call of both, their ratio, and the pairs and the RMS
+distance of the first and the evaluation pass of both metrics.
+
 A kernel trace of one list wraps a --trace-config run:
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/register_bench.py --case da3_3x518 --trace-config R --out \"\""""
 import argparse
@@ -29,6 +34,75 @@ from voxel_bench import _da3_scene, _noise_scene, _time  # noqa: E402
 K = 10
 
 
+def _da3_scene_normals(dev, V=3, S=518):
+    """voxel_bench's DA3 list with its normals"""
+    import torch
+    from burn_depth_amd import weights as Wt
+    from burn_depth_amd.config import DepthAnything3Config, Precision
+    from burn_depth_amd.depth_anything3 import DepthAnything3
+    cfg = DepthAnything3Config.small()
+    cfg.precision, cfg.max_batch = Precision.BF16, V
+    m = DepthAnything3.new(dev, cfg, seed=0, init_scheme=Wt.INIT_PARITY)
+    try:
+        x = ((torch.rand(V, 3, S, S, generator=torch.Generator().manual_seed(0)) - 0.45) / 0.225).cuda()
+        pc = m.infer_points(x, dense=False, world=True, normals=True)
+        n = int(pc.count[-1])
+        return pc.xyz[:n].clone(), pc.normals[:n].clone()
+    finally:
+        m.destroy()
+
+
+def _noise_scene_normals(dev, B=8, S=1536):
+    """voxel_bench's noise list with its normals"""
+    import torch
+    from burn_depth_amd import ops
+    rng = np.random.default_rng(7)
+    d = torch.from_numpy(np.exp(rng.normal(0.5, 0.6, (B, S, S))).astype(np.float32)).cuda()
+    c = torch.from_numpy((1 + 2 * rng.random((B, S, S))).astype(np.float32)).cuda()
+    f = torch.full((B,), 0.9 * S, device="cuda")
+    E = np.zeros((B, 3, 4), np.float32)
+    for b in range(B):
+        a = np.radians(5.0 * b)
+        E[b, :, :3] = [[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]
+        E[b, :, 3] = [0.5 * b, 0, 0]
+    pc = ops.unproject(dev, d, focal_px=f, extrinsics=torch.from_numpy(E).cuda(), conf=c, dense=False, world=True, depth_min=0.5, depth_max=6.0,
+                       conf_min=1.8, normals=True)
+    n = int(pc.count[-1])
+    return pc.xyz[:n].clone(), pc.normals[:n].clone()
+
+
+def _plane_rows(a, torch, ops, dev, res):
+    """--metric plane: both metrics on every list and radius, in one run"""
+    for name, make in (("da3_3x518", _da3_scene_normals), ("8x1536", _noise_scene_normals)):
+        if a.case and a.case != name:
+            continue
+        xyz, nrm = make(dev)
+        fin = xyz[torch.isfinite(xyz).all(1)]
+        extent = float((fin.max(0).values - fin.min(0).values).max())
+        target = _moved(torch, xyz, extent)
+        c, s = float(np.cos(ANGLE)), float(np.sin(ANGLE))
+        rot = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float32, device=xyz.device)
+        tn = (nrm @ rot.T).contiguous()
+        row = {"rows": int(xyz.shape[0]), "target_rows": int(target.shape[0]), "target_rows_with_a_normal": int((tn != 0).any(1).sum())}
+        for share in SHARES:
+            radius = _radius_for_share(ops, dev, xyz, target, share, extent)
+            r = {"radius": radius}
+            for metric, kw in (("point", {}), ("plane", {"target_normals": tn})):
+                out = ops.register_points(dev, xyz, target, radius, iterations=K, min_pairs=6, **kw)
+                ms = _time(lambda: ops.register_points(dev, xyz, target, radius, iterations=K, min_pairs=6, **kw), a.steps, a.warmup)
+                pairs = out.pairs.cpu().numpy()
+                rms = lambda t: [float(np.sqrt(t[k].item() / max(int(pairs[k]), 1))) for k in (0, K)]  # noqa: E731
+                r[metric] = {"call_ms": round(ms, 3), "stats": out.stats.cpu().tolist(), "pairs": pairs.tolist(), "rms_first_last": rms(out.sum_d2)}
+                if metric == "plane":
+                    r[metric]["rms_residual_first_last"] = rms(out.sum_r2)
+                del out
+            r["ratio_plane_to_point"] = round(r["plane"]["call_ms"] / r["point"]["call_ms"], 3)
+            row[f"share{share}"] = r
+            print(json.dumps({name: {f"share{share}": r}}), flush=True)
+        res[name] = row
+        del xyz, nrm, fin, target, tn
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -36,15 +110,21 @@ def main(argv=None) -> int:
     ap.add_argument("--case", choices=["8x1536", "da3_3x518"], default="", help="measure this list only")
     ap.add_argument("--trace-config", type=float, default=0.0, metavar="R", help="only radius R, no yardstick and no host route: the run a kernel trace wraps")
     ap.add_argument("--no-host", action="store_true", help="skip the host route")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "register_bench.json"))
+    ap.add_argument("--metric", choices=["point", "plane"], default="point", help="plane: the point-to-plane form beside the point-to-point call")
+    ap.add_argument("--out", default=None, help="default: profiles/register_bench.json, or profiles/register_plane_bench.json with --metric plane")
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "register_plane_bench.json" if a.metric == "plane" else "register_bench.json")
     import torch
     from burn_depth_amd import ops, pipeline as P
     from burn_depth_amd.depth_pro import Device
     dev = Device(0)
     res = {"steps": a.steps, "warmup": a.warmup, "angle": ANGLE, "shift": SHIFT, "iterations": K}
+    if a.metric == "plane":
+        res["metric"] = "plane"
+        _plane_rows(a, torch, ops, dev, res)
     for name, make in (("da3_3x518", _da3_scene), ("8x1536", _noise_scene)):
-        if a.case and a.case != name:
+        if a.metric == "plane" or (a.case and a.case != name):
             continue
         xyz, _ = make(dev)
         n = int(xyz.shape[0])
